@@ -187,6 +187,57 @@ def run_lba(args, info, windows):
     return dict(windows=windows, results=results, elapsed=elapsed, elapsed_local=elapsed_local, upload_s=upload_s, prof=prof, alg=alg, alg_impl=alg_impl, plan=plan)
 
 
+DUMP_BYTES = 48 << 20   # --dump-outputs stays under 64 MB: every pose, a fixed sample of landmarks and edges
+
+
+def dump_lba_outputs(out_dir, windows, results, rank=0):
+    """What the timed osh_lba_optimize() of the last step returned (osh_lba_download), as float64 .npy files under out_dir.
+    Every window's optimised poses and LM scalars / traces; landmarks and per-edge outputs through a fixed sample of rows
+    (seeded by the window index, the same rows in every run) sized so the whole dump stays under DUMP_BYTES.  Every value is
+    finite: traces are zero past a window's length (lba_trace_length), sample rows past a small window's size are zero with
+    row index -1."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n = len(results)
+    per_window = DUMP_BYTES // max(n, 1) - max((r.pose_qt.nbytes for r in results), default=0) - 1024
+    k_pts = max(1, min(1024, per_window // 2 // 32))    # 3 coords + the row index, 8 bytes each
+    k_edges = max(1, min(2048, per_window // 2 // 24))  # chi2, depth flag, row index
+    n_trace = max((len(r.chi2_trace) for r in results), default=0)
+    arrays = {
+        "lba_status": np.array([r.status for r in results], dtype=np.float64),
+        "lba_iterations": np.array([r.iterations for r in results], dtype=np.float64),
+        "lba_trials": np.array([r.trials for r in results], dtype=np.float64),
+        "lba_chi2_initial": np.array([r.chi2_initial for r in results], dtype=np.float64),
+        "lba_trace_length": np.array([len(r.chi2_trace) for r in results], dtype=np.float64),
+        "lba_pose_qt": np.stack([r.pose_qt for r in results]) if n else np.zeros((0, 0, 7)),
+    }
+    for name in ("chi2_trace", "lambda_trace", "trials_trace"):   # zero past a window's trace length
+        a = np.zeros((n, n_trace))
+        for i, r in enumerate(results):
+            a[i, :len(getattr(r, name))] = getattr(r, name)
+        arrays["lba_" + name] = a
+    pts_idx, pts, e_idx, chi2, depth = [], [], [], [], []
+    for i, (w, r) in enumerate(zip(windows, results)):
+        rng = np.random.default_rng(1000 + i)
+        ip = np.sort(rng.choice(w.n_points, min(k_pts, w.n_points), replace=False))
+        ie = np.sort(rng.choice(w.n_edges, min(k_edges, w.n_edges), replace=False))
+        pts_idx.append(np.pad(ip.astype(np.float64), (0, k_pts - len(ip)), constant_values=-1))
+        pts.append(np.pad(r.points[ip], ((0, k_pts - len(ip)), (0, 0))))
+        e_idx.append(np.pad(ie.astype(np.float64), (0, k_edges - len(ie)), constant_values=-1))
+        chi2.append(np.pad(r.edge_chi2[ie], (0, k_edges - len(ie))))
+        depth.append(np.pad(r.edge_depth_pos[ie].astype(np.float64), (0, k_edges - len(ie))))
+    arrays.update(lba_points_sample_index=np.array(pts_idx).reshape(n, k_pts), lba_points_sample=np.array(pts).reshape(n, k_pts, 3),
+                  lba_edge_sample_index=np.array(e_idx).reshape(n, k_edges), lba_edge_chi2_sample=np.array(chi2).reshape(n, k_edges),
+                  lba_edge_depth_pos_sample=np.array(depth).reshape(n, k_edges))
+    assert all(np.isfinite(a).all() for a in arrays.values()), "--dump-outputs: a non-finite output"
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes, over 64 MB"
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}{suffix}.npy", np.ascontiguousarray(a, dtype=np.float64))
+    return dict(dir=str(out_dir), files=len(arrays), bytes=int(total), windows=n, points_per_window=k_pts, edges_per_window=k_edges)
+
+
 def run_batch_sweep(args, info, windows):
     """windows/s against the batch size B in {1, 8, 64, 256}: the HBM-resident optimize() and the whole
     osh_lba_solve (upload + optimize + download) of one context, one batch at a time; B = 1 is the live-SLAM call pattern
@@ -617,6 +668,8 @@ def main():
     ap.add_argument("--e2e-batches", type=int, default=6, help="batches per solver context in the end-to-end (upload + optimize + download) run; 0 = skip")
     ap.add_argument("--stub-solver", action="store_true", help="CPU rehearsal of the rank plumbing (gloo): no GPU work, the "
                     "timed step is a fixed sleep; the JSON line is marked \"stub\" and is not a measurement")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (every window's poses and "
+                    "LM trace, a fixed sample of landmarks and edges) as DIR/<name>.npy, float64, under 64 MB in all")
     args = ap.parse_args()
 
     if osh_launch.needs_spawn(args.gpus):
@@ -639,6 +692,7 @@ def main():
     torch.cuda.set_device(info.local_rank)
 
     lba_out = run_lba(args, info, windows)
+    dump_out = dump_lba_outputs(args.dump_outputs, lba_out["windows"], lba_out["results"], info.rank) if args.dump_outputs else None
     e2e_out = run_end_to_end(args, info, windows) if args.e2e_batches > 0 else None
     sweep_out = run_batch_sweep(args, info, windows) if (info.rank == 0 and not args.no_sweeps) else None
     orb_sweep_out = run_orb_sweep(args, info) if (info.rank == 0 and not args.no_sweeps and not args.no_orb) else None
@@ -716,6 +770,8 @@ def main():
         "upload_s_per_batch": lba_out["upload_s"],
         "ranks_seen": ranks_seen, "windows_per_s_by_rank": per_rank,
     }
+    if dump_out is not None:
+        out["dump_outputs"] = dump_out
     if sweep_out:
         out["config2_batch_sweep"] = sweep_out
         if "1" in sweep_out:
