@@ -1,6 +1,6 @@
 /* ImuTypes.h -- IMU::Bias / Calib / Preintegrated as used by Optimizer::LocalInertialBA and EdgeInertial
  * (reference include/ImuTypes.h:43-230, src/ImuTypes.cc:147-309,398-410).  All arithmetic is float32, as in the
- * reference.  Own implementation in csrc/host/ImuTypes.cc (no Eigen): Eigen::JacobiSVD's U V^T is computed as the
+ * reference.  Own implementation in csrc/hosttest/ImuTypes.cc (no Eigen): Eigen::JacobiSVD's U V^T is computed as the
  * orthogonal polar factor. */
 #ifndef IMUTYPES_H
 #define IMUTYPES_H

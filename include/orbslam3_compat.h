@@ -1,7 +1,8 @@
 /*
  * orbslam3_compat.h -- tiny stand-ins for the third-party types that appear in the signatures
  * of the hot path's interface (Eigen::Vector3f/Quaternionf, Sophus::SE3f, cv::KeyPoint, cv::Mat),
- * so that the host layer of THIS repository compiles in an image without Eigen/Sophus/OpenCV.
+ * so that the host layer of THIS repository (csrc/host/ with the stand-in bodies of csrc/hosttest/, built
+ * into the test-only liborbslam3_hip_hosttest.so) compiles in an image without Eigen/Sophus/OpenCV.
  *
  * They expose only the members the local-BA / matcher boundary touches.  Inside a
  * real ORB-SLAM3 tree define ORBSLAM3_HIP_USE_REAL_HEADERS and the genuine headers are used

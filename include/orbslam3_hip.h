@@ -10,7 +10,9 @@
  *     ORB_SLAM3::ORBmatcher::SearchByProjection     include/ORBmatcher.h:45-60 (src/ORBmatcher.cc:43,1676,1889)
  *     ORB_SLAM3::ORBmatcher::DescriptorDistance     include/ORBmatcher.h:42  (src/ORBmatcher.cc:2058-2074)
  * walks the KeyFrame/MapPoint graph, packs it into the flat arrays below and
- * calls these entry points.  Citations are relative to /root/reference.
+ * calls these entry points.  liborbslam3_hip.so exports exactly the functions
+ * declared here; the host layer is compiled into the integrator's own library
+ * (INTEGRATION.md).  Citations are relative to the reference ORB-SLAM3 tree.
  *
  * What each entry point replaces in the reference:
  *   osh_lba_*      g2o::SparseOptimizer::initializeOptimization + optimize(10)

@@ -1,5 +1,6 @@
 /*
- * orbslam3_hip_host.h -- C entry points of the C++ host layer (csrc/host/), for tests and bindings.
+ * orbslam3_hip_host.h -- C entry points of the C++ host layer (csrc/host/), for tests and bindings.  Defined in
+ * csrc/hosttest/harness.cc and exported by the test-only liborbslam3_hip_hosttest.so, not by liborbslam3_hip.so.
  *
  * The drop-in itself is C++: ORB_SLAM3::Optimizer::LocalBundleAdjustment (include/Optimizer.h) and
  * ORB_SLAM3::ORBmatcher::SearchByProjection (include/ORBmatcher.h), same signatures as the reference.
@@ -209,7 +210,7 @@ int osh_host_fuse_sim3(osh_host_frame* f, const float scw[8], int32_t n_mp, cons
  * returns the inlier count, the optimised pose and mvbOutlier (keypoints without a match keep the value 1 they are preset to). */
 int osh_host_frame_pose_optimization(osh_host_frame* f, int32_t n_mp, const float* mp_pos, const int32_t* kp_mp,
                                      const float* inv_level_sigma2, int32_t n_levels, float pose_out[7], uint8_t* outlier_out);
-/* ---- Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame on a test frame (csrc/host/harness.cc) */
+/* ---- Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame on a test frame (csrc/hosttest/harness.cc) */
 typedef struct osh_host_posei osh_host_posei;
 osh_host_posei* osh_host_posei_create(int32_t mode, int32_t n_kp, const float* kp_xy, const int32_t* octave, const float* uright,
                                       int32_t n_left, const float pose_qt[7], const float cam5[5], const float* kb8,

@@ -2,7 +2,8 @@
 
 The product path has NO CPU fallback: if the gfx950 library is missing or fails
 to load, :func:`load_library` raises.  (The CPU oracle under ``oracle/`` is test
-infrastructure and is never imported from here.)
+infrastructure and is never imported from here.)  :func:`load_host_library`
+loads the test-only library of the C++ host layer (include/orbslam3_hip_host.h).
 """
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ import numpy as np
 PKG_DIR = Path(__file__).resolve().parent
 REPO_ROOT = PKG_DIR.parent
 LIB_PATH = PKG_DIR / "csrc" / "liborbslam3_hip.so"
+HOST_LIB_PATH = PKG_DIR / "csrc" / "liborbslam3_hip_hosttest.so"
 
 OSH_OK = 0
 OSH_ERR_INVALID = -1
@@ -339,6 +341,21 @@ _HOST_SIGNATURES = {
 HOST_EXPORTED_SYMBOLS = tuple(_HOST_SIGNATURES)
 
 _lib = None
+_host_lib = None
+
+
+def _open(p: Path, signatures: dict) -> C.CDLL:
+    if not p.exists():
+        raise RuntimeError(
+            f"{p} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(there is no CPU fallback for the product path)."
+        )
+    lib = C.CDLL(str(p))
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    return lib
 
 
 def load_library(path: os.PathLike | None = None) -> C.CDLL:
@@ -347,20 +364,22 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if _lib is not None and path is None:
         return _lib
     # ORBSLAM3_HIP_LIB: developer aid for A/B runs of an alternative build of the same library
-    p = Path(path) if path else Path(os.environ.get("ORBSLAM3_HIP_LIB", LIB_PATH))
-    if not p.exists():
-        raise RuntimeError(
-            f"{p} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(there is no CPU fallback for the product path)."
-        )
-    lib = C.CDLL(str(p))
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_HOST_SIGNATURES.items()):
-        fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
-        fn.restype = res
-        fn.argtypes = args
+    lib = _open(Path(path) if path else Path(os.environ.get("ORBSLAM3_HIP_LIB", LIB_PATH)), _SIGNATURES)
     if path is None:
         _lib = lib
     return lib
+
+
+def load_host_library() -> C.CDLL:
+    """Load liborbslam3_hip_hosttest.so (the C++ host layer and its test wrappers); raise if absent.
+
+    The kernel library is loaded first: it carries the soname the host library depends on, so an ORBSLAM3_HIP_LIB
+    override also serves the host library and the process holds one copy of it (one osh_last_error text)."""
+    global _host_lib
+    if _host_lib is None:
+        load_library()
+        _host_lib = _open(HOST_LIB_PATH, _HOST_SIGNATURES)
+    return _host_lib
 
 
 def last_error(lib=None) -> str:

@@ -1375,8 +1375,8 @@ __global__ __launch_bounds__(256) void k_widen_rec(const float4* src, double* ds
 struct osh_lba_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  void* attach[4] = {nullptr, nullptr, nullptr, nullptr};
-  void (*attach_free[4])(void*) = {nullptr, nullptr, nullptr, nullptr};
+  void* attach[kAttachCount] = {};
+  void (*attach_free[kAttachCount])(void*) = {};
   KernelTimer timer;
   // host-side batch description
   int n_windows = 0;
@@ -1419,8 +1419,6 @@ static int launch_check(const char* what) {
   return OSH_OK;
 }
 
-#define OSH_TRY(expr) do { int _rc = (expr); if (_rc != OSH_OK) return _rc; } while (0)
-
 extern "C" int osh_lba_create(int device, osh_lba_ctx** out) {
   if (!out) { set_error("osh_lba_create: out is NULL"); return OSH_ERR_INVALID; }
   int n = 0;
@@ -1435,17 +1433,16 @@ extern "C" int osh_lba_create(int device, osh_lba_ctx** out) {
   return OSH_OK;
 }
 
-// used by liba_device.hip / pose_device.hip: those paths share the context's device and stream
-extern "C" int osh_lba_stream(osh_lba_ctx* c, int* device, hipStream_t* stream) {
+int osh::lba_stream(osh_lba_ctx* c, int* device, hipStream_t* stream) {
   if (!c) { set_error("null context"); return OSH_ERR_INVALID; }
   *device = c->device; *stream = c->stream;
   return OSH_OK;
 }
 
-// State another translation unit keeps with the context (liba_device.hip: its staging and work buffers): created on first use,
-// released by osh_lba_destroy -- not by a thread_local destructor at process exit, when the HIP runtime may already be gone.
-extern "C" void** osh_lba_attachment(osh_lba_ctx* c, int slot, void (*free_fn)(void*)) {
-  if (!c || slot < 0 || slot >= 4) return nullptr;
+// Attachments are created on first use and released by osh_lba_destroy -- not by a thread_local destructor at process exit,
+// when the HIP runtime may already be gone.
+void** osh::lba_attachment(osh_lba_ctx* c, LbaAttachSlot slot, void (*free_fn)(void*)) {
+  if (!c || slot < 0 || slot >= kAttachCount) return nullptr;
   c->attach_free[slot] = free_fn;
   return &c->attach[slot];
 }
@@ -1454,7 +1451,7 @@ extern "C" void osh_lba_destroy(osh_lba_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (int k = 0; k < 4; ++k) if (c->attach[k] && c->attach_free[k]) { c->attach_free[k](c->attach[k]); c->attach[k] = nullptr; }
+  for (int k = 0; k < kAttachCount; ++k) if (c->attach[k] && c->attach_free[k]) { c->attach_free[k](c->attach[k]); c->attach[k] = nullptr; }
   c->timer.destroy();
   c->dpack.release_events();
   if (c->h_nactive) (void)hipHostFree(c->h_nactive);

@@ -1316,16 +1316,11 @@ thread_local int g_liba_last_group = 0;
 thread_local long long g_liba_last_prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 }  // namespace
 
-#define OSH_TRY(expr) do { int _rc = (expr); if (_rc != OSH_OK) return _rc; } while (0)
-
-extern "C" int osh_lba_stream(osh_lba_ctx* ctx, int* device, hipStream_t* stream);   // lba_device.hip
-extern "C" void** osh_lba_attachment(osh_lba_ctx* ctx, int slot, void (*free_fn)(void*));   // lba_device.hip
-
 extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_problem* pr, osh_liba_result* res) {
   if (!ctx || nw <= 0 || !pr || !res) { set_error("osh_liba_solve: bad arguments"); return OSH_ERR_INVALID; }
   int device = 0;
   hipStream_t s = nullptr;
-  OSH_TRY(osh_lba_stream(ctx, &device, &s));
+  OSH_TRY(lba_stream(ctx, &device, &s));
   OSH_HIP(hipSetDevice(device));
   std::vector<LibaDesc> h_desc(nw);
   size_t K = 0, NV = 0, L = 0, E = 0, NL = 0, Htot = 0, btot = 0, LO = 0, PO = 0, EF = 0, LP = 0;
@@ -1430,7 +1425,7 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
   // ---- pack: every input array goes into ONE pinned staging buffer and travels in ONE copy (an upload per array cost more than
   // the optimisation of a single window); the device pointers are offsets into the arena.
   // staging and work buffers live with the context (one solver at a time per context, as for the visual path)
-  void** slot = osh_lba_attachment(ctx, 0, [](void* q) { delete static_cast<LibaBuffers*>(q); });
+  void** slot = lba_attachment(ctx, kAttachLiba, [](void* q) { delete static_cast<LibaBuffers*>(q); });
   if (!slot) { set_error("osh_liba_solve: no context"); return OSH_ERR_INVALID; }
   if (!*slot) *slot = new LibaBuffers();
   LibaBuffers& B = *static_cast<LibaBuffers*>(*slot);

@@ -567,8 +567,6 @@ struct osh_orb_ctx {
   bool uploaded = false, matched = false, windowed = false, grid = false;
 };
 
-#define OSH_TRY(expr) do { int _rc = (expr); if (_rc != OSH_OK) return _rc; } while (0)
-
 extern "C" int osh_orb_create(int device, osh_orb_ctx** out) {
   if (!out) { set_error("osh_orb_create: out is NULL"); return OSH_ERR_INVALID; }
   int n = 0;

@@ -360,16 +360,11 @@ struct PoseBuffers { PosePinned h_in, h_out; DevBuf arena; };
 
 using namespace osh;
 
-#define OSH_TRY(expr) do { int _rc = (expr); if (_rc != OSH_OK) return _rc; } while (0)
-
-extern "C" int osh_lba_stream(osh_lba_ctx* ctx, int* device, hipStream_t* stream);   // lba_device.hip
-extern "C" void** osh_lba_attachment(osh_lba_ctx* ctx, int slot, void (*free_fn)(void*));   // lba_device.hip
-
 extern "C" int osh_pose_optimize(osh_lba_ctx* ctx, int32_t n, const osh_pose_problem* pr, osh_pose_result* res) {
   if (!ctx || n <= 0 || !pr || !res) { set_error("osh_pose_optimize: bad arguments"); return OSH_ERR_INVALID; }
   int device = 0;
   hipStream_t s = nullptr;
-  OSH_TRY(osh_lba_stream(ctx, &device, &s));
+  OSH_TRY(lba_stream(ctx, &device, &s));
   OSH_HIP(hipSetDevice(device));
   std::vector<PoseDesc> h_desc(n);
   size_t NE = 0;
@@ -402,7 +397,7 @@ extern "C" int osh_pose_optimize(osh_lba_ctx* ctx, int32_t n, const osh_pose_pro
   }
   if (NE > 0x7fffff00u) { set_error("batch too large for 32-bit offsets"); return OSH_ERR_UNSUPPORTED; }
   // one pinned staging buffer, one device arena, one copy each way (eight separate copies cost a third of a single frame's call)
-  void** slot = osh_lba_attachment(ctx, 1, [](void* q) { delete static_cast<PoseBuffers*>(q); });
+  void** slot = lba_attachment(ctx, kAttachPose, [](void* q) { delete static_cast<PoseBuffers*>(q); });
   if (!slot) { set_error("osh_pose_optimize: no context"); return OSH_ERR_INVALID; }
   if (!*slot) *slot = new PoseBuffers();
   PoseBuffers& B = *static_cast<PoseBuffers*>(*slot);

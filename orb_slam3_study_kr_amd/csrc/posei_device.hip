@@ -539,16 +539,11 @@ struct PoseiBuffers { PoseiPinned h_in, h_out; DevBuf arena; };
 
 using namespace osh;
 
-#define OSH_TRY(expr) do { int _rc = (expr); if (_rc != OSH_OK) return _rc; } while (0)
-
-extern "C" int osh_lba_stream(osh_lba_ctx* ctx, int* device, hipStream_t* stream);   // lba_device.hip
-extern "C" void** osh_lba_attachment(osh_lba_ctx* ctx, int slot, void (*free_fn)(void*));   // lba_device.hip
-
 extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_problem* pr, osh_posei_result* res) {
   if (!ctx || n <= 0 || !pr || !res) { set_error("osh_posei_optimize: bad arguments"); return OSH_ERR_INVALID; }
   int device = 0;
   hipStream_t s = nullptr;
-  OSH_TRY(osh_lba_stream(ctx, &device, &s));
+  OSH_TRY(lba_stream(ctx, &device, &s));
   OSH_HIP(hipSetDevice(device));
   std::vector<PoseiDesc> h_desc(n);
   size_t NE = 0;
@@ -602,7 +597,7 @@ extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_p
   }
   if (NE > 0x7fffff00u) { set_error("batch too large for 32-bit offsets"); return OSH_ERR_UNSUPPORTED; }
   // one pinned staging buffer, one device arena, one copy each way (the call of a single frame was a dozen copies)
-  void** slot = osh_lba_attachment(ctx, 2, [](void* q) { delete static_cast<PoseiBuffers*>(q); });
+  void** slot = lba_attachment(ctx, kAttachPosei, [](void* q) { delete static_cast<PoseiBuffers*>(q); });
   if (!slot) { set_error("osh_posei_optimize: no context"); return OSH_ERR_INVALID; }
   if (!*slot) *slot = new PoseiBuffers();
   PoseiBuffers& B = *static_cast<PoseiBuffers*>(*slot);

@@ -27,7 +27,7 @@ class HostGraph:
     the newest optimisable one; every other optimisable keyframe is covisible with it."""
 
     def __init__(self, w: LbaWindow, init_kf_fixed: bool = False, inertial: bool = False, init_kf_id_index: int | None = None):
-        self.lib = capi.load_library()
+        self.lib = capi.load_host_library()
         self.w = w
         P, F = w.n_free, w.n_fixed
         self.kf_id = np.array([100 + i for i in range(P)] + [10 + i for i in range(F)], dtype=np.int64)
@@ -208,7 +208,7 @@ class HostGraph:
 
 class HostFrame:
     def __init__(self, xy, octave, desc, angle=None, uright=None, pose_qt=None, mbf=float(synth.BF), mb=0.110078, kb8=None):
-        self.lib = capi.load_library()
+        self.lib = capi.load_host_library()
         n = len(octave)
         self.n = n
         pose = _f32(pose_qt if pose_qt is not None else [0, 0, 0, 1, 0, 0, 0])
@@ -282,7 +282,7 @@ class HostFrame:
             capi.ptr(out["view_cos"], fp), capi.ptr(out["level"], ip), capi.ptr(desc, capi.c_uint8_p), capi.ptr(nobs, ip), nnratio, th,
             capi.ptr(assign, ip), C.cast(C.byref(nm), ip) if assign is not None else C.cast(None, ip))
         if n_in < 0:
-            raise RuntimeError("osh_host_frame_search_local_points_projected failed: " + self.lib.osh_last_error().decode())
+            raise RuntimeError("osh_host_frame_search_local_points_projected failed: " + capi.last_error())
         out.update(n_in_view=n_in, assignment=assign, n_matches=nm.value)
         return out
 
@@ -423,7 +423,7 @@ class HostInertialGraph:
     def __init__(self, w, no_prev=()):
         """``no_prev``: pose indices of temporal keyframes whose mPrevKF stays null (the chain of keyframes breaks before them;
         the window must not hold an inertial link that ends there)."""
-        self.lib = capi.load_library()
+        self.lib = capi.load_host_library()
         self.w = w
         assert not np.isin(w.link_cur, list(no_prev)).any()
         N, K = w.n_opt, w.n_opt + w.n_fixed_imu + w.n_fixed
@@ -586,7 +586,7 @@ class HostInertialGraph:
 
 
 def host_preintegrate(acc, gyr, dt, bias6, nga6, walk6):
-    lib = capi.load_library()
+    lib = capi.load_host_library()
     acc, gyr = _f32(acc), _f32(gyr)
     rec, cov = np.zeros(capi.OSH_PREINT_FLOATS, dtype=np.float32), np.zeros(225, dtype=np.float32)
     fp = capi.c_float_p
@@ -596,7 +596,7 @@ def host_preintegrate(acc, gyr, dt, bias6, nga6, walk6):
 
 
 def host_inertial_information(cov):
-    lib = capi.load_library()
+    lib = capi.load_host_library()
     out = np.zeros(81)
     lib.osh_host_inertial_information(capi.ptr(_f32(cov).ravel(), capi.c_float_p), capi.ptr(out, capi.c_double_p))
     return out.reshape(9, 9)
@@ -608,7 +608,7 @@ class HostPoseiFrame:
     frame lists its left keypoints first)."""
 
     def __init__(self, f):
-        self.lib = capi.load_library()
+        self.lib = capi.load_host_library()
         self.f = f
         right = f.edge_kind == capi.OSH_EDGE_RIGHT
         rig = f.cam2 is not None
@@ -693,7 +693,7 @@ class HostPoseiFrame:
 def search_by_bow_keyframes(desc1, angle1, has_mp1, fv1, desc2, angle2, has_mp2, fv2, nnratio=0.7, check_ori=True):
     """ORBmatcher(nnratio, check_ori).SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:765-905) on two keyframes built from flat
     features; returns (nmatches, match12[n1]) with match12[i] = feature of keyframe 2 whose map point was matched to feature i."""
-    lib = capi.load_library()
+    lib = capi.load_host_library()
     d1, d2 = np.ascontiguousarray(desc1, dtype=np.uint8), np.ascontiguousarray(desc2, dtype=np.uint8)
     keep = [d1, _f32(angle1), np.ascontiguousarray(has_mp1, dtype=np.uint8)] + [_i32(a) for a in fv1] + \
            [d2, _f32(angle2), np.ascontiguousarray(has_mp2, dtype=np.uint8)] + [_i32(a) for a in fv2]
@@ -710,7 +710,7 @@ def search_for_triangulation(kp1, octave1, desc1, has_mp1, pose1_qt, fv1, kp2, o
                              check_ori=True):
     """ORBmatcher(0.6, check_ori).SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (src/ORBmatcher.cc:907-1146) on
     two pinhole keyframes built from flat features (kp = x, y, angle, uright); returns (nmatches, match12[n1])."""
-    lib = capi.load_library()
+    lib = capi.load_host_library()
     u8 = lambda a: np.ascontiguousarray(a, dtype=np.uint8)
     cam4 = _f32([synth.FX, synth.FY, synth.CX, synth.CY])
     keep = [cam4, _f32(kp1), _i32(octave1), u8(desc1), u8(has_mp1), _f32(pose1_qt)] + [_i32(a) for a in fv1] + \
@@ -729,7 +729,7 @@ def search_for_triangulation(kp1, octave1, desc1, has_mp1, pose1_qt, fv1, kp2, o
 def search_for_initialization(f1, f2, prev_xy, window=100, nnratio=0.9, check_ori=True):
     """ORBmatcher(nnratio, check_ori).SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (src/ORBmatcher.cc:648-763)
     on two HostFrames; returns (nmatches, vnMatches12, the updated vbPrevMatched)."""
-    lib = capi.load_library()
+    lib = capi.load_host_library()
     prev = np.array(prev_xy, dtype=np.float32)
     m = -np.ones(f1.n, dtype=np.int32)
     n = lib.osh_host_search_for_initialization(f1.f, f2.f, capi.ptr(prev, capi.c_float_p), int(window), float(nnratio), int(check_ori),
