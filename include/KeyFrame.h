@@ -2,6 +2,7 @@
  * (reference include/KeyFrame.h; src/KeyFrame.cc:109-131,237,309,367,681,1108).  Minimal test double. */
 #ifndef KEYFRAME_H
 #define KEYFRAME_H
+#include <map>
 #include <set>
 #include <vector>
 #include "CameraModels/GeometricCamera.h"
@@ -42,6 +43,12 @@ class KeyFrame {
   Sophus::SE3f GetRelativePoseTrl() { return mTrl; }
   bool isBad() { return mbBad; }
   Map* GetMap() { return mpMap; }
+  // essential-graph accessors (src/KeyFrame.cc:253-273,383-395,612-652,665-680)
+  KeyFrame* GetParent() { return mpParent; }
+  bool hasChild(KeyFrame* pKF) { return mspChildrens.count(pKF) != 0; }
+  std::set<KeyFrame*> GetLoopEdges() { return mspLoopEdges; }
+  std::vector<KeyFrame*> GetCovisiblesByWeight(const int& w);   // the prefix of the weight-ordered list with weights >= w
+  int GetWeight(KeyFrame* pKF);                                  // 0 when not connected
   // candidate generator of the Sim3 searches (src/KeyFrame.cc:704-750): the grid is the one of the Frame the keyframe was made from
   std::vector<size_t> GetFeaturesInArea(const float& x, const float& y, const float& r, const bool bRight = false) const;
   bool IsInImage(const float& x, const float& y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }
@@ -51,6 +58,7 @@ class KeyFrame {
   long unsigned int mnBALocalForMerge = 0;   // include/KeyFrame.h:318
   // global BA results kept beside the live pose until the loop-closing thread applies them (include/KeyFrame.h:369-372)
   Sophus::SE3f mTcwGBA;
+  Sophus::SE3f mTcwBefMerge, mTwcBefMerge;   // include/KeyFrame.h:376-377: poses before a map merge moved them
   long unsigned int mnBAGlobalForKF = 0;
   Eigen::Vector3f mVwbGBA;                   // include/KeyFrame.h:373-375: what FullInertialBA leaves for the loop closer
   IMU::Bias mBiasGBA;
@@ -83,6 +91,10 @@ class KeyFrame {
   IMU::Bias mImuBias;
   bool mbHasVelocity = false;
   std::vector<KeyFrame*> mvpOrderedConnectedKeyFrames;
+  std::vector<int> mvOrderedWeights;                 // weights of mvpOrderedConnectedKeyFrames (descending when set by the test)
+  std::map<KeyFrame*, int> mConnectedKeyFrameWeights;
+  KeyFrame* mpParent = nullptr;
+  std::set<KeyFrame*> mspChildrens, mspLoopEdges;
   std::vector<MapPoint*> mvpMapPoints;
   bool mbBad = false;
   Map* mpMap;

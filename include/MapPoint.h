@@ -40,6 +40,7 @@ class MapPoint {
   int PredictScale(const float& currentDist, Frame* pF);
   int PredictScale(const float& currentDist, KeyFrame* pKF);   // src/MapPoint.cc:514-529
   Eigen::Vector3f GetNormal() { return mNormalVector; }
+  KeyFrame* GetReferenceKeyFrame() { return mpRefKF; }
 
   static std::mutex mGlobalMutex;             // include/MapPoint.h:151 (held while PoseOptimization reads the positions)
   long unsigned int mnId;
@@ -47,6 +48,7 @@ class MapPoint {
   long unsigned int mnBALocalForMerge = 0;    // include/MapPoint.h:139
   Eigen::Vector3f mPosGBA;                    // include/MapPoint.h:147-148
   long unsigned int mnBAGlobalForKF = 0;
+  long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;   // include/MapPoint.h:143-144 (set by LoopClosing::CorrectLoop)
   // tracking scratch written by Frame::isInFrustum (src/Frame.cc:513-587), read by SearchByProjection
   float mTrackProjX = 0, mTrackProjY = 0, mTrackDepth = 0, mTrackProjXR = 0, mTrackProjYR = 0;
   bool mbTrackInView = false, mbTrackInViewR = false;
@@ -63,6 +65,7 @@ class MapPoint {
   cv::Mat mDescriptor;
   int mnNormalUpdates = 0;
   MapPoint* mpReplaced = nullptr;
+  KeyFrame* mpRefKF = nullptr;
   int mnVisible = 1, mnFound = 1, mnDescriptorUpdates = 0;
 };
 }  // namespace ORB_SLAM3

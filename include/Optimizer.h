@@ -6,6 +6,8 @@
 #include "KeyFrame.h"
 #include "LoopClosing.h"
 #include "Map.h"
+#include <map>
+#include <set>
 #include <vector>
 #include "MapPoint.h"
 namespace ORB_SLAM3 {
@@ -35,6 +37,14 @@ class Optimizer {
   void static FullInertialBA(Map* pMap, int its, const bool bFixLocal = false, const unsigned long nLoopKF = 0, bool* pbStopFlag = NULL,
                              bool bInit = false, float priorG = 1e2, float priorA = 1e6, Eigen::VectorXd* vSingVal = NULL, bool* bHess = NULL);
   // src/Optimizer.cc:3956-4498: the welding visual-inertial BA of a map merge (two temporal chains + up to 31 covisible keyframes)
+  // src/Optimizer.cc:1501-1784 (csrc/host/OptimizerEssentialGraph.cc): the Sim3 pose graph of a loop correction, optimize(20) on the
+  // device, then poses SE3f(R, t/s) and the map points through their reference keyframe's correction.  Up to 4000 keyframes.
+  void static OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                     const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                     const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections, const bool& bFixScale);
+  // src/Optimizer.cc:1786-2117: the same problem for a map merge, built from three keyframe lists
+  void static OptimizeEssentialGraph(KeyFrame* pCurKF, std::vector<KeyFrame*>& vpFixedKFs, std::vector<KeyFrame*>& vpFixedCorrectedKFs,
+                                     std::vector<KeyFrame*>& vpNonFixedKFs, std::vector<MapPoint*>& vpNonCorrectedMPs);
   void static MergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, bool* pbStopFlag, Map* pMap, LoopClosing::KeyFrameAndPose& corrPoses);
 };
 }  // namespace ORB_SLAM3

@@ -163,7 +163,9 @@ class Sim3 {
 using Sim3f = Sim3<float>;
 }  // namespace Sophus
 
-// g2o::Sim3 (Thirdparty/g2o/g2o/types/sim3.h:45-80): what Optimizer::MergeInertialBA leaves in LoopClosing::KeyFrameAndPose
+// g2o::Sim3 (Thirdparty/g2o/g2o/types/sim3.h:45-80): what Optimizer::MergeInertialBA leaves in LoopClosing::KeyFrameAndPose,
+// and the product / inverse / map that Optimizer::OptimizeEssentialGraph composes measurements with (:144,233-272), with
+// Eigen's quaternion product and rotation (q * v = v + w uv + vec x uv, uv = 2 vec x v).
 namespace g2o {
 class Sim3 {
  public:
@@ -172,6 +174,29 @@ class Sim3 {
   const Eigen::Quaterniond& rotation() const { return r_; }
   const Eigen::Vector3d& translation() const { return t_; }
   const double& scale() const { return s_; }
+  Eigen::Vector3d map(const Eigen::Vector3d& xyz) const {
+    const Eigen::Vector3d r = rotate(r_, xyz);
+    return Eigen::Vector3d(s_ * r(0) + t_(0), s_ * r(1) + t_(1), s_ * r(2) + t_(2));
+  }
+  Sim3 inverse() const {
+    const Eigen::Quaterniond c(r_.w(), -r_.x(), -r_.y(), -r_.z());
+    const double f = -1. / s_;
+    return Sim3(c, rotate(c, Eigen::Vector3d(f * t_(0), f * t_(1), f * t_(2))), 1. / s_);
+  }
+  Sim3 operator*(const Sim3& o) const {
+    const double aw = r_.w(), ax = r_.x(), ay = r_.y(), az = r_.z();
+    const double bw = o.r_.w(), bx = o.r_.x(), by = o.r_.y(), bz = o.r_.z();
+    const Eigen::Quaterniond q(aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                               aw * by + ay * bw + az * bx - ax * bz, aw * bz + az * bw + ax * by - ay * bx);
+    const Eigen::Vector3d r = rotate(r_, o.t_);
+    return Sim3(q, Eigen::Vector3d(s_ * r(0) + t_(0), s_ * r(1) + t_(1), s_ * r(2) + t_(2)), s_ * o.s_);
+  }
+  static Eigen::Vector3d rotate(const Eigen::Quaterniond& q, const Eigen::Vector3d& v) {
+    double uv0 = q.y() * v(2) - q.z() * v(1), uv1 = q.z() * v(0) - q.x() * v(2), uv2 = q.x() * v(1) - q.y() * v(0);
+    uv0 += uv0; uv1 += uv1; uv2 += uv2;
+    return Eigen::Vector3d(v(0) + q.w() * uv0 + (q.y() * uv2 - q.z() * uv1), v(1) + q.w() * uv1 + (q.z() * uv0 - q.x() * uv2),
+                           v(2) + q.w() * uv2 + (q.x() * uv1 - q.y() * uv0));
+  }
  private:
   Eigen::Quaterniond r_;
   Eigen::Vector3d t_;

@@ -391,6 +391,52 @@ int osh_liba_solve(osh_lba_ctx* ctx, int32_t n_windows, const osh_liba_problem* 
  * (linearise, assembly, Dinv, Schur, LDL^T, back-substitution, errors, outputs). */
 int osh_liba_get_profile(int32_t* group, int64_t cycles[8]);
 
+/* ------------------------------------------------- Sim3 pose graph (essential graph) */
+/*
+ * The solver part of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1501-1784, merge overload :1786-2117):
+ * one VertexSim3Expmap per keyframe, EdgeSim3 with identity information and no robust kernel
+ * (Thirdparty/g2o/g2o/types/types_seven_dof_expmap.h:60-112), numeric Jacobians (base_binary_edge.hpp:147-196,
+ * delta 1e-9), Levenberg-Marquardt as optimization_algorithm_levenberg.cpp:99-169 runs it.  The reduced system is
+ * factored in vertex-array order (pass the vertices in keyframe-id order) with its column envelope kept.
+ * Sim3 layout everywhere: qx qy qz qw tx ty tz s (g2o::Sim3::operator[]).
+ */
+#define OSH_PGO_MAX_VERTICES   4000   /* free vertices of one graph (the global-BA limit)                        */
+#define OSH_PGO_MAX_ENV_TILES  65536  /* envelope storage: 32x32 FP64 tiles, 512 MiB; larger graphs are refused  */
+#define OSH_PGO_SOLVE_ENVELOPE 0
+#define OSH_PGO_SOLVE_DENSE    1      /* diagnostic: the same factorisation over the full upper triangle          */
+
+typedef struct osh_pgo_problem {
+  int32_t n_vertices;
+  const double* estimate;     /* [n_vertices*8] initial Siw */
+  const uint8_t* fixed;       /* [n_vertices] setFixed(true): no Jacobian, no block                      */
+  const uint8_t* fix_scale;   /* [n_vertices] VertexSim3Expmap::_fix_scale: update[6] = 0                 */
+  int32_t n_edges;
+  const int32_t* edge_ij;     /* [n_edges*2] vertex 0 (i) and vertex 1 (j) of every EdgeSim3 (indices into the vertices) */
+  const double* measurement;  /* [n_edges*8] Sji; error = log(Sji * Si * Sj^-1)                           */
+  int32_t iterations;         /* optimize(iterations)                                                     */
+  double lambda_init;         /* setUserLambdaInit (> 0)                                                  */
+  int32_t solve_mode;         /* OSH_PGO_SOLVE_ENVELOPE / OSH_PGO_SOLVE_DENSE                              */
+} osh_pgo_problem;
+
+typedef struct osh_pgo_result {
+  double* estimate;           /* [n_vertices*8] estimates after optimize() (fixed vertices copied unchanged) */
+  int32_t iterations;         /* LM iterations run (cjIterations)                                          */
+  int32_t trials;             /* LM trials over all iterations                                             */
+  double chi2_initial;        /* activeChi2 before the first iteration                                     */
+  double chi2_final;          /* activeChi2 of the returned estimates                                      */
+  int64_t envelope_entries;   /* scalar entries of the upper envelope of the reduced system               */
+  int32_t envelope_tiles;     /* 32x32 tiles stored                                                        */
+  int32_t tall_columns;       /* free vertices whose envelope column reaches more than 64 rows above the diagonal */
+  int32_t status;
+} osh_pgo_result;
+
+/* initializeOptimization + optimize(iterations) of one Sim3 pose graph on the context's device and stream.  Graphs beyond
+ * OSH_PGO_MAX_VERTICES free vertices or OSH_PGO_MAX_ENV_TILES envelope tiles return OSH_ERR_UNSUPPORTED before any device work. */
+int osh_pgo_solve(osh_lba_ctx* ctx, const osh_pgo_problem* problem, osh_pgo_result* result);
+/* Diagnostic: the first linearisation of `problem` (chi2 at the initial estimates, H and b = -J^T e of the free vertices
+ * in array order, dense row-major (7 nf) x (7 nf) with both triangles filled; b[7 nf]).  For small graphs (nf <= 512). */
+int osh_pgo_linearize(osh_lba_ctx* ctx, const osh_pgo_problem* problem, double* H, double* b, double* chi2);
+
 /* --------------------------------------------------------- ORB matching API */
 /*
  * Nearest / second-nearest 256-bit Hamming search (the candidate loops of

@@ -232,6 +232,46 @@ int osh_host_search_by_sim3(osh_host_frame* f1, osh_host_frame* f2, const float 
                             const int32_t* slot_mp1, int32_t n_mp2, const float* mp_pos2, const uint8_t* mp_desc2, const float* mp_min_max2,
                             const uint8_t* mp_bad2, const int32_t* slot_mp2, const int32_t* matches_in, int32_t* matches_out);
 
+/* ---- Optimizer::OptimizeEssentialGraph (csrc/host/OptimizerEssentialGraph.cc) on a map made by osh_host_graph_create ---- */
+/* The essential graph of the stand-in map: parent[n_kf] (keyframe index, -1: none; children follow), covisibility entries
+ * (keyframe, other keyframe, weight; each keyframe's list is ordered by descending weight, ties in entry order), loop edges
+ * (both directions), prev_kf[n_kf] / b_imu[n_kf] (may be NULL), and per map point its reference keyframe index, mnCorrectedByKF
+ * and mnCorrectedReference (may be NULL). */
+int osh_host_pgo_set_graph(osh_host_graph* g, const int32_t* parent, int32_t n_cov, const int32_t* cov_kf, const int32_t* cov_other,
+                           const int32_t* cov_weight, int32_t n_loop, const int32_t* loop_a, const int32_t* loop_b, const int32_t* prev_kf,
+                           const uint8_t* b_imu, const int32_t* mp_ref, const int64_t* mp_corrected_by, const int64_t* mp_corrected_ref);
+/* mTcwBefMerge (and mTwcBefMerge, its inverse) of keyframe kf_index: qx qy qz qw tx ty tz */
+void osh_host_pgo_set_before_merge(osh_host_graph* g, int32_t kf_index, const float qt[7]);
+/* The loop correction handed to the first overload (keyframes by index; Sim3 as qx qy qz qw tx ty tz s). */
+typedef struct osh_host_loop {
+  int32_t cur, loop, fix_scale;
+  int32_t n_corrected;    const int32_t* corrected_kf;    const double* corrected_sim3;      /* CorrectedSim3    */
+  int32_t n_noncorrected; const int32_t* noncorrected_kf; const double* noncorrected_sim3;   /* NonCorrectedSim3 */
+  int32_t n_connections;  const int32_t* conn_kf;         const int32_t* conn_other;         /* LoopConnections  */
+} osh_host_loop;
+/* The three keyframe lists and the map points of the merge overload (indices). */
+typedef struct osh_host_merge {
+  int32_t cur;
+  int32_t n_fixed;           const int32_t* fixed;
+  int32_t n_fixed_corrected; const int32_t* fixed_corrected;
+  int32_t n_non_fixed;       const int32_t* non_fixed;
+  int32_t n_mps;             const int32_t* mps;
+} osh_host_merge;
+/* What the graph walk built: capacities in, sizes out; arrays as osh_pgo_problem, vertex_kf_id = mnId of every vertex. */
+typedef struct osh_host_pgo_out {
+  int32_t max_vertices, max_edges;
+  int32_t n_vertices, n_edges, n_free;
+  int64_t* vertex_kf_id; double* estimate; uint8_t* fixed; uint8_t* fix_scale; int32_t* edge_ij; double* measurement;
+} osh_host_pgo_out;
+/* The graph walk alone (no device): 0, or -1 when a capacity is too small. */
+int osh_host_pgo_pack(osh_host_graph* g, const osh_host_loop* loop, osh_host_pgo_out* out);
+int osh_host_pgo_pack_merge(osh_host_graph* g, const osh_host_merge* merge, osh_host_pgo_out* out);
+/* ORB_SLAM3::Optimizer::OptimizeEssentialGraph, either overload */
+int osh_host_pgo_run(osh_host_graph* g, const osh_host_loop* loop);
+int osh_host_pgo_run_merge(osh_host_graph* g, const osh_host_merge* merge);
+/* UpdateNormalAndDepth calls on map point mp_index (osh_host_mp_normal_updates) and pose writes (osh_host_kf_pose_sets) count the
+ * write-back; osh_host_map_change_index counts IncreaseChangeIndex. */
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,30 @@ class PoseResult(C.Structure):
     ]
 
 
+class PgoProblem(C.Structure):
+    """``osh_pgo_problem`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("n_vertices", C.c_int32), ("estimate", c_double_p), ("fixed", c_uint8_p), ("fix_scale", c_uint8_p),
+        ("n_edges", C.c_int32), ("edge_ij", C.POINTER(C.c_int32)), ("measurement", c_double_p),
+        ("iterations", C.c_int32), ("lambda_init", C.c_double), ("solve_mode", C.c_int32),
+    ]
+
+
+class PgoResult(C.Structure):
+    """``osh_pgo_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("estimate", c_double_p), ("iterations", C.c_int32), ("trials", C.c_int32),
+        ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("envelope_entries", C.c_int64),
+        ("envelope_tiles", C.c_int32), ("tall_columns", C.c_int32), ("status", C.c_int32),
+    ]
+
+
+OSH_PGO_MAX_VERTICES = 4000
+OSH_PGO_SOLVE_ENVELOPE = 0
+OSH_PGO_SOLVE_DENSE = 1
+
 OSH_PREINT_FLOATS = 72
 
 
@@ -247,6 +271,8 @@ _SIGNATURES = {
     "osh_orb_list_distances": (C.c_int, [C.c_void_p, c_int32_p]),
     "osh_orb_get_resolve_profile": (C.c_int, [C.c_void_p, c_int64_p, c_double_p]),
     "osh_orb_distance_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, c_int32_p]),
+    "osh_pgo_solve": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), C.POINTER(PgoResult)]),
+    "osh_pgo_linearize": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), c_double_p, c_double_p, c_double_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -338,6 +364,47 @@ _HOST_SIGNATURES = {
     "osh_host_search_keyframe": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, c_int32_p, C.c_int32, c_float_p, c_uint8_p, c_float_p,
                                            c_uint8_p, c_uint8_p, c_int32_p, C.c_float, C.c_int32, C.c_int32, c_int32_p]),
 }
+
+
+class HostLoop(C.Structure):
+    """``osh_host_loop`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [
+        ("cur", C.c_int32), ("loop", C.c_int32), ("fix_scale", C.c_int32),
+        ("n_corrected", C.c_int32), ("corrected_kf", c_int32_p), ("corrected_sim3", c_double_p),
+        ("n_noncorrected", C.c_int32), ("noncorrected_kf", c_int32_p), ("noncorrected_sim3", c_double_p),
+        ("n_connections", C.c_int32), ("conn_kf", c_int32_p), ("conn_other", c_int32_p),
+    ]
+
+
+class HostMerge(C.Structure):
+    """``osh_host_merge`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [
+        ("cur", C.c_int32), ("n_fixed", C.c_int32), ("fixed", c_int32_p), ("n_fixed_corrected", C.c_int32),
+        ("fixed_corrected", c_int32_p), ("n_non_fixed", C.c_int32), ("non_fixed", c_int32_p), ("n_mps", C.c_int32), ("mps", c_int32_p),
+    ]
+
+
+class HostPgoOut(C.Structure):
+    """``osh_host_pgo_out`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [
+        ("max_vertices", C.c_int32), ("max_edges", C.c_int32), ("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("n_free", C.c_int32),
+        ("vertex_kf_id", c_int64_p), ("estimate", c_double_p), ("fixed", c_uint8_p), ("fix_scale", c_uint8_p),
+        ("edge_ij", c_int32_p), ("measurement", c_double_p),
+    ]
+
+
+_HOST_SIGNATURES.update({
+    "osh_host_pgo_set_graph": (C.c_int, [C.c_void_p, c_int32_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_int32_p,
+                                         c_int32_p, c_uint8_p, c_int32_p, c_int64_p, c_int64_p]),
+    "osh_host_pgo_set_before_merge": (None, [C.c_void_p, C.c_int32, c_float_p]),
+    "osh_host_pgo_pack": (C.c_int, [C.c_void_p, C.POINTER(HostLoop), C.POINTER(HostPgoOut)]),
+    "osh_host_pgo_pack_merge": (C.c_int, [C.c_void_p, C.POINTER(HostMerge), C.POINTER(HostPgoOut)]),
+    "osh_host_pgo_run": (C.c_int, [C.c_void_p, C.POINTER(HostLoop)]),
+    "osh_host_pgo_run_merge": (C.c_int, [C.c_void_p, C.POINTER(HostMerge)]),
+})
 HOST_EXPORTED_SYMBOLS = tuple(_HOST_SIGNATURES)
 
 _lib = None

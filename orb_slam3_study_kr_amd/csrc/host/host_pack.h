@@ -3,9 +3,12 @@
 #include <cmath>
 #include <cstdint>
 #include <list>
+#include <map>
+#include <set>
 #include <vector>
 #include "CameraModels/GeometricCamera.h"
 #include "KeyFrame.h"
+#include "LoopClosing.h"
 #include "Map.h"
 #include "MapPoint.h"
 #include "orbslam3_hip.h"
@@ -184,6 +187,29 @@ bool PackFullInertialBA(Map* pMap, int its, bool bFixLocal, bool bInit, float pr
 bool PackMergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, LibaPack& pk, std::vector<KeyFrame*>& vpCovKFs);
 void InertialInformation(const Eigen::Matrix<float, 15, 15>& C, double* info81);
 osh_lba_ctx* HostSolverContext();   // one solver context per calling thread (Optimizer.cc)
+
+// Optimizer::OptimizeEssentialGraph as an osh_pgo_problem (OptimizerEssentialGraph.cc): vertices in keyframe-id order, edges in
+// the order the reference adds them; vScw / vCorrectedSwc / vpGoodPose / vpBadPose indexed by mnId as there.
+struct PgoPack {
+  std::vector<KeyFrame*> vpVertexKF;         // keyframe of every vertex
+  std::vector<int> vertexOfId;               // mnId -> vertex (-1: none)
+  std::vector<double> estimate, measurement; // [n*8], [E*8]
+  std::vector<uint8_t> fixed, fix_scale;
+  std::vector<int32_t> edge_ij;
+  std::vector<g2o::Sim3> vScw, vCorrectedSwc;
+  std::vector<bool> vpGoodPose, vpBadPose;   // merge overload only
+  int nFree = 0;
+  void fill(osh_pgo_problem& p) const {
+    p.n_vertices = (int32_t)vpVertexKF.size(); p.estimate = estimate.data(); p.fixed = fixed.data(); p.fix_scale = fix_scale.data();
+    p.n_edges = (int32_t)(edge_ij.size() / 2); p.edge_ij = edge_ij.data(); p.measurement = measurement.data();
+    p.iterations = 20; p.lambda_init = 1e-16; p.solve_mode = OSH_PGO_SOLVE_ENVELOPE;   // setUserLambdaInit(1e-16), optimize(20)
+  }
+};
+void PackEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                        const LoopClosing::KeyFrameAndPose& CorrectedSim3, const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections,
+                        const bool& bFixScale, PgoPack& pk);
+void PackEssentialGraphMerge(KeyFrame* pCurKF, std::vector<KeyFrame*>& vpFixedKFs, std::vector<KeyFrame*>& vpFixedCorrectedKFs,
+                             std::vector<KeyFrame*>& vpNonFixedKFs, PgoPack& pk);
 
 // Steps 1-6 of Optimizer::LocalBundleAdjustment; false when the window has no fixed keyframe.
 bool PackLocalBA(KeyFrame* pKF, Map* pMap, LbaPack& pk);

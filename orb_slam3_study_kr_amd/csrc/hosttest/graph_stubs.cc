@@ -121,6 +121,7 @@ void MapPoint::EraseObservation(KeyFrame* pKF) {
   if (leftIndex != -1) nObs -= (!pKF->mpCamera2 && pKF->mvuRight[leftIndex] >= 0) ? 2 : 1;
   if (rightIndex != -1) nObs--;
   mObservations.erase(it);
+  if (mpRefKF == pKF && !mObservations.empty()) mpRefKF = mObservations.begin()->first;   // src/MapPoint.cc:190-191
   if (nObs <= 2) mbBad = true;
 }
 

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <map>
 #include <memory>
 #include <set>
 #include <vector>
@@ -1168,4 +1169,120 @@ extern "C" int osh_host_posei_run(osh_host_posei* h, int32_t rec_init, float pos
   if (F.mpcpi) for (int a = 0; a < 225; ++a) H225_out[a] = F.mpcpi->H.v[a];
   *prev_cpi_deleted = (h->mode == 1 && h->prevF.mpcpi == nullptr) ? 1 : 0;
   return n;
+}
+
+// ---- Optimizer::OptimizeEssentialGraph ----
+extern "C" int osh_host_pgo_set_graph(osh_host_graph* g, const int32_t* parent, int32_t n_cov, const int32_t* cov_kf, const int32_t* cov_other,
+                                      const int32_t* cov_weight, int32_t n_loop, const int32_t* loop_a, const int32_t* loop_b,
+                                      const int32_t* prev_kf, const uint8_t* b_imu, const int32_t* mp_ref, const int64_t* mp_corrected_by,
+                                      const int64_t* mp_corrected_ref) {
+  const int n = (int)g->kfs.size();
+  for (int i = 0; i < n; ++i) {
+    KeyFrame* kf = g->kfs[i].get();
+    if (parent && parent[i] >= 0) { kf->mpParent = g->kfs[parent[i]].get(); kf->mpParent->mspChildrens.insert(kf); }
+    if (prev_kf && prev_kf[i] >= 0) kf->mPrevKF = g->kfs[prev_kf[i]].get();
+    if (b_imu) kf->bImu = b_imu[i] != 0;
+  }
+  std::vector<std::vector<std::pair<int, KeyFrame*>>> cov(n);
+  for (int c = 0; c < n_cov; ++c) {
+    if (cov_kf[c] < 0 || cov_kf[c] >= n || cov_other[c] < 0 || cov_other[c] >= n) return -1;
+    cov[cov_kf[c]].push_back({cov_weight[c], g->kfs[cov_other[c]].get()});
+  }
+  for (int i = 0; i < n; ++i) {
+    KeyFrame* kf = g->kfs[i].get();
+    std::stable_sort(cov[i].begin(), cov[i].end(), [](const std::pair<int, KeyFrame*>& a, const std::pair<int, KeyFrame*>& b) { return a.first > b.first; });
+    kf->mvpOrderedConnectedKeyFrames.clear();
+    kf->mvOrderedWeights.clear();
+    kf->mConnectedKeyFrameWeights.clear();
+    for (const auto& e : cov[i]) {
+      kf->mvpOrderedConnectedKeyFrames.push_back(e.second);
+      kf->mvOrderedWeights.push_back(e.first);
+      kf->mConnectedKeyFrameWeights[e.second] = e.first;
+    }
+  }
+  for (int l = 0; l < n_loop; ++l) {
+    g->kfs[loop_a[l]]->mspLoopEdges.insert(g->kfs[loop_b[l]].get());
+    g->kfs[loop_b[l]]->mspLoopEdges.insert(g->kfs[loop_a[l]].get());
+  }
+  for (size_t j = 0; j < g->mps.size(); ++j) {
+    if (mp_ref) g->mps[j]->mpRefKF = mp_ref[j] >= 0 ? g->kfs[mp_ref[j]].get() : nullptr;
+    if (mp_corrected_by) g->mps[j]->mnCorrectedByKF = (unsigned long)mp_corrected_by[j];
+    if (mp_corrected_ref) g->mps[j]->mnCorrectedReference = (unsigned long)mp_corrected_ref[j];
+  }
+  return 0;
+}
+
+extern "C" void osh_host_pgo_set_before_merge(osh_host_graph* g, int32_t kf_index, const float qt[7]) {
+  KeyFrame* kf = g->kfs[kf_index].get();
+  kf->mTcwBefMerge = pose_from(qt);
+  kf->mTwcBefMerge = kf->mTcwBefMerge.inverse();
+}
+
+namespace {
+struct LoopArgs {
+  LoopClosing::KeyFrameAndPose corrected, noncorrected;
+  std::map<KeyFrame*, std::set<KeyFrame*>> connections;
+};
+g2o::Sim3 sim3_from(const double* v) { return g2o::Sim3(Eigen::Quaterniond(v[3], v[0], v[1], v[2]), Eigen::Vector3d(v[4], v[5], v[6]), v[7]); }
+LoopArgs loop_args(osh_host_graph* g, const osh_host_loop* l) {
+  LoopArgs a;
+  for (int k = 0; k < l->n_corrected; ++k) a.corrected[g->kfs[l->corrected_kf[k]].get()] = sim3_from(l->corrected_sim3 + 8 * k);
+  for (int k = 0; k < l->n_noncorrected; ++k) a.noncorrected[g->kfs[l->noncorrected_kf[k]].get()] = sim3_from(l->noncorrected_sim3 + 8 * k);
+  for (int k = 0; k < l->n_connections; ++k) a.connections[g->kfs[l->conn_kf[k]].get()].insert(g->kfs[l->conn_other[k]].get());
+  return a;
+}
+std::vector<KeyFrame*> kf_list(osh_host_graph* g, int32_t n, const int32_t* idx) {
+  std::vector<KeyFrame*> v;
+  for (int k = 0; k < n; ++k) v.push_back(g->kfs[idx[k]].get());
+  return v;
+}
+int export_pgo(const PgoPack& pk, osh_host_pgo_out* out) {
+  out->n_vertices = (int32_t)pk.vpVertexKF.size();
+  out->n_edges = (int32_t)(pk.edge_ij.size() / 2);
+  out->n_free = pk.nFree;
+  if (out->n_vertices > out->max_vertices || out->n_edges > out->max_edges) return -1;
+  for (int v = 0; v < out->n_vertices; ++v) {
+    if (out->vertex_kf_id) out->vertex_kf_id[v] = (int64_t)pk.vpVertexKF[v]->mnId;
+    if (out->fixed) out->fixed[v] = pk.fixed[v];
+    if (out->fix_scale) out->fix_scale[v] = pk.fix_scale[v];
+  }
+  if (out->estimate) std::copy(pk.estimate.begin(), pk.estimate.end(), out->estimate);
+  if (out->edge_ij) std::copy(pk.edge_ij.begin(), pk.edge_ij.end(), out->edge_ij);
+  if (out->measurement) std::copy(pk.measurement.begin(), pk.measurement.end(), out->measurement);
+  return 0;
+}
+}  // namespace
+
+extern "C" int osh_host_pgo_pack(osh_host_graph* g, const osh_host_loop* l, osh_host_pgo_out* out) {
+  LoopArgs a = loop_args(g, l);
+  PgoPack pk;
+  const bool fix = l->fix_scale != 0;
+  PackEssentialGraph(&g->map, g->kfs[l->loop].get(), g->kfs[l->cur].get(), a.noncorrected, a.corrected, a.connections, fix, pk);
+  return export_pgo(pk, out);
+}
+
+extern "C" int osh_host_pgo_pack_merge(osh_host_graph* g, const osh_host_merge* m, osh_host_pgo_out* out) {
+  std::vector<KeyFrame*> f = kf_list(g, m->n_fixed, m->fixed), fc = kf_list(g, m->n_fixed_corrected, m->fixed_corrected),
+                         nf = kf_list(g, m->n_non_fixed, m->non_fixed);
+  PgoPack pk;
+  PackEssentialGraphMerge(g->kfs[m->cur].get(), f, fc, nf, pk);
+  return export_pgo(pk, out);
+}
+
+extern "C" int osh_host_pgo_run(osh_host_graph* g, const osh_host_loop* l) {
+  LoopArgs a = loop_args(g, l);
+  const bool fix = l->fix_scale != 0;
+  CallTimer t;
+  Optimizer::OptimizeEssentialGraph(&g->map, g->kfs[l->loop].get(), g->kfs[l->cur].get(), a.noncorrected, a.corrected, a.connections, fix);
+  return 0;
+}
+
+extern "C" int osh_host_pgo_run_merge(osh_host_graph* g, const osh_host_merge* m) {
+  std::vector<KeyFrame*> f = kf_list(g, m->n_fixed, m->fixed), fc = kf_list(g, m->n_fixed_corrected, m->fixed_corrected),
+                         nf = kf_list(g, m->n_non_fixed, m->non_fixed);
+  std::vector<MapPoint*> mps;
+  for (int k = 0; k < m->n_mps; ++k) mps.push_back(g->mps[m->mps[k]].get());
+  CallTimer t;
+  Optimizer::OptimizeEssentialGraph(g->kfs[m->cur].get(), f, fc, nf, mps);
+  return 0;
 }
