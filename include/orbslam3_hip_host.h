@@ -272,6 +272,24 @@ int osh_host_pgo_run_merge(osh_host_graph* g, const osh_host_merge* merge);
 /* UpdateNormalAndDepth calls on map point mp_index (osh_host_mp_normal_updates) and pose writes (osh_host_kf_pose_sets) count the
  * write-back; osh_host_map_change_index counts IncreaseChangeIndex. */
 
+/* ---- the device's Sim3 algebra (csrc/pgo_sim3.h) compiled for the host ---- */
+/* op over n items, Sim3 = qx qy qz qw tx ty tz s (8 doubles), tangent = omega upsilon sigma (7), R row-major (9):
+ *   EXP a[7] -> out[8]          LOG a[8] -> out[7]          MUL a[8] b[8] -> out[8]      INVERSE a[8] -> out[8]
+ *   MAP a[8] b[3] -> out[3]     EDGE_ERROR meas a[8], Si b[8], Sj c[8] -> out[7]     OPLUS est a[8], update b[7], flag = fix_scale -> out[8]
+ *   QUAT_TO_R a[4] -> out[9]    R_TO_QUAT a[9] -> out[4]    SOLVE3 (3x3 partial-pivot LU) W a[9] t b[3] -> out[3]
+ * Returns 0, or -1 for an unknown op or a missing array. */
+#define OSH_SIM3_EXP        0
+#define OSH_SIM3_LOG        1
+#define OSH_SIM3_MUL        2
+#define OSH_SIM3_INVERSE    3
+#define OSH_SIM3_MAP        4
+#define OSH_SIM3_EDGE_ERROR 5
+#define OSH_SIM3_OPLUS      6
+#define OSH_SIM3_QUAT_TO_R  7
+#define OSH_SIM3_R_TO_QUAT  8
+#define OSH_SIM3_SOLVE3     9
+int osh_host_sim3_apply(int32_t op, int32_t n, const double* a, const double* b, const double* c, const uint8_t* flag, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -404,6 +404,7 @@ _HOST_SIGNATURES.update({
     "osh_host_pgo_pack_merge": (C.c_int, [C.c_void_p, C.POINTER(HostMerge), C.POINTER(HostPgoOut)]),
     "osh_host_pgo_run": (C.c_int, [C.c_void_p, C.POINTER(HostLoop)]),
     "osh_host_pgo_run_merge": (C.c_int, [C.c_void_p, C.POINTER(HostMerge)]),
+    "osh_host_sim3_apply": (C.c_int, [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_uint8_p, c_double_p]),
 })
 HOST_EXPORTED_SYMBOLS = tuple(_HOST_SIGNATURES)
 

@@ -5,6 +5,10 @@ a leading axis, EdgeSim3's error (types_seven_dof_expmap.h:99-112), the central-
 base_binary_edge.hpp:147-196 through VertexSim3Expmap::oplusImpl (:60-69), a direct sparse solve of H + lambda I, and the
 Levenberg-Marquardt controller of optimization_algorithm_levenberg.cpp:99-169 with this g2o copy's three-bad-iterations stop.
 Sim3 arrays are [..., 8] = qx qy qz qw tx ty tz s.
+
+Every Sim3 function, errors, jacobians and linearize take a dtype: np.float64 (the default, the precision of the device and of
+g2o) or np.longdouble, the extended-precision reference the stage tests of the device compare both against.  Products,
+inverses and maps follow the dtype of their inputs.  solve_ld solves a linear system to extended precision.
 """
 from __future__ import annotations
 
@@ -15,8 +19,14 @@ import numpy as np
 EPS = 0.00001
 
 
+def require_extended():
+    """The reference needs 80-bit (or wider) long double: fail loudly, never skip, where it is missing."""
+    eps = np.finfo(np.longdouble).eps
+    assert eps < 1e-18, f"np.longdouble has eps {eps}: this platform has no extended precision for the reference"
+
+
 def skew(w):
-    z = np.zeros(w.shape[:-1])
+    z = np.zeros(w.shape[:-1], dtype=w.dtype)
     return np.stack([np.stack([z, -w[..., 2], w[..., 1]], -1),
                      np.stack([w[..., 2], z, -w[..., 0]], -1),
                      np.stack([-w[..., 1], w[..., 0], z], -1)], -2)
@@ -32,10 +42,10 @@ def quat_to_R(q):
                      np.stack([txz - twy, tyz + twx, 1 - (txx + tyy)], -1)], -2)
 
 
-def R_to_quat(R):
+def R_to_quat(R, dtype=np.float64):
     """Eigen's Quaterniond(const Matrix3d&), no normalisation."""
-    R = np.asarray(R, dtype=np.float64)
-    out = np.zeros(R.shape[:-2] + (4,))
+    R = np.asarray(R, dtype=dtype)
+    out = np.zeros(R.shape[:-2] + (4,), dtype=dtype)
     flatR = R.reshape(-1, 3, 3)
     flatq = out.reshape(-1, 4)
     for n in range(flatR.shape[0]):
@@ -68,7 +78,7 @@ def R_to_quat(R):
 def _R_to_quat_vec(R):
     """Vectorised R_to_quat for the trace > 0 case, falling back to the loop for the rest."""
     tr = R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2]
-    q = np.zeros(R.shape[:-2] + (4,))
+    q = np.zeros(R.shape[:-2] + (4,), dtype=R.dtype)
     pos = tr > 0
     with np.errstate(all="ignore"):
         t = np.sqrt(np.where(pos, tr, 0.0) + 1.0)
@@ -79,7 +89,7 @@ def _R_to_quat_vec(R):
         q[..., 1] = (R[..., 0, 2] - R[..., 2, 0]) * f
         q[..., 2] = (R[..., 1, 0] - R[..., 0, 1]) * f
     if not np.all(pos):
-        q[~pos] = R_to_quat(R[~pos])
+        q[~pos] = R_to_quat(R[~pos], R.dtype)
     return q
 
 
@@ -115,14 +125,15 @@ def sim3_map(a, p):
     return a[..., 7:8] * quat_rotate(a[..., :4], p) + a[..., 4:7]
 
 
-def sim3_exp(u):
-    u = np.asarray(u, dtype=np.float64)
+def sim3_exp(u, dtype=np.float64):
+    u = np.asarray(u, dtype=dtype)
+    one = dtype(1)
     omega, ups, sigma = u[..., :3], u[..., 3:6], u[..., 6]
     theta = np.sqrt(np.sum(omega * omega, -1))
     Om = skew(omega)
     Om2 = Om @ Om
     s = np.exp(sigma)
-    I = np.eye(3)
+    I = np.eye(3, dtype=dtype)
     small_s = np.abs(sigma) < EPS
     small_t = theta < EPS
     with np.errstate(all="ignore"):
@@ -130,7 +141,7 @@ def sim3_exp(u):
         sg2 = sigma * sigma
         # |sigma| < eps
         A0 = np.where(small_t, 0.5, (1 - np.cos(theta)) / th2)
-        B0 = np.where(small_t, 1.0 / 6.0, (theta - np.sin(theta)) / (th2 * theta))
+        B0 = np.where(small_t, one / 6, (theta - np.sin(theta)) / (th2 * theta))
         C1 = (s - 1) / sigma
         a = s * np.sin(theta)
         b = s * np.cos(theta)
@@ -149,8 +160,9 @@ def sim3_exp(u):
     return np.concatenate([q, t, s[..., None]], -1)
 
 
-def sim3_log(S):
-    S = np.asarray(S, dtype=np.float64)
+def sim3_log(S, dtype=np.float64):
+    S = np.asarray(S, dtype=dtype)
+    one = dtype(1)
     s = S[..., 7]
     sigma = np.log(s)
     R = quat_to_R(S[..., :4])
@@ -165,7 +177,7 @@ def sim3_log(S):
         omega = f[..., None] * dR
         sg2 = sigma * sigma
         A0 = np.where(small_d, 0.5, (1 - np.cos(theta)) / th2)
-        B0 = np.where(small_d, 1.0 / 6.0, (theta - np.sin(theta)) / (th2 * theta))
+        B0 = np.where(small_d, one / 6, (theta - np.sin(theta)) / (th2 * theta))
         C1 = (s - 1) / sigma
         a = s * np.sin(theta)
         b = s * np.cos(theta)
@@ -176,15 +188,15 @@ def sim3_log(S):
         B = np.where(small_s, B0, B1)
         C = np.where(small_s, 1.0, C1)
     Om = skew(omega)
-    W = A[..., None, None] * Om + B[..., None, None] * (Om @ Om) + C[..., None, None] * np.eye(3)
-    ups = _solve3_lu(W, S[..., 4:7])
+    W = A[..., None, None] * Om + B[..., None, None] * (Om @ Om) + C[..., None, None] * np.eye(3, dtype=dtype)
+    ups = _solve3_lu(W, S[..., 4:7], dtype)
     return np.concatenate([omega, ups, sigma[..., None]], -1)
 
 
-def _solve3_lu(W, t):
+def _solve3_lu(W, t, dtype=np.float64):
     """W.lu().solve(t) of every 3x3 system: partial pivoting by rows, elimination and back substitution in Eigen's order."""
-    a = np.array(W, dtype=np.float64, copy=True).reshape(-1, 3, 3)
-    b = np.array(t, dtype=np.float64, copy=True).reshape(-1, 3)
+    a = np.array(W, dtype=dtype, copy=True).reshape(-1, 3, 3)
+    b = np.array(t, dtype=dtype, copy=True).reshape(-1, 3)
     r = np.arange(a.shape[0])
     for k in range(3):
         p = k + np.argmax(np.abs(a[:, k:, k]), axis=1)   # first maximum, as the strict > scan
@@ -206,14 +218,15 @@ def _solve3_lu(W, t):
     return x.reshape(np.shape(t))
 
 
-def edge_error(meas, Si, Sj):
-    return sim3_log(sim3_mul(sim3_mul(meas, Si), sim3_inverse(Sj)))
+def edge_error(meas, Si, Sj, dtype=np.float64):
+    meas, Si, Sj = (np.asarray(a, dtype=dtype) for a in (meas, Si, Sj))
+    return sim3_log(sim3_mul(sim3_mul(meas, Si), sim3_inverse(Sj)), dtype)
 
 
-def oplus(est, upd, fix_scale):
-    upd = np.array(upd, dtype=np.float64, copy=True)
+def oplus(est, upd, fix_scale, dtype=np.float64):
+    upd = np.array(upd, dtype=dtype, copy=True)
     upd[..., 6] = np.where(fix_scale, 0.0, upd[..., 6])
-    return sim3_mul(sim3_exp(upd), est)
+    return sim3_mul(sim3_exp(upd, dtype), np.asarray(est, dtype=dtype))
 
 
 @dataclass
@@ -225,43 +238,45 @@ class PgoGraph:
     measurement: np.ndarray   # [E, 8]
 
 
-def errors(g: PgoGraph, est):
+def errors(g: PgoGraph, est, dtype=np.float64):
     i, j = g.edge_ij[:, 0], g.edge_ij[:, 1]
-    return edge_error(g.measurement, est[i], est[j])
+    return edge_error(g.measurement, est[i], est[j], dtype)
 
 
-def jacobians(g: PgoGraph, est):
-    """Numeric Jacobians [E, 7, 7] of both sides (zero for a fixed side), delta 1e-9, g2o's push / oplus / pop."""
+def jacobians(g: PgoGraph, est, dtype=np.float64):
+    """Numeric Jacobians [E, 7, 7] of both sides (zero for a fixed side), delta 1e-9, g2o's push / oplus / pop.  With
+    np.longdouble the same central difference (the same float64 delta) is taken in extended precision."""
     i, j = g.edge_ij[:, 0], g.edge_ij[:, 1]
     E = len(i)
-    delta = 1e-9
-    scalar = 1.0 / (2 * delta)
-    Ji = np.zeros((E, 7, 7))
-    Jj = np.zeros((E, 7, 7))
+    est = np.asarray(est, dtype=dtype)
+    delta = dtype(1e-9)
+    scalar = dtype(1) / (2 * delta)
+    Ji = np.zeros((E, 7, 7), dtype=dtype)
+    Jj = np.zeros((E, 7, 7), dtype=dtype)
     for d in range(7):
-        add = np.zeros((E, 7))
+        add = np.zeros((E, 7), dtype=dtype)
         add[:, d] = delta
-        ep = edge_error(g.measurement, oplus(est[i], add, g.fix_scale[i]), est[j])
-        em = edge_error(g.measurement, oplus(est[i], -add, g.fix_scale[i]), est[j])
+        ep = edge_error(g.measurement, oplus(est[i], add, g.fix_scale[i], dtype), est[j], dtype)
+        em = edge_error(g.measurement, oplus(est[i], -add, g.fix_scale[i], dtype), est[j], dtype)
         Ji[:, :, d] = scalar * (ep - em)
-        ep = edge_error(g.measurement, est[i], oplus(est[j], add, g.fix_scale[j]))
-        em = edge_error(g.measurement, est[i], oplus(est[j], -add, g.fix_scale[j]))
+        ep = edge_error(g.measurement, est[i], oplus(est[j], add, g.fix_scale[j], dtype), dtype)
+        em = edge_error(g.measurement, est[i], oplus(est[j], -add, g.fix_scale[j], dtype), dtype)
         Jj[:, :, d] = scalar * (ep - em)
     Ji[g.fixed[i]] = 0
     Jj[g.fixed[j]] = 0
     return Ji, Jj
 
 
-def linearize(g: PgoGraph, est):
+def linearize(g: PgoGraph, est, dtype=np.float64):
     """chi2, H (dense, free vertices in array order) and b = -J^T e."""
     free = np.flatnonzero(~g.fixed)
     sys = -np.ones(len(g.fixed), dtype=np.int64)
     sys[free] = np.arange(len(free))
-    e = errors(g, est)
-    Ji, Jj = jacobians(g, est)
+    e = errors(g, est, dtype)
+    Ji, Jj = jacobians(g, est, dtype)
     N = 7 * len(free)
-    H = np.zeros((N, N))
-    b = np.zeros(N)
+    H = np.zeros((N, N), dtype=dtype)
+    b = np.zeros(N, dtype=dtype)
     for k, (vi, vj) in enumerate(g.edge_ij):
         Js = ((sys[vi], Ji[k]), (sys[vj], Jj[k]))
         for a, Ja in Js:
@@ -272,7 +287,27 @@ def linearize(g: PgoGraph, est):
                 if c < 0:
                     continue
                 H[7 * a:7 * a + 7, 7 * c:7 * c + 7] += Ja.T @ Jc
-    return float(np.sum(e * e)), H, b
+    chi2 = np.sum(e * e)
+    return (float(chi2) if dtype == np.float64 else chi2), H, b
+
+
+def solve_ld(A, b, sweeps=3):
+    """x = A^-1 b to extended precision: an LU solve in float64, then iterative refinement with the residual b - A x computed
+    in np.longdouble (A and b taken exactly as given).  Asserts that the refined residual is <= 1e-17 of |A| |x| + |b|
+    (infinity norms), which needs kappa(A) well below 1 / 2^-53.  Returns x as np.longdouble."""
+    import scipy.linalg as sla
+    require_extended()
+    A_ld, b_ld = np.asarray(A, dtype=np.longdouble), np.asarray(b, dtype=np.longdouble)
+    lu = sla.lu_factor(np.asarray(A, dtype=np.float64))
+    x = sla.lu_solve(lu, np.asarray(b, dtype=np.float64)).astype(np.longdouble)
+    for _ in range(sweeps):
+        r = b_ld - A_ld @ x
+        x = x + sla.lu_solve(lu, r.astype(np.float64)).astype(np.longdouble)
+    r = b_ld - A_ld @ x
+    scale = np.abs(A_ld).sum(axis=1).max() * np.abs(x).max() + np.abs(b_ld).max()
+    rel = np.abs(r).max() / scale if scale > 0 else np.longdouble(0)
+    assert rel <= 1e-17, f"solve_ld: refined residual {float(rel):.3g} relative"
+    return x
 
 
 def _assemble_sparse(g, sys, Ji, Jj, e, N):
@@ -304,7 +339,10 @@ class PgoSolution:
     chi2_final: float
 
 
-def optimize(g: PgoGraph, iterations=20, lambda_init=1e-16) -> PgoSolution:
+def optimize(g: PgoGraph, iterations=20, lambda_init=1e-16, trace=None, jacobian_dtype=np.float64) -> PgoSolution:
+    """g2o's Levenberg-Marquardt; `trace`, a list, receives (iteration, rho, lambda of the trial, accepted) per trial.
+    jacobian_dtype=np.longdouble takes the numeric Jacobians in extended precision (rounded to float64 for the solve): the
+    distance between the two runs measures how far the Jacobians' float64 rounding alone moves the result."""
     import scipy.sparse as sp
     import scipy.sparse.linalg as spla
     est = g.estimate.astype(np.float64).copy()
@@ -321,7 +359,7 @@ def optimize(g: PgoGraph, iterations=20, lambda_init=1e-16) -> PgoSolution:
         if chi2_initial is None:
             chi2_initial = current
         ini = current
-        Ji, Jj = jacobians(g, est)
+        Ji, Jj = (J.astype(np.float64) for J in jacobians(g, est, jacobian_dtype))
         H, b = _assemble_sparse(g, sys, Ji, Jj, e, N)
         if it == 0:
             lam, ni, n_bad = lambda_init, 2.0, 0
@@ -337,6 +375,8 @@ def optimize(g: PgoGraph, iterations=20, lambda_init=1e-16) -> PgoSolution:
             temp = float(np.sum(et * et)) if ok2 else np.finfo(np.float64).max
             scale = float(np.dot(x, lam * x + b)) + 1e-3
             rho = (current - temp) / scale
+            if trace is not None:
+                trace.append((it, rho, lam, bool(rho > 0 and np.isfinite(temp))))
             if rho > 0 and np.isfinite(temp):
                 alpha = 1.0 - (2 * rho - 1) ** 3
                 alpha = min(alpha, 2.0 / 3.0)

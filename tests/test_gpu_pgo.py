@@ -56,7 +56,7 @@ def test_optimize_matches_numpy(solver, n, mono):
     ref = pn.optimize(_np(g))
     # Once the chi2 decrease reaches rounding level, accepting or rejecting a trial depends on the last bits of two chi2 sums;
     # the central differences (delta 1e-9) turn ulp differences of the device's and the host's exp / log / sin / cos / acos into
-    # ~5e-8 relative Jacobian noise, and the weakly constrained directions of a long chain amplify it.
+    # ~1e-6 relative Jacobian noise, and the weakly constrained directions of a long chain amplify it.
     assert abs(res.iterations - ref.iterations) <= 1
     if n <= 300:
         assert (res.iterations, res.trials) == (ref.iterations, ref.trials)

@@ -144,3 +144,164 @@ def test_map_over_limit_is_refused_and_untouched():
         assert h.mp_positions().tobytes() == before_x
         assert h.change_index() == 0
         assert h.normal_updates().sum() == 0
+
+
+# ---- the extended-precision reference (pgo_numpy's dtype path and solve_ld) ----
+
+def test_platform_has_extended_long_double():
+    pn.require_extended()    # fails, never skips: the stage tests need an 80-bit reference
+
+
+def _golden_graph(golden_dir):
+    z = np.load(golden_dir / "pgo_f64_small.npz")
+    return z, pn.PgoGraph(z["estimate"], z["fixed"], z["fix_scale"], z["edge_ij"], z["measurement"])
+
+
+def test_float64_reference_unchanged_bit_for_bit(golden_dir):
+    # written once (tests/golden/make_pgo_golden.py) by the float64-only module, before it took a dtype
+    z, G = _golden_graph(golden_dir)
+    chi2, H, b = pn.linearize(G, G.estimate)
+    assert np.float64(chi2).tobytes() == z["chi2"].tobytes()
+    assert H.dtype == np.float64 and H.tobytes() == z["H"].tobytes()
+    assert b.tobytes() == z["b"].tobytes()
+    sol = pn.optimize(G)
+    assert (sol.iterations, sol.trials) == (int(z["opt_iterations"]), int(z["opt_trials"]))
+    assert sol.estimate.tobytes() == z["opt_estimate"].tobytes()
+    assert np.float64(sol.chi2_final).tobytes() == z["opt_chi2_final"].tobytes()
+
+
+@pytest.mark.parametrize("mono", [True, False])
+def test_longdouble_linearization_agrees_with_float64(mono):
+    # the 50-keyframe loop graphs of test_gpu_pgo.py: float64 differs from long double only by the rounding the central
+    # differences amplify (measured up to ~2e-6 per block, median ~6e-7)
+    import pgo_cases as pc
+    m = sp.make_map(50, seed=11, mono=mono)
+    g, _, _ = sp.pack_loop(m)
+    G = pn.PgoGraph(g.estimate, g.fixed, g.fix_scale, g.edge_ij, g.measurement)
+    c64, H64, b64 = pn.linearize(G, G.estimate)
+    cld, Hld, bld = pn.linearize(G, G.estimate, np.longdouble)
+    assert Hld.dtype == np.longdouble and bld.dtype == np.longdouble
+    assert abs(c64 - float(cld)) <= 1e-13 * float(cld)
+    nf = H64.shape[0] // 7
+    eh, eb = pc.block_errors(H64, Hld, nf), pc.block_errors(b64, bld, nf)
+    assert eh.max() < 2e-5 and np.median(eh) < 5e-6, (eh.max(), np.median(eh))
+    assert eb.max() < 2e-5, eb.max()
+    assert eh.max() > 1e-9       # the long-double path is not secretly float64
+    if not mono:
+        assert not np.any(Hld[6::7, :]) and not np.any(bld[6::7])
+
+
+def test_solve_ld_meets_its_residual_bound():
+    rng = np.random.default_rng(3)
+    Q, _ = np.linalg.qr(rng.normal(size=(60, 60)))
+    A = (Q * np.logspace(0, 6, 60)) @ Q.T         # SPD, condition number ~1e6, taken exactly as float64
+    A = 0.5 * (A + A.T)
+    b = rng.normal(size=60)
+    x = pn.solve_ld(A, b)                          # asserts the refined residual <= 1e-17 relative
+    assert x.dtype == np.longdouble
+    r = np.asarray(b, np.longdouble) - np.asarray(A, np.longdouble) @ x
+    assert float(np.abs(r).max()) <= 1e-17 * float(np.abs(A).sum(1).max() * np.abs(x).max())
+    x64 = np.linalg.solve(A, b)                    # a plain float64 solve is worse by about kappa * 2^-53
+    assert np.abs(x64 - x).max() > np.abs(np.asarray(x, np.float64) - x).max()
+
+
+# ---- the device's Sim3 header (csrc/pgo_sim3.h) compiled for the host ----
+
+OPS = {"exp": 0, "log": 1, "mul": 2, "inverse": 3, "map": 4, "edge_error": 5, "oplus": 6, "quat_to_R": 7, "R_to_quat": 8, "solve3": 9}
+OUT_W = {"exp": 8, "log": 7, "mul": 8, "inverse": 8, "map": 3, "edge_error": 7, "oplus": 8, "quat_to_R": 9, "R_to_quat": 4, "solve3": 3}
+
+
+def _hdr(op, a, b=None, c=None, flag=None):
+    from orb_slam3_study_kr_amd import capi
+    lib = capi.load_host_library()
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    n = a.shape[0]
+    arr = [None if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in (b, c)]
+    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
+    out = np.full((n, OUT_W[op]), np.nan)
+    p = lambda x, t: capi.ptr(x, t) if x is not None else None
+    rc = lib.osh_host_sim3_apply(OPS[op], n, p(a, capi.c_double_p), p(arr[0], capi.c_double_p), p(arr[1], capi.c_double_p),
+                                 p(fl, capi.c_uint8_p), capi.ptr(out, capi.c_double_p))
+    assert rc == 0
+    return out
+
+
+def _rel(x, ref):
+    x, ref = np.asarray(x, np.longdouble), np.asarray(ref, np.longdouble)
+    return float(np.abs(x - ref).max() / max(np.abs(ref).max(), 1e-300))
+
+
+def test_header_exp_log_every_branch_against_long_double():
+    import pgo_cases as pc
+    table = pc.branch_table()
+    U = np.array([u for _, u in table])
+    S_ld = pn.sim3_exp(U.astype(np.longdouble), np.longdouble)
+    S_h, S_64 = _hdr("exp", U), pn.sim3_exp(U)
+    S_in = S_ld.astype(np.float64)
+    L_ld = pn.sim3_log(S_in.astype(np.longdouble), np.longdouble)
+    L_h, L_64 = _hdr("log", S_in), pn.sim3_log(S_in)
+    for k, (name, u) in enumerate(table):
+        # same branch, same formula: the host libm and numpy's differ from long double by a few ulps, amplified alike
+        for got, ref, ref64 in ((S_h[k], S_ld[k], S_64[k]), (L_h[k], L_ld[k], L_64[k])):
+            e_h, e_64 = _rel(got, ref), _rel(ref64, ref)
+            assert e_h <= max(8 * e_64, 4e-15), (name, e_h, e_64)
+    # the table reaches all four branches of both
+    th, sg = np.linalg.norm(U[:, :3], axis=1), U[:, 6]
+    d = np.cos(th)
+    assert {(bool(a), bool(b)) for a, b in zip(th < 1e-5, np.abs(sg) < 1e-5)} == {(True, True), (True, False), (False, True), (False, False)}
+    assert {(bool(a), bool(b)) for a, b in zip(d > 1 - 1e-5, np.abs(sg) < 1e-5)} == {(True, True), (True, False), (False, True), (False, False)}
+
+
+def test_header_edge_error_and_oplus_against_long_double():
+    import pgo_cases as pc
+    rng = np.random.default_rng(5)
+    table = pc.branch_table()
+    n = len(table)
+    Si, Sj = pc.random_sim3(rng, n), pc.random_sim3(rng, n)
+    meas = np.array([pc.measurement_for(u, Si[k], Sj[k]) for k, (_, u) in enumerate(table)])
+    e_h = _hdr("edge_error", meas, Si, Sj)
+    e_ld = pn.edge_error(meas, Si, Sj, np.longdouble)
+    e_64 = pn.edge_error(meas, Si, Sj)
+    for k, (name, u) in enumerate(table):
+        assert _rel(e_h[k], e_ld[k]) <= max(8 * _rel(e_64[k], e_ld[k]), 1e-13), name
+        # the measurement was built to put the error at u (up to the O(theta^2) of log's small-angle branch)
+        assert _rel(e_h[k], u) < 1e-3, name
+    upd = rng.normal(size=(n, 7)) * 0.3
+    fs = np.arange(n) % 2 == 1
+    o_h, o_ld, o_64 = _hdr("oplus", Si, upd, flag=fs), pn.oplus(Si, upd, fs, np.longdouble), pn.oplus(Si, upd, fs)
+    assert np.all(o_h[fs, 7] == Si[fs, 7])
+    for k in range(n):
+        assert _rel(o_h[k], o_ld[k]) <= max(8 * _rel(o_64[k], o_ld[k]), 4e-15)
+
+
+def test_header_libm_free_operations_match_float64_reference_bit_for_bit():
+    import pgo_cases as pc
+    rng = np.random.default_rng(6)
+    n = 64
+    a, b = pc.random_sim3(rng, n), pc.random_sim3(rng, n)
+    p = rng.normal(size=(n, 3)) * 4
+    np.testing.assert_array_equal(_hdr("mul", a, b), pn.sim3_mul(a, b))
+    np.testing.assert_array_equal(_hdr("inverse", a), pn.sim3_inverse(a))
+    np.testing.assert_array_equal(_hdr("map", a, p), pn.sim3_map(a, p))
+    np.testing.assert_array_equal(_hdr("quat_to_R", a[:, :4]), pn.quat_to_R(a[:, :4]).reshape(n, 9))
+    # R_to_quat on both branches: trace > 0 and trace <= 0 with the largest diagonal entry at 0, 1 and 2
+    R = pn.quat_to_R(a[:, :4])
+    tr = np.trace(R, axis1=1, axis2=2)
+    big = np.argmax(np.diagonal(R, axis1=1, axis2=2), axis=1)
+    assert np.any(tr > 0) and all(np.any((tr <= 0) & (big == i)) for i in range(3))
+    np.testing.assert_array_equal(_hdr("R_to_quat", R.reshape(n, 9)), pn.R_to_quat(R))
+    np.testing.assert_array_equal(_hdr("R_to_quat", R.reshape(n, 9)), pn._R_to_quat_vec(R))
+    # the 3x3 LU of log(): every pivot order, including the swaps
+    W = rng.normal(size=(n, 3, 3))
+    for k in range(6):
+        W[k] = W[k][[(k + r) % 3 for r in range(3)]] * np.array([[1e-3], [1.0], [10.0]])
+    t = rng.normal(size=(n, 3))
+    np.testing.assert_array_equal(_hdr("solve3", W.reshape(n, 9), t), pn._solve3_lu(W, t))
+
+
+def test_header_rejects_unknown_op():
+    from orb_slam3_study_kr_amd import capi
+    lib = capi.load_host_library()
+    a = np.zeros(8)
+    out = np.zeros(8)
+    assert lib.osh_host_sim3_apply(10, 1, capi.ptr(a, capi.c_double_p), None, None, None, capi.ptr(out, capi.c_double_p)) == -1
