@@ -45,6 +45,12 @@ class Optimizer {
   // src/Optimizer.cc:1786-2117: the same problem for a map merge, built from three keyframe lists
   void static OptimizeEssentialGraph(KeyFrame* pCurKF, std::vector<KeyFrame*>& vpFixedKFs, std::vector<KeyFrame*>& vpFixedCorrectedKFs,
                                      std::vector<KeyFrame*>& vpNonFixedKFs, std::vector<MapPoint*>& vpNonCorrectedMPs);
+  // src/Optimizer.cc:5300-5596 (csrc/host/OptimizerEssentialGraph4DoF.cc): the 4-DoF pose graph of an inertial loop correction
+  // (yaw and translation per keyframe), optimize(20) on the device, then poses SE3f(Rcw, tcw) and the map points through their
+  // reference keyframe.  Up to 4000 keyframes.
+  void static OptimizeEssentialGraph4DoF(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                         const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                         const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections);
   void static MergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, bool* pbStopFlag, Map* pMap, LoopClosing::KeyFrameAndPose& corrPoses);
 };
 }  // namespace ORB_SLAM3

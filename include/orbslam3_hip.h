@@ -437,6 +437,57 @@ int osh_pgo_solve(osh_lba_ctx* ctx, const osh_pgo_problem* problem, osh_pgo_resu
  * in array order, dense row-major (7 nf) x (7 nf) with both triangles filled; b[7 nf]).  For small graphs (nf <= 512). */
 int osh_pgo_linearize(osh_lba_ctx* ctx, const osh_pgo_problem* problem, double* H, double* b, double* chi2);
 
+/*
+ * The solver part of Optimizer::OptimizeEssentialGraph4DoF (src/Optimizer.cc:5300-5596), the inertial loop closure: one
+ * VertexPose4DoF per keyframe (ImuCamPose, update (yaw, tx, ty, tz) through UpdateW, include/G2oTypes.h:155-189,
+ * src/G2oTypes.cc:222-256), Edge4DoF with a diagonal information and no robust kernel (include/G2oTypes.h:817-845), numeric
+ * Jacobians (delta 1e-9, push / oplus / pop, so a vertex's DR and update count belong to its state), Levenberg-Marquardt as
+ * optimization_algorithm_levenberg.cpp:99-169 runs it.  The limits, the solve modes and the factorisation are the Sim3
+ * graph's.  Matrices are 3x3 row-major.
+ */
+typedef struct osh_pgo4_problem {
+  int32_t n_vertices;
+  const double* Rwb;          /* [n*9] initial body rotation (also Rwb0)                                         */
+  const double* twb;          /* [n*3]                                                                           */
+  const double* Rcw;          /* [n*9] the raw camera pose, used until a vertex's first update                   */
+  const double* tcw;          /* [n*3]                                                                           */
+  const double* Rcb;          /* [n*9] mImuCalib.mTcb                                                            */
+  const double* tcb;          /* [n*3]                                                                           */
+  const uint8_t* fixed;       /* [n] setFixed(true)                                                              */
+  int32_t n_edges;
+  const int32_t* edge_ij;     /* [n_edges*2] vertex 0 (i) and vertex 1 (j) of every Edge4DoF                        */
+  const double* dR;           /* [n_edges*9] dRij                                                                */
+  const double* dt;           /* [n_edges*3] dtij                                                                */
+  double info_diag[6];        /* diagonal of the information (the reference: 1e3 1e3 1 1 1 1), finite and >= 0   */
+  int32_t iterations;         /* optimize(iterations)                                                            */
+  double lambda_init;         /* > 0: setUserLambdaInit; 0: g2o's computeLambdaInit, 1e-5 * max diag(H)          */
+  int32_t solve_mode;         /* OSH_PGO_SOLVE_ENVELOPE / OSH_PGO_SOLVE_DENSE                                     */
+} osh_pgo4_problem;
+
+typedef struct osh_pgo4_result {
+  double* Rcw;                /* [n*9] camera poses after optimize() (the fixed vertex's raw pose unchanged)      */
+  double* tcw;                /* [n*3]                                                                           */
+  double* Rwb;                /* optional [n*9] body poses after optimize(), or NULL                             */
+  double* twb;                /* optional [n*3], or NULL                                                         */
+  int32_t iterations;         /* LM iterations run                                                               */
+  int32_t trials;             /* LM trials over all iterations                                                   */
+  double chi2_initial;        /* activeChi2 before the first iteration                                           */
+  double chi2_final;          /* activeChi2 of the returned poses                                                */
+  double lambda_init_used;    /* the first iteration's lambda                                                    */
+  int64_t envelope_entries;   /* scalar entries of the upper envelope of the reduced system                     */
+  int32_t envelope_tiles;     /* 32x32 tiles stored                                                              */
+  int32_t tall_columns;       /* free vertices whose envelope column reaches more than 64 rows above the diagonal */
+  int32_t status;
+} osh_pgo4_result;
+
+/* initializeOptimization + optimize(iterations) of one 4-DoF pose graph on the context's device and stream.  Graphs beyond
+ * OSH_PGO_MAX_VERTICES free vertices or OSH_PGO_MAX_ENV_TILES envelope tiles, and invalid problems, are refused with the
+ * result untouched before any device work. */
+int osh_pgo4_solve(osh_lba_ctx* ctx, const osh_pgo4_problem* problem, osh_pgo4_result* result);
+/* Diagnostic: the first linearisation (chi2 at the initial poses, H = J^T Omega J and b = -J^T Omega e of the free vertices
+ * in array order, dense row-major (4 nf) x (4 nf) with both triangles filled; b[4 nf]).  For small graphs (nf <= 512). */
+int osh_pgo4_linearize(osh_lba_ctx* ctx, const osh_pgo4_problem* problem, double* H, double* b, double* chi2);
+
 /* --------------------------------------------------------- ORB matching API */
 /*
  * Nearest / second-nearest 256-bit Hamming search (the candidate loops of

@@ -269,6 +269,17 @@ int osh_host_pgo_pack_merge(osh_host_graph* g, const osh_host_merge* merge, osh_
 /* ORB_SLAM3::Optimizer::OptimizeEssentialGraph, either overload */
 int osh_host_pgo_run(osh_host_graph* g, const osh_host_loop* loop);
 int osh_host_pgo_run_merge(osh_host_graph* g, const osh_host_merge* merge);
+/* Optimizer::OptimizeEssentialGraph4DoF (csrc/host/OptimizerEssentialGraph4DoF.cc) on the same stand-in map: the graph from
+ * osh_host_pgo_set_graph (prev_kf also sets mNextKF), mImuCalib from osh_host_graph_set_inertial.  osh_host_loop's fix_scale is
+ * not read.  The walk alone (0, or -1 when a capacity is too small; arrays as osh_pgo4_problem) and the call itself. */
+typedef struct osh_host_pgo4_out {
+  int32_t max_vertices, max_edges;
+  int32_t n_vertices, n_edges, n_free;
+  int64_t* vertex_kf_id; double* Rwb; double* twb; double* Rcw; double* tcw; double* Rcb; double* tcb; uint8_t* fixed;
+  int32_t* edge_ij; double* dR; double* dt;
+} osh_host_pgo4_out;
+int osh_host_pgo4_pack(osh_host_graph* g, const osh_host_loop* loop, osh_host_pgo4_out* out);
+int osh_host_pgo4_run(osh_host_graph* g, const osh_host_loop* loop);
 /* UpdateNormalAndDepth calls on map point mp_index (osh_host_mp_normal_updates) and pose writes (osh_host_kf_pose_sets) count the
  * write-back; osh_host_map_change_index counts IncreaseChangeIndex. */
 
@@ -289,6 +300,23 @@ int osh_host_pgo_run_merge(osh_host_graph* g, const osh_host_merge* merge);
 #define OSH_SIM3_R_TO_QUAT  8
 #define OSH_SIM3_SOLVE3     9
 int osh_host_sim3_apply(int32_t op, int32_t n, const double* a, const double* b, const double* c, const uint8_t* flag, double* out);
+
+/* csrc/pgo4_se3.h (the 4-DoF pose graph's algebra) compiled for the host, applied to n items.  A vertex state is 34 doubles
+ * (DR, Rwb, twb, Rcw, tcw row-major, then its), its constants 21 (Rwb0, Rcb, tcb), an edge's measurement 12 (dR, dt).
+ *   EXP         a[3] (x y z)                               -> out[9]   ExpSO3
+ *   LOG         a[9]                                       -> out[3]   LogSO3
+ *   NORMALIZE   a[9]                                       -> out[9]   NormalizeRotation
+ *   UPDATE      a = state[34], b = const[21], c = u[4]     -> out[34]  VertexPose4DoF::oplusImpl
+ *   EDGE_ERROR  a = meas[12], b = state_i, c = state_j      -> out[6]   Edge4DoF::computeError
+ * Returns 0, or -1 for an unknown op or a missing array. */
+#define OSH_PGO4_EXP        0
+#define OSH_PGO4_LOG        1
+#define OSH_PGO4_NORMALIZE  2
+#define OSH_PGO4_UPDATE     3
+#define OSH_PGO4_EDGE_ERROR 4
+int osh_host_pgo4_apply(int32_t op, int32_t n, const double* a, const double* b, const double* c, double* out);
+/* out[0] = sizeof(osh_pgo4_problem), out[1] = sizeof(osh_pgo4_result) as the C compiler lays them out */
+void osh_host_pgo4_sizes(int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -107,6 +107,27 @@ class PgoResult(C.Structure):
     ]
 
 
+class Pgo4Problem(C.Structure):
+    """``osh_pgo4_problem`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("n_vertices", C.c_int32), ("Rwb", c_double_p), ("twb", c_double_p), ("Rcw", c_double_p), ("tcw", c_double_p),
+        ("Rcb", c_double_p), ("tcb", c_double_p), ("fixed", c_uint8_p), ("n_edges", C.c_int32), ("edge_ij", C.POINTER(C.c_int32)),
+        ("dR", c_double_p), ("dt", c_double_p), ("info_diag", C.c_double * 6), ("iterations", C.c_int32), ("lambda_init", C.c_double),
+        ("solve_mode", C.c_int32),
+    ]
+
+
+class Pgo4Result(C.Structure):
+    """``osh_pgo4_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("Rcw", c_double_p), ("tcw", c_double_p), ("Rwb", c_double_p), ("twb", c_double_p), ("iterations", C.c_int32),
+        ("trials", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("lambda_init_used", C.c_double),
+        ("envelope_entries", C.c_int64), ("envelope_tiles", C.c_int32), ("tall_columns", C.c_int32), ("status", C.c_int32),
+    ]
+
+
 OSH_PGO_MAX_VERTICES = 4000
 OSH_PGO_SOLVE_ENVELOPE = 0
 OSH_PGO_SOLVE_DENSE = 1
@@ -273,6 +294,8 @@ _SIGNATURES = {
     "osh_orb_distance_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, c_int32_p]),
     "osh_pgo_solve": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), C.POINTER(PgoResult)]),
     "osh_pgo_linearize": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), c_double_p, c_double_p, c_double_p]),
+    "osh_pgo4_solve": (C.c_int, [C.c_void_p, C.POINTER(Pgo4Problem), C.POINTER(Pgo4Result)]),
+    "osh_pgo4_linearize": (C.c_int, [C.c_void_p, C.POINTER(Pgo4Problem), c_double_p, c_double_p, c_double_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -396,6 +419,16 @@ class HostPgoOut(C.Structure):
     ]
 
 
+class HostPgo4Out(C.Structure):
+    """``osh_host_pgo4_out`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [
+        ("max_vertices", C.c_int32), ("max_edges", C.c_int32), ("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("n_free", C.c_int32),
+        ("vertex_kf_id", c_int64_p), ("Rwb", c_double_p), ("twb", c_double_p), ("Rcw", c_double_p), ("tcw", c_double_p),
+        ("Rcb", c_double_p), ("tcb", c_double_p), ("fixed", c_uint8_p), ("edge_ij", c_int32_p), ("dR", c_double_p), ("dt", c_double_p),
+    ]
+
+
 _HOST_SIGNATURES.update({
     "osh_host_pgo_set_graph": (C.c_int, [C.c_void_p, c_int32_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_int32_p,
                                          c_int32_p, c_uint8_p, c_int32_p, c_int64_p, c_int64_p]),
@@ -405,8 +438,15 @@ _HOST_SIGNATURES.update({
     "osh_host_pgo_run": (C.c_int, [C.c_void_p, C.POINTER(HostLoop)]),
     "osh_host_pgo_run_merge": (C.c_int, [C.c_void_p, C.POINTER(HostMerge)]),
     "osh_host_sim3_apply": (C.c_int, [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_uint8_p, c_double_p]),
+    "osh_host_pgo4_pack": (C.c_int, [C.c_void_p, C.POINTER(HostLoop), C.POINTER(HostPgo4Out)]),
+    "osh_host_pgo4_run": (C.c_int, [C.c_void_p, C.POINTER(HostLoop)]),
+    "osh_host_pgo4_apply": (C.c_int, [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "osh_host_pgo4_sizes": (None, [c_int64_p]),
 })
 HOST_EXPORTED_SYMBOLS = tuple(_HOST_SIGNATURES)
+
+# osh_host_pgo4_apply operations (include/orbslam3_hip_host.h)
+OSH_PGO4_EXP, OSH_PGO4_LOG, OSH_PGO4_NORMALIZE, OSH_PGO4_UPDATE, OSH_PGO4_EDGE_ERROR = range(5)
 
 _lib = None
 _host_lib = None

@@ -208,6 +208,28 @@ struct PgoPack {
 void PackEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
                         const LoopClosing::KeyFrameAndPose& CorrectedSim3, const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections,
                         const bool& bFixScale, PgoPack& pk);
+// The 4-DoF graph of Optimizer::OptimizeEssentialGraph4DoF: 3x3 matrices row-major, vertices in keyframe-id order.
+struct Pgo4Pack {
+  std::vector<KeyFrame*> vpVertexKF;
+  std::vector<int> vertexOfId;                               // mnId -> vertex (-1: none)
+  std::vector<double> Rwb, twb, Rcw, tcw, Rcb, tcb, dR, dt;  // [n*9], [n*3], ... [E*9], [E*3]
+  std::vector<uint8_t> fixed;
+  std::vector<int32_t> edge_ij;
+  std::vector<g2o::Sim3> vScw;                               // by mnId
+  int nFree = 0;
+  void fill(osh_pgo4_problem& p) const {
+    p.n_vertices = (int32_t)vpVertexKF.size(); p.Rwb = Rwb.data(); p.twb = twb.data(); p.Rcw = Rcw.data(); p.tcw = tcw.data();
+    p.Rcb = Rcb.data(); p.tcb = tcb.data(); p.fixed = fixed.data();
+    p.n_edges = (int32_t)(edge_ij.size() / 2); p.edge_ij = edge_ij.data(); p.dR = dR.data(); p.dt = dt.data();
+    // matLambda of src/Optimizer.cc:5372-5375: (0, 0) is set twice, (2, 2) never
+    const double info[6] = {1e3, 1e3, 1.0, 1.0, 1.0, 1.0};
+    for (int k = 0; k < 6; ++k) p.info_diag[k] = info[k];
+    p.iterations = 20; p.lambda_init = 0.0; p.solve_mode = OSH_PGO_SOLVE_ENVELOPE;   // no setUserLambdaInit: computeLambdaInit
+  }
+};
+void PackEssentialGraph4DoF(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                            const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                            const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections, Pgo4Pack& pk);
 void PackEssentialGraphMerge(KeyFrame* pCurKF, std::vector<KeyFrame*>& vpFixedKFs, std::vector<KeyFrame*>& vpFixedCorrectedKFs,
                              std::vector<KeyFrame*>& vpNonFixedKFs, PgoPack& pk);
 

@@ -1180,7 +1180,7 @@ extern "C" int osh_host_pgo_set_graph(osh_host_graph* g, const int32_t* parent, 
   for (int i = 0; i < n; ++i) {
     KeyFrame* kf = g->kfs[i].get();
     if (parent && parent[i] >= 0) { kf->mpParent = g->kfs[parent[i]].get(); kf->mpParent->mspChildrens.insert(kf); }
-    if (prev_kf && prev_kf[i] >= 0) kf->mPrevKF = g->kfs[prev_kf[i]].get();
+    if (prev_kf && prev_kf[i] >= 0) { kf->mPrevKF = g->kfs[prev_kf[i]].get(); kf->mPrevKF->mNextKF = kf; }
     if (b_imu) kf->bImu = b_imu[i] != 0;
   }
   std::vector<std::vector<std::pair<int, KeyFrame*>>> cov(n);
@@ -1284,5 +1284,33 @@ extern "C" int osh_host_pgo_run_merge(osh_host_graph* g, const osh_host_merge* m
   for (int k = 0; k < m->n_mps; ++k) mps.push_back(g->mps[m->mps[k]].get());
   CallTimer t;
   Optimizer::OptimizeEssentialGraph(g->kfs[m->cur].get(), f, fc, nf, mps);
+  return 0;
+}
+
+extern "C" int osh_host_pgo4_pack(osh_host_graph* g, const osh_host_loop* l, osh_host_pgo4_out* out) {
+  LoopArgs a = loop_args(g, l);
+  Pgo4Pack pk;
+  PackEssentialGraph4DoF(&g->map, g->kfs[l->loop].get(), g->kfs[l->cur].get(), a.noncorrected, a.corrected, a.connections, pk);
+  out->n_vertices = (int32_t)pk.vpVertexKF.size();
+  out->n_edges = (int32_t)(pk.edge_ij.size() / 2);
+  out->n_free = pk.nFree;
+  if (out->n_vertices > out->max_vertices || out->n_edges > out->max_edges) return -1;
+  for (int v = 0; v < out->n_vertices; ++v) {
+    if (out->vertex_kf_id) out->vertex_kf_id[v] = (int64_t)pk.vpVertexKF[v]->mnId;
+    if (out->fixed) out->fixed[v] = pk.fixed[v];
+  }
+  const std::pair<const std::vector<double>*, double*> arrays[] = {{&pk.Rwb, out->Rwb}, {&pk.twb, out->twb}, {&pk.Rcw, out->Rcw},
+                                                                    {&pk.tcw, out->tcw}, {&pk.Rcb, out->Rcb}, {&pk.tcb, out->tcb},
+                                                                    {&pk.dR, out->dR},   {&pk.dt, out->dt}};
+  for (const auto& a2 : arrays)
+    if (a2.second) std::copy(a2.first->begin(), a2.first->end(), a2.second);
+  if (out->edge_ij) std::copy(pk.edge_ij.begin(), pk.edge_ij.end(), out->edge_ij);
+  return 0;
+}
+
+extern "C" int osh_host_pgo4_run(osh_host_graph* g, const osh_host_loop* l) {
+  LoopArgs a = loop_args(g, l);
+  CallTimer t;
+  Optimizer::OptimizeEssentialGraph4DoF(&g->map, g->kfs[l->loop].get(), g->kfs[l->cur].get(), a.noncorrected, a.corrected, a.connections);
   return 0;
 }

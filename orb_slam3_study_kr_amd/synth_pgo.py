@@ -15,7 +15,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import capi
-from .pgo import PgoGraph
+from .pgo import INFO_4DOF, Pgo4Graph, PgoGraph
 
 MIN_FEAT = 100
 
@@ -367,6 +367,192 @@ def pack_merge(m: SynthPgoMap, fixed, fixed_corrected, non_fixed, kf_pose=None):
     return g, kfs, vScw, vCorr, good, badp
 
 
+# ---- the inertial loop of Optimizer::OptimizeEssentialGraph4DoF ----
+def _quat_to_R(q):
+    """Eigen's Quaternion::toRotationMatrix."""
+    x, y, z, w = q
+    tx, ty, tz = 2 * x, 2 * y, 2 * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz, tyy, tyz, tzz = tx * x, ty * x, tz * x, ty * y, tz * y, tz * z
+    return np.array([[1 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1 - (txx + tzz), tyz - twx],
+                     [txz - twy, tyz + twx, 1 - (txx + tyy)]])
+
+
+def _rz(a):
+    c, s = np.cos(a), np.sin(a)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+@dataclass
+class SynthInertialMap(SynthPgoMap):
+    """An inertial loop map: SynthPgoMap plus mImuCalib.mTcb (float, as the keyframes keep it)."""
+    Rcb: np.ndarray = None               # [3, 3] float32
+    tcb: np.ndarray = None               # [3] float32
+
+    def next_kf(self, i):
+        nxt = np.flatnonzero(self.prev_kf == i)
+        return int(nxt[0]) if len(nxt) else -1
+
+
+def make_inertial_loop(n_kf: int, seed: int = 0, earlier_loop: bool = False, rp_noise: float = 0.0, neighbourhood: int = 4,
+                       band: int = 6, id_gap: bool = True, n_points: int = 0) -> SynthInertialMap:
+    """Keyframes of an IMU session on a horizontal circle (world z up), a camera mounted on the body by a Tcb that is not the
+    identity, and odometry that drifts in yaw and translation only, as visual-inertial odometry does (gravity keeps roll and
+    pitch).  rp_noise > 0 adds roll / pitch noise per step (radians), which the 4-DoF graph cannot remove.  The loop and its
+    LoopConnections / CorrectedSim3 / NonCorrectedSim3 are laid out as in make_map."""
+    rng = np.random.default_rng(seed)
+    n = n_kf
+    radius = max(2.0, 0.05 * n)
+    theta = 2 * np.pi * np.arange(n) / n
+    Rwb_t = [_rz(th + np.pi / 2) for th in theta]
+    twb_t = [np.array([radius * np.cos(th), radius * np.sin(th), 0.1 * np.sin(3 * th)]) for th in theta]
+    # camera: z forward along the body x, x right, y down; tilted a little and offset on the body
+    Rbc = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]]) @ _rodrigues(np.array([0.03, -0.02, 0.05]))
+    tbc = np.array([0.06, -0.02, 0.015])
+    Rcb = Rbc.T.astype(np.float32)
+    tcb = (-Rbc.T @ tbc).astype(np.float32)
+    Rbc_f, tbc_f = Rcb.astype(np.float64).T, -Rcb.astype(np.float64).T @ tcb.astype(np.float64)
+    Rd, td = [Rwb_t[0]], [twb_t[0]]
+    for i in range(1, n):
+        Rrel = Rwb_t[i - 1].T @ Rwb_t[i]
+        trel = Rwb_t[i - 1].T @ (twb_t[i] - twb_t[i - 1])
+        Rrel = Rrel @ _rz(0.5 / n + rng.normal(0, 0.002))
+        if rp_noise > 0:
+            Rrel = Rrel @ _rodrigues(np.array([rng.normal(0, rp_noise), rng.normal(0, rp_noise), 0.0]))
+        trel = trel + rng.normal(0, 0.002, 3) + np.array([0.3 / n, 0.0, 0.0])
+        Rd.append(Rd[-1] @ Rrel)
+        td.append(td[-1] + Rd[-2] @ trel)
+    pose_qt = np.zeros((n, 7), dtype=np.float32)
+    true_qt = np.zeros((n, 7))
+    for i in range(n):
+        for R, t, out in ((Rd[i], td[i], pose_qt), (Rwb_t[i], twb_t[i], true_qt)):
+            Rwc, twc = R @ Rbc_f, R @ tbc_f + t
+            out[i, :4] = _rot_to_quat(Rwc.T)
+            out[i, 4:] = -Rwc.T @ twc
+    kf_id = np.array([i + i // 5 for i in range(n)] if id_gap else range(n), dtype=np.int64)
+    parent = np.arange(n, dtype=np.int32) - 1
+    cov = [[] for _ in range(n)]
+
+    def connect(a, b, w):
+        cov[a] = [(o, x) for o, x in cov[a] if o != b] + [(b, w)]
+        cov[b] = [(o, x) for o, x in cov[b] if o != a] + [(a, w)]
+
+    for i in range(n):
+        for d in range(1, band + 1):
+            if i + d < n:
+                connect(i, i + d, int(260 - 30 * d + rng.integers(-10, 11)))
+    cur, loop = n - 1, 1
+    near_cur = list(range(n - 1, n - 1 - neighbourhood, -1))
+    near_loop = list(range(0, neighbourhood + 1))
+    m = SynthInertialMap(kf_id=kf_id, pose_qt=pose_qt, true_qt=true_qt, parent=parent, cov=cov, loop_edges=[],
+                         prev_kf=np.arange(n, dtype=np.int32) - 1, b_imu=np.arange(n) >= 1, bad=np.zeros(n, dtype=bool),
+                         mp_pos=np.zeros((0, 3), np.float32), mp_ref=np.zeros(0, np.int32), mp_corrected_by=np.zeros(0, np.int64),
+                         mp_corrected_ref=np.zeros(0, np.int64), init_index=0, cur=cur, loop=loop, fix_scale=True, Rcb=Rcb, tcb=tcb)
+    for a in near_cur:
+        m.corrected[a] = np.concatenate([true_qt[a, :4], true_qt[a, 4:], [1.0]])
+        m.noncorrected[a] = sim3_from_pose(pose_qt[a])
+        conns = set()
+        for b in near_loop:
+            w = int(rng.integers(40, 250))
+            if a == cur and b == loop:
+                w = 60                      # below minFeat: kept by the (pCurKF, pLoopKF) exception
+            connect(a, b, w)
+            conns.add(b)
+        m.connections[a] = conns
+    m.connections[near_cur[1]].add(int(parent[near_cur[1]]))
+    connect(near_cur[1], int(parent[near_cur[1]]), 180)
+    if earlier_loop:
+        m.loop_edges.append((n // 2, 2))
+        m.loop_edges.append((3 * n // 4, n // 4))
+        connect(n // 2, 2, 150)
+    if n_points:
+        m.mp_ref = rng.integers(0, n, n_points).astype(np.int32)
+        pos = np.zeros((n_points, 3))
+        for k, r in enumerate(m.mp_ref):
+            Rwc, twc = Rd[r] @ Rbc_f, Rd[r] @ tbc_f + td[r]
+            pos[k] = twc + Rwc @ np.array([rng.normal(0, 1), rng.normal(0, 0.5), 3 + rng.random() * 4])
+        m.mp_pos = pos.astype(np.float32)
+        m.mp_corrected_by = np.zeros(n_points, np.int64)
+        m.mp_corrected_ref = np.zeros(n_points, np.int64)
+    return m
+
+
+def imu_pose_f32(qt, Rcb, tcb):
+    """KeyFrame::GetImuRotation / GetImuPosition from a float pose: Rwb = Rwc Rcb, twb = Rwc tcb + Owc, in float."""
+    f = np.float32
+    Rcw = _quat_to_R(np.asarray(qt[:4], f).astype(np.float64)).astype(f)
+    Rwc = Rcw.T
+    Owc = (-(Rwc @ np.asarray(qt[4:], f))).astype(f)
+    return (Rwc @ Rcb).astype(f), (Rwc @ tcb + Owc).astype(f)
+
+
+def pack_loop4(m: SynthInertialMap, kf_pose=None):
+    """src/Optimizer.cc:5300-5470 on the synthetic map: (Pgo4Graph, vertex keyframe indices, vScw by index).  Vertices are
+    sorted by mnId; the edge of a bad keyframe, which the reference would dereference as a null vertex, is skipped."""
+    pose = m.pose_qt if kf_pose is None else kf_pose
+    Rcb, tcb = m.Rcb.astype(np.float64), m.tcb.astype(np.float64)
+    vScw, entries = {}, []
+    for i in range(m.n):
+        if m.bad[i]:
+            continue
+        if i in m.corrected:
+            vScw[i] = m.corrected[i]
+            Swc = sim3_inverse(vScw[i])
+            Rwc, twc = _quat_to_R(Swc[:4]), Swc[4:7]
+            Rcw = Rwc.T
+            st = (Rwc @ Rcb, Rwc @ tcb + twc, Rcw, -Rcw @ twc)
+        else:
+            vScw[i] = sim3_from_pose(pose[i])
+            Rwb, twb = imu_pose_f32(pose[i], m.Rcb, m.tcb)
+            Rcw = _quat_to_R(np.asarray(pose[i][:4], np.float32).astype(np.float64)).astype(np.float32)
+            st = (Rwb.astype(np.float64), twb.astype(np.float64), Rcw.astype(np.float64),
+                  np.asarray(pose[i][4:], np.float32).astype(np.float64))
+        entries.append((i, st, i == m.loop))
+    order = sorted(range(len(entries)), key=lambda k: m.kf_id[entries[k][0]])
+    vof = {entries[k][0]: r for r, k in enumerate(order)}
+    kfs = [entries[k][0] for k in order]
+    sts = [entries[k][1] for k in order]
+    edges, dR, dt = [], [], []
+
+    def add(i, j, S):
+        if i in vof and j in vof:
+            edges.append((vof[i], vof[j]))
+            dR.append(_quat_to_R(S[:4]))
+            dt.append(S[4:7])
+
+    def nc(k):
+        return m.noncorrected[k] if k in m.noncorrected else vScw.get(k, np.array([0, 0, 0, 1, 0, 0, 0, 1.0]))
+
+    inserted = set()
+    for i in sorted(m.connections):
+        for j in sorted(m.connections[i]):
+            if (i != m.cur or j != m.loop) and m.weight(i, j) < MIN_FEAT:
+                continue
+            add(i, j, sim3_mul(vScw[i], sim3_inverse(vScw[j])))
+            inserted.add((min(m.kf_id[i], m.kf_id[j]), max(m.kf_id[i], m.kf_id[j])))
+    for i in range(m.n):
+        Siw = nc(i)
+        prev = int(m.prev_kf[i])
+        if prev >= 0:
+            add(i, prev, sim3_mul(Siw, sim3_inverse(nc(prev))))
+        loops = m.loop_set(i)
+        for L in sorted(loops):
+            if m.kf_id[L] < m.kf_id[i]:
+                add(i, L, sim3_mul(Siw, sim3_inverse(nc(L))))
+        ch, nxt = m.children(i), m.next_kf(i)
+        for k in m.covisibles_by_weight(i, MIN_FEAT):
+            if k != prev and k != nxt and k not in ch and k not in loops and not m.bad[k] and m.kf_id[k] < m.kf_id[i]:
+                if (min(m.kf_id[i], m.kf_id[k]), max(m.kf_id[i], m.kf_id[k])) in inserted:
+                    continue
+                add(i, k, sim3_mul(Siw, sim3_inverse(nc(k))))
+    g = Pgo4Graph(np.array([s[0] for s in sts]).reshape(-1, 3, 3), np.array([s[1] for s in sts]).reshape(-1, 3),
+                  np.array([s[2] for s in sts]).reshape(-1, 3, 3), np.array([s[3] for s in sts]).reshape(-1, 3),
+                  np.broadcast_to(Rcb, (len(sts), 3, 3)).copy(), np.broadcast_to(tcb, (len(sts), 3)).copy(),
+                  np.array([e[2] for e in (entries[k] for k in order)], bool), np.array(edges, np.int32).reshape(-1, 2),
+                  np.array(dR).reshape(-1, 3, 3), np.array(dt).reshape(-1, 3), INFO_4DOF)
+    return g, kfs, vScw
+
+
 # ---- the stand-in map of the test-only host library ----
 class HostPgoMap:
     """The synthetic map as stand-in KeyFrame / MapPoint / Map objects (osh_host_graph_create + osh_host_pgo_set_graph)."""
@@ -493,3 +679,36 @@ class HostPgoMap:
 
     def change_index(self):
         return self.lib.osh_host_map_change_index(self.g)
+
+
+class HostPgo4Map(HostPgoMap):
+    """An inertial map as stand-in objects: the graph of HostPgoMap plus every keyframe's mImuCalib (osh_host_graph_set_inertial
+    with no preintegration), for Optimizer::OptimizeEssentialGraph4DoF (osh_host_pgo4_*)."""
+
+    def __init__(self, m: SynthInertialMap):
+        super().__init__(m)
+        Rbc = m.Rcb.astype(np.float64).T
+        tbc = -Rbc @ m.tcb.astype(np.float64)
+        self._tbc = np.ascontiguousarray(np.concatenate([_rot_to_quat(Rbc), tbc]), dtype=np.float32)
+        assert self.lib.osh_host_graph_set_inertial(self.g, 0, None, None, None, None, None, None,
+                                                    capi.ptr(self._tbc, capi.c_float_p)) == 0
+
+    def pack4(self, max_e=None):
+        """The host layer's walk as (Pgo4Graph, mnId of every vertex)."""
+        n = self.m.n
+        max_e = max_e or 64 * n + 64
+        o = dict(kf=np.zeros(n, np.int64), Rwb=np.zeros((n, 3, 3)), twb=np.zeros((n, 3)), Rcw=np.zeros((n, 3, 3)), tcw=np.zeros((n, 3)),
+                 Rcb=np.zeros((n, 3, 3)), tcb=np.zeros((n, 3)), fixed=np.zeros(n, np.uint8), eij=np.zeros((max_e, 2), np.int32),
+                 dR=np.zeros((max_e, 3, 3)), dt=np.zeros((max_e, 3)))
+        D = lambda k: capi.ptr(o[k], capi.c_double_p)  # noqa: E731
+        st = capi.HostPgo4Out(n, max_e, 0, 0, 0, capi.ptr(o["kf"], capi.c_int64_p), D("Rwb"), D("twb"), D("Rcw"), D("tcw"), D("Rcb"),
+                              D("tcb"), capi.ptr(o["fixed"], capi.c_uint8_p), capi.ptr(o["eij"], capi.c_int32_p), D("dR"), D("dt"))
+        assert self.lib.osh_host_pgo4_pack(self.g, C.byref(self._loop()), C.byref(st)) == 0
+        nv, ne = st.n_vertices, st.n_edges
+        g = Pgo4Graph(o["Rwb"][:nv].copy(), o["twb"][:nv].copy(), o["Rcw"][:nv].copy(), o["tcw"][:nv].copy(), o["Rcb"][:nv].copy(),
+                      o["tcb"][:nv].copy(), o["fixed"][:nv].astype(bool), o["eij"][:ne].copy(), o["dR"][:ne].copy(), o["dt"][:ne].copy(),
+                      INFO_4DOF)
+        return g, o["kf"][:nv].copy()
+
+    def run4(self):
+        return self.lib.osh_host_pgo4_run(self.g, C.byref(self._loop()))
