@@ -9,6 +9,12 @@ in HBM: osh_lba_optimize() on `--windows` independent config-2 windows (BASELINE
 the reference's early-stop rules).  Multi-GPU: weak scaling, window w -> rank w mod G, no
 data-path collective; barrier + max-over-ranks timing via torch.distributed (RCCL).
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: generate and upload the windows, warm up, time the steps, download (and
+--dump-outputs) what the last step computed, print the line.  `--full` adds everything else the line can carry, each with
+runs of its own: the per-kernel HIP-event pass and the roofline, the end-to-end pipeline, the batch-size sweeps, the ORB
+and LocalInertialBA figures and the CPU baselines (--no-orb, --no-sweeps, --no-cpu-baseline, --inertial-windows 0 and
+--e2e-batches 0 leave parts of it out).
 """
 from __future__ import annotations
 
@@ -173,7 +179,15 @@ def run_lba(args, info, windows):
     for sv in solvers:
         sv.close()
     pool.shutdown()
-    # per-kernel HIP-event timing: one untimed, un-overlapped step of ALL windows on a single stream
+    out = dict(windows=windows, results=results, elapsed=elapsed, elapsed_local=elapsed_local, upload_s=upload_s)
+    if args.full:
+        out.update(profile_lba(info, windows, results))
+    return out
+
+
+def profile_lba(info, windows, results):
+    """Per-kernel HIP-event timing (--full): one untimed, un-overlapped step of ALL windows on a single stream."""
+    from orb_slam3_study_kr_amd import lba
     solver = lba.LbaSolver(info.local_rank)
     solver.upload(windows)
     solver.optimize()
@@ -184,7 +198,7 @@ def run_lba(args, info, windows):
     solver.set_profiling(False)
     solver.close()
     alg, alg_impl = kernel_algorithmic_bytes(windows, results, plan)
-    return dict(windows=windows, results=results, elapsed=elapsed, elapsed_local=elapsed_local, upload_s=upload_s, prof=prof, alg=alg, alg_impl=alg_impl, plan=plan)
+    return dict(prof=prof, alg=alg, alg_impl=alg_impl, plan=plan)
 
 
 DUMP_BYTES = 48 << 20   # --dump-outputs stays under 64 MB: every pose, a fixed sample of landmarks and edges
@@ -648,51 +662,10 @@ def stub_main(args):
     osh_dist.finalize(info)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--windows", type=int, default=512, help="config-2 windows resident per GPU (one step solves them all)")
-    ap.add_argument("--orb-pairs", type=int, default=64, help="2000x2000 frame pairs per GPU per ORB step")
-    ap.add_argument("--streams", type=int, default=2, help="solver contexts (HIP streams) sharing the GPU in the timed region")
-    ap.add_argument("--workers", type=int, default=0, help="input-generation processes (0 = auto; use 1 under rocprofv3: "
-                    "the profiler's signal handler hangs on the pool's worker teardown)")
-    ap.add_argument("--cache-inputs", default="", help="pickle file to store / reuse the generated windows")
-    ap.add_argument("--prepare-only", action="store_true", help="generate (and cache) the inputs, then exit")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-orb", action="store_true")
-    ap.add_argument("--no-sweeps", action="store_true", help="skip the batch-size sub-tables (config 2: B = 1, 8, 64, 256; config 3: B = 1, 64, 1024)")
-    ap.add_argument("--inertial-windows", type=int, default=128, help="config-4 windows per osh_liba_solve call (0 = skip)")
-    ap.add_argument("--e2e-contexts", type=int, default=4, help="solver contexts (each with its own host thread, stream and pinned staging) of the end-to-end run")
-    ap.add_argument("--e2e-batches", type=int, default=6, help="batches per solver context in the end-to-end (upload + optimize + download) run; 0 = skip")
-    ap.add_argument("--stub-solver", action="store_true", help="CPU rehearsal of the rank plumbing (gloo): no GPU work, the "
-                    "timed step is a fixed sleep; the JSON line is marked \"stub\" and is not a measurement")
-    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (every window's poses and "
-                    "LM trace, a fixed sample of landmarks and edges) as DIR/<name>.npy, float64, under 64 MB in all")
-    args = ap.parse_args()
-
-    if osh_launch.needs_spawn(args.gpus):
-        # `python bench.py --gpus N` outside a rendezvous: start the N ranks as a CHILD process (never exec; this parent
-        # has not touched the GPU) and hand its exit code back
-        raise SystemExit(osh_launch.spawn_ranks(str(Path(__file__).resolve()), args.gpus, sys.argv[1:]))
-    env_rank, env_world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    osh_launch.check_world(args.gpus, env_world)
-    if args.stub_solver:
-        return stub_main(args)
-    windows = make_lba_inputs(args, env_rank, env_world)
-    if args.prepare_only:
-        return
-    inertial_windows = make_inertial_inputs(args) if args.inertial_windows > 0 else None
-    info = osh_dist.init_from_env()
-    osh_launch.check_world(args.gpus, info.world)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU (the product path has no CPU fallback)")
-    torch.cuda.set_device(info.local_rank)
-
-    lba_out = run_lba(args, info, windows)
-    dump_out = dump_lba_outputs(args.dump_outputs, lba_out["windows"], lba_out["results"], info.rank) if args.dump_outputs else None
+def full_report(args, info, lba_out, inertial_windows, out):
+    """What --full adds to the line `out`, each from runs of its own after the timed steps: the end-to-end pipeline, the
+    batch-size sweeps, ORB, LocalInertialBA, the roofline of the per-kernel pass (profile_lba) and the CPU baselines."""
+    windows = lba_out["windows"]
     e2e_out = run_end_to_end(args, info, windows) if args.e2e_batches > 0 else None
     sweep_out = run_batch_sweep(args, info, windows) if (info.rank == 0 and not args.no_sweeps) else None
     orb_sweep_out = run_orb_sweep(args, info) if (info.rank == 0 and not args.no_sweeps and not args.no_orb) else None
@@ -700,12 +673,7 @@ def main():
     inertial_out = run_inertial(args, info, inertial_windows) if inertial_windows else None
 
     n_gpus = info.world
-    ms_per_step = lba_out["elapsed"] / args.steps * 1e3
-    value = args.windows * n_gpus / (ms_per_step * 1e-3)
-    # what the process group saw: an all-reduce of 1 over RCCL (= the number of ranks that took part) and every rank's own rate
-    ranks_seen = int(round(osh_dist.all_reduce_sum(info, [1.0])[0]))
-    per_rank = osh_dist.all_gather_floats(info, args.windows / (lba_out["elapsed_local"] / args.steps))
-
+    ms_per_step, value = out["ms_per_step"], out["value"]
     # roofline of the dominant step of the loop (largest total HIP-event time in one optimize()); a step is one or
     # more kernels (STEP_KERNELS), its launch time the sum of theirs, its algorithmic bytes SURVEY.md 8(d)'s figure
     from orb_slam3_study_kr_amd import lba
@@ -753,25 +721,7 @@ def main():
                          needed_GBps=(alg_impl[st] / (ms * 1e-3) / 1e9) if ms > 0 else None)
         assert ms <= 0 or alg_impl[st] / (ms * 1e-3) / 1e9 <= HBM_PEAK_GBS, f"step {st}: more bytes than the HBM peak allows -- wrong byte model"
     whole_bytes = sum(alg.values())
-    res = lba_out["results"]
-    out = {
-        "metric": "local-BA windows/sec (50 KF, 10k pts, 10 LM iters) + ORB matches/sec; 1/2/4/8 GPU",
-        "value": value, "unit": "windows/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "BASELINE.json configs[1]: synthetic stereo local BA, 50 optimisable + 10 fixed KF, "
-                               "10k landmarks (~75k stereo edges), optimize(10) with the reference's stop rules",
-                   "windows_per_gpu": args.windows, "global_windows": args.windows * n_gpus, "streams_per_gpu": args.streams,
-                   "parallelism": f"independent windows, w mod {n_gpus}", "lm_iterations_mean": float(np.mean([r.iterations for r in res])),
-                   "lm_trials_mean": float(np.mean([r.trials for r in res]))},
-        "roofline": roofline,
-        "kernels": kernels, "step_times": steps,
-        "whole_job_alg_GBps_per_gpu": whole_bytes / (ms_per_step * 1e-3) / 1e9,
-        "upload_s_per_batch": lba_out["upload_s"],
-        "ranks_seen": ranks_seen, "windows_per_s_by_rank": per_rank,
-    }
-    if dump_out is not None:
-        out["dump_outputs"] = dump_out
+    out.update(roofline=roofline, kernels=kernels, step_times=steps, whole_job_alg_GBps_per_gpu=whole_bytes / (ms_per_step * 1e-3) / 1e9)
     if sweep_out:
         out["config2_batch_sweep"] = sweep_out
         if "1" in sweep_out:
@@ -797,8 +747,8 @@ def main():
                       "what": "osh_orb_match_local_points per step: unrestricted search + the sequential slot occupancy of src/ORBmatcher.cc:84-139 "
                               "resolved in fixed-point rounds on the device + D2H of the slot assignment; matches are the function's return values"}
         # integer-VALU bound: a 256-bit Hamming distance is 8 v_xor_b32 + 8 v_bcnt_u32_b32 (the add is folded into bcnt) per pair;
-        # the best / second-best bookkeeping on top is overhead.  Peak = 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz (the FP32 vector
-        # peak of MI355X_MICROARCH.md, 157.3 TFLOP/s, is this rate x 2 flop x 2 packed).  Lane-ops per pair: 19.25 = the 77 vector
+        # the best / second-best bookkeeping on top is overhead.  Peak = 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz (MI355X's FP32
+        # vector peak, 157.3 TFLOP/s, is this rate x 2 flop x 2 packed).  Lane-ops per pair: 19.25 = the 77 vector
         # instructions of the loop body over 4 train descriptors (8 xor + 8 chained v_bcnt + v_lshl_or + v_med3 + v_min each, one
         # v_mov; round 2: 23.4 by SQ_INSTS_VALU, the counts summed by a tree of v_add3 and the second-best kept by max + min).
         pe = orb_out["pairs_per_gpu"] * 4.0e6 / (orb_out["kernel_ms"] * 1e-3)
@@ -834,6 +784,80 @@ def main():
             dt = time.perf_counter() - t0
             out["orb"]["cpu_baseline"] = dict(value=4.0e6 / dt, unit="pair-evals/s", cores=1, kind="port",
                                               sample="one 2000x2000 frame pair, SWAR popcount restatement")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--windows", type=int, default=512, help="config-2 windows resident per GPU (one step solves them all)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline (per-kernel times and roofline, "
+                    "end-to-end pipeline, batch-size sweeps, ORB, LocalInertialBA, CPU baselines); the options below marked --full shape it")
+    ap.add_argument("--orb-pairs", type=int, default=64, help="--full: 2000x2000 frame pairs per GPU per ORB step")
+    ap.add_argument("--streams", type=int, default=2, help="solver contexts (HIP streams) sharing the GPU in the timed region")
+    ap.add_argument("--workers", type=int, default=0, help="input-generation processes (0 = auto; use 1 under rocprofv3: "
+                    "the profiler's signal handler hangs on the pool's worker teardown)")
+    ap.add_argument("--cache-inputs", default="", help="pickle file to store / reuse the generated windows")
+    ap.add_argument("--prepare-only", action="store_true", help="generate (and cache) the inputs, then exit")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-orb", action="store_true", help="--full: skip the ORB figures")
+    ap.add_argument("--no-sweeps", action="store_true", help="--full: skip the batch-size sub-tables (config 2: B = 1, 8, 64, 256; config 3: B = 1, 64, 1024)")
+    ap.add_argument("--inertial-windows", type=int, default=128, help="--full: config-4 windows per osh_liba_solve call (0 = skip)")
+    ap.add_argument("--e2e-contexts", type=int, default=4, help="--full: solver contexts (each with its own host thread, stream and pinned staging) of the end-to-end run")
+    ap.add_argument("--e2e-batches", type=int, default=6, help="--full: batches per solver context in the end-to-end (upload + optimize + download) run; 0 = skip")
+    ap.add_argument("--stub-solver", action="store_true", help="CPU rehearsal of the rank plumbing (gloo): no GPU work, the "
+                    "timed step is a fixed sleep; the JSON line is marked \"stub\" and is not a measurement")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (every window's poses and "
+                    "LM trace, a fixed sample of landmarks and edges) as DIR/<name>.npy, float64, under 64 MB in all")
+    args = ap.parse_args()
+
+    if osh_launch.needs_spawn(args.gpus):
+        # `python bench.py --gpus N` outside a rendezvous: start the N ranks as a CHILD process (never exec; this parent
+        # has not touched the GPU) and hand its exit code back
+        raise SystemExit(osh_launch.spawn_ranks(str(Path(__file__).resolve()), args.gpus, sys.argv[1:]))
+    env_rank, env_world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    osh_launch.check_world(args.gpus, env_world)
+    if args.stub_solver:
+        return stub_main(args)
+    windows = make_lba_inputs(args, env_rank, env_world)
+    if args.prepare_only:
+        return
+    inertial_windows = make_inertial_inputs(args) if (args.full and args.inertial_windows > 0) else None
+    info = osh_dist.init_from_env()
+    osh_launch.check_world(args.gpus, info.world)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs a GPU (the product path has no CPU fallback)")
+    torch.cuda.set_device(info.local_rank)
+
+    lba_out = run_lba(args, info, windows)
+    dump_out = dump_lba_outputs(args.dump_outputs, lba_out["windows"], lba_out["results"], info.rank) if args.dump_outputs else None
+
+    n_gpus = info.world
+    ms_per_step = lba_out["elapsed"] / args.steps * 1e3
+    value = args.windows * n_gpus / (ms_per_step * 1e-3)
+    # what the process group saw: an all-reduce of 1 over RCCL (= the number of ranks that took part) and every rank's own rate
+    ranks_seen = int(round(osh_dist.all_reduce_sum(info, [1.0])[0]))
+    per_rank = osh_dist.all_gather_floats(info, args.windows / (lba_out["elapsed_local"] / args.steps))
+    res = lba_out["results"]
+    out = {
+        "metric": "local-BA windows/sec (50 KF, 10k pts, 10 LM iters) + ORB matches/sec; 1/2/4/8 GPU",
+        "value": value, "unit": "windows/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "BASELINE.json configs[1]: synthetic stereo local BA, 50 optimisable + 10 fixed KF, "
+                               "10k landmarks (~75k stereo edges), optimize(10) with the reference's stop rules",
+                   "windows_per_gpu": args.windows, "global_windows": args.windows * n_gpus, "streams_per_gpu": args.streams,
+                   "parallelism": f"independent windows, w mod {n_gpus}", "lm_iterations_mean": float(np.mean([r.iterations for r in res])),
+                   "lm_trials_mean": float(np.mean([r.trials for r in res]))},
+        "upload_s_per_batch": lba_out["upload_s"],
+        "ranks_seen": ranks_seen, "windows_per_s_by_rank": per_rank,
+    }
+    if dump_out is not None:
+        out["dump_outputs"] = dump_out
+    if args.full:
+        full_report(args, info, lba_out, inertial_windows, out)
     if info.rank == 0:
         print(json.dumps(out))
     osh_dist.finalize(info)

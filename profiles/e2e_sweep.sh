@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT
 python3 bench.py --windows 512 --cache-inputs /tmp/lba_inputs.pkl --prepare-only > /dev/null 2>&1
-B="python3 bench.py --windows 512 --cache-inputs /tmp/lba_inputs.pkl --steps 1 --warmup 1 --no-orb --no-cpu-baseline --inertial-windows 0"
+B="python3 bench.py --full --windows 512 --cache-inputs /tmp/lba_inputs.pkl --steps 1 --warmup 1 --no-orb --no-cpu-baseline --inertial-windows 0"
 for cfg in ${E2E_CFGS:-2x16 4x8 4x8 4x6 4x16 6x4 6x6 8x4}; do
   set -- $(echo $cfg | tr "x" " ")
   ORBSLAM3_HIP_UPLOAD_THREADS=$2 timeout -k 10 250 $B --e2e-contexts $1 --e2e-batches 3 2>/dev/null | python3 -c "
