@@ -1,7 +1,8 @@
 // pgo_env.h -- the parts of the pose-graph solvers that do not depend on the vertex type, shared by pgo_device.hip (Sim3,
 // 7 unknowns per vertex) and pgo4_device.hip (4-DoF, 4 unknowns per vertex): the envelope LDL^T kernels, the fixed-order
-// chi2 / computeScale reduction, and the host-side plan (free-vertex numbering, the assembly CSR of dim x dim blocks, the
-// envelope and the active lists of every panel).  The LDL^T works on scalar unknowns: only the plan knows `dim`.
+// chi2 / computeScale reduction, the host-side plan (free-vertex numbering, the assembly CSR of dim x dim blocks, the
+// envelope and the active lists of every panel), k_pgo_fill, k_pgo_maxdiag, and PgoRun: the arena, the trial sequence, g2o's
+// Levenberg loop and the dense diagnostic.  The LDL^T works on scalar unknowns: only the plan knows `dim`.
 //
 // Envelope storage: the reduced system has dim nf unknowns (free vertices in array order = keyframe-id order), padded to a
 // multiple of 32 with an identity diagonal.  Column tile J keeps row tiles ttop[J] .. J (32 x 32 doubles each, row-major),
@@ -10,8 +11,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <limits>
 #include <map>
+#include <type_traits>
 #include <vector>
 #include "common.h"
 #include "ldlt_block.h"
@@ -304,6 +309,92 @@ int make_plan(const PlanInput& p, int dim, const char* tag, Plan& P) {
   return OSH_OK;
 }
 
+// The arrays k_pgo_assemble and k_pgo_fill read.  A graph's assembly view derives from it and adds nblk (after its information,
+// if it has one).
+struct AsmArrays {
+  const double* J; const double* err;
+  const int* blk_a; const int* blk_b;     // [nblk] free-vertex indices (a == b: diagonal block), a <= b
+  const int* ent_ptr; const int* ent;     // [nblk + 1], entries: diagonal (e << 1 | side), off-diagonal (e << 1 | flip)
+  double* H;                              // [nblk][D D]
+  double* b;                              // [D nf]
+};
+
+// block per D x D block of H: sums its edges in edge order (CSR built at upload, no atomics); b = -J^T Omega e.  Each edge side
+// has an M x D Jacobian (row-major); Omega is the identity, or the diagonal v.info.w when kDiagInfo.
+template <int D, int M, bool kDiagInfo, class AsmV>
+__global__ __launch_bounds__(64) void k_pgo_assemble(AsmV v) {
+  const int k = blockIdx.x, t = threadIdx.x;
+  const int a = v.blk_a[k], bb = v.blk_b[k];
+  const int p0 = v.ent_ptr[k], p1 = v.ent_ptr[k + 1];
+  auto omega = [&](double j, int m) {
+    if constexpr (kDiagInfo) return j * v.info.w[m]; else return j;
+  };
+  if (t < D * D) {
+    const int r = t / D, c = t - D * (t / D);
+    double s = 0;
+    for (int q = p0; q < p1; ++q) {
+      const int en = v.ent[q], e = en >> 1, f = en & 1;
+      const double* Ja = v.J + ((size_t)e * 2 + f) * (M * D);
+      const double* Jb = a == bb ? Ja : v.J + ((size_t)e * 2 + (1 - f)) * (M * D);
+      double h = 0;
+      for (int m = 0; m < M; ++m) h += omega(Ja[m * D + r], m) * Jb[m * D + c];
+      s += h;
+    }
+    v.H[(size_t)k * (D * D) + t] = s;
+  } else if (a == bb && t < D * D + D) {
+    const int r = t - D * D;
+    double s = 0;
+    for (int q = p0; q < p1; ++q) {
+      const int en = v.ent[q], e = en >> 1, f = en & 1;
+      const double* Ja = v.J + ((size_t)e * 2 + f) * (M * D);
+      const double* er = v.err + M * (size_t)e;
+      double h = 0;
+      for (int m = 0; m < M; ++m) h += omega(Ja[m * D + r], m) * er[m];
+      s -= h;
+    }
+    v.b[D * a + r] = s;
+  }
+}
+
+// H + lambda I into the envelope tiles of the working matrix, b into the right-hand side.  D unknowns per vertex; `v` is the
+// graph's assembly view (blk_a, blk_b, H of D x D blocks, b, nblk).
+template <int D, class AsmV>
+__global__ __launch_bounds__(64) void k_pgo_fill(AsmV v, Env g, double lambda, int nf) {
+  const int k = blockIdx.x, t = threadIdx.x;
+  if (k == v.nblk) {   // padding of the last tile: identity, zero rhs
+    for (int R = D * nf + t; R < kT * g.NT; R += 64) { env_tile(g, R >> 5, R >> 5)[(R & 31) * kT + (R & 31)] = 1.0; g.w[R] = 0.0; }
+    return;
+  }
+  const int a = v.blk_a[k], bb = v.blk_b[k];
+  if (t < D * D) {
+    const int r = t / D, c = t - D * (t / D);
+    const int R = D * a + r, Cc = D * bb + c;
+    if (R <= Cc) {
+      double h = v.H[(size_t)k * (D * D) + t];
+      if (R == Cc) h += lambda;
+      env_tile(g, R >> 5, Cc >> 5)[(R & 31) * kT + (Cc & 31)] = h;
+    }
+  } else if (a == bb && t < D * D + D) {
+    g.w[D * a + t - D * D] = v.b[D * a + t - D * D];
+  }
+}
+
+// max |H_kk| over the diagonal blocks 0 .. nf-1 (they come first in the block list); max is exact in any order
+template <int D>
+__global__ __launch_bounds__(256) void k_pgo_maxdiag(const double* H, int nf, double* out) {
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  double m = 0.0;
+  for (int k = t; k < D * nf; k += 256) m = fmax(m, fabs(H[(size_t)(k / D) * (D * D) + (k % D) * (D + 1)]));
+  red[t] = m;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) red[t] = fmax(red[t], red[t + h]);
+    __syncthreads();
+  }
+  if (t == 0) *out = red[0];
+}
+
 struct PgoBuffers {
   DevBuf arena, tiles, V;
   PinBuf h_red;
@@ -314,6 +405,231 @@ int launch_check(const char* what) {
   if (e != hipSuccess) { set_error("kernel launch %s failed: %s", what, hipGetErrorString(e)); return OSH_ERR_DEVICE; }
   return OSH_OK;
 }
+
+struct LmResult {
+  int iterations = 0, trials = 0, cur = 0;   // the returned states are d_x[cur]
+  double chi2_initial = 0, chi2_final = 0, lambda0 = 0;
+};
+
+// Everything of one call on the device for the graph G: the arena, the upload, one LM trial, the LM loop and the dense
+// diagnostic.  G gives
+//   D, M               unknowns per vertex, errors per edge
+//   kState, kMeas      doubles of one vertex state and of one edge measurement
+//   Aux, kAux          its per-vertex device array (type, entries per vertex)
+//   kDiagInfo, kTag    k_pgo_assemble's information (identity or diagonal), the prefix of its messages
+//   lin(R, cur, linearize), step(R, cur)   its kernel launches, each returning launch_check's result
+//   asm_view(R)        the view k_pgo_assemble and k_pgo_fill read
+template <class G>
+struct PgoRun {
+  osh_lba_ctx* ctx;
+  G graph;
+  hipStream_t s = nullptr;
+  PgoBuffers* B = nullptr;
+  Plan P;
+  double *d_x[2] = {nullptr, nullptr}, *d_meas, *d_J, *d_err, *d_chi, *d_H, *d_b, *d_w, *d_z, *d_red;
+  int *d_eij, *d_sys, *d_blk_a, *d_blk_b, *d_ent_ptr, *d_ent, *d_toff, *d_ttop, *d_act_ptr, *d_act, *d_fail;
+  typename G::Aux* d_aux;
+  double* h_red = nullptr;
+
+  explicit PgoRun(osh_lba_ctx* c) : ctx(c) {}
+
+  // the size checks: no device work
+  int plan(const PlanInput& in) { return make_plan(in, G::D, G::kTag, P); }
+  int dense_fits() const {
+    if (P.nf > 512) { set_error("%s_linearize: %d free vertices, the diagnostic takes up to 512", G::kTag, P.nf); return OSH_ERR_UNSUPPORTED; }
+    return OSH_OK;
+  }
+
+  // the arena (zeroed), the plan, the initial states x0 into d_x[0], the measurements, the edges and the per-vertex array
+  int upload(const double* x0, const double* meas, const int32_t* eij, const typename G::Aux* aux) {
+    int device = 0;
+    OSH_TRY(lba_stream(ctx, &device, &s));
+    OSH_HIP(hipSetDevice(device));
+    void** slot = lba_attachment(ctx, kAttachPgo, [](void* q) { delete static_cast<PgoBuffers*>(q); });
+    if (!slot) { set_error("%s: no context", G::kTag); return OSH_ERR_INVALID; }
+    if (!*slot) *slot = new PgoBuffers();
+    B = static_cast<PgoBuffers*>(*slot);
+    const size_t n = P.n, E = std::max(P.E, 1), NT = P.NT;
+    auto layout = [&](uintptr_t base) {
+      size_t bytes = 0;
+      auto take = [&](auto*& d, size_t b) {
+        d = reinterpret_cast<std::remove_reference_t<decltype(d)>>(base + bytes);
+        bytes = (bytes + std::max<size_t>(b, 8) + 255) & ~(size_t)255;
+      };
+      take(d_x[0], n * G::kState * 8); take(d_x[1], n * G::kState * 8); take(d_aux, n * G::kAux * sizeof(typename G::Aux));
+      take(d_meas, E * G::kMeas * 8); take(d_J, E * 2 * G::D * G::M * 8); take(d_err, E * G::M * 8); take(d_chi, E * 8);
+      take(d_H, (size_t)P.nblk * G::D * G::D * 8); take(d_b, (size_t)P.N * 8 + 8); take(d_w, NT * kT * 8); take(d_z, NT * kT * 8);
+      take(d_red, 64); take(d_eij, E * 8); take(d_sys, n * 4); take(d_blk_a, (size_t)P.nblk * 4); take(d_blk_b, (size_t)P.nblk * 4);
+      take(d_ent_ptr, (size_t)(P.nblk + 1) * 4); take(d_ent, P.ent.size() * 4 + 4); take(d_toff, NT * 4); take(d_ttop, NT * 4);
+      take(d_act_ptr, (NT + 1) * 4); take(d_act, P.act.size() * 4); take(d_fail, 4);
+      return bytes;
+    };
+    const size_t bytes = layout(0);
+    OSH_TRY(B->arena.reserve(bytes));
+    OSH_TRY(B->tiles.reserve((size_t)P.ntiles * kTT * 8));
+    OSH_TRY(B->V.reserve((size_t)P.max_act * kTT * 8));
+    h_red = static_cast<double*>(B->h_red.reserve(64));
+    if (!h_red) { set_error("%s: pinned allocation failed", G::kTag); return OSH_ERR_DEVICE; }
+    layout(reinterpret_cast<uintptr_t>(B->arena.p));
+    // Jacobians of fixed sides are never written or read; zero the arena once per call so that nothing depends on its history
+    OSH_HIP(hipMemsetAsync(B->arena.p, 0, bytes, s));
+    auto up = [&](void* d, const void* h, size_t b) -> int { if (b) OSH_HIP(hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, s)); return OSH_OK; };
+    OSH_TRY(up(d_x[0], x0, n * G::kState * 8));
+    OSH_TRY(up(d_aux, aux, n * G::kAux * sizeof(typename G::Aux)));
+    OSH_TRY(up(d_meas, meas, (size_t)P.E * G::kMeas * 8));
+    OSH_TRY(up(d_eij, eij, (size_t)P.E * 8));
+    OSH_TRY(up(d_sys, P.sys.data(), n * 4));
+    OSH_TRY(up(d_blk_a, P.blk_a.data(), (size_t)P.nblk * 4));
+    OSH_TRY(up(d_blk_b, P.blk_b.data(), (size_t)P.nblk * 4));
+    OSH_TRY(up(d_ent_ptr, P.ent_ptr.data(), (size_t)(P.nblk + 1) * 4));
+    OSH_TRY(up(d_ent, P.ent.data(), P.ent.size() * 4));
+    OSH_TRY(up(d_toff, P.toff.data(), NT * 4));
+    OSH_TRY(up(d_ttop, P.ttop.data(), NT * 4));
+    OSH_TRY(up(d_act_ptr, P.act_ptr.data(), (NT + 1) * 4));
+    OSH_TRY(up(d_act, P.act.data(), P.act.size() * 4));
+    return OSH_OK;
+  }
+
+  Env env() const {
+    Env g;
+    g.T = B->tiles.as<double>(); g.toff = d_toff; g.ttop = d_ttop; g.act_ptr = d_act_ptr; g.act = d_act; g.V = B->V.as<double>();
+    g.w = d_w; g.z = d_z; g.fail = d_fail; g.NT = P.NT;
+    return g;
+  }
+
+  AsmArrays asm_arrays() const { return AsmArrays{d_J, d_err, d_blk_a, d_blk_b, d_ent_ptr, d_ent, d_H, d_b}; }
+
+  // errors (and Jacobians) at d_x[cur]
+  int errors(int cur, int linearize) { return graph.lin(*this, cur, linearize); }
+  int assemble() {
+    if (P.nblk > 0) hipLaunchKernelGGL((k_pgo_assemble<G::D, G::M, G::kDiagInfo>), dim3((unsigned)P.nblk), dim3(64), 0, s, graph.asm_view(*this));
+    return launch_check("k_pgo_assemble");
+  }
+  int max_diag(double* out) {
+    hipLaunchKernelGGL(k_pgo_maxdiag<G::D>, dim3(1), dim3(256), 0, s, d_H, P.nf, d_red + 4);
+    OSH_TRY(launch_check("k_pgo_maxdiag"));
+    OSH_HIP(hipMemcpyAsync(h_red, d_red + 4, 8, hipMemcpyDeviceToHost, s));
+    OSH_HIP(hipStreamSynchronize(s));
+    *out = h_red[0];
+    return OSH_OK;
+  }
+  // one trial: (H + lambda I) x = b into d_w, d_x[1 - cur] = x (+) d_x[cur]; chi2, the scale and the fail flag into h_red
+  int trial(int cur, double lambda) {
+    const Env g = env();
+    OSH_HIP(hipMemsetAsync(d_fail, 0, 4, s));
+    OSH_HIP(hipMemsetAsync(B->tiles.p, 0, (size_t)P.ntiles * kTT * 8, s));
+    hipLaunchKernelGGL(k_pgo_fill<G::D>, dim3((unsigned)P.nblk + 1), dim3(64), 0, s, graph.asm_view(*this), g, lambda, P.nf);
+    OSH_TRY(launch_check("k_pgo_fill"));
+    for (int q = 0; q < P.NT; ++q) {
+      hipLaunchKernelGGL(k_env_diag, dim3(1), dim3(64), 0, s, g, q);
+      const int na = P.act_ptr[q + 1] - P.act_ptr[q];
+      if (na > 0) {
+        hipLaunchKernelGGL(k_env_panel, dim3((unsigned)na), dim3(64), 0, s, g, q);
+        hipLaunchKernelGGL(k_env_update, dim3((unsigned)na, (unsigned)na), dim3(64), 0, s, g, q);
+      }
+    }
+    OSH_TRY(launch_check("k_env_factor"));
+    hipLaunchKernelGGL(k_env_back, dim3(1), dim3(1024), 0, s, g);
+    OSH_TRY(graph.step(*this, cur));
+    OSH_TRY(errors(1 - cur, 0));
+    hipLaunchKernelGGL(k_pgo_reduce, dim3(1), dim3(1024), 0, s, d_chi, P.E, d_w, d_b, P.N, lambda, 1, d_red);
+    OSH_TRY(launch_check("k_pgo_reduce"));
+    OSH_HIP(hipMemcpyAsync(d_red + 2, d_fail, 4, hipMemcpyDeviceToDevice, s));
+    OSH_HIP(hipMemcpyAsync(h_red, d_red, 24, hipMemcpyDeviceToHost, s));
+    OSH_HIP(hipStreamSynchronize(s));
+    return OSH_OK;
+  }
+  int chi2_now(double* out) {
+    hipLaunchKernelGGL(k_pgo_reduce, dim3(1), dim3(1024), 0, s, d_chi, P.E, d_w, d_b, 0, 0.0, 0, d_red);
+    OSH_TRY(launch_check("k_pgo_reduce"));
+    OSH_HIP(hipMemcpyAsync(h_red, d_red, 16, hipMemcpyDeviceToHost, s));
+    OSH_HIP(hipStreamSynchronize(s));
+    *out = h_red[0];
+    return OSH_OK;
+  }
+
+  // SparseOptimizer::optimize (sparse_optimizer.cpp:354-419) with OptimizationAlgorithmLevenberg::solve (levenberg.cpp:99-169).
+  // lambda0(&l) is computeLambdaInit, called once after the first assembly.
+  template <class Lambda0>
+  int solve(int max_iterations, Lambda0 lambda0, LmResult& out) {
+    int cur = 0, nBad = 0;
+    double lambda = 0.0, ni = 2.0;
+    const int maxTrials = 10;
+    bool ok = true;
+    for (int it = 0; it < max_iterations && ok; ++it) {
+      OSH_TRY(errors(cur, 1));
+      double currentChi = 0;
+      OSH_TRY(chi2_now(&currentChi));
+      if (it == 0) out.chi2_initial = currentChi;
+      const double iniChi = currentChi;
+      OSH_TRY(assemble());
+      if (it == 0) {
+        OSH_TRY(lambda0(&lambda));
+        out.lambda0 = lambda;
+        ni = 2;
+        nBad = 0;
+      }
+      double rho = 0;
+      int qmax = 0;
+      do {
+        OSH_TRY(trial(cur, lambda));
+        double tempChi = h_red[0];
+        const double scale = h_red[1] + 1e-3;
+        int fail = 0;
+        std::memcpy(&fail, &h_red[2], 4);
+        if (fail) tempChi = std::numeric_limits<double>::max();
+        rho = (currentChi - tempChi) / scale;
+        if (rho > 0 && std::isfinite(tempChi)) {
+          double alpha = 1. - std::pow((2 * rho - 1), 3);
+          alpha = std::min(alpha, 2. / 3.);
+          const double scaleFactor = std::max(1. / 3., alpha);
+          lambda *= scaleFactor;
+          ni = 2;
+          currentChi = tempChi;
+          cur = 1 - cur;   // discardTop: the trial's states become the vertices
+        } else {
+          lambda *= ni;
+          ni *= 2;         // pop: the trial's states are dropped
+        }
+        ++qmax;
+        ++out.trials;
+      } while (rho < 0 && qmax < maxTrials);
+      ++out.iterations;
+      if (qmax == maxTrials || rho == 0) { ok = false; continue; }
+      if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;   // the stop rule of this g2o copy (levenberg.cpp:154-164)
+      if (nBad >= 3) ok = false;
+    }
+    // computeActiveErrors at the returned states
+    OSH_TRY(errors(cur, 0));
+    OSH_TRY(chi2_now(&out.chi2_final));
+    out.cur = cur;
+    return OSH_OK;
+  }
+
+  // the *_linearize diagnostic at the uploaded states: chi2, b, and H expanded from its D x D blocks into dense N x N
+  int linearize(double* H, double* b, double* chi2) {
+    constexpr int D = G::D;
+    OSH_TRY(errors(0, 1));
+    OSH_TRY(chi2_now(chi2));
+    OSH_TRY(assemble());
+    std::vector<double> blocks((size_t)P.nblk * D * D);
+    if (!blocks.empty()) OSH_HIP(hipMemcpyAsync(blocks.data(), d_H, blocks.size() * 8, hipMemcpyDeviceToHost, s));
+    if (P.N > 0) OSH_HIP(hipMemcpyAsync(b, d_b, (size_t)P.N * 8, hipMemcpyDeviceToHost, s));
+    OSH_HIP(hipStreamSynchronize(s));
+    const size_t N = P.N;
+    std::fill(H, H + N * N, 0.0);
+    for (int k = 0; k < P.nblk; ++k) {
+      const int a = P.blk_a[k], bb = P.blk_b[k];
+      for (int r = 0; r < D; ++r)
+        for (int c = 0; c < D; ++c) {
+          const double h = blocks[(size_t)k * D * D + r * D + c];
+          H[(size_t)(D * a + r) * N + D * bb + c] = h;
+          if (a != bb) H[(size_t)(D * bb + c) * N + D * a + r] = h;
+        }
+    }
+    return OSH_OK;
+  }
+};
 
 }  // namespace
 }  // namespace osh
