@@ -51,6 +51,9 @@ class Optimizer {
   void static OptimizeEssentialGraph4DoF(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
                                          const LoopClosing::KeyFrameAndPose& CorrectedSim3,
                                          const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections);
+  // src/Optimizer.cc:2118-2385 (csrc/host/OptimizerSim3.cc): the relative Sim3 of a loop / merge candidate, both rounds on the device
+  int static OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+                          const bool bFixScale, Eigen::Matrix<double, 7, 7>& mAcumHessian, const bool bAllPoints = false);
   void static MergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, bool* pbStopFlag, Map* pMap, LoopClosing::KeyFrameAndPose& corrPoses);
 };
 }  // namespace ORB_SLAM3

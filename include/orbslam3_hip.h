@@ -488,6 +488,51 @@ int osh_pgo4_solve(osh_lba_ctx* ctx, const osh_pgo4_problem* problem, osh_pgo4_r
  * in array order, dense row-major (4 nf) x (4 nf) with both triangles filled; b[4 nf]).  For small graphs (nf <= 512). */
 int osh_pgo4_linearize(osh_lba_ctx* ctx, const osh_pgo4_problem* problem, double* H, double* b, double* chi2);
 
+/*
+ * The solver part of Optimizer::OptimizeSim3 (src/Optimizer.cc:2118-2385), the refinement of a loop or merge candidate's relative
+ * Sim3: one VertexSim3Expmap (types_seven_dof_expmap.h:60-69, _fix_scale), per matched pair an EdgeSim3ProjectXYZ (x1 = S12 X2c
+ * through camera 1) and an EdgeInverseSim3ProjectXYZ (x2 = S12^-1 X1c through camera 2), both with a Huber kernel of delta
+ * (float)sqrt(th2) (include/OptimizableTypes.h:175-215), numeric Jacobians (base_binary_edge.hpp:147-197, delta 1e-9),
+ * Levenberg-Marquardt with a dense 7x7 solve.  Round 1 is optimize(5); a pair is an outlier when either edge's chi2 (the
+ * unrobustified e^T Omega e of the last trial, as double against the float th2) exceeds th2.  With at least 10 inliers left,
+ * round 2 runs optimize(n_bad > 0 ? 10 : 5) over the inliers without robust kernels, and the final estimate re-classifies them.
+ * One problem per block on the device; `n` problems per call.  Sim3 layout: qx qy qz qw tx ty tz s.
+ */
+typedef struct osh_sim3_problem {
+  int32_t n_pairs;
+  double S12[8];              /* initial g2oS12 */
+  int32_t fix_scale;          /* vSim3->_fix_scale: update[6] = 0 */
+  float th2;                  /* chi2 threshold; the Huber delta is (float)sqrt(th2) */
+  double cam1[8];             /* pKF1->mpCamera: fx fy cx cy, then k1..k4 when kb8_1 */
+  double cam2[8];             /* pKF2->mpCamera */
+  int32_t kb8_1, kb8_2;       /* 0: Pinhole, 1: KannalaBrandt8 */
+  const double* X1c;          /* [n_pairs*3] P3D1c (vertex of e21) */
+  const double* X2c;          /* [n_pairs*3] P3D2c (vertex of e12) */
+  const double* obs1;         /* [n_pairs*2] measurement of e12 */
+  const double* obs2;         /* [n_pairs*2] measurement of e21 */
+  const double* info1;        /* [n_pairs] information of e12 (times the 2x2 identity) */
+  const double* info2;        /* [n_pairs] information of e21 */
+} osh_sim3_problem;
+
+typedef struct osh_sim3_result {
+  double S12[8];              /* the optimised S12; the input S12 when round 2 did not run (g2oS12 is not written then) */
+  uint8_t* outlier1;          /* [n_pairs] 1: outlier of round 1 (may be NULL) */
+  uint8_t* outlier;           /* [n_pairs] 1: vpMatches1 nulled by the call, round 1 or final (may be NULL) */
+  double* chi2_12;            /* [n_pairs] chi2 of e12 the pair was last classified with (may be NULL) */
+  double* chi2_21;            /* [n_pairs] chi2 of e21 (may be NULL) */
+  int32_t n_bad;              /* outliers of round 1 */
+  int32_t n_in;               /* OptimizeSim3's return value: final inliers, 0 without round 2 */
+  int32_t round2;             /* 1: n_pairs - n_bad >= 10 and round 2 ran */
+  int32_t iterations[2];      /* LM iterations of each round */
+  double chi2_end[2];         /* activeRobustChi2 at the end of each round */
+  int32_t status;
+} osh_sim3_result;
+
+int osh_sim3_optimize(osh_lba_ctx* ctx, int32_t n, const osh_sim3_problem* problems, osh_sim3_result* results);
+/* Diagnostic: the first linearisation of `problem` (robust chi2, H (7x7 row-major, both triangles) and b = -J^T rho' Omega e at
+ * the initial S12 with round 1's kernels).  A problem without pairs returns zeros. */
+int osh_sim3_linearize(osh_lba_ctx* ctx, const osh_sim3_problem* problem, double H[49], double b[7], double* chi2);
+
 /* --------------------------------------------------------- ORB matching API */
 /*
  * Nearest / second-nearest 256-bit Hamming search (the candidate loops of

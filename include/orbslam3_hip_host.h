@@ -318,6 +318,43 @@ int osh_host_pgo4_apply(int32_t op, int32_t n, const double* a, const double* b,
 /* out[0] = sizeof(osh_pgo4_problem), out[1] = sizeof(osh_pgo4_result) as the C compiler lays them out */
 void osh_host_pgo4_sizes(int64_t* out);
 
+/* ---- Optimizer::OptimizeSim3 (csrc/host/OptimizerSim3.cc) on two stand-in keyframes (csrc/hosttest/sim3opt.cc) ---- */
+typedef struct osh_host_sim3_kf {
+  float pose[7];                  /* Tcw: qx qy qz qw tx ty tz, returned as is by GetPose()                     */
+  float cam[8];                   /* mpCamera->mvParameters: fx fy cx cy, then k1..k4 for a KannalaBrandt8       */
+  int32_t kb8;                    /* 1: mpCamera is a KannalaBrandt8, 0: a Pinhole                              */
+  int32_t n_keys;
+  const float* keys_un;           /* [n_keys*2] mvKeysUn                                                        */
+  const int32_t* octave;          /* [n_keys] their octaves                                                     */
+  int32_t n_levels;
+  const float* inv_level_sigma2;  /* [n_levels] mvInvLevelSigma2                                                */
+} osh_host_sim3_kf;
+
+typedef struct osh_host_sim3_input {
+  osh_host_sim3_kf kf1, kf2;
+  int32_t n_points;
+  const float* mp_pos;            /* [n_points*3] world positions                                               */
+  const uint8_t* mp_bad;          /* [n_points] isBad()                                                         */
+  const int32_t* mp_index2;       /* [n_points] the point's keypoint in pKF2 (GetIndexInKeyFrame), -1: none     */
+  const int32_t* mp_track_level;  /* [n_points] mnTrackScaleLevel                                               */
+  const int32_t* kf1_mp;          /* [kf1.n_keys] map point of pKF1's slot (GetMapPointMatches), -1: NULL       */
+  int32_t n_matches;
+  const int32_t* matches1;        /* [n_matches] vpMatches1, -1: NULL                                           */
+  double S12[8];                  /* g2oS12 passed in                                                           */
+  float th2;
+  int32_t fix_scale, all_points;  /* bFixScale, bAllPoints                                                      */
+} osh_host_sim3_input;
+
+/* The pair walk alone (PackOptimizeSim3, no device): fills *out, pointing its arrays at the caller's (max_pairs entries each:
+ * index, X1c / X2c [3], obs1 / obs2 [2], info1 / info2), and returns the number of pairs; -1 when there are more than max_pairs
+ * or a camera is refused. */
+struct osh_sim3_problem;
+int osh_host_pack_sim3(const osh_host_sim3_input* in, int32_t max_pairs, struct osh_sim3_problem* out, int32_t* index, double* X1c,
+                       double* X2c, double* obs1, double* obs2, double* info1, double* info2);
+/* Optimizer::OptimizeSim3 itself: returns its value; nulled[n_matches] = 1 where it cleared vpMatches1[i]; S12[8] holds g2oS12 after
+ * the call (in->S12 when untouched); hessian[49] is mAcumHessian, read before and written after the call (row-major). */
+int osh_host_optimize_sim3(const osh_host_sim3_input* in, uint8_t* nulled, double* S12, double* hessian);
+
 #ifdef __cplusplus
 }
 #endif

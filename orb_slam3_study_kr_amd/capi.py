@@ -128,6 +128,27 @@ class Pgo4Result(C.Structure):
     ]
 
 
+class Sim3Problem(C.Structure):
+    """``osh_sim3_problem`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("n_pairs", C.c_int32), ("S12", C.c_double * 8), ("fix_scale", C.c_int32), ("th2", C.c_float),
+        ("cam1", C.c_double * 8), ("cam2", C.c_double * 8), ("kb8_1", C.c_int32), ("kb8_2", C.c_int32),
+        ("X1c", c_double_p), ("X2c", c_double_p), ("obs1", c_double_p), ("obs2", c_double_p),
+        ("info1", c_double_p), ("info2", c_double_p),
+    ]
+
+
+class Sim3Result(C.Structure):
+    """``osh_sim3_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("S12", C.c_double * 8), ("outlier1", c_uint8_p), ("outlier", c_uint8_p), ("chi2_12", c_double_p), ("chi2_21", c_double_p),
+        ("n_bad", C.c_int32), ("n_in", C.c_int32), ("round2", C.c_int32), ("iterations", C.c_int32 * 2),
+        ("chi2_end", C.c_double * 2), ("status", C.c_int32),
+    ]
+
+
 OSH_PGO_MAX_VERTICES = 4000
 OSH_PGO_SOLVE_ENVELOPE = 0
 OSH_PGO_SOLVE_DENSE = 1
@@ -296,6 +317,8 @@ _SIGNATURES = {
     "osh_pgo_linearize": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), c_double_p, c_double_p, c_double_p]),
     "osh_pgo4_solve": (C.c_int, [C.c_void_p, C.POINTER(Pgo4Problem), C.POINTER(Pgo4Result)]),
     "osh_pgo4_linearize": (C.c_int, [C.c_void_p, C.POINTER(Pgo4Problem), c_double_p, c_double_p, c_double_p]),
+    "osh_sim3_optimize": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]),
+    "osh_sim3_linearize": (C.c_int, [C.c_void_p, C.POINTER(Sim3Problem), c_double_p, c_double_p, c_double_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -443,6 +466,31 @@ _HOST_SIGNATURES.update({
     "osh_host_pgo4_apply": (C.c_int, [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
     "osh_host_pgo4_sizes": (None, [c_int64_p]),
 })
+class HostSim3Kf(C.Structure):
+    """``osh_host_sim3_kf`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [
+        ("pose", C.c_float * 7), ("cam", C.c_float * 8), ("kb8", C.c_int32), ("n_keys", C.c_int32), ("keys_un", c_float_p),
+        ("octave", c_int32_p), ("n_levels", C.c_int32), ("inv_level_sigma2", c_float_p),
+    ]
+
+
+class HostSim3Input(C.Structure):
+    """``osh_host_sim3_input`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [
+        ("kf1", HostSim3Kf), ("kf2", HostSim3Kf), ("n_points", C.c_int32), ("mp_pos", c_float_p), ("mp_bad", c_uint8_p),
+        ("mp_index2", c_int32_p), ("mp_track_level", c_int32_p), ("kf1_mp", c_int32_p), ("n_matches", C.c_int32),
+        ("matches1", c_int32_p), ("S12", C.c_double * 8), ("th2", C.c_float), ("fix_scale", C.c_int32), ("all_points", C.c_int32),
+    ]
+
+
+_HOST_SIGNATURES.update({
+    "osh_host_pack_sim3": (C.c_int, [C.POINTER(HostSim3Input), C.c_int32, C.POINTER(Sim3Problem), c_int32_p] + [c_double_p] * 6),
+    "osh_host_optimize_sim3": (C.c_int, [C.POINTER(HostSim3Input), c_uint8_p, c_double_p, c_double_p]),
+})
+
+
 HOST_EXPORTED_SYMBOLS = tuple(_HOST_SIGNATURES)
 
 # osh_host_pgo4_apply operations (include/orbslam3_hip_host.h)

@@ -25,7 +25,7 @@ const char* get_error();
 
 // The paths that run on an osh_lba_ctx besides the visual BA (liba_device.hip, pose_device.hip, posei_device.hip) share its
 // device and stream, and keep their staging and work buffers with it (defined in lba_device.hip).
-enum LbaAttachSlot { kAttachLiba = 0, kAttachPose = 1, kAttachPosei = 2, kAttachPgo = 3, kAttachCount };
+enum LbaAttachSlot { kAttachLiba = 0, kAttachPose = 1, kAttachPosei = 2, kAttachPgo = 3, kAttachSim3 = 4, kAttachCount };
 int lba_stream(osh_lba_ctx* c, int* device, hipStream_t* stream);
 // The context's pointer for `slot` (null until the caller stores its state there); osh_lba_destroy hands it to free_fn.
 void** lba_attachment(osh_lba_ctx* c, LbaAttachSlot slot, void (*free_fn)(void*));

@@ -233,6 +233,26 @@ void PackEssentialGraph4DoF(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, cons
 void PackEssentialGraphMerge(KeyFrame* pCurKF, std::vector<KeyFrame*>& vpFixedKFs, std::vector<KeyFrame*>& vpFixedCorrectedKFs,
                              std::vector<KeyFrame*>& vpNonFixedKFs, PgoPack& pk);
 
+// The pairs of Optimizer::OptimizeSim3 (OptimizerSim3.cc): one entry per edge pair in the reference's order, index = i of
+// vpMatches1 (vnIndexEdge).  False (with `unsupported`) when a keyframe's camera is neither a Pinhole nor a KannalaBrandt8.
+struct Sim3OptPack {
+  std::vector<int> index;
+  std::vector<double> X1c, X2c, obs1, obs2, info1, info2;
+  double cam1[8], cam2[8];
+  int32_t kb8_1 = 0, kb8_2 = 0;
+  const char* unsupported = nullptr;
+  void fill(osh_sim3_problem& p, const g2o::Sim3& S12, float th2, bool bFixScale) const {
+    p.n_pairs = (int32_t)index.size();
+    const Eigen::Quaterniond& q = S12.rotation();
+    const Eigen::Vector3d& t = S12.translation();
+    const double S[8] = {q.x(), q.y(), q.z(), q.w(), t(0), t(1), t(2), S12.scale()};
+    for (int k = 0; k < 8; ++k) { p.S12[k] = S[k]; p.cam1[k] = cam1[k]; p.cam2[k] = cam2[k]; }
+    p.fix_scale = bFixScale ? 1 : 0; p.th2 = th2; p.kb8_1 = kb8_1; p.kb8_2 = kb8_2;
+    p.X1c = X1c.data(); p.X2c = X2c.data(); p.obs1 = obs1.data(); p.obs2 = obs2.data(); p.info1 = info1.data(); p.info2 = info2.data();
+  }
+};
+bool PackOptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatches1, const bool bAllPoints, Sim3OptPack& pk);
+
 // Steps 1-6 of Optimizer::LocalBundleAdjustment; false when the window has no fixed keyframe.
 bool PackLocalBA(KeyFrame* pKF, Map* pMap, LbaPack& pk);
 // Vertex / edge construction of the welding Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, ...) (src/Optimizer.cc:3524-3705);

@@ -165,6 +165,33 @@ class LbaSolver:
         capi.check(self.lib.osh_pose_optimize(self.ctx, n, probs, rs), "osh_pose_optimize", self.lib)
         return [a.read_scalars(r) for r, a in zip(rs, res)]
 
+    def optimize_sim3(self, problems):
+        """``osh_sim3_optimize``: Optimizer::OptimizeSim3's two rounds for every problem of the batch, one block per problem.
+
+        `problems` are packs of ``synth_sim3`` (dicts with X1c, X2c, obs1, obs2, info1, info2, cameras, S12, th2, fix_scale)."""
+        from .synth_sim3 import bind_result, problem, read_result
+        n = len(problems)
+        keep = []
+        probs = (capi.Sim3Problem * n)(*[problem(p, keep) for p in problems])
+        rs = (capi.Sim3Result * n)()
+        arrs = []
+        for k, p in enumerate(problems):
+            r, a = bind_result(len(p["index"]))
+            rs[k] = r
+            arrs.append(a)
+        capi.check(self.lib.osh_sim3_optimize(self.ctx, n, probs, rs), "osh_sim3_optimize", self.lib)
+        return [read_result(rs[k], arrs[k]) for k in range(n)]
+
+    def linearize_sim3(self, pk):
+        """``osh_sim3_linearize``: robust chi2, H (7x7) and b of the first linearisation of one problem."""
+        H = np.zeros((7, 7)); b = np.zeros(7); chi2 = C.c_double(0.0)
+        from .synth_sim3 import problem
+        keep = []
+        p = problem(pk, keep)
+        capi.check(self.lib.osh_sim3_linearize(self.ctx, C.byref(p), capi.ptr(H, capi.c_double_p), capi.ptr(b, capi.c_double_p),
+                                               C.byref(chi2)), "osh_sim3_linearize", self.lib)
+        return chi2.value, H, b
+
     def optimize_poses_inertial(self, frames):
         """``osh_posei_optimize``: Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame for every frame of the batch."""
         from .synth_inertial import PoseiResultArrays

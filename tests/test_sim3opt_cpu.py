@@ -1,0 +1,78 @@
+"""OptimizeSim3 without a device: the numpy restatement (recovery, fixed scale, its numeric Jacobian) and the host layer's pair
+walk (osh_host_pack_sim3) against synth_sim3's restatement of it."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import sim3opt_numpy as sn
+from orb_slam3_study_kr_amd import capi
+from orb_slam3_study_kr_amd import synth_sim3 as ss
+
+
+@pytest.mark.parametrize("fix_scale", [False, True])
+def test_restatement_recovers_known_s12(fix_scale):
+    case = ss.make_case(2, 100, 0.0, init_perturb=0.05, fix_scale=fix_scale)
+    r = sn.run(ss.exact_pack(case))
+    assert r.round2 and r.n_in == len(r.outlier)
+    assert np.abs(r.S12 - case.S12_true).max() < 1e-9
+
+
+def test_fix_scale_keeps_s_bit_for_bit():
+    pk = ss.pack(ss.make_case(5, 200, 0.2, n_no_i2=3, fix_scale=True))
+    pk["S12"][7] = 1.0 + 2.0 ** -30
+    r = sn.run(pk)
+    assert r.round2 and r.S12[7] == pk["S12"][7]
+    J12, J21 = sn.jacobians(pk, pk["S12"])
+    assert np.all(J12[..., 6] == 0.0) and np.all(J21[..., 6] == 0.0)
+
+
+def test_numeric_jacobian_agrees_with_a_larger_step():
+    # Pinhole only: KannalaBrandt8 rounds theta and psi to float32, so its 1e-9 differences are quantised (that is the reference)
+    pk = ss.pack(ss.make_case(9, 150, 0.0))
+    J12, J21 = sn.jacobians(pk, pk["S12"])
+    K12, K21 = sn.jacobians(pk, pk["S12"], delta=1e-5)
+    for J, K in ((J12, K12), (J21, K21)):
+        assert np.abs(J - K).max() <= 1e-5 * np.abs(K).max()
+
+
+def _host_pack(case):
+    lib = capi.load_host_library()
+    inp = ss.host_input(case)
+    M = len(case.matches1)
+    idx = np.zeros(M, np.int32)
+    arr = {k: np.zeros((M, w)) for k, w in (("X1c", 3), ("X2c", 3), ("obs1", 2), ("obs2", 2), ("info1", 1), ("info2", 1))}
+    prob = capi.Sim3Problem()
+    n = lib.osh_host_pack_sim3(C.byref(inp), M, C.byref(prob), capi.ptr(idx, capi.c_int32_p),
+                               *[capi.ptr(arr[k], capi.c_double_p) for k in ("X1c", "X2c", "obs1", "obs2", "info1", "info2")])
+    return n, idx, arr, prob
+
+
+@pytest.mark.parametrize("all_points", [True, False])
+@pytest.mark.parametrize("kb8", [False, True])
+def test_host_pack_matches_the_walk(all_points, kb8):
+    case = ss.make_case(21, 200, 0.2, n_no_i2=7, n_bad=6, n_null_mp1=5, n_neg_depth=4, kb8=kb8, all_points=all_points)
+    # give the i2 < 0 points a tracked level different from 0, so that an octave taken from mnTrackScaleLevel would show
+    case.mp_track_level[:] = 3
+    pk = ss.pack(case)
+    n, idx, arr, prob = _host_pack(case)
+    assert n == len(pk["index"]) == prob.n_pairs
+    assert np.array_equal(idx[:n], pk["index"])
+    for k in ("X1c", "X2c", "obs1", "obs2", "info1", "info2"):
+        assert np.array_equal(arr[k][:n].reshape(pk[k].shape), pk[k]), k
+    assert list(prob.S12) == list(pk["S12"]) and prob.fix_scale == int(pk["fix_scale"]) and prob.th2 == np.float32(pk["th2"])
+    assert list(prob.cam1) == list(pk["cam1"]) and list(prob.cam2) == list(pk["cam2"]) and prob.kb8_1 == prob.kb8_2 == int(kb8)
+    # the special slots: bad points, NULL pMP1 and points behind pKF2 never make a pair; i2 < 0 pairs only with bAllPoints
+    N = 200
+    specials = dict(no_i2=range(N, N + 7), bad=range(N + 7, N + 13), null=range(N + 13, N + 18), neg=range(N + 18, N + 22))
+    got = set(pk["index"].tolist())
+    for k in ("bad", "null", "neg"):
+        assert not got & set(specials[k]), k
+    no_i2 = sorted(got & set(specials["no_i2"]))
+    assert len(no_i2) == (7 if all_points else 0)
+    for i in no_i2:
+        r = int(np.where(pk["index"] == i)[0][0])
+        assert abs(pk["obs2"][r, 0]) < 5 and abs(pk["obs2"][r, 1]) < 5           # normalised coordinates, not pixels
+        assert pk["info2"][r] == float(case.kf2["inv_level_sigma2"][0])           # KeyPoint(pt, size): octave 0
