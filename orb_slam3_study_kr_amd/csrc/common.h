@@ -4,6 +4,8 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
+#include <algorithm>
+#include <initializer_list>
 #include "../../include/orbslam3_hip.h"
 
 namespace osh {
@@ -23,12 +25,30 @@ const char* get_error();
 
 #define OSH_TRY(expr) do { int _rc = (expr); if (_rc != OSH_OK) return _rc; } while (0)
 
-// The paths that run on an osh_lba_ctx besides the visual BA (liba_device.hip, pose_device.hip, posei_device.hip) share its
-// device and stream, and keep their staging and work buffers with it (defined in lba_device.hip).
+// The solvers that run on an osh_lba_ctx besides the visual BA (pose_device.hip, posei_device.hip, sim3opt_device.hip,
+// liba_device.hip and the pose graphs of pgo_env.h) share its device and stream, and keep their staging and work buffers in its
+// attachment slots (a StagedCall each, PgoBuffers for the pose graphs; defined in lba_device.hip).
 enum LbaAttachSlot { kAttachLiba = 0, kAttachPose = 1, kAttachPosei = 2, kAttachPgo = 3, kAttachSim3 = 4, kAttachCount };
+// The context's device (made current) and stream.
 int lba_stream(osh_lba_ctx* c, int* device, hipStream_t* stream);
 // The context's pointer for `slot` (null until the caller stores its state there); osh_lba_destroy hands it to free_fn.
 void** lba_attachment(osh_lba_ctx* c, LbaAttachSlot slot, void (*free_fn)(void*));
+// The T kept in `slot`, created on first use and deleted by osh_lba_destroy (null without a context).
+template <class T>
+T* attachment(osh_lba_ctx* c, LbaAttachSlot slot) {
+  void** p = lba_attachment(c, slot, [](void* q) { delete static_cast<T*>(q); });
+  if (!p) { set_error("no context"); return nullptr; }
+  if (!*p) *p = new T();
+  return static_cast<T*>(*p);
+}
+
+// OSH_ERR_DEVICE (with `what` in the message) if the last kernel launch failed.
+int launch_check(const char* what);
+// Opts each kernel in to `bytes` of dynamic LDS on `device`, the current device; the attribute is per kernel and device, so it is set
+// once per pair in the process.
+int allow_dynamic_lds(int device, int bytes, std::initializer_list<const void*> kernels);
+template <class... K>
+int allow_dynamic_lds(int device, int bytes, K... kernels) { return allow_dynamic_lds(device, bytes, {(const void*)kernels...}); }
 
 // Simple growable device buffer (never shrinks; reused across batches).
 struct DevBuf {
@@ -61,12 +81,45 @@ struct PinBuf {
   void* reserve(size_t bytes) {
     if (bytes <= cap) return p;
     release();
-    const size_t want = bytes + bytes / 8 + 4096;
+    const size_t want = bytes + bytes / 8 + 4096;   // slack, as DevBuf: pinning is slow, a slightly larger batch reuses the buffer
     if (hipHostMalloc(&p, want) != hipSuccess) { p = nullptr; cap = 0; return nullptr; }
     cap = want;
     return p;
   }
   void release() { if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; } }
+};
+
+// One section of a Layout: an offset, turned into a typed pointer in a given base (host staging or device arena).
+template <class T>
+struct Section {
+  size_t off;
+  T* in(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+};
+// Sections laid out one after another, each 256-byte aligned and at least 8 bytes long (an empty one still has an address of its own).
+struct Layout {
+  size_t bytes = 0;
+  template <class T>
+  Section<T> take(size_t count) {
+    const Section<T> s{bytes};
+    bytes = (bytes + std::max<size_t>(count * sizeof(T), 8) + 255) & ~(size_t)255;
+    return s;
+  }
+};
+
+// The buffers of a one-launch solver call: the inputs staged in one pinned buffer and uploaded in one copy, the results downloaded in
+// one copy into another (a copy per array cost more than a single frame's solve).  The device arena is [in | out | work].
+struct StagedCall {
+  PinBuf h_in, h_out;
+  DevBuf arena;
+  size_t in_bytes = 0, out_bytes = 0;
+  int reserve(const Layout& in, const Layout& out, size_t work_bytes = 0, size_t min_arena_bytes = 0);
+  char* host_in() const { return static_cast<char*>(h_in.p); }
+  char* host_out() const { return static_cast<char*>(h_out.p); }
+  char* dev_in() const { return arena.as<char>(); }
+  char* dev_out() const { return dev_in() + in_bytes; }
+  char* dev_work() const { return dev_out() + out_bytes; }
+  int upload(hipStream_t s);     // h_in -> [in]
+  int download(hipStream_t s);   // [out] -> h_out, then the stream synchronised
 };
 
 // Per-kernel HIP-event timing on one stream.

@@ -30,7 +30,6 @@
 #include <cstdio>
 #include <atomic>
 #include <chrono>
-#include <mutex>
 #include <thread>
 #include "lba_math.h"
 #include "ldlt_block.h"
@@ -1413,12 +1412,6 @@ struct osh_lba_ctx {
   template <class T> T* dsec(int s) const { return reinterpret_cast<T*>(static_cast<unsigned char*>(d_arena[pb.sec_arena(s)].p) + pb.sec_off(s)); }
 };
 
-static int launch_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("kernel launch %s failed: %s", what, hipGetErrorString(e)); return OSH_ERR_DEVICE; }
-  return OSH_OK;
-}
-
 extern "C" int osh_lba_create(int device, osh_lba_ctx** out) {
   if (!out) { set_error("osh_lba_create: out is NULL"); return OSH_ERR_INVALID; }
   int n = 0;
@@ -1436,6 +1429,7 @@ extern "C" int osh_lba_create(int device, osh_lba_ctx** out) {
 int osh::lba_stream(osh_lba_ctx* c, int* device, hipStream_t* stream) {
   if (!c) { set_error("null context"); return OSH_ERR_INVALID; }
   *device = c->device; *stream = c->stream;
+  OSH_HIP(hipSetDevice(c->device));
   return OSH_OK;
 }
 
@@ -1615,24 +1609,12 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
     c->kp_backsub = f32 ? k_backsub<false, true> : k_backsub<false, false>; c->kp_debug_hpl = k_debug_hpl<false>;
   }
 
-  // opt in to large dynamic LDS: the attribute is per device, so once per device of the process
-  static std::mutex attr_mu;
-  static std::vector<int> attr_devices;
-  std::lock_guard<std::mutex> attr_lock(attr_mu);
-  if (std::find(attr_devices.begin(), attr_devices.end(), c->device) == attr_devices.end()) {
-#define OSH_SOLVE_ATTR(NB, NT) OSH_HIP(hipFuncSetAttribute((const void*)k_solve<NB, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64))
-    OSH_SOLVE_ATTR(24, kSolveThreadsBatch); OSH_SOLVE_ATTR(12, kSolveThreadsBatch); OSH_SOLVE_ATTR(6, kSolveThreadsBatch);
-    OSH_SOLVE_ATTR(24, kSolveThreadsLatency); OSH_SOLVE_ATTR(12, kSolveThreadsLatency); OSH_SOLVE_ATTR(6, kSolveThreadsLatency);
-#undef OSH_SOLVE_ATTR
-#define OSH_LM_ATTR(K) \
-    OSH_HIP(hipFuncSetAttribute((const void*)K<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64)); \
-    OSH_HIP(hipFuncSetAttribute((const void*)K<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64)); \
-    OSH_HIP(hipFuncSetAttribute((const void*)K<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64)); \
-    OSH_HIP(hipFuncSetAttribute((const void*)K<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-    OSH_LM_ATTR(k_backsub) OSH_LM_ATTR(k_lin_lm) OSH_LM_ATTR(k_residual)
-#undef OSH_LM_ATTR
-    attr_devices.push_back(c->device);
-  }
+  // opt in to large dynamic LDS
+  constexpr int kTB = kSolveThreadsBatch, kTL = kSolveThreadsLatency;
+  OSH_TRY(allow_dynamic_lds(c->device, 160 * 1024 - 64, k_solve<24, kTB>, k_solve<12, kTB>, k_solve<6, kTB>, k_solve<24, kTL>,
+                            k_solve<12, kTL>, k_solve<6, kTL>, k_backsub<false, false>, k_backsub<false, true>, k_backsub<true, false>,
+                            k_backsub<true, true>, k_lin_lm<false, false>, k_lin_lm<false, true>, k_lin_lm<true, false>, k_lin_lm<true, true>,
+                            k_residual<false, false>, k_residual<false, true>, k_residual<true, false>, k_residual<true, true>));
   c->n_windows = nw;
   return OSH_OK;
 }

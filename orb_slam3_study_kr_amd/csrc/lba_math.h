@@ -642,6 +642,19 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+// Sum over a block of NT threads, every thread ends with the total: wave_sum in each wavefront, the wavefronts' sums parked in
+// sh[NT / 64] and added in wavefront order (deterministic).  Both barriers are its own.
+template <int NT>
+__device__ __forceinline__ double block_sum_all(double v, double* sh) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int k = 0; k < NT / 64; ++k) t += sh[k];
+  return t;
+}
 // Sum over the wavefront without the LDS crossbar: four DPP steps leave every lane with the sum of its row of 16, the four row
 // sums are then read as scalars and added in row order.  (wave_sum's xor butterfly is 12 ds_bpermute per value.)
 template <int CTRL>

@@ -1294,24 +1294,6 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
 using namespace osh;
 
 namespace {
-struct PinnedBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-  void* reserve(size_t bytes) {
-    if (bytes <= cap) return p;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipHostMalloc(&p, want) != hipSuccess) { p = nullptr; return nullptr; }
-    cap = want;
-    return p;
-  }
-};
-struct LibaBuffers {
-  PinnedBuf h_in, h_out;
-  DevBuf arena;
-};
-
 thread_local int g_liba_last_group = 0;
 thread_local long long g_liba_last_prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 }  // namespace
@@ -1321,7 +1303,6 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(lba_stream(ctx, &device, &s));
-  OSH_HIP(hipSetDevice(device));
   std::vector<LibaDesc> h_desc(nw);
   size_t K = 0, NV = 0, L = 0, E = 0, NL = 0, Htot = 0, btot = 0, LO = 0, PO = 0, EF = 0, LP = 0;
   int n_max = 0;
@@ -1422,36 +1403,44 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
       if (15 * (span + 1) <= d.n / 2) { d.il = 1; d.bw_kf = span; d.bw = 15 * (span + 1) - 1; }
     }
   }
-  // ---- pack: every input array goes into ONE pinned staging buffer and travels in ONE copy (an upload per array cost more than
-  // the optimisation of a single window); the device pointers are offsets into the arena.
-  // staging and work buffers live with the context (one solver at a time per context, as for the visual path)
-  void** slot = lba_attachment(ctx, kAttachLiba, [](void* q) { delete static_cast<LibaBuffers*>(q); });
-  if (!slot) { set_error("osh_liba_solve: no context"); return OSH_ERR_INVALID; }
-  if (!*slot) *slot = new LibaBuffers();
-  LibaBuffers& B = *static_cast<LibaBuffers*>(*slot);
-  size_t in_bytes = 0;
-  auto take = [&](size_t bytes) { const size_t o = in_bytes; in_bytes = (in_bytes + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_desc = take(nw * sizeof(LibaDesc)), o_pose = take(K * 24 * 8), o_vba = take(NV * 9 * 8), o_pts = take(L * 3 * 8), o_obs = take(E * 3 * 8),
-               o_info = take(E * 8), o_ep = take(E * 4), o_el = take(E * 4), o_eo = take(E * 4), o_lmo = take(LO * 4), o_po = take(PO * 4),
-               o_pel = take(E * 4), o_lmpe = take(LP * 4), o_lp = take(NL * 4), o_lc = take(NL * 4), o_kind = take(E), o_rob = take(NL),
-               o_pre = take(NL * OSH_PREINT_FLOATS * 4), o_li = take(NL * 81 * 8), o_lg = take(NL * 9 * 8), o_la = take(NL * 9 * 8),
-               o_bar = take(nw * sizeof(unsigned)), o_abort = take(sizeof(int)), o_col = take(NL * 4), o_lb = take(NL * 4);
-  char* hs = static_cast<char*>(B.h_in.reserve(in_bytes));
-  if (!hs) { set_error("osh_liba_solve: pinned staging allocation of %zu bytes failed", in_bytes); return OSH_ERR_DEVICE; }
-  LibaDesc* h_descp = reinterpret_cast<LibaDesc*>(hs + o_desc);
-  double* h_pose = reinterpret_cast<double*>(hs + o_pose); double* h_vba = reinterpret_cast<double*>(hs + o_vba);
-  double* h_pts = reinterpret_cast<double*>(hs + o_pts); double* h_obs = reinterpret_cast<double*>(hs + o_obs);
-  double* h_info = reinterpret_cast<double*>(hs + o_info);
-  int* h_ep = reinterpret_cast<int*>(hs + o_ep); int* h_el = reinterpret_cast<int*>(hs + o_el); int* h_eo = reinterpret_cast<int*>(hs + o_eo);
-  int* h_lmo = reinterpret_cast<int*>(hs + o_lmo); int* h_po = reinterpret_cast<int*>(hs + o_po); int* h_pel = reinterpret_cast<int*>(hs + o_pel);
-  int* h_lmpe = reinterpret_cast<int*>(hs + o_lmpe); int* h_lp = reinterpret_cast<int*>(hs + o_lp); int* h_lc = reinterpret_cast<int*>(hs + o_lc); int* h_lb = reinterpret_cast<int*>(hs + o_lb);
-  unsigned char* h_kind = reinterpret_cast<unsigned char*>(hs + o_kind); unsigned char* h_rob = reinterpret_cast<unsigned char*>(hs + o_rob);
-  float* h_pre = reinterpret_cast<float*>(hs + o_pre);
-  int* h_col = reinterpret_cast<int*>(hs + o_col);
-  double* h_li = reinterpret_cast<double*>(hs + o_li); double* h_lg = reinterpret_cast<double*>(hs + o_lg); double* h_la = reinterpret_cast<double*>(hs + o_la);
+  // ---- pack: every input array goes into ONE pinned staging buffer and travels in ONE copy; the results come back in one copy
+  // (LibaOut per window, abort word, final poses / velocities+biases / points, edge chi2 and depth flags), and the work buffers follow
+  // them in the device arena.  All of it lives with the context (one solver at a time per context, as for the visual path).
+  Layout in, out, work;
+  const auto o_desc = in.take<LibaDesc>(nw);
+  const auto o_pose = in.take<double>(K * 24), o_vba = in.take<double>(NV * 9), o_pts = in.take<double>(L * 3), o_obs = in.take<double>(E * 3),
+             o_info = in.take<double>(E);
+  const auto o_ep = in.take<int>(E), o_el = in.take<int>(E), o_eo = in.take<int>(E), o_lmo = in.take<int>(LO), o_po = in.take<int>(PO),
+             o_pel = in.take<int>(E), o_lmpe = in.take<int>(LP), o_lp = in.take<int>(NL), o_lc = in.take<int>(NL);
+  const auto o_kind = in.take<unsigned char>(E), o_rob = in.take<unsigned char>(NL);
+  const auto o_pre = in.take<float>(NL * OSH_PREINT_FLOATS);
+  const auto o_li = in.take<double>(NL * 81), o_lg = in.take<double>(NL * 9), o_la = in.take<double>(NL * 9);
+  const auto o_bar = in.take<unsigned>(nw);
+  const auto o_abort = in.take<int>(1), o_col = in.take<int>(NL), o_lb = in.take<int>(NL);
+  const auto r_out = out.take<LibaOut>(nw);
+  const auto r_abort = out.take<int>(1);
+  const auto r_pose = out.take<double>((btot / 15) * 24), r_vba = out.take<double>((btot / 15) * 9), r_pts = out.take<double>(L * 3),
+             r_chi2 = out.take<double>(E);
+  const auto r_depth = out.take<unsigned char>(E);
+  const auto a_pose1 = work.take<double>(K * 24), a_vba1 = work.take<double>(NV * 9), a_pts1 = work.take<double>(L * 3), a_eh = work.take<double>(E * 9),
+             a_ep = work.take<double>(EF * 27), a_bfull = work.take<double>(btot), a_Hpl = work.take<double>(EF * 18), a_BD = work.take<double>(EF * 18),
+             a_Hll = work.take<double>(L * 6), a_bl = work.take<double>(L * 3), a_dinv = work.take<double>(L * 9), a_H = work.take<double>(Htot),
+             a_S = work.take<double>(Htot), a_b = work.take<double>(btot), a_bs = work.take<double>(btot), a_x = work.take<double>(btot),
+             a_linkQ = work.take<double>(NL * kLinkQ), a_ppart = work.take<double>((btot / 15) * kPoseChunks * 27),
+             a_red = work.take<double>((size_t)nw * 4 * kLG * 2), a_ctrl = work.take<double>((size_t)nw * 4);
+  StagedCall* B = attachment<StagedCall>(ctx, kAttachLiba);
+  if (!B) return OSH_ERR_INVALID;
+  OSH_TRY(B->reserve(in, out, work.bytes, (size_t)64 << 20));   // an arena of at least 64 MiB: large page fragments
+  char* const hs = B->host_in();
+  double *h_pose = o_pose.in(hs), *h_vba = o_vba.in(hs), *h_pts = o_pts.in(hs), *h_obs = o_obs.in(hs), *h_info = o_info.in(hs);
+  int *h_ep = o_ep.in(hs), *h_el = o_el.in(hs), *h_eo = o_eo.in(hs), *h_lmo = o_lmo.in(hs), *h_po = o_po.in(hs), *h_pel = o_pel.in(hs);
+  int *h_lmpe = o_lmpe.in(hs), *h_lp = o_lp.in(hs), *h_lc = o_lc.in(hs), *h_lb = o_lb.in(hs), *h_col = o_col.in(hs);
+  unsigned char *h_kind = o_kind.in(hs), *h_rob = o_rob.in(hs);
+  float* h_pre = o_pre.in(hs);
+  double *h_li = o_li.in(hs), *h_lg = o_lg.in(hs), *h_la = o_la.in(hs);
   std::memset(h_lmpe, 0xff, LP * 4);
-  std::memset(hs + o_bar, 0, nw * sizeof(unsigned));
-  std::memset(hs + o_abort, 0, sizeof(int));
+  std::memset(o_bar.in(hs), 0, nw * sizeof(unsigned));
+  std::memset(o_abort.in(hs), 0, sizeof(int));
   std::vector<int> cnt, fill, order;
   for (int w = 0; w < nw; ++w) {
     const osh_liba_problem& p = pr[w];
@@ -1533,64 +1522,31 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
       h_desc[w].n_colours = std::max(h_desc[w].n_colours, col + 1);
     }
   }
-  std::memcpy(h_descp, h_desc.data(), nw * sizeof(LibaDesc));
-  // ---- result arena (one copy back): LibaOut per window, abort word, final poses / velocities+biases / points, edge chi2 and depth flags
-  size_t out_bytes = 0;
-  auto take_out = [&](size_t bytes) { const size_t o = out_bytes; out_bytes = (out_bytes + bytes + 255) & ~(size_t)255; return o; };
-  const size_t r_out = take_out(nw * sizeof(LibaOut)), r_abort = take_out(sizeof(int)), r_pose = take_out((btot / 15) * 24 * 8), r_vba = take_out((btot / 15) * 9 * 8),
-               r_pts = take_out(L * 3 * 8), r_chi2 = take_out(E * 8), r_depth = take_out(E);
-  char* hr = static_cast<char*>(B.h_out.reserve(out_bytes));
-  if (!hr) { set_error("osh_liba_solve: pinned result allocation of %zu bytes failed", out_bytes); return OSH_ERR_DEVICE; }
-  auto R = [](DevBuf& b, size_t bytes) { return b.reserve(std::max<size_t>(bytes, (size_t)64 << 20)); };   // at least 64 MiB: large page fragments
-  // ONE device arena: inputs (uploaded in one copy), results (downloaded in one copy), then the work buffers
-  size_t dev_bytes = 0;
-  auto take_dev = [&](size_t bytes) { const size_t o = dev_bytes; dev_bytes = (dev_bytes + std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return o; };
-  const size_t a_in = take_dev(in_bytes), a_res = take_dev(out_bytes), a_pose1 = take_dev(K * 24 * 8), a_vba1 = take_dev(NV * 9 * 8), a_pts1 = take_dev(L * 3 * 8),
-               a_eh = take_dev(E * 9 * 8), a_ep = take_dev(EF * 27 * 8), a_bfull = take_dev(btot * 8), a_Hpl = take_dev(EF * 18 * 8), a_BD = take_dev(EF * 18 * 8),
-               a_Hll = take_dev(L * 6 * 8), a_bl = take_dev(L * 3 * 8), a_dinv = take_dev(L * 9 * 8), a_H = take_dev(Htot * 8), a_S = take_dev(Htot * 8),
-               a_b = take_dev(btot * 8), a_bs = take_dev(btot * 8), a_x = take_dev(btot * 8), a_linkQ = take_dev(NL * kLinkQ * 8),
-               a_ppart = take_dev((btot / 15) * kPoseChunks * 27 * 8), a_red = take_dev((size_t)nw * 4 * kLG * 2 * 8), a_ctrl = take_dev((size_t)nw * 4 * 8);
-  OSH_TRY(R(B.arena, dev_bytes));
-  char* const dbase = B.arena.as<char>();
-  auto dptr = [&](size_t off) { return reinterpret_cast<double*>(dbase + off); };
-  char* din = dbase + a_in;
-  char* dres = dbase + a_res;
-  OSH_HIP(hipMemcpyAsync(din, hs, in_bytes, hipMemcpyHostToDevice, s));
+  std::memcpy(o_desc.in(hs), h_desc.data(), nw * sizeof(LibaDesc));
+  OSH_TRY(B->upload(s));
+  char* const din = B->dev_in();
+  char* const dres = B->dev_out();
+  char* const dwork = B->dev_work();
   LibaView v{};
-  v.desc = reinterpret_cast<const LibaDesc*>(din + o_desc); v.out = reinterpret_cast<LibaOut*>(dres + r_out);
-  v.pose[0] = reinterpret_cast<double*>(din + o_pose); v.vba[0] = reinterpret_cast<double*>(din + o_vba); v.pts[0] = reinterpret_cast<double*>(din + o_pts);
-  v.pose[1] = dptr(a_pose1); v.vba[1] = dptr(a_vba1); v.pts[1] = dptr(a_pts1);
-  v.e_pose = reinterpret_cast<const int*>(din + o_ep); v.e_point = reinterpret_cast<const int*>(din + o_el);
-  v.e_kind = reinterpret_cast<const unsigned char*>(din + o_kind); v.e_obs = reinterpret_cast<const double*>(din + o_obs);
-  v.e_info = reinterpret_cast<const double*>(din + o_info); v.e_orig = reinterpret_cast<const int*>(din + o_eo);
-  v.lm_off = reinterpret_cast<const int*>(din + o_lmo); v.pel_off = reinterpret_cast<const int*>(din + o_po);
-  v.pel_edge = reinterpret_cast<const int*>(din + o_pel); v.lm_pose_edge = reinterpret_cast<const int*>(din + o_lmpe);
-  v.link_prev = reinterpret_cast<const int*>(din + o_lp); v.link_cur = reinterpret_cast<const int*>(din + o_lc); v.link_bias = reinterpret_cast<const int*>(din + o_lb);
-  v.link_preint = reinterpret_cast<const float*>(din + o_pre); v.link_info = reinterpret_cast<const double*>(din + o_li);
-  v.link_info_g = reinterpret_cast<const double*>(din + o_lg); v.link_info_a = reinterpret_cast<const double*>(din + o_la);
-  v.link_robust = reinterpret_cast<const unsigned char*>(din + o_rob);
-  v.Hpl = dptr(a_Hpl); v.BD = dptr(a_BD); v.Hll = dptr(a_Hll); v.bl = dptr(a_bl);
-  v.dinv = dptr(a_dinv); v.H = dptr(a_H); v.b = dptr(a_b); v.S = dptr(a_S); v.bs = dptr(a_bs);
-  v.x = dptr(a_x); v.linkQ = dptr(a_linkQ); v.ppart = dptr(a_ppart);
-  v.bar = reinterpret_cast<unsigned*>(din + o_bar); v.abort_flag = reinterpret_cast<int*>(din + o_abort);
-  v.red = dptr(a_red); v.ctrl = dptr(a_ctrl); v.nw = nw;
+  v.desc = o_desc.in(din); v.out = r_out.in(dres);
+  v.pose[0] = o_pose.in(din); v.vba[0] = o_vba.in(din); v.pts[0] = o_pts.in(din);
+  v.pose[1] = a_pose1.in(dwork); v.vba[1] = a_vba1.in(dwork); v.pts[1] = a_pts1.in(dwork);
+  v.e_pose = o_ep.in(din); v.e_point = o_el.in(din); v.e_kind = o_kind.in(din); v.e_obs = o_obs.in(din); v.e_info = o_info.in(din); v.e_orig = o_eo.in(din);
+  v.lm_off = o_lmo.in(din); v.pel_off = o_po.in(din); v.pel_edge = o_pel.in(din); v.lm_pose_edge = o_lmpe.in(din);
+  v.link_prev = o_lp.in(din); v.link_cur = o_lc.in(din); v.link_bias = o_lb.in(din);
+  v.link_preint = o_pre.in(din); v.link_info = o_li.in(din); v.link_info_g = o_lg.in(din); v.link_info_a = o_la.in(din);
+  v.link_robust = o_rob.in(din);
+  v.Hpl = a_Hpl.in(dwork); v.BD = a_BD.in(dwork); v.Hll = a_Hll.in(dwork); v.bl = a_bl.in(dwork);
+  v.dinv = a_dinv.in(dwork); v.H = a_H.in(dwork); v.b = a_b.in(dwork); v.S = a_S.in(dwork); v.bs = a_bs.in(dwork);
+  v.x = a_x.in(dwork); v.linkQ = a_linkQ.in(dwork); v.ppart = a_ppart.in(dwork);
+  v.bar = o_bar.in(din); v.abort_flag = o_abort.in(din);
+  v.red = a_red.in(dwork); v.ctrl = a_ctrl.in(dwork); v.nw = nw;
   v.force_heavy = getenv("OSH_LIBA_HEAVY_BARRIER") ? 1 : 0;
-  v.eh = dptr(a_eh); v.ep = dptr(a_ep); v.bfull = dptr(a_bfull); v.E_total = E; v.EF_total = EF;
-  v.link_colour = reinterpret_cast<const int*>(din + o_col);
-  v.res_abort = reinterpret_cast<int*>(dres + r_abort); v.res_pose = reinterpret_cast<double*>(dres + r_pose); v.res_vba = reinterpret_cast<double*>(dres + r_vba);
-  v.res_pts = reinterpret_cast<double*>(dres + r_pts); v.out_chi2 = reinterpret_cast<double*>(dres + r_chi2);
-  v.out_depth = reinterpret_cast<unsigned char*>(dres + r_depth);
-  {
-    // opt in to large dynamic LDS: the attribute is per device, so once per device of the process
-    static std::mutex attr_mu;
-    static std::vector<int> attr_devices;
-    std::lock_guard<std::mutex> attr_lock(attr_mu);
-    if (std::find(attr_devices.begin(), attr_devices.end(), device) == attr_devices.end()) {
-      OSH_HIP(hipFuncSetAttribute((const void*)k_liba<24>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-      OSH_HIP(hipFuncSetAttribute((const void*)k_liba<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-      attr_devices.push_back(device);
-    }
-  }
+  v.eh = a_eh.in(dwork); v.ep = a_ep.in(dwork); v.bfull = a_bfull.in(dwork); v.E_total = E; v.EF_total = EF;
+  v.link_colour = o_col.in(din);
+  v.res_abort = r_abort.in(dres); v.res_pose = r_pose.in(dres); v.res_vba = r_vba.in(dres);
+  v.res_pts = r_pts.in(dres); v.out_chi2 = r_chi2.in(dres); v.out_depth = r_depth.in(dres);
+  OSH_TRY(allow_dynamic_lds(device, 160 * 1024 - 64, k_liba<24>, k_liba<6>));
   // blocks per window: the tracker's single window (and small batches) get a group of 32 = one whole XCD; a large batch fills the chip
   // with one block per window.  A group needs all its blocks resident (they meet at barriers): the grid is kept within what the device
   // holds at once (occupancy query) and launched as an ordinary kernel.  (hipLaunchCooperativeKernel would check the same, but it
@@ -1615,20 +1571,19 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
     void* args[] = {(void*)&v, (void*)&W_arg, (void*)&g_arg};
     const hipError_t le = hipLaunchKernel(kfn, dim3((unsigned)((nw + 7) / 8 * 8 * Gx)), dim3(kLT), args, lds, s);
     if (le != hipSuccess) { set_error("k_liba launch failed: %s", hipGetErrorString(le)); return OSH_ERR_DEVICE; }
-    OSH_HIP(hipMemcpyAsync(hr, dres, out_bytes, hipMemcpyDeviceToHost, s));
-    OSH_HIP(hipStreamSynchronize(s));
-    return OSH_OK;
+    return B->download(s);
   };
   OSH_TRY(run(G, (G > 1 && getenv("OSH_LIBA_TEST_ABORT")) ? 1 : 0));
-  if (*reinterpret_cast<const int*>(hr + r_abort) && G > 1) {
+  char* const hr = B->host_out();
+  if (*r_abort.in(hr) && G > 1) {
     // A barrier of a block group gave up (blocks of other streams kept part of a group off the device for seconds): the same
     // problem once more with one block per window, which has no barrier to wait at.  The estimates live in the input arena: upload again.
-    OSH_HIP(hipMemcpyAsync(din, hs, in_bytes, hipMemcpyHostToDevice, s));
+    OSH_TRY(B->upload(s));
     G = 1;
     OSH_TRY(run(1, 0));
   }
-  if (*reinterpret_cast<const int*>(hr + r_abort)) { set_error("k_liba: a barrier of a window's block group did not complete (group of %d blocks)", G); return OSH_ERR_DEVICE; }
-  const LibaOut* h_out = reinterpret_cast<const LibaOut*>(hr + r_out);
+  if (*r_abort.in(hr)) { set_error("k_liba: a barrier of a window's block group did not complete (group of %d blocks)", G); return OSH_ERR_DEVICE; }
+  const LibaOut* h_out = r_out.in(hr);
   g_liba_last_group = G;
   std::memcpy(g_liba_last_prof, h_out[0].prof, sizeof(g_liba_last_prof));
   for (int w = 0; w < nw; ++w) {
@@ -1638,8 +1593,8 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
     r.status = OSH_OK; r.iterations = o.iterations; r.trials = o.trials; r.n_trace = o.n_trace;
     r.chi2_initial = o.chi2_initial; r.chi2_final = o.chi2_final;
     for (int k = 0; k < o.n_trace; ++k) { r.chi2_trace[k] = o.chi2_trace[k]; r.lambda_trace[k] = o.lambda_trace[k]; r.trials_trace[k] = o.trials_trace[k]; }
-    const double* q0 = reinterpret_cast<const double*>(hr + r_pose) + (size_t)(d.b_off / 15) * 24;
-    const double* s0 = reinterpret_cast<const double*>(hr + r_vba) + (size_t)(d.b_off / 15) * 9;
+    const double* q0 = r_pose.in(hr) + (size_t)(d.b_off / 15) * 24;
+    const double* s0 = r_vba.in(hr) + (size_t)(d.b_off / 15) * 9;
     for (int k = 0; k < d.N; ++k) {
       const double* q = q0 + (size_t)k * 24;
       if (r.pose_Rcw) std::memcpy(r.pose_Rcw + 9 * k, q, 72);
@@ -1650,9 +1605,9 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
       if (r.bias_g) std::memcpy(r.bias_g + 3 * k, s0 + (size_t)k * 9 + 3, 24);
       if (r.bias_a) std::memcpy(r.bias_a + 3 * k, s0 + (size_t)k * 9 + 6, 24);
     }
-    if (r.points && d.L) std::memcpy(r.points, reinterpret_cast<const double*>(hr + r_pts) + (size_t)d.pt_off * 3, (size_t)d.L * 24);
-    if (r.edge_chi2 && d.E) std::memcpy(r.edge_chi2, reinterpret_cast<const double*>(hr + r_chi2) + d.edge_off, (size_t)d.E * 8);
-    if (r.edge_depth_pos && d.E) std::memcpy(r.edge_depth_pos, reinterpret_cast<const unsigned char*>(hr + r_depth) + d.edge_off, (size_t)d.E);
+    if (r.points && d.L) std::memcpy(r.points, r_pts.in(hr) + (size_t)d.pt_off * 3, (size_t)d.L * 24);
+    if (r.edge_chi2 && d.E) std::memcpy(r.edge_chi2, r_chi2.in(hr) + d.edge_off, (size_t)d.E * 8);
+    if (r.edge_depth_pos && d.E) std::memcpy(r.edge_depth_pos, r_depth.in(hr) + d.edge_off, (size_t)d.E);
   }
   return OSH_OK;
 }

@@ -739,8 +739,7 @@ extern "C" int osh_orb_match(osh_orb_ctx* c) {
     if (v.n_split > 1) hipLaunchKernelGGL(k_orb_merge, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, v);
   }
   if (t) c->timer.end(s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("orb kernel launch failed: %s", hipGetErrorString(e)); return OSH_ERR_DEVICE; }
+  OSH_TRY(launch_check("orb search"));
   OSH_HIP(hipStreamSynchronize(s));
   if (c->timer.enabled) c->timer.collect();
   c->matched = true;
@@ -832,8 +831,7 @@ extern "C" int osh_orb_match_local_points(osh_orb_ctx* c, float nn_ratio, int32_
   }
   hipLaunchKernelGGL(k_orb_assign, dim3((unsigned)v.n_pairs), dim3(256), 0, s, v, r, c->d_assign.as<int>(), c->d_nmatch.as<int>());
   if (t1) c->timer.end(s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("orb kernel launch failed: %s", hipGetErrorString(e)); return OSH_ERR_DEVICE; }
+  OSH_TRY(launch_check("orb occupancy rounds"));
   OSH_HIP(hipMemcpyAsync(assignment, c->d_assign.p, nt * 4, hipMemcpyDeviceToHost, s));
   OSH_HIP(hipMemcpyAsync(n_matches, c->d_nmatch.p, (size_t)v.n_pairs * 4, hipMemcpyDeviceToHost, s));
   if (query_slot) OSH_HIP(hipMemcpyAsync(query_slot, c->d_claim.p, nq * 4, hipMemcpyDeviceToHost, s));
@@ -851,8 +849,7 @@ extern "C" int osh_orb_list_distances(osh_orb_ctx* c, int32_t* dist_out) {
   hipStream_t s = c->stream;
   OSH_TRY(c->d_ldist.reserve((size_t)c->list_total * 4));
   hipLaunchKernelGGL(k_orb_list_dist, dim3((unsigned)((c->list_longest_pair + 255) / 256), (unsigned)c->v.n_pairs), dim3(256), 0, s, c->v, c->d_ldist.as<int>());
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) { set_error("k_orb_list_dist launch failed: %s", hipGetErrorString(le)); return OSH_ERR_DEVICE; }
+  OSH_TRY(launch_check("k_orb_list_dist"));
   OSH_HIP(hipMemcpyAsync(dist_out, c->d_ldist.p, (size_t)c->list_total * 4, hipMemcpyDeviceToHost, s));
   OSH_HIP(hipStreamSynchronize(s));
   return OSH_OK;
@@ -921,8 +918,7 @@ extern "C" int osh_orb_frustum(osh_orb_ctx* c, const osh_frustum_frame* fr, cons
   f.fisheye = fr->fisheye ? 1 : 0;
   for (int k = 0; k < 4; ++k) f.kb[k] = fr->fisheye ? fr->kb8[k] : 0.f;
   hipLaunchKernelGGL(k_frustum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, f, n, c->d_fin.as<float4>(), c->d_fout.as<float4>());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("k_frustum launch failed: %s", hipGetErrorString(e)); return OSH_ERR_DEVICE; }
+  OSH_TRY(launch_check("k_frustum"));
   OSH_HIP(hipMemcpyAsync(c->h_fout.data(), c->d_fout.p, (size_t)n * 32, hipMemcpyDeviceToHost, s));
   OSH_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < n; ++i) {
@@ -947,8 +943,7 @@ extern "C" int osh_orb_distance_matrix(osh_orb_ctx* c, int32_t n, int32_t m, con
   OSH_HIP(hipMemcpyAsync(c->d_b.p, b, (size_t)m * 32, hipMemcpyHostToDevice, s));
   const size_t tot = (size_t)n * m;
   hipLaunchKernelGGL(k_orb_distance_matrix, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, n, m, c->d_a.as<uint4>(), c->d_b.as<uint4>(), c->d_dm.as<int>());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("k_orb_distance_matrix launch failed: %s", hipGetErrorString(e)); return OSH_ERR_DEVICE; }
+  OSH_TRY(launch_check("k_orb_distance_matrix"));
   OSH_HIP(hipMemcpyAsync(out, c->d_dm.p, tot * 4, hipMemcpyDeviceToHost, s));
   OSH_HIP(hipStreamSynchronize(s));
   return OSH_OK;

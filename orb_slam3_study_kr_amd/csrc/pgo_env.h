@@ -400,12 +400,6 @@ struct PgoBuffers {
   PinBuf h_red;
 };
 
-int launch_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("kernel launch %s failed: %s", what, hipGetErrorString(e)); return OSH_ERR_DEVICE; }
-  return OSH_OK;
-}
-
 struct LmResult {
   int iterations = 0, trials = 0, cur = 0;   // the returned states are d_x[cur]
   double chi2_initial = 0, chi2_final = 0, lambda0 = 0;
@@ -444,35 +438,30 @@ struct PgoRun {
   int upload(const double* x0, const double* meas, const int32_t* eij, const typename G::Aux* aux) {
     int device = 0;
     OSH_TRY(lba_stream(ctx, &device, &s));
-    OSH_HIP(hipSetDevice(device));
-    void** slot = lba_attachment(ctx, kAttachPgo, [](void* q) { delete static_cast<PgoBuffers*>(q); });
-    if (!slot) { set_error("%s: no context", G::kTag); return OSH_ERR_INVALID; }
-    if (!*slot) *slot = new PgoBuffers();
-    B = static_cast<PgoBuffers*>(*slot);
+    B = attachment<PgoBuffers>(ctx, kAttachPgo);
+    if (!B) return OSH_ERR_INVALID;
     const size_t n = P.n, E = std::max(P.E, 1), NT = P.NT;
-    auto layout = [&](uintptr_t base) {
-      size_t bytes = 0;
-      auto take = [&](auto*& d, size_t b) {
-        d = reinterpret_cast<std::remove_reference_t<decltype(d)>>(base + bytes);
-        bytes = (bytes + std::max<size_t>(b, 8) + 255) & ~(size_t)255;
-      };
-      take(d_x[0], n * G::kState * 8); take(d_x[1], n * G::kState * 8); take(d_aux, n * G::kAux * sizeof(typename G::Aux));
-      take(d_meas, E * G::kMeas * 8); take(d_J, E * 2 * G::D * G::M * 8); take(d_err, E * G::M * 8); take(d_chi, E * 8);
-      take(d_H, (size_t)P.nblk * G::D * G::D * 8); take(d_b, (size_t)P.N * 8 + 8); take(d_w, NT * kT * 8); take(d_z, NT * kT * 8);
-      take(d_red, 64); take(d_eij, E * 8); take(d_sys, n * 4); take(d_blk_a, (size_t)P.nblk * 4); take(d_blk_b, (size_t)P.nblk * 4);
-      take(d_ent_ptr, (size_t)(P.nblk + 1) * 4); take(d_ent, P.ent.size() * 4 + 4); take(d_toff, NT * 4); take(d_ttop, NT * 4);
-      take(d_act_ptr, (NT + 1) * 4); take(d_act, P.act.size() * 4); take(d_fail, 4);
-      return bytes;
-    };
-    const size_t bytes = layout(0);
-    OSH_TRY(B->arena.reserve(bytes));
+    Layout L;
+    const auto s_x0 = L.take<double>(n * G::kState), s_x1 = L.take<double>(n * G::kState);
+    const auto s_aux = L.take<typename G::Aux>(n * G::kAux);
+    const auto s_meas = L.take<double>(E * G::kMeas), s_J = L.take<double>(E * 2 * G::D * G::M), s_err = L.take<double>(E * G::M), s_chi = L.take<double>(E),
+               s_H = L.take<double>((size_t)P.nblk * G::D * G::D), s_b = L.take<double>((size_t)P.N + 1), s_w = L.take<double>(NT * kT),
+               s_z = L.take<double>(NT * kT), s_red = L.take<double>(8);
+    const auto s_eij = L.take<int>(E * 2), s_sys = L.take<int>(n), s_blk_a = L.take<int>(P.nblk), s_blk_b = L.take<int>(P.nblk), s_ent_ptr = L.take<int>(P.nblk + 1),
+               s_ent = L.take<int>(P.ent.size() + 1), s_toff = L.take<int>(NT), s_ttop = L.take<int>(NT), s_act_ptr = L.take<int>(NT + 1),
+               s_act = L.take<int>(P.act.size()), s_fail = L.take<int>(1);
+    OSH_TRY(B->arena.reserve(L.bytes));
     OSH_TRY(B->tiles.reserve((size_t)P.ntiles * kTT * 8));
     OSH_TRY(B->V.reserve((size_t)P.max_act * kTT * 8));
     h_red = static_cast<double*>(B->h_red.reserve(64));
     if (!h_red) { set_error("%s: pinned allocation failed", G::kTag); return OSH_ERR_DEVICE; }
-    layout(reinterpret_cast<uintptr_t>(B->arena.p));
+    char* const a = B->arena.as<char>();
+    d_x[0] = s_x0.in(a); d_x[1] = s_x1.in(a); d_aux = s_aux.in(a); d_meas = s_meas.in(a); d_J = s_J.in(a); d_err = s_err.in(a); d_chi = s_chi.in(a);
+    d_H = s_H.in(a); d_b = s_b.in(a); d_w = s_w.in(a); d_z = s_z.in(a); d_red = s_red.in(a); d_eij = s_eij.in(a); d_sys = s_sys.in(a);
+    d_blk_a = s_blk_a.in(a); d_blk_b = s_blk_b.in(a); d_ent_ptr = s_ent_ptr.in(a); d_ent = s_ent.in(a); d_toff = s_toff.in(a); d_ttop = s_ttop.in(a);
+    d_act_ptr = s_act_ptr.in(a); d_act = s_act.in(a); d_fail = s_fail.in(a);
     // Jacobians of fixed sides are never written or read; zero the arena once per call so that nothing depends on its history
-    OSH_HIP(hipMemsetAsync(B->arena.p, 0, bytes, s));
+    OSH_HIP(hipMemsetAsync(B->arena.p, 0, L.bytes, s));
     auto up = [&](void* d, const void* h, size_t b) -> int { if (b) OSH_HIP(hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, s)); return OSH_OK; };
     OSH_TRY(up(d_x[0], x0, n * G::kState * 8));
     OSH_TRY(up(d_aux, aux, n * G::kAux * sizeof(typename G::Aux)));

@@ -42,18 +42,6 @@ struct PoseView {
   unsigned char* level;       // [NE] 1: classified outlier, outside the active set
 };
 
-// deterministic block sum: butterfly inside each wavefront, wavefronts added in order
-__device__ __forceinline__ double pose_block_sum(double v, double* sh) {
-  v = dev::wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int k = 0; k < kPT / 64; ++k) t += sh[k];
-  return t;
-}
-
 // edge residual / Jacobians through the frame's camera model; the pinhole instantiation carries no KannalaBrandt8 code
 template <bool KB8>
 __device__ __forceinline__ double pose_edge_residual(const PoseDesc& d, int kind, const double* qt, const double* X, const double* obs,
@@ -113,7 +101,7 @@ __device__ double pose_eval(const PoseView& v, const PoseDesc& d, EdgeCache& ec,
       acc += r0;
     } else acc += c;
   });
-  return pose_block_sum(acc, sh);
+  return dev::block_sum_all<kPT>(acc, sh);
 }
 
 template <bool KB8>
@@ -157,7 +145,7 @@ __global__ __launch_bounds__(kPT) void k_pose_opt(PoseView v) {
     // initializeOptimization(0): nothing to do without active edges
     int active = 0;
     for_edges(v, d, ec, [&](int, const double*, const double*, double, unsigned char& level, double&) { active += level ? 0 : 1; });
-    const bool any = pose_block_sum((double)active, sh) > 0.0;
+    const bool any = dev::block_sum_all<kPT>((double)active, sh) > 0.0;
     for (int it = 0; it < d.iters[round] && ok && any; ++it) {
       double qt[7];
 #pragma unroll
@@ -320,7 +308,7 @@ __global__ __launch_bounds__(kPT) void k_pose_opt(PoseView v) {
       const float th = kind != OSH_EDGE_STEREO ? d.chi2_mono[round] : d.chi2_stereo[round];
       if (chi2 > th) { level = 1; ++bad; } else level = 0;
     });
-    n_bad = (int)pose_block_sum((double)bad, sh);
+    n_bad = (int)dev::block_sum_all<kPT>((double)bad, sh);
     rounds = round + 1;
     if (tid == 0) { out.iterations[round] = cj; out.chi2_final[round] = last_chi; }
     if (round == 2) robust = false;
@@ -340,22 +328,6 @@ __global__ __launch_bounds__(kPT) void k_pose_opt(PoseView v) {
   }
 }
 
-struct PosePinned {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~PosePinned() { if (p) (void)hipHostFree(p); }
-  void* reserve(size_t bytes) {
-    if (bytes <= cap) return p;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipHostMalloc(&p, want) != hipSuccess) { p = nullptr; return nullptr; }
-    cap = want;
-    return p;
-  }
-};
-// staging and device arena of osh_pose_optimize: kept with the context (released by osh_lba_destroy)
-struct PoseBuffers { PosePinned h_in, h_out; DevBuf arena; };
-
 }  // namespace osh
 
 using namespace osh;
@@ -365,7 +337,6 @@ extern "C" int osh_pose_optimize(osh_lba_ctx* ctx, int32_t n, const osh_pose_pro
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(lba_stream(ctx, &device, &s));
-  OSH_HIP(hipSetDevice(device));
   std::vector<PoseDesc> h_desc(n);
   size_t NE = 0;
   bool any_kb8 = false;
@@ -396,49 +367,43 @@ extern "C" int osh_pose_optimize(osh_lba_ctx* ctx, int32_t n, const osh_pose_pro
     NE += (size_t)p.n_edges;
   }
   if (NE > 0x7fffff00u) { set_error("batch too large for 32-bit offsets"); return OSH_ERR_UNSUPPORTED; }
-  // one pinned staging buffer, one device arena, one copy each way (eight separate copies cost a third of a single frame's call)
-  void** slot = lba_attachment(ctx, kAttachPose, [](void* q) { delete static_cast<PoseBuffers*>(q); });
-  if (!slot) { set_error("osh_pose_optimize: no context"); return OSH_ERR_INVALID; }
-  if (!*slot) *slot = new PoseBuffers();
-  PoseBuffers& B = *static_cast<PoseBuffers*>(*slot);
-  size_t in_bytes = 0, out_bytes = 0;
-  auto take = [](size_t& total, size_t bytes) { const size_t o = total; total = (total + std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return o; };
-  const size_t i_desc = take(in_bytes, n * sizeof(PoseDesc)), i_X = take(in_bytes, NE * 24), i_obs = take(in_bytes, NE * 24), i_info = take(in_bytes, NE * 8),
-               i_kind = take(in_bytes, NE);
-  const size_t o_out = take(out_bytes, n * sizeof(PoseOut)), o_level = take(out_bytes, NE), o_chi2 = take(out_bytes, NE * 8);
-  char* hs = static_cast<char*>(B.h_in.reserve(in_bytes));
-  char* hr = static_cast<char*>(B.h_out.reserve(out_bytes));
-  if (!hs || !hr) { set_error("osh_pose_optimize: pinned staging allocation failed"); return OSH_ERR_DEVICE; }
-  std::memcpy(hs + i_desc, h_desc.data(), n * sizeof(PoseDesc));
-  double* h_X = reinterpret_cast<double*>(hs + i_X); double* h_obs = reinterpret_cast<double*>(hs + i_obs); double* h_info = reinterpret_cast<double*>(hs + i_info);
-  unsigned char* h_kind = reinterpret_cast<unsigned char*>(hs + i_kind);
+  Layout in, out;
+  const auto i_desc = in.take<PoseDesc>(n);
+  const auto i_X = in.take<double>(NE * 3), i_obs = in.take<double>(NE * 3), i_info = in.take<double>(NE);
+  const auto i_kind = in.take<unsigned char>(NE);
+  const auto o_out = out.take<PoseOut>(n);
+  const auto o_level = out.take<unsigned char>(NE);
+  const auto o_chi2 = out.take<double>(NE);
+  StagedCall* B = attachment<StagedCall>(ctx, kAttachPose);
+  if (!B) return OSH_ERR_INVALID;
+  OSH_TRY(B->reserve(in, out));
+  char* const hs = B->host_in();
+  std::memcpy(i_desc.in(hs), h_desc.data(), n * sizeof(PoseDesc));
   for (int f = 0; f < n; ++f) {
     const osh_pose_problem& p = pr[f];
     const size_t o = (size_t)h_desc[f].edge_off;
     if (p.n_edges > 0) {
-      std::memcpy(h_X + o * 3, p.points, (size_t)p.n_edges * 24);
-      std::memcpy(h_obs + o * 3, p.edge_obs, (size_t)p.n_edges * 24);
-      std::memcpy(h_info + o, p.edge_info, (size_t)p.n_edges * 8);
-      std::memcpy(h_kind + o, p.edge_kind, (size_t)p.n_edges);
+      std::memcpy(i_X.in(hs) + o * 3, p.points, (size_t)p.n_edges * 24);
+      std::memcpy(i_obs.in(hs) + o * 3, p.edge_obs, (size_t)p.n_edges * 24);
+      std::memcpy(i_info.in(hs) + o, p.edge_info, (size_t)p.n_edges * 8);
+      std::memcpy(i_kind.in(hs) + o, p.edge_kind, (size_t)p.n_edges);
     }
   }
-  OSH_TRY(B.arena.reserve(in_bytes + out_bytes));
-  char* din = B.arena.as<char>();
-  char* dout = din + in_bytes;
-  OSH_HIP(hipMemcpyAsync(din, hs, in_bytes, hipMemcpyHostToDevice, s));
+  OSH_TRY(B->upload(s));
+  char* const din = B->dev_in();
+  char* const dout = B->dev_out();
   PoseView v;
-  v.desc = reinterpret_cast<const PoseDesc*>(din + i_desc); v.out = reinterpret_cast<PoseOut*>(dout + o_out);
-  v.X = reinterpret_cast<const double*>(din + i_X); v.kind = reinterpret_cast<const unsigned char*>(din + i_kind);
-  v.obs = reinterpret_cast<const double*>(din + i_obs); v.info = reinterpret_cast<const double*>(din + i_info);
-  v.chi2 = reinterpret_cast<double*>(dout + o_chi2); v.level = reinterpret_cast<unsigned char*>(dout + o_level);
+  v.desc = i_desc.in(din); v.out = o_out.in(dout);
+  v.X = i_X.in(din); v.kind = i_kind.in(din); v.obs = i_obs.in(din); v.info = i_info.in(din);
+  v.chi2 = o_chi2.in(dout); v.level = o_level.in(dout);
   if (any_kb8) hipLaunchKernelGGL(k_pose_opt<true>, dim3((unsigned)n), dim3(kPT), 0, s, v);
   else hipLaunchKernelGGL(k_pose_opt<false>, dim3((unsigned)n), dim3(kPT), 0, s, v);
-  { hipError_t e = hipGetLastError(); if (e != hipSuccess) { set_error("kernel launch k_pose_opt failed: %s", hipGetErrorString(e)); return OSH_ERR_DEVICE; } }
-  OSH_HIP(hipMemcpyAsync(hr, dout, out_bytes, hipMemcpyDeviceToHost, s));
-  OSH_HIP(hipStreamSynchronize(s));
-  const PoseOut* h_out = reinterpret_cast<const PoseOut*>(hr + o_out);
-  const unsigned char* h_level = reinterpret_cast<const unsigned char*>(hr + o_level);
-  const double* h_chi2 = reinterpret_cast<const double*>(hr + o_chi2);
+  OSH_TRY(launch_check("k_pose_opt"));
+  OSH_TRY(B->download(s));
+  char* const hr = B->host_out();
+  const PoseOut* h_out = o_out.in(hr);
+  const unsigned char* h_level = o_level.in(hr);
+  const double* h_chi2 = o_chi2.in(hr);
   for (int f = 0; f < n; ++f) {
     osh_pose_result& r = res[f];
     const PoseOut& o = h_out[f];

@@ -17,7 +17,6 @@
 #include "liba_edges.h"
 #include <cfloat>
 #include <cstring>
-#include <mutex>
 #include <algorithm>
 #include <vector>
 
@@ -45,17 +44,6 @@ struct PoseiView {
   double* chi2; unsigned char* level; unsigned char* outlier;
   int ecap;                   // edges per frame the block's dynamic LDS can hold (0: every access goes to global memory)
 };
-
-__device__ __forceinline__ double posei_block_sum(double v, double* sh) {
-  v = dev::wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int k = 0; k < kIT / 64; ++k) t += sh[k];
-  return t;
-}
 
 // N block sums with TWO barriers: butterfly inside each wavefront, the wavefront partials parked in LDS ([kIT/64][N]) and added in
 // wavefront order by every thread (deterministic).  27 single sums cost 54 barriers per Gauss-Newton iteration before.
@@ -300,7 +288,7 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
       __syncthreads();
       double chi = 0.0;
       if (tid < 15) { double t = 0.0; for (int m = 0; m < 15; ++m) t += d.prior_H[tid * 15 + m] * shr[m]; chi = shr[tid] * t; }
-      chi = posei_block_sum(chi, sh);
+      chi = dev::block_sum_all<kIT>(chi, sh);
       double r0, rho1;
       dev::huber(chi, d.huber_prior, r0, rho1);
       for (int idx = tid; idx < 225; idx += kIT) {   // W J with W = rho' Omega
@@ -391,8 +379,8 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
       setOutlier(e, o); setLevel(e, o);
       if (o) ++bad; else ++inl;
     }
-    n_bad = (int)posei_block_sum((double)bad, sh);
-    n_inl = (int)posei_block_sum((double)inl, sh);
+    n_bad = (int)dev::block_sum_all<kIT>((double)bad, sh);
+    n_inl = (int)dev::block_sum_all<kIT>((double)inl, sh);
     rounds = round + 1;
     if (round == 2) robust = false;
     __syncthreads();
@@ -413,7 +401,7 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
       setChi(e, ev.chi2);
       if (ev.chi2 < (kind == OSH_EDGE_STEREO ? 24.f : 18.f)) setOutlier(e, false); else ++bad;
     }
-    n_bad = (int)posei_block_sum((double)bad, sh);
+    n_bad = (int)dev::block_sum_all<kIT>((double)bad, sh);
   }
   // ---- Hessian of the frame's ConstraintPoseImu (:4858-4893 / :5252-5293): re-linearised at the final estimate, plain information
   {
@@ -519,22 +507,6 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
   }
 }
 
-struct PoseiPinned {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~PoseiPinned() { if (p) (void)hipHostFree(p); }
-  void* reserve(size_t bytes) {
-    if (bytes <= cap) return p;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipHostMalloc(&p, want) != hipSuccess) { p = nullptr; return nullptr; }
-    cap = want;
-    return p;
-  }
-};
-// staging and device arena of osh_posei_optimize: kept with the context (released by osh_lba_destroy)
-struct PoseiBuffers { PoseiPinned h_in, h_out; DevBuf arena; };
-
 }  // namespace osh
 
 using namespace osh;
@@ -544,7 +516,6 @@ extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_p
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(lba_stream(ctx, &device, &s));
-  OSH_HIP(hipSetDevice(device));
   std::vector<PoseiDesc> h_desc(n);
   size_t NE = 0;
   for (int f = 0; f < n; ++f) {
@@ -596,66 +567,53 @@ extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_p
     NE += (size_t)p.n_edges;
   }
   if (NE > 0x7fffff00u) { set_error("batch too large for 32-bit offsets"); return OSH_ERR_UNSUPPORTED; }
-  // one pinned staging buffer, one device arena, one copy each way (the call of a single frame was a dozen copies)
-  void** slot = lba_attachment(ctx, kAttachPosei, [](void* q) { delete static_cast<PoseiBuffers*>(q); });
-  if (!slot) { set_error("osh_posei_optimize: no context"); return OSH_ERR_INVALID; }
-  if (!*slot) *slot = new PoseiBuffers();
-  PoseiBuffers& B = *static_cast<PoseiBuffers*>(*slot);
-  size_t in_bytes = 0, out_bytes = 0;
-  auto take = [](size_t& total, size_t bytes) { const size_t o = total; total = (total + std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return o; };
-  const size_t i_desc = take(in_bytes, n * sizeof(PoseiDesc)), i_X = take(in_bytes, NE * 24), i_obs = take(in_bytes, NE * 24), i_info = take(in_bytes, NE * 8),
-               i_kind = take(in_bytes, NE), i_close = take(in_bytes, NE);
-  const size_t o_out = take(out_bytes, n * sizeof(PoseiOut)), o_outlier = take(out_bytes, NE), o_chi2 = take(out_bytes, NE * 8), o_level = take(out_bytes, NE);
-  char* hs = static_cast<char*>(B.h_in.reserve(in_bytes));
-  char* hr = static_cast<char*>(B.h_out.reserve(out_bytes));
-  if (!hs || !hr) { set_error("osh_posei_optimize: pinned staging allocation failed"); return OSH_ERR_DEVICE; }
-  std::memcpy(hs + i_desc, h_desc.data(), n * sizeof(PoseiDesc));
+  Layout in, out;
+  const auto i_desc = in.take<PoseiDesc>(n);
+  const auto i_X = in.take<double>(NE * 3), i_obs = in.take<double>(NE * 3), i_info = in.take<double>(NE);
+  const auto i_kind = in.take<unsigned char>(NE), i_close = in.take<unsigned char>(NE);
+  const auto o_out = out.take<PoseiOut>(n);
+  const auto o_outlier = out.take<unsigned char>(NE);
+  const auto o_chi2 = out.take<double>(NE);
+  const auto o_level = out.take<unsigned char>(NE);
+  StagedCall* B = attachment<StagedCall>(ctx, kAttachPosei);
+  if (!B) return OSH_ERR_INVALID;
+  OSH_TRY(B->reserve(in, out));
+  char* const hs = B->host_in();
+  std::memcpy(i_desc.in(hs), h_desc.data(), n * sizeof(PoseiDesc));
   for (int f = 0; f < n; ++f) {
     const osh_posei_problem& p = pr[f];
     const size_t o = (size_t)h_desc[f].edge_off;
     if (p.n_edges > 0) {
-      std::memcpy(hs + i_X + o * 24, p.points, (size_t)p.n_edges * 24);
-      std::memcpy(hs + i_obs + o * 24, p.edge_obs, (size_t)p.n_edges * 24);
-      std::memcpy(hs + i_info + o * 8, p.edge_info, (size_t)p.n_edges * 8);
-      std::memcpy(hs + i_kind + o, p.edge_kind, (size_t)p.n_edges);
-      if (p.edge_close) std::memcpy(hs + i_close + o, p.edge_close, (size_t)p.n_edges); else std::memset(hs + i_close + o, 0, (size_t)p.n_edges);
+      std::memcpy(i_X.in(hs) + o * 3, p.points, (size_t)p.n_edges * 24);
+      std::memcpy(i_obs.in(hs) + o * 3, p.edge_obs, (size_t)p.n_edges * 24);
+      std::memcpy(i_info.in(hs) + o, p.edge_info, (size_t)p.n_edges * 8);
+      std::memcpy(i_kind.in(hs) + o, p.edge_kind, (size_t)p.n_edges);
+      if (p.edge_close) std::memcpy(i_close.in(hs) + o, p.edge_close, (size_t)p.n_edges); else std::memset(i_close.in(hs) + o, 0, (size_t)p.n_edges);
     }
   }
-  OSH_TRY(B.arena.reserve(in_bytes + out_bytes));
-  char* din = B.arena.as<char>();
-  char* dout = din + in_bytes;
-  OSH_HIP(hipMemcpyAsync(din, hs, in_bytes, hipMemcpyHostToDevice, s));
+  OSH_TRY(B->upload(s));
+  char* const din = B->dev_in();
+  char* const dout = B->dev_out();
   PoseiView v;
-  v.desc = reinterpret_cast<const PoseiDesc*>(din + i_desc); v.out = reinterpret_cast<PoseiOut*>(dout + o_out);
-  v.X = reinterpret_cast<const double*>(din + i_X); v.kind = reinterpret_cast<const unsigned char*>(din + i_kind);
-  v.obs = reinterpret_cast<const double*>(din + i_obs); v.info = reinterpret_cast<const double*>(din + i_info);
-  v.close = reinterpret_cast<const unsigned char*>(din + i_close); v.chi2 = reinterpret_cast<double*>(dout + o_chi2);
-  v.level = reinterpret_cast<unsigned char*>(dout + o_level); v.outlier = reinterpret_cast<unsigned char*>(dout + o_outlier);
+  v.desc = i_desc.in(din); v.out = o_out.in(dout);
+  v.X = i_X.in(din); v.kind = i_kind.in(din); v.obs = i_obs.in(din); v.info = i_info.in(din); v.close = i_close.in(din);
+  v.chi2 = o_chi2.in(dout); v.level = o_level.in(dout); v.outlier = o_outlier.in(dout);
   // dynamic LDS for the edges of a frame: 8 doubles + 4 bytes each; frames of more than kPoseiMaxCached edges read global memory instead
   int e_max = 0;
   for (int f = 0; f < n; ++f) e_max = std::max(e_max, h_desc[f].E);
   constexpr int kPoseiMaxCached = 1400;
   v.ecap = (e_max > 0 && e_max <= kPoseiMaxCached) ? ((e_max + 63) & ~63) : 0;
   const size_t dyn_bytes = (size_t)v.ecap * (8 * 8 + 4) + 16;
-  {
-    static std::mutex attr_mu;
-    static std::vector<int> attr_devices;
-    std::lock_guard<std::mutex> attr_lock(attr_mu);
-    if (std::find(attr_devices.begin(), attr_devices.end(), device) == attr_devices.end()) {
-      OSH_HIP(hipFuncSetAttribute((const void*)k_posei, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-      attr_devices.push_back(device);
-    }
-  }
+  OSH_TRY(allow_dynamic_lds(device, 128 * 1024, k_posei));
   hipLaunchKernelGGL(k_posei, dim3((unsigned)n), dim3(kIT), dyn_bytes, s, v);
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) { set_error("k_posei launch failed: %s", hipGetErrorString(le)); return OSH_ERR_DEVICE; }
-  OSH_HIP(hipMemcpyAsync(hr, dout, out_bytes, hipMemcpyDeviceToHost, s));
-  OSH_HIP(hipStreamSynchronize(s));
-  const PoseiOut* h_out = reinterpret_cast<const PoseiOut*>(hr + o_out);
+  OSH_TRY(launch_check("k_posei"));
+  OSH_TRY(B->download(s));
+  char* const hr = B->host_out();
+  const PoseiOut* h_out = o_out.in(hr);
   for (int f = 0; f < n; ++f) {
     const PoseiDesc& d = h_desc[f];
-    if (res[f].outlier && d.E) std::memcpy(res[f].outlier, hr + o_outlier + d.edge_off, (size_t)d.E);
-    if (res[f].edge_chi2 && d.E) std::memcpy(res[f].edge_chi2, hr + o_chi2 + (size_t)d.edge_off * 8, (size_t)d.E * 8);
+    if (res[f].outlier && d.E) std::memcpy(res[f].outlier, o_outlier.in(hr) + d.edge_off, (size_t)d.E);
+    if (res[f].edge_chi2 && d.E) std::memcpy(res[f].edge_chi2, o_chi2.in(hr) + d.edge_off, (size_t)d.E * 8);
   }
   for (int f = 0; f < n; ++f) {
     const PoseiOut& o = h_out[f];

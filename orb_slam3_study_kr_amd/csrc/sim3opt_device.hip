@@ -53,17 +53,6 @@ struct Sim3View {
   unsigned char* level;  // [NP] 1: round-1 outlier (edges removed), 2: final outlier, 0: inlier
 };
 
-__device__ __forceinline__ double sim3_block_sum(double v, double* sh) {
-  v = dev::wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int k = 0; k < kST / 64; ++k) t += sh[k];
-  return t;
-}
-
 // project(const Eigen::Vector3d&): Pinhole (src/CameraModels/Pinhole.cpp:35-41) or KannalaBrandt8 (lba_math.h, atan2f_rn)
 template <bool KB8>
 __device__ __forceinline__ void sim3_project(const double* cam, int kb8, const double* X, double& u, double& v) {
@@ -119,7 +108,7 @@ __device__ __forceinline__ double sim3_eval(const Sim3View& v, const Sim3Desc& d
       dev::huber(c21, d.delta, r0, r1); acc += r0;
     } else acc += c12 + c21;
   }
-  return sim3_block_sum(acc, sm.sh);
+  return dev::block_sum_all<kST>(acc, sm.sh);
 }
 
 // one edge's contribution to H (upper, 28) and b (7): J = (e(+delta) - e(-delta)) / (2 delta) per column, H += J^T rho' Omega J,
@@ -363,7 +352,7 @@ __global__ __launch_bounds__(kST) void k_sim3_opt(Sim3View v) {
         const size_t g = (size_t)d.off + p;
         if (v.chi2_12[g] > th2 || v.chi2_21[g] > th2) { v.level[g] = 1; ++bad; }
       }
-      n_bad = (int)sim3_block_sum((double)bad, sm.sh);
+      n_bad = (int)dev::block_sum_all<kST>((double)bad, sm.sh);
       if (tid == 0) out.n_bad = n_bad;
       if (d.n - n_bad < 10) return;   // g2oS12 and mAcumHessian untouched, return 0
     }
@@ -381,7 +370,7 @@ __global__ __launch_bounds__(kST) void k_sim3_opt(Sim3View v) {
     v.chi2_12[g] = c12; v.chi2_21[g] = c21;
     if (c12 > th2 || c21 > th2) v.level[g] = 2; else ++in;
   }
-  const int n_in = (int)sim3_block_sum((double)in, sm.sh);
+  const int n_in = (int)dev::block_sum_all<kST>((double)in, sm.sh);
   if (tid == 0) {
     out.round2 = 1; out.n_in = n_in;
     for (int k = 0; k < 8; ++k) out.S[k] = sm.S[sel][k];
@@ -404,29 +393,12 @@ __global__ __launch_bounds__(kST) void k_sim3_lin(Sim3View v) {
   else if (tid == 35) out.chi2_lin = d.n > 0 ? sm.sys[35] : 0.0;
 }
 
-struct Sim3Pinned {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~Sim3Pinned() { if (p) (void)hipHostFree(p); }
-  void* reserve(size_t bytes) {
-    if (bytes <= cap) return p;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipHostMalloc(&p, want) != hipSuccess) { p = nullptr; return nullptr; }
-    cap = want;
-    return p;
-  }
-};
-// staging and device arena of osh_sim3_optimize: kept with the context (released by osh_lba_destroy)
-struct Sim3Buffers { Sim3Pinned h_in, h_out; DevBuf arena; };
-
 // validate, stage, launch, copy back: the shared body of osh_sim3_optimize (lin_only 0) and osh_sim3_linearize (lin_only 1)
 static int sim3_run(osh_lba_ctx* ctx, int n, const osh_sim3_problem* pr, int lin_only, std::vector<Sim3Out>& outs,
                     std::vector<unsigned char>& level, std::vector<double>& c12, std::vector<double>& c21, std::vector<int>& offs) {
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(lba_stream(ctx, &device, &s));
-  OSH_HIP(hipSetDevice(device));
   std::vector<Sim3Desc> h_desc(n);
   size_t NP = 0;
   bool any_kb8 = false;
@@ -451,42 +423,36 @@ static int sim3_run(osh_lba_ctx* ctx, int n, const osh_sim3_problem* pr, int lin
     NP += (size_t)p.n_pairs;
   }
   if (NP > 0x7fffff00u) { set_error("batch too large for 32-bit offsets"); return OSH_ERR_UNSUPPORTED; }
-  void** slot = lba_attachment(ctx, kAttachSim3, [](void* q) { delete static_cast<Sim3Buffers*>(q); });
-  if (!slot) { set_error("osh_sim3_optimize: no context"); return OSH_ERR_INVALID; }
-  if (!*slot) *slot = new Sim3Buffers();
-  Sim3Buffers& B = *static_cast<Sim3Buffers*>(*slot);
-  size_t in_bytes = 0, out_bytes = 0;
-  auto take = [](size_t& total, size_t bytes) { const size_t o = total; total = (total + std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return o; };
-  const size_t i_desc = take(in_bytes, n * sizeof(Sim3Desc)), i_X1 = take(in_bytes, NP * 24), i_X2 = take(in_bytes, NP * 24),
-               i_o1 = take(in_bytes, NP * 16), i_o2 = take(in_bytes, NP * 16), i_i1 = take(in_bytes, NP * 8), i_i2 = take(in_bytes, NP * 8);
-  const size_t o_out = take(out_bytes, n * sizeof(Sim3Out)), o_c12 = take(out_bytes, NP * 8), o_c21 = take(out_bytes, NP * 8),
-               o_level = take(out_bytes, NP);
-  char* hs = static_cast<char*>(B.h_in.reserve(in_bytes));
-  char* hr = static_cast<char*>(B.h_out.reserve(out_bytes));
-  if (!hs || !hr) { set_error("osh_sim3_optimize: pinned staging allocation failed"); return OSH_ERR_DEVICE; }
-  std::memcpy(hs + i_desc, h_desc.data(), n * sizeof(Sim3Desc));
+  Layout in, out;
+  const auto i_desc = in.take<Sim3Desc>(n);
+  const auto i_X1 = in.take<double>(NP * 3), i_X2 = in.take<double>(NP * 3), i_o1 = in.take<double>(NP * 2), i_o2 = in.take<double>(NP * 2),
+             i_i1 = in.take<double>(NP), i_i2 = in.take<double>(NP);
+  const auto o_out = out.take<Sim3Out>(n);
+  const auto o_c12 = out.take<double>(NP), o_c21 = out.take<double>(NP);
+  const auto o_level = out.take<unsigned char>(NP);
+  StagedCall* B = attachment<StagedCall>(ctx, kAttachSim3);
+  if (!B) return OSH_ERR_INVALID;
+  OSH_TRY(B->reserve(in, out));
+  char* const hs = B->host_in();
+  std::memcpy(i_desc.in(hs), h_desc.data(), n * sizeof(Sim3Desc));
   for (int f = 0; f < n; ++f) {
     const osh_sim3_problem& p = pr[f];
     const size_t o = (size_t)offs[f], np = (size_t)p.n_pairs;
     if (np == 0) continue;
-    std::memcpy(hs + i_X1 + o * 24, p.X1c, np * 24);
-    std::memcpy(hs + i_X2 + o * 24, p.X2c, np * 24);
-    std::memcpy(hs + i_o1 + o * 16, p.obs1, np * 16);
-    std::memcpy(hs + i_o2 + o * 16, p.obs2, np * 16);
-    std::memcpy(hs + i_i1 + o * 8, p.info1, np * 8);
-    std::memcpy(hs + i_i2 + o * 8, p.info2, np * 8);
+    std::memcpy(i_X1.in(hs) + o * 3, p.X1c, np * 24);
+    std::memcpy(i_X2.in(hs) + o * 3, p.X2c, np * 24);
+    std::memcpy(i_o1.in(hs) + o * 2, p.obs1, np * 16);
+    std::memcpy(i_o2.in(hs) + o * 2, p.obs2, np * 16);
+    std::memcpy(i_i1.in(hs) + o, p.info1, np * 8);
+    std::memcpy(i_i2.in(hs) + o, p.info2, np * 8);
   }
-  OSH_TRY(B.arena.reserve(in_bytes + out_bytes));
-  char* din = B.arena.as<char>();
-  char* dout = din + in_bytes;
-  OSH_HIP(hipMemcpyAsync(din, hs, in_bytes, hipMemcpyHostToDevice, s));
+  OSH_TRY(B->upload(s));
+  char* const din = B->dev_in();
+  char* const dout = B->dev_out();
   Sim3View v;
-  v.desc = reinterpret_cast<const Sim3Desc*>(din + i_desc); v.out = reinterpret_cast<Sim3Out*>(dout + o_out);
-  v.X1c = reinterpret_cast<const double*>(din + i_X1); v.X2c = reinterpret_cast<const double*>(din + i_X2);
-  v.obs1 = reinterpret_cast<const double*>(din + i_o1); v.obs2 = reinterpret_cast<const double*>(din + i_o2);
-  v.info1 = reinterpret_cast<const double*>(din + i_i1); v.info2 = reinterpret_cast<const double*>(din + i_i2);
-  v.chi2_12 = reinterpret_cast<double*>(dout + o_c12); v.chi2_21 = reinterpret_cast<double*>(dout + o_c21);
-  v.level = reinterpret_cast<unsigned char*>(dout + o_level);
+  v.desc = i_desc.in(din); v.out = o_out.in(dout);
+  v.X1c = i_X1.in(din); v.X2c = i_X2.in(din); v.obs1 = i_o1.in(din); v.obs2 = i_o2.in(din); v.info1 = i_i1.in(din); v.info2 = i_i2.in(din);
+  v.chi2_12 = o_c12.in(dout); v.chi2_21 = o_c21.in(dout); v.level = o_level.in(dout);
   if (lin_only) {
     if (any_kb8) hipLaunchKernelGGL(k_sim3_lin<true>, dim3((unsigned)n), dim3(kST), 0, s, v);
     else hipLaunchKernelGGL(k_sim3_lin<false>, dim3((unsigned)n), dim3(kST), 0, s, v);
@@ -494,13 +460,13 @@ static int sim3_run(osh_lba_ctx* ctx, int n, const osh_sim3_problem* pr, int lin
     if (any_kb8) hipLaunchKernelGGL(k_sim3_opt<true>, dim3((unsigned)n), dim3(kST), 0, s, v);
     else hipLaunchKernelGGL(k_sim3_opt<false>, dim3((unsigned)n), dim3(kST), 0, s, v);
   }
-  { hipError_t e = hipGetLastError(); if (e != hipSuccess) { set_error("kernel launch k_sim3_opt failed: %s", hipGetErrorString(e)); return OSH_ERR_DEVICE; } }
-  OSH_HIP(hipMemcpyAsync(hr, dout, out_bytes, hipMemcpyDeviceToHost, s));
-  OSH_HIP(hipStreamSynchronize(s));
-  outs.assign(reinterpret_cast<const Sim3Out*>(hr + o_out), reinterpret_cast<const Sim3Out*>(hr + o_out) + n);
-  level.assign(reinterpret_cast<const unsigned char*>(hr + o_level), reinterpret_cast<const unsigned char*>(hr + o_level) + NP);
-  c12.assign(reinterpret_cast<const double*>(hr + o_c12), reinterpret_cast<const double*>(hr + o_c12) + NP);
-  c21.assign(reinterpret_cast<const double*>(hr + o_c21), reinterpret_cast<const double*>(hr + o_c21) + NP);
+  OSH_TRY(launch_check(lin_only ? "k_sim3_lin" : "k_sim3_opt"));
+  OSH_TRY(B->download(s));
+  char* const hr = B->host_out();
+  outs.assign(o_out.in(hr), o_out.in(hr) + n);
+  level.assign(o_level.in(hr), o_level.in(hr) + NP);
+  c12.assign(o_c12.in(hr), o_c12.in(hr) + NP);
+  c21.assign(o_c21.in(hr), o_c21.in(hr) + NP);
   return OSH_OK;
 }
 
