@@ -85,35 +85,12 @@ bool PackLocalBA(KeyFrame* pKF, Map* pMap, LbaPack& pk) {
   pk.num_fixedKF += (int)pk.lFixedCameras.size();
   if (pk.num_fixedKF == 0) return false;  // caller prints the reference's message and returns (:1182-1186)
 
-  // 4./5. vertices.  Hessian order = ascending vertex id among the non-fixed poses, then the points
-  // (g2o/core/sparse_optimizer.cpp:166-190); the map's initial keyframe is a fixed vertex (:1220).
+  // 4./5. vertices; the map's initial keyframe is a fixed vertex (:1220)
   std::vector<KeyFrame*> vFree, vFixed;
   for (KeyFrame* pKFi : pk.lLocalKeyFrames) (pKFi->mnId == pMap->GetInitKFid() ? vFixed : vFree).push_back(pKFi);
-  std::sort(vFree.begin(), vFree.end(), [](KeyFrame* a, KeyFrame* b) { return a->mnId < b->mnId; });
-  for (KeyFrame* pKFi : pk.lFixedCameras) vFixed.push_back(pKFi);
-  pk.vPoseKFs = vFree;
-  pk.vPoseKFs.insert(pk.vPoseKFs.end(), vFixed.begin(), vFixed.end());
-  pk.n_free = (int)vFree.size();
-  pk.n_fixed = (int)vFixed.size();
-  std::map<KeyFrame*, int> poseIndex;
-  for (size_t i = 0; i < pk.vPoseKFs.size(); ++i) poseIndex[pk.vPoseKFs[i]] = (int)i;
-  for (KeyFrame* pKFi : pk.vPoseKFs) {
-    const Sophus::SE3f Tcw = pKFi->GetPose();
-    const Eigen::Quaterniond q = Tcw.unit_quaternion().cast<double>();   // :1217-1218 float -> double
-    const Eigen::Vector3d t = Tcw.translation().cast<double>();
-    const double qt[7] = {q.x(), q.y(), q.z(), q.w(), t[0], t[1], t[2]};
-    pk.pose_qt.insert(pk.pose_qt.end(), qt, qt + 7);
-    const double cam[5] = {pKFi->fx, pKFi->fy, pKFi->cx, pKFi->cy, pKFi->mbf};  // :1352-1356
-    pk.pose_cam.insert(pk.pose_cam.end(), cam, cam + 5);
-  }
-  pk.vPointMPs.assign(pk.lLocalMapPoints.begin(), pk.lLocalMapPoints.end());
-  std::sort(pk.vPointMPs.begin(), pk.vPointMPs.end(), [](MapPoint* a, MapPoint* b) { return a->mnId < b->mnId; });
-  std::map<MapPoint*, int> pointIndex;
-  for (size_t j = 0; j < pk.vPointMPs.size(); ++j) {
-    pointIndex[pk.vPointMPs[j]] = (int)j;
-    const Eigen::Vector3d X = pk.vPointMPs[j]->GetWorldPos().cast<double>();  // :1286
-    pk.points.push_back(X[0]); pk.points.push_back(X[1]); pk.points.push_back(X[2]);
-  }
+  vFixed.insert(vFixed.end(), pk.lFixedCameras.begin(), pk.lFixedCameras.end());
+  const std::map<KeyFrame*, int> poseIndex = pk.set_poses(vFree, vFixed);
+  const std::map<MapPoint*, int> pointIndex = pk.set_points(std::vector<MapPoint*>(pk.lLocalMapPoints.begin(), pk.lLocalMapPoints.end()));   // :1286
   // 6. edges in g2o insertion order: landmark list order x observation-map order (:1293-1402)
   for (MapPoint* pMP : pk.lLocalMapPoints) {
     const std::map<KeyFrame*, std::tuple<int, int>> observations = pMP->GetObservations();
@@ -129,14 +106,7 @@ bool PackLocalBA(KeyFrame* pKF, Map* pMap, LbaPack& pk) {
           // the mono edge projects through pKFi->mpCamera (:1323); the device keeps ONE intrinsics row per keyframe
           if (!pk.mono_camera(pKFi->mpCamera, pKFi->fx, pKFi->fy, pKFi->cx, pKFi->cy)) return true;
         }
-        pk.edge_pose.push_back(poseIndex.at(pKFi));
-        pk.edge_point.push_back(pointIndex.at(pMP));
-        pk.edge_kind.push_back(stereo ? OSH_EDGE_STEREO : OSH_EDGE_MONO);
-        pk.edge_obs.push_back(kpUn.pt.x); pk.edge_obs.push_back(kpUn.pt.y); pk.edge_obs.push_back(stereo ? kp_ur : -1.0);
-        const float& invSigma2 = pKFi->mvInvLevelSigma2[kpUn.octave];
-        pk.edge_info.push_back(invSigma2);
-        pk.vEdgeKF.push_back(pKFi);
-        pk.vEdgeMP.push_back(pMP);
+        pk.add_edge(poseIndex.at(pKFi), pointIndex.at(pMP), stereo ? OSH_EDGE_STEREO : OSH_EDGE_MONO, kpUn, kp_ur, pKFi->mvInvLevelSigma2[kpUn.octave], pKFi, pMP);
       }
       if (pKFi->mpCamera2 && std::get<1>(ob.second) != -1) {
         // EdgeSE3ProjectXYZToBody (:1365-1399): the right-camera observation, a second edge on the pair's Hessian block
@@ -176,16 +146,13 @@ void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap
   if (!ctx) return;  // device error: map stays consistent (SURVEY.md 8b "Errors")
   osh_lba_problem prob;
   pk.fill(prob);
-  prob.huber_mono = (double)(float)std::sqrt(5.991);    // const float thHuberMono = sqrt(5.991)  (:1275)
-  prob.huber_stereo = (double)(float)std::sqrt(7.815);  // (:1276)
+  prob.huber_mono = kHuberMono;
+  prob.huber_stereo = kHuberStereo;
   prob.lambda_init = pMap->IsInertial() ? 100.0 : 0.0;  // solver->setUserLambdaInit(100.0) (:1197-1198)
   prob.max_iterations = 10;                             // optimizer.optimize(10) (:1411)
   prob.stop_flag = reinterpret_cast<const volatile unsigned char*>(pbStopFlag);
-  std::vector<double> out_pose((size_t)pk.n_free * 7), out_pts(pk.points.size()), out_chi2(pk.edge_pose.size());
-  std::vector<uint8_t> out_depth(pk.edge_pose.size());
-  osh_lba_result res;
-  res.pose_qt = out_pose.data(); res.points = out_pts.data(); res.edge_chi2 = out_chi2.data(); res.edge_depth_pos = out_depth.data();
-  if (osh_lba_solve(ctx, 1, &prob, &res) != OSH_OK) {
+  LbaOutput out(pk.n_free, pk.vPointMPs.size(), pk.edge_pose.size());
+  if (osh_lba_solve(ctx, 1, &prob, &out.res) != OSH_OK) {
     std::fprintf(stderr, "LM-LBA: device solve failed (%s); map left untouched\n", osh_last_error());
     return;
   }
@@ -200,30 +167,19 @@ void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap
       if (pk.edge_kind[e] != kind) continue;
       MapPoint* pMP = pk.vEdgeMP[e];
       if (pMP->isBad()) continue;
-      if (out_chi2[e] > th || !out_depth[e]) vToErase.push_back(std::make_pair(pk.vEdgeKF[e], pMP));
+      if (out.chi[e] > th || !out.dep[e]) vToErase.push_back(std::make_pair(pk.vEdgeKF[e], pMP));
     }
   }
   // 10. commit under the map mutex (:1464-1475)
   std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
-  for (auto& er : vToErase) {
-    er.first->EraseMapPointMatch(er.second);
-    er.second->EraseObservation(er.first);
-  }
+  EraseObservations(vToErase);
   // 11. recover optimised data (:1477-1497); poses of the map's initial keyframe were fixed and stay as they are
   for (KeyFrame* pKFi : pk.lLocalKeyFrames) {
-    int idx = -1;
-    for (int i = 0; i < (int)pk.vPoseKFs.size(); ++i) if (pk.vPoseKFs[i] == pKFi) { idx = i; break; }
-    const double* qt = (idx < pk.n_free) ? &out_pose[(size_t)idx * 7] : &pk.pose_qt[(size_t)idx * 7];
-    Sophus::SE3f Tiw(Eigen::Quaterniond(qt[3], qt[0], qt[1], qt[2]).cast<float>(), Eigen::Vector3d(qt[4], qt[5], qt[6]).cast<float>());
-    pKFi->SetPose(Tiw);
+    const int idx = (int)(std::find(pk.vPoseKFs.begin(), pk.vPoseKFs.end(), pKFi) - pk.vPoseKFs.begin());
+    pKFi->SetPose(pk.pose(idx, out.pose.data()));
   }
   for (MapPoint* pMP : pk.lLocalMapPoints) {
-    int j = -1;
-    {
-      auto it = std::lower_bound(pk.vPointMPs.begin(), pk.vPointMPs.end(), pMP, [](MapPoint* a, MapPoint* b) { return a->mnId < b->mnId; });
-      j = (int)(it - pk.vPointMPs.begin());
-    }
-    pMP->SetWorldPos(Eigen::Vector3d(out_pts[3 * (size_t)j], out_pts[3 * (size_t)j + 1], out_pts[3 * (size_t)j + 2]).cast<float>());
+    pMP->SetWorldPos(out.point(pk.point_of(pMP)));
     pMP->UpdateNormalAndDepth();
   }
   pMap->IncreaseChangeIndex();

@@ -18,11 +18,6 @@ namespace ORB_SLAM3 {
 
 namespace {
 
-g2o::Sim3 Sim3FromPose(const Sophus::SE3f& T) {
-  const Sophus::SE3d Tcw = T.cast<double>();
-  return g2o::Sim3(Tcw.unit_quaternion(), Tcw.translation(), 1.0);
-}
-
 void PutSim3(const g2o::Sim3& S, std::vector<double>& out) {
   const Eigen::Quaterniond& q = S.rotation();
   const double v[8] = {q.x(), q.y(), q.z(), q.w(), S.translation()(0), S.translation()(1), S.translation()(2), S.scale()};

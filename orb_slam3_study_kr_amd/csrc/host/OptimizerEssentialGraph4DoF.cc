@@ -62,11 +62,6 @@ void PutV3f(const Eigen::Vector3f& v, std::vector<double>& out) {
   for (int r = 0; r < 3; ++r) out.push_back((double)v(r));
 }
 
-g2o::Sim3 Sim3FromPose(const Sophus::SE3f& T) {
-  const Sophus::SE3d Tcw = T.cast<double>();
-  return g2o::Sim3(Tcw.unit_quaternion(), Tcw.translation(), 1.0);
-}
-
 struct Vertex4 {
   KeyFrame* kf;
   double Rwb[9], twb[3], Rcw[9], tcw[3], Rcb[9], tcb[3];

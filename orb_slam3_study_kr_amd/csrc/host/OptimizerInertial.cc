@@ -152,25 +152,7 @@ bool PackLocalInertialBA(KeyFrame* pKF, Map* pMap, bool bLarge, bool bRecInit, L
   std::map<KeyFrame*, int> poseIndex;
   for (size_t i = 0; i < pk.vPoseKFs.size(); ++i) poseIndex[pk.vPoseKFs[i]] = (int)i;
   for (KeyFrame* k : vOpt) if (!k->bImu) { pk.unsupported = "temporal keyframe without IMU"; return false; }
-  // ImuCamPose(KeyFrame*) (src/G2oTypes.cc:25-71): float members widened to double
-  for (size_t i = 0; i < pk.vPoseKFs.size(); ++i) {
-    KeyFrame* k = pk.vPoseKFs[i];
-    const Eigen::Matrix3f Rcw = k->GetRotation(), Rwb = k->GetImuRotation();
-    const Eigen::Vector3f tcw = k->GetTranslation(), twb = k->GetImuPosition();
-    for (int a = 0; a < 9; ++a) { pk.pose_Rcw.push_back((double)Rcw.v[a]); pk.pose_Rwb.push_back((double)Rwb.v[a]); }
-    for (int a = 0; a < 3; ++a) { pk.pose_tcw.push_back((double)tcw(a)); pk.pose_twb.push_back((double)twb(a)); }
-    if ((int)i < pk.n_opt + pk.n_fixed_imu) {
-      const Eigen::Vector3f v = k->GetVelocity(), bg = k->GetGyroBias(), ba = k->GetAccBias();
-      for (int a = 0; a < 3; ++a) { pk.vel.push_back((double)v(a)); pk.bias_g.push_back((double)bg(a)); pk.bias_a.push_back((double)ba(a)); }
-    }
-  }
-  {
-    const IMU::Calib& cal = pKF->mImuCalib;
-    const Eigen::Matrix3f Rcb = cal.mTcb.rotationMatrix();
-    for (int a = 0; a < 9; ++a) pk.Rcb[a] = (double)Rcb.v[a];
-    for (int a = 0; a < 3; ++a) { pk.tcb[a] = (double)cal.mTcb.translation()(a); pk.tbc[a] = (double)cal.mTbc.translation()(a); }
-    pk.cam[0] = pKF->fx; pk.cam[1] = pKF->fy; pk.cam[2] = pKF->cx; pk.cam[3] = pKF->cy; pk.cam[4] = pKF->mbf;
-  }
+  pk.set_states(pKF);
   // ---- inertial links (:2600-2667), in the reference's newest-first order i = 0..N-1
   for (int i = 0; i < N; i++) {
     KeyFrame* pKFi = vpOptimizableKFs[i];
@@ -179,38 +161,12 @@ bool PackLocalInertialBA(KeyFrame* pKF, Map* pMap, bool bLarge, bool bRecInit, L
     pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());
     auto itp = poseIndex.find(pKFi->mPrevKF);
     if (itp == poseIndex.end() || itp->second >= pk.n_opt + pk.n_fixed_imu) continue;   // vertex missing (:2625-2629)
-    IMU::Preintegrated* P = pKFi->mpImuPreintegrated;
-    pk.link_prev.push_back(itp->second);
-    pk.link_cur.push_back(poseIndex.at(pKFi));
-    float rec[OSH_PREINT_FLOATS];
-    std::memset(rec, 0, sizeof(rec));
-    rec[0] = P->dT;
-    for (int a = 0; a < 9; ++a) { rec[1 + a] = P->dR.v[a]; rec[16 + a] = P->JRg.v[a]; rec[25 + a] = P->JVg.v[a]; rec[34 + a] = P->JVa.v[a]; rec[43 + a] = P->JPg.v[a]; rec[52 + a] = P->JPa.v[a]; }
-    for (int a = 0; a < 3; ++a) { rec[10 + a] = P->dV(a); rec[13 + a] = P->dP(a); }
-    rec[61] = P->b.bax; rec[62] = P->b.bay; rec[63] = P->b.baz; rec[64] = P->b.bwx; rec[65] = P->b.bwy; rec[66] = P->b.bwz;
-    pk.link_preint.insert(pk.link_preint.end(), rec, rec + OSH_PREINT_FLOATS);
-    double info[81];
-    InertialInformation(P->C, info);
-    const bool robust = (i == N - 1) || bRecInit;
-    if (i == N - 1) for (double& x : info) x *= 1e-2;   // the link to the fixed keyframe is down-weighted (:2644-2645)
-    pk.link_info.insert(pk.link_info.end(), info, info + 81);
-    pk.link_robust.push_back(robust ? 1 : 0);
-    for (int which = 0; which < 2; ++which) {
-      double Cb[9], inv[9];
-      for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) Cb[a * 3 + c] = (double)P->C(9 + 3 * which + a, 9 + 3 * which + c);
-      InvertDense(3, Cb, inv);
-      (which == 0 ? pk.link_info_g : pk.link_info_a).insert((which == 0 ? pk.link_info_g : pk.link_info_a).end(), inv, inv + 9);
-    }
+    // the link to the fixed keyframe is robust and down-weighted (:2640-2646)
+    pk.add_link(pKFi, itp->second, poseIndex.at(pKFi), (i == N - 1) || bRecInit, i == N - 1 ? 1e-2 : 1.0);
   }
   // ---- points and visual edges (:2694-2832)
-  pk.vPointMPs.assign(pk.lLocalMapPoints.begin(), pk.lLocalMapPoints.end());
-  std::sort(pk.vPointMPs.begin(), pk.vPointMPs.end(), [](MapPoint* a, MapPoint* b) { return a->mnId < b->mnId; });
-  std::map<MapPoint*, int> pointIndex;
-  for (size_t j = 0; j < pk.vPointMPs.size(); ++j) {
-    pointIndex[pk.vPointMPs[j]] = (int)j;
-    const Eigen::Vector3d X = pk.vPointMPs[j]->GetWorldPos().cast<double>();
-    pk.points.push_back(X[0]); pk.points.push_back(X[1]); pk.points.push_back(X[2]);
-  }
+  const std::map<MapPoint*, int> pointIndex = pk.set_points(std::vector<MapPoint*>(pk.lLocalMapPoints.begin(), pk.lLocalMapPoints.end()));
+  const char* const notOwnModel = "monocular observation through a camera that is not the window's own model";
   for (MapPoint* pMP : pk.lLocalMapPoints) {
     const std::map<KeyFrame*, std::tuple<int, int>> observations = pMP->GetObservations();
     for (const auto& ob : observations) {
@@ -221,34 +177,15 @@ bool PackLocalInertialBA(KeyFrame* pKF, Map* pMap, bool bLarge, bool bRecInit, L
       if (itk == poseIndex.end()) continue;   // marked fixed but never added (the `break` above / the 200 cap)
       const int leftIndex = std::get<0>(ob.second);
       cv::KeyPoint kpUn;   // declared per observation like the reference's (:2732): default-constructed unless there is a left observation
-      // one KannalaBrandt8 per window: EdgeMono projects through pKFi->mpCamera (ImuCamPose::Project, src/G2oTypes.cc:166-171)
-      auto window_fisheye = [&]() -> bool {
-        GeometricCamera* c = pKFi->mpCamera;
-        if (c->getParameter(0) != pKF->fx || c->getParameter(1) != pKF->fy || c->getParameter(2) != pKF->cx || c->getParameter(3) != pKF->cy) {
-          pk.unsupported = "monocular observation through a camera that is not the window's own model"; return false;
-        }
-        for (int k = 0; k < 4; ++k) {
-          if (pk.has_kb8 && pk.kb8[k] != (double)c->getParameter(4 + k)) { pk.unsupported = "keyframes with different KannalaBrandt8 coefficients"; return false; }
-          pk.kb8[k] = c->getParameter(4 + k);
-        }
-        pk.has_kb8 = true;
-        return true;
-      };
       if (leftIndex != -1) {
         kpUn = pKFi->mvKeysUn[leftIndex];
         const float kp_ur = pKFi->mvuRight[leftIndex];
         const bool stereo = !(kp_ur < 0);
-        if (!stereo && pKFi->mpCamera && pKFi->mpCamera->GetType() == GeometricCamera::CAM_FISHEYE && !window_fisheye()) return true;
+        if (!stereo && pKFi->mpCamera && pKFi->mpCamera->GetType() == GeometricCamera::CAM_FISHEYE && !pk.note_fisheye(pKFi, notOwnModel)) return true;
         Eigen::Matrix<double, 2, 1> obs2(kpUn.pt.x, kpUn.pt.y);
         const float unc2 = pKFi->mpCamera->uncertainty2(obs2);
         const float invSigma2 = pKFi->mvInvLevelSigma2[kpUn.octave] / unc2;   // :2741, float division
-        pk.edge_pose.push_back(itk->second);
-        pk.edge_point.push_back(pointIndex.at(pMP));
-        pk.edge_kind.push_back(stereo ? OSH_EDGE_STEREO : OSH_EDGE_MONO);
-        pk.edge_obs.push_back(kpUn.pt.x); pk.edge_obs.push_back(kpUn.pt.y); pk.edge_obs.push_back(stereo ? kp_ur : -1.0);
-        pk.edge_info.push_back(invSigma2);
-        pk.vEdgeKF.push_back(pKFi);
-        pk.vEdgeMP.push_back(pMP);
+        pk.add_edge(itk->second, pointIndex.at(pMP), stereo ? OSH_EDGE_STEREO : OSH_EDGE_MONO, kpUn, kp_ur, invSigma2, pKFi, pMP);
       }
       // monocular right observation (:2798-2835): EdgeMono(1) on camera 1 of the keyframe's ImuCamPose
       if (pKFi->mpCamera2) {
@@ -258,38 +195,17 @@ bool PackLocalInertialBA(KeyFrame* pKF, Map* pMap, bool bLarge, bool bRecInit, L
           // (the reference reads mvKeysRight[rightIndex] without a check, :2803; an observation tuple whose right slot lies below NLeft
           // would read out of bounds: declined like the same case of FullInertialBA)
           if (rightIndex < 0 || rightIndex >= (int)pKFi->mvKeysRight.size()) { pk.unsupported = "right-camera index outside mvKeysRight"; return true; }
-          if (pKFi->mpCamera->GetType() != GeometricCamera::CAM_FISHEYE || pKFi->mpCamera2->GetType() != GeometricCamera::CAM_FISHEYE) {
-            pk.unsupported = "right-camera observation of a rig that is not a KannalaBrandt8 pair"; return true;
-          }
-          if (!window_fisheye()) return true;
-          double c2[8], T[12];
-          for (int k = 0; k < 8; ++k) c2[k] = pKFi->mpCamera2->getParameter(k);
-          const Sophus::SE3f Trl = pKFi->GetRelativePoseTrl();       // ImuCamPose: Trl.matrix().cast<double>() (src/G2oTypes.cc:58)
-          const Eigen::Matrix3f Rrl = Trl.rotationMatrix();
-          for (int a = 0; a < 3; ++a) { for (int b = 0; b < 3; ++b) T[a * 4 + b] = (double)Rrl(a, b); T[a * 4 + 3] = (double)Trl.translation()(a); }
-          if (pk.has_rig) {
-            for (int k = 0; k < 8; ++k) if (pk.cam2[k] != c2[k]) { pk.unsupported = "keyframes with different right cameras"; return true; }
-            for (int k = 0; k < 12; ++k) if (pk.trl[k] != T[k]) { pk.unsupported = "keyframes with different left-to-right transforms"; return true; }
-          }
-          std::copy(c2, c2 + 8, pk.cam2); std::copy(T, T + 12, pk.trl);
-          pk.has_rig = true;
+          if (!pk.note_rig(pKFi, notOwnModel)) return true;
           const cv::KeyPoint kp = pKFi->mvKeysRight[rightIndex];
           Eigen::Matrix<double, 2, 1> obs2(kp.pt.x, kp.pt.y);
           const float unc2 = pKFi->mpCamera->uncertainty2(obs2);                  // the LEFT camera's, as the reference has it (:2819)
           const float invSigma2 = pKFi->mvInvLevelSigma2[kpUn.octave] / unc2;     // kpUn: the left keypoint variable (:2821)
-          pk.edge_pose.push_back(itk->second);
-          pk.edge_point.push_back(pointIndex.at(pMP));
-          pk.edge_kind.push_back(OSH_EDGE_RIGHT);
-          pk.edge_obs.push_back(kp.pt.x); pk.edge_obs.push_back(kp.pt.y); pk.edge_obs.push_back(-1.0);
-          pk.edge_info.push_back(invSigma2);
-          pk.vEdgeKF.push_back(pKFi);
-          pk.vEdgeMP.push_back(pMP);
+          pk.add_edge(itk->second, pointIndex.at(pMP), OSH_EDGE_RIGHT, kp, -1.f, invSigma2, pKFi, pMP);
         }
       }
     }
   }
-  if (pk.has_kb8)
-    for (uint8_t k : pk.edge_kind) if (k == OSH_EDGE_STEREO) { pk.unsupported = "rectified-stereo observation in a KannalaBrandt8 window"; return true; }
+  pk.no_stereo_with_kb8("rectified-stereo observation in a KannalaBrandt8 window");
   return true;
 }
 
@@ -308,23 +224,18 @@ void Optimizer::LocalInertialBA(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int&
   if (!ctx) return;
   osh_liba_problem prob;
   pk.fill(prob);
-  prob.huber_mono = (double)(float)std::sqrt(5.991);     // :2694
-  prob.huber_stereo = (double)(float)std::sqrt(7.815);   // :2696
-  prob.huber_inertial = std::sqrt(16.92);                // rki->setDelta(sqrt(16.92)) :2646
+  prob.huber_mono = kHuberMono;
+  prob.huber_stereo = kHuberStereo;
+  prob.huber_inertial = kHuberInertial;
   prob.lambda_init = bLarge ? 1e-2 : 1e0;                // :2517-2528
   prob.max_iterations = pk.opt_it;
   const int N = pk.n_opt, L = (int)pk.vPointMPs.size(), E = (int)pk.edge_pose.size();
-  std::vector<double> oRcw((size_t)N * 9), otcw((size_t)N * 3), oRwb((size_t)N * 9), otwb((size_t)N * 3), ov((size_t)N * 3),
-      obg((size_t)N * 3), oba((size_t)N * 3), opts((size_t)L * 3), ochi(E);
-  std::vector<uint8_t> odep(E);
-  osh_liba_result res;
-  res.pose_Rcw = oRcw.data(); res.pose_tcw = otcw.data(); res.pose_Rwb = oRwb.data(); res.pose_twb = otwb.data();
-  res.vel = ov.data(); res.bias_g = obg.data(); res.bias_a = oba.data(); res.points = opts.data(); res.edge_chi2 = ochi.data(); res.edge_depth_pos = odep.data();
-  if (osh_liba_solve(ctx, 1, &prob, &res) != OSH_OK) {
+  LibaOutput out(N, L, E);
+  if (osh_liba_solve(ctx, 1, &prob, &out.res) != OSH_OK) {
     std::fprintf(stderr, "LocalInertialBA: device solve failed (%s); map left untouched\n", osh_last_error());
     return;
   }
-  const float err = (float)res.chi2_initial, err_end = (float)res.chi2_final;   // `float err = optimizer.activeRobustChi2()` :2845,2848
+  const float err = (float)out.res.chi2_initial, err_end = (float)out.res.chi2_final;   // `float err = optimizer.activeRobustChi2()` :2845,2848
   // inlier check (:2855-2888): float thresholds; close points get 1.5x; stereo edges have no depth test
   const float chi2Mono2 = 5.991f, chi2Stereo2 = 7.815f;
   std::vector<std::pair<KeyFrame*, MapPoint*>> vToErase;
@@ -335,10 +246,10 @@ void Optimizer::LocalInertialBA(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int&
       if (pass == 0) {
         const bool bClose = pMP->mTrackDepth < 10.f;
         if (pMP->isBad()) continue;
-        if ((ochi[e] > chi2Mono2 && !bClose) || (ochi[e] > 1.5f * chi2Mono2 && bClose) || !odep[e]) vToErase.push_back(std::make_pair(pk.vEdgeKF[e], pMP));
+        if ((out.chi[e] > chi2Mono2 && !bClose) || (out.chi[e] > 1.5f * chi2Mono2 && bClose) || !out.dep[e]) vToErase.push_back(std::make_pair(pk.vEdgeKF[e], pMP));
       } else {
         if (pMP->isBad()) continue;
-        if (ochi[e] > chi2Stereo2) vToErase.push_back(std::make_pair(pk.vEdgeKF[e], pMP));
+        if (out.chi[e] > chi2Stereo2) vToErase.push_back(std::make_pair(pk.vEdgeKF[e], pMP));
       }
     }
   std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
@@ -346,26 +257,21 @@ void Optimizer::LocalInertialBA(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int&
     std::printf("FAIL LOCAL-INERTIAL BA!!!!\n");
     return;
   }
-  for (auto& er : vToErase) { er.first->EraseMapPointMatch(er.second); er.second->EraseObservation(er.first); }
+  EraseObservations(vToErase);
   reset_marks();
   // recover optimised data (:2909-2963)
   for (KeyFrame* pKFi : pk.vpOptimizableKFs) {
     int idx = 0;
     while (pk.vPoseKFs[idx] != pKFi) ++idx;
-    Eigen::Matrix3f R; Eigen::Vector3f t;
-    for (int a = 0; a < 9; ++a) R.v[a] = (float)oRcw[(size_t)idx * 9 + a];
-    for (int a = 0; a < 3; ++a) t(a) = (float)otcw[(size_t)idx * 3 + a];
-    pKFi->SetPose(Sophus::SE3f(R, t));
+    pKFi->SetPose(out.pose(idx));
     pKFi->mnBALocalForKF = 0;
     if (pKFi->bImu) {
-      pKFi->SetVelocity(Eigen::Vector3f((float)ov[(size_t)idx * 3], (float)ov[(size_t)idx * 3 + 1], (float)ov[(size_t)idx * 3 + 2]));
-      pKFi->SetNewBias(IMU::Bias(oba[(size_t)idx * 3], oba[(size_t)idx * 3 + 1], oba[(size_t)idx * 3 + 2], obg[(size_t)idx * 3], obg[(size_t)idx * 3 + 1],
-                                 obg[(size_t)idx * 3 + 2]));
+      pKFi->SetVelocity(out.velocity(idx));
+      pKFi->SetNewBias(out.bias(idx));
     }
   }
   for (MapPoint* pMP : pk.lLocalMapPoints) {
-    const int j = (int)(std::lower_bound(pk.vPointMPs.begin(), pk.vPointMPs.end(), pMP, [](MapPoint* a, MapPoint* b) { return a->mnId < b->mnId; }) - pk.vPointMPs.begin());
-    pMP->SetWorldPos(Eigen::Vector3d(opts[3 * (size_t)j], opts[3 * (size_t)j + 1], opts[3 * (size_t)j + 2]).cast<float>());
+    pMP->SetWorldPos(out.point(pk.point_of(pMP)));
     pMP->UpdateNormalAndDepth();
   }
   pMap->IncreaseChangeIndex();

@@ -21,133 +21,6 @@
 #include "orbslam3_hip.h"
 
 namespace ORB_SLAM3 {
-bool InvertDense(int n, const double* A, double* inv);   // OptimizerInertial.cc
-
-namespace {
-// ImuCamPose(KeyFrame*) (src/G2oTypes.cc:25-71) of every keyframe of pk.vPoseKFs, calibration of the first one
-void PackKeyframeStates(LibaPack& pk) {
-  for (size_t i = 0; i < pk.vPoseKFs.size(); ++i) {
-    KeyFrame* k = pk.vPoseKFs[i];
-    const Eigen::Matrix3f Rcw = k->GetRotation(), Rwb = k->GetImuRotation();
-    const Eigen::Vector3f tcw = k->GetTranslation(), twb = k->GetImuPosition();
-    for (int a = 0; a < 9; ++a) { pk.pose_Rcw.push_back((double)Rcw.v[a]); pk.pose_Rwb.push_back((double)Rwb.v[a]); }
-    for (int a = 0; a < 3; ++a) { pk.pose_tcw.push_back((double)tcw(a)); pk.pose_twb.push_back((double)twb(a)); }
-    if ((int)i < pk.n_opt + pk.n_fixed_imu) {
-      const Eigen::Vector3f v = k->GetVelocity(), bg = k->GetGyroBias(), ba = k->GetAccBias();
-      for (int a = 0; a < 3; ++a) { pk.vel.push_back((double)v(a)); pk.bias_g.push_back((double)bg(a)); pk.bias_a.push_back((double)ba(a)); }
-    }
-  }
-  KeyFrame* pKF = pk.vPoseKFs.front();
-  const IMU::Calib& cal = pKF->mImuCalib;
-  const Eigen::Matrix3f Rcb = cal.mTcb.rotationMatrix();
-  for (int a = 0; a < 9; ++a) pk.Rcb[a] = (double)Rcb.v[a];
-  for (int a = 0; a < 3; ++a) { pk.tcb[a] = (double)cal.mTcb.translation()(a); pk.tbc[a] = (double)cal.mTbc.translation()(a); }
-  pk.cam[0] = pKF->fx; pk.cam[1] = pKF->fy; pk.cam[2] = pKF->cx; pk.cam[3] = pKF->cy; pk.cam[4] = pKF->mbf;
-}
-
-// EdgeInertial + EdgeGyroRW + EdgeAccRW between pKFi->mPrevKF and pKFi (src/Optimizer.cc:523-568, 4226-4257): Huber on the inertial
-// edge, plain information (no down-weighting of the oldest link here)
-void PackLink(LibaPack& pk, KeyFrame* pKFi, int prev, int cur) {
-  IMU::Preintegrated* P = pKFi->mpImuPreintegrated;
-  pk.link_prev.push_back(prev);
-  pk.link_cur.push_back(cur);
-  float rec[OSH_PREINT_FLOATS];
-  std::memset(rec, 0, sizeof(rec));
-  rec[0] = P->dT;
-  for (int a = 0; a < 9; ++a) { rec[1 + a] = P->dR.v[a]; rec[16 + a] = P->JRg.v[a]; rec[25 + a] = P->JVg.v[a]; rec[34 + a] = P->JVa.v[a]; rec[43 + a] = P->JPg.v[a]; rec[52 + a] = P->JPa.v[a]; }
-  for (int a = 0; a < 3; ++a) { rec[10 + a] = P->dV(a); rec[13 + a] = P->dP(a); }
-  rec[61] = P->b.bax; rec[62] = P->b.bay; rec[63] = P->b.baz; rec[64] = P->b.bwx; rec[65] = P->b.bwy; rec[66] = P->b.bwz;
-  pk.link_preint.insert(pk.link_preint.end(), rec, rec + OSH_PREINT_FLOATS);
-  double info[81];
-  InertialInformation(P->C, info);
-  pk.link_info.insert(pk.link_info.end(), info, info + 81);
-  pk.link_robust.push_back(1);
-  for (int which = 0; which < 2; ++which) {
-    double Cb[9], inv[9];
-    for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) Cb[a * 3 + c] = (double)P->C(9 + 3 * which + a, 9 + 3 * which + c);
-    InvertDense(3, Cb, inv);
-    (which == 0 ? pk.link_info_g : pk.link_info_a).insert((which == 0 ? pk.link_info_g : pk.link_info_a).end(), inv, inv + 9);
-  }
-}
-
-// one camera model per problem (ImuCamPose::Project goes through pKFi->mpCamera, src/G2oTypes.cc:166-171)
-bool NoteFisheye(LibaPack& pk, KeyFrame* pKFi) {
-  GeometricCamera* c = pKFi->mpCamera;
-  if (c->getParameter(0) != (float)pk.cam[0] || c->getParameter(1) != (float)pk.cam[1] || c->getParameter(2) != (float)pk.cam[2] || c->getParameter(3) != (float)pk.cam[3]) {
-    pk.unsupported = "monocular observation through a camera that is not the map's own model"; return false;
-  }
-  for (int k = 0; k < 4; ++k) {
-    if (pk.has_kb8 && pk.kb8[k] != (double)c->getParameter(4 + k)) { pk.unsupported = "keyframes with different KannalaBrandt8 coefficients"; return false; }
-    pk.kb8[k] = c->getParameter(4 + k);
-  }
-  pk.has_kb8 = true;
-  return true;
-}
-
-void PushEdge(LibaPack& pk, int pose, int point, uint8_t kind, float u, float v, float ur, float invSigma2, KeyFrame* pKFi, MapPoint* pMP) {
-  pk.edge_pose.push_back(pose);
-  pk.edge_point.push_back(point);
-  pk.edge_kind.push_back(kind);
-  pk.edge_obs.push_back(u); pk.edge_obs.push_back(v); pk.edge_obs.push_back(kind == OSH_EDGE_STEREO ? ur : -1.0);
-  pk.edge_info.push_back(invSigma2);
-  pk.vEdgeKF.push_back(pKFi);
-  pk.vEdgeMP.push_back(pMP);
-}
-
-bool NoteRig(LibaPack& pk, KeyFrame* pKFi) {
-  if (pKFi->mpCamera->GetType() != GeometricCamera::CAM_FISHEYE || pKFi->mpCamera2->GetType() != GeometricCamera::CAM_FISHEYE) {
-    pk.unsupported = "right-camera observation of a rig that is not a KannalaBrandt8 pair"; return false;
-  }
-  if (!NoteFisheye(pk, pKFi)) return false;
-  double c2[8], T[12];
-  for (int k = 0; k < 8; ++k) c2[k] = pKFi->mpCamera2->getParameter(k);
-  const Sophus::SE3f Trl = pKFi->GetRelativePoseTrl();
-  const Eigen::Matrix3f Rrl = Trl.rotationMatrix();
-  for (int a = 0; a < 3; ++a) { for (int b = 0; b < 3; ++b) T[a * 4 + b] = (double)Rrl(a, b); T[a * 4 + 3] = (double)Trl.translation()(a); }
-  if (pk.has_rig) {
-    for (int k = 0; k < 8; ++k) if (pk.cam2[k] != c2[k]) { pk.unsupported = "keyframes with different right cameras"; return false; }
-    for (int k = 0; k < 12; ++k) if (pk.trl[k] != T[k]) { pk.unsupported = "keyframes with different left-to-right transforms"; return false; }
-  }
-  std::copy(c2, c2 + 8, pk.cam2); std::copy(T, T + 12, pk.trl);
-  pk.has_rig = true;
-  return true;
-}
-
-// drops the points no edge refers to (g2o never activates them) and renumbers edge_point; `kept` = the surviving points in order
-void DropUnobservedPoints(LibaPack& pk, std::vector<MapPoint*>& all) {
-  std::vector<int> count(all.size(), 0), remap(all.size(), -1);
-  for (int32_t j : pk.edge_point) ++count[j];
-  pk.vPointMPs.clear(); pk.points.clear();
-  for (size_t j = 0; j < all.size(); ++j)
-    if (count[j]) {
-      remap[j] = (int)pk.vPointMPs.size();
-      pk.vPointMPs.push_back(all[j]);
-      const Eigen::Vector3d X = all[j]->GetWorldPos().cast<double>();
-      pk.points.push_back(X[0]); pk.points.push_back(X[1]); pk.points.push_back(X[2]);
-    }
-  for (int32_t& j : pk.edge_point) j = remap[j];
-}
-
-struct LibaOutput {
-  std::vector<double> Rcw, tcw, Rwb, twb, v, bg, ba, pts, chi;
-  std::vector<uint8_t> dep;
-  osh_liba_result res;
-  LibaOutput(int N, int L, int E) : Rcw((size_t)N * 9), tcw((size_t)N * 3), Rwb((size_t)N * 9), twb((size_t)N * 3), v((size_t)N * 3), bg((size_t)N * 3), ba((size_t)N * 3),
-                                    pts((size_t)L * 3), chi(E), dep(E) {
-    res.pose_Rcw = Rcw.data(); res.pose_tcw = tcw.data(); res.pose_Rwb = Rwb.data(); res.pose_twb = twb.data();
-    res.vel = v.data(); res.bias_g = bg.data(); res.bias_a = ba.data(); res.points = pts.data(); res.edge_chi2 = chi.data(); res.edge_depth_pos = dep.data();
-  }
-  Sophus::SE3f pose(int i) const {
-    Eigen::Matrix3f R; Eigen::Vector3f t;
-    for (int a = 0; a < 9; ++a) R.v[a] = (float)Rcw[(size_t)i * 9 + a];
-    for (int a = 0; a < 3; ++a) t(a) = (float)tcw[(size_t)i * 3 + a];
-    return Sophus::SE3f(R, t);
-  }
-  Eigen::Vector3f velocity(int i) const { return Eigen::Vector3f((float)v[(size_t)i * 3], (float)v[(size_t)i * 3 + 1], (float)v[(size_t)i * 3 + 2]); }
-  IMU::Bias bias(int i) const { return IMU::Bias(ba[(size_t)i * 3], ba[(size_t)i * 3 + 1], ba[(size_t)i * 3 + 2], bg[(size_t)i * 3], bg[(size_t)i * 3 + 1], bg[(size_t)i * 3 + 2]); }
-  Eigen::Vector3f point(int j) const { return Eigen::Vector3d(pts[3 * (size_t)j], pts[3 * (size_t)j + 1], pts[3 * (size_t)j + 2]).cast<float>(); }
-};
-}  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // FullInertialBA: vertices :417-470, inertial links :480-579, points and visual edges :604-727
@@ -181,7 +54,7 @@ bool PackFullInertialBA(Map* pMap, int its, bool bFixLocal, bool bInit, float pr
   pk.vpOptimizableKFs = pk.vPoseKFs;
   std::map<KeyFrame*, int> poseIndex;
   for (size_t i = 0; i < pk.vPoseKFs.size(); ++i) poseIndex[pk.vPoseKFs[i]] = (int)i;
-  PackKeyframeStates(pk);
+  pk.set_states(pk.vPoseKFs.front());
   for (KeyFrame* pKFi : vpKFs) {   // the reference's order (the map's), :481
     if (!pKFi->mPrevKF) { std::printf("NOT INERTIAL LINK TO PREVIOUS FRAME!\n"); continue; }
     if (pKFi->mnId > maxKFid) continue;
@@ -189,7 +62,7 @@ bool PackFullInertialBA(Map* pMap, int its, bool bFixLocal, bool bInit, float pr
     if (!(pKFi->bImu && pKFi->mPrevKF->bImu)) { std::printf("%lu or %lu no imu\n", pKFi->mnId, pKFi->mPrevKF->mnId); continue; }
     if (!pKFi->mpImuPreintegrated || !sKF.count(pKFi->mPrevKF)) continue;
     pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());   // :504
-    PackLink(pk, pKFi, poseIndex.at(pKFi->mPrevKF), poseIndex.at(pKFi));
+    pk.add_link(pKFi, poseIndex.at(pKFi->mPrevKF), poseIndex.at(pKFi), true, 1.0);   // Huber, no down-weighting (:523-549)
   }
   if (bInit) {
     // ONE gyro and ONE accelerometer bias vertex for the whole map, created from the last keyframe of the map's list (:452-462); every
@@ -214,8 +87,7 @@ bool PackFullInertialBA(Map* pMap, int its, bool bFixLocal, bool bInit, float pr
     for (int a = 0; a < 3; ++a) { pk.pose_tcw.push_back(pk.pose_tcw[(size_t)slot * 3 + a]); pk.pose_twb.push_back(pk.pose_twb[(size_t)slot * 3 + a]); }
     for (int a = 0; a < 3; ++a) { pk.vel.push_back(0.0); pk.bias_g.push_back(0.0); pk.bias_a.push_back(0.0); }
     pk.link_prev.push_back(N); pk.link_cur.push_back(slot); pk.link_bias.push_back(N);
-    float rec[OSH_PREINT_FLOATS];
-    std::memset(rec, 0, sizeof(rec));
+    float rec[OSH_PREINT_FLOATS] = {};
     rec[1] = rec[5] = rec[9] = 1.f;   // dR = I, dT = 0: a finite residual, dropped by the zero information
     pk.link_preint.insert(pk.link_preint.end(), rec, rec + OSH_PREINT_FLOATS);
     pk.link_info.insert(pk.link_info.end(), 81, 0.0);
@@ -226,9 +98,10 @@ bool PackFullInertialBA(Map* pMap, int its, bool bFixLocal, bool bInit, float pr
   }
   // points in map order; vertex id = mnId + 5 maxKFid + 1, so the Hessian order is ascending mnId
   std::vector<MapPoint*> vMP(vpAllMPs);
-  std::sort(vMP.begin(), vMP.end(), [](MapPoint* a, MapPoint* b) { return a->mnId < b->mnId; });
+  std::sort(vMP.begin(), vMP.end(), ByMnId);
   std::map<MapPoint*, int> pointIndex;
   for (size_t j = 0; j < vMP.size(); ++j) pointIndex[vMP[j]] = (int)j;
+  const char* const notOwnModel = "monocular observation through a camera that is not the map's own model";
   for (MapPoint* pMP : vpAllMPs) {
     const std::map<KeyFrame*, std::tuple<int, int>> observations = pMP->GetObservations();
     const int j = pointIndex.at(pMP);
@@ -242,24 +115,23 @@ bool PackFullInertialBA(Map* pMap, int its, bool bFixLocal, bool bInit, float pr
         const cv::KeyPoint kpUn = pKFi->mvKeysUn[leftIndex];
         const float kp_ur = pKFi->mvuRight[leftIndex];
         const bool stereo = !(kp_ur < 0);
-        if (!stereo && pKFi->mpCamera && pKFi->mpCamera->GetType() == GeometricCamera::CAM_FISHEYE && !NoteFisheye(pk, pKFi)) return true;
-        PushEdge(pk, itk->second, j, stereo ? OSH_EDGE_STEREO : OSH_EDGE_MONO, kpUn.pt.x, kpUn.pt.y, kp_ur, pKFi->mvInvLevelSigma2[kpUn.octave], pKFi, pMP);
+        if (!stereo && pKFi->mpCamera && pKFi->mpCamera->GetType() == GeometricCamera::CAM_FISHEYE && !pk.note_fisheye(pKFi, notOwnModel)) return true;
+        pk.add_edge(itk->second, j, stereo ? OSH_EDGE_STEREO : OSH_EDGE_MONO, kpUn, kp_ur, pKFi->mvInvLevelSigma2[kpUn.octave], pKFi, pMP);
       }
       if (pKFi->mpCamera2) {   // :684-716: the index is compared with mvKeysRight.size() BEFORE NLeft is taken off, as the reference has it
         int rightIndex = std::get<1>(ob.second);
         if (rightIndex != -1 && rightIndex < (int)pKFi->mvKeysRight.size()) {
           rightIndex -= pKFi->NLeft;
           if (rightIndex < 0) { pk.unsupported = "right-camera index below NLeft"; return true; }
-          if (!NoteRig(pk, pKFi)) return true;
+          if (!pk.note_rig(pKFi, notOwnModel)) return true;
           const cv::KeyPoint kpUn = pKFi->mvKeysRight[rightIndex];
-          PushEdge(pk, itk->second, j, OSH_EDGE_RIGHT, kpUn.pt.x, kpUn.pt.y, -1.f, pKFi->mvInvLevelSigma2[kpUn.octave], pKFi, pMP);
+          pk.add_edge(itk->second, j, OSH_EDGE_RIGHT, kpUn, -1.f, pKFi->mvInvLevelSigma2[kpUn.octave], pKFi, pMP);
         }
       }
     }
   }
-  DropUnobservedPoints(pk, vMP);   // bAllFixed stays true without an edge: the vertex is removed (:719-725)
-  if (pk.has_kb8)
-    for (uint8_t k : pk.edge_kind) if (k == OSH_EDGE_STEREO) { pk.unsupported = "rectified-stereo observation in a KannalaBrandt8 map"; return true; }
+  pk.drop_unobserved_points(vMP);   // bAllFixed stays true without an edge: the vertex is removed (:719-725)
+  if (!pk.no_stereo_with_kb8("rectified-stereo observation in a KannalaBrandt8 map")) return true;
   return !pk.edge_pose.empty() || !pk.link_prev.empty();
 }
 
@@ -280,9 +152,9 @@ void Optimizer::FullInertialBA(Map* pMap, int its, const bool bFixLocal, const u
   if (!ctx) return;
   osh_liba_problem prob;
   pk.fill(prob);
-  prob.huber_mono = (double)(float)std::sqrt(5.991);     // :592
-  prob.huber_stereo = (double)(float)std::sqrt(7.815);   // :593
-  prob.huber_inertial = std::sqrt(16.92);                // :541
+  prob.huber_mono = kHuberMono;
+  prob.huber_stereo = kHuberStereo;
+  prob.huber_inertial = kHuberInertial;
   prob.lambda_init = 1e-5;                               // setUserLambdaInit(1e-5) :408
   prob.max_iterations = its;
   const int N = pk.n_opt, L = (int)pk.vPointMPs.size(), E = (int)pk.edge_pose.size();
@@ -302,7 +174,7 @@ void Optimizer::FullInertialBA(Map* pMap, int its, const bool bFixLocal, const u
   };
   for (int i = 0; i < N; ++i) {
     KeyFrame* pKFi = pk.vPoseKFs[i];
-    const bool linked = std::find(pk.link_prev.begin(), pk.link_prev.end(), i) != pk.link_prev.end() || std::find(pk.link_cur.begin(), pk.link_cur.end(), i) != pk.link_cur.end();
+    const bool linked = pk.linked(i);
     // velocity / bias vertices without an edge keep their float values (the device's increment there is exactly zero as well)
     // with bInit every keyframe is handed the one optimised bias pair (:779-789)
     write_kf(pKFi, out.pose(i), linked ? out.velocity(i) : pKFi->GetVelocity(), slot >= 0 ? out.bias(slot) : linked ? out.bias(i) : pKFi->GetImuBias());
@@ -411,7 +283,7 @@ bool PackMergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, LibaPack& pk, st
   pk.n_opt = (int)vOpt.size(); pk.n_fixed_imu = fixedLinked ? 1 : 0; pk.n_fixed = fixedLinked ? 0 : 1; pk.opt_it = 8;
   std::map<KeyFrame*, int> poseIndex;
   for (size_t k = 0; k < pk.vPoseKFs.size(); ++k) poseIndex[pk.vPoseKFs[k]] = (int)k;
-  PackKeyframeStates(pk);
+  pk.set_states(pk.vPoseKFs.front());
   for (int k = 0; k < N; k++) {   // :4203-4262
     KeyFrame* pKFi = vpOptimizableKFs[k];
     if (!pKFi->mPrevKF) { std::printf("NOT INERTIAL LINK TO PREVIOUS FRAME!!!!\n"); continue; }
@@ -419,11 +291,11 @@ bool PackMergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, LibaPack& pk, st
     pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());
     auto itp = poseIndex.find(pKFi->mPrevKF);
     if (itp == poseIndex.end()) { std::fprintf(stderr, "Error: inertial edge to a keyframe without vertices\n"); continue; }   // :4224-4228
-    PackLink(pk, pKFi, itp->second, poseIndex.at(pKFi));
+    pk.add_link(pKFi, itp->second, poseIndex.at(pKFi), true, 1.0);
   }
   // points and visual edges (:4290-4382): an observation's keyframe must carry the window's mark AND a vertex
   std::vector<MapPoint*> vMP(pk.lLocalMapPoints.begin(), pk.lLocalMapPoints.end());
-  std::sort(vMP.begin(), vMP.end(), [](MapPoint* a, MapPoint* b) { return a->mnId < b->mnId; });
+  std::sort(vMP.begin(), vMP.end(), ByMnId);
   std::map<MapPoint*, int> pointIndex;
   for (size_t j = 0; j < vMP.size(); ++j) pointIndex[vMP[j]] = (int)j;
   for (MapPoint* pMP : pk.lLocalMapPoints) {
@@ -440,13 +312,12 @@ bool PackMergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, LibaPack& pk, st
       const cv::KeyPoint& kpUn = pKFi->mvKeysUn[leftIndex];
       const float kp_ur = pKFi->mvuRight[leftIndex];
       const bool stereo = !(kp_ur < 0);
-      if (!stereo && pKFi->mpCamera && pKFi->mpCamera->GetType() == GeometricCamera::CAM_FISHEYE && !NoteFisheye(pk, pKFi)) return true;
-      PushEdge(pk, itk->second, pointIndex.at(pMP), stereo ? OSH_EDGE_STEREO : OSH_EDGE_MONO, kpUn.pt.x, kpUn.pt.y, kp_ur, pKFi->mvInvLevelSigma2[kpUn.octave], pKFi, pMP);
+      if (!stereo && pKFi->mpCamera && pKFi->mpCamera->GetType() == GeometricCamera::CAM_FISHEYE && !pk.note_fisheye(pKFi, "monocular observation through a camera that is not the map's own model")) return true;
+      pk.add_edge(itk->second, pointIndex.at(pMP), stereo ? OSH_EDGE_STEREO : OSH_EDGE_MONO, kpUn, kp_ur, pKFi->mvInvLevelSigma2[kpUn.octave], pKFi, pMP);
     }
   }
-  DropUnobservedPoints(pk, vMP);
-  if (pk.has_kb8)
-    for (uint8_t k : pk.edge_kind) if (k == OSH_EDGE_STEREO) { pk.unsupported = "rectified-stereo observation in a KannalaBrandt8 map"; return true; }
+  pk.drop_unobserved_points(vMP);
+  pk.no_stereo_with_kb8("rectified-stereo observation in a KannalaBrandt8 map");
   return true;
 }
 
@@ -463,9 +334,9 @@ void Optimizer::MergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, bool* pbS
   if (!ctx) return;
   osh_liba_problem prob;
   pk.fill(prob);
-  prob.huber_mono = (double)(float)std::sqrt(5.991);     // :4283
-  prob.huber_stereo = (double)(float)std::sqrt(7.815);   // :4285
-  prob.huber_inertial = std::sqrt(16.92);                // :4244
+  prob.huber_mono = kHuberMono;
+  prob.huber_stereo = kHuberStereo;
+  prob.huber_inertial = kHuberInertial;
   prob.lambda_init = 1e3;                                // setUserLambdaInit(1e3) :4121
   prob.max_iterations = 8;                               // optimizer.optimize(8) :4391
   const int N = pk.n_opt, L = (int)pk.vPointMPs.size(), E = (int)pk.edge_pose.size();
@@ -485,19 +356,17 @@ void Optimizer::MergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, bool* pbS
       if (out.chi[e] > (pass == 0 ? chi2Mono2 : chi2Stereo2)) vToErase.push_back(std::make_pair(pk.vEdgeKF[e], pMP));
     }
   std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
-  for (auto& er : vToErase) { er.first->EraseMapPointMatch(er.second); er.second->EraseObservation(er.first); }
+  EraseObservations(vToErase);
   // recover optimised data (:4444-4495): temporal keyframes, then covisible ones; every corrected pose also goes into corrPoses
   std::map<KeyFrame*, int> poseIndex;
   for (int i = 0; i < N; ++i) poseIndex[pk.vPoseKFs[i]] = i;
   auto write_kf = [&](KeyFrame* pKFi) {
     const int i = poseIndex.at(pKFi);
     pKFi->SetPose(out.pose(i));
-    const Sophus::SE3d Tiw = pKFi->GetPose().cast<double>();
-    corrPoses[pKFi] = g2o::Sim3(Tiw.unit_quaternion(), Tiw.translation(), 1.0);
+    corrPoses[pKFi] = Sim3FromPose(pKFi->GetPose());
     if (pKFi->bImu) {
-      const bool linked = std::find(pk.link_prev.begin(), pk.link_prev.end(), i) != pk.link_prev.end() || std::find(pk.link_cur.begin(), pk.link_cur.end(), i) != pk.link_cur.end();
-      pKFi->SetVelocity(linked ? out.velocity(i) : pKFi->GetVelocity());
-      pKFi->SetNewBias(linked ? out.bias(i) : pKFi->GetImuBias());
+      pKFi->SetVelocity(pk.linked(i) ? out.velocity(i) : pKFi->GetVelocity());
+      pKFi->SetNewBias(pk.linked(i) ? out.bias(i) : pKFi->GetImuBias());
     }
   };
   for (KeyFrame* pKFi : pk.vpOptimizableKFs) write_kf(pKFi);

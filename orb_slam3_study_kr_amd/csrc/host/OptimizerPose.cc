@@ -17,10 +17,8 @@ namespace ORB_SLAM3 {
 
 int Optimizer::PoseOptimization(Frame* pFrame) {
   int nInitialCorrespondences = 0;
-  const Sophus::SE3f Tcw = pFrame->GetPose();
-  const Eigen::Quaterniond q = Tcw.unit_quaternion().cast<double>();   // :833-834 float -> double
-  const Eigen::Vector3d t = Tcw.translation().cast<double>();
-  const double pose_qt[7] = {q.x(), q.y(), q.z(), q.w(), t[0], t[1], t[2]};
+  double pose_qt[7];
+  PoseToQt(pFrame->GetPose(), pose_qt);   // :833-834 float -> double
   const double cam[5] = {pFrame->fx, pFrame->fy, pFrame->cx, pFrame->cy, pFrame->mbf};   // :928-932
   const int N = pFrame->N;
   std::vector<double> points, obs, info;
@@ -43,7 +41,7 @@ int Optimizer::PoseOptimization(Frame* pFrame) {
         const bool right = i >= pFrame->Nleft;
         GeometricCamera* c = pFrame->mpCamera;
         if (!c || c->GetType() != GeometricCamera::CAM_FISHEYE || pFrame->mpCamera2->GetType() != GeometricCamera::CAM_FISHEYE ||
-            c->getParameter(0) != pFrame->fx || c->getParameter(1) != pFrame->fy || c->getParameter(2) != pFrame->cx || c->getParameter(3) != pFrame->cy) {
+            !HasIntrinsics(c, pFrame->fx, pFrame->fy, pFrame->cx, pFrame->cy)) {
           std::fprintf(stderr, "PoseOptimization: a two-camera frame that is not a KannalaBrandt8 pair; not supported\n");
           return 0;
         }
@@ -65,8 +63,7 @@ int Optimizer::PoseOptimization(Frame* pFrame) {
         // the mono edge projects through pFrame->mpCamera (:897): the frame's pinhole model or its KannalaBrandt8 (fisheye) model
         GeometricCamera* c = pFrame->mpCamera;
         const bool fisheye = c && c->GetType() == GeometricCamera::CAM_FISHEYE;
-        if (!c || (!fisheye && c->GetType() != GeometricCamera::CAM_PINHOLE) || c->getParameter(0) != pFrame->fx ||
-            c->getParameter(1) != pFrame->fy || c->getParameter(2) != pFrame->cx || c->getParameter(3) != pFrame->cy) {
+        if (!c || (!fisheye && c->GetType() != GeometricCamera::CAM_PINHOLE) || !HasIntrinsics(c, pFrame->fx, pFrame->fy, pFrame->cx, pFrame->cy)) {
           std::fprintf(stderr, "PoseOptimization: monocular observation through a camera that is not the frame's own model; not supported yet\n");
           return 0;
         }
@@ -94,15 +91,13 @@ int Optimizer::PoseOptimization(Frame* pFrame) {
   prob.edge_obs = obs.data(); prob.edge_info = info.data();
   if (has_rig) {
     for (int k = 0; k < 8; ++k) cam2[k] = pFrame->mpCamera2->getParameter(k);
-    const Sophus::SE3f Trl = pFrame->GetRelativePoseTrl();   // e->mTrl = g2o::SE3Quat(Trl.unit_quaternion().cast<double>(), Trl.translation().cast<double>()) (:997)
-    const Eigen::Quaterniond ql = Trl.unit_quaternion().cast<double>();
-    const Eigen::Vector3d tl = Trl.translation().cast<double>();
-    trl[0] = ql.x(); trl[1] = ql.y(); trl[2] = ql.z(); trl[3] = ql.w(); trl[4] = tl[0]; trl[5] = tl[1]; trl[6] = tl[2];
+    // e->mTrl = g2o::SE3Quat(Trl.unit_quaternion().cast<double>(), Trl.translation().cast<double>()) (:997)
+    PoseToQt(pFrame->GetRelativePoseTrl(), trl);
   }
   prob.kb8 = has_kb8 ? kb8 : nullptr;
   prob.cam2 = has_rig ? cam2 : nullptr; prob.trl = has_rig ? trl : nullptr;
-  prob.huber_mono = (double)(float)std::sqrt(5.991);     // const float deltaMono = sqrt(5.991) (:858)
-  prob.huber_stereo = (double)(float)std::sqrt(7.815);   // (:859)
+  prob.huber_mono = kHuberMono;     // const float deltaMono = sqrt(5.991) (:858)
+  prob.huber_stereo = kHuberStereo;
   for (int k = 0; k < 4; ++k) { prob.chi2_mono[k] = 5.991f; prob.chi2_stereo[k] = 7.815f; prob.iterations[k] = 10; }   // :1016-1018
   std::vector<uint8_t> outlier(index.size());
   osh_pose_result res;
@@ -112,9 +107,7 @@ int Optimizer::PoseOptimization(Frame* pFrame) {
     return 0;
   }
   for (size_t e = 0; e < index.size(); ++e) pFrame->mvbOutlier[index[e]] = outlier[e] != 0;
-  const double* qt = res.pose_qt;
-  const Sophus::SE3f pose(Eigen::Quaterniond(qt[3], qt[0], qt[1], qt[2]).cast<float>(), Eigen::Vector3d(qt[4], qt[5], qt[6]).cast<float>());
-  pFrame->SetPose(pose);   // :1111-1112
+  pFrame->SetPose(PoseFromQt(res.pose_qt));   // :1111-1112
   return nInitialCorrespondences - res.n_bad;
 }
 

@@ -22,14 +22,6 @@ namespace ORB_SLAM3 {
 
 namespace {
 
-void pack_preintegration(const IMU::Preintegrated* P, float* rec) {
-  std::memset(rec, 0, sizeof(float) * OSH_PREINT_FLOATS);
-  rec[0] = P->dT;
-  for (int a = 0; a < 9; ++a) { rec[1 + a] = P->dR(a / 3, a % 3); rec[16 + a] = P->JRg(a / 3, a % 3); rec[25 + a] = P->JVg(a / 3, a % 3); rec[34 + a] = P->JVa(a / 3, a % 3); rec[43 + a] = P->JPg(a / 3, a % 3); rec[52 + a] = P->JPa(a / 3, a % 3); }
-  for (int a = 0; a < 3; ++a) { rec[10 + a] = P->dV(a); rec[13 + a] = P->dP(a); }
-  rec[61] = P->b.bax; rec[62] = P->b.bay; rec[63] = P->b.baz; rec[64] = P->b.bwx; rec[65] = P->b.bwy; rec[66] = P->b.bwz;
-}
-
 void invert3(const Eigen::Matrix<float, 15, 15>& C, int o, double* inv) {
   double m[9];
   for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) m[a * 3 + c] = (double)C(o + a, o + c);
@@ -114,8 +106,10 @@ bool PackPoseInertial(Frame* pFrame, bool bRecInit, int mode, PoseiPack& pk) {
       GeometricCamera* c = pFrame->mpCamera;
       const bool fisheye = c && c->GetType() == GeometricCamera::CAM_FISHEYE;
       if (kind != OSH_EDGE_STEREO) {
-        if (!c || (!fisheye && c->GetType() != GeometricCamera::CAM_PINHOLE) || c->getParameter(0) != pFrame->fx || c->getParameter(1) != pFrame->fy ||
-            c->getParameter(2) != pFrame->cx || c->getParameter(3) != pFrame->cy) { pk.unsupported = "monocular observation through a camera that is not the frame's own model"; return false; }
+        if (!c || (!fisheye && c->GetType() != GeometricCamera::CAM_PINHOLE) || !HasIntrinsics(c, pFrame->fx, pFrame->fy, pFrame->cx, pFrame->cy)) {
+          pk.unsupported = "monocular observation through a camera that is not the frame's own model";
+          return false;
+        }
         if (fisheye) { pk.has_kb8 = true; for (int k = 0; k < 4; ++k) pk.kb8[k] = c->getParameter(4 + k); }
       }
       Eigen::Matrix<double, 2, 1> obs2(kpUn.pt.x, kpUn.pt.y);
@@ -134,9 +128,7 @@ bool PackPoseInertial(Frame* pFrame, bool bRecInit, int mode, PoseiPack& pk) {
   if (bRight) {
     if (!pFrame->mpCamera2 || pFrame->mpCamera2->GetType() != GeometricCamera::CAM_FISHEYE || !pk.has_kb8) { pk.unsupported = "a two-camera frame that is not a KannalaBrandt8 pair"; return false; }
     for (int k = 0; k < 8; ++k) pk.cam2[k] = pFrame->mpCamera2->getParameter(k);
-    const Sophus::SE3f Trl = pFrame->GetRelativePoseTrl();               // ImuCamPose(Frame*): Trl.matrix().cast<double>() (src/G2oTypes.cc:104)
-    const Eigen::Matrix3f Rrl = Trl.rotationMatrix();
-    for (int a = 0; a < 3; ++a) { for (int b = 0; b < 3; ++b) pk.trl[a * 4 + b] = (double)Rrl(a, b); pk.trl[a * 4 + 3] = (double)Trl.translation()(a); }
+    PoseTo3x4(pFrame->GetRelativePoseTrl(), pk.trl);                   // ImuCamPose(Frame*): Trl.matrix().cast<double>() (src/G2oTypes.cc:104)
     pk.has_rig = true;
   }
   // current frame: VertexPose / Velocity / GyroBias / AccBias (pFrame) (:4520-4539)
@@ -178,7 +170,7 @@ bool PackPoseInertial(Frame* pFrame, bool bRecInit, int mode, PoseiPack& pk) {
     for (int a = 0; a < 15; ++a) for (int b = 0; b < 15; ++b) pk.prior_H[a * 15 + b] = c->H(a, b);
     Plink = pFrame->mpImuPreintegratedFrame;
   }
-  pack_preintegration(Plink, pk.preint);
+  PackPreintegration(Plink, pk.preint);
   InertialInformation(Plink->C, pk.info_inertial);
   // the random-walk informations come from mpImuPreintegrated in BOTH variants (:4702, 4710 / :5092, 5100)
   invert3(pFrame->mpImuPreintegrated->C, 9, pk.info_g);

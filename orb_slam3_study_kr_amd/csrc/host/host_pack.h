@@ -1,5 +1,7 @@
-// host_pack.h -- the flattened local-BA window produced by PackLocalBA (csrc/host/Optimizer.cc).
+// host_pack.h -- the flat problems the host layer hands to the device (one struct per solver) and the packing and write-back
+// steps the Optimizer:: bodies of csrc/host/ share.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <list>
@@ -7,6 +9,7 @@
 #include <set>
 #include <vector>
 #include "CameraModels/GeometricCamera.h"
+#include "ImuTypes.h"
 #include "KeyFrame.h"
 #include "LoopClosing.h"
 #include "Map.h"
@@ -14,24 +17,134 @@
 #include "orbslam3_hip.h"
 
 namespace ORB_SLAM3 {
-struct LbaPack {
-  std::list<KeyFrame*> lLocalKeyFrames, lFixedCameras;   // same containers / order as src/Optimizer.cc:1119,1163
-  std::list<MapPoint*> lLocalMapPoints;                  // :1136
-  std::vector<KeyFrame*> vPoseKFs;                       // pose order of the problem: optimisable (ascending id), then fixed
+bool InvertDense(int n, const double* A, double* inv);             // Gauss-Jordan, partial pivoting (OptimizerInertial.cc)
+void SymmetricEigen(int n, const double* A, double* w, double* V);  // cyclic Jacobi: A = V diag(w) V^T (OptimizerInertial.cc)
+void InertialInformation(const Eigen::Matrix<float, 15, 15>& C, double* info81);
+
+// Huber deltas of the reference, each the float constant it declares, widened
+inline const double kHuberMono = (double)(float)std::sqrt(5.991);     // const float thHuberMono = sqrt(5.991) (src/Optimizer.cc:1275)
+inline const double kHuberStereo = (double)(float)std::sqrt(7.815);   // const float thHuberStereo = sqrt(7.815) (:1276)
+inline const double kHuber2D = (double)(float)std::sqrt(5.99);        // const float thHuber2D = sqrt(5.99) (:130, 3625)
+inline const double kHuberInertial = std::sqrt(16.92);                // rki->setDelta(sqrt(16.92)) (:2646)
+
+// [qx qy qz qw tx ty tz] of a pose, float members widened to double (src/Optimizer.cc:1217-1218), and back
+inline void PoseToQt(const Sophus::SE3f& T, double* qt) {
+  const Eigen::Quaterniond q = T.unit_quaternion().cast<double>();
+  const Eigen::Vector3d t = T.translation().cast<double>();
+  qt[0] = q.x(); qt[1] = q.y(); qt[2] = q.z(); qt[3] = q.w(); qt[4] = t[0]; qt[5] = t[1]; qt[6] = t[2];
+}
+inline Sophus::SE3f PoseFromQt(const double* qt) {
+  return Sophus::SE3f(Eigen::Quaterniond(qt[3], qt[0], qt[1], qt[2]).cast<float>(), Eigen::Vector3d(qt[4], qt[5], qt[6]).cast<float>());
+}
+// Trl as the 3x4 row-major [R | t] of ImuCamPose (Trl.matrix().cast<double>(), src/G2oTypes.cc:58, 104)
+inline void PoseTo3x4(const Sophus::SE3f& T, double* m) {
+  const Eigen::Matrix3f R = T.rotationMatrix();
+  for (int a = 0; a < 3; ++a) { for (int b = 0; b < 3; ++b) m[a * 4 + b] = (double)R(a, b); m[a * 4 + 3] = (double)T.translation()(a); }
+}
+inline g2o::Sim3 Sim3FromPose(const Sophus::SE3f& T) {
+  const Sophus::SE3d Tcw = T.cast<double>();
+  return g2o::Sim3(Tcw.unit_quaternion(), Tcw.translation(), 1.0);
+}
+// the camera's pinhole part is (fx, fy, cx, cy)
+inline bool HasIntrinsics(GeometricCamera* c, float fx, float fy, float cx, float cy) {
+  return c->getParameter(0) == fx && c->getParameter(1) == fy && c->getParameter(2) == cx && c->getParameter(3) == cy;
+}
+inline bool ByMnId(const MapPoint* a, const MapPoint* b) { return a->mnId < b->mnId; }
+inline void PushPosition(MapPoint* pMP, std::vector<double>& points) {
+  const Eigen::Vector3d X = pMP->GetWorldPos().cast<double>();
+  points.push_back(X[0]); points.push_back(X[1]); points.push_back(X[2]);
+}
+// The 67-float IMU::Preintegrated record of osh_liba_problem / osh_posei_problem: dT, dR, dV, dP, JRg, JVg, JVa, JPg, JPa, b
+inline void PackPreintegration(const IMU::Preintegrated* P, float* rec) {
+  for (int a = 0; a < OSH_PREINT_FLOATS; ++a) rec[a] = 0.f;
+  rec[0] = P->dT;
+  for (int a = 0; a < 9; ++a) {
+    const int r = a / 3, c = a % 3;
+    rec[1 + a] = P->dR(r, c); rec[16 + a] = P->JRg(r, c); rec[25 + a] = P->JVg(r, c); rec[34 + a] = P->JVa(r, c); rec[43 + a] = P->JPg(r, c); rec[52 + a] = P->JPa(r, c);
+  }
+  for (int a = 0; a < 3; ++a) { rec[10 + a] = P->dV(a); rec[13 + a] = P->dP(a); }
+  rec[61] = P->b.bax; rec[62] = P->b.bay; rec[63] = P->b.baz; rec[64] = P->b.bwx; rec[65] = P->b.bwy; rec[66] = P->b.bwz;
+}
+// the reference's erase step for the selected outlier observations (caller holds mMutexMapUpdate)
+inline void EraseObservations(const std::vector<std::pair<KeyFrame*, MapPoint*>>& vToErase) {
+  for (const auto& er : vToErase) {
+    er.first->EraseMapPointMatch(er.second);
+    er.second->EraseObservation(er.first);
+  }
+}
+
+// Map points and visual edges, as both bundle-adjustment packs carry them
+struct VisualPack {
   std::vector<MapPoint*> vPointMPs;                      // ascending id
   std::vector<KeyFrame*> vEdgeKF;                        // per edge, insertion order
   std::vector<MapPoint*> vEdgeMP;
-  int n_free = 0, n_fixed = 0, num_fixedKF = 0;
-  const char* unsupported = nullptr;
-  std::vector<double> pose_qt, pose_cam, points, edge_obs, edge_info;
+  std::vector<double> points, edge_obs, edge_info;
   std::vector<int32_t> edge_pose, edge_point;
   std::vector<uint8_t> edge_kind;
+  const char* unsupported = nullptr;
   bool has_kb8 = false;       // the keyframes' camera is a KannalaBrandt8 (monocular fisheye)
   double kb8[4] = {0, 0, 0, 0};
-  int n_pinhole_mono = 0;
-  bool has_rig = false;       // fisheye stereo rig: right-camera (body) edges through cam2 / trl
+  bool has_rig = false;       // fisheye stereo rig: right-camera edges through cam2 / trl
   double cam2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // point vertices in ascending mnId (their Hessian order): vPointMPs and their positions; returns each point's index
+  std::map<MapPoint*, int> set_points(std::vector<MapPoint*> vMPs) {
+    std::sort(vMPs.begin(), vMPs.end(), ByMnId);
+    vPointMPs = std::move(vMPs);
+    std::map<MapPoint*, int> index;
+    for (size_t j = 0; j < vPointMPs.size(); ++j) {
+      index[vPointMPs[j]] = (int)j;
+      PushPosition(vPointMPs[j], points);
+    }
+    return index;
+  }
+  // index of a point of vPointMPs
+  int point_of(MapPoint* pMP) const { return (int)(std::lower_bound(vPointMPs.begin(), vPointMPs.end(), pMP, ByMnId) - vPointMPs.begin()); }
+  // one visual edge: keypoint kp of pKF observing pMP (an index already checked by the caller), information invSigma2
+  void add_edge(int pose, int point, uint8_t kind, const cv::KeyPoint& kp, float ur, float invSigma2, KeyFrame* pKF, MapPoint* pMP) {
+    edge_pose.push_back(pose);
+    edge_point.push_back(point);
+    edge_kind.push_back(kind);
+    edge_obs.push_back(kp.pt.x); edge_obs.push_back(kp.pt.y); edge_obs.push_back(kind == OSH_EDGE_STEREO ? ur : -1.0);
+    edge_info.push_back(invSigma2);
+    vEdgeKF.push_back(pKF);
+    vEdgeMP.push_back(pMP);
+  }
+  // a fisheye problem is monocular on the device (no rectified-stereo edges next to KannalaBrandt8 ones)
+  bool no_stereo_with_kb8(const char* msg) {
+    if (has_kb8)
+      for (uint8_t k : edge_kind) if (k == OSH_EDGE_STEREO) { unsupported = msg; return false; }
+    return true;
+  }
+};
+
+struct LbaPack : VisualPack {
+  std::list<KeyFrame*> lLocalKeyFrames, lFixedCameras;   // same containers / order as src/Optimizer.cc:1119,1163
+  std::list<MapPoint*> lLocalMapPoints;                  // :1136
+  std::vector<KeyFrame*> vPoseKFs;                       // pose order of the problem: optimisable (ascending id), then fixed
+  int n_free = 0, n_fixed = 0, num_fixedKF = 0;
+  std::vector<double> pose_qt, pose_cam;
+  int n_pinhole_mono = 0;
   double trl[7] = {0, 0, 0, 1, 0, 0, 0};
+  // pose vertices: vFree in ascending id (the Hessian order of the non-fixed vertices, g2o/core/sparse_optimizer.cpp:166-190),
+  // then vFixed; the estimate (:1217-1218) and the camera row (:1352-1356) of each.  Returns each keyframe's pose index.
+  std::map<KeyFrame*, int> set_poses(std::vector<KeyFrame*> vFree, const std::vector<KeyFrame*>& vFixed) {
+    std::sort(vFree.begin(), vFree.end(), [](KeyFrame* a, KeyFrame* b) { return a->mnId < b->mnId; });
+    vPoseKFs = vFree;
+    vPoseKFs.insert(vPoseKFs.end(), vFixed.begin(), vFixed.end());
+    n_free = (int)vFree.size();
+    n_fixed = (int)vFixed.size();
+    std::map<KeyFrame*, int> index;
+    for (size_t i = 0; i < vPoseKFs.size(); ++i) {
+      KeyFrame* pKF = vPoseKFs[i];
+      index[pKF] = (int)i;
+      double qt[7];
+      PoseToQt(pKF->GetPose(), qt);
+      pose_qt.insert(pose_qt.end(), qt, qt + 7);
+      const double cam[5] = {pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf};
+      pose_cam.insert(pose_cam.end(), cam, cam + 5);
+    }
+    return index;
+  }
   // Right camera of a keyframe with a right-camera observation (e->pCamera = pKFi->mpCamera2, e->mTrl = GetRelativePoseTrl(),
   // src/Optimizer.cc:1389-1392): one KannalaBrandt8 model and one Trl shared by the whole window (a rig is rigid).
   bool rig_camera(KeyFrame* pKF) {
@@ -39,10 +152,7 @@ struct LbaPack {
     if (!cam || cam->GetType() != GeometricCamera::CAM_FISHEYE) { unsupported = "right camera that is not a KannalaBrandt8"; return false; }
     double c[8], t[7];
     for (int i = 0; i < 8; ++i) c[i] = cam->getParameter(i);
-    const Sophus::SE3f Trl = pKF->GetRelativePoseTrl();
-    const Eigen::Quaterniond q = Trl.unit_quaternion().cast<double>();
-    const Eigen::Vector3d tt = Trl.translation().cast<double>();
-    t[0] = q.x(); t[1] = q.y(); t[2] = q.z(); t[3] = q.w(); t[4] = tt[0]; t[5] = tt[1]; t[6] = tt[2];
+    PoseToQt(pKF->GetRelativePoseTrl(), t);
     if (has_rig) {
       for (int i = 0; i < 8; ++i) if (c[i] != cam2[i]) { unsupported = "keyframes with different right cameras in one window"; return false; }
       for (int i = 0; i < 7; ++i) if (t[i] != trl[i]) { unsupported = "keyframes with different Trl in one window"; return false; }
@@ -58,19 +168,13 @@ struct LbaPack {
     rightIndex -= pKF->NLeft;                                   // :1369
     if (rightIndex < 0 || rightIndex >= (int)pKF->mvKeysRight.size()) { unsupported = "right-camera index outside mvKeysRight"; return false; }
     const cv::KeyPoint& kp = pKF->mvKeysRight[rightIndex];      // :1372
-    edge_pose.push_back(pose);
-    edge_point.push_back(point);
-    edge_kind.push_back(OSH_EDGE_BODY);
-    edge_obs.push_back(kp.pt.x); edge_obs.push_back(kp.pt.y); edge_obs.push_back(-1.0);
-    edge_info.push_back(pKF->mvInvLevelSigma2[kp.octave]);      // :1380-1381
-    vEdgeKF.push_back(pKF);
-    vEdgeMP.push_back(pMP);
+    add_edge(pose, point, OSH_EDGE_BODY, kp, -1.f, pKF->mvInvLevelSigma2[kp.octave], pKF, pMP);   // :1380-1381
     return true;
   }
   // Camera of a monocular observation (the edge projects through pKF->mpCamera, src/Optimizer.cc:1323): the keyframe's own
   // pinhole model, or one KannalaBrandt8 model shared by the whole window.  Anything else sets `unsupported`.
   bool mono_camera(GeometricCamera* cam, float fx, float fy, float cx, float cy) {
-    if (!cam || cam->getParameter(0) != fx || cam->getParameter(1) != fy || cam->getParameter(2) != cx || cam->getParameter(3) != cy) {
+    if (!cam || !HasIntrinsics(cam, fx, fy, cx, cy)) {
       unsupported = "monocular observation through a camera that is not the keyframe's own model";
       return false;
     }
@@ -88,13 +192,13 @@ struct LbaPack {
     if (has_kb8 && n_pinhole_mono > 0) { unsupported = "pinhole and KannalaBrandt8 monocular observations in one window"; return false; }
     return true;
   }
-  // a fisheye window is monocular on the device (no rectified-stereo edges next to KannalaBrandt8 ones)
   bool camera_models_ok() {
-    if (has_kb8)
-      for (uint8_t k : edge_kind) if (k == OSH_EDGE_STEREO) { unsupported = "rectified-stereo observation in a KannalaBrandt8 window"; return false; }
+    if (!no_stereo_with_kb8("rectified-stereo observation in a KannalaBrandt8 window")) return false;
     if (has_rig && !has_kb8) { unsupported = "right-camera observations without a KannalaBrandt8 left camera"; return false; }
     return true;
   }
+  // the pose of vPoseKFs[i] after a solve: optimised for a free one, as packed for a fixed one
+  Sophus::SE3f pose(int i, const double* out_pose) const { return PoseFromQt(i < n_free ? &out_pose[(size_t)i * 7] : &pose_qt[(size_t)i * 7]); }
   void fill(osh_lba_problem& p) const {
     p.n_free = n_free; p.n_fixed = n_fixed; p.n_points = (int32_t)vPointMPs.size(); p.n_edges = (int32_t)edge_pose.size();
     p.pose_qt = pose_qt.data(); p.pose_cam = pose_cam.data(); p.points = points.data();
@@ -105,26 +209,119 @@ struct LbaPack {
     p.cam2 = has_rig ? cam2 : nullptr; p.trl = has_rig ? trl : nullptr;
   }
 };
-struct LibaPack {
+// The result buffers of one osh_lba_solve; no per-edge outputs when n_edges is 0
+struct LbaOutput {
+  std::vector<double> pose, pts, chi;
+  std::vector<uint8_t> dep;
+  osh_lba_result res;
+  LbaOutput(int n_free, size_t n_points, size_t n_edges) : pose((size_t)n_free * 7), pts(n_points * 3), chi(n_edges), dep(n_edges) {
+    res.pose_qt = pose.data(); res.points = pts.data();
+    res.edge_chi2 = n_edges ? chi.data() : nullptr; res.edge_depth_pos = n_edges ? dep.data() : nullptr;
+  }
+  Eigen::Vector3f point(size_t j) const { return Eigen::Vector3d(pts[3 * j], pts[3 * j + 1], pts[3 * j + 2]).cast<float>(); }
+};
+
+struct LibaPack : VisualPack {
   std::vector<KeyFrame*> vpOptimizableKFs;              // newest first, as the reference builds it (:2402-2417)
   std::list<KeyFrame*> lFixedKeyFrames;
   std::list<MapPoint*> lLocalMapPoints;
   std::vector<KeyFrame*> vPoseKFs;                       // problem order: temporal (ascending id), fixed predecessor, fixed observers
-  std::vector<MapPoint*> vPointMPs;
-  std::vector<KeyFrame*> vEdgeKF;
-  std::vector<MapPoint*> vEdgeMP;
   int n_opt = 0, n_fixed_imu = 0, n_fixed = 0, opt_it = 10;
-  const char* unsupported = nullptr;
-  std::vector<double> pose_Rcw, pose_tcw, pose_Rwb, pose_twb, vel, bias_g, bias_a, points, edge_obs, edge_info, link_info, link_info_g, link_info_a;
+  std::vector<double> pose_Rcw, pose_tcw, pose_Rwb, pose_twb, vel, bias_g, bias_a, link_info, link_info_g, link_info_a;
   double Rcb[9], tcb[3], tbc[3], cam[5];
-  bool has_kb8 = false;       // the window's camera is a KannalaBrandt8 (monocular fisheye)
-  double kb8[4] = {0, 0, 0, 0};
-  bool has_rig = false;       // fisheye stereo rig: OSH_EDGE_RIGHT edges (EdgeMono(1)) through cam2 / trl
-  double cam2[8] = {0, 0, 0, 0, 0, 0, 0, 0}, trl[12] = {0};
-  std::vector<int32_t> edge_pose, edge_point, link_prev, link_cur;
+  double trl[12] = {0};
+  std::vector<int32_t> link_prev, link_cur;
   std::vector<int32_t> link_bias;   // empty, or per link the keyframe that stores the edge's bias vertices (FullInertialBA with bInit)
-  std::vector<uint8_t> edge_kind, link_robust;
+  std::vector<uint8_t> link_robust;
   std::vector<float> link_preint;
+  // ImuCamPose(KeyFrame*) (src/G2oTypes.cc:25-71) of every keyframe of vPoseKFs, float members widened to double; velocity and
+  // biases of the first n_opt + n_fixed_imu; body-camera calibration and camera row of pCalibKF
+  void set_states(KeyFrame* pCalibKF) {
+    for (size_t i = 0; i < vPoseKFs.size(); ++i) {
+      KeyFrame* k = vPoseKFs[i];
+      const Eigen::Matrix3f Rcw = k->GetRotation(), Rwb = k->GetImuRotation();
+      const Eigen::Vector3f tcw = k->GetTranslation(), twb = k->GetImuPosition();
+      for (int a = 0; a < 9; ++a) { pose_Rcw.push_back((double)Rcw(a / 3, a % 3)); pose_Rwb.push_back((double)Rwb(a / 3, a % 3)); }
+      for (int a = 0; a < 3; ++a) { pose_tcw.push_back((double)tcw(a)); pose_twb.push_back((double)twb(a)); }
+      if ((int)i < n_opt + n_fixed_imu) {
+        const Eigen::Vector3f v = k->GetVelocity(), bg = k->GetGyroBias(), ba = k->GetAccBias();
+        for (int a = 0; a < 3; ++a) { vel.push_back((double)v(a)); bias_g.push_back((double)bg(a)); bias_a.push_back((double)ba(a)); }
+      }
+    }
+    const IMU::Calib& cal = pCalibKF->mImuCalib;
+    const Eigen::Matrix3f R = cal.mTcb.rotationMatrix();
+    for (int a = 0; a < 9; ++a) Rcb[a] = (double)R(a / 3, a % 3);
+    for (int a = 0; a < 3; ++a) { tcb[a] = (double)cal.mTcb.translation()(a); tbc[a] = (double)cal.mTbc.translation()(a); }
+    cam[0] = pCalibKF->fx; cam[1] = pCalibKF->fy; cam[2] = pCalibKF->cx; cam[3] = pCalibKF->cy; cam[4] = pCalibKF->mbf;
+  }
+  // EdgeInertial + EdgeGyroRW + EdgeAccRW between pKFi->mPrevKF (pose prev) and pKFi (pose cur) (src/Optimizer.cc:523-568,
+  // 2600-2667, 4226-4257); the inertial information is scaled by infoScale
+  void add_link(KeyFrame* pKFi, int prev, int cur, bool robust, double infoScale) {
+    IMU::Preintegrated* P = pKFi->mpImuPreintegrated;
+    link_prev.push_back(prev);
+    link_cur.push_back(cur);
+    float rec[OSH_PREINT_FLOATS];
+    PackPreintegration(P, rec);
+    link_preint.insert(link_preint.end(), rec, rec + OSH_PREINT_FLOATS);
+    double info[81];
+    InertialInformation(P->C, info);
+    for (double& x : info) x *= infoScale;
+    link_info.insert(link_info.end(), info, info + 81);
+    link_robust.push_back(robust ? 1 : 0);
+    for (int which = 0; which < 2; ++which) {
+      double Cb[9], inv[9];
+      for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) Cb[a * 3 + c] = (double)P->C(9 + 3 * which + a, 9 + 3 * which + c);
+      InvertDense(3, Cb, inv);
+      std::vector<double>& dst = which == 0 ? link_info_g : link_info_a;
+      dst.insert(dst.end(), inv, inv + 9);
+    }
+  }
+  // one KannalaBrandt8 per problem (ImuCamPose::Project goes through pKFi->mpCamera, src/G2oTypes.cc:166-171); notOwnModel is the
+  // message for a camera whose pinhole part is not cam
+  bool note_fisheye(KeyFrame* pKFi, const char* notOwnModel) {
+    GeometricCamera* c = pKFi->mpCamera;
+    if (!HasIntrinsics(c, (float)cam[0], (float)cam[1], (float)cam[2], (float)cam[3])) { unsupported = notOwnModel; return false; }
+    for (int k = 0; k < 4; ++k) {
+      if (has_kb8 && kb8[k] != (double)c->getParameter(4 + k)) { unsupported = "keyframes with different KannalaBrandt8 coefficients"; return false; }
+      kb8[k] = c->getParameter(4 + k);
+    }
+    has_kb8 = true;
+    return true;
+  }
+  // the KannalaBrandt8 pair and Trl of a keyframe with a right-camera observation (EdgeMono(1)): one rig per problem
+  bool note_rig(KeyFrame* pKFi, const char* notOwnModel) {
+    if (pKFi->mpCamera->GetType() != GeometricCamera::CAM_FISHEYE || pKFi->mpCamera2->GetType() != GeometricCamera::CAM_FISHEYE) {
+      unsupported = "right-camera observation of a rig that is not a KannalaBrandt8 pair"; return false;
+    }
+    if (!note_fisheye(pKFi, notOwnModel)) return false;
+    double c2[8], T[12];
+    for (int k = 0; k < 8; ++k) c2[k] = pKFi->mpCamera2->getParameter(k);
+    PoseTo3x4(pKFi->GetRelativePoseTrl(), T);
+    if (has_rig) {
+      for (int k = 0; k < 8; ++k) if (cam2[k] != c2[k]) { unsupported = "keyframes with different right cameras"; return false; }
+      for (int k = 0; k < 12; ++k) if (trl[k] != T[k]) { unsupported = "keyframes with different left-to-right transforms"; return false; }
+    }
+    std::copy(c2, c2 + 8, cam2); std::copy(T, T + 12, trl);
+    has_rig = true;
+    return true;
+  }
+  // keeps the points of `all` (ascending id) that an edge refers to (g2o never activates the others) and renumbers edge_point
+  void drop_unobserved_points(const std::vector<MapPoint*>& all) {
+    std::vector<int> count(all.size(), 0), remap(all.size(), -1);
+    for (int32_t j : edge_point) ++count[j];
+    vPointMPs.clear(); points.clear();
+    for (size_t j = 0; j < all.size(); ++j)
+      if (count[j]) {
+        remap[j] = (int)vPointMPs.size();
+        vPointMPs.push_back(all[j]);
+        PushPosition(all[j], points);
+      }
+    for (int32_t& j : edge_point) j = remap[j];
+  }
+  // the pose index is an end of some inertial link
+  bool linked(int i) const {
+    return std::find(link_prev.begin(), link_prev.end(), i) != link_prev.end() || std::find(link_cur.begin(), link_cur.end(), i) != link_cur.end();
+  }
   void fill(osh_liba_problem& p) const {
     p.n_opt = n_opt; p.n_fixed_imu = n_fixed_imu; p.n_fixed = n_fixed;
     p.n_points = (int32_t)vPointMPs.size(); p.n_edges = (int32_t)edge_pose.size(); p.n_links = (int32_t)link_prev.size();
@@ -139,6 +336,26 @@ struct LibaPack {
     p.cam2 = has_rig ? cam2 : nullptr; p.trl = has_rig ? trl : nullptr;
     p.link_bias = link_bias.empty() ? nullptr : link_bias.data();
   }
+};
+// The result buffers of one osh_liba_solve and the map types its rows become
+struct LibaOutput {
+  std::vector<double> Rcw, tcw, Rwb, twb, v, bg, ba, pts, chi;
+  std::vector<uint8_t> dep;
+  osh_liba_result res;
+  LibaOutput(int N, int L, int E) : Rcw((size_t)N * 9), tcw((size_t)N * 3), Rwb((size_t)N * 9), twb((size_t)N * 3), v((size_t)N * 3), bg((size_t)N * 3), ba((size_t)N * 3),
+                                    pts((size_t)L * 3), chi(E), dep(E) {
+    res.pose_Rcw = Rcw.data(); res.pose_tcw = tcw.data(); res.pose_Rwb = Rwb.data(); res.pose_twb = twb.data();
+    res.vel = v.data(); res.bias_g = bg.data(); res.bias_a = ba.data(); res.points = pts.data(); res.edge_chi2 = chi.data(); res.edge_depth_pos = dep.data();
+  }
+  Sophus::SE3f pose(int i) const {
+    Eigen::Matrix3f R; Eigen::Vector3f t;
+    for (int a = 0; a < 9; ++a) R(a / 3, a % 3) = (float)Rcw[(size_t)i * 9 + a];
+    for (int a = 0; a < 3; ++a) t(a) = (float)tcw[(size_t)i * 3 + a];
+    return Sophus::SE3f(R, t);
+  }
+  Eigen::Vector3f velocity(int i) const { return Eigen::Vector3f((float)v[(size_t)i * 3], (float)v[(size_t)i * 3 + 1], (float)v[(size_t)i * 3 + 2]); }
+  IMU::Bias bias(int i) const { return IMU::Bias(ba[(size_t)i * 3], ba[(size_t)i * 3 + 1], ba[(size_t)i * 3 + 2], bg[(size_t)i * 3], bg[(size_t)i * 3 + 1], bg[(size_t)i * 3 + 2]); }
+  Eigen::Vector3f point(int j) const { return Eigen::Vector3d(pts[3 * (size_t)j], pts[3 * (size_t)j + 1], pts[3 * (size_t)j + 2]).cast<float>(); }
 };
 // Flat problem of Optimizer::PoseInertialOptimizationLastKeyFrame (mode 0) / LastFrame (mode 1), src/Optimizer.cc:4499-5299
 struct PoseiPack {
@@ -169,8 +386,8 @@ struct PoseiPack {
     p.prior_bg = pr ? prior_bg : nullptr; p.prior_ba = pr ? prior_ba : nullptr; p.prior_H = pr ? prior_H : nullptr;
     p.points = points.data(); p.edge_kind = edge_kind.data(); p.edge_obs = edge_obs.data(); p.edge_info = edge_info.data();
     p.edge_close = edge_close.data();
-    p.huber_mono = (double)(float)std::sqrt(5.991);     // const float thHuberMono = sqrt(5.991) (:4552)
-    p.huber_stereo = (double)(float)std::sqrt(7.815);
+    p.huber_mono = kHuberMono;                           // const float thHuberMono = sqrt(5.991) (:4552)
+    p.huber_stereo = kHuberStereo;
     p.huber_prior = 5.0;                                 // rkp->setDelta(5) (:5117)
     const float m0[4] = {12.f, 7.5f, 5.991f, 5.991f}, m1[4] = {5.991f, 5.991f, 5.991f, 5.991f}, st[4] = {15.6f, 9.8f, 7.815f, 7.815f};
     for (int k = 0; k < 4; ++k) { p.chi2_mono[k] = mode == 0 ? m0[k] : m1[k]; p.chi2_stereo[k] = st[k]; p.iterations[k] = 10; }   // :4714-4716 / :5121-5123
@@ -185,7 +402,6 @@ bool PackLocalInertialBA(KeyFrame* pKF, Map* pMap, bool bLarge, bool bRecInit, L
 bool PackFullInertialBA(Map* pMap, int its, bool bFixLocal, bool bInit, float priorG, float priorA, LibaPack& pk, std::vector<KeyFrame*>& vpIdle,
                         std::vector<MapPoint*>& vpAllMPs, int* sharedBiasSlot);
 bool PackMergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, LibaPack& pk, std::vector<KeyFrame*>& vpCovKFs);
-void InertialInformation(const Eigen::Matrix<float, 15, 15>& C, double* info81);
 osh_lba_ctx* HostSolverContext();   // one solver context per calling thread (Optimizer.cc)
 
 // Optimizer::OptimizeEssentialGraph as an osh_pgo_problem (OptimizerEssentialGraph.cc): vertices in keyframe-id order, edges in
