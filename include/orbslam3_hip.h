@@ -281,7 +281,7 @@ typedef struct osh_posei_result {
   int32_t n_inliers;          /* nInliers of the last round */
   int32_t rounds;
   int32_t status;
-  double H[900];              /* mode 0: 15x15 in the first 225 entries; mode 1: 30x30 */
+  double H[900];              /* mode 0: 15x15 in the first 225 entries, the rest 0; mode 1: 30x30 */
 } osh_posei_result;
 
 int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_problem* problems, osh_posei_result* results);

@@ -4,6 +4,8 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <algorithm>
 #include <initializer_list>
 #include "../../include/orbslam3_hip.h"
@@ -50,6 +52,25 @@ int allow_dynamic_lds(int device, int bytes, std::initializer_list<const void*> 
 template <class... K>
 int allow_dynamic_lds(int device, int bytes, K... kernels) { return allow_dynamic_lds(device, bytes, {(const void*)kernels...}); }
 
+// OSH_ZERO_NEW_BUFFERS=1 (a test aid, read at every allocation): every new device or pinned allocation of a context is zero-filled
+// before it is handed out, so that what a call reads without having written it no longer depends on which memory the allocator
+// recycled.  Zero only: it is a valid index and a harmless double everywhere.
+inline bool zero_new_buffers() {
+  const char* e = std::getenv("OSH_ZERO_NEW_BUFFERS");
+  return e && std::strcmp(e, "1") == 0;
+}
+// Zero-fills `bytes` of device memory at `p` when OSH_ZERO_NEW_BUFFERS=1, complete on return (the contexts' streams do not wait for
+// the null stream).
+inline int zero_new_device(void* p, size_t bytes) {
+  if (!zero_new_buffers()) return OSH_OK;
+  OSH_HIP(hipMemset(p, 0, bytes));
+  OSH_HIP(hipStreamSynchronize(nullptr));
+  return OSH_OK;
+}
+inline void zero_new_host(void* p, size_t bytes) {
+  if (zero_new_buffers()) std::memset(p, 0, bytes);
+}
+
 // Simple growable device buffer (never shrinks; reused across batches).
 struct DevBuf {
   void* p = nullptr;
@@ -64,7 +85,7 @@ struct DevBuf {
     size_t want = bytes + bytes / 8 + 256;
     OSH_HIP(hipMalloc(&p, want));
     cap = want;
-    return OSH_OK;
+    return zero_new_device(p, want);
   }
   void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -84,6 +105,7 @@ struct PinBuf {
     const size_t want = bytes + bytes / 8 + 4096;   // slack, as DevBuf: pinning is slow, a slightly larger batch reuses the buffer
     if (hipHostMalloc(&p, want) != hipSuccess) { p = nullptr; cap = 0; return nullptr; }
     cap = want;
+    zero_new_host(p, want);
     return p;
   }
   void release() { if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; } }

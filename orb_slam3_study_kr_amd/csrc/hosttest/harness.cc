@@ -4,7 +4,9 @@
 #include <cmath>
 #include <map>
 #include <memory>
+#include <new>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 #include "Frame.h"
@@ -16,10 +18,17 @@
 
 using namespace ORB_SLAM3;
 
+// The keyframes of a stand-in map live in one block, in array order: containers the reference keys by KeyFrame* (LoopConnections
+// of the essential graphs, std::set<KeyFrame*>) then iterate in the same order for every construction of the same map, as they
+// would not with one heap allocation per keyframe, whose addresses depend on what the thread freed before.
+struct KfDestroy { void operator()(KeyFrame* k) const { k->~KeyFrame(); } };
+using KfSlot = std::aligned_storage_t<sizeof(KeyFrame), alignof(KeyFrame)>;
+
 struct osh_host_graph {
   Map map;
   std::unique_ptr<GeometricCamera> cam, cam2;
-  std::vector<std::unique_ptr<KeyFrame>> kfs;
+  std::unique_ptr<KfSlot[]> kf_block;   // declared before kfs: released after the keyframes in it are destroyed
+  std::vector<std::unique_ptr<KeyFrame, KfDestroy>> kfs;
   std::vector<std::unique_ptr<MapPoint>> mps;
   std::vector<std::unique_ptr<IMU::Preintegrated>> preints;
   LibaPack liba;   // storage behind osh_host_pack_liba
@@ -51,8 +60,9 @@ extern "C" osh_host_graph* osh_host_graph_create(int32_t n_kf, const int64_t* kf
   g->map.mnInitKFid = (unsigned long)init_kf_id;
   g->map.mbIsInertial = inertial != 0;
   g->cam.reset(new Pinhole(std::vector<float>{cam5[0], cam5[1], cam5[2], cam5[3]}));
+  g->kf_block.reset(new KfSlot[std::max(n_kf, 1)]);
   for (int i = 0; i < n_kf; ++i) {
-    std::unique_ptr<KeyFrame> kf(new KeyFrame((unsigned long)kf_id[i], &g->map));
+    std::unique_ptr<KeyFrame, KfDestroy> kf(new (&g->kf_block[i]) KeyFrame((unsigned long)kf_id[i], &g->map));
     kf->SetPose(pose_from(kf_pose_qt + 7 * i));
     kf->mnPoseSets = 0;
     kf->fx = cam5[0]; kf->fy = cam5[1]; kf->cx = cam5[2]; kf->cy = cam5[3]; kf->mbf = cam5[4];

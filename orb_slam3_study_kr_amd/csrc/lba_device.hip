@@ -1422,6 +1422,7 @@ extern "C" int osh_lba_create(int device, osh_lba_ctx** out) {
   c->device = device;
   OSH_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   OSH_HIP(hipHostMalloc((void**)&c->h_nactive, sizeof(int)));
+  zero_new_host(c->h_nactive, sizeof(int));
   *out = c;
   return OSH_OK;
 }
@@ -1541,6 +1542,7 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
   if (c->h_stop_cap < (size_t)nw) {
     if (c->h_stop) (void)hipHostFree(c->h_stop);
     OSH_HIP(hipHostMalloc((void**)&c->h_stop, nw));
+    zero_new_host(c->h_stop, nw);
     c->h_stop_cap = nw;
   }
   OSH_HIP(hipMemsetAsync(c->d_xp.p, 0, std::max<size_t>(NFP * 6 * 8, 8), s));

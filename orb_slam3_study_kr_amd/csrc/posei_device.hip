@@ -621,7 +621,10 @@ extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_p
     std::memcpy(r.Rcw, o.P, 72); std::memcpy(r.tcw, o.P + 9, 24); std::memcpy(r.Rwb, o.P + 12, 72); std::memcpy(r.twb, o.P + 21, 24);
     std::memcpy(r.vel, o.s, 24); std::memcpy(r.bias_g, o.s + 3, 24); std::memcpy(r.bias_a, o.s + 6, 24);
     r.n_bad = o.n_bad; r.n_inliers = o.n_inliers; r.rounds = o.rounds; r.status = OSH_OK;
-    std::memcpy(r.H, o.H, sizeof(r.H));
+    // the kernel writes the frame's n x n entries only: the rest of the slot is what an earlier mode-1 frame left in the arena
+    const size_t nH = h_desc[f].mode == 1 ? 900 : 225;
+    std::memcpy(r.H, o.H, nH * 8);
+    std::fill(r.H + nH, r.H + 900, 0.0);
   }
   return OSH_OK;
 }

@@ -4,9 +4,12 @@ size -- local-BA batches of 1 .. 200 windows (both packers, windows of 1 .. 60 k
 factorisation), LocalInertialBA windows alone and in batches, FullInertialBA-shaped maps in the dense and in the banded layout -- and
 every result is compared, bit for bit, with the same call in a FRESH context (buffers that grow and are reused, sections a kernel
 assumes to be zero, state left by the previous call).  Found in r03: the banded layout of an inertial map read 15 columns past the band it
-had written (profiles/r03_soak.txt).
+had written (profiles/r03_soak.txt).  Pose, pose-inertial, both pose graphs and OptimizeSim3 batches join the draw through the raw calls
+of tests/test_gpu_reuse.py (every result scalar and output array compared).  OSH_ZERO_NEW_BUFFERS=1: new allocations start zeroed, so
+a fresh context never starts from memory the allocator recycled from the previous one.
 Usage: python profiles/soak_reuse.py [seconds] [seed]"""
 import dataclasses
+import os
 import sys
 import time
 from pathlib import Path
@@ -15,9 +18,12 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+os.environ["OSH_ZERO_NEW_BUFFERS"] = "1"
 
 from orb_slam3_study_kr_amd import lba, synth  # noqa: E402
 from orb_slam3_study_kr_amd import synth_inertial as si  # noqa: E402
+import test_gpu_reuse as tr  # noqa: E402
 
 LBA_FIELDS = ("pose_qt", "points", "edge_chi2", "chi2_trace")
 LIBA_FIELDS = ("chi2_trace", "pose_twb", "vel", "bias_g", "bias_a", "points")
@@ -56,12 +62,40 @@ def main():
                 pool[key] = dataclasses.replace(w, lambda_init=1e-5, max_iterations=4, link_robust=np.ones_like(w.link_robust))
         return pool[key]
 
+    def other_call(kind):
+        k = int(rng.integers(0, 6))
+        if kind == "pose":
+            frames = [synth.make_pose_frame(60 + (k + i) % 6, n_points=[12, 300, 900, 1500][(k + i) % 4]) for i in range(int(rng.choice([1, 5, 48])))]
+            return tr.pose_call(f"{len(frames)} frames", frames)
+        if kind == "posei":
+            ins = tr.posei_script_inputs()
+            return tr.posei_call(f"set {k}", [ins["batch1"], ins["mode0"], ins["mixed"], [ins["large"]], [ins["recovery"]], ins["batch1"][:3]][k])
+        if kind == "pgo":
+            return tr.pgo_call(f"{[50, 300, 1000][k % 3]} vertices", tr._pgo_graph([50, 300, 1000][k % 3], mono=k < 3), dense=k == 5)
+        if kind == "pgo4":
+            return tr.pgo4_call(f"{[50, 300][k % 2]} vertices", tr._pgo4_graph([50, 300][k % 2]), dense=k == 4)
+        ins = tr.sim3_script_inputs()
+        return tr.sim3_call(f"set {k}", [ins["batch"], [ins["round2"]], [ins["early"]], [ins["kb8"]], [ins["pin"]], ins["batch"][:4]][k])
+
     n = 0
     kinds = {}
     with lba.LbaSolver(0) as live:
         while time.time() < t_end:
-            kind = str(rng.choice(["lba_small", "lba_batch", "lba_map", "liba_one", "liba_batch", "liba_dense_map", "liba_banded_map"],
-                              p=[0.25, 0.2, 0.05, 0.15, 0.15, 0.1, 0.1]))
+            kind = str(rng.choice(["lba_small", "lba_batch", "lba_map", "liba_one", "liba_batch", "liba_dense_map", "liba_banded_map",
+                                   "pose", "posei", "pgo", "pgo4", "sim3"],
+                                  p=[0.15, 0.12, 0.04, 0.1, 0.1, 0.07, 0.07, 0.07, 0.07, 0.07, 0.07, 0.07]))
+            if kind in ("pose", "posei", "pgo", "pgo4", "sim3"):
+                call = other_call(kind)
+                got = call.run(live.lib, live.ctx)
+                missing = call.written(got)
+                ref = tr.fresh_run(live.lib, call)
+                diff = next((f"{k}: {tr._first_difference(got[k], ref[k])}" for k in sorted(got) if got[k].tobytes() != ref[k].tobytes()), None)
+                if missing or diff:
+                    print(f"MISMATCH call {n} ({kind}: {call.desc}): {'; '.join(missing) or diff}", flush=True)
+                    return 1
+                kinds[kind] = kinds.get(kind, 0) + 1
+                n += 1
+                continue
             if kind in ("lba_small", "lba_batch", "lba_map"):
                 if kind == "lba_small":
                     ws = [lba_window(int(rng.integers(0, 40))) for _ in range(int(rng.integers(1, 6)))]

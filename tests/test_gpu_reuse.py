@@ -1,0 +1,940 @@
+"""No solver result may depend on what its context ran before.
+
+Every solver keeps its staging and work buffers in one ``osh_lba_ctx`` (the ORB searches in one ``osh_orb_ctx``); the buffers only grow
+and are never cleared, and the host layer keeps one context per thread for as long as the system runs.  A value a kernel reads without
+having written it, or an output slot it skips, then carries the previous call's data into this call's result.
+
+The tests here run a fixed script of calls of every kind and size on ONE long-lived context and compare every step, bit for bit, with
+the same call in a fresh context made for that step.  OSH_ZERO_NEW_BUFFERS=1 zero-fills every new allocation, so the fresh side never
+starts from memory the allocator recycled from an earlier context.  The live side's output arrays are caller-owned and filled with a
+sentinel: every entry the header documents as written must have lost it.  The last (small) step of each solver is also checked
+against an independent reference.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import threading
+from dataclasses import dataclass
+from typing import Callable
+
+import numpy as np
+import pytest
+
+from orb_slam3_study_kr_amd import capi, host, orb, synth
+from orb_slam3_study_kr_amd import synth_inertial as si
+from orb_slam3_study_kr_amd import synth_pgo as sp
+from orb_slam3_study_kr_amd import synth_sim3 as ss
+
+pytestmark = pytest.mark.gpu
+
+# ---------------------------------------------------------------------------------------------------------------- sentinels
+# Caller-owned output arrays start with these bit patterns (a NaN with a payload no kernel produces, and values no output takes).
+SENT = {np.dtype(np.float64): np.uint64(0x7FF8DEADBEEF0BAD), np.dtype(np.float32): np.uint32(0x7FC0DEAD),
+        np.dtype(np.int32): np.uint32(0xA5A5A5A5), np.dtype(np.uint8): np.uint8(0xEE)}
+STRUCT_BYTE = 0xEE      # the scalar fields of a result struct start as 0xEE bytes
+
+
+def _bits(a):
+    a = np.asarray(a)
+    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def _out(shape, dtype=np.float64):
+    a = np.empty(shape, dtype=dtype)
+    _bits(a)[...] = SENT[np.dtype(dtype)]
+    return a
+
+
+def _unwritten(a):
+    a = np.asarray(a)
+    return _bits(a) == SENT[a.dtype]
+
+
+def _struct(cls):
+    r = cls()
+    C.memset(C.addressof(r), STRUCT_BYTE, C.sizeof(r))
+    return r
+
+
+def _is_pointer(ct):
+    return isinstance(ct, type) and (issubclass(ct, C._Pointer) or ct in (C.c_void_p, C.c_char_p))
+
+
+_SCALAR_KEYS = set()   # the keys _scalars made (a name is never both a struct field and a caller-owned array)
+
+
+def _scalars(r, prefix):
+    """Every non-pointer field of a ctypes result struct as a numpy array of its own type (traces and fixed arrays included)."""
+    out = {}
+    for name, ct in type(r)._fields_:
+        if _is_pointer(ct):
+            continue
+        base = ct
+        while hasattr(base, "_length_"):
+            base = base._type_
+        f = getattr(type(r), name)
+        raw = C.string_at(C.addressof(r) + f.offset, f.size)
+        out[f"{prefix}.{name}"] = np.frombuffer(raw, dtype=np.dtype(base)).copy()
+        _SCALAR_KEYS.add(f"{prefix}.{name}")
+    return out
+
+
+def _struct_unset(v):
+    return v.view(np.uint8).reshape(v.size, -1).min(axis=1) == STRUCT_BYTE if v.size else np.zeros(0, bool)
+
+
+def _need_written(out, missing, key, sl=slice(None)):
+    v = out[key]
+    bad = (_struct_unset(v) if key in _SCALAR_KEYS else _unwritten(v).reshape(-1))[sl]
+    if bad.any():
+        missing.append(f"{key}: {int(bad.sum())} of {bad.size} documented entries never written (first at {int(np.argmax(bad))})")
+
+
+# -------------------------------------------------------------------------------------------------------------- the call kinds
+@dataclass
+class Call:
+    """One C-ABI call: `run(lib, ctx)` makes it with sentinel-filled outputs and returns every output array and result scalar;
+    `written(out)` lists what the header promises to write and was not."""
+    kind: str
+    desc: str
+    run: Callable
+    written: Callable
+    reference: Callable | None = None
+
+
+def _ok(lib, rc, what):
+    capi.check(rc, what, lib)
+
+
+def lba_call(desc, windows, pack_mode=-1, reference=None):
+    def run(lib, ctx):
+        _ok(lib, lib.osh_lba_set_pack_mode(ctx, pack_mode), "osh_lba_set_pack_mode")
+        probs = (capi.LbaProblem * len(windows))(*[w.as_struct() for w in windows])
+        res = (capi.LbaResult * len(windows))()
+        out = {}
+        for i, w in enumerate(windows):
+            res[i] = _struct(capi.LbaResult)
+            arrs = dict(pose_qt=_out((w.n_free, 7)), points=_out((w.n_points, 3)), edge_chi2=_out(w.n_edges), edge_depth_pos=_out(w.n_edges, np.uint8))
+            res[i].pose_qt, res[i].points = capi.ptr(arrs["pose_qt"], capi.c_double_p), capi.ptr(arrs["points"], capi.c_double_p)
+            res[i].edge_chi2, res[i].edge_depth_pos = capi.ptr(arrs["edge_chi2"], capi.c_double_p), capi.ptr(arrs["edge_depth_pos"], capi.c_uint8_p)
+            out.update({f"w{i}.{k}": v for k, v in arrs.items()})
+        _ok(lib, lib.osh_lba_solve(ctx, len(windows), probs, res), "osh_lba_solve")
+        for i in range(len(windows)):
+            out.update(_scalars(res[i], f"w{i}"))
+        return out
+
+    def written(out):
+        missing = []
+        for i in range(len(windows)):
+            for k in ("pose_qt", "points", "edge_chi2", "edge_depth_pos", "status", "iterations", "trials", "n_trace", "chi2_initial"):
+                _need_written(out, missing, f"w{i}.{k}")
+            n = int(out[f"w{i}.n_trace"][0])
+            for k in ("chi2_trace", "lambda_trace", "trials_trace"):
+                _need_written(out, missing, f"w{i}.{k}", slice(0, n))
+            assert out[f"w{i}.status"][0] == capi.OSH_OK
+        return missing
+    return Call("lba", desc, run, written, reference)
+
+
+LIBA_STATE = (("pose_Rcw", 9), ("pose_tcw", 3), ("pose_Rwb", 9), ("pose_twb", 3), ("vel", 3), ("bias_g", 3), ("bias_a", 3))
+
+
+def liba_call(desc, windows, reference=None):
+    def run(lib, ctx):
+        probs = (capi.LibaProblem * len(windows))(*[w.as_struct() for w in windows])
+        res = (capi.LibaResult * len(windows))()
+        out = {}
+        for i, w in enumerate(windows):
+            res[i] = _struct(capi.LibaResult)
+            arrs = {k: _out((w.n_opt, d)) for k, d in LIBA_STATE}
+            arrs.update(points=_out((w.n_points, 3)), edge_chi2=_out(w.n_edges), edge_depth_pos=_out(w.n_edges, np.uint8))
+            for k, v in arrs.items():
+                setattr(res[i], k, capi.ptr(v, capi.c_uint8_p if v.dtype == np.uint8 else capi.c_double_p))
+            out.update({f"w{i}.{k}": v for k, v in arrs.items()})
+        _ok(lib, lib.osh_liba_solve(ctx, len(windows), probs, res), "osh_liba_solve")
+        for i in range(len(windows)):
+            out.update(_scalars(res[i], f"w{i}"))
+        return out
+
+    def written(out):
+        missing = []
+        for i in range(len(windows)):
+            for k in [k for k, _ in LIBA_STATE] + ["points", "edge_chi2", "edge_depth_pos", "status", "iterations", "trials", "n_trace",
+                                                    "chi2_initial", "chi2_final"]:
+                _need_written(out, missing, f"w{i}.{k}")
+            n = int(out[f"w{i}.n_trace"][0])
+            for k in ("chi2_trace", "lambda_trace", "trials_trace"):
+                _need_written(out, missing, f"w{i}.{k}", slice(0, n))
+            assert out[f"w{i}.status"][0] == capi.OSH_OK
+        return missing
+    return Call("liba", desc, run, written, reference)
+
+
+def pose_call(desc, frames, reference=None):
+    def run(lib, ctx):
+        probs = (capi.PoseProblem * len(frames))(*[f.as_struct() for f in frames])
+        res = (capi.PoseResult * len(frames))()
+        out = {}
+        for i, f in enumerate(frames):
+            res[i] = _struct(capi.PoseResult)
+            arrs = dict(outlier=_out(f.n_edges, np.uint8), edge_chi2=_out(f.n_edges))
+            res[i].outlier, res[i].edge_chi2 = capi.ptr(arrs["outlier"], capi.c_uint8_p), capi.ptr(arrs["edge_chi2"], capi.c_double_p)
+            out.update({f"f{i}.{k}": v for k, v in arrs.items()})
+        _ok(lib, lib.osh_pose_optimize(ctx, len(frames), probs, res), "osh_pose_optimize")
+        for i in range(len(frames)):
+            out.update(_scalars(res[i], f"f{i}"))
+        return out
+
+    def written(out):
+        missing = []
+        for i in range(len(frames)):
+            for k in ("outlier", "edge_chi2", "pose_qt", "n_bad", "rounds", "status"):
+                _need_written(out, missing, f"f{i}.{k}")
+            n = int(out[f"f{i}.rounds"][0])
+            for k in ("iterations", "chi2_final"):
+                _need_written(out, missing, f"f{i}.{k}", slice(0, n))
+            assert out[f"f{i}.status"][0] == capi.OSH_OK
+        return missing
+    return Call("pose", desc, run, written, reference)
+
+
+def posei_call(desc, frames, reference=None):
+    def run(lib, ctx):
+        probs = (capi.PoseiProblem * len(frames))(*[f.as_struct() for f in frames])
+        res = (capi.PoseiResult * len(frames))()
+        out = {}
+        for i, f in enumerate(frames):
+            res[i] = _struct(capi.PoseiResult)
+            arrs = dict(outlier=_out(f.n_edges, np.uint8), edge_chi2=_out(f.n_edges))
+            res[i].outlier, res[i].edge_chi2 = capi.ptr(arrs["outlier"], capi.c_uint8_p), capi.ptr(arrs["edge_chi2"], capi.c_double_p)
+            out.update({f"f{i}.{k}": v for k, v in arrs.items()})
+        _ok(lib, lib.osh_posei_optimize(ctx, len(frames), probs, res), "osh_posei_optimize")
+        for i in range(len(frames)):
+            out.update(_scalars(res[i], f"f{i}"))
+        return out
+
+    def written(out):
+        missing = []
+        for i, f in enumerate(frames):
+            for k in ("Rcw", "tcw", "Rwb", "twb", "vel", "bias_g", "bias_a", "outlier", "edge_chi2", "n_bad", "n_inliers", "rounds", "status"):
+                _need_written(out, missing, f"f{i}.{k}")
+            _need_written(out, missing, f"f{i}.H", slice(0, 900 if f.mode == 1 else 225))
+            if f.mode == 0 and np.any(out[f"f{i}.H"][225:] != 0.0):   # (the header: the rest 0)
+                missing.append(f"f{i}.H: entries beyond the 15 x 15 block of a mode-0 frame are not 0")
+            assert out[f"f{i}.status"][0] == capi.OSH_OK
+        return missing
+    return Call("posei", desc, run, written, reference)
+
+
+def sim3_call(desc, packs, reference=None):
+    def run(lib, ctx):
+        keep = []
+        probs = (capi.Sim3Problem * len(packs))(*[ss.problem(p, keep) for p in packs])
+        res = (capi.Sim3Result * len(packs))()
+        out = {}
+        for i, p in enumerate(packs):
+            n = len(p["index"])
+            res[i] = _struct(capi.Sim3Result)
+            arrs = dict(outlier1=_out(n, np.uint8), outlier=_out(n, np.uint8), chi2_12=_out(n), chi2_21=_out(n))
+            res[i].outlier1, res[i].outlier = capi.ptr(arrs["outlier1"], capi.c_uint8_p), capi.ptr(arrs["outlier"], capi.c_uint8_p)
+            res[i].chi2_12, res[i].chi2_21 = capi.ptr(arrs["chi2_12"], capi.c_double_p), capi.ptr(arrs["chi2_21"], capi.c_double_p)
+            out.update({f"p{i}.{k}": v for k, v in arrs.items()})
+        _ok(lib, lib.osh_sim3_optimize(ctx, len(packs), probs, res), "osh_sim3_optimize")
+        for i in range(len(packs)):
+            out.update(_scalars(res[i], f"p{i}"))
+        return out
+
+    def written(out):
+        missing = []
+        for i in range(len(packs)):
+            for k in ("S12", "outlier1", "outlier", "chi2_12", "chi2_21", "n_bad", "n_in", "round2", "iterations", "status"):
+                _need_written(out, missing, f"p{i}.{k}")
+            _need_written(out, missing, f"p{i}.chi2_end", slice(0, 2 if out[f"p{i}.round2"][0] else 1))
+            assert out[f"p{i}.status"][0] == capi.OSH_OK
+        return missing
+    return Call("sim3", desc, run, written, reference)
+
+
+def _lin_out(n):
+    return dict(H=_out(n * n), b=_out(max(n, 1)), chi2=_out(1))
+
+
+def _lin_written(n):
+    def written(out):
+        missing = []
+        _need_written(out, missing, "H")
+        _need_written(out, missing, "b", slice(0, n))
+        _need_written(out, missing, "chi2")
+        return missing
+    return written
+
+
+def sim3_lin_call(desc, pk):
+    def run(lib, ctx):
+        keep = []
+        p = ss.problem(pk, keep)
+        out = _lin_out(7)
+        _ok(lib, lib.osh_sim3_linearize(ctx, C.byref(p), capi.ptr(out["H"], capi.c_double_p), capi.ptr(out["b"], capi.c_double_p),
+                                        capi.ptr(out["chi2"], capi.c_double_p)), "osh_sim3_linearize")
+        return out
+    return Call("sim3_lin", desc, run, _lin_written(7))
+
+
+PGO_SCALARS = ("iterations", "trials", "chi2_initial", "chi2_final", "envelope_entries", "envelope_tiles", "tall_columns", "status")
+
+
+def pgo_call(desc, g, iterations=20, dense=False, reference=None):
+    mode = capi.OSH_PGO_SOLVE_DENSE if dense else capi.OSH_PGO_SOLVE_ENVELOPE
+
+    def run(lib, ctx):
+        prob = g.as_struct(iterations, 1e-16, mode)
+        est = _out((len(g.estimate), 8))
+        res = _struct(capi.PgoResult)
+        res.estimate = capi.ptr(est, capi.c_double_p)
+        _ok(lib, lib.osh_pgo_solve(ctx, C.byref(prob), C.byref(res)), "osh_pgo_solve")
+        return dict(estimate=est, **_scalars(res, "r"))
+
+    def written(out):
+        missing = []
+        for k in ("estimate",) + tuple(f"r.{s}" for s in PGO_SCALARS):
+            _need_written(out, missing, k)
+        assert out["r.status"][0] == capi.OSH_OK
+        return missing
+    return Call("pgo", desc, run, written, reference)
+
+
+def pgo4_call(desc, g, iterations=20, dense=False, reference=None):
+    mode = capi.OSH_PGO_SOLVE_DENSE if dense else capi.OSH_PGO_SOLVE_ENVELOPE
+
+    def run(lib, ctx):
+        prob = g.as_struct(iterations, 0.0, mode)
+        n = len(g.fixed)
+        arrs = dict(Rcw=_out((n, 9)), tcw=_out((n, 3)), Rwb=_out((n, 9)), twb=_out((n, 3)))
+        res = _struct(capi.Pgo4Result)
+        for k, v in arrs.items():
+            setattr(res, k, capi.ptr(v, capi.c_double_p))
+        _ok(lib, lib.osh_pgo4_solve(ctx, C.byref(prob), C.byref(res)), "osh_pgo4_solve")
+        return dict(**arrs, **_scalars(res, "r"))
+
+    def written(out):
+        missing = []
+        for k in ("Rcw", "tcw", "Rwb", "twb") + tuple(f"r.{s}" for s in PGO_SCALARS + ("lambda_init_used",)):
+            _need_written(out, missing, k)
+        assert out["r.status"][0] == capi.OSH_OK
+        return missing
+    return Call("pgo4", desc, run, written, reference)
+
+
+def pgo_lin_call(desc, g, four=False):
+    d = 4 if four else 7
+    n = d * int(np.count_nonzero(~np.asarray(g.fixed, dtype=bool)))
+
+    def run(lib, ctx):
+        prob = g.as_struct()
+        out = _lin_out(n)
+        fn = lib.osh_pgo4_linearize if four else lib.osh_pgo_linearize
+        _ok(lib, fn(ctx, C.byref(prob), capi.ptr(out["H"], capi.c_double_p), capi.ptr(out["b"], capi.c_double_p),
+                    capi.ptr(out["chi2"], capi.c_double_p)), "osh_pgo_linearize")
+        return out
+    return Call("pgo4_lin" if four else "pgo_lin", desc, run, _lin_written(n))
+
+
+# ---------------------------------------------------------------------------------------------------------------- comparison
+def _first_difference(a, b):
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return f"shape / type {a.shape} {a.dtype} vs {b.shape} {b.dtype}"
+    ne = (_bits(a) != _bits(b)).reshape(-1)
+    i = int(np.argmax(ne))
+    fa, fb = a.reshape(-1).astype(np.float64), b.reshape(-1).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        d = np.abs(fa[ne] - fb[ne])
+    big = float(np.nanmax(d)) if np.isfinite(d).any() else float("nan")
+    return f"{int(ne.sum())} of {ne.size} entries differ, first at index {i} ({fa[i]!r} vs {fb[i]!r}), largest difference {big:.3g}"
+
+
+def compare(step, call, got, ref):
+    for key in sorted(set(got) | set(ref)):
+        if key not in got or key not in ref:
+            pytest.fail(f"step {step} ({call.kind}: {call.desc}): field {key} only on one side")
+        a, b = got[key], ref[key]
+        if a.tobytes() != b.tobytes():
+            pytest.fail(f"step {step} ({call.kind}: {call.desc}): {key} differs from a fresh context: {_first_difference(a, b)}")
+
+
+def fresh_run(lib, call):
+    ctx = C.c_void_p()
+    capi.check(lib.osh_lba_create(0, C.byref(ctx)), "osh_lba_create", lib)
+    try:
+        return call.run(lib, ctx)
+    finally:
+        lib.osh_lba_destroy(ctx)
+
+
+@pytest.fixture(scope="module")
+def zero_new_buffers():
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("OSH_ZERO_NEW_BUFFERS", "1")
+        yield
+
+
+@pytest.fixture(scope="module")
+def live(hip_lib, zero_new_buffers):
+    """The long-lived context every part of the script runs on, in file order (a part run alone gets a context of its own)."""
+    ctx = C.c_void_p()
+    capi.check(hip_lib.osh_lba_create(0, C.byref(ctx)), "osh_lba_create", hip_lib)
+    state = dict(ctx=ctx, step=0)
+    yield state
+    hip_lib.osh_lba_destroy(ctx)
+
+
+def run_script(lib, live, calls):
+    for call in calls:
+        step = live["step"]
+        live["step"] += 1
+        got = call.run(lib, live["ctx"])
+        missing = call.written(got)
+        assert not missing, f"step {step} ({call.kind}: {call.desc}): " + "; ".join(missing)
+        ref = fresh_run(lib, call)
+        compare(step, call, got, ref)
+        if call.reference is not None:
+            call.reference(got)
+
+
+# ------------------------------------------------------------------------------------------------------------------ references
+def _lba_golden(name):
+    from helpers import load_lba_fixture
+    w, z = load_lba_fixture(name)
+
+    def check(out):
+        n = int(out["w0.n_trace"][0])
+        assert int(out["w0.iterations"][0]) == int(z["exp_iterations"])
+        np.testing.assert_array_equal(out["w0.trials_trace"][:n], z["exp_trials_trace"])
+        T = z["exp_T"]
+        q = out["w0.pose_qt"]
+        t_rel = np.max(np.linalg.norm(q[:, 4:] - T[:, :3, 3], axis=1) / np.linalg.norm(T[:, :3, 3], axis=1))
+        assert t_rel < 1e-6
+        for i in range(w.n_free):
+            np.testing.assert_allclose(synth.quat_to_R(q[i, :4] / np.linalg.norm(q[i, :4])), T[i, :3, :3], atol=1e-6)
+    return w, check
+
+
+def _liba_golden(name):
+    from helpers import check_against_liba_fixture, load_liba_fixture
+    w, z = load_liba_fixture(name)
+
+    def check(out):
+        n, N = int(out["w0.n_trace"][0]), w.n_opt
+        got = dict(iterations=int(out["w0.iterations"][0]), trials_trace=out["w0.trials_trace"][:n], chi2_initial=float(out["w0.chi2_initial"][0]),
+                   chi2_trace=out["w0.chi2_trace"][:n], lambda_trace=out["w0.lambda_trace"][:n], points=out["w0.points"],
+                   pose_Rcw=out["w0.pose_Rcw"].reshape(N, 3, 3), pose_Rwb=out["w0.pose_Rwb"].reshape(N, 3, 3), pose_twb=out["w0.pose_twb"],
+                   vel=out["w0.vel"], bias_g=out["w0.bias_g"], bias_a=out["w0.bias_a"])
+        check_against_liba_fixture(_ns(got), z, fisheye=w.kb8 is not None)
+    return w, check
+
+
+def _pose_golden(name):
+    from helpers import check_against_pose_fixture, load_pose_fixture
+    f, z = load_pose_fixture(name)
+
+    def check(out):
+        got = dict(pose_qt=out["f0.pose_qt"], outlier=out["f0.outlier"], n_bad=int(out["f0.n_bad"][0]), rounds=int(out["f0.rounds"][0]),
+                   chi2_final=out["f0.chi2_final"], edge_chi2=out["f0.edge_chi2"])
+        check_against_pose_fixture(_ns(got), z)
+    return f, check
+
+
+def _posei_golden(name):
+    from helpers import load_posei_fixture
+    from test_oracle_posei import check_against_posei_fixture
+    f, z = load_posei_fixture(name)
+
+    def check(out):
+        n = 30 if f.mode == 1 else 15
+        got = {k: out[f"f0.{k}"].reshape(3, 3) if k in ("Rcw", "Rwb") else out[f"f0.{k}"] for k in ("Rcw", "tcw", "Rwb", "twb", "vel", "bias_g", "bias_a")}
+        got.update(outlier=out["f0.outlier"], edge_chi2=out["f0.edge_chi2"], n_bad=int(out["f0.n_bad"][0]), n_inliers=int(out["f0.n_inliers"][0]),
+                   rounds=int(out["f0.rounds"][0]), H=out["f0.H"][:n * n].reshape(n, n))
+        fish = f.kb8 is not None
+        check_against_posei_fixture(_ns(got), z, f, state_tol=2e-6 if fish else 1e-7, chi_tol=2e-3 if fish else 2e-5)
+    return f, check
+
+
+def _sim3_early_reference(pk):
+    import sim3opt_numpy as sn
+
+    def check(out):
+        ref = sn.run(pk)
+        assert not ref.round2 and out["p0.round2"][0] == 0 and out["p0.n_in"][0] == 0 and out["p0.iterations"][1] == 0
+        np.testing.assert_array_equal(out["p0.S12"], pk["S12"])
+        np.testing.assert_array_equal(out["p0.outlier1"], ref.outlier1)
+        np.testing.assert_array_equal(out["p0.outlier"], out["p0.outlier1"])
+    return check
+
+
+def _pgo4_reference(g):
+    import pgo4_numpy as p4
+
+    def check(out):
+        ref = p4.optimize(g)
+        assert (int(out["r.iterations"][0]), int(out["r.trials"][0])) == (ref.iterations, ref.trials)
+        assert np.isclose(out["r.chi2_initial"][0], ref.chi2_initial, rtol=1e-12)
+        assert np.isclose(out["r.chi2_final"][0], ref.chi2_final, rtol=1e-6)
+        assert np.abs(out["Rcw"].reshape(-1, 3, 3) - ref.state["Rcw"]).max() <= 1.2e-5
+        assert np.abs(out["tcw"] - ref.state["tcw"]).max() <= 7e-6 * np.abs(ref.state["tcw"]).max()
+    return check
+
+
+def _pgo_unchanged(g, no_edges=False):
+    """test_gpu_pgo_stages.py: a graph without free vertices or without edges comes back unchanged (and without edges at chi2 0)."""
+    def check(out):
+        assert out["estimate"].tobytes() == np.ascontiguousarray(g.estimate, dtype=np.float64).tobytes()
+        if no_edges:
+            assert out["r.chi2_final"][0] == 0.0
+    return check
+
+
+def _pgo_single_free_reference(g):
+    import pgo_numpy as pn
+
+    def check(out):
+        ref = pn.optimize(pn.PgoGraph(g.estimate, g.fixed, g.fix_scale, g.edge_ij, g.measurement))
+        # test_gpu_pgo.py's bounds: the stop rule may fall one iteration apart, the minimum to 1e-3 of chi2 and 1e-4 of the state
+        assert abs(int(out["r.iterations"][0]) - ref.iterations) <= 1
+        np.testing.assert_allclose(out["r.chi2_final"][0], ref.chi2_final, rtol=1e-3, atol=1e-12)
+        np.testing.assert_allclose(out["estimate"], ref.estimate, rtol=0, atol=1e-4)
+        np.testing.assert_array_equal(out["estimate"][g.fixed], g.estimate[g.fixed])
+    return check
+
+
+def _ns(d):
+    import types
+    return types.SimpleNamespace(**d)
+
+
+# -------------------------------------------------------------------------------------------------------------------- inputs
+_CACHE = {}
+
+
+def _cached(key, make):
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+def _lba_pool():
+    return _cached("lba_pool", lambda: [synth.make_window(3000 + k, n_free=[3, 8, 20][k % 3], n_fixed=1 + k % 4, n_points=[400, 1500, 3000][k % 3],
+                                                          stereo=k % 2 == 0, track_len=(3, 10), max_iterations=4) for k in range(8)])
+
+
+def _with_stop(w, raised):
+    return dataclasses.replace(w, stop_flag=np.array([1 if raised else 0], dtype=np.uint8))
+
+
+def lba_script():
+    pool = _lba_pool()
+    big_map = _cached("lba_map", lambda: synth.make_window(77, n_free=300, n_fixed=2, n_points=8000, stereo=True, track_len=(3, 20), max_iterations=3))
+    fish = synth.make_window(503, n_free=8, n_fixed=3, n_points=700, stereo=False, fisheye=True, track_len=(3, 8), max_iterations=5)
+    rig = synth.make_rig_window(504, n_free=7, n_fixed=3, n_points=500, track_len=(3, 8), max_iterations=5)
+    small = synth.make_window(7, n_free=5, n_fixed=2, n_points=300, stereo=True, max_iterations=5)
+    mono = synth.make_window(8, n_free=6, n_fixed=2, n_points=500, stereo=False, max_iterations=5)
+    tiny, tiny_check = _lba_golden("lba_tiny_stereo")
+    return [
+        lba_call("200-window batch (batch solve threads, device packer)", [pool[k % 8] for k in range(200)]),
+        lba_call("1 window after the batch (latency solve, host packer)", [pool[1]]),
+        lba_call("300-keyframe map (global-memory factorisation)", [big_map]),
+        lba_call("5-keyframe window after the map", [small]),
+        lba_call("4 windows, device packer forced", [pool[k] for k in range(4)], pack_mode=0),
+        lba_call("4 windows, host packer forced", [pool[k + 2] for k in range(4)], pack_mode=1),
+        lba_call("4 windows, device packer again", [pool[k + 1] for k in range(4)], pack_mode=0),
+        lba_call("KannalaBrandt8 + rig batch", [fish, rig, fish]),
+        lba_call("pinhole batch after the fisheye one", [pool[0], small]),
+        lba_call("stereo window", [pool[0]]),
+        lba_call("mono window after stereo", [mono]),
+        lba_call("a window with a raised stop flag", [_with_stop(pool[1], True), pool[2]]),
+        lba_call("the same windows without stop flags", [pool[1], pool[2]]),
+        lba_call("golden lba_tiny_stereo (small, last)", [tiny], reference=tiny_check),
+    ]
+
+
+def _liba_pool():
+    return _cached("liba_pool", lambda: [si.make_inertial_window(11 + k, n_opt=[4, 10, 14][k % 3], n_points=[600, 1500, 2400][k % 3]) for k in range(6)])
+
+
+def _map(seed, n_opt, its, n_points):
+    w = si.make_inertial_window(seed, n_opt=n_opt, n_fixed=0, n_points=n_points, large=True)
+    return dataclasses.replace(w, lambda_init=1e-5, max_iterations=its, link_robust=np.ones_like(w.link_robust))
+
+
+def liba_script():
+    pool = _liba_pool()
+    dense = _cached("liba_dense", lambda: _map(905, 100, 3, 4000))
+    banded = _cached("liba_banded", lambda: _map(906, 150, 3, 6000))
+    full = si.make_inertial_window(81, n_opt=14, n_fixed=4, n_points=900)
+    fish = si.make_inertial_window(83, n_opt=6, n_fixed=4, n_points=600, fisheye=True)
+    tiny, tiny_check = _liba_golden("liba_tiny")
+    return [
+        liba_call("130 windows (one block per window)", [pool[k % 6] for k in range(130)]),
+        liba_call("1 window after the batch (block group)", [pool[1]]),
+        liba_call("dense map, 100 keyframes", [dense]),
+        liba_call("banded map, 150 keyframes", [banded]),
+        liba_call("single window after the maps", [pool[2]]),
+        liba_call("FullInertialBA shape with bInit priors (shared bias)", [si.with_shared_bias(full)]),
+        liba_call("FullInertialBA shape without priors", [full]),
+        liba_call("fisheye window", [fish]),
+        liba_call("golden liba_tiny (pinhole, small, last)", [tiny], reference=tiny_check),
+    ]
+
+
+def pose_script():
+    frames = _cached("pose_frames", lambda: [synth.make_pose_frame(60 + k, n_points=[300, 900, 1500][k % 3], stereo=k % 4 != 1, mixed_mono_frac=0.3)
+                                             for k in range(6)])
+    fish = synth.make_pose_frame(52, n_points=700, stereo=False, outlier_frac=0.15, fisheye=True)
+    rig = synth.make_pose_frame(53, n_points=600, rig=True)
+    mono = synth.make_pose_frame(54, n_points=400, stereo=False)
+    tiny, tiny_check = _pose_golden("pose_tiny")
+    itiny, itiny_check = _posei_golden("posei_tiny_frame")
+    pk = posei_script_inputs()
+    return [
+        pose_call("batch of 48 frames", [frames[k % 6] for k in range(48)]),
+        pose_call("one tiny frame after the batch", [synth.make_pose_frame(61, n_points=12, stereo=True, outlier_frac=0.0)]),
+        pose_call("mono / stereo / fisheye / rig interleaved", [mono, frames[1], fish, rig, frames[0]]),
+        posei_call("LastFrame batch (mode 1), 24 frames", pk["batch1"]),
+        posei_call("LastKeyFrame frames (mode 0), rec_init", pk["mode0"]),
+        posei_call("mono / stereo / fisheye / rig frames interleaved", pk["mixed"]),
+        posei_call("a large frame", [pk["large"]]),
+        posei_call("fewer than 30 inliers (recovery) after the large frame", [pk["recovery"]]),
+        pose_call("golden pose_tiny (small, last)", [tiny], reference=tiny_check),
+        posei_call("golden posei_tiny_frame (small, last)", [itiny], reference=itiny_check),
+    ]
+
+
+def posei_script_inputs():
+    def make():
+        mk = si.make_posei_frame
+        return dict(
+            batch1=[mk(30 + k % 6, mode=1, n_points=[200, 500, 900][k % 3]) for k in range(24)],
+            mode0=[mk(40, mode=0, n_points=400), mk(41, mode=0, n_points=300, rec_init=True)],
+            mixed=[mk(42, mode=0, n_points=300, stereo=False), mk(43, mode=1, n_points=300), mk(44, mode=0, n_points=300, fisheye=True),
+                   mk(45, mode=1, n_points=300, rig=True)],
+            large=mk(46, mode=1, n_points=2500),
+            recovery=mk(47, mode=0, n_points=40, outlier_frac=0.5))
+    return _cached("posei", make)
+
+
+def _pgo_graph(n, mono=True, seed=11):
+    return _cached(("pgo", n, mono, seed), lambda: sp.pack_loop(sp.make_map(n, seed=seed, mono=mono, earlier_loop=True))[0])
+
+
+def _pgo4_graph(n, seed=7):
+    return _cached(("pgo4", n, seed), lambda: sp.pack_loop4(sp.make_inertial_loop(n, seed=seed, earlier_loop=n >= 300, rp_noise=0.001))[0])
+
+
+def _dev(g):
+    from orb_slam3_study_kr_amd.pgo import PgoGraph
+    return PgoGraph(np.asarray(g.estimate, np.float64), np.asarray(g.fixed, bool), np.asarray(g.fix_scale, bool),
+                    np.asarray(g.edge_ij, np.int32).reshape(-1, 2), np.asarray(g.measurement, np.float64).reshape(-1, 8))
+
+
+def pgo_script():
+    import pgo_cases as pc
+    chain = lambda n: [(i, i + 1) for i in range(n - 1)]   # noqa: E731
+    g1000 = _pgo_graph(1000)
+    g4 = _pgo4_graph(300)
+    g_small = _pgo_graph(50, mono=False)
+    g4_small = _pgo4_graph(50)
+    all_fixed = _dev(pc.make_graph(5, chain(5), fixed=(0, 1, 2, 3, 4), seed=30))
+    no_edges = _dev(pc.make_graph(5, [], fixed=(0,), seed=31))
+    one_free = _dev(pc.make_graph(3, chain(3), fixed=(0, 2), seed=32))
+    return [
+        pgo_call("Sim3 graph, 1000 vertices", g1000),
+        pgo4_call("4-DoF graph, 300 vertices, after the Sim3 graph", g4),
+        pgo_lin_call("Sim3 linearize, 50 vertices", g_small),
+        pgo_lin_call("4-DoF linearize4, 50 vertices", g4_small, four=True),
+        pgo_call("Sim3 dense mode, 300 vertices", _pgo_graph(300), iterations=2, dense=True),
+        pgo4_call("4-DoF dense mode, 50 vertices", g4_small, iterations=2, dense=True),
+        pgo_call("Sim3 graph without free vertices (nf = 0)", all_fixed, iterations=5, reference=_pgo_unchanged(all_fixed)),
+        pgo_call("Sim3 graph without edges (E = 0)", no_edges, iterations=5, reference=_pgo_unchanged(no_edges, no_edges=True)),
+        pgo_call("Sim3 graph with a single free vertex", one_free, iterations=5, reference=_pgo_single_free_reference(one_free)),
+        pgo4_call("small 4-DoF graph (50 vertices, last)", g4_small, reference=_pgo4_reference(g4_small)),
+    ]
+
+
+def sim3_script():
+    def make():
+        packs = [ss.pack(ss.make_case(300 + k, [30, 300, 800, 12][k % 4], [0.0, 0.2, 0.4, 0.6][k % 4], n_no_i2=k % 3, fix_scale=k % 2 == 1,
+                                      kb8=k % 5 == 0)) for k in range(16)]
+        return dict(batch=packs, round2=ss.pack(ss.make_case(2, 300, 0.2)), early=ss.pack(ss.make_case(77, 14, 0.6)),
+                    kb8=ss.pack(ss.make_case(41, 300, 0.2, n_no_i2=3, kb8=True)), pin=ss.pack(ss.make_case(42, 60, 0.1)),
+                    early_last=ss.pack(ss.make_case(78, 14, 0.6)))
+    s = _cached("sim3", make)
+    return [
+        sim3_call("16-problem batch", s["batch"]),
+        sim3_call("1 problem after the batch", [s["batch"][3]]),
+        sim3_call("a round-2 case", [s["round2"]]),
+        sim3_call("an early return after round 2", [s["early"]]),
+        sim3_lin_call("linearize_sim3 between the solves", s["round2"]),
+        sim3_call("KannalaBrandt8", [s["kb8"]]),
+        sim3_lin_call("linearize_sim3 of the fisheye case", s["kb8"]),
+        sim3_call("pinhole after KannalaBrandt8", [s["pin"]]),
+        sim3_call("early return (small, last)", [s["early_last"]], reference=_sim3_early_reference(s["early_last"])),
+    ]
+
+
+def across_script():
+    """Every slot again after the others have run (the pose graph after a global BA, local BA after FullInertialBA, ...)."""
+    gba = _cached("lba_map", None)
+    tiny, tiny_check = _lba_golden("lba_tiny_mono")
+    ltiny, ltiny_check = _liba_golden("liba_tiny")
+    ptiny, ptiny_check = _pose_golden("pose_tiny_mono")
+    g4_small = _pgo4_graph(50)
+    return [
+        lba_call("global BA map", [gba]),
+        pgo_call("Sim3 graph after the global BA", _pgo_graph(300)),
+        liba_call("FullInertialBA-shaped map", [_cached("liba_banded", None)]),
+        lba_call("local BA after FullInertialBA", [_lba_pool()[4]]),
+        sim3_call("OptimizeSim3 after local BA", [sim3_script_inputs()["round2"]]),
+        pose_call("PoseOptimization after OptimizeSim3", [ptiny]),
+        pgo4_call("4-DoF graph after the pose solvers", _pgo4_graph(300)),
+        posei_call("pose-inertial after the 4-DoF graph", [posei_script_inputs()["large"]]),
+        liba_call("LocalInertialBA after pose-inertial", [ltiny], reference=ltiny_check),
+        lba_call("local BA (small, last)", [tiny], reference=tiny_check),
+        pose_call("PoseOptimization (small, last)", [ptiny], reference=ptiny_check),
+        pgo4_call("4-DoF graph (small, last)", g4_small, reference=_pgo4_reference(g4_small)),
+    ]
+
+
+def sim3_script_inputs():
+    sim3_script()
+    return _CACHE["sim3"]
+
+
+PARTS = dict(lba=lba_script, inertial=liba_script, pose=pose_script, pgo=pgo_script, sim3=sim3_script, across=across_script)
+
+
+@pytest.mark.parametrize("part", list(PARTS))
+def test_one_context_equals_fresh_contexts(hip_lib, live, part):
+    """The script in ONE context, part after part (file order; `across` needs the earlier parts' inputs): every step bit for bit equal
+    to the same call in a fresh context, every documented output written, the last small step of each solver against its reference."""
+    if part == "across" and "lba_map" not in _CACHE:
+        lba_script(), liba_script()
+    run_script(hip_lib, live, PARTS[part]())
+
+
+# ------------------------------------------------------------------------------------------------------------------- ORB matcher
+def _orb_steps():
+    from test_gpu_orb import _frustum_scene
+    rng = np.random.Generator(np.random.PCG64(5))
+
+    def grid(nq, nt, seed, skip=True):
+        r = np.random.Generator(np.random.PCG64(seed))
+        xy = np.stack([r.uniform(0, synth.IMG_W, nt), r.uniform(0, synth.IMG_H, nt)], axis=1).astype(np.float32)
+        level = r.integers(0, synth.N_LEVELS, nt).astype(np.int32)
+        tdesc = r.integers(0, 256, (nt, 32), dtype=np.uint8)
+        src = r.integers(0, nt, nq)
+        qdesc = tdesc[src] ^ np.packbits(r.uniform(0, 1, (nq, 256)) < 0.05, axis=1)
+        win = np.stack([xy[src, 0] + r.normal(0, 3, nq), xy[src, 1] + r.normal(0, 3, nq), r.choice([0.0, 8.0, 20.0, 60.0], nq)], axis=1).astype(np.float32)
+        lev = np.stack([level[src] - 1, level[src] + 1], axis=1).astype(np.int32)
+        return dict(query_desc=qdesc, train_desc=tdesc, train_level=level, train_xy=xy, query_window=win, query_levels=lev,
+                    train_skip=(r.uniform(0, 1, nt) < 0.1).astype(np.uint8) if skip else None)
+
+    big_pairs = [synth.make_orb_pair(90 + k, 1500, 1800, windowed=True, same_level=False) for k in range(4)]
+    small_pairs = [synth.make_orb_pair(95, 60, 80, windowed=True, same_level=False)]
+    a_big, b_big = rng.integers(0, 256, (700, 32), dtype=np.uint8), rng.integers(0, 256, (900, 32), dtype=np.uint8)
+    a_small, b_small = rng.integers(0, 256, (5, 32), dtype=np.uint8), rng.integers(0, 256, (7, 32), dtype=np.uint8)
+    g_big, g_small = grid(2500, 3000, 1), grid(40, 60, 2, skip=False)
+    occ_big = (np.random.default_rng(3).uniform(0, 1, 3000) < 0.2).astype(np.uint8)
+    fr_big, fr_small = _frustum_scene(11, 5000), _frustum_scene(12, 9)
+
+    def search(pairs, windowed):
+        return lambda m: m.search(pairs, windowed=windowed)
+
+    def local(g, occupied):
+        def run(m):
+            m.upload_grid(**g)
+            m.match()
+            d = m.download()
+            n, assign, slot, rounds = m.match_local_points(occupied=occupied)
+            return dict(**d, n=n, assign=assign, slot=slot, rounds=np.array([rounds]))
+        return run
+
+    def dists(pairs):
+        def run(m):
+            m.upload(pairs, windowed=True)
+            return dict(dist=m.list_distances())
+        return run
+
+    def frustum(sc):
+        frame, P, normal, mn, mx = sc
+        return lambda m: m.frustum(frame, P, normal, mn, mx)
+
+    return [
+        ("search, windowed, 4 large pairs", search(big_pairs, True)),
+        ("search, brute force, 4 large pairs", search(big_pairs, False)),
+        ("grid + match_local_points with occupied, large", local(g_big, occ_big)),
+        ("list_distances, large", dists(big_pairs)),
+        ("frustum, 5000 points", frustum(fr_big)),
+        ("distance_matrix 700 x 900", lambda m: dict(d=m.distance_matrix(a_big, b_big))),
+        ("grid + match_local_points without occupied, small", local(g_small, None)),
+        ("search, windowed, small pair", search(small_pairs, True)),
+        ("search, brute force, small pair", search(small_pairs, False)),
+        ("list_distances, small", dists(small_pairs)),
+        ("frustum, 9 points", frustum(fr_small)),
+        ("distance_matrix 5 x 7", lambda m: dict(d=m.distance_matrix(a_small, b_small))),
+        ("grid + match_local_points with occupied, large again", local(g_big, occ_big)),
+    ]
+
+
+def test_orb_matcher_context_equals_fresh_matchers(hip_lib, zero_new_buffers):
+    """One OrbMatcher across plain and windowed searches, device-built candidates with and without occupancy, frustum tests, list
+    distances and distance matrices, large then small: each result bit for bit what a fresh matcher returns."""
+    steps = _orb_steps()
+    with orb.OrbMatcher(0) as m:
+        for i, (desc, run) in enumerate(steps):
+            got = run(m)
+            with orb.OrbMatcher(0) as fresh:
+                ref = run(fresh)
+            call = Call("orb", desc, None, None)
+            compare(i, call, {k: np.asarray(v) for k, v in got.items()}, {k: np.asarray(v) for k, v in ref.items()})
+
+
+# ---------------------------------------------------------------------------------------------------- reference signatures
+def _lba_state(g, w):
+    return dict(kf=np.stack([g.kf_pose(k) for k in range(w.n_free + w.n_fixed)]), mp=np.stack([g.mp_pos(j) for j in range(w.n_points)]))
+
+
+def _inertial_state(g):
+    n = len(g.kf_id)
+    return dict(kf=np.stack([g.kf_pose(k) for k in range(n)]), vel=np.stack([g.kf_velocity(k) for k in range(n)]),
+                bias=np.stack([g.kf_bias(k) for k in range(n)]), mp=np.stack([g.mp_pos(j) for j in range(len(g.mp_id))]))
+
+
+def _host_local_ba():
+    w = synth.make_window(502, n_free=24, n_fixed=5, n_points=3000, stereo=True)
+    with host.HostGraph(w) as g:
+        g.run_lba()
+        return _lba_state(g, w)
+
+
+def _host_local_inertial_ba():
+    w = si.make_inertial_window(51, n_opt=10, n_fixed=8, n_points=1200)
+    with host.HostInertialGraph(w) as g:
+        rc = g.run()
+        return dict(ret=np.array([rc]), **_inertial_state(g))
+
+
+def _host_pose_optimization():
+    f = synth.make_pose_frame(51, n_points=900, mixed_mono_frac=0.4, outlier_frac=0.15)
+    E = f.n_edges
+    xy = f.edge_obs[:, :2].astype(np.float32)
+    uright = np.where(f.edge_kind == 1, f.edge_obs[:, 2], -1.0).astype(np.float32)
+    octave = np.round(np.log(1.0 / f.edge_info) / np.log(1.44)).astype(np.int32)
+    frame = host.HostFrame(xy, octave, np.zeros((E, 32), np.uint8), uright=uright, pose_qt=f.pose_qt)
+    try:
+        n, pose, outlier = frame.pose_optimization(np.arange(E, dtype=np.int32), f.points)
+    finally:
+        frame.close()
+    return dict(ret=np.array([n]), pose=pose, outlier=outlier)
+
+
+def _host_pose_inertial_last_frame():
+    with host.HostPoseiFrame(si.make_posei_frame(33, mode=1, n_points=500)) as h:
+        r = h.run()
+    return {k: np.asarray(v) for k, v in r.items()}
+
+
+def _host_optimize_sim3():
+    case = ss.make_case(501, 400, 0.2, n_no_i2=6, n_bad=6, n_null_mp1=4, n_neg_depth=4)
+    lib = capi.load_host_library()
+    inp = ss.host_input(case)
+    nulled = np.zeros(len(case.matches1), np.uint8)
+    S = np.zeros(8)
+    H = np.full(49, 7.0)
+    ret = lib.osh_host_optimize_sim3(C.byref(inp), capi.ptr(nulled, capi.c_uint8_p), capi.ptr(S, capi.c_double_p), capi.ptr(H, capi.c_double_p))
+    return dict(ret=np.array([ret]), nulled=nulled, S=S, H=H)
+
+
+def _host_essential_graph():
+    with sp.HostPgoMap(sp.make_map(120, seed=21, mono=True, earlier_loop=True, n_points=300)) as h:
+        rc = h.run()
+        return dict(ret=np.array([rc]), kf=h.kf_poses(), mp=h.mp_positions())
+
+
+def _host_essential_graph_4dof():
+    with sp.HostPgo4Map(sp.make_inertial_loop(300, seed=4, earlier_loop=True, rp_noise=0.001, n_points=500)) as h:
+        rc = h.run4()
+        return dict(ret=np.array([rc]), kf=h.kf_poses(), mp=h.mp_positions())
+
+
+def _host_global_ba():
+    w = synth.make_window(46, n_free=80, n_fixed=1, n_points=4000, stereo=True, track_len=(3, 10))
+    with host.HostGraph(w, init_kf_id_index=w.n_free) as g:
+        g.run_gba(5, 0)
+        return _lba_state(g, w)
+
+
+def _host_full_inertial_ba():
+    w = si.make_inertial_window(81, n_opt=14, n_fixed=4, n_points=900)
+    with host.HostInertialGraph(w) as g:
+        rc = g.run_full(7, 0, init=True)
+        return dict(ret=np.array([rc]), **_inertial_state(g))
+
+
+def _host_search_by_projection():
+    rng = np.random.Generator(np.random.PCG64(3))
+    n_kp, n_mp = 800, 500
+    xy = np.stack([rng.uniform(5, synth.IMG_W - 5, n_kp), rng.uniform(5, synth.IMG_H - 5, n_kp)], axis=1).astype(np.float32)
+    octave = rng.integers(0, synth.N_LEVELS, n_kp).astype(np.int32)
+    desc = rng.integers(0, 256, (n_kp, 32), dtype=np.uint8)
+    src = rng.permutation(n_kp)[:n_mp]
+    mp_desc = desc[src] ^ np.packbits(rng.uniform(0, 1, (n_mp, 256)) < 0.06, axis=1)
+    proj = (xy[src] + rng.normal(0, 2.0, (n_mp, 2))).astype(np.float32)
+    level = np.clip(octave[src] + rng.integers(0, 2, n_mp), 0, synth.N_LEVELS - 1).astype(np.int32)
+    viewcos = rng.uniform(0.99, 1.0, n_mp).astype(np.float32)
+    f = host.HostFrame(xy, octave, desc)
+    try:
+        n, assign = f.search_local_points(mp_desc, proj, level, viewcos, nnratio=0.8, th=3.0)
+    finally:
+        f.close()
+    return dict(ret=np.array([n]), assign=assign)
+
+
+HOST_SEQUENCE = [
+    ("LocalBundleAdjustment", _host_local_ba),
+    ("LocalInertialBA", _host_local_inertial_ba),
+    ("PoseOptimization", _host_pose_optimization),
+    ("PoseInertialOptimizationLastFrame", _host_pose_inertial_last_frame),
+    ("OptimizeSim3", _host_optimize_sim3),
+    ("OptimizeEssentialGraph", _host_essential_graph),
+    ("OptimizeEssentialGraph4DoF", _host_essential_graph_4dof),
+    ("GlobalBundleAdjustemnt", _host_global_ba),
+    ("FullInertialBA", _host_full_inertial_ba),
+    ("SearchByProjection", _host_search_by_projection),
+    ("LocalBundleAdjustment again", _host_local_ba),
+]
+
+
+def _in_thread(fns):
+    out, err = [], []
+
+    def body():
+        try:
+            for fn in fns:
+                out.append(fn())
+        except BaseException as e:   # noqa: BLE001 -- re-raised by the caller's thread
+            err.append(e)
+    t = threading.Thread(target=body)
+    t.start()
+    t.join()
+    if err:
+        raise err[0]
+    return out
+
+
+def test_reference_signatures_in_one_thread_equal_fresh_threads(hip_lib, zero_new_buffers):
+    """The host layer's per-thread context: one thread makes the sequence of Optimizer / ORBmatcher calls a SLAM session makes, each
+    on a freshly built map; every call again in a new thread (a context of its own) on an identical map writes the same bits."""
+    capi.load_host_library()
+    session = _in_thread([fn for _, fn in HOST_SEQUENCE])
+    for step, ((name, fn), got) in enumerate(zip(HOST_SEQUENCE, session)):
+        ref = _in_thread([fn])[0]
+        compare(step, Call("host", name, None, None), {k: np.asarray(v) for k, v in got.items()}, {k: np.asarray(v) for k, v in ref.items()})
