@@ -9,6 +9,7 @@
 #include "G2oTypes.h"
 #include "ImuTypes.h"
 #include "MapPoint.h"
+#include "ORBextractor.h"
 #include "orbslam3_compat.h"
 #define FRAME_GRID_ROWS 48
 #define FRAME_GRID_COLS 64
@@ -28,6 +29,8 @@ class Frame {
   // as one device launch: it fills the same MapPoint fields and returns how many points are in view (-1 on a device error).
   bool isInFrustum(MapPoint* pMP, float viewingCosLimit);
   int isInFrustum(const std::vector<MapPoint*>& vpMPs, float viewingCosLimit, std::vector<bool>& vbInView);
+  // src/Frame.cc:816-986 on the device: fills mvuRight / mvDepth (all -1 with a message on stderr on a device error)
+  void ComputeStereoMatches();
 
   int N = 0;
   int Nleft = -1, Nright = -1;
@@ -38,11 +41,15 @@ class Frame {
   int mnPoseSets = 0;                            // test-double bookkeeping
   std::vector<cv::KeyPoint> mvKeys, mvKeysUn, mvKeysRight;
   std::vector<float> mvuRight;
+  std::vector<float> mvDepth;                     // include/Frame.h:235
   std::vector<MapPoint*> mvpMapPoints;
   std::vector<bool> mvbOutlier;
-  cv::Mat mDescriptors;
+  cv::Mat mDescriptors, mDescriptorsRight;        // include/Frame.h:242
   DBoW2::FeatureVector mFeatVec;   // include/Frame.h:262 (filled by ComputeBoW)
   std::vector<float> mvScaleFactors;
+  std::vector<float> mvInvScaleFactors;           // include/Frame.h:282
+  ORBextractor* mpORBextractorLeft = nullptr;     // include/Frame.h:196; only mvImagePyramid is read (ComputeStereoMatches)
+  ORBextractor* mpORBextractorRight = nullptr;
   int mnScaleLevels = 0;
   float mfLogScaleFactor = 0;   // log(mfScaleFactor), src/Frame.cc:75
   GeometricCamera* mpCamera = nullptr;

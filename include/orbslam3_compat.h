@@ -8,7 +8,7 @@
  * real ORB-SLAM3 tree define ORBSLAM3_HIP_USE_REAL_HEADERS and the genuine headers are used
  * instead; csrc/host/Optimizer.cc and ORBmatcher.cc only rely on the common subset
  * (operator(), x()/y()/z()/w(), cast<T>(), unit_quaternion(), translation(), pt/octave/angle,
- * ptr<T>(row), rows/cols).
+ * ptr<T>(row), rows/cols/step).
  */
 #ifndef ORBSLAM3_COMPAT_H
 #define ORBSLAM3_COMPAT_H
@@ -219,17 +219,22 @@ typedef std::map<unsigned int, double> BowVector;
 namespace cv {
 struct Point2f { float x = 0, y = 0; };
 struct KeyPoint { Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1; };
-// Row-major byte matrix (only CV_8U descriptor matrices N x 32 cross this boundary).
+// Row-major byte matrix (CV_8U only: descriptor matrices N x 32 and the pyramid levels of an ORBextractor cross this boundary).
+// `step` is the row stride in bytes as in cv::Mat; it equals cols unless the matrix is a view() into a larger one, which is how the
+// reference's pyramid levels are stored (views into a bordered image, src/ORBextractor.cc ComputePyramid).
 class Mat {
  public:
   int rows = 0, cols = 0;
+  size_t step = 0;
   Mat() {}
-  Mat(int r, int c) : rows(r), cols(c), buf_(new std::vector<uint8_t>((size_t)r * c, 0)), off_(0) {}
+  Mat(int r, int c) : rows(r), cols(c), step((size_t)c), buf_(new std::vector<uint8_t>((size_t)r * c, 0)), off_(0) {}
   bool empty() const { return rows == 0; }
-  template <class T> T* ptr(int r = 0) { return reinterpret_cast<T*>(buf_->data() + off_ + (size_t)r * cols); }
-  template <class T> const T* ptr(int r = 0) const { return reinterpret_cast<const T*>(buf_->data() + off_ + (size_t)r * cols); }
-  Mat row(int r) const { Mat m; m.rows = 1; m.cols = cols; m.buf_ = buf_; m.off_ = off_ + (size_t)r * cols; return m; }
-  Mat clone() const { Mat m(rows, cols); if (rows) std::memcpy(m.buf_->data(), buf_->data() + off_, (size_t)rows * cols); return m; }
+  template <class T> T* ptr(int r = 0) { return reinterpret_cast<T*>(buf_->data() + off_ + (size_t)r * step); }
+  template <class T> const T* ptr(int r = 0) const { return reinterpret_cast<const T*>(buf_->data() + off_ + (size_t)r * step); }
+  Mat row(int r) const { Mat m; m.rows = 1; m.cols = cols; m.step = step; m.buf_ = buf_; m.off_ = off_ + (size_t)r * step; return m; }
+  // rows [r0, r0 + nr) x columns [c0, c0 + nc) of this matrix, sharing its storage (cv::Mat::operator()(Rect))
+  Mat view(int r0, int c0, int nr, int nc) const { Mat m; m.rows = nr; m.cols = nc; m.step = step; m.buf_ = buf_; m.off_ = off_ + (size_t)r0 * step + c0; return m; }
+  Mat clone() const { Mat m(rows, cols); for (int r = 0; r < rows; ++r) std::memcpy(m.buf_->data() + (size_t)r * cols, buf_->data() + off_ + (size_t)r * step, (size_t)cols); return m; }
  private:
   std::shared_ptr<std::vector<uint8_t>> buf_;
   size_t off_ = 0;

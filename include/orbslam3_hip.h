@@ -659,6 +659,69 @@ int osh_orb_frustum(osh_orb_ctx* ctx, const osh_frustum_frame* frame, const osh_
 int osh_orb_distance_matrix(osh_orb_ctx* ctx, int32_t n, int32_t m,
                             const uint8_t* a, const uint8_t* b, int32_t* out);
 
+/* ------------------------------------------------- rectified stereo matching */
+/*
+ * Frame::ComputeStereoMatches (src/Frame.cc:816-986) for n_frames independent rectified stereo frames in one call: the row-band
+ * Hamming search, the 11x11 SAD sliding window on the pyramid level of the left keypoint, the parabola fit and the median cut, all on
+ * the device; the downloaded arrays are final.  Integer arithmetic and single IEEE float32 operations in the reference's order.
+ *
+ * Where the reference has undefined behaviour this call has a defined skip: a right keypoint is entered only into rows inside
+ * [0, left_pyramid[0].rows), a left keypoint whose (int)y is outside has no candidates, a keypoint whose left 11x11 patch or right
+ * 11x21 strip leaves its pyramid image is skipped (stage 3), and a frame without accepted keypoints has no median cut.
+ *
+ * Refused with OSH_ERR_INVALID before any device work: n_levels outside [1, OSH_STEREO_MAX_LEVELS], an octave outside
+ * [0, n_levels), a coordinate that is not finite or beyond +-OSH_STEREO_MAX_COORD, left_pyramid[0].rows <= 0, a level that a left
+ * keypoint's octave names whose image (either side) is NULL, empty or has stride < cols.  Levels no left keypoint names may be NULL;
+ * they are not uploaded.  n_right is limited to 2^22 - 1 (OSH_ERR_UNSUPPORTED beyond).
+ */
+#define OSH_STEREO_MAX_LEVELS 16
+#define OSH_STEREO_MAX_COORD  1.0e6f
+#define OSH_STEREO_NO_INC     (-128)  /* best_inc of a keypoint whose SAD search did not run */
+/* stage[i]: where left keypoint i stopped */
+#define OSH_STEREO_NO_CANDIDATE 0  /* row (int)y holds no right keypoint (:863), is outside the image, or x < 0 (:869): hamming = best_right = -1 */
+#define OSH_STEREO_HAMMING      1  /* best descriptor distance >= (TH_HIGH + TH_LOW) / 2 = 75 (:902); hamming = 100, best_right = -1 if none was below TH_HIGH */
+#define OSH_STEREO_RIGHT_GUARD  2  /* scaleduR0 < 0 or scaleduR0 + 11 >= cols of the right level (:923)                         */
+#define OSH_STEREO_PATCH        3  /* a patch would leave its image (undefined in the reference)                               */
+#define OSH_STEREO_BORDER_INC   4  /* the SAD minimum sits at incR = -5 or +5 (:940)                                           */
+#define OSH_STEREO_DELTA        5  /* deltaR outside [-1, 1] (:950; cannot happen for an interior first strict minimum)        */
+#define OSH_STEREO_DISPARITY    6  /* disparity < 0 or >= bf / b (:958)                                                         */
+#define OSH_STEREO_ACCEPTED     7  /* u_right = mvuRight, depth = mvDepth                                                       */
+#define OSH_STEREO_MEDIAN_CUT   8  /* accepted, then set back to -1 / -1 because its SAD >= 1.5f * 1.4f * median (:972-985)      */
+typedef struct osh_stereo_image {
+  const uint8_t* data;     /* first pixel of the level (CV_8U); NULL when no left keypoint has this octave                     */
+  int32_t rows, cols;
+  int64_t stride;          /* bytes from one row to the next (>= cols): the reference's levels are views into a bordered image */
+} osh_stereo_image;
+typedef struct osh_stereo_frame {
+  int32_t n_left, n_right;
+  const float* left_xy;            /* [n_left*2]   mvKeys[i].pt                                             */
+  const int32_t* left_octave;      /* [n_left]     mvKeys[i].octave                                         */
+  const uint8_t* left_desc;        /* [n_left*32]  mDescriptors                                             */
+  const float* right_xy;           /* [n_right*2]  mvKeysRight[i].pt                                        */
+  const int32_t* right_octave;     /* [n_right]                                                             */
+  const uint8_t* right_desc;       /* [n_right*32] mDescriptorsRight                                        */
+  int32_t n_levels;
+  const float* scale_factors;      /* [n_levels]   mvScaleFactors                                           */
+  const float* inv_scale_factors;  /* [n_levels]   mvInvScaleFactors                                        */
+  const osh_stereo_image* left_pyramid;    /* [n_levels] mpORBextractorLeft->mvImagePyramid                 */
+  const osh_stereo_image* right_pyramid;   /* [n_levels] mpORBextractorRight->mvImagePyramid                */
+  float bf, b;                     /* mbf, mb                                                               */
+} osh_stereo_frame;
+typedef struct osh_stereo_result {
+  float* u_right;          /* [n_left]    mvuRight (-1: no stereo match)                                                  */
+  float* depth;            /* [n_left]    mvDepth                                                                         */
+  /* stage outputs, each may be NULL */
+  int32_t* best_right;     /* [n_left]    bestIdxR, -1 if no candidate was below TH_HIGH                                  */
+  int32_t* hamming;        /* [n_left]    bestDist of the descriptor search                                               */
+  int32_t* sad;            /* [n_left*11] vDists for incR = -5 .. 5 (stage >= 4), else -1                                 */
+  int32_t* best_inc;       /* [n_left]    bestincR (stage >= 4), else OSH_STEREO_NO_INC                                   */
+  uint8_t* stage;          /* [n_left]    OSH_STEREO_*                                                                    */
+} osh_stereo_result;
+int osh_orb_stereo_match(osh_orb_ctx* ctx, int32_t n_frames, const osh_stereo_frame* frames, const osh_stereo_result* results);
+/* With osh_orb_set_profiling on, the last osh_orb_stereo_match is synchronised between its phases and their host-clock times (ms) are
+ * kept: ms[0] validation + staging (pyramid rows into pinned memory), ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
+int osh_orb_stereo_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -355,6 +355,35 @@ int osh_host_pack_sim3(const osh_host_sim3_input* in, int32_t max_pairs, struct 
  * the call (in->S12 when untouched); hessian[49] is mAcumHessian, read before and written after the call (row-major). */
 int osh_host_optimize_sim3(const osh_host_sim3_input* in, uint8_t* nulled, double* S12, double* hessian);
 
+/* ---- Frame::ComputeStereoMatches (src/Frame.cc:816-986; csrc/host/Frame.cc, csrc/hosttest/stereo.cc) ---- */
+/* A rectified stereo frame as flat arrays.  The pyramid levels of a side lie one after another in *_pixels, each contiguous
+ * (rows[l] * cols[l] bytes, row-major). */
+typedef struct osh_host_stereo_input {
+  int32_t n_left, n_right;
+  const float* left_xy; const int32_t* left_octave; const uint8_t* left_desc;      /* [n_left*2], [n_left], [n_left*32]    */
+  const float* right_xy; const int32_t* right_octave; const uint8_t* right_desc;   /* [n_right*2], [n_right], [n_right*32] */
+  int32_t n_levels;
+  const float* scale_factors; const float* inv_scale_factors;                      /* [n_levels] each                      */
+  const int32_t* left_rows; const int32_t* left_cols; const int32_t* right_rows; const int32_t* right_cols;   /* [n_levels] */
+  const uint8_t* left_pixels; const uint8_t* right_pixels;
+  float bf, b;
+} osh_host_stereo_input;
+/* The pack alone (PackStereoMatches of csrc/host/host_pack.h, no device) on a stand-in Frame whose pyramid levels are views into
+ * images with `border` pixels around them (row stride cols + 2 * border), then read back the way a consumer of osh_stereo_frame
+ * reads it: sizes = n_left, n_right, n_levels; scales[2*l] = scale, [2*l+1] = inverse scale; level_shape[(side*n_levels + l)*3] =
+ * rows, cols, stride; *_pixels = the levels gathered row by row through data + r * stride.  Every output may be NULL. */
+int osh_host_pack_stereo(const osh_host_stereo_input* in, int32_t border, int32_t sizes[3], float* left_xy, int32_t* left_octave,
+                         uint8_t* left_desc, float* right_xy, int32_t* right_octave, uint8_t* right_desc, float* scales,
+                         int64_t* level_shape, uint8_t* left_pixels, uint8_t* right_pixels, float bf_b[2]);
+/* Frame::ComputeStereoMatches itself on such a Frame: u_right = mvuRight, depth = mvDepth ([n_left] each). */
+int osh_host_compute_stereo_matches(const osh_host_stereo_input* in, int32_t border, float* u_right, float* depth);
+/* A plain single-thread C++ restatement of src/Frame.cc:816-986 with the outputs of osh_stereo_result (all but u_right / depth may be
+ * NULL); flags[i] bit 0: the disparity <= 0 branch (0.01) was taken, bit 1: the smallest SAD occurs at more than one increment;
+ * undefined[4] counts the inputs on which the reference's behaviour is undefined (defined skips here): row-table entries outside the
+ * image, left keypoints whose row is outside, patches that leave their image, 1 if no keypoint was accepted; *ms = its wall time. */
+int osh_host_stereo_restatement(const osh_host_stereo_input* in, float* u_right, float* depth, int32_t* best_right, int32_t* hamming,
+                                int32_t* sad, int32_t* best_inc, uint8_t* stage, uint8_t* flags, int32_t undefined[4], double* ms);
+
 #ifdef __cplusplus
 }
 #endif

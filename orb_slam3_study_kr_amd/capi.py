@@ -265,6 +265,38 @@ class FrustumResult(C.Structure):
                 ("depth", c_float_p), ("view_cos", c_float_p), ("level", c_int32_p)]
 
 
+class StereoImage(C.Structure):
+    """``osh_stereo_image`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("data", c_uint8_p), ("rows", C.c_int32), ("cols", C.c_int32), ("stride", C.c_int64)]
+
+
+class StereoFrame(C.Structure):
+    """``osh_stereo_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("n_left", C.c_int32), ("n_right", C.c_int32),
+        ("left_xy", c_float_p), ("left_octave", c_int32_p), ("left_desc", c_uint8_p),
+        ("right_xy", c_float_p), ("right_octave", c_int32_p), ("right_desc", c_uint8_p),
+        ("n_levels", C.c_int32), ("scale_factors", c_float_p), ("inv_scale_factors", c_float_p),
+        ("left_pyramid", C.POINTER(StereoImage)), ("right_pyramid", C.POINTER(StereoImage)),
+        ("bf", C.c_float), ("b", C.c_float),
+    ]
+
+
+class StereoResult(C.Structure):
+    """``osh_stereo_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("u_right", c_float_p), ("depth", c_float_p), ("best_right", c_int32_p), ("hamming", c_int32_p),
+                ("sad", c_int32_p), ("best_inc", c_int32_p), ("stage", c_uint8_p)]
+
+
+OSH_STEREO_MAX_LEVELS = 16
+OSH_STEREO_NO_INC = -128
+(OSH_STEREO_NO_CANDIDATE, OSH_STEREO_HAMMING, OSH_STEREO_RIGHT_GUARD, OSH_STEREO_PATCH, OSH_STEREO_BORDER_INC, OSH_STEREO_DELTA,
+ OSH_STEREO_DISPARITY, OSH_STEREO_ACCEPTED, OSH_STEREO_MEDIAN_CUT) = range(9)
+
+
 def ptr(a, typ):
     """Pointer of ctypes type `typ` to the data of numpy array `a` (None -> NULL)."""
     if a is None:
@@ -313,6 +345,8 @@ _SIGNATURES = {
     "osh_orb_list_distances": (C.c_int, [C.c_void_p, c_int32_p]),
     "osh_orb_get_resolve_profile": (C.c_int, [C.c_void_p, c_int64_p, c_double_p]),
     "osh_orb_distance_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, c_int32_p]),
+    "osh_orb_stereo_match": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(StereoFrame), C.POINTER(StereoResult)]),
+    "osh_orb_stereo_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_pgo_solve": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), C.POINTER(PgoResult)]),
     "osh_pgo_linearize": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), c_double_p, c_double_p, c_double_p]),
     "osh_pgo4_solve": (C.c_int, [C.c_void_p, C.POINTER(Pgo4Problem), C.POINTER(Pgo4Result)]),
@@ -325,6 +359,22 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 # include/orbslam3_hip_host.h (C wrappers of the C++ host layer)
 c_float_p = C.POINTER(C.c_float)
+
+
+class HostStereoInput(C.Structure):
+    """``osh_host_stereo_input`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [
+        ("n_left", C.c_int32), ("n_right", C.c_int32),
+        ("left_xy", c_float_p), ("left_octave", c_int32_p), ("left_desc", c_uint8_p),
+        ("right_xy", c_float_p), ("right_octave", c_int32_p), ("right_desc", c_uint8_p),
+        ("n_levels", C.c_int32), ("scale_factors", c_float_p), ("inv_scale_factors", c_float_p),
+        ("left_rows", c_int32_p), ("left_cols", c_int32_p), ("right_rows", c_int32_p), ("right_cols", c_int32_p),
+        ("left_pixels", c_uint8_p), ("right_pixels", c_uint8_p),
+        ("bf", C.c_float), ("b", C.c_float),
+    ]
+
+
 _HOST_SIGNATURES = {
     "osh_host_graph_create": (C.c_void_p, [C.c_int32, c_int64_p, c_float_p, c_float_p, c_float_p, C.c_int32, C.c_int32, c_int64_p,
                                            c_float_p, C.c_int32, c_int32_p, c_int32_p, c_float_p, c_int32_p, C.c_int64, C.c_int32]),
@@ -407,6 +457,11 @@ _HOST_SIGNATURES = {
     "osh_host_get_mp_pos_gba": (C.c_int64, [C.c_void_p, C.c_int32, c_float_p]),
     "osh_host_mp_normal_updates": (C.c_int, [C.c_void_p, C.c_int32]),
     "osh_host_set_bad": (None, [C.c_void_p, C.c_int32, C.c_int32]),
+    "osh_host_pack_stereo": (C.c_int, [C.POINTER(HostStereoInput), C.c_int32, c_int32_p, c_float_p, c_int32_p, c_uint8_p, c_float_p, c_int32_p,
+                                       c_uint8_p, c_float_p, c_int64_p, c_uint8_p, c_uint8_p, c_float_p]),
+    "osh_host_compute_stereo_matches": (C.c_int, [C.POINTER(HostStereoInput), C.c_int32, c_float_p, c_float_p]),
+    "osh_host_stereo_restatement": (C.c_int, [C.POINTER(HostStereoInput), c_float_p, c_float_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                                              c_uint8_p, c_uint8_p, c_int32_p, c_double_p]),
     "osh_host_search_keyframe": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, c_int32_p, C.c_int32, c_float_p, c_uint8_p, c_float_p,
                                            c_uint8_p, c_uint8_p, c_int32_p, C.c_float, C.c_int32, C.c_int32, c_int32_p]),
 }

@@ -5,10 +5,14 @@
 // below projects the whole list in one launch of k_frustum (csrc/orb_device.hip) and writes the same MapPoint fields
 // (mbTrackInView, mTrackProjX/Y/XR, mTrackDepth, mnTrackScaleLevel, mTrackViewCos).  The single-point overload keeps the
 // reference signature and goes through the same kernel with a batch of one.  There is no CPU fallback.
+//
+// Frame::ComputeStereoMatches (src/Frame.cc:816-986, called by the stereo constructor at :141) is a pack and a write-back around
+// osh_orb_stereo_match (csrc/stereo_device.hip): the row-band search, the SAD window, the parabola and the median cut run on the device.
 #include <cstdio>
 #include <vector>
 #include "Frame.h"
 #include "MapPoint.h"
+#include "host_pack.h"
 #include "orbslam3_hip.h"
 
 namespace ORB_SLAM3 {
@@ -89,6 +93,33 @@ int Frame::isInFrustum(const std::vector<MapPoint*>& vpMPs, float viewingCosLimi
     }
   }
   return n_in;
+}
+
+void Frame::ComputeStereoMatches() {
+  const size_t n = mvKeys.size();
+  mvuRight = std::vector<float>(n, -1.0f);   // :818-819; the state in which every keypoint is monocular
+  mvDepth = std::vector<float>(n, -1.0f);
+  if (n == 0) return;
+  StereoPack pk;
+  if (!PackStereoMatches(*this, pk)) {
+    std::fprintf(stderr, "Frame::ComputeStereoMatches: %s\n", pk.unsupported);
+    return;
+  }
+  osh_orb_ctx* ctx = HostMatcherContext();
+  if (!ctx) {
+    std::fprintf(stderr, "Frame::ComputeStereoMatches: %s\n", osh_last_error());
+    return;
+  }
+  osh_stereo_frame f;
+  pk.fill(f, *this);
+  std::vector<float> u_right(n), depth(n);
+  osh_stereo_result res{u_right.data(), depth.data(), nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (osh_orb_stereo_match(ctx, 1, &f, &res) != OSH_OK) {
+    std::fprintf(stderr, "Frame::ComputeStereoMatches: %s\n", osh_last_error());
+    return;
+  }
+  mvuRight.swap(u_right);
+  mvDepth.swap(depth);
 }
 
 bool Frame::isInFrustum(MapPoint* pMP, float viewingCosLimit) {

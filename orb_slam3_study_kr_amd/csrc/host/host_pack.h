@@ -9,6 +9,7 @@
 #include <set>
 #include <vector>
 #include "CameraModels/GeometricCamera.h"
+#include "Frame.h"
 #include "ImuTypes.h"
 #include "KeyFrame.h"
 #include "LoopClosing.h"
@@ -478,4 +479,55 @@ void PackWeldingBA(KeyFrame* pMainKF, const std::vector<KeyFrame*>& vpAdjustKF, 
 // Vertex / edge construction of Optimizer::BundleAdjustment (src/Optimizer.cc:112-300); vbNotIncludedMP as there.
 void PackBundleAdjustment(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& vpMP, LbaPack& pk,
                           std::vector<bool>& vbNotIncludedMP);
+
+// The frame Frame::ComputeStereoMatches (Frame.cc) hands to osh_orb_stereo_match: keypoints and descriptors copied into flat arrays,
+// the pyramid levels referenced in place through ptr<uchar>(0) and step (a level is a view into a bordered image: its rows are
+// `step` bytes apart, never `cols`).  False (with `unsupported`) when the frame's members do not fit together.
+struct StereoPack {
+  std::vector<float> left_xy, right_xy;
+  std::vector<int32_t> left_octave, right_octave;
+  std::vector<uint8_t> left_desc, right_desc;
+  std::vector<osh_stereo_image> left_pyramid, right_pyramid;
+  const char* unsupported = nullptr;
+  void fill(osh_stereo_frame& f, const Frame& F) const {
+    f.n_left = (int32_t)left_octave.size(); f.n_right = (int32_t)right_octave.size();
+    f.left_xy = left_xy.data(); f.left_octave = left_octave.data(); f.left_desc = left_desc.data();
+    f.right_xy = right_xy.data(); f.right_octave = right_octave.data(); f.right_desc = right_desc.data();
+    f.n_levels = (int32_t)left_pyramid.size();
+    f.scale_factors = F.mvScaleFactors.data(); f.inv_scale_factors = F.mvInvScaleFactors.data();
+    f.left_pyramid = left_pyramid.data(); f.right_pyramid = right_pyramid.data();
+    f.bf = F.mbf; f.b = F.mb;
+  }
+};
+inline bool PackStereoMatches(const Frame& F, StereoPack& pk) {
+  if (!F.mpORBextractorLeft || !F.mpORBextractorRight) { pk.unsupported = "no ORB extractors"; return false; }
+  const std::vector<cv::Mat>& pl = F.mpORBextractorLeft->mvImagePyramid;
+  const std::vector<cv::Mat>& pr = F.mpORBextractorRight->mvImagePyramid;
+  if (pl.empty() || pl.size() != pr.size() || F.mvScaleFactors.size() < pl.size() || F.mvInvScaleFactors.size() < pl.size()) {
+    pk.unsupported = "image pyramids and scale factors differ in their number of levels"; return false;
+  }
+  const size_t nl = F.mvKeys.size(), nr = F.mvKeysRight.size();
+  if ((size_t)F.mDescriptors.rows < nl || (size_t)F.mDescriptorsRight.rows < nr || (nl && F.mDescriptors.cols != 32) || (nr && F.mDescriptorsRight.cols != 32)) {
+    pk.unsupported = "descriptor matrices do not match the keypoints"; return false;
+  }
+  auto keys = [](const std::vector<cv::KeyPoint>& k, const cv::Mat& D, std::vector<float>& xy, std::vector<int32_t>& oct, std::vector<uint8_t>& desc) {
+    xy.resize(k.size() * 2); oct.resize(k.size()); desc.resize(k.size() * 32);
+    for (size_t i = 0; i < k.size(); ++i) {
+      xy[2 * i] = k[i].pt.x; xy[2 * i + 1] = k[i].pt.y; oct[i] = k[i].octave;
+      std::copy(D.ptr<uint8_t>((int)i), D.ptr<uint8_t>((int)i) + 32, &desc[32 * i]);
+    }
+  };
+  keys(F.mvKeys, F.mDescriptors, pk.left_xy, pk.left_octave, pk.left_desc);
+  keys(F.mvKeysRight, F.mDescriptorsRight, pk.right_xy, pk.right_octave, pk.right_desc);
+  auto levels = [](const std::vector<cv::Mat>& pyr, std::vector<osh_stereo_image>& out) {
+    out.resize(pyr.size());
+    for (size_t l = 0; l < pyr.size(); ++l) {
+      const cv::Mat& m = pyr[l];
+      out[l].data = m.empty() ? nullptr : m.ptr<uint8_t>(0);
+      out[l].rows = m.rows; out[l].cols = m.cols; out[l].stride = (int64_t)(size_t)m.step;
+    }
+  };
+  levels(pl, pk.left_pyramid); levels(pr, pk.right_pyramid);
+  return true;
+}
 }  // namespace ORB_SLAM3

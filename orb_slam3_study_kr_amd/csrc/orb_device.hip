@@ -11,6 +11,7 @@
 // Integer-VALU bound: per descriptor pair 8 v_xor_b32 + 8 v_bcnt_u32_b32 and
 // 4 select ops; the 32-byte train rows are staged in LDS and read as wave-wide broadcasts.
 #include "common.h"
+#include "orb_hamming.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -41,26 +42,6 @@ struct OrbView {
   float min_x, min_y, winv, hinv; int cols, rows;
   int* best_idx; int* best_dist; int* second_dist; int* best_level; int* second_level; int* second_idx;
 };
-
-// popcount(x) + acc in ONE instruction (v_bcnt_u32_b32 adds its second operand).  Written as `__builtin_popcount(x) + acc` the
-// compiler re-associates the eight terms of a distance into separate counts and a tree of v_add3_u32: 3 extra lane-ops per pair
-// (22.8 measured against the 16 of eight xor + eight chained counts).
-__device__ __forceinline__ unsigned bcnt_acc(unsigned x, unsigned acc) {
-  unsigned r;
-  asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-  return r;
-}
-__device__ __forceinline__ unsigned hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-  unsigned d = __builtin_popcount(a0.x ^ b0.x);
-  d = bcnt_acc(a0.y ^ b0.y, d);
-  d = bcnt_acc(a0.z ^ b0.z, d);
-  d = bcnt_acc(a0.w ^ b0.w, d);
-  d = bcnt_acc(a1.x ^ b1.x, d);
-  d = bcnt_acc(a1.y ^ b1.y, d);
-  d = bcnt_acc(a1.z ^ b1.z, d);
-  d = bcnt_acc(a1.w ^ b1.w, d);
-  return d;
-}
 
 // keep the two smallest keys: with best <= second the new second is the MEDIAN of (best, second, key) -- one v_med3_u32 instead of
 // a max and a min
@@ -565,7 +546,22 @@ struct osh_orb_ctx {
   std::vector<float> h_fin, h_fout;
   OrbView v{};
   bool uploaded = false, matched = false, windowed = false, grid = false;
+  void* attach = nullptr;                 // state of osh_orb_stereo_match (stereo_device.hip)
+  void (*attach_free)(void*) = nullptr;
 };
+
+int osh::orb_stream(osh_orb_ctx* c, int* device, hipStream_t* stream) {
+  if (!c) { set_error("no context"); return OSH_ERR_INVALID; }
+  OSH_HIP(hipSetDevice(c->device));
+  *device = c->device; *stream = c->stream;
+  return OSH_OK;
+}
+void** osh::orb_attachment(osh_orb_ctx* c, void (*free_fn)(void*)) {
+  if (!c) return nullptr;
+  c->attach_free = free_fn;
+  return &c->attach;
+}
+bool osh::orb_profiling(osh_orb_ctx* c) { return c && c->timer.enabled; }
 
 extern "C" int osh_orb_create(int device, osh_orb_ctx** out) {
   if (!out) { set_error("osh_orb_create: out is NULL"); return OSH_ERR_INVALID; }
@@ -590,6 +586,7 @@ extern "C" void osh_orb_destroy(osh_orb_ctx* c) {
                     &c->d_claim, &c->d_owner[0], &c->d_owner[1], &c->d_pre, &c->d_blocks, &c->d_cur[0], &c->d_cur[1], &c->d_cur[2], &c->d_cur[3],
                     &c->d_cur[4], &c->d_state, &c->d_assign, &c->d_nmatch, &c->d_fin, &c->d_fout};
   for (DevBuf* b : bufs) b->release();
+  if (c->attach && c->attach_free) { c->attach_free(c->attach); c->attach = nullptr; }
   c->timer.destroy();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

@@ -137,6 +137,65 @@ class OrbMatcher:
                    "osh_orb_distance_matrix", self.lib)
         return out
 
+    def stereo_match(self, frames, stages: bool = False, borders=None) -> list:
+        """Frame::ComputeStereoMatches (src/Frame.cc:816-986) for a batch of synth_stereo.StereoFrame in one osh_orb_stereo_match
+        call: per frame a dict with u_right / depth, and with `stages` also best_right, hamming, sad [n, 11], best_inc, stage.
+        borders: per frame the pixels of border around every pyramid level (None: contiguous levels); the levels are then handed
+        over as views into larger images, row stride cols + 2 * border."""
+        cf, cr, _keep, outs = stereo_args(frames, stages, borders)
+        capi.check(self.lib.osh_orb_stereo_match(self.ctx, len(frames), cf, cr), "osh_orb_stereo_match", self.lib)
+        return outs
+
+    @staticmethod
+    def _stereo_args(frames, stages, borders):
+        n_frames = len(frames)
+        cf = (capi.StereoFrame * max(n_frames, 1))()
+        cr = (capi.StereoResult * max(n_frames, 1))()
+        keep, outs = [], []
+        c = np.ascontiguousarray
+        for k, fr in enumerate(frames):
+            border = 0 if borders is None else int(borders[k])
+            a = dict(lxy=c(fr.left_xy, np.float32), loct=c(fr.left_octave, np.int32), ldesc=c(fr.left_desc, np.uint8),
+                     rxy=c(fr.right_xy, np.float32), roct=c(fr.right_octave, np.int32), rdesc=c(fr.right_desc, np.uint8),
+                     sf=c(fr.scale_factors, np.float32), isf=c(fr.inv_scale_factors, np.float32))
+            f = cf[k]
+            f.n_left, f.n_right, f.n_levels = a["loct"].shape[0], a["roct"].shape[0], fr.n_levels
+            f.left_xy, f.left_octave, f.left_desc = capi.ptr(a["lxy"], capi.c_float_p), capi.ptr(a["loct"], capi.c_int32_p), capi.ptr(a["ldesc"], capi.c_uint8_p)
+            f.right_xy, f.right_octave, f.right_desc = capi.ptr(a["rxy"], capi.c_float_p), capi.ptr(a["roct"], capi.c_int32_p), capi.ptr(a["rdesc"], capi.c_uint8_p)
+            f.scale_factors, f.inv_scale_factors = capi.ptr(a["sf"], capi.c_float_p), capi.ptr(a["isf"], capi.c_float_p)
+            pyr = []
+            for side in (fr.left_pyramid, fr.right_pyramid):
+                imgs = (capi.StereoImage * fr.n_levels)()
+                for l, m in enumerate(side):
+                    if m is None:
+                        continue                           # a level no left keypoint names: data stays NULL
+                    whole = np.full((m.shape[0] + 2 * border, m.shape[1] + 2 * border), 167, dtype=np.uint8)
+                    whole[border:border + m.shape[0], border:border + m.shape[1]] = m
+                    a[f"img{len(a)}"] = whole
+                    imgs[l].data = C.cast(whole.ctypes.data + border * whole.shape[1] + border, capi.c_uint8_p)
+                    imgs[l].rows, imgs[l].cols, imgs[l].stride = m.shape[0], m.shape[1], whole.shape[1]
+                pyr.append(imgs)
+            f.left_pyramid, f.right_pyramid = pyr[0], pyr[1]
+            f.bf, f.b = fr.bf, fr.b
+            n = f.n_left
+            o = dict(u_right=np.zeros(n, np.float32), depth=np.zeros(n, np.float32))
+            cr[k].u_right, cr[k].depth = capi.ptr(o["u_right"], capi.c_float_p), capi.ptr(o["depth"], capi.c_float_p)
+            if stages:
+                o.update(best_right=np.zeros(n, np.int32), hamming=np.zeros(n, np.int32), sad=np.zeros((n, 11), np.int32),
+                         best_inc=np.zeros(n, np.int32), stage=np.zeros(n, np.uint8))
+                for name in ("best_right", "hamming", "sad", "best_inc"):
+                    setattr(cr[k], name, capi.ptr(o[name], capi.c_int32_p))
+                cr[k].stage = capi.ptr(o["stage"], capi.c_uint8_p)
+            keep.append((a, pyr))
+            outs.append(o)
+        return cf, cr, keep, outs
+
+    def stereo_times(self):
+        """Host-clock phases (ms) of the last stereo_match under set_profiling(True): staging, upload, kernels, download."""
+        ms = np.zeros(4, dtype=np.float64)
+        capi.check(self.lib.osh_orb_stereo_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_stereo_get_times", self.lib)
+        return ms
+
     def set_profiling(self, enable: bool):
         capi.check(self.lib.osh_orb_set_profiling(self.ctx, int(enable)), "osh_orb_set_profiling", self.lib)
 
@@ -150,6 +209,12 @@ class OrbMatcher:
         n, ms = C.c_int64(0), C.c_double(0)
         capi.check(self.lib.osh_orb_get_resolve_profile(self.ctx, C.byref(n), C.byref(ms)), "osh_orb_get_resolve_profile", self.lib)
         return int(n.value), float(ms.value)
+
+
+def stereo_args(frames, stages: bool = False, borders=None):
+    """The osh_stereo_frame / osh_stereo_result arrays of OrbMatcher.stereo_match for repeated calls: (frames, results, the arrays
+    that keep their pointers alive, the per-frame dicts of output arrays)."""
+    return OrbMatcher._stereo_args(frames, stages, borders)
 
 
 def accept_local_points(res: dict, pair_index: int, nn_ratio: float = 0.8, th_high: int = 100) -> np.ndarray:
