@@ -365,6 +365,75 @@ def test_search_by_projection_last_frame_equals_sequential_reference(ob):
     np.testing.assert_array_equal(assign, assign_ref)
 
 
+@pytest.mark.parametrize("motion", ["forward", "backward"])
+def test_search_by_projection_last_frame_rectified_stereo_equals_sequential_reference(ob, motion):
+    """M3 on a rectified stereo frame (bMono = false, mvuRight set), src/ORBmatcher.cc:1676-1792: the camera has moved by more than
+    the baseline along its axis, so the level range is [octave, inf) (forward, :1744-1745) or [0, octave] (backward, :1746-1747),
+    and a candidate with a stereo measurement must have it within the window of the predicted one (:1762-1767)."""
+    rng = np.random.Generator(np.random.PCG64(41 if motion == "forward" else 43))
+    f32 = np.float32
+    n_kp = 600
+    mb = 0.110078
+    xy, octave, desc, _, _, _, _ = _frame_and_points(44, n_kp=n_kp, n_mp=10)
+    angle = rng.uniform(0, 360, n_kp).astype(f32)
+    # the last frame sits at the origin; the current camera is 0.3 in front of / behind it (Tcw = [I | -twc])
+    tcw = np.array([0.0, 0.0, -0.3 if motion == "forward" else 0.3], dtype=f32)
+    pose_qt = np.concatenate([[0, 0, 0, 1], tcw]).astype(f32)
+    tlc_z = float(-tcw[2])                                   # tlc = Tlw * twc with Tlw = I, twc = -Rcw^T tcw
+    assert (tlc_z > mb) if motion == "forward" else (-tlc_z > mb)
+    # one map point per current keypoint, on its viewing ray (a little off); uright of the keypoint from its depth: most agree
+    # with the prediction, some are far off (dropped by the u_right test although inside the window), some are monocular (-1)
+    depth = rng.uniform(4, 10, n_kp)
+    noisy = xy + rng.normal(0, 1.5, xy.shape)
+    Xc = np.stack([(noisy[:, 0] - float(synth.CX)) / float(synth.FX) * depth, (noisy[:, 1] - float(synth.CY)) / float(synth.FY) * depth, depth], axis=1)
+    pos = (Xc - tcw.astype(np.float64)).astype(f32)
+    kind = rng.choice(3, n_kp, p=[0.7, 0.2, 0.1])
+    uright = (xy[:, 0] - float(synth.BF) / depth + rng.normal(0, 1.0, n_kp)).astype(f32)
+    uright[kind == 1] += (rng.choice([-1.0, 1.0], n_kp) * rng.uniform(40, 80, n_kp)).astype(f32)[kind == 1]
+    uright[kind == 2] = -1.0
+    mp_desc = desc ^ np.packbits(rng.uniform(0, 1, (n_kp, 256)) < 0.05, axis=1)
+    # the last frame's keypoint of every point: octave one off in either direction (so each level range excludes some), angle
+    # turned by one of four amounts -> four histogram bins, the smallest of which is pruned
+    last_octave = np.clip(octave + rng.integers(-1, 2, n_kp), 0, synth.N_LEVELS - 1).astype(np.int32)
+    last_angle = ((angle + rng.choice([0.0, 95.0, 185.0, 275.0], n_kp, p=[0.55, 0.25, 0.12, 0.08])) % 360).astype(f32)
+    cur = host.HostFrame(xy, octave, desc, angle=angle, uright=uright, pose_qt=pose_qt, mb=mb)
+    last = host.HostFrame(xy, last_octave, mp_desc, angle=last_angle)
+    th = 15.0
+    try:
+        n, assign = cur.search_last_frame(last, np.arange(n_kp), pos, mp_desc, th=th, mono=False, check_ori=True)
+    finally:
+        cur.close(); last.close()
+    # reference pipeline in float32: x3Dc = pos + tcw (identity rotation), pinhole projection, 1 / z in double rounded to float
+    x3Dc = (pos + tcw).astype(f32)
+    u = (synth.FX * x3Dc[:, 0] / x3Dc[:, 2] + synth.CX).astype(f32)
+    v = (synth.FY * x3Dc[:, 1] / x3Dc[:, 2] + synth.CY).astype(f32)
+    invz = (1.0 / x3Dc[:, 2].astype(np.float64)).astype(f32)
+    ur_pred = (u - (f32(synth.BF) * invz).astype(f32)).astype(f32)
+    radius = (f32(th) * synth.SCALE_FACTORS[last_octave]).astype(f32)
+    inb = (u >= 0) & (u <= synth.IMG_W) & (v >= 0) & (v <= synth.IMG_H)
+    assert (invz > 0).all()
+    if motion == "forward":
+        lo, hi = last_octave, -np.ones(n_kp, dtype=np.int32)   # max_level = -1: unbounded
+    else:
+        lo, hi = np.zeros(n_kp, dtype=np.int32), last_octave
+    off, idx = synth.features_in_area_lists(xy[:, 0], xy[:, 1], octave, u, v, np.where(inb, radius, f32(0)), lo, hi)
+    # the u_right rule: a candidate with uright > 0 is dropped when |ur_pred - uright| > radius
+    q_of = np.repeat(np.arange(n_kp), np.diff(off))
+    er = np.abs((ur_pred[q_of] - uright[idx]).astype(f32))
+    keep = ~((uright[idx] > 0) & (er > radius[q_of]))
+    assert (~keep).sum() >= 1                                  # candidates that the window alone would have kept
+    off_f = np.concatenate([[0], np.cumsum(np.bincount(q_of[keep], minlength=n_kp))]).astype(np.int32)
+    idx_f = idx[keep]
+    n_ref, assign_ref, _ = ob.orb_match_last_frame(mp_desc, desc, off_f, idx_f, last_angle, angle)
+    n_all, _, _ = ob.orb_match_last_frame(mp_desc, desc, off_f, idx_f, last_angle, angle, check_orientation=False)
+    assert n_all - n_ref >= 1                                  # the histogram pruned matches
+    assert n == n_ref and n > 100
+    np.testing.assert_array_equal(assign, assign_ref)
+    # the level range of the other motion (and the static one) would give other lists: the branch under test is the one compared
+    off_s, _ = synth.features_in_area_lists(xy[:, 0], xy[:, 1], octave, u, v, np.where(inb, radius, f32(0)), last_octave - 1, last_octave + 1)
+    assert not np.array_equal(off_s, off)
+
+
 def test_search_by_projection_last_frame_fisheye_stereo_frame(ob):
     """M3 with a fisheye stereo current frame, src/ORBmatcher.cc:1676-1887 including the right-camera block :1794-1858: the last
     frame's map points are searched among the left keypoints and then -- through Trl, projected with mpCamera as the reference
