@@ -305,6 +305,16 @@ int osh_lba_schur_plan_stats(const osh_lba_problem* problem, int64_t stats[8]);
  * of the packing. */
 int osh_lba_pack_check(int32_t n_windows, const osh_lba_problem* problems, int32_t n_threads, int64_t stats[8], double* pack_ms);
 
+/* Host-only self check of the Levenberg-Marquardt controller every solver of this library shares (needs no GPU): plays
+ * g2o's optimize() loop from `current_chi` and `lambda` over a script of n_script trials {tempChi, computeScale sum, solve_ok}
+ * (script[3 k ..]; solve_ok 0: the linear solve failed).  Per trial played: accepted[k], rho[k] and the lambda[k] / ni[k]
+ * after its update.  Per finished iteration: iter_go_on (0: optimize() stops), iter_nbad, iter_trials.  The play ends with
+ * the script or with the first iteration that stops; n_played = {trials, iterations}.  Every output array holds n_script
+ * entries. */
+int osh_lm_control_check(double current_chi, double lambda, int32_t n_script, const double* script, int32_t* accepted,
+                         double* rho, double* lambda_out, double* ni, int32_t* iter_go_on, int32_t* iter_nbad,
+                         int32_t* iter_trials, int32_t n_played[2]);
+
 /* ----------------------------------------------- local inertial BA (config 4) */
 /*
  * One Optimizer::LocalInertialBA window (src/Optimizer.cc:2387-2964) as flat arrays.

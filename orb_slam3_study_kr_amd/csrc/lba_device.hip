@@ -37,6 +37,7 @@
 #include "schur_plan.h"
 #include "lba_pack.h"
 #include "lba_pack_device.h"
+#include "g2o_lm.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -46,8 +47,6 @@
 namespace osh {
 
 constexpr int kResidualSplit = 1;    // blocks of k_residual per chunk
-constexpr double kTau = 1e-5;      // OptimizationAlgorithmLevenberg::_tau
-constexpr int kMaxTrials = 10;     // maxTrialsAfterFailure
 constexpr int kSolveThreadsBatch = 256, kSolveThreadsLatency = 512;
 constexpr int kPoseRec = 21;       // staged pose: quaternion + translation (7), camera (5), rotation matrix (9)
 constexpr int kDevicePackMinWindows = 24;   // smaller batches are packed by host threads (osh_lba_upload)
@@ -1120,7 +1119,7 @@ __global__ __launch_bounds__(64) void k_control(BatchView bv, int phase) {
       st.currentChi = chi; st.tempChi = chi; st.iniChi = chi;
       if (st.iter == 0) {
         st.chi2_initial = chi;
-        st.lambda = (wd.lambda_init > 0) ? wd.lambda_init : kTau * dm;  // computeLambdaInit
+        st.lambda = (wd.lambda_init > 0) ? wd.lambda_init : kLmTau * dm;  // computeLambdaInit
         st.ni = 2.0; st.nBad = 0;
         st.need_dl = 1;   // the landmark factors could not be formed before lambda was known
       }
@@ -1139,26 +1138,16 @@ __global__ __launch_bounds__(64) void k_control(BatchView bv, int phase) {
   st.tempChi = tempChi;
   st.last_eval_sel = st.sel ^ 1;  // computeActiveErrors just ran on the trial estimates
   st.lin_now = 0;
-  double rho = st.currentChi - tempChi;
-  double scale = st.scale_pose + sc;
-  scale += 1e-3;
-  rho /= scale;
-  if (rho > 0 && isfinite(tempChi)) {
-    double alpha = 1. - pow((2 * rho - 1), 3);
-    alpha = fmin(alpha, 2. / 3.);
-    const double scaleFactor = fmax(1. / 3., alpha);
-    st.lambda *= scaleFactor;
-    st.ni = 2;
+  const LmTrial trial = lm_judge_trial(st.lambda, st.ni, st.currentChi, tempChi, st.scale_pose + sc);
+  const double rho = trial.rho;
+  if (trial.accepted) {
     st.currentChi = tempChi;
-    st.sel ^= 1;  // discardTop: the trial estimates become current
-  } else {
-    st.lambda *= st.ni;
-    st.ni *= 2;  // pop: trial buffer is simply abandoned
+    st.sel ^= 1;  // discardTop: the trial estimates become current (pop: a rejected trial's buffer is simply abandoned)
   }
   st.rho = rho;
   st.qmax++;
   st.trials++;
-  const bool again = (rho < 0) && (st.qmax < kMaxTrials) && !st.stop;
+  const bool again = (rho < 0) && (st.qmax < kLmMaxTrials) && !st.stop;
   st.need_dl = again ? 1 : 0;   // another trial of this iteration: same Hll, new lambda
   if (!again) {
     // the iteration is over
@@ -1169,12 +1158,7 @@ __global__ __launch_bounds__(64) void k_control(BatchView bv, int phase) {
       st.trials_trace[st.n_trace] = st.qmax;
       st.n_trace++;
     }
-    bool ok = true;
-    if (st.qmax == kMaxTrials || rho == 0) ok = false;  // Terminate
-    else {
-      if ((st.iniChi - st.currentChi) * 1e3 < st.iniChi) st.nBad++; else st.nBad = 0;  // Raul's stop
-      if (st.nBad >= 3) ok = false;
-    }
+    const bool ok = lm_iteration_goes_on(st.nBad, st.iniChi, st.currentChi, st.qmax, rho);
     st.iter++;
     if (!ok || st.iter >= wd.max_iter || st.stop) st.active = 0;
     else st.need_lin = 1;
@@ -1742,7 +1726,7 @@ extern "C" int osh_lba_optimize(osh_lba_ctx* c) {
   OSH_TRY(read_nactive(c, &n_active));
   int max_iter = 0;
   for (const WinDesc& d : pb.win) max_iter = std::max(max_iter, d.max_iter);
-  const long max_rounds = (long)max_iter * kMaxTrials + 1;
+  const long max_rounds = (long)max_iter * kLmMaxTrials + 1;
   for (long round = 0; round < max_rounds && n_active > 0; ++round) {
     if (round == 0) {
       OSH_TRY(first_linearisation(c));

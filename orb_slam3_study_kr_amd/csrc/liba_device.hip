@@ -20,6 +20,7 @@
 #include "ldlt_block.h"
 #include "liba_math.h"
 #include "liba_edges.h"
+#include "g2o_lm.h"
 #include <algorithm>
 #include <cfloat>
 #include <cstring>
@@ -1208,7 +1209,7 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
       OSH_GSYNC();
     }
     if (!lambda_known) {
-      // setLambda's default: 1e-5 x the largest diagonal entry of the full Hessian (computeLambdaInit)
+      // setLambda's default: kLmTau x the largest diagonal entry of the full Hessian (computeLambdaInit)
       if (m == 0) {
         double mx = 0.0;
         for (int k = tid; k < n; k += kLT) {
@@ -1219,7 +1220,7 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
         }
         for (int j = tid; j < L; j += kLT) mx = fmax(mx, fmax(fabs(Hll[(size_t)j * 6]), fmax(fabs(Hll[(size_t)j * 6 + 3]), fabs(Hll[(size_t)j * 6 + 5]))));
         mx = blk_max(mx, shw);
-        if (tid == 0) ctrl[0] = 1e-5 * mx;
+        if (tid == 0) ctrl[0] = kLmTau * mx;
       }
       OSH_GSYNC();
       lambda = ctrl[0];
@@ -1256,27 +1257,16 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
       eval_sel = trs;
       if (!ok2) tempChi = DBL_MAX;
       // controller: identical decisions in every thread of every block (all inputs are group-uniform)
-      rho = (currentChi - tempChi);
-      const double scale = scale_sum + 1e-3;
-      rho /= scale;
-      if (rho > 0 && isfinite(tempChi)) {
-        double alpha = 1. - pow((2 * rho - 1), 3);
-        alpha = fmin(alpha, 2. / 3.);
-        lambda *= fmax(1. / 3., alpha);
-        ni = 2; currentChi = tempChi;
-        sel = trs;   // discardTop
-      } else {
-        lambda *= ni; ni *= 2;   // pop
-      }
+      const LmTrial trial = lm_judge_trial(lambda, ni, currentChi, tempChi, scale_sum);
+      rho = trial.rho;
+      if (trial.accepted) { currentChi = tempChi; sel = trs; }   // discardTop; a rejected trial's buffer is simply abandoned (pop)
       qmax++; trials_total++;
       OSH_PROF(6);
-    } while (rho < 0 && qmax < 10);
+    } while (rho < 0 && qmax < kLmMaxTrials);
     ++cj;
     if (m == 0 && tid == 0 && n_trace < OSH_LBA_MAX_TRACE) { out.chi2_trace[n_trace] = currentChi; out.lambda_trace[n_trace] = lambda; out.trials_trace[n_trace] = qmax; }
     if (n_trace < OSH_LBA_MAX_TRACE) ++n_trace;
-    if (qmax == 10 || rho == 0) { ok = false; continue; }
-    if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-    if (nBad >= 3) { ok = false; continue; }
+    ok = lm_iteration_goes_on(nBad, iniChi, currentChi, qmax, rho);
   }
   if (m == 0 && tid == 0) { out.iterations = cj; out.trials = trials_total; out.n_trace = n_trace; out.sel = sel; out.chi2_final = last_chi; }
   liba_outputs(c, sel, eval_sel);

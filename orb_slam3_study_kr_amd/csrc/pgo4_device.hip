@@ -190,12 +190,12 @@ extern "C" int osh_pgo4_solve(osh_lba_ctx* ctx, const osh_pgo4_problem* p, osh_p
   res->envelope_entries = R.P.env_entries;
   res->envelope_tiles = R.P.ntiles;
   res->tall_columns = R.P.tall;
-  // computeLambdaInit: the user's value, else tau * max diag(H), tau = 1e-5
+  // computeLambdaInit: the user's value, else tau * max diag(H), tau = kLmTau
   auto lambda0 = [&](double* l) {
     if (p->lambda_init > 0) { *l = p->lambda_init; return OSH_OK; }
     double maxd = 0;
     OSH_TRY(R.max_diag(&maxd));
-    *l = 1e-5 * maxd;
+    *l = kLmTau * maxd;
     return OSH_OK;
   };
   LmResult lm;

@@ -24,6 +24,7 @@
 // No FMA contraction, as in the vertex algebra: the factorisation and the reductions round every operation, so that both graphs
 // solve in the same bits whichever header a translation unit includes first.
 #pragma clang fp contract(off)
+#include "g2o_lm.h"   // below the pragma: PgoRun::solve's controller is compiled without contraction in both graphs, as it was
 
 namespace osh {
 namespace {
@@ -543,7 +544,6 @@ struct PgoRun {
   int solve(int max_iterations, Lambda0 lambda0, LmResult& out) {
     int cur = 0, nBad = 0;
     double lambda = 0.0, ni = 2.0;
-    const int maxTrials = 10;
     bool ok = true;
     for (int it = 0; it < max_iterations && ok; ++it) {
       OSH_TRY(errors(cur, 1));
@@ -563,30 +563,20 @@ struct PgoRun {
       do {
         OSH_TRY(trial(cur, lambda));
         double tempChi = h_red[0];
-        const double scale = h_red[1] + 1e-3;
         int fail = 0;
         std::memcpy(&fail, &h_red[2], 4);
         if (fail) tempChi = std::numeric_limits<double>::max();
-        rho = (currentChi - tempChi) / scale;
-        if (rho > 0 && std::isfinite(tempChi)) {
-          double alpha = 1. - std::pow((2 * rho - 1), 3);
-          alpha = std::min(alpha, 2. / 3.);
-          const double scaleFactor = std::max(1. / 3., alpha);
-          lambda *= scaleFactor;
-          ni = 2;
+        const LmTrial t = lm_judge_trial(lambda, ni, currentChi, tempChi, h_red[1]);
+        rho = t.rho;
+        if (t.accepted) {
           currentChi = tempChi;
-          cur = 1 - cur;   // discardTop: the trial's states become the vertices
-        } else {
-          lambda *= ni;
-          ni *= 2;         // pop: the trial's states are dropped
+          cur = 1 - cur;   // discardTop: the trial's states become the vertices (pop: a rejected trial's states are dropped)
         }
         ++qmax;
         ++out.trials;
-      } while (rho < 0 && qmax < maxTrials);
+      } while (rho < 0 && qmax < kLmMaxTrials);
       ++out.iterations;
-      if (qmax == maxTrials || rho == 0) { ok = false; continue; }
-      if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;   // the stop rule of this g2o copy (levenberg.cpp:154-164)
-      if (nBad >= 3) ok = false;
+      ok = lm_iteration_goes_on(nBad, iniChi, currentChi, qmax, rho);
     }
     // computeActiveErrors at the returned states
     OSH_TRY(errors(cur, 0));

@@ -13,6 +13,8 @@
 // trip, thread per edge, fixed-order block reductions (bitwise reproducible).
 #include "common.h"
 #include "lba_math.h"
+#include "block_kit.h"   // compiled under this file's default FMA contraction
+#include "g2o_lm.h"
 #include <cfloat>
 #include <cstring>
 #include <vector>
@@ -182,30 +184,16 @@ __global__ __launch_bounds__(kPT) void k_pose_opt(PoseView v) {
         }
       });
       {
-        // 27 block sums with two barriers: wavefront butterflies, partials parked in LDS, added in wavefront order (deterministic);
-        // one barrier pair per value cost 54 barriers per LM iteration
         double red[27];
 #pragma unroll
-        for (int k = 0; k < 21; ++k) red[k] = dev::wave_sum(H[k]);
+        for (int k = 0; k < 21; ++k) red[k] = H[k];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) red[21 + k] = dev::wave_sum(b[k]);
-        __syncthreads();
-        if ((tid & 63) == 0) {
-#pragma unroll
-          for (int k = 0; k < 27; ++k) shn[(tid >> 6) * 27 + k] = red[k];
-        }
-        __syncthreads();
-        if (tid < 27) {
-          double t = 0.0;
-#pragma unroll
-          for (int w = 0; w < kPT / 64; ++w) t += shn[w * 27 + tid];
-          shH[tid] = t;
-        }
+        for (int k = 0; k < 6; ++k) red[21 + k] = b[k];
+        dev::block_sum_n_to<kPT, 27>(red, shn, shH);
       }
       __syncthreads();
       if (it == 0) {
-        // computeLambdaInit: tau * max |H_dd| (optimization_algorithm_levenberg.cpp:171-185); diagonal = entries 0, 6, 11, 15, 18, 20
-        lambda = 1e-5 * fmax(fmax(fmax(fabs(shH[0]), fabs(shH[6])), fmax(fabs(shH[11]), fabs(shH[15]))), fmax(fabs(shH[18]), fabs(shH[20])));
+        lambda = kLmTau * dev::upper_max_abs_diag<6>(shH);   // computeLambdaInit
         ni = 2.0; nBad = 0;
       }
       double rho = 0.0;
@@ -213,49 +201,9 @@ __global__ __launch_bounds__(kPT) void k_pose_opt(PoseView v) {
       do {
         const int trs = sel ^ 1;
         if (tid == 0) {
-          // (Hpp + lambda I) x = b by LDL^T; the solver reports failure unless every pivot is positive
-          // (every loop unrolled: with run-time indices the 6x6 array lives in scratch memory and this one-thread section was
-          // most of an iteration; a non-positive pivot no longer leaves the loop early, its results are simply not used)
-          double A[36], x[6];
-          {
-            int m = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-              for (int c2 = a; c2 < 6; ++c2) { A[a * 6 + c2] = shH[m] + ((a == c2) ? lambda : 0.0); ++m; }
-          }
-          bool good = true;
-#pragma unroll
-          for (int k = 0; k < 6; ++k) {
-            const double dk = A[k * 6 + k];
-            good = good && (dk > 0.0);
-            double l[6];
-#pragma unroll
-            for (int i = k + 1; i < 6; ++i) l[i] = A[k * 6 + i] / dk;
-#pragma unroll
-            for (int i = k + 1; i < 6; ++i)
-#pragma unroll
-              for (int j = i; j < 6; ++j) A[i * 6 + j] -= l[i] * A[k * 6 + j];
-#pragma unroll
-            for (int i = k + 1; i < 6; ++i) A[k * 6 + i] = l[i];
-          }
-#pragma unroll
-          for (int k = 0; k < 6; ++k) x[k] = shH[21 + k];
-#pragma unroll
-          for (int k = 0; k < 6; ++k)
-#pragma unroll
-            for (int i = k + 1; i < 6; ++i) x[i] -= A[k * 6 + i] * x[k];
-#pragma unroll
-          for (int k = 0; k < 6; ++k) x[k] /= A[k * 6 + k];
-#pragma unroll
-          for (int k = 5; k >= 0; --k) {
-            double s2 = x[k];
-#pragma unroll
-            for (int i = k + 1; i < 6; ++i) s2 -= A[k * 6 + i] * x[i];
-            x[k] = s2;
-          }
-#pragma unroll
-          for (int k = 0; k < 6; ++k) x[k] = good ? x[k] : 0.0;
+          // (Hpp + lambda I) x = b; the solver reports failure unless every pivot is positive
+          double x[6];
+          const bool good = dev::ldlt_solve_upper<6>(shH, shH + 21, lambda, x);
           double qin[7], qout[7];
           for (int k = 0; k < 7; ++k) qin[k] = sh_qt[sel][k];
           dev::pose_oplus(x, qin, qout);
@@ -269,29 +217,18 @@ __global__ __launch_bounds__(kPT) void k_pose_opt(PoseView v) {
         for (int k = 0; k < 7; ++k) qtr[k] = sh_qt[trs][k];
         double tempChi = pose_eval<KB8>(v, d, ec, qtr, robust, sh);
         if (!sh_ok) tempChi = DBL_MAX;
-        rho = currentChi - tempChi;
-        double scale = 0.0;
+        double scale = 0.0;   // computeScale
 #pragma unroll
         for (int k = 0; k < 6; ++k) scale += sh_x[k] * (lambda * sh_x[k] + shH[21 + k]);
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && isfinite(tempChi)) {
-          double alpha = 1. - pow((2 * rho - 1), 3);
-          alpha = fmin(alpha, 2. / 3.);
-          lambda *= fmax(1. / 3., alpha);
-          ni = 2; currentChi = tempChi;
-          sel = trs;
-        } else {
-          lambda *= ni; ni *= 2;
-        }
+        const LmTrial trial = lm_judge_trial(lambda, ni, currentChi, tempChi, scale);
+        rho = trial.rho;
+        if (trial.accepted) { currentChi = tempChi; sel = trs; }
         qmax++;
         __syncthreads();
-      } while (rho < 0 && qmax < 10);
+      } while (rho < 0 && qmax < kLmMaxTrials);
       ++cj;
       last_chi = currentChi;
-      if (qmax == 10 || rho == 0) { ok = false; continue; }
-      if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-      if (nBad >= 3) { ok = false; continue; }
+      ok = lm_iteration_goes_on(nBad, iniChi, currentChi, qmax, rho);
     }
     // ---- classification (:1030-1105).  chi2 of an inlier = its _error as last computed by the optimiser (after a rejected
     // final trial that is the trial's error, as in the reference); an outlier is re-evaluated at the final estimate.

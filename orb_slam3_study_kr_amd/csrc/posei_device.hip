@@ -15,6 +15,7 @@
 #include "ldlt_block.h"
 #include "liba_math.h"
 #include "liba_edges.h"
+#include "block_kit.h"   // compiled under this file's default FMA contraction
 #include <cfloat>
 #include <cstring>
 #include <algorithm>
@@ -44,27 +45,6 @@ struct PoseiView {
   double* chi2; unsigned char* level; unsigned char* outlier;
   int ecap;                   // edges per frame the block's dynamic LDS can hold (0: every access goes to global memory)
 };
-
-// N block sums with TWO barriers: butterfly inside each wavefront, the wavefront partials parked in LDS ([kIT/64][N]) and added in
-// wavefront order by every thread (deterministic).  27 single sums cost 54 barriers per Gauss-Newton iteration before.
-template <int N>
-__device__ __forceinline__ void posei_block_sum_n(double* v, double* shn) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = dev::wave_sum(v[k]);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) shn[(threadIdx.x >> 6) * N + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kIT / 64; ++w) t += shn[w * N + k];
-    v[k] = t;
-  }
-}
 
 // A x = b for a symmetric n x n system (n <= NMAX = 16 or 32: 15 unknowns of the frame, 30 with the previous frame free) held row-major in LDS, by ONE wavefront: lane j keeps column j, the pivot row
 // is broadcast with v_readlane; returns false unless every pivot is positive (Eigen::LDLT::isPositive).  U: 32 x 33 doubles of
@@ -217,7 +197,7 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
     for (int k = 0; k < 21; ++k) red[k] = H[k];
 #pragma unroll
     for (int k = 0; k < 6; ++k) red[21 + k] = b[k];
-    posei_block_sum_n<27>(red, shn);
+    dev::block_sum_n_all<kIT, 27>(red, shn);
     if (tid == 0) {
 #pragma unroll
       for (int k = 0; k < 27; ++k) shred[k] = red[k];
@@ -228,7 +208,7 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
       double acc = 0.0;
       if (r < 6 && c < 6) {   // visual edges: upper-triangle sums mirrored
         const int a = r < c ? r : c, bq = r < c ? c : r;
-        acc += shred[a * 6 - a * (a - 1) / 2 + (bq - a)];
+        acc += shred[dev::upper_index(6, a, bq)];
       }
       // random walks: r = b_cur - b_prev, J = [-I, I]
       for (int which = 0; which < 2; ++which) {
@@ -436,16 +416,15 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
     double red[21];
 #pragma unroll
     for (int k = 0; k < 21; ++k) red[k] = H[k];
-    posei_block_sum_n<21>(red, shn);
+    dev::block_sum_n_all<kIT, 21>(red, shn);
     if (tid == 0) {
 #pragma unroll
       for (int k = 0; k < 21; ++k) shred[k] = red[k];
     }
     if (mode1 && tid == 0) {
-      double T[9], dd[3], rr[15], invJr[9];
+      double T[9], rr[15], invJr[9];
       imu::m3_tmul(d.prior_R, shpP + 12, T);
       imu::log_so3(T, rr);
-      (void)dd;
       imu::inv_right_jac(rr, invJr);
       for (int i = 0; i < 225; ++i) shJp[i] = 0.0;
       for (int i = 0; i < 3; ++i) for (int jq = 0; jq < 3; ++jq) { shJp[i * 15 + jq] = invJr[i * 3 + jq]; shJp[(3 + i) * 15 + 3 + jq] = T[i * 3 + jq]; }
@@ -470,7 +449,7 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
       if (r >= o2 && r < o2 + 6 && c >= o2 && c < o2 + 6) {
         const int a0 = r - o2, c0 = c - o2;
         const int a = a0 < c0 ? a0 : c0, bq = a0 < c0 ? c0 : a0;
-        acc += shred[a * 6 - a * (a - 1) / 2 + (bq - a)];
+        acc += shred[dev::upper_index(6, a, bq)];
       }
       for (int ca = 0; ca < 24; ++ca) {
         if (ref_of(ca) != r) continue;

@@ -14,6 +14,8 @@
 #include "common.h"
 #include "lba_math.h"
 #include "pgo_sim3.h"   // g2o::Sim3 restated; it also turns FMA contraction off for the rest of this file (central differences)
+#include "block_kit.h"  // after pgo_sim3.h: the kit has no pragma of its own and is compiled without contraction here
+#include "g2o_lm.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -188,71 +190,14 @@ __device__ __forceinline__ void sim3_linearize(const Sim3View& v, const Sim3Desc
     }
     sim3_accumulate(J, e21, i2, r1_21, H, b);
   }
-  // 36 block sums with two barriers: wavefront butterflies, partials in LDS, added in wavefront order
   double red[kSR];
 #pragma unroll
-  for (int k = 0; k < 28; ++k) red[k] = dev::wave_sum(H[k]);
+  for (int k = 0; k < 28; ++k) red[k] = H[k];
 #pragma unroll
-  for (int k = 0; k < 7; ++k) red[28 + k] = dev::wave_sum(b[k]);
-  red[35] = dev::wave_sum(acc);
+  for (int k = 0; k < 7; ++k) red[28 + k] = b[k];
+  red[35] = acc;
+  dev::block_sum_n_to<kST, kSR>(red, sm.red, sm.sys);
   __syncthreads();
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kSR; ++k) sm.red[(tid >> 6) * kSR + k] = red[k];
-  }
-  __syncthreads();
-  if (tid < kSR) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kST / 64; ++w) t += sm.red[w * kSR + tid];
-    sm.sys[tid] = t;
-  }
-  __syncthreads();
-}
-
-// (H + lambda I) x = b by LDL^T on thread 0; the solver fails unless every pivot is positive (LinearSolverDense, isPositive)
-__device__ __forceinline__ bool sim3_solve(const double* sys, double lambda, double* x) {
-  double A[49];
-  {
-    int m = 0;
-#pragma unroll
-    for (int a = 0; a < 7; ++a)
-#pragma unroll
-      for (int c = a; c < 7; ++c) { A[a * 7 + c] = sys[m] + ((a == c) ? lambda : 0.0); ++m; }
-  }
-  bool good = true;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const double dk = A[k * 7 + k];
-    good = good && (dk > 0.0);
-    double l[7];
-#pragma unroll
-    for (int i = k + 1; i < 7; ++i) l[i] = A[k * 7 + i] / dk;
-#pragma unroll
-    for (int i = k + 1; i < 7; ++i)
-#pragma unroll
-      for (int j = i; j < 7; ++j) A[i * 7 + j] -= l[i] * A[k * 7 + j];
-#pragma unroll
-    for (int i = k + 1; i < 7; ++i) A[k * 7 + i] = l[i];
-  }
-#pragma unroll
-  for (int k = 0; k < 7; ++k) x[k] = sys[28 + k];
-#pragma unroll
-  for (int k = 0; k < 7; ++k)
-#pragma unroll
-    for (int i = k + 1; i < 7; ++i) x[i] -= A[k * 7 + i] * x[k];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) x[k] /= A[k * 7 + k];
-#pragma unroll
-  for (int k = 6; k >= 0; --k) {
-    double s = x[k];
-#pragma unroll
-    for (int i = k + 1; i < 7; ++i) s -= A[k * 7 + i] * x[i];
-    x[k] = s;
-  }
-#pragma unroll
-  for (int k = 0; k < 7; ++k) x[k] = good ? x[k] : 0.0;
-  return good;
 }
 
 // initializeOptimization + optimize(iterations) from estimate `sel` over the pairs of level 0; returns the index of the final estimate
@@ -268,12 +213,7 @@ __device__ int sim3_optimize(const Sim3View& v, const Sim3Desc& d, Sim3Shared& s
     currentChi = sm.sys[35];
     const double iniChi = currentChi;
     if (it == 0) {
-      // computeLambdaInit: tau * max |H_dd| (optimization_algorithm_levenberg.cpp:171-185); diagonal = entries 0, 7, 13, 18, 22, 25, 27
-      double m = 0.0;
-      const int diag[7] = {0, 7, 13, 18, 22, 25, 27};
-#pragma unroll
-      for (int k = 0; k < 7; ++k) m = fmax(m, fabs(sm.sys[diag[k]]));
-      lambda = 1e-5 * m;
+      lambda = kLmTau * dev::upper_max_abs_diag<7>(sm.sys);   // computeLambdaInit
       ni = 2.0; nBad = 0;
     }
     double rho = 0.0;
@@ -282,7 +222,8 @@ __device__ int sim3_optimize(const Sim3View& v, const Sim3Desc& d, Sim3Shared& s
       const int trs = sel ^ 1;
       if (tid == 0) {
         double x[7];
-        const bool good = sim3_solve(sm.sys, lambda, x);
+        // the dense 7x7 solve of LinearSolverDense: failure unless every pivot is positive
+        const bool good = dev::ldlt_solve_upper<7>(sm.sys, sm.sys + 28, lambda, x);
         if (d.fix_scale) x[6] = 0;   // oplusImpl zeroes update[6] in the solver's own vector
         sim3_set_state(sm, trs, pgo::vertex_oplus(sim3_lds(sm.S[sel]), x, d.fix_scale != 0));
 #pragma unroll
@@ -292,28 +233,17 @@ __device__ int sim3_optimize(const Sim3View& v, const Sim3Desc& d, Sim3Shared& s
       __syncthreads();
       double tempChi = sim3_eval<KB8>(v, d, sm, trs, robust);
       if (!sm.ok) tempChi = DBL_MAX;
-      rho = currentChi - tempChi;
-      double scale = 0.0;
+      double scale = 0.0;   // computeScale
 #pragma unroll
       for (int k = 0; k < 7; ++k) scale += sm.x[k] * (lambda * sm.x[k] + sm.sys[28 + k]);
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0 && isfinite(tempChi)) {
-        double alpha = 1. - pow((2 * rho - 1), 3);
-        alpha = fmin(alpha, 2. / 3.);
-        lambda *= fmax(1. / 3., alpha);
-        ni = 2; currentChi = tempChi;
-        sel = trs;
-      } else {
-        lambda *= ni; ni *= 2;
-      }
+      const LmTrial trial = lm_judge_trial(lambda, ni, currentChi, tempChi, scale);
+      rho = trial.rho;
+      if (trial.accepted) { currentChi = tempChi; sel = trs; }
       qmax++;
       __syncthreads();
-    } while (rho < 0 && qmax < 10);
+    } while (rho < 0 && qmax < kLmMaxTrials);
     ++cj;
-    if (qmax == 10 || rho == 0) { ok = false; continue; }
-    if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-    if (nBad >= 3) ok = false;
+    ok = lm_iteration_goes_on(nBad, iniChi, currentChi, qmax, rho);
   }
   iters_out = cj;
   chi_out = currentChi;
