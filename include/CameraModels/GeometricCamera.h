@@ -67,7 +67,10 @@ class Pinhole : public GeometricCamera {
 // project() is the formula of src/CameraModels/KannalaBrandt8.cpp:45-63 for completeness.
 class KannalaBrandt8 : public GeometricCamera {
  public:
-  explicit KannalaBrandt8(const std::vector<float>& p) : GeometricCamera(p) { mnType = CAM_FISHEYE; }
+  explicit KannalaBrandt8(const std::vector<float>& p) : GeometricCamera(p), precision(1e-6) { mnType = CAM_FISHEYE; }
+  KannalaBrandt8(const std::vector<float>& p, const float _precision) : GeometricCamera(p), precision(_precision) { mnType = CAM_FISHEYE; }
+  float GetPrecision() { return precision; }   // include/CameraModels/KannalaBrandt8.h:98,102: the Newton tolerance of unproject
+  const float precision;
   Eigen::Vector2d project(const Eigen::Vector3d& v) override {
     const double x2_plus_y2 = v[0] * v[0] + v[1] * v[1];
     const double theta = atan2f(sqrtf(x2_plus_y2), v[2]), psi = atan2f(v[1], v[0]);

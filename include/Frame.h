@@ -31,6 +31,10 @@ class Frame {
   int isInFrustum(const std::vector<MapPoint*>& vpMPs, float viewingCosLimit, std::vector<bool>& vbInView);
   // src/Frame.cc:816-986 on the device: fills mvuRight / mvDepth (all -1 with a message on stderr on a device error)
   void ComputeStereoMatches();
+  // src/Frame.cc:1131-1171 on the device: fills mvLeftToRightMatch / mvRightToLeftMatch / mvDepth / mvStereo3Dpoints of a
+  // KannalaBrandt8 rig frame.  A device error, a camera pair that is not CAM_FISHEYE or members that do not fit together: a
+  // message on stderr and every keypoint unmatched (all -1)
+  void ComputeStereoFishEyeMatches();
 
   int N = 0;
   int Nleft = -1, Nright = -1;
@@ -57,6 +61,21 @@ class Frame {
   std::vector<std::size_t> mGridRight[FRAME_GRID_COLS][FRAME_GRID_ROWS];   // include/Frame.h:329
   std::vector<int> mvLeftToRightMatch, mvRightToLeftMatch;                 // include/Frame.h:301 (stereo fisheye matches)
   Sophus::SE3f mTrl;                                                        // include/Frame.h:297
+  // what ComputeStereoFishEyeMatches reads and writes besides (include/Frame.h:247,283,331,341; mTlr / mRlr / mtlr of :180-182 below)
+  int monoLeft = 0, monoRight = 0;             // keypoints below lie outside the overlapping area
+  std::vector<float> mvLevelSigma2;
+  std::vector<Eigen::Vector3f> mvStereo3Dpoints;
+  int mnCloseMPs = 0;
+  Eigen::Matrix3f GetRelativePoseTlr_rotation() { return mRlr; }      // include/Frame.h:96-97
+  Eigen::Vector3f GetRelativePoseTlr_translation() { return mtlr; }
+  // test-double bookkeeping: what the rig constructor does at src/Frame.cc:1102-1105 (mRlr / mtlr stored as given)
+  void SetRelativePoseTlr(const Eigen::Matrix3f& Rlr, const Eigen::Vector3f& tlr) { mRlr = Rlr; mtlr = tlr; mTlr = Sophus::SE3f(Rlr, tlr); mTrl = mTlr.inverse(); }
+ private:
+  // private in the reference too (include/Frame.h:167-189): only Frame's own members may read them
+  Sophus::SE3f mTlr;
+  Eigen::Matrix3f mRlr;                        // mTlr.rotationMatrix()
+  Eigen::Vector3f mtlr;                        // mTlr.translation()
+ public:
   Sophus::SE3f GetRelativePoseTrl() const { return mTrl; }                  // src/Frame.cc:1134-1137
   float mnMinX = 0, mnMaxX = 752, mnMinY = 0, mnMaxY = 480;   // static in the reference
   float mfGridElementWidthInv = 64.f / 752.f, mfGridElementHeightInv = 48.f / 480.f;

@@ -732,6 +732,86 @@ int osh_orb_stereo_match(osh_orb_ctx* ctx, int32_t n_frames, const osh_stereo_fr
  * kept: ms[0] validation + staging (pyramid rows into pinned memory), ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
 int osh_orb_stereo_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- fisheye stereo matching */
+/*
+ * Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1131-1171) for n_frames independent frames of a KannalaBrandt8 rig in one call:
+ *   A  the two nearest neighbours (256-bit Hamming) of every left keypoint >= mono_left among the right keypoints >= mono_right
+ *      (BFmatcher.knnMatch(.., 2), :1149; among equal distances the lowest right index is the nearest), and Lowe's test
+ *      (float)d0 < (float)d1 * 0.7 as a double comparison (:1156);
+ *   B  KannalaBrandt8::TriangulateMatches (src/CameraModels/KannalaBrandt8.cpp:306-375, unproject :116-143, project :67-84,
+ *      Triangulate :394-406) of every pair that passed, with sigmaLevel = level_sigma2[left octave], unc = level_sigma2[right octave],
+ *      and the caller's depth > 0.0001f (:1162);
+ *   C  mvLeftToRightMatch / mvDepth / mvStereo3Dpoints of every accepted left keypoint, and mvRightToLeftMatch[r] = the LARGEST
+ *      accepted l that names r (the reference's loop runs in ascending l and its last writer stays, :1164).
+ * mvuRight stays -1 for every keypoint in the reference; it is not an output.
+ *
+ * Arithmetic: single IEEE float32 operations in the reference's order, no fused multiply-add; Eigen's three-term reductions (dot,
+ * norm, matrix * vector) as a0 + (a1 + a2); sqrtf, tan, atan2f, cos, sin as their correctly rounded float32 values (the FP64 function
+ * rounded once).  One deliberate deviation: the right singular vector of the 4x4 matrix A (:397-403) is computed in FP64 from the
+ * float32 entries of A by a fixed-sweep one-sided Jacobi method instead of Eigen's float JacobiSVD, and x3D = head(3) / w is rounded
+ * to float32 once.
+ *
+ * Refused with OSH_ERR_INVALID before any device work: mono_left outside [0, n_left] or mono_right outside [0, n_right], n_levels
+ * outside [1, OSH_STEREO_MAX_LEVELS], an octave outside [0, n_levels), a keypoint coordinate, level_sigma2 entry, camera parameter,
+ * precision, Rlr or tlr entry that is not finite, fx or fy equal to 0, a NULL array whose count is not 0.  n_right is limited to
+ * 2^22 - 1 (OSH_ERR_UNSUPPORTED beyond).  A refused call leaves the context usable.
+ */
+/* stage[l]: where left keypoint l stopped */
+#define OSH_FSTEREO_OUTSIDE     0  /* l < mono_left: outside the overlapping area, not a query                                  */
+#define OSH_FSTEREO_NO_PAIR     1  /* fewer than two right keypoints >= mono_right ((*it).size() >= 2, :1156)                   */
+#define OSH_FSTEREO_RATIO       2  /* Lowe's test failed (:1156)                                                               */
+#define OSH_FSTEREO_PARALLAX    3  /* TriangulateMatches returned -1: cosParallaxRays > 0.9998 (KannalaBrandt8.cpp:316)         */
+#define OSH_FSTEREO_BEHIND_1    4  /* -2: z1 <= 0 (:343)                                                                        */
+#define OSH_FSTEREO_BEHIND_2    5  /* -3: z2 <= 0 (:348)                                                                        */
+#define OSH_FSTEREO_REPROJ_1    6  /* -4: squared re-projection error in the left camera > 5.991 * sigmaLevel (:358)            */
+#define OSH_FSTEREO_REPROJ_2    7  /* -5: squared re-projection error in the right camera > 5.991 * unc (:368)                  */
+#define OSH_FSTEREO_DEPTH       8  /* triangulated, but depth <= 0.0001f (src/Frame.cc:1162)                                    */
+#define OSH_FSTEREO_ACCEPTED    9
+#define OSH_FSTEREO_NO_COS      (-2.0f)  /* cos_parallax of a left keypoint that was not triangulated (stage < 3) */
+typedef struct osh_fisheye_stereo_frame {
+  int32_t n_left, n_right;         /* Nleft, Nright                                                          */
+  int32_t mono_left, mono_right;   /* monoLeft, monoRight: keypoints below lie outside the overlapping area  */
+  const float* left_xy;            /* [n_left*2]   mvKeys[i].pt                                              */
+  const int32_t* left_octave;      /* [n_left]     mvKeys[i].octave                                          */
+  const uint8_t* left_desc;        /* [n_left*32]  mDescriptors                                              */
+  const float* right_xy;           /* [n_right*2]  mvKeysRight[i].pt                                         */
+  const int32_t* right_octave;     /* [n_right]                                                              */
+  const uint8_t* right_desc;       /* [n_right*32] mDescriptorsRight                                         */
+  int32_t n_levels;
+  const float* level_sigma2;       /* [n_levels]   mvLevelSigma2                                             */
+  float cam1[8], cam2[8];          /* mpCamera / mpCamera2: fx fy cx cy k1 k2 k3 k4                          */
+  float precision1, precision2;    /* KannalaBrandt8::precision of either camera (1e-6 in the reference)     */
+  float Rlr[9], tlr[3];            /* mRlr (row-major), mtlr                                                 */
+} osh_fisheye_stereo_frame;
+typedef struct osh_fisheye_stereo_result {
+  int32_t* left_to_right;  /* [n_left]    mvLeftToRightMatch (-1: none)                                                      */
+  int32_t* right_to_left;  /* [n_right]   mvRightToLeftMatch (-1: none)                                                      */
+  float* depth;            /* [n_left]    mvDepth (-1: none)                                                                 */
+  float* p3d;              /* [n_left*3]  mvStereo3Dpoints of the accepted keypoints; 0 0 0 elsewhere (unset in the reference) */
+  /* stage outputs, each may be NULL */
+  int32_t* best_right;     /* [n_left]    nearest right keypoint (stage >= 2), else -1                                        */
+  int32_t* best_dist;      /* [n_left]    its distance (stage >= 2), else -1                                                  */
+  int32_t* second_dist;    /* [n_left]    the second smallest distance (stage >= 2), else -1                                  */
+  float* cos_parallax;     /* [n_left]    cosParallaxRays (stage >= 3), else OSH_FSTEREO_NO_COS                               */
+  uint8_t* stage;          /* [n_left]    OSH_FSTEREO_*                                                                       */
+} osh_fisheye_stereo_result;
+int osh_orb_fisheye_stereo_match(osh_orb_ctx* ctx, int32_t n_frames, const osh_fisheye_stereo_frame* frames,
+                                 const osh_fisheye_stereo_result* results);
+/* Host-clock phases (ms) of the last osh_orb_fisheye_stereo_match under osh_orb_set_profiling: ms[0] validation + staging,
+ * ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
+int osh_orb_fisheye_stereo_get_times(osh_orb_ctx* ctx, double ms[4]);
+
+/* KannalaBrandt8::TriangulateMatches alone (step B above) for n explicit keypoint pairs of one rig: ret[i] = the reference's return
+ * value (z1, or -1 .. -5), p3d[i] = x3D when ret[i] > 0 (else 0 0 0), cos_parallax[i] = cosParallaxRays.  p3d and cos_parallax may be
+ * NULL.  What GeometricCamera::epipolarConstrain of a KannalaBrandt8 (:232-235) evaluates per candidate.  Refusals as above. */
+typedef struct osh_kb8_rig {
+  float cam1[8], cam2[8];
+  float precision1, precision2;
+  float R12[9], t12[3];
+} osh_kb8_rig;
+int osh_kb8_triangulate(osh_orb_ctx* ctx, int32_t n, const osh_kb8_rig* rig, const float* xy1, const float* xy2, const float* sigma1,
+                        const float* sigma2, float* ret, float* p3d, float* cos_parallax);
+
 #ifdef __cplusplus
 }
 #endif

@@ -384,6 +384,27 @@ int osh_host_compute_stereo_matches(const osh_host_stereo_input* in, int32_t bor
 int osh_host_stereo_restatement(const osh_host_stereo_input* in, float* u_right, float* depth, int32_t* best_right, int32_t* hamming,
                                 int32_t* sad, int32_t* best_inc, uint8_t* stage, uint8_t* flags, int32_t undefined[4], double* ms);
 
+/* ---- Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1131-1171; csrc/host/Frame.cc, csrc/hosttest/stereo.cc) ---- */
+/* A frame of a KannalaBrandt8 rig as flat arrays (the fields of osh_fisheye_stereo_frame). */
+typedef struct osh_host_fisheye_input {
+  int32_t n_left, n_right, mono_left, mono_right;
+  const float* left_xy; const int32_t* left_octave; const uint8_t* left_desc;      /* [n_left*2], [n_left], [n_left*32]    */
+  const float* right_xy; const int32_t* right_octave; const uint8_t* right_desc;   /* [n_right*2], [n_right], [n_right*32] */
+  int32_t n_levels;
+  const float* level_sigma2;                                                       /* [n_levels] mvLevelSigma2             */
+  float cam1[8], cam2[8], precision1, precision2, Rlr[9], tlr[3];
+} osh_host_fisheye_input;
+/* Frame::ComputeStereoFishEyeMatches itself on a stand-in Frame made of it (mpCamera / mpCamera2 = KannalaBrandt8 with the given
+ * precision, mRlr / mtlr as given; camera2_pinhole != 0: mpCamera2 is a Pinhole instead, which the body refuses with a message).
+ * Outputs (each may be NULL): mvLeftToRightMatch, mvRightToLeftMatch, mvDepth, mvStereo3Dpoints [n_left*3], mvuRight. */
+int osh_host_compute_fisheye_stereo_matches(const osh_host_fisheye_input* in, int32_t camera2_pinhole, int32_t* left_to_right,
+                                            int32_t* right_to_left, float* depth, float* p3d, float* u_right);
+/* csrc/kb8_triangulate.h (the device's KannalaBrandt8::TriangulateMatches) compiled for the host, arguments as osh_kb8_triangulate
+ * without a context; no output may be NULL. */
+struct osh_kb8_rig;
+int osh_host_kb8_triangulate_cpu(int32_t n, const struct osh_kb8_rig* rig, const float* xy1, const float* xy2, const float* sigma1,
+                                 const float* sigma2, float* ret, float* p3d, float* cos_parallax);
+
 #ifdef __cplusplus
 }
 #endif

@@ -297,6 +297,39 @@ OSH_STEREO_NO_INC = -128
  OSH_STEREO_DISPARITY, OSH_STEREO_ACCEPTED, OSH_STEREO_MEDIAN_CUT) = range(9)
 
 
+class FisheyeStereoFrame(C.Structure):
+    """``osh_fisheye_stereo_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("n_left", C.c_int32), ("n_right", C.c_int32), ("mono_left", C.c_int32), ("mono_right", C.c_int32),
+        ("left_xy", c_float_p), ("left_octave", c_int32_p), ("left_desc", c_uint8_p),
+        ("right_xy", c_float_p), ("right_octave", c_int32_p), ("right_desc", c_uint8_p),
+        ("n_levels", C.c_int32), ("level_sigma2", c_float_p),
+        ("cam1", C.c_float * 8), ("cam2", C.c_float * 8), ("precision1", C.c_float), ("precision2", C.c_float),
+        ("Rlr", C.c_float * 9), ("tlr", C.c_float * 3),
+    ]
+
+
+class FisheyeStereoResult(C.Structure):
+    """``osh_fisheye_stereo_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("left_to_right", c_int32_p), ("right_to_left", c_int32_p), ("depth", c_float_p), ("p3d", c_float_p),
+                ("best_right", c_int32_p), ("best_dist", c_int32_p), ("second_dist", c_int32_p), ("cos_parallax", c_float_p),
+                ("stage", c_uint8_p)]
+
+
+class Kb8Rig(C.Structure):
+    """``osh_kb8_rig`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("cam1", C.c_float * 8), ("cam2", C.c_float * 8), ("precision1", C.c_float), ("precision2", C.c_float),
+                ("R12", C.c_float * 9), ("t12", C.c_float * 3)]
+
+
+(OSH_FSTEREO_OUTSIDE, OSH_FSTEREO_NO_PAIR, OSH_FSTEREO_RATIO, OSH_FSTEREO_PARALLAX, OSH_FSTEREO_BEHIND_1, OSH_FSTEREO_BEHIND_2,
+ OSH_FSTEREO_REPROJ_1, OSH_FSTEREO_REPROJ_2, OSH_FSTEREO_DEPTH, OSH_FSTEREO_ACCEPTED) = range(10)
+OSH_FSTEREO_NO_COS = -2.0
+
+
 def ptr(a, typ):
     """Pointer of ctypes type `typ` to the data of numpy array `a` (None -> NULL)."""
     if a is None:
@@ -349,6 +382,9 @@ _SIGNATURES = {
     "osh_orb_distance_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, c_int32_p]),
     "osh_orb_stereo_match": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(StereoFrame), C.POINTER(StereoResult)]),
     "osh_orb_stereo_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_fisheye_stereo_match": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FisheyeStereoFrame), C.POINTER(FisheyeStereoResult)]),
+    "osh_orb_fisheye_stereo_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_kb8_triangulate": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
     "osh_pgo_solve": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), C.POINTER(PgoResult)]),
     "osh_pgo_linearize": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), c_double_p, c_double_p, c_double_p]),
     "osh_pgo4_solve": (C.c_int, [C.c_void_p, C.POINTER(Pgo4Problem), C.POINTER(Pgo4Result)]),
@@ -377,7 +413,22 @@ class HostStereoInput(C.Structure):
     ]
 
 
+class HostFisheyeInput(C.Structure):
+    """``osh_host_fisheye_input`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [
+        ("n_left", C.c_int32), ("n_right", C.c_int32), ("mono_left", C.c_int32), ("mono_right", C.c_int32),
+        ("left_xy", c_float_p), ("left_octave", c_int32_p), ("left_desc", c_uint8_p),
+        ("right_xy", c_float_p), ("right_octave", c_int32_p), ("right_desc", c_uint8_p),
+        ("n_levels", C.c_int32), ("level_sigma2", c_float_p),
+        ("cam1", C.c_float * 8), ("cam2", C.c_float * 8), ("precision1", C.c_float), ("precision2", C.c_float),
+        ("Rlr", C.c_float * 9), ("tlr", C.c_float * 3),
+    ]
+
+
 _HOST_SIGNATURES = {
+    "osh_host_compute_fisheye_stereo_matches": (C.c_int, [C.POINTER(HostFisheyeInput), C.c_int32, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p]),
+    "osh_host_kb8_triangulate_cpu": (C.c_int, [C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
     "osh_host_graph_create": (C.c_void_p, [C.c_int32, c_int64_p, c_float_p, c_float_p, c_float_p, C.c_int32, C.c_int32, c_int64_p,
                                            c_float_p, C.c_int32, c_int32_p, c_int32_p, c_float_p, c_int32_p, C.c_int64, C.c_int32]),
     "osh_host_graph_destroy": (None, [C.c_void_p]),

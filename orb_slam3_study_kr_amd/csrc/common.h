@@ -44,10 +44,12 @@ T* attachment(osh_lba_ctx* c, LbaAttachSlot slot) {
   return static_cast<T*>(*p);
 }
 
-// osh_orb_stereo_match (stereo_device.hip) runs on an osh_orb_ctx the same way: the context's device (made current) and stream,
-// its one attachment pointer (handed to free_fn by osh_orb_destroy), and whether osh_orb_set_profiling switched timing on.
+// osh_orb_stereo_match (stereo_device.hip) and osh_orb_fisheye_stereo_match (fisheye_stereo_device.hip) run on an osh_orb_ctx the
+// same way: the context's device (made current) and stream, one attachment pointer each (handed to free_fn by osh_orb_destroy), and
+// whether osh_orb_set_profiling switched timing on.
+enum OrbAttachSlot { kOrbAttachStereo = 0, kOrbAttachFisheye = 1, kOrbAttachCount };
 int orb_stream(osh_orb_ctx* c, int* device, hipStream_t* stream);
-void** orb_attachment(osh_orb_ctx* c, void (*free_fn)(void*));
+void** orb_attachment(osh_orb_ctx* c, void (*free_fn)(void*), OrbAttachSlot slot = kOrbAttachStereo);
 bool orb_profiling(osh_orb_ctx* c);
 
 // OSH_ERR_DEVICE (with `what` in the message) if the last kernel launch failed.

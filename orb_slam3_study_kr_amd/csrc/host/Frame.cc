@@ -8,6 +8,10 @@
 //
 // Frame::ComputeStereoMatches (src/Frame.cc:816-986, called by the stereo constructor at :141) is a pack and a write-back around
 // osh_orb_stereo_match (csrc/stereo_device.hip): the row-band search, the SAD window, the parabola and the median cut run on the device.
+//
+// Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1131-1171, called by the rig constructor at :1110) is the same around
+// osh_orb_fisheye_stereo_match (csrc/fisheye_stereo_device.hip): the 2-nearest-neighbour search, Lowe's test and
+// KannalaBrandt8::TriangulateMatches run on the device.  mvuRight stays -1, as in the reference.
 #include <cstdio>
 #include <vector>
 #include "Frame.h"
@@ -120,6 +124,41 @@ void Frame::ComputeStereoMatches() {
   }
   mvuRight.swap(u_right);
   mvDepth.swap(depth);
+}
+
+void Frame::ComputeStereoFishEyeMatches() {
+  const size_t nl = mvKeys.size(), nr = mvKeysRight.size();
+  mvLeftToRightMatch = std::vector<int>(nl, -1);   // :1139-1144; the state in which every keypoint is unmatched
+  mvRightToLeftMatch = std::vector<int>(nr, -1);
+  mvDepth = std::vector<float>(nl, -1.0f);
+  mvuRight = std::vector<float>(nl, -1);
+  mvStereo3Dpoints = std::vector<Eigen::Vector3f>(nl);
+  mnCloseMPs = 0;
+  FisheyeStereoPack pk;
+  if (!PackStereoFishEyeMatches(*this, pk)) {
+    std::fprintf(stderr, "Frame::ComputeStereoFishEyeMatches: %s\n", pk.unsupported);
+    return;
+  }
+  if (nl == 0 && nr == 0) return;
+  osh_orb_ctx* ctx = HostMatcherContext();
+  if (!ctx) {
+    std::fprintf(stderr, "Frame::ComputeStereoFishEyeMatches: %s\n", osh_last_error());
+    return;
+  }
+  osh_fisheye_stereo_frame f;
+  pk.fill(f, *this);
+  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) f.Rlr[3 * r + c] = mRlr(r, c); f.tlr[r] = mtlr(r); }   // private members
+  std::vector<int32_t> l2r(nl), r2l(nr);
+  std::vector<float> depth(nl), p3d(nl * 3);
+  osh_fisheye_stereo_result res{l2r.data(), r2l.data(), depth.data(), p3d.data(), nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (osh_orb_fisheye_stereo_match(ctx, 1, &f, &res) != OSH_OK) {
+    std::fprintf(stderr, "Frame::ComputeStereoFishEyeMatches: %s\n", osh_last_error());
+    return;
+  }
+  mvLeftToRightMatch.assign(l2r.begin(), l2r.end());
+  mvRightToLeftMatch.assign(r2l.begin(), r2l.end());
+  mvDepth.swap(depth);
+  for (size_t i = 0; i < nl; ++i) mvStereo3Dpoints[i] = Eigen::Vector3f(p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]);
 }
 
 bool Frame::isInFrustum(MapPoint* pMP, float viewingCosLimit) {

@@ -530,4 +530,45 @@ inline bool PackStereoMatches(const Frame& F, StereoPack& pk) {
   levels(pl, pk.left_pyramid); levels(pr, pk.right_pyramid);
   return true;
 }
+
+// The frame Frame::ComputeStereoFishEyeMatches (Frame.cc) hands to osh_orb_fisheye_stereo_match, all but Rlr / tlr: mRlr and mtlr
+// are private members of Frame, so the member function fills those itself.  False (with `unsupported`) when
+// the cameras are not a KannalaBrandt8 pair or the frame's members do not fit together.
+struct FisheyeStereoPack {
+  std::vector<float> left_xy, right_xy;
+  std::vector<int32_t> left_octave, right_octave;
+  std::vector<uint8_t> left_desc, right_desc;
+  const char* unsupported = nullptr;
+  void fill(osh_fisheye_stereo_frame& f, const Frame& F) const {
+    f.n_left = (int32_t)left_octave.size(); f.n_right = (int32_t)right_octave.size();
+    f.mono_left = F.monoLeft; f.mono_right = F.monoRight;
+    f.left_xy = left_xy.data(); f.left_octave = left_octave.data(); f.left_desc = left_desc.data();
+    f.right_xy = right_xy.data(); f.right_octave = right_octave.data(); f.right_desc = right_desc.data();
+    f.n_levels = (int32_t)F.mvLevelSigma2.size(); f.level_sigma2 = F.mvLevelSigma2.data();
+    for (int k = 0; k < 8; ++k) { f.cam1[k] = F.mpCamera->getParameter(k); f.cam2[k] = F.mpCamera2->getParameter(k); }
+    f.precision1 = static_cast<KannalaBrandt8*>(F.mpCamera)->GetPrecision();
+    f.precision2 = static_cast<KannalaBrandt8*>(F.mpCamera2)->GetPrecision();
+  }
+};
+inline bool PackStereoFishEyeMatches(const Frame& F, FisheyeStereoPack& pk) {
+  if (!F.mpCamera || !F.mpCamera2 || F.mpCamera->GetType() != GeometricCamera::CAM_FISHEYE || F.mpCamera2->GetType() != GeometricCamera::CAM_FISHEYE) {
+    pk.unsupported = "the cameras are not a KannalaBrandt8 (CAM_FISHEYE) pair"; return false;
+  }
+  const size_t nl = F.mvKeys.size(), nr = F.mvKeysRight.size();
+  if (F.monoLeft < 0 || (size_t)F.monoLeft > nl || F.monoRight < 0 || (size_t)F.monoRight > nr) { pk.unsupported = "monoLeft / monoRight outside the keypoints"; return false; }
+  if ((size_t)F.mDescriptors.rows < nl || (size_t)F.mDescriptorsRight.rows < nr || (nl && F.mDescriptors.cols != 32) || (nr && F.mDescriptorsRight.cols != 32)) {
+    pk.unsupported = "descriptor matrices do not match the keypoints"; return false;
+  }
+  if (F.mvLevelSigma2.empty()) { pk.unsupported = "mvLevelSigma2 is empty"; return false; }
+  auto keys = [](const std::vector<cv::KeyPoint>& k, const cv::Mat& D, std::vector<float>& xy, std::vector<int32_t>& oct, std::vector<uint8_t>& desc) {
+    xy.resize(k.size() * 2); oct.resize(k.size()); desc.resize(k.size() * 32);
+    for (size_t i = 0; i < k.size(); ++i) {
+      xy[2 * i] = k[i].pt.x; xy[2 * i + 1] = k[i].pt.y; oct[i] = k[i].octave;
+      std::copy(D.ptr<uint8_t>((int)i), D.ptr<uint8_t>((int)i) + 32, &desc[32 * i]);
+    }
+  };
+  keys(F.mvKeys, F.mDescriptors, pk.left_xy, pk.left_octave, pk.left_desc);
+  keys(F.mvKeysRight, F.mDescriptorsRight, pk.right_xy, pk.right_octave, pk.right_desc);
+  return true;
+}
 }  // namespace ORB_SLAM3

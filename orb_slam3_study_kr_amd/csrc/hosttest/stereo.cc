@@ -1,7 +1,9 @@
 // stereo.cc -- osh_host_pack_stereo / osh_host_compute_stereo_matches / osh_host_stereo_restatement (include/orbslam3_hip_host.h):
 // Frame::ComputeStereoMatches and its pack on a stand-in Frame built from flat arrays, whose pyramid levels are views into bordered
 // images like the reference's, and a plain single-thread C++ restatement of src/Frame.cc:816-986 (the CPU baseline of
-// profiles/stereo_timing.py and the checker of long runs).  Test library only.
+// profiles/stereo_timing.py and the checker of long runs).  osh_host_compute_fisheye_stereo_matches drives
+// Frame::ComputeStereoFishEyeMatches on a stand-in rig Frame; osh_host_kb8_triangulate_cpu runs the device's
+// csrc/kb8_triangulate.h on the host.  Test library only.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -14,6 +16,7 @@
 #include "Frame.h"
 #include "ORBextractor.h"
 #include "host_pack.h"
+#include "../kb8_triangulate.h"
 #include "orbslam3_hip.h"
 #include "orbslam3_hip_host.h"
 
@@ -246,5 +249,55 @@ extern "C" int osh_host_stereo_restatement(const osh_host_stereo_input* in, floa
   }
   if (undefined) for (int k = 0; k < 4; ++k) undefined[k] = undef[k];
   if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+// ---- Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1131-1171)
+extern "C" int osh_host_compute_fisheye_stereo_matches(const osh_host_fisheye_input* in, int32_t camera2_pinhole, int32_t* left_to_right,
+                                                       int32_t* right_to_left, float* depth, float* p3d, float* u_right) {
+  if (!in || in->n_left < 0 || in->n_right < 0 || in->n_levels < 0) return -1;
+  Frame F;
+  auto keys = [](int n, const float* xy, const int32_t* oct, const uint8_t* desc, std::vector<cv::KeyPoint>& k, cv::Mat& D) {
+    k.resize(n);
+    D = cv::Mat(n, 32);
+    for (int i = 0; i < n; ++i) {
+      k[i].pt.x = xy[2 * i]; k[i].pt.y = xy[2 * i + 1]; k[i].octave = oct[i];
+      std::memcpy(D.ptr<uint8_t>(i), desc + 32 * (size_t)i, 32);
+    }
+  };
+  keys(in->n_left, in->left_xy, in->left_octave, in->left_desc, F.mvKeys, F.mDescriptors);
+  keys(in->n_right, in->right_xy, in->right_octave, in->right_desc, F.mvKeysRight, F.mDescriptorsRight);
+  F.Nleft = in->n_left; F.Nright = in->n_right; F.N = in->n_left + in->n_right;
+  F.monoLeft = in->mono_left; F.monoRight = in->mono_right;
+  if (in->n_levels) F.mvLevelSigma2.assign(in->level_sigma2, in->level_sigma2 + in->n_levels);
+  F.mnScaleLevels = in->n_levels;
+  KannalaBrandt8 cam1(std::vector<float>(in->cam1, in->cam1 + 8), in->precision1), cam2(std::vector<float>(in->cam2, in->cam2 + 8), in->precision2);
+  Pinhole pin(std::vector<float>(in->cam2, in->cam2 + 4));
+  F.mpCamera = &cam1;
+  F.mpCamera2 = camera2_pinhole ? static_cast<GeometricCamera*>(&pin) : &cam2;
+  Eigen::Matrix3f Rlr; Eigen::Vector3f tlr;
+  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) Rlr(r, c) = in->Rlr[3 * r + c]; tlr(r) = in->tlr[r]; }
+  F.SetRelativePoseTlr(Rlr, tlr);   // :1102-1105
+  F.ComputeStereoFishEyeMatches();
+  const size_t nl = (size_t)in->n_left, nr = (size_t)in->n_right;
+  if (F.mvLeftToRightMatch.size() != nl || F.mvRightToLeftMatch.size() != nr || F.mvDepth.size() != nl || F.mvStereo3Dpoints.size() != nl ||
+      F.mvuRight.size() != nl) return -2;
+  if (left_to_right) std::copy(F.mvLeftToRightMatch.begin(), F.mvLeftToRightMatch.end(), left_to_right);
+  if (right_to_left) std::copy(F.mvRightToLeftMatch.begin(), F.mvRightToLeftMatch.end(), right_to_left);
+  if (depth) std::copy(F.mvDepth.begin(), F.mvDepth.end(), depth);
+  if (u_right) std::copy(F.mvuRight.begin(), F.mvuRight.end(), u_right);
+  if (p3d) for (size_t i = 0; i < nl; ++i) for (int k = 0; k < 3; ++k) p3d[3 * i + k] = F.mvStereo3Dpoints[i](k);
+  return 0;
+}
+
+extern "C" int osh_host_kb8_triangulate_cpu(int32_t n, const osh_kb8_rig* rig, const float* xy1, const float* xy2, const float* sigma1,
+                                            const float* sigma2, float* ret, float* p3d, float* cos_parallax) {
+  if (n < 0 || !rig || (n && (!xy1 || !xy2 || !sigma1 || !sigma2 || !ret || !p3d || !cos_parallax))) return -1;
+  osh::Kb8Rig g;
+  std::memcpy(g.cam1, rig->cam1, sizeof g.cam1); std::memcpy(g.cam2, rig->cam2, sizeof g.cam2);
+  g.prec1 = rig->precision1; g.prec2 = rig->precision2;
+  std::memcpy(g.R12, rig->R12, sizeof g.R12); std::memcpy(g.t12, rig->t12, sizeof g.t12);
+  for (int i = 0; i < n; ++i)
+    ret[i] = osh::kb8_triangulate_match(g, xy1[2 * i], xy1[2 * i + 1], xy2[2 * i], xy2[2 * i + 1], sigma1[i], sigma2[i], p3d + 3 * (size_t)i, cos_parallax + i);
   return 0;
 }

@@ -546,8 +546,8 @@ struct osh_orb_ctx {
   std::vector<float> h_fin, h_fout;
   OrbView v{};
   bool uploaded = false, matched = false, windowed = false, grid = false;
-  void* attach = nullptr;                 // state of osh_orb_stereo_match (stereo_device.hip)
-  void (*attach_free)(void*) = nullptr;
+  void* attach[kOrbAttachCount] = {};     // state of osh_orb_stereo_match (stereo_device.hip) and of fisheye_stereo_device.hip
+  void (*attach_free[kOrbAttachCount])(void*) = {};
 };
 
 int osh::orb_stream(osh_orb_ctx* c, int* device, hipStream_t* stream) {
@@ -556,10 +556,10 @@ int osh::orb_stream(osh_orb_ctx* c, int* device, hipStream_t* stream) {
   *device = c->device; *stream = c->stream;
   return OSH_OK;
 }
-void** osh::orb_attachment(osh_orb_ctx* c, void (*free_fn)(void*)) {
+void** osh::orb_attachment(osh_orb_ctx* c, void (*free_fn)(void*), OrbAttachSlot slot) {
   if (!c) return nullptr;
-  c->attach_free = free_fn;
-  return &c->attach;
+  c->attach_free[slot] = free_fn;
+  return &c->attach[slot];
 }
 bool osh::orb_profiling(osh_orb_ctx* c) { return c && c->timer.enabled; }
 
@@ -586,7 +586,8 @@ extern "C" void osh_orb_destroy(osh_orb_ctx* c) {
                     &c->d_claim, &c->d_owner[0], &c->d_owner[1], &c->d_pre, &c->d_blocks, &c->d_cur[0], &c->d_cur[1], &c->d_cur[2], &c->d_cur[3],
                     &c->d_cur[4], &c->d_state, &c->d_assign, &c->d_nmatch, &c->d_fin, &c->d_fout};
   for (DevBuf* b : bufs) b->release();
-  if (c->attach && c->attach_free) { c->attach_free(c->attach); c->attach = nullptr; }
+  for (int k = 0; k < kOrbAttachCount; ++k)
+    if (c->attach[k] && c->attach_free[k]) { c->attach_free[k](c->attach[k]); c->attach[k] = nullptr; }
   c->timer.destroy();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

@@ -196,6 +196,30 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_stereo_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_stereo_get_times", self.lib)
         return ms
 
+    def fisheye_stereo_match(self, frames, stages: bool = False) -> list:
+        """Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1131-1171) for a batch of synth_fisheye.FisheyeFrame in one
+        osh_orb_fisheye_stereo_match call: per frame a dict with left_to_right / right_to_left / depth / p3d [n, 3], and with
+        `stages` also best_right, best_dist, second_dist, cos_parallax, stage."""
+        cf, cr, _keep, outs = fisheye_stereo_args(frames, stages)
+        capi.check(self.lib.osh_orb_fisheye_stereo_match(self.ctx, len(frames), cf, cr), "osh_orb_fisheye_stereo_match", self.lib)
+        return outs
+
+    def fisheye_stereo_times(self):
+        """Host-clock phases (ms) of the last fisheye_stereo_match under set_profiling(True): staging, upload, kernels, download."""
+        ms = np.zeros(4, dtype=np.float64)
+        capi.check(self.lib.osh_orb_fisheye_stereo_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_fisheye_stereo_get_times", self.lib)
+        return ms
+
+    def kb8_triangulate(self, rig: "capi.Kb8Rig", xy1, xy2, sigma1, sigma2) -> dict:
+        """KannalaBrandt8::TriangulateMatches for explicit keypoint pairs (osh_kb8_triangulate): ret [n], p3d [n, 3], cos_parallax [n]."""
+        a = kb8_pairs(xy1, xy2, sigma1, sigma2)
+        n = a[0].shape[0]
+        out = dict(ret=np.zeros(n, np.float32), p3d=np.zeros((n, 3), np.float32), cos_parallax=np.zeros(n, np.float32))
+        capi.check(self.lib.osh_kb8_triangulate(self.ctx, n, C.byref(rig), *[capi.ptr(x, capi.c_float_p) for x in a],
+                                                capi.ptr(out["ret"], capi.c_float_p), capi.ptr(out["p3d"], capi.c_float_p),
+                                                capi.ptr(out["cos_parallax"], capi.c_float_p)), "osh_kb8_triangulate", self.lib)
+        return out
+
     def set_profiling(self, enable: bool):
         capi.check(self.lib.osh_orb_set_profiling(self.ctx, int(enable)), "osh_orb_set_profiling", self.lib)
 
@@ -215,6 +239,65 @@ def stereo_args(frames, stages: bool = False, borders=None):
     """The osh_stereo_frame / osh_stereo_result arrays of OrbMatcher.stereo_match for repeated calls: (frames, results, the arrays
     that keep their pointers alive, the per-frame dicts of output arrays)."""
     return OrbMatcher._stereo_args(frames, stages, borders)
+
+
+def fisheye_stereo_args(frames, stages: bool = False):
+    """The osh_fisheye_stereo_frame / osh_fisheye_stereo_result arrays of OrbMatcher.fisheye_stereo_match for repeated calls:
+    (frames, results, the arrays that keep their pointers alive, the per-frame dicts of output arrays)."""
+    n_frames = len(frames)
+    cf = (capi.FisheyeStereoFrame * max(n_frames, 1))()
+    cr = (capi.FisheyeStereoResult * max(n_frames, 1))()
+    keep, outs = [], []
+    c = np.ascontiguousarray
+    for k, fr in enumerate(frames):
+        a = dict(lxy=c(fr.left_xy, np.float32), loct=c(fr.left_octave, np.int32), ldesc=c(fr.left_desc, np.uint8),
+                 rxy=c(fr.right_xy, np.float32), roct=c(fr.right_octave, np.int32), rdesc=c(fr.right_desc, np.uint8),
+                 sig=c(fr.level_sigma2, np.float32))
+        f = cf[k]
+        fill_fisheye_frame(f, fr, a)
+        nl, nr = f.n_left, f.n_right
+        o = dict(left_to_right=np.zeros(nl, np.int32), right_to_left=np.zeros(nr, np.int32), depth=np.zeros(nl, np.float32),
+                 p3d=np.zeros((nl, 3), np.float32))
+        cr[k].left_to_right, cr[k].right_to_left = capi.ptr(o["left_to_right"], capi.c_int32_p), capi.ptr(o["right_to_left"], capi.c_int32_p)
+        cr[k].depth, cr[k].p3d = capi.ptr(o["depth"], capi.c_float_p), capi.ptr(o["p3d"], capi.c_float_p)
+        if stages:
+            o.update(best_right=np.zeros(nl, np.int32), best_dist=np.zeros(nl, np.int32), second_dist=np.zeros(nl, np.int32),
+                     cos_parallax=np.zeros(nl, np.float32), stage=np.zeros(nl, np.uint8))
+            for name in ("best_right", "best_dist", "second_dist"):
+                setattr(cr[k], name, capi.ptr(o[name], capi.c_int32_p))
+            cr[k].cos_parallax, cr[k].stage = capi.ptr(o["cos_parallax"], capi.c_float_p), capi.ptr(o["stage"], capi.c_uint8_p)
+        keep.append(a)
+        outs.append(o)
+    return cf, cr, keep, outs
+
+
+def fill_fisheye_frame(f, fr, a):
+    """The fields capi.FisheyeStereoFrame and capi.HostFisheyeInput share, from a synth_fisheye.FisheyeFrame and its contiguous arrays."""
+    f.n_left, f.n_right, f.mono_left, f.mono_right = a["loct"].shape[0], a["roct"].shape[0], int(fr.mono_left), int(fr.mono_right)
+    f.left_xy, f.left_octave, f.left_desc = capi.ptr(a["lxy"], capi.c_float_p), capi.ptr(a["loct"], capi.c_int32_p), capi.ptr(a["ldesc"], capi.c_uint8_p)
+    f.right_xy, f.right_octave, f.right_desc = capi.ptr(a["rxy"], capi.c_float_p), capi.ptr(a["roct"], capi.c_int32_p), capi.ptr(a["rdesc"], capi.c_uint8_p)
+    f.n_levels, f.level_sigma2 = a["sig"].shape[0], capi.ptr(a["sig"], capi.c_float_p)
+    f.cam1[:] = [float(x) for x in np.asarray(fr.cam1, np.float32)]
+    f.cam2[:] = [float(x) for x in np.asarray(fr.cam2, np.float32)]
+    f.precision1, f.precision2 = float(fr.precision1), float(fr.precision2)
+    f.Rlr[:] = [float(x) for x in np.asarray(fr.Rlr, np.float32).reshape(9)]
+    f.tlr[:] = [float(x) for x in np.asarray(fr.tlr, np.float32)]
+
+
+def kb8_rig(cam1, cam2, precision1, precision2, R12, t12) -> "capi.Kb8Rig":
+    g = capi.Kb8Rig()
+    g.cam1[:] = [float(x) for x in np.asarray(cam1, np.float32)]
+    g.cam2[:] = [float(x) for x in np.asarray(cam2, np.float32)]
+    g.precision1, g.precision2 = float(precision1), float(precision2)
+    g.R12[:] = [float(x) for x in np.asarray(R12, np.float32).reshape(9)]
+    g.t12[:] = [float(x) for x in np.asarray(t12, np.float32)]
+    return g
+
+
+def kb8_pairs(xy1, xy2, sigma1, sigma2):
+    """The four input arrays of osh_kb8_triangulate, contiguous float32."""
+    f32 = lambda x, shape: np.ascontiguousarray(np.asarray(x, np.float32).reshape(shape))
+    return f32(xy1, (-1, 2)), f32(xy2, (-1, 2)), f32(sigma1, (-1,)), f32(sigma2, (-1,))
 
 
 def accept_local_points(res: dict, pair_index: int, nn_ratio: float = 0.8, th_high: int = 100) -> np.ndarray:
