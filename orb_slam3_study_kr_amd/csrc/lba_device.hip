@@ -457,7 +457,8 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(BatchView bv) {
 // image for symmetric items; the accumulators stay in registers across the chunks of the item.  At the end every live
 // pose pair (sa, sb) is written as one 6x6 contribution; k_schur_reduce sums them in plan order.
 //   SYM: X == Y, only the tiles on and above the diagonal; owns the pose side and the rhs term.
-//   cross items (parts a < b of a landmark with more than 8 optimisable observers): a second image for the Y poses.
+//   cross items (parts a < b of a landmark with more than 8 optimisable observers): a second image for the Y poses; with at most
+//   4 of them (pinhole) that image is filled for two chunks at a time by one 16 x 4 pass (cross_pairs).
 //   mode 0: pose side only (the first round of optimize(): computeLambdaInit needs Hpp before any Schur product)
 //   mode 1: Schur products, and the pose side when this round opened an iteration other than the first
 // --------------------------------------------------------------------------------------------
@@ -635,7 +636,9 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
       }
     };
     auto multiply_cross = [&]() {
-      // cross items keep run-time tile tests: nine instantiations cost registers for no gain
+      // Cross items that come here (fisheye, or more than 4 column poses: parts b of tracks with 13+ observers) keep run-time tile
+      // tests: nine instantiations cost registers for no gain.  Pinhole cross items of at most 4 column poses -- every cross item of
+      // the headline window -- take cross_pairs() below: TX = 3, TY = 1 or 2 at compile time.
 #pragma unroll
       for (int ks = 0; ks < KST; ++ks) {
         double a[3], b[3];
@@ -740,6 +743,147 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
       }
     }
   };
+  // Pinhole cross items of at most 4 column poses (part b of a 9-12-observer track; on the headline window all of them: 85 items,
+  // 465 chunks, an edge in 0.29 of the 8 x 8 column lane slots).  The row side stays one 8 x 8 pass per chunk; the column side is ONE
+  // 16 x 4 pass for a PAIR of chunks: lane (l, s) = landmark l of 16, column slot s of 4, rows 6 s + r of the 24 x 49 column image (in the 48 x 25 doubles of shB), whose
+  // columns 0..23 belong to the first chunk of the pair and 24..47 to the second.  The k steps of a chunk read the same (landmark,
+  // component) columns in the same order as with one 8 x 8 column pass per chunk, so every Schur product keeps its bits.  TX is 3 (part
+  // a of such a track has 8 poses), TY 1 or 2: the loop is instantiated for the two values of TY and dispatched once per item.
+  auto cross_pairs = [&](auto tyc) __attribute__((always_inline)) {
+    constexpr int TYc = decltype(tyc)::value;
+    constexpr int KS = 3 * kSiLm + 1, KSB = 3 * 16 + 1, KST = (3 * kSiLm) / 4;
+    static_assert(16 * TYc <= 32 && kSiRows * KS <= sizeof(shA) / sizeof(double) && 24 * KSB <= sizeof(shB) / sizeof(double), "image sizes");
+    const int l = lane >> 3, s = lane & 7;      // row pass
+    const int lc = lane >> 2, sc = lane & 3;    // column pass
+    f64x4 acc[3][TYc];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < TYc; ++b) acc[a][b] = (f64x4){0.0, 0.0, 0.0, 0.0};
+
+    // Software pipeline as in body(): row record two chunks ahead and row data one chunk ahead; the column records two PAIRS ahead and
+    // the column data of the next pair requested before the MFMAs of a pair's second chunk.  Every load unconditional on a clamped index.
+    struct SDat { double2 e[2]; double X[3]; double dl[9]; };
+    const int last_rec = it.n_lm - 1;
+    const size_t last_edge = (size_t)wd.edge_off + (size_t)max(wd.E - 1, 0);
+    auto edge_of = [&](const int4& ra, unsigned o) { return min((size_t)wd.edge_off + (size_t)(ra.y + (o != kAbsent ? (int)o : 0)), last_edge); };
+    auto row_slot = [&](const int4& ra) { return (unsigned)((((unsigned long long)(unsigned)ra.w << 32) | (unsigned)ra.z) >> (8 * s)) & 0xffu; };
+    auto col_slot = [&](const int4& rb) { return ((unsigned)rb.x >> (8 * sc)) & 0xffu; };   // slots 0..3: y_lo
+    auto load_row_rec = [&](int c0, int4& ra) { ra = *reinterpret_cast<const int4*>(recs + min(c0 + l, last_rec)); };
+    auto load_col_rec = [&](int p0, int4& ra, int4& rb) {
+      const int4* src = reinterpret_cast<const int4*>(recs + min(p0 + lc, last_rec));
+      ra = src[0]; rb = src[1];
+    };
+    auto load_dat = [&](const int4& ra, unsigned o, SDat& d) {
+      const double2* src = reinterpret_cast<const double2*>(bv.e_rec + edge_of(ra, o) * 4);
+      d.e[0] = src[0]; d.e[1] = src[1];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) d.X[k] = pts[(size_t)ra.x * 3 + k];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) d.dl[k] = DL[(size_t)ra.x * 9 + k];
+    };
+    // rows of W F of one edge -> six rows of an image (as side_rows of body())
+    auto wf_rows = [&](const double* ps, bool present, size_t ge, const SDat& d, double* row, int ks) __attribute__((always_inline)) {
+      double qt[7], cam[5], Rm[9];
+#pragma unroll
+      for (int k = 0; k < 7; ++k) qt[k] = ps[k];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) cam[k] = ps[7 + k];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) Rm[k] = ps[12 + k];
+      const double rec[4] = {d.e[0].x, d.e[0].y, d.e[1].x, d.e[1].y};
+      double Xc[3], Q[6], g[3], rho0;
+      win_edge_core<KB8>(wd, bv, ge, rec, qt, cam, Rm, d.X, Xc, Q, g, rho0);
+      // an empty slot computes on another edge's data: its result is discarded here (select, not multiply: it may be NaN)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) Q[k] = present ? Q[k] : 0.0;
+      double WF[18];
+      dev::core_WF<KB8>(Xc, Q, Rm, d.dl, WF);
+#pragma unroll
+      for (int r = 0; r < 6; ++r) { row[r * ks + 0] = WF[r * 3]; row[r * ks + 1] = WF[r * 3 + 1]; row[r * ks + 2] = WF[r * 3 + 2]; }
+    };
+    auto row_pass = [&](int c0, const int4& ra, const SDat& d) __attribute__((always_inline)) {
+      const unsigned o = (c0 + l) < it.n_lm ? row_slot(ra) : kAbsent;
+      wf_rows(shPose + s * kPoseRec, o != kAbsent, edge_of(ra, o), d, shA + (6 * s) * KS + 3 * l, KS);
+    };
+    auto col_pass = [&](int p0, const int4& ra, const int4& rb, const SDat& d) __attribute__((always_inline)) {
+      const unsigned o = (p0 + lc) < it.n_lm ? col_slot(rb) : kAbsent;
+      wf_rows(shPose + (8 + sc) * kPoseRec, o != kAbsent, edge_of(ra, o), d, shB + (6 * sc) * KSB + 3 * lc, KSB);
+    };
+    // the k steps of one chunk: A columns 0..23, B columns cb..cb + 23 (cb = 0 / 24: first / second chunk of the pair)
+    auto multiply = [&](int cb) __attribute__((always_inline)) {
+#pragma unroll
+      for (int ks = 0; ks < KST; ++ks) {
+        double a[3], b[TYc];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) a[t] = shA[(16 * t + mrow) * KS + 4 * ks + mk];
+#pragma unroll
+        for (int t = 0; t < TYc; ++t) b[t] = shB[min(16 * t + mrow, 23) * KSB + cb + 4 * ks + mk];   // (rows 24..31: columns of D nobody stores)
+#pragma unroll
+        for (int ti = 0; ti < 3; ++ti)
+#pragma unroll
+          for (int tj = 0; tj < TYc; ++tj) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[tj], acc[ti][tj], 0, 0, 0);
+        if (ks & 1) __builtin_amdgcn_sched_barrier(0);   // operands of two k-steps in flight at most (the prefetched chunks need the registers)
+      }
+    };
+    int4 rc, rn, cc0, cc1, cn0, cn1;
+    SDat rd, cd;
+    load_row_rec(0, rc);
+    load_col_rec(0, cc0, cc1);
+    load_row_rec(kSiLm, rn);
+    load_col_rec(2 * kSiLm, cn0, cn1);
+    load_dat(rc, row_slot(rc), rd);
+    load_dat(cc0, col_slot(cc1), cd);
+    wave_sync();   // the staged poses are visible
+    int p0 = 0;
+    for (; p0 + kSiLm < it.n_lm; p0 += 2 * kSiLm) {     // pairs of chunks p0, p0 + 8
+      wave_sync();                                      // the previous chunk's MFMA reads are done
+      col_pass(p0, cc0, cc1, cd);                       // both chunks' column rows -> shB (consumes cd)
+      row_pass(p0, rc, rd);                             // (consumes rd)
+      wave_sync();
+      rc = rn;
+      load_dat(rc, row_slot(rc), rd);                   // rows of chunk p0 + 8: in flight during the MFMAs below
+      load_row_rec(p0 + 2 * kSiLm, rn);
+      multiply(0);
+      wave_sync();
+      row_pass(p0 + kSiLm, rc, rd);
+      wave_sync();
+      rc = rn; cc0 = cn0; cc1 = cn1;
+      load_dat(rc, row_slot(rc), rd);                   // rows of chunk p0 + 16 and columns of the pair that starts there
+      load_dat(cc0, col_slot(cc1), cd);
+      load_row_rec(p0 + 3 * kSiLm, rn);
+      load_col_rec(p0 + 4 * kSiLm, cn0, cn1);
+      multiply(3 * kSiLm);
+    }
+    if (p0 < it.n_lm) {                                 // an odd number of chunks: the last one alone (columns 24..47 are written, not read)
+      wave_sync();
+      col_pass(p0, cc0, cc1, cd);
+      row_pass(p0, rc, rd);
+      wave_sync();
+      multiply(0);
+    }
+    // contributions: lane holds D[row = (lane >> 4) + 4 reg][col = lane & 15] of each tile
+#pragma unroll
+    for (int ti = 0; ti < 3; ++ti)
+#pragma unroll
+      for (int tj = 0; tj < TYc; ++tj) {
+        const int C = 16 * tj + (lane & 15);
+        const int sb = C / 6, cc = C - 6 * sb;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int R = 16 * ti + (lane >> 4) + 4 * reg;
+          const int sa = R / 6, rr = R - 6 * sa;
+          const int slot = shP[sa * 8 + sb];
+          if (slot >= 0) bv.contrib[(size_t)slot * 36 + rr * 6 + cc] = acc[ti][tj][reg];
+        }
+      }
+  };
+  if constexpr (!SYM && !KB8) {
+    if (nx > 5 && ny <= 4) {
+      if (ny <= 2) cross_pairs(integral_constant<int, 1>{}); else cross_pairs(integral_constant<int, 2>{});
+      return;
+    }
+  }
   if constexpr (SYM && !KB8) {
     if (nx <= 4) body(integral_constant<int, 16>{}, integral_constant<int, 4>{});
     else if (nx == 5) body(integral_constant<int, 12>{}, integral_constant<int, 5>{});
