@@ -45,11 +45,11 @@ T* attachment(osh_lba_ctx* c, LbaAttachSlot slot) {
 }
 
 // osh_orb_stereo_match (stereo_device.hip) and osh_orb_fisheye_stereo_match (fisheye_stereo_device.hip) run on an osh_orb_ctx the
-// same way: the context's device (made current) and stream, one attachment pointer each (handed to free_fn by osh_orb_destroy), and
-// whether osh_orb_set_profiling switched timing on.
+// same way: the context's device (made current) and stream, one attachment pointer each (handed to free_fn by osh_orb_destroy;
+// orb_state of orb_stage.h is the typed fetch-or-create), and whether osh_orb_set_profiling switched timing on.
 enum OrbAttachSlot { kOrbAttachStereo = 0, kOrbAttachFisheye = 1, kOrbAttachCount };
 int orb_stream(osh_orb_ctx* c, int* device, hipStream_t* stream);
-void** orb_attachment(osh_orb_ctx* c, void (*free_fn)(void*), OrbAttachSlot slot = kOrbAttachStereo);
+void** orb_attachment(osh_orb_ctx* c, void (*free_fn)(void*), OrbAttachSlot slot);
 bool orb_profiling(osh_orb_ctx* c);
 
 // OSH_ERR_DEVICE (with `what` in the message) if the last kernel launch failed.
@@ -124,6 +124,7 @@ template <class T>
 struct Section {
   size_t off;
   T* in(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+  const T* in(const void* base) const { return reinterpret_cast<const T*>(static_cast<const char*>(base) + off); }
 };
 // Sections laid out one after another, each 256-byte aligned and at least 8 bytes long (an empty one still has an address of its own).
 struct Layout {

@@ -14,14 +14,12 @@
 #include "common.h"
 #include "kb8_triangulate.h"
 #include "orb_hamming.h"
-#include <chrono>
+#include "orb_stage.h"
 #include <cmath>
 #include <vector>
 
 namespace osh {
 
-constexpr int kFPosBits = 22;
-constexpr unsigned kFPosMask = (1u << kFPosBits) - 1;
 constexpr unsigned kFNone = 0xFFFFFFFFu;
 constexpr int kFBlock = 64;    // left keypoints per block (one per lane of one wavefront)
 constexpr int kFTile = 256;    // right keypoints staged in LDS per tile: 8 KiB of descriptors
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(kFBlock) void k_fstereo_knn(FStereoView v) {
       else if (d < d2) d2 = d;
     }
   }
-  if (valid) v.part[(size_t)blockIdx.z * v.n_left_total + gl] = make_uint2(d1 == kFNone ? kFNone : (d1 << kFPosBits) | i1, d2);
+  if (valid) v.part[(size_t)blockIdx.z * v.n_left_total + gl] = make_uint2(d1 == kFNone ? kFNone : (d1 << kPosBits) | i1, d2);
 }
 
 // grid = (ceil(max n_left / 64), n_frames)
@@ -89,8 +87,8 @@ __global__ __launch_bounds__(kFBlock) void k_fstereo_tri(FStereoView v) {
     for (int z = 0; z < v.n_split; ++z) {              // ascending slices: a later equal distance never displaces an earlier one
       const uint2 p = v.part[(size_t)z * v.n_left_total + gl];
       if (p.x == kFNone) continue;
-      const unsigned d = p.x >> kFPosBits;
-      if (d < d1) { d2 = d1; d1 = d; i1 = p.x & kFPosMask; }
+      const unsigned d = p.x >> kPosBits;
+      if (d < d1) { d2 = d1; d1 = d; i1 = p.x & kPosMask; }
       else if (d < d2) d2 = d;
       if (p.y < d2) d2 = p.y;
     }
@@ -157,18 +155,15 @@ static int fstereo_validate(int n_frames, const osh_fisheye_stereo_frame* frames
     if (f.n_left < 0 || f.n_right < 0) { set_error("frame %d: negative keypoint count", k); return OSH_ERR_INVALID; }
     if (f.mono_left < 0 || f.mono_left > f.n_left) { set_error("frame %d: mono_left %d outside [0, %d]", k, f.mono_left, f.n_left); return OSH_ERR_INVALID; }
     if (f.mono_right < 0 || f.mono_right > f.n_right) { set_error("frame %d: mono_right %d outside [0, %d]", k, f.mono_right, f.n_right); return OSH_ERR_INVALID; }
-    if (f.n_levels < 1 || f.n_levels > OSH_STEREO_MAX_LEVELS) { set_error("frame %d: n_levels %d outside [1, %d]", k, f.n_levels, OSH_STEREO_MAX_LEVELS); return OSH_ERR_INVALID; }
-    if ((unsigned)f.n_right > kFPosMask) { set_error("frame %d: n_right exceeds %u", k, kFPosMask); return OSH_ERR_UNSUPPORTED; }
+    OSH_TRY(validate_keypoint_sides(k, f, kPosMask));
     if (!f.level_sigma2) { set_error("frame %d: NULL level_sigma2", k); return OSH_ERR_INVALID; }
     if (f.n_left && (!f.left_xy || !f.left_octave || !f.left_desc || !r.left_to_right || !r.depth || !r.p3d)) { set_error("frame %d: NULL left keypoint or result array", k); return OSH_ERR_INVALID; }
     if (f.n_right && (!f.right_xy || !f.right_octave || !f.right_desc || !r.right_to_left)) { set_error("frame %d: NULL right keypoint or result array", k); return OSH_ERR_INVALID; }
     if (!all_finite(f.level_sigma2, (size_t)f.n_levels)) { set_error("frame %d: level_sigma2 entry not finite", k); return OSH_ERR_INVALID; }
     OSH_TRY(rig_validate("frame", k, f.cam1, f.cam2, f.precision1, f.precision2, f.Rlr, f.tlr));
     if (!all_finite(f.left_xy, (size_t)f.n_left * 2) || !all_finite(f.right_xy, (size_t)f.n_right * 2)) { set_error("frame %d: keypoint coordinate not finite", k); return OSH_ERR_INVALID; }
-    for (int i = 0; i < f.n_left; ++i)
-      if (f.left_octave[i] < 0 || f.left_octave[i] >= f.n_levels) { set_error("frame %d: left octave %d outside [0, %d)", k, f.left_octave[i], f.n_levels); return OSH_ERR_INVALID; }
-    for (int i = 0; i < f.n_right; ++i)
-      if (f.right_octave[i] < 0 || f.right_octave[i] >= f.n_levels) { set_error("frame %d: right octave %d outside [0, %d)", k, f.right_octave[i], f.n_levels); return OSH_ERR_INVALID; }
+    OSH_TRY(validate_octaves(k, "left", f.left_octave, f.n_left, f.n_levels));
+    OSH_TRY(validate_octaves(k, "right", f.right_octave, f.n_right, f.n_levels));
   }
   return OSH_OK;
 }
@@ -179,20 +174,13 @@ static void fill_rig(Kb8Rig& g, const float* cam1, const float* cam2, float prec
   std::memcpy(g.R12, R, sizeof g.R12); std::memcpy(g.t12, t, sizeof g.t12);
 }
 
-static FStereoState* fstereo_state(osh_orb_ctx* c) {
-  void** slot = orb_attachment(c, [](void* q) { delete static_cast<FStereoState*>(q); }, kOrbAttachFisheye);
-  if (!*slot) *slot = new FStereoState();
-  return static_cast<FStereoState*>(*slot);
-}
-
 }  // namespace osh
 
 using namespace osh;
 
 extern "C" int osh_orb_fisheye_stereo_match(osh_orb_ctx* c, int32_t n_frames, const osh_fisheye_stereo_frame* frames,
                                             const osh_fisheye_stereo_result* results) {
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
+  PhaseClock clock;
   if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_fisheye_stereo_match: bad arguments"); return OSH_ERR_INVALID; }
   OSH_TRY(fstereo_validate(n_frames, frames, results));   // the frames first: a refusal needs no context and no device
   if (!c) { set_error("osh_orb_fisheye_stereo_match: no context"); return OSH_ERR_INVALID; }
@@ -200,37 +188,32 @@ extern "C" int osh_orb_fisheye_stereo_match(osh_orb_ctx* c, int32_t n_frames, co
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(orb_stream(c, &device, &s));
-  FStereoState* st = fstereo_state(c);
-  const bool prof = orb_profiling(c);
+  FStereoState* st = orb_state<FStereoState>(c, kOrbAttachFisheye);
+  clock.profiling = orb_profiling(c);
 
-  size_t NL = 0, NR = 0;
-  int max_left = 0, max_query = 0, max_train = 0;
+  KeypointBatch kb;
+  OSH_TRY(kb.size("osh_orb_fisheye_stereo_match", n_frames, frames));
+  const size_t NL = kb.NL, NR = kb.NR;
+  int max_query = 0, max_train = 0;
   std::vector<FStereoFrameDev> fd(n_frames);
   for (int k = 0; k < n_frames; ++k) {
     const osh_fisheye_stereo_frame& f = frames[k];
     FStereoFrameDev& d = fd[k];
     std::memset(&d, 0, sizeof d);
     d.n_left = f.n_left; d.n_right = f.n_right; d.mono_left = f.mono_left; d.mono_right = f.mono_right;
-    d.left_base = (int)NL; d.right_base = (int)NR; d.n_levels = f.n_levels;
+    d.left_base = kb.base[k].left; d.right_base = kb.base[k].right; d.n_levels = f.n_levels;
     for (int l = 0; l < OSH_STEREO_MAX_LEVELS; ++l) d.sigma2[l] = l < f.n_levels ? f.level_sigma2[l] : 1.f;
     fill_rig(d.rig, f.cam1, f.cam2, f.precision1, f.precision2, f.Rlr, f.tlr);
-    NL += (size_t)f.n_left; NR += (size_t)f.n_right;
-    max_left = std::max(max_left, f.n_left);
     max_query = std::max(max_query, f.n_left - f.mono_left);
     max_train = std::max(max_train, f.n_right - f.mono_right);
-    if (NL > (size_t)INT_MAX / 16 || NR > (size_t)INT_MAX / 16) { set_error("osh_orb_fisheye_stereo_match: batch too large"); return OSH_ERR_UNSUPPORTED; }
   }
-  // slices of the right set, of at least one LDS tile (256 keypoints) each: a single 1000 + 1000 frame becomes 16 x 4 = 64
-  // one-wavefront blocks, which does not fill the 256 CUs (a frame is only 10^6 distances); a batch needs no slicing
+  // a single 1000 + 1000 frame becomes 16 x 4 = 64 one-wavefront blocks, which does not fill the 256 CUs (a frame is only 10^6 distances)
   const int qblocks = (max_query + kFBlock - 1) / kFBlock;
-  const long blocks = std::max<long>(1, (long)qblocks * n_frames);
-  int split = (int)std::min<long>(16, std::max<long>(1, (1024 + blocks - 1) / blocks));
-  split = std::min(split, std::max(1, (max_train + kFTile - 1) / kFTile));
+  const int split = right_set_slices(qblocks, n_frames, max_train, kFTile);
 
   Layout in, out, work;
   const auto s_frames = in.take<FStereoFrameDev>(n_frames);
-  const auto s_lxy = in.take<float2>(NL); const auto s_loct = in.take<int>(NL); const auto s_ldesc = in.take<uint4>(NL * 2);
-  const auto s_rxy = in.take<float2>(NR); const auto s_roct = in.take<int>(NR); const auto s_rdesc = in.take<uint4>(NR * 2);
+  kb.take(in);
   const auto o_l2r = out.take<int>(NL); const auto o_r2l = out.take<int>(NR); const auto o_depth = out.take<float>(NL);
   const auto o_p3d = out.take<float>(NL * 3); const auto o_br = out.take<int>(NL); const auto o_bd = out.take<int>(NL);
   const auto o_sd = out.take<int>(NL); const auto o_cos = out.take<float>(NL); const auto o_stage = out.take<unsigned char>(NL);
@@ -239,24 +222,10 @@ extern "C" int osh_orb_fisheye_stereo_match(osh_orb_ctx* c, int32_t n_frames, co
 
   char* h = st->call.host_in();
   std::memcpy(s_frames.in(h), fd.data(), sizeof(FStereoFrameDev) * n_frames);
-  for (int k = 0; k < n_frames; ++k) {
-    const osh_fisheye_stereo_frame& f = frames[k];
-    const FStereoFrameDev& d = fd[k];
-    if (f.n_left) {
-      std::memcpy(s_lxy.in(h) + d.left_base, f.left_xy, (size_t)f.n_left * 8);
-      std::memcpy(s_loct.in(h) + d.left_base, f.left_octave, (size_t)f.n_left * 4);
-      std::memcpy(s_ldesc.in(h) + (size_t)d.left_base * 2, f.left_desc, (size_t)f.n_left * 32);
-    }
-    if (f.n_right) {
-      std::memcpy(s_rxy.in(h) + d.right_base, f.right_xy, (size_t)f.n_right * 8);
-      std::memcpy(s_roct.in(h) + d.right_base, f.right_octave, (size_t)f.n_right * 4);
-      std::memcpy(s_rdesc.in(h) + (size_t)d.right_base * 2, f.right_desc, (size_t)f.n_right * 32);
-    }
-  }
-  const auto t1 = clk::now();
+  kb.stage(h, frames);
+  clock.mark();
   OSH_TRY(st->call.upload(s));
-  if (prof) OSH_HIP(hipStreamSynchronize(s));
-  const auto t2 = clk::now();
+  OSH_TRY(clock.mark_synced(s));
 
   char* dout = st->call.dev_out();
   if (NR) OSH_HIP(hipMemsetAsync(o_r2l.in(dout), 0xFF, NR * 4, s));   // -1: the floor of the atomicMax
@@ -265,46 +234,33 @@ extern "C" int osh_orb_fisheye_stereo_match(osh_orb_ctx* c, int32_t n_frames, co
     char* di = st->call.dev_in();
     v.n_frames = n_frames; v.n_split = split; v.n_left_total = NL;
     v.frames = s_frames.in(di);
-    v.lxy = s_lxy.in(di); v.loct = s_loct.in(di); v.ldesc = s_ldesc.in(di);
-    v.rxy = s_rxy.in(di); v.roct = s_roct.in(di); v.rdesc = s_rdesc.in(di);
+    kb.bind(v, di);
     v.part = w_part.in(st->call.dev_work());
     v.l2r = o_l2r.in(dout); v.r2l = o_r2l.in(dout); v.depth = o_depth.in(dout); v.p3d = o_p3d.in(dout);
     v.best_right = o_br.in(dout); v.best_dist = o_bd.in(dout); v.second_dist = o_sd.in(dout); v.cosp = o_cos.in(dout); v.stage = o_stage.in(dout);
     if (qblocks > 0 && max_train >= 2)
       hipLaunchKernelGGL(k_fstereo_knn, dim3((unsigned)qblocks, (unsigned)n_frames, (unsigned)split), dim3(kFBlock), 0, s, v);
-    hipLaunchKernelGGL(k_fstereo_tri, dim3((unsigned)((max_left + kFBlock - 1) / kFBlock), (unsigned)n_frames), dim3(kFBlock), 0, s, v);
+    hipLaunchKernelGGL(k_fstereo_tri, dim3((unsigned)((kb.max_left + kFBlock - 1) / kFBlock), (unsigned)n_frames), dim3(kFBlock), 0, s, v);
     OSH_TRY(launch_check("fisheye stereo match"));
   }
-  if (prof) OSH_HIP(hipStreamSynchronize(s));
-  const auto t3 = clk::now();
+  OSH_TRY(clock.mark_synced(s));
   OSH_TRY(st->call.download(s));
-  char* ho = st->call.host_out();
+  const char* ho = st->call.host_out();
   for (int k = 0; k < n_frames; ++k) {
     const osh_fisheye_stereo_result& r = results[k];
-    const FStereoFrameDev& d = fd[k];
-    const size_t n = (size_t)d.n_left, b = (size_t)d.left_base;
-    if (d.n_right) std::memcpy(r.right_to_left, o_r2l.in(ho) + d.right_base, (size_t)d.n_right * 4);
-    if (!n) continue;
-    std::memcpy(r.left_to_right, o_l2r.in(ho) + b, n * 4);
-    std::memcpy(r.depth, o_depth.in(ho) + b, n * 4);
-    std::memcpy(r.p3d, o_p3d.in(ho) + b * 3, n * 12);
-    if (r.best_right) std::memcpy(r.best_right, o_br.in(ho) + b, n * 4);
-    if (r.best_dist) std::memcpy(r.best_dist, o_bd.in(ho) + b, n * 4);
-    if (r.second_dist) std::memcpy(r.second_dist, o_sd.in(ho) + b, n * 4);
-    if (r.cos_parallax) std::memcpy(r.cos_parallax, o_cos.in(ho) + b, n * 4);
-    if (r.stage) std::memcpy(r.stage, o_stage.in(ho) + b, n);
+    const size_t n = (size_t)frames[k].n_left, b = (size_t)kb.base[k].left;
+    scatter(r.right_to_left, o_r2l, ho, (size_t)kb.base[k].right, (size_t)frames[k].n_right);
+    scatter(r.left_to_right, o_l2r, ho, b, n); scatter(r.depth, o_depth, ho, b, n); scatter(r.p3d, o_p3d, ho, b, n, 3);
+    scatter(r.best_right, o_br, ho, b, n); scatter(r.best_dist, o_bd, ho, b, n); scatter(r.second_dist, o_sd, ho, b, n);
+    scatter(r.cos_parallax, o_cos, ho, b, n); scatter(r.stage, o_stage, ho, b, n);
   }
-  const auto t4 = clk::now();
-  auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-  if (prof) { st->ms[0] = ms(t0, t1); st->ms[1] = ms(t1, t2); st->ms[2] = ms(t2, t3); st->ms[3] = ms(t3, t4); }
+  clock.mark();
+  clock.store(st->ms);
   return OSH_OK;
 }
 
 extern "C" int osh_orb_fisheye_stereo_get_times(osh_orb_ctx* c, double ms[4]) {
-  if (!c || !ms) { set_error("osh_orb_fisheye_stereo_get_times: bad arguments"); return OSH_ERR_INVALID; }
-  const FStereoState* st = fstereo_state(c);
-  for (int k = 0; k < 4; ++k) ms[k] = st->ms[k];
-  return OSH_OK;
+  return copy_times<FStereoState>("osh_orb_fisheye_stereo_get_times", c, kOrbAttachFisheye, ms);
 }
 
 extern "C" int osh_kb8_triangulate(osh_orb_ctx* c, int32_t n, const osh_kb8_rig* rig, const float* xy1, const float* xy2, const float* sigma1,
@@ -321,7 +277,7 @@ extern "C" int osh_kb8_triangulate(osh_orb_ctx* c, int32_t n, const osh_kb8_rig*
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(orb_stream(c, &device, &s));
-  FStereoState* st = fstereo_state(c);
+  FStereoState* st = orb_state<FStereoState>(c, kOrbAttachFisheye);
   const size_t N = (size_t)n;
   Layout in, out;
   const auto s_xy1 = in.take<float2>(N); const auto s_xy2 = in.take<float2>(N); const auto s_s1 = in.take<float>(N); const auto s_s2 = in.take<float>(N);

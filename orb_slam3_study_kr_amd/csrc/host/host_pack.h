@@ -480,19 +480,46 @@ void PackWeldingBA(KeyFrame* pMainKF, const std::vector<KeyFrame*>& vpAdjustKF, 
 void PackBundleAdjustment(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& vpMP, LbaPack& pk,
                           std::vector<bool>& vbNotIncludedMP);
 
-// The frame Frame::ComputeStereoMatches (Frame.cc) hands to osh_orb_stereo_match: keypoints and descriptors copied into flat arrays,
-// the pyramid levels referenced in place through ptr<uchar>(0) and step (a level is a view into a bordered image: its rows are
-// `step` bytes apart, never `cols`).  False (with `unsupported`) when the frame's members do not fit together.
-struct StereoPack {
+// The keypoints of a stereo Frame as both stereo entries take them: positions, octaves and descriptor rows copied into flat arrays.
+struct KeypointArrays {
   std::vector<float> left_xy, right_xy;
   std::vector<int32_t> left_octave, right_octave;
   std::vector<uint8_t> left_desc, right_desc;
+};
+// False (with `unsupported`) when the descriptor matrices do not fit the keypoints.
+inline bool pack_keypoints(const Frame& F, KeypointArrays& a, const char*& unsupported) {
+  const size_t nl = F.mvKeys.size(), nr = F.mvKeysRight.size();
+  if ((size_t)F.mDescriptors.rows < nl || (size_t)F.mDescriptorsRight.rows < nr || (nl && F.mDescriptors.cols != 32) || (nr && F.mDescriptorsRight.cols != 32)) {
+    unsupported = "descriptor matrices do not match the keypoints"; return false;
+  }
+  auto keys = [](const std::vector<cv::KeyPoint>& k, const cv::Mat& D, std::vector<float>& xy, std::vector<int32_t>& oct, std::vector<uint8_t>& desc) {
+    xy.resize(k.size() * 2); oct.resize(k.size()); desc.resize(k.size() * 32);
+    for (size_t i = 0; i < k.size(); ++i) {
+      xy[2 * i] = k[i].pt.x; xy[2 * i + 1] = k[i].pt.y; oct[i] = k[i].octave;
+      std::copy(D.ptr<uint8_t>((int)i), D.ptr<uint8_t>((int)i) + 32, &desc[32 * i]);
+    }
+  };
+  keys(F.mvKeys, F.mDescriptors, a.left_xy, a.left_octave, a.left_desc);
+  keys(F.mvKeysRight, F.mDescriptorsRight, a.right_xy, a.right_octave, a.right_desc);
+  return true;
+}
+// the eight keypoint fields of osh_stereo_frame / osh_fisheye_stereo_frame
+template <class FrameStruct>
+void fill_keypoints(FrameStruct& f, const KeypointArrays& a) {
+  f.n_left = (int32_t)a.left_octave.size(); f.n_right = (int32_t)a.right_octave.size();
+  f.left_xy = a.left_xy.data(); f.left_octave = a.left_octave.data(); f.left_desc = a.left_desc.data();
+  f.right_xy = a.right_xy.data(); f.right_octave = a.right_octave.data(); f.right_desc = a.right_desc.data();
+}
+
+// The frame Frame::ComputeStereoMatches (Frame.cc) hands to osh_orb_stereo_match: the keypoint arrays, and the pyramid levels
+// referenced in place through ptr<uchar>(0) and step (a level is a view into a bordered image: its rows are `step` bytes apart,
+// never `cols`).  False (with `unsupported`) when the frame's members do not fit together.
+struct StereoPack {
+  KeypointArrays keys;
   std::vector<osh_stereo_image> left_pyramid, right_pyramid;
   const char* unsupported = nullptr;
   void fill(osh_stereo_frame& f, const Frame& F) const {
-    f.n_left = (int32_t)left_octave.size(); f.n_right = (int32_t)right_octave.size();
-    f.left_xy = left_xy.data(); f.left_octave = left_octave.data(); f.left_desc = left_desc.data();
-    f.right_xy = right_xy.data(); f.right_octave = right_octave.data(); f.right_desc = right_desc.data();
+    fill_keypoints(f, keys);
     f.n_levels = (int32_t)left_pyramid.size();
     f.scale_factors = F.mvScaleFactors.data(); f.inv_scale_factors = F.mvInvScaleFactors.data();
     f.left_pyramid = left_pyramid.data(); f.right_pyramid = right_pyramid.data();
@@ -506,19 +533,7 @@ inline bool PackStereoMatches(const Frame& F, StereoPack& pk) {
   if (pl.empty() || pl.size() != pr.size() || F.mvScaleFactors.size() < pl.size() || F.mvInvScaleFactors.size() < pl.size()) {
     pk.unsupported = "image pyramids and scale factors differ in their number of levels"; return false;
   }
-  const size_t nl = F.mvKeys.size(), nr = F.mvKeysRight.size();
-  if ((size_t)F.mDescriptors.rows < nl || (size_t)F.mDescriptorsRight.rows < nr || (nl && F.mDescriptors.cols != 32) || (nr && F.mDescriptorsRight.cols != 32)) {
-    pk.unsupported = "descriptor matrices do not match the keypoints"; return false;
-  }
-  auto keys = [](const std::vector<cv::KeyPoint>& k, const cv::Mat& D, std::vector<float>& xy, std::vector<int32_t>& oct, std::vector<uint8_t>& desc) {
-    xy.resize(k.size() * 2); oct.resize(k.size()); desc.resize(k.size() * 32);
-    for (size_t i = 0; i < k.size(); ++i) {
-      xy[2 * i] = k[i].pt.x; xy[2 * i + 1] = k[i].pt.y; oct[i] = k[i].octave;
-      std::copy(D.ptr<uint8_t>((int)i), D.ptr<uint8_t>((int)i) + 32, &desc[32 * i]);
-    }
-  };
-  keys(F.mvKeys, F.mDescriptors, pk.left_xy, pk.left_octave, pk.left_desc);
-  keys(F.mvKeysRight, F.mDescriptorsRight, pk.right_xy, pk.right_octave, pk.right_desc);
+  if (!pack_keypoints(F, pk.keys, pk.unsupported)) return false;
   auto levels = [](const std::vector<cv::Mat>& pyr, std::vector<osh_stereo_image>& out) {
     out.resize(pyr.size());
     for (size_t l = 0; l < pyr.size(); ++l) {
@@ -535,15 +550,11 @@ inline bool PackStereoMatches(const Frame& F, StereoPack& pk) {
 // are private members of Frame, so the member function fills those itself.  False (with `unsupported`) when
 // the cameras are not a KannalaBrandt8 pair or the frame's members do not fit together.
 struct FisheyeStereoPack {
-  std::vector<float> left_xy, right_xy;
-  std::vector<int32_t> left_octave, right_octave;
-  std::vector<uint8_t> left_desc, right_desc;
+  KeypointArrays keys;
   const char* unsupported = nullptr;
   void fill(osh_fisheye_stereo_frame& f, const Frame& F) const {
-    f.n_left = (int32_t)left_octave.size(); f.n_right = (int32_t)right_octave.size();
+    fill_keypoints(f, keys);
     f.mono_left = F.monoLeft; f.mono_right = F.monoRight;
-    f.left_xy = left_xy.data(); f.left_octave = left_octave.data(); f.left_desc = left_desc.data();
-    f.right_xy = right_xy.data(); f.right_octave = right_octave.data(); f.right_desc = right_desc.data();
     f.n_levels = (int32_t)F.mvLevelSigma2.size(); f.level_sigma2 = F.mvLevelSigma2.data();
     for (int k = 0; k < 8; ++k) { f.cam1[k] = F.mpCamera->getParameter(k); f.cam2[k] = F.mpCamera2->getParameter(k); }
     f.precision1 = static_cast<KannalaBrandt8*>(F.mpCamera)->GetPrecision();
@@ -556,19 +567,8 @@ inline bool PackStereoFishEyeMatches(const Frame& F, FisheyeStereoPack& pk) {
   }
   const size_t nl = F.mvKeys.size(), nr = F.mvKeysRight.size();
   if (F.monoLeft < 0 || (size_t)F.monoLeft > nl || F.monoRight < 0 || (size_t)F.monoRight > nr) { pk.unsupported = "monoLeft / monoRight outside the keypoints"; return false; }
-  if ((size_t)F.mDescriptors.rows < nl || (size_t)F.mDescriptorsRight.rows < nr || (nl && F.mDescriptors.cols != 32) || (nr && F.mDescriptorsRight.cols != 32)) {
-    pk.unsupported = "descriptor matrices do not match the keypoints"; return false;
-  }
+  if (!pack_keypoints(F, pk.keys, pk.unsupported)) return false;
   if (F.mvLevelSigma2.empty()) { pk.unsupported = "mvLevelSigma2 is empty"; return false; }
-  auto keys = [](const std::vector<cv::KeyPoint>& k, const cv::Mat& D, std::vector<float>& xy, std::vector<int32_t>& oct, std::vector<uint8_t>& desc) {
-    xy.resize(k.size() * 2); oct.resize(k.size()); desc.resize(k.size() * 32);
-    for (size_t i = 0; i < k.size(); ++i) {
-      xy[2 * i] = k[i].pt.x; xy[2 * i + 1] = k[i].pt.y; oct[i] = k[i].octave;
-      std::copy(D.ptr<uint8_t>((int)i), D.ptr<uint8_t>((int)i) + 32, &desc[32 * i]);
-    }
-  };
-  keys(F.mvKeys, F.mDescriptors, pk.left_xy, pk.left_octave, pk.left_desc);
-  keys(F.mvKeysRight, F.mDescriptorsRight, pk.right_xy, pk.right_octave, pk.right_desc);
   return true;
 }
 }  // namespace ORB_SLAM3

@@ -19,8 +19,6 @@
 
 namespace osh {
 
-constexpr int kPosBits = 22;
-constexpr unsigned kPosMask = (1u << kPosBits) - 1;
 constexpr unsigned kKeyNone = 0xFFFFFFFFu;
 constexpr int kQBlock = 256;     // queries per block (one per thread)
 constexpr int kTrainTile = 1024; // train descriptors staged in LDS per tile (32 KiB)

@@ -11,14 +11,12 @@
 // Float32 steps are single IEEE operations in the reference's order, contraction off; `/` is the correctly rounded division.
 #include "common.h"
 #include "orb_hamming.h"
-#include <chrono>
+#include "orb_stage.h"
 #include <cmath>
 #include <vector>
 
 namespace osh {
 
-constexpr int kStereoPosBits = 22;
-constexpr unsigned kStereoPosMask = (1u << kStereoPosBits) - 1;
 constexpr int kSBlock = 64;       // left keypoints per block of k_stereo_hamming (one per lane of one wavefront)
 constexpr int kSTile = 256;       // right keypoints staged in LDS per tile: 8 KiB descriptors + 4 KiB predicate data
 constexpr int kSadWaves = 4;      // left keypoints per block of k_stereo_sad (one per wavefront)
@@ -89,7 +87,7 @@ __global__ __launch_bounds__(kSBlock) void k_stereo_hamming(StereoView v) {
       const float uR = __int_as_float(p.z);
       if (in_row && !(p.w < levelL - 1 || p.w > levelL + 1) && uR >= minU && uR <= maxU) {   // :883-888
         const unsigned d = hamming256(a0, a1, sh_desc[2 * t], sh_desc[2 * t + 1]);
-        best = min(best, (d << kStereoPosBits) | (unsigned)(t0 + t));
+        best = min(best, (d << kPosBits) | (unsigned)(t0 + t));
       }
     }
   }
@@ -125,9 +123,9 @@ __global__ __launch_bounds__(kSadWaves * 64) void k_stereo_sad(StereoView v) {
     if (!has_row || maxU < 0) {                          // :863-870
       stage = OSH_STEREO_NO_CANDIDATE;
     } else {
-      const unsigned d = key >> kStereoPosBits;
+      const unsigned d = key >> kPosBits;
       ham = kThHigh;
-      if (key != 0xFFFFFFFFu && d < (unsigned)kThHigh) { ham = (int)d; best_right = (int)(key & kStereoPosMask); }
+      if (key != 0xFFFFFFFFu && d < (unsigned)kThHigh) { ham = (int)d; best_right = (int)(key & kPosMask); }
       if (!(ham < kThOrbDist)) {                         // :902
         stage = OSH_STEREO_HAMMING;
       } else {
@@ -261,6 +259,7 @@ __global__ __launch_bounds__(256) void k_stereo_median(StereoView v) {
   }
 }
 
+
 struct StereoState {
   StagedCall call;
   double ms[4] = {0, 0, 0, 0};
@@ -271,8 +270,7 @@ static int stereo_validate(int n_frames, const osh_stereo_frame* frames, const o
     const osh_stereo_frame& f = frames[k];
     const osh_stereo_result& r = results[k];
     if (f.n_left < 0 || f.n_right < 0) { set_error("frame %d: negative keypoint count", k); return OSH_ERR_INVALID; }
-    if (f.n_levels < 1 || f.n_levels > OSH_STEREO_MAX_LEVELS) { set_error("frame %d: n_levels %d outside [1, %d]", k, f.n_levels, OSH_STEREO_MAX_LEVELS); return OSH_ERR_INVALID; }
-    if ((unsigned)f.n_right > kStereoPosMask) { set_error("frame %d: n_right exceeds %u", k, kStereoPosMask); return OSH_ERR_UNSUPPORTED; }
+    OSH_TRY(validate_keypoint_sides(k, f, kPosMask));
     if (!f.scale_factors || !f.inv_scale_factors || !f.left_pyramid || !f.right_pyramid) { set_error("frame %d: NULL scale factors or pyramid", k); return OSH_ERR_INVALID; }
     if (f.n_left && (!f.left_xy || !f.left_octave || !f.left_desc || !r.u_right || !r.depth)) { set_error("frame %d: NULL left keypoint or result array", k); return OSH_ERR_INVALID; }
     if (f.n_right && (!f.right_xy || !f.right_octave || !f.right_desc)) { set_error("frame %d: NULL right keypoint array", k); return OSH_ERR_INVALID; }
@@ -283,9 +281,8 @@ static int stereo_validate(int n_frames, const osh_stereo_frame* frames, const o
       return true;
     };
     if (!coords_ok(f.left_xy, f.n_left) || !coords_ok(f.right_xy, f.n_right)) { set_error("frame %d: keypoint coordinate not finite or beyond %g", k, (double)OSH_STEREO_MAX_COORD); return OSH_ERR_INVALID; }
-    for (int i = 0; i < f.n_right; ++i)
-      if (f.right_octave[i] < 0 || f.right_octave[i] >= f.n_levels) { set_error("frame %d: right octave %d outside [0, %d)", k, f.right_octave[i], f.n_levels); return OSH_ERR_INVALID; }
-    for (int i = 0; i < f.n_left; ++i) {
+    OSH_TRY(validate_octaves(k, "right", f.right_octave, f.n_right, f.n_levels));
+    for (int i = 0; i < f.n_left; ++i) {   // octave and image keypoint by keypoint: not validate_octaves, which would test every octave first
       const int o = f.left_octave[i];
       if (o < 0 || o >= f.n_levels) { set_error("frame %d: left octave %d outside [0, %d)", k, o, f.n_levels); return OSH_ERR_INVALID; }
       const osh_stereo_image* im[2] = {&f.left_pyramid[o], &f.right_pyramid[o]};
@@ -306,26 +303,25 @@ using namespace osh;
 extern "C" int osh_orb_stereo_match(osh_orb_ctx* c, int32_t n_frames, const osh_stereo_frame* frames, const osh_stereo_result* results) {
   if (!c || n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_stereo_match: bad arguments"); return OSH_ERR_INVALID; }
   if (n_frames == 0) return OSH_OK;
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
+  PhaseClock clock;
   OSH_TRY(stereo_validate(n_frames, frames, results));
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(orb_stream(c, &device, &s));
-  void** slot = orb_attachment(c, [](void* q) { delete static_cast<StereoState*>(q); });
-  if (!*slot) *slot = new StereoState();
-  StereoState* st = static_cast<StereoState*>(*slot);
-  const bool prof = orb_profiling(c);
+  StereoState* st = orb_state<StereoState>(c, kOrbAttachStereo);
+  clock.profiling = orb_profiling(c);
 
   // sizes: keypoints of the batch one frame after another; the image arena holds the used levels, rows packed
-  size_t NL = 0, NR = 0, img_bytes = 0;
-  int max_left = 0;
+  KeypointBatch kb;
+  OSH_TRY(kb.size("osh_orb_stereo_match", n_frames, frames));
+  const size_t NL = kb.NL;
+  size_t img_bytes = 0;
   std::vector<StereoFrameDev> fd(n_frames);
   for (int k = 0; k < n_frames; ++k) {
     const osh_stereo_frame& f = frames[k];
     StereoFrameDev& d = fd[k];
     std::memset(&d, 0, sizeof d);
-    d.n_left = f.n_left; d.n_right = f.n_right; d.left_base = (int)NL; d.right_base = (int)NR;
+    d.n_left = f.n_left; d.n_right = f.n_right; d.left_base = kb.base[k].left; d.right_base = kb.base[k].right;
     d.n_rows = f.left_pyramid[0].rows; d.n_levels = f.n_levels; d.bf = f.bf; d.b = f.b;
     bool used[OSH_STEREO_MAX_LEVELS] = {false};
     for (int i = 0; i < f.n_left; ++i) used[f.left_octave[i]] = true;
@@ -338,37 +334,23 @@ extern "C" int osh_orb_stereo_match(osh_orb_ctx* c, int32_t n_frames, const osh_
       d.off_l[l] = (long long)img_bytes; img_bytes += (size_t)d.rows_l[l] * d.cols_l[l];
       d.off_r[l] = (long long)img_bytes; img_bytes += (size_t)d.rows_r[l] * d.cols_r[l];
     }
-    NL += (size_t)f.n_left; NR += (size_t)f.n_right;
-    max_left = std::max(max_left, f.n_left);
-    if (NL > (size_t)INT_MAX / 16 || NR > (size_t)INT_MAX / 16) { set_error("osh_orb_stereo_match: batch too large"); return OSH_ERR_UNSUPPORTED; }
   }
-  Layout in, out;
+  Layout in, out, work;
   const auto s_frames = in.take<StereoFrameDev>(n_frames);
-  const auto s_lxy = in.take<float2>(NL); const auto s_loct = in.take<int>(NL); const auto s_ldesc = in.take<uint4>(NL * 2);
-  const auto s_rxy = in.take<float2>(NR); const auto s_roct = in.take<int>(NR); const auto s_rdesc = in.take<uint4>(NR * 2);
+  kb.take(in);
   const auto s_img = in.take<unsigned char>(img_bytes);
   const auto o_ur = out.take<float>(NL); const auto o_depth = out.take<float>(NL);
   const auto o_br = out.take<int>(NL); const auto o_ham = out.take<int>(NL); const auto o_sad = out.take<int>(NL * 11);
   const auto o_inc = out.take<int>(NL); const auto o_stage = out.take<unsigned char>(NL);
-  Layout work;
   const auto w_key = work.take<unsigned>(NL); const auto w_hit = work.take<unsigned>(NL); const auto w_bsad = work.take<int>(NL);
   OSH_TRY(st->call.reserve(in, out, work.bytes));
 
   char* h = st->call.host_in();
   std::memcpy(s_frames.in(h), fd.data(), sizeof(StereoFrameDev) * n_frames);
+  kb.stage(h, frames);
   for (int k = 0; k < n_frames; ++k) {
     const osh_stereo_frame& f = frames[k];
     const StereoFrameDev& d = fd[k];
-    if (f.n_left) {
-      std::memcpy(s_lxy.in(h) + d.left_base, f.left_xy, (size_t)f.n_left * 8);
-      std::memcpy(s_loct.in(h) + d.left_base, f.left_octave, (size_t)f.n_left * 4);
-      std::memcpy(s_ldesc.in(h) + (size_t)d.left_base * 2, f.left_desc, (size_t)f.n_left * 32);
-    }
-    if (f.n_right) {
-      std::memcpy(s_rxy.in(h) + d.right_base, f.right_xy, (size_t)f.n_right * 8);
-      std::memcpy(s_roct.in(h) + d.right_base, f.right_octave, (size_t)f.n_right * 4);
-      std::memcpy(s_rdesc.in(h) + (size_t)d.right_base * 2, f.right_desc, (size_t)f.n_right * 32);
-    }
     for (int l = 0; l < f.n_levels; ++l) {
       if (d.off_l[l] < 0) continue;
       const osh_stereo_image* im[2] = {&f.left_pyramid[l], &f.right_pyramid[l]};
@@ -380,64 +362,44 @@ extern "C" int osh_orb_stereo_match(osh_orb_ctx* c, int32_t n_frames, const osh_
       }
     }
   }
-  const auto t1 = clk::now();
+  clock.mark();
   OSH_TRY(st->call.upload(s));
-  if (prof) OSH_HIP(hipStreamSynchronize(s));
-  const auto t2 = clk::now();
+  OSH_TRY(clock.mark_synced(s));
 
   if (NL) {
     StereoView v{};
     char* di = st->call.dev_in(); char* dout = st->call.dev_out(); char* dw = st->call.dev_work();
     v.n_frames = n_frames;
     v.frames = s_frames.in(di);
-    v.lxy = s_lxy.in(di); v.loct = s_loct.in(di); v.ldesc = s_ldesc.in(di);
-    v.rxy = s_rxy.in(di); v.roct = s_roct.in(di); v.rdesc = s_rdesc.in(di);
+    kb.bind(v, di);
     v.images = s_img.in(di);
     v.key = w_key.in(dw); v.rowhit = w_hit.in(dw); v.best_sad = w_bsad.in(dw);
     v.u_right = o_ur.in(dout); v.depth = o_depth.in(dout); v.best_right = o_br.in(dout); v.hamming = o_ham.in(dout);
     v.sad = o_sad.in(dout); v.best_inc = o_inc.in(dout); v.stage = o_stage.in(dout);
     OSH_HIP(hipMemsetAsync(v.key, 0xFF, NL * 4, s));
     OSH_HIP(hipMemsetAsync(v.rowhit, 0, NL * 4, s));
-    const int qblocks = (max_left + kSBlock - 1) / kSBlock;
-    int max_right = 0;
-    for (int k = 0; k < n_frames; ++k) max_right = std::max(max_right, frames[k].n_right);
-    // slices of the right set: enough blocks to fill the device when the batch is a single frame
-    const long blocks = (long)qblocks * n_frames;
-    int split = (int)std::min<long>(16, std::max<long>(1, (1024 + blocks - 1) / blocks));
-    split = std::min(split, std::max(1, (max_right + kSTile - 1) / kSTile));
-    v.n_split = split;
-    hipLaunchKernelGGL(k_stereo_hamming, dim3((unsigned)qblocks, (unsigned)n_frames, (unsigned)split), dim3(kSBlock), 0, s, v);
-    hipLaunchKernelGGL(k_stereo_sad, dim3((unsigned)((max_left + kSadWaves - 1) / kSadWaves), (unsigned)n_frames), dim3(kSadWaves * 64), 0, s, v);
+    const int qblocks = (kb.max_left + kSBlock - 1) / kSBlock;
+    v.n_split = right_set_slices(qblocks, n_frames, kb.max_right, kSTile);
+    hipLaunchKernelGGL(k_stereo_hamming, dim3((unsigned)qblocks, (unsigned)n_frames, (unsigned)v.n_split), dim3(kSBlock), 0, s, v);
+    hipLaunchKernelGGL(k_stereo_sad, dim3((unsigned)((kb.max_left + kSadWaves - 1) / kSadWaves), (unsigned)n_frames), dim3(kSadWaves * 64), 0, s, v);
     hipLaunchKernelGGL(k_stereo_median, dim3((unsigned)n_frames), dim3(256), 0, s, v);
     OSH_TRY(launch_check("stereo match"));
   }
-  if (prof) OSH_HIP(hipStreamSynchronize(s));
-  const auto t3 = clk::now();
+  OSH_TRY(clock.mark_synced(s));
   OSH_TRY(st->call.download(s));
   const char* ho = st->call.host_out();
   for (int k = 0; k < n_frames; ++k) {
     const osh_stereo_result& r = results[k];
-    const StereoFrameDev& d = fd[k];
-    const size_t n = (size_t)d.n_left, b = (size_t)d.left_base;
-    if (!n) continue;
-    std::memcpy(r.u_right, o_ur.in(const_cast<char*>(ho)) + b, n * 4);
-    std::memcpy(r.depth, o_depth.in(const_cast<char*>(ho)) + b, n * 4);
-    if (r.best_right) std::memcpy(r.best_right, o_br.in(const_cast<char*>(ho)) + b, n * 4);
-    if (r.hamming) std::memcpy(r.hamming, o_ham.in(const_cast<char*>(ho)) + b, n * 4);
-    if (r.sad) std::memcpy(r.sad, o_sad.in(const_cast<char*>(ho)) + b * 11, n * 44);
-    if (r.best_inc) std::memcpy(r.best_inc, o_inc.in(const_cast<char*>(ho)) + b, n * 4);
-    if (r.stage) std::memcpy(r.stage, o_stage.in(const_cast<char*>(ho)) + b, n);
+    const size_t n = (size_t)frames[k].n_left, b = (size_t)kb.base[k].left;
+    scatter(r.u_right, o_ur, ho, b, n); scatter(r.depth, o_depth, ho, b, n);
+    scatter(r.best_right, o_br, ho, b, n); scatter(r.hamming, o_ham, ho, b, n); scatter(r.sad, o_sad, ho, b, n, 11);
+    scatter(r.best_inc, o_inc, ho, b, n); scatter(r.stage, o_stage, ho, b, n);
   }
-  const auto t4 = clk::now();
-  auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-  if (prof) { st->ms[0] = ms(t0, t1); st->ms[1] = ms(t1, t2); st->ms[2] = ms(t2, t3); st->ms[3] = ms(t3, t4); }
+  clock.mark();
+  clock.store(st->ms);
   return OSH_OK;
 }
 
 extern "C" int osh_orb_stereo_get_times(osh_orb_ctx* c, double ms[4]) {
-  if (!c || !ms) { set_error("osh_orb_stereo_get_times: bad arguments"); return OSH_ERR_INVALID; }
-  void** slot = orb_attachment(c, [](void* q) { delete static_cast<StereoState*>(q); });
-  const StereoState* st = static_cast<const StereoState*>(*slot);
-  for (int k = 0; k < 4; ++k) ms[k] = st ? st->ms[k] : 0.0;
-  return OSH_OK;
+  return copy_times<StereoState>("osh_orb_stereo_get_times", c, kOrbAttachStereo, ms);
 }

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -146,55 +147,14 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_stereo_match(self.ctx, len(frames), cf, cr), "osh_orb_stereo_match", self.lib)
         return outs
 
-    @staticmethod
-    def _stereo_args(frames, stages, borders):
-        n_frames = len(frames)
-        cf = (capi.StereoFrame * max(n_frames, 1))()
-        cr = (capi.StereoResult * max(n_frames, 1))()
-        keep, outs = [], []
-        c = np.ascontiguousarray
-        for k, fr in enumerate(frames):
-            border = 0 if borders is None else int(borders[k])
-            a = dict(lxy=c(fr.left_xy, np.float32), loct=c(fr.left_octave, np.int32), ldesc=c(fr.left_desc, np.uint8),
-                     rxy=c(fr.right_xy, np.float32), roct=c(fr.right_octave, np.int32), rdesc=c(fr.right_desc, np.uint8),
-                     sf=c(fr.scale_factors, np.float32), isf=c(fr.inv_scale_factors, np.float32))
-            f = cf[k]
-            f.n_left, f.n_right, f.n_levels = a["loct"].shape[0], a["roct"].shape[0], fr.n_levels
-            f.left_xy, f.left_octave, f.left_desc = capi.ptr(a["lxy"], capi.c_float_p), capi.ptr(a["loct"], capi.c_int32_p), capi.ptr(a["ldesc"], capi.c_uint8_p)
-            f.right_xy, f.right_octave, f.right_desc = capi.ptr(a["rxy"], capi.c_float_p), capi.ptr(a["roct"], capi.c_int32_p), capi.ptr(a["rdesc"], capi.c_uint8_p)
-            f.scale_factors, f.inv_scale_factors = capi.ptr(a["sf"], capi.c_float_p), capi.ptr(a["isf"], capi.c_float_p)
-            pyr = []
-            for side in (fr.left_pyramid, fr.right_pyramid):
-                imgs = (capi.StereoImage * fr.n_levels)()
-                for l, m in enumerate(side):
-                    if m is None:
-                        continue                           # a level no left keypoint names: data stays NULL
-                    whole = np.full((m.shape[0] + 2 * border, m.shape[1] + 2 * border), 167, dtype=np.uint8)
-                    whole[border:border + m.shape[0], border:border + m.shape[1]] = m
-                    a[f"img{len(a)}"] = whole
-                    imgs[l].data = C.cast(whole.ctypes.data + border * whole.shape[1] + border, capi.c_uint8_p)
-                    imgs[l].rows, imgs[l].cols, imgs[l].stride = m.shape[0], m.shape[1], whole.shape[1]
-                pyr.append(imgs)
-            f.left_pyramid, f.right_pyramid = pyr[0], pyr[1]
-            f.bf, f.b = fr.bf, fr.b
-            n = f.n_left
-            o = dict(u_right=np.zeros(n, np.float32), depth=np.zeros(n, np.float32))
-            cr[k].u_right, cr[k].depth = capi.ptr(o["u_right"], capi.c_float_p), capi.ptr(o["depth"], capi.c_float_p)
-            if stages:
-                o.update(best_right=np.zeros(n, np.int32), hamming=np.zeros(n, np.int32), sad=np.zeros((n, 11), np.int32),
-                         best_inc=np.zeros(n, np.int32), stage=np.zeros(n, np.uint8))
-                for name in ("best_right", "hamming", "sad", "best_inc"):
-                    setattr(cr[k], name, capi.ptr(o[name], capi.c_int32_p))
-                cr[k].stage = capi.ptr(o["stage"], capi.c_uint8_p)
-            keep.append((a, pyr))
-            outs.append(o)
-        return cf, cr, keep, outs
-
-    def stereo_times(self):
-        """Host-clock phases (ms) of the last stereo_match under set_profiling(True): staging, upload, kernels, download."""
+    def _times(self, symbol):
+        """Host-clock phases (ms) of an entry's last call under set_profiling(True): staging, upload, kernels, download."""
         ms = np.zeros(4, dtype=np.float64)
-        capi.check(self.lib.osh_orb_stereo_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_stereo_get_times", self.lib)
+        capi.check(getattr(self.lib, symbol)(self.ctx, capi.ptr(ms, capi.c_double_p)), symbol, self.lib)
         return ms
+
+    stereo_times = functools.partialmethod(_times, "osh_orb_stereo_get_times")                   # of the last stereo_match
+    fisheye_stereo_times = functools.partialmethod(_times, "osh_orb_fisheye_stereo_get_times")   # of the last fisheye_stereo_match
 
     def fisheye_stereo_match(self, frames, stages: bool = False) -> list:
         """Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1131-1171) for a batch of synth_fisheye.FisheyeFrame in one
@@ -203,12 +163,6 @@ class OrbMatcher:
         cf, cr, _keep, outs = fisheye_stereo_args(frames, stages)
         capi.check(self.lib.osh_orb_fisheye_stereo_match(self.ctx, len(frames), cf, cr), "osh_orb_fisheye_stereo_match", self.lib)
         return outs
-
-    def fisheye_stereo_times(self):
-        """Host-clock phases (ms) of the last fisheye_stereo_match under set_profiling(True): staging, upload, kernels, download."""
-        ms = np.zeros(4, dtype=np.float64)
-        capi.check(self.lib.osh_orb_fisheye_stereo_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_fisheye_stereo_get_times", self.lib)
-        return ms
 
     def kb8_triangulate(self, rig: "capi.Kb8Rig", xy1, xy2, sigma1, sigma2) -> dict:
         """KannalaBrandt8::TriangulateMatches for explicit keypoint pairs (osh_kb8_triangulate): ret [n], p3d [n, 3], cos_parallax [n]."""
@@ -235,10 +189,66 @@ class OrbMatcher:
         return int(n.value), float(ms.value)
 
 
+_POINTER = {np.dtype(np.float32): capi.c_float_p, np.dtype(np.int32): capi.c_int32_p, np.dtype(np.uint8): capi.c_uint8_p}
+# the keypoint arrays of a frame: attribute of the synthetic frame = field of the frame struct, key in the dict of arrays, dtype
+_KEYPOINTS = (("left_xy", "lxy", np.float32), ("left_octave", "loct", np.int32), ("left_desc", "ldesc", np.uint8),
+              ("right_xy", "rxy", np.float32), ("right_octave", "roct", np.int32), ("right_desc", "rdesc", np.uint8))
+
+
+def _fill_keypoints(f, fr, a=None):
+    """n_left, n_right and the six keypoint arrays of a capi.StereoFrame, capi.FisheyeStereoFrame or capi.HostFisheyeInput from a
+    synthetic frame; a: its contiguous arrays if the caller made them already.  Returns the arrays the pointers refer to."""
+    if a is None:
+        a = {key: np.ascontiguousarray(getattr(fr, field), dtype) for field, key, dtype in _KEYPOINTS}
+    f.n_left, f.n_right = a["loct"].shape[0], a["roct"].shape[0]
+    for field, key, _ in _KEYPOINTS:
+        setattr(f, field, capi.ptr(a[key], _POINTER[a[key].dtype]))
+    return a
+
+
+def _wire_outputs(res, outs):
+    """Points the fields of a result struct at the arrays of `outs` (field name -> array), each through the pointer type of its dtype."""
+    for name, o in outs.items():
+        setattr(res, name, capi.ptr(o, _POINTER[o.dtype]))
+
+
 def stereo_args(frames, stages: bool = False, borders=None):
     """The osh_stereo_frame / osh_stereo_result arrays of OrbMatcher.stereo_match for repeated calls: (frames, results, the arrays
     that keep their pointers alive, the per-frame dicts of output arrays)."""
-    return OrbMatcher._stereo_args(frames, stages, borders)
+    n_frames = len(frames)
+    cf = (capi.StereoFrame * max(n_frames, 1))()
+    cr = (capi.StereoResult * max(n_frames, 1))()
+    keep, outs = [], []
+    for k, fr in enumerate(frames):
+        border = 0 if borders is None else int(borders[k])
+        f = cf[k]
+        a = _fill_keypoints(f, fr)
+        a.update(sf=np.ascontiguousarray(fr.scale_factors, np.float32), isf=np.ascontiguousarray(fr.inv_scale_factors, np.float32))
+        f.n_levels = fr.n_levels
+        f.scale_factors, f.inv_scale_factors = capi.ptr(a["sf"], capi.c_float_p), capi.ptr(a["isf"], capi.c_float_p)
+        pyr = []
+        for side in (fr.left_pyramid, fr.right_pyramid):
+            imgs = (capi.StereoImage * fr.n_levels)()
+            for l, m in enumerate(side):
+                if m is None:
+                    continue                           # a level no left keypoint names: data stays NULL
+                whole = np.full((m.shape[0] + 2 * border, m.shape[1] + 2 * border), 167, dtype=np.uint8)
+                whole[border:border + m.shape[0], border:border + m.shape[1]] = m
+                a[f"img{len(a)}"] = whole
+                imgs[l].data = C.cast(whole.ctypes.data + border * whole.shape[1] + border, capi.c_uint8_p)
+                imgs[l].rows, imgs[l].cols, imgs[l].stride = m.shape[0], m.shape[1], whole.shape[1]
+            pyr.append(imgs)
+        f.left_pyramid, f.right_pyramid = pyr[0], pyr[1]
+        f.bf, f.b = fr.bf, fr.b
+        n = f.n_left
+        o = dict(u_right=np.zeros(n, np.float32), depth=np.zeros(n, np.float32))
+        if stages:
+            o.update(best_right=np.zeros(n, np.int32), hamming=np.zeros(n, np.int32), sad=np.zeros((n, 11), np.int32),
+                     best_inc=np.zeros(n, np.int32), stage=np.zeros(n, np.uint8))
+        _wire_outputs(cr[k], o)
+        keep.append((a, pyr))
+        outs.append(o)
+    return cf, cr, keep, outs
 
 
 def fisheye_stereo_args(frames, stages: bool = False):
@@ -248,40 +258,33 @@ def fisheye_stereo_args(frames, stages: bool = False):
     cf = (capi.FisheyeStereoFrame * max(n_frames, 1))()
     cr = (capi.FisheyeStereoResult * max(n_frames, 1))()
     keep, outs = [], []
-    c = np.ascontiguousarray
     for k, fr in enumerate(frames):
-        a = dict(lxy=c(fr.left_xy, np.float32), loct=c(fr.left_octave, np.int32), ldesc=c(fr.left_desc, np.uint8),
-                 rxy=c(fr.right_xy, np.float32), roct=c(fr.right_octave, np.int32), rdesc=c(fr.right_desc, np.uint8),
-                 sig=c(fr.level_sigma2, np.float32))
-        f = cf[k]
-        fill_fisheye_frame(f, fr, a)
-        nl, nr = f.n_left, f.n_right
+        a = fill_fisheye_frame(cf[k], fr)
+        nl, nr = cf[k].n_left, cf[k].n_right
         o = dict(left_to_right=np.zeros(nl, np.int32), right_to_left=np.zeros(nr, np.int32), depth=np.zeros(nl, np.float32),
                  p3d=np.zeros((nl, 3), np.float32))
-        cr[k].left_to_right, cr[k].right_to_left = capi.ptr(o["left_to_right"], capi.c_int32_p), capi.ptr(o["right_to_left"], capi.c_int32_p)
-        cr[k].depth, cr[k].p3d = capi.ptr(o["depth"], capi.c_float_p), capi.ptr(o["p3d"], capi.c_float_p)
         if stages:
             o.update(best_right=np.zeros(nl, np.int32), best_dist=np.zeros(nl, np.int32), second_dist=np.zeros(nl, np.int32),
                      cos_parallax=np.zeros(nl, np.float32), stage=np.zeros(nl, np.uint8))
-            for name in ("best_right", "best_dist", "second_dist"):
-                setattr(cr[k], name, capi.ptr(o[name], capi.c_int32_p))
-            cr[k].cos_parallax, cr[k].stage = capi.ptr(o["cos_parallax"], capi.c_float_p), capi.ptr(o["stage"], capi.c_uint8_p)
+        _wire_outputs(cr[k], o)
         keep.append(a)
         outs.append(o)
     return cf, cr, keep, outs
 
 
-def fill_fisheye_frame(f, fr, a):
-    """The fields capi.FisheyeStereoFrame and capi.HostFisheyeInput share, from a synth_fisheye.FisheyeFrame and its contiguous arrays."""
-    f.n_left, f.n_right, f.mono_left, f.mono_right = a["loct"].shape[0], a["roct"].shape[0], int(fr.mono_left), int(fr.mono_right)
-    f.left_xy, f.left_octave, f.left_desc = capi.ptr(a["lxy"], capi.c_float_p), capi.ptr(a["loct"], capi.c_int32_p), capi.ptr(a["ldesc"], capi.c_uint8_p)
-    f.right_xy, f.right_octave, f.right_desc = capi.ptr(a["rxy"], capi.c_float_p), capi.ptr(a["roct"], capi.c_int32_p), capi.ptr(a["rdesc"], capi.c_uint8_p)
+def fill_fisheye_frame(f, fr, a=None):
+    """The fields capi.FisheyeStereoFrame and capi.HostFisheyeInput share, from a synth_fisheye.FisheyeFrame; a: its contiguous
+    arrays (the six of the keypoints and sig) if the caller made them already.  Returns the arrays the pointers refer to."""
+    a = _fill_keypoints(f, fr, a)
+    a.setdefault("sig", np.ascontiguousarray(fr.level_sigma2, np.float32))
+    f.mono_left, f.mono_right = int(fr.mono_left), int(fr.mono_right)
     f.n_levels, f.level_sigma2 = a["sig"].shape[0], capi.ptr(a["sig"], capi.c_float_p)
     f.cam1[:] = [float(x) for x in np.asarray(fr.cam1, np.float32)]
     f.cam2[:] = [float(x) for x in np.asarray(fr.cam2, np.float32)]
     f.precision1, f.precision2 = float(fr.precision1), float(fr.precision2)
     f.Rlr[:] = [float(x) for x in np.asarray(fr.Rlr, np.float32).reshape(9)]
     f.tlr[:] = [float(x) for x in np.asarray(fr.tlr, np.float32)]
+    return a
 
 
 def kb8_rig(cam1, cam2, precision1, precision2, R12, t12) -> "capi.Kb8Rig":
