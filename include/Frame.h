@@ -15,6 +15,7 @@
 #define FRAME_GRID_COLS 64
 namespace ORB_SLAM3 {
 class KeyFrame;
+class ORBVocabulary;
 class Frame {
  public:
   Frame() {}
@@ -35,6 +36,9 @@ class Frame {
   // KannalaBrandt8 rig frame.  A device error, a camera pair that is not CAM_FISHEYE or members that do not fit together: a
   // message on stderr and every keypoint unmatched (all -1)
   void ComputeStereoFishEyeMatches();
+  // src/Frame.cc:737-744: mBowVec / mFeatVec from mDescriptors through mpORBvocabulary->transform(.., 4), only if mBowVec is empty.
+  // The reference body is kept by an integrator (ORBVocabulary is the replaced part); csrc/hosttest/bow.cc holds the stand-in's
+  void ComputeBoW();
 
   int N = 0;
   int Nleft = -1, Nright = -1;
@@ -49,6 +53,8 @@ class Frame {
   std::vector<MapPoint*> mvpMapPoints;
   std::vector<bool> mvbOutlier;
   cv::Mat mDescriptors, mDescriptorsRight;        // include/Frame.h:242
+  ORBVocabulary* mpORBvocabulary = nullptr;        // include/Frame.h:193
+  DBoW2::BowVector mBowVec;        // include/Frame.h:238 (filled by ComputeBoW)
   DBoW2::FeatureVector mFeatVec;   // include/Frame.h:262 (filled by ComputeBoW)
   std::vector<float> mvScaleFactors;
   std::vector<float> mvInvScaleFactors;           // include/Frame.h:282

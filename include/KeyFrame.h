@@ -11,6 +11,7 @@
 #include "MapPoint.h"
 #include "orbslam3_compat.h"
 namespace ORB_SLAM3 {
+class ORBVocabulary;
 class KeyFrame {
  public:
   KeyFrame(long unsigned int id, Map* pMap) : mnId(id), mpMap(pMap) {}
@@ -52,6 +53,8 @@ class KeyFrame {
   // candidate generator of the Sim3 searches (src/KeyFrame.cc:704-750): the grid is the one of the Frame the keyframe was made from
   std::vector<size_t> GetFeaturesInArea(const float& x, const float& y, const float& r, const bool bRight = false) const;
   bool IsInImage(const float& x, const float& y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }
+  // src/KeyFrame.cc:92-102: as Frame::ComputeBoW, only if mBowVec or mFeatVec is empty (stand-in body: csrc/hosttest/bow.cc)
+  void ComputeBoW();
 
   long unsigned int mnId;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
@@ -65,6 +68,8 @@ class KeyFrame {
   float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
   int N = 0, NLeft = -1;
   std::vector<cv::KeyPoint> mvKeys, mvKeysUn, mvKeysRight;
+  ORBVocabulary* mpORBvocabulary = nullptr;   // include/KeyFrame.h:455
+  DBoW2::BowVector mBowVec;        // include/KeyFrame.h:388 (filled by ComputeBoW)
   DBoW2::FeatureVector mFeatVec;   // include/KeyFrame.h:403 (filled by ComputeBoW)
   std::vector<float> mvuRight;
   std::vector<float> mvInvLevelSigma2;

@@ -812,6 +812,73 @@ typedef struct osh_kb8_rig {
 int osh_kb8_triangulate(osh_orb_ctx* ctx, int32_t n, const osh_kb8_rig* rig, const float* xy1, const float* xy2, const float* sigma1,
                         const float* sigma2, float* ret, float* p3d, float* cos_parallax);
 
+/* ------------------------------------------------- bag-of-words transform */
+/*
+ * TemplatedVocabulary::transform (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1259) for ORB descriptors: what
+ * Frame::ComputeBoW and KeyFrame::ComputeBoW run per frame.  Every feature descends the vocabulary tree from the root, at each
+ * node to the child with the smallest Hamming distance (the first such child in the order the loader appended them), until a
+ * node without children; the word reached adds its weight to the BowVector and the node passed at depth L - levelsup collects
+ * the feature in the FeatureVector.  Everything is integer or order-fixed FP64: the outputs equal the reference's bit for bit.
+ *
+ * A vocabulary is an object of its own, immutable after creation and resident once per device: every osh_orb_ctx of that device,
+ * on any thread, may run transforms on it at the same time.  It must outlive the calls that use it.
+ *
+ * osh_bow_tree describes nodes 1..n in file order (the root is node 0 and is not listed).  osh_bow_tree_check (no device work)
+ * and osh_bow_vocab_create refuse with OSH_ERR_INVALID: k outside [0, OSH_BOW_MAX_K] or L outside [1, OSH_BOW_MAX_L], weighting
+ * or scoring outside their enums, a parent that is not an earlier node, a node whose leaf flag and whether it has children
+ * disagree, more than OSH_BOW_MAX_K children under one node, an empty tree.  osh_bow_vocab_create refuses OSH_BOW_L2_NORM with
+ * OSH_ERR_UNSUPPORTED (its square root is the one step whose rounding is not pinned).  Word ids are assigned in file order to
+ * the nodes flagged leaf.
+ */
+#define OSH_BOW_MAX_K 20
+#define OSH_BOW_MAX_L 10
+#define OSH_BOW_MAX_FEATURES 16384   /* per frame; a larger frame is refused with OSH_ERR_UNSUPPORTED */
+enum { OSH_BOW_TF_IDF = 0, OSH_BOW_TF = 1, OSH_BOW_IDF = 2, OSH_BOW_BINARY = 3 };                       /* DBoW2::WeightingType */
+enum { OSH_BOW_L1_NORM = 0, OSH_BOW_L2_NORM = 1, OSH_BOW_CHI_SQUARE = 2, OSH_BOW_KL = 3, OSH_BOW_BHATTACHARYYA = 4,
+       OSH_BOW_DOT_PRODUCT = 5 };                                                                      /* DBoW2::ScoringType   */
+typedef struct osh_bow_tree {
+  int32_t k, L;              /* m_k, m_L of the file's first line                                  */
+  int32_t weighting;         /* OSH_BOW_TF_IDF ..                                                  */
+  int32_t scoring;           /* OSH_BOW_L1_NORM ..                                                 */
+  int32_t n;                 /* nodes besides the root                                             */
+  const int32_t* parent;     /* [n]    parent of node i + 1, in [0, i]                             */
+  const uint8_t* is_leaf;    /* [n]    leaf flag of the file                                       */
+  const uint8_t* desc;       /* [n*32] node descriptors                                            */
+  const double* weight;      /* [n]    node weights                                                */
+} osh_bow_tree;
+typedef struct osh_bow_vocab osh_bow_vocab;
+int  osh_bow_tree_check(const osh_bow_tree* tree);
+int  osh_bow_vocab_create(int device, const osh_bow_tree* tree, osh_bow_vocab** out);
+void osh_bow_vocab_destroy(osh_bow_vocab* vocab);
+
+typedef struct osh_bow_frame {
+  int32_t n;                 /* features                                                           */
+  const uint8_t* desc;       /* [n*32]                                                             */
+} osh_bow_frame;
+/* Caller-allocated, n entries each unless noted; any pointer may be NULL. */
+typedef struct osh_bow_result {
+  int32_t* n_words;          /* [1]   entries of the BowVector                                                          */
+  int32_t* word_id;          /*       ascending word ids                                                                */
+  double* word_value;        /*       their final values                                                                */
+  int32_t* n_nodes;          /* [1]   entries of the FeatureVector                                                      */
+  int32_t* node_id;          /*       ascending node ids                                                                */
+  int32_t* node_start;       /* [n+1] features of node_id[a]: node_feat[node_start[a] .. node_start[a+1])               */
+  int32_t* node_feat;        /*       feature indices, ascending inside a node                                          */
+  int32_t* feat_word;        /*       stage output: the word feature i reached (stopped features included)              */
+  int32_t* feat_node;        /*       stage output: the node recorded for it                                            */
+  int32_t* feat_dist;        /*       stage output: its Hamming distance to the descriptor of the leaf                  */
+} osh_bow_result;
+/* n_frames frames against one vocabulary in one call.  The node recorded for a feature is the one reached at depth L - levelsup,
+ * the root (0) when that depth is <= 0, and the leaf itself when the leaf is shallower (the reference leaves it unset there).
+ * A feature whose word has a weight <= 0 enters neither vector.  Refused with OSH_ERR_INVALID: a vocabulary of another device,
+ * a negative n, a NULL desc with n > 0; with OSH_ERR_UNSUPPORTED: n above OSH_BOW_MAX_FEATURES.  A refused call leaves the
+ * context usable. */
+int osh_orb_bow_transform(osh_orb_ctx* ctx, const osh_bow_vocab* vocab, int32_t levelsup, int32_t n_frames, const osh_bow_frame* frames,
+                          const osh_bow_result* results);
+/* Host-clock phases (ms) of the last osh_orb_bow_transform under osh_orb_set_profiling: ms[0] validation + staging, ms[1] upload,
+ * ms[2] kernels, ms[3] download + write-back (the FP64 sums run there). */
+int osh_orb_bow_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -405,6 +405,32 @@ struct osh_kb8_rig;
 int osh_host_kb8_triangulate_cpu(int32_t n, const struct osh_kb8_rig* rig, const float* xy1, const float* xy2, const float* sigma1,
                                  const float* sigma2, float* ret, float* p3d, float* cos_parallax);
 
+/* ---- ORBVocabulary / ComputeBoW (include/ORBVocabulary.h, csrc/host/ORBVocabulary.cc, csrc/hosttest/bow.cc) ---- */
+struct osh_bow_tree;
+struct osh_bow_result;
+/* TemplatedVocabulary::transform (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1259) restated in one thread with std::map
+ * vectors, on n descriptors; every output of osh_bow_result, stage outputs included.  -1: bad arguments or a tree
+ * osh_bow_tree_check refuses, -2: L2_NORM scoring.  *ms = wall time of the transform without the construction of the nodes. */
+int osh_host_bow_restatement(const struct osh_bow_tree* tree, int32_t levelsup, int32_t n, const uint8_t* desc,
+                             const struct osh_bow_result* out, double* ms);
+/* An ORB_SLAM3::ORBVocabulary behind a handle; NULL when loadFromTextFile returns false. */
+typedef struct osh_host_bow_vocab osh_host_bow_vocab;
+osh_host_bow_vocab* osh_host_bow_vocab_load(const char* path);
+void osh_host_bow_vocab_free(osh_host_bow_vocab* h);
+/* Its getters and tree: info = getBranchingFactor, getDepthLevels, getWeightingType, getScoringType, nodes besides the root, size,
+ * empty; the four arrays of osh_bow_tree (each may be NULL; call once with NULLs for the sizes) and getParentNode(w, levelsup) of
+ * every word w. */
+int osh_host_bow_vocab_tree(const osh_host_bow_vocab* h, int32_t info[7], int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight,
+                            int32_t levelsup, int32_t* word_parent);
+/* Frame::ComputeBoW (keyframe == 0) or KeyFrame::ComputeBoW on a stand-in whose mDescriptors are the n descriptors; mBowVec and
+ * mFeatVec come back as the first seven arrays of osh_bow_result.  second_desc != NULL: mDescriptors are then replaced by it and
+ * ComputeBoW runs once more (its guard has to keep the vectors).  n_threads > 1: that many threads do the same at once, each on a
+ * stand-in of its own; -3 if their results differ. */
+int osh_host_bow_compute(osh_host_bow_vocab* h, int32_t keyframe, int32_t n, const uint8_t* desc, const uint8_t* second_desc, int32_t n_threads,
+                         const struct osh_bow_result* out);
+/* ORBVocabulary::score of two BowVectors given as (word id, value) lists. */
+double osh_host_bow_score(int32_t n1, const int32_t* id1, const double* value1, int32_t n2, const int32_t* id2, const double* value2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -330,6 +330,32 @@ class Kb8Rig(C.Structure):
 OSH_FSTEREO_NO_COS = -2.0
 
 
+class BowTree(C.Structure):
+    """``osh_bow_tree`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32), ("n", C.c_int32),
+                ("parent", c_int32_p), ("is_leaf", c_uint8_p), ("desc", c_uint8_p), ("weight", c_double_p)]
+
+
+class BowFrame(C.Structure):
+    """``osh_bow_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n", C.c_int32), ("desc", c_uint8_p)]
+
+
+class BowResult(C.Structure):
+    """``osh_bow_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n_words", c_int32_p), ("word_id", c_int32_p), ("word_value", c_double_p), ("n_nodes", c_int32_p),
+                ("node_id", c_int32_p), ("node_start", c_int32_p), ("node_feat", c_int32_p), ("feat_word", c_int32_p),
+                ("feat_node", c_int32_p), ("feat_dist", c_int32_p)]
+
+
+OSH_BOW_MAX_K, OSH_BOW_MAX_L, OSH_BOW_MAX_FEATURES = 20, 10, 16384
+OSH_BOW_TF_IDF, OSH_BOW_TF, OSH_BOW_IDF, OSH_BOW_BINARY = range(4)
+(OSH_BOW_L1_NORM, OSH_BOW_L2_NORM, OSH_BOW_CHI_SQUARE, OSH_BOW_KL, OSH_BOW_BHATTACHARYYA, OSH_BOW_DOT_PRODUCT) = range(6)
+
+
 def ptr(a, typ):
     """Pointer of ctypes type `typ` to the data of numpy array `a` (None -> NULL)."""
     if a is None:
@@ -385,6 +411,11 @@ _SIGNATURES = {
     "osh_orb_fisheye_stereo_match": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FisheyeStereoFrame), C.POINTER(FisheyeStereoResult)]),
     "osh_orb_fisheye_stereo_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_kb8_triangulate": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
+    "osh_bow_tree_check": (C.c_int, [C.POINTER(BowTree)]),
+    "osh_bow_vocab_create": (C.c_int, [C.c_int, C.POINTER(BowTree), C.POINTER(C.c_void_p)]),
+    "osh_bow_vocab_destroy": (None, [C.c_void_p]),
+    "osh_orb_bow_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BowFrame), C.POINTER(BowResult)]),
+    "osh_orb_bow_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_pgo_solve": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), C.POINTER(PgoResult)]),
     "osh_pgo_linearize": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), c_double_p, c_double_p, c_double_p]),
     "osh_pgo4_solve": (C.c_int, [C.c_void_p, C.POINTER(Pgo4Problem), C.POINTER(Pgo4Result)]),
@@ -515,6 +546,12 @@ _HOST_SIGNATURES = {
     "osh_host_compute_stereo_matches": (C.c_int, [C.POINTER(HostStereoInput), C.c_int32, c_float_p, c_float_p]),
     "osh_host_stereo_restatement": (C.c_int, [C.POINTER(HostStereoInput), c_float_p, c_float_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
                                               c_uint8_p, c_uint8_p, c_int32_p, c_double_p]),
+    "osh_host_bow_restatement": (C.c_int, [C.POINTER(BowTree), C.c_int32, C.c_int32, c_uint8_p, C.POINTER(BowResult), c_double_p]),
+    "osh_host_bow_vocab_load": (C.c_void_p, [C.c_char_p]),
+    "osh_host_bow_vocab_free": (None, [C.c_void_p]),
+    "osh_host_bow_vocab_tree": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_uint8_p, c_uint8_p, c_double_p, C.c_int32, c_int32_p]),
+    "osh_host_bow_compute": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, C.c_int32, C.POINTER(BowResult)]),
+    "osh_host_bow_score": (C.c_double, [C.c_int32, c_int32_p, c_double_p, C.c_int32, c_int32_p, c_double_p]),
     "osh_host_search_keyframe": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, c_int32_p, C.c_int32, c_float_p, c_uint8_p, c_float_p,
                                            c_uint8_p, c_uint8_p, c_int32_p, C.c_float, C.c_int32, C.c_int32, c_int32_p]),
 }

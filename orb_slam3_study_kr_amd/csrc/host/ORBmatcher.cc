@@ -56,11 +56,16 @@ struct ThreadCtx {   // destroyed at thread exit (Tracking / LoopClosing threads
 
 }  // namespace
 
+// the device of every thread's matcher context (and of the vocabulary copy ORBVocabulary::transform makes for it)
+int HostMatcherDevice() {
+  const char* dev = std::getenv("ORBSLAM3_HIP_DEVICE");
+  return dev ? std::atoi(dev) : 0;
+}
+
 osh_orb_ctx* HostMatcherContext() {
   static thread_local ThreadCtx holder;
   if (!holder.ctx) {
-    const char* dev = std::getenv("ORBSLAM3_HIP_DEVICE");
-    if (osh_orb_create(dev ? std::atoi(dev) : 0, &holder.ctx) != OSH_OK) {
+    if (osh_orb_create(HostMatcherDevice(), &holder.ctx) != OSH_OK) {
       std::fprintf(stderr, "ORBmatcher: cannot create the HIP matcher context: %s\n", osh_last_error());
       holder.ctx = nullptr;
     }

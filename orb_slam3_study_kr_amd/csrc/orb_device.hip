@@ -544,7 +544,7 @@ struct osh_orb_ctx {
   std::vector<float> h_fin, h_fout;
   OrbView v{};
   bool uploaded = false, matched = false, windowed = false, grid = false;
-  void* attach[kOrbAttachCount] = {};     // state of osh_orb_stereo_match (stereo_device.hip) and of fisheye_stereo_device.hip
+  void* attach[kOrbAttachCount] = {};     // state of the entries that run on the context: OrbAttachSlot (common.h)
   void (*attach_free[kOrbAttachCount])(void*) = {};
 };
 

@@ -735,3 +735,84 @@ def search_for_initialization(f1, f2, prev_xy, window=100, nnratio=0.9, check_or
     n = lib.osh_host_search_for_initialization(f1.f, f2.f, capi.ptr(prev, capi.c_float_p), int(window), float(nnratio), int(check_ori),
                                                capi.ptr(m, capi.c_int32_p))
     return n, m, prev
+
+
+def _bow_result(o: dict) -> "capi.BowResult":
+    from . import orb
+    r = capi.BowResult()
+    orb._wire_outputs(r, o)
+    return r
+
+
+def bow_restatement(tree, desc, levelsup: int = 4, timed: bool = False):
+    """osh_host_bow_restatement: TemplatedVocabulary::transform restated in one C++ thread on a synth_bow.BowTree and descriptors
+    [n, 32]; the dict of orb.OrbMatcher.bow_transform(.., stages=True) (with `timed`: that and the milliseconds)."""
+    from . import orb
+    lib = capi.load_host_library()
+    t, _keep = orb.bow_tree(tree)
+    d = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+    o = orb.bow_outputs(d.shape[0], stages=True)
+    ms = C.c_double(0)
+    rc = lib.osh_host_bow_restatement(C.byref(t), int(levelsup), d.shape[0], capi.ptr(d, capi.c_uint8_p), C.byref(_bow_result(o)), C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_bow_restatement returned {rc}")
+    return (orb.bow_trim(o), float(ms.value)) if timed else orb.bow_trim(o)
+
+
+class HostBowVocab:
+    """An ORB_SLAM3::ORBVocabulary loaded from a text file (osh_host_bow_vocab_load); `loaded` is what loadFromTextFile returned."""
+
+    def __init__(self, path):
+        self.lib = capi.load_host_library()
+        self.h = self.lib.osh_host_bow_vocab_load(str(path).encode())
+        self.loaded = bool(self.h)
+
+    def close(self):
+        if self.h:
+            self.lib.osh_host_bow_vocab_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def tree(self, levelsup: int = 4):
+        """(synth_bow.BowTree of the loaded arrays, dict of the getters, getParentNode(w, levelsup) of every word)."""
+        from . import synth_bow
+        info = np.zeros(7, dtype=np.int32)
+        ip = capi.ptr(info, capi.c_int32_p)
+        assert self.lib.osh_host_bow_vocab_tree(self.h, ip, None, None, None, None, 0, None) == 0
+        n, words = int(info[4]), int(info[5])
+        parent, leaf, desc = np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8)
+        weight, word_parent = np.zeros(n, np.float64), np.zeros(words, np.int32)
+        assert self.lib.osh_host_bow_vocab_tree(self.h, ip, capi.ptr(parent, capi.c_int32_p), capi.ptr(leaf, capi.c_uint8_p),
+                                                capi.ptr(desc, capi.c_uint8_p), capi.ptr(weight, capi.c_double_p), int(levelsup),
+                                                capi.ptr(word_parent, capi.c_int32_p)) == 0
+        k, L, weighting, scoring = (int(x) for x in info[:4])
+        getters = dict(k=k, L=L, weighting=weighting, scoring=scoring, size=words, empty=bool(info[6]))
+        return synth_bow.BowTree(k, L, weighting, scoring, parent, leaf, desc, weight), getters, word_parent
+
+    def compute_bow(self, desc, keyframe: bool = False, second_desc=None, n_threads: int = 1) -> dict:
+        """Frame::ComputeBoW (or KeyFrame::ComputeBoW) on a stand-in with these descriptors: mBowVec as word_id / word_value and
+        mFeatVec as node_id / node_start / node_feat.  second_desc: ComputeBoW is called once more after the descriptors were
+        replaced by it.  n_threads > 1: as many threads do the same at once and have to agree."""
+        from . import orb
+        d = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        d2 = None if second_desc is None else np.ascontiguousarray(second_desc, dtype=np.uint8).reshape(-1, 32)
+        assert d2 is None or d2.shape == d.shape
+        o = orb.bow_outputs(d.shape[0], stages=False)
+        rc = self.lib.osh_host_bow_compute(self.h, int(keyframe), d.shape[0], capi.ptr(d, capi.c_uint8_p), capi.ptr(d2, capi.c_uint8_p),
+                                           int(n_threads), C.byref(_bow_result(o)))
+        if rc != 0:
+            raise RuntimeError(f"osh_host_bow_compute returned {rc}")
+        return orb.bow_trim(o)
+
+
+def bow_score(id1, value1, id2, value2) -> float:
+    """ORBVocabulary::score (L1) of two BowVectors given as word ids and values."""
+    lib = capi.load_host_library()
+    a = [_i32(id1), np.ascontiguousarray(value1, np.float64), _i32(id2), np.ascontiguousarray(value2, np.float64)]
+    return float(lib.osh_host_bow_score(len(a[0]), capi.ptr(a[0], capi.c_int32_p), capi.ptr(a[1], capi.c_double_p),
+                                        len(a[2]), capi.ptr(a[2], capi.c_int32_p), capi.ptr(a[3], capi.c_double_p)))

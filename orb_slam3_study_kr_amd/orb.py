@@ -155,6 +155,15 @@ class OrbMatcher:
 
     stereo_times = functools.partialmethod(_times, "osh_orb_stereo_get_times")                   # of the last stereo_match
     fisheye_stereo_times = functools.partialmethod(_times, "osh_orb_fisheye_stereo_get_times")   # of the last fisheye_stereo_match
+    bow_times = functools.partialmethod(_times, "osh_orb_bow_get_times")                         # of the last bow_transform
+
+    def bow_transform(self, vocab: "BowVocab", frames, levelsup: int = 4, stages: bool = False) -> list:
+        """TemplatedVocabulary::transform for a batch of descriptor arrays [n, 32] in one osh_orb_bow_transform call: per frame a
+        dict with word_id / word_value (the BowVector) and node_id / node_start / node_feat (the FeatureVector as CSR), and with
+        `stages` also feat_word, feat_node, feat_dist."""
+        cf, cr, _keep, outs = bow_args(frames, stages)
+        capi.check(self.lib.osh_orb_bow_transform(self.ctx, vocab.handle, int(levelsup), len(frames), cf, cr), "osh_orb_bow_transform", self.lib)
+        return [bow_trim(o) for o in outs]
 
     def fisheye_stereo_match(self, frames, stages: bool = False) -> list:
         """Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1131-1171) for a batch of synth_fisheye.FisheyeFrame in one
@@ -189,7 +198,29 @@ class OrbMatcher:
         return int(n.value), float(ms.value)
 
 
-_POINTER = {np.dtype(np.float32): capi.c_float_p, np.dtype(np.int32): capi.c_int32_p, np.dtype(np.uint8): capi.c_uint8_p}
+class BowVocab:
+    """A device-resident vocabulary (osh_bow_vocab) made from a synth_bow.BowTree; shared by every OrbMatcher of the device."""
+
+    def __init__(self, tree, device: int = 0):
+        self.lib = capi.load_library()
+        self.handle = C.c_void_p()
+        t, _keep = bow_tree(tree)
+        capi.check(self.lib.osh_bow_vocab_create(device, C.byref(t), C.byref(self.handle)), "osh_bow_vocab_create", self.lib)
+
+    def close(self):
+        if self.handle:
+            self.lib.osh_bow_vocab_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+_POINTER = {np.dtype(np.float32): capi.c_float_p, np.dtype(np.int32): capi.c_int32_p, np.dtype(np.uint8): capi.c_uint8_p,
+            np.dtype(np.float64): capi.c_double_p}
 # the keypoint arrays of a frame: attribute of the synthetic frame = field of the frame struct, key in the dict of arrays, dtype
 _KEYPOINTS = (("left_xy", "lxy", np.float32), ("left_octave", "loct", np.int32), ("left_desc", "ldesc", np.uint8),
               ("right_xy", "rxy", np.float32), ("right_octave", "roct", np.int32), ("right_desc", "rdesc", np.uint8))
@@ -247,6 +278,53 @@ def stereo_args(frames, stages: bool = False, borders=None):
                      best_inc=np.zeros(n, np.int32), stage=np.zeros(n, np.uint8))
         _wire_outputs(cr[k], o)
         keep.append((a, pyr))
+        outs.append(o)
+    return cf, cr, keep, outs
+
+
+def bow_tree(tree):
+    """capi.BowTree of a synth_bow.BowTree and the arrays its pointers refer to."""
+    keep = (np.ascontiguousarray(tree.parent, np.int32), np.ascontiguousarray(tree.is_leaf, np.uint8),
+            np.ascontiguousarray(tree.desc, np.uint8), np.ascontiguousarray(tree.weight, np.float64))
+    t = capi.BowTree()
+    t.k, t.L, t.weighting, t.scoring, t.n = int(tree.k), int(tree.L), int(tree.weighting), int(tree.scoring), keep[0].shape[0]
+    t.parent, t.is_leaf = capi.ptr(keep[0], capi.c_int32_p), capi.ptr(keep[1], capi.c_uint8_p)
+    t.desc, t.weight = capi.ptr(keep[2], capi.c_uint8_p), capi.ptr(keep[3], capi.c_double_p)
+    return t, keep
+
+
+def bow_outputs(n: int, stages: bool = True) -> dict:
+    """The arrays of an osh_bow_result for a frame of n features."""
+    o = dict(n_words=np.zeros(1, np.int32), word_id=np.zeros(n, np.int32), word_value=np.zeros(n, np.float64),
+             n_nodes=np.zeros(1, np.int32), node_id=np.zeros(n, np.int32), node_start=np.zeros(n + 1, np.int32),
+             node_feat=np.zeros(n, np.int32))
+    if stages:
+        o.update(feat_word=np.zeros(n, np.int32), feat_node=np.zeros(n, np.int32), feat_dist=np.zeros(n, np.int32))
+    return o
+
+
+def bow_trim(o: dict) -> dict:
+    """The outputs cut to the entries the call filled: n_words words, n_nodes nodes and their features."""
+    nw, nn = int(o["n_words"][0]), int(o["n_nodes"][0])
+    t = dict(o, word_id=o["word_id"][:nw], word_value=o["word_value"][:nw], node_id=o["node_id"][:nn], node_start=o["node_start"][:nn + 1])
+    t["node_feat"] = o["node_feat"][:int(t["node_start"][nn])]
+    del t["n_words"], t["n_nodes"]
+    return t
+
+
+def bow_args(frames, stages: bool = False):
+    """The osh_bow_frame / osh_bow_result arrays of OrbMatcher.bow_transform for repeated calls: (frames, results, the arrays that
+    keep their pointers alive, the per-frame dicts of output arrays)."""
+    n_frames = len(frames)
+    cf = (capi.BowFrame * max(n_frames, 1))()
+    cr = (capi.BowResult * max(n_frames, 1))()
+    keep, outs = [], []
+    for k, fr in enumerate(frames):
+        d = np.ascontiguousarray(fr, dtype=np.uint8).reshape(-1, 32)
+        cf[k].n, cf[k].desc = d.shape[0], capi.ptr(d, capi.c_uint8_p)
+        o = bow_outputs(d.shape[0], stages)
+        _wire_outputs(cr[k], o)
+        keep.append(d)
         outs.append(o)
     return cf, cr, keep, outs
 
