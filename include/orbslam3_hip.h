@@ -286,6 +286,11 @@ typedef struct osh_posei_result {
 
 int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_problem* problems, osh_posei_result* results);
 
+/* Debug / parity aid: H (n x n, row-major) and b (n) of the first Gauss-Newton iteration of one frame, every edge active and
+ * Huber on; n = 15 (mode 0) or 30 (mode 1), unknowns [current P V G A], then in mode 1 [previous P V G A].  The same kernel as
+ * osh_posei_optimize, told to leave after its first buildSystem. */
+int osh_posei_linearize(osh_lba_ctx* ctx, const osh_posei_problem* frame, double* H, double* b);
+
 /* Statistics of the Schur work plan of the resident batch: {items, symmetric items, v_mfma_f64_16x16x4 instructions of one
  * pass over every window, useful 6x6x3 products of one pass (upper triangle), contribution slots, reduce entries, landmark records,
  * right-hand-side contribution slots}. */
@@ -395,6 +400,23 @@ typedef struct osh_liba_result {
 
 /* Solve one batch of inertial windows on the device (upload + optimize + download). */
 int osh_liba_solve(osh_lba_ctx* ctx, int32_t n_windows, const osh_liba_problem* problems, osh_liba_result* results);
+
+/* Debug / parity aids of the inertial BA: the launch of osh_liba_solve for ONE window, told to leave after a stage of its first
+ * iteration; the host side brings the kernel's buffers back into the caller's layout.  The reduced system has n = 15 n_opt unknowns,
+ * the 6-dof poses of the optimisable keyframes first, then (v, bg, ba) per keyframe (g2o's vertex order).
+ *   osh_liba_linearize       the first buildSystem: H [n][n], b [n + 3 n_points] (keyframes, then landmarks), Hll [n_points][3][3],
+ *                            Hpl [n_edges][6][3] in the caller's edge order (zero for an edge of a fixed keyframe; a left + right
+ *                            pair's one block under its left edge), the robust chi2 before it, and
+ *                            info[5] = {LDL^T panel width NB (24: LDS panels, 6: group factorisation), blocks per window G, chunks
+ *                            per pose row C, 1 if the banded interleaved layout was used, number of link colours}.
+ *   osh_liba_inertial_edges  per link what the kernel keeps of EdgeInertial: J [n_links][9][24] (columns P1 V1 G1 A1 P2 V2),
+ *                            Wr [n_links][9] = -rho' W r, rho1 [n_links] (Huber's rho', 1 for a link that is not robustified).
+ *   osh_liba_debug_trial     the first trial: S [n][n] (both triangles filled from the one the kernel forms), bs [n], the keyframe
+ *                            step x [n] and the landmark step x_landmarks [n_points][3] (trial point - point).  lambda <= 0 takes
+ *                            the default (kLmTau x the largest diagonal entry); lambda_used returns the value used.  Two launches. */
+int osh_liba_linearize(osh_lba_ctx* ctx, const osh_liba_problem* problem, double* H, double* b, double* Hll, double* Hpl, double* chi2, int32_t info[5]);
+int osh_liba_inertial_edges(osh_lba_ctx* ctx, const osh_liba_problem* problem, double* J, double* Wr, double* rho1);
+int osh_liba_debug_trial(osh_lba_ctx* ctx, const osh_liba_problem* problem, double lambda, double* S, double* bs, double* x, double* x_landmarks, double* lambda_used);
 
 /* Diagnostics of the calling thread's last osh_liba_solve: the number of thread blocks that worked on each window (8 for the
  * tracker's single window, 1 for a large batch) and, for window 0, shader-clock cycles per phase of the optimisation

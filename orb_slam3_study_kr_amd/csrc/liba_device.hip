@@ -47,6 +47,7 @@ __host__ __device__ constexpr size_t liba_scratch_doubles(int NB, int W) {
 struct LibaOut {
   double chi2_initial, chi2_final;
   int iterations, trials, n_trace, sel;
+  int chunks;          // C, the chunks per pose row (written by a run that stops after a stage only)
   double chi2_trace[OSH_LBA_MAX_TRACE], lambda_trace[OSH_LBA_MAX_TRACE];
   int trials_trace[OSH_LBA_MAX_TRACE];
   long long prof[8];   // shader-clock cycles of block 0 per phase: linearise, assembly, Dinv, Schur, LDL^T, back-substitution, errors, outputs
@@ -79,7 +80,13 @@ struct LibaView {
   double* out_chi2; unsigned char* out_depth;   // result arena: per edge, caller's order
   int* res_abort; double* res_pose; double* res_vba; double* res_pts;   // result arena: abort word, final [sum N][24], [sum N][9], [sum L][3]
   int test_abort;   // OSH_LIBA_TEST_ABORT: make the first group barrier of the launch give up (exercises the one-block retry)
+  int stop_after;   // 0: the whole optimisation; else leave after this stage of the first iteration (the debug exports, kLibaStop*)
 };
+// stages a run can stop after: the work buffers then hold what the stage left.  Set by the host, the same for every block, and tested
+// right after a barrier of the group that every block has passed: all blocks of a group leave at the same barrier count.
+constexpr int kLibaStopLinearised = 1;   // buildSystem: H, b (links), ppart, Hll, bl, Hpl, linkQ
+constexpr int kLibaStopSchur = 2;        // + the first trial's S, bs (and ctrl[0], the default lambda)
+constexpr int kLibaStopStep = 3;         // + x and the trial buffers after the back-substitution
 
 // deterministic block reductions over kLT threads
 __device__ __forceinline__ double blk_sum(double v, double* shw) {
@@ -250,6 +257,7 @@ __device__ __noinline__ double eval_partial(const LibaView& v, const LibaDesc& d
 
 #define OSH_GSYNC() do { if (!grp_sync(g, lds_flag)) return; } while (0)
 #define OSH_PROF(i) do { if (prof_on) { const long long _n = clock64(); prof[i] += _n - prof_last; prof_last = _n; } } while (0)
+#define OSH_STOP_AFTER(stage) do { if (v.stop_after == (stage)) { if (m == 0 && tid == 0) out.chunks = C; return; } } while (0)
 
 // linearisation of one visual edge: robust weight, weighted residual, JX (3x3), Jp (3x6)
 struct EdgeLin { double ww, wr[3], JX[9], Jp[18]; };
@@ -1208,6 +1216,7 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
       liba_assemble_links(c, sel, col);
       OSH_GSYNC();
     }
+    OSH_STOP_AFTER(kLibaStopLinearised);
     if (!lambda_known) {
       // setLambda's default: kLmTau x the largest diagonal entry of the full Hessian (computeLambdaInit)
       if (m == 0) {
@@ -1241,6 +1250,7 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
       OSH_PROF(2);
       liba_schur(c, lambda);
       OSH_GSYNC();
+      OSH_STOP_AFTER(kLibaStopSchur);
       OSH_PROF(3);
       if constexpr (NB == kLNB) { if (m == 0) liba_solve<NB>(c, sh); }
       else { if (!liba_solve_group(c, g, lds_flag)) return; }
@@ -1249,6 +1259,7 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
       OSH_PROF(4);
       double sc = liba_backsub(c, sel, lambda, ok2);
       OSH_GSYNC();
+      OSH_STOP_AFTER(kLibaStopStep);
       OSH_PROF(5);
       double tempChi = eval_partial(v, d, trs, g);
       if (!grp_sum2(g, tempChi, sc, shw, lds_flag)) return;
@@ -1275,6 +1286,7 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
 }
 #undef OSH_GSYNC
 #undef OSH_PROF
+#undef OSH_STOP_AFTER
 
 }  // namespace osh
 
@@ -1286,10 +1298,20 @@ using namespace osh;
 namespace {
 thread_local int g_liba_last_group = 0;
 thread_local long long g_liba_last_prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+// what a debug export asks of liba_run: the stage to stop after and where the un-permuted buffers of window 0 go (NULL: not wanted)
+struct LibaDebug {
+  int stop_after;
+  double lambda;                                   // kLibaStopSchur / kLibaStopStep: > 0 replaces the problem's lambda_init, else the default
+  double *H, *b, *Hll, *Hpl, *chi2; int32_t* info; // kLibaStopLinearised (info: NB, G, C, il, n_colours -- every stage)
+  double *J, *Wr, *rho1;                           // kLibaStopLinearised: per link
+  double *S, *bs, *lambda_used;                    // kLibaStopSchur
+  double *x, *xl;                                  // kLibaStopStep
+};
 }  // namespace
 
-extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_problem* pr, osh_liba_result* res) {
-  if (!ctx || nw <= 0 || !pr || !res) { set_error("osh_liba_solve: bad arguments"); return OSH_ERR_INVALID; }
+// upload + one launch + download.  dbg: one window, stopped after a stage; its buffers come back in the caller's layout (the reduced
+// system with the 6-dof poses first, then v bg ba per keyframe; edges in the caller's order) and res is not touched.
+static int liba_run(osh_lba_ctx* ctx, int32_t nw, const osh_liba_problem* pr, osh_liba_result* res, const LibaDebug* dbg) {
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(lba_stream(ctx, &device, &s));
@@ -1307,6 +1329,7 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
     d.peloff_off = (int)PO; d.pel_off = (int)EF; d.lmpose_off = (int)LP; d.H_off = (long long)Htot; d.b_off = (int)btot;
     std::memcpy(d.Rcb, p.Rcb, 72); std::memcpy(d.tcb, p.tcb, 24); std::memcpy(d.tbc, p.tbc, 24); std::memcpy(d.cam, p.cam, 40);
     d.huber_mono = p.huber_mono; d.huber_stereo = p.huber_stereo; d.huber_inertial = p.huber_inertial; d.lambda_init = p.lambda_init;
+    if (dbg) { d.max_iter = 1; if (dbg->stop_after != kLibaStopLinearised) d.lambda_init = dbg->lambda > 0 ? dbg->lambda : 0.0; }
     d.kb8_on = p.kb8 ? 1 : 0;
     for (int k = 0; k < 4; ++k) d.kb8[k] = p.kb8 ? p.kb8[k] : 0.0;
     d.rig_on = (p.kb8 && p.cam2 && p.trl) ? 1 : 0;
@@ -1412,12 +1435,14 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
   const auto r_pose = out.take<double>((btot / 15) * 24), r_vba = out.take<double>((btot / 15) * 9), r_pts = out.take<double>(L * 3),
              r_chi2 = out.take<double>(E);
   const auto r_depth = out.take<unsigned char>(E);
-  const auto a_pose1 = work.take<double>(K * 24), a_vba1 = work.take<double>(NV * 9), a_pts1 = work.take<double>(L * 3), a_eh = work.take<double>(E * 9),
-             a_ep = work.take<double>(EF * 27), a_bfull = work.take<double>(btot), a_Hpl = work.take<double>(EF * 18), a_BD = work.take<double>(EF * 18),
-             a_Hll = work.take<double>(L * 6), a_bl = work.take<double>(L * 3), a_dinv = work.take<double>(L * 9), a_H = work.take<double>(Htot),
-             a_S = work.take<double>(Htot), a_b = work.take<double>(btot), a_bs = work.take<double>(btot), a_x = work.take<double>(btot),
-             a_linkQ = work.take<double>(NL * kLinkQ), a_ppart = work.take<double>((btot / 15) * kPoseChunks * 27),
-             a_red = work.take<double>((size_t)nw * 4 * kLG * 2), a_ctrl = work.take<double>((size_t)nw * 4);
+  // a debug run keeps the buffers it reports in the result arena, so that they come back with the one download
+  Layout& kept = dbg ? out : work;
+  const auto a_pose1 = work.take<double>(K * 24), a_vba1 = work.take<double>(NV * 9), a_pts1 = kept.take<double>(L * 3), a_eh = work.take<double>(E * 9),
+             a_ep = work.take<double>(EF * 27), a_bfull = work.take<double>(btot), a_Hpl = kept.take<double>(EF * 18), a_BD = work.take<double>(EF * 18),
+             a_Hll = kept.take<double>(L * 6), a_bl = kept.take<double>(L * 3), a_dinv = work.take<double>(L * 9), a_H = kept.take<double>(Htot),
+             a_S = kept.take<double>(Htot), a_b = kept.take<double>(btot), a_bs = kept.take<double>(btot), a_x = kept.take<double>(btot),
+             a_linkQ = kept.take<double>(NL * kLinkQ), a_ppart = kept.take<double>((btot / 15) * kPoseChunks * 27),
+             a_red = work.take<double>((size_t)nw * 4 * kLG * 2), a_ctrl = kept.take<double>((size_t)nw * 4);
   StagedCall* B = attachment<StagedCall>(ctx, kAttachLiba);
   if (!B) return OSH_ERR_INVALID;
   OSH_TRY(B->reserve(in, out, work.bytes, (size_t)64 << 20));   // an arena of at least 64 MiB: large page fragments
@@ -1517,20 +1542,22 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
   char* const din = B->dev_in();
   char* const dres = B->dev_out();
   char* const dwork = B->dev_work();
+  char* const dkept = dbg ? dres : dwork;
   LibaView v{};
   v.desc = o_desc.in(din); v.out = r_out.in(dres);
   v.pose[0] = o_pose.in(din); v.vba[0] = o_vba.in(din); v.pts[0] = o_pts.in(din);
-  v.pose[1] = a_pose1.in(dwork); v.vba[1] = a_vba1.in(dwork); v.pts[1] = a_pts1.in(dwork);
+  v.pose[1] = a_pose1.in(dwork); v.vba[1] = a_vba1.in(dwork); v.pts[1] = a_pts1.in(dkept);
   v.e_pose = o_ep.in(din); v.e_point = o_el.in(din); v.e_kind = o_kind.in(din); v.e_obs = o_obs.in(din); v.e_info = o_info.in(din); v.e_orig = o_eo.in(din);
   v.lm_off = o_lmo.in(din); v.pel_off = o_po.in(din); v.pel_edge = o_pel.in(din); v.lm_pose_edge = o_lmpe.in(din);
   v.link_prev = o_lp.in(din); v.link_cur = o_lc.in(din); v.link_bias = o_lb.in(din);
   v.link_preint = o_pre.in(din); v.link_info = o_li.in(din); v.link_info_g = o_lg.in(din); v.link_info_a = o_la.in(din);
   v.link_robust = o_rob.in(din);
-  v.Hpl = a_Hpl.in(dwork); v.BD = a_BD.in(dwork); v.Hll = a_Hll.in(dwork); v.bl = a_bl.in(dwork);
-  v.dinv = a_dinv.in(dwork); v.H = a_H.in(dwork); v.b = a_b.in(dwork); v.S = a_S.in(dwork); v.bs = a_bs.in(dwork);
-  v.x = a_x.in(dwork); v.linkQ = a_linkQ.in(dwork); v.ppart = a_ppart.in(dwork);
+  v.Hpl = a_Hpl.in(dkept); v.BD = a_BD.in(dwork); v.Hll = a_Hll.in(dkept); v.bl = a_bl.in(dkept);
+  v.dinv = a_dinv.in(dwork); v.H = a_H.in(dkept); v.b = a_b.in(dkept); v.S = a_S.in(dkept); v.bs = a_bs.in(dkept);
+  v.x = a_x.in(dkept); v.linkQ = a_linkQ.in(dkept); v.ppart = a_ppart.in(dkept);
   v.bar = o_bar.in(din); v.abort_flag = o_abort.in(din);
-  v.red = a_red.in(dwork); v.ctrl = a_ctrl.in(dwork); v.nw = nw;
+  v.red = a_red.in(dwork); v.ctrl = a_ctrl.in(dkept); v.nw = nw;
+  v.stop_after = dbg ? dbg->stop_after : 0;
   v.force_heavy = getenv("OSH_LIBA_HEAVY_BARRIER") ? 1 : 0;
   v.eh = a_eh.in(dwork); v.ep = a_ep.in(dwork); v.bfull = a_bfull.in(dwork); v.E_total = E; v.EF_total = EF;
   v.link_colour = o_col.in(din);
@@ -1574,6 +1601,72 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
   }
   if (*r_abort.in(hr)) { set_error("k_liba: a barrier of a window's block group did not complete (group of %d blocks)", G); return OSH_ERR_DEVICE; }
   const LibaOut* h_out = r_out.in(hr);
+  if (dbg) {
+    // window 0 in the caller's layout: the reduced system with the poses first (whatever LibaDesc::il says), the pose rows' visual
+    // part summed over its chunks, Hll unpacked, Hpl per edge of the caller (a left + right pair's block under its left edge)
+    const LibaDesc& d = h_desc[0];
+    const int n = d.n, N = d.N, C = h_out[0].chunks;
+    std::vector<int> to_ref(n);
+    for (int i = 0; i < N; ++i) {
+      for (int r = 0; r < 6; ++r) to_ref[(d.il ? 15 * i : 6 * i) + r] = 6 * i + r;
+      for (int r = 0; r < 9; ++r) to_ref[(d.il ? 15 * i + 6 : 6 * N + 9 * i) + r] = 6 * N + 9 * i + r;
+    }
+    const double *hH = a_H.in(hr), *hb = a_b.in(hr), *hpp = a_ppart.in(hr), *hHll = a_Hll.in(hr), *hbl = a_bl.in(hr), *hHpl = a_Hpl.in(hr);
+    auto up = [](int r, int c) { const int lo = r < c ? r : c, hi = r < c ? c : r; return lo * 6 - lo * (lo - 1) / 2 + (hi - lo); };
+    if (dbg->info) { dbg->info[0] = NB; dbg->info[1] = G; dbg->info[2] = C; dbg->info[3] = d.il; dbg->info[4] = d.n_colours; }
+    if (dbg->chi2) *dbg->chi2 = h_out[0].chi2_initial;
+    if (dbg->H) {
+      std::fill(dbg->H, dbg->H + (size_t)n * n, 0.0);
+      for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c)
+          if (!d.il || std::abs(r - c) <= d.bw) dbg->H[(size_t)to_ref[r] * n + to_ref[c]] = hH[(size_t)r * n + c];   // outside the band nothing is written
+      for (int i = 0; i < N; ++i)
+        for (int r = 0; r < 6; ++r)
+          for (int c = 0; c < 6; ++c)
+            for (int ch = 0; ch < C; ++ch) dbg->H[(size_t)(6 * i + r) * n + 6 * i + c] += hpp[((size_t)i * kPoseChunks + ch) * 27 + up(r, c)];
+    }
+    if (dbg->b) {
+      for (int k = 0; k < n; ++k) dbg->b[to_ref[k]] = hb[k];
+      for (int i = 0; i < N; ++i)
+        for (int r = 0; r < 6; ++r)
+          for (int ch = 0; ch < C; ++ch) dbg->b[6 * i + r] += hpp[((size_t)i * kPoseChunks + ch) * 27 + 21 + r];
+      for (size_t k = 0; k < (size_t)d.L * 3; ++k) dbg->b[n + k] = hbl[k];
+    }
+    if (dbg->Hll)
+      for (int j = 0; j < d.L; ++j) {
+        const double* h = hHll + (size_t)j * 6;
+        double* o = dbg->Hll + (size_t)j * 9;
+        o[0] = h[0]; o[1] = o[3] = h[1]; o[2] = o[6] = h[2]; o[4] = h[3]; o[5] = o[7] = h[4]; o[8] = h[5];
+      }
+    if (dbg->Hpl) {
+      std::fill(dbg->Hpl, dbg->Hpl + (size_t)d.E * 18, 0.0);
+      const int n_free_edges = h_po[d.peloff_off + N];
+      for (int idx = 0; idx < n_free_edges; ++idx) {
+        const int x = h_pel[(size_t)d.edge_off + idx];
+        if (x > 0 && h_el[x - 1] == h_el[x] && h_ep[x - 1] == h_ep[x]) continue;   // the right edge of a pair: its term is in the left edge's block
+        for (int k = 0; k < 18; ++k) dbg->Hpl[(size_t)h_eo[x] * 18 + k] = hHpl[(size_t)k * EF + idx];
+      }
+    }
+    const double* hQ = a_linkQ.in(hr);
+    for (int l = 0; l < d.NL; ++l) {
+      const double* Q = hQ + (size_t)l * kLinkQ + 600;
+      if (dbg->J) std::memcpy(dbg->J + (size_t)l * 216, Q, 216 * 8);
+      if (dbg->Wr) std::memcpy(dbg->Wr + (size_t)l * 9, Q + 216, 72);
+      if (dbg->rho1) dbg->rho1[l] = Q[225];
+    }
+    if (dbg->S) {   // the kernel forms the upper triangle (of its own order of the unknowns)
+      const double* hS = a_S.in(hr);
+      std::fill(dbg->S, dbg->S + (size_t)n * n, 0.0);
+      for (int r = 0; r < n; ++r)
+        for (int c = r; c < n; ++c)
+          if (!d.il || c - r <= d.bw) dbg->S[(size_t)to_ref[r] * n + to_ref[c]] = dbg->S[(size_t)to_ref[c] * n + to_ref[r]] = hS[(size_t)r * n + c];
+    }
+    if (dbg->bs) { const double* hbs = a_bs.in(hr); for (int k = 0; k < n; ++k) dbg->bs[to_ref[k]] = hbs[k]; }
+    if (dbg->lambda_used) *dbg->lambda_used = dbg->lambda > 0 ? dbg->lambda : a_ctrl.in(hr)[0];
+    if (dbg->x) { const double* hx = a_x.in(hr); for (int k = 0; k < n; ++k) dbg->x[to_ref[k]] = hx[k]; }
+    if (dbg->xl) { const double* t = a_pts1.in(hr); for (size_t k = 0; k < (size_t)d.L * 3; ++k) dbg->xl[k] = t[k] - h_pts[k]; }   // the trial buffer holds point + step
+    return OSH_OK;
+  }
   g_liba_last_group = G;
   std::memcpy(g_liba_last_prof, h_out[0].prof, sizeof(g_liba_last_prof));
   for (int w = 0; w < nw; ++w) {
@@ -1600,6 +1693,37 @@ extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_probl
     if (r.edge_depth_pos && d.E) std::memcpy(r.edge_depth_pos, r_depth.in(hr) + d.edge_off, (size_t)d.E);
   }
   return OSH_OK;
+}
+
+extern "C" int osh_liba_solve(osh_lba_ctx* ctx, int32_t nw, const osh_liba_problem* pr, osh_liba_result* res) {
+  if (!ctx || nw <= 0 || !pr || !res) { set_error("osh_liba_solve: bad arguments"); return OSH_ERR_INVALID; }
+  return liba_run(ctx, nw, pr, res, nullptr);
+}
+
+// ---- debug / parity aids: the same launch, stopped after a stage of its first iteration (see kLibaStop*)
+extern "C" int osh_liba_linearize(osh_lba_ctx* ctx, const osh_liba_problem* problem, double* H, double* b, double* Hll, double* Hpl, double* chi2, int32_t* info) {
+  if (!ctx || !problem || !H || !b || !Hll || !Hpl || !chi2 || !info) { set_error("osh_liba_linearize: bad arguments"); return OSH_ERR_INVALID; }
+  LibaDebug g{};
+  g.stop_after = kLibaStopLinearised; g.H = H; g.b = b; g.Hll = Hll; g.Hpl = Hpl; g.chi2 = chi2; g.info = info;
+  return liba_run(ctx, 1, problem, nullptr, &g);
+}
+
+extern "C" int osh_liba_inertial_edges(osh_lba_ctx* ctx, const osh_liba_problem* problem, double* J, double* Wr, double* rho1) {
+  if (!ctx || !problem || !J || !Wr || !rho1) { set_error("osh_liba_inertial_edges: bad arguments"); return OSH_ERR_INVALID; }
+  LibaDebug g{};
+  g.stop_after = kLibaStopLinearised; g.J = J; g.Wr = Wr; g.rho1 = rho1;
+  return liba_run(ctx, 1, problem, nullptr, &g);
+}
+
+extern "C" int osh_liba_debug_trial(osh_lba_ctx* ctx, const osh_liba_problem* problem, double lambda, double* S, double* bs, double* x, double* x_landmarks, double* lambda_used) {
+  if (!ctx || !problem || !S || !bs || !x || !x_landmarks || !lambda_used) { set_error("osh_liba_debug_trial: bad arguments"); return OSH_ERR_INVALID; }
+  // two runs: the factorisation of a map-sized system works in place, so S is read before it and the step after it
+  LibaDebug g{};
+  g.stop_after = kLibaStopSchur; g.lambda = lambda; g.S = S; g.bs = bs; g.lambda_used = lambda_used;
+  OSH_TRY(liba_run(ctx, 1, problem, nullptr, &g));
+  LibaDebug h{};
+  h.stop_after = kLibaStopStep; h.lambda = lambda; h.x = x; h.xl = x_landmarks;
+  return liba_run(ctx, 1, problem, nullptr, &h);
 }
 
 // phase cycle counters of window 0 of the last osh_liba_solve on this thread (block 0 of its group) and the group size used

@@ -37,13 +37,14 @@ struct PoseiDesc {
   float chi2_mono[4], chi2_stereo[4];
   int iters[4];
 };
-struct PoseiOut { double P[24], s[9], H[900]; int n_bad, n_inliers, rounds; };
+struct PoseiOut { double P[24], s[9], H[900], b[30]; int n_bad, n_inliers, rounds; };   // b: written by osh_posei_linearize only
 struct PoseiView {
   const PoseiDesc* desc;
   PoseiOut* out;
   const double* X; const unsigned char* kind; const double* obs; const double* info; const unsigned char* close;
   double* chi2; unsigned char* level; unsigned char* outlier;
   int ecap;                   // edges per frame the block's dynamic LDS can hold (0: every access goes to global memory)
+  int stop_after;             // 0: the whole optimisation; 1 (osh_posei_linearize): leave after the first build, shH / shb in out.H / out.b
 };
 
 // A x = b for a symmetric n x n system (n <= NMAX = 16 or 32: 15 unknowns of the frame, 30 with the previous frame free) held row-major in LDS, by ONE wavefront: lane j keeps column j, the pivot row
@@ -322,6 +323,11 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
     bool ok = true;
     for (int it = 0; it < d.iters[round] && ok; ++it) {
       build(robust);
+      if (v.stop_after) {   // the same for every block and thread of the launch: all of them leave here
+        for (int k = tid; k < n * n; k += kIT) out.H[k] = shH[k];
+        if (tid < n) out.b[tid] = shb[tid];
+        return;
+      }
       if (tid < 64) {
         const bool good = mode1 ? posei_solve_wave<32>(shH, shb, n, shU, shx) : posei_solve_wave<16>(shH, shb, n, shU, shx);   // on failure x keeps the previous values and is still applied
         if (tid == 0) sh_ok = good ? 1 : 0;
@@ -490,8 +496,9 @@ __global__ __launch_bounds__(kIT) void k_posei(PoseiView v) {
 
 using namespace osh;
 
-extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_problem* pr, osh_posei_result* res) {
-  if (!ctx || n <= 0 || !pr || !res) { set_error("osh_posei_optimize: bad arguments"); return OSH_ERR_INVALID; }
+// upload + one launch + download.  stop_after = 1: the kernel leaves after its first build and H_out / b_out get frame 0's system
+// (n x n and n entries, n = 15 or 30; unknowns [cur P V G A], then in mode 1 [prev P V G A]); res is not touched then.
+static int posei_run(osh_lba_ctx* ctx, int32_t n, const osh_posei_problem* pr, osh_posei_result* res, int stop_after, double* H_out, double* b_out) {
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(lba_stream(ctx, &device, &s));
@@ -582,6 +589,7 @@ extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_p
   for (int f = 0; f < n; ++f) e_max = std::max(e_max, h_desc[f].E);
   constexpr int kPoseiMaxCached = 1400;
   v.ecap = (e_max > 0 && e_max <= kPoseiMaxCached) ? ((e_max + 63) & ~63) : 0;
+  v.stop_after = stop_after;
   const size_t dyn_bytes = (size_t)v.ecap * (8 * 8 + 4) + 16;
   OSH_TRY(allow_dynamic_lds(device, 128 * 1024, k_posei));
   hipLaunchKernelGGL(k_posei, dim3((unsigned)n), dim3(kIT), dyn_bytes, s, v);
@@ -589,6 +597,12 @@ extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_p
   OSH_TRY(B->download(s));
   char* const hr = B->host_out();
   const PoseiOut* h_out = o_out.in(hr);
+  if (stop_after) {
+    const int nu = h_desc[0].mode == 1 ? 30 : 15;
+    std::memcpy(H_out, h_out[0].H, (size_t)nu * nu * 8);
+    std::memcpy(b_out, h_out[0].b, (size_t)nu * 8);
+    return OSH_OK;
+  }
   for (int f = 0; f < n; ++f) {
     const PoseiDesc& d = h_desc[f];
     if (res[f].outlier && d.E) std::memcpy(res[f].outlier, o_outlier.in(hr) + d.edge_off, (size_t)d.E);
@@ -606,4 +620,17 @@ extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_p
     std::fill(r.H + nH, r.H + 900, 0.0);
   }
   return OSH_OK;
+}
+
+extern "C" int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_problem* pr, osh_posei_result* res) {
+  if (!ctx || n <= 0 || !pr || !res) { set_error("osh_posei_optimize: bad arguments"); return OSH_ERR_INVALID; }
+  return posei_run(ctx, n, pr, res, 0, nullptr, nullptr);
+}
+
+// Debug / parity aid: H (n x n, row-major) and b (n) of the first Gauss-Newton iteration of one frame (every edge active, Huber on),
+// n = 15 (mode 0) or 30 (mode 1), unknowns [cur P V G A] then [prev P V G A] -- the system the kernel hands to its LDL^T.
+extern "C" int osh_posei_linearize(osh_lba_ctx* ctx, const osh_posei_problem* frame, double* H, double* b) {
+  if (!ctx || !frame || !H || !b) { set_error("osh_posei_linearize: bad arguments"); return OSH_ERR_INVALID; }
+  if (frame->iterations[0] <= 0) { set_error("osh_posei_linearize: the first round has no iteration, so the kernel builds no system"); return OSH_ERR_INVALID; }
+  return posei_run(ctx, 1, frame, nullptr, 1, H, b);
 }

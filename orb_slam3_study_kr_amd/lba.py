@@ -152,6 +152,38 @@ class LbaSolver:
                    "osh_lba_debug_trial", self.lib)
         return S, bs, x
 
+    def linearize_inertial(self, w) -> dict:
+        """``osh_liba_linearize``: the system of the first buildSystem of one inertial window in the layout of the oracle's
+        liba_linearize, and the path taken (NB, G, C, il, n_colours)."""
+        n, L, E = 15 * w.n_opt, w.n_points, w.n_edges
+        out = dict(H=np.zeros((n, n)), b=np.zeros(n + 3 * L), Hll=np.zeros((L, 3, 3)), Hpl=np.zeros((E, 6, 3)))
+        chi, info = np.zeros(1), np.zeros(5, dtype=np.int32)
+        p, d = w.as_struct(), capi.c_double_p
+        capi.check(self.lib.osh_liba_linearize(self.ctx, C.byref(p), capi.ptr(out["H"], d), capi.ptr(out["b"], d), capi.ptr(out["Hll"], d),
+                                               capi.ptr(out["Hpl"], d), capi.ptr(chi, d), capi.ptr(info, capi.c_int32_p)),
+                   "osh_liba_linearize", self.lib)
+        out["chi2"] = float(chi[0])
+        out["info"] = dict(zip(("NB", "G", "C", "il", "n_colours"), (int(k) for k in info)))
+        return out
+
+    def inertial_edges(self, w):
+        """``osh_liba_inertial_edges``: (J [links][9][24], -rho' W r [links][9], rho' [links]) of the first linearisation."""
+        NL = w.n_links
+        J, Wr, rho1 = np.zeros((NL, 9, 24)), np.zeros((NL, 9)), np.zeros(NL)
+        p, d = w.as_struct(), capi.c_double_p
+        capi.check(self.lib.osh_liba_inertial_edges(self.ctx, C.byref(p), capi.ptr(J, d), capi.ptr(Wr, d), capi.ptr(rho1, d)),
+                   "osh_liba_inertial_edges", self.lib)
+        return J, Wr, rho1
+
+    def debug_trial_inertial(self, w, lam: float = 0.0):
+        """``osh_liba_debug_trial``: (S, bs, keyframe step, landmark step, lambda used) of the first trial; lam <= 0: the default lambda."""
+        n, L = 15 * w.n_opt, w.n_points
+        S, bs, x, xl, used = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros((L, 3)), np.zeros(1)
+        p, d = w.as_struct(), capi.c_double_p
+        capi.check(self.lib.osh_liba_debug_trial(self.ctx, C.byref(p), float(lam), capi.ptr(S, d), capi.ptr(bs, d), capi.ptr(x, d), capi.ptr(xl, d),
+                                                 capi.ptr(used, d)), "osh_liba_debug_trial", self.lib)
+        return S, bs, x, xl, float(used[0])
+
     # -- profiling ------------------------------------------------------------------------------
     def optimize_poses(self, frames):
         """``osh_pose_optimize``: Optimizer::PoseOptimization's four rounds for every frame of the batch, one block per frame."""
@@ -203,6 +235,15 @@ class LbaSolver:
             a.bind(r)
         capi.check(self.lib.osh_posei_optimize(self.ctx, n, probs, rs), "osh_posei_optimize", self.lib)
         return [a.read(r, f.mode) for r, a, f in zip(rs, res, frames)]
+
+    def linearize_pose_inertial(self, frame):
+        """``osh_posei_linearize``: H and b of the first Gauss-Newton iteration of one frame ([current P V G A | previous P V G A])."""
+        n = 30 if frame.mode == 1 else 15
+        H, b = np.zeros((n, n)), np.zeros(n)
+        p = frame.as_struct()
+        capi.check(self.lib.osh_posei_linearize(self.ctx, C.byref(p), capi.ptr(H, capi.c_double_p), capi.ptr(b, capi.c_double_p)),
+                   "osh_posei_linearize", self.lib)
+        return H, b
 
     def plan_stats(self) -> dict:
         st = np.zeros(8, dtype=np.int64)

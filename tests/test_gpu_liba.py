@@ -47,6 +47,13 @@ def test_config4_stereo_inertial_window(solver, ob):
     _check(solver.solve_inertial([w])[0], ob.liba_solve(w), w)
 
 
+def test_config4_at_the_benched_size(solver, ob):
+    """The window bench.py times for config 4 (n_points=3600: 2 032 landmarks seen, 29 937 edges), not only its default-sized sibling."""
+    w = si.make_inertial_window(11, n_points=3600)
+    assert (w.n_points, w.n_edges) == (2032, 29937)
+    _check(solver.solve_inertial([w])[0], ob.liba_solve(w), w)
+
+
 def test_small_and_large_variants_in_one_batch(solver, ob):
     ws = [si.make_inertial_window(21, n_opt=3, n_fixed=2, n_points=80),
           si.make_inertial_window(22, n_opt=6, n_fixed=5, n_points=400, rec_init=True),
