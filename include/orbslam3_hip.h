@@ -310,6 +310,14 @@ int osh_lba_schur_plan_stats(const osh_lba_problem* problem, int64_t stats[8]);
  * of the packing. */
 int osh_lba_pack_check(int32_t n_windows, const osh_lba_problem* problems, int32_t n_threads, int64_t stats[8], double* pack_ms);
 
+/* Host-only self check of the packer osh_liba_solve and the inertial debug exports run before their one copy (needs no GPU):
+ * window offsets, landmark-major edge order with a rig's left + right pairs, the pose-by-pose walk order, the (landmark, pose) ->
+ * block table, link colours, the band of map-sized problems, the arena layout.  A problem osh_liba_solve refuses is refused here
+ * with the same code and message.  stats = {edges, edges of optimisable keyframes, left + right pairs, largest colour count of a
+ * window, windows in the banded layout, bytes of the three arenas, LDL^T panel width, panel row stride}. */
+struct osh_liba_problem;
+int osh_liba_pack_check(int32_t n_windows, const struct osh_liba_problem* problems, int64_t stats[8]);
+
 /* Host-only self check of the Levenberg-Marquardt controller every solver of this library shares (needs no GPU): plays
  * g2o's optimize() loop from `current_chi` and `lambda` over a script of n_script trials {tempChi, computeScale sum, solve_ok}
  * (script[3 k ..]; solve_ok 0: the linear solve failed).  Per trial played: accepted[k], rho[k] and the lambda[k] / ni[k]

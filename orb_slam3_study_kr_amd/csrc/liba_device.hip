@@ -29,29 +29,8 @@
 
 namespace osh {
 
-constexpr int kLT = 256;      // threads of a block: one wavefront per SIMD, so a phase may use all 512 registers (with 512 threads the
-                              // per-edge code spilled: 1.2 KB of scratch per lane)
-constexpr int kLNB = 24;      // LDL^T panel width (12 or 6 for windows whose 24-wide panels do not fit LDS: k_liba<NB>)
-constexpr int kLG = 32;       // blocks per window at most (one XCD's worth of a group)
 constexpr int kPB = 16;       // pivots per step of the group factorisation (liba_solve_group)
-constexpr int kPoseChunks = 8;   // a pose row's edges are summed in at most this many chunks
-constexpr int kLinkQ = 832;   // per link: J^T W J (24x24), -J^T W r (24), then J (9x24), -W r (9), rho'
-// LDS scratch: the LDL^T panels of the reduced system when they fit one block's LDS (NB = 24: up to 51 keyframes, every LocalInertialBA /
-// MergeInertialBA window, liba_solve); beyond that the group factorises in global memory (NB = 6 names that variant, liba_solve_group)
-// and LDS holds its 16 x 16 blocks and two vectors only.  600 keyframes = a dense 9000 x 9000 system (H and S: 1.3 GB).
-constexpr int kLibaMaxKeyframes = 1200;
-__host__ __device__ constexpr size_t liba_scratch_doubles(int NB, int W) {
-  const size_t need = NB == kLNB ? ldlt_lds_doubles(NB, W, kLT) : (size_t)(6 * 256 + 64 + W + 32);
-  return need > 512 ? need : 512;
-}
-struct LibaOut {
-  double chi2_initial, chi2_final;
-  int iterations, trials, n_trace, sel;
-  int chunks;          // C, the chunks per pose row (written by a run that stops after a stage only)
-  double chi2_trace[OSH_LBA_MAX_TRACE], lambda_trace[OSH_LBA_MAX_TRACE];
-  int trials_trace[OSH_LBA_MAX_TRACE];
-  long long prof[8];   // shader-clock cycles of block 0 per phase: linearise, assembly, Dinv, Schur, LDL^T, back-substitution, errors, outputs
-};
+// (the constants that size the arenas, LibaDesc and LibaOut: liba_pack.h)
 
 struct LibaView {
   const LibaDesc* desc;
@@ -78,7 +57,7 @@ struct LibaView {
   int nw;
   int force_heavy;            // diagnostic: keep the agent-scope fences even when a group shares an XCD (OSH_LIBA_HEAVY_BARRIER=1)
   double* out_chi2; unsigned char* out_depth;   // result arena: per edge, caller's order
-  int* res_abort; double* res_pose; double* res_vba; double* res_pts;   // result arena: abort word, final [sum N][24], [sum N][9], [sum L][3]
+  int* res_abort; double* res_pose; double* res_vba; double* res_pts;   // result arena: abort word (cleared by the host before a launch), final [sum N][24], [sum N][9], [sum L][3]
   int test_abort;   // OSH_LIBA_TEST_ABORT: make the first group barrier of the launch give up (exercises the one-block retry)
   int stop_after;   // 0: the whole optimisation; else leave after this stage of the first iteration (the debug exports, kLibaStop*)
 };
@@ -1167,7 +1146,6 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
   const bool prof_on = (m == 0 && tid == 0);
   long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long prof_last = clock64();
-  if (bid == 0 && tid == 0) *v.res_abort = 0;
   // the trial buffers start as copies of the estimates (the fixed keyframes and the fixed IMU state are only ever read)
   for (int k = gt; k < d.K * 24; k += GT) v.pose[1][(size_t)d.pose_off * 24 + k] = v.pose[0][(size_t)d.pose_off * 24 + k];
   for (int k = gt; k < d.NV * 9; k += GT) v.vba[1][(size_t)d.vel_off * 9 + k] = v.vba[0][(size_t)d.vel_off * 9 + k];
@@ -1291,7 +1269,7 @@ __global__ __launch_bounds__(kLT) void k_liba(LibaView v, int W, int G) {
 }  // namespace osh
 
 // =============================================================================================
-// Host driver: osh_liba_solve (upload + one launch + download)
+// Host driver: osh_liba_solve (describe, lay out, pack -- liba_pack.h; upload + one launch + download here)
 // =============================================================================================
 using namespace osh;
 
@@ -1307,377 +1285,143 @@ struct LibaDebug {
   double *S, *bs, *lambda_used;                    // kLibaStopSchur
   double *x, *xl;                                  // kLibaStopStep
 };
-}  // namespace
 
-// upload + one launch + download.  dbg: one window, stopped after a stage; its buffers come back in the caller's layout (the reduced
-// system with the 6-dof poses first, then v bg ba per keyframe; edges in the caller's order) and res is not touched.
-static int liba_run(osh_lba_ctx* ctx, int32_t nw, const osh_liba_problem* pr, osh_liba_result* res, const LibaDebug* dbg) {
-  int device = 0;
-  hipStream_t s = nullptr;
-  OSH_TRY(lba_stream(ctx, &device, &s));
-  std::vector<LibaDesc> h_desc(nw);
-  size_t K = 0, NV = 0, L = 0, E = 0, NL = 0, Htot = 0, btot = 0, LO = 0, PO = 0, EF = 0, LP = 0;
-  int n_max = 0;
-  for (int w = 0; w < nw; ++w) {
-    const osh_liba_problem& p = pr[w];
-    if (p.n_opt <= 0 || p.n_fixed_imu < 0 || p.n_fixed_imu > 1 || p.n_fixed < 0 || p.n_points < 0 || p.n_edges < 0 || p.n_links < 0 ||
-        p.max_iterations > OSH_LBA_MAX_TRACE) { set_error("window %d: bad sizes", w); return OSH_ERR_INVALID; }
-    LibaDesc& d = h_desc[w];
-    d.N = p.n_opt; d.NV = p.n_opt + p.n_fixed_imu; d.K = d.NV + p.n_fixed; d.L = p.n_points; d.E = p.n_edges; d.NL = p.n_links;
-    d.n = 15 * d.N; d.max_iter = p.max_iterations; d.n_colours = 0; d.il = 0; d.bw = d.n; d.bw_kf = d.N;
-    d.pose_off = (int)K; d.vel_off = (int)NV; d.pt_off = (int)L; d.edge_off = (int)E; d.link_off = (int)NL; d.lmoff_off = (int)LO;
-    d.peloff_off = (int)PO; d.pel_off = (int)EF; d.lmpose_off = (int)LP; d.H_off = (long long)Htot; d.b_off = (int)btot;
-    std::memcpy(d.Rcb, p.Rcb, 72); std::memcpy(d.tcb, p.tcb, 24); std::memcpy(d.tbc, p.tbc, 24); std::memcpy(d.cam, p.cam, 40);
-    d.huber_mono = p.huber_mono; d.huber_stereo = p.huber_stereo; d.huber_inertial = p.huber_inertial; d.lambda_init = p.lambda_init;
-    if (dbg) { d.max_iter = 1; if (dbg->stop_after != kLibaStopLinearised) d.lambda_init = dbg->lambda > 0 ? dbg->lambda : 0.0; }
-    d.kb8_on = p.kb8 ? 1 : 0;
-    for (int k = 0; k < 4; ++k) d.kb8[k] = p.kb8 ? p.kb8[k] : 0.0;
-    d.rig_on = (p.kb8 && p.cam2 && p.trl) ? 1 : 0;
-    if (d.rig_on) {
-      // ImuCamPose(KeyFrame*) camera 1 (src/G2oTypes.cc:56-66): Rcb[1] = Rrl Rcb[0], tcb[1] = Rrl tcb[0] + trl, tbc[1] = -Rbc[1] tcb[1]
-      double tcb1[3];
-      for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) d.Rrl[i * 3 + j] = p.trl[i * 4 + j]; d.trl[i] = p.trl[i * 4 + 3]; }
-      for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-          double a = 0.0;
-          for (int k = 0; k < 3; ++k) a += d.Rrl[i * 3 + k] * d.Rcb[k * 3 + j];
-          d.Rcb1[i * 3 + j] = a;
-        }
-      for (int i = 0; i < 3; ++i) tcb1[i] = d.Rrl[i * 3] * d.tcb[0] + d.Rrl[i * 3 + 1] * d.tcb[1] + d.Rrl[i * 3 + 2] * d.tcb[2] + d.trl[i];
-      for (int i = 0; i < 3; ++i) d.tbc1[i] = -(d.Rcb1[i] * tcb1[0] + d.Rcb1[3 + i] * tcb1[1] + d.Rcb1[6 + i] * tcb1[2]);
-      std::memcpy(d.cam2, p.cam2, 64);
-    }
-    if (p.kb8)
-      for (int e = 0; e < p.n_edges; ++e)
-        if (p.edge_kind[e] == OSH_EDGE_STEREO) { set_error("window %d: a KannalaBrandt8 window takes monocular edges only (edge %d)", w, e); return OSH_ERR_UNSUPPORTED; }
-    size_t ef = 0;
-    for (int e = 0; e < p.n_edges; ++e) {
-      if (p.edge_pose[e] < 0 || p.edge_pose[e] >= d.K || p.edge_point[e] < 0 || p.edge_point[e] >= d.L || p.edge_kind[e] > OSH_EDGE_RIGHT) {
-        set_error("window %d edge %d: index or kind out of range", w, e); return OSH_ERR_INVALID;
-      }
-      if (p.edge_kind[e] == OSH_EDGE_RIGHT && !d.rig_on) { set_error("window %d edge %d: a right-camera edge (EdgeMono(1)) needs kb8, cam2 and trl", w, e); return OSH_ERR_INVALID; }
-      if (p.edge_pose[e] < d.N) ++ef;
-    }
-    for (int l = 0; l < p.n_links; ++l)
-      if (p.link_prev[l] < 0 || p.link_prev[l] >= d.NV || p.link_cur[l] < 0 || p.link_cur[l] >= d.N) {
-        set_error("window %d link %d: keyframe index out of range", w, l); return OSH_ERR_INVALID;
-      }
-    if (p.link_bias)
-      for (int l = 0; l < p.n_links; ++l) {
-        if (p.link_bias[l] < 0 || p.link_bias[l] >= d.NV) { set_error("window %d link %d: bias keyframe out of range", w, l); return OSH_ERR_INVALID; }
-        if (p.link_bias[l] == p.link_prev[l]) continue;
-        // the random-walk terms of the later keyframe are added beside the edge's own terms, by other threads of the same phase
-        if (p.link_bias[l] == p.link_cur[l]) { set_error("window %d link %d: the bias vertices of a link cannot be those of its later keyframe", w, l); return OSH_ERR_UNSUPPORTED; }
-        // the random-walk terms of a link's earlier keyframe are summed into the blocks of the edge's own bias vertices
-        for (int k = 0; k < 9; ++k)
-          if (p.link_info_g[(size_t)l * 9 + k] != 0.0 || p.link_info_a[(size_t)l * 9 + k] != 0.0) {
-            set_error("window %d link %d: a link whose bias vertices belong to another keyframe carries no random-walk edges", w, l); return OSH_ERR_UNSUPPORTED;
-          }
-      }
-    K += d.K; NV += d.NV; L += d.L; E += d.E; NL += d.NL; Htot += (size_t)d.n * d.n; btot += d.n; LO += (size_t)d.L + 1; PO += (size_t)d.N + 1;
-    EF += ef; LP += (size_t)d.L * d.N;
-    n_max = std::max(n_max, d.n);
-  }
-  const int W = ldlt_row_stride(n_max);
-  // 24-wide panels in the LDS of one block while they fit (51 keyframes); beyond, the whole group factorises in global memory
-  // (liba_solve_group; k_liba<6> -- its LDS need, vectors of n doubles, stays below what 6-wide panels would take)
-  int NB = kLNB;
-  if ((liba_scratch_doubles(NB, W) + kLT / 64 + 8) * sizeof(double) > 160 * 1024 - 64) NB = 6;
-  const size_t lds = (liba_scratch_doubles(NB, W) + kLT / 64 + 8) * sizeof(double);
-  if (lds > 160 * 1024 - 64 || n_max > 15 * kLibaMaxKeyframes) {
-    set_error("inertial window with %d optimisable keyframes: the device path handles up to %d (LocalInertialBA uses 10 or 25)", n_max / 15, kLibaMaxKeyframes);
-    return OSH_ERR_UNSUPPORTED;
-  }
-  // Map-sized problems (the group factorisation in global memory): with the keyframes in temporal order a landmark is seen by nearby
-  // keyframes and an IMU link joins neighbours, so with the unknowns interleaved per keyframe the reduced system is banded.  The band is
-  // the largest keyframe distance any landmark or link spans; a loop closure or the one-bias-pair mode of FullInertialBA (every link on
-  // one keyframe's bias vertices) makes it the whole map, and the problem stays in the dense layout.
-  if (NB != kLNB && !getenv("OSH_LIBA_DENSE")) {
-    std::vector<int> lo, hi;
-    for (int w = 0; w < nw; ++w) {
-      const osh_liba_problem& p = pr[w];
-      LibaDesc& d = h_desc[w];
-      if (d.N < 32) continue;
-      int span = 1;
-      lo.assign(d.L, d.N); hi.assign(d.L, -1);
-      for (int e = 0; e < p.n_edges; ++e) {
-        const int ip = p.edge_pose[e], j = p.edge_point[e];
-        if (ip >= d.N) continue;
-        lo[j] = std::min(lo[j], ip); hi[j] = std::max(hi[j], ip);
-      }
-      for (int j = 0; j < d.L; ++j) if (hi[j] >= 0) span = std::max(span, hi[j] - lo[j]);
-      for (int l = 0; l < p.n_links; ++l) {
-        const int a = p.link_prev[l], c2 = p.link_cur[l], ab = p.link_bias ? p.link_bias[l] : a;
-        int mn = c2, mx = c2;
-        if (a < d.N) { mn = std::min(mn, a); mx = std::max(mx, a); }
-        if (ab < d.N) { mn = std::min(mn, ab); mx = std::max(mx, ab); }
-        span = std::max(span, mx - mn);
-      }
-      if (15 * (span + 1) <= d.n / 2) { d.il = 1; d.bw_kf = span; d.bw = 15 * (span + 1) - 1; }
-    }
-  }
-  // ---- pack: every input array goes into ONE pinned staging buffer and travels in ONE copy; the results come back in one copy
-  // (LibaOut per window, abort word, final poses / velocities+biases / points, edge chi2 and depth flags), and the work buffers follow
-  // them in the device arena.  All of it lives with the context (one solver at a time per context, as for the visual path).
-  Layout in, out, work;
-  const auto o_desc = in.take<LibaDesc>(nw);
-  const auto o_pose = in.take<double>(K * 24), o_vba = in.take<double>(NV * 9), o_pts = in.take<double>(L * 3), o_obs = in.take<double>(E * 3),
-             o_info = in.take<double>(E);
-  const auto o_ep = in.take<int>(E), o_el = in.take<int>(E), o_eo = in.take<int>(E), o_lmo = in.take<int>(LO), o_po = in.take<int>(PO),
-             o_pel = in.take<int>(E), o_lmpe = in.take<int>(LP), o_lp = in.take<int>(NL), o_lc = in.take<int>(NL);
-  const auto o_kind = in.take<unsigned char>(E), o_rob = in.take<unsigned char>(NL);
-  const auto o_pre = in.take<float>(NL * OSH_PREINT_FLOATS);
-  const auto o_li = in.take<double>(NL * 81), o_lg = in.take<double>(NL * 9), o_la = in.take<double>(NL * 9);
-  const auto o_bar = in.take<unsigned>(nw);
-  const auto o_abort = in.take<int>(1), o_col = in.take<int>(NL), o_lb = in.take<int>(NL);
-  const auto r_out = out.take<LibaOut>(nw);
-  const auto r_abort = out.take<int>(1);
-  const auto r_pose = out.take<double>((btot / 15) * 24), r_vba = out.take<double>((btot / 15) * 9), r_pts = out.take<double>(L * 3),
-             r_chi2 = out.take<double>(E);
-  const auto r_depth = out.take<unsigned char>(E);
-  // a debug run keeps the buffers it reports in the result arena, so that they come back with the one download
-  Layout& kept = dbg ? out : work;
-  const auto a_pose1 = work.take<double>(K * 24), a_vba1 = work.take<double>(NV * 9), a_pts1 = kept.take<double>(L * 3), a_eh = work.take<double>(E * 9),
-             a_ep = work.take<double>(EF * 27), a_bfull = work.take<double>(btot), a_Hpl = kept.take<double>(EF * 18), a_BD = work.take<double>(EF * 18),
-             a_Hll = kept.take<double>(L * 6), a_bl = kept.take<double>(L * 3), a_dinv = work.take<double>(L * 9), a_H = kept.take<double>(Htot),
-             a_S = kept.take<double>(Htot), a_b = kept.take<double>(btot), a_bs = kept.take<double>(btot), a_x = kept.take<double>(btot),
-             a_linkQ = kept.take<double>(NL * kLinkQ), a_ppart = kept.take<double>((btot / 15) * kPoseChunks * 27),
-             a_red = work.take<double>((size_t)nw * 4 * kLG * 2), a_ctrl = kept.take<double>((size_t)nw * 4);
-  StagedCall* B = attachment<StagedCall>(ctx, kAttachLiba);
-  if (!B) return OSH_ERR_INVALID;
-  OSH_TRY(B->reserve(in, out, work.bytes, (size_t)64 << 20));   // an arena of at least 64 MiB: large page fragments
-  char* const hs = B->host_in();
-  double *h_pose = o_pose.in(hs), *h_vba = o_vba.in(hs), *h_pts = o_pts.in(hs), *h_obs = o_obs.in(hs), *h_info = o_info.in(hs);
-  int *h_ep = o_ep.in(hs), *h_el = o_el.in(hs), *h_eo = o_eo.in(hs), *h_lmo = o_lmo.in(hs), *h_po = o_po.in(hs), *h_pel = o_pel.in(hs);
-  int *h_lmpe = o_lmpe.in(hs), *h_lp = o_lp.in(hs), *h_lc = o_lc.in(hs), *h_lb = o_lb.in(hs), *h_col = o_col.in(hs);
-  unsigned char *h_kind = o_kind.in(hs), *h_rob = o_rob.in(hs);
-  float* h_pre = o_pre.in(hs);
-  double *h_li = o_li.in(hs), *h_lg = o_lg.in(hs), *h_la = o_la.in(hs);
-  std::memset(h_lmpe, 0xff, LP * 4);
-  std::memset(o_bar.in(hs), 0, nw * sizeof(unsigned));
-  std::memset(o_abort.in(hs), 0, sizeof(int));
-  std::vector<int> cnt, fill, order;
-  for (int w = 0; w < nw; ++w) {
-    const osh_liba_problem& p = pr[w];
-    const LibaDesc& d = h_desc[w];
-    for (int k = 0; k < d.K; ++k) {
-      double* o = &h_pose[((size_t)d.pose_off + k) * 24];
-      std::memcpy(o, p.pose_Rcw + 9 * k, 72); std::memcpy(o + 9, p.pose_tcw + 3 * k, 24);
-      std::memcpy(o + 12, p.pose_Rwb + 9 * k, 72); std::memcpy(o + 21, p.pose_twb + 3 * k, 24);
-    }
-    for (int k = 0; k < d.NV; ++k) {
-      double* o = &h_vba[((size_t)d.vel_off + k) * 9];
-      std::memcpy(o, p.vel + 3 * k, 24); std::memcpy(o + 3, p.bias_g + 3 * k, 24); std::memcpy(o + 6, p.bias_a + 3 * k, 24);
-    }
-    if (d.L) std::memcpy(&h_pts[(size_t)d.pt_off * 3], p.points, (size_t)d.L * 24);
-    cnt.assign((size_t)d.L + 1, 0);
-    for (int e = 0; e < d.E; ++e) cnt[p.edge_point[e] + 1]++;
-    for (int j = 0; j < d.L; ++j) cnt[j + 1] += cnt[j];
-    fill.assign(cnt.begin(), cnt.end() - 1);
-    order.resize(d.E);
-    for (int e = 0; e < d.E; ++e) order[fill[p.edge_point[e]]++] = e;
-    for (int j = 0; j <= d.L; ++j) h_lmo[d.lmoff_off + j] = cnt[j];
-    for (int j = 0; j < d.L; ++j) {
-      std::stable_sort(order.begin() + cnt[j], order.begin() + cnt[j + 1], [&](int a, int b) {
-        return p.edge_pose[a] != p.edge_pose[b] ? p.edge_pose[a] < p.edge_pose[b] : p.edge_kind[a] < p.edge_kind[b];
-      });
-      for (int x = cnt[j]; x < cnt[j + 1]; ++x) {
-        if (x > cnt[j] && p.edge_pose[order[x]] == p.edge_pose[order[x - 1]]) {
-          // one Hessian block, two edges: only the left EdgeMono(0) + right EdgeMono(1) of a fisheye rig (src/Optimizer.cc:2737-2835)
-          const bool pair = p.edge_kind[order[x]] == OSH_EDGE_RIGHT && p.edge_kind[order[x - 1]] == OSH_EDGE_MONO &&
-                            !(x - 1 > cnt[j] && p.edge_pose[order[x - 2]] == p.edge_pose[order[x]]);
-          if (!pair) {
-            set_error("window %d: landmark %d is observed twice by keyframe %d with edge kinds that do not form a left + right pair", w, j, p.edge_pose[order[x]]);
-            return OSH_ERR_UNSUPPORTED;
-          }
-          continue;   // the pair's block is the first edge's
-        }
-        if (p.edge_pose[order[x]] < d.N) h_lmpe[(size_t)d.lmpose_off + (size_t)j * d.N + p.edge_pose[order[x]]] = x;
-      }
-    }
-    int* po = &h_po[d.peloff_off];
-    for (int i = 0; i <= d.N; ++i) po[i] = 0;
-    for (int x = 0; x < d.E; ++x) {
-      const int e = order[x];
-      const size_t g = (size_t)d.edge_off + x;
-      h_ep[g] = p.edge_pose[e]; h_el[g] = p.edge_point[e]; h_kind[g] = p.edge_kind[e]; h_eo[g] = e; h_info[g] = p.edge_info[e];
-      for (int k = 0; k < 3; ++k) h_obs[g * 3 + k] = p.edge_obs[3 * e + k];
-      if (p.edge_pose[e] < d.N) po[p.edge_pose[e] + 1]++;
-    }
-    for (int i = 0; i < d.N; ++i) po[i + 1] += po[i];
-    fill.assign(po, po + d.N);
-    int nfix = po[d.N];   // the fixed keyframes' edges follow the optimisable ones in the walk order of the linearisation
-    cnt.assign((size_t)d.E, -1);   // place of each optimisable-pose edge in that order
-    for (int x = 0; x < d.E; ++x) {
-      const int ip = h_ep[(size_t)d.edge_off + x];
-      if (ip < d.N) cnt[x] = fill[ip];
-      h_pel[(size_t)d.edge_off + (ip < d.N ? fill[ip]++ : nfix++)] = x;
-    }
-    // (landmark, pose) -> place of the pair's block: Hpl and B Dinv are stored pose by pose, a landmark's neighbours next to it
-    for (size_t k = 0; k < (size_t)d.L * d.N; ++k) { int& x = h_lmpe[(size_t)d.lmpose_off + k]; if (x >= 0) x = cnt[x]; }
-    for (int l = 0; l < d.NL; ++l) {
-      const size_t g = (size_t)d.link_off + l;
-      h_lp[g] = p.link_prev[l]; h_lc[g] = p.link_cur[l]; h_rob[g] = p.link_robust[l];
-      h_lb[g] = p.link_bias ? p.link_bias[l] : p.link_prev[l];
-      std::memcpy(&h_pre[g * OSH_PREINT_FLOATS], p.link_preint + (size_t)l * OSH_PREINT_FLOATS, OSH_PREINT_FLOATS * 4);
-      std::memcpy(&h_li[g * 81], p.link_info + (size_t)l * 81, 81 * 8);
-      std::memcpy(&h_lg[g * 9], p.link_info_g + (size_t)l * 9, 72); std::memcpy(&h_la[g * 9], p.link_info_a + (size_t)l * 9, 72);
-      // greedy colouring: the first colour none of the earlier links sharing a keyframe with this one has (a chain takes two)
-      int col = 0;
-      for (bool clash = true; clash; ) {
-        clash = false;
-        for (int l2 = 0; l2 < l && !clash; ++l2) {
-          if (h_col[(size_t)d.link_off + l2] != col) continue;
-          const int k1[3] = {p.link_prev[l], p.link_cur[l], h_lb[g]}, k2[3] = {p.link_prev[l2], p.link_cur[l2], h_lb[(size_t)d.link_off + l2]};
-          for (int x = 0; x < 3; ++x) for (int y = 0; y < 3; ++y) clash = clash || k1[x] == k2[y];
-        }
-        if (clash) ++col;
-      }
-      h_col[g] = col;
-      h_desc[w].n_colours = std::max(h_desc[w].n_colours, col + 1);
-    }
-  }
-  std::memcpy(o_desc.in(hs), h_desc.data(), nw * sizeof(LibaDesc));
-  OSH_TRY(B->upload(s));
-  char* const din = B->dev_in();
-  char* const dres = B->dev_out();
-  char* const dwork = B->dev_work();
-  char* const dkept = dbg ? dres : dwork;
+const void* liba_kernel(int NB) { return NB == 24 ? (const void*)k_liba<24> : (const void*)k_liba<6>; }
+
+// the sections of the layout in the device arena [in | out | work]
+LibaView liba_bind_view(const LibaLayout& y, char* din, char* dres, char* dwork) {
+  char* const dkept = y.debug ? dres : dwork;
   LibaView v{};
-  v.desc = o_desc.in(din); v.out = r_out.in(dres);
-  v.pose[0] = o_pose.in(din); v.vba[0] = o_vba.in(din); v.pts[0] = o_pts.in(din);
-  v.pose[1] = a_pose1.in(dwork); v.vba[1] = a_vba1.in(dwork); v.pts[1] = a_pts1.in(dkept);
-  v.e_pose = o_ep.in(din); v.e_point = o_el.in(din); v.e_kind = o_kind.in(din); v.e_obs = o_obs.in(din); v.e_info = o_info.in(din); v.e_orig = o_eo.in(din);
-  v.lm_off = o_lmo.in(din); v.pel_off = o_po.in(din); v.pel_edge = o_pel.in(din); v.lm_pose_edge = o_lmpe.in(din);
-  v.link_prev = o_lp.in(din); v.link_cur = o_lc.in(din); v.link_bias = o_lb.in(din);
-  v.link_preint = o_pre.in(din); v.link_info = o_li.in(din); v.link_info_g = o_lg.in(din); v.link_info_a = o_la.in(din);
-  v.link_robust = o_rob.in(din);
-  v.Hpl = a_Hpl.in(dkept); v.BD = a_BD.in(dwork); v.Hll = a_Hll.in(dkept); v.bl = a_bl.in(dkept);
-  v.dinv = a_dinv.in(dwork); v.H = a_H.in(dkept); v.b = a_b.in(dkept); v.S = a_S.in(dkept); v.bs = a_bs.in(dkept);
-  v.x = a_x.in(dkept); v.linkQ = a_linkQ.in(dkept); v.ppart = a_ppart.in(dkept);
-  v.bar = o_bar.in(din); v.abort_flag = o_abort.in(din);
-  v.red = a_red.in(dwork); v.ctrl = a_ctrl.in(dkept); v.nw = nw;
-  v.stop_after = dbg ? dbg->stop_after : 0;
-  v.force_heavy = getenv("OSH_LIBA_HEAVY_BARRIER") ? 1 : 0;
-  v.eh = a_eh.in(dwork); v.ep = a_ep.in(dwork); v.bfull = a_bfull.in(dwork); v.E_total = E; v.EF_total = EF;
-  v.link_colour = o_col.in(din);
-  v.res_abort = r_abort.in(dres); v.res_pose = r_pose.in(dres); v.res_vba = r_vba.in(dres);
-  v.res_pts = r_pts.in(dres); v.out_chi2 = r_chi2.in(dres); v.out_depth = r_depth.in(dres);
-  OSH_TRY(allow_dynamic_lds(device, 160 * 1024 - 64, k_liba<24>, k_liba<6>));
-  // blocks per window: the tracker's single window (and small batches) get a group of 32 = one whole XCD; a large batch fills the chip
-  // with one block per window.  A group needs all its blocks resident (they meet at barriers): the grid is kept within what the device
-  // holds at once (occupancy query) and launched as an ordinary kernel.  (hipLaunchCooperativeKernel would check the same, but it
-  // makes the runtime create a second, cooperative HSA queue, and under rocprofv3 the process then faults at exit inside
-  // libhsa-runtime64's shutdown, called from libamdhip64's exit handler, on that queue's device mapping -- resolved from the fault
-  // report and /proc/self/maps by profiles/exit_probe.py; k_liba was the only cooperative launch of the library.)
+  v.desc = y.desc.in(din); v.out = y.res.in(dres);
+  v.pose[0] = y.pose.in(din); v.vba[0] = y.vba.in(din); v.pts[0] = y.pts.in(din);
+  v.pose[1] = y.pose1.in(dwork); v.vba[1] = y.vba1.in(dwork); v.pts[1] = y.pts1.in(dkept);
+  v.e_pose = y.e_pose.in(din); v.e_point = y.e_point.in(din); v.e_kind = y.e_kind.in(din); v.e_obs = y.e_obs.in(din); v.e_info = y.e_info.in(din);
+  v.e_orig = y.e_orig.in(din);
+  v.lm_off = y.lm_off.in(din); v.pel_off = y.pel_off.in(din); v.pel_edge = y.pel_edge.in(din); v.lm_pose_edge = y.lm_pose_edge.in(din);
+  v.link_prev = y.link_prev.in(din); v.link_cur = y.link_cur.in(din); v.link_bias = y.link_bias.in(din); v.link_colour = y.link_colour.in(din);
+  v.link_preint = y.link_preint.in(din); v.link_info = y.link_info.in(din); v.link_info_g = y.link_info_g.in(din); v.link_info_a = y.link_info_a.in(din);
+  v.link_robust = y.link_robust.in(din);
+  v.bar = y.bar.in(din); v.abort_flag = y.abort_flag.in(din);
+  v.Hpl = y.Hpl.in(dkept); v.BD = y.BD.in(dwork); v.Hll = y.Hll.in(dkept); v.bl = y.bl.in(dkept);
+  v.dinv = y.dinv.in(dwork); v.H = y.H.in(dkept); v.b = y.b.in(dkept); v.S = y.S.in(dkept); v.bs = y.bs.in(dkept);
+  v.x = y.x.in(dkept); v.linkQ = y.linkQ.in(dkept); v.ppart = y.ppart.in(dkept);
+  v.red = y.red.in(dwork); v.ctrl = y.ctrl.in(dkept);
+  v.eh = y.eh.in(dwork); v.ep = y.ep.in(dwork); v.bfull = y.bfull.in(dwork);
+  v.res_abort = y.res_abort.in(dres); v.res_pose = y.res_pose.in(dres); v.res_vba = y.res_vba.in(dres);
+  v.res_pts = y.res_pts.in(dres); v.out_chi2 = y.out_chi2.in(dres); v.out_depth = y.out_depth.in(dres);
+  return v;
+}
+
+// blocks per window: the tracker's single window (and small batches) get a group of 32 = one whole XCD; a large batch fills the chip
+// with one block per window.  A group needs all its blocks resident (they meet at barriers): the grid is kept within what the device
+// holds at once (occupancy query).
+int liba_group_size(int nw, const LibaKnobs& knobs, int device, const LibaPanels& pan) {
   int G = nw <= 8 ? kLG : (nw <= 16 ? 16 : (nw <= 32 ? 8 : (nw <= 64 ? 4 : (nw <= 128 ? 2 : 1))));
-  if (const char* gs = getenv("OSH_LIBA_GROUP")) { const int gv = atoi(gs); if (gv == 1 || gv == 2 || gv == 4 || gv == 8 || gv == 16 || gv == 32) G = gv; }
-  int W_arg = W;
-  const void* kfn = NB == 24 ? (const void*)k_liba<24> : (const void*)k_liba<6>;
-  {
-    int per_cu = 0, n_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, kLT, lds) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
-      (void)hipGetLastError();
-      per_cu = 0;
-    }
-    while (G > 1 && (long long)((nw + 7) / 8 * 8) * G > (long long)per_cu * n_cu) G >>= 1;
+  if (knobs.group) G = knobs.group;
+  int per_cu = 0, n_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, liba_kernel(pan.NB), kLT, pan.lds) != hipSuccess ||
+      hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+    (void)hipGetLastError();
+    per_cu = 0;
   }
-  auto run = [&](int Gx, int test_abort) -> int {
-    v.test_abort = test_abort;
-    int g_arg = Gx;
-    void* args[] = {(void*)&v, (void*)&W_arg, (void*)&g_arg};
-    const hipError_t le = hipLaunchKernel(kfn, dim3((unsigned)((nw + 7) / 8 * 8 * Gx)), dim3(kLT), args, lds, s);
-    if (le != hipSuccess) { set_error("k_liba launch failed: %s", hipGetErrorString(le)); return OSH_ERR_DEVICE; }
-    return B->download(s);
-  };
-  OSH_TRY(run(G, (G > 1 && getenv("OSH_LIBA_TEST_ABORT")) ? 1 : 0));
-  char* const hr = B->host_out();
-  if (*r_abort.in(hr) && G > 1) {
-    // A barrier of a block group gave up (blocks of other streams kept part of a group off the device for seconds): the same
-    // problem once more with one block per window, which has no barrier to wait at.  The estimates live in the input arena: upload again.
-    OSH_TRY(B->upload(s));
-    G = 1;
-    OSH_TRY(run(1, 0));
+  while (G > 1 && (long long)((nw + 7) / 8 * 8) * G > (long long)per_cu * n_cu) G >>= 1;
+  return G;
+}
+
+// One launch with G blocks per window, then the download.  The abort word of the result arena is cleared on the stream first: the
+// blocks only ever set it (grp_sync), so what comes back does not depend on the order in which they start.
+// k_liba is launched as an ordinary kernel.  (hipLaunchCooperativeKernel would check residency as liba_group_size does, but it
+// makes the runtime create a second, cooperative HSA queue, and under rocprofv3 the process then faults at exit inside
+// libhsa-runtime64's shutdown, called from libamdhip64's exit handler, on that queue's device mapping -- resolved from the fault
+// report and /proc/self/maps by profiles/exit_probe.py; k_liba was the only cooperative launch of the library.)
+int liba_launch(StagedCall* B, hipStream_t s, LibaView v, const LibaPanels& pan, int G, int test_abort) {
+  v.test_abort = test_abort;
+  int W_arg = pan.W, g_arg = G;
+  void* args[] = {(void*)&v, (void*)&W_arg, (void*)&g_arg};
+  OSH_HIP(hipMemsetAsync(v.res_abort, 0, sizeof(int), s));
+  const hipError_t le = hipLaunchKernel(liba_kernel(pan.NB), dim3((unsigned)((v.nw + 7) / 8 * 8 * G)), dim3(kLT), args, pan.lds, s);
+  if (le != hipSuccess) { set_error("k_liba launch failed: %s", hipGetErrorString(le)); return OSH_ERR_DEVICE; }
+  return B->download(s);
+}
+
+// Window 0 of a stopped run in the caller's layout: the reduced system with the poses first (whatever LibaDesc::il says), the pose
+// rows' visual part summed over its chunks, Hll unpacked, Hpl per edge of the caller (a left + right pair's block under its left
+// edge).  hs / hr: the staged inputs and the downloaded result arena.
+void liba_debug_export(const LibaDebug& dbg, const LibaDesc& d, const LibaLayout& y, size_t EF, const char* hs, const char* hr, int NB, int G) {
+  const int n = d.n, N = d.N, C = y.res.in(hr)[0].chunks;
+  std::vector<int> to_ref(n);
+  for (int i = 0; i < N; ++i) {
+    for (int r = 0; r < 6; ++r) to_ref[(d.il ? 15 * i : 6 * i) + r] = 6 * i + r;
+    for (int r = 0; r < 9; ++r) to_ref[(d.il ? 15 * i + 6 : 6 * N + 9 * i) + r] = 6 * N + 9 * i + r;
   }
-  if (*r_abort.in(hr)) { set_error("k_liba: a barrier of a window's block group did not complete (group of %d blocks)", G); return OSH_ERR_DEVICE; }
-  const LibaOut* h_out = r_out.in(hr);
-  if (dbg) {
-    // window 0 in the caller's layout: the reduced system with the poses first (whatever LibaDesc::il says), the pose rows' visual
-    // part summed over its chunks, Hll unpacked, Hpl per edge of the caller (a left + right pair's block under its left edge)
-    const LibaDesc& d = h_desc[0];
-    const int n = d.n, N = d.N, C = h_out[0].chunks;
-    std::vector<int> to_ref(n);
-    for (int i = 0; i < N; ++i) {
-      for (int r = 0; r < 6; ++r) to_ref[(d.il ? 15 * i : 6 * i) + r] = 6 * i + r;
-      for (int r = 0; r < 9; ++r) to_ref[(d.il ? 15 * i + 6 : 6 * N + 9 * i) + r] = 6 * N + 9 * i + r;
-    }
-    const double *hH = a_H.in(hr), *hb = a_b.in(hr), *hpp = a_ppart.in(hr), *hHll = a_Hll.in(hr), *hbl = a_bl.in(hr), *hHpl = a_Hpl.in(hr);
-    auto up = [](int r, int c) { const int lo = r < c ? r : c, hi = r < c ? c : r; return lo * 6 - lo * (lo - 1) / 2 + (hi - lo); };
-    if (dbg->info) { dbg->info[0] = NB; dbg->info[1] = G; dbg->info[2] = C; dbg->info[3] = d.il; dbg->info[4] = d.n_colours; }
-    if (dbg->chi2) *dbg->chi2 = h_out[0].chi2_initial;
-    if (dbg->H) {
-      std::fill(dbg->H, dbg->H + (size_t)n * n, 0.0);
-      for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c)
-          if (!d.il || std::abs(r - c) <= d.bw) dbg->H[(size_t)to_ref[r] * n + to_ref[c]] = hH[(size_t)r * n + c];   // outside the band nothing is written
-      for (int i = 0; i < N; ++i)
-        for (int r = 0; r < 6; ++r)
-          for (int c = 0; c < 6; ++c)
-            for (int ch = 0; ch < C; ++ch) dbg->H[(size_t)(6 * i + r) * n + 6 * i + c] += hpp[((size_t)i * kPoseChunks + ch) * 27 + up(r, c)];
-    }
-    if (dbg->b) {
-      for (int k = 0; k < n; ++k) dbg->b[to_ref[k]] = hb[k];
-      for (int i = 0; i < N; ++i)
-        for (int r = 0; r < 6; ++r)
-          for (int ch = 0; ch < C; ++ch) dbg->b[6 * i + r] += hpp[((size_t)i * kPoseChunks + ch) * 27 + 21 + r];
-      for (size_t k = 0; k < (size_t)d.L * 3; ++k) dbg->b[n + k] = hbl[k];
-    }
-    if (dbg->Hll)
-      for (int j = 0; j < d.L; ++j) {
-        const double* h = hHll + (size_t)j * 6;
-        double* o = dbg->Hll + (size_t)j * 9;
-        o[0] = h[0]; o[1] = o[3] = h[1]; o[2] = o[6] = h[2]; o[4] = h[3]; o[5] = o[7] = h[4]; o[8] = h[5];
-      }
-    if (dbg->Hpl) {
-      std::fill(dbg->Hpl, dbg->Hpl + (size_t)d.E * 18, 0.0);
-      const int n_free_edges = h_po[d.peloff_off + N];
-      for (int idx = 0; idx < n_free_edges; ++idx) {
-        const int x = h_pel[(size_t)d.edge_off + idx];
-        if (x > 0 && h_el[x - 1] == h_el[x] && h_ep[x - 1] == h_ep[x]) continue;   // the right edge of a pair: its term is in the left edge's block
-        for (int k = 0; k < 18; ++k) dbg->Hpl[(size_t)h_eo[x] * 18 + k] = hHpl[(size_t)k * EF + idx];
-      }
-    }
-    const double* hQ = a_linkQ.in(hr);
-    for (int l = 0; l < d.NL; ++l) {
-      const double* Q = hQ + (size_t)l * kLinkQ + 600;
-      if (dbg->J) std::memcpy(dbg->J + (size_t)l * 216, Q, 216 * 8);
-      if (dbg->Wr) std::memcpy(dbg->Wr + (size_t)l * 9, Q + 216, 72);
-      if (dbg->rho1) dbg->rho1[l] = Q[225];
-    }
-    if (dbg->S) {   // the kernel forms the upper triangle (of its own order of the unknowns)
-      const double* hS = a_S.in(hr);
-      std::fill(dbg->S, dbg->S + (size_t)n * n, 0.0);
-      for (int r = 0; r < n; ++r)
-        for (int c = r; c < n; ++c)
-          if (!d.il || c - r <= d.bw) dbg->S[(size_t)to_ref[r] * n + to_ref[c]] = dbg->S[(size_t)to_ref[c] * n + to_ref[r]] = hS[(size_t)r * n + c];
-    }
-    if (dbg->bs) { const double* hbs = a_bs.in(hr); for (int k = 0; k < n; ++k) dbg->bs[to_ref[k]] = hbs[k]; }
-    if (dbg->lambda_used) *dbg->lambda_used = dbg->lambda > 0 ? dbg->lambda : a_ctrl.in(hr)[0];
-    if (dbg->x) { const double* hx = a_x.in(hr); for (int k = 0; k < n; ++k) dbg->x[to_ref[k]] = hx[k]; }
-    if (dbg->xl) { const double* t = a_pts1.in(hr); for (size_t k = 0; k < (size_t)d.L * 3; ++k) dbg->xl[k] = t[k] - h_pts[k]; }   // the trial buffer holds point + step
-    return OSH_OK;
+  const double *hH = y.H.in(hr), *hb = y.b.in(hr), *hpp = y.ppart.in(hr), *hHll = y.Hll.in(hr), *hbl = y.bl.in(hr), *hHpl = y.Hpl.in(hr);
+  auto up = [](int r, int c) { const int lo = r < c ? r : c, hi = r < c ? c : r; return lo * 6 - lo * (lo - 1) / 2 + (hi - lo); };
+  if (dbg.info) { dbg.info[0] = NB; dbg.info[1] = G; dbg.info[2] = C; dbg.info[3] = d.il; dbg.info[4] = d.n_colours; }
+  if (dbg.chi2) *dbg.chi2 = y.res.in(hr)[0].chi2_initial;
+  if (dbg.H) {
+    std::fill(dbg.H, dbg.H + (size_t)n * n, 0.0);
+    for (int r = 0; r < n; ++r)
+      for (int c = 0; c < n; ++c)
+        if (!d.il || std::abs(r - c) <= d.bw) dbg.H[(size_t)to_ref[r] * n + to_ref[c]] = hH[(size_t)r * n + c];   // outside the band nothing is written
+    for (int i = 0; i < N; ++i)
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c)
+          for (int ch = 0; ch < C; ++ch) dbg.H[(size_t)(6 * i + r) * n + 6 * i + c] += hpp[((size_t)i * kPoseChunks + ch) * 27 + up(r, c)];
   }
-  g_liba_last_group = G;
-  std::memcpy(g_liba_last_prof, h_out[0].prof, sizeof(g_liba_last_prof));
+  if (dbg.b) {
+    for (int k = 0; k < n; ++k) dbg.b[to_ref[k]] = hb[k];
+    for (int i = 0; i < N; ++i)
+      for (int r = 0; r < 6; ++r)
+        for (int ch = 0; ch < C; ++ch) dbg.b[6 * i + r] += hpp[((size_t)i * kPoseChunks + ch) * 27 + 21 + r];
+    for (size_t k = 0; k < (size_t)d.L * 3; ++k) dbg.b[n + k] = hbl[k];
+  }
+  if (dbg.Hll)
+    for (int j = 0; j < d.L; ++j) {
+      const double* h = hHll + (size_t)j * 6;
+      double* o = dbg.Hll + (size_t)j * 9;
+      o[0] = h[0]; o[1] = o[3] = h[1]; o[2] = o[6] = h[2]; o[4] = h[3]; o[5] = o[7] = h[4]; o[8] = h[5];
+    }
+  if (dbg.Hpl) {
+    const int *h_pel = y.pel_edge.in(hs), *h_ep = y.e_pose.in(hs), *h_el = y.e_point.in(hs), *h_eo = y.e_orig.in(hs);
+    std::fill(dbg.Hpl, dbg.Hpl + (size_t)d.E * 18, 0.0);
+    const int n_free_edges = y.pel_off.in(hs)[d.peloff_off + N];
+    for (int idx = 0; idx < n_free_edges; ++idx) {
+      const int x = h_pel[(size_t)d.edge_off + idx];
+      if (x > 0 && h_el[x - 1] == h_el[x] && h_ep[x - 1] == h_ep[x]) continue;   // the right edge of a pair: its term is in the left edge's block
+      for (int k = 0; k < 18; ++k) dbg.Hpl[(size_t)h_eo[x] * 18 + k] = hHpl[(size_t)k * EF + idx];
+    }
+  }
+  const double* hQ = y.linkQ.in(hr);
+  for (int l = 0; l < d.NL; ++l) {
+    const double* Q = hQ + (size_t)l * kLinkQ + 600;
+    if (dbg.J) std::memcpy(dbg.J + (size_t)l * 216, Q, 216 * 8);
+    if (dbg.Wr) std::memcpy(dbg.Wr + (size_t)l * 9, Q + 216, 72);
+    if (dbg.rho1) dbg.rho1[l] = Q[225];
+  }
+  if (dbg.S) {   // the kernel forms the upper triangle (of its own order of the unknowns)
+    const double* hS = y.S.in(hr);
+    std::fill(dbg.S, dbg.S + (size_t)n * n, 0.0);
+    for (int r = 0; r < n; ++r)
+      for (int c = r; c < n; ++c)
+        if (!d.il || c - r <= d.bw) dbg.S[(size_t)to_ref[r] * n + to_ref[c]] = dbg.S[(size_t)to_ref[c] * n + to_ref[r]] = hS[(size_t)r * n + c];
+  }
+  if (dbg.bs) { const double* hbs = y.bs.in(hr); for (int k = 0; k < n; ++k) dbg.bs[to_ref[k]] = hbs[k]; }
+  if (dbg.lambda_used) *dbg.lambda_used = dbg.lambda > 0 ? dbg.lambda : y.ctrl.in(hr)[0];
+  if (dbg.x) { const double* hx = y.x.in(hr); for (int k = 0; k < n; ++k) dbg.x[to_ref[k]] = hx[k]; }
+  if (dbg.xl) { const double *t = y.pts1.in(hr), *h_pts = y.pts.in(hs); for (size_t k = 0; k < (size_t)d.L * 3; ++k) dbg.xl[k] = t[k] - h_pts[k]; }   // the trial buffer holds point + step
+}
+
+// the downloaded result arena `hr` into the caller's results, window by window
+void liba_scatter_results(int nw, const LibaPack& pk, const LibaLayout& y, const char* hr, osh_liba_result* res) {
   for (int w = 0; w < nw; ++w) {
-    const LibaDesc& d = h_desc[w];
-    const LibaOut& o = h_out[w];
+    const LibaDesc& d = pk.desc[w];
+    const LibaOut& o = y.res.in(hr)[w];
     osh_liba_result& r = res[w];
     r.status = OSH_OK; r.iterations = o.iterations; r.trials = o.trials; r.n_trace = o.n_trace;
     r.chi2_initial = o.chi2_initial; r.chi2_final = o.chi2_final;
     for (int k = 0; k < o.n_trace; ++k) { r.chi2_trace[k] = o.chi2_trace[k]; r.lambda_trace[k] = o.lambda_trace[k]; r.trials_trace[k] = o.trials_trace[k]; }
-    const double* q0 = r_pose.in(hr) + (size_t)(d.b_off / 15) * 24;
-    const double* s0 = r_vba.in(hr) + (size_t)(d.b_off / 15) * 9;
+    const double* q0 = y.res_pose.in(hr) + (size_t)(d.b_off / 15) * 24;
+    const double* s0 = y.res_vba.in(hr) + (size_t)(d.b_off / 15) * 9;
     for (int k = 0; k < d.N; ++k) {
       const double* q = q0 + (size_t)k * 24;
       if (r.pose_Rcw) std::memcpy(r.pose_Rcw + 9 * k, q, 72);
@@ -1688,10 +1432,55 @@ static int liba_run(osh_lba_ctx* ctx, int32_t nw, const osh_liba_problem* pr, os
       if (r.bias_g) std::memcpy(r.bias_g + 3 * k, s0 + (size_t)k * 9 + 3, 24);
       if (r.bias_a) std::memcpy(r.bias_a + 3 * k, s0 + (size_t)k * 9 + 6, 24);
     }
-    if (r.points && d.L) std::memcpy(r.points, r_pts.in(hr) + (size_t)d.pt_off * 3, (size_t)d.L * 24);
-    if (r.edge_chi2 && d.E) std::memcpy(r.edge_chi2, r_chi2.in(hr) + d.edge_off, (size_t)d.E * 8);
-    if (r.edge_depth_pos && d.E) std::memcpy(r.edge_depth_pos, r_depth.in(hr) + d.edge_off, (size_t)d.E);
+    if (r.points && d.L) std::memcpy(r.points, y.res_pts.in(hr) + (size_t)d.pt_off * 3, (size_t)d.L * 24);
+    if (r.edge_chi2 && d.E) std::memcpy(r.edge_chi2, y.out_chi2.in(hr) + d.edge_off, (size_t)d.E * 8);
+    if (r.edge_depth_pos && d.E) std::memcpy(r.edge_depth_pos, y.out_depth.in(hr) + d.edge_off, (size_t)d.E);
   }
+}
+}  // namespace
+
+// upload + one launch + download.  dbg: one window, stopped after a stage; its buffers come back in the caller's layout (the reduced
+// system with the 6-dof poses first, then v bg ba per keyframe; edges in the caller's order) and res is not touched.
+static int liba_run(osh_lba_ctx* ctx, int32_t nw, const osh_liba_problem* pr, osh_liba_result* res, const LibaDebug* dbg) {
+  int device = 0;
+  hipStream_t s = nullptr;
+  OSH_TRY(lba_stream(ctx, &device, &s));
+  const LibaKnobs knobs = liba_read_knobs();
+  LibaPack pk;
+  LibaPanels pan;
+  LibaScratch sc;
+  LibaLayout y;
+  // a debug run: one iteration, and past the linearisation the lambda asked for (0: the default) in place of the problem's
+  const double dbg_lambda = dbg && dbg->stop_after != kLibaStopLinearised ? (dbg->lambda > 0 ? dbg->lambda : 0.0) : -1.0;
+  if (liba_describe(nw, pr, dbg ? 1 : -1, dbg_lambda, pk) != OSH_OK || liba_panels(pk, pan) != OSH_OK) { set_error("%s", pk.msg); return pk.err; }
+  if (pan.NB != kLNB && !knobs.dense) liba_band(nw, pr, pk, sc);
+  // all of it lives with the context (one solver at a time per context, as for the visual path)
+  liba_layout(nw, pk.tot, dbg != nullptr, y);
+  StagedCall* B = attachment<StagedCall>(ctx, kAttachLiba);
+  if (!B) return OSH_ERR_INVALID;
+  OSH_TRY(B->reserve(y.in, y.out, y.work.bytes, (size_t)64 << 20));   // an arena of at least 64 MiB: large page fragments
+  if (liba_pack(nw, pr, pk, y, B->host_in(), sc) != OSH_OK) { set_error("%s", pk.msg); return pk.err; }
+  OSH_TRY(B->upload(s));
+  LibaView v = liba_bind_view(y, B->dev_in(), B->dev_out(), B->dev_work());
+  v.nw = nw; v.E_total = pk.tot.E; v.EF_total = pk.tot.EF;
+  v.stop_after = dbg ? dbg->stop_after : 0;
+  v.force_heavy = knobs.heavy_barrier ? 1 : 0;
+  OSH_TRY(allow_dynamic_lds(device, (int)kLibaLdsBytes, k_liba<24>, k_liba<6>));
+  int G = liba_group_size(nw, knobs, device, pan);
+  OSH_TRY(liba_launch(B, s, v, pan, G, (G > 1 && knobs.test_abort) ? 1 : 0));
+  const char* const hr = B->host_out();
+  if (*y.res_abort.in(hr) && G > 1) {
+    // A barrier of a block group gave up (blocks of other streams kept part of a group off the device for seconds): the same
+    // problem once more with one block per window, which has no barrier to wait at.  The estimates live in the input arena: upload again.
+    OSH_TRY(B->upload(s));
+    G = 1;
+    OSH_TRY(liba_launch(B, s, v, pan, 1, 0));
+  }
+  if (*y.res_abort.in(hr)) { set_error("k_liba: a barrier of a window's block group did not complete (group of %d blocks)", G); return OSH_ERR_DEVICE; }
+  if (dbg) { liba_debug_export(*dbg, pk.desc[0], y, pk.tot.EF, B->host_in(), hr, pan.NB, G); return OSH_OK; }
+  g_liba_last_group = G;
+  std::memcpy(g_liba_last_prof, y.res.in(hr)[0].prof, sizeof(g_liba_last_prof));
+  liba_scatter_results(nw, pk, y, hr, res);
   return OSH_OK;
 }
 

@@ -5,28 +5,11 @@
 #include "common.h"
 #include "lba_math.h"
 #include "liba_math.h"
+#include "liba_pack.h"   // LibaDesc
 
 namespace osh {
 
 constexpr double kGrav = (double)9.81f;   // g << 0, 0, -IMU::GRAVITY_VALUE (a float constant)
-
-struct LibaDesc {
-  int N, NV, K, L, E, NL, n, max_iter;
-  int pose_off, vel_off, pt_off, edge_off, link_off, lmoff_off, pel_off, peloff_off, lmpose_off;
-  long long H_off;       // n*n doubles (H and S use the same offset in their own arrays)
-  int b_off;             // n doubles
-  double Rcb[9], tcb[3], tbc[3], cam[5];
-  double kb8[4];   // KannalaBrandt8 k1..k4 (osh_liba_problem.kb8)
-  int kb8_on;      // 1: mono edges project through KannalaBrandt8
-  int rig_on;      // 1: fisheye stereo rig, OSH_EDGE_RIGHT edges are EdgeMono(1) on camera 1 of ImuCamPose (src/G2oTypes.cc:56-66)
-  double Rrl[9], trl[3], Rcb1[9], tbc1[3], cam2[8];   // Trl; Rcb[1] = Rrl Rcb[0]; tbc[1] = -Rbc[1] tcb[1]; right camera fx fy cx cy k1..k4
-  double huber_mono, huber_stereo, huber_inertial, lambda_init;
-  int n_colours;         // inertial links are coloured so that the links of one colour share no keyframe (liba_device.hip)
-  int il;                // layout of the reduced unknowns: 0 = [pose 6] x N then [velocity, gyro bias, accelerometer bias 9] x N (every
-                         // LocalInertialBA window), 1 = [pose 6 | v bg ba 9] per keyframe (map-sized problems: with the keyframes in
-                         // temporal order the reduced system is then BANDED -- landmarks and IMU links couple nearby keyframes only)
-  int bw, bw_kf;         // il = 1: entries (r, c) with |r - c| > bw are structurally zero and never touched; bw_kf = the same in keyframes
-};
 
 struct VisEval { double r[3], chi2, Xc[3]; };
 
