@@ -50,6 +50,12 @@ class KeyFrame {
   std::set<KeyFrame*> GetLoopEdges() { return mspLoopEdges; }
   std::vector<KeyFrame*> GetCovisiblesByWeight(const int& w);   // the prefix of the weight-ordered list with weights >= w
   int GetWeight(KeyFrame* pKF);                                  // 0 when not connected
+  // what KeyFrameDatabase reads (src/KeyFrame.cc:224-251): the keys of the weight map, the first N of the weight-ordered list
+  std::set<KeyFrame*> GetConnectedKeyFrames() { std::set<KeyFrame*> s; for (const auto& e : mConnectedKeyFrameWeights) s.insert(e.first); return s; }
+  std::vector<KeyFrame*> GetBestCovisibilityKeyFrames(const int& N) {
+    if ((int)mvpOrderedConnectedKeyFrames.size() < N) return mvpOrderedConnectedKeyFrames;
+    return std::vector<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + N);
+  }
   // candidate generator of the Sim3 searches (src/KeyFrame.cc:704-750): the grid is the one of the Frame the keyframe was made from
   std::vector<size_t> GetFeaturesInArea(const float& x, const float& y, const float& r, const bool bRight = false) const;
   bool IsInImage(const float& x, const float& y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }
@@ -59,6 +65,13 @@ class KeyFrame {
   long unsigned int mnId;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
   long unsigned int mnBALocalForMerge = 0;   // include/KeyFrame.h:318
+  // markers of KeyFrameDatabase (include/KeyFrame.h:334-342)
+  long unsigned int mnRelocQuery = 0;
+  int mnRelocWords = 0;
+  float mRelocScore = 0;
+  long unsigned int mnPlaceRecognitionQuery = 0;
+  int mnPlaceRecognitionWords = 0;
+  float mPlaceRecognitionScore = 0;
   // global BA results kept beside the live pose until the loop-closing thread applies them (include/KeyFrame.h:369-372)
   Sophus::SE3f mTcwGBA;
   Sophus::SE3f mTcwBefMerge, mTwcBefMerge;   // include/KeyFrame.h:376-377: poses before a map merge moved them

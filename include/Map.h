@@ -19,6 +19,7 @@ class Map {
   KeyFrame* GetOriginKF() { return mpKFinitial; }                     // src/Map.cc:186-189
   void IncreaseChangeIndex() { ++mnMapChange; }
   int GetMapChangeIndex() { return mnMapChange; }
+  bool IsBad() { return mbBad; }                                      // src/Map.cc:246-249
   std::mutex mMutexMapUpdate;
   std::set<long unsigned int> msOptKFs;
   std::set<long unsigned int> msFixedKFs;
@@ -26,6 +27,7 @@ class Map {
   long unsigned int mnInitKFid = 0;
   long unsigned int mnMaxKFid = 0;
   bool mbIsInertial = false;
+  bool mbBad = false;
   int mnMapChange = 0;
   long unsigned int mnKeyFrames = 0;
   std::vector<KeyFrame*> mvpKeyFrames;

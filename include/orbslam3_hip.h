@@ -909,6 +909,67 @@ int osh_orb_bow_transform(osh_orb_ctx* ctx, const osh_bow_vocab* vocab, int32_t 
  * ms[2] kernels, ms[3] download + write-back (the FP64 sums run there). */
 int osh_orb_bow_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- bag-of-words keyframe database */
+/*
+ * The inverted-file walk and the L1 scores of KeyFrameDatabase::DetectNBestCandidates and DetectRelocalizationCandidates
+ * (src/KeyFrameDatabase.cc:604-845): which stored BowVectors share words with a query, how many, and
+ * L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68) of those that share enough.  Integer set intersection and an
+ * order-fixed FP64 sum: every output equals the reference's bit for bit.
+ *
+ * A database is an object of its own, resident on one device and mutable.  It keeps one row per added vector in add order; a row
+ * is named by a 64-bit handle that only ever grows, so ascending handles are add order, the order in which every inverted list of
+ * the reference holds its keyframes.  Any number of osh_orb_ctx of the device, on any threads, may query it at the same time: a
+ * query writes nothing into it.  add, erase and clear wait for running queries and return with their device work complete.
+ *
+ * Word ids arrive ascending and distinct (BowVector iteration order), below the n_words given at creation; anything else is
+ * refused with OSH_ERR_INVALID, more than OSH_BOW_MAX_FEATURES words with OSH_ERR_UNSUPPORTED.  erase marks a row dead; when the
+ * dead entries exceed half of the used arena the next add or erase compacts it first, order and handles kept.  The arenas grow by
+ * doubling, copied device to device.  The table holds up to OSH_BOW_DB_MAX_ROWS rows (OSH_ERR_UNSUPPORTED beyond).
+ * OSH_ZERO_NEW_BUFFERS=1 zero-fills the database's new buffers too.
+ */
+#define OSH_BOW_DB_MAX_ROWS 1048576
+typedef struct osh_bow_db osh_bow_db;
+int  osh_bow_db_create(int device, int64_t n_words, osh_bow_db** out);
+void osh_bow_db_destroy(osh_bow_db* db);
+/* A new last row; n = 0 is a row that shares no word with anything. */
+int  osh_bow_db_add(osh_bow_db* db, int32_t n, const int32_t* word_id, const double* value, uint64_t* handle);
+/* OSH_ERR_INVALID for a handle that names no live row. */
+int  osh_bow_db_erase(osh_bow_db* db, uint64_t handle);
+/* No row left; handles go on counting. */
+int  osh_bow_db_clear(osh_bow_db* db);
+/* info[0] live rows, [1] rows of the table (dead ones included), [2] used arena entries (dead ones included), [3] arena capacity
+ * in entries, [4] compactions, [5] reallocations so far. */
+int  osh_bow_db_info(osh_bow_db* db, int64_t info[6]);
+
+typedef struct osh_bow_db_query {
+  int32_t n;                 /* words of the query vector                                          */
+  const int32_t* word_id;    /* [n] ascending, distinct                                            */
+  const double* value;       /* [n]                                                                */
+  int32_t n_excluded;
+  const uint64_t* excluded;  /* [n_excluded] handles in any order; one that names no live row is ignored */
+} osh_bow_db_query;
+/* Caller-allocated; the arrays hold `capacity` entries each and may be NULL. */
+typedef struct osh_bow_db_result {
+  int32_t capacity;
+  int32_t* max_common;       /* [1] the largest number of shared words among the live rows that are not excluded (0: none) */
+  int32_t* min_common;       /* [1] (int)((float)max_common * 0.8f), src/KeyFrameDatabase.cc:648                           */
+  int32_t* n_rows;           /* [1] listed rows: the live rows that share a word with the query, excluded ones included    */
+  uint64_t* handle;          /*     ascending                                                                              */
+  int32_t* common;           /*     shared words                                                                           */
+  int32_t* first_word;       /*     the smallest shared word id                                                            */
+  uint8_t* scored;           /*     1: not excluded and common > min_common                                                */
+  double* score;             /*     the L1 score of a scored row, else 0                                                   */
+} osh_bow_db_result;
+/* n_queries queries against one database in one call.  A result whose capacity is below its n_rows gets max_common, min_common and
+ * n_rows only, and the call returns OSH_ERR_INVALID; the number of live rows (osh_bow_db_info) always suffices.  Refused with
+ * OSH_ERR_INVALID: a database of another device, word ids as for add; with OSH_ERR_UNSUPPORTED: n_queries times the rows of the
+ * table above 2^26.  A refused call leaves context and database usable. */
+int osh_orb_bow_db_query(osh_orb_ctx* ctx, osh_bow_db* db, int32_t n_queries, const osh_bow_db_query* queries,
+                         const osh_bow_db_result* results);
+/* Host-clock phases (ms) of the last osh_orb_bow_db_query under osh_orb_set_profiling: ms[0] validation + staging, ms[1] upload,
+ * ms[2] kernels, ms[3] download + write-back. */
+int osh_orb_bow_db_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -431,6 +431,66 @@ int osh_host_bow_compute(osh_host_bow_vocab* h, int32_t keyframe, int32_t n, con
 /* ORBVocabulary::score of two BowVectors given as (word id, value) lists. */
 double osh_host_bow_score(int32_t n1, const int32_t* id1, const double* value1, int32_t n2, const int32_t* id2, const double* value2);
 
+/* ---- KeyFrameDatabase (include/KeyFrameDatabase.h, csrc/host/KeyFrameDatabase.cc, csrc/hosttest/kfdb.cc) ---- */
+/* A stand-in graph from flat arrays: keyframes with their BowVector, map, bad flag, weight-ordered covisibles
+ * (GetBestCovisibilityKeyFrames reads their first 10) and connected set (GetConnectedKeyFrames), maps with their bad flag, and
+ * frames (mnId and BowVector) for relocalisation.  Word ids ascend inside a vector and lie below n_words. */
+typedef struct osh_host_kfdb_graph {
+  int64_t n_words;
+  int32_t n_kf;
+  const int32_t* kf_id;      /* [n_kf]   mnId                                         */
+  const int32_t* kf_map;     /* [n_kf]   index of its map                             */
+  const uint8_t* kf_bad;     /* [n_kf]   isBad()                                      */
+  const int32_t* bow_start;  /* [n_kf+1] mBowVec of keyframe k: entries [bow_start[k], bow_start[k+1]) */
+  const int32_t* bow_word;
+  const double* bow_value;
+  const int32_t* cov_start;  /* [n_kf+1] mvpOrderedConnectedKeyFrames, as keyframe indices */
+  const int32_t* cov;
+  const int32_t* con_start;  /* [n_kf+1] keys of mConnectedKeyFrameWeights             */
+  const int32_t* con;
+  int32_t n_maps;
+  const uint8_t* map_bad;    /* [n_maps] Map::IsBad()                                 */
+  int32_t n_frames;
+  const int32_t* fr_id;      /* [n_frames] mnId                                       */
+  const int32_t* fr_start;   /* [n_frames+1]                                          */
+  const int32_t* fr_word;
+  const double* fr_value;
+} osh_host_kfdb_graph;
+/* A script is n_ops triples (code, a, b). */
+#define OSH_HOST_KFDB_ADD        0  /* add(keyframe a)                                                    */
+#define OSH_HOST_KFDB_ERASE      1  /* erase(keyframe a)                                                  */
+#define OSH_HOST_KFDB_CLEAR_MAP  2  /* clearMap(map a)                                                    */
+#define OSH_HOST_KFDB_CLEAR      3  /* clear()                                                            */
+#define OSH_HOST_KFDB_NBEST      4  /* DetectNBestCandidates(keyframe a, loop, merge, b)                  */
+#define OSH_HOST_KFDB_RELOC      5  /* DetectRelocalizationCandidates(frame a, map b); result in `loop`   */
+/* Per query of the script, in script order (each pointer may be NULL): the candidate lists as keyframe indices and, after the query,
+ * of every keyframe mnPlaceRecognitionQuery, mnPlaceRecognitionWords, mnRelocQuery, mnRelocWords (marker) and
+ * mPlaceRecognitionScore, mRelocScore (score). */
+typedef struct osh_host_kfdb_out {
+  int32_t* n_loop;   /* [queries]          */
+  int32_t* loop;     /* [queries * n_kf]   */
+  int32_t* n_merge;  /* [queries]          */
+  int32_t* merge;    /* [queries * n_kf]   */
+  int64_t* marker;   /* [queries * n_kf * 4] */
+  float* score;      /* [queries * n_kf * 2] */
+} osh_host_kfdb_out;
+/* The script on a plain single-thread restatement of the reference's class with its std::vector<std::list<KeyFrame*>> inverted file
+ * (the bad-keyframe skip at :712 as in the drop-in class).  Returns the number of queries, -1 for bad arguments.  *ms = wall time
+ * of the queries alone. */
+int osh_host_kfdb_restatement(const osh_host_kfdb_graph* graph, int32_t n_ops, const int32_t* ops, const osh_host_kfdb_out* out, double* ms);
+/* The script on an ORB_SLAM3::KeyFrameDatabase constructed on the vocabulary.  -2: the vocabulary has fewer than n_words words. */
+int osh_host_kfdb_run(osh_host_bow_vocab* voc, const osh_host_kfdb_graph* graph, int32_t n_ops, const int32_t* ops, const osh_host_kfdb_out* out,
+                      double* ms);
+/* bowdb_check_words of csrc/bowdb_book.h: 0 accepted, 1 not ascending or a duplicate, 2 an id outside [0, n_words). */
+int osh_host_bowdb_check_words(int32_t n, const int32_t* word_id, int64_t n_words);
+/* A script of n_ops pairs (0, entries of the new row) / (1, handle to erase) / (2, unused: clear) through BowDbBook of
+ * csrc/bowdb_book.h the way osh_bow_db runs it; needs no device.  op_handle [n_ops]: the handle an add returned (0 otherwise).
+ * The row table afterwards (up to max_rows rows; each array may be NULL) and info = live rows, rows, entries, entry capacity,
+ * compactions, reallocations, row capacity, entries moved by the plans.  Returns the rows of the table; -1 bad arguments, -2 an
+ * erase of a handle that names no live row, -3 more than max_rows rows. */
+int osh_host_bowdb_book_replay(int32_t n_ops, const int64_t* ops, uint64_t* op_handle, int32_t max_rows, uint64_t* handle, int64_t* start,
+                               int32_t* len, uint8_t* alive, int64_t info[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -351,7 +351,23 @@ class BowResult(C.Structure):
                 ("feat_node", c_int32_p), ("feat_dist", c_int32_p)]
 
 
+class BowDbQuery(C.Structure):
+    """``osh_bow_db_query`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n", C.c_int32), ("word_id", c_int32_p), ("value", c_double_p), ("n_excluded", C.c_int32),
+                ("excluded", C.POINTER(C.c_uint64))]
+
+
+class BowDbResult(C.Structure):
+    """``osh_bow_db_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("capacity", C.c_int32), ("max_common", c_int32_p), ("min_common", c_int32_p), ("n_rows", c_int32_p),
+                ("handle", C.POINTER(C.c_uint64)), ("common", c_int32_p), ("first_word", c_int32_p), ("scored", c_uint8_p),
+                ("score", c_double_p)]
+
+
 OSH_BOW_MAX_K, OSH_BOW_MAX_L, OSH_BOW_MAX_FEATURES = 20, 10, 16384
+OSH_BOW_DB_MAX_ROWS = 1 << 20
 OSH_BOW_TF_IDF, OSH_BOW_TF, OSH_BOW_IDF, OSH_BOW_BINARY = range(4)
 (OSH_BOW_L1_NORM, OSH_BOW_L2_NORM, OSH_BOW_CHI_SQUARE, OSH_BOW_KL, OSH_BOW_BHATTACHARYYA, OSH_BOW_DOT_PRODUCT) = range(6)
 
@@ -421,6 +437,14 @@ _SIGNATURES = {
     "osh_bow_vocab_destroy": (None, [C.c_void_p]),
     "osh_orb_bow_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BowFrame), C.POINTER(BowResult)]),
     "osh_orb_bow_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_bow_db_create": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_void_p)]),
+    "osh_bow_db_destroy": (None, [C.c_void_p]),
+    "osh_bow_db_add": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_double_p, C.POINTER(C.c_uint64)]),
+    "osh_bow_db_erase": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "osh_bow_db_clear": (C.c_int, [C.c_void_p]),
+    "osh_bow_db_info": (C.c_int, [C.c_void_p, c_int64_p]),
+    "osh_orb_bow_db_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(BowDbQuery), C.POINTER(BowDbResult)]),
+    "osh_orb_bow_db_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_pgo_solve": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), C.POINTER(PgoResult)]),
     "osh_pgo_linearize": (C.c_int, [C.c_void_p, C.POINTER(PgoProblem), c_double_p, c_double_p, c_double_p]),
     "osh_pgo4_solve": (C.c_int, [C.c_void_p, C.POINTER(Pgo4Problem), C.POINTER(Pgo4Result)]),
@@ -560,6 +584,33 @@ _HOST_SIGNATURES = {
     "osh_host_search_keyframe": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, c_int32_p, C.c_int32, c_float_p, c_uint8_p, c_float_p,
                                            c_uint8_p, c_uint8_p, c_int32_p, C.c_float, C.c_int32, C.c_int32, c_int32_p]),
 }
+
+
+class HostKfdbGraph(C.Structure):
+    """``osh_host_kfdb_graph`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("n_words", C.c_int64), ("n_kf", C.c_int32), ("kf_id", c_int32_p), ("kf_map", c_int32_p), ("kf_bad", c_uint8_p),
+                ("bow_start", c_int32_p), ("bow_word", c_int32_p), ("bow_value", c_double_p), ("cov_start", c_int32_p), ("cov", c_int32_p),
+                ("con_start", c_int32_p), ("con", c_int32_p), ("n_maps", C.c_int32), ("map_bad", c_uint8_p), ("n_frames", C.c_int32),
+                ("fr_id", c_int32_p), ("fr_start", c_int32_p), ("fr_word", c_int32_p), ("fr_value", c_double_p)]
+
+
+class HostKfdbOut(C.Structure):
+    """``osh_host_kfdb_out`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("n_loop", c_int32_p), ("loop", c_int32_p), ("n_merge", c_int32_p), ("merge", c_int32_p), ("marker", c_int64_p),
+                ("score", c_float_p)]
+
+
+(OSH_HOST_KFDB_ADD, OSH_HOST_KFDB_ERASE, OSH_HOST_KFDB_CLEAR_MAP, OSH_HOST_KFDB_CLEAR, OSH_HOST_KFDB_NBEST, OSH_HOST_KFDB_RELOC) = range(6)
+
+_HOST_SIGNATURES.update({
+    "osh_host_kfdb_restatement": (C.c_int, [C.POINTER(HostKfdbGraph), C.c_int32, c_int32_p, C.POINTER(HostKfdbOut), c_double_p]),
+    "osh_host_kfdb_run": (C.c_int, [C.c_void_p, C.POINTER(HostKfdbGraph), C.c_int32, c_int32_p, C.POINTER(HostKfdbOut), c_double_p]),
+    "osh_host_bowdb_check_words": (C.c_int, [C.c_int32, c_int32_p, C.c_int64]),
+    "osh_host_bowdb_book_replay": (C.c_int, [C.c_int32, c_int64_p, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint64), c_int64_p, c_int32_p,
+                                             c_uint8_p, c_int64_p]),
+})
 
 
 class HostLoop(C.Structure):

@@ -816,3 +816,84 @@ def bow_score(id1, value1, id2, value2) -> float:
     a = [_i32(id1), np.ascontiguousarray(value1, np.float64), _i32(id2), np.ascontiguousarray(value2, np.float64)]
     return float(lib.osh_host_bow_score(len(a[0]), capi.ptr(a[0], capi.c_int32_p), capi.ptr(a[1], capi.c_double_p),
                                         len(a[2]), capi.ptr(a[2], capi.c_int32_p), capi.ptr(a[3], capi.c_double_p)))
+
+
+def _kfdb_graph(g):
+    """capi.HostKfdbGraph of a synth_kfdb.KfdbGraph and the arrays its pointers refer to."""
+    def csr(lists, dtype=np.int32):
+        start = np.zeros(len(lists) + 1, np.int32)
+        start[1:] = np.cumsum([len(x) for x in lists])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype) for x in lists] + [np.zeros(0, dtype)]), dtype)
+        return start, flat
+    a = dict(kf_id=_i32(g.kf_id), kf_map=_i32(g.kf_map), kf_bad=np.ascontiguousarray(g.kf_bad, np.uint8),
+             map_bad=np.ascontiguousarray(g.map_bad, np.uint8), fr_id=_i32([f[0] for f in g.frames]))
+    a["bow_start"], a["bow_word"] = csr([b[0] for b in g.bow])
+    _, a["bow_value"] = csr([b[1] for b in g.bow], np.float64)
+    a["cov_start"], a["cov"] = csr(g.cov)
+    a["con_start"], a["con"] = csr(g.con)
+    a["fr_start"], a["fr_word"] = csr([f[1] for f in g.frames])
+    _, a["fr_value"] = csr([f[2] for f in g.frames], np.float64)
+    c = capi.HostKfdbGraph()
+    c.n_words, c.n_kf, c.n_maps, c.n_frames = int(g.n_words), g.n_kf, len(g.map_bad), len(g.frames)
+    for name, arr in a.items():
+        typ = {np.dtype(np.int32): capi.c_int32_p, np.dtype(np.uint8): capi.c_uint8_p, np.dtype(np.float64): capi.c_double_p}[arr.dtype]
+        setattr(c, name, capi.ptr(arr, typ))
+    return c, a
+
+
+def _kfdb_script(symbol, handle, g, ops):
+    """Runs a script of (code, a, b) operations; per query a dict with loop / merge (keyframe indices), marker [n_kf, 4] and
+    score [n_kf, 2] (see osh_host_kfdb_out), and the wall time of the queries in ms."""
+    lib = capi.load_host_library()
+    c, _keep = _kfdb_graph(g)
+    ops = np.ascontiguousarray(ops, np.int32).reshape(-1, 3)
+    nq = max(int(np.sum(ops[:, 0] >= 4)), 1)
+    n = max(g.n_kf, 1)
+    o = dict(n_loop=np.zeros(nq, np.int32), loop=np.zeros((nq, n), np.int32), n_merge=np.zeros(nq, np.int32), merge=np.zeros((nq, n), np.int32),
+             marker=np.zeros((nq, n, 4), np.int64), score=np.zeros((nq, n, 2), np.float32))
+    out = capi.HostKfdbOut()
+    for name, arr in o.items():
+        typ = {np.dtype(np.int32): capi.c_int32_p, np.dtype(np.int64): capi.c_int64_p, np.dtype(np.float32): capi.c_float_p}[arr.dtype]
+        setattr(out, name, capi.ptr(arr, typ))
+    ms = C.c_double(0)
+    args = (C.byref(c), ops.shape[0], capi.ptr(ops, capi.c_int32_p), C.byref(out), C.byref(ms))
+    rc = getattr(lib, symbol)(*(args if handle is None else (handle,) + args))
+    if rc < 0:
+        raise RuntimeError(f"{symbol} returned {rc}")
+    res = [dict(loop=o["loop"][q, :o["n_loop"][q]].tolist(), merge=o["merge"][q, :o["n_merge"][q]].tolist(),
+                marker=o["marker"][q, :g.n_kf].copy(), score=o["score"][q, :g.n_kf].copy()) for q in range(rc)]
+    return res, float(ms.value)
+
+
+def kfdb_restatement(g, ops):
+    """The script on the single-thread C++ restatement of the reference's KeyFrameDatabase (osh_host_kfdb_restatement)."""
+    return _kfdb_script("osh_host_kfdb_restatement", None, g, ops)
+
+
+def kfdb_run(voc: "HostBowVocab", g, ops):
+    """The script on an ORB_SLAM3::KeyFrameDatabase over the loaded vocabulary (osh_host_kfdb_run)."""
+    return _kfdb_script("osh_host_kfdb_run", voc.h, g, ops)
+
+
+def bowdb_check_words(word_id, n_words: int) -> int:
+    """bowdb_check_words of csrc/bowdb_book.h: 0 accepted, 1 not ascending or a duplicate, 2 an id outside the vocabulary."""
+    w = _i32(word_id)
+    return int(capi.load_host_library().osh_host_bowdb_check_words(len(w), capi.ptr(w, capi.c_int32_p), int(n_words)))
+
+
+def bowdb_book_replay(ops, max_rows: int = 1 << 16) -> dict:
+    """A script of (0, entries) adds, (1, handle) erases and (2, 0) clears through the bookkeeping of osh_bow_db, without a device:
+    op_handle per operation, the row table (handle, start, len, alive) and info (osh_host_bowdb_book_replay)."""
+    lib = capi.load_host_library()
+    ops = np.ascontiguousarray(ops, np.int64).reshape(-1, 2)
+    u64 = C.POINTER(C.c_uint64)
+    o = dict(op_handle=np.zeros(max(len(ops), 1), np.uint64), handle=np.zeros(max_rows, np.uint64), start=np.zeros(max_rows, np.int64),
+             len=np.zeros(max_rows, np.int32), alive=np.zeros(max_rows, np.uint8), info=np.zeros(8, np.int64))
+    rc = lib.osh_host_bowdb_book_replay(len(ops), capi.ptr(ops, capi.c_int64_p), capi.ptr(o["op_handle"], u64), max_rows, capi.ptr(o["handle"], u64),
+                                        capi.ptr(o["start"], capi.c_int64_p), capi.ptr(o["len"], capi.c_int32_p),
+                                        capi.ptr(o["alive"], capi.c_uint8_p), capi.ptr(o["info"], capi.c_int64_p))
+    if rc < 0:
+        raise RuntimeError(f"osh_host_bowdb_book_replay returned {rc}")
+    names = ("live_rows", "rows", "entries", "capacity", "compactions", "reallocations", "row_capacity", "moved")
+    return dict(op_handle=o["op_handle"][:len(ops)], handle=o["handle"][:rc], start=o["start"][:rc], len=o["len"][:rc], alive=o["alive"][:rc],
+                info=dict(zip(names, (int(x) for x in o["info"]))))

@@ -156,6 +156,16 @@ class OrbMatcher:
     stereo_times = functools.partialmethod(_times, "osh_orb_stereo_get_times")                   # of the last stereo_match
     fisheye_stereo_times = functools.partialmethod(_times, "osh_orb_fisheye_stereo_get_times")   # of the last fisheye_stereo_match
     bow_times = functools.partialmethod(_times, "osh_orb_bow_get_times")                         # of the last bow_transform
+    bow_db_times = functools.partialmethod(_times, "osh_orb_bow_db_get_times")                   # of the last bow_db_query
+
+    def bow_db_query(self, db: "BowDb", queries) -> list:
+        """The inverted-file walk and the L1 scores of KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates
+        for a batch of queries in one osh_orb_bow_db_query call.  A query is (word_id, value) or (word_id, value, excluded
+        handles); per query a dict with max_common, min_common and, for the live rows that share a word, in ascending handle
+        order: handle, common, first_word, scored, score."""
+        cq, cr, _keep, outs = bow_db_args(queries, db.info()["live_rows"])
+        capi.check(self.lib.osh_orb_bow_db_query(self.ctx, db.handle, len(queries), cq, cr), "osh_orb_bow_db_query", self.lib)
+        return [bow_db_trim(o) for o in outs]
 
     def bow_transform(self, vocab: "BowVocab", frames, levelsup: int = 4, stages: bool = False) -> list:
         """TemplatedVocabulary::transform for a batch of descriptor arrays [n, 32] in one osh_orb_bow_transform call: per frame a
@@ -219,8 +229,51 @@ class BowVocab:
         self.close()
 
 
+class BowDb:
+    """A device-resident, mutable database of BowVectors (osh_bow_db) over a vocabulary of n_words words; queried through
+    OrbMatcher.bow_db_query by any number of matchers of the device at once."""
+
+    INFO = ("live_rows", "rows", "entries", "capacity", "compactions", "reallocations")
+
+    def __init__(self, n_words: int, device: int = 0):
+        self.lib = capi.load_library()
+        self.handle = C.c_void_p()
+        capi.check(self.lib.osh_bow_db_create(device, int(n_words), C.byref(self.handle)), "osh_bow_db_create", self.lib)
+
+    def close(self):
+        if self.handle:
+            self.lib.osh_bow_db_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, word_id, value) -> int:
+        """A new last row; its handle."""
+        w, v = np.ascontiguousarray(word_id, np.int32), np.ascontiguousarray(value, np.float64)
+        assert w.shape == v.shape and w.ndim == 1
+        h = C.c_uint64(0)
+        capi.check(self.lib.osh_bow_db_add(self.handle, w.shape[0], capi.ptr(w, capi.c_int32_p), capi.ptr(v, capi.c_double_p), C.byref(h)),
+                   "osh_bow_db_add", self.lib)
+        return int(h.value)
+
+    def erase(self, handle: int):
+        capi.check(self.lib.osh_bow_db_erase(self.handle, int(handle)), "osh_bow_db_erase", self.lib)
+
+    def clear(self):
+        capi.check(self.lib.osh_bow_db_clear(self.handle), "osh_bow_db_clear", self.lib)
+
+    def info(self) -> dict:
+        a = np.zeros(6, np.int64)
+        capi.check(self.lib.osh_bow_db_info(self.handle, capi.ptr(a, capi.c_int64_p)), "osh_bow_db_info", self.lib)
+        return dict(zip(self.INFO, (int(x) for x in a)))
+
+
 _POINTER = {np.dtype(np.float32): capi.c_float_p, np.dtype(np.int32): capi.c_int32_p, np.dtype(np.uint8): capi.c_uint8_p,
-            np.dtype(np.float64): capi.c_double_p}
+            np.dtype(np.float64): capi.c_double_p, np.dtype(np.uint64): C.POINTER(C.c_uint64)}
 # the keypoint arrays of a frame: attribute of the synthetic frame = field of the frame struct, key in the dict of arrays, dtype
 _KEYPOINTS = (("left_xy", "lxy", np.float32), ("left_octave", "loct", np.int32), ("left_desc", "ldesc", np.uint8),
               ("right_xy", "rxy", np.float32), ("right_octave", "roct", np.int32), ("right_desc", "rdesc", np.uint8))
@@ -327,6 +380,37 @@ def bow_args(frames, stages: bool = False):
         keep.append(d)
         outs.append(o)
     return cf, cr, keep, outs
+
+
+def bow_db_args(queries, capacity: int):
+    """The osh_bow_db_query / osh_bow_db_result arrays of OrbMatcher.bow_db_query for repeated calls: (queries, results, the arrays
+    that keep their pointers alive, the per-query dicts of output arrays of `capacity` entries)."""
+    n = len(queries)
+    cq = (capi.BowDbQuery * max(n, 1))()
+    cr = (capi.BowDbResult * max(n, 1))()
+    keep, outs = [], []
+    for k, q in enumerate(queries):
+        w, v = np.ascontiguousarray(q[0], np.int32), np.ascontiguousarray(q[1], np.float64)
+        ex = np.ascontiguousarray(q[2] if len(q) > 2 else [], np.uint64)
+        assert w.shape == v.shape and w.ndim == 1
+        cq[k].n, cq[k].word_id, cq[k].value = w.shape[0], capi.ptr(w, capi.c_int32_p), capi.ptr(v, capi.c_double_p)
+        cq[k].n_excluded, cq[k].excluded = ex.shape[0], capi.ptr(ex, C.POINTER(C.c_uint64))
+        o = dict(max_common=np.zeros(1, np.int32), min_common=np.zeros(1, np.int32), n_rows=np.zeros(1, np.int32),
+                 handle=np.zeros(capacity, np.uint64), common=np.zeros(capacity, np.int32), first_word=np.zeros(capacity, np.int32),
+                 scored=np.zeros(capacity, np.uint8), score=np.zeros(capacity, np.float64))
+        cr[k].capacity = capacity
+        _wire_outputs(cr[k], o)
+        keep.append((w, v, ex))
+        outs.append(o)
+    return cq, cr, keep, outs
+
+
+def bow_db_trim(o: dict) -> dict:
+    """The outputs of a query cut to its listed rows; max_common and min_common as ints."""
+    n = int(o["n_rows"][0])
+    t = {k: o[k][:n] for k in ("handle", "common", "first_word", "scored", "score")}
+    t.update(max_common=int(o["max_common"][0]), min_common=int(o["min_common"][0]))
+    return t
 
 
 def fisheye_stereo_args(frames, stages: bool = False):
