@@ -61,6 +61,9 @@ class KeyFrame {
   bool IsInImage(const float& x, const float& y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }
   // src/KeyFrame.cc:92-102: as Frame::ComputeBoW, only if mBowVec or mFeatVec is empty (stand-in body: csrc/hosttest/bow.cc)
   void ComputeBoW();
+  // what LocalMapping::CreateNewMapPoints calls (src/KeyFrame.cc:755-772 and :774-807; stand-in bodies: csrc/hosttest/newpoints.cc)
+  bool UnprojectStereo(int i, Eigen::Vector3f& x3D);
+  float ComputeSceneMedianDepth(const int q);
 
   long unsigned int mnId;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
@@ -79,6 +82,9 @@ class KeyFrame {
   Eigen::Vector3f mVwbGBA;                   // include/KeyFrame.h:373-375: what FullInertialBA leaves for the loop closer
   IMU::Bias mBiasGBA;
   float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+  float invfx = 0, invfy = 0, mb = 0;          // include/KeyFrame.h:374
+  float mfScaleFactor = 0;                     // include/KeyFrame.h:396
+  std::vector<float> mvDepth;                  // include/KeyFrame.h:384 (negative value for monocular points)
   int N = 0, NLeft = -1;
   std::vector<cv::KeyPoint> mvKeys, mvKeysUn, mvKeysRight;
   ORBVocabulary* mpORBvocabulary = nullptr;   // include/KeyFrame.h:455

@@ -1,0 +1,33 @@
+/* LocalMapping.h -- members of ORB_SLAM3::LocalMapping used by LocalMapping::CreateNewMapPoints (reference include/LocalMapping.h:
+ * 111-112,134,144-145,164-170; src/LocalMapping.cc:398-741).  Minimal test double: the members the method reads, public, and no
+ * thread. */
+#ifndef LOCALMAPPING_H
+#define LOCALMAPPING_H
+#include <list>
+#include <mutex>
+#include "Atlas.h"
+#include "KeyFrame.h"
+#include "MapPoint.h"
+#include "Tracking.h"
+namespace ORB_SLAM3 {
+class LocalMapping {
+ public:
+  // src/LocalMapping.cc:398-741: the neighbour list, the baseline test and ORBmatcher::SearchForTriangulation per neighbour on the
+  // host side, the per-match body (:503-720) in one osh_orb_triangulate_new_points call per neighbour, the map points created from
+  // its results in match order (csrc/host/LocalMapping.cc)
+  void CreateNewMapPoints();
+  bool CheckNewKeyFrames() { std::unique_lock<std::mutex> lock(mMutexNewKFs); return !mlNewKeyFrames.empty(); }   // :342-346
+
+  bool mbFarPoints = false;
+  float mThFarPoints = 0;
+  bool mbMonocular = false;
+  bool mbInertial = false;
+  Atlas* mpAtlas = nullptr;
+  Tracking* mpTracker = nullptr;
+  KeyFrame* mpCurrentKeyFrame = nullptr;
+  std::list<KeyFrame*> mlNewKeyFrames;
+  std::list<MapPoint*> mlpRecentAddedMapPoints;
+  std::mutex mMutexNewKFs;
+};
+}  // namespace ORB_SLAM3
+#endif

@@ -20,6 +20,8 @@ class Map {
   void IncreaseChangeIndex() { ++mnMapChange; }
   int GetMapChangeIndex() { return mnMapChange; }
   bool IsBad() { return mbBad; }                                      // src/Map.cc:246-249
+  bool GetIniertialBA2() { return mbIMU_BA2; }                        // src/Map.cc:315-319
+  void AddMapPoint(MapPoint* pMP) { mvpMapPoints.push_back(pMP); }    // src/Map.cc:80-84 (a set there)
   std::mutex mMutexMapUpdate;
   std::set<long unsigned int> msOptKFs;
   std::set<long unsigned int> msFixedKFs;
@@ -28,6 +30,7 @@ class Map {
   long unsigned int mnMaxKFid = 0;
   bool mbIsInertial = false;
   bool mbBad = false;
+  bool mbIMU_BA2 = false;
   int mnMapChange = 0;
   long unsigned int mnKeyFrames = 0;
   std::vector<KeyFrame*> mvpKeyFrames;

@@ -14,6 +14,8 @@ class Map;
 class MapPoint {
  public:
   MapPoint(long unsigned int id, const Eigen::Vector3f& Pos, Map* pMap) : mnId(id), mWorldPos(Pos), mpMap(pMap) {}
+  // src/MapPoint.cc:39-56: the constructor of LocalMapping::CreateNewMapPoints; ids count up from nNextId
+  MapPoint(const Eigen::Vector3f& Pos, KeyFrame* pRefKF, Map* pMap) : mnId(nNextId++), mWorldPos(Pos), mpMap(pMap), mpRefKF(pRefKF) {}
   void SetWorldPos(const Eigen::Vector3f& Pos) { mWorldPos = Pos; }
   Eigen::Vector3f GetWorldPos() { return mWorldPos; }
   std::map<KeyFrame*, std::tuple<int, int>> GetObservations() { return mObservations; }
@@ -42,6 +44,7 @@ class MapPoint {
   Eigen::Vector3f GetNormal() { return mNormalVector; }
   KeyFrame* GetReferenceKeyFrame() { return mpRefKF; }
 
+  static long unsigned int nNextId;           // include/MapPoint.h:165
   static std::mutex mGlobalMutex;             // include/MapPoint.h:151 (held while PoseOptimization reads the positions)
   long unsigned int mnId;
   long unsigned int mnBALocalForKF = 0;

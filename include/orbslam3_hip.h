@@ -842,6 +842,106 @@ typedef struct osh_kb8_rig {
 int osh_kb8_triangulate(osh_orb_ctx* ctx, int32_t n, const osh_kb8_rig* rig, const float* xy1, const float* xy2, const float* sigma1,
                         const float* sigma2, float* ret, float* p3d, float* cos_parallax);
 
+/* ------------------------------------------------- new map points (triangulation) */
+/*
+ * The per-match body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:503-720) for n_segments segments in one call.  A
+ * segment is one (current keyframe, neighbour) pair with the matches ORBmatcher::SearchForTriangulation found between them.  Per
+ * match: the right / left pose and camera choice of a rig from idx and NLeft (:503-575), the ray parallax against the stereo
+ * parallax (:577-597), GeometricTools::Triangulate (src/GeometricTools.cc:47-66), KeyFrame::UnprojectStereo
+ * (src/KeyFrame.cc:755-772) of either keyframe or giving up (:599-635), the depth tests, the mono (5.991) or stereo (7.8)
+ * re-projection tests of both keyframes (:637-697), the far-point limit and the scale consistency (:699-720).  The quirks stay:
+ * the stereo test of the second keyframe subtracts the CURRENT keyframe's mbf * invz2 (:690), cosParallaxStereo2 is only computed
+ * when bStereo1 is false (:591), bStereo is false for a keyframe with a second camera (:507,520).
+ *
+ * Arithmetic as osh_orb_fisheye_stereo_match: single IEEE float32 operations in the reference's order, no fused multiply-add,
+ * three-term reductions as a0 + (a1 + a2), sqrt / atan2 / cos / tan / sin as the FP64 function rounded once, double comparisons
+ * where the reference compares with a double literal.  The same deliberate deviation: the null vector of A is computed in FP64 by
+ * the fixed-sweep one-sided Jacobi method, x3Dh(3) == 0 is tested on it, and x3D = head(3) / w is rounded to float32 once.
+ * UnprojectStereo takes the match's pt (mvKeysUn) for mvKeys[i].pt: the same pixel on a rectified keyframe.
+ *
+ * Refused before any device work and without a context, which stays usable: with OSH_ERR_INVALID a negative count, a NULL array
+ * whose count is not 0, a pose entry, camera parameter, keypoint coordinate, mvuRight, mvDepth, level table entry, ratio_factor or
+ * th_far_points that is not finite, fx or fy equal to 0 (of a keyframe, or of a camera that can be chosen), a camera type outside
+ * the two, n_levels outside [1, OSH_NEWPOINT_MAX_LEVELS], an octave outside [0, n_levels), an index outside [0, n_keys); with
+ * OSH_ERR_UNSUPPORTED more than OSH_NEWPOINT_MAX_SEGMENTS segments or more than OSH_NEWPOINT_MAX_MATCHES matches in one call.
+ * n_segments = 0 and segments without matches are valid.  Every entry of the result arrays is written.
+ */
+#define OSH_NEWPOINT_MAX_LEVELS   OSH_STEREO_MAX_LEVELS
+#define OSH_NEWPOINT_MAX_SEGMENTS 65535
+#define OSH_NEWPOINT_MAX_MATCHES  4194304   /* 2^22, all segments of a call together */
+#define OSH_NEWPOINT_PINHOLE 0   /* GeometricCamera::CAM_PINHOLE */
+#define OSH_NEWPOINT_KB8     1   /* GeometricCamera::CAM_FISHEYE */
+/* stage[i]: where match i stopped, in the reference's order */
+#define OSH_NEWPOINT_LOW_PARALLAX 0   /* the final `continue` (:628): no stereo and very low parallax            */
+#define OSH_NEWPOINT_W_ZERO       1   /* x3Dh(3) == 0 (src/GeometricTools.cc:59)                                */
+#define OSH_NEWPOINT_NO_DEPTH     2   /* UnprojectStereo returned false: mvDepth <= 0                           */
+#define OSH_NEWPOINT_BEHIND_1     3   /* z1 <= 0 (:639)                                                         */
+#define OSH_NEWPOINT_BEHIND_2     4   /* z2 <= 0 (:643)                                                         */
+#define OSH_NEWPOINT_REPROJ_1     5   /* re-projection test of the current keyframe (:658,670)                  */
+#define OSH_NEWPOINT_REPROJ_2     6   /* re-projection test of the neighbour (:684,695)                         */
+#define OSH_NEWPOINT_ZERO_DIST    7   /* dist1 == 0 or dist2 == 0 (:706)                                        */
+#define OSH_NEWPOINT_FAR          8   /* mbFarPoints and a distance >= mThFarPoints (:711)                      */
+#define OSH_NEWPOINT_SCALE        9   /* scale consistency (:719)                                               */
+#define OSH_NEWPOINT_ACCEPTED    10   /* a new map point                                                        */
+/* source[i]: where x3D came from */
+#define OSH_NEWPOINT_TRIANGULATED 0
+#define OSH_NEWPOINT_STEREO_1     1   /* mpCurrentKeyFrame->UnprojectStereo(idx1)                               */
+#define OSH_NEWPOINT_STEREO_2     2   /* pKF2->UnprojectStereo(idx2)                                            */
+#define OSH_NEWPOINT_NO_SOURCE    255 /* stage OSH_NEWPOINT_LOW_PARALLAX                                        */
+typedef struct osh_newpoint_camera {
+  int32_t type;          /* OSH_NEWPOINT_PINHOLE or OSH_NEWPOINT_KB8                                            */
+  float precision;       /* KannalaBrandt8::precision (ignored for a pinhole)                                   */
+  float params[8];       /* mvParameters: fx fy cx cy, then k1 k2 k3 k4 of a KannalaBrandt8                      */
+} osh_newpoint_camera;
+typedef struct osh_newpoint_pose {
+  float Rcw[9], tcw[3];  /* GetPose(): rotation (row-major) and translation                                     */
+  float Rwc[9];          /* its transpose, as the reference forms it (:428,483,568,573)                         */
+  float Ow[3];           /* GetCameraCenter()                                                                   */
+} osh_newpoint_pose;
+typedef struct osh_newpoint_keyframe {
+  osh_newpoint_pose pose;           /* GetPose / GetCameraCenter                                                 */
+  osh_newpoint_pose right_pose;     /* GetRightPose / GetRightCameraCenter; read only when has_camera2          */
+  int32_t has_camera2;              /* mpCamera2 != nullptr                                                     */
+  osh_newpoint_camera camera;       /* mpCamera                                                                 */
+  osh_newpoint_camera camera2;      /* mpCamera2; read only when has_camera2                                    */
+  float fx, fy, cx, cy, invfx, invfy, mbf, mb;
+  int32_t n_left;                   /* NLeft (-1 without the rig layout)                                        */
+  int32_t n_keys;                   /* N: the length of the keyframe's keypoint arrays, for the index check     */
+  int32_t n_levels;
+  const float* level_sigma2;        /* [n_levels] mvLevelSigma2                                                 */
+  const float* scale_factors;       /* [n_levels] mvScaleFactors                                                */
+} osh_newpoint_keyframe;
+typedef struct osh_newpoint_segment {
+  osh_newpoint_keyframe kf1, kf2;   /* mpCurrentKeyFrame, pKF2                                                  */
+  float ratio_factor;               /* 1.5f * mpCurrentKeyFrame->mfScaleFactor                                  */
+  int32_t inertial;                 /* mbInertial                                                               */
+  int32_t far_points;               /* mbFarPoints                                                              */
+  float th_far_points;              /* mThFarPoints                                                             */
+  int32_t n_matches;
+  const int32_t* idx1;              /* [n_matches]   vMatchedIndices[i].first                                   */
+  const int32_t* idx2;              /* [n_matches]   vMatchedIndices[i].second                                  */
+  const float* pt1;                 /* [n_matches*2] kp1.pt: mvKeysUn / mvKeys / mvKeysRight as :503-505 choose  */
+  const float* pt2;                 /* [n_matches*2] kp2.pt                                                     */
+  const int32_t* octave1;           /* [n_matches]   kp1.octave                                                 */
+  const int32_t* octave2;           /* [n_matches]   kp2.octave                                                 */
+  const float* u_right1;            /* [n_matches]   mpCurrentKeyFrame->mvuRight[idx1]                          */
+  const float* u_right2;            /* [n_matches]   pKF2->mvuRight[idx2]                                       */
+  const float* depth1;              /* [n_matches]   mpCurrentKeyFrame->mvDepth[idx1]                           */
+  const float* depth2;              /* [n_matches]   pKF2->mvDepth[idx2]                                        */
+} osh_newpoint_segment;
+/* Caller-allocated, one entry per match of the segment; each may be NULL. */
+typedef struct osh_newpoint_result {
+  uint8_t* stage;          /* [n_matches]   OSH_NEWPOINT_LOW_PARALLAX .. OSH_NEWPOINT_ACCEPTED                      */
+  uint8_t* source;         /* [n_matches]   OSH_NEWPOINT_TRIANGULATED .. OSH_NEWPOINT_STEREO_2, or NO_SOURCE        */
+  float* cos_parallax;     /* [n_matches]   cosParallaxRays                                                        */
+  float* x3d;              /* [n_matches*3] x3D of a match that reached the depth tests (stage >= BEHIND_1), else 0 */
+} osh_newpoint_result;
+int osh_orb_triangulate_new_points(osh_orb_ctx* ctx, int32_t n_segments, const osh_newpoint_segment* segments,
+                                   const osh_newpoint_result* results);
+/* Host-clock phases (ms) of the last osh_orb_triangulate_new_points under osh_orb_set_profiling: ms[0] validation + staging,
+ * ms[1] upload, ms[2] kernel, ms[3] download + write-back. */
+int osh_orb_newpoint_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 /* ------------------------------------------------- bag-of-words transform */
 /*
  * TemplatedVocabulary::transform (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1259) for ORB descriptors: what

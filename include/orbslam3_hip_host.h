@@ -405,6 +405,63 @@ struct osh_kb8_rig;
 int osh_host_kb8_triangulate_cpu(int32_t n, const struct osh_kb8_rig* rig, const float* xy1, const float* xy2, const float* sigma1,
                                  const float* sigma2, float* ret, float* p3d, float* cos_parallax);
 
+/* ---- LocalMapping::CreateNewMapPoints (include/LocalMapping.h, csrc/host/LocalMapping.cc, csrc/hosttest/newpoints.cc) ---- */
+struct osh_newpoint_segment;
+struct osh_newpoint_result;
+/* csrc/newpoint_triangulate.h (the statements k_newpoint_triangulate runs per match) compiled for the host, on one thread: arguments
+ * as osh_orb_triangulate_new_points without a context and without its validation (the segments must be valid).  *ms (may be NULL) =
+ * wall time of the loop over the matches.  -1: bad arguments. */
+int osh_host_newpoint_triangulate_cpu(int32_t n_segments, const struct osh_newpoint_segment* segments,
+                                      const struct osh_newpoint_result* results, double* ms);
+
+/* A keyframe of the stand-in class from flat arrays.  n_left < 0: mvKeysUn = mvKeys = the n keypoints; else a rig keyframe, the
+ * first n_left keypoints in mvKeys, the rest in mvKeysRight.  Feature i holds a map point at mp_pos[i] already when has_mp[i].
+ * mFeatVec as CSR (node ids ascending).  The level tables are scale_factor^level and its square by repeated float multiplication. */
+typedef struct osh_host_newpoint_kf {
+  int32_t n, n_left;
+  const float* xy;            /* [n*2]  */
+  const int32_t* octave;      /* [n]    */
+  const uint8_t* desc;        /* [n*32] */
+  const float* u_right;       /* [n] mvuRight */
+  const float* depth;         /* [n] mvDepth  */
+  const uint8_t* has_mp;      /* [n]    */
+  const float* mp_pos;        /* [n*3]  */
+  int32_t n_nodes;
+  const int32_t* node_id;     /* [n_nodes]   */
+  const int32_t* node_off;    /* [n_nodes+1] */
+  const int32_t* node_feat;
+  float pose_qt[7];           /* Tcw: qx qy qz qw tx ty tz */
+  float trl_qt[7];            /* mTrl (rig only)           */
+  int32_t camera_kb8;         /* mpCamera: 0 Pinhole, 1 KannalaBrandt8 */
+  float camera[8];
+  int32_t has_camera2;        /* mpCamera2: a KannalaBrandt8 */
+  float camera2[8];
+  float mbf, mb;
+  int32_t n_levels;
+  float scale_factor;
+  int32_t prev;               /* mPrevKF as an index into the scene's keyframes, -1: none */
+} osh_host_newpoint_kf;
+typedef struct osh_host_newpoint_scene {
+  int32_t n_kf;
+  const osh_host_newpoint_kf* kf;      /* kf[0] is mpCurrentKeyFrame */
+  int32_t n_neighbours;
+  const int32_t* neighbours;           /* its covisibles, best first, as indices into kf */
+  int32_t monocular, inertial, far_points;
+  float th_far_points;
+  int32_t recently_lost;               /* mpTracker->mState == Tracking::RECENTLY_LOST */
+  int32_t inertial_ba2;                /* Map::GetIniertialBA2()                        */
+  int32_t new_keyframe_waiting;        /* CheckNewKeyFrames() returns true              */
+} osh_host_newpoint_scene;
+/* LocalMapping::CreateNewMapPoints on the scene.  Returns the number of map points created (in mlpRecentAddedMapPoints order) and,
+ * for the first `capacity` of them: the neighbour (index into kf), idx1, idx2, the position [3], nObs, and flags: bit 0 / 1 the
+ * slot idx1 of the current keyframe / idx2 of the neighbour holds the point, bit 2 / 3 its observation of the current keyframe /
+ * the neighbour names idx1 / idx2 (in the right-camera slot of the tuple for a right keypoint of a rig), bit 4
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth ran once each, bit 5 the map lists it, bit 6 its reference keyframe is the
+ * current one.  poses (may be NULL) [n_kf*48]: Rcw tcw Rwc Ow of the left and of the right pose of every keyframe as the pack hands
+ * them to the device (the right one only for a rig).  -1: bad arguments. */
+int osh_host_create_new_map_points(const osh_host_newpoint_scene* scene, int32_t capacity, int32_t* neighbour, int32_t* idx1, int32_t* idx2,
+                                   float* x3d, int32_t* n_obs, int32_t* flags, float* poses);
+
 /* ---- ORBVocabulary / ComputeBoW (include/ORBVocabulary.h, csrc/host/ORBVocabulary.cc, csrc/hosttest/bow.cc) ---- */
 struct osh_bow_tree;
 struct osh_bow_result;

@@ -330,6 +330,50 @@ class Kb8Rig(C.Structure):
 OSH_FSTEREO_NO_COS = -2.0
 
 
+class NewPointCamera(C.Structure):
+    """``osh_newpoint_camera`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("type", C.c_int32), ("precision", C.c_float), ("params", C.c_float * 8)]
+
+
+class NewPointPose(C.Structure):
+    """``osh_newpoint_pose`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Rwc", C.c_float * 9), ("Ow", C.c_float * 3)]
+
+
+class NewPointKeyFrame(C.Structure):
+    """``osh_newpoint_keyframe`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("pose", NewPointPose), ("right_pose", NewPointPose), ("has_camera2", C.c_int32), ("camera", NewPointCamera),
+                ("camera2", NewPointCamera), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("invfx", C.c_float), ("invfy", C.c_float), ("mbf", C.c_float), ("mb", C.c_float), ("n_left", C.c_int32),
+                ("n_keys", C.c_int32), ("n_levels", C.c_int32), ("level_sigma2", c_float_p), ("scale_factors", c_float_p)]
+
+
+class NewPointSegment(C.Structure):
+    """``osh_newpoint_segment`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("kf1", NewPointKeyFrame), ("kf2", NewPointKeyFrame), ("ratio_factor", C.c_float), ("inertial", C.c_int32),
+                ("far_points", C.c_int32), ("th_far_points", C.c_float), ("n_matches", C.c_int32),
+                ("idx1", c_int32_p), ("idx2", c_int32_p), ("pt1", c_float_p), ("pt2", c_float_p), ("octave1", c_int32_p),
+                ("octave2", c_int32_p), ("u_right1", c_float_p), ("u_right2", c_float_p), ("depth1", c_float_p), ("depth2", c_float_p)]
+
+
+class NewPointResult(C.Structure):
+    """``osh_newpoint_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("stage", c_uint8_p), ("source", c_uint8_p), ("cos_parallax", c_float_p), ("x3d", c_float_p)]
+
+
+OSH_NEWPOINT_MAX_LEVELS, OSH_NEWPOINT_MAX_SEGMENTS, OSH_NEWPOINT_MAX_MATCHES = 16, 65535, 1 << 22
+OSH_NEWPOINT_PINHOLE, OSH_NEWPOINT_KB8 = 0, 1
+(OSH_NEWPOINT_LOW_PARALLAX, OSH_NEWPOINT_W_ZERO, OSH_NEWPOINT_NO_DEPTH, OSH_NEWPOINT_BEHIND_1, OSH_NEWPOINT_BEHIND_2,
+ OSH_NEWPOINT_REPROJ_1, OSH_NEWPOINT_REPROJ_2, OSH_NEWPOINT_ZERO_DIST, OSH_NEWPOINT_FAR, OSH_NEWPOINT_SCALE,
+ OSH_NEWPOINT_ACCEPTED) = range(11)
+OSH_NEWPOINT_TRIANGULATED, OSH_NEWPOINT_STEREO_1, OSH_NEWPOINT_STEREO_2, OSH_NEWPOINT_NO_SOURCE = 0, 1, 2, 255
+
+
 class BowTree(C.Structure):
     """``osh_bow_tree`` (include/orbslam3_hip.h)."""
 
@@ -432,6 +476,8 @@ _SIGNATURES = {
     "osh_orb_fisheye_stereo_match": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FisheyeStereoFrame), C.POINTER(FisheyeStereoResult)]),
     "osh_orb_fisheye_stereo_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_kb8_triangulate": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
+    "osh_orb_triangulate_new_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(NewPointSegment), C.POINTER(NewPointResult)]),
+    "osh_orb_newpoint_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_bow_tree_check": (C.c_int, [C.POINTER(BowTree)]),
     "osh_bow_vocab_create": (C.c_int, [C.c_int, C.POINTER(BowTree), C.POINTER(C.c_void_p)]),
     "osh_bow_vocab_destroy": (None, [C.c_void_p]),
@@ -486,9 +532,31 @@ class HostFisheyeInput(C.Structure):
     ]
 
 
+class HostNewPointKf(C.Structure):
+    """``osh_host_newpoint_kf`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("n", C.c_int32), ("n_left", C.c_int32), ("xy", c_float_p), ("octave", c_int32_p), ("desc", c_uint8_p),
+                ("u_right", c_float_p), ("depth", c_float_p), ("has_mp", c_uint8_p), ("mp_pos", c_float_p), ("n_nodes", C.c_int32),
+                ("node_id", c_int32_p), ("node_off", c_int32_p), ("node_feat", c_int32_p), ("pose_qt", C.c_float * 7),
+                ("trl_qt", C.c_float * 7), ("camera_kb8", C.c_int32), ("camera", C.c_float * 8), ("has_camera2", C.c_int32),
+                ("camera2", C.c_float * 8), ("mbf", C.c_float), ("mb", C.c_float), ("n_levels", C.c_int32),
+                ("scale_factor", C.c_float), ("prev", C.c_int32)]
+
+
+class HostNewPointScene(C.Structure):
+    """``osh_host_newpoint_scene`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("n_kf", C.c_int32), ("kf", C.POINTER(HostNewPointKf)), ("n_neighbours", C.c_int32), ("neighbours", c_int32_p),
+                ("monocular", C.c_int32), ("inertial", C.c_int32), ("far_points", C.c_int32), ("th_far_points", C.c_float),
+                ("recently_lost", C.c_int32), ("inertial_ba2", C.c_int32), ("new_keyframe_waiting", C.c_int32)]
+
+
 _HOST_SIGNATURES = {
+    "osh_host_create_new_map_points": (C.c_int, [C.POINTER(HostNewPointScene), C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_float_p,
+                                                 c_int32_p, c_int32_p, c_float_p]),
     "osh_host_compute_fisheye_stereo_matches": (C.c_int, [C.POINTER(HostFisheyeInput), C.c_int32, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p]),
     "osh_host_kb8_triangulate_cpu": (C.c_int, [C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
+    "osh_host_newpoint_triangulate_cpu": (C.c_int, [C.c_int32, C.POINTER(NewPointSegment), C.POINTER(NewPointResult), c_double_p]),
     "osh_host_graph_create": (C.c_void_p, [C.c_int32, c_int64_p, c_float_p, c_float_p, c_float_p, C.c_int32, C.c_int32, c_int64_p,
                                            c_float_p, C.c_int32, c_int32_p, c_int32_p, c_float_p, c_int32_p, C.c_int64, C.c_int32]),
     "osh_host_graph_destroy": (None, [C.c_void_p]),

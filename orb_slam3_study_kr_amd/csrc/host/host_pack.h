@@ -571,4 +571,83 @@ inline bool PackStereoFishEyeMatches(const Frame& F, FisheyeStereoPack& pk) {
   if (F.mvLevelSigma2.empty()) { pk.unsupported = "mvLevelSigma2 is empty"; return false; }
   return true;
 }
+
+// ---- LocalMapping::CreateNewMapPoints: one (current keyframe, neighbour) segment of osh_orb_triangulate_new_points
+// The poses as the reference forms them (src/LocalMapping.cc:425-430,480-484,566-574): Rcw of the pose's 3x4 matrix, its transpose,
+// the translation and the camera centre.
+inline void FillNewPointPose(osh_newpoint_pose& p, const Sophus::SE3f& Tcw, const Eigen::Vector3f& Ow) {
+  const Eigen::Matrix3f R = Tcw.rotationMatrix();
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) { p.Rcw[3 * r + c] = R(r, c); p.Rwc[3 * c + r] = R(r, c); }
+    p.tcw[r] = Tcw.translation()(r); p.Ow[r] = Ow(r);
+  }
+}
+inline bool FillNewPointCamera(osh_newpoint_camera& c, GeometricCamera* cam) {
+  const bool kb8 = cam->GetType() == GeometricCamera::CAM_FISHEYE;
+  if (!kb8 && cam->GetType() != GeometricCamera::CAM_PINHOLE) return false;
+  c.type = kb8 ? OSH_NEWPOINT_KB8 : OSH_NEWPOINT_PINHOLE;
+  c.precision = kb8 ? static_cast<KannalaBrandt8*>(cam)->GetPrecision() : 0.f;
+  for (int k = 0; k < 8; ++k) c.params[k] = k < (kb8 ? 8 : 4) ? cam->getParameter(k) : 0.f;
+  return true;
+}
+struct NewPointPack {
+  std::vector<int32_t> idx1, idx2, octave1, octave2;
+  std::vector<float> pt1, pt2, u_right1, u_right2, depth1, depth2;
+  const char* unsupported = nullptr;
+  // the segment record; the arrays it points at live in this pack and in the two keyframes
+  void fill(osh_newpoint_segment& s, KeyFrame* pKF1, KeyFrame* pKF2, float ratioFactor, bool bInertial, bool bFarPoints, float thFarPoints) const {
+    KeyFrame* kfs[2] = {pKF1, pKF2};
+    osh_newpoint_keyframe* out[2] = {&s.kf1, &s.kf2};
+    for (int a = 0; a < 2; ++a) {
+      KeyFrame* k = kfs[a];
+      osh_newpoint_keyframe& o = *out[a];
+      FillNewPointPose(o.pose, k->GetPose(), k->GetCameraCenter());
+      FillNewPointCamera(o.camera, k->mpCamera);
+      o.has_camera2 = k->mpCamera2 ? 1 : 0;
+      if (k->mpCamera2) {
+        FillNewPointPose(o.right_pose, k->GetRightPose(), k->GetRightCameraCenter());
+        FillNewPointCamera(o.camera2, k->mpCamera2);
+      } else {
+        o.right_pose = o.pose; o.camera2 = o.camera;
+      }
+      o.fx = k->fx; o.fy = k->fy; o.cx = k->cx; o.cy = k->cy; o.invfx = k->invfx; o.invfy = k->invfy; o.mbf = k->mbf; o.mb = k->mb;
+      o.n_left = k->NLeft; o.n_keys = k->N;
+      o.n_levels = (int32_t)k->mvLevelSigma2.size();
+      o.level_sigma2 = k->mvLevelSigma2.data(); o.scale_factors = k->mvScaleFactors.data();
+    }
+    s.ratio_factor = ratioFactor; s.inertial = bInertial ? 1 : 0; s.far_points = bFarPoints ? 1 : 0; s.th_far_points = thFarPoints;
+    s.n_matches = (int32_t)idx1.size();
+    s.idx1 = idx1.data(); s.idx2 = idx2.data(); s.pt1 = pt1.data(); s.pt2 = pt2.data(); s.octave1 = octave1.data(); s.octave2 = octave2.data();
+    s.u_right1 = u_right1.data(); s.u_right2 = u_right2.data(); s.depth1 = depth1.data(); s.depth2 = depth2.data();
+  }
+};
+// What the loop over vMatchedIndices reads per match (:497-519): the keypoint :503-505 / :515-517 choose, mvuRight and mvDepth.
+// False (with pk.unsupported) for keyframes whose arrays do not fit together; the device entry checks the values.
+inline bool PackNewMapPoints(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<std::pair<size_t, size_t>>& vMatchedIndices, NewPointPack& pk) {
+  KeyFrame* kfs[2] = {pKF1, pKF2};
+  for (KeyFrame* k : kfs) {
+    if (!k->mpCamera) { pk.unsupported = "a keyframe has no camera"; return false; }
+    osh_newpoint_camera c;
+    if (!FillNewPointCamera(c, k->mpCamera) || (k->mpCamera2 && !FillNewPointCamera(c, k->mpCamera2))) { pk.unsupported = "a camera is neither a Pinhole nor a KannalaBrandt8"; return false; }
+    if (k->mvLevelSigma2.empty() || k->mvLevelSigma2.size() != k->mvScaleFactors.size()) { pk.unsupported = "mvLevelSigma2 and mvScaleFactors do not fit together"; return false; }
+    if ((int)k->mvuRight.size() < k->N || (int)k->mvDepth.size() < k->N) { pk.unsupported = "mvuRight or mvDepth is shorter than N"; return false; }
+    const size_t keys = k->NLeft == -1 ? k->mvKeysUn.size() : k->mvKeys.size() + k->mvKeysRight.size();
+    if ((int)keys < k->N || (k->NLeft != -1 && (int)k->mvKeys.size() != k->NLeft)) { pk.unsupported = "the keypoint arrays are shorter than N"; return false; }
+  }
+  const size_t n = vMatchedIndices.size();
+  pk.idx1.resize(n); pk.idx2.resize(n); pk.octave1.resize(n); pk.octave2.resize(n);
+  pk.pt1.resize(2 * n); pk.pt2.resize(2 * n); pk.u_right1.resize(n); pk.u_right2.resize(n); pk.depth1.resize(n); pk.depth2.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    const int idx1 = (int)vMatchedIndices[i].first, idx2 = (int)vMatchedIndices[i].second;
+    if (idx1 < 0 || idx1 >= pKF1->N || idx2 < 0 || idx2 >= pKF2->N) { pk.unsupported = "a matched index lies outside its keyframe"; return false; }
+    const cv::KeyPoint& kp1 = (pKF1->NLeft == -1) ? pKF1->mvKeysUn[idx1] : (idx1 < pKF1->NLeft) ? pKF1->mvKeys[idx1] : pKF1->mvKeysRight[idx1 - pKF1->NLeft];
+    const cv::KeyPoint& kp2 = (pKF2->NLeft == -1) ? pKF2->mvKeysUn[idx2] : (idx2 < pKF2->NLeft) ? pKF2->mvKeys[idx2] : pKF2->mvKeysRight[idx2 - pKF2->NLeft];
+    pk.idx1[i] = idx1; pk.idx2[i] = idx2;
+    pk.pt1[2 * i] = kp1.pt.x; pk.pt1[2 * i + 1] = kp1.pt.y; pk.pt2[2 * i] = kp2.pt.x; pk.pt2[2 * i + 1] = kp2.pt.y;
+    pk.octave1[i] = kp1.octave; pk.octave2[i] = kp2.octave;
+    pk.u_right1[i] = pKF1->mvuRight[idx1]; pk.u_right2[i] = pKF2->mvuRight[idx2];
+    pk.depth1[i] = pKF1->mvDepth[idx1]; pk.depth2[i] = pKF2->mvDepth[idx2];
+  }
+  return true;
+}
 }  // namespace ORB_SLAM3

@@ -88,8 +88,8 @@ OSH_KB8_HD void kb8_rotate(double (&a)[4][4], double (&v)[4][4]) {
   }
 }
 
-// :394-406: x3D = head(3) / w of the right singular vector of A's smallest singular value
-OSH_KB8_HD void kb8_null_vector(const float A[4][4], float x3D[3]) {
+// :394-406: h = the right singular vector of A's smallest singular value, homogeneous (newpoint_triangulate.h tests h[3] == 0)
+OSH_KB8_HD void kb8_null_vector_h(const float A[4][4], double h[4]) {
 #pragma clang fp contract(off)
   double a[4][4], v[4][4];
 #pragma unroll
@@ -100,7 +100,8 @@ OSH_KB8_HD void kb8_null_vector(const float A[4][4], float x3D[3]) {
     kb8_rotate<0, 1>(a, v); kb8_rotate<0, 2>(a, v); kb8_rotate<0, 3>(a, v);
     kb8_rotate<1, 2>(a, v); kb8_rotate<1, 3>(a, v); kb8_rotate<2, 3>(a, v);
   }
-  double best = 0, h[4] = {0, 0, 0, 0};
+  double best = 0;
+  h[0] = h[1] = h[2] = h[3] = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     double n = 0;
@@ -112,6 +113,13 @@ OSH_KB8_HD void kb8_null_vector(const float A[4][4], float x3D[3]) {
       for (int i = 0; i < 4; ++i) h[i] = v[i][j];
     }
   }
+}
+
+// x3D = head(3) / w of it, rounded to float32 once
+OSH_KB8_HD void kb8_null_vector(const float A[4][4], float x3D[3]) {
+#pragma clang fp contract(off)
+  double h[4];
+  kb8_null_vector_h(A, h);
   x3D[0] = (float)(h[0] / h[3]); x3D[1] = (float)(h[1] / h[3]); x3D[2] = (float)(h[2] / h[3]);
 }
 

@@ -5,6 +5,7 @@
 // osh_kb8_triangulate is not a client: it stages four flat arrays and no frames through a StagedCall of its own.
 // osh_orb_bow_transform (bow_device.hip) has frames of descriptors only: it uses scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_bow_db_query (bowdb_device.hip) has queries against a database: it uses PhaseClock, orb_state and copy_times.
+// osh_orb_triangulate_new_points (newpoint_device.hip) has segments of matched pairs: it uses scatter, PhaseClock, orb_state and copy_times.
 #pragma once
 #include "common.h"
 #include <chrono>

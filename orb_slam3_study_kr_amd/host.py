@@ -897,3 +897,92 @@ def bowdb_book_replay(ops, max_rows: int = 1 << 16) -> dict:
     names = ("live_rows", "rows", "entries", "capacity", "compactions", "reallocations", "row_capacity", "moved")
     return dict(op_handle=o["op_handle"][:len(ops)], handle=o["handle"][:rc], start=o["start"][:rc], len=o["len"][:rc], alive=o["alive"][:rc],
                 info=dict(zip(names, (int(x) for x in o["info"]))))
+
+
+def newpoint_triangulate_cpu(segments):
+    """csrc/newpoint_triangulate.h on the host in one thread (osh_host_newpoint_triangulate_cpu): per-segment output dicts, ms."""
+    from . import orb
+    return orb.newpoint_cpu(segments)
+
+
+def create_new_map_points(scene, coarse: bool = True, new_keyframe_waiting: bool = False, capacity: int = 4096) -> dict:
+    """LocalMapping::CreateNewMapPoints on the stand-in classes built from a synth_newpoints.Scene (osh_host_create_new_map_points).
+    Keyframe 0 is the current one, keyframe 1 + k neighbour k; the first two neighbours are covisibles, the third is reached
+    through mPrevKF (an inertial scene) or is a covisible too.  Every matched feature pair shares a descriptor and a vocabulary node
+    of its own.  Returns the created points in creation order (neighbour as a segment index, idx1, idx2, x3d, n_obs, flags) and
+    poses [n_kf, 2, 24]: Rcw tcw Rwc Ow of every keyframe's left and right pose as handed to the device."""
+    from . import synth_fisheye as sf
+    from . import synth_newpoints as sn
+    lib = capi.load_host_library()
+    segs = scene.segments
+    k1 = segs[0].kf1
+    N = k1.n_keys
+    rng = np.random.default_rng(12345)
+    desc1 = rng.integers(0, 256, (N, 32), dtype=np.uint8)
+    keep = []
+
+    def keyframe(c, kf, idx, pt, octave, ur, depth, node_of, desc, has_mp, mp_pos, prev):
+        n = kf.n_keys
+        a = dict(xy=np.zeros((n, 2), np.float32), octave=np.zeros(n, np.int32), ur=np.full(n, -1, np.float32), depth=np.full(n, -1, np.float32),
+                 desc=np.ascontiguousarray(desc), has_mp=np.ascontiguousarray(has_mp, np.uint8), mp_pos=np.ascontiguousarray(mp_pos, np.float32))
+        a["xy"][idx], a["octave"][idx], a["ur"][idx], a["depth"][idx] = pt, octave, ur, depth
+        nodes = sorted(set(int(v) for v in node_of.values()))
+        feats = {v: [] for v in nodes}
+        for f in sorted(node_of):
+            feats[int(node_of[f])].append(f)
+        a["node_id"] = np.asarray(nodes, np.int32)
+        a["node_off"] = np.concatenate([[0], np.cumsum([len(feats[v]) for v in nodes])]).astype(np.int32)
+        a["node_feat"] = np.asarray([f for v in nodes for f in feats[v]], np.int32)
+        keep.append(a)
+        c.n, c.n_left = n, int(kf.n_left)
+        for field, key, typ in (("xy", "xy", capi.c_float_p), ("octave", "octave", capi.c_int32_p), ("desc", "desc", capi.c_uint8_p),
+                                ("u_right", "ur", capi.c_float_p), ("depth", "depth", capi.c_float_p), ("has_mp", "has_mp", capi.c_uint8_p),
+                                ("mp_pos", "mp_pos", capi.c_float_p), ("node_id", "node_id", capi.c_int32_p),
+                                ("node_off", "node_off", capi.c_int32_p), ("node_feat", "node_feat", capi.c_int32_p)):
+            setattr(c, field, capi.ptr(a[key], typ))
+        c.n_nodes = len(nodes)
+        R = kf.pose.Rcw.astype(np.float64)
+        c.pose_qt[:] = [float(np.float32(v)) for v in np.concatenate([synth._quat_from_R(R), kf.pose.tcw.astype(np.float64)])]
+        c.trl_qt[:] = [float(np.float32(v)) for v in np.concatenate([synth._quat_from_R(sf.rotation(sn.RIG_ROTVEC)), np.asarray(sn.RIG_T)])]
+        c.camera_kb8 = int(kf.camera.type == sn.KB8)
+        c.camera[:] = [float(v) for v in kf.camera.params]
+        c.has_camera2 = int(kf.camera2 is not None)
+        if kf.camera2 is not None:
+            c.camera2[:] = [float(v) for v in kf.camera2.params]
+        c.mbf, c.mb, c.n_levels, c.scale_factor, c.prev = float(kf.mbf), float(kf.mb), len(kf.scale_factors), float(np.float32(sf.SCALE)), prev
+
+    n_kf = 1 + len(segs)
+    ckf = (capi.HostNewPointKf * n_kf)()
+    # the current keyframe: its features over all segments (a shared feature carries the same keypoint in each)
+    idx1 = np.concatenate([s.idx1 for s in segs])
+    cat = lambda f: np.concatenate([getattr(s, f) for s in segs])
+    inertial_walk = bool(scene.inertial) and len(segs) == 3
+    keyframe(ckf[0], k1, idx1, cat("pt1"), cat("octave1"), cat("u_right1"), cat("depth1"), {int(i): int(i) for i in idx1}, desc1,
+             np.zeros(N, np.uint8), np.zeros((N, 3), np.float32), 3 if inertial_walk else -1)
+    for k, s in enumerate(segs):
+        d = rng.integers(0, 256, (N, 32), dtype=np.uint8)
+        d[s.idx2] = desc1[s.idx1]
+        has = np.zeros(N, np.uint8)
+        pos = np.zeros((N, 3), np.float32)
+        feats, p = scene.map_points[k]
+        has[feats], pos[feats] = 1, p
+        keyframe(ckf[1 + k], s.kf2, s.idx2, s.pt2, s.octave2, s.u_right2, s.depth2, {int(b): int(a) for a, b in zip(s.idx1, s.idx2)}, d, has, pos,
+                 1 if (inertial_walk and k == 2) else -1)
+    sc = capi.HostNewPointScene()
+    nb = np.asarray([1, 2] if inertial_walk else list(range(1, n_kf)), np.int32)
+    sc.n_kf, sc.kf, sc.n_neighbours, sc.neighbours = n_kf, ckf, len(nb), capi.ptr(nb, capi.c_int32_p)
+    sc.monocular, sc.inertial, sc.far_points, sc.th_far_points = int(scene.monocular), int(scene.inertial), int(scene.far_points), float(scene.th_far_points)
+    sc.recently_lost = sc.inertial_ba2 = int(coarse)
+    sc.new_keyframe_waiting = int(new_keyframe_waiting)
+    o = dict(neighbour=np.zeros(capacity, np.int32), idx1=np.zeros(capacity, np.int32), idx2=np.zeros(capacity, np.int32),
+             x3d=np.zeros((capacity, 3), np.float32), n_obs=np.zeros(capacity, np.int32), flags=np.zeros(capacity, np.int32))
+    poses = np.zeros((n_kf, 2, 24), np.float32)
+    n = lib.osh_host_create_new_map_points(C.byref(sc), capacity, capi.ptr(o["neighbour"], capi.c_int32_p), capi.ptr(o["idx1"], capi.c_int32_p),
+                                           capi.ptr(o["idx2"], capi.c_int32_p), capi.ptr(o["x3d"], capi.c_float_p),
+                                           capi.ptr(o["n_obs"], capi.c_int32_p), capi.ptr(o["flags"], capi.c_int32_p), capi.ptr(poses, capi.c_float_p))
+    if n < 0 or n > capacity:
+        raise RuntimeError(f"osh_host_create_new_map_points returned {n}")
+    out = {k: v[:n] for k, v in o.items()}
+    out["neighbour"] = out["neighbour"] - 1          # keyframe index -> segment index
+    out["poses"] = poses
+    return out

@@ -155,6 +155,7 @@ class OrbMatcher:
 
     stereo_times = functools.partialmethod(_times, "osh_orb_stereo_get_times")                   # of the last stereo_match
     fisheye_stereo_times = functools.partialmethod(_times, "osh_orb_fisheye_stereo_get_times")   # of the last fisheye_stereo_match
+    newpoint_times = functools.partialmethod(_times, "osh_orb_newpoint_get_times")               # of the last triangulate_new_points
     bow_times = functools.partialmethod(_times, "osh_orb_bow_get_times")                         # of the last bow_transform
     bow_db_times = functools.partialmethod(_times, "osh_orb_bow_db_get_times")                   # of the last bow_db_query
 
@@ -181,6 +182,14 @@ class OrbMatcher:
         `stages` also best_right, best_dist, second_dist, cos_parallax, stage."""
         cf, cr, _keep, outs = fisheye_stereo_args(frames, stages)
         capi.check(self.lib.osh_orb_fisheye_stereo_match(self.ctx, len(frames), cf, cr), "osh_orb_fisheye_stereo_match", self.lib)
+        return outs
+
+    def triangulate_new_points(self, segments) -> list:
+        """The per-match body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:503-720) for a batch of
+        synth_newpoints.Segment in one osh_orb_triangulate_new_points call: per segment a dict with stage, source,
+        cos_parallax [n] and x3d [n, 3]."""
+        cs, cr, _keep, outs = newpoint_args(segments)
+        capi.check(self.lib.osh_orb_triangulate_new_points(self.ctx, len(segments), cs, cr), "osh_orb_triangulate_new_points", self.lib)
         return outs
 
     def kb8_triangulate(self, rig: "capi.Kb8Rig", xy1, xy2, sigma1, sigma2) -> dict:
@@ -447,6 +456,72 @@ def fill_fisheye_frame(f, fr, a=None):
     f.Rlr[:] = [float(x) for x in np.asarray(fr.Rlr, np.float32).reshape(9)]
     f.tlr[:] = [float(x) for x in np.asarray(fr.tlr, np.float32)]
     return a
+
+
+def _fill_newpoint_pose(p, pose):
+    p.Rcw[:] = [float(x) for x in np.asarray(pose.Rcw, np.float32).reshape(9)]
+    p.tcw[:] = [float(x) for x in np.asarray(pose.tcw, np.float32)]
+    p.Rwc[:] = [float(x) for x in np.asarray(pose.Rwc, np.float32).reshape(9)]
+    p.Ow[:] = [float(x) for x in np.asarray(pose.Ow, np.float32)]
+
+
+def _fill_newpoint_camera(c, cam):
+    c.type, c.precision = int(cam.type), float(cam.precision)
+    c.params[:] = [float(x) for x in np.asarray(cam.params, np.float32)]
+
+
+def fill_newpoint_keyframe(k, kf):
+    """capi.NewPointKeyFrame from a synth_newpoints.KeyFrame; returns the arrays its pointers refer to."""
+    _fill_newpoint_pose(k.pose, kf.pose)
+    _fill_newpoint_camera(k.camera, kf.camera)
+    k.has_camera2 = int(kf.camera2 is not None)
+    if kf.camera2 is not None:
+        _fill_newpoint_pose(k.right_pose, kf.right_pose)
+        _fill_newpoint_camera(k.camera2, kf.camera2)
+    for name in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mbf", "mb"):
+        setattr(k, name, float(getattr(kf, name)))
+    keep = (np.ascontiguousarray(kf.level_sigma2, np.float32), np.ascontiguousarray(kf.scale_factors, np.float32))
+    k.n_left, k.n_keys, k.n_levels = int(kf.n_left), int(kf.n_keys), keep[0].shape[0]
+    k.level_sigma2, k.scale_factors = capi.ptr(keep[0], capi.c_float_p), capi.ptr(keep[1], capi.c_float_p)
+    return keep
+
+
+_NEWPOINT_ARRAYS = (("idx1", np.int32), ("idx2", np.int32), ("pt1", np.float32), ("pt2", np.float32), ("octave1", np.int32),
+                    ("octave2", np.int32), ("u_right1", np.float32), ("u_right2", np.float32), ("depth1", np.float32), ("depth2", np.float32))
+
+
+def newpoint_args(segments):
+    """The osh_newpoint_segment / osh_newpoint_result arrays of OrbMatcher.triangulate_new_points for repeated calls: (segments,
+    results, the arrays that keep their pointers alive, the per-segment dicts of output arrays)."""
+    n_seg = len(segments)
+    cs = (capi.NewPointSegment * max(n_seg, 1))()
+    cr = (capi.NewPointResult * max(n_seg, 1))()
+    keep, outs = [], []
+    for k, sg in enumerate(segments):
+        c = cs[k]
+        a = {"kf1": fill_newpoint_keyframe(c.kf1, sg.kf1), "kf2": fill_newpoint_keyframe(c.kf2, sg.kf2)}
+        c.ratio_factor, c.inertial, c.far_points, c.th_far_points = float(sg.ratio_factor), int(sg.inertial), int(sg.far_points), float(sg.th_far_points)
+        n = c.n_matches = int(np.asarray(sg.idx1).shape[0])
+        for name, dt in _NEWPOINT_ARRAYS:
+            a[name] = np.ascontiguousarray(getattr(sg, name), dt)
+            setattr(c, name, capi.ptr(a[name], _POINTER[np.dtype(dt)]))
+        o = dict(stage=np.zeros(n, np.uint8), source=np.zeros(n, np.uint8), cos_parallax=np.zeros(n, np.float32), x3d=np.zeros((n, 3), np.float32))
+        _wire_outputs(cr[k], o)
+        keep.append(a)
+        outs.append(o)
+    return cs, cr, keep, outs
+
+
+def newpoint_cpu(segments, host_lib=None):
+    """csrc/newpoint_triangulate.h on the host in one thread (osh_host_newpoint_triangulate_cpu of the test library): the per-segment
+    output dicts of triangulate_new_points and the wall time of the loops in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    cs, cr, _keep, outs = newpoint_args(segments)
+    ms = C.c_double(0)
+    rc = host_lib.osh_host_newpoint_triangulate_cpu(len(segments), cs, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_newpoint_triangulate_cpu -> {rc}")
+    return outs, float(ms.value)
 
 
 def kb8_rig(cam1, cam2, precision1, precision2, R12, t12) -> "capi.Kb8Rig":
