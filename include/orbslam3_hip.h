@@ -942,6 +942,89 @@ int osh_orb_triangulate_new_points(osh_orb_ctx* ctx, int32_t n_segments, const o
  * ms[1] upload, ms[2] kernel, ms[3] download + write-back. */
 int osh_orb_newpoint_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- FAST corners and orientation (ORBextractor) */
+/*
+ * The integer part of ORBextractor::ComputeKeyPointsOctTree (src/ORBextractor.cc:781-896) for n_frames pyramids in one call: what
+ * the loops over the cells of every level hand to DistributeOctTree (osh_orb_fast_detect), and IC_Angle (:76-103) for keypoints of
+ * those levels (osh_orb_ic_angle).  The pyramid, DistributeOctTree, the blur and the descriptors stay with the caller.
+ *
+ * Cells (:785-822): minBorder = 16, maxBorderX = cols - 16, width = maxBorderX - 16, nCols = (int)(width / 35.f),
+ * wCell = (int)ceil(width / nCols), cell (i, j) spans columns [16 + j * wCell, min(16 + j * wCell + wCell + 6, maxBorderX)), likewise
+ * for rows; cells with iniY >= maxBorderY - 3 or iniX >= maxBorderX - 6 do not exist.  A level with nCols == 0 or nRows == 0 has no
+ * cells (the reference divides by zero there): a defined skip.  The cells of a frame are numbered level by level in (i, j) order,
+ * the cells that do not exist left out.
+ *
+ * Corners: cv::FAST(sub-image, threshold, true) from its definition.  With p_k the 16 circle pixels at radius 3 and v the centre,
+ * score = max(max over the 16 arcs of 9 contiguous p_k of min(p_k - v), the same of (v - p_k)) - 1, defined for the rows and columns
+ * [3, size - 3) of the cell's sub-image and 0 elsewhere; a pixel is kept at threshold t when score >= t and score is strictly
+ * greater than the scores of its eight neighbours in the same sub-image.  A cell yields its kept corners at ini_th, or, when there
+ * are none, those at min_th (:826-869), in row-major order, as pt = (x + j * wCell, y + i * hCell) relative to minBorder with
+ * response = score.  Cells overlap by 6 pixels, which are exactly the two 3-pixel rims without scores: the areas in which
+ * neighbouring cells have scores tile the level, so no pixel is listed twice.  What a cell edge changes is the neighbourhood: two
+ * adjacent pixels on either side of it are both listed when each is the maximum of its own cell.  The order of the result is a
+ * function of the input alone.
+ *
+ * osh_orb_fast_detect reads the levels in place (rows `stride` bytes apart) and keeps its packed copy on the context until the next
+ * osh_orb_fast_detect of that context; pyramid_token names the copy of one frame for osh_orb_ic_angle.  When n_out > capacity (or
+ * used_min_th is given and n_cells > cell_capacity) the counts are written, the arrays of that frame are not, and the call still returns OSH_OK: size the
+ * arrays and call again.
+ *
+ * IC_Angle: at (cvRound(x), cvRound(y)), halves to even, the moments m_10 and m_01 over the 31-pixel disc with the row half-widths
+ * 15 15 15 15 14 14 14 13 13 12 11 10 9 8 6 3, and angle = fastAtan2((float)m_01, (float)m_10) in OpenCV's documented scalar form:
+ * c = min(|x|, |y|) / (max(|x|, |y|) + (float)DBL_EPSILON), a = (((p7 c^2 + p5) c^2 + p3) c^2 + p1) c, 90 - a when |x| < |y|,
+ * 180 - a when x < 0, 360 - a when y < 0, every step one float32 operation, no fused multiply-add.
+ *
+ * Refused with OSH_ERR_INVALID before any device work and without a context: n_levels outside [1, OSH_STEREO_MAX_LEVELS], a level
+ * that is NULL, empty or has stride < cols, a threshold outside [1, 255], min_th > ini_th, a negative count or capacity, a NULL
+ * array whose count is not 0, a keypoint that is not finite, whose level is outside the pyramid or whose 31-pixel disc would leave
+ * its level; with OSH_ERR_UNSUPPORTED a level above OSH_FAST_MAX_SIDE pixels in either direction.  A token that does not name a
+ * frame of the context's last osh_orb_fast_detect is refused too.  A refused call leaves the context and its resident pyramid as
+ * they were.
+ */
+#define OSH_FAST_MAX_SIDE 32768
+/* used_min_th[c]: how cell c was decided */
+#define OSH_FAST_AT_INI 0   /* corners at ini_th                                  */
+#define OSH_FAST_AT_MIN 1   /* none at ini_th, corners at min_th                  */
+#define OSH_FAST_EMPTY  2   /* none at either threshold                           */
+typedef struct osh_fast_frame {
+  int32_t n_levels;
+  const osh_stereo_image* pyramid;   /* [n_levels] mvImagePyramid                                                          */
+  int32_t ini_th, min_th;            /* iniThFAST, minThFAST                                                               */
+} osh_fast_frame;
+typedef struct osh_fast_result {
+  int32_t capacity;          /* in:  entries xy / response / level / cell can take                                          */
+  int32_t cell_capacity;     /* in:  entries used_min_th can take                                                           */
+  int32_t n_out;             /* out: corners of the frame, all levels                                                       */
+  int32_t n_cells;           /* out: cells of the frame                                                                     */
+  uint64_t pyramid_token;    /* out: names this frame's resident pyramid for osh_orb_ic_angle                               */
+  int32_t* level_count;      /* [n_levels] out: corners per level (vToDistributeKeys.size())                                */
+  float* xy;                 /* [capacity*2] pt relative to minBorder, level after level, cells in (i, j) order             */
+  float* response;           /* [capacity]                                                                                  */
+  int32_t* level;            /* [capacity]   may be NULL                                                                    */
+  int32_t* cell;             /* [capacity]   the cell that emitted the corner; may be NULL                                  */
+  uint8_t* used_min_th;      /* [cell_capacity] OSH_FAST_AT_INI / AT_MIN / EMPTY; may be NULL                               */
+} osh_fast_result;
+int osh_orb_fast_detect(osh_orb_ctx* ctx, int32_t n_frames, const osh_fast_frame* frames, osh_fast_result* results);
+typedef struct osh_ic_angle_frame {
+  int32_t n_levels;                  /* with a pyramid: its levels                                                          */
+  const osh_stereo_image* pyramid;   /* [n_levels], or NULL: the resident pyramid pyramid_token names                       */
+  uint64_t pyramid_token;
+  int32_t n;                         /* keypoints                                                                           */
+  const float* xy;                   /* [n*2] in the pixels of their level (minBorder added)                                */
+  const int32_t* level;              /* [n]                                                                                 */
+} osh_ic_angle_frame;
+typedef struct osh_ic_angle_result {   /* each may be NULL */
+  float* angle;              /* [n] degrees in [0, 360)                                                                     */
+  int32_t* m10;              /* [n]                                                                                         */
+  int32_t* m01;              /* [n]                                                                                         */
+} osh_ic_angle_result;
+int osh_orb_ic_angle(osh_orb_ctx* ctx, int32_t n_frames, const osh_ic_angle_frame* frames, const osh_ic_angle_result* results);
+/* Host-clock phases (ms) of the last osh_orb_fast_detect / osh_orb_ic_angle under osh_orb_set_profiling: ms[0] validation + staging
+ * (pyramid rows into pinned memory), ms[1] upload, ms[2] kernels (for the detector with the download of the counts between the
+ * scan and the emit), ms[3] download + write-back. */
+int osh_orb_fast_get_times(osh_orb_ctx* ctx, double ms[4]);
+int osh_orb_ic_angle_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 /* ------------------------------------------------- bag-of-words transform */
 /*
  * TemplatedVocabulary::transform (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1259) for ORB descriptors: what

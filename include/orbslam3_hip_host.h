@@ -462,6 +462,52 @@ typedef struct osh_host_newpoint_scene {
 int osh_host_create_new_map_points(const osh_host_newpoint_scene* scene, int32_t capacity, int32_t* neighbour, int32_t* idx1, int32_t* idx2,
                                    float* x3d, int32_t* n_obs, int32_t* flags, float* poses);
 
+/* ---- ORBextractor::ComputeKeyPointsOctTree (include/ORBextractor.h, csrc/host/ORBextractor.cc, csrc/hosttest/orbextractor.cc) ---- */
+struct osh_fast_frame;
+struct osh_fast_result;
+struct osh_ic_angle_frame;
+struct osh_ic_angle_result;
+/* csrc/orb_fast.h (the statements k_fast_cells, k_fast_emit and k_ic_angle run) compiled for the host, on one thread: arguments as
+ * osh_orb_fast_detect / osh_orb_ic_angle without a context and without their validation (the frames must be valid and bring their
+ * pyramid; pyramid_token comes back 0).  *ms (may be NULL) = wall time of the loops.  -1: bad arguments. */
+int osh_host_orb_fast_cpu(int32_t n_frames, const struct osh_fast_frame* frames, struct osh_fast_result* results, double* ms);
+int osh_host_orb_ic_angle_cpu(int32_t n_frames, const struct osh_ic_angle_frame* frames, const struct osh_ic_angle_result* results, double* ms);
+/* The cell geometry of csrc/orb_fast.h for a level of rows x cols pixels: geom[0..5] = nCols, nRows, wCell, hCell, maxBorderX,
+ * maxBorderY (nCols = nRows = 0: no cells), and the rectangle x0, y0, w, h of each existing cell in (i, j) order in rects (may be
+ * NULL, else room for nCols * nRows * 4).  Returns the number of existing cells.  -1: bad arguments. */
+int osh_host_orb_fast_level_cells(int32_t rows, int32_t cols, int32_t geom[6], int32_t* rects);
+
+/* An ORBextractor of the stand-in class, ORBextractor(nfeatures, scale_factor, nlevels, ini_th, min_th), with the n_images levels
+ * (nlevels of them, or fewer to see the refusal) stored as views into images with `border` pixels around them. */
+typedef struct osh_host_orbextractor_input {
+  int32_t nfeatures;
+  float scale_factor;
+  int32_t nlevels, ini_th, min_th;
+  int32_t n_images;
+  const int32_t* rows;        /* [n_images] */
+  const int32_t* cols;        /* [n_images] */
+  const uint8_t* pixels;      /* the levels one after another, rows packed */
+  int32_t border;
+} osh_host_orbextractor_input;
+typedef struct osh_host_orbextractor_output {
+  int32_t capacity, cand_capacity;
+  int32_t* level_count;       /* [nlevels] allKeypoints[level].size()                                                 */
+  float* xy;                  /* [capacity*2] allKeypoints level after level: pt                                      */
+  float* response;            /* [capacity] */
+  float* angle;               /* [capacity] */
+  float* size;                /* [capacity] */
+  int32_t* octave;            /* [capacity] */
+  int32_t* cand_level_count;  /* [nlevels] vToDistributeKeys.size() of the level's DistributeOctTree call (0: no call) */
+  float* cand_xy;             /* [cand_capacity*2] the vToDistributeKeys of the calls, level after level               */
+  float* cand_response;       /* [cand_capacity] */
+  int32_t* cand_args;         /* [nlevels*6] minX maxX minY maxY nFeatures level of the level's call; may be NULL      */
+  int32_t* features_per_level;/* [nlevels] mnFeaturesPerLevel; may be NULL                                            */
+  float* scale_factors;       /* [nlevels] mvScaleFactor; may be NULL                                                 */
+} osh_host_orbextractor_output;
+/* ORBextractor::ComputeKeyPointsOctTree on that extractor.  Returns the number of keypoints of all levels (the arrays take the
+ * first `capacity` keypoints and `cand_capacity` candidates).  -1: bad arguments, -2: the member left something inconsistent. */
+int osh_host_orbextractor_compute_keypoints(const osh_host_orbextractor_input* in, const osh_host_orbextractor_output* out);
+
 /* ---- ORBVocabulary / ComputeBoW (include/ORBVocabulary.h, csrc/host/ORBVocabulary.cc, csrc/hosttest/bow.cc) ---- */
 struct osh_bow_tree;
 struct osh_bow_result;

@@ -374,6 +374,37 @@ OSH_NEWPOINT_PINHOLE, OSH_NEWPOINT_KB8 = 0, 1
 OSH_NEWPOINT_TRIANGULATED, OSH_NEWPOINT_STEREO_1, OSH_NEWPOINT_STEREO_2, OSH_NEWPOINT_NO_SOURCE = 0, 1, 2, 255
 
 
+class FastFrame(C.Structure):
+    """``osh_fast_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n_levels", C.c_int32), ("pyramid", C.POINTER(StereoImage)), ("ini_th", C.c_int32), ("min_th", C.c_int32)]
+
+
+class FastResult(C.Structure):
+    """``osh_fast_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("capacity", C.c_int32), ("cell_capacity", C.c_int32), ("n_out", C.c_int32), ("n_cells", C.c_int32),
+                ("pyramid_token", C.c_uint64), ("level_count", c_int32_p), ("xy", c_float_p), ("response", c_float_p),
+                ("level", c_int32_p), ("cell", c_int32_p), ("used_min_th", c_uint8_p)]
+
+
+class IcAngleFrame(C.Structure):
+    """``osh_ic_angle_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n_levels", C.c_int32), ("pyramid", C.POINTER(StereoImage)), ("pyramid_token", C.c_uint64), ("n", C.c_int32),
+                ("xy", c_float_p), ("level", c_int32_p)]
+
+
+class IcAngleResult(C.Structure):
+    """``osh_ic_angle_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("angle", c_float_p), ("m10", c_int32_p), ("m01", c_int32_p)]
+
+
+OSH_FAST_MAX_SIDE = 32768
+OSH_FAST_AT_INI, OSH_FAST_AT_MIN, OSH_FAST_EMPTY = 0, 1, 2
+
+
 class BowTree(C.Structure):
     """``osh_bow_tree`` (include/orbslam3_hip.h)."""
 
@@ -478,6 +509,10 @@ _SIGNATURES = {
     "osh_kb8_triangulate": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
     "osh_orb_triangulate_new_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(NewPointSegment), C.POINTER(NewPointResult)]),
     "osh_orb_newpoint_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_fast_detect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult)]),
+    "osh_orb_ic_angle": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult)]),
+    "osh_orb_fast_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_ic_angle_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_bow_tree_check": (C.c_int, [C.POINTER(BowTree)]),
     "osh_bow_vocab_create": (C.c_int, [C.c_int, C.POINTER(BowTree), C.POINTER(C.c_void_p)]),
     "osh_bow_vocab_destroy": (None, [C.c_void_p]),
@@ -551,7 +586,28 @@ class HostNewPointScene(C.Structure):
                 ("recently_lost", C.c_int32), ("inertial_ba2", C.c_int32), ("new_keyframe_waiting", C.c_int32)]
 
 
+class HostOrbExtractorInput(C.Structure):
+    """``osh_host_orbextractor_input`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32), ("ini_th", C.c_int32),
+                ("min_th", C.c_int32), ("n_images", C.c_int32), ("rows", c_int32_p), ("cols", c_int32_p), ("pixels", c_uint8_p),
+                ("border", C.c_int32)]
+
+
+class HostOrbExtractorOutput(C.Structure):
+    """``osh_host_orbextractor_output`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("capacity", C.c_int32), ("cand_capacity", C.c_int32), ("level_count", c_int32_p), ("xy", c_float_p),
+                ("response", c_float_p), ("angle", c_float_p), ("size", c_float_p), ("octave", c_int32_p),
+                ("cand_level_count", c_int32_p), ("cand_xy", c_float_p), ("cand_response", c_float_p), ("cand_args", c_int32_p),
+                ("features_per_level", c_int32_p), ("scale_factors", c_float_p)]
+
+
 _HOST_SIGNATURES = {
+    "osh_host_orb_fast_cpu": (C.c_int, [C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult), c_double_p]),
+    "osh_host_orb_ic_angle_cpu": (C.c_int, [C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult), c_double_p]),
+    "osh_host_orb_fast_level_cells": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
+    "osh_host_orbextractor_compute_keypoints": (C.c_int, [C.POINTER(HostOrbExtractorInput), C.POINTER(HostOrbExtractorOutput)]),
     "osh_host_create_new_map_points": (C.c_int, [C.POINTER(HostNewPointScene), C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_float_p,
                                                  c_int32_p, c_int32_p, c_float_p]),
     "osh_host_compute_fisheye_stereo_matches": (C.c_int, [C.POINTER(HostFisheyeInput), C.c_int32, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p]),

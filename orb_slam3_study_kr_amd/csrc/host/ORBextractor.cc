@@ -1,0 +1,103 @@
+// ORBextractor.cc -- ORBextractor::ComputeKeyPointsOctTree (reference src/ORBextractor.cc:781-896) on MI355X (host side).
+//
+// The loops over the cells of every level (:787-872: cv::FAST at iniThFAST, again at minThFAST for a cell without corners) are ONE
+// osh_orb_fast_detect call for the whole pyramid (csrc/orb_fast_device.hip); DistributeOctTree stays the reference's and runs per
+// level on what the device returned, followed by the write-back of :880-890; computeOrientation of all levels (:893-895) is ONE
+// osh_orb_ic_angle call on the pyramid the detector left on the device.  In the integrator's tree the constructor, ComputePyramid,
+// DistributeOctTree and operator() stay the reference's; only this body replaces :781-896.
+//
+// Deviations from the reference, all intended:
+//   * a level with fewer than 35 columns or rows between its borders has no cells (the reference divides by zero there);
+//   * fastAtan2 is OpenCV's documented scalar form in unfused float32 operations (include/orbslam3_hip.h);
+//   * on a device error, or a pyramid the call refuses, a message goes to stderr and allKeypoints is empty at every level.
+#include "ORBextractor.h"
+
+#include <cstdio>
+#include <vector>
+
+#include "orbslam3_hip.h"
+
+namespace ORB_SLAM3 {
+
+osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
+
+void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint> >& allKeypoints) {
+  allKeypoints.clear();
+  allKeypoints.resize(nlevels);
+  if (nlevels <= 0) return;
+  if ((int)mvImagePyramid.size() < nlevels) {
+    std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: the pyramid has %d of %d levels\n", (int)mvImagePyramid.size(), nlevels);
+    return;
+  }
+  osh_orb_ctx* ctx = HostMatcherContext();
+  if (!ctx) {
+    std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: %s\n", osh_last_error());
+    return;
+  }
+
+  // every cell of every level (:787-872) in one call; the levels are read in place, views into the bordered images included
+  std::vector<osh_stereo_image> pyramid(nlevels);
+  for (int level = 0; level < nlevels; ++level) {
+    const cv::Mat& im = mvImagePyramid[level];
+    pyramid[level].data = im.empty() ? nullptr : im.ptr<uint8_t>(0);
+    pyramid[level].rows = im.rows; pyramid[level].cols = im.cols; pyramid[level].stride = (int64_t)(size_t)im.step;
+  }
+  const osh_fast_frame frame{nlevels, pyramid.data(), iniThFAST, minThFAST};
+  std::vector<int32_t> levelCount(nlevels);
+  std::vector<float> xy, response;
+  osh_fast_result res{};
+  res.level_count = levelCount.data();
+  size_t capacity = (size_t)(nfeatures > 0 ? nfeatures : 0) * 10 * (size_t)nlevels;   // vToDistributeKeys.reserve(nfeatures*10) per level
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    xy.resize(capacity * 2); response.resize(capacity);
+    res.capacity = (int32_t)capacity; res.xy = xy.data(); res.response = response.data();
+    if (osh_orb_fast_detect(ctx, 1, &frame, &res) != OSH_OK) {
+      std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: %s\n", osh_last_error());
+      return;
+    }
+    if ((size_t)res.n_out <= capacity) break;
+    capacity = (size_t)res.n_out;   // the counts came back without the arrays: once more with room for them
+  }
+
+  // per level: the candidates of the device as the octree's input, the reference's DistributeOctTree, and what :880-890 add to its
+  // selection (the border, the level, the patch diameter 31 at the level's scale, cut to int)
+  constexpr int kBorder = 16;   // EDGE_THRESHOLD - 3, the margin of the detect area on every side
+  size_t offset = 0, total = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    std::vector<cv::KeyPoint> candidates((size_t)levelCount[l]);
+    for (cv::KeyPoint& c : candidates) {   // the fields cv::FAST fills: size 7, no angle, the score as response
+      c.pt.x = xy[2 * offset]; c.pt.y = xy[2 * offset + 1]; c.response = response[offset];
+      c.size = 7.f; c.angle = -1.f; c.octave = 0; c.class_id = -1;
+      ++offset;
+    }
+    allKeypoints[l] = DistributeOctTree(candidates, kBorder, mvImagePyramid[l].cols - kBorder, kBorder, mvImagePyramid[l].rows - kBorder,
+                                        mnFeaturesPerLevel[l], l);
+    const float diameter = (float)(int)(31 * mvScaleFactor[l]);
+    for (cv::KeyPoint& kp : allKeypoints[l]) {
+      kp.pt.x += kBorder; kp.pt.y += kBorder;
+      kp.octave = l;
+      kp.size = diameter;
+    }
+    total += allKeypoints[l].size();
+  }
+
+  // the orientation of every kept keypoint (:893-895): all levels in one call, on the pyramid the detector left on the device
+  if (total == 0) return;
+  std::vector<float> pts(total * 2), angle(total);
+  std::vector<int32_t> lvl(total);
+  size_t n = 0;
+  for (int l = 0; l < nlevels; ++l)
+    for (const cv::KeyPoint& kp : allKeypoints[l]) { pts[2 * n] = kp.pt.x; pts[2 * n + 1] = kp.pt.y; lvl[n] = l; ++n; }
+  const osh_ic_angle_frame icf{0, nullptr, res.pyramid_token, (int32_t)total, pts.data(), lvl.data()};
+  const osh_ic_angle_result icr{angle.data(), nullptr, nullptr};
+  if (osh_orb_ic_angle(ctx, 1, &icf, &icr) != OSH_OK) {
+    std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: %s\n", osh_last_error());
+    for (std::vector<cv::KeyPoint>& kps : allKeypoints) kps.clear();
+    return;
+  }
+  n = 0;
+  for (std::vector<cv::KeyPoint>& kps : allKeypoints)
+    for (cv::KeyPoint& kp : kps) kp.angle = angle[n++];
+}
+
+}  // namespace ORB_SLAM3

@@ -1,0 +1,224 @@
+// orbextractor.cc -- what the stand-in ORB_SLAM3::ORBextractor (include/ORBextractor.h) needs around
+// ORBextractor::ComputeKeyPointsOctTree (csrc/host/ORBextractor.cc), and the C wrappers that drive it
+// (include/orbslam3_hip_host.h): the constructor (scale tables and mnFeaturesPerLevel as reference src/ORBextractor.cc:409-447), a
+// DistributeOctTree test double, osh_host_orbextractor_compute_keypoints, and csrc/orb_fast.h on the host in one thread
+// (osh_host_orb_fast_cpu, osh_host_orb_ic_angle_cpu: the CPU baseline of profiles/fast_timing.py; osh_host_orb_fast_level_cells).  Test library only.
+//
+// The DistributeOctTree here is written from the behaviour, not taken from the reference: a quadtree over the level's detect area
+// that splits the nodes holding more than one keypoint until there are nFeatures nodes (or nothing left to split), the fullest
+// nodes first once a whole round would overshoot, and keeps the strongest keypoint of every node.  The reference sorts
+// pair<int, ExtractorNode*> and so breaks ties between equally full nodes by pointer value; this double breaks them by the order in
+// which the nodes were created.  Its selection is therefore its own and no test compares it with anything else.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "ORBextractor.h"
+#include "../orb_fast.h"
+#include "orbslam3_hip.h"
+#include "orbslam3_hip_host.h"
+
+namespace ORB_SLAM3 {
+
+ORBextractor::ORBextractor(int _nfeatures, float _scaleFactor, int _nlevels, int _iniThFAST, int _minThFAST)
+    : nfeatures(_nfeatures), scaleFactor(_scaleFactor), nlevels(_nlevels), iniThFAST(_iniThFAST), minThFAST(_minThFAST) {
+  mvScaleFactor.resize(nlevels); mvLevelSigma2.resize(nlevels);
+  mvInvScaleFactor.resize(nlevels); mvInvLevelSigma2.resize(nlevels);
+  for (int i = 0; i < nlevels; i++) {
+    mvScaleFactor[i] = i ? (float)(mvScaleFactor[i - 1] * scaleFactor) : 1.0f;
+    mvLevelSigma2[i] = mvScaleFactor[i] * mvScaleFactor[i];
+    mvInvScaleFactor[i] = 1.0f / mvScaleFactor[i];
+    mvInvLevelSigma2[i] = 1.0f / mvLevelSigma2[i];
+  }
+  mvImagePyramid.resize(nlevels);
+  // the features of a level: a geometric series over the levels that sums to nfeatures, each term rounded half to even, the last
+  // level taking what is left
+  mnFeaturesPerLevel.assign(nlevels, 0);
+  const float q = 1.0f / scaleFactor;                                                         // ratio of the series
+  float share = nfeatures * (1 - q) / (1 - (float)std::pow((double)q, (double)nlevels));      // of level 0, in float32 steps
+  int given = 0;
+  for (int l = 0; l + 1 < nlevels; ++l, share *= q) given += mnFeaturesPerLevel[l] = (int)std::nearbyint(share);
+  if (nlevels > 0) mnFeaturesPerLevel[nlevels - 1] = std::max(nfeatures - given, 0);
+}
+
+namespace {
+struct OctNode {
+  int x0, x1, y0, y1;        // [x0, x1) x [y0, y1), relative to (minX, minY) like the keypoints
+  std::vector<int> keys;     // indices into vToDistributeKeys, ascending
+  bool splittable() const { return keys.size() > 1 && (x1 - x0 > 1 || y1 - y0 > 1); }
+};
+}  // namespace
+
+std::vector<cv::KeyPoint> ORBextractor::DistributeOctTree(const std::vector<cv::KeyPoint>& vToDistributeKeys, const int& minX, const int& maxX,
+                                                          const int& minY, const int& maxY, const int& N, const int& level) {
+  mvDistributeCalls.push_back({vToDistributeKeys, minX, maxX, minY, maxY, N, level});
+  std::vector<cv::KeyPoint> result;
+  const int W = maxX - minX, H = maxY - minY;
+  if (vToDistributeKeys.empty() || W <= 0 || H <= 0) return result;
+  // roots: as many side by side as the area is wider than high
+  const int nIni = std::max(1, (int)std::nearbyint((float)W / (float)H));
+  std::vector<OctNode> nodes(nIni);   // in creation order
+  for (int r = 0; r < nIni; ++r) nodes[r] = {(int)((long long)W * r / nIni), (int)((long long)W * (r + 1) / nIni), 0, H, {}};
+  for (int k = 0; k < (int)vToDistributeKeys.size(); ++k) {
+    int r = 0;
+    while (r + 1 < nIni && vToDistributeKeys[k].pt.x >= (float)nodes[r].x1) ++r;
+    nodes[r].keys.push_back(k);
+  }
+  nodes.erase(std::remove_if(nodes.begin(), nodes.end(), [](const OctNode& n) { return n.keys.empty(); }), nodes.end());
+
+  auto split = [&](size_t at) {   // the node at `at` leaves, its non-empty quarters join at the end
+    const OctNode n = nodes[at];
+    nodes.erase(nodes.begin() + (long)at);
+    const int mx = n.x0 + (n.x1 - n.x0 + 1) / 2, my = n.y0 + (n.y1 - n.y0 + 1) / 2;
+    OctNode q[4] = {{n.x0, mx, n.y0, my, {}}, {mx, n.x1, n.y0, my, {}}, {n.x0, mx, my, n.y1, {}}, {mx, n.x1, my, n.y1, {}}};
+    for (int k : n.keys) q[(vToDistributeKeys[k].pt.x >= (float)mx ? 1 : 0) + (vToDistributeKeys[k].pt.y >= (float)my ? 2 : 0)].keys.push_back(k);
+    for (const OctNode& c : q) if (!c.keys.empty()) nodes.push_back(c);
+  };
+  while ((int)nodes.size() < N) {
+    std::vector<size_t> open;
+    for (size_t k = 0; k < nodes.size(); ++k) if (nodes[k].splittable()) open.push_back(k);
+    if (open.empty()) break;
+    const size_t before = nodes.size();
+    if ((int)(nodes.size() + 3 * open.size()) > N) {
+      // a whole round would overshoot: the fullest node first, one at a time (ties: the node created first)
+      size_t best = open[0];
+      for (size_t k : open) if (nodes[k].keys.size() > nodes[best].keys.size()) best = k;
+      split(best);
+    } else {
+      for (size_t k = open.size(); k-- > 0;) split(open[k]);   // back to front: the indices in front stay valid
+    }
+    if (nodes.size() == before) {
+      bool shrunk = false;   // no node more, but the boxes got smaller: go on until they cannot
+      for (const OctNode& n : nodes) shrunk |= n.splittable();
+      if (!shrunk) break;
+    }
+  }
+  result.reserve(nodes.size());
+  for (const OctNode& n : nodes) {
+    int best = n.keys[0];
+    for (int k : n.keys) if (vToDistributeKeys[k].response > vToDistributeKeys[best].response) best = k;
+    result.push_back(vToDistributeKeys[best]);
+  }
+  return result;
+}
+
+}  // namespace ORB_SLAM3
+
+using namespace ORB_SLAM3;
+
+extern "C" int osh_host_orb_fast_cpu(int32_t n_frames, const osh_fast_frame* frames, osh_fast_result* results, double* ms) {
+  if (n_frames < 0 || (n_frames && (!frames || !results))) return -1;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_fast_frame& f = frames[k];
+    osh_fast_result& r = results[k];
+    if (!f.pyramid || !r.level_count) return -1;
+    std::vector<osh::FastCorner> corners;
+    std::vector<uint8_t> used;
+    std::vector<int> level_of;
+    for (int l = 0; l < f.n_levels; ++l) {
+      const size_t before = corners.size();
+      osh::fast_level_host(f.pyramid[l].data, f.pyramid[l].rows, f.pyramid[l].cols, (long long)f.pyramid[l].stride, f.ini_th, f.min_th, 0, corners, used);
+      r.level_count[l] = (int32_t)(corners.size() - before);
+      level_of.resize(corners.size(), l);
+    }
+    r.n_out = (int32_t)corners.size(); r.n_cells = (int32_t)used.size(); r.pyramid_token = 0;
+    if (r.n_out > r.capacity || (r.used_min_th && r.n_cells > r.cell_capacity)) continue;
+    if (r.used_min_th) std::copy(used.begin(), used.end(), r.used_min_th);
+    for (size_t i = 0; i < corners.size(); ++i) {
+      r.xy[2 * i] = corners[i].x; r.xy[2 * i + 1] = corners[i].y; r.response[i] = corners[i].response;
+      if (r.level) r.level[i] = level_of[i];
+      if (r.cell) r.cell[i] = corners[i].cell;
+    }
+  }
+  if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+extern "C" int osh_host_orb_ic_angle_cpu(int32_t n_frames, const osh_ic_angle_frame* frames, const osh_ic_angle_result* results, double* ms) {
+  if (n_frames < 0 || (n_frames && (!frames || !results))) return -1;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_ic_angle_frame& f = frames[k];
+    if (!f.pyramid || (f.n && (!f.xy || !f.level))) return -1;
+    for (int i = 0; i < f.n; ++i) {
+      const osh_stereo_image& im = f.pyramid[f.level[i]];
+      int m10, m01;
+      const float a = osh::fast_ic_angle_host(im.data, (long long)im.stride, f.xy[2 * i], f.xy[2 * i + 1], m10, m01);
+      if (results[k].angle) results[k].angle[i] = a;
+      if (results[k].m10) results[k].m10[i] = m10;
+      if (results[k].m01) results[k].m01[i] = m01;
+    }
+  }
+  if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+extern "C" int osh_host_orb_fast_level_cells(int32_t rows, int32_t cols, int32_t geom[6], int32_t* rects) {
+  if (rows <= 0 || cols <= 0 || !geom) return -1;
+  const osh::FastGeom g = osh::fast_geometry(rows, cols);
+  geom[0] = g.n_cols; geom[1] = g.n_rows; geom[2] = g.w_cell; geom[3] = g.h_cell; geom[4] = g.max_x; geom[5] = g.max_y;
+  int n = 0;
+  osh::FastRect r;
+  for (int i = 0; i < g.n_rows; ++i)
+    for (int j = 0; j < g.n_cols; ++j) {
+      if (!osh::fast_cell_rect(g, i, j, r)) continue;
+      if (rects) { rects[4 * n] = r.x0; rects[4 * n + 1] = r.y0; rects[4 * n + 2] = r.w; rects[4 * n + 3] = r.h; }
+      ++n;
+    }
+  return n;
+}
+
+extern "C" int osh_host_orbextractor_compute_keypoints(const osh_host_orbextractor_input* in, const osh_host_orbextractor_output* out) {
+  if (!in || !out || in->nlevels < 0 || in->n_images < 0 || in->border < 0 || (in->n_images && (!in->rows || !in->cols || !in->pixels)) || !out->level_count ||
+      !out->cand_level_count) return -1;
+  ORBextractor ex(in->nfeatures, in->scale_factor, in->nlevels, in->ini_th, in->min_th);
+  // levels as views into bordered images, like the reference's ComputePyramid leaves them
+  ex.mvImagePyramid.resize(in->n_images);
+  size_t off = 0;
+  for (int l = 0; l < in->n_images; ++l) {
+    cv::Mat whole(in->rows[l] + 2 * in->border, in->cols[l] + 2 * in->border);
+    for (int r = 0; r < whole.rows; ++r) std::memset(whole.ptr<uint8_t>(r), 167, (size_t)whole.cols);
+    ex.mvImagePyramid[l] = whole.view(in->border, in->border, in->rows[l], in->cols[l]);
+    for (int r = 0; r < in->rows[l]; ++r) std::memcpy(ex.mvImagePyramid[l].ptr<uint8_t>(r), in->pixels + off + (size_t)r * in->cols[l], (size_t)in->cols[l]);
+    off += (size_t)in->rows[l] * in->cols[l];
+  }
+  std::vector<std::vector<cv::KeyPoint> > all;
+  ex.ComputeKeyPointsOctTree(all);
+  if ((int)all.size() != in->nlevels) return -2;
+  for (int l = 0; l < in->nlevels; ++l) {
+    out->cand_level_count[l] = 0;
+    if (out->features_per_level) out->features_per_level[l] = ex.mnFeaturesPerLevel[l];
+    if (out->scale_factors) out->scale_factors[l] = ex.mvScaleFactor[l];
+  }
+  size_t n = 0, nc = 0;
+  for (const ORBextractor::DistributeCall& d : ex.mvDistributeCalls) {
+    if (d.level < 0 || d.level >= in->nlevels) return -2;
+    out->cand_level_count[d.level] += (int32_t)d.keys.size();
+    if (out->cand_args) { int32_t* a = out->cand_args + 6 * d.level; a[0] = d.minX; a[1] = d.maxX; a[2] = d.minY; a[3] = d.maxY; a[4] = d.nFeatures; a[5] = d.level; }
+    for (const cv::KeyPoint& kp : d.keys) {
+      if (nc < (size_t)out->cand_capacity) {
+        if (out->cand_xy) { out->cand_xy[2 * nc] = kp.pt.x; out->cand_xy[2 * nc + 1] = kp.pt.y; }
+        if (out->cand_response) out->cand_response[nc] = kp.response;
+      }
+      ++nc;
+    }
+  }
+  for (int l = 0; l < in->nlevels; ++l) {
+    out->level_count[l] = (int32_t)all[l].size();
+    for (const cv::KeyPoint& kp : all[l]) {
+      if (n < (size_t)out->capacity) {
+        if (out->xy) { out->xy[2 * n] = kp.pt.x; out->xy[2 * n + 1] = kp.pt.y; }
+        if (out->response) out->response[n] = kp.response;
+        if (out->angle) out->angle[n] = kp.angle;
+        if (out->size) out->size[n] = kp.size;
+        if (out->octave) out->octave[n] = kp.octave;
+      }
+      ++n;
+    }
+  }
+  return (int)n;
+}

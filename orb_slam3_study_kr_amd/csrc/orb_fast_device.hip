@@ -1,0 +1,469 @@
+// orb_fast_device.hip -- the integer part of ORBextractor::ComputeKeyPointsOctTree (src/ORBextractor.cc:781-896) on MI355X (gfx950)
+// for a batch of pyramids: the cell-wise FAST-9/16 corners that go into DistributeOctTree and IC_Angle.  The statements are those of
+// orb_fast.h.
+//
+// osh_orb_fast_detect, every cell of every level of every frame in each kernel:
+//   k_fast_cells   one block per cell, largest cells first: the sub-image (at most 75 x 75 bytes) into LDS, the score map as bytes
+//                  beside it, the 3x3 strict-maximum test, and per wavefront one ballot per 64 pixels at each threshold.  The block
+//                  leaves the kept-corner bit mask of the threshold the cell is decided at (row-major, one bit per pixel), its
+//                  count and how it was decided.  No atomic: every word of the mask is one wavefront's ballot.
+//   k_fast_scan    one block: the exclusive scan of the counts over the cells in (frame, level, i, j) order.
+//   k_fast_emit    one wavefront per cell: the set bits of the mask in ascending order at offset[cell] + rank, the score of each
+//                  read again from the packed level.
+// The host reads the offsets between scan and emit: they size the output.  Where a result lands is a function of the counts alone.
+//
+// osh_orb_ic_angle: k_ic_angle, one keypoint per lane, reads its 31-pixel disc from the packed level.
+#include "common.h"
+#include "orb_fast.h"
+#include "orb_stage.h"
+#include <atomic>
+#include <cmath>
+#include <numeric>
+#include <vector>
+
+namespace osh {
+
+constexpr int kFcBlock = 256;                       // k_fast_cells: 4 wavefronts
+constexpr int kFcImgPitch = kFastMaxCell + 1;       // 76
+constexpr int kFcScorePitch = kFastMaxCell + 2;     // 77: one pixel of zeros around the map
+constexpr int kFcRounds = (kFastMaxCell * kFastMaxCell + kFcBlock - 1) / kFcBlock;   // 22
+constexpr int kFeWords = (kFastMaskWords + 63) / 64;                                  // mask words per lane of k_fast_emit: 3
+constexpr int kScanBlock = 256;
+constexpr int kIcBlock = 64;
+
+struct FastCellDev {
+  long long img_off;       // first pixel of the level in the image arena (rows packed)
+  int cols;                // of the level
+  int x0, y0, w, h;        // the sub-image
+  int shift_x, shift_y;    // j * wCell, i * hCell
+  int level, cell;         // cell: number inside its frame
+  int ini_th, min_th;
+};
+
+struct FastView {
+  int n_cells;
+  const FastCellDev* cells;     // (frame, level, i, j) order
+  const int* order;             // launch order: largest sub-image first
+  const unsigned char* images;
+  unsigned* mask;               // [n_cells * kFastMaskWords]
+  int* count;                   // [n_cells]
+  int* offset;                  // [n_cells + 1]
+  unsigned char* used_min;      // [n_cells]
+  float2* xy; float* response; int* level; int* cell;   // [total]
+};
+
+__global__ __launch_bounds__(kFcBlock) void k_fast_cells(FastView v) {
+  __shared__ unsigned char sh_img[kFastMaxCell * kFcImgPitch];
+  __shared__ unsigned char sh_score[kFcScorePitch * kFcScorePitch];
+  __shared__ unsigned sh_mask[2][kFcRounds * (kFcBlock / 32)];
+  __shared__ int sh_cnt[2][kFcBlock / 64];
+  const int c = v.order[blockIdx.x];
+  const FastCellDev& cd = v.cells[c];
+  const int w = cd.w, h = cd.h, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const unsigned char* src = v.images + cd.img_off + (size_t)cd.y0 * cd.cols + cd.x0;
+  // one pixel per thread and round, with a division: a row per wavefront avoids it but was measured slower (93 VGPR against 64)
+  for (int k = tid; k < w * h; k += kFcBlock) { const int y = k / w, x = k - y * w; sh_img[y * kFcImgPitch + x] = src[(size_t)y * cd.cols + x]; }
+  for (int k = tid; k < kFcScorePitch * kFcScorePitch; k += kFcBlock) sh_score[k] = 0;
+  __syncthreads();
+  const int wi = w - 6, hi = h - 6;   // scores exist for rows and columns [3, size - 3)
+  if (wi > 0 && hi > 0)
+    for (int k = tid; k < wi * hi; k += kFcBlock) {
+      const int y = 3 + k / wi, x = 3 + k % wi;
+      sh_score[(y + 1) * kFcScorePitch + x + 1] = (unsigned char)fast_score_at(&sh_img[y * kFcImgPitch + x], kFcImgPitch);
+    }
+  __syncthreads();
+  int n_ini = 0, n_min = 0;   // of this wavefront (the same in every lane)
+  const int rounds = (w * h + kFcBlock - 1) / kFcBlock;
+  for (int r = 0; r < rounds; ++r) {
+    const int k = r * kFcBlock + tid;
+    bool at_ini = false, at_min = false;
+    if (k < w * h) {
+      const int y = k / w, x = k - y * w;
+      const unsigned char* s = &sh_score[(y + 1) * kFcScorePitch + x + 1];
+      const bool kept = fast_is_kept(s, kFcScorePitch);
+      at_ini = kept && s[0] >= cd.ini_th; at_min = kept && s[0] >= cd.min_th;
+    }
+    const unsigned long long b_ini = __ballot(at_ini), b_min = __ballot(at_min);
+    n_ini += __popcll(b_ini); n_min += __popcll(b_min);
+    if (lane < 2) {
+      const int word = r * (kFcBlock / 32) + wave * 2 + lane;
+      sh_mask[0][word] = (unsigned)(b_ini >> (32 * lane)); sh_mask[1][word] = (unsigned)(b_min >> (32 * lane));
+    }
+  }
+  if (lane == 0) { sh_cnt[0][wave] = n_ini; sh_cnt[1][wave] = n_min; }
+  __syncthreads();
+  int t_ini = 0, t_min = 0;
+  for (int k = 0; k < kFcBlock / 64; ++k) { t_ini += sh_cnt[0][k]; t_min += sh_cnt[1][k]; }
+  const int which = t_ini ? 0 : 1;                      // :843: the second threshold only for a cell without corners at the first
+  const int words = (w * h + 31) / 32;                  // <= rounds * 8
+  for (int k = tid; k < words; k += kFcBlock) v.mask[(size_t)c * kFastMaskWords + k] = sh_mask[which][k];
+  if (tid == 0) {
+    v.count[c] = t_ini ? t_ini : t_min;
+    v.used_min[c] = (unsigned char)(t_ini ? kFastAtIni : t_min ? kFastAtMin : kFastEmpty);
+  }
+}
+
+// offset[c] = count[0] + ... + count[c - 1], offset[n_cells] = the total.  One block; every thread sums a run of cells.
+__global__ __launch_bounds__(kScanBlock) void k_fast_scan(FastView v) {
+  __shared__ int sh[kScanBlock];
+  const int tid = threadIdx.x;
+  const int per = (v.n_cells + kScanBlock - 1) / kScanBlock;
+  const int begin = min(v.n_cells, tid * per), end = min(v.n_cells, begin + per);
+  int sum = 0;
+  for (int c = begin; c < end; ++c) sum += v.count[c];
+  sh[tid] = sum;
+  __syncthreads();
+  for (int step = 1; step < kScanBlock; step <<= 1) {
+    const int add = tid >= step ? sh[tid - step] : 0;
+    __syncthreads();
+    sh[tid] += add;
+    __syncthreads();
+  }
+  int run = sh[tid] - sum;
+  for (int c = begin; c < end; ++c) { v.offset[c] = run; run += v.count[c]; }
+  if (tid == kScanBlock - 1) v.offset[v.n_cells] = sh[tid];
+}
+
+// One wavefront per cell; lane l owns the mask words [3 l, 3 l + 3), so ranks ascend with the lane and inside it with the bit.
+__global__ __launch_bounds__(64) void k_fast_emit(FastView v) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  if (v.count[c] == 0) return;
+  const FastCellDev& cd = v.cells[c];
+  const int words = (cd.w * cd.h + 31) / 32;
+  unsigned m[kFeWords];
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < kFeWords; ++k) {
+    const int word = lane * kFeWords + k;
+    m[k] = word < words ? v.mask[(size_t)c * kFastMaskWords + word] : 0u;
+    mine += __popc(m[k]);
+  }
+  int incl = mine;
+#pragma unroll
+  for (int step = 1; step < 64; step <<= 1) { const int up = __shfl_up(incl, step); if (lane >= step) incl += up; }
+  int at = v.offset[c] + incl - mine;
+  const unsigned char* lvl = v.images + cd.img_off;
+#pragma unroll
+  for (int k = 0; k < kFeWords; ++k) {
+    unsigned bits = m[k];
+    while (bits) {
+      const int b = __ffs(bits) - 1;
+      bits &= bits - 1;
+      const int pix = (lane * kFeWords + k) * 32 + b;
+      const int y = pix / cd.w, x = pix - y * cd.w;
+      const int s = fast_score_at(lvl + (size_t)(cd.y0 + y) * cd.cols + cd.x0 + x, cd.cols);
+      v.xy[at] = make_float2((float)(x + cd.shift_x), (float)(y + cd.shift_y));
+      v.response[at] = (float)s; v.level[at] = cd.level; v.cell[at] = cd.cell;
+      ++at;
+    }
+  }
+}
+
+struct IcLevelDev { const unsigned char* data; int rows, cols; };   // data: first pixel of the packed level on the device
+struct IcView {
+  int n;
+  const IcLevelDev* levels;      // of every frame of the call, frame after frame
+  const int* level_index;        // [n] the keypoint's entry of `levels`
+  const float2* xy;              // [n]
+  float* angle; int* m10; int* m01;
+};
+
+__global__ __launch_bounds__(kIcBlock) void k_ic_angle(IcView v) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * kIcBlock + threadIdx.x;
+  if (i >= v.n) return;
+  const IcLevelDev L = v.levels[v.level_index[i]];
+  const float2 p = v.xy[i];
+  const unsigned char* center = L.data + (size_t)fast_cv_round(p.y) * L.cols + fast_cv_round(p.x);
+  int m10, m01;
+  fast_ic_moments(center, (long long)L.cols, m10, m01);
+  v.m10[i] = m10; v.m01[i] = m01;
+  v.angle[i] = fast_atan2((float)m01, (float)m10);
+}
+
+struct FastLevelHost { long long img_off; int rows, cols, cell0, n_cells; };
+struct FastFrameHost { int level0, n_levels, cell0, n_cells; };   // level0 / cell0: first entry of the frame in the call's lists
+
+struct FastState {
+  StagedCall call;              // detect: [cells | order | images] in, [count | offset | used_min] out, mask as work
+  DevBuf emitted;               // xy, response, level, cell of the call
+  PinBuf h_emitted;
+  StagedCall ic_call;           // ic_angle: keypoints (and the pyramid, when the caller hands one over)
+  // the resident pyramid of the last detect
+  uint64_t token0 = 0;          // token of its frame 0; 0: none
+  std::vector<FastFrameHost> frames;
+  std::vector<FastLevelHost> levels;
+  size_t img_off = 0;           // of the image section in call's in region
+  double ms[4] = {0, 0, 0, 0}, ms_ic[4] = {0, 0, 0, 0};
+};
+
+static std::atomic<uint64_t> g_next_token{1};
+
+static int fast_validate_pyramid(const char* entry, int k, int n_levels, const osh_stereo_image* pyr) {
+  if (n_levels < 1 || n_levels > OSH_STEREO_MAX_LEVELS) { set_error("%s: frame %d: n_levels %d outside [1, %d]", entry, k, n_levels, OSH_STEREO_MAX_LEVELS); return OSH_ERR_INVALID; }
+  if (!pyr) { set_error("%s: frame %d: NULL pyramid", entry, k); return OSH_ERR_INVALID; }
+  for (int l = 0; l < n_levels; ++l) {
+    const osh_stereo_image& im = pyr[l];
+    if (!im.data || im.rows <= 0 || im.cols <= 0 || im.stride < im.cols) { set_error("%s: frame %d: level %d is NULL, empty or has stride < cols", entry, k, l); return OSH_ERR_INVALID; }
+    if (im.rows > OSH_FAST_MAX_SIDE || im.cols > OSH_FAST_MAX_SIDE) { set_error("%s: frame %d: level %d exceeds %d pixels in one direction", entry, k, l, OSH_FAST_MAX_SIDE); return OSH_ERR_UNSUPPORTED; }
+  }
+  return OSH_OK;
+}
+
+static int fast_validate(int n_frames, const osh_fast_frame* frames, const osh_fast_result* results) {
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_fast_frame& f = frames[k];
+    const osh_fast_result& r = results[k];
+    OSH_TRY(fast_validate_pyramid("osh_orb_fast_detect", k, f.n_levels, f.pyramid));
+    if (f.ini_th < 1 || f.ini_th > 255 || f.min_th < 1 || f.min_th > 255) { set_error("osh_orb_fast_detect: frame %d: threshold outside [1, 255]", k); return OSH_ERR_INVALID; }
+    if (f.min_th > f.ini_th) { set_error("osh_orb_fast_detect: frame %d: min_th %d > ini_th %d", k, f.min_th, f.ini_th); return OSH_ERR_INVALID; }
+    if (r.capacity < 0 || r.cell_capacity < 0) { set_error("osh_orb_fast_detect: frame %d: negative capacity", k); return OSH_ERR_INVALID; }
+    if (!r.level_count) { set_error("osh_orb_fast_detect: frame %d: NULL level_count", k); return OSH_ERR_INVALID; }
+    if (r.capacity && (!r.xy || !r.response)) { set_error("osh_orb_fast_detect: frame %d: NULL result array with capacity %d", k, r.capacity); return OSH_ERR_INVALID; }
+  }
+  return OSH_OK;
+}
+
+// The keypoints of an ic_angle frame against the level sizes rows[] / cols[]
+static int ic_validate_keypoints(int k, const osh_ic_angle_frame& f, int n_levels, const int* rows, const int* cols) {
+  if (f.n < 0) { set_error("osh_orb_ic_angle: frame %d: negative keypoint count", k); return OSH_ERR_INVALID; }
+  if (f.n && (!f.xy || !f.level)) { set_error("osh_orb_ic_angle: frame %d: NULL keypoint array with n = %d", k, f.n); return OSH_ERR_INVALID; }
+  for (int i = 0; i < f.n; ++i) {
+    const float x = f.xy[2 * i], y = f.xy[2 * i + 1];
+    const int l = f.level[i];
+    if (!std::isfinite(x) || !std::isfinite(y)) { set_error("osh_orb_ic_angle: frame %d: keypoint %d is not finite", k, i); return OSH_ERR_INVALID; }
+    if (l < 0 || l >= n_levels) { set_error("osh_orb_ic_angle: frame %d: keypoint %d: level %d outside [0, %d)", k, i, l, n_levels); return OSH_ERR_INVALID; }
+    // compared as floats first: a coordinate beyond the int range must not reach the conversion
+    if (!(x >= 0.f && y >= 0.f && x <= (float)OSH_FAST_MAX_SIDE && y <= (float)OSH_FAST_MAX_SIDE)) { set_error("osh_orb_ic_angle: frame %d: keypoint %d: the 31-pixel disc leaves level %d", k, i, l); return OSH_ERR_INVALID; }
+    const int cx = fast_cv_round(x), cy = fast_cv_round(y);
+    if (cx - kFastHalfPatch < 0 || cx + kFastHalfPatch >= cols[l] || cy - kFastHalfPatch < 0 || cy + kFastHalfPatch >= rows[l]) {
+      set_error("osh_orb_ic_angle: frame %d: keypoint %d: the 31-pixel disc leaves level %d", k, i, l); return OSH_ERR_INVALID;
+    }
+  }
+  return OSH_OK;
+}
+
+}  // namespace osh
+
+using namespace osh;
+
+extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_fast_frame* frames, osh_fast_result* results) {
+  PhaseClock clock;
+  if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_fast_detect: bad arguments"); return OSH_ERR_INVALID; }
+  OSH_TRY(fast_validate(n_frames, frames, results));   // a refusal needs no context and no device
+  if (!c) { set_error("osh_orb_fast_detect: no context"); return OSH_ERR_INVALID; }
+  if (n_frames == 0) return OSH_OK;
+
+  // the cells of the call in (frame, level, i, j) order, the levels packed one after another
+  std::vector<FastFrameHost> fh(n_frames);
+  std::vector<FastLevelHost> lh;
+  std::vector<FastCellDev> cells;
+  size_t img_bytes = 0;
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_fast_frame& f = frames[k];
+    fh[k] = {(int)lh.size(), f.n_levels, (int)cells.size(), 0};
+    for (int l = 0; l < f.n_levels; ++l) {
+      const osh_stereo_image& im = f.pyramid[l];
+      FastLevelHost L{(long long)img_bytes, im.rows, im.cols, (int)cells.size(), 0};
+      const FastGeom g = fast_geometry(im.rows, im.cols);
+      FastRect r;
+      for (int i = 0; i < g.n_rows; ++i)
+        for (int j = 0; j < g.n_cols; ++j) {
+          if (!fast_cell_rect(g, i, j, r)) continue;
+          if (r.w > kFastMaxCell || r.h > kFastMaxCell || r.x0 + r.w > im.cols || r.y0 + r.h > im.rows) { set_error("osh_orb_fast_detect: frame %d level %d: cell (%d, %d) out of bounds", k, l, i, j); return OSH_ERR_UNSUPPORTED; }
+          cells.push_back({L.img_off, im.cols, r.x0, r.y0, r.w, r.h, j * g.w_cell, i * g.h_cell, l, (int)cells.size() - fh[k].cell0, f.ini_th, f.min_th});
+        }
+      L.n_cells = (int)cells.size() - L.cell0;
+      lh.push_back(L);
+      img_bytes += (size_t)im.rows * im.cols;
+      if (cells.size() > (size_t)1 << 22 || img_bytes > (size_t)1 << 31) { set_error("osh_orb_fast_detect: batch too large"); return OSH_ERR_UNSUPPORTED; }
+    }
+    fh[k].n_cells = (int)cells.size() - fh[k].cell0;
+  }
+  const int n_cells = (int)cells.size();
+  std::vector<int> order(n_cells);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cells[a].w * cells[a].h > cells[b].w * cells[b].h; });
+
+  int device = 0;
+  hipStream_t s = nullptr;
+  OSH_TRY(orb_stream(c, &device, &s));
+  FastState* st = orb_state<FastState>(c, kOrbAttachFast);
+  clock.profiling = orb_profiling(c);
+  st->token0 = 0;   // the resident pyramid is about to be replaced
+
+  Layout in, out, work;
+  const auto s_cells = in.take<FastCellDev>(n_cells);
+  const auto s_order = in.take<int>(n_cells);
+  const auto s_img = in.take<unsigned char>(img_bytes);
+  const auto o_offset = out.take<int>((size_t)n_cells + 1);
+  const auto o_used = out.take<unsigned char>(n_cells);
+  const auto w_count = work.take<int>(n_cells);
+  const auto w_mask = work.take<unsigned>((size_t)n_cells * kFastMaskWords);
+  OSH_TRY(st->call.reserve(in, out, work.bytes));
+  char* h = st->call.host_in();
+  if (n_cells) {
+    std::memcpy(s_cells.in(h), cells.data(), sizeof(FastCellDev) * n_cells);
+    std::memcpy(s_order.in(h), order.data(), sizeof(int) * n_cells);
+  }
+  for (int k = 0; k < n_frames; ++k)
+    for (int l = 0; l < frames[k].n_levels; ++l) pack_level(s_img.in(h) + lh[fh[k].level0 + l].img_off, frames[k].pyramid[l]);
+  clock.mark();
+  OSH_TRY(st->call.upload(s));
+  OSH_TRY(clock.mark_synced(s));
+
+  FastView v{};
+  char* di = st->call.dev_in(); char* dout = st->call.dev_out(); char* dw = st->call.dev_work();
+  v.n_cells = n_cells; v.cells = s_cells.in(di); v.order = s_order.in(di); v.images = s_img.in(di);
+  v.mask = w_mask.in(dw); v.count = w_count.in(dw); v.offset = o_offset.in(dout); v.used_min = o_used.in(dout);
+  if (n_cells) hipLaunchKernelGGL(k_fast_cells, dim3((unsigned)n_cells), dim3(kFcBlock), 0, s, v);
+  hipLaunchKernelGGL(k_fast_scan, dim3(1), dim3(kScanBlock), 0, s, v);
+  OSH_TRY(launch_check("FAST cells"));
+  OSH_TRY(st->call.download(s));   // offsets and used_min; synchronises
+  const int* offset = o_offset.in(st->call.host_out());
+  const unsigned char* used = o_used.in(st->call.host_out());
+  const size_t total = (size_t)offset[n_cells];
+
+  Layout em;
+  const auto e_xy = em.take<float2>(total); const auto e_resp = em.take<float>(total);
+  const auto e_level = em.take<int>(total); const auto e_cell = em.take<int>(total);
+  if (total) {
+    OSH_TRY(st->emitted.reserve(em.bytes));
+    if (!st->h_emitted.reserve(em.bytes)) { set_error("osh_orb_fast_detect: pinned allocation of %zu bytes failed", em.bytes); return OSH_ERR_DEVICE; }
+    char* de = st->emitted.as<char>();
+    v.xy = e_xy.in(de); v.response = e_resp.in(de); v.level = e_level.in(de); v.cell = e_cell.in(de);
+    hipLaunchKernelGGL(k_fast_emit, dim3((unsigned)n_cells), dim3(64), 0, s, v);
+    OSH_TRY(launch_check("FAST emit"));
+  }
+  OSH_TRY(clock.mark_synced(s));
+  if (total) {
+    OSH_HIP(hipMemcpyAsync(st->h_emitted.p, st->emitted.p, em.bytes, hipMemcpyDeviceToHost, s));
+    OSH_HIP(hipStreamSynchronize(s));
+  }
+  const char* he = static_cast<const char*>(st->h_emitted.p);
+  const uint64_t token0 = g_next_token.fetch_add((uint64_t)n_frames);
+  for (int k = 0; k < n_frames; ++k) {
+    osh_fast_result& r = results[k];
+    const FastFrameHost& F = fh[k];
+    const size_t base = (size_t)offset[F.cell0], n = (size_t)offset[F.cell0 + F.n_cells] - base;
+    r.n_out = (int32_t)n; r.n_cells = F.n_cells; r.pyramid_token = token0 + (uint64_t)k;
+    for (int l = 0; l < F.n_levels; ++l) {
+      const FastLevelHost& L = lh[F.level0 + l];
+      r.level_count[l] = offset[L.cell0 + L.n_cells] - offset[L.cell0];
+    }
+    if (n > (size_t)r.capacity || (r.used_min_th && F.n_cells > r.cell_capacity)) continue;   // counts only: the caller sizes its arrays and calls again
+    if (r.used_min_th && F.n_cells) std::memcpy(r.used_min_th, used + F.cell0, (size_t)F.n_cells);
+    if (n) {
+      scatter(reinterpret_cast<float2*>(r.xy), e_xy, he, base, n); scatter(r.response, e_resp, he, base, n);
+      scatter(r.level, e_level, he, base, n); scatter(r.cell, e_cell, he, base, n);
+    }
+  }
+  st->frames = std::move(fh); st->levels = std::move(lh); st->img_off = s_img.off; st->token0 = token0;
+  clock.mark();
+  clock.store(st->ms);
+  return OSH_OK;
+}
+
+extern "C" int osh_orb_ic_angle(osh_orb_ctx* c, int32_t n_frames, const osh_ic_angle_frame* frames, const osh_ic_angle_result* results) {
+  PhaseClock clock;
+  if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_ic_angle: bad arguments"); return OSH_ERR_INVALID; }
+  // frames that bring their pyramid first: their refusals need no context and no device
+  bool any_token = false;
+  size_t N = 0;
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_ic_angle_frame& f = frames[k];
+    if (!f.pyramid) { any_token = true; continue; }
+    OSH_TRY(fast_validate_pyramid("osh_orb_ic_angle", k, f.n_levels, f.pyramid));
+    int rows[OSH_STEREO_MAX_LEVELS], cols[OSH_STEREO_MAX_LEVELS];
+    for (int l = 0; l < f.n_levels; ++l) { rows[l] = f.pyramid[l].rows; cols[l] = f.pyramid[l].cols; }
+    OSH_TRY(ic_validate_keypoints(k, f, f.n_levels, rows, cols));
+  }
+  if (!c) { set_error("osh_orb_ic_angle: no context"); return OSH_ERR_INVALID; }
+  FastState* st = any_token ? orb_state<FastState>(c, kOrbAttachFast) : nullptr;
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_ic_angle_frame& f = frames[k];
+    if (f.pyramid) continue;
+    if (!st->token0 || f.pyramid_token < st->token0 || f.pyramid_token - st->token0 >= (uint64_t)st->frames.size()) {
+      set_error("osh_orb_ic_angle: frame %d: the token names no frame of this context's last osh_orb_fast_detect", k); return OSH_ERR_INVALID;
+    }
+    const FastFrameHost& F = st->frames[(size_t)(f.pyramid_token - st->token0)];
+    int rows[OSH_STEREO_MAX_LEVELS], cols[OSH_STEREO_MAX_LEVELS];
+    for (int l = 0; l < F.n_levels; ++l) { rows[l] = st->levels[F.level0 + l].rows; cols[l] = st->levels[F.level0 + l].cols; }
+    OSH_TRY(ic_validate_keypoints(k, f, F.n_levels, rows, cols));
+  }
+  for (int k = 0; k < n_frames; ++k) N += (size_t)frames[k].n;
+  if (N > (size_t)1 << 24) { set_error("osh_orb_ic_angle: more than 2^24 keypoints in one call"); return OSH_ERR_UNSUPPORTED; }
+  if (N == 0) return OSH_OK;
+  int device = 0;
+  hipStream_t s = nullptr;
+  OSH_TRY(orb_stream(c, &device, &s));
+  if (!st) st = orb_state<FastState>(c, kOrbAttachFast);
+  clock.profiling = orb_profiling(c);
+
+  // levels of the call: a frame with a token points into the resident arena of the detector, the others into this call's upload
+  struct Lv { bool resident; size_t off; int rows, cols; };
+  std::vector<Lv> lv;
+  std::vector<int> level0(n_frames);
+  size_t img_bytes = 0;
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_ic_angle_frame& f = frames[k];
+    level0[k] = (int)lv.size();
+    if (f.pyramid) {
+      for (int l = 0; l < f.n_levels; ++l) { lv.push_back({false, img_bytes, f.pyramid[l].rows, f.pyramid[l].cols}); img_bytes += (size_t)f.pyramid[l].rows * f.pyramid[l].cols; }
+    } else {
+      const FastFrameHost& F = st->frames[(size_t)(f.pyramid_token - st->token0)];
+      for (int l = 0; l < F.n_levels; ++l) { const FastLevelHost& L = st->levels[F.level0 + l]; lv.push_back({true, (size_t)L.img_off, L.rows, L.cols}); }
+    }
+    if (img_bytes > (size_t)1 << 31) { set_error("osh_orb_ic_angle: batch too large"); return OSH_ERR_UNSUPPORTED; }
+  }
+  Layout in, out;
+  const auto s_levels = in.take<IcLevelDev>(lv.size());
+  const auto s_index = in.take<int>(N);
+  const auto s_xy = in.take<float2>(N);
+  const auto s_img = in.take<unsigned char>(img_bytes);
+  const auto o_angle = out.take<float>(N); const auto o_m10 = out.take<int>(N); const auto o_m01 = out.take<int>(N);
+  OSH_TRY(st->ic_call.reserve(in, out));
+  char* h = st->ic_call.host_in();
+  const unsigned char* resident = reinterpret_cast<const unsigned char*>(st->call.dev_in()) + st->img_off;
+  const unsigned char* uploaded = s_img.in(static_cast<const char*>(st->ic_call.dev_in()));
+  for (size_t l = 0; l < lv.size(); ++l) s_levels.in(h)[l] = {(lv[l].resident ? resident : uploaded) + lv[l].off, lv[l].rows, lv[l].cols};
+  std::vector<size_t> base(n_frames);
+  size_t b = 0;
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_ic_angle_frame& f = frames[k];
+    base[k] = b;
+    if (f.n) std::memcpy(s_xy.in(h) + b, f.xy, (size_t)f.n * 8);
+    for (int i = 0; i < f.n; ++i) s_index.in(h)[b + i] = level0[k] + f.level[i];
+    b += (size_t)f.n;
+    if (f.pyramid) for (int l = 0; l < f.n_levels; ++l) pack_level(s_img.in(h) + lv[level0[k] + l].off, f.pyramid[l]);
+  }
+  clock.mark();
+  OSH_TRY(st->ic_call.upload(s));
+  OSH_TRY(clock.mark_synced(s));
+  IcView v{};
+  char* di = st->ic_call.dev_in(); char* dout = st->ic_call.dev_out();
+  v.n = (int)N; v.levels = s_levels.in(di); v.level_index = s_index.in(di); v.xy = s_xy.in(di);
+  v.angle = o_angle.in(dout); v.m10 = o_m10.in(dout); v.m01 = o_m01.in(dout);
+  hipLaunchKernelGGL(k_ic_angle, dim3((unsigned)((N + kIcBlock - 1) / kIcBlock)), dim3(kIcBlock), 0, s, v);
+  OSH_TRY(launch_check("IC_Angle"));
+  OSH_TRY(clock.mark_synced(s));
+  OSH_TRY(st->ic_call.download(s));
+  const char* ho = st->ic_call.host_out();
+  for (int k = 0; k < n_frames; ++k) {
+    const size_t n = (size_t)frames[k].n;
+    scatter(results[k].angle, o_angle, ho, base[k], n); scatter(results[k].m10, o_m10, ho, base[k], n); scatter(results[k].m01, o_m01, ho, base[k], n);
+  }
+  clock.mark();
+  clock.store(st->ms_ic);
+  return OSH_OK;
+}
+
+extern "C" int osh_orb_fast_get_times(osh_orb_ctx* c, double ms[4]) {
+  return copy_times<FastState>("osh_orb_fast_get_times", c, kOrbAttachFast, ms);
+}
+
+extern "C" int osh_orb_ic_angle_get_times(osh_orb_ctx* c, double ms[4]) {
+  if (!c || !ms) { set_error("osh_orb_ic_angle_get_times: bad arguments"); return OSH_ERR_INVALID; }
+  std::memcpy(ms, orb_state<FastState>(c, kOrbAttachFast)->ms_ic, sizeof(double) * 4);
+  return OSH_OK;
+}

@@ -6,6 +6,7 @@
 // osh_orb_bow_transform (bow_device.hip) has frames of descriptors only: it uses scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_bow_db_query (bowdb_device.hip) has queries against a database: it uses PhaseClock, orb_state and copy_times.
 // osh_orb_triangulate_new_points (newpoint_device.hip) has segments of matched pairs: it uses scatter, PhaseClock, orb_state and copy_times.
+// osh_orb_fast_detect / osh_orb_ic_angle (orb_fast_device.hip) have pyramids: they use pack_level, scatter, PhaseClock, orb_state and copy_times.
 #pragma once
 #include "common.h"
 #include <chrono>
@@ -54,6 +55,12 @@ struct KeypointBatch {
     v.rxy = rxy.in(dev_in); v.roct = roct.in(dev_in); v.rdesc = rdesc.in(dev_in);
   }
 };
+
+// The rows of a pyramid level (rows `stride` bytes apart) one after another at dst, stride = cols
+inline void pack_level(unsigned char* dst, const osh_stereo_image& im) {
+  if (im.stride == im.cols) { std::memcpy(dst, im.data, (size_t)im.rows * im.cols); return; }
+  for (int r = 0; r < im.rows; ++r) std::memcpy(dst + (size_t)r * im.cols, im.data + (size_t)r * im.stride, (size_t)im.cols);
+}
 
 // `n` results of `per_item` values each from `section` of the downloaded outputs, for a frame whose results start at `base`
 template <class T>

@@ -355,11 +355,7 @@ extern "C" int osh_orb_stereo_match(osh_orb_ctx* c, int32_t n_frames, const osh_
       if (d.off_l[l] < 0) continue;
       const osh_stereo_image* im[2] = {&f.left_pyramid[l], &f.right_pyramid[l]};
       const long long off[2] = {d.off_l[l], d.off_r[l]};
-      for (int side = 0; side < 2; ++side) {
-        unsigned char* dst = s_img.in(h) + off[side];
-        if (im[side]->stride == im[side]->cols) std::memcpy(dst, im[side]->data, (size_t)im[side]->rows * im[side]->cols);
-        else for (int r = 0; r < im[side]->rows; ++r) std::memcpy(dst + (size_t)r * im[side]->cols, im[side]->data + (size_t)r * im[side]->stride, (size_t)im[side]->cols);
-      }
+      for (int side = 0; side < 2; ++side) pack_level(s_img.in(h) + off[side], *im[side]);
     }
   }
   clock.mark();

@@ -986,3 +986,50 @@ def create_new_map_points(scene, coarse: bool = True, new_keyframe_waiting: bool
     out["neighbour"] = out["neighbour"] - 1          # keyframe index -> segment index
     out["poses"] = poses
     return out
+
+
+def orb_fast_cpu(frames):
+    """csrc/orb_fast.h on the host in one thread (osh_host_orb_fast_cpu): the per-frame dicts of OrbMatcher.fast_detect, ms."""
+    from . import orb
+    return orb.fast_cpu(frames)
+
+
+def orb_ic_angle_cpu(items):
+    """IC_Angle of csrc/orb_fast.h on the host in one thread (osh_host_orb_ic_angle_cpu): per-item dicts angle / m10 / m01, ms."""
+    from . import orb
+    return orb.ic_angle_cpu(items)
+
+
+def orbextractor_compute_keypoints(pyramid, nfeatures=1000, scale_factor=1.2, ini_th=20, min_th=7, nlevels=None, border=0) -> dict:
+    """ORBextractor::ComputeKeyPointsOctTree of the stand-in class on a pyramid (a list of uint8 levels) through
+    osh_host_orbextractor_compute_keypoints.  nlevels: of the extractor (default: the pyramid's; more than the pyramid has shows the
+    refusal).  Returns level_count and the keypoints level after level (xy, response, angle, size, octave), the candidates every
+    DistributeOctTree call received (cand_level_count, cand_xy, cand_response, cand_args [nlevels, 6]: minX maxX minY maxY nFeatures
+    level), and the extractor's features_per_level and scale_factors."""
+    lib = capi.load_host_library()
+    nlevels = len(pyramid) if nlevels is None else int(nlevels)
+    rows = np.asarray([p.shape[0] for p in pyramid], np.int32)
+    cols = np.asarray([p.shape[1] for p in pyramid], np.int32)
+    pixels = np.concatenate([np.ascontiguousarray(p, np.uint8).ravel() for p in pyramid]) if len(pyramid) else np.zeros(1, np.uint8)
+    cin = capi.HostOrbExtractorInput()
+    cin.nfeatures, cin.scale_factor, cin.nlevels, cin.ini_th, cin.min_th = int(nfeatures), float(scale_factor), nlevels, int(ini_th), int(min_th)
+    cin.n_images, cin.border = len(pyramid), int(border)
+    cin.rows, cin.cols, cin.pixels = capi.ptr(rows, capi.c_int32_p), capi.ptr(cols, capi.c_int32_p), capi.ptr(pixels, capi.c_uint8_p)
+    cap = cand_cap = 0
+    for _ in range(2):   # the first pass counts
+        o = dict(level_count=np.zeros(max(nlevels, 1), np.int32), xy=np.zeros((cap, 2), np.float32), response=np.zeros(cap, np.float32),
+                 angle=np.zeros(cap, np.float32), size=np.zeros(cap, np.float32), octave=np.zeros(cap, np.int32),
+                 cand_level_count=np.zeros(max(nlevels, 1), np.int32), cand_xy=np.zeros((cand_cap, 2), np.float32),
+                 cand_response=np.zeros(cand_cap, np.float32), cand_args=np.zeros((max(nlevels, 1), 6), np.int32),
+                 features_per_level=np.zeros(max(nlevels, 1), np.int32), scale_factors=np.zeros(max(nlevels, 1), np.float32))
+        cout = capi.HostOrbExtractorOutput()
+        cout.capacity, cout.cand_capacity = cap, cand_cap
+        for name, a in o.items():
+            setattr(cout, name, capi.ptr(a, {np.dtype(np.float32): capi.c_float_p, np.dtype(np.int32): capi.c_int32_p}[a.dtype]))
+        n = lib.osh_host_orbextractor_compute_keypoints(C.byref(cin), C.byref(cout))
+        if n < 0:
+            raise RuntimeError(f"osh_host_orbextractor_compute_keypoints returned {n}")
+        if n <= cap and int(o["cand_level_count"].sum()) <= cand_cap:
+            break
+        cap, cand_cap = n, int(o["cand_level_count"].sum())
+    return {k: v[:nlevels] if k in ("level_count", "cand_level_count", "cand_args", "features_per_level", "scale_factors") else v for k, v in o.items()}

@@ -156,6 +156,8 @@ class OrbMatcher:
     stereo_times = functools.partialmethod(_times, "osh_orb_stereo_get_times")                   # of the last stereo_match
     fisheye_stereo_times = functools.partialmethod(_times, "osh_orb_fisheye_stereo_get_times")   # of the last fisheye_stereo_match
     newpoint_times = functools.partialmethod(_times, "osh_orb_newpoint_get_times")               # of the last triangulate_new_points
+    fast_times = functools.partialmethod(_times, "osh_orb_fast_get_times")                       # of the last fast_detect
+    ic_angle_times = functools.partialmethod(_times, "osh_orb_ic_angle_get_times")               # of the last ic_angle
     bow_times = functools.partialmethod(_times, "osh_orb_bow_get_times")                         # of the last bow_transform
     bow_db_times = functools.partialmethod(_times, "osh_orb_bow_db_get_times")                   # of the last bow_db_query
 
@@ -190,6 +192,25 @@ class OrbMatcher:
         cos_parallax [n] and x3d [n, 3]."""
         cs, cr, _keep, outs = newpoint_args(segments)
         capi.check(self.lib.osh_orb_triangulate_new_points(self.ctx, len(segments), cs, cr), "osh_orb_triangulate_new_points", self.lib)
+        return outs
+
+    def fast_detect(self, frames, capacities=None, borders=None) -> list:
+        """The cell-wise FAST corners of ORBextractor::ComputeKeyPointsOctTree (src/ORBextractor.cc:787-872) for a batch of
+        synth_fast.FastFrame in one osh_orb_fast_detect call: per frame a dict with n_out, n_cells, token, level_count and xy [n, 2],
+        response, level, cell, used_min_th.  capacities: per frame (capacity, cell_capacity); a frame that does not fit comes back
+        with its counts and None for the arrays.  None: a first call with no room sizes the arrays of a second."""
+        if capacities is None:
+            sized = self.fast_detect(frames, [(0, 0)] * len(frames), borders)
+            capacities = [(r["n_out"], r["n_cells"]) for r in sized]
+        cf, cr, _keep, outs = fast_args(frames, capacities, borders)
+        capi.check(self.lib.osh_orb_fast_detect(self.ctx, len(frames), cf, cr), "osh_orb_fast_detect", self.lib)
+        return _fast_outputs(cr, outs)
+
+    def ic_angle(self, items, borders=None) -> list:
+        """IC_Angle (src/ORBextractor.cc:76-103) for a batch of items dict(xy, level, pyramid or token) in one osh_orb_ic_angle
+        call: per item a dict with angle, m10, m01."""
+        cf, cr, _keep, outs = ic_angle_args(items, borders)
+        capi.check(self.lib.osh_orb_ic_angle(self.ctx, len(items), cf, cr), "osh_orb_ic_angle", self.lib)
         return outs
 
     def kb8_triangulate(self, rig: "capi.Kb8Rig", xy1, xy2, sigma1, sigma2) -> dict:
@@ -305,6 +326,21 @@ def _wire_outputs(res, outs):
         setattr(res, name, capi.ptr(o, _POINTER[o.dtype]))
 
 
+def pyramid_images(levels, border, keep: dict):
+    """The osh_stereo_image array of a pyramid (a list of uint8 [rows, cols] arrays; None: the level's data stays NULL), every level
+    handed over as a view into an image with `border` pixels of 167 around it.  The images are added to `keep`."""
+    imgs = (capi.StereoImage * max(len(levels), 1))()
+    for l, m in enumerate(levels):
+        if m is None:
+            continue
+        whole = np.full((m.shape[0] + 2 * border, m.shape[1] + 2 * border), 167, dtype=np.uint8)
+        whole[border:border + m.shape[0], border:border + m.shape[1]] = m
+        keep[f"img{len(keep)}"] = whole
+        imgs[l].data = C.cast(whole.ctypes.data + border * whole.shape[1] + border, capi.c_uint8_p)
+        imgs[l].rows, imgs[l].cols, imgs[l].stride = m.shape[0], m.shape[1], whole.shape[1]
+    return imgs
+
+
 def stereo_args(frames, stages: bool = False, borders=None):
     """The osh_stereo_frame / osh_stereo_result arrays of OrbMatcher.stereo_match for repeated calls: (frames, results, the arrays
     that keep their pointers alive, the per-frame dicts of output arrays)."""
@@ -321,16 +357,7 @@ def stereo_args(frames, stages: bool = False, borders=None):
         f.scale_factors, f.inv_scale_factors = capi.ptr(a["sf"], capi.c_float_p), capi.ptr(a["isf"], capi.c_float_p)
         pyr = []
         for side in (fr.left_pyramid, fr.right_pyramid):
-            imgs = (capi.StereoImage * fr.n_levels)()
-            for l, m in enumerate(side):
-                if m is None:
-                    continue                           # a level no left keypoint names: data stays NULL
-                whole = np.full((m.shape[0] + 2 * border, m.shape[1] + 2 * border), 167, dtype=np.uint8)
-                whole[border:border + m.shape[0], border:border + m.shape[1]] = m
-                a[f"img{len(a)}"] = whole
-                imgs[l].data = C.cast(whole.ctypes.data + border * whole.shape[1] + border, capi.c_uint8_p)
-                imgs[l].rows, imgs[l].cols, imgs[l].stride = m.shape[0], m.shape[1], whole.shape[1]
-            pyr.append(imgs)
+            pyr.append(pyramid_images(side, border, a))
         f.left_pyramid, f.right_pyramid = pyr[0], pyr[1]
         f.bf, f.b = fr.bf, fr.b
         n = f.n_left
@@ -342,6 +369,105 @@ def stereo_args(frames, stages: bool = False, borders=None):
         keep.append((a, pyr))
         outs.append(o)
     return cf, cr, keep, outs
+
+
+def fast_level_cells(rows, cols, host_lib=None):
+    """The cell geometry of csrc/orb_fast.h on the host (osh_host_orb_fast_level_cells of the test library): (nCols, nRows, wCell,
+    hCell, maxBorderX, maxBorderY) and the [n, 4] rectangles x0 y0 w h of the level's cells in (i, j) order."""
+    host_lib = host_lib or capi.load_host_library()
+    geom = np.zeros(6, np.int32)
+    if host_lib.osh_host_orb_fast_level_cells(int(rows), int(cols), capi.ptr(geom, capi.c_int32_p), None) < 0:
+        raise RuntimeError("osh_host_orb_fast_level_cells refused the level")
+    rects = np.zeros((max(int(geom[0]) * int(geom[1]), 1), 4), np.int32)
+    n = host_lib.osh_host_orb_fast_level_cells(int(rows), int(cols), capi.ptr(geom, capi.c_int32_p), capi.ptr(rects, capi.c_int32_p))
+    return tuple(int(g) for g in geom), rects[:n].copy()
+
+
+def fast_args(frames, capacities, borders=None):
+    """The osh_fast_frame / osh_fast_result arrays of OrbMatcher.fast_detect for frames with .pyramid / .ini_th / .min_th
+    (synth_fast.FastFrame) and per frame a (capacity, cell_capacity): (frames, results, keep-alive, per-frame dicts of outputs)."""
+    n_frames = len(frames)
+    cf = (capi.FastFrame * max(n_frames, 1))()
+    cr = (capi.FastResult * max(n_frames, 1))()
+    keep, outs = [], []
+    for k, fr in enumerate(frames):
+        a = {}
+        cf[k].n_levels = len(fr.pyramid)
+        cf[k].pyramid = pyramid_images(list(fr.pyramid), 0 if borders is None else int(borders[k]), a)
+        a["pyr"] = cf[k].pyramid
+        cf[k].ini_th, cf[k].min_th = int(fr.ini_th), int(fr.min_th)
+        cap, cell_cap = (int(c) for c in capacities[k])
+        o = dict(level_count=np.zeros(len(fr.pyramid), np.int32), xy=np.zeros((cap, 2), np.float32), response=np.zeros(cap, np.float32),
+                 level=np.zeros(cap, np.int32), cell=np.zeros(cap, np.int32), used_min_th=np.zeros(cell_cap, np.uint8))
+        cr[k].capacity, cr[k].cell_capacity = cap, cell_cap
+        _wire_outputs(cr[k], o)
+        keep.append(a)
+        outs.append(o)
+    return cf, cr, keep, outs
+
+
+def _fast_outputs(cr, outs):
+    """Per frame: the counts, the token and, when the arrays were large enough, the arrays cut to their lengths (else None)."""
+    res = []
+    for k, o in enumerate(outs):
+        n, nc = int(cr[k].n_out), int(cr[k].n_cells)
+        d = dict(n_out=n, n_cells=nc, token=int(cr[k].pyramid_token), level_count=o["level_count"])
+        fits = n <= int(cr[k].capacity) and nc <= int(cr[k].cell_capacity)
+        for name in ("xy", "response", "level", "cell"):
+            d[name] = o[name][:n] if fits else None
+        d["used_min_th"] = o["used_min_th"][:nc] if fits else None
+        res.append(d)
+    return res
+
+
+def ic_angle_args(items, borders=None):
+    """The osh_ic_angle_frame / osh_ic_angle_result arrays for items dict(xy [n, 2], level [n], and pyramid (a list of levels) or
+    token)."""
+    n_items = len(items)
+    cf = (capi.IcAngleFrame * max(n_items, 1))()
+    cr = (capi.IcAngleResult * max(n_items, 1))()
+    keep, outs = [], []
+    for k, it in enumerate(items):
+        a = dict(xy=np.ascontiguousarray(it["xy"], np.float32).reshape(-1, 2), level=np.ascontiguousarray(it["level"], np.int32))
+        n = cf[k].n = a["level"].shape[0]
+        cf[k].xy, cf[k].level = capi.ptr(a["xy"], capi.c_float_p), capi.ptr(a["level"], capi.c_int32_p)
+        if it.get("pyramid") is not None:
+            cf[k].n_levels = len(it["pyramid"])
+            cf[k].pyramid = pyramid_images(list(it["pyramid"]), 0 if borders is None else int(borders[k]), a)
+            a["pyr"] = cf[k].pyramid
+        else:
+            cf[k].pyramid_token = int(it["token"])
+        o = dict(angle=np.zeros(n, np.float32), m10=np.zeros(n, np.int32), m01=np.zeros(n, np.int32))
+        _wire_outputs(cr[k], o)
+        keep.append(a)
+        outs.append(o)
+    return cf, cr, keep, outs
+
+
+def fast_cpu(frames, host_lib=None, borders=None):
+    """csrc/orb_fast.h on the host in one thread (osh_host_orb_fast_cpu of the test library): the per-frame dicts of
+    OrbMatcher.fast_detect (token 0) and the wall time of the loops in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    ms = C.c_double(0)
+    cf, cr, _keep, outs = fast_args(frames, [(0, 0)] * len(frames), borders)
+    if host_lib.osh_host_orb_fast_cpu(len(frames), cf, cr, None) != 0:
+        raise RuntimeError("osh_host_orb_fast_cpu refused the frames")
+    cf, cr, _keep, outs = fast_args(frames, [(cr[k].n_out, cr[k].n_cells) for k in range(len(frames))], borders)
+    rc = host_lib.osh_host_orb_fast_cpu(len(frames), cf, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_orb_fast_cpu -> {rc}")
+    return _fast_outputs(cr, outs), float(ms.value)
+
+
+def ic_angle_cpu(items, host_lib=None, borders=None):
+    """IC_Angle of csrc/orb_fast.h on the host in one thread (osh_host_orb_ic_angle_cpu); every item brings its pyramid."""
+    host_lib = host_lib or capi.load_host_library()
+    ms = C.c_double(0)
+    cf, cr, _keep, outs = ic_angle_args(items, borders)
+    rc = host_lib.osh_host_orb_ic_angle_cpu(len(items), cf, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_orb_ic_angle_cpu -> {rc}")
+    return outs, float(ms.value)
 
 
 def bow_tree(tree):
