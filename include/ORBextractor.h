@@ -1,7 +1,7 @@
 /* ORBextractor.h -- the members of ORB_SLAM3::ORBextractor that Frame::ComputeStereoMatches reads (mvImagePyramid, reference
- * include/ORBextractor.h:83) and that ORBextractor::ComputeKeyPointsOctTree (csrc/host/ORBextractor.cc) needs.  Minimal test double:
- * the constructor and DistributeOctTree live in csrc/hosttest/orbextractor.cc, and the pyramid, the blur and the descriptors
- * (ComputePyramid, operator()) are not part of this repository. */
+ * include/ORBextractor.h:83) and that ORBextractor::operator() and ORBextractor::ComputeKeyPointsOctTree (csrc/host/ORBextractor.cc)
+ * need.  Minimal test double: the constructor (with a generated sampling table of its own), ComputePyramid and DistributeOctTree
+ * live in csrc/hosttest/orbextractor.cc; the blur and the descriptors of operator() run on the device (osh_orb_describe). */
 #ifndef ORBEXTRACTOR_H
 #define ORBEXTRACTOR_H
 #include <vector>
@@ -11,12 +11,18 @@ class ORBextractor {
  public:
   ORBextractor() {}
   ORBextractor(int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST);
+  /* the reference's signature (include/ORBextractor.h:56); the mask is ignored there too */
+  int operator()(cv::InputArray _image, cv::InputArray _mask, std::vector<cv::KeyPoint>& _keypoints, cv::OutputArray _descriptors,
+                 std::vector<int>& vLappingArea);
   std::vector<cv::Mat> mvImagePyramid;
 
   /* protected in the reference; public here so that the test wrappers can call it */
+  void ComputePyramid(cv::Mat image);
   void ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint> >& allKeypoints);
   std::vector<cv::KeyPoint> DistributeOctTree(const std::vector<cv::KeyPoint>& vToDistributeKeys, const int& minX, const int& maxX,
                                               const int& minY, const int& maxY, const int& nFeatures, const int& level);
+
+  std::vector<cv::Point> pattern;   /* the 512 sampling points, filled by the constructor */
 
   int nfeatures = 0;
   double scaleFactor = 1.0;
@@ -28,6 +34,10 @@ class ORBextractor {
   std::vector<float> mvInvScaleFactor;
   std::vector<float> mvLevelSigma2;
   std::vector<float> mvInvLevelSigma2;
+
+  /* ADD THIS MEMBER to the reference's class: the token of the pyramid the last ComputeKeyPointsOctTree left on the device
+   * (0: none), which operator() hands to osh_orb_describe */
+  uint64_t mnPyramidToken = 0;
 
   /* test double only: every DistributeOctTree call of the last ComputeKeyPointsOctTree, as it was made */
   struct DistributeCall {

@@ -217,7 +217,11 @@ typedef std::map<unsigned int, double> BowVector;
 }  // namespace DBoW2
 
 namespace cv {
-struct Point2f { float x = 0, y = 0; };
+struct Point2f {
+  float x = 0, y = 0;
+  Point2f& operator*=(float s) { x *= s; y *= s; return *this; }
+};
+struct Point { int x = 0, y = 0; Point() {} Point(int x_, int y_) : x(x_), y(y_) {} };
 struct KeyPoint { Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1; };
 // Row-major byte matrix (CV_8U only: descriptor matrices N x 32 and the pyramid levels of an ORBextractor cross this boundary).
 // `step` is the row stride in bytes as in cv::Mat; it equals cols unless the matrix is a view() into a larger one, which is how the
@@ -234,12 +238,21 @@ class Mat {
   Mat row(int r) const { Mat m; m.rows = 1; m.cols = cols; m.step = step; m.buf_ = buf_; m.off_ = off_ + (size_t)r * step; return m; }
   // rows [r0, r0 + nr) x columns [c0, c0 + nc) of this matrix, sharing its storage (cv::Mat::operator()(Rect))
   Mat view(int r0, int c0, int nr, int nc) const { Mat m; m.rows = nr; m.cols = nc; m.step = step; m.buf_ = buf_; m.off_ = off_ + (size_t)r0 * step + c0; return m; }
+  // what ORBextractor::operator() asks of its InputArray / OutputArray arguments, which are Mat references here
+  void create(int r, int c, int /*type*/) { if (r != rows || c != cols || step != (size_t)c || !buf_) *this = Mat(r, c); }
+  void release() { *this = Mat(); }
+  Mat getMat() const { return *this; }   // shares the storage
   Mat clone() const { Mat m(rows, cols); for (int r = 0; r < rows; ++r) std::memcpy(m.buf_->data() + (size_t)r * cols, buf_->data() + off_ + (size_t)r * step, (size_t)cols); return m; }
  private:
   std::shared_ptr<std::vector<uint8_t>> buf_;
   size_t off_ = 0;
 };
+typedef const Mat& InputArray;
+typedef Mat& OutputArray;
 }  // namespace cv
+#ifndef CV_8U
+#define CV_8U 0
+#endif
 
 #ifndef EIGEN_MAKE_ALIGNED_OPERATOR_NEW
 #define EIGEN_MAKE_ALIGNED_OPERATOR_NEW

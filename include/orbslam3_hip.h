@@ -946,7 +946,8 @@ int osh_orb_newpoint_get_times(osh_orb_ctx* ctx, double ms[4]);
 /*
  * The integer part of ORBextractor::ComputeKeyPointsOctTree (src/ORBextractor.cc:781-896) for n_frames pyramids in one call: what
  * the loops over the cells of every level hand to DistributeOctTree (osh_orb_fast_detect), and IC_Angle (:76-103) for keypoints of
- * those levels (osh_orb_ic_angle).  The pyramid, DistributeOctTree, the blur and the descriptors stay with the caller.
+ * those levels (osh_orb_ic_angle).  The pyramid and DistributeOctTree stay with the caller; the blur and the descriptors are
+ * osh_orb_describe below.
  *
  * Cells (:785-822): minBorder = 16, maxBorderX = cols - 16, width = maxBorderX - 16, nCols = (int)(width / 35.f),
  * wCell = (int)ceil(width / nCols), cell (i, j) spans columns [16 + j * wCell, min(16 + j * wCell + wCell + 6, maxBorderX)), likewise
@@ -1024,6 +1025,60 @@ int osh_orb_ic_angle(osh_orb_ctx* ctx, int32_t n_frames, const osh_ic_angle_fram
  * scan and the emit), ms[3] download + write-back. */
 int osh_orb_fast_get_times(osh_orb_ctx* ctx, double ms[4]);
 int osh_orb_ic_angle_get_times(osh_orb_ctx* ctx, double ms[4]);
+
+/* ------------------------------------------------- blur and steered-BRIEF descriptors (ORBextractor) */
+/*
+ * What ORBextractor::operator() (src/ORBextractor.cc:1123-1165) runs per level after ComputeKeyPointsOctTree, for n_frames
+ * pyramids in one call: the 7x7 Gaussian blur of every level that holds a keypoint, and computeOrbDescriptor (:107-146) for every
+ * keypoint.  A frame names the pyramid an osh_orb_fast_detect of the same context left resident (pyramid == NULL, pyramid_token), or
+ * brings its own, exactly as in osh_ic_angle_frame.
+ *
+ * The sampling table is input data: 512 points, x and y interleaved, in the order of the reference's member
+ * std::vector<cv::Point> pattern (pattern[2 i] = pattern_[i].x, pattern[2 i + 1] = pattern_[i].y); every coordinate in [-15, 15].
+ * Its reach R = ceil(max sqrt(x^2 + y^2)) is the distance a sample can lie from the keypoint's pixel: 19 for the reference's table.
+ *
+ * Blur (defined here; OpenCV is not available to compare with, and what follows is recalled of its bit-exact 8-bit path, not
+ * verified): separable, Q8 weights w[0..6] that sum to 256, r(i, n) = -i for i < 0 and 2 (n - 1) - i for i >= n (reflect-101),
+ *   h(y, x) = sum_u w[u] * I(y, r(x + u - 3, cols))                        exact in 16 bits
+ *   B(y, x) = (sum_v w[v] * h(r(y + v - 3, rows), x) + 32768) >> 16        32 bits, one rounding
+ * blur_q8 == NULL selects 18 34 48 56 48 34 18: exp(-x^2 / 8) normalised, times 256, the first half rounded tap by tap with the
+ * rounding error carried on, mirrored, the centre taking what is left of 256.  A level with fewer than 4 rows or columns has no
+ * blur: it cannot hold a keypoint, and a frame with such a level cannot ask for `blurred`.
+ *
+ * Descriptor of keypoint (x, y, angle in degrees): rad = angle * (float)(pi / 180) in float32; a and b the float32 nearest to
+ * cos(rad) and sin(rad), taken through the FP64 functions of (double)rad (the reference calls the float overloads: the two differ
+ * only where cosf is not correctly rounded); centre (cvRound(y), cvRound(x)); for table point p the sample is
+ * B[cy + cvRound(p.x * b + p.y * a)][cx + cvRound(p.x * a - p.y * b)], the coordinates converted to float32, two float32 products
+ * and one float32 sum or difference, never fused, cvRound to nearest with halves to even; bit k of byte i is
+ * sample(16 i + 2 k) < sample(16 i + 2 k + 1).
+ *
+ * Refused with OSH_ERR_INVALID before any device work (and, for frames that bring their pyramid, without a context): everything
+ * osh_orb_ic_angle refuses about pyramids, tokens and counts; a NULL pattern; a table coordinate outside [-15, 15]; weights that do
+ * not sum to 256; a coordinate or angle that is not finite; a keypoint whose (2 R + 1)-square around its rounded centre leaves its
+ * level; NULL descriptors with n > 0.  With OSH_ERR_UNSUPPORTED: more than 2^24 keypoints in a call; `blurred` for a frame with a
+ * level of fewer than 4 rows or columns.  No kernel reads outside a level for input that passed.
+ */
+typedef struct osh_describe_frame {
+  int32_t n_levels;                  /* with a pyramid: its levels                                                          */
+  const osh_stereo_image* pyramid;   /* [n_levels], or NULL: the resident pyramid pyramid_token names                       */
+  uint64_t pyramid_token;
+  int32_t n;                         /* keypoints                                                                           */
+  const float* xy;                   /* [n*2] in the pixels of their level                                                  */
+  const int32_t* level;              /* [n]                                                                                 */
+  const float* angle;                /* [n] degrees                                                                         */
+  const int8_t* pattern;             /* [1024] the sampling table, x and y interleaved                                      */
+  const uint16_t* blur_q8;           /* [7] weights that sum to 256, or NULL: the default                                   */
+} osh_describe_frame;
+typedef struct osh_describe_result {
+  uint8_t* descriptors;      /* [n*32]                                                                                      */
+  float* cos_sin;            /* [n*2] a, b of every keypoint; may be NULL                                                   */
+  uint8_t* blurred;          /* the blurred levels of the frame in level order, rows*cols bytes each; may be NULL.  When
+                                given, every level is blurred, else only those that hold a keypoint                         */
+} osh_describe_result;
+int osh_orb_describe(osh_orb_ctx* ctx, int32_t n_frames, const osh_describe_frame* frames, const osh_describe_result* results);
+/* Host-clock phases (ms) of the last osh_orb_describe under osh_orb_set_profiling: ms[0] validation + staging, ms[1] upload,
+ * ms[2] kernels, ms[3] download + write-back. */
+int osh_orb_describe_get_times(osh_orb_ctx* ctx, double ms[4]);
 
 /* ------------------------------------------------- bag-of-words transform */
 /*

@@ -508,6 +508,53 @@ typedef struct osh_host_orbextractor_output {
  * first `capacity` keypoints and `cand_capacity` candidates).  -1: bad arguments, -2: the member left something inconsistent. */
 int osh_host_orbextractor_compute_keypoints(const osh_host_orbextractor_input* in, const osh_host_orbextractor_output* out);
 
+/* ---- ORBextractor::operator() (csrc/orb_brief.h, csrc/host/ORBextractor.cc, csrc/hosttest/orbextractor.cc) ---- */
+struct osh_describe_frame;
+struct osh_describe_result;
+/* csrc/orb_brief.h (the statements k_orb_blur and k_orb_brief run) compiled for the host, on one thread: arguments as
+ * osh_orb_describe without a context and without its validation (the frames must be valid and bring their pyramid).  *ms (may be
+ * NULL) = wall time of the loops.  -1: bad arguments. */
+int osh_host_orb_describe_cpu(int32_t n_frames, const struct osh_describe_frame* frames, const struct osh_describe_result* results, double* ms);
+/* brief_gaussian_q8 of csrc/orb_brief.h: the ksize (odd, at most 31) Q8 weights of sigma into out.  -1: bad arguments. */
+int osh_host_brief_gaussian_q8(int32_t ksize, double sigma, uint16_t* out);
+/* brief_reach of csrc/orb_brief.h for a table of 512 points. */
+int osh_host_brief_reach(const int8_t* pattern);
+/* The table the stand-in constructor generates (its own: 512 points in [-13, 12]^2 with radius at most 18.38) into pattern[1024]. */
+int osh_host_orbextractor_pattern(int8_t* pattern);
+
+/* ORBextractor(nfeatures, scale_factor, nlevels, ini_th, min_th)(image, mask, keypoints, descriptors, lapping_area) of the stand-in
+ * class on a rows x cols image (rows == 0: an empty image). */
+typedef struct osh_host_extract_input {
+  int32_t nfeatures;
+  float scale_factor;
+  int32_t nlevels, ini_th, min_th;
+  int32_t rows, cols;
+  const uint8_t* pixels;      /* rows packed */
+  int32_t lapping[2];         /* vLappingArea */
+} osh_host_extract_input;
+typedef struct osh_host_extract_output {
+  int32_t capacity;           /* keypoints the arrays below can take */
+  int32_t pixel_capacity;     /* bytes pyramid can take */
+  int32_t* level_rows;        /* [nlevels] the pyramid ComputePyramid built */
+  int32_t* level_cols;        /* [nlevels] */
+  uint8_t* pyramid;           /* its levels one after another, rows packed */
+  int32_t* level_count;       /* [nlevels] allKeypoints[level].size() of ComputeKeyPointsOctTree */
+  float* level_xy;            /* [capacity*2] allKeypoints level after level, in the pixels of their level */
+  float* level_angle;         /* [capacity] */
+  float* xy;                  /* [capacity*2] _keypoints */
+  float* angle;               /* [capacity] */
+  float* size;                /* [capacity] */
+  float* response;            /* [capacity] */
+  int32_t* octave;            /* [capacity] */
+  uint8_t* descriptors;       /* [capacity*32] _descriptors */
+  int32_t* ret;               /* the return value (monoIndex, -1 for an empty image) */
+  int32_t* desc_rows;         /* _descriptors.rows after the call (0: released) */
+  int32_t* pixels_needed;     /* bytes of the pyramid */
+  double* call_ms;            /* wall time of the operator() call alone; may be NULL */
+} osh_host_extract_output;
+/* Returns _keypoints.size() (the arrays are filled when it and the pyramid fit the capacities).  -1: bad arguments. */
+int osh_host_orbextractor_extract(const osh_host_extract_input* in, const osh_host_extract_output* out);
+
 /* ---- ORBVocabulary / ComputeBoW (include/ORBVocabulary.h, csrc/host/ORBVocabulary.cc, csrc/hosttest/bow.cc) ---- */
 struct osh_bow_tree;
 struct osh_bow_result;

@@ -401,6 +401,20 @@ class IcAngleResult(C.Structure):
     _fields_ = [("angle", c_float_p), ("m10", c_int32_p), ("m01", c_int32_p)]
 
 
+class DescribeFrame(C.Structure):
+    """``osh_describe_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n_levels", C.c_int32), ("pyramid", C.POINTER(StereoImage)), ("pyramid_token", C.c_uint64), ("n", C.c_int32),
+                ("xy", c_float_p), ("level", c_int32_p), ("angle", c_float_p), ("pattern", C.POINTER(C.c_int8)),
+                ("blur_q8", C.POINTER(C.c_uint16))]
+
+
+class DescribeResult(C.Structure):
+    """``osh_describe_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("descriptors", c_uint8_p), ("cos_sin", c_float_p), ("blurred", c_uint8_p)]
+
+
 OSH_FAST_MAX_SIDE = 32768
 OSH_FAST_AT_INI, OSH_FAST_AT_MIN, OSH_FAST_EMPTY = 0, 1, 2
 
@@ -513,6 +527,8 @@ _SIGNATURES = {
     "osh_orb_ic_angle": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult)]),
     "osh_orb_fast_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_ic_angle_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_describe": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(DescribeFrame), C.POINTER(DescribeResult)]),
+    "osh_orb_describe_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_bow_tree_check": (C.c_int, [C.POINTER(BowTree)]),
     "osh_bow_vocab_create": (C.c_int, [C.c_int, C.POINTER(BowTree), C.POINTER(C.c_void_p)]),
     "osh_bow_vocab_destroy": (None, [C.c_void_p]),
@@ -603,7 +619,29 @@ class HostOrbExtractorOutput(C.Structure):
                 ("features_per_level", c_int32_p), ("scale_factors", c_float_p)]
 
 
+class HostExtractInput(C.Structure):
+    """``osh_host_extract_input`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32), ("ini_th", C.c_int32),
+                ("min_th", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("pixels", c_uint8_p), ("lapping", C.c_int32 * 2)]
+
+
+class HostExtractOutput(C.Structure):
+    """``osh_host_extract_output`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("capacity", C.c_int32), ("pixel_capacity", C.c_int32), ("level_rows", c_int32_p), ("level_cols", c_int32_p),
+                ("pyramid", c_uint8_p), ("level_count", c_int32_p), ("level_xy", c_float_p), ("level_angle", c_float_p),
+                ("xy", c_float_p), ("angle", c_float_p), ("size", c_float_p), ("response", c_float_p), ("octave", c_int32_p),
+                ("descriptors", c_uint8_p), ("ret", c_int32_p), ("desc_rows", c_int32_p), ("pixels_needed", c_int32_p),
+                ("call_ms", c_double_p)]
+
+
 _HOST_SIGNATURES = {
+    "osh_host_orb_describe_cpu": (C.c_int, [C.c_int32, C.POINTER(DescribeFrame), C.POINTER(DescribeResult), c_double_p]),
+    "osh_host_brief_gaussian_q8": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_uint16)]),
+    "osh_host_brief_reach": (C.c_int, [C.POINTER(C.c_int8)]),
+    "osh_host_orbextractor_pattern": (C.c_int, [C.POINTER(C.c_int8)]),
+    "osh_host_orbextractor_extract": (C.c_int, [C.POINTER(HostExtractInput), C.POINTER(HostExtractOutput)]),
     "osh_host_orb_fast_cpu": (C.c_int, [C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult), c_double_p]),
     "osh_host_orb_ic_angle_cpu": (C.c_int, [C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult), c_double_p]),
     "osh_host_orb_fast_level_cells": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),

@@ -1,18 +1,29 @@
-// ORBextractor.cc -- ORBextractor::ComputeKeyPointsOctTree (reference src/ORBextractor.cc:781-896) on MI355X (host side).
+// ORBextractor.cc -- ORBextractor::ComputeKeyPointsOctTree (reference src/ORBextractor.cc:781-896) and ORBextractor::operator()
+// (:1086-1168) on MI355X (host side).
 //
 // The loops over the cells of every level (:787-872: cv::FAST at iniThFAST, again at minThFAST for a cell without corners) are ONE
 // osh_orb_fast_detect call for the whole pyramid (csrc/orb_fast_device.hip); DistributeOctTree stays the reference's and runs per
 // level on what the device returned, followed by the write-back of :880-890; computeOrientation of all levels (:893-895) is ONE
 // osh_orb_ic_angle call on the pyramid the detector left on the device.  In the integrator's tree the constructor, ComputePyramid,
-// DistributeOctTree and operator() stay the reference's; only this body replaces :781-896.
+// DistributeOctTree stay the reference's; these bodies replace :781-896 and :1086-1168.  ComputeKeyPointsOctTree leaves the
+// detector's pyramid token in the member mnPyramidToken.
+//
+// operator(): ComputePyramid, ComputeKeyPointsOctTree, then the per-level GaussianBlur and computeDescriptors of :1123-1140 as ONE
+// osh_orb_describe call for all levels (csrc/orb_brief_device.hip) on the pyramid the detector left on the device (or on
+// mvImagePyramid itself when there is no token), with the member `pattern` as the sampling table; the write-back of :1143-1164
+// follows on the host.
 //
 // Deviations from the reference, all intended:
 //   * a level with fewer than 35 columns or rows between its borders has no cells (the reference divides by zero there);
 //   * fastAtan2 is OpenCV's documented scalar form in unfused float32 operations (include/orbslam3_hip.h);
-//   * on a device error, or a pyramid the call refuses, a message goes to stderr and allKeypoints is empty at every level.
+//   * on a device error, or a pyramid the call refuses, a message goes to stderr and allKeypoints is empty at every level;
+//   * operator(): cos and sin of the keypoint angle through the FP64 functions, the sample offsets in unfused float32, the blur as
+//     include/orbslam3_hip.h defines it (parity with cv::GaussianBlur is not pinned); on a device error or a refused call a message
+//     goes to stderr and the result is no keypoints (return value 0, descriptors released).
 #include "ORBextractor.h"
 
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "orbslam3_hip.h"
@@ -24,6 +35,7 @@ osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
 void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint> >& allKeypoints) {
   allKeypoints.clear();
   allKeypoints.resize(nlevels);
+  mnPyramidToken = 0;
   if (nlevels <= 0) return;
   if ((int)mvImagePyramid.size() < nlevels) {
     std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: the pyramid has %d of %d levels\n", (int)mvImagePyramid.size(), nlevels);
@@ -98,6 +110,80 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
   n = 0;
   for (std::vector<cv::KeyPoint>& kps : allKeypoints)
     for (cv::KeyPoint& kp : kps) kp.angle = angle[n++];
+  mnPyramidToken = res.pyramid_token;
+}
+
+int ORBextractor::operator()(cv::InputArray _image, cv::InputArray /*_mask*/, std::vector<cv::KeyPoint>& _keypoints, cv::OutputArray _descriptors,
+                             std::vector<int>& vLappingArea) {
+  if (_image.empty()) return -1;
+  cv::Mat image = _image.getMat();
+  ComputePyramid(image);
+  std::vector<std::vector<cv::KeyPoint> > allKeypoints;
+  ComputeKeyPointsOctTree(allKeypoints);
+
+  int nkeypoints = 0;
+  for (int level = 0; level < nlevels; ++level) nkeypoints += (int)allKeypoints[level].size();
+
+  // blur and descriptors of all levels (:1131-1138) in one call, in allKeypoints order
+  std::vector<uint8_t> desc((size_t)nkeypoints * 32);
+  if (nkeypoints) {
+    bool ok = pattern.size() == 512 && (int)vLappingArea.size() >= 2;
+    if (!ok) std::fprintf(stderr, "ORBextractor::operator(): the pattern has %d of 512 points or vLappingArea fewer than 2 entries\n", (int)pattern.size());
+    osh_orb_ctx* ctx = ok ? HostMatcherContext() : nullptr;
+    if (ok && !ctx) { std::fprintf(stderr, "ORBextractor::operator(): %s\n", osh_last_error()); ok = false; }
+    if (ok) {
+      std::vector<float> pts((size_t)nkeypoints * 2), angle(nkeypoints);
+      std::vector<int32_t> lvl(nkeypoints);
+      int8_t table[1024];
+      for (int i = 0; i < 512; ++i) {
+        ok = ok && pattern[i].x >= -128 && pattern[i].x <= 127 && pattern[i].y >= -128 && pattern[i].y <= 127;
+        table[2 * i] = (int8_t)pattern[i].x; table[2 * i + 1] = (int8_t)pattern[i].y;
+      }
+      if (!ok) std::fprintf(stderr, "ORBextractor::operator(): a pattern point does not fit 8 bits\n");
+      size_t n = 0;
+      for (int l = 0; l < nlevels; ++l)
+        for (const cv::KeyPoint& kp : allKeypoints[l]) { pts[2 * n] = kp.pt.x; pts[2 * n + 1] = kp.pt.y; angle[n] = kp.angle; lvl[n] = l; ++n; }
+      std::vector<osh_stereo_image> pyramid(nlevels);
+      for (int level = 0; level < nlevels; ++level) {
+        const cv::Mat& im = mvImagePyramid[level];
+        pyramid[level].data = im.empty() ? nullptr : im.ptr<uint8_t>(0);
+        pyramid[level].rows = im.rows; pyramid[level].cols = im.cols; pyramid[level].stride = (int64_t)(size_t)im.step;
+      }
+      osh_describe_frame f{};
+      if (mnPyramidToken) f.pyramid_token = mnPyramidToken;
+      else { f.n_levels = nlevels; f.pyramid = pyramid.data(); }
+      f.n = nkeypoints; f.xy = pts.data(); f.level = lvl.data(); f.angle = angle.data(); f.pattern = table; f.blur_q8 = nullptr;
+      const osh_describe_result r{desc.data(), nullptr, nullptr};
+      if (ok && osh_orb_describe(ctx, 1, &f, &r) != OSH_OK) {
+        if (mnPyramidToken) {   // a stale token (another extractor used this thread's context in between): the pyramid itself
+          f.pyramid_token = 0; f.n_levels = nlevels; f.pyramid = pyramid.data();
+          ok = osh_orb_describe(ctx, 1, &f, &r) == OSH_OK;
+        } else ok = false;
+        if (!ok) std::fprintf(stderr, "ORBextractor::operator(): %s\n", osh_last_error());
+      }
+    }
+    if (!ok) { nkeypoints = 0; for (std::vector<cv::KeyPoint>& kps : allKeypoints) kps.clear(); }
+  }
+
+  cv::Mat descriptors;
+  if (nkeypoints == 0) _descriptors.release();
+  else { _descriptors.create(nkeypoints, 32, CV_8U); descriptors = _descriptors.getMat(); }
+  _keypoints = std::vector<cv::KeyPoint>(nkeypoints);
+
+  // :1120-1167: scale to level 0, keypoints of the lapping area from the back, the others from the front
+  int monoIndex = 0, stereoIndex = nkeypoints - 1;
+  size_t i = 0;
+  for (int level = 0; level < nlevels; ++level) {
+    const float scale = mvScaleFactor[level];
+    for (cv::KeyPoint& keypoint : allKeypoints[level]) {
+      if (level != 0) keypoint.pt *= scale;
+      const int at = keypoint.pt.x >= vLappingArea[0] && keypoint.pt.x <= vLappingArea[1] ? stereoIndex-- : monoIndex++;
+      _keypoints.at(at) = keypoint;
+      std::memcpy(descriptors.ptr<uint8_t>(at), &desc[32 * i], 32);
+      ++i;
+    }
+  }
+  return monoIndex;
 }
 
 }  // namespace ORB_SLAM3

@@ -1,8 +1,18 @@
 // orbextractor.cc -- what the stand-in ORB_SLAM3::ORBextractor (include/ORBextractor.h) needs around
-// ORBextractor::ComputeKeyPointsOctTree (csrc/host/ORBextractor.cc), and the C wrappers that drive it
-// (include/orbslam3_hip_host.h): the constructor (scale tables and mnFeaturesPerLevel as reference src/ORBextractor.cc:409-447), a
-// DistributeOctTree test double, osh_host_orbextractor_compute_keypoints, and csrc/orb_fast.h on the host in one thread
-// (osh_host_orb_fast_cpu, osh_host_orb_ic_angle_cpu: the CPU baseline of profiles/fast_timing.py; osh_host_orb_fast_level_cells).  Test library only.
+// ORBextractor::ComputeKeyPointsOctTree and ORBextractor::operator() (csrc/host/ORBextractor.cc), and the C wrappers that drive them
+// (include/orbslam3_hip_host.h): the constructor (scale tables and mnFeaturesPerLevel as reference src/ORBextractor.cc:409-447, and
+// a generated sampling table), a ComputePyramid and a DistributeOctTree test double, osh_host_orbextractor_compute_keypoints,
+// osh_host_orbextractor_extract, and csrc/orb_fast.h / csrc/orb_brief.h on the host in one thread (osh_host_orb_fast_cpu,
+// osh_host_orb_ic_angle_cpu, osh_host_orb_describe_cpu: the CPU baselines of profiles/fast_timing.py and profiles/brief_timing.py;
+// osh_host_orb_fast_level_cells).  Test library only.
+//
+// The sampling table is this file's own: 512 points drawn by a fixed linear congruential generator, uniformly in [-13, 12]^2 (so
+// the radius is at most sqrt(338) = 18.38), the first one set to (-13, -13) so that the reach is 19 as for the reference's table.
+//
+// The ComputePyramid here is written from the behaviour: level l has cvRound(size * mvInvScaleFactor[l]) pixels per side, is a view
+// into an image with a 19-pixel border, level 0 is a copy of the input and level l > 0 a bilinear resampling of level l - 1 at
+// pixel centres (float32, rounded to nearest); the border repeats the level by reflect-101 where the level is large enough and
+// by clamping otherwise.  Its pixels are its own and no test compares them with anything.
 //
 // The DistributeOctTree here is written from the behaviour, not taken from the reference: a quadtree over the level's detect area
 // that splits the nodes holding more than one keypoint until there are nFeatures nodes (or nothing left to split), the fullest
@@ -17,6 +27,7 @@
 #include <vector>
 
 #include "ORBextractor.h"
+#include "../orb_brief.h"
 #include "../orb_fast.h"
 #include "orbslam3_hip.h"
 #include "orbslam3_hip_host.h"
@@ -42,6 +53,45 @@ ORBextractor::ORBextractor(int _nfeatures, float _scaleFactor, int _nlevels, int
   int given = 0;
   for (int l = 0; l + 1 < nlevels; ++l, share *= q) given += mnFeaturesPerLevel[l] = (int)std::nearbyint(share);
   if (nlevels > 0) mnFeaturesPerLevel[nlevels - 1] = std::max(nfeatures - given, 0);
+  pattern.resize(512);
+  uint32_t state = 0x0b5e55edu;
+  for (cv::Point& p : pattern) {
+    state = state * 1664525u + 1013904223u; p.x = (int)((state >> 8) % 26u) - 13;
+    state = state * 1664525u + 1013904223u; p.y = (int)((state >> 8) % 26u) - 13;
+  }
+  pattern[0] = cv::Point(-13, -13);
+}
+
+void ORBextractor::ComputePyramid(cv::Mat image) {
+  constexpr int kEdge = 19;   // EDGE_THRESHOLD
+  mvImagePyramid.resize(nlevels);
+  for (int level = 0; level < nlevels; ++level) {
+    const float scale = mvInvScaleFactor[level];
+    const int w = osh::fast_cv_round((float)image.cols * scale), h = osh::fast_cv_round((float)image.rows * scale);
+    if (w <= 0 || h <= 0) { mvImagePyramid[level] = cv::Mat(); continue; }
+    cv::Mat whole(h + 2 * kEdge, w + 2 * kEdge);
+    cv::Mat lv = whole.view(kEdge, kEdge, h, w);
+    const cv::Mat& src = level ? mvImagePyramid[level - 1] : image;
+    if (src.empty()) { mvImagePyramid[level] = cv::Mat(); continue; }
+    for (int y = 0; y < h; ++y) {
+      const float fy = std::min(std::max(((float)y + 0.5f) * (float)src.rows / (float)h - 0.5f, 0.f), (float)(src.rows - 1));
+      const int y0 = (int)fy, y1 = std::min(y0 + 1, src.rows - 1);
+      const float ty = fy - (float)y0;
+      for (int x = 0; x < w; ++x) {
+        const float fx = std::min(std::max(((float)x + 0.5f) * (float)src.cols / (float)w - 0.5f, 0.f), (float)(src.cols - 1));
+        const int x0 = (int)fx, x1 = std::min(x0 + 1, src.cols - 1);
+        const float tx = fx - (float)x0;
+        const float top = (float)src.ptr<uint8_t>(y0)[x0] * (1.f - tx) + (float)src.ptr<uint8_t>(y0)[x1] * tx;
+        const float bot = (float)src.ptr<uint8_t>(y1)[x0] * (1.f - tx) + (float)src.ptr<uint8_t>(y1)[x1] * tx;
+        lv.ptr<uint8_t>(y)[x] = (uint8_t)std::min(std::max((int)std::nearbyint(top * (1.f - ty) + bot * ty), 0), 255);
+      }
+    }
+    auto mirror = [](int i, int n) { return n > kEdge ? osh::brief_reflect101(i, n) : std::min(std::max(i, 0), n - 1); };
+    for (int y = -kEdge; y < h + kEdge; ++y)
+      for (int x = -kEdge; x < w + kEdge; ++x)
+        if (y < 0 || y >= h || x < 0 || x >= w) whole.ptr<uint8_t>(y + kEdge)[x + kEdge] = lv.ptr<uint8_t>(mirror(y, h))[mirror(x, w)];
+    mvImagePyramid[level] = lv;
+  }
 }
 
 namespace {
@@ -221,4 +271,111 @@ extern "C" int osh_host_orbextractor_compute_keypoints(const osh_host_orbextract
     }
   }
   return (int)n;
+}
+
+extern "C" int osh_host_orb_describe_cpu(int32_t n_frames, const osh_describe_frame* frames, const osh_describe_result* results, double* ms) {
+  if (n_frames < 0 || (n_frames && (!frames || !results))) return -1;
+  uint16_t default_w[osh::kBriefTaps];
+  osh::brief_gaussian_q8(osh::kBriefTaps, 2.0, default_w);
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_describe_frame& f = frames[k];
+    const osh_describe_result& r = results[k];
+    if (!f.pyramid || !f.pattern || (f.n && (!f.xy || !f.level || !f.angle || !r.descriptors))) return -1;
+    const uint16_t* w = f.blur_q8 ? f.blur_q8 : default_w;
+    std::vector<std::vector<uint8_t> > blurred(f.n_levels);
+    std::vector<bool> wanted(f.n_levels, r.blurred != nullptr);
+    for (int i = 0; i < f.n; ++i) wanted[f.level[i]] = true;
+    size_t off = 0;
+    for (int l = 0; l < f.n_levels; ++l) {
+      const osh_stereo_image& im = f.pyramid[l];
+      const size_t bytes = (size_t)im.rows * im.cols;
+      if (wanted[l]) {
+        if (im.rows < osh::kBriefMinSide || im.cols < osh::kBriefMinSide) return -1;
+        blurred[l].resize(bytes);
+        osh::brief_blur_level_host(im.data, im.rows, im.cols, (long long)im.stride, w, blurred[l].data());
+        if (r.blurred) std::memcpy(r.blurred + off, blurred[l].data(), bytes);
+      }
+      off += bytes;
+    }
+    for (int i = 0; i < f.n; ++i) {
+      const int l = f.level[i];
+      const osh::BriefRot rot = osh::brief_descriptor_host(blurred[l].data(), (long long)f.pyramid[l].cols, f.xy[2 * i], f.xy[2 * i + 1], f.angle[i], f.pattern,
+                                                           r.descriptors + 32 * (size_t)i);
+      if (r.cos_sin) { r.cos_sin[2 * i] = rot.a; r.cos_sin[2 * i + 1] = rot.b; }
+    }
+  }
+  if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+extern "C" int osh_host_brief_gaussian_q8(int32_t ksize, double sigma, uint16_t* out) {
+  if (ksize < 1 || ksize > 31 || !(ksize & 1) || !(sigma > 0) || !out) return -1;
+  osh::brief_gaussian_q8(ksize, sigma, out);
+  return 0;
+}
+
+extern "C" int osh_host_brief_reach(const int8_t* pattern) { return pattern ? osh::brief_reach(pattern) : -1; }
+
+extern "C" int osh_host_orbextractor_pattern(int8_t* pattern) {
+  if (!pattern) return -1;
+  const ORBextractor ex(1, 1.2f, 1, 20, 7);
+  for (int i = 0; i < 512; ++i) { pattern[2 * i] = (int8_t)ex.pattern[i].x; pattern[2 * i + 1] = (int8_t)ex.pattern[i].y; }
+  return 0;
+}
+
+extern "C" int osh_host_orbextractor_extract(const osh_host_extract_input* in, const osh_host_extract_output* out) {
+  if (!in || !out || in->nlevels < 1 || in->rows < 0 || in->cols < 0 || (in->rows && in->cols && !in->pixels) || !out->level_rows || !out->level_cols ||
+      !out->level_count || !out->ret || !out->desc_rows || !out->pixels_needed || out->capacity < 0 || out->pixel_capacity < 0) return -1;
+  ORBextractor ex(in->nfeatures, in->scale_factor, in->nlevels, in->ini_th, in->min_th);
+  cv::Mat image;
+  if (in->rows && in->cols) {
+    image = cv::Mat(in->rows, in->cols);
+    std::memcpy(image.ptr<uint8_t>(0), in->pixels, (size_t)in->rows * in->cols);
+  }
+  std::vector<int> lapping{in->lapping[0], in->lapping[1]};
+  // the stages on their own first: what operator() computes inside is a function of the image alone
+  std::vector<std::vector<cv::KeyPoint> > all(in->nlevels);
+  size_t pixels = 0;
+  if (!image.empty()) {
+    ex.ComputePyramid(image);
+    ex.ComputeKeyPointsOctTree(all);
+    if ((int)all.size() != in->nlevels) return -1;
+  }
+  for (int l = 0; l < in->nlevels; ++l) {
+    const cv::Mat& im = image.empty() ? image : ex.mvImagePyramid[l];
+    out->level_rows[l] = im.rows; out->level_cols[l] = im.cols;
+    if (out->pyramid && pixels + (size_t)im.rows * im.cols <= (size_t)out->pixel_capacity)
+      for (int r = 0; r < im.rows; ++r) std::memcpy(out->pyramid + pixels + (size_t)r * im.cols, im.ptr<uint8_t>(r), (size_t)im.cols);
+    pixels += (size_t)im.rows * im.cols;
+  }
+  *out->pixels_needed = (int32_t)pixels;
+  size_t n = 0;
+  for (int l = 0; l < in->nlevels; ++l) {
+    out->level_count[l] = (int32_t)all[l].size();
+    for (const cv::KeyPoint& kp : all[l]) {
+      if (n < (size_t)out->capacity) {
+        if (out->level_xy) { out->level_xy[2 * n] = kp.pt.x; out->level_xy[2 * n + 1] = kp.pt.y; }
+        if (out->level_angle) out->level_angle[n] = kp.angle;
+      }
+      ++n;
+    }
+  }
+  std::vector<cv::KeyPoint> keys(3);   // what the call must replace
+  cv::Mat desc(2, 32);
+  const auto t0 = std::chrono::steady_clock::now();
+  *out->ret = ex(image, cv::Mat(), keys, desc, lapping);
+  if (out->call_ms) *out->call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  *out->desc_rows = desc.rows;
+  if (*out->ret < 0) return 0;   // an empty image: nothing was touched
+  if (!keys.empty() && (desc.rows != (int)keys.size() || desc.cols != 32)) return -1;
+  for (size_t i = 0; i < keys.size() && i < (size_t)out->capacity; ++i) {
+    if (out->xy) { out->xy[2 * i] = keys[i].pt.x; out->xy[2 * i + 1] = keys[i].pt.y; }
+    if (out->angle) out->angle[i] = keys[i].angle;
+    if (out->size) out->size[i] = keys[i].size;
+    if (out->response) out->response[i] = keys[i].response;
+    if (out->octave) out->octave[i] = keys[i].octave;
+    if (out->descriptors) std::memcpy(out->descriptors + 32 * i, desc.ptr<uint8_t>((int)i), 32);
+  }
+  return (int)keys.size();
 }

@@ -15,6 +15,7 @@
 // osh_orb_ic_angle: k_ic_angle, one keypoint per lane, reads its 31-pixel disc from the packed level.
 #include "common.h"
 #include "orb_fast.h"
+#include "orb_fast_state.h"
 #include "orb_stage.h"
 #include <atomic>
 #include <cmath>
@@ -181,34 +182,7 @@ __global__ __launch_bounds__(kIcBlock) void k_ic_angle(IcView v) {
   v.angle[i] = fast_atan2((float)m01, (float)m10);
 }
 
-struct FastLevelHost { long long img_off; int rows, cols, cell0, n_cells; };
-struct FastFrameHost { int level0, n_levels, cell0, n_cells; };   // level0 / cell0: first entry of the frame in the call's lists
-
-struct FastState {
-  StagedCall call;              // detect: [cells | order | images] in, [count | offset | used_min] out, mask as work
-  DevBuf emitted;               // xy, response, level, cell of the call
-  PinBuf h_emitted;
-  StagedCall ic_call;           // ic_angle: keypoints (and the pyramid, when the caller hands one over)
-  // the resident pyramid of the last detect
-  uint64_t token0 = 0;          // token of its frame 0; 0: none
-  std::vector<FastFrameHost> frames;
-  std::vector<FastLevelHost> levels;
-  size_t img_off = 0;           // of the image section in call's in region
-  double ms[4] = {0, 0, 0, 0}, ms_ic[4] = {0, 0, 0, 0};
-};
-
 static std::atomic<uint64_t> g_next_token{1};
-
-static int fast_validate_pyramid(const char* entry, int k, int n_levels, const osh_stereo_image* pyr) {
-  if (n_levels < 1 || n_levels > OSH_STEREO_MAX_LEVELS) { set_error("%s: frame %d: n_levels %d outside [1, %d]", entry, k, n_levels, OSH_STEREO_MAX_LEVELS); return OSH_ERR_INVALID; }
-  if (!pyr) { set_error("%s: frame %d: NULL pyramid", entry, k); return OSH_ERR_INVALID; }
-  for (int l = 0; l < n_levels; ++l) {
-    const osh_stereo_image& im = pyr[l];
-    if (!im.data || im.rows <= 0 || im.cols <= 0 || im.stride < im.cols) { set_error("%s: frame %d: level %d is NULL, empty or has stride < cols", entry, k, l); return OSH_ERR_INVALID; }
-    if (im.rows > OSH_FAST_MAX_SIDE || im.cols > OSH_FAST_MAX_SIDE) { set_error("%s: frame %d: level %d exceeds %d pixels in one direction", entry, k, l, OSH_FAST_MAX_SIDE); return OSH_ERR_UNSUPPORTED; }
-  }
-  return OSH_OK;
-}
 
 static int fast_validate(int n_frames, const osh_fast_frame* frames, const osh_fast_result* results) {
   for (int k = 0; k < n_frames; ++k) {

@@ -158,6 +158,7 @@ class OrbMatcher:
     newpoint_times = functools.partialmethod(_times, "osh_orb_newpoint_get_times")               # of the last triangulate_new_points
     fast_times = functools.partialmethod(_times, "osh_orb_fast_get_times")                       # of the last fast_detect
     ic_angle_times = functools.partialmethod(_times, "osh_orb_ic_angle_get_times")               # of the last ic_angle
+    describe_times = functools.partialmethod(_times, "osh_orb_describe_get_times")               # of the last describe
     bow_times = functools.partialmethod(_times, "osh_orb_bow_get_times")                         # of the last bow_transform
     bow_db_times = functools.partialmethod(_times, "osh_orb_bow_db_get_times")                   # of the last bow_db_query
 
@@ -212,6 +213,18 @@ class OrbMatcher:
         cf, cr, _keep, outs = ic_angle_args(items, borders)
         capi.check(self.lib.osh_orb_ic_angle(self.ctx, len(items), cf, cr), "osh_orb_ic_angle", self.lib)
         return outs
+
+    def describe(self, items, borders=None, debug: bool = False) -> list:
+        """The blur and the steered-BRIEF descriptors of ORBextractor::operator() (src/ORBextractor.cc:1123-1165) for a batch of
+        items dict(xy, level, angle, pattern [512, 2] int8, pyramid or token, optionally blur_q8 [7]) in one osh_orb_describe call:
+        per item a dict with descriptors [n, 32], and with `debug` also cos_sin [n, 2] and blurred (the blurred levels as a list;
+        an item by token then names its level shapes under `shapes`)."""
+        cf, cr, _keep, outs = describe_args(items, borders, debug)
+        capi.check(self.lib.osh_orb_describe(self.ctx, len(items), cf, cr), "osh_orb_describe", self.lib)
+        return _describe_outputs(outs)
+
+    describe_cpu = staticmethod(lambda items, borders=None, debug=False: describe_cpu(items, borders=borders, debug=debug))
+    extract = staticmethod(lambda image, **kw: extract(image, **kw))
 
     def kb8_triangulate(self, rig: "capi.Kb8Rig", xy1, xy2, sigma1, sigma2) -> dict:
         """KannalaBrandt8::TriangulateMatches for explicit keypoint pairs (osh_kb8_triangulate): ret [n], p3d [n, 3], cos_parallax [n]."""
@@ -468,6 +481,142 @@ def ic_angle_cpu(items, host_lib=None, borders=None):
     if rc != 0:
         raise RuntimeError(f"osh_host_orb_ic_angle_cpu -> {rc}")
     return outs, float(ms.value)
+
+
+_POINTER[np.dtype(np.int8)] = C.POINTER(C.c_int8)
+_POINTER[np.dtype(np.uint16)] = C.POINTER(C.c_uint16)
+
+
+def describe_args(items, borders=None, debug: bool = False):
+    """The osh_describe_frame / osh_describe_result arrays for items dict(xy [n, 2], level [n], angle [n], pattern [512, 2], and
+    pyramid (a list of levels) or token with shapes (the level shapes, needed only for `debug`), optionally blur_q8 [7])."""
+    n_items = len(items)
+    cf = (capi.DescribeFrame * max(n_items, 1))()
+    cr = (capi.DescribeResult * max(n_items, 1))()
+    keep, outs = [], []
+    for k, it in enumerate(items):
+        a = dict(xy=np.ascontiguousarray(it["xy"], np.float32).reshape(-1, 2), level=np.ascontiguousarray(it["level"], np.int32),
+                 angle=np.ascontiguousarray(it["angle"], np.float32))
+        n = cf[k].n = a["level"].shape[0]
+        for name in ("xy", "level", "angle"):
+            setattr(cf[k], name, capi.ptr(a[name], _POINTER[a[name].dtype]))
+        if it.get("pattern") is not None:
+            a["pattern"] = np.ascontiguousarray(it["pattern"], np.int8).reshape(-1)
+            assert a["pattern"].shape[0] == 1024
+            cf[k].pattern = capi.ptr(a["pattern"], _POINTER[a["pattern"].dtype])
+        if it.get("blur_q8") is not None:
+            a["blur_q8"] = np.ascontiguousarray(it["blur_q8"], np.uint16).reshape(-1)
+            assert a["blur_q8"].shape[0] == 7
+            cf[k].blur_q8 = capi.ptr(a["blur_q8"], _POINTER[a["blur_q8"].dtype])
+        if it.get("pyramid") is not None:
+            cf[k].n_levels = len(it["pyramid"])
+            cf[k].pyramid = pyramid_images(list(it["pyramid"]), 0 if borders is None else int(borders[k]), a)
+            a["pyr"] = cf[k].pyramid
+            shapes = [(0, 0) if p is None else tuple(p.shape) for p in it["pyramid"]]
+        else:
+            cf[k].pyramid_token = int(it["token"])
+            shapes = [tuple(s) for s in it.get("shapes", ())]
+        o = dict(descriptors=np.zeros((n, 32), np.uint8))
+        if debug:
+            o.update(cos_sin=np.zeros((n, 2), np.float32), blurred=np.zeros(max(sum(r * c for r, c in shapes), 1), np.uint8))
+        _wire_outputs(cr[k], o)
+        o["shapes"] = shapes
+        keep.append(a)
+        outs.append(o)
+    return cf, cr, keep, outs
+
+
+def _describe_outputs(outs):
+    """`blurred` cut into the levels of the item."""
+    res = []
+    for o in outs:
+        d = {k: v for k, v in o.items() if k != "shapes"}
+        if "blurred" in d:
+            flat, d["blurred"], off = d["blurred"], [], 0
+            for r, c in o["shapes"]:
+                d["blurred"].append(flat[off:off + r * c].reshape(r, c))
+                off += r * c
+        res.append(d)
+    return res
+
+
+def describe_cpu(items, host_lib=None, borders=None, debug: bool = False):
+    """csrc/orb_brief.h on the host in one thread (osh_host_orb_describe_cpu of the test library); every item brings its pyramid.
+    Returns the per-item dicts of OrbMatcher.describe and the wall time of the loops in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    ms = C.c_double(0)
+    cf, cr, _keep, outs = describe_args(items, borders, debug)
+    rc = host_lib.osh_host_orb_describe_cpu(len(items), cf, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_orb_describe_cpu -> {rc}")
+    return _describe_outputs(outs), float(ms.value)
+
+
+def brief_gaussian_q8(ksize: int = 7, sigma: float = 2.0, host_lib=None) -> np.ndarray:
+    """brief_gaussian_q8 of csrc/orb_brief.h: the default blur weights for (7, 2)."""
+    host_lib = host_lib or capi.load_host_library()
+    out = np.zeros(int(ksize), np.uint16)
+    if host_lib.osh_host_brief_gaussian_q8(int(ksize), float(sigma), capi.ptr(out, _POINTER[out.dtype])) != 0:
+        raise RuntimeError("osh_host_brief_gaussian_q8 refused its arguments")
+    return out
+
+
+def brief_reach(pattern, host_lib=None) -> int:
+    """brief_reach of csrc/orb_brief.h: ceil of the largest radius of a table [512, 2]."""
+    host_lib = host_lib or capi.load_host_library()
+    p = np.ascontiguousarray(pattern, np.int8).reshape(-1)
+    assert p.shape[0] == 1024
+    return int(host_lib.osh_host_brief_reach(capi.ptr(p, _POINTER[p.dtype])))
+
+
+def standin_pattern(host_lib=None) -> np.ndarray:
+    """The sampling table [512, 2] the stand-in ORBextractor constructor generates."""
+    host_lib = host_lib or capi.load_host_library()
+    p = np.zeros(1024, np.int8)
+    if host_lib.osh_host_orbextractor_pattern(capi.ptr(p, _POINTER[p.dtype])) != 0:
+        raise RuntimeError("osh_host_orbextractor_pattern failed")
+    return p.reshape(512, 2)
+
+
+def extract(image, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, lapping=(0, 0), host_lib=None) -> dict:
+    """ORBextractor::operator() of the stand-in class on a uint8 image (None or an empty array: an empty image) through
+    osh_host_orbextractor_extract: ret, desc_rows, the pyramid ComputePyramid built (a list of levels), the per-level keypoints of
+    ComputeKeyPointsOctTree (level_count, level_xy, level_angle) and _keypoints (xy, angle, size, response, octave) with
+    descriptors [n, 32]; call_ms is the wall time of the operator() call alone."""
+    host_lib = host_lib or capi.load_host_library()
+    img = np.zeros((0, 0), np.uint8) if image is None else np.ascontiguousarray(image, np.uint8)
+    cin = capi.HostExtractInput()
+    cin.nfeatures, cin.scale_factor, cin.nlevels, cin.ini_th, cin.min_th = int(nfeatures), float(scale_factor), int(nlevels), int(ini_th), int(min_th)
+    cin.rows, cin.cols = (img.shape if img.size else (0, 0))
+    cin.pixels = capi.ptr(img if img.size else None, capi.c_uint8_p)
+    cin.lapping[0], cin.lapping[1] = int(lapping[0]), int(lapping[1])
+    cap = pix = 0
+    for _ in range(2):   # the first pass counts
+        o = dict(level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), pyramid=np.zeros(max(pix, 1), np.uint8),
+                 level_count=np.zeros(nlevels, np.int32), level_xy=np.zeros((cap, 2), np.float32), level_angle=np.zeros(cap, np.float32),
+                 xy=np.zeros((cap, 2), np.float32), angle=np.zeros(cap, np.float32), size=np.zeros(cap, np.float32),
+                 response=np.zeros(cap, np.float32), octave=np.zeros(cap, np.int32), descriptors=np.zeros((cap, 32), np.uint8),
+                 ret=np.zeros(1, np.int32), desc_rows=np.zeros(1, np.int32), pixels_needed=np.zeros(1, np.int32), call_ms=np.zeros(1, np.float64))
+        cout = capi.HostExtractOutput()
+        cout.capacity, cout.pixel_capacity = cap, pix
+        _wire_outputs(cout, o)
+        n = host_lib.osh_host_orbextractor_extract(C.byref(cin), C.byref(cout))
+        if n < 0:
+            raise RuntimeError(f"osh_host_orbextractor_extract returned {n}")
+        need = max(n, int(o["level_count"].sum()))
+        if need <= cap and int(o["pixels_needed"][0]) <= pix:
+            break
+        cap, pix = need, int(o["pixels_needed"][0])
+    nl = int(o["level_count"].sum())
+    out = dict(ret=int(o["ret"][0]), desc_rows=int(o["desc_rows"][0]), call_ms=float(o["call_ms"][0]), n=n, level_count=o["level_count"], level_xy=o["level_xy"][:nl],
+               level_angle=o["level_angle"][:nl])
+    for name in ("xy", "angle", "size", "response", "octave", "descriptors"):
+        out[name] = o[name][:n]
+    out["pyramid"], off = [], 0
+    for r, c in zip(o["level_rows"].tolist(), o["level_cols"].tolist()):
+        out["pyramid"].append(o["pyramid"][off:off + r * c].reshape(r, c).copy())
+        off += r * c
+    return out
 
 
 def bow_tree(tree):
