@@ -895,13 +895,90 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
 
 // --------------------------------------------------------------------------------------------
 // k_schur_reduce: S(i,j) = [i == j] (Hpp_i + lambda I) - sum of the block's contributions,
-// b_s(i) = b_p(i) - sum of the pose's rhs contributions; 7 blocks of S per 256-thread group,
-// one thread per entry, contributions in plan order.
+// b_s(i) = b_p(i) - sum of the pose's rhs contributions; every entry by one thread, contributions in plan order.
 // --------------------------------------------------------------------------------------------
-// DEEP: 24 contributions in flight where a block has that many -- a call with few windows cuts its Schur items small (item_max_lm) and
-// has four times as many contributions per block; in a large batch (about six per block) the extra registers only cost (0.315 -> 0.33 ms).
-template <bool DEEP>
+// k_schur_reduce (calls of more than 8 windows, about six contributions per block).  With one thread per entry a lane reads 8 bytes
+// per load, and 8-byte loads stream at 0.54-0.70 of the rate of 16-byte ones: that kernel ran at 4.0 of 6.3 TB/s however many loads
+// it kept in flight.  Here a lane owns two neighbouring entries of a block (18 lanes per block, 14 blocks per 256 threads, 16-byte
+// loads and stores, two sums side by side).  The envelope, the initial value and the first eight contributions are requested before
+// one wait; the loads a block does not have are skipped (immediate offsets from one address: a load costs its compare and itself; the
+// wait that follows a load a lane may skip is a wait for every load of the wavefront, so everything the block needs from its RBlk
+// entry and its window is worked out before the first of them).  Every entry is still v = init; v -= c_0; v -= c_1; ... in plan
+// order by one thread.  Several blocks per 18-lane group (RBlk entries and window state requested together) only cost wavefronts
+// per CU: DESIGN.md section 4.
+
+// contributions k .. k + 7 of a block of n, as far as it has them: this lane's two entries of each
+__device__ __forceinline__ void reduce_load8(double2* t, const double* c, int k, int n) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u)
+    if (k + u < n) t[u] = *reinterpret_cast<const double2*>(c + (size_t)k * 36 + u * 36);
+}
+
 __global__ __launch_bounds__(256) void k_schur_reduce(BatchView bv) {
+  const int t = threadIdx.x / 18, e = threadIdx.x - 18 * t;
+  const int idx = blockIdx.x * 14 + t;
+  if (t >= 14 || idx >= bv.n_rblk) return;
+  const int r = e / 3, cc = 2 * (e - 3 * r);   // entries (r, cc) and (r, cc + 1) of the block: 16 bytes, 16-byte aligned in every array
+  // No early exit below: one would let the compiler put the loads behind it, one round trip after the other.  What the lane has to
+  // do is kept as indices, -1: nothing.
+  const RBlk rb = bv.rblk[idx];
+  const WinDesc& wd = bv.win[rb.win];
+  const LmState& st = bv.lm[rb.win];
+  const int fpose_off = wd.fpose_off, n = wd.n;
+  const long long S_off = wd.S_off;
+  const double lambda = st.lambda;
+  const bool live = st.active != 0;
+  const int i = rb.ij & 0xffff, j = (rb.ij >> 16) & 0xffff;
+  const bool rhs = j == 0xffff;
+  const long long gp = (long long)fpose_off + i;
+  const int cnt = live && !rhs ? rb.count : 0;
+  const long long off = (long long)rb.start * 36 + 2 * e;                                                   // the block's first contribution
+  const long long src = live && i == j ? gp * 36 + 2 * e : -1;                                              // a diagonal block: its entries of Hpp
+  const long long dst = live && !rhs ? S_off + (long long)(6 * i + r) * n + 6 * j + cc : -1;                // where the entries go in S
+  const long long seg = live && rhs && e < 3 ? gp * 6 + 2 * e : -1;                                         // a rhs segment: its entries of b_p and b_s
+  // the block column's entry of pose_lo, read by every lane (a lane that may skip it would wait for it on the spot: the compiler
+  // moves the comparison to the load); without an envelope any int of an optimisable pose, not looked at
+  const int lo = (bv.pose_lo ? bv.pose_lo : bv.fpose_win)[live && !rhs ? fpose_off + j : 0];
+  double2 init{0.0, 0.0}, tt[8];
+  if (src >= 0) init = *reinterpret_cast<const double2*>(bv.Hpp + src);
+  reduce_load8(tt, bv.contrib + off, 0, cnt);
+  __builtin_amdgcn_sched_barrier(0);
+  double ax = 0.0, ay = 0.0;
+  if (src >= 0) { ax = init.x + ((r == cc) ? lambda : 0.0); ay = init.y + ((r == cc + 1) ? lambda : 0.0); }
+#pragma unroll
+  for (int u = 0; u < 8; ++u)
+    if (u < cnt) { ax -= tt[u].x; ay -= tt[u].y; }
+  for (int k = 8; k < cnt; k += 8) {   // a block with more than eight contributions: eight more in flight at a time
+    double2 more[8];
+    reduce_load8(more, bv.contrib + off, k, cnt);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (k + u < cnt) { ax -= more[u].x; ay -= more[u].y; }
+  }
+  // A block above the column envelope of S (no landmark joins keyframe i to j or to any keyframe before i, k_schur_env) is zero, is
+  // never touched by the envelope factorisation of k_solve and was zeroed at upload: nothing to write (it has no contributions either).
+  if (dst >= 0 && (!bv.pose_lo || i >= lo)) *reinterpret_cast<double2*>(bv.S + dst) = double2{ax, ay};
+  if (seg >= 0) {   // a rhs segment (P of a window's P (P + 1) / 2 + P entries): three lanes, eight contributions in flight
+    double2 a = *reinterpret_cast<const double2*>(bv.bp + seg);
+    const double* c = bv.ccontrib + (size_t)rb.start * 6 + 2 * e;
+    int k = 0;
+    for (; k + 8 <= rb.count; k += 8) {
+      double2 t8[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t8[u] = *reinterpret_cast<const double2*>(c + (size_t)(k + u) * 6);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { a.x -= t8[u].x; a.y -= t8[u].y; }
+    }
+    for (; k < rb.count; ++k) { const double2 t1 = *reinterpret_cast<const double2*>(c + (size_t)k * 6); a.x -= t1.x; a.y -= t1.y; }
+    *reinterpret_cast<double2*>(bv.bs + seg) = a;
+  }
+}
+
+// k_schur_reduce_deep (calls of at most 8 windows): one block of S per 36-lane group, 24 contributions in flight where a block has
+// that many -- a call with few windows cuts its Schur items small (item_max_lm) and has four times as many contributions per block.
+__global__ __launch_bounds__(256) void k_schur_reduce_deep(BatchView bv) {
   const int t = threadIdx.x / 36, el = threadIdx.x - 36 * t;
   const int idx = blockIdx.x * 7 + t;
   if (t >= 7 || idx >= bv.n_rblk) return;
@@ -916,15 +993,13 @@ __global__ __launch_bounds__(256) void k_schur_reduce(BatchView bv) {
     double v = bv.bp[gp * 6 + el];
     const double* c = bv.ccontrib + (size_t)rb.start * 6 + el;
     int k = 0;
-    if constexpr (DEEP) {
-      for (; k + 24 <= rb.count; k += 24) {
-        double t[24];
+    for (; k + 24 <= rb.count; k += 24) {
+      double t[24];
 #pragma unroll
-        for (int u = 0; u < 24; ++u) t[u] = c[(size_t)(k + u) * 6];
-        __builtin_amdgcn_sched_barrier(0);
+      for (int u = 0; u < 24; ++u) t[u] = c[(size_t)(k + u) * 6];
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int u = 0; u < 24; ++u) v -= t[u];
-      }
+      for (int u = 0; u < 24; ++u) v -= t[u];
     }
     for (; k + 8 <= rb.count; k += 8) {
       double t[8];
@@ -946,15 +1021,13 @@ __global__ __launch_bounds__(256) void k_schur_reduce(BatchView bv) {
   if (i == j) v = bv.Hpp[((size_t)wd.fpose_off + i) * 36 + el] + ((r == cc) ? st.lambda : 0.0);
   const double* c = bv.contrib + (size_t)rb.start * 36 + el;
   int k = 0;
-  if constexpr (DEEP) {
-    for (; k + 24 <= rb.count; k += 24) {
-      double t[24];
+  for (; k + 24 <= rb.count; k += 24) {
+    double t[24];
 #pragma unroll
-      for (int u = 0; u < 24; ++u) t[u] = c[(size_t)(k + u) * 36];
-      __builtin_amdgcn_sched_barrier(0);
+    for (int u = 0; u < 24; ++u) t[u] = c[(size_t)(k + u) * 36];
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int u = 0; u < 24; ++u) v -= t[u];
-    }
+    for (int u = 0; u < 24; ++u) v -= t[u];
   }
   for (; k + 8 <= rb.count; k += 8) {   // eight contributions in flight (one load per iteration left every memory round trip exposed),
     double t[8];                        // subtracted in plan order: the sum is the same number as before
@@ -1842,6 +1915,15 @@ static int first_linearisation(osh_lba_ctx* c) {
   return OSH_OK;
 }
 
+// S and b_s of every active window from the contributions of the trial's Schur items.
+static int launch_schur_reduce(osh_lba_ctx* c) {
+  hipStream_t s = c->stream;
+  const int n = (int)c->pb.n_rblk;
+  if (c->n_windows <= 8) { LAUNCH(OSH_K_SCHUR_REDUCE, k_schur_reduce_deep, (n + 6) / 7, 256, 0, c->bv); }
+  else { LAUNCH(OSH_K_SCHUR_REDUCE, k_schur_reduce, (n + 13) / 14, 256, 0, c->bv); }
+  return OSH_OK;
+}
+
 // One LM trial of every active window from the Schur products to the trial residual.
 static int trial_kernels(osh_lba_ctx* c, bool later_round) {
   hipStream_t s = c->stream;
@@ -1849,7 +1931,7 @@ static int trial_kernels(osh_lba_ctx* c, bool later_round) {
   LAUNCH(OSH_K_SCHUR, c->kp_schur_sym, pb.n_sym, 64, 0, c->bv, 0, 1);
   LAUNCH(OSH_K_SCHUR_CROSS, c->kp_schur_cross, pb.n_items - pb.n_sym, 64, 0, c->bv, (int)pb.n_sym, 1);
   if (later_round) LAUNCH(OSH_K_POSE_HESS, k_pose_reduce, (pb.NFP + 1) / 2, 64, 0, c->bv, 1);
-  if (c->n_windows <= 8) { LAUNCH(OSH_K_SCHUR_REDUCE, k_schur_reduce<true>, (pb.n_rblk + 6) / 7, 256, 0, c->bv); } else { LAUNCH(OSH_K_SCHUR_REDUCE, k_schur_reduce<false>, (pb.n_rblk + 6) / 7, 256, 0, c->bv); }
+  OSH_TRY(launch_schur_reduce(c));
   {
     const bool _t = c->timer.begin(OSH_K_SOLVE, s);
     OSH_TRY(launch_solve(c, s));
@@ -2064,7 +2146,7 @@ extern "C" int osh_lba_debug_trial(osh_lba_ctx* c, int32_t window, double lambda
   LAUNCH(OSH_K_LIN_AUX, c->kp_lin_lm, pb.n_chunks, kBlock, c->lin_lds, c->bv);
   LAUNCH(OSH_K_SCHUR, c->kp_schur_sym, pb.n_sym, 64, 0, c->bv, 0, 1);
   LAUNCH(OSH_K_SCHUR_CROSS, c->kp_schur_cross, pb.n_items - pb.n_sym, 64, 0, c->bv, (int)pb.n_sym, 1);
-  if (c->n_windows <= 8) { LAUNCH(OSH_K_SCHUR_REDUCE, k_schur_reduce<true>, (pb.n_rblk + 6) / 7, 256, 0, c->bv); } else { LAUNCH(OSH_K_SCHUR_REDUCE, k_schur_reduce<false>, (pb.n_rblk + 6) / 7, 256, 0, c->bv); }
+  OSH_TRY(launch_schur_reduce(c));
   OSH_HIP(hipStreamSynchronize(s));
   if (S && d.n) OSH_HIP(hipMemcpy(S, c->d_S.as<double>() + d.S_off, (size_t)d.n * d.n * 8, hipMemcpyDeviceToHost));
   if (bs && d.n) OSH_HIP(hipMemcpy(bs, c->d_bs.as<double>() + (size_t)d.fpose_off * 6, (size_t)d.n * 8, hipMemcpyDeviceToHost));
@@ -2150,7 +2232,7 @@ extern "C" int osh_lba_get_upload_times(osh_lba_ctx* c, double ms[2]) {
 extern "C" const char* osh_lba_kernel_name(int k) {
   // pinhole instantiations reading float32 records (<true, ..> for a fisheye batch, <.., false> when a record is not exact in float32)
   static const char* names[OSH_K_COUNT] = {"k_lin_lm<false, true>", "k_pose_reduce", "k_schur_fused<true, false> (mode 1)", "k_solve", "k_backsub<false, true>",
-                                           "k_residual<false, true>", "k_control", "k_schur_reduce<false>", "k_schur_fused<false, false>",
+                                           "k_residual<false, true>", "k_control", "k_schur_reduce", "k_schur_fused<false, false>",
                                            "k_lin_lm<false, true> (factors only)", "k_schur_fused<true, false> (mode 0)"};
   return (k >= 0 && k < OSH_K_COUNT) ? names[k] : "?";
 }
