@@ -190,6 +190,10 @@ int osh_lba_pack_compare(osh_lba_ctx* ctx, int32_t n_windows, const osh_lba_prob
 int osh_lba_get_pack_profile(osh_lba_ctx* ctx, double ms[30]);
 /* Host-side cost of the last osh_lba_upload: ms[0] packing (sort, Schur plan, staging), ms[1] host-to-device copies. */
 int osh_lba_get_upload_times(osh_lba_ctx* ctx, double ms[2]);
+/* Which factorisation the reduced camera systems of the last osh_lba_upload take: out = {big, nb, threads, lds_bytes}.
+ * big 0: the LDS-resident blocked LDL^T, one block of `threads` threads per window with panels of `nb` rows and `lds_bytes` of
+ * dynamic LDS; big 1: the global-memory factorisation (a window beyond 438 optimisable poses, or OSH_LBA_SOLVE_BIG=1). */
+int osh_lba_get_solver(osh_lba_ctx* ctx, int32_t out[4]);
 const char* osh_lba_kernel_name(int kernel_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -327,6 +331,13 @@ int osh_liba_pack_check(int32_t n_windows, const struct osh_liba_problem* proble
 int osh_lm_control_check(double current_chi, double lambda, int32_t n_script, const double* script, int32_t* accepted,
                          double* rho, double* lambda_out, double* ni, int32_t* iter_go_on, int32_t* iter_nbad,
                          int32_t* iter_trials, int32_t n_played[2]);
+
+/* Host-only view of the rule osh_lba_upload picks the factorisation of the reduced camera systems with (needs no GPU): the plan
+ * for a batch of n_windows whose largest window has n_max unknowns (6 per optimisable pose), with force_nb / force_threads /
+ * force_big standing for the values of OSH_LBA_SOLVE_NB / OSH_LBA_SOLVE_THREADS / OSH_LBA_SOLVE_BIG (0: not set).
+ * out = {big, nb, threads, lds_bytes} as osh_lba_get_solver reports them after the upload. */
+int osh_lba_solve_plan_check(int32_t n_max, int32_t n_windows, int32_t force_nb, int32_t force_threads, int32_t force_big,
+                             int32_t out[4]);
 
 /* ----------------------------------------------- local inertial BA (config 4) */
 /*

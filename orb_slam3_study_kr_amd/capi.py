@@ -497,6 +497,8 @@ _SIGNATURES = {
     "osh_liba_pack_check": (C.c_int, [C.c_int32, C.POINTER(LibaProblem), c_int64_p]),
     "osh_lm_control_check": (C.c_int, [C.c_double, C.c_double, C.c_int32, c_double_p, c_int32_p, c_double_p, c_double_p, c_double_p,
                                        c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    "osh_lba_get_solver": (C.c_int, [C.c_void_p, c_int32_p]),
+    "osh_lba_solve_plan_check": (C.c_int, [C.c_int32] * 5 + [c_int32_p]),
     "osh_orb_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "osh_orb_destroy": (None, [C.c_void_p]),
     "osh_orb_upload": (C.c_int, [C.c_void_p, C.POINTER(OrbBatch)]),

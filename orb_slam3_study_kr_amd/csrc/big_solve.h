@@ -1,6 +1,7 @@
 // big_solve.h -- LDL^T + solve of ONE reduced camera system that does not fit a block's LDS: the global bundle adjustment
-// of a map beyond ~230 keyframes (Optimizer::GlobalBundleAdjustemnt / BundleAdjustment, src/Optimizer.cc:53-392, whose
-// LinearSolverEigen::solve factors the whole-map system, Thirdparty/g2o/g2o/solvers/linear_solver_eigen.h:94-124).
+// of a map of 439 optimisable keyframes or more (Optimizer::GlobalBundleAdjustemnt / BundleAdjustment, src/Optimizer.cc:53-392, whose
+// LinearSolverEigen::solve factors the whole-map system, Thirdparty/g2o/g2o/solvers/linear_solver_eigen.h:94-124).  The limit is
+// lba_solve_plan's (solve_plan.h); OSH_LBA_SOLVE_BIG=1 sends a system of any size here.
 //
 // Same factorisation as ldlt_block.h (no pivoting, upper storage, A = U^T D U with U unit upper triangular; fails only on an
 // exactly-zero pivot), right-looking with 32-wide panels, the matrix in global memory and the whole chip on the trailing update:

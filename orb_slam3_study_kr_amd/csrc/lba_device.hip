@@ -34,6 +34,7 @@
 #include "lba_math.h"
 #include "ldlt_block.h"
 #include "big_solve.h"
+#include "solve_plan.h"
 #include "schur_plan.h"
 #include "lba_pack.h"
 #include "lba_pack_device.h"
@@ -47,10 +48,22 @@
 namespace osh {
 
 constexpr int kResidualSplit = 1;    // blocks of k_residual per chunk
-constexpr int kSolveThreadsBatch = 256, kSolveThreadsLatency = 512;
 constexpr int kPoseRec = 21;       // staged pose: quaternion + translation (7), camera (5), rotation matrix (9)
 constexpr int kDevicePackMinWindows = 24;   // smaller batches are packed by host threads (osh_lba_upload)
 constexpr int kLdsPoses = 512;     // windows with more poses read them from global memory in the landmark-major kernels
+constexpr int kMaxDynamicLds = 160 * 1024 - 64;   // bytes of dynamic LDS the kernels of this file opt in to
+
+// LDS of k_backsub for a window of P optimisable and F fixed keyframes, in doubles: partials, reduce scratch and the chunk's landmarks;
+// when `staged`, x_p and the optimisable poses at the current estimates; the trial poses of all keyframes when there are at most
+// kLdsPoses.  x_p and the current poses are staged when that fits the block (with two fixed keyframes: up to 393 optimisable ones; the
+// budget was once taken for granted up to kLdsPoses, and the launch of a window of 394 to 510 failed); otherwise the kernel reads them
+// from global memory, as it does beyond kLdsPoses.
+__host__ __device__ constexpr int backsub_lds_doubles(int P, int F, bool staged) {
+  return 3 * kChunkEdges + 4 + 3 * kBlock + (staged ? 6 * P + P * kPoseRec : 0) + (P + F <= kLdsPoses ? (P + F) * kPoseRec : 0);
+}
+__host__ __device__ constexpr bool backsub_stages(int P, int F) {
+  return P <= kLdsPoses && backsub_lds_doubles(P, F, true) * (int)sizeof(double) <= kMaxDynamicLds;
+}
 
 struct LmState {
   double lambda, ni, currentChi, iniChi, tempChi, rho, scale_pose, chi2_initial;
@@ -1130,7 +1143,7 @@ __device__ void solve_tail(BatchView& bv, const WinDesc& wd, LmState& st, const 
 // k_solve: dense blocked LDL^T (no pivoting, upper storage) of the reduced camera system of
 // one window per block, forward elimination fused (rhs carried as an extra column), blocked
 // back-substitution, then the pose update T <- exp(x) T and the pose part of computeScale.
-// LDS: U panel [nb][W] (unscaled rows), L panel [nb][W] (rows / pivot), x [n], d [nb].
+// LDS: one panel [nb][W] (unscaled rows), x [n], d [nb] (ldlt_block.h); which instantiation runs: solve_plan.h.
 // --------------------------------------------------------------------------------------------
 template <int NB, int NT>
 __global__ __launch_bounds__(NT) void k_solve(BatchView bv, int W) {
@@ -1186,7 +1199,7 @@ __global__ __launch_bounds__(kBlock) void k_backsub(BatchView bv) {
   const double* poses = bv.pose_state[st.sel] + (size_t)wd.pose_off * 7;
   const double* cams = bv.pose_cam + (size_t)wd.pose_off * 5;
   const double* pts = bv.pt_state[st.sel] + (size_t)wd.pt_off * 3;
-  const bool staged = wd.P <= kLdsPoses;
+  const bool staged = backsub_stages(wd.P, wd.F);
   const double* xp = bv.xp + (size_t)wd.fpose_off * 6;
   double* sh_pose = sh_x + (staged ? n : 0);
   const int* lmo = bv.lm_off + wd.lmoff_off;
@@ -1701,30 +1714,30 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
     const int staged = std::min(pb.np_max, kLdsPoses);
     c->lin_lds = (size_t)(9 * kChunkEdges + 4 + 3 * kBlock + staged * kPoseRec) * sizeof(double);
     c->resid_lds = (size_t)(4 + 3 * kBlock + staged * kPoseRec) * sizeof(double);
-    const int pmax = pb.n_max / 6;
-    c->backsub_lds = (size_t)(3 * kChunkEdges + 4 + 3 * kBlock + (pmax <= kLdsPoses ? pb.n_max + pmax * kPoseRec : 0) + staged * kPoseRec) * sizeof(double);
+    int backsub_doubles = 0;   // the largest need of a window (backsub_lds_doubles: each window stages what fits)
+    for (const WinDesc& d : pb.win) backsub_doubles = std::max(backsub_doubles, backsub_lds_doubles(d.P, d.F, backsub_stages(d.P, d.F)));
+    c->backsub_lds = (size_t)backsub_doubles * sizeof(double);
     // One block per window with the widest panel that fits.  A batch takes 256-thread blocks: the one LDS panel of ldlt_block.h
     // (70 KB for 50 keyframes) lets two windows share a CU, and the factorisation is latency bound, so they overlap (measured:
     // 5.5 ms of solve per 512-window step against 6.0 with 512-thread blocks, profiles/solve_sweep.sh); a few windows take 512 threads.
-    c->solve_threads = nw >= 128 ? kSolveThreadsBatch : kSolveThreadsLatency;
-    auto need = [&](int b) { return ldlt_lds_doubles(b, ldlt_row_stride(pb.n_max), c->solve_threads) * sizeof(double); };
-    int nb = 24;
-    while (nb > 6 && need(nb) > (size_t)150 * 1024) nb /= 2;  // 24 -> 12 -> 6 (template instantiations of k_solve)
-    if (const char* e = std::getenv("OSH_LBA_SOLVE_THREADS")) { const int t = std::atoi(e); if (t == kSolveThreadsBatch || t == kSolveThreadsLatency) c->solve_threads = t; }
-    if (const char* e = std::getenv("OSH_LBA_SOLVE_NB")) { const int b = std::atoi(e); if ((b == 24 || b == 12 || b == 6) && b <= nb) nb = b; }
-    c->solve_big = need(nb) > (size_t)150 * 1024;
+    // (the rule, its limits and the three measurement switches: solve_plan.h)
+    auto knob = [](const char* name) { const char* e = std::getenv(name); return e ? std::atoi(e) : 0; };
+    const SolvePlan plan = lba_solve_plan(pb.n_max, nw, knob("OSH_LBA_SOLVE_NB"), knob("OSH_LBA_SOLVE_THREADS"), knob("OSH_LBA_SOLVE_BIG"));
+    c->solve_threads = plan.threads;
+    c->solve_big = plan.big;
     if (c->solve_big) {
-      // beyond ~240 optimisable poses (global BA of a long session) the system is factored in global memory, one window at a time
+      // beyond 438 optimisable poses (global BA of a long session; OSH_LBA_SOLVE_BIG=1: whatever the size) the system is factored in
+      // global memory, one window at a time
       if (pb.n_max / 6 > kBigMaxPoses) {
         set_error("window with %d optimisable poses: the dense reduced system is limited to %d poses", pb.n_max / 6, kBigMaxPoses);
         return OSH_ERR_UNSUPPORTED;
       }
-      OSH_TRY(c->d_bigV.reserve((size_t)kBigNB * pb.n_max * 8)); OSH_TRY(c->d_bigz.reserve((size_t)pb.n_max * 8)); OSH_TRY(c->d_bigfail.reserve(sizeof(int)));
-      nb = 6;
+      OSH_TRY(c->d_bigV.reserve(std::max<size_t>((size_t)kBigNB * pb.n_max * 8, 8))); OSH_TRY(c->d_bigz.reserve(std::max<size_t>((size_t)pb.n_max * 8, 8)));
+      OSH_TRY(c->d_bigfail.reserve(sizeof(int)));
     }
-    c->solve_nb = nb;
+    c->solve_nb = plan.nb;
     c->solve_W = ldlt_row_stride(pb.n_max);
-    c->solve_lds = c->solve_big ? 0 : need(nb);
+    c->solve_lds = plan.lds_bytes;
   }
 
   // ---- work buffers
@@ -1814,7 +1827,7 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
 
   // opt in to large dynamic LDS
   constexpr int kTB = kSolveThreadsBatch, kTL = kSolveThreadsLatency;
-  OSH_TRY(allow_dynamic_lds(c->device, 160 * 1024 - 64, k_solve<24, kTB>, k_solve<12, kTB>, k_solve<6, kTB>, k_solve<24, kTL>,
+  OSH_TRY(allow_dynamic_lds(c->device, kMaxDynamicLds, k_solve<24, kTB>, k_solve<12, kTB>, k_solve<6, kTB>, k_solve<24, kTL>,
                             k_solve<12, kTL>, k_solve<6, kTL>, k_backsub<false, false>, k_backsub<false, true>, k_backsub<true, false>,
                             k_backsub<true, true>, k_lin_lm<false, false>, k_lin_lm<false, true>, k_lin_lm<true, false>, k_lin_lm<true, true>,
                             k_residual<false, false>, k_residual<false, true>, k_residual<true, false>, k_residual<true, true>));
@@ -2170,6 +2183,13 @@ extern "C" int osh_lba_debug_trial(osh_lba_ctx* c, int32_t window, double lambda
     }
   }
   c->optimized = false;
+  return OSH_OK;
+}
+
+// {big, nb, threads, lds_bytes} of the last upload: which factorisation its reduced systems take (solve_plan.h)
+extern "C" int osh_lba_get_solver(osh_lba_ctx* c, int32_t out[4]) {
+  if (!c || !out || c->n_windows <= 0) { set_error("osh_lba_get_solver: nothing uploaded"); return OSH_ERR_INVALID; }
+  out[0] = c->solve_big ? 1 : 0; out[1] = c->solve_nb; out[2] = c->solve_threads; out[3] = (int32_t)c->solve_lds;
   return OSH_OK;
 }
 

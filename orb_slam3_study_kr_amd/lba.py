@@ -251,6 +251,12 @@ class LbaSolver:
         return dict(items=int(st[0]), sym_items=int(st[1]), mfma_per_pass=int(st[2]), useful_blocks=int(st[3]), contributions=int(st[4]),
                     reduce_entries=int(st[5]), records=int(st[6]), rhs_contributions=int(st[7]))
 
+    def get_solver(self) -> dict:
+        """Which factorisation the reduced systems of the last upload take: big (csrc/big_solve.h) or k_solve<nb, threads>."""
+        out = np.zeros(4, dtype=np.int32)
+        capi.check(self.lib.osh_lba_get_solver(self.ctx, capi.ptr(out, capi.c_int32_p)), "osh_lba_get_solver", self.lib)
+        return dict(big=bool(out[0]), nb=int(out[1]), threads=int(out[2]), lds_bytes=int(out[3]))
+
     def set_profiling(self, enable: bool):
         capi.check(self.lib.osh_lba_set_profiling(self.ctx, int(enable)), "osh_lba_set_profiling", self.lib)
 

@@ -138,9 +138,13 @@ def test_global_bundle_adjustment_for_a_loop_keeps_results_beside_the_live_map(o
 
 
 def test_global_bundle_adjustment_of_a_map_of_320_keyframes(ob):
-    """A EuRoC-sized session: 320 keyframes, one of them (the origin) fixed -- beyond the LDS-resident factorisation, the reduced
-    system (n = 1914) goes through csrc/big_solve.h.  Results against the oracle's dense solve of the same packed window."""
+    """A EuRoC-sized session: 320 keyframes, one of them (the origin) fixed.  The reduced system (n = 1914) takes the narrowest
+    LDS-resident factorisation, k_solve<6, 512> (csrc/big_solve.h starts at 439 optimisable keyframes: csrc/solve_plan.h,
+    test_gpu_solve.py).  Results against the oracle's dense solve of the same packed window."""
     w = synth.make_window(46, n_free=319, n_fixed=1, n_points=5000, stereo=True)
+    plan = np.zeros(4, dtype=np.int32)   # the host layer keeps its context to itself: the rule its upload calls, for this size
+    assert capi.load_library().osh_lba_solve_plan_check(6 * 319, 1, 0, 0, 0, capi.ptr(plan, capi.c_int32_p)) == 0
+    assert plan[:3].tolist() == [0, 6, 512]
     with host.HostGraph(w, init_kf_id_index=w.n_free) as g:
         pw, o, ref = _gba_reference(g, ob, 5, True)
         assert pw.n_free == 319 and pw.n_fixed == 1

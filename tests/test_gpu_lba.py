@@ -111,12 +111,14 @@ def test_config2_stereo_window_full_size(solver, ob):
 
 
 def test_window_beyond_the_lds_factorisation_uses_the_global_memory_solver(solver, ob):
-    """A reduced system of 300 optimisable keyframes (n = 1800) does not fit the LDS-resident LDL^T of k_solve: it is factored in
-    global memory by big_solve.h (global BA of a long session, src/Optimizer.cc:53-392).  Same LM trace as the oracle's dense solve;
-    a small window in the same batch takes the same path."""
+    """A reduced system of 300 optimisable keyframes (n = 1800; global BA of a long session, src/Optimizer.cc:53-392).  When this
+    test was named, ldlt_block.h kept two panels in LDS and such a system went to big_solve.h; with one panel it fits the narrowest
+    LDS-resident factorisation, k_solve<6, 512>, which is what runs here (big_solve.h starts at 439 poses and has tests of its own in
+    test_gpu_solve.py).  Same LM trace as the oracle's dense solve; a small window in the same batch takes the same path."""
     big = synth.make_window(900, n_free=300, n_fixed=3, n_points=6000, stereo=True, max_iterations=5)
     small = synth.make_window(901, n_free=6, n_fixed=2, n_points=300, stereo=True)
     got = solver.solve([big, small])
+    assert {k: v for k, v in solver.get_solver().items() if k != "lds_bytes"} == dict(big=False, nb=6, threads=512)
     _check_result(got[0], ob.lba_solve(big), big, t_tol=1e-5, chi_tol=1e-6, pts_tol=1e-5)
     _check_result(got[1], ob.lba_solve(small), small)
 

@@ -541,7 +541,7 @@ def lba_script():
     return [
         lba_call("200-window batch (batch solve threads, device packer)", [pool[k % 8] for k in range(200)]),
         lba_call("1 window after the batch (latency solve, host packer)", [pool[1]]),
-        lba_call("300-keyframe map (global-memory factorisation)", [big_map]),
+        lba_call("300-keyframe map (k_solve<6, 512>, the narrowest LDS panel)", [big_map]),
         lba_call("5-keyframe window after the map", [small]),
         lba_call("4 windows, device packer forced", [pool[k] for k in range(4)], pack_mode=0),
         lba_call("4 windows, host packer forced", [pool[k + 2] for k in range(4)], pack_mode=1),
