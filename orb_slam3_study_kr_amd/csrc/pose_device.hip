@@ -121,10 +121,17 @@ __global__ __launch_bounds__(kPT) void k_pose_opt(PoseView v) {
   EdgeCache ec;
 #pragma unroll
   for (int q = 0; q < kPC; ++q) {
-    const size_t ge = (size_t)d.edge_off + min(tid + q * kPT, max(d.E - 1, 0));
+    // slots past the frame's last edge load that edge again and are never used; a frame without edges has no element of its
+    // own in any array (edge_off may be the end of the batch's arrays), so it loads nothing
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { ec.X[q][k] = v.X[ge * 3 + k]; ec.obs[q][k] = v.obs[ge * 3 + k]; }
-    ec.info[q] = v.info[ge]; ec.kind[q] = v.kind[ge]; ec.level[q] = 0; ec.chi2[q] = 0.0;
+    for (int k = 0; k < 3; ++k) { ec.X[q][k] = 0.0; ec.obs[q][k] = 0.0; }
+    ec.info[q] = 0.0; ec.kind[q] = OSH_EDGE_MONO; ec.level[q] = 0; ec.chi2[q] = 0.0;
+    if (d.E > 0) {
+      const size_t ge = (size_t)d.edge_off + min(tid + q * kPT, d.E - 1);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { ec.X[q][k] = v.X[ge * 3 + k]; ec.obs[q][k] = v.obs[ge * 3 + k]; }
+      ec.info[q] = v.info[ge]; ec.kind[q] = v.kind[ge];
+    }
   }
   bool robust = true;
   int n_bad = 0, rounds = 0;
