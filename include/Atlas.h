@@ -1,7 +1,8 @@
-/* Atlas.h -- members of ORB_SLAM3::Atlas used by LocalMapping::CreateNewMapPoints (reference include/Atlas.h;
- * src/Atlas.cc:109-113,249-258).  Minimal test double: one current map, no locking. */
+/* Atlas.h -- members of ORB_SLAM3::Atlas used by LocalMapping::CreateNewMapPoints and ProcessNewKeyFrame (reference
+ * include/Atlas.h; src/Atlas.cc:103-113,249-258).  Minimal test double: one current map, no locking. */
 #ifndef ATLAS_H
 #define ATLAS_H
+#include "KeyFrame.h"
 #include "Map.h"
 #include "MapPoint.h"
 namespace ORB_SLAM3 {
@@ -9,6 +10,7 @@ class Atlas {
  public:
   Map* GetCurrentMap() { return mpCurrentMap; }
   void AddMapPoint(MapPoint* pMP) { pMP->GetMap()->AddMapPoint(pMP); }
+  void AddKeyFrame(KeyFrame* pKF) { pKF->GetMap()->AddKeyFrame(pKF); }   // src/Atlas.cc:103-107
   // test-double state
   Map* mpCurrentMap = nullptr;
 };

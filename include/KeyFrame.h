@@ -64,10 +64,13 @@ class KeyFrame {
   // what LocalMapping::CreateNewMapPoints calls (src/KeyFrame.cc:755-772 and :774-807; stand-in bodies: csrc/hosttest/newpoints.cc)
   bool UnprojectStereo(int i, Eigen::Vector3f& x3D);
   float ComputeSceneMedianDepth(const int q);
+  // src/KeyFrame.cc:379-476: rebuilds the covisibility links from the map point matches; the stand-in counts the calls
+  void UpdateConnections(bool upParent = true) { (void)upParent; ++mnConnectionUpdates; }
 
   long unsigned int mnId;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
   long unsigned int mnBALocalForMerge = 0;   // include/KeyFrame.h:318
+  long unsigned int mnFuseTargetForKF = 0;   // include/KeyFrame.h:325 (LocalMapping::SearchInNeighbors)
   // markers of KeyFrameDatabase (include/KeyFrame.h:334-342)
   long unsigned int mnRelocQuery = 0;
   int mnRelocWords = 0;
@@ -123,6 +126,7 @@ class KeyFrame {
   bool mbBad = false;
   Map* mpMap;
   int mnPoseSets = 0;
+  int mnConnectionUpdates = 0;
 };
 }  // namespace ORB_SLAM3
 #endif

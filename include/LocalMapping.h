@@ -1,5 +1,5 @@
-/* LocalMapping.h -- members of ORB_SLAM3::LocalMapping used by LocalMapping::CreateNewMapPoints (reference include/LocalMapping.h:
- * 111-112,134,144-145,164-170; src/LocalMapping.cc:398-741).  Minimal test double: the members the method reads, public, and no
+/* LocalMapping.h -- members of ORB_SLAM3::LocalMapping used by LocalMapping::ProcessNewKeyFrame, CreateNewMapPoints and
+ * SearchInNeighbors (reference include/LocalMapping.h:111-112,134,144-145,164-172; src/LocalMapping.cc:306-346,398-853).  Minimal test double: the members the method reads, public, and no
  * thread. */
 #ifndef LOCALMAPPING_H
 #define LOCALMAPPING_H
@@ -16,12 +16,17 @@ class LocalMapping {
   // host side, the per-match body (:503-720) in one osh_orb_triangulate_new_points call per neighbour, the map points created from
   // its results in match order (csrc/host/LocalMapping.cc)
   void CreateNewMapPoints();
+  // src/LocalMapping.cc:306-346 and :743-853, statement for statement; the per-point ComputeDistinctiveDescriptors /
+  // UpdateNormalAndDepth pairs (:328-331, :843-846) are one MapPoint::RefreshBatch each (csrc/host/LocalMapping.cc)
+  void ProcessNewKeyFrame();
+  void SearchInNeighbors();
   bool CheckNewKeyFrames() { std::unique_lock<std::mutex> lock(mMutexNewKFs); return !mlNewKeyFrames.empty(); }   // :342-346
 
   bool mbFarPoints = false;
   float mThFarPoints = 0;
   bool mbMonocular = false;
   bool mbInertial = false;
+  bool mbAbortBA = false;   // include/LocalMapping.h:172
   Atlas* mpAtlas = nullptr;
   Tracking* mpTracker = nullptr;
   KeyFrame* mpCurrentKeyFrame = nullptr;

@@ -22,6 +22,7 @@ class Map {
   bool IsBad() { return mbBad; }                                      // src/Map.cc:246-249
   bool GetIniertialBA2() { return mbIMU_BA2; }                        // src/Map.cc:315-319
   void AddMapPoint(MapPoint* pMP) { mvpMapPoints.push_back(pMP); }    // src/Map.cc:80-84 (a set there)
+  void AddKeyFrame(KeyFrame* pKF) { mvpKeyFrames.push_back(pKF); }    // src/Map.cc:60-78 (a set there; ids and the lower keyframe are left out)
   std::mutex mMutexMapUpdate;
   std::set<long unsigned int> msOptKFs;
   std::set<long unsigned int> msFixedKFs;

@@ -1,11 +1,12 @@
 /* MapPoint.h -- members of ORB_SLAM3::MapPoint used on the hot path (reference include/MapPoint.h;
- * src/MapPoint.cc:118-127,168-201,204,302,426-494,560).  Minimal test double: same names and meaning,
+ * src/MapPoint.cc:118-127,168-201,204,302,329-403,426-494,560).  Minimal test double: same names and meaning,
  * no locking (the real getters copy under mMutexPos / mMutexFeatures). */
 #ifndef MAPPOINT_H
 #define MAPPOINT_H
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <vector>
 #include "orbslam3_compat.h"
 namespace ORB_SLAM3 {
 class KeyFrame;
@@ -44,11 +45,20 @@ class MapPoint {
   Eigen::Vector3f GetNormal() { return mNormalVector; }
   KeyFrame* GetReferenceKeyFrame() { return mpRefKF; }
 
+  /* ADD THIS MEMBER to the reference's class: ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) and UpdateNormalAndDepth
+   * (:426-494) for every point of the list, in list order, in one device call (csrc/host/MapPoint.cc).  A bad point, a point
+   * without observations and a null entry are left alone; a point that occurs twice is refreshed twice.  It writes mDescriptor,
+   * mNormalVector, mfMinDistance and mfMaxDistance (and, in this stand-in, counts mnDescriptorUpdates and mnNormalUpdates once per
+   * occurrence).  LocalMapping::ProcessNewKeyFrame and SearchInNeighbors (csrc/host/LocalMapping.cc) call it where the reference
+   * loops over the pair. */
+  static void RefreshBatch(const std::vector<MapPoint*>& vpMPs);
+
   static long unsigned int nNextId;           // include/MapPoint.h:165
   static std::mutex mGlobalMutex;             // include/MapPoint.h:151 (held while PoseOptimization reads the positions)
   long unsigned int mnId;
   long unsigned int mnBALocalForKF = 0;
   long unsigned int mnBALocalForMerge = 0;    // include/MapPoint.h:139
+  long unsigned int mnFuseCandidateForKF = 0; // include/MapPoint.h:185 (LocalMapping::SearchInNeighbors)
   Eigen::Vector3f mPosGBA;                    // include/MapPoint.h:147-148
   long unsigned int mnBAGlobalForKF = 0;
   long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;   // include/MapPoint.h:143-144 (set by LoopClosing::CorrectLoop)

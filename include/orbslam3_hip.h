@@ -953,6 +953,61 @@ int osh_orb_triangulate_new_points(osh_orb_ctx* ctx, int32_t n_segments, const o
  * ms[1] upload, ms[2] kernel, ms[3] download + write-back. */
 int osh_orb_newpoint_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- map point refresh (distinctive descriptor, normal and depth) */
+/*
+ * MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) and MapPoint::UpdateNormalAndDepth (:426-494) for the points
+ * of n_batches batches in one call.  A batch is one caller's list of points, for example the map points of one keyframe.  A
+ * point has entries in observation order; an entry is one camera of one observing keyframe: its 32-byte descriptor, the index of
+ * its camera centre in the batch's centre table, and use_desc, 0 when the keyframe is bad (the reference leaves a bad keyframe
+ * out of the descriptor, :352, and keeps it in the normal, :447-466).
+ *
+ * Descriptor: over the M entries of the point with use_desc, in order, d(i, j) is the Hamming distance, the median of row i is the
+ * element of index (M - 1) / 2 of the ascending row, self-distance included (:390), and best_entry is the first row with the least
+ * median (:392), as an index into the point's entries; best_median is that median.  M = 0: best_entry = best_median = -1.
+ *
+ * Normal and depth, single IEEE float32 operations, no fused multiply-add: normali = pos - centre; norm = sqrt(x*x + (y*y + z*z));
+ * normal = the sum of normali / norm over all n entries as one chain in entry order, divided by (float)n; dist = the norm of
+ * pos - centres[ref_centre]; max_distance = dist * level_scale; min_distance = max_distance / top_scale.  Parity with the code Eigen
+ * generates for these statements in the reference is not pinned.  A point without entries gets best_entry = best_median = -1, a
+ * zero normal and zero distances: there is nothing to apply (both reference functions return early).
+ *
+ * Refused with OSH_ERR_INVALID before any device work and without a context, which stays usable: a negative count, a NULL array
+ * whose count is not 0, entry_off that does not start at 0 or decreases, a point with more than OSH_MAPPOINT_MAX_DESCRIPTORS
+ * entries (the message names the batch, the point and the count), a centre index outside [0, n_centres), ref_centre outside
+ * [0, n_centres) on a point with entries; with OSH_ERR_UNSUPPORTED more than OSH_MAPPOINT_MAX_POINTS points or
+ * OSH_MAPPOINT_MAX_ENTRIES entries or centres in one call.  n_batches = 0, batches without points and points without entries are valid.  Every
+ * entry of every result array that is not NULL is written.
+ */
+#define OSH_MAPPOINT_MAX_DESCRIPTORS 256        /* entries of one point                  */
+#define OSH_MAPPOINT_MAX_POINTS      4194304    /* 2^22, all batches of a call together  */
+#define OSH_MAPPOINT_MAX_ENTRIES     33554432   /* 2^25, all batches of a call together  */
+typedef struct osh_mappoint_batch {
+  int32_t n_points;
+  const int32_t* entry_off;     /* [n_points+1] the entries of point p are [entry_off[p], entry_off[p+1]); entry_off[0] = 0    */
+  const uint8_t* desc;          /* [n_entries*32] pKF->mDescriptors.row(leftIndex or rightIndex)                                */
+  const int32_t* centre;        /* [n_entries]    index into centres: GetCameraCenter / GetRightCameraCenter of the keyframe    */
+  const uint8_t* use_desc;      /* [n_entries]    !pKF->isBad()                                                                 */
+  int32_t n_centres;
+  const float* centres;         /* [n_centres*3]                                                                                */
+  const float* pos;             /* [n_points*3]   mWorldPos                                                                     */
+  const int32_t* ref_centre;    /* [n_points]     index into centres: pRefKF->GetCameraCenter(); not read for an empty point    */
+  const float* level_scale;     /* [n_points]     pRefKF->mvScaleFactors[level]                                                 */
+  const float* top_scale;       /* [n_points]     pRefKF->mvScaleFactors[nLevels - 1]                                           */
+} osh_mappoint_batch;
+/* Caller-allocated, one entry per point of the batch; each may be NULL (not wanted). */
+typedef struct osh_mappoint_result {
+  int32_t* best_entry;     /* [n_points]   index into the point's entries of the new mDescriptor, or -1                        */
+  int32_t* best_median;    /* [n_points]   its median distance, or -1                                                          */
+  float* normal;           /* [n_points*3] mNormalVector                                                                       */
+  float* min_distance;     /* [n_points]   mfMinDistance                                                                       */
+  float* max_distance;     /* [n_points]   mfMaxDistance                                                                       */
+} osh_mappoint_result;
+int osh_orb_refresh_map_points(osh_orb_ctx* ctx, int32_t n_batches, const osh_mappoint_batch* batches,
+                               const osh_mappoint_result* results);
+/* Host-clock phases (ms) of the last osh_orb_refresh_map_points under osh_orb_set_profiling: ms[0] validation + staging (the
+ * points sorted into the wavefront and the block class), ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
+int osh_orb_refresh_map_points_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 /* ------------------------------------------------- FAST corners and orientation (ORBextractor) */
 /*
  * The integer part of ORBextractor::ComputeKeyPointsOctTree (src/ORBextractor.cc:781-896) for n_frames pyramids in one call: what

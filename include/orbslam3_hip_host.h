@@ -641,6 +641,60 @@ int osh_host_bowdb_check_words(int32_t n, const int32_t* word_id, int64_t n_word
 int osh_host_bowdb_book_replay(int32_t n_ops, const int64_t* ops, uint64_t* op_handle, int32_t max_rows, uint64_t* handle, int64_t* start,
                                int32_t* len, uint8_t* alive, int64_t info[8]);
 
+/* ---- MapPoint::RefreshBatch, LocalMapping::SearchInNeighbors / ProcessNewKeyFrame (include/MapPoint.h, include/LocalMapping.h,
+ *      csrc/host/MapPoint.cc, csrc/host/LocalMapping.cc, csrc/hosttest/mappoints.cc) ---- */
+struct osh_mappoint_batch;
+struct osh_mappoint_result;
+/* csrc/mappoint_refresh.h (the statements k_mappoint_wave / k_mappoint_block run) compiled for the host, on one thread: arguments as
+ * osh_orb_refresh_map_points without a context, without its validation (the batches must be valid) and without its limit on the
+ * entries of a point.  *ms (may be NULL) = wall time of the loops over the points.  -1: bad arguments. */
+int osh_host_mappoint_refresh_cpu(int32_t n_batches, const struct osh_mappoint_batch* batches, const struct osh_mappoint_result* results,
+                                  double* ms);
+/* Makes the keyframes of a graph fit for ORBmatcher::Fuse and MapPoint::RefreshBatch: the level tables scale_factor^level by
+ * repeated float multiplication (n_levels of them), mfLogScaleFactor, invfx / invfy, mb, mvKeys = mvKeysUn, N, the image bounds
+ * (min x, min y, max x, max y) and the grid of the left / only camera, and mDescriptors: kf_rows[k] rows for keyframe k (it must
+ * be the length of its match table: left keypoints, then the right ones of a rig), all keyframes one after another in desc.
+ * -1: bad arguments. */
+int osh_host_graph_set_mapping(osh_host_graph* g, float scale_factor, int32_t n_levels, const float bounds[4], float mb,
+                               const int32_t* kf_rows, const uint8_t* desc);
+/* mpRefKF of n points (kf[i] = -1: none). */
+int osh_host_graph_set_ref_kf(osh_host_graph* g, int32_t n, const int32_t* mp, const int32_t* kf);
+/* Takes the observation of keyframe kf out of point mp: the keypoint stays.  keep_match: the keyframe's slot keeps the point (a
+ * keyframe fresh from Tracking, whose points do not know it yet); else the slot is emptied.  No bad flag, no new reference. */
+int osh_host_graph_unlink(osh_host_graph* g, int32_t kf, int32_t mp, int32_t keep_match);
+/* A second map point (id new_id) at the position of point mp that takes over its observations in the n_kf keyframes listed: the
+ * duplicate a fusion finds.  Returns the index of the new point; -1: bad arguments. */
+int osh_host_graph_clone_point(osh_host_graph* g, int32_t mp, int64_t new_id, int32_t n_kf, const int32_t* kf);
+/* MapPoint::RefreshBatch on the points mp[0..n) in that order (-1: a null entry). */
+int osh_host_mp_refresh_batch(osh_host_graph* g, int32_t n, const int32_t* mp);
+/* What RefreshBatch packs for that list (PackMapPointRefresh of csrc/host/host_pack.h), without a device: sizes = points,
+ * entries, centres; every array may be NULL (call once for the sizes).  point_mp: the point of each packed occurrence; entry_kf /
+ * entry_row: the keyframe and descriptor row of each entry; the others as osh_mappoint_batch. */
+int osh_host_mp_refresh_pack(osh_host_graph* g, int32_t n, const int32_t* mp, int32_t sizes[3], int32_t* point_mp, int32_t* entry_off,
+                             int32_t* entry_kf, int32_t* entry_row, uint8_t* desc, int32_t* centre, uint8_t* use_desc, float* centres,
+                             float* pos, int32_t* ref_centre, float* level_scale, float* top_scale);
+/* mDescriptor (zeros when empty), mNormalVector, mfMinDistance / mfMaxDistance and the counters mnDescriptorUpdates /
+ * mnNormalUpdates of a point.  Returns 1 when the point has a descriptor, 0 when not, -1: bad arguments. */
+int osh_host_mp_get_refresh(osh_host_graph* g, int32_t mp, uint8_t desc[32], float normal[3], float min_max[2], int32_t counts[2]);
+/* The observations of a point in the order std::map<KeyFrame*, ...> iterates (by pointer value; the order both reference functions
+ * walk): keyframe index, left index, right index.  Returns their number (which may exceed capacity). */
+int osh_host_mp_observations(osh_host_graph* g, int32_t mp, int32_t capacity, int32_t* kf, int32_t* left, int32_t* right);
+/* out = isBad, GetReplaced as a point index (-1: none), mnFuseCandidateForKF, the reference keyframe's index (-1: none). */
+int osh_host_mp_state(osh_host_graph* g, int32_t mp, int64_t out[4]);
+/* GetMapPointMatches of a keyframe as point indices (-1: empty slot).  Returns its length. */
+int osh_host_kf_matches(osh_host_graph* g, int32_t kf, int32_t capacity, int32_t* mp);
+/* marks = mnFuseTargetForKF, the calls of UpdateConnections, NLeft; centres = GetCameraCenter, GetRightCameraCenter (the left one
+ * again without a rig).  Each may be NULL. */
+int osh_host_kf_state(osh_host_graph* g, int32_t kf, int64_t marks[3], float centres[6]);
+/* One ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th, bRight) on the graph; returns its result. */
+int osh_host_graph_fuse(osh_host_graph* g, int32_t kf, int32_t n, const int32_t* mp, float th, int32_t right);
+/* LocalMapping::SearchInNeighbors with mpCurrentKeyFrame = keyframe kf and the three flags. */
+int osh_host_local_mapping_search_in_neighbors(osh_host_graph* g, int32_t kf, int32_t monocular, int32_t inertial, int32_t abort_ba);
+/* LocalMapping::ProcessNewKeyFrame with keyframe kf alone in mlNewKeyFrames (its BoW vectors are marked as computed).  Returns the
+ * length of mlpRecentAddedMapPoints, the first `capacity` as point indices in recent; *in_map = how many times more the map lists
+ * the keyframe than before. */
+int osh_host_local_mapping_process_new_keyframe(osh_host_graph* g, int32_t kf, int32_t capacity, int32_t* recent, int32_t* in_map);
+
 #ifdef __cplusplus
 }
 #endif

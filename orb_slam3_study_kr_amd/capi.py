@@ -374,6 +374,24 @@ OSH_NEWPOINT_PINHOLE, OSH_NEWPOINT_KB8 = 0, 1
 OSH_NEWPOINT_TRIANGULATED, OSH_NEWPOINT_STEREO_1, OSH_NEWPOINT_STEREO_2, OSH_NEWPOINT_NO_SOURCE = 0, 1, 2, 255
 
 
+class MapPointBatch(C.Structure):
+    """``osh_mappoint_batch`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n_points", C.c_int32), ("entry_off", c_int32_p), ("desc", c_uint8_p), ("centre", c_int32_p), ("use_desc", c_uint8_p),
+                ("n_centres", C.c_int32), ("centres", c_float_p), ("pos", c_float_p), ("ref_centre", c_int32_p),
+                ("level_scale", c_float_p), ("top_scale", c_float_p)]
+
+
+class MapPointResult(C.Structure):
+    """``osh_mappoint_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("best_entry", c_int32_p), ("best_median", c_int32_p), ("normal", c_float_p), ("min_distance", c_float_p),
+                ("max_distance", c_float_p)]
+
+
+OSH_MAPPOINT_MAX_DESCRIPTORS, OSH_MAPPOINT_MAX_POINTS, OSH_MAPPOINT_MAX_ENTRIES = 256, 1 << 22, 1 << 25
+
+
 class FastFrame(C.Structure):
     """``osh_fast_frame`` (include/orbslam3_hip.h)."""
 
@@ -525,6 +543,8 @@ _SIGNATURES = {
     "osh_kb8_triangulate": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
     "osh_orb_triangulate_new_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(NewPointSegment), C.POINTER(NewPointResult)]),
     "osh_orb_newpoint_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_refresh_map_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MapPointBatch), C.POINTER(MapPointResult)]),
+    "osh_orb_refresh_map_points_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_fast_detect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult)]),
     "osh_orb_ic_angle": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult)]),
     "osh_orb_fast_get_times": (C.c_int, [C.c_void_p, c_double_p]),
@@ -853,6 +873,26 @@ class HostSim3Input(C.Structure):
 _HOST_SIGNATURES.update({
     "osh_host_pack_sim3": (C.c_int, [C.POINTER(HostSim3Input), C.c_int32, C.POINTER(Sim3Problem), c_int32_p] + [c_double_p] * 6),
     "osh_host_optimize_sim3": (C.c_int, [C.POINTER(HostSim3Input), c_uint8_p, c_double_p, c_double_p]),
+})
+
+# MapPoint::RefreshBatch, LocalMapping::SearchInNeighbors / ProcessNewKeyFrame (csrc/hosttest/mappoints.cc)
+_HOST_SIGNATURES.update({
+    "osh_host_mappoint_refresh_cpu": (C.c_int, [C.c_int32, C.POINTER(MapPointBatch), C.POINTER(MapPointResult), c_double_p]),
+    "osh_host_graph_set_mapping": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, c_float_p, C.c_float, c_int32_p, c_uint8_p]),
+    "osh_host_graph_set_ref_kf": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p]),
+    "osh_host_graph_unlink": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "osh_host_graph_clone_point": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, c_int32_p]),
+    "osh_host_mp_refresh_batch": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p]),
+    "osh_host_mp_refresh_pack": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_uint8_p,
+                                           c_int32_p, c_uint8_p, c_float_p, c_float_p, c_int32_p, c_float_p, c_float_p]),
+    "osh_host_mp_get_refresh": (C.c_int, [C.c_void_p, C.c_int32, c_uint8_p, c_float_p, c_float_p, c_int32_p]),
+    "osh_host_mp_observations": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    "osh_host_mp_state": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
+    "osh_host_kf_matches": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p]),
+    "osh_host_kf_state": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p, c_float_p]),
+    "osh_host_graph_fuse": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p, C.c_float, C.c_int32]),
+    "osh_host_local_mapping_search_in_neighbors": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "osh_host_local_mapping_process_new_keyframe": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
 })
 
 

@@ -1,5 +1,17 @@
-// LocalMapping.cc -- LocalMapping::CreateNewMapPoints (reference src/LocalMapping.cc:398-741) on MI355X (host side).
+// LocalMapping.cc -- LocalMapping::ProcessNewKeyFrame (reference src/LocalMapping.cc:306-346), CreateNewMapPoints (:398-741) and
+// SearchInNeighbors (:743-853) on MI355X (host side).
 //
+// ProcessNewKeyFrame and SearchInNeighbors follow the reference statement for statement: the order of vpTargetKFs, the
+// mnFuseTargetForKF / mnFuseCandidateForKF marks, the mbAbortBA exits, one ORBmatcher::Fuse per target keyframe (and one more for
+// the right camera of a rig), each of them on the device (ORBmatcher.cc).  Their loops over MapPoint::ComputeDistinctiveDescriptors
+// and UpdateNormalAndDepth (:328-331 and :843-846) are ONE MapPoint::RefreshBatch (MapPoint.cc) over the same points in the same
+// order.  That is the same computation: neither function reads another point's state, and nothing between the pairs of two points
+// changes what either reads (in ProcessNewKeyFrame the AddObservation calls of all points come first; each touches its own point).
+// The rig calls are kept as the reference writes them, Fuse(pKF, points, true): with the signature Fuse(KeyFrame*, const
+// vector<MapPoint*>&, const float th = 3.0, const bool bRight = false) the `true` is th = 1.0f and bRight stays false, so the
+// second call searches the left camera again with a narrower radius (:803,833).
+//
+// CreateNewMapPoints:
 // The neighbour list, the baseline test and ORBmatcher::SearchForTriangulation (itself on the device, ORBmatcher.cc) stay in the
 // reference's order, one neighbour after another: a point created for neighbour i takes its feature out of the search of
 // neighbour i + 1.  The loop over the matched pairs (:495-739) is split: everything up to the decision "a new map point"
@@ -115,6 +127,126 @@ void LocalMapping::CreateNewMapPoints() {
       mlpRecentAddedMapPoints.push_back(pMP);
     }
   }
+}
+
+// src/LocalMapping.cc:306-346
+void LocalMapping::ProcessNewKeyFrame() {
+  {
+    std::unique_lock<std::mutex> lock(mMutexNewKFs);
+    mpCurrentKeyFrame = mlNewKeyFrames.front();
+    mlNewKeyFrames.pop_front();
+  }
+
+  // Compute Bags of Words structures
+  mpCurrentKeyFrame->ComputeBoW();
+
+  // Associate MapPoints to the new keyframe and update normal and descriptor
+  const std::vector<MapPoint*> vpMapPointMatches = mpCurrentKeyFrame->GetMapPointMatches();
+  std::vector<MapPoint*> vpRefresh;
+  for (size_t i = 0; i < vpMapPointMatches.size(); i++) {
+    MapPoint* pMP = vpMapPointMatches[i];
+    if (pMP) {
+      if (!pMP->isBad()) {
+        if (!pMP->IsInKeyFrame(mpCurrentKeyFrame)) {
+          pMP->AddObservation(mpCurrentKeyFrame, i);
+          vpRefresh.push_back(pMP);   // UpdateNormalAndDepth, ComputeDistinctiveDescriptors (:330-331)
+        } else {                      // this can only happen for new stereo points inserted by the Tracking
+          mlpRecentAddedMapPoints.push_back(pMP);
+        }
+      }
+    }
+  }
+  MapPoint::RefreshBatch(vpRefresh);
+
+  // Update links in the Covisibility Graph
+  mpCurrentKeyFrame->UpdateConnections();
+
+  // Insert Keyframe in Map
+  mpAtlas->AddKeyFrame(mpCurrentKeyFrame);
+}
+
+// src/LocalMapping.cc:743-853
+void LocalMapping::SearchInNeighbors() {
+  // Retrieve neighbor keyframes
+  int nn = 10;
+  if (mbMonocular) nn = 30;
+  const std::vector<KeyFrame*> vpNeighKFs = mpCurrentKeyFrame->GetBestCovisibilityKeyFrames(nn);
+  std::vector<KeyFrame*> vpTargetKFs;
+  for (std::vector<KeyFrame*>::const_iterator vit = vpNeighKFs.begin(), vend = vpNeighKFs.end(); vit != vend; vit++) {
+    KeyFrame* pKFi = *vit;
+    if (pKFi->isBad() || pKFi->mnFuseTargetForKF == mpCurrentKeyFrame->mnId) continue;
+    vpTargetKFs.push_back(pKFi);
+    pKFi->mnFuseTargetForKF = mpCurrentKeyFrame->mnId;
+  }
+
+  // Add some covisible of covisible; extend to some second neighbors if abort is not requested
+  for (int i = 0, imax = vpTargetKFs.size(); i < imax; i++) {
+    const std::vector<KeyFrame*> vpSecondNeighKFs = vpTargetKFs[i]->GetBestCovisibilityKeyFrames(20);
+    for (std::vector<KeyFrame*>::const_iterator vit2 = vpSecondNeighKFs.begin(), vend2 = vpSecondNeighKFs.end(); vit2 != vend2; vit2++) {
+      KeyFrame* pKFi2 = *vit2;
+      if (pKFi2->isBad() || pKFi2->mnFuseTargetForKF == mpCurrentKeyFrame->mnId || pKFi2->mnId == mpCurrentKeyFrame->mnId) continue;
+      vpTargetKFs.push_back(pKFi2);
+      pKFi2->mnFuseTargetForKF = mpCurrentKeyFrame->mnId;
+    }
+    if (mbAbortBA) break;
+  }
+
+  // Extend to temporal neighbors
+  if (mbInertial) {
+    KeyFrame* pKFi = mpCurrentKeyFrame->mPrevKF;
+    while (vpTargetKFs.size() < 20 && pKFi) {
+      if (pKFi->isBad() || pKFi->mnFuseTargetForKF == mpCurrentKeyFrame->mnId) {
+        pKFi = pKFi->mPrevKF;
+        continue;
+      }
+      vpTargetKFs.push_back(pKFi);
+      pKFi->mnFuseTargetForKF = mpCurrentKeyFrame->mnId;
+      pKFi = pKFi->mPrevKF;
+    }
+  }
+
+  // Search matches by projection from current KF in target KFs
+  ORBmatcher matcher;
+  std::vector<MapPoint*> vpMapPointMatches = mpCurrentKeyFrame->GetMapPointMatches();
+  for (std::vector<KeyFrame*>::iterator vit = vpTargetKFs.begin(), vend = vpTargetKFs.end(); vit != vend; vit++) {
+    KeyFrame* pKFi = *vit;
+    matcher.Fuse(pKFi, vpMapPointMatches);
+    if (pKFi->NLeft != -1) matcher.Fuse(pKFi, vpMapPointMatches, true);
+  }
+
+  if (mbAbortBA) return;
+
+  // Search matches by projection from target KFs in current KF
+  std::vector<MapPoint*> vpFuseCandidates;
+  vpFuseCandidates.reserve(vpTargetKFs.size() * vpMapPointMatches.size());
+  for (std::vector<KeyFrame*>::iterator vitKF = vpTargetKFs.begin(), vendKF = vpTargetKFs.end(); vitKF != vendKF; vitKF++) {
+    KeyFrame* pKFi = *vitKF;
+    std::vector<MapPoint*> vpMapPointsKFi = pKFi->GetMapPointMatches();
+    for (std::vector<MapPoint*>::iterator vitMP = vpMapPointsKFi.begin(), vendMP = vpMapPointsKFi.end(); vitMP != vendMP; vitMP++) {
+      MapPoint* pMP = *vitMP;
+      if (!pMP) continue;
+      if (pMP->isBad() || pMP->mnFuseCandidateForKF == mpCurrentKeyFrame->mnId) continue;
+      pMP->mnFuseCandidateForKF = mpCurrentKeyFrame->mnId;
+      vpFuseCandidates.push_back(pMP);
+    }
+  }
+
+  matcher.Fuse(mpCurrentKeyFrame, vpFuseCandidates);
+  if (mpCurrentKeyFrame->NLeft != -1) matcher.Fuse(mpCurrentKeyFrame, vpFuseCandidates, true);
+
+  // Update points (:837-849): the pairs of all non-bad matches as one batch
+  vpMapPointMatches = mpCurrentKeyFrame->GetMapPointMatches();
+  std::vector<MapPoint*> vpRefresh;
+  for (size_t i = 0, iend = vpMapPointMatches.size(); i < iend; i++) {
+    MapPoint* pMP = vpMapPointMatches[i];
+    if (pMP) {
+      if (!pMP->isBad()) vpRefresh.push_back(pMP);
+    }
+  }
+  MapPoint::RefreshBatch(vpRefresh);
+
+  // Update connections in covisibility graph
+  mpCurrentKeyFrame->UpdateConnections();
 }
 
 }  // namespace ORB_SLAM3

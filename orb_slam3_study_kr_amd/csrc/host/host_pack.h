@@ -650,4 +650,74 @@ inline bool PackNewMapPoints(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<s
   }
   return true;
 }
+
+// ---- MapPoint::RefreshBatch: one batch of osh_orb_refresh_map_points
+// What MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) and UpdateNormalAndDepth (:426-494) read of each point
+// of a list: its observations in map order (a left and a right index of one keyframe are two entries, left first), the descriptor
+// row and the camera centre of each, whether the keyframe is bad, and the level of the reference keyframe's keypoint.
+struct MapPointRefreshPack {
+  std::vector<MapPoint*> points;                        // the occurrences that are refreshed, in list order
+  std::vector<std::pair<KeyFrame*, int>> entry_row;     // per entry: the keyframe and the row of its mDescriptors
+  std::vector<int32_t> entry_off{0}, centre, ref_centre;
+  std::vector<uint8_t> desc, use_desc;
+  std::vector<float> centres, pos, level_scale, top_scale;
+  std::map<KeyFrame*, int> centre_of;                   // the keyframe's left centre in `centres`; the right one follows it on a rig
+  void fill(osh_mappoint_batch& b) const {
+    b.n_points = (int32_t)points.size(); b.entry_off = entry_off.data(); b.desc = desc.data(); b.centre = centre.data();
+    b.use_desc = use_desc.data(); b.n_centres = (int32_t)(centres.size() / 3); b.centres = centres.data(); b.pos = pos.data();
+    b.ref_centre = ref_centre.data(); b.level_scale = level_scale.data(); b.top_scale = top_scale.data();
+  }
+  int centre_index(KeyFrame* pKF) {
+    const auto it = centre_of.find(pKF);
+    if (it != centre_of.end()) return it->second;
+    const int at = (int)(centres.size() / 3);
+    const Eigen::Vector3f Ow = pKF->GetCameraCenter();
+    centres.insert(centres.end(), {Ow(0), Ow(1), Ow(2)});
+    if (pKF->NLeft != -1) {
+      const Eigen::Vector3f Owr = pKF->GetRightCameraCenter();
+      centres.insert(centres.end(), {Owr(0), Owr(1), Owr(2)});
+    }
+    centre_of[pKF] = at;
+    return at;
+  }
+  void add_entry(KeyFrame* pKF, int row, int centre_at) {
+    const uint8_t* d = pKF->mDescriptors.ptr<uint8_t>(row);
+    desc.insert(desc.end(), d, d + 32);
+    entry_row.emplace_back(pKF, row);
+    centre.push_back(centre_at);
+    use_desc.push_back(pKF->isBad() ? 0 : 1);
+  }
+};
+// A bad point, a point without observations (both reference functions return early) and a point without a reference keyframe
+// (the reference dereferences it) are left out.
+inline void PackMapPointRefresh(const std::vector<MapPoint*>& vpMPs, MapPointRefreshPack& pk) {
+  for (MapPoint* pMP : vpMPs) {
+    if (!pMP || pMP->isBad()) continue;
+    std::map<KeyFrame*, std::tuple<int, int>> observations = pMP->GetObservations();
+    KeyFrame* pRefKF = pMP->GetReferenceKeyFrame();
+    if (observations.empty() || !pRefKF) continue;
+    for (const auto& ob : observations) {
+      KeyFrame* pKF = ob.first;
+      const int leftIndex = std::get<0>(ob.second), rightIndex = std::get<1>(ob.second);
+      if (leftIndex == -1 && rightIndex == -1) continue;
+      const int at = pk.centre_index(pKF);
+      if (leftIndex != -1) pk.add_entry(pKF, leftIndex, at);
+      if (rightIndex != -1) pk.add_entry(pKF, rightIndex, at + 1);
+    }
+    // :471-482; observations[pRefKF] default-constructs (0, 0) in the copy when the reference keyframe is not an observer
+    const std::tuple<int, int> indexes = observations[pRefKF];
+    const int leftIndex = std::get<0>(indexes), rightIndex = std::get<1>(indexes);
+    int level;
+    if (pRefKF->NLeft == -1) level = pRefKF->mvKeysUn[leftIndex].octave;
+    else if (leftIndex != -1) level = pRefKF->mvKeys[leftIndex].octave;
+    else level = pRefKF->mvKeysRight[rightIndex - pRefKF->NLeft].octave;
+    const Eigen::Vector3f Pos = pMP->GetWorldPos();
+    pk.points.push_back(pMP);
+    pk.entry_off.push_back((int32_t)pk.centre.size());
+    pk.pos.insert(pk.pos.end(), {Pos(0), Pos(1), Pos(2)});
+    pk.ref_centre.push_back(pk.centre_index(pRefKF));
+    pk.level_scale.push_back(pRefKF->mvScaleFactors[level]);
+    pk.top_scale.push_back(pRefKF->mvScaleFactors[pRefKF->mnScaleLevels - 1]);
+  }
+}
 }  // namespace ORB_SLAM3

@@ -8,6 +8,7 @@
 // osh_orb_triangulate_new_points (newpoint_device.hip) has segments of matched pairs: it uses scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_fast_detect / osh_orb_ic_angle (orb_fast_device.hip) have pyramids: they use pack_level, scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_describe (orb_brief_device.hip) has pyramids or the detector's resident one (orb_fast_state.h): the same helpers.
+// osh_orb_refresh_map_points (mappoint_device.hip) has batches of map points: it uses scatter, PhaseClock, orb_state and copy_times.
 #pragma once
 #include "common.h"
 #include <chrono>

@@ -205,6 +205,130 @@ class HostGraph:
         self.lib.osh_host_get_mp_pos(self.g, j, capi.ptr(o, capi.c_float_p))
         return o
 
+    # ---- the local-mapping steps: MapPoint::RefreshBatch, LocalMapping::SearchInNeighbors / ProcessNewKeyFrame
+    def set_mapping(self, seed: int = 0, max_flips: int = 6, scale_factor: float = 1.2, n_levels: int = 8,
+                    bounds=(0.0, 0.0, 752.0, 480.0), mb: float = 0.110078):
+        """Descriptors (the parent descriptor of the observed point with up to max_flips bits flipped), level tables, image
+        bounds and grid for every keyframe, and the first observing keyframe as every point's reference keyframe.  Keeps
+        kf_desc[k] [rows, 32], kf_octave[k] and kf_point[k] [rows]: left keypoints in observation order, then the right ones of
+        a rig."""
+        w = self.w
+        rng = np.random.default_rng(seed)
+        body = w.edge_kind == capi.OSH_EDGE_BODY
+        octave = np.round(np.log(1.0 / w.edge_info) / np.log(1.44)).astype(np.int32)
+        n_kf = w.n_free + w.n_fixed
+        parent = rng.integers(0, 256, (w.n_points, 32), dtype=np.uint8)
+        self.kf_desc, self.kf_octave, self.kf_point = [], [], []
+        for k in range(n_kf):
+            rows = np.concatenate([np.flatnonzero(~body & (w.edge_pose == k)), np.flatnonzero(body & (w.edge_pose == k))])
+            d = np.zeros((rows.size, 32), np.uint8)
+            for i, e in enumerate(rows):
+                bits = np.unpackbits(parent[w.edge_point[e]])
+                bits[rng.choice(256, size=int(rng.integers(0, max_flips + 1)), replace=False)] ^= 1
+                d[i] = np.packbits(bits)
+            self.kf_desc.append(d)
+            self.kf_octave.append(octave[rows].astype(np.int32))
+            self.kf_point.append(np.asarray(w.edge_point)[rows].astype(np.int32))
+        kf_rows = _i32([d.shape[0] for d in self.kf_desc])
+        desc = np.ascontiguousarray(np.concatenate(self.kf_desc), np.uint8)
+        self.scale_factors = np.ones(n_levels, np.float32)
+        for level in range(1, n_levels):
+            self.scale_factors[level] = self.scale_factors[level - 1] * np.float32(scale_factor)
+        rc = self.lib.osh_host_graph_set_mapping(self.g, float(scale_factor), int(n_levels), capi.ptr(_f32(bounds), capi.c_float_p), float(mb),
+                                                 capi.ptr(kf_rows, capi.c_int32_p), capi.ptr(desc, capi.c_uint8_p))
+        assert rc == 0, rc
+        first = np.full(w.n_points, n_kf, np.int32)
+        np.minimum.at(first, np.asarray(w.edge_point), np.asarray(w.edge_pose, np.int32))
+        first[first == n_kf] = -1
+        self.set_ref_kf(np.arange(w.n_points), first)
+
+    def set_ref_kf(self, mp, kf):
+        mp, kf = _i32(mp), _i32(kf)
+        assert self.lib.osh_host_graph_set_ref_kf(self.g, mp.shape[0], capi.ptr(mp, capi.c_int32_p), capi.ptr(kf, capi.c_int32_p)) == 0
+
+    def unlink(self, kf: int, mp: int, keep_match: bool = False):
+        assert self.lib.osh_host_graph_unlink(self.g, int(kf), int(mp), int(keep_match)) == 0
+
+    def clone_point(self, mp: int, new_id: int, kfs) -> int:
+        kfs = _i32(kfs)
+        j = self.lib.osh_host_graph_clone_point(self.g, int(mp), int(new_id), kfs.shape[0], capi.ptr(kfs, capi.c_int32_p))
+        assert j >= 0
+        return j
+
+    def refresh_batch(self, mps):
+        """MapPoint::RefreshBatch on the points listed (-1: a null entry)."""
+        mps = _i32(mps)
+        assert self.lib.osh_host_mp_refresh_batch(self.g, mps.shape[0], capi.ptr(mps, capi.c_int32_p)) == 0
+
+    def refresh_pack(self, mps) -> dict:
+        """What RefreshBatch packs for the list, without a device."""
+        mps = _i32(mps)
+        sizes = np.zeros(3, np.int32)
+        pointer = {np.dtype(np.int32): capi.c_int32_p, np.dtype(np.uint8): capi.c_uint8_p, np.dtype(np.float32): capi.c_float_p}
+        call = lambda arrays: self.lib.osh_host_mp_refresh_pack(self.g, mps.shape[0], capi.ptr(mps, capi.c_int32_p), capi.ptr(sizes, capi.c_int32_p), *arrays)
+        types = (np.int32,) * 4 + (np.uint8, np.int32, np.uint8, np.float32, np.float32, np.int32, np.float32, np.float32)
+        assert call([C.cast(None, pointer[np.dtype(t)]) for t in types]) == 0
+        P, E, Cn = (int(x) for x in sizes)
+        o = dict(point_mp=np.zeros(P, np.int32), entry_off=np.zeros(P + 1, np.int32), entry_kf=np.zeros(E, np.int32),
+                 entry_row=np.zeros(E, np.int32), desc=np.zeros((E, 32), np.uint8), centre=np.zeros(E, np.int32),
+                 use_desc=np.zeros(E, np.uint8), centres=np.zeros((Cn, 3), np.float32), pos=np.zeros((P, 3), np.float32),
+                 ref_centre=np.zeros(P, np.int32), level_scale=np.zeros(P, np.float32), top_scale=np.zeros(P, np.float32))
+        assert call([capi.ptr(v, pointer[v.dtype]) for v in o.values()]) == 0
+        return o
+
+    def mp_refresh(self, j: int) -> dict:
+        """mDescriptor, mNormalVector, the two distances and the two update counters of point j."""
+        desc, normal, mm, counts = np.zeros(32, np.uint8), np.zeros(3, np.float32), np.zeros(2, np.float32), np.zeros(2, np.int32)
+        has = self.lib.osh_host_mp_get_refresh(self.g, int(j), capi.ptr(desc, capi.c_uint8_p), capi.ptr(normal, capi.c_float_p),
+                                               capi.ptr(mm, capi.c_float_p), capi.ptr(counts, capi.c_int32_p))
+        assert has >= 0
+        return dict(has_desc=bool(has), desc=desc, normal=normal, min_distance=mm[0], max_distance=mm[1],
+                    desc_updates=int(counts[0]), normal_updates=int(counts[1]))
+
+    def mp_observations(self, j: int) -> list:
+        """(keyframe index, left index, right index) in the order the reference walks mObservations."""
+        n = self.lib.osh_host_mp_observations(self.g, int(j), 0, *[C.cast(None, capi.c_int32_p)] * 3)
+        kf, left, right = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+        self.lib.osh_host_mp_observations(self.g, int(j), n, *[capi.ptr(a, capi.c_int32_p) for a in (kf, left, right)])
+        return [(int(kf[i]), int(left[i]), int(right[i])) for i in range(n)]
+
+    def mp_state(self, j: int) -> dict:
+        o = np.zeros(4, np.int64)
+        assert self.lib.osh_host_mp_state(self.g, int(j), capi.ptr(o, capi.c_int64_p)) == 0
+        return dict(bad=bool(o[0]), replaced=int(o[1]), fuse_candidate_for=int(o[2]), ref_kf=int(o[3]))
+
+    def kf_matches(self, k: int) -> np.ndarray:
+        n = self.lib.osh_host_kf_matches(self.g, int(k), 0, C.cast(None, capi.c_int32_p))
+        mp = np.zeros(max(n, 1), np.int32)
+        self.lib.osh_host_kf_matches(self.g, int(k), n, capi.ptr(mp, capi.c_int32_p))
+        return mp[:n]
+
+    def kf_state(self, k: int) -> dict:
+        marks, centres = np.zeros(3, np.int64), np.zeros(6, np.float32)
+        assert self.lib.osh_host_kf_state(self.g, int(k), capi.ptr(marks, capi.c_int64_p), capi.ptr(centres, capi.c_float_p)) == 0
+        return dict(fuse_target_for=int(marks[0]), connection_updates=int(marks[1]), n_left=int(marks[2]), centres=centres.reshape(2, 3))
+
+    def fuse(self, kf: int, mps, th: float = 3.0, right: bool = False) -> int:
+        mps = _i32(mps)
+        return self.lib.osh_host_graph_fuse(self.g, int(kf), mps.shape[0], capi.ptr(mps, capi.c_int32_p), float(th), int(right))
+
+    def set_covisible(self, kf: int, others):
+        others = _i32(others)
+        assert self.lib.osh_host_graph_set_covisible(self.g, int(kf), others.shape[0], capi.ptr(others, capi.c_int32_p)) == 0
+
+    def set_bad(self, kf: int = -1, mp: int = -1):
+        self.lib.osh_host_set_bad(self.g, int(kf), int(mp))
+
+    def search_in_neighbors(self, kf: int | None = None, monocular: bool = False, inertial: bool = False, abort_ba: bool = False):
+        kf = self.cur if kf is None else kf
+        assert self.lib.osh_host_local_mapping_search_in_neighbors(self.g, int(kf), int(monocular), int(inertial), int(abort_ba)) == 0
+
+    def process_new_keyframe(self, kf: int) -> dict:
+        recent, in_map = np.zeros(4096, np.int32), C.c_int32(0)
+        n = self.lib.osh_host_local_mapping_process_new_keyframe(self.g, int(kf), recent.shape[0], capi.ptr(recent, capi.c_int32_p), C.byref(in_map))
+        assert n >= 0
+        return dict(recent=recent[:n].copy(), in_map=int(in_map.value))
+
 
 class HostFrame:
     def __init__(self, xy, octave, desc, angle=None, uright=None, pose_qt=None, mbf=float(synth.BF), mb=0.110078, kb8=None):

@@ -156,6 +156,7 @@ class OrbMatcher:
     stereo_times = functools.partialmethod(_times, "osh_orb_stereo_get_times")                   # of the last stereo_match
     fisheye_stereo_times = functools.partialmethod(_times, "osh_orb_fisheye_stereo_get_times")   # of the last fisheye_stereo_match
     newpoint_times = functools.partialmethod(_times, "osh_orb_newpoint_get_times")               # of the last triangulate_new_points
+    refresh_map_points_times = functools.partialmethod(_times, "osh_orb_refresh_map_points_get_times")   # of the last refresh_map_points
     fast_times = functools.partialmethod(_times, "osh_orb_fast_get_times")                       # of the last fast_detect
     ic_angle_times = functools.partialmethod(_times, "osh_orb_ic_angle_get_times")               # of the last ic_angle
     describe_times = functools.partialmethod(_times, "osh_orb_describe_get_times")               # of the last describe
@@ -193,6 +194,14 @@ class OrbMatcher:
         cos_parallax [n] and x3d [n, 3]."""
         cs, cr, _keep, outs = newpoint_args(segments)
         capi.check(self.lib.osh_orb_triangulate_new_points(self.ctx, len(segments), cs, cr), "osh_orb_triangulate_new_points", self.lib)
+        return outs
+
+    def refresh_map_points(self, batches, want=None) -> list:
+        """MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth (src/MapPoint.cc:329-403,426-494) for a list of
+        synth_mappoints.Batch in one osh_orb_refresh_map_points call: per batch a dict with best_entry, best_median [n],
+        normal [n, 3], min_distance and max_distance [n].  want: the names of the outputs asked for (None: all)."""
+        cb, cr, _keep, outs = mappoint_args(batches, want)
+        capi.check(self.lib.osh_orb_refresh_map_points(self.ctx, len(batches), cb, cr), "osh_orb_refresh_map_points", self.lib)
         return outs
 
     def fast_detect(self, frames, capacities=None, borders=None) -> list:
@@ -796,6 +805,53 @@ def newpoint_cpu(segments, host_lib=None):
     rc = host_lib.osh_host_newpoint_triangulate_cpu(len(segments), cs, cr, C.byref(ms))
     if rc != 0:
         raise RuntimeError(f"osh_host_newpoint_triangulate_cpu -> {rc}")
+    return outs, float(ms.value)
+
+
+_MAPPOINT_ARRAYS = (("entry_off", np.int32), ("desc", np.uint8), ("centre", np.int32), ("use_desc", np.uint8), ("centres", np.float32),
+                    ("pos", np.float32), ("ref_centre", np.int32), ("level_scale", np.float32), ("top_scale", np.float32))
+MAPPOINT_OUTPUTS = ("best_entry", "best_median", "normal", "min_distance", "max_distance")
+
+
+def mappoint_outputs(n: int, want=None, fill=None) -> dict:
+    """The output arrays of one batch of n points; fill = (int32 value, float32 value) presets them (default zeros)."""
+    ifill, ffill = (0, 0.0) if fill is None else fill
+    o = dict(best_entry=np.full(n, ifill, np.int32), best_median=np.full(n, ifill, np.int32), normal=np.full((n, 3), ffill, np.float32),
+             min_distance=np.full(n, ffill, np.float32), max_distance=np.full(n, ffill, np.float32))
+    return {k: v for k, v in o.items() if want is None or k in want}
+
+
+def mappoint_args(batches, want=None, fill=None):
+    """The osh_mappoint_batch / osh_mappoint_result arrays of OrbMatcher.refresh_map_points for repeated calls: (batches, results,
+    the arrays that keep their pointers alive, the per-batch dicts of output arrays).  Outputs not in `want` stay NULL."""
+    n_b = len(batches)
+    cb = (capi.MapPointBatch * max(n_b, 1))()
+    cr = (capi.MapPointResult * max(n_b, 1))()
+    keep, outs = [], []
+    for k, b in enumerate(batches):
+        c = cb[k]
+        a = {}
+        for name, dt in _MAPPOINT_ARRAYS:
+            a[name] = np.ascontiguousarray(getattr(b, name), dt)
+            setattr(c, name, capi.ptr(a[name], _POINTER[np.dtype(dt)]))
+        c.n_points = int(a["entry_off"].shape[0]) - 1
+        c.n_centres = int(a["centres"].reshape(-1, 3).shape[0])
+        o = mappoint_outputs(c.n_points, want, fill)
+        _wire_outputs(cr[k], o)
+        keep.append(a)
+        outs.append(o)
+    return cb, cr, keep, outs
+
+
+def mappoint_cpu(batches, host_lib=None):
+    """csrc/mappoint_refresh.h on the host in one thread (osh_host_mappoint_refresh_cpu of the test library): the per-batch output
+    dicts of refresh_map_points and the wall time of the loops in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    cb, cr, _keep, outs = mappoint_args(batches)
+    ms = C.c_double(0)
+    rc = host_lib.osh_host_mappoint_refresh_cpu(len(batches), cb, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_mappoint_refresh_cpu -> {rc}")
     return outs, float(ms.value)
 
 
