@@ -1,7 +1,8 @@
 /* ORBextractor.h -- the members of ORB_SLAM3::ORBextractor that Frame::ComputeStereoMatches reads (mvImagePyramid, reference
  * include/ORBextractor.h:83) and that ORBextractor::operator() and ORBextractor::ComputeKeyPointsOctTree (csrc/host/ORBextractor.cc)
- * need.  Minimal test double: the constructor (with a generated sampling table of its own), ComputePyramid and DistributeOctTree
- * live in csrc/hosttest/orbextractor.cc; the blur and the descriptors of operator() run on the device (osh_orb_describe). */
+ * need.  Minimal test double: the constructor (with a generated sampling table of its own) and DistributeOctTree live in
+ * csrc/hosttest/orbextractor.cc; ComputePyramid (osh_orb_pyramid_build) and the blur and the descriptors of operator()
+ * (osh_orb_describe) run on the device. */
 #ifndef ORBEXTRACTOR_H
 #define ORBEXTRACTOR_H
 #include <vector>
@@ -38,6 +39,9 @@ class ORBextractor {
   /* ADD THIS MEMBER to the reference's class: the token of the pyramid the last ComputeKeyPointsOctTree left on the device
    * (0: none), which operator() hands to osh_orb_describe */
   uint64_t mnPyramidToken = 0;
+  /* ADD THIS MEMBER too: the token of the pyramid the last ComputePyramid built on the device (0: none).  The next
+   * ComputeKeyPointsOctTree consumes it: while it is valid the detector reads the resident levels, not mvImagePyramid */
+  uint64_t mnBuiltPyramidToken = 0;
 
   /* test double only: every DistributeOctTree call of the last ComputeKeyPointsOctTree, as it was made */
   struct DistributeCall {

@@ -1032,7 +1032,7 @@ int osh_orb_refresh_map_points_get_times(osh_orb_ctx* ctx, double ms[4]);
  * function of the input alone.
  *
  * osh_orb_fast_detect reads the levels in place (rows `stride` bytes apart) and keeps its packed copy on the context until the next
- * osh_orb_fast_detect of that context; pyramid_token names the copy of one frame for osh_orb_ic_angle.  When n_out > capacity (or
+ * osh_orb_fast_detect or osh_orb_pyramid_build of that context; pyramid_token names the copy of one frame for osh_orb_ic_angle.  When n_out > capacity (or
  * used_min_th is given and n_cells > cell_capacity) the counts are written, the arrays of that frame are not, and the call still returns OSH_OK: size the
  * arrays and call again.
  *
@@ -1091,6 +1091,72 @@ int osh_orb_ic_angle(osh_orb_ctx* ctx, int32_t n_frames, const osh_ic_angle_fram
  * scan and the emit), ms[3] download + write-back. */
 int osh_orb_fast_get_times(osh_orb_ctx* ctx, double ms[4]);
 int osh_orb_ic_angle_get_times(osh_orb_ctx* ctx, double ms[4]);
+/* osh_orb_fast_detect over frames of the context's resident pyramid (left by an osh_orb_pyramid_build or an osh_orb_fast_detect):
+ * the same kernels, nothing uploaded but the cells.  The pyramid and its tokens stay valid and results[k].pyramid_token is the
+ * token the frame named.  Refused as osh_orb_fast_detect refuses thresholds, capacities and arrays; a token that names no frame
+ * of the resident pyramid is OSH_ERR_INVALID.  Its phases are read through osh_orb_fast_get_times. */
+typedef struct osh_fast_resident_frame {
+  uint64_t pyramid_token;
+  int32_t ini_th, min_th;
+} osh_fast_resident_frame;
+int osh_orb_fast_detect_resident(osh_orb_ctx* ctx, int32_t n_frames, const osh_fast_resident_frame* frames, osh_fast_result* results);
+
+/* ------------------------------------------------- the image pyramid (ORBextractor::ComputePyramid) */
+/*
+ * ORBextractor::ComputePyramid (src/ORBextractor.cc:1170-1195) for n_frames images in one call: every level is resampled on the
+ * device from the level before it and becomes the context's resident pyramid, one token per frame, which
+ * osh_orb_fast_detect_resident, osh_orb_ic_angle and osh_orb_describe read.  Only the image crosses to the device.  A build takes
+ * its tokens from the counter of osh_orb_fast_detect and replaces the resident pyramid: the tokens of an earlier build or detect
+ * of the context go stale, and an osh_orb_fast_detect does the same to a build's tokens.
+ *
+ * The resampling is defined here.  OpenCV is not available to compare with: what follows is recalled of the 8-bit fixed-point
+ * path of cv::resize(..., INTER_LINEAR) and of copyMakeBorder(BORDER_REFLECT_101) on CV_8UC1, not verified, so PARITY WITH OPENCV
+ * IS NOT PINNED.
+ *   Sizes: level l has cols_l = cvRound((float)cols_0 * inv_scale[l]) columns and rows likewise, always from level 0's size,
+ *   halves to even.  Level 0 must come out at the image's size and is the image; level l > 0 is resampled from level l - 1.
+ *   Tables, one pair per level and axis, computed on the host: scale = 1.0 / ((double)dst / (double)src) and, for d in [0, dst),
+ *   f = (float)((d + 0.5) * scale - 0.5) (a double expression, one cast), s = floor(f), f -= s in float32.  Columns: s < 0 gives
+ *   s = 0, f = 0; s >= src - 1 gives s = src - 1, f = 0 and the second tap is not read.  Rows keep f; the two source rows are
+ *   clamp(s, 0, src - 1) and clamp(s + 1, 0, src - 1).  Weights w0 = cvRound((1.f - f) * 2048.f), w1 = cvRound(f * 2048.f), int16.
+ *   One pixel: h_r = S[r][sx] * a0 + S[r][sx + 1] * a1 (int32) for the two rows,
+ *   out = (uint8)((((b0 * (h_0 >> 4)) >> 16) + ((b1 * (h_1 >> 4)) >> 16) + 2) >> 2).
+ *   Exact halving (src_cols == 2 dst_cols and src_rows == 2 dst_rows): out = (S[2y][2x] + S[2y][2x+1] + S[2y+1][2x] +
+ *   S[2y+1][2x+1] + 2) >> 2.
+ *   Border: index p outside [0, len) maps to m = p mod 2 (len - 1) (non-negative) when m < len, else to 2 (len - 1) - m;
+ *   len == 1 gives 0.
+ * The device computes no table entry; its kernels are integer only.
+ *
+ * results[k].levels == NULL: nothing is downloaded.  Otherwise levels[l].data points at the first pixel of level l inside a larger
+ * image (as mvImagePyramid[l] does inside `temp`), rows and cols are the level's size, and the level with `border` pixels on every
+ * side is written: stride >= cols + 2 border, and `border` rows above and below must exist.
+ *
+ * Refused with OSH_ERR_INVALID before any device work and without a context: an image that is NULL, empty or has stride < cols;
+ * n_levels outside [1, OSH_STEREO_MAX_LEVELS]; a NULL, non-finite or non-positive inv_scale; a level 0 whose size is not the
+ * image's; a level that rounds to 0 pixels in a direction; a negative border; a levels entry that is NULL, has another size than
+ * its level or is under-strided.  With OSH_ERR_UNSUPPORTED a level above OSH_FAST_MAX_SIDE pixels in either direction.  A refused
+ * call leaves the context and its resident pyramid as they were.
+ */
+typedef struct osh_pyramid_image {
+  uint8_t* data;           /* first pixel of the level                                                                          */
+  int32_t rows, cols;
+  int64_t stride;
+} osh_pyramid_image;
+typedef struct osh_pyramid_frame {
+  osh_stereo_image image;            /* read in place                                                                       */
+  int32_t n_levels;
+  const float* inv_scale;            /* [n_levels] mvInvScaleFactor: any finite positive values                             */
+} osh_pyramid_frame;
+typedef struct osh_pyramid_result {
+  uint64_t pyramid_token;            /* out                                                                                 */
+  int32_t* level_rows;               /* [n_levels] out; may be NULL                                                         */
+  int32_t* level_cols;               /* [n_levels] out; may be NULL                                                         */
+  const osh_pyramid_image* levels;   /* [n_levels] where the bordered levels go, or NULL: no download                       */
+  int32_t border;                    /* pixels around every level of `levels` (EDGE_THRESHOLD = 19 in the reference)        */
+} osh_pyramid_result;
+int osh_orb_pyramid_build(osh_orb_ctx* ctx, int32_t n_frames, const osh_pyramid_frame* frames, osh_pyramid_result* results);
+/* Host-clock phases (ms) of the last osh_orb_pyramid_build under osh_orb_set_profiling: ms[0] validation, tables and staging of
+ * the images, ms[1] upload, ms[2] kernels, ms[3] download + the scatter of the rows. */
+int osh_orb_pyramid_get_times(osh_orb_ctx* ctx, double ms[4]);
 
 /* ------------------------------------------------- blur and steered-BRIEF descriptors (ORBextractor) */
 /*

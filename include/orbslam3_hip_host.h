@@ -555,6 +555,35 @@ typedef struct osh_host_extract_output {
 /* Returns _keypoints.size() (the arrays are filled when it and the pyramid fit the capacities).  -1: bad arguments. */
 int osh_host_orbextractor_extract(const osh_host_extract_input* in, const osh_host_extract_output* out);
 
+/* ---- ORBextractor::ComputePyramid (csrc/orb_pyramid.h, csrc/host/ORBextractor.cc, csrc/hosttest/orbextractor.cc) ---- */
+struct osh_pyramid_frame;
+struct osh_pyramid_result;
+/* csrc/orb_pyramid.h (the statements k_pyr_level and k_pyr_border run) compiled for the host, on one thread: arguments as
+ * osh_orb_pyramid_build without a context; pyramid_token comes back 0.  What that call refuses is refused here with the same code
+ * (OSH_ERR_INVALID / OSH_ERR_UNSUPPORTED) and no message.  *ms (may be NULL) = wall time of the loops.  -1: bad arguments. */
+int osh_host_orb_pyramid_cpu(int32_t n_frames, const struct osh_pyramid_frame* frames, struct osh_pyramid_result* results, double* ms);
+/* ORBextractor::ComputePyramid of the stand-in class on the image of `in` (lapping is not read), then ComputeKeyPointsOctTree right
+ * after it (which consumes mnBuiltPyramidToken) and once more after mvImagePyramid has been replaced by a hand-set copy of itself. */
+typedef struct osh_host_pyramid_output {
+  int32_t capacity;           /* keypoints each of the two sets of arrays can take */
+  int32_t pixel_capacity;     /* bytes `bordered` can take */
+  int32_t* level_rows;        /* [nlevels] mvImagePyramid[l].rows */
+  int32_t* level_cols;        /* [nlevels] */
+  uint8_t* bordered;          /* the whole bordered images, (rows + 38) x (cols + 38) each, one after another; may be NULL */
+  int32_t* pixels_needed;     /* [1] bytes of all bordered images */
+  uint64_t* built_token;      /* [2] mnBuiltPyramidToken after ComputePyramid, and after the first ComputeKeyPointsOctTree */
+  int32_t* level_count;       /* [nlevels] allKeypoints[level].size() right after ComputePyramid */
+  float* xy;                  /* [capacity*2] in the pixels of their level; may be NULL */
+  float* angle;               /* [capacity] may be NULL */
+  float* response;            /* [capacity] may be NULL */
+  int32_t* hand_level_count;  /* the same from the hand-set copy */
+  float* hand_xy;
+  float* hand_angle;
+  float* hand_response;
+} osh_host_pyramid_output;
+/* Returns the larger of the two keypoint counts.  -1: bad arguments, -2: the member left something inconsistent. */
+int osh_host_orbextractor_compute_pyramid(const osh_host_extract_input* in, const osh_host_pyramid_output* out);
+
 /* ---- ORBVocabulary / ComputeBoW (include/ORBVocabulary.h, csrc/host/ORBVocabulary.cc, csrc/hosttest/bow.cc) ---- */
 struct osh_bow_tree;
 struct osh_bow_result;

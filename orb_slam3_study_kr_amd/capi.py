@@ -406,6 +406,31 @@ class FastResult(C.Structure):
                 ("level", c_int32_p), ("cell", c_int32_p), ("used_min_th", c_uint8_p)]
 
 
+class FastResidentFrame(C.Structure):
+    """``osh_fast_resident_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("pyramid_token", C.c_uint64), ("ini_th", C.c_int32), ("min_th", C.c_int32)]
+
+
+class PyramidImage(C.Structure):
+    """``osh_pyramid_image`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("data", c_uint8_p), ("rows", C.c_int32), ("cols", C.c_int32), ("stride", C.c_int64)]
+
+
+class PyramidFrame(C.Structure):
+    """``osh_pyramid_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("image", StereoImage), ("n_levels", C.c_int32), ("inv_scale", c_float_p)]
+
+
+class PyramidResult(C.Structure):
+    """``osh_pyramid_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("pyramid_token", C.c_uint64), ("level_rows", c_int32_p), ("level_cols", c_int32_p), ("levels", C.POINTER(PyramidImage)),
+                ("border", C.c_int32)]
+
+
 class IcAngleFrame(C.Structure):
     """``osh_ic_angle_frame`` (include/orbslam3_hip.h)."""
 
@@ -549,6 +574,9 @@ _SIGNATURES = {
     "osh_orb_ic_angle": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult)]),
     "osh_orb_fast_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_ic_angle_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_fast_detect_resident": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FastResidentFrame), C.POINTER(FastResult)]),
+    "osh_orb_pyramid_build": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(PyramidFrame), C.POINTER(PyramidResult)]),
+    "osh_orb_pyramid_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_describe": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(DescribeFrame), C.POINTER(DescribeResult)]),
     "osh_orb_describe_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_bow_tree_check": (C.c_int, [C.POINTER(BowTree)]),
@@ -658,7 +686,18 @@ class HostExtractOutput(C.Structure):
                 ("call_ms", c_double_p)]
 
 
+class HostPyramidOutput(C.Structure):
+    """``osh_host_pyramid_output`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("capacity", C.c_int32), ("pixel_capacity", C.c_int32), ("level_rows", c_int32_p), ("level_cols", c_int32_p),
+                ("bordered", c_uint8_p), ("pixels_needed", c_int32_p), ("built_token", C.POINTER(C.c_uint64)), ("level_count", c_int32_p),
+                ("xy", c_float_p), ("angle", c_float_p), ("response", c_float_p), ("hand_level_count", c_int32_p), ("hand_xy", c_float_p),
+                ("hand_angle", c_float_p), ("hand_response", c_float_p)]
+
+
 _HOST_SIGNATURES = {
+    "osh_host_orb_pyramid_cpu": (C.c_int, [C.c_int32, C.POINTER(PyramidFrame), C.POINTER(PyramidResult), c_double_p]),
+    "osh_host_orbextractor_compute_pyramid": (C.c_int, [C.POINTER(HostExtractInput), C.POINTER(HostPyramidOutput)]),
     "osh_host_orb_describe_cpu": (C.c_int, [C.c_int32, C.POINTER(DescribeFrame), C.POINTER(DescribeResult), c_double_p]),
     "osh_host_brief_gaussian_q8": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_uint16)]),
     "osh_host_brief_reach": (C.c_int, [C.POINTER(C.c_int8)]),

@@ -4,9 +4,16 @@
 // The loops over the cells of every level (:787-872: cv::FAST at iniThFAST, again at minThFAST for a cell without corners) are ONE
 // osh_orb_fast_detect call for the whole pyramid (csrc/orb_fast_device.hip); DistributeOctTree stays the reference's and runs per
 // level on what the device returned, followed by the write-back of :880-890; computeOrientation of all levels (:893-895) is ONE
-// osh_orb_ic_angle call on the pyramid the detector left on the device.  In the integrator's tree the constructor, ComputePyramid,
-// DistributeOctTree stay the reference's; these bodies replace :781-896 and :1086-1168.  ComputeKeyPointsOctTree leaves the
-// detector's pyramid token in the member mnPyramidToken.
+// osh_orb_ic_angle call on the pyramid the detector left on the device.  In the integrator's tree the constructor and
+// DistributeOctTree stay the reference's; these bodies replace :781-896, :1086-1168 and :1170-1195.  ComputeKeyPointsOctTree leaves
+// the detector's pyramid token in the member mnPyramidToken.
+//
+// ComputePyramid (:1170-1195): the bordered `temp` of every level is allocated here and mvImagePyramid[level] is the view into it,
+// as the reference leaves them; cv::resize and copyMakeBorder of all levels are ONE osh_orb_pyramid_build call
+// (csrc/orb_pyramid_device.hip) that keeps the levels on the device and downloads them with their borders.  Its token goes into the
+// member mnBuiltPyramidToken; ComputeKeyPointsOctTree consumes it and, if it is still valid, detects on the resident levels with
+// osh_orb_fast_detect_resident instead of uploading mvImagePyramid (so an edit of mvImagePyramid between the two calls is not seen
+// by the detector).  With the member 0, or a stale token, it does what it did before.
 //
 // operator(): ComputePyramid, ComputeKeyPointsOctTree, then the per-level GaussianBlur and computeDescriptors of :1123-1140 as ONE
 // osh_orb_describe call for all levels (csrc/orb_brief_device.hip) on the pyramid the detector left on the device (or on
@@ -17,11 +24,14 @@
 //   * a level with fewer than 35 columns or rows between its borders has no cells (the reference divides by zero there);
 //   * fastAtan2 is OpenCV's documented scalar form in unfused float32 operations (include/orbslam3_hip.h);
 //   * on a device error, or a pyramid the call refuses, a message goes to stderr and allKeypoints is empty at every level;
+//   * ComputePyramid: the resampling is the one include/orbslam3_hip.h defines (parity with cv::resize is not pinned); on a device
+//     error or a refused call a message goes to stderr and every level of mvImagePyramid is empty;
 //   * operator(): cos and sin of the keypoint angle through the FP64 functions, the sample offsets in unfused float32, the blur as
 //     include/orbslam3_hip.h defines it (parity with cv::GaussianBlur is not pinned); on a device error or a refused call a message
 //     goes to stderr and the result is no keypoints (return value 0, descriptors released).
 #include "ORBextractor.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -32,10 +42,56 @@ namespace ORB_SLAM3 {
 
 osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
 
+void ORBextractor::ComputePyramid(cv::Mat image) {
+  constexpr int kEdge = 19;   // EDGE_THRESHOLD
+  mnBuiltPyramidToken = 0;
+  mvImagePyramid.assign(nlevels > 0 ? nlevels : 0, cv::Mat());
+  if (nlevels <= 0 || image.empty()) return;
+  if ((int)mvInvScaleFactor.size() < nlevels) {
+    std::fprintf(stderr, "ORBextractor::ComputePyramid: mvInvScaleFactor has %d of %d entries\n", (int)mvInvScaleFactor.size(), nlevels);
+    return;
+  }
+  // :1174-1178 per level: the bordered `temp` and mvImagePyramid[level] as the view into it; the sizes are cvRound's
+  std::vector<cv::Mat> levels(nlevels);
+  std::vector<osh_pyramid_image> out(nlevels);
+  for (int level = 0; level < nlevels; ++level) {
+    const float scale = mvInvScaleFactor[level];
+    const float fw = (float)image.cols * scale, fh = (float)image.rows * scale;
+    const int w = fw >= 0.f && fw < 1.0e6f ? (int)std::nearbyint(fw) : 0, h = fh >= 0.f && fh < 1.0e6f ? (int)std::nearbyint(fh) : 0;
+    if (w <= 0 || h <= 0) {
+      std::fprintf(stderr, "ORBextractor::ComputePyramid: level %d has no pixels or too many\n", level);
+      return;
+    }
+    cv::Mat temp(h + 2 * kEdge, w + 2 * kEdge);
+    levels[level] = temp.view(kEdge, kEdge, h, w);
+    out[level].data = levels[level].ptr<uint8_t>(0);
+    out[level].rows = h; out[level].cols = w; out[level].stride = (int64_t)(size_t)levels[level].step;
+  }
+  osh_orb_ctx* ctx = HostMatcherContext();
+  if (!ctx) {
+    std::fprintf(stderr, "ORBextractor::ComputePyramid: %s\n", osh_last_error());
+    return;
+  }
+  // the resize and copyMakeBorder of every level (:1181-1193) in one call; the levels stay on the device under the token
+  osh_pyramid_frame frame{};
+  frame.image.data = image.ptr<uint8_t>(0); frame.image.rows = image.rows; frame.image.cols = image.cols; frame.image.stride = (int64_t)(size_t)image.step;
+  frame.n_levels = nlevels; frame.inv_scale = mvInvScaleFactor.data();
+  osh_pyramid_result res{};
+  res.levels = out.data(); res.border = kEdge;
+  if (osh_orb_pyramid_build(ctx, 1, &frame, &res) != OSH_OK) {
+    std::fprintf(stderr, "ORBextractor::ComputePyramid: %s\n", osh_last_error());
+    return;
+  }
+  mvImagePyramid = levels;
+  mnBuiltPyramidToken = res.pyramid_token;
+}
+
 void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint> >& allKeypoints) {
   allKeypoints.clear();
   allKeypoints.resize(nlevels);
   mnPyramidToken = 0;
+  const uint64_t built = mnBuiltPyramidToken;   // consumed: a later call on a hand-set pyramid must not see it
+  mnBuiltPyramidToken = 0;
   if (nlevels <= 0) return;
   if ((int)mvImagePyramid.size() < nlevels) {
     std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: the pyramid has %d of %d levels\n", (int)mvImagePyramid.size(), nlevels);
@@ -60,10 +116,15 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
   osh_fast_result res{};
   res.level_count = levelCount.data();
   size_t capacity = (size_t)(nfeatures > 0 ? nfeatures : 0) * 10 * (size_t)nlevels;   // vToDistributeKeys.reserve(nfeatures*10) per level
+  // the pyramid ComputePyramid left on the device, if it is still there (another extractor may have used this thread's context in
+  // between: a stale token is refused and the levels of mvImagePyramid go up instead)
+  const osh_fast_resident_frame resident{built, iniThFAST, minThFAST};
+  bool use_resident = built != 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
     xy.resize(capacity * 2); response.resize(capacity);
     res.capacity = (int32_t)capacity; res.xy = xy.data(); res.response = response.data();
-    if (osh_orb_fast_detect(ctx, 1, &frame, &res) != OSH_OK) {
+    if (use_resident && osh_orb_fast_detect_resident(ctx, 1, &resident, &res) != OSH_OK) use_resident = false;
+    if (!use_resident && osh_orb_fast_detect(ctx, 1, &frame, &res) != OSH_OK) {
       std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: %s\n", osh_last_error());
       return;
     }

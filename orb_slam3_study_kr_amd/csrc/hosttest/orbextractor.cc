@@ -1,18 +1,14 @@
 // orbextractor.cc -- what the stand-in ORB_SLAM3::ORBextractor (include/ORBextractor.h) needs around
 // ORBextractor::ComputeKeyPointsOctTree and ORBextractor::operator() (csrc/host/ORBextractor.cc), and the C wrappers that drive them
 // (include/orbslam3_hip_host.h): the constructor (scale tables and mnFeaturesPerLevel as reference src/ORBextractor.cc:409-447, and
-// a generated sampling table), a ComputePyramid and a DistributeOctTree test double, osh_host_orbextractor_compute_keypoints,
-// osh_host_orbextractor_extract, and csrc/orb_fast.h / csrc/orb_brief.h on the host in one thread (osh_host_orb_fast_cpu,
-// osh_host_orb_ic_angle_cpu, osh_host_orb_describe_cpu: the CPU baselines of profiles/fast_timing.py and profiles/brief_timing.py;
-// osh_host_orb_fast_level_cells).  Test library only.
+// a generated sampling table), a DistributeOctTree test double, osh_host_orbextractor_compute_keypoints,
+// osh_host_orbextractor_extract, osh_host_orbextractor_compute_pyramid, and csrc/orb_fast.h / csrc/orb_brief.h / csrc/orb_pyramid.h
+// on the host in one thread (osh_host_orb_fast_cpu, osh_host_orb_ic_angle_cpu, osh_host_orb_describe_cpu, osh_host_orb_pyramid_cpu:
+// the CPU baselines of profiles/fast_timing.py, profiles/brief_timing.py and profiles/pyramid_timing.py;
+// osh_host_orb_fast_level_cells).  Test library only.  ComputePyramid is the product body of csrc/host/ORBextractor.cc.
 //
 // The sampling table is this file's own: 512 points drawn by a fixed linear congruential generator, uniformly in [-13, 12]^2 (so
 // the radius is at most sqrt(338) = 18.38), the first one set to (-13, -13) so that the reach is 19 as for the reference's table.
-//
-// The ComputePyramid here is written from the behaviour: level l has cvRound(size * mvInvScaleFactor[l]) pixels per side, is a view
-// into an image with a 19-pixel border, level 0 is a copy of the input and level l > 0 a bilinear resampling of level l - 1 at
-// pixel centres (float32, rounded to nearest); the border repeats the level by reflect-101 where the level is large enough and
-// by clamping otherwise.  Its pixels are its own and no test compares them with anything.
 //
 // The DistributeOctTree here is written from the behaviour, not taken from the reference: a quadtree over the level's detect area
 // that splits the nodes holding more than one keypoint until there are nFeatures nodes (or nothing left to split), the fullest
@@ -29,6 +25,7 @@
 #include "ORBextractor.h"
 #include "../orb_brief.h"
 #include "../orb_fast.h"
+#include "../orb_pyramid.h"
 #include "orbslam3_hip.h"
 #include "orbslam3_hip_host.h"
 
@@ -60,38 +57,6 @@ ORBextractor::ORBextractor(int _nfeatures, float _scaleFactor, int _nlevels, int
     state = state * 1664525u + 1013904223u; p.y = (int)((state >> 8) % 26u) - 13;
   }
   pattern[0] = cv::Point(-13, -13);
-}
-
-void ORBextractor::ComputePyramid(cv::Mat image) {
-  constexpr int kEdge = 19;   // EDGE_THRESHOLD
-  mvImagePyramid.resize(nlevels);
-  for (int level = 0; level < nlevels; ++level) {
-    const float scale = mvInvScaleFactor[level];
-    const int w = osh::fast_cv_round((float)image.cols * scale), h = osh::fast_cv_round((float)image.rows * scale);
-    if (w <= 0 || h <= 0) { mvImagePyramid[level] = cv::Mat(); continue; }
-    cv::Mat whole(h + 2 * kEdge, w + 2 * kEdge);
-    cv::Mat lv = whole.view(kEdge, kEdge, h, w);
-    const cv::Mat& src = level ? mvImagePyramid[level - 1] : image;
-    if (src.empty()) { mvImagePyramid[level] = cv::Mat(); continue; }
-    for (int y = 0; y < h; ++y) {
-      const float fy = std::min(std::max(((float)y + 0.5f) * (float)src.rows / (float)h - 0.5f, 0.f), (float)(src.rows - 1));
-      const int y0 = (int)fy, y1 = std::min(y0 + 1, src.rows - 1);
-      const float ty = fy - (float)y0;
-      for (int x = 0; x < w; ++x) {
-        const float fx = std::min(std::max(((float)x + 0.5f) * (float)src.cols / (float)w - 0.5f, 0.f), (float)(src.cols - 1));
-        const int x0 = (int)fx, x1 = std::min(x0 + 1, src.cols - 1);
-        const float tx = fx - (float)x0;
-        const float top = (float)src.ptr<uint8_t>(y0)[x0] * (1.f - tx) + (float)src.ptr<uint8_t>(y0)[x1] * tx;
-        const float bot = (float)src.ptr<uint8_t>(y1)[x0] * (1.f - tx) + (float)src.ptr<uint8_t>(y1)[x1] * tx;
-        lv.ptr<uint8_t>(y)[x] = (uint8_t)std::min(std::max((int)std::nearbyint(top * (1.f - ty) + bot * ty), 0), 255);
-      }
-    }
-    auto mirror = [](int i, int n) { return n > kEdge ? osh::brief_reflect101(i, n) : std::min(std::max(i, 0), n - 1); };
-    for (int y = -kEdge; y < h + kEdge; ++y)
-      for (int x = -kEdge; x < w + kEdge; ++x)
-        if (y < 0 || y >= h || x < 0 || x >= w) whole.ptr<uint8_t>(y + kEdge)[x + kEdge] = lv.ptr<uint8_t>(mirror(y, h))[mirror(x, w)];
-    mvImagePyramid[level] = lv;
-  }
 }
 
 namespace {
@@ -205,6 +170,110 @@ extern "C" int osh_host_orb_ic_angle_cpu(int32_t n_frames, const osh_ic_angle_fr
   }
   if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return 0;
+}
+
+extern "C" int osh_host_orb_pyramid_cpu(int32_t n_frames, const osh_pyramid_frame* frames, osh_pyramid_result* results, double* ms) {
+  if (n_frames < 0 || (n_frames && (!frames || !results))) return -1;
+  // the checks of osh_orb_pyramid_build, in its order
+  std::vector<std::vector<int> > rows(n_frames), cols(n_frames);
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_pyramid_frame& f = frames[k];
+    const osh_pyramid_result& r = results[k];
+    if (!f.image.data || f.image.rows <= 0 || f.image.cols <= 0 || f.image.stride < f.image.cols) return OSH_ERR_INVALID;
+    if (f.image.rows > OSH_FAST_MAX_SIDE || f.image.cols > OSH_FAST_MAX_SIDE) return OSH_ERR_UNSUPPORTED;
+    if (f.n_levels < 1 || f.n_levels > OSH_STEREO_MAX_LEVELS || !f.inv_scale || r.border < 0) return OSH_ERR_INVALID;
+    for (int l = 0; l < f.n_levels; ++l) {
+      const float inv = f.inv_scale[l];
+      if (!std::isfinite(inv) || !(inv > 0.f)) return OSH_ERR_INVALID;
+      const int h = osh::pyr_level_size(f.image.rows, inv), w = osh::pyr_level_size(f.image.cols, inv);
+      if (h <= 0 || w <= 0) return OSH_ERR_INVALID;
+      if (l == 0 && (h != f.image.rows || w != f.image.cols)) return OSH_ERR_INVALID;
+      if (h > OSH_FAST_MAX_SIDE || w > OSH_FAST_MAX_SIDE) return OSH_ERR_UNSUPPORTED;
+      if (r.levels && (!r.levels[l].data || r.levels[l].rows != h || r.levels[l].cols != w || r.levels[l].stride < (int64_t)w + 2 * (int64_t)r.border)) return OSH_ERR_INVALID;
+      rows[k].push_back(h); cols[k].push_back(w);
+    }
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_pyramid_frame& f = frames[k];
+    osh_pyramid_result& r = results[k];
+    std::vector<std::vector<uint8_t> > own(f.n_levels);   // the levels nobody asked for
+    const uint8_t* prev = nullptr;
+    long long prev_stride = 0;
+    for (int l = 0; l < f.n_levels; ++l) {
+      const int h = rows[k][l], w = cols[k][l];
+      uint8_t* dst;
+      long long stride;
+      if (r.levels) { dst = r.levels[l].data; stride = (long long)r.levels[l].stride; }
+      else { own[l].resize((size_t)h * w); dst = own[l].data(); stride = w; }
+      if (l == 0) for (int y = 0; y < h; ++y) std::memcpy(dst + y * stride, f.image.data + y * (long long)f.image.stride, (size_t)w);
+      else osh::pyr_resample_level_host(prev, rows[k][l - 1], cols[k][l - 1], prev_stride, dst, h, w, stride);
+      if (r.levels) osh::pyr_border_host(dst, h, w, stride, r.border);
+      if (r.level_rows) r.level_rows[l] = h;
+      if (r.level_cols) r.level_cols[l] = w;
+      prev = dst; prev_stride = stride;
+    }
+    r.pyramid_token = 0;
+  }
+  if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+extern "C" int osh_host_orbextractor_compute_pyramid(const osh_host_extract_input* in, const osh_host_pyramid_output* out) {
+  constexpr int kEdge = 19;
+  if (!in || !out || in->nlevels < 1 || in->rows <= 0 || in->cols <= 0 || !in->pixels || !out->level_rows || !out->level_cols || !out->pixels_needed ||
+      !out->level_count || !out->hand_level_count || !out->built_token || out->capacity < 0 || out->pixel_capacity < 0) return -1;
+  ORBextractor ex(in->nfeatures, in->scale_factor, in->nlevels, in->ini_th, in->min_th);
+  cv::Mat image(in->rows, in->cols);
+  std::memcpy(image.ptr<uint8_t>(0), in->pixels, (size_t)in->rows * in->cols);
+  ex.ComputePyramid(image);
+  out->built_token[0] = ex.mnBuiltPyramidToken; out->built_token[1] = 0;
+  if ((int)ex.mvImagePyramid.size() != in->nlevels) return -2;
+  // the whole bordered images: the levels are views at (19, 19) of them
+  size_t pixels = 0;
+  for (int l = 0; l < in->nlevels; ++l) {
+    const cv::Mat& im = ex.mvImagePyramid[l];
+    out->level_rows[l] = im.rows; out->level_cols[l] = im.cols;
+    if (im.empty()) continue;
+    if (im.step != (size_t)im.cols + 2 * kEdge) return -2;
+    const size_t bytes = (size_t)(im.rows + 2 * kEdge) * im.step;
+    if (out->bordered && pixels + bytes <= (size_t)out->pixel_capacity)
+      for (int r = -kEdge; r < im.rows + kEdge; ++r) std::memcpy(out->bordered + pixels + (size_t)(r + kEdge) * im.step, im.ptr<uint8_t>(0) + (long long)r * (long long)im.step - kEdge, im.step);
+    pixels += bytes;
+  }
+  *out->pixels_needed = (int32_t)pixels;
+  auto report = [&](const std::vector<std::vector<cv::KeyPoint> >& all, int32_t* level_count, float* xy, float* angle, float* response) {
+    size_t n = 0;
+    for (int l = 0; l < in->nlevels; ++l) {
+      level_count[l] = (int32_t)all[l].size();
+      for (const cv::KeyPoint& kp : all[l]) {
+        if (n < (size_t)out->capacity) {
+          if (xy) { xy[2 * n] = kp.pt.x; xy[2 * n + 1] = kp.pt.y; }
+          if (angle) angle[n] = kp.angle;
+          if (response) response[n] = kp.response;
+        }
+        ++n;
+      }
+    }
+    return (int)n;
+  };
+  // ComputeKeyPointsOctTree right after ComputePyramid (the resident levels), then on a hand-set copy of that pyramid
+  std::vector<std::vector<cv::KeyPoint> > all;
+  ex.ComputeKeyPointsOctTree(all);
+  if ((int)all.size() != in->nlevels) return -2;
+  const int n = report(all, out->level_count, out->xy, out->angle, out->response);
+  for (int l = 0; l < in->nlevels; ++l) {
+    const cv::Mat im = ex.mvImagePyramid[l];
+    if (im.empty()) continue;
+    cv::Mat whole(im.rows + 2 * kEdge, im.cols + 2 * kEdge);
+    for (int r = -kEdge; r < im.rows + kEdge; ++r) std::memcpy(whole.ptr<uint8_t>(r + kEdge), im.ptr<uint8_t>(0) + (long long)r * (long long)im.step - kEdge, im.step);
+    ex.mvImagePyramid[l] = whole.view(kEdge, kEdge, im.rows, im.cols);
+  }
+  out->built_token[1] = ex.mnBuiltPyramidToken;   // 0: the first call consumed it
+  ex.ComputeKeyPointsOctTree(all);
+  if ((int)all.size() != in->nlevels) return -2;
+  const int n_hand = report(all, out->hand_level_count, out->hand_xy, out->hand_angle, out->hand_response);
+  return std::max(n, n_hand);
 }
 
 extern "C" int osh_host_orb_fast_level_cells(int32_t rows, int32_t cols, int32_t geom[6], int32_t* rects) {

@@ -182,19 +182,46 @@ __global__ __launch_bounds__(kIcBlock) void k_ic_angle(IcView v) {
   v.angle[i] = fast_atan2((float)m01, (float)m10);
 }
 
-static std::atomic<uint64_t> g_next_token{1};
+// What a detector frame brings besides its pyramid
+static int fast_validate_params(const char* entry, int k, int ini_th, int min_th, const osh_fast_result& r) {
+  if (ini_th < 1 || ini_th > 255 || min_th < 1 || min_th > 255) { set_error("%s: frame %d: threshold outside [1, 255]", entry, k); return OSH_ERR_INVALID; }
+  if (min_th > ini_th) { set_error("%s: frame %d: min_th %d > ini_th %d", entry, k, min_th, ini_th); return OSH_ERR_INVALID; }
+  if (r.capacity < 0 || r.cell_capacity < 0) { set_error("%s: frame %d: negative capacity", entry, k); return OSH_ERR_INVALID; }
+  if (!r.level_count) { set_error("%s: frame %d: NULL level_count", entry, k); return OSH_ERR_INVALID; }
+  if (r.capacity && (!r.xy || !r.response)) { set_error("%s: frame %d: NULL result array with capacity %d", entry, k, r.capacity); return OSH_ERR_INVALID; }
+  return OSH_OK;
+}
 
 static int fast_validate(int n_frames, const osh_fast_frame* frames, const osh_fast_result* results) {
   for (int k = 0; k < n_frames; ++k) {
-    const osh_fast_frame& f = frames[k];
-    const osh_fast_result& r = results[k];
-    OSH_TRY(fast_validate_pyramid("osh_orb_fast_detect", k, f.n_levels, f.pyramid));
-    if (f.ini_th < 1 || f.ini_th > 255 || f.min_th < 1 || f.min_th > 255) { set_error("osh_orb_fast_detect: frame %d: threshold outside [1, 255]", k); return OSH_ERR_INVALID; }
-    if (f.min_th > f.ini_th) { set_error("osh_orb_fast_detect: frame %d: min_th %d > ini_th %d", k, f.min_th, f.ini_th); return OSH_ERR_INVALID; }
-    if (r.capacity < 0 || r.cell_capacity < 0) { set_error("osh_orb_fast_detect: frame %d: negative capacity", k); return OSH_ERR_INVALID; }
-    if (!r.level_count) { set_error("osh_orb_fast_detect: frame %d: NULL level_count", k); return OSH_ERR_INVALID; }
-    if (r.capacity && (!r.xy || !r.response)) { set_error("osh_orb_fast_detect: frame %d: NULL result array with capacity %d", k, r.capacity); return OSH_ERR_INVALID; }
+    OSH_TRY(fast_validate_pyramid("osh_orb_fast_detect", k, frames[k].n_levels, frames[k].pyramid));
+    OSH_TRY(fast_validate_params("osh_orb_fast_detect", k, frames[k].ini_th, frames[k].min_th, results[k]));
   }
+  return OSH_OK;
+}
+
+// The cells of a detector call in (frame, level, i, j) order, frame after frame
+struct FastPlan {
+  std::vector<FastFrameHost> fh;
+  std::vector<FastLevelHost> lh;
+  std::vector<FastCellDev> cells;
+  std::vector<uint64_t> token;   // of every frame, as its result names it
+};
+// One more level of the plan's last frame: rows x cols pixels at img_off of the resident pyramid
+static int fast_plan_level(const char* entry, FastPlan& p, int l, int rows, int cols, long long img_off, int ini_th, int min_th) {
+  const int k = (int)p.fh.size() - 1;
+  FastLevelHost L{img_off, rows, cols, (int)p.cells.size(), 0};
+  const FastGeom g = fast_geometry(rows, cols);
+  FastRect r;
+  for (int i = 0; i < g.n_rows; ++i)
+    for (int j = 0; j < g.n_cols; ++j) {
+      if (!fast_cell_rect(g, i, j, r)) continue;
+      if (r.w > kFastMaxCell || r.h > kFastMaxCell || r.x0 + r.w > cols || r.y0 + r.h > rows) { set_error("%s: frame %d level %d: cell (%d, %d) out of bounds", entry, k, l, i, j); return OSH_ERR_UNSUPPORTED; }
+      p.cells.push_back({L.img_off, cols, r.x0, r.y0, r.w, r.h, j * g.w_cell, i * g.h_cell, l, (int)p.cells.size() - p.fh[k].cell0, ini_th, min_th});
+    }
+  L.n_cells = (int)p.cells.size() - L.cell0;
+  p.lh.push_back(L);
+  if (p.cells.size() > (size_t)1 << 22) { set_error("%s: batch too large", entry); return OSH_ERR_UNSUPPORTED; }
   return OSH_OK;
 }
 
@@ -221,55 +248,18 @@ static int ic_validate_keypoints(int k, const osh_ic_angle_frame& f, int n_level
 
 using namespace osh;
 
-extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_fast_frame* frames, osh_fast_result* results) {
-  PhaseClock clock;
-  if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_fast_detect: bad arguments"); return OSH_ERR_INVALID; }
-  OSH_TRY(fast_validate(n_frames, frames, results));   // a refusal needs no context and no device
-  if (!c) { set_error("osh_orb_fast_detect: no context"); return OSH_ERR_INVALID; }
-  if (n_frames == 0) return OSH_OK;
-
-  // the cells of the call in (frame, level, i, j) order, the levels packed one after another
-  std::vector<FastFrameHost> fh(n_frames);
-  std::vector<FastLevelHost> lh;
-  std::vector<FastCellDev> cells;
-  size_t img_bytes = 0;
-  for (int k = 0; k < n_frames; ++k) {
-    const osh_fast_frame& f = frames[k];
-    fh[k] = {(int)lh.size(), f.n_levels, (int)cells.size(), 0};
-    for (int l = 0; l < f.n_levels; ++l) {
-      const osh_stereo_image& im = f.pyramid[l];
-      FastLevelHost L{(long long)img_bytes, im.rows, im.cols, (int)cells.size(), 0};
-      const FastGeom g = fast_geometry(im.rows, im.cols);
-      FastRect r;
-      for (int i = 0; i < g.n_rows; ++i)
-        for (int j = 0; j < g.n_cols; ++j) {
-          if (!fast_cell_rect(g, i, j, r)) continue;
-          if (r.w > kFastMaxCell || r.h > kFastMaxCell || r.x0 + r.w > im.cols || r.y0 + r.h > im.rows) { set_error("osh_orb_fast_detect: frame %d level %d: cell (%d, %d) out of bounds", k, l, i, j); return OSH_ERR_UNSUPPORTED; }
-          cells.push_back({L.img_off, im.cols, r.x0, r.y0, r.w, r.h, j * g.w_cell, i * g.h_cell, l, (int)cells.size() - fh[k].cell0, f.ini_th, f.min_th});
-        }
-      L.n_cells = (int)cells.size() - L.cell0;
-      lh.push_back(L);
-      img_bytes += (size_t)im.rows * im.cols;
-      if (cells.size() > (size_t)1 << 22 || img_bytes > (size_t)1 << 31) { set_error("osh_orb_fast_detect: batch too large"); return OSH_ERR_UNSUPPORTED; }
-    }
-    fh[k].n_cells = (int)cells.size() - fh[k].cell0;
-  }
-  const int n_cells = (int)cells.size();
+// The kernels of a planned detector call over the resident pyramid and the results of every frame.  `frames` (osh_orb_fast_detect):
+// their levels are staged into st->h_images and uploaded into st->resident first, img_bytes of them; nullptr: the pyramid is there.
+static int fast_run(const char* entry, FastState* st, hipStream_t s, PhaseClock& clock, const FastPlan& p, const osh_fast_frame* frames, size_t img_bytes,
+                    osh_fast_result* results) {
+  const int n_frames = (int)p.fh.size(), n_cells = (int)p.cells.size();
   std::vector<int> order(n_cells);
   std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cells[a].w * cells[a].h > cells[b].w * cells[b].h; });
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  OSH_TRY(orb_stream(c, &device, &s));
-  FastState* st = orb_state<FastState>(c, kOrbAttachFast);
-  clock.profiling = orb_profiling(c);
-  st->token0 = 0;   // the resident pyramid is about to be replaced
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p.cells[a].w * p.cells[a].h > p.cells[b].w * p.cells[b].h; });
 
   Layout in, out, work;
   const auto s_cells = in.take<FastCellDev>(n_cells);
   const auto s_order = in.take<int>(n_cells);
-  const auto s_img = in.take<unsigned char>(img_bytes);
   const auto o_offset = out.take<int>((size_t)n_cells + 1);
   const auto o_used = out.take<unsigned char>(n_cells);
   const auto w_count = work.take<int>(n_cells);
@@ -277,18 +267,24 @@ extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_f
   OSH_TRY(st->call.reserve(in, out, work.bytes));
   char* h = st->call.host_in();
   if (n_cells) {
-    std::memcpy(s_cells.in(h), cells.data(), sizeof(FastCellDev) * n_cells);
+    std::memcpy(s_cells.in(h), p.cells.data(), sizeof(FastCellDev) * n_cells);
     std::memcpy(s_order.in(h), order.data(), sizeof(int) * n_cells);
   }
-  for (int k = 0; k < n_frames; ++k)
-    for (int l = 0; l < frames[k].n_levels; ++l) pack_level(s_img.in(h) + lh[fh[k].level0 + l].img_off, frames[k].pyramid[l]);
+  if (frames) {
+    OSH_TRY(st->resident.reserve(img_bytes));
+    unsigned char* hi = static_cast<unsigned char*>(st->h_images.reserve(img_bytes));
+    if (!hi) { set_error("%s: pinned allocation of %zu bytes failed", entry, img_bytes); return OSH_ERR_DEVICE; }
+    for (int k = 0; k < n_frames; ++k)
+      for (int l = 0; l < frames[k].n_levels; ++l) pack_level(hi + p.lh[p.fh[k].level0 + l].img_off, frames[k].pyramid[l]);
+  }
   clock.mark();
   OSH_TRY(st->call.upload(s));
+  if (frames) OSH_HIP(hipMemcpyAsync(st->resident.p, st->h_images.p, img_bytes, hipMemcpyHostToDevice, s));
   OSH_TRY(clock.mark_synced(s));
 
   FastView v{};
   char* di = st->call.dev_in(); char* dout = st->call.dev_out(); char* dw = st->call.dev_work();
-  v.n_cells = n_cells; v.cells = s_cells.in(di); v.order = s_order.in(di); v.images = s_img.in(di);
+  v.n_cells = n_cells; v.cells = s_cells.in(di); v.order = s_order.in(di); v.images = fast_resident_images(st);
   v.mask = w_mask.in(dw); v.count = w_count.in(dw); v.offset = o_offset.in(dout); v.used_min = o_used.in(dout);
   if (n_cells) hipLaunchKernelGGL(k_fast_cells, dim3((unsigned)n_cells), dim3(kFcBlock), 0, s, v);
   hipLaunchKernelGGL(k_fast_scan, dim3(1), dim3(kScanBlock), 0, s, v);
@@ -303,7 +299,7 @@ extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_f
   const auto e_level = em.take<int>(total); const auto e_cell = em.take<int>(total);
   if (total) {
     OSH_TRY(st->emitted.reserve(em.bytes));
-    if (!st->h_emitted.reserve(em.bytes)) { set_error("osh_orb_fast_detect: pinned allocation of %zu bytes failed", em.bytes); return OSH_ERR_DEVICE; }
+    if (!st->h_emitted.reserve(em.bytes)) { set_error("%s: pinned allocation of %zu bytes failed", entry, em.bytes); return OSH_ERR_DEVICE; }
     char* de = st->emitted.as<char>();
     v.xy = e_xy.in(de); v.response = e_resp.in(de); v.level = e_level.in(de); v.cell = e_cell.in(de);
     hipLaunchKernelGGL(k_fast_emit, dim3((unsigned)n_cells), dim3(64), 0, s, v);
@@ -315,14 +311,13 @@ extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_f
     OSH_HIP(hipStreamSynchronize(s));
   }
   const char* he = static_cast<const char*>(st->h_emitted.p);
-  const uint64_t token0 = g_next_token.fetch_add((uint64_t)n_frames);
   for (int k = 0; k < n_frames; ++k) {
     osh_fast_result& r = results[k];
-    const FastFrameHost& F = fh[k];
+    const FastFrameHost& F = p.fh[k];
     const size_t base = (size_t)offset[F.cell0], n = (size_t)offset[F.cell0 + F.n_cells] - base;
-    r.n_out = (int32_t)n; r.n_cells = F.n_cells; r.pyramid_token = token0 + (uint64_t)k;
+    r.n_out = (int32_t)n; r.n_cells = F.n_cells; r.pyramid_token = p.token[k];
     for (int l = 0; l < F.n_levels; ++l) {
-      const FastLevelHost& L = lh[F.level0 + l];
+      const FastLevelHost& L = p.lh[F.level0 + l];
       r.level_count[l] = offset[L.cell0 + L.n_cells] - offset[L.cell0];
     }
     if (n > (size_t)r.capacity || (r.used_min_th && F.n_cells > r.cell_capacity)) continue;   // counts only: the caller sizes its arrays and calls again
@@ -332,7 +327,69 @@ extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_f
       scatter(r.level, e_level, he, base, n); scatter(r.cell, e_cell, he, base, n);
     }
   }
-  st->frames = std::move(fh); st->levels = std::move(lh); st->img_off = s_img.off; st->token0 = token0;
+  return OSH_OK;
+}
+
+extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_fast_frame* frames, osh_fast_result* results) {
+  PhaseClock clock;
+  if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_fast_detect: bad arguments"); return OSH_ERR_INVALID; }
+  OSH_TRY(fast_validate(n_frames, frames, results));   // a refusal needs no context and no device
+  if (!c) { set_error("osh_orb_fast_detect: no context"); return OSH_ERR_INVALID; }
+  if (n_frames == 0) return OSH_OK;
+
+  // the levels packed one after another
+  FastPlan p;
+  size_t img_bytes = 0;
+  for (int k = 0; k < n_frames; ++k) {
+    const osh_fast_frame& f = frames[k];
+    p.fh.push_back({(int)p.lh.size(), f.n_levels, (int)p.cells.size(), 0});
+    for (int l = 0; l < f.n_levels; ++l) {
+      OSH_TRY(fast_plan_level("osh_orb_fast_detect", p, l, f.pyramid[l].rows, f.pyramid[l].cols, (long long)img_bytes, f.ini_th, f.min_th));
+      img_bytes += (size_t)f.pyramid[l].rows * f.pyramid[l].cols;
+      if (img_bytes > (size_t)1 << 31) { set_error("osh_orb_fast_detect: batch too large"); return OSH_ERR_UNSUPPORTED; }
+    }
+    p.fh[k].n_cells = (int)p.cells.size() - p.fh[k].cell0;
+  }
+
+  int device = 0;
+  hipStream_t s = nullptr;
+  OSH_TRY(orb_stream(c, &device, &s));
+  FastState* st = orb_state<FastState>(c, kOrbAttachFast);
+  clock.profiling = orb_profiling(c);
+  st->token0 = 0;   // the resident pyramid is about to be replaced
+  const uint64_t token0 = g_fast_next_token.fetch_add((uint64_t)n_frames);
+  for (int k = 0; k < n_frames; ++k) p.token.push_back(token0 + (uint64_t)k);
+  OSH_TRY(fast_run("osh_orb_fast_detect", st, s, clock, p, frames, img_bytes, results));
+  st->frames = std::move(p.fh); st->levels = std::move(p.lh); st->token0 = token0;
+  clock.mark();
+  clock.store(st->ms);
+  return OSH_OK;
+}
+
+extern "C" int osh_orb_fast_detect_resident(osh_orb_ctx* c, int32_t n_frames, const osh_fast_resident_frame* frames, osh_fast_result* results) {
+  PhaseClock clock;
+  if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_fast_detect_resident: bad arguments"); return OSH_ERR_INVALID; }
+  for (int k = 0; k < n_frames; ++k) OSH_TRY(fast_validate_params("osh_orb_fast_detect_resident", k, frames[k].ini_th, frames[k].min_th, results[k]));
+  if (!c) { set_error("osh_orb_fast_detect_resident: no context"); return OSH_ERR_INVALID; }
+  if (n_frames == 0) return OSH_OK;
+  FastState* st = orb_state<FastState>(c, kOrbAttachFast);
+  FastPlan p;
+  for (int k = 0; k < n_frames; ++k) {
+    const FastFrameHost* F = fast_resident_frame(st, frames[k].pyramid_token);
+    if (!F) { set_error("osh_orb_fast_detect_resident: frame %d: the token names no frame of this context's resident pyramid", k); return OSH_ERR_INVALID; }
+    p.fh.push_back({(int)p.lh.size(), F->n_levels, (int)p.cells.size(), 0});
+    for (int l = 0; l < F->n_levels; ++l) {
+      const FastLevelHost& L = st->levels[F->level0 + l];
+      OSH_TRY(fast_plan_level("osh_orb_fast_detect_resident", p, l, L.rows, L.cols, L.img_off, frames[k].ini_th, frames[k].min_th));
+    }
+    p.fh[k].n_cells = (int)p.cells.size() - p.fh[k].cell0;
+    p.token.push_back(frames[k].pyramid_token);
+  }
+  int device = 0;
+  hipStream_t s = nullptr;
+  OSH_TRY(orb_stream(c, &device, &s));
+  clock.profiling = orb_profiling(c);
+  OSH_TRY(fast_run("osh_orb_fast_detect_resident", st, s, clock, p, nullptr, 0, results));   // the pyramid and its tokens stay
   clock.mark();
   clock.store(st->ms);
   return OSH_OK;
@@ -357,8 +414,8 @@ extern "C" int osh_orb_ic_angle(osh_orb_ctx* c, int32_t n_frames, const osh_ic_a
   for (int k = 0; k < n_frames; ++k) {
     const osh_ic_angle_frame& f = frames[k];
     if (f.pyramid) continue;
-    if (!st->token0 || f.pyramid_token < st->token0 || f.pyramid_token - st->token0 >= (uint64_t)st->frames.size()) {
-      set_error("osh_orb_ic_angle: frame %d: the token names no frame of this context's last osh_orb_fast_detect", k); return OSH_ERR_INVALID;
+    if (!fast_resident_frame(st, f.pyramid_token)) {
+      set_error("osh_orb_ic_angle: frame %d: the token names no frame of this context's resident pyramid", k); return OSH_ERR_INVALID;
     }
     const FastFrameHost& F = st->frames[(size_t)(f.pyramid_token - st->token0)];
     int rows[OSH_STEREO_MAX_LEVELS], cols[OSH_STEREO_MAX_LEVELS];
@@ -398,7 +455,7 @@ extern "C" int osh_orb_ic_angle(osh_orb_ctx* c, int32_t n_frames, const osh_ic_a
   const auto o_angle = out.take<float>(N); const auto o_m10 = out.take<int>(N); const auto o_m01 = out.take<int>(N);
   OSH_TRY(st->ic_call.reserve(in, out));
   char* h = st->ic_call.host_in();
-  const unsigned char* resident = reinterpret_cast<const unsigned char*>(st->call.dev_in()) + st->img_off;
+  const unsigned char* resident = fast_resident_images(st);
   const unsigned char* uploaded = s_img.in(static_cast<const char*>(st->ic_call.dev_in()));
   for (size_t l = 0; l < lv.size(); ++l) s_levels.in(h)[l] = {(lv[l].resident ? resident : uploaded) + lv[l].off, lv[l].rows, lv[l].cols};
   std::vector<size_t> base(n_frames);

@@ -216,6 +216,26 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_fast_detect(self.ctx, len(frames), cf, cr), "osh_orb_fast_detect", self.lib)
         return _fast_outputs(cr, outs)
 
+    def fast_detect_resident(self, items, capacities=None) -> list:
+        """osh_orb_fast_detect over frames of the resident pyramid in one osh_orb_fast_detect_resident call: items are
+        dict(token, n_levels, ini_th, min_th); the per-frame dicts and `capacities` are those of fast_detect."""
+        if capacities is None:
+            sized = self.fast_detect_resident(items, [(0, 0)] * len(items))
+            capacities = [(r["n_out"], r["n_cells"]) for r in sized]
+        cf, cr, _keep, outs = fast_resident_args(items, capacities)
+        capi.check(self.lib.osh_orb_fast_detect_resident(self.ctx, len(items), cf, cr), "osh_orb_fast_detect_resident", self.lib)
+        return _fast_outputs(cr, outs)
+
+    def pyramid_build(self, items, download: bool = True) -> list:
+        """ORBextractor::ComputePyramid (src/ORBextractor.cc:1170-1195) for a batch of items dict(image uint8 [rows, cols] (rows may
+        be strided), inv_scale [n_levels], optionally border (19)) in one osh_orb_pyramid_build call: per item a dict with token,
+        shapes [(rows, cols)] and, with `download`, levels (views into `bordered`, the whole images with the border around them)."""
+        cf, cr, _keep, outs = pyramid_args(items, download)
+        capi.check(self.lib.osh_orb_pyramid_build(self.ctx, len(items), cf, cr), "osh_orb_pyramid_build", self.lib)
+        return _pyramid_outputs(cr, outs)
+
+    pyramid_times = functools.partialmethod(_times, "osh_orb_pyramid_get_times")                 # of the last pyramid_build
+
     def ic_angle(self, items, borders=None) -> list:
         """IC_Angle (src/ORBextractor.cc:76-103) for a batch of items dict(xy, level, pyramid or token) in one osh_orb_ic_angle
         call: per item a dict with angle, m10, m01."""
@@ -440,6 +460,130 @@ def _fast_outputs(cr, outs):
         d["used_min_th"] = o["used_min_th"][:nc] if fits else None
         res.append(d)
     return res
+
+
+def fast_resident_args(items, capacities):
+    """The osh_fast_resident_frame / osh_fast_result arrays of OrbMatcher.fast_detect_resident for items dict(token, n_levels,
+    ini_th, min_th) and per item a (capacity, cell_capacity)."""
+    n = len(items)
+    cf = (capi.FastResidentFrame * max(n, 1))()
+    cr = (capi.FastResult * max(n, 1))()
+    outs = []
+    for k, it in enumerate(items):
+        cf[k].pyramid_token, cf[k].ini_th, cf[k].min_th = int(it["token"]), int(it["ini_th"]), int(it["min_th"])
+        cap, cell_cap = (int(c) for c in capacities[k])
+        o = dict(level_count=np.zeros(int(it["n_levels"]), np.int32), xy=np.zeros((cap, 2), np.float32), response=np.zeros(cap, np.float32),
+                 level=np.zeros(cap, np.int32), cell=np.zeros(cap, np.int32), used_min_th=np.zeros(cell_cap, np.uint8))
+        cr[k].capacity, cr[k].cell_capacity = cap, cell_cap
+        _wire_outputs(cr[k], o)
+        outs.append(o)
+    return cf, cr, outs, outs
+
+
+def pyramid_level_shapes(rows, cols, inv_scale) -> list:
+    """(rows, cols) of every level as ORBextractor::ComputePyramid sizes them: cvRound((float)size * inv_scale[l]), halves to even."""
+    inv = np.asarray(inv_scale, np.float32)
+    return [(int(np.rint(np.float32(rows) * s)), int(np.rint(np.float32(cols) * s))) for s in inv]
+
+
+def pyramid_args(items, download: bool = True):
+    """The osh_pyramid_frame / osh_pyramid_result arrays of OrbMatcher.pyramid_build for items dict(image, inv_scale, optionally
+    border): (frames, results, keep-alive, per-item dicts of outputs).  The image is read in place: a view with strided rows stays
+    one.  With `download` every level gets a whole image of 167 with `border` pixels around the level."""
+    n = len(items)
+    cf = (capi.PyramidFrame * max(n, 1))()
+    cr = (capi.PyramidResult * max(n, 1))()
+    keep, outs = [], []
+    for k, it in enumerate(items):
+        img = it["image"]
+        assert img.dtype == np.uint8 and img.ndim == 2 and (img.shape[1] == 1 or img.strides[1] == 1)
+        inv = np.ascontiguousarray(it["inv_scale"], np.float32)
+        nl = inv.shape[0]
+        f = cf[k]
+        f.image.data = C.cast(img.ctypes.data, capi.c_uint8_p)
+        f.image.rows, f.image.cols, f.image.stride = img.shape[0], img.shape[1], img.strides[0] if img.shape[0] > 1 else max(img.strides[0], img.shape[1])
+        f.n_levels, f.inv_scale = nl, capi.ptr(inv, capi.c_float_p)
+        a = dict(img=img, inv=inv, level_rows=np.zeros(nl, np.int32), level_cols=np.zeros(nl, np.int32))
+        cr[k].level_rows, cr[k].level_cols = capi.ptr(a["level_rows"], capi.c_int32_p), capi.ptr(a["level_cols"], capi.c_int32_p)
+        o = dict(level_rows=a["level_rows"], level_cols=a["level_cols"])
+        if download:
+            b = int(it.get("border", 19))
+            shapes = pyramid_level_shapes(img.shape[0], img.shape[1], inv)
+            lv = (capi.PyramidImage * max(nl, 1))()
+            o["bordered"], o["levels"] = [], []
+            for l, (r, c) in enumerate(shapes):
+                whole = np.full((max(r, 0) + 2 * b, max(c, 0) + 2 * b), 167, np.uint8)
+                o["bordered"].append(whole)
+                o["levels"].append(whole[b:b + r, b:b + c])
+                lv[l].data = C.cast(whole.ctypes.data + b * whole.shape[1] + b, capi.c_uint8_p)
+                lv[l].rows, lv[l].cols, lv[l].stride = r, c, whole.shape[1]
+            a["lv"] = lv
+            cr[k].levels, cr[k].border = lv, b
+        keep.append(a)
+        outs.append(o)
+    return cf, cr, keep, outs
+
+
+def _pyramid_outputs(cr, outs):
+    res = []
+    for k, o in enumerate(outs):
+        d = dict(o, token=int(cr[k].pyramid_token), shapes=list(zip(o["level_rows"].tolist(), o["level_cols"].tolist())))
+        res.append(d)
+    return res
+
+
+def pyramid_cpu(items, download: bool = True, host_lib=None):
+    """csrc/orb_pyramid.h on the host in one thread (osh_host_orb_pyramid_cpu of the test library): the per-item dicts of
+    OrbMatcher.pyramid_build (token 0) and the wall time of the loops in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    ms = C.c_double(0)
+    cf, cr, _keep, outs = pyramid_args(items, download)
+    rc = host_lib.osh_host_orb_pyramid_cpu(len(items), cf, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_orb_pyramid_cpu -> {rc}")
+    return _pyramid_outputs(cr, outs), float(ms.value)
+
+
+def compute_pyramid(image, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, host_lib=None) -> dict:
+    """ORBextractor::ComputePyramid of the stand-in class on a uint8 image through osh_host_orbextractor_compute_pyramid: shapes,
+    bordered (the whole images, 19 pixels around every level), built_token (after ComputePyramid, after the first
+    ComputeKeyPointsOctTree), and the keypoints of ComputeKeyPointsOctTree right after it (level_count, xy, angle, response) and
+    from a hand-set copy of the pyramid (hand_*)."""
+    host_lib = host_lib or capi.load_host_library()
+    img = np.ascontiguousarray(image, np.uint8)
+    cin = capi.HostExtractInput()
+    cin.nfeatures, cin.scale_factor, cin.nlevels, cin.ini_th, cin.min_th = int(nfeatures), float(scale_factor), int(nlevels), int(ini_th), int(min_th)
+    cin.rows, cin.cols = img.shape
+    cin.pixels = capi.ptr(img, capi.c_uint8_p)
+    cap = pix = 0
+    for _ in range(2):   # the first pass counts
+        o = dict(level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), bordered=np.zeros(max(pix, 1), np.uint8),
+                 pixels_needed=np.zeros(1, np.int32), built_token=np.zeros(2, np.uint64), level_count=np.zeros(nlevels, np.int32),
+                 xy=np.zeros((cap, 2), np.float32), angle=np.zeros(cap, np.float32), response=np.zeros(cap, np.float32),
+                 hand_level_count=np.zeros(nlevels, np.int32), hand_xy=np.zeros((cap, 2), np.float32), hand_angle=np.zeros(cap, np.float32),
+                 hand_response=np.zeros(cap, np.float32))
+        cout = capi.HostPyramidOutput()
+        cout.capacity, cout.pixel_capacity = cap, pix
+        _wire_outputs(cout, o)
+        n = host_lib.osh_host_orbextractor_compute_pyramid(C.byref(cin), C.byref(cout))
+        if n < 0:
+            raise RuntimeError(f"osh_host_orbextractor_compute_pyramid returned {n}")
+        if n <= cap and int(o["pixels_needed"][0]) <= pix:
+            break
+        cap, pix = n, int(o["pixels_needed"][0])
+    n1, n2 = int(o["level_count"].sum()), int(o["hand_level_count"].sum())
+    out = dict(shapes=list(zip(o["level_rows"].tolist(), o["level_cols"].tolist())), built_token=[int(t) for t in o["built_token"]],
+               level_count=o["level_count"], hand_level_count=o["hand_level_count"])
+    for name in ("xy", "angle", "response"):
+        out[name], out["hand_" + name] = o[name][:n1], o["hand_" + name][:n2]
+    out["bordered"], off = [], 0
+    for r, c in out["shapes"]:
+        if r == 0:
+            out["bordered"].append(None)
+            continue
+        out["bordered"].append(o["bordered"][off:off + (r + 38) * (c + 38)].reshape(r + 38, c + 38).copy())
+        off += (r + 38) * (c + 38)
+    return out
 
 
 def ic_angle_args(items, borders=None):

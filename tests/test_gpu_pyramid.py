@@ -1,0 +1,223 @@
+"""ORBextractor::ComputePyramid on the device (osh_orb_pyramid_build) against the numpy restatement of tests/pyramid_numpy.py bit for
+bit, the resident pyramid it leaves under tokens for osh_orb_fast_detect_resident, osh_orb_ic_angle and osh_orb_describe, and the
+member behind the reference signature through the stand-in class."""
+import numpy as np
+import pytest
+
+import brief_numpy as bn
+import pyramid_numpy as pn
+from orb_slam3_study_kr_amd import capi, orb, synth
+from orb_slam3_study_kr_amd import synth_fast as sf
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+
+
+def _check(m, names, what, download=True):
+    got = m.pyramid_build([pn.case(n)[0] for n in names], download=download)
+    for g, n in zip(got, names):
+        pn.assert_same(g, pn.case(n)[1], f"{what}: {n}", download=download)
+        assert g["token"] != 0
+    return got
+
+
+@pytest.mark.parametrize("name", pn.CASE_NAMES)
+def test_committed_cases_equal_the_restatement(hip_lib, name):
+    with orb.OrbMatcher(0) as m:
+        _check(m, [name], "with the download")
+        got = _check(m, [name], "without the download", download=False)
+        # what the call left on the device, read back through the blur export of osh_orb_describe with identity weights
+        shapes = got[0]["shapes"]
+        if min(min(s) for s in shapes) >= 4:
+            it = dict(token=got[0]["token"], shapes=shapes, xy=np.zeros((0, 2), F), level=np.zeros(0, np.int32), angle=np.zeros(0, F),
+                      pattern=np.zeros((512, 2), np.int8), blur_q8=np.asarray([0, 0, 0, 256, 0, 0, 0], np.uint16))
+            back = m.describe([it], debug=True)[0]["blurred"]
+            for l, (b, e) in enumerate(zip(back, pn.case(name)[1]["levels"])):
+                assert np.array_equal(b, e), f"{name}: resident level {l} differs"
+        # the image as a view with strided rows
+        it = pn.case(name)[0]
+        whole = np.full((it["image"].shape[0] + 2, it["image"].shape[1] + 5), 33, np.uint8)
+        view = whole[1:1 + it["image"].shape[0], 2:2 + it["image"].shape[1]]
+        view[:] = it["image"]
+        pn.assert_same(m.pyramid_build([dict(it, image=view)])[0], pn.case(name)[1], name + " strided")
+
+
+MIXED = ["chain_37x53", "halving_40x64", "border3_9x70", "clamps_12x20", "cols_30x41"]
+
+
+def test_batches_equal_single_calls(hip_lib):
+    with orb.OrbMatcher(0) as m:
+        for names in (["tile_17x65"], ["one_row_1x50", "chain_37x53"], MIXED):
+            for download in (True, False):
+                batch = _check(m, names, f"batch of {len(names)}", download)
+                assert [g["token"] for g in batch] == list(range(batch[0]["token"], batch[0]["token"] + len(names)))
+            for k, n in enumerate(names):
+                one = _check(m, [n], f"single {n}")[0]
+                batch = _check(m, names, "again")
+                for a, b in zip(one["bordered"], batch[k]["bordered"]):
+                    assert np.array_equal(a, b)
+        # two frames of equal geometry share their tables and still agree, each with its own pixels
+        a, b = pn.case("cols_30x42")[0], dict(pn.case("cols_30x42")[0], image=pn.image(99, 30, 42))
+        got = m.pyramid_build([a, b, a])
+        pn.assert_same(got[0], pn.case("cols_30x42")[1], "shared tables, frame 0")
+        pn.assert_same(got[2], pn.case("cols_30x42")[1], "shared tables, frame 2")
+        levels, whole = pn.build(b["image"], b["inv_scale"], 19)
+        pn.assert_same(got[1], dict(levels=levels, bordered=whole), "shared tables, frame 1")
+
+
+def _keypoints(levels, seed=3, per_level=12, margin=20):
+    """Keypoints far enough inside every level that is large enough for a descriptor of reach 19."""
+    rng = np.random.default_rng(seed)
+    xy, level = [], []
+    for l, lv in enumerate(levels):
+        if lv.shape[0] < 2 * margin + 1 or lv.shape[1] < 2 * margin + 1:
+            continue
+        for _ in range(per_level):
+            xy.append((rng.integers(margin, lv.shape[1] - margin), rng.integers(margin, lv.shape[0] - margin)))
+            level.append(l)
+    return np.asarray(xy, F).reshape(-1, 2), np.asarray(level, np.int32)
+
+
+def _frame(name="vga_752x480_L8"):
+    it, exp = pn.case(name)
+    return it, exp
+
+
+def _same_detection(a, b, what):
+    assert a["n_out"] == b["n_out"] and a["n_cells"] == b["n_cells"], what
+    for key in ("level_count", "xy", "response", "level", "cell", "used_min_th"):
+        assert np.array_equal(a[key], b[key]), (what, key)
+
+
+SMALL = dict(image=pn.image(41, 120, 160, "smooth"), inv_scale=np.asarray(pn.standin_inv_scale(3), F), border=19)
+
+
+def test_tokens(hip_lib):
+    it = SMALL
+    with orb.OrbMatcher(0) as m, orb.OrbMatcher(0) as other:
+        built = m.pyramid_build([pn.case("chain_37x53")[0], it])
+        token, levels = built[1]["token"], [np.ascontiguousarray(lv) for lv in built[1]["levels"]]
+        pn.assert_same(built[1], dict(zip(("levels", "bordered"), pn.build(it["image"], it["inv_scale"], 19))), "the frame")
+        xy, level = _keypoints(levels)
+        assert len(level) >= 24
+        angle = np.linspace(0, 350, len(level)).astype(F)
+        pattern = orb.standin_pattern()
+        # ic_angle and describe by the build's token equal the same calls handed the downloaded levels
+        by_token = m.ic_angle([dict(xy=xy, level=level, token=token)])[0]
+        by_levels = m.ic_angle([dict(xy=xy, level=level, pyramid=levels)])[0]
+        for key in ("angle", "m10", "m01"):
+            assert np.array_equal(by_token[key].view(np.uint32), by_levels[key].view(np.uint32)), key
+        d_token = m.describe([dict(xy=xy, level=level, angle=angle, pattern=pattern, token=token)])[0]
+        d_levels = m.describe([dict(xy=xy, level=level, angle=angle, pattern=pattern, pyramid=levels)])[0]
+        assert np.array_equal(d_token["descriptors"], d_levels["descriptors"]) and d_token["descriptors"].any()
+        # the resident detector equals the detector on the downloaded levels in every output array; its token still serves describe
+        res = m.fast_detect_resident([dict(token=token, n_levels=3, ini_th=20, min_th=7)])[0]
+        assert res["token"] == token and res["n_out"] > 30
+        ref = other.fast_detect([sf.FastFrame(tuple(levels), 20, 7)])[0]
+        _same_detection(res, ref, "resident against uploaded")
+        both = m.fast_detect_resident([dict(token=built[0]["token"], n_levels=4, ini_th=20, min_th=7), dict(token=token, n_levels=3, ini_th=30, min_th=30)])
+        _same_detection(both[1], other.fast_detect([sf.FastFrame(tuple(levels), 30, 30)])[0], "two resident frames, other thresholds")
+        again = m.describe([dict(xy=xy, level=level, angle=angle, pattern=pattern, token=res["token"])])[0]
+        assert np.array_equal(again["descriptors"], d_token["descriptors"])
+        # a foreign token, and numbers that were never handed out
+        for bad in (ref["token"], 0, 2 ** 63, token + 1):
+            with pytest.raises(capi.OshError) as e:
+                m.fast_detect_resident([dict(token=bad, n_levels=3, ini_th=20, min_th=7)])
+            assert e.value.code == capi.OSH_ERR_INVALID and "token" in str(e.value)
+        with pytest.raises(capi.OshError):
+            other.ic_angle([dict(xy=xy, level=level, token=token)])
+        # a refused build leaves the previous tokens usable
+        with pytest.raises(capi.OshError) as e:
+            m.pyramid_build([dict(it, inv_scale=np.asarray([1, 0.001], F))], download=False)
+        assert e.value.code == capi.OSH_ERR_INVALID and "rounds to 0 pixels" in str(e.value)
+        with pytest.raises(capi.OshError):
+            m.fast_detect_resident([dict(token=token, n_levels=3, ini_th=7, min_th=20)])
+        assert np.array_equal(m.describe([dict(xy=xy, level=level, angle=angle, pattern=pattern, token=token)])[0]["descriptors"], d_token["descriptors"])
+        # a detect stales a build's tokens ...
+        det = m.fast_detect([sf.FastFrame(tuple(levels), 20, 7)])[0]
+        _same_detection(det, ref, "the detector after the buffer moved")
+        with pytest.raises(capi.OshError) as e:
+            m.fast_detect_resident([dict(token=token, n_levels=3, ini_th=20, min_th=7)])
+        assert "token" in str(e.value)
+        _same_detection(m.fast_detect_resident([dict(token=det["token"], n_levels=3, ini_th=20, min_th=7)])[0], ref, "resident after a detect")
+        # ... and a build stales a detect's
+        rebuilt = m.pyramid_build([it], download=False)[0]
+        assert rebuilt["token"] > det["token"]
+        with pytest.raises(capi.OshError) as e:
+            m.ic_angle([dict(xy=xy, level=level, token=det["token"])])
+        assert "token" in str(e.value)
+        _same_detection(m.fast_detect_resident([dict(token=rebuilt["token"], n_levels=3, ini_th=20, min_th=7)])[0], ref, "after the rebuild")
+
+
+@pytest.fixture()
+def zero_new_buffers():
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("OSH_ZERO_NEW_BUFFERS", "1")
+        yield
+
+
+def test_long_lived_context_equals_fresh_contexts(hip_lib, zero_new_buffers):
+    later = [["tiny_3x3"], ["tile_15x63", "halving_40x64"], MIXED[:3], ["chain_37x53"]]
+    pair = synth.make_orb_pair(9, 2000, 2000)
+
+    def step(m, names, k):
+        got = _check(m, names, f"step {k}", download=bool(k % 2 == 0))
+        det = m.fast_detect_resident([dict(token=g["token"], n_levels=len(g["shapes"]), ini_th=20, min_th=7) for g in got])
+        return got, det
+
+    with orb.OrbMatcher(0) as m:
+        m.search([pair])
+        _check(m, ["chain_37x53"], "warm-up")
+        m.pyramid_build([SMALL])
+        m.fast_detect([sf.FastFrame((pn.image(5, 90, 120, "smooth"),), 20, 7)])
+        for k, names in enumerate(later):
+            got, det = step(m, names, k)
+            m.search([pair], windowed=False)
+            with orb.OrbMatcher(0) as fresh:
+                ref, ref_det = step(fresh, names, k)
+            for g, r, d, rd in zip(got, ref, det, ref_det):
+                assert g["shapes"] == r["shapes"]
+                _same_detection(d, rd, f"step {k}")
+                for a, b in zip(g.get("bordered", ()), r.get("bordered", ())):
+                    assert np.array_equal(a, b)
+
+
+def test_one_752x480_frame_of_eight_levels(hip_lib):
+    with orb.OrbMatcher(0) as m:
+        got = _check(m, ["vga_752x480_L8"], "752x480")
+        assert got[0]["shapes"] == sf.level_sizes(480, 752, 8)
+        res = m.fast_detect_resident([dict(token=got[0]["token"], n_levels=8, ini_th=20, min_th=7)])[0]
+        levels = tuple(np.ascontiguousarray(lv) for lv in got[0]["levels"])
+        _same_detection(res, m.fast_detect([sf.FastFrame(levels, 20, 7)])[0], "752x480")
+        assert res["n_out"] > 1000
+
+
+def test_compute_pyramid_through_the_stand_in(hip_lib):
+    img = np.ascontiguousarray(sf.make_image(31, 200, 260))
+    r = orb.compute_pyramid(img, nfeatures=300, nlevels=4)
+    assert r["shapes"] == sf.level_sizes(200, 260, 4)
+    levels, whole = pn.build(img, pn.standin_inv_scale(4), 19)
+    for l, (g, e) in enumerate(zip(r["bordered"], whole)):
+        assert np.array_equal(g, e), f"level {l}: {int((g != e).sum())} pixels of the bordered image differ"
+    # the member: set by ComputePyramid, consumed by ComputeKeyPointsOctTree
+    assert r["built_token"][0] != 0 and r["built_token"][1] == 0
+    # on the resident levels and on a hand-set copy of them the extractor returns the same keypoints
+    assert int(r["level_count"].sum()) > 100 and (r["level_count"] > 0).sum() >= 3
+    assert np.array_equal(r["level_count"], r["hand_level_count"])
+    for key in ("xy", "angle", "response"):
+        assert np.array_equal(r[key].view(np.uint32), r["hand_" + key].view(np.uint32)), key
+    # operator() returns the pyramid the member built
+    e = orb.extract(img, nfeatures=300, nlevels=4)
+    for g, x in zip(e["pyramid"], levels):
+        assert np.array_equal(g, x)
+    assert np.array_equal(e["level_count"], r["level_count"]) and np.array_equal(e["level_xy"], r["xy"])
+
+
+def test_time_slots(hip_lib):
+    with orb.OrbMatcher(0) as m:
+        assert (m.pyramid_times() == 0).all()
+        m.set_profiling(True)
+        got = m.pyramid_build([pn.case("chain_37x53")[0]])
+        assert (m.pyramid_times() > 0).all()
+        m.fast_detect_resident([dict(token=got[0]["token"], n_levels=4, ini_th=20, min_th=7)])
+        assert (m.fast_times() > 0).all()
