@@ -1045,7 +1045,7 @@ int osh_orb_refresh_map_points_get_times(osh_orb_ctx* ctx, double ms[4]);
  * that is NULL, empty or has stride < cols, a threshold outside [1, 255], min_th > ini_th, a negative count or capacity, a NULL
  * array whose count is not 0, a keypoint that is not finite, whose level is outside the pyramid or whose 31-pixel disc would leave
  * its level; with OSH_ERR_UNSUPPORTED a level above OSH_FAST_MAX_SIDE pixels in either direction.  A token that does not name a
- * frame of the context's last osh_orb_fast_detect is refused too.  A refused call leaves the context and its resident pyramid as
+ * frame of the context's resident pyramid is refused too.  A refused call leaves the context and its resident pyramid as
  * they were.
  */
 #define OSH_FAST_MAX_SIDE 32768

@@ -42,6 +42,40 @@ namespace ORB_SLAM3 {
 
 osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
 
+// The levels of mvImagePyramid as the calls read them: in place, views into the bordered images included
+static std::vector<osh_stereo_image> PyramidViews(const std::vector<cv::Mat>& levels, int nlevels) {
+  std::vector<osh_stereo_image> pyramid(nlevels);
+  for (int level = 0; level < nlevels; ++level) {
+    const cv::Mat& im = levels[level];
+    pyramid[level].data = im.empty() ? nullptr : im.ptr<uint8_t>(0);
+    pyramid[level].rows = im.rows; pyramid[level].cols = im.cols; pyramid[level].stride = (int64_t)(size_t)im.step;
+  }
+  return pyramid;
+}
+
+// The `total` keypoints of allKeypoints, level after level, as the arrays of one call; `angle` may be null
+static void FlattenKeypoints(const std::vector<std::vector<cv::KeyPoint> >& allKeypoints, int nlevels, size_t total, std::vector<float>& pts,
+                             std::vector<int32_t>& lvl, std::vector<float>* angle) {
+  pts.resize(total * 2); lvl.resize(total);
+  if (angle) angle->resize(total);
+  size_t n = 0;
+  for (int l = 0; l < nlevels; ++l)
+    for (const cv::KeyPoint& kp : allKeypoints[l]) {
+      pts[2 * n] = kp.pt.x; pts[2 * n + 1] = kp.pt.y; lvl[n] = l;
+      if (angle) (*angle)[n] = kp.angle;
+      ++n;
+    }
+}
+
+// By token while there is one; on a refused token (stale: another extractor used this thread's context in between) or without
+// one, with the pyramid itself.  False: that call was refused too
+template <class ByToken, class ByPyramid>
+static bool ByTokenOrPyramid(bool& have_token, ByToken by_token, ByPyramid by_pyramid) {
+  if (have_token && by_token() == OSH_OK) return true;
+  have_token = false;
+  return by_pyramid() == OSH_OK;
+}
+
 void ORBextractor::ComputePyramid(cv::Mat image) {
   constexpr int kEdge = 19;   // EDGE_THRESHOLD
   mnBuiltPyramidToken = 0;
@@ -103,13 +137,8 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
     return;
   }
 
-  // every cell of every level (:787-872) in one call; the levels are read in place, views into the bordered images included
-  std::vector<osh_stereo_image> pyramid(nlevels);
-  for (int level = 0; level < nlevels; ++level) {
-    const cv::Mat& im = mvImagePyramid[level];
-    pyramid[level].data = im.empty() ? nullptr : im.ptr<uint8_t>(0);
-    pyramid[level].rows = im.rows; pyramid[level].cols = im.cols; pyramid[level].stride = (int64_t)(size_t)im.step;
-  }
+  // every cell of every level (:787-872) in one call
+  const std::vector<osh_stereo_image> pyramid = PyramidViews(mvImagePyramid, nlevels);
   const osh_fast_frame frame{nlevels, pyramid.data(), iniThFAST, minThFAST};
   std::vector<int32_t> levelCount(nlevels);
   std::vector<float> xy, response;
@@ -123,8 +152,7 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
   for (int attempt = 0; attempt < 2; ++attempt) {
     xy.resize(capacity * 2); response.resize(capacity);
     res.capacity = (int32_t)capacity; res.xy = xy.data(); res.response = response.data();
-    if (use_resident && osh_orb_fast_detect_resident(ctx, 1, &resident, &res) != OSH_OK) use_resident = false;
-    if (!use_resident && osh_orb_fast_detect(ctx, 1, &frame, &res) != OSH_OK) {
+    if (!ByTokenOrPyramid(use_resident, [&] { return osh_orb_fast_detect_resident(ctx, 1, &resident, &res); }, [&] { return osh_orb_fast_detect(ctx, 1, &frame, &res); })) {
       std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: %s\n", osh_last_error());
       return;
     }
@@ -156,11 +184,9 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
 
   // the orientation of every kept keypoint (:893-895): all levels in one call, on the pyramid the detector left on the device
   if (total == 0) return;
-  std::vector<float> pts(total * 2), angle(total);
-  std::vector<int32_t> lvl(total);
-  size_t n = 0;
-  for (int l = 0; l < nlevels; ++l)
-    for (const cv::KeyPoint& kp : allKeypoints[l]) { pts[2 * n] = kp.pt.x; pts[2 * n + 1] = kp.pt.y; lvl[n] = l; ++n; }
+  std::vector<float> pts, angle(total);
+  std::vector<int32_t> lvl;
+  FlattenKeypoints(allKeypoints, nlevels, total, pts, lvl, nullptr);
   const osh_ic_angle_frame icf{0, nullptr, res.pyramid_token, (int32_t)total, pts.data(), lvl.data()};
   const osh_ic_angle_result icr{angle.data(), nullptr, nullptr};
   if (osh_orb_ic_angle(ctx, 1, &icf, &icr) != OSH_OK) {
@@ -168,7 +194,7 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
     for (std::vector<cv::KeyPoint>& kps : allKeypoints) kps.clear();
     return;
   }
-  n = 0;
+  size_t n = 0;
   for (std::vector<cv::KeyPoint>& kps : allKeypoints)
     for (cv::KeyPoint& kp : kps) kp.angle = angle[n++];
   mnPyramidToken = res.pyramid_token;
@@ -193,34 +219,26 @@ int ORBextractor::operator()(cv::InputArray _image, cv::InputArray /*_mask*/, st
     osh_orb_ctx* ctx = ok ? HostMatcherContext() : nullptr;
     if (ok && !ctx) { std::fprintf(stderr, "ORBextractor::operator(): %s\n", osh_last_error()); ok = false; }
     if (ok) {
-      std::vector<float> pts((size_t)nkeypoints * 2), angle(nkeypoints);
-      std::vector<int32_t> lvl(nkeypoints);
+      std::vector<float> pts, angle;
+      std::vector<int32_t> lvl;
       int8_t table[1024];
       for (int i = 0; i < 512; ++i) {
         ok = ok && pattern[i].x >= -128 && pattern[i].x <= 127 && pattern[i].y >= -128 && pattern[i].y <= 127;
         table[2 * i] = (int8_t)pattern[i].x; table[2 * i + 1] = (int8_t)pattern[i].y;
       }
       if (!ok) std::fprintf(stderr, "ORBextractor::operator(): a pattern point does not fit 8 bits\n");
-      size_t n = 0;
-      for (int l = 0; l < nlevels; ++l)
-        for (const cv::KeyPoint& kp : allKeypoints[l]) { pts[2 * n] = kp.pt.x; pts[2 * n + 1] = kp.pt.y; angle[n] = kp.angle; lvl[n] = l; ++n; }
-      std::vector<osh_stereo_image> pyramid(nlevels);
-      for (int level = 0; level < nlevels; ++level) {
-        const cv::Mat& im = mvImagePyramid[level];
-        pyramid[level].data = im.empty() ? nullptr : im.ptr<uint8_t>(0);
-        pyramid[level].rows = im.rows; pyramid[level].cols = im.cols; pyramid[level].stride = (int64_t)(size_t)im.step;
-      }
-      osh_describe_frame f{};
-      if (mnPyramidToken) f.pyramid_token = mnPyramidToken;
-      else { f.n_levels = nlevels; f.pyramid = pyramid.data(); }
-      f.n = nkeypoints; f.xy = pts.data(); f.level = lvl.data(); f.angle = angle.data(); f.pattern = table; f.blur_q8 = nullptr;
+      FlattenKeypoints(allKeypoints, nlevels, (size_t)nkeypoints, pts, lvl, &angle);
+      const std::vector<osh_stereo_image> pyramid = PyramidViews(mvImagePyramid, nlevels);
+      osh_describe_frame named{};   // the keypoints on the resident pyramid; `brought`: on the levels of mvImagePyramid
+      named.pyramid_token = mnPyramidToken;
+      named.n = nkeypoints; named.xy = pts.data(); named.level = lvl.data(); named.angle = angle.data(); named.pattern = table; named.blur_q8 = nullptr;
+      osh_describe_frame brought = named;
+      brought.pyramid_token = 0; brought.n_levels = nlevels; brought.pyramid = pyramid.data();
       const osh_describe_result r{desc.data(), nullptr, nullptr};
-      if (ok && osh_orb_describe(ctx, 1, &f, &r) != OSH_OK) {
-        if (mnPyramidToken) {   // a stale token (another extractor used this thread's context in between): the pyramid itself
-          f.pyramid_token = 0; f.n_levels = nlevels; f.pyramid = pyramid.data();
-          ok = osh_orb_describe(ctx, 1, &f, &r) == OSH_OK;
-        } else ok = false;
-        if (!ok) std::fprintf(stderr, "ORBextractor::operator(): %s\n", osh_last_error());
+      bool have_token = mnPyramidToken != 0;
+      if (ok && !ByTokenOrPyramid(have_token, [&] { return osh_orb_describe(ctx, 1, &named, &r); }, [&] { return osh_orb_describe(ctx, 1, &brought, &r); })) {
+        ok = false;
+        std::fprintf(stderr, "ORBextractor::operator(): %s\n", osh_last_error());
       }
     }
     if (!ok) { nkeypoints = 0; for (std::vector<cv::KeyPoint>& kps : allKeypoints) kps.clear(); }

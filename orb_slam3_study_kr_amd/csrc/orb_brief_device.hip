@@ -10,10 +10,10 @@
 //                 to frames with different tables): lane t evaluates pairs t, 64 + t, 128 + t, 192 + t; each of the four ballots
 //                 is eight consecutive descriptor bytes.  No atomic.  The samples are gathered from the blurred level in global
 //                 memory; staging the keypoint's window in LDS first was measured slower.
-// A frame reads the pyramid its token names (the copy osh_orb_fast_detect left on the context) or brings its own.
+// A frame reads the pyramid its token names (the context's resident pyramid) or brings its own: orb_pyramid_set.h.
 #include "common.h"
 #include "orb_brief.h"
-#include "orb_fast_state.h"
+#include "orb_pyramid_set.h"
 #include "orb_stage.h"
 #include <cmath>
 #include <vector>
@@ -77,10 +77,9 @@ __global__ __launch_bounds__(kBlurBlock) void k_orb_blur(const BlurLevelDev* lev
   }
 }
 
-struct BriefLevelDev { const unsigned char* blurred; int rows, cols; };
 struct BriefView {
   int n;
-  const BriefLevelDev* levels;     // of every frame of the call, frame after frame
+  const PyramidLevelDev* levels;   // the blurred levels of every frame of the call, frame after frame
   const int* level_index;          // [n] the keypoint's entry of `levels`
   const int* frame;                // [n] the keypoint's frame: its table
   const float2* xy;                // [n]
@@ -102,10 +101,10 @@ __global__ __launch_bounds__(kBriefBlock) void k_orb_brief(BriefView v) {
   }
   __syncthreads();
   if (!live) return;
-  const BriefLevelDev L = v.levels[v.level_index[i]];
+  const PyramidLevelDev L = v.levels[v.level_index[i]];
   const float2 p = v.xy[i];
   const BriefRot r = brief_rotation(v.angle[i]);
-  const unsigned char* centre = L.blurred + (size_t)fast_cv_round(p.y) * L.cols + fast_cv_round(p.x);
+  const unsigned char* centre = L.data + (size_t)fast_cv_round(p.y) * L.cols + fast_cv_round(p.x);
   unsigned long long bits[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) bits[q] = __ballot(brief_pair(centre, L.cols, r, sh_pattern[wave], 64 * q + lane));
@@ -119,8 +118,8 @@ struct BriefState {
   double ms[4] = {0, 0, 0, 0};
 };
 
-// One frame's table, weights, keypoints and result arrays against the level sizes rows[] / cols[]
-static int brief_validate_frame(int k, const osh_describe_frame& f, const osh_describe_result& r, int n_levels, const int* rows, const int* cols) {
+// One frame's table, weights, keypoints and result arrays against its levels
+static int brief_validate_frame(int k, const osh_describe_frame& f, const osh_describe_result& r, int n_levels, const PyramidLevel* lv) {
   if (f.n < 0) { set_error("osh_orb_describe: frame %d: negative keypoint count", k); return OSH_ERR_INVALID; }
   if (f.n && (!f.xy || !f.level || !f.angle)) { set_error("osh_orb_describe: frame %d: NULL keypoint array with n = %d", k, f.n); return OSH_ERR_INVALID; }
   if (f.n && !r.descriptors) { set_error("osh_orb_describe: frame %d: NULL descriptors with n = %d", k, f.n); return OSH_ERR_INVALID; }
@@ -132,23 +131,19 @@ static int brief_validate_frame(int k, const osh_describe_frame& f, const osh_de
     for (int u = 0; u < kBriefTaps; ++u) sum += f.blur_q8[u];
     if (sum != 256) { set_error("osh_orb_describe: frame %d: the blur weights sum to %d, not 256", k, sum); return OSH_ERR_INVALID; }
   }
-  const int R = brief_reach(f.pattern);
-  for (int i = 0; i < f.n; ++i) {
-    const float x = f.xy[2 * i], y = f.xy[2 * i + 1];
-    const int l = f.level[i];
-    if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(f.angle[i])) { set_error("osh_orb_describe: frame %d: keypoint %d is not finite", k, i); return OSH_ERR_INVALID; }
-    if (l < 0 || l >= n_levels) { set_error("osh_orb_describe: frame %d: keypoint %d: level %d outside [0, %d)", k, i, l, n_levels); return OSH_ERR_INVALID; }
-    // compared as floats first: a coordinate beyond the int range must not reach the conversion
-    bool inside = x >= 0.f && y >= 0.f && x <= (float)OSH_FAST_MAX_SIDE && y <= (float)OSH_FAST_MAX_SIDE && rows[l] >= kBriefMinSide && cols[l] >= kBriefMinSide;
-    if (inside) {
-      const int cx = fast_cv_round(x), cy = fast_cv_round(y);
-      inside = cx - R >= 0 && cx + R < cols[l] && cy - R >= 0 && cy + R < rows[l];
-    }
-    if (!inside) { set_error("osh_orb_describe: frame %d: keypoint %d: the %d-pixel square leaves level %d", k, i, 2 * R + 1, l); return OSH_ERR_INVALID; }
+  bool angles_finite = true;   // the angles are this entry's alone: a pass of their own, without an exit inside it (no branch per keypoint)
+  for (int i = 0; i < f.n; ++i) angles_finite &= std::isfinite(f.angle[i]);
+  for (int i = 0; !angles_finite; ++i)
+    if (!std::isfinite(f.angle[i])) { set_error("osh_orb_describe: frame %d: keypoint %d is not finite", k, i); return OSH_ERR_INVALID; }
+  // a level without a blur holds no keypoint, whatever the table's reach: the keypoints see it as empty
+  PyramidLevel blurred[OSH_STEREO_MAX_LEVELS];
+  int no_blur = -1;
+  for (int l = n_levels - 1; l >= 0; --l) {
+    blurred[l] = lv[l];
+    if (lv[l].rows < kBriefMinSide || lv[l].cols < kBriefMinSide) { blurred[l].rows = blurred[l].cols = 0; no_blur = l; }
   }
-  if (r.blurred)
-    for (int l = 0; l < n_levels; ++l)
-      if (rows[l] < kBriefMinSide || cols[l] < kBriefMinSide) { set_error("osh_orb_describe: frame %d: level %d has fewer than %d rows or columns: no blur", k, l, kBriefMinSide); return OSH_ERR_UNSUPPORTED; }
+  OSH_TRY(validate_keypoints("osh_orb_describe", k, f.n, f.xy, f.level, n_levels, blurred, brief_reach(f.pattern), "square"));
+  if (r.blurred && no_blur >= 0) { set_error("osh_orb_describe: frame %d: level %d has fewer than %d rows or columns: no blur", k, no_blur, kBriefMinSide); return OSH_ERR_UNSUPPORTED; }
   return OSH_OK;
 }
 
@@ -159,28 +154,13 @@ using namespace osh;
 extern "C" int osh_orb_describe(osh_orb_ctx* c, int32_t n_frames, const osh_describe_frame* frames, const osh_describe_result* results) {
   PhaseClock clock;
   if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_describe: bad arguments"); return OSH_ERR_INVALID; }
-  // frames that bring their pyramid first: their refusals need no context and no device
-  bool any_token = false;
-  size_t N = 0;
-  for (int k = 0; k < n_frames; ++k) {
-    const osh_describe_frame& f = frames[k];
-    if (!f.pyramid) { any_token = true; continue; }
-    OSH_TRY(fast_validate_pyramid("osh_orb_describe", k, f.n_levels, f.pyramid));
-    int rows[OSH_STEREO_MAX_LEVELS], cols[OSH_STEREO_MAX_LEVELS];
-    for (int l = 0; l < f.n_levels; ++l) { rows[l] = f.pyramid[l].rows; cols[l] = f.pyramid[l].cols; }
-    OSH_TRY(brief_validate_frame(k, f, results[k], f.n_levels, rows, cols));
-  }
+  PyramidLevels<osh_describe_frame> pl{"osh_orb_describe", n_frames, frames};
+  const auto frame_ok = [&](int k, int n_levels, const PyramidLevel* lv) { return brief_validate_frame(k, frames[k], results[k], n_levels, lv); };
+  OSH_TRY(pl.check_brought(frame_ok));
   if (!c) { set_error("osh_orb_describe: no context"); return OSH_ERR_INVALID; }
-  FastState* fs = any_token ? orb_state<FastState>(c, kOrbAttachFast) : nullptr;
-  for (int k = 0; k < n_frames; ++k) {
-    const osh_describe_frame& f = frames[k];
-    if (f.pyramid) continue;
-    const FastFrameHost* F = fast_resident_frame(fs, f.pyramid_token);
-    if (!F) { set_error("osh_orb_describe: frame %d: the token names no frame of this context's last osh_orb_fast_detect", k); return OSH_ERR_INVALID; }
-    int rows[OSH_STEREO_MAX_LEVELS], cols[OSH_STEREO_MAX_LEVELS];
-    for (int l = 0; l < F->n_levels; ++l) { rows[l] = fs->levels[F->level0 + l].rows; cols[l] = fs->levels[F->level0 + l].cols; }
-    OSH_TRY(brief_validate_frame(k, f, results[k], F->n_levels, rows, cols));
-  }
+  const ResidentPyramid* rp = pl.any_token ? &orb_state<FastState>(c, kOrbAttachFast)->pyramid : nullptr;
+  OSH_TRY(pl.check_tokens(rp, frame_ok));
+  size_t N = 0;
   for (int k = 0; k < n_frames; ++k) N += (size_t)frames[k].n;
   if (N > (size_t)1 << 24) { set_error("osh_orb_describe: more than 2^24 keypoints in one call"); return OSH_ERR_UNSUPPORTED; }
   bool any_blurred = false;
@@ -192,81 +172,68 @@ extern "C" int osh_orb_describe(osh_orb_ctx* c, int32_t n_frames, const osh_desc
   BriefState* st = orb_state<BriefState>(c, kOrbAttachBrief);
   clock.profiling = orb_profiling(c);
 
-  // levels of the call: a frame with a token points into the resident arena of the detector, the others into this call's upload;
-  // the blurred arena packs all of them in this order
-  struct Lv { bool resident; size_t off, blur_off; int rows, cols, frame; bool wanted; };
-  std::vector<Lv> lv;
-  std::vector<int> level0(n_frames), n_levels(n_frames);
-  size_t img_bytes = 0, blur_bytes = 0;
+  // the blurred arena packs the levels of the call in the order of the list; a level is blurred when it holds a keypoint or the
+  // frame asks for its blurred levels
+  OSH_TRY(pl.list(rp));
+  const auto& lv = pl.lv;
+  struct Blur { size_t off; int frame; bool wanted; };
+  std::vector<Blur> blur(lv.size());
+  size_t blur_bytes = 0;
   for (int k = 0; k < n_frames; ++k) {
-    const osh_describe_frame& f = frames[k];
-    level0[k] = (int)lv.size();
-    const bool all = results[k].blurred != nullptr;
-    if (f.pyramid) {
-      n_levels[k] = f.n_levels;
-      for (int l = 0; l < f.n_levels; ++l) {
-        const size_t bytes = (size_t)f.pyramid[l].rows * f.pyramid[l].cols;
-        lv.push_back({false, img_bytes, blur_bytes, f.pyramid[l].rows, f.pyramid[l].cols, k, all});
-        img_bytes += bytes; blur_bytes += bytes;
-      }
-    } else {
-      const FastFrameHost* F = fast_resident_frame(fs, f.pyramid_token);
-      n_levels[k] = F->n_levels;
-      for (int l = 0; l < F->n_levels; ++l) {
-        const FastLevelHost& L = fs->levels[F->level0 + l];
-        lv.push_back({true, (size_t)L.img_off, blur_bytes, L.rows, L.cols, k, all});
-        blur_bytes += (size_t)L.rows * L.cols;
-      }
+    for (int l = pl.level0[k]; l < pl.level0[k] + pl.n_levels[k]; ++l) {
+      blur[l] = {blur_bytes, k, results[k].blurred != nullptr};
+      blur_bytes += (size_t)lv[l].rows * lv[l].cols;
     }
-    for (int i = 0; i < f.n; ++i) lv[level0[k] + f.level[i]].wanted = true;
-    if (img_bytes > (size_t)1 << 31 || blur_bytes > (size_t)1 << 32) { set_error("osh_orb_describe: batch too large"); return OSH_ERR_UNSUPPORTED; }
+    for (int i = 0; i < frames[k].n; ++i) blur[pl.level0[k] + frames[k].level[i]].wanted = true;
+    if (blur_bytes > (size_t)1 << 32) { set_error("osh_orb_describe: batch too large"); return OSH_ERR_UNSUPPORTED; }
   }
   std::vector<BlurTileDev> tiles;
   for (size_t l = 0; l < lv.size(); ++l) {
-    if (!lv[l].wanted) continue;
+    if (!blur[l].wanted) continue;
     const int nty = (lv[l].rows + kBlurTH - 1) / kBlurTH, ntx = (lv[l].cols + kBlurTW - 1) / kBlurTW;
     for (int ty = 0; ty < nty; ++ty) for (int tx = 0; tx < ntx; ++tx) tiles.push_back({(int)l, tx, ty});
   }
 
   Layout in, out;
   const auto s_blur = in.take<BlurLevelDev>(lv.size());
-  const auto s_levels = in.take<BriefLevelDev>(lv.size());
+  const auto s_levels = in.take<PyramidLevelDev>(lv.size());
   const auto s_tiles = in.take<BlurTileDev>(tiles.size());
   const auto s_index = in.take<int>(N);
   const auto s_frame = in.take<int>(N);
   const auto s_xy = in.take<float2>(N);
   const auto s_angle = in.take<float>(N);
   const auto s_pattern = in.take<signed char>((size_t)n_frames * 2 * kBriefPoints);
-  const auto s_img = in.take<unsigned char>(img_bytes);
+  const auto s_img = in.take<unsigned char>(pl.img_bytes);
   const auto o_desc = out.take<unsigned long long>(N * 4);
   const auto o_cs = out.take<float2>(N);
   OSH_TRY(st->call.reserve(in, out));
   OSH_TRY(st->blurred.reserve(blur_bytes));
   char* h = st->call.host_in();
-  const unsigned char* resident = fs ? fast_resident_images(fs) : nullptr;
+  const unsigned char* resident = rp ? rp->images() : nullptr;
   const unsigned char* uploaded = s_img.in(static_cast<const char*>(st->call.dev_in()));
   unsigned char* blurred = st->blurred.as<unsigned char>();
   uint16_t default_w[kBriefTaps];
   brief_gaussian_q8(kBriefTaps, 2.0, default_w);
   for (size_t l = 0; l < lv.size(); ++l) {
     BlurLevelDev& B = s_blur.in(h)[l];
-    B.src = (lv[l].resident ? resident : uploaded) + lv[l].off; B.dst = blurred + lv[l].blur_off; B.rows = lv[l].rows; B.cols = lv[l].cols;
-    const uint16_t* w = frames[lv[l].frame].blur_q8 ? frames[lv[l].frame].blur_q8 : default_w;
+    B.src = pl.data(l, resident, uploaded); B.dst = blurred + blur[l].off; B.rows = lv[l].rows; B.cols = lv[l].cols;
+    const uint16_t* w = frames[blur[l].frame].blur_q8 ? frames[blur[l].frame].blur_q8 : default_w;
     for (int u = 0; u < kBriefTaps; ++u) B.w[u] = w[u];
     B.w[7] = 0;
     s_levels.in(h)[l] = {B.dst, lv[l].rows, lv[l].cols};
   }
   if (!tiles.empty()) std::memcpy(s_tiles.in(h), tiles.data(), sizeof(BlurTileDev) * tiles.size());
+  pl.index(s_index.in(h));
+  pl.stage(s_img.in(h));
   std::vector<size_t> base(n_frames);
   size_t b = 0;
   for (int k = 0; k < n_frames; ++k) {
     const osh_describe_frame& f = frames[k];
     base[k] = b;
     if (f.n) { std::memcpy(s_xy.in(h) + b, f.xy, (size_t)f.n * 8); std::memcpy(s_angle.in(h) + b, f.angle, (size_t)f.n * 4); }
-    for (int i = 0; i < f.n; ++i) { s_index.in(h)[b + i] = level0[k] + f.level[i]; s_frame.in(h)[b + i] = k; }
+    std::fill_n(s_frame.in(h) + b, f.n, k);
     b += (size_t)f.n;
     std::memcpy(s_pattern.in(h) + (size_t)k * 2 * kBriefPoints, f.pattern, 2 * kBriefPoints);
-    if (f.pyramid) for (int l = 0; l < f.n_levels; ++l) pack_level(s_img.in(h) + lv[level0[k] + l].off, f.pyramid[l]);
   }
   clock.mark();
   OSH_TRY(st->call.upload(s));
@@ -287,11 +254,10 @@ extern "C" int osh_orb_describe(osh_orb_ctx* c, int32_t n_frames, const osh_desc
     const size_t n = (size_t)frames[k].n;
     scatter(reinterpret_cast<unsigned long long*>(results[k].descriptors), o_desc, ho, base[k], n, 4);
     scatter(reinterpret_cast<float2*>(results[k].cos_sin), o_cs, ho, base[k], n);
-    if (results[k].blurred && n_levels[k]) {
-      const Lv& first = lv[level0[k]];
-      const Lv& last = lv[level0[k] + n_levels[k] - 1];
-      const size_t bytes = last.blur_off + (size_t)last.rows * last.cols - first.blur_off;
-      OSH_HIP(hipMemcpyAsync(results[k].blurred, blurred + first.blur_off, bytes, hipMemcpyDeviceToHost, s));
+    if (results[k].blurred && pl.n_levels[k]) {
+      const size_t first = blur[pl.level0[k]].off, last = (size_t)pl.level0[k] + pl.n_levels[k] - 1;
+      const size_t bytes = blur[last].off + (size_t)lv[last].rows * lv[last].cols - first;
+      OSH_HIP(hipMemcpyAsync(results[k].blurred, blurred + first, bytes, hipMemcpyDeviceToHost, s));
       OSH_HIP(hipStreamSynchronize(s));
     }
   }

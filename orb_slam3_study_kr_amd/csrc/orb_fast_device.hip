@@ -15,9 +15,8 @@
 // osh_orb_ic_angle: k_ic_angle, one keypoint per lane, reads its 31-pixel disc from the packed level.
 #include "common.h"
 #include "orb_fast.h"
-#include "orb_fast_state.h"
+#include "orb_pyramid_set.h"
 #include "orb_stage.h"
-#include <atomic>
 #include <cmath>
 #include <numeric>
 #include <vector>
@@ -160,10 +159,9 @@ __global__ __launch_bounds__(64) void k_fast_emit(FastView v) {
   }
 }
 
-struct IcLevelDev { const unsigned char* data; int rows, cols; };   // data: first pixel of the packed level on the device
 struct IcView {
   int n;
-  const IcLevelDev* levels;      // of every frame of the call, frame after frame
+  const PyramidLevelDev* levels; // of every frame of the call, frame after frame
   const int* level_index;        // [n] the keypoint's entry of `levels`
   const float2* xy;              // [n]
   float* angle; int* m10; int* m01;
@@ -173,7 +171,7 @@ __global__ __launch_bounds__(kIcBlock) void k_ic_angle(IcView v) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * kIcBlock + threadIdx.x;
   if (i >= v.n) return;
-  const IcLevelDev L = v.levels[v.level_index[i]];
+  const PyramidLevelDev L = v.levels[v.level_index[i]];
   const float2 p = v.xy[i];
   const unsigned char* center = L.data + (size_t)fast_cv_round(p.y) * L.cols + fast_cv_round(p.x);
   int m10, m01;
@@ -205,7 +203,6 @@ struct FastPlan {
   std::vector<FastFrameHost> fh;
   std::vector<FastLevelHost> lh;
   std::vector<FastCellDev> cells;
-  std::vector<uint64_t> token;   // of every frame, as its result names it
 };
 // One more level of the plan's last frame: rows x cols pixels at img_off of the resident pyramid
 static int fast_plan_level(const char* entry, FastPlan& p, int l, int rows, int cols, long long img_off, int ini_th, int min_th) {
@@ -225,23 +222,11 @@ static int fast_plan_level(const char* entry, FastPlan& p, int l, int rows, int 
   return OSH_OK;
 }
 
-// The keypoints of an ic_angle frame against the level sizes rows[] / cols[]
-static int ic_validate_keypoints(int k, const osh_ic_angle_frame& f, int n_levels, const int* rows, const int* cols) {
+// The keypoints of an ic_angle frame against its levels
+static int ic_validate_keypoints(int k, const osh_ic_angle_frame& f, int n_levels, const PyramidLevel* lv) {
   if (f.n < 0) { set_error("osh_orb_ic_angle: frame %d: negative keypoint count", k); return OSH_ERR_INVALID; }
   if (f.n && (!f.xy || !f.level)) { set_error("osh_orb_ic_angle: frame %d: NULL keypoint array with n = %d", k, f.n); return OSH_ERR_INVALID; }
-  for (int i = 0; i < f.n; ++i) {
-    const float x = f.xy[2 * i], y = f.xy[2 * i + 1];
-    const int l = f.level[i];
-    if (!std::isfinite(x) || !std::isfinite(y)) { set_error("osh_orb_ic_angle: frame %d: keypoint %d is not finite", k, i); return OSH_ERR_INVALID; }
-    if (l < 0 || l >= n_levels) { set_error("osh_orb_ic_angle: frame %d: keypoint %d: level %d outside [0, %d)", k, i, l, n_levels); return OSH_ERR_INVALID; }
-    // compared as floats first: a coordinate beyond the int range must not reach the conversion
-    if (!(x >= 0.f && y >= 0.f && x <= (float)OSH_FAST_MAX_SIDE && y <= (float)OSH_FAST_MAX_SIDE)) { set_error("osh_orb_ic_angle: frame %d: keypoint %d: the 31-pixel disc leaves level %d", k, i, l); return OSH_ERR_INVALID; }
-    const int cx = fast_cv_round(x), cy = fast_cv_round(y);
-    if (cx - kFastHalfPatch < 0 || cx + kFastHalfPatch >= cols[l] || cy - kFastHalfPatch < 0 || cy + kFastHalfPatch >= rows[l]) {
-      set_error("osh_orb_ic_angle: frame %d: keypoint %d: the 31-pixel disc leaves level %d", k, i, l); return OSH_ERR_INVALID;
-    }
-  }
-  return OSH_OK;
+  return validate_keypoints("osh_orb_ic_angle", k, f.n, f.xy, f.level, n_levels, lv, kFastHalfPatch, "disc");
 }
 
 }  // namespace osh
@@ -249,7 +234,8 @@ static int ic_validate_keypoints(int k, const osh_ic_angle_frame& f, int n_level
 using namespace osh;
 
 // The kernels of a planned detector call over the resident pyramid and the results of every frame.  `frames` (osh_orb_fast_detect):
-// their levels are staged into st->h_images and uploaded into st->resident first, img_bytes of them; nullptr: the pyramid is there.
+// their levels are staged into st->pyramid.h_images and uploaded into its buffer first, img_bytes of them; nullptr: the pyramid is there.
+// The caller writes the tokens into the results.
 static int fast_run(const char* entry, FastState* st, hipStream_t s, PhaseClock& clock, const FastPlan& p, const osh_fast_frame* frames, size_t img_bytes,
                     osh_fast_result* results) {
   const int n_frames = (int)p.fh.size(), n_cells = (int)p.cells.size();
@@ -271,20 +257,20 @@ static int fast_run(const char* entry, FastState* st, hipStream_t s, PhaseClock&
     std::memcpy(s_order.in(h), order.data(), sizeof(int) * n_cells);
   }
   if (frames) {
-    OSH_TRY(st->resident.reserve(img_bytes));
-    unsigned char* hi = static_cast<unsigned char*>(st->h_images.reserve(img_bytes));
+    OSH_TRY(st->pyramid.buffer.reserve(img_bytes));
+    unsigned char* hi = static_cast<unsigned char*>(st->pyramid.h_images.reserve(img_bytes));
     if (!hi) { set_error("%s: pinned allocation of %zu bytes failed", entry, img_bytes); return OSH_ERR_DEVICE; }
     for (int k = 0; k < n_frames; ++k)
       for (int l = 0; l < frames[k].n_levels; ++l) pack_level(hi + p.lh[p.fh[k].level0 + l].img_off, frames[k].pyramid[l]);
   }
   clock.mark();
   OSH_TRY(st->call.upload(s));
-  if (frames) OSH_HIP(hipMemcpyAsync(st->resident.p, st->h_images.p, img_bytes, hipMemcpyHostToDevice, s));
+  if (frames) OSH_HIP(hipMemcpyAsync(st->pyramid.buffer.p, st->pyramid.h_images.p, img_bytes, hipMemcpyHostToDevice, s));
   OSH_TRY(clock.mark_synced(s));
 
   FastView v{};
   char* di = st->call.dev_in(); char* dout = st->call.dev_out(); char* dw = st->call.dev_work();
-  v.n_cells = n_cells; v.cells = s_cells.in(di); v.order = s_order.in(di); v.images = fast_resident_images(st);
+  v.n_cells = n_cells; v.cells = s_cells.in(di); v.order = s_order.in(di); v.images = st->pyramid.images();
   v.mask = w_mask.in(dw); v.count = w_count.in(dw); v.offset = o_offset.in(dout); v.used_min = o_used.in(dout);
   if (n_cells) hipLaunchKernelGGL(k_fast_cells, dim3((unsigned)n_cells), dim3(kFcBlock), 0, s, v);
   hipLaunchKernelGGL(k_fast_scan, dim3(1), dim3(kScanBlock), 0, s, v);
@@ -315,7 +301,7 @@ static int fast_run(const char* entry, FastState* st, hipStream_t s, PhaseClock&
     osh_fast_result& r = results[k];
     const FastFrameHost& F = p.fh[k];
     const size_t base = (size_t)offset[F.cell0], n = (size_t)offset[F.cell0 + F.n_cells] - base;
-    r.n_out = (int32_t)n; r.n_cells = F.n_cells; r.pyramid_token = p.token[k];
+    r.n_out = (int32_t)n; r.n_cells = F.n_cells;
     for (int l = 0; l < F.n_levels; ++l) {
       const FastLevelHost& L = p.lh[F.level0 + l];
       r.level_count[l] = offset[L.cell0 + L.n_cells] - offset[L.cell0];
@@ -356,11 +342,10 @@ extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_f
   OSH_TRY(orb_stream(c, &device, &s));
   FastState* st = orb_state<FastState>(c, kOrbAttachFast);
   clock.profiling = orb_profiling(c);
-  st->token0 = 0;   // the resident pyramid is about to be replaced
-  const uint64_t token0 = g_fast_next_token.fetch_add((uint64_t)n_frames);
-  for (int k = 0; k < n_frames; ++k) p.token.push_back(token0 + (uint64_t)k);
+  st->pyramid.invalidate();   // the resident pyramid is about to be replaced
   OSH_TRY(fast_run("osh_orb_fast_detect", st, s, clock, p, frames, img_bytes, results));
-  st->frames = std::move(p.fh); st->levels = std::move(p.lh); st->token0 = token0;
+  const uint64_t token0 = st->pyramid.commit(std::move(p.fh), std::move(p.lh));
+  for (int k = 0; k < n_frames; ++k) results[k].pyramid_token = token0 + (uint64_t)k;
   clock.mark();
   clock.store(st->ms);
   return OSH_OK;
@@ -375,21 +360,21 @@ extern "C" int osh_orb_fast_detect_resident(osh_orb_ctx* c, int32_t n_frames, co
   FastState* st = orb_state<FastState>(c, kOrbAttachFast);
   FastPlan p;
   for (int k = 0; k < n_frames; ++k) {
-    const FastFrameHost* F = fast_resident_frame(st, frames[k].pyramid_token);
+    const FastFrameHost* F = st->pyramid.frame(frames[k].pyramid_token);
     if (!F) { set_error("osh_orb_fast_detect_resident: frame %d: the token names no frame of this context's resident pyramid", k); return OSH_ERR_INVALID; }
     p.fh.push_back({(int)p.lh.size(), F->n_levels, (int)p.cells.size(), 0});
     for (int l = 0; l < F->n_levels; ++l) {
-      const FastLevelHost& L = st->levels[F->level0 + l];
+      const FastLevelHost& L = st->pyramid.levels[F->level0 + l];
       OSH_TRY(fast_plan_level("osh_orb_fast_detect_resident", p, l, L.rows, L.cols, L.img_off, frames[k].ini_th, frames[k].min_th));
     }
     p.fh[k].n_cells = (int)p.cells.size() - p.fh[k].cell0;
-    p.token.push_back(frames[k].pyramid_token);
   }
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(orb_stream(c, &device, &s));
   clock.profiling = orb_profiling(c);
   OSH_TRY(fast_run("osh_orb_fast_detect_resident", st, s, clock, p, nullptr, 0, results));   // the pyramid and its tokens stay
+  for (int k = 0; k < n_frames; ++k) results[k].pyramid_token = frames[k].pyramid_token;
   clock.mark();
   clock.store(st->ms);
   return OSH_OK;
@@ -398,30 +383,13 @@ extern "C" int osh_orb_fast_detect_resident(osh_orb_ctx* c, int32_t n_frames, co
 extern "C" int osh_orb_ic_angle(osh_orb_ctx* c, int32_t n_frames, const osh_ic_angle_frame* frames, const osh_ic_angle_result* results) {
   PhaseClock clock;
   if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("osh_orb_ic_angle: bad arguments"); return OSH_ERR_INVALID; }
-  // frames that bring their pyramid first: their refusals need no context and no device
-  bool any_token = false;
-  size_t N = 0;
-  for (int k = 0; k < n_frames; ++k) {
-    const osh_ic_angle_frame& f = frames[k];
-    if (!f.pyramid) { any_token = true; continue; }
-    OSH_TRY(fast_validate_pyramid("osh_orb_ic_angle", k, f.n_levels, f.pyramid));
-    int rows[OSH_STEREO_MAX_LEVELS], cols[OSH_STEREO_MAX_LEVELS];
-    for (int l = 0; l < f.n_levels; ++l) { rows[l] = f.pyramid[l].rows; cols[l] = f.pyramid[l].cols; }
-    OSH_TRY(ic_validate_keypoints(k, f, f.n_levels, rows, cols));
-  }
+  PyramidLevels<osh_ic_angle_frame> pl{"osh_orb_ic_angle", n_frames, frames};
+  const auto keypoints = [&](int k, int n_levels, const PyramidLevel* lv) { return ic_validate_keypoints(k, frames[k], n_levels, lv); };
+  OSH_TRY(pl.check_brought(keypoints));
   if (!c) { set_error("osh_orb_ic_angle: no context"); return OSH_ERR_INVALID; }
-  FastState* st = any_token ? orb_state<FastState>(c, kOrbAttachFast) : nullptr;
-  for (int k = 0; k < n_frames; ++k) {
-    const osh_ic_angle_frame& f = frames[k];
-    if (f.pyramid) continue;
-    if (!fast_resident_frame(st, f.pyramid_token)) {
-      set_error("osh_orb_ic_angle: frame %d: the token names no frame of this context's resident pyramid", k); return OSH_ERR_INVALID;
-    }
-    const FastFrameHost& F = st->frames[(size_t)(f.pyramid_token - st->token0)];
-    int rows[OSH_STEREO_MAX_LEVELS], cols[OSH_STEREO_MAX_LEVELS];
-    for (int l = 0; l < F.n_levels; ++l) { rows[l] = st->levels[F.level0 + l].rows; cols[l] = st->levels[F.level0 + l].cols; }
-    OSH_TRY(ic_validate_keypoints(k, f, F.n_levels, rows, cols));
-  }
+  FastState* st = pl.any_token ? orb_state<FastState>(c, kOrbAttachFast) : nullptr;
+  OSH_TRY(pl.check_tokens(st ? &st->pyramid : nullptr, keypoints));
+  size_t N = 0;
   for (int k = 0; k < n_frames; ++k) N += (size_t)frames[k].n;
   if (N > (size_t)1 << 24) { set_error("osh_orb_ic_angle: more than 2^24 keypoints in one call"); return OSH_ERR_UNSUPPORTED; }
   if (N == 0) return OSH_OK;
@@ -431,42 +399,25 @@ extern "C" int osh_orb_ic_angle(osh_orb_ctx* c, int32_t n_frames, const osh_ic_a
   if (!st) st = orb_state<FastState>(c, kOrbAttachFast);
   clock.profiling = orb_profiling(c);
 
-  // levels of the call: a frame with a token points into the resident arena of the detector, the others into this call's upload
-  struct Lv { bool resident; size_t off; int rows, cols; };
-  std::vector<Lv> lv;
-  std::vector<int> level0(n_frames);
-  size_t img_bytes = 0;
-  for (int k = 0; k < n_frames; ++k) {
-    const osh_ic_angle_frame& f = frames[k];
-    level0[k] = (int)lv.size();
-    if (f.pyramid) {
-      for (int l = 0; l < f.n_levels; ++l) { lv.push_back({false, img_bytes, f.pyramid[l].rows, f.pyramid[l].cols}); img_bytes += (size_t)f.pyramid[l].rows * f.pyramid[l].cols; }
-    } else {
-      const FastFrameHost& F = st->frames[(size_t)(f.pyramid_token - st->token0)];
-      for (int l = 0; l < F.n_levels; ++l) { const FastLevelHost& L = st->levels[F.level0 + l]; lv.push_back({true, (size_t)L.img_off, L.rows, L.cols}); }
-    }
-    if (img_bytes > (size_t)1 << 31) { set_error("osh_orb_ic_angle: batch too large"); return OSH_ERR_UNSUPPORTED; }
-  }
+  OSH_TRY(pl.list(&st->pyramid));
   Layout in, out;
-  const auto s_levels = in.take<IcLevelDev>(lv.size());
+  const auto s_levels = in.take<PyramidLevelDev>(pl.lv.size());
   const auto s_index = in.take<int>(N);
   const auto s_xy = in.take<float2>(N);
-  const auto s_img = in.take<unsigned char>(img_bytes);
+  const auto s_img = in.take<unsigned char>(pl.img_bytes);
   const auto o_angle = out.take<float>(N); const auto o_m10 = out.take<int>(N); const auto o_m01 = out.take<int>(N);
   OSH_TRY(st->ic_call.reserve(in, out));
   char* h = st->ic_call.host_in();
-  const unsigned char* resident = fast_resident_images(st);
   const unsigned char* uploaded = s_img.in(static_cast<const char*>(st->ic_call.dev_in()));
-  for (size_t l = 0; l < lv.size(); ++l) s_levels.in(h)[l] = {(lv[l].resident ? resident : uploaded) + lv[l].off, lv[l].rows, lv[l].cols};
+  for (size_t l = 0; l < pl.lv.size(); ++l) s_levels.in(h)[l] = {pl.data(l, st->pyramid.images(), uploaded), pl.lv[l].rows, pl.lv[l].cols};
+  pl.index(s_index.in(h));
+  pl.stage(s_img.in(h));
   std::vector<size_t> base(n_frames);
   size_t b = 0;
   for (int k = 0; k < n_frames; ++k) {
-    const osh_ic_angle_frame& f = frames[k];
     base[k] = b;
-    if (f.n) std::memcpy(s_xy.in(h) + b, f.xy, (size_t)f.n * 8);
-    for (int i = 0; i < f.n; ++i) s_index.in(h)[b + i] = level0[k] + f.level[i];
-    b += (size_t)f.n;
-    if (f.pyramid) for (int l = 0; l < f.n_levels; ++l) pack_level(s_img.in(h) + lv[level0[k] + l].off, f.pyramid[l]);
+    if (frames[k].n) std::memcpy(s_xy.in(h) + b, frames[k].xy, (size_t)frames[k].n * 8);
+    b += (size_t)frames[k].n;
   }
   clock.mark();
   OSH_TRY(st->ic_call.upload(s));

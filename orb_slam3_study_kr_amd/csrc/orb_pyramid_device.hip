@@ -1,6 +1,6 @@
 // orb_pyramid_device.hip -- ORBextractor::ComputePyramid (src/ORBextractor.cc:1170-1195) on MI355X (gfx950) for a batch of images:
 // every level of every frame is resampled on the device from the level before it and stays there as the context's resident pyramid
-// (orb_fast_state.h), under one token per frame, for osh_orb_fast_detect_resident, osh_orb_ic_angle and osh_orb_describe.  The
+// (orb_pyramid_set.h), under one token per frame, for osh_orb_fast_detect_resident, osh_orb_ic_angle and osh_orb_describe.  The
 // statements are those of orb_pyramid.h; the kernels are integer only and the tap tables are input data computed on the host.
 //
 // osh_orb_pyramid_build:
@@ -15,7 +15,7 @@
 //                  of its own (rows padded to dwords), one D2H copy, and the rows scattered into the caller's images.
 // Level l waits for level l - 1 through the order of the stream: ordinary launches, no barrier across blocks.
 #include "common.h"
-#include "orb_fast_state.h"
+#include "orb_pyramid_set.h"
 #include "orb_pyramid.h"
 #include "orb_stage.h"
 #include <cmath>
@@ -215,7 +215,7 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
   OSH_TRY(orb_stream(c, &device, &s));
   FastState* st = orb_state<FastState>(c, kOrbAttachFast);
   clock.profiling = orb_profiling(c);
-  st->token0 = 0;   // the resident pyramid is about to be replaced
+  st->pyramid.invalidate();   // the resident pyramid is about to be replaced
 
   Layout in, out;
   const auto s_jobs = in.take<PyrJobDev>(jobs.size());
@@ -223,8 +223,8 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
   const auto s_taps = in.take<PyrTap>(taps.size());
   out.take<int>(1);   // nothing comes back through this staging; an empty region has no pinned buffer
   OSH_TRY(st->pyr_call.reserve(in, out));
-  OSH_TRY(st->resident.reserve(bytes));
-  unsigned char* hi = static_cast<unsigned char*>(st->h_images.reserve(img0_bytes));
+  OSH_TRY(st->pyramid.buffer.reserve(bytes));
+  unsigned char* hi = static_cast<unsigned char*>(st->pyramid.h_images.reserve(img0_bytes));
   if (!hi) { set_error("%s: pinned allocation of %zu bytes failed", entry, img0_bytes); return OSH_ERR_DEVICE; }
   if (bordered_bytes) {
     OSH_TRY(st->bordered.reserve(bordered_bytes));
@@ -237,13 +237,13 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
   for (int k = 0; k < n_frames; ++k) pack_level(hi + lh[fh[k].level0].img_off, frames[k].image);
   clock.mark();
   OSH_TRY(st->pyr_call.upload(s));
-  OSH_HIP(hipMemcpyAsync(st->resident.p, hi, img0_bytes, hipMemcpyHostToDevice, s));
+  OSH_HIP(hipMemcpyAsync(st->pyramid.buffer.p, hi, img0_bytes, hipMemcpyHostToDevice, s));
   OSH_TRY(clock.mark_synced(s));
 
   PyrView v{};
   char* di = st->pyr_call.dev_in();
   v.jobs = s_jobs.in(di); v.border_jobs = s_bjobs.in(di); v.taps = s_taps.in(di);
-  v.images = st->resident.as<unsigned char>(); v.bordered = st->bordered.as<unsigned char>();
+  v.images = st->pyramid.buffer.as<unsigned char>(); v.bordered = st->bordered.as<unsigned char>();
   for (int l = 1; l < OSH_STEREO_MAX_LEVELS; ++l) {
     const int n = level_job0[l + 1] - level_job0[l];
     if (n) hipLaunchKernelGGL(k_pyr_level, dim3((unsigned)level_tiles[l], (unsigned)n), dim3(kPyrBlockX, kPyrBlockY), 0, s, v, level_job0[l]);
@@ -263,7 +263,7 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
         std::memcpy(o.data + (long long)y * o.stride - J.border, hb + J.dst_off + (size_t)(y + J.border) * J.pitch, (size_t)J.cols + 2 * (size_t)J.border);
     }
   }
-  const uint64_t token0 = g_fast_next_token.fetch_add((uint64_t)n_frames);
+  const uint64_t token0 = st->pyramid.commit(std::move(fh), std::move(lh));
   for (int k = 0; k < n_frames; ++k) {
     results[k].pyramid_token = token0 + (uint64_t)k;
     for (int l = 0; l < frames[k].n_levels; ++l) {
@@ -271,7 +271,6 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
       if (results[k].level_cols) results[k].level_cols[l] = sz[k].cols[l];
     }
   }
-  st->frames = std::move(fh); st->levels = std::move(lh); st->token0 = token0;
   clock.mark();
   clock.store(st->ms_pyr);
   return OSH_OK;

@@ -6,8 +6,9 @@
 // osh_orb_bow_transform (bow_device.hip) has frames of descriptors only: it uses scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_bow_db_query (bowdb_device.hip) has queries against a database: it uses PhaseClock, orb_state and copy_times.
 // osh_orb_triangulate_new_points (newpoint_device.hip) has segments of matched pairs: it uses scatter, PhaseClock, orb_state and copy_times.
-// osh_orb_fast_detect / osh_orb_ic_angle (orb_fast_device.hip) have pyramids: they use pack_level, scatter, PhaseClock, orb_state and copy_times.
-// osh_orb_describe (orb_brief_device.hip) has pyramids or the detector's resident one (orb_fast_state.h): the same helpers.
+// osh_orb_fast_detect / osh_orb_ic_angle (orb_fast_device.hip) and osh_orb_describe (orb_brief_device.hip) have pyramids, brought
+// along or resident on the context: orb_pyramid_set.h, built on pack_level, is their level list; they use scatter, PhaseClock,
+// orb_state and copy_times.  osh_orb_pyramid_build (orb_pyramid_device.hip) fills the resident pyramid: pack_level, PhaseClock, orb_state.
 // osh_orb_refresh_map_points (mappoint_device.hip) has batches of map points: it uses scatter, PhaseClock, orb_state and copy_times.
 #pragma once
 #include "common.h"
