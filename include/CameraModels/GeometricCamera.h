@@ -7,6 +7,7 @@
 #include <vector>
 #include "../orbslam3_compat.h"
 namespace ORB_SLAM3 {
+class TwoViewReconstruction;
 class GeometricCamera {
  public:
   GeometricCamera() {}
@@ -18,6 +19,10 @@ class GeometricCamera {
   // include/CameraModels/GeometricCamera.h:79
   virtual bool epipolarConstrain(GeometricCamera* otherCamera, const cv::KeyPoint& kp1, const cv::KeyPoint& kp2, const Eigen::Matrix3f& R12,
                                  const Eigen::Vector3f& t12, const float sigmaLevel, const float unc) = 0;
+  // include/CameraModels/GeometricCamera.h:73: the monocular initialisation (include/TwoViewReconstruction.h); the bodies of the two
+  // stand-ins are in csrc/hosttest/two_view.cc
+  virtual bool ReconstructWithTwoViews(const std::vector<cv::KeyPoint>& vKeys1, const std::vector<cv::KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
+                                       Sophus::SE3f& T21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) = 0;
   float getParameter(const int i) { return mvParameters[i]; }
   unsigned int GetType() { return mnType; }
   const static unsigned int CAM_PINHOLE = 0;
@@ -29,6 +34,11 @@ class GeometricCamera {
 class Pinhole : public GeometricCamera {
  public:
   explicit Pinhole(const std::vector<float>& p) : GeometricCamera(p) { mnType = CAM_PINHOLE; }
+  ~Pinhole() override;
+  // src/CameraModels/Pinhole.cpp:83-91
+  bool ReconstructWithTwoViews(const std::vector<cv::KeyPoint>& vKeys1, const std::vector<cv::KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
+                               Sophus::SE3f& T21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) override;
+  TwoViewReconstruction* tvr = nullptr;
   Eigen::Vector2d project(const Eigen::Vector3d& v) override {
     return Eigen::Vector2d(mvParameters[0] * v[0] / v[2] + mvParameters[2], mvParameters[1] * v[1] / v[2] + mvParameters[3]);
   }
@@ -69,6 +79,11 @@ class KannalaBrandt8 : public GeometricCamera {
  public:
   explicit KannalaBrandt8(const std::vector<float>& p) : GeometricCamera(p), precision(1e-6) { mnType = CAM_FISHEYE; }
   KannalaBrandt8(const std::vector<float>& p, const float _precision) : GeometricCamera(p), precision(_precision) { mnType = CAM_FISHEYE; }
+  ~KannalaBrandt8() override;
+  // src/CameraModels/KannalaBrandt8.cpp:177-201, the keypoints undistorted by unproject (csrc/kb8_triangulate.h) followed by K
+  bool ReconstructWithTwoViews(const std::vector<cv::KeyPoint>& vKeys1, const std::vector<cv::KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
+                               Sophus::SE3f& T21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) override;
+  TwoViewReconstruction* tvr = nullptr;
   float GetPrecision() { return precision; }   // include/CameraModels/KannalaBrandt8.h:98,102: the Newton tolerance of unproject
   const float precision;
   Eigen::Vector2d project(const Eigen::Vector3d& v) override {

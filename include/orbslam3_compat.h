@@ -221,6 +221,7 @@ struct Point2f {
   float x = 0, y = 0;
   Point2f& operator*=(float s) { x *= s; y *= s; return *this; }
 };
+struct Point3f { float x = 0, y = 0, z = 0; Point3f() {} Point3f(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {} };
 struct Point { int x = 0, y = 0; Point() {} Point(int x_, int y_) : x(x_), y(y_) {} };
 struct KeyPoint { Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1; };
 // Row-major byte matrix (CV_8U only: descriptor matrices N x 32 and the pyramid levels of an ORBextractor cross this boundary).

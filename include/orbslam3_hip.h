@@ -953,6 +953,94 @@ int osh_orb_triangulate_new_points(osh_orb_ctx* ctx, int32_t n_segments, const o
  * ms[1] upload, ms[2] kernel, ms[3] download + write-back. */
 int osh_orb_newpoint_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- two-view reconstruction (the monocular initialisation) */
+/*
+ * TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc:41-129) behind its minimal-set draw, for n_problems problems in
+ * one call: for each of n_iterations minimal sets a homography (ComputeH21, :232-272) and a fundamental matrix (ComputeF21,
+ * :274-308), each scored against every match (CheckHomography / CheckFundamental, :310-473); per model the first hypothesis with
+ * the strictly greatest score above 0 (:172,223); RH = SH / (SH + SF) and the branch RH > 0.50 (:112-128); the 8 motion hypotheses
+ * of ReconstructH (:582-690) or the 4 of ReconstructF / DecomposeE (:484-493,903-927); CheckRT of each over the inliers (:786-901);
+ * and the decision (:505-568 or :693-733, minParallax = 1.0, minTriangulated = 50).  One upload, a fixed chain of kernels, one
+ * download.
+ *
+ * The caller draws the minimal sets (`sets`: data, the entry draws no random numbers) and normalises (Normalize, :737-784, over ALL
+ * keypoints of each frame): T1, T2 and the normalised coordinates of the matched keypoints.  Per-match results are in match order;
+ * the reference indexes vP3D / vbTriangulated by idx1.  ReconstructH returns true without assigning vP3D (:725-731); the result
+ * here carries the winner's points in both branches.
+ *
+ * Arithmetic: csrc/two_view.h states it.  float32 operations in the reference's order with no fused multiply-add; the score is the
+ * reference's sequential float32 sum in match order.  Deviations defined there: singular vectors from the fixed-sweep FP64
+ * one-sided Jacobi method (rounded to float32 once), the float32 cofactor inverse for .inverse(), the order statistic of the
+ * parallax in the total order of float32 bit patterns.
+ *
+ * status: the winner's T21 / x3d / triangulated / parallax are reported for every status that has a winner (info[3] >= 0), also
+ * when the reference returns false; for OSH_TWOVIEW_NO_MODEL and OSH_TWOVIEW_H_DEGENERATE they are 0.
+ *
+ * Refused before any device work, the context staying usable: with OSH_ERR_INVALID a negative count, a NULL array whose count is
+ * not 0, a K, T1, T2, sigma, pixel or normalised coordinate that is not finite, K[0] (fx) or K[4] (fy) or sigma equal to 0, an
+ * idx1 / idx2 outside [0, n_keys1) / [0, n_keys2), a set index outside [0, n_matches), a set that repeats an index, n_matches in
+ * 1..7 with n_iterations > 0; with OSH_ERR_UNSUPPORTED more than OSH_TWOVIEW_MAX_MATCHES matches or OSH_TWOVIEW_MAX_ITERATIONS
+ * iterations in a problem, more than OSH_TWOVIEW_MAX_PROBLEMS problems, or more than OSH_TWOVIEW_MAX_TOTAL_MATCHES matches or
+ * OSH_TWOVIEW_MAX_TOTAL_ITERATIONS iterations in a call.  n_problems = 0, n_matches = 0 and n_iterations = 0 are valid (the
+ * status is then OSH_TWOVIEW_NO_MODEL).  Every entry of the result arrays is written.
+ */
+#define OSH_TWOVIEW_MAX_MATCHES          8192
+#define OSH_TWOVIEW_MAX_ITERATIONS       1024
+#define OSH_TWOVIEW_MAX_PROBLEMS         4096
+#define OSH_TWOVIEW_MAX_TOTAL_MATCHES    524288   /* all problems of a call together */
+#define OSH_TWOVIEW_MAX_TOTAL_ITERATIONS 262144
+#define OSH_TWOVIEW_ACCEPTED_H      0   /* ReconstructH returned true                                                  */
+#define OSH_TWOVIEW_ACCEPTED_F      1   /* ReconstructF returned true                                                  */
+#define OSH_TWOVIEW_NO_MODEL        2   /* SH + SF == 0 (:113)                                                         */
+#define OSH_TWOVIEW_H_DEGENERATE    3   /* d1 / d2 or d2 / d3 below 1.00001 (:597)                                     */
+#define OSH_TWOVIEW_NO_CLEAR_WINNER 4   /* nsimilar > 1 (:520), or secondBestGood >= 0.75 * bestGood (:725)            */
+#define OSH_TWOVIEW_TOO_FEW_POINTS  5   /* maxGood < nMinGood (:520), or bestGood <= minTriangulated or 0.9 * N (:725) */
+#define OSH_TWOVIEW_LOW_PARALLAX    6   /* the winner's parallax is below minParallax (:528-565,725)                   */
+typedef struct osh_two_view_problem {
+  float K[9];                /* mK, row-major                                                                          */
+  float sigma;               /* mSigma                                                                                 */
+  int32_t n_iterations;      /* mMaxIterations                                                                         */
+  int32_t n_matches;         /* mvMatches12.size()                                                                     */
+  int32_t n_keys1, n_keys2;  /* mvKeys1.size(), mvKeys2.size(): for the index check                                    */
+  const int32_t* idx1;       /* [n_matches]   mvMatches12[i].first                                                     */
+  const int32_t* idx2;       /* [n_matches]   mvMatches12[i].second                                                    */
+  const float* pt1;          /* [n_matches*2] mvKeys1[idx1[i]].pt                                                      */
+  const float* pt2;          /* [n_matches*2] mvKeys2[idx2[i]].pt                                                      */
+  float T1[9], T2[9];        /* Normalize(mvKeys1), Normalize(mvKeys2): the transforms, row-major                      */
+  const float* pn1;          /* [n_matches*2] vPn1[idx1[i]]                                                            */
+  const float* pn2;          /* [n_matches*2] vPn2[idx2[i]]                                                            */
+  const int32_t* sets;       /* [n_iterations*8] mvSets: indices into the matches                                      */
+} osh_two_view_problem;
+/* Caller-allocated; each may be NULL. */
+typedef struct osh_two_view_result {
+  int32_t* status;           /* [1]  OSH_TWOVIEW_ACCEPTED_H .. OSH_TWOVIEW_LOW_PARALLAX                                */
+  float* T21;                /* [12] the winner's R (row-major), then t                                                */
+  float* sh;                 /* [1]  SH                                                                                */
+  float* sf;                 /* [1]  SF                                                                                */
+  float* H21;                /* [9]  the winning homography (0 without one)                                            */
+  float* F21;                /* [9]  the winning fundamental matrix (0 without one)                                    */
+  int32_t* best_h;           /* [1]  its iteration, -1 without one                                                     */
+  int32_t* best_f;           /* [1]                                                                                    */
+  int32_t* info;             /* [4]  branch (1 H, 0 F, -1 none), N (inliers of the branch's model), motion hypotheses
+                                     (8, 4 or 0), winner (-1 none)                                                     */
+  uint8_t* inlier;           /* [n_matches]   vbMatchesInliers of the branch's model                                   */
+  float* x3d;                /* [n_matches*3] the winner's vP3D, 0 for a match it did not count                        */
+  uint8_t* triangulated;     /* [n_matches]   the winner's vbTriangulated                                              */
+  int32_t* n_good;           /* [8]  nGood per motion hypothesis (0 beyond their number)                               */
+  float* parallax;           /* [8]  parallax per motion hypothesis                                                    */
+  /* debug: the stages */
+  float* debug_model_n;      /* [2*n_iterations*9] Hn of every iteration, then Fn of every iteration                   */
+  float* debug_model;        /* [2*n_iterations*9] H21i, then F21i                                                     */
+  float* debug_score;        /* [2*n_iterations]   currentScore                                                        */
+  float* debug_R;            /* [8*9] the motion hypotheses                                                            */
+  float* debug_t;            /* [8*3]                                                                                  */
+} osh_two_view_result;
+int osh_orb_two_view_reconstruct(osh_orb_ctx* ctx, int32_t n_problems, const osh_two_view_problem* problems,
+                                 const osh_two_view_result* results);
+/* Host-clock phases (ms) of the last osh_orb_two_view_reconstruct under osh_orb_set_profiling: ms[0] validation + staging,
+ * ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
+int osh_orb_two_view_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 /* ------------------------------------------------- map point refresh (distinctive descriptor, normal and depth) */
 /*
  * MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) and MapPoint::UpdateNormalAndDepth (:426-494) for the points

@@ -462,6 +462,33 @@ typedef struct osh_host_newpoint_scene {
 int osh_host_create_new_map_points(const osh_host_newpoint_scene* scene, int32_t capacity, int32_t* neighbour, int32_t* idx1, int32_t* idx2,
                                    float* x3d, int32_t* n_obs, int32_t* flags, float* poses);
 
+/* ---- TwoViewReconstruction (include/TwoViewReconstruction.h, csrc/host/TwoViewReconstruction.cc, csrc/hosttest/two_view.cc) ---- */
+struct osh_two_view_problem;
+struct osh_two_view_result;
+/* csrc/two_view.h (the statements of two_view_device.hip) compiled for the host, on one thread: arguments as
+ * osh_orb_two_view_reconstruct without a context, without its validation (the problems must be valid) and without its limits.
+ * *ms (may be NULL) = wall time of the call.  -1: bad arguments. */
+int osh_host_two_view_cpu(int32_t n_problems, const struct osh_two_view_problem* problems, const struct osh_two_view_result* results,
+                          double* ms);
+/* Normalize (src/TwoViewReconstruction.cc:737-784) of csrc/two_view.h over the n keypoints xy [n*2]: pn [n*2], T [9] row-major. */
+int osh_host_two_view_normalize(int32_t n, const float* xy, float* pn, float* T);
+/* The decision of ReconstructF (branch 0, n_good / parallax [4]) or ReconstructH (branch 1, [8]) on N inliers: returns the
+ * OSH_TWOVIEW_* status, *winner = the hypothesis it reports (-1: none).  -1: bad arguments. */
+int osh_host_two_view_decide(int32_t branch, int32_t n_inliers, const int32_t* n_good, const float* parallax, int32_t* winner);
+/* The motion hypotheses of ReconstructH (branch 1, model = H21 [9]: :582-690) or of ReconstructF / DecomposeE (branch 0, model = F21:
+ * :484-493,903-927) for K [9]: R [8*9], t [8*3].  Returns their number: 8, 4, or 0 when ReconstructH's 1.00001 test refuses.  -1: bad
+ * arguments. */
+int osh_host_two_view_motion(int32_t branch, const float* model, const float* K, float* R, float* t);
+/* camera 0: TwoViewReconstruction(K = params[9], sigma, iterations).Reconstruct; 1: Pinhole(params[4]).ReconstructWithTwoViews;
+ * 2: KannalaBrandt8(params[8]).ReconstructWithTwoViews (both with the class defaults sigma 1, 200 iterations; pass iterations = 200).
+ * xy1 [n1*2], xy2 [n2*2], matches12 [n1] (-1: unmatched).  vP3D and vbTriangulated go in with *n_p3d / *n_triangulated entries
+ * (p3d [max(*n_p3d, n1)*3] holds the incoming points) and come back with the sizes Reconstruct left and their first n1 entries.
+ * T21 [12]; sets [iterations*8] = mvSets; info [3] = status, 1 if the device answered, mvSets.size().  Returns 1 / 0 as
+ * Reconstruct, -1: bad arguments. */
+int osh_host_two_view_reconstruct(int32_t camera, const float* params, float sigma, int32_t iterations, int32_t n1, const float* xy1,
+                                  int32_t n2, const float* xy2, const int32_t* matches12, float* T21, float* p3d, int32_t* n_p3d,
+                                  uint8_t* triangulated, int32_t* n_triangulated, int32_t* sets, int32_t* info);
+
 /* ---- ORBextractor::ComputeKeyPointsOctTree (include/ORBextractor.h, csrc/host/ORBextractor.cc, csrc/hosttest/orbextractor.cc) ---- */
 struct osh_fast_frame;
 struct osh_fast_result;

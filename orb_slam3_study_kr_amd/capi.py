@@ -374,6 +374,30 @@ OSH_NEWPOINT_PINHOLE, OSH_NEWPOINT_KB8 = 0, 1
 OSH_NEWPOINT_TRIANGULATED, OSH_NEWPOINT_STEREO_1, OSH_NEWPOINT_STEREO_2, OSH_NEWPOINT_NO_SOURCE = 0, 1, 2, 255
 
 
+class TwoViewProblem(C.Structure):
+    """``osh_two_view_problem`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("K", C.c_float * 9), ("sigma", C.c_float), ("n_iterations", C.c_int32), ("n_matches", C.c_int32),
+                ("n_keys1", C.c_int32), ("n_keys2", C.c_int32), ("idx1", c_int32_p), ("idx2", c_int32_p), ("pt1", c_float_p),
+                ("pt2", c_float_p), ("T1", C.c_float * 9), ("T2", C.c_float * 9), ("pn1", c_float_p), ("pn2", c_float_p),
+                ("sets", c_int32_p)]
+
+
+class TwoViewResult(C.Structure):
+    """``osh_two_view_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("status", c_int32_p), ("T21", c_float_p), ("sh", c_float_p), ("sf", c_float_p), ("H21", c_float_p), ("F21", c_float_p),
+                ("best_h", c_int32_p), ("best_f", c_int32_p), ("info", c_int32_p), ("inlier", c_uint8_p), ("x3d", c_float_p),
+                ("triangulated", c_uint8_p), ("n_good", c_int32_p), ("parallax", c_float_p), ("debug_model_n", c_float_p),
+                ("debug_model", c_float_p), ("debug_score", c_float_p), ("debug_R", c_float_p), ("debug_t", c_float_p)]
+
+
+OSH_TWOVIEW_MAX_MATCHES, OSH_TWOVIEW_MAX_ITERATIONS, OSH_TWOVIEW_MAX_PROBLEMS = 8192, 1024, 4096
+OSH_TWOVIEW_MAX_TOTAL_MATCHES, OSH_TWOVIEW_MAX_TOTAL_ITERATIONS = 524288, 262144
+(OSH_TWOVIEW_ACCEPTED_H, OSH_TWOVIEW_ACCEPTED_F, OSH_TWOVIEW_NO_MODEL, OSH_TWOVIEW_H_DEGENERATE, OSH_TWOVIEW_NO_CLEAR_WINNER,
+ OSH_TWOVIEW_TOO_FEW_POINTS, OSH_TWOVIEW_LOW_PARALLAX) = range(7)
+
+
 class MapPointBatch(C.Structure):
     """``osh_mappoint_batch`` (include/orbslam3_hip.h)."""
 
@@ -568,6 +592,8 @@ _SIGNATURES = {
     "osh_kb8_triangulate": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
     "osh_orb_triangulate_new_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(NewPointSegment), C.POINTER(NewPointResult)]),
     "osh_orb_newpoint_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_two_view_reconstruct": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(TwoViewProblem), C.POINTER(TwoViewResult)]),
+    "osh_orb_two_view_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_refresh_map_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MapPointBatch), C.POINTER(MapPointResult)]),
     "osh_orb_refresh_map_points_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_fast_detect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult)]),
@@ -712,6 +738,12 @@ _HOST_SIGNATURES = {
     "osh_host_compute_fisheye_stereo_matches": (C.c_int, [C.POINTER(HostFisheyeInput), C.c_int32, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p]),
     "osh_host_kb8_triangulate_cpu": (C.c_int, [C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
     "osh_host_newpoint_triangulate_cpu": (C.c_int, [C.c_int32, C.POINTER(NewPointSegment), C.POINTER(NewPointResult), c_double_p]),
+    "osh_host_two_view_cpu": (C.c_int, [C.c_int32, C.POINTER(TwoViewProblem), C.POINTER(TwoViewResult), c_double_p]),
+    "osh_host_two_view_normalize": (C.c_int, [C.c_int32, c_float_p, c_float_p, c_float_p]),
+    "osh_host_two_view_decide": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_float_p, c_int32_p]),
+    "osh_host_two_view_motion": (C.c_int, [C.c_int32, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "osh_host_two_view_reconstruct": (C.c_int, [C.c_int32, c_float_p, C.c_float, C.c_int32, C.c_int32, c_float_p, C.c_int32, c_float_p,
+                                                c_int32_p, c_float_p, c_float_p, c_int32_p, c_uint8_p, c_int32_p, c_int32_p, c_int32_p]),
     "osh_host_graph_create": (C.c_void_p, [C.c_int32, c_int64_p, c_float_p, c_float_p, c_float_p, C.c_int32, C.c_int32, c_int64_p,
                                            c_float_p, C.c_int32, c_int32_p, c_int32_p, c_float_p, c_int32_p, C.c_int64, C.c_int32]),
     "osh_host_graph_destroy": (None, [C.c_void_p]),

@@ -10,6 +10,7 @@
 // along or resident on the context: orb_pyramid_set.h, built on pack_level, is their level list; they use scatter, PhaseClock,
 // orb_state and copy_times.  osh_orb_pyramid_build (orb_pyramid_device.hip) fills the resident pyramid: pack_level, PhaseClock, orb_state.
 // osh_orb_refresh_map_points (mappoint_device.hip) has batches of map points: it uses scatter, PhaseClock, orb_state and copy_times.
+// osh_orb_two_view_reconstruct (two_view_device.hip) has problems of matches and minimal sets: scatter, PhaseClock, orb_state, copy_times.
 #pragma once
 #include "common.h"
 #include <chrono>

@@ -1029,6 +1029,39 @@ def newpoint_triangulate_cpu(segments):
     return orb.newpoint_cpu(segments)
 
 
+def two_view_reconstruct(scene, camera: str = "class", iterations: int = 200, p3d_in=None) -> dict:
+    """TwoViewReconstruction::Reconstruct (camera "class": K, sigma and `iterations` of the scene), Pinhole::ReconstructWithTwoViews
+    ("pinhole") or KannalaBrandt8::ReconstructWithTwoViews ("kb8", the scene's fisheye parameters) on a synth_two_view.Scene
+    (osh_host_two_view_reconstruct); the two cameras run the class defaults, 200 iterations.  p3d_in: what vP3D holds on entry
+    [m, 3], m <= n1.  Returns ok, T21 [12], p3d [n1, 3] and triangulated [n1] (the first n_p3d / n_triangulated entries are what
+    Reconstruct left), sets [iterations, 8] and info = (status, 1 if the device answered, mvSets.size())."""
+    lib = capi.load_host_library()
+    kind = {"class": 0, "pinhole": 1, "kb8": 2}[camera]
+    K = np.asarray(scene.K, np.float32)
+    params = {0: K.reshape(9), 1: np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], np.float32), 2: scene.kb8}[kind]
+    params = np.ascontiguousarray(params, np.float32)
+    if kind:
+        iterations = 200
+    xy1, xy2 = np.ascontiguousarray(scene.keys1, np.float32), np.ascontiguousarray(scene.keys2, np.float32)
+    m12 = np.ascontiguousarray(scene.matches12, np.int32)
+    n1 = xy1.shape[0]
+    p3d = np.zeros((n1, 3), np.float32)
+    n_p3d = C.c_int32(0)
+    if p3d_in is not None:
+        p3d_in = np.asarray(p3d_in, np.float32).reshape(-1, 3)
+        p3d[:p3d_in.shape[0]] = p3d_in
+        n_p3d = C.c_int32(p3d_in.shape[0])
+    tri, n_tri = np.zeros(n1, np.uint8), C.c_int32(0)
+    T21, sets, info = np.zeros(12, np.float32), np.zeros((iterations, 8), np.int32), np.zeros(3, np.int32)
+    rc = lib.osh_host_two_view_reconstruct(kind, capi.ptr(params, capi.c_float_p), float(scene.sigma), iterations, n1, capi.ptr(xy1, capi.c_float_p),
+                                           xy2.shape[0], capi.ptr(xy2, capi.c_float_p), capi.ptr(m12, capi.c_int32_p), capi.ptr(T21, capi.c_float_p),
+                                           capi.ptr(p3d, capi.c_float_p), C.byref(n_p3d), capi.ptr(tri, capi.c_uint8_p), C.byref(n_tri),
+                                           capi.ptr(sets, capi.c_int32_p), capi.ptr(info, capi.c_int32_p))
+    if rc < 0:
+        raise RuntimeError(f"osh_host_two_view_reconstruct returned {rc}")
+    return dict(ok=bool(rc), T21=T21, p3d=p3d, n_p3d=int(n_p3d.value), triangulated=tri, n_triangulated=int(n_tri.value), sets=sets, info=info)
+
+
 def create_new_map_points(scene, coarse: bool = True, new_keyframe_waiting: bool = False, capacity: int = 4096) -> dict:
     """LocalMapping::CreateNewMapPoints on the stand-in classes built from a synth_newpoints.Scene (osh_host_create_new_map_points).
     Keyframe 0 is the current one, keyframe 1 + k neighbour k; the first two neighbours are covisibles, the third is reached

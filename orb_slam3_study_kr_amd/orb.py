@@ -156,6 +156,7 @@ class OrbMatcher:
     stereo_times = functools.partialmethod(_times, "osh_orb_stereo_get_times")                   # of the last stereo_match
     fisheye_stereo_times = functools.partialmethod(_times, "osh_orb_fisheye_stereo_get_times")   # of the last fisheye_stereo_match
     newpoint_times = functools.partialmethod(_times, "osh_orb_newpoint_get_times")               # of the last triangulate_new_points
+    two_view_times = functools.partialmethod(_times, "osh_orb_two_view_get_times")               # of the last two_view_reconstruct
     refresh_map_points_times = functools.partialmethod(_times, "osh_orb_refresh_map_points_get_times")   # of the last refresh_map_points
     fast_times = functools.partialmethod(_times, "osh_orb_fast_get_times")                       # of the last fast_detect
     ic_angle_times = functools.partialmethod(_times, "osh_orb_ic_angle_get_times")               # of the last ic_angle
@@ -194,6 +195,15 @@ class OrbMatcher:
         cos_parallax [n] and x3d [n, 3]."""
         cs, cr, _keep, outs = newpoint_args(segments)
         capi.check(self.lib.osh_orb_triangulate_new_points(self.ctx, len(segments), cs, cr), "osh_orb_triangulate_new_points", self.lib)
+        return outs
+
+    def two_view_reconstruct(self, problems, debug: bool = False) -> list:
+        """TwoViewReconstruction::Reconstruct behind its minimal-set draw (src/TwoViewReconstruction.cc:100-129 and what it calls)
+        for a batch of synth_two_view.Problem in one osh_orb_two_view_reconstruct call: per problem a dict with status, T21 [12],
+        sh, sf, H21, F21 [3, 3], best_h, best_f, info [4], inlier, triangulated [n], x3d [n, 3], n_good, parallax [8], and with
+        `debug` also debug_model_n, debug_model [2, iterations, 3, 3], debug_score [2, iterations], debug_R [8, 3, 3], debug_t [8, 3]."""
+        cp, cr, _keep, outs = two_view_args(problems, debug)
+        capi.check(self.lib.osh_orb_two_view_reconstruct(self.ctx, len(problems), cp, cr), "osh_orb_two_view_reconstruct", self.lib)
         return outs
 
     def refresh_map_points(self, batches, want=None) -> list:
@@ -949,6 +959,57 @@ def newpoint_cpu(segments, host_lib=None):
     rc = host_lib.osh_host_newpoint_triangulate_cpu(len(segments), cs, cr, C.byref(ms))
     if rc != 0:
         raise RuntimeError(f"osh_host_newpoint_triangulate_cpu -> {rc}")
+    return outs, float(ms.value)
+
+
+_TWOVIEW_ARRAYS = (("idx1", np.int32), ("idx2", np.int32), ("pt1", np.float32), ("pt2", np.float32), ("pn1", np.float32),
+                   ("pn2", np.float32), ("sets", np.int32))
+
+
+def two_view_args(problems, debug: bool = False, fill=None):
+    """The osh_two_view_problem / osh_two_view_result arrays of OrbMatcher.two_view_reconstruct for repeated calls: (problems,
+    results, the arrays that keep their pointers alive, the per-problem dicts of output arrays).  fill: a byte the output arrays
+    are pre-filled with (None: zeros)."""
+    n_p = len(problems)
+    cp = (capi.TwoViewProblem * max(n_p, 1))()
+    cr = (capi.TwoViewResult * max(n_p, 1))()
+    keep, outs = [], []
+    for k, pb in enumerate(problems):
+        c = cp[k]
+        c.K[:] = [float(x) for x in np.asarray(pb.K, np.float32).reshape(9)]
+        c.T1[:] = [float(x) for x in np.asarray(pb.T1, np.float32).reshape(9)]
+        c.T2[:] = [float(x) for x in np.asarray(pb.T2, np.float32).reshape(9)]
+        a = {name: np.ascontiguousarray(getattr(pb, name), dt) for name, dt in _TWOVIEW_ARRAYS}
+        n, it = a["idx1"].shape[0], a["sets"].reshape(-1, 8).shape[0]
+        c.sigma, c.n_iterations, c.n_matches, c.n_keys1, c.n_keys2 = float(pb.sigma), it, n, int(pb.n_keys1), int(pb.n_keys2)
+        for name, dt in _TWOVIEW_ARRAYS:
+            setattr(c, name, capi.ptr(a[name], _POINTER[np.dtype(dt)]))
+        f32, i32 = np.float32, np.int32
+        o = dict(status=np.zeros(1, i32), T21=np.zeros(12, f32), sh=np.zeros(1, f32), sf=np.zeros(1, f32), H21=np.zeros((3, 3), f32),
+                 F21=np.zeros((3, 3), f32), best_h=np.zeros(1, i32), best_f=np.zeros(1, i32), info=np.zeros(4, i32),
+                 inlier=np.zeros(n, np.uint8), x3d=np.zeros((n, 3), f32), triangulated=np.zeros(n, np.uint8), n_good=np.zeros(8, i32),
+                 parallax=np.zeros(8, f32))
+        if debug:
+            o.update(debug_model_n=np.zeros((2, it, 3, 3), f32), debug_model=np.zeros((2, it, 3, 3), f32), debug_score=np.zeros((2, it), f32),
+                     debug_R=np.zeros((8, 3, 3), f32), debug_t=np.zeros((8, 3), f32))
+        if fill is not None:
+            for v in o.values():
+                v.view(np.uint8)[...] = fill
+        _wire_outputs(cr[k], o)
+        keep.append(a)
+        outs.append(o)
+    return cp, cr, keep, outs
+
+
+def two_view_cpu(problems, debug: bool = False, host_lib=None):
+    """csrc/two_view.h on the host in one thread (osh_host_two_view_cpu of the test library): the per-problem output dicts of
+    two_view_reconstruct and the wall time in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    cp, cr, _keep, outs = two_view_args(problems, debug)
+    ms = C.c_double(0)
+    rc = host_lib.osh_host_two_view_cpu(len(problems), cp, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_two_view_cpu -> {rc}")
     return outs, float(ms.value)
 
 
