@@ -23,6 +23,9 @@ class GeometricCamera {
   // stand-ins are in csrc/hosttest/two_view.cc
   virtual bool ReconstructWithTwoViews(const std::vector<cv::KeyPoint>& vKeys1, const std::vector<cv::KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
                                        Sophus::SE3f& T21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) = 0;
+  // include/CameraModels/GeometricCamera.h:64: what MLPnPsolver's constructor turns into a bearing vector; the bodies of the two
+  // stand-ins are in csrc/hosttest/mlpnp.cc
+  virtual cv::Point3f unproject(const cv::Point2f& p2D) = 0;
   float getParameter(const int i) { return mvParameters[i]; }
   unsigned int GetType() { return mnType; }
   const static unsigned int CAM_PINHOLE = 0;
@@ -39,6 +42,7 @@ class Pinhole : public GeometricCamera {
   bool ReconstructWithTwoViews(const std::vector<cv::KeyPoint>& vKeys1, const std::vector<cv::KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
                                Sophus::SE3f& T21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) override;
   TwoViewReconstruction* tvr = nullptr;
+  cv::Point3f unproject(const cv::Point2f& p2D) override;   // src/CameraModels/Pinhole.cpp:66-69
   Eigen::Vector2d project(const Eigen::Vector3d& v) override {
     return Eigen::Vector2d(mvParameters[0] * v[0] / v[2] + mvParameters[2], mvParameters[1] * v[1] / v[2] + mvParameters[3]);
   }
@@ -84,6 +88,7 @@ class KannalaBrandt8 : public GeometricCamera {
   bool ReconstructWithTwoViews(const std::vector<cv::KeyPoint>& vKeys1, const std::vector<cv::KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
                                Sophus::SE3f& T21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated) override;
   TwoViewReconstruction* tvr = nullptr;
+  cv::Point3f unproject(const cv::Point2f& p2D) override;   // src/CameraModels/KannalaBrandt8.cpp:116-143 (kb8_unproject of csrc/kb8_triangulate.h)
   float GetPrecision() { return precision; }   // include/CameraModels/KannalaBrandt8.h:98,102: the Newton tolerance of unproject
   const float precision;
   Eigen::Vector2d project(const Eigen::Vector3d& v) override {

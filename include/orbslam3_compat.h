@@ -39,10 +39,12 @@ struct Matrix {
   const T& operator[](int i) const { return v[i]; }
   T& operator()(int r, int c) { return v[r * C + c]; }
   const T& operator()(int r, int c) const { return v[r * C + c]; }
+  void setIdentity() { for (int r = 0; r < R; ++r) for (int c = 0; c < C; ++c) v[r * C + c] = r == c ? T(1) : T(0); }
   template <class U> Matrix<U, R, C> cast() const { Matrix<U, R, C> o; for (int i = 0; i < R * C; ++i) o.v[i] = (U)v[i]; return o; }
 };
 using Matrix3f = Matrix<float, 3, 3>;
 using Matrix3d = Matrix<double, 3, 3>;
+using Matrix4f = Matrix<float, 4, 4>;
 using Vector2d = Matrix<double, 2>;
 using Vector3d = Matrix<double, 3>;
 using Vector3f = Matrix<float, 3>;

@@ -1041,6 +1041,80 @@ int osh_orb_two_view_reconstruct(osh_orb_ctx* ctx, int32_t n_problems, const osh
  * ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
 int osh_orb_two_view_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- MLPnP (the PnP RANSAC of relocalisation) */
+/*
+ * MLPnPsolver::iterate (src/MLPnPsolver.cpp:100-223) behind its minimal-set draw, for n_problems problems (one per candidate
+ * keyframe) in one call: for each of n_iterations minimal sets of 6 correspondences computePose (:356-658) and CheckInliers
+ * (:262-293) against every correspondence; the records (an iteration with count >= min_inliers and count > the running best, which
+ * starts at best_inliers_in, :169-187); Refine (:295-353) of every record: computePose over its inliers in ascending index order and
+ * CheckInliers again, successful when the refined count > min_inliers; and the decision: first_hit is the first iteration with
+ * count >= min_inliers whose running best has a successful Refine (best_refine_ok_in while no record has occurred in this call:
+ * the reference refines the unchanged best again, and Refine is a function of the best mask alone).  One upload, a fixed chain of
+ * kernels, one download.  The caller draws the sets (data; the entry draws no random numbers).
+ *
+ * Arithmetic: csrc/mlpnp.h states it.  The solver is FP64; CheckInliers is the reference's float32 statement.  Deviations defined
+ * there: the null space of a bearing vector by a Householder reflection, the rank test by column-pivoted QR, eigenvectors, null
+ * vector and polar factor by fixed-sweep FP64 Jacobi methods, sums over the correspondences as 64 strided partial sums joined by a
+ * pairwise tree, an unpivoted LDL^T, an analytic Jacobian.  A pose is 12 doubles: R row-major, then t.  A mask is bit words: bit
+ * i % 32 of word i / 32 is correspondence i; a mask has OSH_MLPNP_MASK_WORDS(n) words.
+ *
+ * Refused before any device work, the context staying usable: with OSH_ERR_INVALID a negative count, a NULL array whose count is
+ * not 0, a camera type other than the two, min_inliers < 6, n < 6 with n_iterations > 0, a set index outside [0, n), a set that
+ * repeats an index; with OSH_ERR_UNSUPPORTED more than OSH_MLPNP_MAX_POINTS correspondences or OSH_MLPNP_MAX_ITERATIONS iterations in
+ * a problem or more than OSH_MLPNP_MAX_PROBLEMS problems.  Coordinates are not checked: a NaN ends in 0 inliers.  Every entry of the
+ * result arrays is written.
+ */
+#define OSH_MLPNP_MAX_POINTS     2048
+#define OSH_MLPNP_MAX_ITERATIONS 1024
+#define OSH_MLPNP_MAX_PROBLEMS   64
+#define OSH_MLPNP_PINHOLE 0   /* camera: fx fy cx cy             */
+#define OSH_MLPNP_KB8     1   /* camera: fx fy cx cy k1 k2 k3 k4 */
+#define OSH_MLPNP_MASK_WORDS(n) (2 * (((n) + 63) / 64))
+typedef struct osh_mlpnp_problem {
+  int32_t camera_type;       /* OSH_MLPNP_PINHOLE or OSH_MLPNP_KB8                                                      */
+  float camera[8];           /* mpCamera's parameters                                                                  */
+  int32_t n;                 /* N                                                                                      */
+  const double* bearing;     /* [n*3] mvBearingVecs                                                                    */
+  const double* p3d;         /* [n*3] mvP3Dw                                                                           */
+  const float* p2d;          /* [n*2] mvP2D                                                                            */
+  const float* max_error;    /* [n]   mvMaxError                                                                       */
+  int32_t n_iterations;
+  const int32_t* sets;       /* [n_iterations*6] indices into the correspondences                                      */
+  int32_t min_inliers;       /* mRansacMinInliers                                                                      */
+  int32_t best_inliers_in;   /* mnBestInliers on entry                                                                 */
+  int32_t best_refine_ok_in; /* whether Refine of the best on entry succeeds                                           */
+} osh_mlpnp_problem;
+/* Caller-allocated; each may be NULL. */
+typedef struct osh_mlpnp_result {
+  int32_t* first_hit;        /* [1]  the iteration iterate returns true in, -1: none                                   */
+  int32_t* hit_record;       /* [1]  the record refined there, -1: none, or the best on entry (its Refine is the caller's) */
+  double* hit_pose;          /* [12] the refined pose there (0 when hit_record is -1)                                  */
+  int32_t* hit_count;        /* [1]  mnRefinedInliers                                                                  */
+  uint32_t* hit_mask;        /* [OSH_MLPNP_MASK_WORDS(n)] mvbRefinedInliers                                            */
+  int32_t* best_iteration;   /* [1]  the running best at first_hit, or after the last iteration: its iteration, -1 when
+                                     it is still the best on entry                                                     */
+  int32_t* best_count;       /* [1]  mnBestInliers                                                                     */
+  uint32_t* best_mask;       /* [OSH_MLPNP_MASK_WORDS(n)] mvbBestInliers (0 when best_iteration is -1)                 */
+  double* best_pose;         /* [12]                                                                                   */
+  int32_t* best_refine_ok;   /* [1]  whether Refine of that best succeeds                                              */
+  int32_t* n_records;        /* [1]  records over all n_iterations                                                     */
+  /* debug: the stages */
+  double* debug_pose;        /* [n_iterations*12] the pose of every iteration                                          */
+  int32_t* debug_count;      /* [n_iterations]    mnInliersi                                                           */
+  int32_t* debug_record;     /* [n_iterations]    the iterations that are records, then -1                             */
+  int32_t* debug_record_count; /* [n_iterations]  the refined count per record, then 0                                 */
+  double* debug_record_pose; /* [n_iterations*12] the refined pose per record, then 0                                  */
+} osh_mlpnp_result;
+int osh_orb_mlpnp_solve(osh_orb_ctx* ctx, int32_t n_problems, const osh_mlpnp_problem* problems, const osh_mlpnp_result* results);
+/* The scoring stage alone: CheckInliers of n_poses given poses [n_poses*12] against the correspondences of `problem` (its sets,
+ * iterations and RANSAC fields are not read; n_poses <= OSH_MLPNP_MAX_ITERATIONS): count [n_poses], mask
+ * [n_poses*OSH_MLPNP_MASK_WORDS(n)]. */
+int osh_orb_mlpnp_check_inliers(osh_orb_ctx* ctx, const osh_mlpnp_problem* problem, int32_t n_poses, const double* poses, int32_t* count,
+                                uint32_t* mask);
+/* Host-clock phases (ms) of the last osh_orb_mlpnp_solve under osh_orb_set_profiling: ms[0] validation + staging, ms[1] upload,
+ * ms[2] kernels, ms[3] download + write-back; ms[4] the hypothesis kernel alone (device events; part of ms[2]). */
+int osh_orb_mlpnp_get_times(osh_orb_ctx* ctx, double ms[5]);
+
 /* ------------------------------------------------- map point refresh (distinctive descriptor, normal and depth) */
 /*
  * MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) and MapPoint::UpdateNormalAndDepth (:426-494) for the points

@@ -489,6 +489,58 @@ int osh_host_two_view_reconstruct(int32_t camera, const float* params, float sig
                                   int32_t n2, const float* xy2, const int32_t* matches12, float* T21, float* p3d, int32_t* n_p3d,
                                   uint8_t* triangulated, int32_t* n_triangulated, int32_t* sets, int32_t* info);
 
+/* ---- MLPnP, the PnP RANSAC of relocalisation (csrc/mlpnp.h, csrc/hosttest/mlpnp.cc) ---- */
+struct osh_mlpnp_problem;
+struct osh_mlpnp_result;
+/* csrc/mlpnp.h (the statements of mlpnp_device.hip) compiled for the host, on one thread: arguments as osh_orb_mlpnp_solve without a
+ * context, without its validation (the problems must be valid) and without its limits.  *ms (may be NULL) = wall time of the call.
+ * -1: bad arguments. */
+int osh_host_mlpnp_cpu(int32_t n_problems, const struct osh_mlpnp_problem* problems, const struct osh_mlpnp_result* results, double* ms);
+/* CheckInliers of csrc/mlpnp.h: arguments as osh_orb_mlpnp_check_inliers without a context. */
+int osh_host_mlpnp_check_inliers(const struct osh_mlpnp_problem* problem, int32_t n_poses, const double* poses, int32_t* count, uint32_t* mask);
+/* The stages of computePose, one by one.  nullspace: N [3*2] row-major for the bearing vector f [3].  rank: the rank of the symmetric
+ * S [9] as the planarity test counts it.  null_vector: the null vector h [cols] of the symmetric M [cols*cols], cols 9 or 12.
+ * compute_pose: computePose over n >= 6 correspondences (bearing, p3d [n*3]): pose [12], info [3] (may be NULL) = planar,
+ * Gauss-Newton updates applied, how it ended (0: its bound, 1: the break on dx, 2: the stop on J dx).  gauss_newton: mlpnp_gn from
+ * x [6] (omega, t; updated in place) with at most max_iterations rounds: info [2] = updates applied, how it ended.  -1: bad arguments. */
+int osh_host_mlpnp_nullspace(const double* f, double* N);
+int osh_host_mlpnp_rank(const double* S);
+int osh_host_mlpnp_null_vector(const double* M, int32_t cols, double* h);
+int osh_host_mlpnp_compute_pose(int32_t n, const double* bearing, const double* p3d, double* pose, int32_t* info);
+int osh_host_mlpnp_gauss_newton(int32_t n, const double* bearing, const double* p3d, double* x, int32_t max_iterations, int32_t* info);
+/* SetRansacParameters (src/MLPnPsolver.cpp:225-260) of csrc/mlpnp.h for n correspondences: out [2] = mRansacMinInliers, mRansacMaxIts. */
+int osh_host_mlpnp_ransac_parameters(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations, int32_t min_set, float epsilon,
+                                     int32_t* out);
+/* The record scan and the decision of csrc/mlpnp.h from per-iteration counts and per-record refined counts (record_count
+ * [n_iterations], read for the records that occur): record [n_iterations] gets the record iterations; out [7] = first_hit,
+ * hit_record, hit_count, best_iteration, best_count, best_refine_ok, n_records.  -1: bad arguments. */
+int osh_host_mlpnp_replay(int32_t n_iterations, const int32_t* count, int32_t min_inliers, int32_t best_inliers_in, int32_t best_refine_ok_in,
+                          const int32_t* record_count, int32_t* record, int32_t* out);
+
+/* An MLPnPsolver (include/MLPnPsolver.h, csrc/host/MLPnPsolver.cc) of the stand-in classes: camera_type 0 Pinhole(params[4]), 1
+ * KannalaBrandt8(params[8]); a Frame with n_keys undistorted keypoints (xy [n_keys*2], octave [n_keys]) and level_sigma2 [n_levels];
+ * vpMapPointMatches of n_matches entries, state [n_matches] 0 none, 1 a map point at world [i*3], 2 a bad one.  NULL: bad arguments. */
+void* osh_host_mlpnp_solver_create(int32_t camera_type, const float* params, int32_t n_keys, const float* xy, const int32_t* octave,
+                                   int32_t n_levels, const float* level_sigma2, int32_t n_matches, const float* world, const uint8_t* state);
+void osh_host_mlpnp_solver_destroy(void* solver);
+int osh_host_mlpnp_solver_set_ransac(void* solver, double probability, int32_t min_inliers, int32_t max_iterations, int32_t min_set,
+                                     float epsilon, float th2);
+/* out [7] = N, mRansacMinInliers, mRansacMaxIts, mnIterations, mnBestInliers, queued sets, 1 if the device answered the last iterate */
+int osh_host_mlpnp_solver_state(void* solver, int32_t* out);
+/* iterate(n_iterations, ..) of every solver, one by one (batch 0) or through MLPnPsolver::IterateBatch (batch 1).  Per solver:
+ * found, no_more, n_inliers, inliers [n_matches + 1] (vbInliers cut to n_matches; the last byte: 1 if vbInliers is not empty),
+ * Tout [16] row-major.  -1: bad arguments. */
+int osh_host_mlpnp_solver_iterate(int32_t n_solvers, void* const* solvers, int32_t n_iterations, int32_t batch, int32_t n_matches,
+                                  uint8_t* found, uint8_t* no_more, int32_t* n_inliers, uint8_t* inliers, float* Tout);
+/* The two halves of iterate around the device call.  prepare: draws (or takes from the queue) the sets of one iterate(n_iterations):
+ * returns their number and the first `capacity` of them in sets [capacity*6]; -2 when N < mRansacMinInliers.  replay: walks a given
+ * answer for the prepared round: head [6] = first_hit, hit_record, hit_count, best_iteration, best_count, best_refine_ok; poses
+ * [12], masks [OSH_MLPNP_MASK_WORDS(N)]; outputs as iterate's.  Returns iterate's return value; -1: bad arguments. */
+int osh_host_mlpnp_solver_prepare(void* solver, int32_t n_iterations, int32_t capacity, int32_t* sets);
+int osh_host_mlpnp_solver_replay(void* solver, const int32_t* head, const double* hit_pose, const uint32_t* hit_mask, const double* best_pose,
+                                 const uint32_t* best_mask, int32_t n_matches, uint8_t* no_more, int32_t* n_inliers, uint8_t* inliers,
+                                 float* Tout);
+
 /* ---- ORBextractor::ComputeKeyPointsOctTree (include/ORBextractor.h, csrc/host/ORBextractor.cc, csrc/hosttest/orbextractor.cc) ---- */
 struct osh_fast_frame;
 struct osh_fast_result;

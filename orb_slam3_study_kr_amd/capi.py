@@ -36,6 +36,7 @@ c_int32_p = C.POINTER(C.c_int32)
 c_uint8_p = C.POINTER(C.c_uint8)
 c_int64_p = C.POINTER(C.c_int64)
 c_float_p = C.POINTER(C.c_float)
+c_uint32_p = C.POINTER(C.c_uint32)
 
 
 class LbaProblem(C.Structure):
@@ -398,6 +399,33 @@ OSH_TWOVIEW_MAX_TOTAL_MATCHES, OSH_TWOVIEW_MAX_TOTAL_ITERATIONS = 524288, 262144
  OSH_TWOVIEW_TOO_FEW_POINTS, OSH_TWOVIEW_LOW_PARALLAX) = range(7)
 
 
+class MlpnpProblem(C.Structure):
+    """``osh_mlpnp_problem`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("camera_type", C.c_int32), ("camera", C.c_float * 8), ("n", C.c_int32), ("bearing", c_double_p), ("p3d", c_double_p),
+                ("p2d", c_float_p), ("max_error", c_float_p), ("n_iterations", C.c_int32), ("sets", c_int32_p),
+                ("min_inliers", C.c_int32), ("best_inliers_in", C.c_int32), ("best_refine_ok_in", C.c_int32)]
+
+
+class MlpnpResult(C.Structure):
+    """``osh_mlpnp_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("first_hit", c_int32_p), ("hit_record", c_int32_p), ("hit_pose", c_double_p), ("hit_count", c_int32_p),
+                ("hit_mask", c_uint32_p), ("best_iteration", c_int32_p), ("best_count", c_int32_p), ("best_mask", c_uint32_p),
+                ("best_pose", c_double_p), ("best_refine_ok", c_int32_p), ("n_records", c_int32_p), ("debug_pose", c_double_p),
+                ("debug_count", c_int32_p), ("debug_record", c_int32_p), ("debug_record_count", c_int32_p),
+                ("debug_record_pose", c_double_p)]
+
+
+OSH_MLPNP_MAX_POINTS, OSH_MLPNP_MAX_ITERATIONS, OSH_MLPNP_MAX_PROBLEMS = 2048, 1024, 64
+OSH_MLPNP_PINHOLE, OSH_MLPNP_KB8 = 0, 1
+
+
+def mlpnp_mask_words(n: int) -> int:
+    """OSH_MLPNP_MASK_WORDS(n)."""
+    return 2 * ((n + 63) // 64)
+
+
 class MapPointBatch(C.Structure):
     """``osh_mappoint_batch`` (include/orbslam3_hip.h)."""
 
@@ -594,6 +622,9 @@ _SIGNATURES = {
     "osh_orb_newpoint_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_two_view_reconstruct": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(TwoViewProblem), C.POINTER(TwoViewResult)]),
     "osh_orb_two_view_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_mlpnp_solve": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MlpnpProblem), C.POINTER(MlpnpResult)]),
+    "osh_orb_mlpnp_check_inliers": (C.c_int, [C.c_void_p, C.POINTER(MlpnpProblem), C.c_int32, c_double_p, c_int32_p, c_uint32_p]),
+    "osh_orb_mlpnp_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_refresh_map_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MapPointBatch), C.POINTER(MapPointResult)]),
     "osh_orb_refresh_map_points_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_fast_detect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult)]),
@@ -738,6 +769,25 @@ _HOST_SIGNATURES = {
     "osh_host_compute_fisheye_stereo_matches": (C.c_int, [C.POINTER(HostFisheyeInput), C.c_int32, c_int32_p, c_int32_p, c_float_p, c_float_p, c_float_p]),
     "osh_host_kb8_triangulate_cpu": (C.c_int, [C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
     "osh_host_newpoint_triangulate_cpu": (C.c_int, [C.c_int32, C.POINTER(NewPointSegment), C.POINTER(NewPointResult), c_double_p]),
+    "osh_host_mlpnp_cpu": (C.c_int, [C.c_int32, C.POINTER(MlpnpProblem), C.POINTER(MlpnpResult), c_double_p]),
+    "osh_host_mlpnp_check_inliers": (C.c_int, [C.POINTER(MlpnpProblem), C.c_int32, c_double_p, c_int32_p, c_uint32_p]),
+    "osh_host_mlpnp_nullspace": (C.c_int, [c_double_p, c_double_p]),
+    "osh_host_mlpnp_rank": (C.c_int, [c_double_p]),
+    "osh_host_mlpnp_null_vector": (C.c_int, [c_double_p, C.c_int32, c_double_p]),
+    "osh_host_mlpnp_compute_pose": (C.c_int, [C.c_int32, c_double_p, c_double_p, c_double_p, c_int32_p]),
+    "osh_host_mlpnp_gauss_newton": (C.c_int, [C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int32, c_int32_p]),
+    "osh_host_mlpnp_ransac_parameters": (C.c_int, [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_float, c_int32_p]),
+    "osh_host_mlpnp_solver_create": (C.c_void_p, [C.c_int32, c_float_p, C.c_int32, c_float_p, c_int32_p, C.c_int32, c_float_p, C.c_int32, c_float_p,
+                                                  c_uint8_p]),
+    "osh_host_mlpnp_solver_destroy": (None, [C.c_void_p]),
+    "osh_host_mlpnp_solver_set_ransac": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float]),
+    "osh_host_mlpnp_solver_state": (C.c_int, [C.c_void_p, c_int32_p]),
+    "osh_host_mlpnp_solver_iterate": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, c_int32_p,
+                                                c_uint8_p, c_float_p]),
+    "osh_host_mlpnp_solver_prepare": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p]),
+    "osh_host_mlpnp_solver_replay": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, c_uint32_p, c_double_p, c_uint32_p, C.c_int32, c_uint8_p, c_int32_p,
+                                               c_uint8_p, c_float_p]),
+    "osh_host_mlpnp_replay": (C.c_int, [C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
     "osh_host_two_view_cpu": (C.c_int, [C.c_int32, C.POINTER(TwoViewProblem), C.POINTER(TwoViewResult), c_double_p]),
     "osh_host_two_view_normalize": (C.c_int, [C.c_int32, c_float_p, c_float_p, c_float_p]),
     "osh_host_two_view_decide": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_float_p, c_int32_p]),

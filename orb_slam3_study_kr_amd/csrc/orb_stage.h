@@ -11,6 +11,7 @@
 // orb_state and copy_times.  osh_orb_pyramid_build (orb_pyramid_device.hip) fills the resident pyramid: pack_level, PhaseClock, orb_state.
 // osh_orb_refresh_map_points (mappoint_device.hip) has batches of map points: it uses scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_two_view_reconstruct (two_view_device.hip) has problems of matches and minimal sets: scatter, PhaseClock, orb_state, copy_times.
+// osh_orb_mlpnp_solve (mlpnp_device.hip) has problems of correspondences and minimal sets: scatter, PhaseClock, orb_state.
 #pragma once
 #include "common.h"
 #include <chrono>

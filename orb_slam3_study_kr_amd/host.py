@@ -1062,6 +1062,116 @@ def two_view_reconstruct(scene, camera: str = "class", iterations: int = 200, p3
     return dict(ok=bool(rc), T21=T21, p3d=p3d, n_p3d=int(n_p3d.value), triangulated=tri, n_triangulated=int(n_tri.value), sets=sets, info=info)
 
 
+class MlpnpSolver:
+    """An MLPnPsolver (include/MLPnPsolver.h) of the stand-in classes, built from a synth_mlpnp.Problem: keypoint i of the frame is
+    correspondence order[i] (default: the problem's order), with `extra` keypoints without a map point in front and `bad` bad map
+    points behind; level_sigma2 is 1.2^(2 l) and every keypoint's octave is the one its max_error came from.  relocalisation: the
+    parameters Tracking::Relocalization sets (0.99, 10, 300, 6, 0.5, 5.991) instead of the constructor's."""
+
+    def __init__(self, pb, extra: int = 0, bad: int = 0, relocalisation: bool = False, ransac=None):
+        self.lib = capi.load_host_library()
+        n = pb.n
+        self.n_matches = extra + n + bad
+        self.index = extra + np.arange(n)     # mvKeyPointIndices of the problem's correspondences
+        sigma2 = (np.float32(1.2) ** (2 * np.arange(8))).astype(np.float32)
+        octave = np.zeros(self.n_matches, np.int32)
+        octave[self.index] = np.argmin(np.abs(np.asarray(pb.max_error, np.float32)[:, None] / np.float32(5.991) - sigma2[None, :]), 1)
+        xy = np.zeros((self.n_matches, 2), np.float32)
+        xy[self.index] = pb.p2d
+        world = np.zeros((self.n_matches, 3), np.float32)
+        world[self.index] = pb.p3d
+        state = np.zeros(self.n_matches, np.uint8)
+        state[self.index] = 1
+        state[extra + n:] = 2
+        cam = np.ascontiguousarray(pb.camera, np.float32)
+        self.handle = self.lib.osh_host_mlpnp_solver_create(int(pb.camera_type), capi.ptr(cam, capi.c_float_p), self.n_matches, capi.ptr(xy, capi.c_float_p),
+                                                            capi.ptr(octave, capi.c_int32_p), 8, capi.ptr(sigma2, capi.c_float_p), self.n_matches,
+                                                            capi.ptr(world, capi.c_float_p), capi.ptr(state, capi.c_uint8_p))
+        if not self.handle:
+            raise RuntimeError("osh_host_mlpnp_solver_create refused the arguments")
+        if relocalisation:
+            ransac = (0.99, 10, 300, 6, 0.5, 5.991)
+        if ransac is not None:
+            self.set_ransac(*ransac)
+
+    def set_ransac(self, probability, min_inliers, max_iterations, min_set, epsilon, th2):
+        if self.lib.osh_host_mlpnp_solver_set_ransac(self.handle, probability, min_inliers, max_iterations, min_set, epsilon, th2) != 0:
+            raise RuntimeError("osh_host_mlpnp_solver_set_ransac")
+
+    def state(self) -> dict:
+        out = np.zeros(7, np.int32)
+        self.lib.osh_host_mlpnp_solver_state(self.handle, capi.ptr(out, capi.c_int32_p))
+        return dict(zip(("N", "min_inliers", "max_iterations", "iterations", "best_inliers", "queued_sets", "on_device"), (int(v) for v in out)))
+
+    def iterate(self, n_iterations: int) -> dict:
+        return mlpnp_iterate([self], n_iterations, batch=False)[0]
+
+    def prepare(self, n_iterations: int, capacity: int = 1024):
+        """The sets one iterate(n_iterations) would run: [count, 6] (None when N < mRansacMinInliers)."""
+        sets = np.zeros((capacity, 6), np.int32)
+        rc = self.lib.osh_host_mlpnp_solver_prepare(self.handle, n_iterations, capacity, capi.ptr(sets, capi.c_int32_p))
+        if rc == -2:
+            return None
+        if rc < 0:
+            raise RuntimeError(f"osh_host_mlpnp_solver_prepare -> {rc}")
+        return sets[:min(rc, capacity)], rc
+
+    def replay(self, first_hit=-1, hit_record=-1, hit_count=0, best_iteration=-1, best_count=0, best_refine_ok=0, hit_pose=None, hit_flags=None,
+               best_pose=None, best_flags=None) -> dict:
+        """Walks a given answer of the device for the prepared round as iterate would."""
+        n = self.state()["N"]
+        words = capi.mlpnp_mask_words(n)
+
+        def mask(flags):
+            bits = np.zeros(words * 32, np.uint8)
+            if flags is not None:
+                bits[:n] = np.asarray(flags, bool)
+            return np.packbits(bits, bitorder="little").view(np.uint32).copy()
+
+        head = np.array([first_hit, hit_record, hit_count, best_iteration, best_count, best_refine_ok], np.int32)
+        hp = np.ascontiguousarray(np.zeros(12) if hit_pose is None else hit_pose, np.float64)
+        bp = np.ascontiguousarray(np.zeros(12) if best_pose is None else best_pose, np.float64)
+        hm, bm = mask(hit_flags), mask(best_flags)
+        no_more, n_in = np.zeros(1, np.uint8), np.zeros(1, np.int32)
+        inl, T = np.zeros(self.n_matches + 1, np.uint8), np.zeros(16, np.float32)
+        rc = self.lib.osh_host_mlpnp_solver_replay(self.handle, capi.ptr(head, capi.c_int32_p), capi.ptr(hp, capi.c_double_p), capi.ptr(hm, capi.c_uint32_p),
+                                                   capi.ptr(bp, capi.c_double_p), capi.ptr(bm, capi.c_uint32_p), self.n_matches,
+                                                   capi.ptr(no_more, capi.c_uint8_p), capi.ptr(n_in, capi.c_int32_p), capi.ptr(inl, capi.c_uint8_p),
+                                                   capi.ptr(T, capi.c_float_p))
+        if rc < 0:
+            raise RuntimeError(f"osh_host_mlpnp_solver_replay -> {rc}")
+        return dict(found=bool(rc), no_more=bool(no_more[0]), n_inliers=int(n_in[0]), inliers=inl[:-1].astype(bool), has_inliers=bool(inl[-1]),
+                    Tout=T.reshape(4, 4))
+
+    def close(self):
+        if self.handle:
+            self.lib.osh_host_mlpnp_solver_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def mlpnp_iterate(solvers, n_iterations: int, batch: bool = True) -> list:
+    """iterate(n_iterations, ..) of every MlpnpSolver, through MLPnPsolver::IterateBatch (one device call) or one by one: per solver
+    a dict with found, no_more, n_inliers, inliers [n_matches], has_inliers (vbInliers not empty) and Tout [4, 4]."""
+    lib = capi.load_host_library()
+    S = len(solvers)
+    m = max([s.n_matches for s in solvers], default=0)
+    handles = (C.c_void_p * max(S, 1))(*[s.handle for s in solvers])
+    found, no_more, n_in = np.zeros(S, np.uint8), np.zeros(S, np.uint8), np.zeros(S, np.int32)
+    inl, T = np.zeros((S, m + 1), np.uint8), np.zeros((S, 16), np.float32)
+    rc = lib.osh_host_mlpnp_solver_iterate(S, handles, int(n_iterations), int(batch), m, capi.ptr(found, capi.c_uint8_p), capi.ptr(no_more, capi.c_uint8_p),
+                                           capi.ptr(n_in, capi.c_int32_p), capi.ptr(inl, capi.c_uint8_p), capi.ptr(T, capi.c_float_p))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_mlpnp_solver_iterate -> {rc}")
+    return [dict(found=bool(found[k]), no_more=bool(no_more[k]), n_inliers=int(n_in[k]), inliers=inl[k, :s.n_matches].astype(bool),
+                 has_inliers=bool(inl[k, m]), Tout=T[k].reshape(4, 4).copy()) for k, s in enumerate(solvers)]
+
+
 def create_new_map_points(scene, coarse: bool = True, new_keyframe_waiting: bool = False, capacity: int = 4096) -> dict:
     """LocalMapping::CreateNewMapPoints on the stand-in classes built from a synth_newpoints.Scene (osh_host_create_new_map_points).
     Keyframe 0 is the current one, keyframe 1 + k neighbour k; the first two neighbours are covisibles, the third is reached

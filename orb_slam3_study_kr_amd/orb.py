@@ -206,6 +206,34 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_two_view_reconstruct(self.ctx, len(problems), cp, cr), "osh_orb_two_view_reconstruct", self.lib)
         return outs
 
+    def mlpnp_solve(self, problems, debug: bool = False, fill=None) -> list:
+        """MLPnPsolver::iterate behind its minimal-set draw (src/MLPnPsolver.cpp:100-353) for a batch of synth_mlpnp.Problem in one
+        osh_orb_mlpnp_solve call: per problem a dict with first_hit, hit_record, hit_pose [12], hit_count, hit_mask [words],
+        best_iteration, best_count, best_mask, best_pose, best_refine_ok, n_records, debug_count, debug_record, debug_record_count
+        [iterations], and with `debug` also debug_pose and debug_record_pose [iterations, 12]."""
+        cp, cr, _keep, outs = mlpnp_args(problems, debug, fill)
+        capi.check(self.lib.osh_orb_mlpnp_solve(self.ctx, len(problems), cp, cr), "osh_orb_mlpnp_solve", self.lib)
+        return outs
+
+    def mlpnp_check_inliers(self, problem, poses):
+        """CheckInliers (src/MLPnPsolver.cpp:262-293) of the poses [k, 12] against a synth_mlpnp.Problem's correspondences
+        (osh_orb_mlpnp_check_inliers): count [k], mask [k, words]."""
+        cp, _cr, _keep, _outs = mlpnp_args([problem])
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        count = np.zeros(poses.shape[0], np.int32)
+        mask = np.zeros((poses.shape[0], capi.mlpnp_mask_words(problem.n)), np.uint32)
+        capi.check(self.lib.osh_orb_mlpnp_check_inliers(self.ctx, cp, poses.shape[0], capi.ptr(poses, capi.c_double_p),
+                                                        capi.ptr(count, capi.c_int32_p), capi.ptr(mask, capi.c_uint32_p)),
+                   "osh_orb_mlpnp_check_inliers", self.lib)
+        return count, mask
+
+    def mlpnp_times(self):
+        """Phases (ms) of the last mlpnp_solve under set_profiling(True): staging, upload, kernels, download, and the hypothesis
+        kernel alone (part of the kernels)."""
+        ms = np.zeros(5, dtype=np.float64)
+        capi.check(self.lib.osh_orb_mlpnp_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_mlpnp_get_times", self.lib)
+        return ms
+
     def refresh_map_points(self, batches, want=None) -> list:
         """MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth (src/MapPoint.cc:329-403,426-494) for a list of
         synth_mappoints.Batch in one osh_orb_refresh_map_points call: per batch a dict with best_entry, best_median [n],
@@ -355,7 +383,7 @@ class BowDb:
 
 
 _POINTER = {np.dtype(np.float32): capi.c_float_p, np.dtype(np.int32): capi.c_int32_p, np.dtype(np.uint8): capi.c_uint8_p,
-            np.dtype(np.float64): capi.c_double_p, np.dtype(np.uint64): C.POINTER(C.c_uint64)}
+            np.dtype(np.float64): capi.c_double_p, np.dtype(np.uint64): C.POINTER(C.c_uint64), np.dtype(np.uint32): capi.c_uint32_p}
 # the keypoint arrays of a frame: attribute of the synthetic frame = field of the frame struct, key in the dict of arrays, dtype
 _KEYPOINTS = (("left_xy", "lxy", np.float32), ("left_octave", "loct", np.int32), ("left_desc", "ldesc", np.uint8),
               ("right_xy", "rxy", np.float32), ("right_octave", "roct", np.int32), ("right_desc", "rdesc", np.uint8))
@@ -1011,6 +1039,122 @@ def two_view_cpu(problems, debug: bool = False, host_lib=None):
     if rc != 0:
         raise RuntimeError(f"osh_host_two_view_cpu -> {rc}")
     return outs, float(ms.value)
+
+
+_MLPNP_ARRAYS = (("bearing", np.float64), ("p3d", np.float64), ("p2d", np.float32), ("max_error", np.float32), ("sets", np.int32))
+
+
+def mlpnp_args(problems, debug: bool = False, fill=None):
+    """The osh_mlpnp_problem / osh_mlpnp_result arrays of OrbMatcher.mlpnp_solve for repeated calls: (problems, results, the arrays
+    that keep their pointers alive, the per-problem dicts of output arrays).  fill: a byte the output arrays are pre-filled with
+    (None: zeros)."""
+    n_p = len(problems)
+    cp = (capi.MlpnpProblem * max(n_p, 1))()
+    cr = (capi.MlpnpResult * max(n_p, 1))()
+    keep, outs = [], []
+    for k, pb in enumerate(problems):
+        c = cp[k]
+        a = {name: np.ascontiguousarray(getattr(pb, name), dt) for name, dt in _MLPNP_ARRAYS}
+        n, it = a["p3d"].reshape(-1, 3).shape[0], a["sets"].reshape(-1, 6).shape[0]
+        c.camera_type = int(pb.camera_type)
+        c.camera[:] = [float(x) for x in np.asarray(pb.camera, np.float32).reshape(8)]
+        c.n, c.n_iterations = n, it
+        c.min_inliers, c.best_inliers_in, c.best_refine_ok_in = int(pb.min_inliers), int(pb.best_inliers_in), int(pb.best_refine_ok_in)
+        for name, dt in _MLPNP_ARRAYS:
+            setattr(c, name, capi.ptr(a[name], _POINTER[np.dtype(dt)]))
+        i32, f64, words = np.int32, np.float64, capi.mlpnp_mask_words(n)
+        o = dict(first_hit=np.zeros(1, i32), hit_record=np.zeros(1, i32), hit_pose=np.zeros(12, f64), hit_count=np.zeros(1, i32),
+                 hit_mask=np.zeros(words, np.uint32), best_iteration=np.zeros(1, i32), best_count=np.zeros(1, i32),
+                 best_mask=np.zeros(words, np.uint32), best_pose=np.zeros(12, f64), best_refine_ok=np.zeros(1, i32),
+                 n_records=np.zeros(1, i32), debug_count=np.zeros(it, i32), debug_record=np.zeros(it, i32),
+                 debug_record_count=np.zeros(it, i32))
+        if debug:
+            o.update(debug_pose=np.zeros((it, 12), f64), debug_record_pose=np.zeros((it, 12), f64))
+        if fill is not None:
+            for v in o.values():
+                v.view(np.uint8)[...] = fill
+        _wire_outputs(cr[k], o)
+        keep.append(a)
+        outs.append(o)
+    return cp, cr, keep, outs
+
+
+def mlpnp_cpu(problems, debug: bool = False, host_lib=None):
+    """csrc/mlpnp.h on the host in one thread (osh_host_mlpnp_cpu of the test library): the per-problem output dicts of mlpnp_solve
+    and the wall time in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    cp, cr, _keep, outs = mlpnp_args(problems, debug)
+    ms = C.c_double(0)
+    rc = host_lib.osh_host_mlpnp_cpu(len(problems), cp, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_mlpnp_cpu -> {rc}")
+    return outs, float(ms.value)
+
+
+def mlpnp_check_inliers_cpu(problem, poses, host_lib=None):
+    """CheckInliers of csrc/mlpnp.h on the host (osh_host_mlpnp_check_inliers): count [k], mask [k, words]."""
+    host_lib = host_lib or capi.load_host_library()
+    cp, _cr, _keep, _outs = mlpnp_args([problem])
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+    count = np.zeros(poses.shape[0], np.int32)
+    mask = np.zeros((poses.shape[0], capi.mlpnp_mask_words(problem.n)), np.uint32)
+    rc = host_lib.osh_host_mlpnp_check_inliers(cp, poses.shape[0], capi.ptr(poses, capi.c_double_p), capi.ptr(count, capi.c_int32_p),
+                                               capi.ptr(mask, capi.c_uint32_p))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_mlpnp_check_inliers -> {rc}")
+    return count, mask
+
+
+def mlpnp_mask_bits(mask, n: int) -> np.ndarray:
+    """The flags [.., n] of mask words [.., words]."""
+    m = np.ascontiguousarray(mask, np.uint32)
+    bits = np.unpackbits(m.view(np.uint8).reshape(m.shape[:-1] + (-1,)), axis=-1, bitorder="little")
+    return bits[..., :n].astype(bool)
+
+
+def mlpnp_stage(name: str, *args, host_lib=None):
+    """The stages of csrc/mlpnp.h on the host (osh_host_mlpnp_* of the test library).  "nullspace": f [3] -> N [3, 2].  "rank": S [3, 3]
+    -> rank.  "null_vector": M [c, c] -> h [c].  "compute_pose": bearing, p3d [n, 3] -> pose [12], info [3].  "gauss_newton": bearing,
+    p3d, x [6], max_iterations -> x [6], info [2].  "replay": count, min_inliers, best_in, ok_in, record_count -> record, out [7].  "ransac_parameters": N, probability, minInliers,
+    maxIterations, minSet, epsilon -> (mRansacMinInliers, mRansacMaxIts)."""
+    lib = host_lib or capi.load_host_library()
+    d = lambda a: np.ascontiguousarray(a, np.float64)
+    dp = lambda a: capi.ptr(a, capi.c_double_p)
+    ip = lambda a: capi.ptr(a, capi.c_int32_p)
+    if name == "nullspace":
+        f, N = d(args[0]), np.zeros((3, 2))
+        rc = lib.osh_host_mlpnp_nullspace(dp(f), dp(N))
+        out = N
+    elif name == "rank":
+        S = d(args[0])
+        return int(lib.osh_host_mlpnp_rank(dp(S)))
+    elif name == "null_vector":
+        M = d(args[0])
+        h = np.zeros(M.shape[0])
+        rc = lib.osh_host_mlpnp_null_vector(dp(M), M.shape[0], dp(h))
+        out = h
+    elif name == "compute_pose":
+        f, p, pose, info = d(args[0]), d(args[1]), np.zeros(12), np.zeros(3, np.int32)
+        rc = lib.osh_host_mlpnp_compute_pose(f.shape[0], dp(f), dp(p), dp(pose), ip(info))
+        out = (pose, info)
+    elif name == "gauss_newton":
+        f, p, x, info = d(args[0]), d(args[1]), d(args[2]).copy(), np.zeros(2, np.int32)
+        rc = lib.osh_host_mlpnp_gauss_newton(f.shape[0], dp(f), dp(p), dp(x), int(args[3]), ip(info))
+        out = (x, info)
+    elif name == "ransac_parameters":
+        res = np.zeros(2, np.int32)
+        rc = lib.osh_host_mlpnp_ransac_parameters(int(args[0]), float(args[1]), int(args[2]), int(args[3]), int(args[4]), float(args[5]), ip(res))
+        out = (int(res[0]), int(res[1]))
+    elif name == "replay":
+        count, rcount = np.ascontiguousarray(args[0], np.int32), np.ascontiguousarray(args[4], np.int32)
+        record, res = np.full(max(count.shape[0], 1), -1, np.int32), np.zeros(7, np.int32)
+        rc = lib.osh_host_mlpnp_replay(count.shape[0], ip(count), int(args[1]), int(args[2]), int(args[3]), ip(rcount), ip(record), ip(res))
+        out = (record[:int(res[6])], res)
+    else:
+        raise ValueError(name)
+    if rc != 0:
+        raise RuntimeError(f"osh_host_mlpnp_{name} -> {rc}")
+    return out
 
 
 _MAPPOINT_ARRAYS = (("entry_off", np.int32), ("desc", np.uint8), ("centre", np.int32), ("use_desc", np.uint8), ("centres", np.float32),
