@@ -295,8 +295,8 @@ int osh_posei_optimize(osh_lba_ctx* ctx, int32_t n, const osh_posei_problem* pro
  * osh_posei_optimize, told to leave after its first buildSystem. */
 int osh_posei_linearize(osh_lba_ctx* ctx, const osh_posei_problem* frame, double* H, double* b);
 
-/* Statistics of the Schur work plan of the resident batch: {items, symmetric items, v_mfma_f64_16x16x4 instructions of one
- * pass over every window, useful 6x6x3 products of one pass (upper triangle), contribution slots, reduce entries, landmark records,
+/* Statistics of the Schur work plan of the resident batch: {items, symmetric items, matrix work of one pass over every window
+ * in v_mfma_f64_16x16x4 instructions (2048 flop; a four-block 4x4x4 instruction counts a quarter), useful 6x6x3 products of one pass (upper triangle), contribution slots, reduce entries, landmark records,
  * right-hand-side contribution slots}. */
 int osh_lba_get_plan_stats(osh_lba_ctx* ctx, int64_t stats[8]);
 
@@ -306,6 +306,19 @@ int osh_lba_get_plan_stats(osh_lba_ctx* ctx, int64_t stats[8]);
  * stats = {items, symmetric items, records, contributions, rhs contributions, MFMA instructions
  * per pass, useful 6x6 products per pass, reduce entries}. */
 int osh_lba_schur_plan_stats(const osh_lba_problem* problem, int64_t stats[8]);
+
+/* Host-only (needs no GPU): the item shapes of the Schur plan of `problem` cut at item_max landmarks per item (<= 0: what a call
+ * with one window uses): hist[((sym * 9 + nx) * 9 + ny) * 65 + landmarks] = number of such items (2 * 9 * 9 * 65 entries), and
+ * cycles = matrix-pipe cycles of one pass {with whole 16x16x4 tiles, with the symmetric items' four-block instructions} at 64 / 17
+ * cycles per instruction. */
+int osh_lba_schur_plan_shapes(const osh_lba_problem* problem, int item_max, int64_t* hist, int64_t cycles[2]);
+
+/* Host-only: the matrix instructions of one k step of an item of shape (sym, nx, ny), with the symmetric items' four-block
+ * instructions (use_blocks != 0) or whole tiles: 16 ints per instruction into out (room for 24), their number into *n_instr.
+ * {kind, ti, tj, 0, then for block q = 0 .. 3: block row, block column, use}; kind 0: a 16x16x4 of tile (ti, tj); kind 1: four
+ * 4 x 4 blocks (of image rows 4 b .. 4 b + 3), use 0: not stored, 1: stored where it lies, 2: also mirrored inside a diagonal
+ * pose pair. */
+int osh_lba_schur_block_list(int sym, int nx, int ny, int use_blocks, int32_t* out, int* n_instr);
 
 /* Host-only self check + timing of the batch packer osh_lba_upload runs before its copies (needs no GPU): landmark-major
  * edge order, landmark renumbering along the Schur plan, sign-coded observation records, merged fisheye-rig edges, chunks,

@@ -588,6 +588,8 @@ _SIGNATURES = {
     "osh_lba_set_pack_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "osh_lba_pack_compare": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(LbaProblem), c_int64_p]),
     "osh_lba_schur_plan_stats": (C.c_int, [C.POINTER(LbaProblem), c_int64_p]),
+    "osh_lba_schur_plan_shapes": (C.c_int, [C.POINTER(LbaProblem), C.c_int, c_int64_p, c_int64_p]),
+    "osh_lba_schur_block_list": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p]),
     "osh_lba_pack_check": (C.c_int, [C.c_int32, C.POINTER(LbaProblem), C.c_int32, c_int64_p, c_double_p]),
     "osh_liba_pack_check": (C.c_int, [C.c_int32, C.POINTER(LibaProblem), c_int64_p]),
     "osh_lm_control_check": (C.c_int, [C.c_double, C.c_double, C.c_int32, c_double_p, c_int32_p, c_double_p, c_double_p, c_double_p,

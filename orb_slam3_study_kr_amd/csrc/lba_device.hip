@@ -485,9 +485,22 @@ constexpr int kSiRows = 6 * kItemPoses;
 // the Schur products are the same bits as with 8 x 8 chunks.  (32 x 2 for items of one or two poses -- 18 % of the chunks -- was
 // measured too and gained nothing over 16 x 4: with one tile the 24 k steps of such a chunk are one dependent MFMA chain.)
 constexpr int kSiImage = 32 * 49;
+// BLK (symmetric pinhole items, unless OSH_LBA_SCHUR_TILES is set at upload): the tiles of which only a part is ever stored are formed
+// from 4 x 4 blocks, four to a v_mfma_f64_4x4x4_4b_f64 (17 cycles against the 64 of a 16x16x4, the same bits entry by entry and
+// (r, c) == (c, r): profiles/ubench/mfma_f64_blocks.hip).  Of block q = (lane >> 2) & 3 a lane holds A[row = lane & 3][k = lane >> 4],
+// B[col = lane & 3][k = lane >> 4] and D[row = lane >> 4][col = lane & 3], so the tile operand a[t] (image row 16 t + (lane & 15)) is
+// block row q of tile t for the four blocks at once, on either side.  With nx row poses the image has 6 nx rows:
+//   a diagonal tile of four live block rows: a[t] x a[t] (blocks (q, q)), a[t] x a[t] turned by one block row ((q, q + 1 mod 4): (3, 0)
+//     is (0, 3) mirrored) and by two ((0, 2), (1, 3); the other two repeat them): 3 instructions, 51 cycles instead of 64
+//   the last tile column when only L < 4 of its block rows hold image rows (nx = 1 .. 4, 6, 7): a[ti] x block row c of it, the same
+//     for all four blocks, c < L, for every tile row ti up to the diagonal: L instructions, and on the diagonal blocks (q <= c) only
+//   every other tile: 16x16x4 as before.
+// Every instruction of k step ks reads image columns 4 ks .. 4 ks + 3: the k sequence of every entry is the one of the tiles.
+// (schur_plan.h: schur_live_blocks, and schur_step for the instruction counts.)
 
-template <bool SYM, bool KB8>
+template <bool SYM, bool KB8, bool BLK = false>
 __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, int item_base, int mode) {
+  static_assert(!BLK || (SYM && !KB8), "block path: symmetric pinhole items");
   __shared__ double shA[(SYM && !KB8) ? kSiImage : kSiRows * (3 * kSiLm + 1)];   // (the wider mappings: symmetric pinhole items only)
   __shared__ double shB[SYM ? 1 : kSiRows * (3 * kSiLm + 1)];
   __shared__ double shPose[(SYM ? 1 : 2) * 8 * kPoseRec];
@@ -545,6 +558,13 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
     for (int a = 0; a < 3; ++a)
 #pragma unroll
       for (int b = 0; b < 3; ++b) acc[a][b] = (f64x4){0.0, 0.0, 0.0, 0.0};
+    double bacc[3][3][3];   // BLK: [tile row][tile column][four-block instruction], one entry per lane each
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) bacc[a][b][q] = 0.0;
     double csum[6] = {0, 0, 0, 0, 0, 0};
     double H[21], hb[6];
 #pragma unroll
@@ -648,6 +668,95 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
         if (ks & 1) __builtin_amdgcn_sched_barrier(0);   // operands of two k-steps in flight at most (the prefetched chunk needs the registers)
       }
     };
+    // BLK: the multiply of an item of NX row poses (see above k_schur_fused).  The row offsets of the turned and the single-block-row
+    // operands are the lane's own for the whole item; per k step they cost one LDS read each beside the a[t] of the tiles.
+    const int off_a = mrow * KS + mk, off_s1 = ((mrow + 4) & 15) * KS + mk, off_s2 = ((mrow + 8) & 15) * KS + mk, off_c = (lane & 3) * KS + mk;
+    auto multiply_b = [&](auto nxc) {
+      constexpr int NX = decltype(nxc)::value, TXc = (6 * NX + 15) / 16, LL = schur_live_blocks(NX, TXc - 1);   // only the last tile is ragged
+#pragma unroll
+      for (int ks = 0; ks < KST; ++ks) {
+        double a[3], s1[3], s2[3], cb[3];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+          const bool full = t < TXc && (t < TXc - 1 || LL == 4);
+          a[t] = (t < TXc) ? shA[16 * t * KS + off_a + 4 * ks] : 0.0;
+          s1[t] = full ? shA[16 * t * KS + off_s1 + 4 * ks] : 0.0;
+          s2[t] = full ? shA[16 * t * KS + off_s2 + 4 * ks] : 0.0;
+          cb[t] = (LL < 4 && t < LL) ? shA[(16 * (TXc - 1) + 4 * t) * KS + off_c + 4 * ks] : 0.0;
+        }
+#pragma unroll
+        for (int ti = 0; ti < TXc; ++ti)
+#pragma unroll
+          for (int tj = ti; tj < TXc; ++tj) {
+            if (tj == TXc - 1 && LL < 4) {
+#pragma unroll
+              for (int c = 0; c < LL; ++c) bacc[ti][tj][c] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[ti], cb[c], bacc[ti][tj][c], 0, 0, 0);
+            } else if (ti == tj) {
+              bacc[ti][ti][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[ti], a[ti], bacc[ti][ti][0], 0, 0, 0);
+              bacc[ti][ti][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[ti], s1[ti], bacc[ti][ti][1], 0, 0, 0);
+              bacc[ti][ti][2] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[ti], s2[ti], bacc[ti][ti][2], 0, 0, 0);
+            } else {
+              acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], a[tj], acc[ti][tj], 0, 0, 0);
+            }
+          }
+        if (ks & 1) __builtin_amdgcn_sched_barrier(0);   // as in multiply_t
+      }
+    };
+    // BLK: the contributions of the item, the entries multiply_t's tiles would have stored and no others.  Pose pairs sa < sb only
+    // have blocks with block row <= block column (schur_plan.h marks pair (sa, sb) live for sa <= sb only); a diagonal pair's 6 x 6
+    // contribution is stored in full wherever both (r, c) and (c, r) lie in one diagonal tile, as the tile stored it.
+    auto store_b = [&](auto nxc) {
+      constexpr int NX = decltype(nxc)::value, TXc = (6 * NX + 15) / 16, LL = schur_live_blocks(NX, TXc - 1);
+      const int bi = lane >> 4, bq = (lane >> 2) & 3, bj = lane & 3;
+      // entry (R, C), R <= C; mirrored: an off-diagonal block of a diagonal tile also fills (C, R) of a diagonal pose pair
+      auto put = [&](int R, int C, double v, bool mirrored) {
+        const int sa = R / 6, rr = R - 6 * sa, sb = C / 6, cc = C - 6 * sb;
+        const int slot = shP[sa * 8 + sb];
+        if (slot >= 0) {
+          bv.contrib[(size_t)slot * 36 + rr * 6 + cc] = v;
+          if (mirrored && sa == sb) bv.contrib[(size_t)slot * 36 + cc * 6 + rr] = v;
+        }
+      };
+#pragma unroll
+      for (int ti = 0; ti < TXc; ++ti)
+#pragma unroll
+        for (int tj = ti; tj < TXc; ++tj) {
+          if (tj == TXc - 1 && LL < 4) {
+#pragma unroll
+            for (int c = 0; c < LL; ++c) {
+              const int R = 16 * ti + 4 * bq + bi, C = 16 * tj + 4 * c + bj;
+              if (ti < tj || bq == c) {
+                const int sa = R / 6, sb = C / 6, slot = shP[sa * 8 + sb];   // as the tile: (r, c) where the lane holds it
+                if (slot >= 0) bv.contrib[(size_t)slot * 36 + (R - 6 * sa) * 6 + (C - 6 * sb)] = bacc[ti][tj][c];
+              } else if (bq < c) {
+                put(R, C, bacc[ti][tj][c], true);
+              }
+            }
+          } else if (ti == tj) {
+            const int R = 16 * ti + 4 * bq + bi;
+            {
+              const int C = 16 * ti + 4 * bq + bj;
+              const int sa = R / 6, sb = C / 6, slot = shP[sa * 8 + sb];
+              if (slot >= 0) bv.contrib[(size_t)slot * 36 + (R - 6 * sa) * 6 + (C - 6 * sb)] = bacc[ti][ti][0];
+            }
+            {
+              const int C = 16 * ti + 4 * ((bq + 1) & 3) + bj;   // block (3, 0): the mirror image of (0, 3)
+              put(bq == 3 ? C : R, bq == 3 ? R : C, bacc[ti][ti][1], true);
+            }
+            if (bq < 2) put(R, 16 * ti + 4 * (bq + 2) + bj, bacc[ti][ti][2], true);
+          } else {
+            const int C = 16 * tj + (lane & 15);
+            const int sb = C / 6, cc = C - 6 * sb;
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+              const int R = 16 * ti + (lane >> 4) + 4 * reg;
+              const int sa = R / 6, rr = R - 6 * sa;
+              const int slot = shP[sa * 8 + sb];
+              if (slot >= 0) bv.contrib[(size_t)slot * 36 + rr * 6 + cc] = acc[ti][tj][reg];
+            }
+          }
+        }
+    };
     auto multiply_cross = [&]() {
       // Cross items that come here (fisheye, or more than 4 column poses: parts b of tracks with 13+ observers) keep run-time tile
       // tests: nine instantiations cost registers for no gain.  Pinhole cross items of at most 4 column poses -- every cross item of
@@ -675,6 +784,7 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
     wave_sync();   // the staged poses are visible
     // The chunk loop is instantiated per tile count (dispatched ONCE per item): a dispatch inside the loop makes the compiler
     // reconcile the register assignment of the accumulators at every merge (dozens of 64-bit moves per chunk).
+    // (BLK: per number of row poses, so that the block list of the ragged last tile is a compile-time constant too)
     auto chunk_loop = [&](auto txc) {
       for (int c0 = 0; c0 < it.n_lm; c0 += LM) {
         park(c0, rc0, rc1, d);                 // edge descriptions, W F rows of chunk c0 -> LDS (consumes d)
@@ -683,22 +793,40 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
         load_dat(rc0, rc1, d);                 // chunk c0 + 1: in flight during the MFMAs below
         load_rec(c0 + 2 * LM, rn0, rn1);
         if (do_schur) {
-          if (SYM) multiply_t(txc, txc); else multiply_cross();
+          if constexpr (BLK && decltype(txc)::value > 0) multiply_b(txc);   // (txc: NX)
+          else if (SYM) multiply_t(txc, txc);
+          else multiply_cross();
         }
       }
+      if constexpr (BLK && decltype(txc)::value > 0) store_b(txc);
     };
     if (SYM && do_schur) {   // TX == TY
-      if (PS > 5 && TX == 3) chunk_loop(integral_constant<int, 3>{});
-      else if (PS > 2 && TX == 2) chunk_loop(integral_constant<int, 2>{});
-      else chunk_loop(integral_constant<int, 1>{});
+      if constexpr (BLK) {
+        if constexpr (PS == 8) {
+          if (nx >= 8) chunk_loop(integral_constant<int, 8>{});
+          else if (nx == 7) chunk_loop(integral_constant<int, 7>{});
+          else chunk_loop(integral_constant<int, 6>{});
+        } else if constexpr (PS == 5) {
+          chunk_loop(integral_constant<int, 5>{});
+        } else {
+          if (nx >= 4) chunk_loop(integral_constant<int, 4>{});
+          else if (nx == 3) chunk_loop(integral_constant<int, 3>{});
+          else if (nx == 2) chunk_loop(integral_constant<int, 2>{});
+          else chunk_loop(integral_constant<int, 1>{});
+        }
+      } else {
+        if (PS > 5 && TX == 3) chunk_loop(integral_constant<int, 3>{});
+        else if (PS > 2 && TX == 2) chunk_loop(integral_constant<int, 2>{});
+        else chunk_loop(integral_constant<int, 1>{});
+      }
     } else {
       chunk_loop(integral_constant<int, 0>{});
     }
     wave_sync();
     if (do_schur) {
-      // contributions: lane holds D[row = (lane >> 4) + 4 reg][col = lane & 15] of each tile
+      // contributions: lane holds D[row = (lane >> 4) + 4 reg][col = lane & 15] of each tile  (BLK: stored by store_b)
 #pragma unroll
-      for (int ti = 0; ti < 3; ++ti)
+      for (int ti = 0; ti < (BLK ? 0 : 3); ++ti)
 #pragma unroll
         for (int tj = SYM ? ti : 0; tj < 3; ++tj) {
           if (ti < TX && tj < TY) {
@@ -1820,7 +1948,9 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
     c->kp_residual = f32 ? k_residual<true, true> : k_residual<true, false>; c->kp_finalize = k_finalize<true>;
     c->kp_backsub = f32 ? k_backsub<true, true> : k_backsub<true, false>; c->kp_debug_hpl = k_debug_hpl<true>;
   } else {
-    c->kp_lin_lm = f32 ? k_lin_lm<false, true> : k_lin_lm<false, false>; c->kp_schur_sym = k_schur_fused<true, false>; c->kp_schur_cross = k_schur_fused<false, false>;
+    c->kp_lin_lm = f32 ? k_lin_lm<false, true> : k_lin_lm<false, false>; c->kp_schur_cross = k_schur_fused<false, false>;
+    // symmetric items: the diagonal and ragged tiles from 4 x 4 blocks; OSH_LBA_SCHUR_TILES keeps whole tiles (the same bits: tests/test_gpu_schur_blocks.py)
+    c->kp_schur_sym = std::getenv("OSH_LBA_SCHUR_TILES") ? k_schur_fused<true, false> : k_schur_fused<true, false, true>;
     c->kp_residual = f32 ? k_residual<false, true> : k_residual<false, false>; c->kp_finalize = k_finalize<false>;
     c->kp_backsub = f32 ? k_backsub<false, true> : k_backsub<false, false>; c->kp_debug_hpl = k_debug_hpl<false>;
   }

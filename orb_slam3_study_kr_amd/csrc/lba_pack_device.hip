@@ -849,9 +849,7 @@ __global__ __launch_bounds__(NT, 8) void k_pack_pre2(PackArgs a) {
       z.builds[b].clive = (int)cl;
       atomicAdd(&sh_n[7], __popc(lo) + __popc(hi));
       atomicAdd(&sh_n[8], __popc(cl));
-      const int tx = tiles_of_dev(nx), ty = tiles_of_dev(ny);
-      const long long tiles = sym ? (long long)tx * (tx + 1) / 2 : (long long)tx * ty;
-      atomicAdd((u64*)&sh_ts, (u64)(tiles * 6 * (long long)((bd.n + 7) / 8)));
+      atomicAdd((u64*)&sh_ts, (u64)schur_item_steps(sym, nx, ny, bd.n));
     }
   }
   __syncthreads();

@@ -39,6 +39,60 @@ inline int item_max_lm(int nw) {
 }
 constexpr unsigned kAbsent = 0xffu;
 
+// The matrix instructions of one k step of an item (k_schur_fused, and the statistics of the plan: both packers and the host check).
+// An item of n poses on a side has 6 n image rows in tiles of 16; of the last tile only schur_live_blocks() block rows of 4 hold image
+// rows.  Symmetric items form a diagonal tile of four live block rows with 3 four-block instructions (v_mfma_f64_4x4x4_4b_f64), a last
+// tile column of L < 4 live block rows with L of them per tile row (the diagonal included), every other tile on or above the diagonal
+// with one v_mfma_f64_16x16x4_f64; cross items one 16x16x4 per tile.
+constexpr int schur_tiles(int n) { return (6 * n + 15) / 16; }
+constexpr int schur_live_blocks(int n, int t) { return (6 * n - 16 * t + 3) / 4 < 4 ? (6 * n - 16 * t + 3) / 4 : 4; }
+struct SchurStep { int tiles, blocks; };   // 16x16x4 instructions, four-block instructions
+constexpr SchurStep schur_step(bool sym, int nx, int ny, bool use_blocks = true) {
+  const int tx = schur_tiles(nx), ty = schur_tiles(ny);
+  if (!sym) return SchurStep{tx * ty, 0};
+  if (!use_blocks) return SchurStep{tx * (tx + 1) / 2, 0};
+  const int last = schur_live_blocks(nx, tx - 1);
+  const int full = last == 4 ? tx : tx - 1;   // tile columns with four live block rows
+  return SchurStep{full * (full - 1) / 2, 3 * full + (last < 4 ? last * tx : 0)};
+}
+// the statistic SchurPlan::tile_steps of an item of n landmarks: issued matrix flop / 2048 (a four-block instruction is a quarter of a 16x16x4)
+constexpr long long schur_item_steps(bool sym, int nx, int ny, int n) {
+  return (long long)(4 * schur_step(sym, nx, ny).tiles + schur_step(sym, nx, ny).blocks) * 6 * ((n + 7) / 8) / 4;
+}
+// The instructions of one k step one by one, for the host check of what they cover (tests/test_schur_blocks_cpu.py); k_schur_fused's
+// multiply_b / store_b unroll the same rule.  kind 0: 16x16x4 of tile (ti, tj).  kind 1: four blocks; brow / bcol: the block row and
+// column (of 4 image rows) whose product block q holds AS IT IS STORED; use 0: not stored, 1: stored where it lies, 2: stored where it
+// lies and, inside a diagonal pose pair, mirrored too.
+struct SchurInstr { int kind, ti, tj, brow[4], bcol[4], use[4]; };
+constexpr int kSchurInstrMax = 24;
+inline int schur_instr_list(bool sym, int nx, int ny, bool use_blocks, SchurInstr* out) {
+  const int tx = schur_tiles(nx), ty = schur_tiles(ny), last = schur_live_blocks(nx, tx - 1);
+  int n = 0;
+  auto tile = [&](int ti, int tj) { SchurInstr& I = out[n++]; I = SchurInstr{}; I.kind = 0; I.ti = ti; I.tj = tj; };
+  for (int ti = 0; ti < tx; ++ti)
+    for (int tj = sym ? ti : 0; tj < ty; ++tj) {
+      if (!sym || !use_blocks) { tile(ti, tj); continue; }
+      if (tj == tx - 1 && last < 4) {            // the ragged last tile column: a[ti] x block row c of it
+        for (int c = 0; c < last; ++c) {
+          SchurInstr& I = out[n++]; I = SchurInstr{}; I.kind = 1; I.ti = ti; I.tj = tj;
+          for (int q = 0; q < 4; ++q) { I.brow[q] = 4 * ti + q; I.bcol[q] = 4 * tj + c; I.use[q] = (ti < tj || q == c) ? 1 : (q < c ? 2 : 0); }
+        }
+      } else if (ti == tj) {                     // a diagonal tile: a[t] x a[t], x a[t] turned by one and by two block rows
+        for (int turn = 0; turn < 3; ++turn) {
+          SchurInstr& I = out[n++]; I = SchurInstr{}; I.kind = 1; I.ti = ti; I.tj = tj;
+          for (int q = 0; q < 4; ++q) {
+            const int c = (q + turn) & 3;        // block (q, c); (3, 0) is stored as (0, 3)
+            I.brow[q] = 4 * ti + (q < c ? q : c); I.bcol[q] = 4 * ti + (q < c ? c : q);
+            I.use[q] = turn == 0 ? 1 : ((turn == 1 || q < 2) ? 2 : 0);
+          }
+        }
+      } else {
+        tile(ti, tj);
+      }
+    }
+  return n;
+}
+
 struct SItem { int win, rec_off, n_lm, shape; };  // shape = nx | ny << 8 | sym << 16
 struct SRec {
   int lm, e_first;                // window-local landmark, its first sorted edge (window-local)
@@ -60,7 +114,7 @@ struct SchurPlan {
   std::vector<RBlk> rblk;         // every block of every window + one rhs segment per pose
   size_t n_contrib = 0, n_ccontrib = 0;
   // statistics
-  long long tile_steps = 0;       // MFMA instructions of one pass
+  long long tile_steps = 0;       // MFMA work of one pass in v_mfma_f64_16x16x4_f64 instructions (schur_item_steps)
   long long pair_blocks = 0;      // useful 6x6 products (upper triangle, per landmark)
 };
 
@@ -249,9 +303,7 @@ inline bool plan_window(int w, int P, int L, const int* lmo, const int* nfree, c
             if (((ys >> (8 * sb)) & 0xff) != kAbsent) bd.pair_slot[sa * 8 + sb] = -2;
         }
       }
-      const int tx = tiles_of(ncx), ty = tiles_of(ncy);
-      const long long tiles = cur_sym ? (long long)tx * (tx + 1) / 2 : (long long)tx * ty;
-      plan.tile_steps += tiles * 6 * (long long)((end - base + 7) / 8);
+      plan.tile_steps += schur_item_steps(cur_sym, ncx, ncy, (int)(end - base));
     }
     cur0 = cur1;
   };

@@ -10,17 +10,23 @@
 
 using namespace osh;
 
-extern "C" int osh_lba_schur_plan_stats(const osh_lba_problem* p, int64_t stats[8]) {
-  if (!p || !stats) { set_error("osh_lba_schur_plan_stats: NULL argument"); return OSH_ERR_INVALID; }
+// the plan of one window as osh_lba_upload builds it, items of at most item_max landmarks
+struct WindowPlan {
+  std::vector<std::vector<int>> obs;   // optimisable-pose edges of every landmark, poses ascending (what upload's sort produces)
+  std::vector<int> lmo, nfree, epose;
+  SchurPlan plan;
+};
+static int build_window_plan(const osh_lba_problem* p, int item_max, WindowPlan& wp) {
   const int P = p->n_free, L = p->n_points;
-  // optimisable-pose edges of every landmark, poses ascending (what upload's sort produces)
-  std::vector<std::vector<int>> obs(L);
+  std::vector<std::vector<int>>& obs = wp.obs;
+  std::vector<int>&lmo = wp.lmo, &nfree = wp.nfree, &epose = wp.epose;
+  obs.assign(L, {});
   for (int e = 0; e < p->n_edges; ++e) {
     const int ip = p->edge_pose[e], il = p->edge_point[e];
     if (ip < 0 || ip >= P + p->n_fixed || il < 0 || il >= L) { set_error("edge %d out of range", e); return OSH_ERR_INVALID; }
     if (ip < P) obs[il].push_back(ip);
   }
-  std::vector<int> lmo(L + 1, 0), nfree(L), epose;
+  lmo.assign(L + 1, 0); nfree.assign(L, 0);
   for (int j = 0; j < L; ++j) {
     std::sort(obs[j].begin(), obs[j].end());
     for (size_t k = 1; k < obs[j].size(); ++k)
@@ -31,14 +37,64 @@ extern "C" int osh_lba_schur_plan_stats(const osh_lba_problem* p, int64_t stats[
   }
   lmo[L] = (int)epose.size();
   epose.push_back(0);
-  SchurPlan plan;
   std::vector<plan_detail::Build> builds;
   std::vector<SRec> brecs;
   plan_detail::PlanScratch psc;
-  // (a call with one window cuts its items at item_max_lm(1) landmarks; OSH_LBA_ITEM_MAX overrides it: the tests run the check at 8, 24 and 64)
-  if (!plan_window(0, P, L, lmo.data(), nfree.data(), epose.data(), builds, brecs, plan, psc, item_max_lm(1))) { set_error("landmark with > 254 observers"); return OSH_ERR_UNSUPPORTED; }
+  if (!plan_window(0, P, L, lmo.data(), nfree.data(), epose.data(), builds, brecs, wp.plan, psc, item_max)) { set_error("landmark with > 254 observers"); return OSH_ERR_UNSUPPORTED; }
   std::vector<int> build_win(builds.size(), 0);
-  finish_plan(build_win, builds, brecs, plan);
+  finish_plan(build_win, builds, brecs, wp.plan);
+  return OSH_OK;
+}
+
+// Shapes of the plan of one window (needs no GPU): hist[sym][nx][ny][landmarks] = items of that shape ([2][9][9][65]), and the
+// matrix-pipe cycles of one pass with whole tiles and with the four-block instructions of the symmetric items, at the 64 and 17
+// cycles per instruction that profiles/ubench/mfma_f64_blocks.hip measured.  item_max <= 0: what a call with one window uses.
+extern "C" int osh_lba_schur_plan_shapes(const osh_lba_problem* p, int item_max, int64_t* hist, int64_t cycles[2]) {
+  if (!p || !hist || !cycles) { set_error("osh_lba_schur_plan_shapes: NULL argument"); return OSH_ERR_INVALID; }
+  if (item_max > kItemMaxLm) { set_error("osh_lba_schur_plan_shapes: item_max %d > %d", item_max, kItemMaxLm); return OSH_ERR_INVALID; }
+  WindowPlan wp;
+  if (const int rc = build_window_plan(p, item_max > 0 ? item_max : item_max_lm(1), wp)) return rc;
+  std::fill(hist, hist + 2 * 9 * 9 * 65, (int64_t)0);
+  cycles[0] = cycles[1] = 0;
+  for (const SItem& I : wp.plan.items) {
+    const int nx = I.shape & 0xff, ny = (I.shape >> 8) & 0xff, sym = (I.shape >> 16) & 1;
+    if (nx > 8 || ny > 8 || I.n_lm > 64) { set_error("plan: item of shape (%d, %d), %d landmarks", nx, ny, I.n_lm); return OSH_ERR_DEVICE; }
+    hist[((sym * 9 + nx) * 9 + ny) * 65 + I.n_lm]++;
+    const long long ksteps = 6 * (long long)((I.n_lm + 7) / 8);
+    const SchurStep t = schur_step(sym, nx, ny, false), b = schur_step(sym, nx, ny, true);
+    cycles[0] += ksteps * (64 * t.tiles + 17 * t.blocks);
+    cycles[1] += ksteps * (64 * b.tiles + 17 * b.blocks);
+  }
+  return OSH_OK;
+}
+
+// The matrix instructions of one k step of an item of shape (sym, nx, ny) as k_schur_fused issues and stores them (needs no GPU):
+// 16 ints per instruction, at most 24 instructions; *n_instr = their number.  {kind, ti, tj, 0, then per block q = 0 .. 3:
+// block row, block column, use}.  kind 0: one 16x16x4 of tile (ti, tj), every entry stored where it lies if its pose pair is live.
+// kind 1: four blocks of 4 x 4 (block row / column: image rows 4 b .. 4 b + 3); use 0: not stored, 1: stored where it lies, 2: stored
+// where it lies and, inside a diagonal pose pair, at the mirrored place too.
+extern "C" int osh_lba_schur_block_list(int sym, int nx, int ny, int use_blocks, int32_t* out, int* n_instr) {
+  if (!out || !n_instr || nx < 1 || nx > 8 || ny < 1 || ny > 8 || (sym && nx != ny)) { set_error("osh_lba_schur_block_list: invalid argument"); return OSH_ERR_INVALID; }
+  SchurInstr list[kSchurInstrMax];
+  const int n = schur_instr_list(sym != 0, nx, ny, use_blocks != 0, list);
+  for (int k = 0; k < n; ++k) {
+    int32_t* o = out + 16 * k;
+    o[0] = list[k].kind; o[1] = list[k].ti; o[2] = list[k].tj; o[3] = 0;
+    for (int q = 0; q < 4; ++q) { o[4 + 3 * q] = list[k].brow[q]; o[5 + 3 * q] = list[k].bcol[q]; o[6 + 3 * q] = list[k].use[q]; }
+  }
+  *n_instr = n;
+  return OSH_OK;
+}
+
+extern "C" int osh_lba_schur_plan_stats(const osh_lba_problem* p, int64_t stats[8]) {
+  if (!p || !stats) { set_error("osh_lba_schur_plan_stats: NULL argument"); return OSH_ERR_INVALID; }
+  const int P = p->n_free, L = p->n_points;
+  // (a call with one window cuts its items at item_max_lm(1) landmarks; OSH_LBA_ITEM_MAX overrides it: the tests run the check at 8, 24 and 64)
+  WindowPlan wp;
+  if (const int rc = build_window_plan(p, item_max_lm(1), wp)) return rc;
+  const std::vector<std::vector<int>>& obs = wp.obs;
+  const std::vector<int>&lmo = wp.lmo, &nfree = wp.nfree;
+  const SchurPlan& plan = wp.plan;
 
   // ---- verification
   std::map<std::pair<int, int>, std::pair<int, int>> range;   // block -> [start, start+count)

@@ -269,6 +269,30 @@ class LbaSolver:
         return {capi.KERNEL_NAMES[k]: (int(launches[k]), float(ms[k])) for k in range(capi.OSH_K_COUNT)}
 
 
+def schur_plan_shapes(window: LbaWindow, item_max: int = 0) -> tuple[dict, int, int]:
+    """Item shapes of the Schur plan of one window, on the CPU: ({(sym, nx, ny, landmarks): items}, matrix-pipe cycles of one pass
+    with whole tiles, the same with the symmetric items' four-block instructions).  item_max 0: what a call with one window uses."""
+    lib = capi.load_library()
+    pr = window.as_struct()
+    hist = np.zeros((2, 9, 9, 65), dtype=np.int64)
+    cyc = np.zeros(2, dtype=np.int64)
+    capi.check(lib.osh_lba_schur_plan_shapes(C.byref(pr), int(item_max), capi.ptr(hist, capi.c_int64_p), capi.ptr(cyc, capi.c_int64_p)),
+               "osh_lba_schur_plan_shapes", lib)
+    return {tuple(int(v) for v in k): int(hist[tuple(k)]) for k in np.argwhere(hist)}, int(cyc[0]), int(cyc[1])
+
+
+def schur_block_list(sym: bool, nx: int, ny: int, use_blocks: bool = True) -> list[tuple]:
+    """Matrix instructions of one k step of an item: ("tile", ti, tj) or ("blocks", [(block row, block column, use)] * 4)
+    (include/orbslam3_hip.h:osh_lba_schur_block_list)."""
+    lib = capi.load_library()
+    out = np.zeros((24, 16), dtype=np.int32)
+    n = np.zeros(1, dtype=np.int32)
+    capi.check(lib.osh_lba_schur_block_list(int(sym), nx, ny, int(use_blocks), capi.ptr(out, capi.c_int32_p), capi.ptr(n, capi.c_int32_p)),
+               "osh_lba_schur_block_list", lib)
+    return [("tile", int(r[1]), int(r[2])) if r[0] == 0 else ("blocks", [tuple(int(v) for v in r[4 + 3 * q:7 + 3 * q]) for q in range(4)])
+            for r in out[:int(n[0])]]
+
+
 def kernel_symbol(short_name: str) -> str:
     """Device kernel name (as rocprofv3 prints it) behind a short name of ``capi.KERNEL_NAMES``."""
     lib = capi.load_library()
