@@ -1128,6 +1128,74 @@ int osh_orb_mlpnp_check_inliers(osh_orb_ctx* ctx, const osh_mlpnp_problem* probl
  * ms[2] kernels, ms[3] download + write-back; ms[4] the hypothesis kernel alone (device events; part of ms[2]). */
 int osh_orb_mlpnp_get_times(osh_orb_ctx* ctx, double ms[5]);
 
+/* ------------------------------------------------- Sim3 RANSAC (the loop-candidate Sim3 of loop closing and map merging) */
+/*
+ * Sim3Solver::iterate (src/Sim3Solver.cc:149-294) behind its minimal-set draw, for n_problems problems (one per place-recognition
+ * candidate) in one call: for each of n_iterations minimal sets of 3 correspondences ComputeSim3 (:311-412) and CheckInliers
+ * (:415-439) against every correspondence in both images; the records (an iteration with count >= the running best, which starts at
+ * best_inliers_in; ties go to the later iteration, :192, :265) with their transforms and inlier masks, in iteration order; first_hit,
+ * the first record with count > min_inliers (:201, :274); and the best after the last iteration.  The running best goes on across a
+ * hit, so a caller that returned early at a hit reads what its next iterate would find from the same answer.  One upload, two
+ * kernels, one download.  The caller draws the sets (data; the entry draws no random numbers).
+ *
+ * Arithmetic: csrc/sim3_ransac.h states it.  Float32 as the reference where the reference's statements pin it; defined there: the
+ * eigenvector of the largest eigenvalue of N by a fixed-sweep FP64 Jacobi method, the rotation matrix straight from that unit
+ * quaternion.  A transform is 13 floats: R row-major, t, s (mR12i, mt12i, ms12i; mT12i = [s R | t]).  A mask is bit words: bit
+ * i % 32 of word i / 32 is correspondence i; a mask has OSH_SIM3R_MASK_WORDS(n) words and its bits beyond n are 0.
+ *
+ * Refused before any device work, the context staying usable: with OSH_ERR_INVALID a negative count, a NULL array whose count is
+ * not 0, a camera type other than the two, n < 3 with n_iterations > 0, a set index outside [0, n), a set that repeats an index;
+ * with OSH_ERR_UNSUPPORTED more than OSH_SIM3R_MAX_POINTS correspondences or OSH_SIM3R_MAX_ITERATIONS iterations in a problem or
+ * more than OSH_SIM3R_MAX_PROBLEMS problems.  Coordinates are not checked: a NaN ends in 0 inliers.  Every entry of every result
+ * array that is passed is written.
+ */
+#define OSH_SIM3R_MAX_POINTS     4096
+#define OSH_SIM3R_MAX_ITERATIONS 1024
+#define OSH_SIM3R_MAX_PROBLEMS   64
+#define OSH_SIM3R_PINHOLE 0   /* camera: fx fy cx cy             */
+#define OSH_SIM3R_KB8     1   /* camera: fx fy cx cy k1 k2 k3 k4 */
+#define OSH_SIM3R_MASK_WORDS(n) (2 * (((n) + 63) / 64))   /* the layout of OSH_MLPNP_MASK_WORDS */
+typedef struct osh_sim3r_problem {
+  int32_t camera_type1;      /* pCamera1: OSH_SIM3R_PINHOLE or OSH_SIM3R_KB8                                            */
+  float camera1[8];
+  int32_t camera_type2;      /* pCamera2                                                                               */
+  float camera2[8];
+  int32_t fix_scale;         /* mbFixScale                                                                             */
+  int32_t n;                 /* N                                                                                      */
+  const float* x3dc1;        /* [n*3] mvX3Dc1                                                                          */
+  const float* x3dc2;        /* [n*3] mvX3Dc2                                                                          */
+  const float* p1im1;        /* [n*2] mvP1im1                                                                          */
+  const float* p2im2;        /* [n*2] mvP2im2                                                                          */
+  const float* max_error1;   /* [n]   (float)mvnMaxError1[i]: the reference truncates 9.210 * sigma2 to size_t         */
+  const float* max_error2;   /* [n]   (float)mvnMaxError2[i]                                                           */
+  int32_t n_iterations;
+  const int32_t* sets;       /* [n_iterations*3] indices into the correspondences                                      */
+  int32_t min_inliers;       /* mRansacMinInliers                                                                      */
+  int32_t best_inliers_in;   /* mnBestInliers on entry                                                                 */
+} osh_sim3r_problem;
+/* Caller-allocated; each may be NULL. */
+typedef struct osh_sim3r_result {
+  int32_t* first_hit;        /* [1]  the first iteration iterate returns a transform in, -1: none                      */
+  int32_t* n_records;        /* [1]  records over all n_iterations                                                     */
+  int32_t* record;           /* [n_iterations]    the iterations that are records, then -1                             */
+  int32_t* record_count;     /* [n_iterations]    mnInliersi per record, then 0                                        */
+  float* record_T;           /* [n_iterations*13] R, t, s per record, then 0                                           */
+  uint32_t* record_mask;     /* [n_iterations*OSH_SIM3R_MASK_WORDS(n)] mvbInliersi per record, then 0                  */
+  int32_t* best_iteration;   /* [1]  the last record, -1 when the best on entry is still the best                      */
+  int32_t* best_count;       /* [1]  mnBestInliers after the last iteration                                            */
+  /* debug: the stages */
+  int32_t* debug_count;      /* [n_iterations]    mnInliersi                                                           */
+  float* debug_T;            /* [n_iterations*13] R, t, s of every iteration                                           */
+} osh_sim3r_result;
+int osh_orb_sim3_ransac(osh_orb_ctx* ctx, int32_t n_problems, const osh_sim3r_problem* problems, const osh_sim3r_result* results);
+/* The scoring stage alone: CheckInliers of n_T given transforms [n_T*13] against the correspondences of `problem` (its sets,
+ * iterations and RANSAC fields are not read; n_T <= OSH_SIM3R_MAX_ITERATIONS): count [n_T], mask [n_T*OSH_SIM3R_MASK_WORDS(n)]. */
+int osh_orb_sim3_ransac_check_inliers(osh_orb_ctx* ctx, const osh_sim3r_problem* problem, int32_t n_T, const float* T12s, int32_t* count,
+                                      uint32_t* mask);
+/* Host-clock phases (ms) of the last osh_orb_sim3_ransac under osh_orb_set_profiling: ms[0] validation + staging, ms[1] upload,
+ * ms[2] kernels, ms[3] download + write-back. */
+int osh_orb_sim3_ransac_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 /* ------------------------------------------------- map point refresh (distinctive descriptor, normal and depth) */
 /*
  * MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) and MapPoint::UpdateNormalAndDepth (:426-494) for the points

@@ -541,6 +541,70 @@ int osh_host_mlpnp_solver_replay(void* solver, const int32_t* head, const double
                                  const uint32_t* best_mask, int32_t n_matches, uint8_t* no_more, int32_t* n_inliers, uint8_t* inliers,
                                  float* Tout);
 
+/* ---- Sim3Solver, the Sim3 RANSAC of loop closing (csrc/sim3_ransac.h, csrc/hosttest/sim3solver.cc) ---- */
+struct osh_sim3r_problem;
+struct osh_sim3r_result;
+/* csrc/sim3_ransac.h (the statements of sim3_ransac_device.hip) compiled for the host, on one thread: arguments as
+ * osh_orb_sim3_ransac without a context, without its validation (the problems must be valid) and without its limits.  *ms (may be
+ * NULL) = wall time of the call.  -1: bad arguments. */
+int osh_host_sim3r_cpu(int32_t n_problems, const struct osh_sim3r_problem* problems, const struct osh_sim3r_result* results, double* ms);
+/* CheckInliers of csrc/sim3_ransac.h: arguments as osh_orb_sim3_ransac_check_inliers without a context. */
+int osh_host_sim3r_check_inliers(const struct osh_sim3r_problem* problem, int32_t n_T, const float* T12s, int32_t* count, uint32_t* mask);
+/* ComputeSim3 of one minimal set: P1, P2 [9] = the three members in camera 1 and camera 2 (point after point), T13 [13] = R, t, s. */
+int osh_host_sim3r_compute_sim3(const float* P1, const float* P2, int32_t fix_scale, float* T13);
+/* The record scan from per-iteration counts: record [n_iterations] gets the record iterations; out [4] = first_hit, n_records,
+ * best_iteration, best_count.  -1: bad arguments. */
+int osh_host_sim3r_scan(int32_t n_iterations, const int32_t* count, int32_t min_inliers, int32_t best_inliers_in, int32_t* record, int32_t* out);
+/* mRansacMaxIts of SetRansacParameters (src/Sim3Solver.cc:123-147) for n correspondences. */
+int osh_host_sim3r_max_iterations(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations);
+/* A Sim3Solver (include/Sim3Solver.h, csrc/host/Sim3Solver.cc) of the stand-in classes.  Keyframe 0 is pKF1, 1 is pKF2, 2 (n_kf = 3)
+ * one more keyframe a point may be matched in.  Map points by world position, isBad() and their keypoint index in each keyframe
+ * (GetIndexInKeyFrame, -1: not observed).  pKF1's GetMapPointMatches() has n1 slots (kf1_mp: a point or -1); vpMatched12 has n1
+ * entries (matched12: a point or -1); matched_kf [n1]: vpKeyFrameMatchedMP as keyframe indices, or NULL: passed empty. */
+typedef struct osh_host_sim3_scene {
+  int32_t n_kf;
+  int32_t camera_type[3];         /* 0 Pinhole (4 parameters), 1 KannalaBrandt8 (8)                                  */
+  float camera[3][8];
+  float Rcw[3][9], tcw[3][3];     /* GetRotation() (row-major, the entries as given), GetTranslation()                */
+  int32_t n_keys[3];
+  const float* xy[3];             /* [n_keys*2] mvKeysUn                                                             */
+  const int32_t* octave[3];       /* [n_keys]                                                                        */
+  int32_t n_levels;
+  const float* level_sigma2;      /* [n_levels] mvLevelSigma2 of every keyframe                                      */
+  int32_t n_points;
+  const float* world;             /* [n_points*3]                                                                    */
+  const uint8_t* bad;             /* [n_points]                                                                      */
+  const int32_t* index_in_kf;     /* [n_points*3]                                                                    */
+  int32_t n1;
+  const int32_t* kf1_mp;          /* [n1]                                                                            */
+  const int32_t* matched12;       /* [n1]                                                                            */
+  const int32_t* matched_kf;      /* [n1] or NULL                                                                    */
+  int32_t fix_scale;
+} osh_host_sim3_scene;
+void* osh_host_sim3_solver_create(const osh_host_sim3_scene* scene);
+void osh_host_sim3_solver_destroy(void* solver);
+int osh_host_sim3_solver_set_ransac(void* solver, double probability, int32_t min_inliers, int32_t max_iterations);
+/* out [8] = N, mN1, mRansacMinInliers, mRansacMaxIts, mnIterations, mnBestInliers, 1 if an answer is kept, 1 if the device gave it */
+int osh_host_sim3_solver_state(void* solver, int32_t* out);
+/* The constructor's pack, N entries each: mvX3Dc1/2 [N*3], mvP1im1 / mvP2im2 [N*2], (float)mvnMaxError1/2 [N], mvnIndices1 [N]. */
+int osh_host_sim3_solver_pack(void* solver, float* x3dc1, float* x3dc2, float* p1im1, float* p2im2, float* max_error1, float* max_error2,
+                              int32_t* indices1);
+/* GetEstimatedTransformation [16], Rotation [9], Translation [3], Scale, mvbBestInliers [N]. */
+int osh_host_sim3_solver_best(void* solver, float* T12, float* R, float* t, float* scale, uint8_t* flags);
+/* Every solver once.  mode 0: iterate(n_iterations, bNoMore, vbInliers, nInliers); 1: the overload with bConverge; 2: all through
+ * Sim3Solver::IterateBatch; 3: find.  Per solver: no_more, n_inliers, converged, inliers [n1] (vbInliers cut to n1), Tout [16]
+ * row-major.  -1: bad arguments. */
+int osh_host_sim3_solver_iterate(int32_t n_solvers, void* const* solvers, int32_t n_iterations, int32_t mode, int32_t n1, uint8_t* no_more,
+                                 int32_t* n_inliers, uint8_t* converged, uint8_t* inliers, float* Tout);
+/* The two halves of iterate around the device call.  prepare: the sets the call would run, their number returned (0: no call is
+ * due) and the first `capacity` of them in sets [capacity*3].  keep: a given answer for the prepared round (the records only).
+ * replay: nIterations iterations from the kept answer, outputs as iterate's for one solver. */
+int osh_host_sim3_solver_prepare(void* solver, int32_t capacity, int32_t* sets);
+int osh_host_sim3_solver_keep(void* solver, int32_t n_records, const int32_t* record, const int32_t* record_count, const float* record_T,
+                              const uint32_t* record_mask);
+int osh_host_sim3_solver_replay(void* solver, int32_t n_iterations, int32_t five, int32_t n1, uint8_t* no_more, int32_t* n_inliers,
+                                uint8_t* converged, uint8_t* inliers, float* Tout);
+
 /* ---- ORBextractor::ComputeKeyPointsOctTree (include/ORBextractor.h, csrc/host/ORBextractor.cc, csrc/hosttest/orbextractor.cc) ---- */
 struct osh_fast_frame;
 struct osh_fast_result;

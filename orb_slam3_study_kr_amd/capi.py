@@ -426,6 +426,42 @@ def mlpnp_mask_words(n: int) -> int:
     return 2 * ((n + 63) // 64)
 
 
+class Sim3rProblem(C.Structure):
+    """``osh_sim3r_problem`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("camera_type1", C.c_int32), ("camera1", C.c_float * 8), ("camera_type2", C.c_int32), ("camera2", C.c_float * 8),
+                ("fix_scale", C.c_int32), ("n", C.c_int32), ("x3dc1", c_float_p), ("x3dc2", c_float_p), ("p1im1", c_float_p),
+                ("p2im2", c_float_p), ("max_error1", c_float_p), ("max_error2", c_float_p), ("n_iterations", C.c_int32),
+                ("sets", c_int32_p), ("min_inliers", C.c_int32), ("best_inliers_in", C.c_int32)]
+
+
+class Sim3rResult(C.Structure):
+    """``osh_sim3r_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("first_hit", c_int32_p), ("n_records", c_int32_p), ("record", c_int32_p), ("record_count", c_int32_p),
+                ("record_T", c_float_p), ("record_mask", c_uint32_p), ("best_iteration", c_int32_p), ("best_count", c_int32_p),
+                ("debug_count", c_int32_p), ("debug_T", c_float_p)]
+
+
+class HostSim3Scene(C.Structure):
+    """``osh_host_sim3_scene`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("n_kf", C.c_int32), ("camera_type", C.c_int32 * 3), ("camera", (C.c_float * 8) * 3), ("Rcw", (C.c_float * 9) * 3),
+                ("tcw", (C.c_float * 3) * 3), ("n_keys", C.c_int32 * 3), ("xy", c_float_p * 3), ("octave", c_int32_p * 3),
+                ("n_levels", C.c_int32), ("level_sigma2", c_float_p), ("n_points", C.c_int32), ("world", c_float_p), ("bad", c_uint8_p),
+                ("index_in_kf", c_int32_p), ("n1", C.c_int32), ("kf1_mp", c_int32_p), ("matched12", c_int32_p), ("matched_kf", c_int32_p),
+                ("fix_scale", C.c_int32)]
+
+
+OSH_SIM3R_MAX_POINTS, OSH_SIM3R_MAX_ITERATIONS, OSH_SIM3R_MAX_PROBLEMS = 4096, 1024, 64
+OSH_SIM3R_PINHOLE, OSH_SIM3R_KB8 = 0, 1
+
+
+def sim3r_mask_words(n: int) -> int:
+    """OSH_SIM3R_MASK_WORDS(n)."""
+    return 2 * ((n + 63) // 64)
+
+
 class MapPointBatch(C.Structure):
     """``osh_mappoint_batch`` (include/orbslam3_hip.h)."""
 
@@ -627,6 +663,9 @@ _SIGNATURES = {
     "osh_orb_mlpnp_solve": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MlpnpProblem), C.POINTER(MlpnpResult)]),
     "osh_orb_mlpnp_check_inliers": (C.c_int, [C.c_void_p, C.POINTER(MlpnpProblem), C.c_int32, c_double_p, c_int32_p, c_uint32_p]),
     "osh_orb_mlpnp_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_sim3_ransac": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Sim3rProblem), C.POINTER(Sim3rResult)]),
+    "osh_orb_sim3_ransac_check_inliers": (C.c_int, [C.c_void_p, C.POINTER(Sim3rProblem), C.c_int32, c_float_p, c_int32_p, c_uint32_p]),
+    "osh_orb_sim3_ransac_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_refresh_map_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MapPointBatch), C.POINTER(MapPointResult)]),
     "osh_orb_refresh_map_points_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_fast_detect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult)]),
@@ -790,6 +829,22 @@ _HOST_SIGNATURES = {
     "osh_host_mlpnp_solver_replay": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, c_uint32_p, c_double_p, c_uint32_p, C.c_int32, c_uint8_p, c_int32_p,
                                                c_uint8_p, c_float_p]),
     "osh_host_mlpnp_replay": (C.c_int, [C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    "osh_host_sim3r_cpu": (C.c_int, [C.c_int32, C.POINTER(Sim3rProblem), C.POINTER(Sim3rResult), c_double_p]),
+    "osh_host_sim3r_check_inliers": (C.c_int, [C.POINTER(Sim3rProblem), C.c_int32, c_float_p, c_int32_p, c_uint32_p]),
+    "osh_host_sim3r_compute_sim3": (C.c_int, [c_float_p, c_float_p, C.c_int32, c_float_p]),
+    "osh_host_sim3r_scan": (C.c_int, [C.c_int32, c_int32_p, C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
+    "osh_host_sim3r_max_iterations": (C.c_int, [C.c_int32, C.c_double, C.c_int32, C.c_int32]),
+    "osh_host_sim3_solver_create": (C.c_void_p, [C.POINTER(HostSim3Scene)]),
+    "osh_host_sim3_solver_destroy": (None, [C.c_void_p]),
+    "osh_host_sim3_solver_set_ransac": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int32]),
+    "osh_host_sim3_solver_state": (C.c_int, [C.c_void_p, c_int32_p]),
+    "osh_host_sim3_solver_pack": (C.c_int, [C.c_void_p] + [c_float_p] * 6 + [c_int32_p]),
+    "osh_host_sim3_solver_best": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_uint8_p]),
+    "osh_host_sim3_solver_iterate": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, c_uint8_p, c_int32_p, c_uint8_p,
+                                               c_uint8_p, c_float_p]),
+    "osh_host_sim3_solver_prepare": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p]),
+    "osh_host_sim3_solver_keep": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_float_p, c_uint32_p]),
+    "osh_host_sim3_solver_replay": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_uint8_p, c_int32_p, c_uint8_p, c_uint8_p, c_float_p]),
     "osh_host_two_view_cpu": (C.c_int, [C.c_int32, C.POINTER(TwoViewProblem), C.POINTER(TwoViewResult), c_double_p]),
     "osh_host_two_view_normalize": (C.c_int, [C.c_int32, c_float_p, c_float_p, c_float_p]),
     "osh_host_two_view_decide": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_float_p, c_int32_p]),

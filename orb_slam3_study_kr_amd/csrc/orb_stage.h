@@ -12,6 +12,7 @@
 // osh_orb_refresh_map_points (mappoint_device.hip) has batches of map points: it uses scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_two_view_reconstruct (two_view_device.hip) has problems of matches and minimal sets: scatter, PhaseClock, orb_state, copy_times.
 // osh_orb_mlpnp_solve (mlpnp_device.hip) has problems of correspondences and minimal sets: scatter, PhaseClock, orb_state.
+// osh_orb_sim3_ransac (sim3_ransac_device.hip) has problems of correspondences and minimal sets: scatter, PhaseClock, orb_state, copy_times.
 #pragma once
 #include "common.h"
 #include <chrono>

@@ -1172,6 +1172,185 @@ def mlpnp_iterate(solvers, n_iterations: int, batch: bool = True) -> list:
                  has_inliers=bool(inl[k, m]), Tout=T[k].reshape(4, 4).copy()) for k, s in enumerate(solvers)]
 
 
+class Sim3Scene:
+    """What a Sim3Solver's constructor reads, as flat arrays (osh_host_sim3_scene), built from a synth_sim3_ransac.Problem:
+    correspondence i is slot slot[i] of pKF1 (n1 slots in all), its map point of map 1 is point i and sits at keypoint key1[i] of
+    pKF1, its map point of map 2 is point n + i and sits at keypoint key2[i] of pKF2.  The keyword sets name correspondences that
+    are spoilt: null_match (vpMatched12 entry NULL), null_kf1 (pKF1's slot empty), bad1 / bad2 (a bad point), unindexed1 /
+    unindexed2 (the point does not observe its keyframe), other_kf (the second point is observed in a third keyframe only).
+    matched_kf: None passes vpKeyFrameMatchedMP empty, True passes one entry per slot (pKF2, or the third keyframe for other_kf)."""
+
+    def __init__(self, pb, extra: int = 3, seed: int = 0, null_match=(), null_kf1=(), bad1=(), bad2=(), unindexed1=(), unindexed2=(), other_kf=(),
+                 matched_kf=None):
+        from . import synth_sim3_ransac as ss
+        rng = np.random.RandomState(seed)
+        n = pb.n
+        self.pb, self.n, self.n1 = pb, n, n + extra
+        self.slot = np.sort(rng.permutation(self.n1)[:n]).astype(np.int32)
+        self.key1, self.key2 = rng.permutation(n).astype(np.int32), rng.permutation(n).astype(np.int32)
+        self.level_sigma2 = ss.level_sigma2()
+        self.camera_type = [int(pb.camera_type1), int(pb.camera_type2), int(pb.camera_type2)]
+        self.camera = [np.asarray(pb.camera1, np.float32), np.asarray(pb.camera2, np.float32), np.asarray(pb.camera2, np.float32)]
+        self.Rcw = [np.asarray(pb.Rcw1, np.float32), np.asarray(pb.Rcw2, np.float32), np.eye(3, dtype=np.float32)]
+        self.tcw = [np.asarray(pb.tcw1, np.float32), np.asarray(pb.tcw2, np.float32), np.zeros(3, np.float32)]
+        self.octave = [np.zeros(n, np.int32), np.zeros(n, np.int32), np.full(n, 7, np.int32)]
+        self.octave[0][self.key1], self.octave[1][self.key2] = pb.octave1, pb.octave2
+        self.world = np.concatenate([pb.world1, pb.world2]).astype(np.float32)
+        self.bad = np.zeros(2 * n, np.uint8)
+        self.bad[list(bad1)] = 1
+        self.bad[[n + i for i in bad2]] = 1
+        self.index_in_kf = np.full((2 * n, 3), -1, np.int32)
+        self.index_in_kf[:n, 0], self.index_in_kf[n:, 1] = self.key1, self.key2
+        self.index_in_kf[list(unindexed1), 0] = -1
+        for i in list(unindexed2) + list(other_kf):
+            self.index_in_kf[n + i, 1] = -1
+        for i in other_kf:
+            self.index_in_kf[n + i, 2] = self.key2[i]
+        self.kf1_mp = np.full(self.n1, -1, np.int32)
+        self.kf1_mp[self.slot] = np.arange(n)
+        self.kf1_mp[self.slot[list(null_kf1)]] = -1
+        self.matched12 = np.full(self.n1, -1, np.int32)
+        self.matched12[self.slot] = n + np.arange(n)
+        self.matched12[self.slot[list(null_match)]] = -1
+        self.matched_kf = None
+        if matched_kf:
+            self.matched_kf = np.ones(self.n1, np.int32)
+            self.matched_kf[self.slot[list(other_kf)]] = 2
+        self.fix_scale = int(pb.fix_scale)
+
+    def c_struct(self):
+        sc, keep = capi.HostSim3Scene(), []
+        sc.n_kf = 3
+        for k in range(3):
+            sc.camera_type[k] = self.camera_type[k]
+            sc.camera[k][:] = [float(v) for v in self.camera[k]]
+            sc.Rcw[k][:] = [float(v) for v in self.Rcw[k].reshape(9)]
+            sc.tcw[k][:] = [float(v) for v in self.tcw[k]]
+            sc.n_keys[k] = self.n
+            xy = np.zeros((self.n, 2), np.float32)
+            keep += [xy, np.ascontiguousarray(self.octave[k], np.int32)]
+            sc.xy[k], sc.octave[k] = capi.ptr(keep[-2], capi.c_float_p), capi.ptr(keep[-1], capi.c_int32_p)
+        keep += [np.ascontiguousarray(a) for a in (self.level_sigma2, self.world, self.bad, self.index_in_kf, self.kf1_mp, self.matched12)]
+        sc.n_levels, sc.level_sigma2 = len(self.level_sigma2), capi.ptr(keep[-6], capi.c_float_p)
+        sc.n_points, sc.world, sc.bad = 2 * self.n, capi.ptr(keep[-5], capi.c_float_p), capi.ptr(keep[-4], capi.c_uint8_p)
+        sc.index_in_kf = capi.ptr(keep[-3], capi.c_int32_p)
+        sc.n1, sc.kf1_mp, sc.matched12 = self.n1, capi.ptr(keep[-2], capi.c_int32_p), capi.ptr(keep[-1], capi.c_int32_p)
+        if self.matched_kf is not None:
+            keep.append(np.ascontiguousarray(self.matched_kf, np.int32))
+            sc.matched_kf = capi.ptr(keep[-1], capi.c_int32_p)
+        sc.fix_scale = self.fix_scale
+        return sc, keep
+
+
+class Sim3Solver:
+    """A Sim3Solver (include/Sim3Solver.h) of the stand-in classes built from a Sim3Scene."""
+
+    STATE = ("N", "n1", "min_inliers", "max_iterations", "iterations", "best_inliers", "has_answer", "on_device")
+
+    def __init__(self, scene: Sim3Scene, ransac=None):
+        self.lib = capi.load_host_library()
+        self.scene, self.n1 = scene, scene.n1
+        sc, _keep = scene.c_struct()
+        self.handle = self.lib.osh_host_sim3_solver_create(C.byref(sc))
+        if not self.handle:
+            raise RuntimeError("osh_host_sim3_solver_create refused the arguments")
+        if ransac is not None:
+            self.set_ransac(*ransac)
+
+    def set_ransac(self, probability=0.99, min_inliers=6, max_iterations=300):
+        if self.lib.osh_host_sim3_solver_set_ransac(self.handle, probability, min_inliers, max_iterations) != 0:
+            raise RuntimeError("osh_host_sim3_solver_set_ransac")
+
+    def state(self) -> dict:
+        out = np.zeros(8, np.int32)
+        self.lib.osh_host_sim3_solver_state(self.handle, capi.ptr(out, capi.c_int32_p))
+        return dict(zip(self.STATE, (int(v) for v in out)))
+
+    def pack(self) -> dict:
+        n = self.state()["N"]
+        f = lambda *shape: np.zeros(shape, np.float32)
+        o = dict(x3dc1=f(n, 3), x3dc2=f(n, 3), p1im1=f(n, 2), p2im2=f(n, 2), max_error1=f(n), max_error2=f(n), indices1=np.zeros(n, np.int32))
+        rc = self.lib.osh_host_sim3_solver_pack(self.handle, *[capi.ptr(o[k], capi.c_float_p) for k in list(o)[:6]], capi.ptr(o["indices1"], capi.c_int32_p))
+        if rc != 0:
+            raise RuntimeError(f"osh_host_sim3_solver_pack -> {rc}")
+        return o
+
+    def best(self) -> dict:
+        n = self.state()["N"]
+        o = dict(T12=np.zeros((4, 4), np.float32), R=np.zeros((3, 3), np.float32), t=np.zeros(3, np.float32), s=np.zeros(1, np.float32))
+        flags = np.zeros(max(n, 1), np.uint8)
+        rc = self.lib.osh_host_sim3_solver_best(self.handle, *[capi.ptr(v, capi.c_float_p) for v in o.values()], capi.ptr(flags, capi.c_uint8_p))
+        if rc != 0:
+            raise RuntimeError(f"osh_host_sim3_solver_best -> {rc}")
+        o["flags"] = flags[:n].astype(bool)
+        return o
+
+    def iterate(self, n_iterations: int, mode: int = 1) -> dict:
+        """mode 0: the four-argument iterate, 1: the one with bConverge, 3: find."""
+        return sim3_iterate([self], n_iterations, mode)[0]
+
+    def prepare(self, capacity: int = 1024):
+        """The sets the device call of the next iterate would run: [count, 3] (an empty array when no call is due)."""
+        sets = np.zeros((capacity, 3), np.int32)
+        rc = self.lib.osh_host_sim3_solver_prepare(self.handle, capacity, capi.ptr(sets, capi.c_int32_p))
+        if rc < 0:
+            raise RuntimeError(f"osh_host_sim3_solver_prepare -> {rc}")
+        return sets[:min(rc, capacity)]
+
+    def keep(self, record, record_count, record_T, record_flags):
+        """Hands the prepared round a given answer: the record iterations, their counts, transforms [k, 13] and flags [k, N]."""
+        n = self.state()["N"]
+        words = capi.sim3r_mask_words(n)
+        record, record_count = np.ascontiguousarray(record, np.int32), np.ascontiguousarray(record_count, np.int32)
+        T = np.ascontiguousarray(record_T, np.float32).reshape(-1, 13)
+        bits = np.zeros((len(record), words * 32), np.uint8)
+        if len(record):
+            bits[:, :n] = np.asarray(record_flags, bool).reshape(len(record), n)
+        mask = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view(np.uint32)
+        rc = self.lib.osh_host_sim3_solver_keep(self.handle, len(record), capi.ptr(record, capi.c_int32_p), capi.ptr(record_count, capi.c_int32_p),
+                                                capi.ptr(T, capi.c_float_p), capi.ptr(mask, capi.c_uint32_p))
+        if rc != 0:
+            raise RuntimeError(f"osh_host_sim3_solver_keep -> {rc}")
+
+    def replay(self, n_iterations: int, five: bool = True) -> dict:
+        no_more, conv, n_in = np.zeros(1, np.uint8), np.zeros(1, np.uint8), np.zeros(1, np.int32)
+        inl, T = np.zeros(max(self.n1, 1), np.uint8), np.zeros(16, np.float32)
+        rc = self.lib.osh_host_sim3_solver_replay(self.handle, int(n_iterations), int(five), self.n1, capi.ptr(no_more, capi.c_uint8_p),
+                                                  capi.ptr(n_in, capi.c_int32_p), capi.ptr(conv, capi.c_uint8_p), capi.ptr(inl, capi.c_uint8_p),
+                                                  capi.ptr(T, capi.c_float_p))
+        if rc != 0:
+            raise RuntimeError(f"osh_host_sim3_solver_replay -> {rc}")
+        return dict(no_more=bool(no_more[0]), converged=bool(conv[0]), n_inliers=int(n_in[0]), inliers=inl[:self.n1].astype(bool), T12=T.reshape(4, 4))
+
+    def close(self):
+        if self.handle:
+            self.lib.osh_host_sim3_solver_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def sim3_iterate(solvers, n_iterations: int, mode: int = 2) -> list:
+    """Every Sim3Solver once: mode 0 / 1 the two iterate overloads one by one, 2 Sim3Solver::IterateBatch (one device call), 3 find.
+    Per solver a dict with no_more, converged, n_inliers, inliers [n1] and T12 [4, 4]."""
+    lib = capi.load_host_library()
+    S = len(solvers)
+    m = max([s.n1 for s in solvers], default=0)
+    handles = (C.c_void_p * max(S, 1))(*[s.handle for s in solvers])
+    no_more, conv, n_in = np.zeros(S, np.uint8), np.zeros(S, np.uint8), np.zeros(S, np.int32)
+    inl, T = np.zeros((S, max(m, 1)), np.uint8), np.zeros((S, 16), np.float32)
+    rc = lib.osh_host_sim3_solver_iterate(S, handles, int(n_iterations), int(mode), m, capi.ptr(no_more, capi.c_uint8_p), capi.ptr(n_in, capi.c_int32_p),
+                                          capi.ptr(conv, capi.c_uint8_p), capi.ptr(inl, capi.c_uint8_p), capi.ptr(T, capi.c_float_p))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_sim3_solver_iterate -> {rc}")
+    return [dict(no_more=bool(no_more[k]), converged=bool(conv[k]), n_inliers=int(n_in[k]), inliers=inl[k, :s.n1].astype(bool),
+                 T12=T[k].reshape(4, 4).copy()) for k, s in enumerate(solvers)]
+
+
 def create_new_map_points(scene, coarse: bool = True, new_keyframe_waiting: bool = False, capacity: int = 4096) -> dict:
     """LocalMapping::CreateNewMapPoints on the stand-in classes built from a synth_newpoints.Scene (osh_host_create_new_map_points).
     Keyframe 0 is the current one, keyframe 1 + k neighbour k; the first two neighbours are covisibles, the third is reached

@@ -234,6 +234,33 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_mlpnp_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_mlpnp_get_times", self.lib)
         return ms
 
+    def sim3_ransac(self, problems, debug: bool = False, fill=None) -> list:
+        """Sim3Solver::iterate behind its minimal-set draw (src/Sim3Solver.cc:149-294) for a batch of synth_sim3_ransac.Problem in
+        one osh_orb_sim3_ransac call: per problem a dict with first_hit, n_records, record, record_count [iterations], record_T
+        [iterations, 13], record_mask [iterations, words], best_iteration, best_count, debug_count [iterations], and with `debug`
+        also debug_T [iterations, 13]."""
+        cp, cr, _keep, outs = sim3_ransac_args(problems, debug, fill)
+        capi.check(self.lib.osh_orb_sim3_ransac(self.ctx, len(problems), cp, cr), "osh_orb_sim3_ransac", self.lib)
+        return outs
+
+    def sim3_ransac_check_inliers(self, problem, T12s):
+        """CheckInliers (src/Sim3Solver.cc:415-439) of the transforms [k, 13] (R, t, s) against a synth_sim3_ransac.Problem's
+        correspondences (osh_orb_sim3_ransac_check_inliers): count [k], mask [k, words]."""
+        cp, _cr, _keep, _outs = sim3_ransac_args([problem])
+        T = np.ascontiguousarray(T12s, np.float32).reshape(-1, 13)
+        count = np.zeros(T.shape[0], np.int32)
+        mask = np.zeros((T.shape[0], capi.sim3r_mask_words(problem.n)), np.uint32)
+        capi.check(self.lib.osh_orb_sim3_ransac_check_inliers(self.ctx, cp, T.shape[0], capi.ptr(T, capi.c_float_p),
+                                                              capi.ptr(count, capi.c_int32_p), capi.ptr(mask, capi.c_uint32_p)),
+                   "osh_orb_sim3_ransac_check_inliers", self.lib)
+        return count, mask
+
+    def sim3_ransac_times(self):
+        """Phases (ms) of the last sim3_ransac under set_profiling(True): staging, upload, kernels, download."""
+        ms = np.zeros(4, dtype=np.float64)
+        capi.check(self.lib.osh_orb_sim3_ransac_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_sim3_ransac_get_times", self.lib)
+        return ms
+
     def refresh_map_points(self, batches, want=None) -> list:
         """MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth (src/MapPoint.cc:329-403,426-494) for a list of
         synth_mappoints.Batch in one osh_orb_refresh_map_points call: per batch a dict with best_entry, best_median [n],
@@ -1154,6 +1181,94 @@ def mlpnp_stage(name: str, *args, host_lib=None):
         raise ValueError(name)
     if rc != 0:
         raise RuntimeError(f"osh_host_mlpnp_{name} -> {rc}")
+    return out
+
+
+_SIM3R_ARRAYS = (("x3dc1", np.float32), ("x3dc2", np.float32), ("p1im1", np.float32), ("p2im2", np.float32), ("max_error1", np.float32),
+                 ("max_error2", np.float32), ("sets", np.int32))
+
+
+def sim3_ransac_args(problems, debug: bool = False, fill=None):
+    """The osh_sim3r_problem / osh_sim3r_result arrays of OrbMatcher.sim3_ransac for repeated calls: (problems, results, the arrays
+    that keep their pointers alive, the per-problem dicts of output arrays).  fill: a byte the output arrays are pre-filled with
+    (None: zeros)."""
+    n_p = len(problems)
+    cp = (capi.Sim3rProblem * max(n_p, 1))()
+    cr = (capi.Sim3rResult * max(n_p, 1))()
+    keep, outs = [], []
+    for k, pb in enumerate(problems):
+        c = cp[k]
+        a = {name: np.ascontiguousarray(getattr(pb, name), dt) for name, dt in _SIM3R_ARRAYS}
+        n, it = a["x3dc1"].reshape(-1, 3).shape[0], a["sets"].reshape(-1, 3).shape[0]
+        c.camera_type1, c.camera_type2 = int(pb.camera_type1), int(pb.camera_type2)
+        c.camera1[:] = [float(x) for x in np.asarray(pb.camera1, np.float32).reshape(8)]
+        c.camera2[:] = [float(x) for x in np.asarray(pb.camera2, np.float32).reshape(8)]
+        c.fix_scale, c.n, c.n_iterations = int(pb.fix_scale), n, it
+        c.min_inliers, c.best_inliers_in = int(pb.min_inliers), int(pb.best_inliers_in)
+        for name, dt in _SIM3R_ARRAYS:
+            setattr(c, name, capi.ptr(a[name], _POINTER[np.dtype(dt)]))
+        i32, f32, words = np.int32, np.float32, capi.sim3r_mask_words(n)
+        o = dict(first_hit=np.zeros(1, i32), n_records=np.zeros(1, i32), record=np.zeros(it, i32), record_count=np.zeros(it, i32),
+                 record_T=np.zeros((it, 13), f32), record_mask=np.zeros((it, words), np.uint32), best_iteration=np.zeros(1, i32),
+                 best_count=np.zeros(1, i32), debug_count=np.zeros(it, i32))
+        if debug:
+            o.update(debug_T=np.zeros((it, 13), f32))
+        if fill is not None:
+            for v in o.values():
+                v.view(np.uint8)[...] = fill
+        _wire_outputs(cr[k], o)
+        keep.append(a)
+        outs.append(o)
+    return cp, cr, keep, outs
+
+
+def sim3_ransac_cpu(problems, debug: bool = False, host_lib=None):
+    """csrc/sim3_ransac.h on the host in one thread (osh_host_sim3r_cpu of the test library): the per-problem output dicts of
+    sim3_ransac and the wall time in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    cp, cr, _keep, outs = sim3_ransac_args(problems, debug)
+    ms = C.c_double(0)
+    rc = host_lib.osh_host_sim3r_cpu(len(problems), cp, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_sim3r_cpu -> {rc}")
+    return outs, float(ms.value)
+
+
+def sim3_ransac_check_inliers_cpu(problem, T12s, host_lib=None):
+    """CheckInliers of csrc/sim3_ransac.h on the host (osh_host_sim3r_check_inliers): count [k], mask [k, words]."""
+    host_lib = host_lib or capi.load_host_library()
+    cp, _cr, _keep, _outs = sim3_ransac_args([problem])
+    T = np.ascontiguousarray(T12s, np.float32).reshape(-1, 13)
+    count = np.zeros(T.shape[0], np.int32)
+    mask = np.zeros((T.shape[0], capi.sim3r_mask_words(problem.n)), np.uint32)
+    rc = host_lib.osh_host_sim3r_check_inliers(cp, T.shape[0], capi.ptr(T, capi.c_float_p), capi.ptr(count, capi.c_int32_p),
+                                               capi.ptr(mask, capi.c_uint32_p))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_sim3r_check_inliers -> {rc}")
+    return count, mask
+
+
+def sim3_ransac_stage(name: str, *args, host_lib=None):
+    """The stages of csrc/sim3_ransac.h on the host (osh_host_sim3r_* of the test library).  "compute_sim3": P1, P2 [3, 3] (the set's
+    members in camera 1 and camera 2), fix_scale -> T [13].  "scan": count, min_inliers, best_in -> record, out [4] (first_hit,
+    n_records, best_iteration, best_count).  "max_iterations": N, probability, minInliers, maxIterations -> mRansacMaxIts."""
+    lib = host_lib or capi.load_host_library()
+    if name == "compute_sim3":
+        P1, P2, T = np.ascontiguousarray(args[0], np.float32), np.ascontiguousarray(args[1], np.float32), np.zeros(13, np.float32)
+        rc = lib.osh_host_sim3r_compute_sim3(capi.ptr(P1, capi.c_float_p), capi.ptr(P2, capi.c_float_p), int(args[2]), capi.ptr(T, capi.c_float_p))
+        out = T
+    elif name == "scan":
+        count = np.ascontiguousarray(args[0], np.int32)
+        record, res = np.full(max(count.shape[0], 1), -1, np.int32), np.zeros(4, np.int32)
+        rc = lib.osh_host_sim3r_scan(count.shape[0], capi.ptr(count, capi.c_int32_p), int(args[1]), int(args[2]), capi.ptr(record, capi.c_int32_p),
+                                     capi.ptr(res, capi.c_int32_p))
+        out = (record[:int(res[1])], res)
+    elif name == "max_iterations":
+        return int(lib.osh_host_sim3r_max_iterations(int(args[0]), float(args[1]), int(args[2]), int(args[3])))
+    else:
+        raise ValueError(name)
+    if rc != 0:
+        raise RuntimeError(f"osh_host_sim3r_{name} -> {rc}")
     return out
 
 
