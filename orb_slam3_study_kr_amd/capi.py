@@ -421,9 +421,12 @@ OSH_MLPNP_MAX_POINTS, OSH_MLPNP_MAX_ITERATIONS, OSH_MLPNP_MAX_PROBLEMS = 2048, 1
 OSH_MLPNP_PINHOLE, OSH_MLPNP_KB8 = 0, 1
 
 
-def mlpnp_mask_words(n: int) -> int:
-    """OSH_MLPNP_MASK_WORDS(n)."""
+def ransac_mask_words(n: int) -> int:
+    """OSH_MLPNP_MASK_WORDS(n) and OSH_SIM3R_MASK_WORDS(n): the words of one inlier mask over n correspondences."""
     return 2 * ((n + 63) // 64)
+
+
+mlpnp_mask_words = sim3r_mask_words = ransac_mask_words   # the names of the two macros, for callers written against them
 
 
 class Sim3rProblem(C.Structure):
@@ -455,11 +458,6 @@ class HostSim3Scene(C.Structure):
 
 OSH_SIM3R_MAX_POINTS, OSH_SIM3R_MAX_ITERATIONS, OSH_SIM3R_MAX_PROBLEMS = 4096, 1024, 64
 OSH_SIM3R_PINHOLE, OSH_SIM3R_KB8 = 0, 1
-
-
-def sim3r_mask_words(n: int) -> int:
-    """OSH_SIM3R_MASK_WORDS(n)."""
-    return 2 * ((n + 63) // 64)
 
 
 class MapPointBatch(C.Structure):

@@ -26,17 +26,9 @@
 
 #include "../mlpnp.h"
 #include "orbslam3_hip.h"
+#include "ransac_host.h"
 
 namespace ORB_SLAM3 {
-
-osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
-
-namespace {
-int RandomInt(int min, int max) {
-  int d = max - min + 1;
-  return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
-}
-}  // namespace
 
 MLPnPsolver::MLPnPsolver(const Frame& F, const std::vector<MapPoint*>& vpMapPointMatches) : mpCamera(F.mpCamera) {
   mvpMapPointMatches = vpMapPointMatches;
@@ -90,21 +82,13 @@ MLPnPsolver::Round MLPnPsolver::Prepare(int nIterations) {
   // while (mnIterations < mRansacMaxIts || nCurrentIterations < nIterations)
   r.iterations = std::max(std::max(mRansacMaxIts - mnIterations, nIterations), 0);
   r.sets.reserve(6 * (size_t)r.iterations);
-  std::vector<size_t> vAvailableIndices;
   for (int it = 0; it < r.iterations; ++it) {
     if (!mvQueuedSets.empty()) {
       for (int j = 0; j < 6; ++j) r.sets.push_back(mvQueuedSets.front()[j]);
       mvQueuedSets.pop_front();
       continue;
     }
-    vAvailableIndices = mvAllIndices;
-    // Get min set of points
-    for (short i = 0; i < 6; ++i) {
-      int randi = RandomInt(0, vAvailableIndices.size() - 1);
-      r.sets.push_back((int32_t)vAvailableIndices[randi]);
-      vAvailableIndices[randi] = vAvailableIndices.back();
-      vAvailableIndices.pop_back();
-    }
+    DrawMinimalSet(mvAllIndices, 6, r.sets);   // Get min set of points
   }
   return r;
 }
@@ -126,18 +110,14 @@ bool MLPnPsolver::Replay(const Round& round, const Outcome& o, bool& bNoMore, st
     T.setIdentity();
     for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) T(i, j) = (float)pose[3 * i + j]; T(i, 3) = (float)pose[9 + i]; }
   };
-  auto to_flags = [this](const std::vector<uint32_t>& mask, std::vector<bool>& flags) {
-    flags.assign(N, false);
-    for (int i = 0; i < N; ++i) flags[i] = (mask[i >> 5] >> (i & 31)) & 1u;
-  };
   if (o.best_iteration >= 0) {   // a record of this call is the running best now (:172-187)
     mnBestInliers = o.best_count;
-    to_flags(o.best_mask, mvbBestInliers);
+    MaskToFlags(o.best_mask.data(), N, mvbBestInliers);
     to_matrix(o.best_pose, mBestTcw);
     mbBestRefineOk = o.best_refine_ok != 0;
     if (o.hit_record >= 0) {
       mnRefinedInliers = o.hit_count;
-      to_flags(o.hit_mask, mvbRefinedInliers);
+      MaskToFlags(o.hit_mask.data(), N, mvbRefinedInliers);
       to_matrix(o.hit_pose, mRefinedTcw);
     }
   }
@@ -186,7 +166,6 @@ void MLPnPsolver::IterateBatch(const std::vector<MLPnPsolver*>& solvers, int nIt
   std::vector<size_t> device;   // the solvers whose round fits the entry
   for (size_t k = 0; k < S; ++k) {
     MLPnPsolver& s = *solvers[k];
-    s.mbLastOnDevice = false;
     if (s.mRansacMinSet != 6) {
       std::fprintf(stderr, "MLPnPsolver::iterate: a minimal set of %d is not supported\n", s.mRansacMinSet);
       invalid[k] = true; rounds[k].skip = true;
@@ -195,7 +174,6 @@ void MLPnPsolver::IterateBatch(const std::vector<MLPnPsolver*>& solvers, int nIt
     rounds[k] = s.Prepare(nIterations);
     if (rounds[k].skip) continue;
     osh_mlpnp_problem& p = problems[k];
-    p = osh_mlpnp_problem{};
     p.camera_type = s.mpCamera->GetType() == GeometricCamera::CAM_FISHEYE ? OSH_MLPNP_KB8 : OSH_MLPNP_PINHOLE;
     for (int i = 0; i < (p.camera_type == OSH_MLPNP_KB8 ? 8 : 4); ++i) p.camera[i] = s.mpCamera->getParameter(i);
     p2d[k].resize(2 * (size_t)s.N);
@@ -208,35 +186,26 @@ void MLPnPsolver::IterateBatch(const std::vector<MLPnPsolver*>& solvers, int nIt
     const size_t words = (size_t)OSH_MLPNP_MASK_WORDS(s.N);
     o.hit_mask.assign(words, 0u); o.best_mask.assign(words, 0u);
     osh_mlpnp_result& r = results[k];
-    r = osh_mlpnp_result{};
     r.first_hit = &o.first_hit; r.hit_record = &o.hit_record; r.hit_pose = o.hit_pose; r.hit_count = &o.hit_count; r.hit_mask = o.hit_mask.data();
     r.best_iteration = &o.best_iteration; r.best_count = &o.best_count; r.best_mask = o.best_mask.data(); r.best_pose = o.best_pose;
     r.best_refine_ok = &o.best_refine_ok;
     if (s.N <= OSH_MLPNP_MAX_POINTS && p.n_iterations <= OSH_MLPNP_MAX_ITERATIONS) device.push_back(k);
   }
-  std::vector<bool> answered(S, false);
   osh_orb_ctx* ctx = device.empty() ? nullptr : HostMatcherContext();
-  for (size_t b = 0; ctx && b < device.size(); b += OSH_MLPNP_MAX_PROBLEMS) {   // one call for up to OSH_MLPNP_MAX_PROBLEMS solvers
-    const size_t n = std::min(device.size() - b, (size_t)OSH_MLPNP_MAX_PROBLEMS);
-    std::vector<osh_mlpnp_problem> ps(n);
-    std::vector<osh_mlpnp_result> rs(n);
-    for (size_t i = 0; i < n; ++i) { ps[i] = problems[device[b + i]]; rs[i] = results[device[b + i]]; }
-    const int rc = osh_orb_mlpnp_solve(ctx, (int32_t)n, ps.data(), rs.data());
-    if (rc == OSH_OK) { for (size_t i = 0; i < n; ++i) { answered[device[b + i]] = true; solvers[device[b + i]]->mbLastOnDevice = true; } }
-    else if (rc == OSH_ERR_INVALID) {
-      std::fprintf(stderr, "MLPnPsolver::iterate: %s\n", osh_last_error());
-      for (size_t i = 0; i < n; ++i) { invalid[device[b + i]] = true; answered[device[b + i]] = true; }
-    } else std::fprintf(stderr, "MLPnPsolver::iterate: %s; running on the host\n", osh_last_error());
-  }
+  const std::vector<int> rc = RunOnDevice(ctx, osh_orb_mlpnp_solve, OSH_MLPNP_MAX_PROBLEMS, problems, results, device, [](int r) {
+    if (r == OSH_ERR_INVALID) std::fprintf(stderr, "MLPnPsolver::iterate: %s\n", osh_last_error());
+    else std::fprintf(stderr, "MLPnPsolver::iterate: %s; running on the host\n", osh_last_error());
+  });
   for (size_t k = 0; k < S; ++k) {
     MLPnPsolver& s = *solvers[k];
     bool noMore = false;
     int n = 0;
-    if (invalid[k]) {   // refused: nothing was run, the solver gives up
+    s.mbLastOnDevice = !rounds[k].skip && rc[k] == OSH_OK;
+    if (invalid[k] || (!rounds[k].skip && rc[k] == OSH_ERR_INVALID)) {   // refused: nothing was run, the solver gives up
       vTout[k].setIdentity(); vbNoMore[k] = true;
       continue;
     }
-    if (!rounds[k].skip && !answered[k]) {
+    if (!rounds[k].skip && rc[k] != OSH_OK) {
       if (s.N > OSH_MLPNP_MAX_POINTS || rounds[k].iterations > OSH_MLPNP_MAX_ITERATIONS)
         std::fprintf(stderr, "MLPnPsolver::iterate: beyond the device limits; running on the host\n");
       osh::ml_solve_host(problems[k], results[k]);

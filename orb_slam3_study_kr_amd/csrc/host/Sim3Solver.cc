@@ -32,17 +32,9 @@
 
 #include "../sim3_ransac.h"
 #include "orbslam3_hip.h"
+#include "ransac_host.h"
 
 namespace ORB_SLAM3 {
-
-osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
-
-namespace {
-int RandomInt(int min, int max) {
-  int d = max - min + 1;
-  return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
-}
-}  // namespace
 
 Sim3Solver::Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const bool bFixScale,
                        std::vector<KeyFrame*> vpKeyFrameMatchedMP)
@@ -133,17 +125,7 @@ Sim3Solver::Round Sim3Solver::Prepare() {
   if (r.iterations == 0) return r;
   r.pending = true;
   r.sets.reserve(3 * (size_t)r.iterations);
-  std::vector<size_t> vAvailableIndices;
-  for (int it = 0; it < r.iterations; ++it) {
-    vAvailableIndices = mvAllIndices;
-    // Get min set of points
-    for (short i = 0; i < 3; ++i) {
-      int randi = RandomInt(0, vAvailableIndices.size() - 1);
-      r.sets.push_back((int32_t)vAvailableIndices[randi]);
-      vAvailableIndices[randi] = vAvailableIndices.back();
-      vAvailableIndices.pop_back();
-    }
-  }
+  for (int it = 0; it < r.iterations; ++it) DrawMinimalSet(mvAllIndices, 3, r.sets);   // Get min set of points
   return r;
 }
 
@@ -180,8 +162,7 @@ Eigen::Matrix4f Sim3Solver::Replay(int nIterations, bool five, bool& bNoMore, st
     const int mnInliersi = mAnswer.record_count[q];
     const uint32_t* mask = &mAnswer.record_mask[(size_t)q * words];
     const float* T = &mAnswer.record_T[13 * (size_t)q];
-    mvbBestInliers.assign(N, false);
-    for (int k = 0; k < N; ++k) mvbBestInliers[k] = (mask[k >> 5] >> (k & 31)) & 1u;
+    MaskToFlags(mask, N, mvbBestInliers);
     mnBestInliers = mnInliersi;
     mBestT12.setIdentity();
     for (int r = 0; r < 3; ++r) {
@@ -212,38 +193,28 @@ void RunPending(const std::vector<Sim3Solver*>& solvers, const std::vector<Sim3S
   std::vector<Sim3Solver::Answer> answers(S);
   std::vector<size_t> device;   // the solvers whose round fits the entry
   for (size_t k = 0; k < S; ++k) {
-    Sim3Solver& s = *solvers[k];
     if (!rounds[k].pending) continue;
-    s.mbLastOnDevice = false;
     osh_sim3r_problem& p = problems[k];
-    p = osh_sim3r_problem{};
-    s.FillProblem(p);
+    solvers[k]->FillProblem(p);
     p.n_iterations = rounds[k].iterations; p.sets = rounds[k].sets.data();
     Sim3Solver::Answer& a = answers[k];
     const size_t ni = (size_t)rounds[k].iterations, words = (size_t)OSH_SIM3R_MASK_WORDS(p.n);
     a.record.assign(ni, -1); a.record_count.assign(ni, 0); a.record_T.assign(ni * 13, 0.f); a.record_mask.assign(ni * words, 0u);
     osh_sim3r_result& r = results[k];
-    r = osh_sim3r_result{};
     r.n_records = &a.n_records; r.record = a.record.data(); r.record_count = a.record_count.data(); r.record_T = a.record_T.data();
     r.record_mask = a.record_mask.data();
     if (p.n <= OSH_SIM3R_MAX_POINTS && p.n_iterations <= OSH_SIM3R_MAX_ITERATIONS) device.push_back(k);
     else std::fprintf(stderr, "Sim3Solver::iterate: beyond the device limits; running on the host\n");
   }
-  std::vector<bool> answered(S, false);
   osh_orb_ctx* ctx = device.empty() ? nullptr : HostMatcherContext();
   if (!device.empty() && !ctx) std::fprintf(stderr, "Sim3Solver::iterate: no device context; running on the host\n");
-  for (size_t b = 0; ctx && b < device.size(); b += OSH_SIM3R_MAX_PROBLEMS) {   // one call for up to OSH_SIM3R_MAX_PROBLEMS solvers
-    const size_t n = std::min(device.size() - b, (size_t)OSH_SIM3R_MAX_PROBLEMS);
-    std::vector<osh_sim3r_problem> ps(n);
-    std::vector<osh_sim3r_result> rs(n);
-    for (size_t i = 0; i < n; ++i) { ps[i] = problems[device[b + i]]; rs[i] = results[device[b + i]]; }
-    const int rc = osh_orb_sim3_ransac(ctx, (int32_t)n, ps.data(), rs.data());
-    if (rc == OSH_OK) { for (size_t i = 0; i < n; ++i) { answered[device[b + i]] = true; solvers[device[b + i]]->mbLastOnDevice = true; } }
-    else std::fprintf(stderr, "Sim3Solver::iterate: %s; running on the host\n", osh_last_error());
-  }
+  const std::vector<int> rc = RunOnDevice(ctx, osh_orb_sim3_ransac, OSH_SIM3R_MAX_PROBLEMS, problems, results, device, [](int) {
+    std::fprintf(stderr, "Sim3Solver::iterate: %s; running on the host\n", osh_last_error());
+  });
   for (size_t k = 0; k < S; ++k) {
     if (!rounds[k].pending) continue;
-    if (!answered[k]) osh::s3r_solve_host(problems[k], results[k]);
+    solvers[k]->mbLastOnDevice = rc[k] == OSH_OK;
+    if (rc[k] != OSH_OK) osh::s3r_solve_host(problems[k], results[k]);
     solvers[k]->Keep(rounds[k], answers[k]);
   }
 }

@@ -5,8 +5,8 @@
 //
 // Kept from the reference:
 //   * DUtils::Random::SeedRandOnce(0) and RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp:38-50): srand(0) once per process, then
-//     int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min, and the swap-with-back removal.  The once-flag lives here; an
-//     integrator whose other code also calls DUtils::Random::SeedRandOnce replaces SeedRandOnce / RandomInt below by DUtils' own.
+//     RandomInt on rand() and the swap-with-back removal (DrawMinimalSet of ransac_host.h).  The once-flag lives here; an integrator whose other code also calls DUtils::Random::SeedRandOnce replaces SeedRandOnce below and
+//     RandomInt there by DUtils' own.
 //   * ReconstructH returns true without assigning vP3D (:725-731): on the H branch vP3D is left as passed.  The C-ABI result carries
 //     the points in both branches (INTEGRATION.md section 5 says how to use them).
 // Deviations, all intended:
@@ -25,19 +25,14 @@
 
 #include "../two_view.h"
 #include "orbslam3_hip.h"
+#include "ransac_host.h"
 
 namespace ORB_SLAM3 {
-
-osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
 
 namespace {
 bool already_seeded = false;
 void SeedRandOnce(int seed) {
   if (!already_seeded) { srand(seed); already_seeded = true; }
-}
-int RandomInt(int min, int max) {
-  int d = max - min + 1;
-  return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
 }
 }  // namespace
 
@@ -62,22 +57,14 @@ bool TwoViewReconstruction::Reconstruct(const std::vector<cv::KeyPoint>& vKeys1,
   if (mMaxIterations > 0 && N < 8) { mvSets.clear(); return false; }
 
   // Generate sets of 8 points for each RANSAC iteration
-  std::vector<size_t> vAllIndices, vAvailableIndices;
+  std::vector<size_t> vAllIndices;
   vAllIndices.reserve(N);
   for (int i = 0; i < N; i++) vAllIndices.push_back(i);
-  mvSets = std::vector<std::vector<size_t> >(mMaxIterations > 0 ? mMaxIterations : 0, std::vector<size_t>(8, 0));
+  std::vector<int32_t> sets;
   SeedRandOnce(0);
-  for (int it = 0; it < mMaxIterations; it++) {
-    vAvailableIndices = vAllIndices;
-    // Select a minimum set
-    for (size_t j = 0; j < 8; j++) {
-      int randi = RandomInt(0, vAvailableIndices.size() - 1);
-      int idx = vAvailableIndices[randi];
-      mvSets[it][j] = idx;
-      vAvailableIndices[randi] = vAvailableIndices.back();
-      vAvailableIndices.pop_back();
-    }
-  }
+  for (int it = 0; it < mMaxIterations; it++) DrawMinimalSet(vAllIndices, 8, sets);   // Select a minimum set
+  mvSets = std::vector<std::vector<size_t> >(mMaxIterations > 0 ? mMaxIterations : 0, std::vector<size_t>(8, 0));
+  for (size_t it = 0; it < mvSets.size(); ++it) for (int j = 0; j < 8; ++j) mvSets[it][j] = sets[8 * it + j];
 
   // Normalize coordinates, over all keypoints of each frame
   const size_t n1 = vKeys1.size(), n2 = vKeys2.size();
@@ -87,7 +74,7 @@ bool TwoViewReconstruction::Reconstruct(const std::vector<cv::KeyPoint>& vKeys1,
   osh_two_view_problem p{};
   osh::tv_normalize(xy1.data(), (int)n1, vPn1.data(), p.T1);
   osh::tv_normalize(xy2.data(), (int)n2, vPn2.data(), p.T2);
-  std::vector<int32_t> idx1(N), idx2(N), sets((size_t)mvSets.size() * 8);
+  std::vector<int32_t> idx1(N), idx2(N);
   std::vector<float> pt1(2 * (size_t)N), pt2(2 * (size_t)N), pn1(2 * (size_t)N), pn2(2 * (size_t)N);
   bool valid = true;
   for (int i = 0; i < N; ++i) {
@@ -97,7 +84,6 @@ bool TwoViewReconstruction::Reconstruct(const std::vector<cv::KeyPoint>& vKeys1,
     for (int k = 0; k < 2; ++k) { pt1[2 * i + k] = xy1[2 * a + k]; pt2[2 * i + k] = xy2[2 * b + k]; pn1[2 * i + k] = vPn1[2 * a + k]; pn2[2 * i + k] = vPn2[2 * b + k]; }
   }
   if (!valid) { std::fprintf(stderr, "TwoViewReconstruction::Reconstruct: a match names a keypoint outside vKeys2\n"); return false; }
-  for (size_t it = 0; it < mvSets.size(); ++it) for (int j = 0; j < 8; ++j) sets[8 * it + j] = (int32_t)mvSets[it][j];
   for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) p.K[3 * r + c] = mK(r, c);
   p.sigma = mSigma; p.n_iterations = (int32_t)mvSets.size(); p.n_matches = N; p.n_keys1 = (int32_t)n1; p.n_keys2 = (int32_t)n2;
   p.idx1 = idx1.data(); p.idx2 = idx2.data(); p.pt1 = pt1.data(); p.pt2 = pt2.data(); p.pn1 = pn1.data(); p.pn2 = pn2.data(); p.sets = sets.data();

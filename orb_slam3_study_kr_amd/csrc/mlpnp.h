@@ -16,10 +16,9 @@
 //   * The rank of planarTest: column-pivoted Householder QR (the column of the largest remaining norm first), pivots counted while
 //     |pivot| > 3 * eps * |largest pivot|, Eigen's default threshold for a 3x3 matrix (ml_rank3).
 //   * The eigenvectors of planarTest (ascending eigenvalues), the null vector of the 12x12 or 9x9 normal matrix and the polar factor
-//     U V^T of a 3x3 matrix come from the one-sided Jacobi method of two_view.h (tv_rotation, tv_rotate_pair, tv_rotate3) in FP64
-//     with a fixed number of sweeps.  For the normal matrix the sums over the rows are the pairwise tree over 16 rows (tv_tree16; rows
-//     12..15 are zero): the device keeps one row per lane.  The null vector is the column of V whose column of M V has the smallest
-//     norm (the first on a tie) among the first 12 or 9.
+//     U V^T of a 3x3 matrix come from the one-sided Jacobi method of jacobi_rows.h (jacobi_rotate3, null_vector) in FP64 with a fixed
+//     number of sweeps.  The normal matrix is a row array there (rows 12..15 are zero); its null vector is taken among the first 12
+//     or 9 columns.
 //   * Every sum over the correspondences (planarTest, the normal matrix, J^T J, J^T r) is 64 partial sums, partial l adding the
 //     correspondences l, l + 64, .. in that order, joined by the pairwise tree over the 64 (ml_tree64): the same for 6 and for 2048
 //     correspondences, whatever the launch.  The normal matrix is kept as its 60 distinct sums Q[r][r'] * ([p;1][p;1]^T)[a][a'].
@@ -32,7 +31,8 @@
 //     entry < 1e-5", false for a NaN, so the loop goes on to its bound of 5.
 // No loop here depends on a convergence test: every bound is fixed, a NaN input ends in 0 inliers.
 #pragma once
-#include "two_view.h"
+#include "jacobi_rows.h"
+#include "ransac_stage.h"
 #include <algorithm>
 #include <cstdint>
 #include <vector>
@@ -41,7 +41,7 @@ namespace osh {
 
 constexpr int kMlWave = 64;      // partial sums of a sum over the correspondences
 constexpr int kMlSweeps = 12;    // Jacobi sweeps over the 66 column pairs of the 12x12 normal matrix
-constexpr int kMlRows = 16;      // rows the pairwise tree of the Jacobi sums runs over
+constexpr int kMlRows = kJacobiRows;   // rows of the normal matrix as a row array: 12 and four of zeros
 constexpr int kMlGnIterations = 5;
 constexpr double kMlEps = 2.220446049250313e-16;
 
@@ -190,7 +190,7 @@ OSH_KB8_HD void ml_jacobi3(const double* A, double (&b)[3][3], double (&v)[3][3]
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) { b[i][j] = A[3 * i + j]; v[i][j] = i == j ? 1.0 : 0.0; }
-  for (int sweep = 0; sweep < kTvSweeps; ++sweep) { tv_rotate3<0, 1>(b, v); tv_rotate3<0, 2>(b, v); tv_rotate3<1, 2>(b, v); }
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) { jacobi_rotate3<0, 1>(b, v); jacobi_rotate3<0, 2>(b, v); jacobi_rotate3<1, 2>(b, v); }
 }
 // SelfAdjointEigenSolver(planarTest).eigenvectors()^T: row j of E is the eigenvector of the j-th smallest eigenvalue (stable order)
 OSH_KB8_HD void ml_eig3_rows(const double S[6], double* E) {
@@ -285,30 +285,8 @@ OSH_KB8_HD void ml_add_system(const double* f, const double* p, bool planar, con
     }
 }
 
-// The null vector of the 16x12 array of rows (rows 12..15 and, planar, rows and columns 9..11 zero), plain C++: the kernel runs the
-// same operations with a row per lane
-inline void ml_null12(double a[kMlRows][12], int cols, double h[12]) {
-#pragma clang fp contract(off)
-  double v[12][12], x[kMlRows], y[kMlRows], z[kMlRows];
-  for (int i = 0; i < 12; ++i) for (int j = 0; j < 12; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < kMlSweeps; ++sweep)
-    for (int p = 0; p < 11; ++p)
-      for (int q = p + 1; q < 12; ++q) {
-        for (int i = 0; i < kMlRows; ++i) { x[i] = a[i][p] * a[i][p]; y[i] = a[i][q] * a[i][q]; z[i] = a[i][p] * a[i][q]; }
-        double c, s;
-        tv_rotation(tv_tree16(x), tv_tree16(y), tv_tree16(z), c, s);
-        for (int i = 0; i < kMlRows; ++i) tv_rotate_pair(a[i][p], a[i][q], c, s);
-        for (int i = 0; i < 12; ++i) tv_rotate_pair(v[i][p], v[i][q], c, s);
-      }
-  int best = 0;
-  double best_n = 0;
-  for (int j = 0; j < cols; ++j) {
-    for (int i = 0; i < kMlRows; ++i) x[i] = a[i][j] * a[i][j];
-    const double n = tv_tree16(x);
-    if (j == 0 || n < best_n) { best_n = n; best = j; }
-  }
-  for (int k = 0; k < 12; ++k) h[k] = v[k][best];
-}
+// The null vector of the 16x12 array of rows (rows 12..15 and, planar, rows and columns 9..11 zero) among the first `cols` columns
+inline void ml_null12(double a[kMlRows][12], int cols, double h[12]) { null_vector<12, kMlSweeps>(a, cols, h); }
 
 // ---------------------------------------------------------------------------------------------------- computePose: :526-637
 // h: the null vector (planar: 9 entries).  E: eigenRot (rows: eigenvectors), read when planar.  f6, p6: the first six correspondences.
@@ -513,10 +491,8 @@ OSH_KB8_HD bool ml_inlier(int camera_type, const float* cam, const double* T, co
   const float v[3] = {(float)(T[0] * (double)X + T[1] * (double)Y + T[2] * (double)Z + T[9]),
                       (float)(T[3] * (double)X + T[4] * (double)Y + T[5] * (double)Z + T[10]),
                       (float)(T[6] * (double)X + T[7] * (double)Y + T[8] * (double)Z + T[11])};
-  float uv[2];
-  if (camera_type == OSH_MLPNP_KB8) kb8_project(cam, v, uv);
-  else { uv[0] = cam[0] * v[0] / v[2] + cam[2]; uv[1] = cam[1] * v[1] / v[2] + cam[3]; }
-  const float distX = p2d[0] - uv[0], distY = p2d[1] - uv[1];
+  const Pixel uv = ransac_project(camera_type, cam, v);
+  const float distX = p2d[0] - uv.u, distY = p2d[1] - uv.v;
   const float error2 = distX * distX + distY * distY;
   return error2 < max_error;
 }
@@ -631,7 +607,7 @@ inline void ml_compute_pose_host(int n, const int* idx, const double* bearing, c
 }
 // CheckInliers of one pose over the n correspondences: the count, the mask as bit words (bit i % 32 of word i / 32)
 inline int ml_check_inliers_host(const osh_mlpnp_problem& P, const double* pose, uint32_t* mask) {
-  const int words = 2 * ((P.n + 63) / 64);
+  const int words = ransac_mask_words(P.n);
   int count = 0;
   for (int w = 0; w < words; ++w) mask[w] = 0;
   for (int i = 0; i < P.n; ++i)
@@ -639,8 +615,6 @@ inline int ml_check_inliers_host(const osh_mlpnp_problem& P, const double* pose,
   return count;
 }
 
-template <class T>
-inline void ml_copy(T* dst, const T* src, size_t n) { if (dst && n) std::memcpy(dst, src, n * sizeof(T)); }
 template <class T>
 inline void ml_zero(T* dst, size_t n) { if (dst && n) std::memset(dst, 0, n * sizeof(T)); }
 inline void ml_write_head(const osh_mlpnp_result& r, const MlHead& H) {
@@ -651,13 +625,13 @@ inline void ml_write_head(const osh_mlpnp_result& r, const MlHead& H) {
   if (r.best_count) *r.best_count = H.best_count;
   if (r.best_refine_ok) *r.best_refine_ok = H.best_refine_ok;
   if (r.n_records) *r.n_records = H.n_records;
-  ml_copy(r.hit_pose, H.hit_pose, 12);
-  ml_copy(r.best_pose, H.best_pose, 12);
+  copy_if(r.hit_pose, H.hit_pose, 12);
+  copy_if(r.best_pose, H.best_pose, 12);
 }
 
 // osh_orb_mlpnp_solve for one valid problem, on one thread
 inline void ml_solve_host(const osh_mlpnp_problem& P, const osh_mlpnp_result& r) {
-  const int n = P.n, n_it = P.n_iterations, words = 2 * ((n + 63) / 64);
+  const int n = P.n, n_it = P.n_iterations, words = ransac_mask_words(n);
   const size_t ni = (size_t)n_it;
   std::vector<double> pose(ni * 12 + 12), rec_pose(ni * 12 + 12);
   std::vector<int> count(ni + 1), record(ni + 1), rec_count(ni + 1), idx((size_t)n + 6);
@@ -680,14 +654,14 @@ inline void ml_solve_host(const osh_mlpnp_problem& P, const osh_mlpnp_result& r)
   if (H.hit_record >= 0) std::memcpy(H.hit_pose, &rec_pose[12 * (size_t)H.hit_record], 96);
   if (H.best_iteration >= 0) std::memcpy(H.best_pose, &pose[12 * (size_t)H.best_iteration], 96);
   ml_write_head(r, H);
-  if (H.hit_record >= 0) ml_copy(r.hit_mask, &rec_mask[(size_t)H.hit_record * words], words); else ml_zero(r.hit_mask, words);
-  if (H.best_iteration >= 0) ml_copy(r.best_mask, &mask[(size_t)H.best_iteration * words], words); else ml_zero(r.best_mask, words);
-  ml_copy(r.debug_pose, pose.data(), ni * 12);
-  ml_copy(r.debug_count, count.data(), ni);
+  if (H.hit_record >= 0) copy_if(r.hit_mask, &rec_mask[(size_t)H.hit_record * words], words); else ml_zero(r.hit_mask, words);
+  if (H.best_iteration >= 0) copy_if(r.best_mask, &mask[(size_t)H.best_iteration * words], words); else ml_zero(r.best_mask, words);
+  copy_if(r.debug_pose, pose.data(), ni * 12);
+  copy_if(r.debug_count, count.data(), ni);
   for (size_t q = (size_t)H.n_records; q < ni; ++q) { record[q] = -1; rec_count[q] = 0; for (int k = 0; k < 12; ++k) rec_pose[12 * q + k] = 0.0; }
-  ml_copy(r.debug_record, record.data(), ni);
-  ml_copy(r.debug_record_count, rec_count.data(), ni);
-  ml_copy(r.debug_record_pose, rec_pose.data(), ni * 12);
+  copy_if(r.debug_record, record.data(), ni);
+  copy_if(r.debug_record_count, rec_count.data(), ni);
+  copy_if(r.debug_record_pose, rec_pose.data(), ni * 12);
 }
 
 }  // namespace osh

@@ -43,14 +43,6 @@ __device__ __forceinline__ double ml_wave_sum(double x) {   // ml_tree64 over th
   x = x + __shfl_xor(x, 32);
   return x;
 }
-__device__ __forceinline__ double ml_rows_sum(double x) {   // tv_tree16 over lanes 0..15, the result in every lane
-#pragma clang fp contract(off)
-  x = x + __shfl_xor(x, 1);
-  x = x + __shfl_xor(x, 2);
-  x = x + __shfl_xor(x, 4);
-  x = x + __shfl_xor(x, 8);
-  return __shfl(x, 0);
-}
 
 // computePose over the correspondences idx[0..n) (LDS) of the problem whose arrays start at bearing / p3d: what ml_compute_pose_host
 // states, by one wavefront.  sT: 60 doubles of LDS.  The pose is left in every lane.
@@ -79,28 +71,7 @@ __device__ __forceinline__ void ml_compute_pose_wave(int lane, int n, const int*
   double row[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) row[k] = lane < kMlRows ? (lane < 12 ? ml_system_entry(sT, planar, lane, k) : 0.0) : (lane - kMlRows == k ? 1.0 : 0.0);
-  for (int sweep = 0; sweep < kMlSweeps; ++sweep) {
-#pragma unroll
-    for (int p = 0; p < 11; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 12; ++q) {
-        const double alpha = ml_rows_sum(row[p] * row[p]), beta = ml_rows_sum(row[q] * row[q]), gamma = ml_rows_sum(row[p] * row[q]);
-        double c, s;
-        tv_rotation(alpha, beta, gamma, c, s);
-        tv_rotate_pair(row[p], row[q], c, s);
-      }
-  }
-  const int cols = planar ? 9 : 12;
-  int best = 0;
-  double best_n = 0;
-#pragma unroll
-  for (int j = 0; j < 12; ++j) {
-    const double nj = ml_rows_sum(row[j] * row[j]);
-    if (j < cols && (j == 0 || nj < best_n)) { best_n = nj; best = j; }
-  }
-  double mine = 0;
-#pragma unroll
-  for (int j = 0; j < 12; ++j) if (j == best) mine = row[j];
+  const double mine = null_vector_wave<12, kMlSweeps>(row, planar ? 9 : 12);
   double h[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) h[k] = __shfl(mine, kMlRows + k);
@@ -166,19 +137,10 @@ __global__ __launch_bounds__(kMlWave) void k_ml_score(MlView v, const double* po
   float cam[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) cam[k] = P.cam[k];
-  unsigned* m = mask + (size_t)P.base_w + (size_t)it * P.words;
-  int c = 0;
-  for (int base = 0; base < n; base += kMlWave) {
-    const int i = base + lane;
-    bool in = false;
-    if (i < n) {
-      const size_t j = (size_t)P.base_p + i;
-      in = ml_inlier(P.camera_type, cam, T, v.p3d + 3 * j, v.p2d + 2 * j, v.max_error[j]);
-    }
-    const unsigned long long b = __ballot(in);
-    if (lane == 0) { m[base >> 5] = (unsigned)b; m[(base >> 5) + 1] = (unsigned)(b >> 32); }
-    c += __popcll(b);
-  }
+  const int c = wave_score(lane, n, mask + (size_t)P.base_w + (size_t)it * P.words, [&](int i) {
+    const size_t j = (size_t)P.base_p + i;
+    return ml_inlier(P.camera_type, cam, T, v.p3d + 3 * j, v.p2d + 2 * j, v.max_error[j]);
+  });
   if (lane == 0) count[g] = c;
 }
 
@@ -208,14 +170,7 @@ __global__ __launch_bounds__(kMlWave) void k_ml_refine(MlView v) {
   __shared__ double s_T[60];
   const size_t g = (size_t)P.base_h + q;
   const unsigned* m = v.mask + (size_t)P.base_w + (size_t)v.record[g] * P.words;
-  int c = 0;
-  for (int base = 0; base < n; base += kMlWave) {
-    const int i = base + lane;
-    const bool in = i < n && ((m[i >> 5] >> (i & 31)) & 1u);
-    const unsigned long long b = __ballot(in);
-    if (in) s_idx[c + __popcll(b & ((1ull << lane) - 1ull))] = i;
-    c += __popcll(b);
-  }
+  const int c = wave_compact(lane, n, [&](int i) { return i < n && ((m[i >> 5] >> (i & 31)) & 1u); }, s_idx);
   __syncthreads();
   double pose[12];
   ml_compute_pose_wave(lane, c, s_idx, v.bearing + 3 * (size_t)P.base_p, v.p3d + 3 * (size_t)P.base_p, s_T, pose);
@@ -264,32 +219,19 @@ static int ml_validate_points(const char* entry, int k, const osh_mlpnp_problem&
   return OSH_OK;
 }
 
-static int ml_validate(int n_problems, const osh_mlpnp_problem* ps, size_t* total_n, size_t* total_i, size_t* total_w, size_t* total_o, int* max_iter) {
+static int ml_validate(int n_problems, const osh_mlpnp_problem* ps, RansacBatch& batch) {
   const char* entry = "osh_orb_mlpnp_solve";
   if (n_problems > OSH_MLPNP_MAX_PROBLEMS) { set_error("%s: more than %d problems", entry, OSH_MLPNP_MAX_PROBLEMS); return OSH_ERR_UNSUPPORTED; }
-  size_t N = 0, I = 0, W = 0, O = 0;
-  int mx = 0;
+  batch.base.reserve((size_t)n_problems);
   for (int k = 0; k < n_problems; ++k) {
     const osh_mlpnp_problem& p = ps[k];
     OSH_TRY(ml_validate_points(entry, k, p));
     if (p.n_iterations < 0) { set_error("%s: problem %d: negative count", entry, k); return OSH_ERR_INVALID; }
     if (p.n_iterations > OSH_MLPNP_MAX_ITERATIONS) { set_error("%s: problem %d: more than %d iterations", entry, k, OSH_MLPNP_MAX_ITERATIONS); return OSH_ERR_UNSUPPORTED; }
     if (p.min_inliers < 6) { set_error("%s: problem %d: min_inliers %d below the minimal set of 6", entry, k, p.min_inliers); return OSH_ERR_INVALID; }
-    if (p.n_iterations && !p.sets) { set_error("%s: problem %d: NULL sets with n_iterations = %d", entry, k, p.n_iterations); return OSH_ERR_INVALID; }
-    if (p.n_iterations && p.n < 6) { set_error("%s: problem %d: %d correspondences cannot fill a minimal set of 6", entry, k, p.n); return OSH_ERR_INVALID; }
-    for (int it = 0; it < p.n_iterations; ++it) {
-      const int32_t* s = p.sets + 6 * (size_t)it;
-      for (int a = 0; a < 6; ++a) {
-        if (s[a] < 0 || s[a] >= p.n) { set_error("%s: problem %d: set %d: index %d outside [0, %d)", entry, k, it, s[a], p.n); return OSH_ERR_INVALID; }
-        for (int b = 0; b < a; ++b)
-          if (s[a] == s[b]) { set_error("%s: problem %d: set %d repeats index %d", entry, k, it, s[a]); return OSH_ERR_INVALID; }
-      }
-    }
-    const size_t words = (size_t)OSH_MLPNP_MASK_WORDS(p.n);
-    N += (size_t)p.n; I += (size_t)p.n_iterations; W += words * (size_t)p.n_iterations; O += words;
-    mx = std::max(mx, p.n_iterations);
+    OSH_TRY(validate_minimal_sets<6>(entry, k, p.sets, p.n_iterations, p.n));
+    batch.add(p.n, p.n_iterations, ransac_mask_words(p.n));
   }
-  *total_n = N; *total_i = I; *total_w = W; *total_o = O; *max_iter = mx;
   return OSH_OK;
 }
 
@@ -297,7 +239,7 @@ static void ml_fill_problem(MlProblem& d, const osh_mlpnp_problem& p, int n_iter
   d.camera_type = p.camera_type;
   for (int k = 0; k < 8; ++k) d.cam[k] = p.camera[k];
   d.n = p.n; d.n_iter = n_iter; d.min_inliers = p.min_inliers; d.best_in = p.best_inliers_in; d.ok_in = p.best_refine_ok_in ? 1 : 0;
-  d.words = OSH_MLPNP_MASK_WORDS(p.n);
+  d.words = ransac_mask_words(p.n);
   d.base_p = (int)base_p; d.base_h = (int)base_h; d.base_w = (int)base_w;
 }
 
@@ -308,9 +250,8 @@ using namespace osh;
 extern "C" int osh_orb_mlpnp_solve(osh_orb_ctx* c, int32_t n_problems, const osh_mlpnp_problem* ps, const osh_mlpnp_result* results) {
   PhaseClock clock;
   if (n_problems < 0 || (n_problems && (!ps || !results))) { set_error("osh_orb_mlpnp_solve: bad arguments"); return OSH_ERR_INVALID; }
-  size_t N = 0, I = 0, W = 0, O = 0;
-  int max_iter = 0;
-  OSH_TRY(ml_validate(n_problems, ps, &N, &I, &W, &O, &max_iter));   // the problems first: a refusal needs no context and no device
+  RansacBatch batch;
+  OSH_TRY(ml_validate(n_problems, ps, batch));   // the problems first: a refusal needs no context and no device
   if (!c) { set_error("osh_orb_mlpnp_solve: no context"); return OSH_ERR_INVALID; }
   if (n_problems == 0) return OSH_OK;
   int device = 0;
@@ -322,7 +263,10 @@ extern "C" int osh_orb_mlpnp_solve(osh_orb_ctx* c, int32_t n_problems, const osh
   bool debug = false;
   for (int k = 0; k < n_problems; ++k) debug = debug || results[k].debug_pose || results[k].debug_record_pose;
 
-  const size_t nP = (size_t)n_problems;
+  const size_t nP = (size_t)n_problems, N = batch.N, I = batch.I, W = batch.W;
+  std::vector<size_t> base_o(nP);   // the two masks of a problem's result: one mask row per problem, beside the rows per iteration
+  size_t O = 0;
+  for (int k = 0; k < n_problems; ++k) { base_o[k] = O; O += (size_t)ransac_mask_words(ps[k].n); }
   Layout in, out, work;
   const auto s_prob = in.take<MlProblem>(nP);
   const auto s_base_o = in.take<int>(nP);
@@ -339,21 +283,17 @@ extern "C" int osh_orb_mlpnp_solve(osh_orb_ctx* c, int32_t n_problems, const osh
   OSH_TRY(st->call.reserve(in, out, work.bytes));
 
   char* h = st->call.host_in();
-  std::vector<size_t> base_p(nP), base_h(nP), base_o(nP);
-  size_t bp = 0, bh = 0, bw = 0, bo = 0;
   for (int k = 0; k < n_problems; ++k) {
     const osh_mlpnp_problem& p = ps[k];
-    const size_t n = (size_t)p.n, ni = (size_t)p.n_iterations, words = (size_t)OSH_MLPNP_MASK_WORDS(p.n);
-    base_p[k] = bp; base_h[k] = bh; base_o[k] = bo;
-    ml_fill_problem(s_prob.in(h)[k], p, p.n_iterations, bp, bh, bw);
-    s_base_o.in(h)[k] = (int)bo;
+    const size_t n = (size_t)p.n, bp = batch.base[k].p;
+    ml_fill_problem(s_prob.in(h)[k], p, p.n_iterations, bp, batch.base[k].h, batch.base[k].w);
+    s_base_o.in(h)[k] = (int)base_o[k];
     if (n) {
       std::memcpy(s_bearing.in(h) + bp * 3, p.bearing, n * 24); std::memcpy(s_p3d.in(h) + bp * 3, p.p3d, n * 24);
       std::memcpy(s_p2d.in(h) + bp * 2, p.p2d, n * 8); std::memcpy(s_err.in(h) + bp, p.max_error, n * 4);
     }
-    if (ni) std::memcpy(s_sets.in(h) + bh * 6, p.sets, ni * 24);
-    bp += n; bh += ni; bw += words * ni; bo += words;
   }
+  batch.stage_sets<6>(s_sets.in(h), ps);
   clock.mark();
   OSH_TRY(st->call.upload(s));
   OSH_TRY(clock.mark_synced(s));
@@ -369,7 +309,7 @@ extern "C" int osh_orb_mlpnp_solve(osh_orb_ctx* c, int32_t n_problems, const osh
   v.count = o_count.in(dout); v.record = o_record.in(dout); v.rec_count = o_rcount.in(dout);
   v.mask = w_mask.in(dw); v.rec_mask = w_rmask.in(dw);
   v.head = o_head.in(dout); v.out_hit_mask = o_hit.in(dout); v.out_best_mask = o_best.in(dout);
-  const dim3 per_pose((unsigned)std::max(max_iter, 1), (unsigned)n_problems), per_problem((unsigned)n_problems), wave(kMlWave);
+  const dim3 per_pose((unsigned)std::max(batch.max_iter, 1), (unsigned)n_problems), per_problem((unsigned)n_problems), wave(kMlWave);
   if (clock.profiling) OSH_HIP(hipEventRecord(st->ev[0], s));
   hipLaunchKernelGGL(k_ml_hypothesis, per_pose, wave, 0, s, v);
   OSH_TRY(launch_check("MLPnP hypotheses"));
@@ -389,12 +329,12 @@ extern "C" int osh_orb_mlpnp_solve(osh_orb_ctx* c, int32_t n_problems, const osh
   const char* ho = st->call.host_out();
   for (int k = 0; k < n_problems; ++k) {
     const osh_mlpnp_result& r = results[k];
-    const size_t ni = (size_t)ps[k].n_iterations, words = (size_t)OSH_MLPNP_MASK_WORDS(ps[k].n);
+    const size_t ni = (size_t)ps[k].n_iterations, words = (size_t)ransac_mask_words(ps[k].n), bh = batch.base[k].h;
     ml_write_head(r, o_head.in(ho)[k]);
     scatter(r.hit_mask, o_hit, ho, base_o[k], words); scatter(r.best_mask, o_best, ho, base_o[k], words);
-    scatter(r.debug_count, o_count, ho, base_h[k], ni); scatter(r.debug_record, o_record, ho, base_h[k], ni);
-    scatter(r.debug_record_count, o_rcount, ho, base_h[k], ni);
-    if (debug) { scatter(r.debug_pose, h_pose, ho, base_h[k], ni, 12); scatter(r.debug_record_pose, h_rpose, ho, base_h[k], ni, 12); }
+    scatter(r.debug_count, o_count, ho, bh, ni); scatter(r.debug_record, o_record, ho, bh, ni);
+    scatter(r.debug_record_count, o_rcount, ho, bh, ni);
+    if (debug) { scatter(r.debug_pose, h_pose, ho, bh, ni, 12); scatter(r.debug_record_pose, h_rpose, ho, bh, ni, 12); }
   }
   clock.mark();
   clock.store(st->ms);
@@ -418,7 +358,7 @@ extern "C" int osh_orb_mlpnp_check_inliers(osh_orb_ctx* c, const osh_mlpnp_probl
   hipStream_t s = nullptr;
   OSH_TRY(orb_stream(c, &device, &s));
   MlpnpState* st = orb_state<MlpnpState>(c, kOrbAttachMlpnp);
-  const size_t n = (size_t)p->n, np = (size_t)n_poses, words = (size_t)OSH_MLPNP_MASK_WORDS(p->n);
+  const size_t n = (size_t)p->n, np = (size_t)n_poses, words = (size_t)ransac_mask_words(p->n);
   Layout in, out;
   const auto s_prob = in.take<MlProblem>(1);
   const auto s_p3d = in.take<double>(n * 3); const auto s_p2d = in.take<float>(n * 2); const auto s_err = in.take<float>(n);
@@ -444,7 +384,5 @@ extern "C" int osh_orb_mlpnp_check_inliers(osh_orb_ctx* c, const osh_mlpnp_probl
 }
 
 extern "C" int osh_orb_mlpnp_get_times(osh_orb_ctx* c, double ms[5]) {
-  if (!c || !ms) { set_error("osh_orb_mlpnp_get_times: bad arguments"); return OSH_ERR_INVALID; }
-  std::memcpy(ms, orb_state<MlpnpState>(c, kOrbAttachMlpnp)->ms, sizeof(double) * 5);
-  return OSH_OK;
+  return copy_times<MlpnpState, 5>("osh_orb_mlpnp_get_times", c, kOrbAttachMlpnp, ms);
 }

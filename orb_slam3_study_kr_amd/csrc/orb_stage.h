@@ -10,9 +10,9 @@
 // along or resident on the context: orb_pyramid_set.h, built on pack_level, is their level list; they use scatter, PhaseClock,
 // orb_state and copy_times.  osh_orb_pyramid_build (orb_pyramid_device.hip) fills the resident pyramid: pack_level, PhaseClock, orb_state.
 // osh_orb_refresh_map_points (mappoint_device.hip) has batches of map points: it uses scatter, PhaseClock, orb_state and copy_times.
-// osh_orb_two_view_reconstruct (two_view_device.hip) has problems of matches and minimal sets: scatter, PhaseClock, orb_state, copy_times.
-// osh_orb_mlpnp_solve (mlpnp_device.hip) has problems of correspondences and minimal sets: scatter, PhaseClock, orb_state.
-// osh_orb_sim3_ransac (sim3_ransac_device.hip) has problems of correspondences and minimal sets: scatter, PhaseClock, orb_state, copy_times.
+// osh_orb_two_view_reconstruct (two_view_device.hip), osh_orb_mlpnp_solve (mlpnp_device.hip) and osh_orb_sim3_ransac
+// (sim3_ransac_device.hip) have problems of correspondences and minimal sets: ransac_stage.h is their validator, batch bookkeeping and
+// ballot loops; they use scatter, PhaseClock, orb_state and copy_times (MLPnP with five times).
 #pragma once
 #include "common.h"
 #include <chrono>
@@ -116,11 +116,12 @@ T* orb_state(osh_orb_ctx* c, OrbAttachSlot slot) {
   if (!*p) *p = new T();
   return static_cast<T*>(*p);
 }
-// osh_orb_*_get_times: the phases the last profiled call of the entry stored in its state's ms[4]; zeros before any
-template <class T>
-int copy_times(const char* entry, osh_orb_ctx* c, OrbAttachSlot slot, double ms[4]) {
+// osh_orb_*_get_times: the N times the last profiled call of the entry stored in its state's ms (the four phases first); zeros before any
+template <class T, int N = 4>
+int copy_times(const char* entry, osh_orb_ctx* c, OrbAttachSlot slot, double* ms) {
   if (!c || !ms) { set_error("%s: bad arguments", entry); return OSH_ERR_INVALID; }
-  std::memcpy(ms, orb_state<T>(c, slot)->ms, sizeof(double) * 4);
+  static_assert(sizeof(T::ms) == sizeof(double) * N, "the state keeps N times");
+  std::memcpy(ms, orb_state<T>(c, slot)->ms, sizeof(double) * N);
   return OSH_OK;
 }
 

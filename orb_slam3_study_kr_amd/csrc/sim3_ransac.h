@@ -20,9 +20,9 @@
 //     floats; the drop-in class fills them with the reference's truncation to size_t.
 // What is defined here and not by the reference (Eigen is not available, so parity with it is unpinned):
 //   * The eigenvector of the largest eigenvalue of the symmetric N: the cyclic two-sided Jacobi method in FP64 on the float32 entries,
-//     kS3rSweeps sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), the rotation of a pair from tv_rotation (two_view.h) of
-//     (a_pp, a_qq, a_pq) applied to both columns and both rows with tv_rotate_pair and to the columns of V; a pair with a_pq == 0 is
-//     not rotated.  (The one-sided method of two_view.h does not fit: N of three points has the eigenvalues +-(s1 + s2), +-(s1 - s2),
+//     kS3rSweeps sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), the rotation of a pair from jacobi_rotation (jacobi_rows.h) of
+//     (a_pp, a_qq, a_pq) applied to both columns and both rows with jacobi_rotate_pair and to the columns of V; a pair with a_pq == 0
+//     is not rotated.  (The one-sided method of jacobi_rows.h does not fit: N of three points has the eigenvalues +-(s1 + s2), +-(s1 - s2),
 //     so its largest singular value is double.)  The eigenvalues are the diagonal; the largest wins, the first column on a tie.
 //     The vector is divided by its norm and its sign set so that its real part is >= 0.  The reference runs Eigen's EigenSolver in float.
 //   * mR12i is the rotation matrix of that unit quaternion (w, x, y, z), formed in FP64 and rounded to float32 once.  The reference goes
@@ -32,7 +32,8 @@
 //     iteration); it is a hit when it is a record and count_k > min_inliers.  The running best goes on across a hit.
 // No loop here depends on a convergence test: every bound is fixed, a NaN input ends in 0 inliers.
 #pragma once
-#include "two_view.h"
+#include "jacobi_rows.h"
+#include "ransac_stage.h"
 #include <algorithm>
 #include <cstdint>
 #include <vector>
@@ -40,7 +41,7 @@
 namespace osh {
 
 constexpr int kS3rWave = 64;
-constexpr int kS3rSweeps = 10;   // as kTvSweeps; with 10 the host build equals LAPACK's FP64 eigh in every float32 bit of R, t, s on the
+constexpr int kS3rSweeps = 10;   // as kJacobiSweeps; with 10 the host build equals LAPACK's FP64 eigh in every float32 bit of R, t, s on the
                                  // well-conditioned test sets (tests/sim3_ransac_cases.py)
 
 struct S3rProblem {
@@ -64,13 +65,13 @@ template <int P, int Q>
 OSH_KB8_HD void s3r_jacobi_pair(double (&a)[4][4], double (&v)[4][4]) {
 #pragma clang fp contract(off)
   double c, s;
-  tv_rotation(a[P][P], a[Q][Q], a[P][Q], c, s);
+  jacobi_rotation(a[P][P], a[Q][Q], a[P][Q], c, s);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) tv_rotate_pair(a[r][P], a[r][Q], c, s);
+  for (int r = 0; r < 4; ++r) jacobi_rotate_pair(a[r][P], a[r][Q], c, s);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) tv_rotate_pair(a[P][r], a[Q][r], c, s);
+  for (int r = 0; r < 4; ++r) jacobi_rotate_pair(a[P][r], a[Q][r], c, s);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) tv_rotate_pair(v[r][P], v[r][Q], c, s);
+  for (int r = 0; r < 4; ++r) jacobi_rotate_pair(v[r][P], v[r][Q], c, s);
 }
 // The unit eigenvector (w, x, y, z) of the largest eigenvalue of the symmetric 4x4 matrix N (row-major), w >= 0
 OSH_KB8_HD void s3r_top_eigenvector(const float* N, double q[4]) {
@@ -185,8 +186,8 @@ OSH_KB8_HD void s3r_project(int camera_type, const float* cam, const float* sR, 
 #pragma clang fp contract(off)
   const float v[3] = {((sR[0] * x + sR[1] * y) + sR[2] * z) + t[0], ((sR[3] * x + sR[4] * y) + sR[5] * z) + t[1],
                       ((sR[6] * x + sR[7] * y) + sR[8] * z) + t[2]};
-  if (camera_type == OSH_SIM3R_KB8) kb8_project(cam, v, uv);
-  else { uv[0] = cam[0] * v[0] / v[2] + cam[2]; uv[1] = cam[1] * v[1] / v[2] + cam[3]; }
+  const Pixel p = ransac_project(camera_type, cam, v);
+  uv[0] = p.u; uv[1] = p.v;
 }
 // X1, X2: the point in camera 1 and camera 2; p1, p2: its pixels in image 1 and image 2
 OSH_KB8_HD bool s3r_inlier(int type1, const float* cam1, int type2, const float* cam2, const S3rTransform& T, const float* X1, const float* X2,
@@ -231,7 +232,7 @@ inline void s3r_gather_set(const osh_sim3r_problem& P, const int32_t* set, float
 }
 // CheckInliers of one transform (13 floats) over the n correspondences: the count, the mask as bit words (bit i % 32 of word i / 32)
 inline int s3r_check_inliers_host(const osh_sim3r_problem& P, const float* T13, uint32_t* mask) {
-  const int words = OSH_SIM3R_MASK_WORDS(P.n);
+  const int words = ransac_mask_words(P.n);
   S3rTransform T;
   s3r_transforms(T13, T13 + 9, T13[12], T);
   int count = 0;
@@ -244,8 +245,6 @@ inline int s3r_check_inliers_host(const osh_sim3r_problem& P, const float* T13, 
   return count;
 }
 
-template <class T>
-inline void s3r_copy(T* dst, const T* src, size_t n) { if (dst && n) std::memcpy(dst, src, n * sizeof(T)); }
 inline void s3r_write_head(const osh_sim3r_result& r, const S3rHead& H) {
   if (r.first_hit) *r.first_hit = H.first_hit;
   if (r.n_records) *r.n_records = H.n_records;
@@ -255,7 +254,7 @@ inline void s3r_write_head(const osh_sim3r_result& r, const S3rHead& H) {
 
 // osh_orb_sim3_ransac for one valid problem, on one thread
 inline void s3r_solve_host(const osh_sim3r_problem& P, const osh_sim3r_result& r) {
-  const int n_it = P.n_iterations, words = OSH_SIM3R_MASK_WORDS(P.n);
+  const int n_it = P.n_iterations, words = ransac_mask_words(P.n);
   const size_t ni = (size_t)n_it, nw = (size_t)words;
   std::vector<float> T(ni * 13 + 13), rec_T(ni * 13 + 13, 0.f);
   std::vector<int> count(ni + 1), record(ni + 1, -1), rec_count(ni + 1, 0);
@@ -276,12 +275,12 @@ inline void s3r_solve_host(const osh_sim3r_problem& P, const osh_sim3r_result& r
   }
   for (size_t q = (size_t)H.n_records; q < ni; ++q) record[q] = -1;
   s3r_write_head(r, H);
-  s3r_copy(r.record, record.data(), ni);
-  s3r_copy(r.record_count, rec_count.data(), ni);
-  s3r_copy(r.record_T, rec_T.data(), ni * 13);
-  s3r_copy(r.record_mask, rec_mask.data(), ni * nw);
-  s3r_copy(r.debug_count, count.data(), ni);
-  s3r_copy(r.debug_T, T.data(), ni * 13);
+  copy_if(r.record, record.data(), ni);
+  copy_if(r.record_count, rec_count.data(), ni);
+  copy_if(r.record_T, rec_T.data(), ni * 13);
+  copy_if(r.record_mask, rec_mask.data(), ni * nw);
+  copy_if(r.debug_count, count.data(), ni);
+  copy_if(r.debug_T, T.data(), ni * 13);
 }
 
 }  // namespace osh

@@ -56,22 +56,13 @@ __global__ __launch_bounds__(kS3rWave) void k_s3r_hypothesis(S3rView v, const fl
   float cam1[8], cam2[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { cam1[k] = P.cam1[k]; cam2[k] = P.cam2[k]; }
-  unsigned* m = v.mask + (size_t)P.base_w + (size_t)it * P.words;
-  int c = 0;
-  for (int base = 0; base < n; base += kS3rWave) {
-    const int i = base + lane;
-    bool in = false;
-    if (i < n) {
-      const float X1[3] = {soa[(kS3rX1 + 0) * total + i], soa[(kS3rX1 + 1) * total + i], soa[(kS3rX1 + 2) * total + i]};
-      const float X2[3] = {soa[(kS3rX2 + 0) * total + i], soa[(kS3rX2 + 1) * total + i], soa[(kS3rX2 + 2) * total + i]};
-      const float p1[2] = {soa[(kS3rP1 + 0) * total + i], soa[(kS3rP1 + 1) * total + i]};
-      const float p2[2] = {soa[(kS3rP2 + 0) * total + i], soa[(kS3rP2 + 1) * total + i]};
-      in = s3r_inlier(P.camera_type1, cam1, P.camera_type2, cam2, T, X1, X2, p1, p2, soa[kS3rE1 * total + i], soa[kS3rE2 * total + i]);
-    }
-    const unsigned long long b = __ballot(in);
-    if (lane < 2) m[(base >> 5) + lane] = (unsigned)(b >> (32 * lane));
-    c += __popcll(b);
-  }
+  const int c = wave_score(lane, n, v.mask + (size_t)P.base_w + (size_t)it * P.words, [&](int i) {
+    const float X1[3] = {soa[(kS3rX1 + 0) * total + i], soa[(kS3rX1 + 1) * total + i], soa[(kS3rX1 + 2) * total + i]};
+    const float X2[3] = {soa[(kS3rX2 + 0) * total + i], soa[(kS3rX2 + 1) * total + i], soa[(kS3rX2 + 2) * total + i]};
+    const float p1[2] = {soa[(kS3rP1 + 0) * total + i], soa[(kS3rP1 + 1) * total + i]};
+    const float p2[2] = {soa[(kS3rP2 + 0) * total + i], soa[(kS3rP2 + 1) * total + i]};
+    return s3r_inlier(P.camera_type1, cam1, P.camera_type2, cam2, T, X1, X2, p1, p2, soa[kS3rE1 * total + i], soa[kS3rE2 * total + i]);
+  });
   if (lane == 0) {
     v.count[g] = c;
     if (!given) {
@@ -87,9 +78,9 @@ __global__ __launch_bounds__(kS3rWave) void k_s3r_decide(S3rView v) {
   const int lane = threadIdx.x, n_it = P.n_iter, words = P.words;
   const size_t bh = (size_t)P.base_h, bw = (size_t)P.base_w;
   __shared__ int s_rec[OSH_SIM3R_MAX_ITERATIONS];
-  int best = P.best_in, n_rec = 0, hit = -1, last = -1;
-  for (int base = 0; base < n_it; base += kS3rWave) {
-    const int k = base + lane;
+  int best = P.best_in, hit = -1, last = -1;
+  const int n_rec = wave_compact(lane, n_it, [&](int k) {   // 64 iterations at a time: is k a record?
+    const int base = k - lane;
     const int c = k < n_it ? v.count[bh + k] : INT_MIN;
     int m = c;   // the maximum over the lanes up to this one
 #pragma unroll
@@ -101,12 +92,11 @@ __global__ __launch_bounds__(kS3rWave) void k_s3r_decide(S3rView v) {
     const int running = lane == 0 ? best : max(best, before);   // s3r_scan_records' `best` when it reaches k
     const bool rec = k < n_it && c >= running;
     const unsigned long long b = __ballot(rec), h = __ballot(rec && c > P.min_inliers);
-    if (rec) s_rec[n_rec + __popcll(b & ((1ull << lane) - 1ull))] = k;
     if (hit < 0 && h) hit = base + __ffsll((long long)h) - 1;
     if (b) last = base + 63 - __clzll((long long)b);
-    n_rec += __popcll(b);
     best = max(best, __shfl(m, kS3rWave - 1));
-  }
+    return rec;
+  }, s_rec);
   __syncthreads();
   if (lane == 0) {
     S3rHead& H = v.head[blockIdx.x];
@@ -144,30 +134,18 @@ static int s3r_validate_points(const char* entry, int k, const osh_sim3r_problem
   return OSH_OK;
 }
 
-static int s3r_validate(int n_problems, const osh_sim3r_problem* ps, size_t* total_n, size_t* total_i, size_t* total_w, int* max_iter) {
+static int s3r_validate(int n_problems, const osh_sim3r_problem* ps, RansacBatch& batch) {
   const char* entry = "osh_orb_sim3_ransac";
   if (n_problems > OSH_SIM3R_MAX_PROBLEMS) { set_error("%s: more than %d problems", entry, OSH_SIM3R_MAX_PROBLEMS); return OSH_ERR_UNSUPPORTED; }
-  size_t N = 0, I = 0, W = 0;
-  int mx = 0;
+  batch.base.reserve((size_t)n_problems);
   for (int k = 0; k < n_problems; ++k) {
     const osh_sim3r_problem& p = ps[k];
     OSH_TRY(s3r_validate_points(entry, k, p));
     if (p.n_iterations < 0) { set_error("%s: problem %d: negative count", entry, k); return OSH_ERR_INVALID; }
     if (p.n_iterations > OSH_SIM3R_MAX_ITERATIONS) { set_error("%s: problem %d: more than %d iterations", entry, k, OSH_SIM3R_MAX_ITERATIONS); return OSH_ERR_UNSUPPORTED; }
-    if (p.n_iterations && !p.sets) { set_error("%s: problem %d: NULL sets with n_iterations = %d", entry, k, p.n_iterations); return OSH_ERR_INVALID; }
-    if (p.n_iterations && p.n < 3) { set_error("%s: problem %d: %d correspondences cannot fill a minimal set of 3", entry, k, p.n); return OSH_ERR_INVALID; }
-    for (int it = 0; it < p.n_iterations; ++it) {
-      const int32_t* s = p.sets + 3 * (size_t)it;
-      for (int a = 0; a < 3; ++a) {
-        if (s[a] < 0 || s[a] >= p.n) { set_error("%s: problem %d: set %d: index %d outside [0, %d)", entry, k, it, s[a], p.n); return OSH_ERR_INVALID; }
-        for (int b = 0; b < a; ++b)
-          if (s[a] == s[b]) { set_error("%s: problem %d: set %d repeats index %d", entry, k, it, s[a]); return OSH_ERR_INVALID; }
-      }
-    }
-    N += (size_t)p.n; I += (size_t)p.n_iterations; W += (size_t)OSH_SIM3R_MASK_WORDS(p.n) * (size_t)p.n_iterations;
-    mx = std::max(mx, p.n_iterations);
+    OSH_TRY(validate_minimal_sets<3>(entry, k, p.sets, p.n_iterations, p.n));
+    batch.add(p.n, p.n_iterations, ransac_mask_words(p.n));
   }
-  *total_n = N; *total_i = I; *total_w = W; *max_iter = mx;
   return OSH_OK;
 }
 
@@ -176,7 +154,7 @@ static void s3r_fill_problem(S3rProblem& d, const osh_sim3r_problem& p, int n_it
   for (int k = 0; k < 8; ++k) { d.cam1[k] = p.camera1[k]; d.cam2[k] = p.camera2[k]; }
   d.fix_scale = p.fix_scale ? 1 : 0;
   d.n = p.n; d.n_iter = n_iter; d.min_inliers = p.min_inliers; d.best_in = p.best_inliers_in;
-  d.words = OSH_SIM3R_MASK_WORDS(p.n);
+  d.words = ransac_mask_words(p.n);
   d.base_p = (int)base_p; d.base_h = (int)base_h; d.base_w = (int)base_w;
 }
 
@@ -197,9 +175,8 @@ using namespace osh;
 extern "C" int osh_orb_sim3_ransac(osh_orb_ctx* c, int32_t n_problems, const osh_sim3r_problem* ps, const osh_sim3r_result* results) {
   PhaseClock clock;
   if (n_problems < 0 || (n_problems && (!ps || !results))) { set_error("osh_orb_sim3_ransac: bad arguments"); return OSH_ERR_INVALID; }
-  size_t N = 0, I = 0, W = 0;
-  int max_iter = 0;
-  OSH_TRY(s3r_validate(n_problems, ps, &N, &I, &W, &max_iter));   // the problems first: a refusal needs no context and no device
+  RansacBatch batch;
+  OSH_TRY(s3r_validate(n_problems, ps, batch));   // the problems first: a refusal needs no context and no device
   if (!c) { set_error("osh_orb_sim3_ransac: no context"); return OSH_ERR_INVALID; }
   if (n_problems == 0) return OSH_OK;
   int device = 0;
@@ -210,7 +187,7 @@ extern "C" int osh_orb_sim3_ransac(osh_orb_ctx* c, int32_t n_problems, const osh
   bool debug = false;
   for (int k = 0; k < n_problems; ++k) debug = debug || results[k].debug_T;
 
-  const size_t nP = (size_t)n_problems;
+  const size_t nP = (size_t)n_problems, N = batch.N, I = batch.I, W = batch.W;
   Layout in, out, work;
   const auto s_prob = in.take<S3rProblem>(nP);
   const auto s_soa = in.take<float>(N * kS3rArrays);
@@ -225,17 +202,12 @@ extern "C" int osh_orb_sim3_ransac(osh_orb_ctx* c, int32_t n_problems, const osh
   OSH_TRY(st->call.reserve(in, out, work.bytes));
 
   char* h = st->call.host_in();
-  std::vector<size_t> base_h(nP), base_w(nP);
-  size_t bp = 0, bh = 0, bw = 0;
   for (int k = 0; k < n_problems; ++k) {
-    const osh_sim3r_problem& p = ps[k];
-    const size_t ni = (size_t)p.n_iterations;
-    base_h[k] = bh; base_w[k] = bw;
-    s3r_fill_problem(s_prob.in(h)[k], p, p.n_iterations, bp, bh, bw);
-    s3r_stage_points(s_soa.in(h), N, bp, p);
-    if (ni) std::memcpy(s_sets.in(h) + bh * 3, p.sets, ni * 12);
-    bp += (size_t)p.n; bh += ni; bw += (size_t)OSH_SIM3R_MASK_WORDS(p.n) * ni;
+    const RansacBatch::Base& b = batch.base[k];
+    s3r_fill_problem(s_prob.in(h)[k], ps[k], ps[k].n_iterations, b.p, b.h, b.w);
+    s3r_stage_points(s_soa.in(h), N, b.p, ps[k]);
   }
+  batch.stage_sets<3>(s_sets.in(h), ps);
   clock.mark();
   OSH_TRY(st->call.upload(s));
   OSH_TRY(clock.mark_synced(s));
@@ -248,7 +220,7 @@ extern "C" int osh_orb_sim3_ransac(osh_orb_ctx* c, int32_t n_problems, const osh
   v.T = h_T.in(debug ? dout : dw); v.count = o_count.in(dout); v.mask = w_mask.in(dw);
   v.record = o_record.in(dout); v.rec_count = o_rcount.in(dout); v.rec_T = o_rT.in(dout); v.rec_mask = o_rmask.in(dout);
   v.head = o_head.in(dout);
-  const dim3 per_iteration((unsigned)std::max(max_iter, 1), (unsigned)n_problems), per_problem((unsigned)n_problems), wave(kS3rWave);
+  const dim3 per_iteration((unsigned)std::max(batch.max_iter, 1), (unsigned)n_problems), per_problem((unsigned)n_problems), wave(kS3rWave);
   hipLaunchKernelGGL(k_s3r_hypothesis, per_iteration, wave, 0, s, v, (const float*)nullptr);
   OSH_TRY(launch_check("Sim3 RANSAC hypotheses"));
   hipLaunchKernelGGL(k_s3r_decide, per_problem, wave, 0, s, v);
@@ -258,13 +230,13 @@ extern "C" int osh_orb_sim3_ransac(osh_orb_ctx* c, int32_t n_problems, const osh
   const char* ho = st->call.host_out();
   for (int k = 0; k < n_problems; ++k) {
     const osh_sim3r_result& r = results[k];
-    const size_t ni = (size_t)ps[k].n_iterations, words = (size_t)OSH_SIM3R_MASK_WORDS(ps[k].n);
+    const size_t ni = (size_t)ps[k].n_iterations, words = (size_t)ransac_mask_words(ps[k].n), bh = batch.base[k].h;
     s3r_write_head(r, o_head.in(ho)[k]);
-    scatter(r.record, o_record, ho, base_h[k], ni); scatter(r.record_count, o_rcount, ho, base_h[k], ni);
-    scatter(r.record_T, o_rT, ho, base_h[k], ni, 13);
-    if (r.record_mask && ni * words) std::memcpy(r.record_mask, o_rmask.in(ho) + base_w[k], ni * words * sizeof(uint32_t));
-    scatter(r.debug_count, o_count, ho, base_h[k], ni);
-    if (debug) scatter(r.debug_T, h_T, ho, base_h[k], ni, 13);
+    scatter(r.record, o_record, ho, bh, ni); scatter(r.record_count, o_rcount, ho, bh, ni);
+    scatter(r.record_T, o_rT, ho, bh, ni, 13);
+    scatter(r.record_mask, o_rmask, ho, batch.base[k].w, ni * words);
+    scatter(r.debug_count, o_count, ho, bh, ni);
+    if (debug) scatter(r.debug_T, h_T, ho, bh, ni, 13);
   }
   clock.mark();
   clock.store(st->ms);
@@ -283,7 +255,7 @@ extern "C" int osh_orb_sim3_ransac_check_inliers(osh_orb_ctx* c, const osh_sim3r
   hipStream_t s = nullptr;
   OSH_TRY(orb_stream(c, &device, &s));
   Sim3RansacState* st = orb_state<Sim3RansacState>(c, kOrbAttachSim3Ransac);
-  const size_t n = (size_t)p->n, nt = (size_t)n_T, words = (size_t)OSH_SIM3R_MASK_WORDS(p->n);
+  const size_t n = (size_t)p->n, nt = (size_t)n_T, words = (size_t)ransac_mask_words(p->n);
   Layout in, out;
   const auto s_prob = in.take<S3rProblem>(1);
   const auto s_soa = in.take<float>(n * kS3rArrays);

@@ -8,11 +8,9 @@
 // contraction off, Eigen's three-term reductions (3x3 products, dot, norm) as a0 + (a1 + a2), plain C++ expressions left to right,
 // sqrt and acos as the FP64 function rounded once, double comparisons where the reference compares with a double literal,
 // x = 1.0 / y as the double division rounded once.  What is defined here and not by the reference:
-//   * Singular vectors come from a one-sided Jacobi method in FP64 on the float32 entries, kTvSweeps = 10 sweeps, no data-dependent
-//     loop.  A sweep visits the column pairs in cyclic order (0,1) (0,2) .. (0,8) (1,2) .. (7,8); a pair whose columns are
-//     orthogonal already (gamma == 0) is not rotated.  For the 16x9 (H) or 8x9 (F, rows 8..15 zero) system every sum over the rows is
-//     the pairwise tree ((r0+r1)+(r2+r3))+..: the device keeps one row per lane and adds across lanes in exactly that tree.  The
-//     null vector is the column of V whose column of A*V has the smallest norm (the first on a tie), rounded to float32 once.
+//   * Singular vectors come from the one-sided Jacobi method of jacobi_rows.h in FP64 on the float32 entries, kJacobiSweeps = 10
+//     sweeps, no data-dependent loop.  The 16x9 (H) or 8x9 (F, rows 8..15 zero) system is a row array there: every sum over the rows
+//     is the pairwise tree, and the null vector (null_vector<9, kJacobiSweeps>) is rounded to float32 once.
 //   * The 3x3 SVD (rank 2 of F, DecomposeE, ReconstructH): the same method, 10 sweeps over (0,1) (0,2) (1,2), sums in row order;
 //     singular values descending (stable); u0 = B0 / s0 and u1 = B1 / s1 of B = A * V (a zero vector for a zero singular value),
 //     u2 = +-(u0 x u1) with the sign that makes u2 . B2 >= 0; everything rounded to float32 once.
@@ -22,14 +20,13 @@
 //   * The order statistic of CheckRT is taken in the total order of the float32 bit patterns (tv_cos_key), so that it is defined for
 //     every input; on ordinary cosines it is std::sort's.
 #pragma once
-#include "kb8_triangulate.h"
+#include "jacobi_rows.h"
 #include "../../include/orbslam3_hip.h"
 #include <cstring>
 
 namespace osh {
 
-constexpr int kTvSweeps = 10;   // 8 sweeps agreed with LAPACK's FP64 SVD to 3e-13 on 8-point sets of general and planar scenes, 6 did not
-constexpr int kTvRows = 16;     // rows of the system of a minimal set: 2 * 8 (H); F fills 8 and leaves the rest zero
+constexpr int kTvRows = kJacobiRows;   // rows of the system of a minimal set: 2 * 8 (H); F fills 8 and leaves the rest zero
 
 struct TvProblem {
   float K[9], T1[9], T2[9];   // row-major
@@ -123,65 +120,15 @@ OSH_KB8_HD void tv_system_row(int model, int r, float u1, float v1, float u2, fl
   }
 }
 
-// The rotation of one column pair from the three sums (as kb8_rotate)
-OSH_KB8_HD void tv_rotation(double alpha, double beta, double gamma, double& c, double& s) {
-#pragma clang fp contract(off)
-  const double zeta = (beta - alpha) / (2.0 * gamma);
-  double t = (zeta < 0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  if (gamma == 0.0 || !(t == t)) t = 0.0;
-  c = 1.0 / sqrt(1.0 + t * t); s = c * t;
-}
-OSH_KB8_HD void tv_rotate_pair(double& xp, double& xq, double c, double s) {
-#pragma clang fp contract(off)
-  const double p = xp, q = xq;
-  xp = c * p - s * q; xq = s * p + c * q;
-}
-// The pairwise tree over the 16 rows: what four xor-butterfly steps across 16 lanes leave in every one of them
-OSH_KB8_HD double tv_tree16(const double x[kTvRows]) {
-#pragma clang fp contract(off)
-  double t[kTvRows];
-  for (int i = 0; i < kTvRows; ++i) t[i] = x[i];
-  for (int w = 1; w < kTvRows; w *= 2)
-    for (int i = 0; i < kTvRows; i += 2 * w) t[i] = t[i] + t[i + w];
-  return t[0];
-}
-// The null vector of a 16x9 system, plain C++ (the kernel runs the same operations with a row per lane)
+// The null vector of a 16x9 system, rounded to float32 once
 inline void tv_null9(const float A[kTvRows][9], float h[9]) {
-#pragma clang fp contract(off)
-  double a[kTvRows][9], v[9][9], x[kTvRows], y[kTvRows], z[kTvRows];
+  double a[kTvRows][9], hd[9];
   for (int i = 0; i < kTvRows; ++i) for (int j = 0; j < 9; ++j) a[i][j] = (double)A[i][j];
-  for (int i = 0; i < 9; ++i) for (int j = 0; j < 9; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < kTvSweeps; ++sweep)
-    for (int p = 0; p < 8; ++p)
-      for (int q = p + 1; q < 9; ++q) {
-        for (int i = 0; i < kTvRows; ++i) { x[i] = a[i][p] * a[i][p]; y[i] = a[i][q] * a[i][q]; z[i] = a[i][p] * a[i][q]; }
-        double c, s;
-        tv_rotation(tv_tree16(x), tv_tree16(y), tv_tree16(z), c, s);
-        for (int i = 0; i < kTvRows; ++i) tv_rotate_pair(a[i][p], a[i][q], c, s);
-        for (int i = 0; i < 9; ++i) tv_rotate_pair(v[i][p], v[i][q], c, s);
-      }
-  int best = 0;
-  double best_n = 0;
-  for (int j = 0; j < 9; ++j) {
-    for (int i = 0; i < kTvRows; ++i) x[i] = a[i][j] * a[i][j];
-    const double n = tv_tree16(x);
-    if (j == 0 || n < best_n) { best_n = n; best = j; }
-  }
-  for (int k = 0; k < 9; ++k) h[k] = (float)v[k][best];
+  null_vector<9, kJacobiSweeps>(a, 9, hd);
+  for (int k = 0; k < 9; ++k) h[k] = (float)hd[k];
 }
 
 // ---------------------------------------------------------------------------------------------------- the 3x3 SVD
-template <int P, int Q>
-OSH_KB8_HD void tv_rotate3(double (&b)[3][3], double (&v)[3][3]) {
-#pragma clang fp contract(off)
-  double alpha = 0, beta = 0, gamma = 0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { alpha += b[i][P] * b[i][P]; beta += b[i][Q] * b[i][Q]; gamma += b[i][P] * b[i][Q]; }
-  double c, s;
-  tv_rotation(alpha, beta, gamma, c, s);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { tv_rotate_pair(b[i][P], b[i][Q], c, s); tv_rotate_pair(v[i][P], v[i][Q], c, s); }
-}
 // M = U * diag(w) * V^T (row-major), w descending
 OSH_KB8_HD void tv_svd3(const float* M, float* U, float* w, float* V) {
 #pragma clang fp contract(off)
@@ -190,7 +137,7 @@ OSH_KB8_HD void tv_svd3(const float* M, float* U, float* w, float* V) {
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) { b[i][j] = (double)M[3 * i + j]; v[i][j] = i == j ? 1.0 : 0.0; }
-  for (int sweep = 0; sweep < kTvSweeps; ++sweep) { tv_rotate3<0, 1>(b, v); tv_rotate3<0, 2>(b, v); tv_rotate3<1, 2>(b, v); }
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) { jacobi_rotate3<0, 1>(b, v); jacobi_rotate3<0, 2>(b, v); jacobi_rotate3<1, 2>(b, v); }
   double n[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) n[j] = sqrt(b[0][j] * b[0][j] + b[1][j] * b[1][j] + b[2][j] * b[2][j]);
@@ -234,7 +181,7 @@ OSH_KB8_HD void tv_rank2(const float* Fpre, float* Fn) {
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) { b[i][j] = (double)Fpre[3 * i + j]; v[i][j] = i == j ? 1.0 : 0.0; }
-  for (int sweep = 0; sweep < kTvSweeps; ++sweep) { tv_rotate3<0, 1>(b, v); tv_rotate3<0, 2>(b, v); tv_rotate3<1, 2>(b, v); }
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) { jacobi_rotate3<0, 1>(b, v); jacobi_rotate3<0, 2>(b, v); jacobi_rotate3<1, 2>(b, v); }
   double n[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) n[j] = b[0][j] * b[0][j] + b[1][j] * b[1][j] + b[2][j] * b[2][j];

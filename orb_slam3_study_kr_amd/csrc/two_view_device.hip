@@ -3,8 +3,9 @@
 // one download:
 //   k_tv_hypothesis  one wavefront per (iteration, model, problem).  The 16x9 system of the minimal set (8x9 and eight zero rows for
 //                    F) lives one row per lane in lanes 0..15 and V one row per lane in lanes 16..24, so a column pair's three sums
-//                    are four xor-butterfly steps across the 16 lanes (the pairwise tree tv_tree16 states) and the rotation is two
-//                    FP64 multiply-adds per lane; the 36 pairs of a sweep are unrolled so the rows stay in registers.  Then every
+//                    are four xor-butterfly steps across the 16 lanes (the pairwise tree tree16 states) and the rotation is two
+//                    FP64 multiply-adds per lane (null_vector_wave of jacobi_rows.h: the 36 pairs of a sweep are unrolled so the rows
+//                    stay in registers).  Then every
 //                    lane forms the model, the lanes evaluate 64 matches at a time, and the terms are added in match order from LDS.
 //   k_tv_select      one wavefront per problem: per model the first iteration with the strictly greatest score above 0, the branch,
 //                    the inlier flags of the branch's model (recomputed from the stored model: the same statements, so the same
@@ -16,6 +17,7 @@
 #include "common.h"
 #include "two_view.h"
 #include "orb_stage.h"
+#include "ransac_stage.h"
 #include <cmath>
 #include <vector>
 
@@ -34,15 +36,6 @@ struct TvView {
   TvHead* head;
   unsigned char* out_inlier; unsigned char* out_tri; float* out_x3d;
 };
-
-__device__ __forceinline__ double tv_rows_sum(double x) {   // tv_tree16 over lanes 0..15, the result in every lane
-#pragma clang fp contract(off)
-  x = x + __shfl_xor(x, 1);
-  x = x + __shfl_xor(x, 2);
-  x = x + __shfl_xor(x, 4);
-  x = x + __shfl_xor(x, 8);
-  return __shfl(x, 0);
-}
 
 // grid = (max iterations, 2, n_problems)
 __global__ __launch_bounds__(kTvWave) void k_tv_hypothesis(TvView v) {
@@ -65,27 +58,7 @@ __global__ __launch_bounds__(kTvWave) void k_tv_hypothesis(TvView v) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) row[k] = lane - kTvRows == k ? 1.0 : 0.0;   // V; lanes 25..63 carry zeros
   }
-  for (int sweep = 0; sweep < kTvSweeps; ++sweep) {
-#pragma unroll
-    for (int p = 0; p < 8; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 9; ++q) {
-        const double alpha = tv_rows_sum(row[p] * row[p]), beta = tv_rows_sum(row[q] * row[q]), gamma = tv_rows_sum(row[p] * row[q]);
-        double c, s;
-        tv_rotation(alpha, beta, gamma, c, s);
-        tv_rotate_pair(row[p], row[q], c, s);
-      }
-  }
-  int best = 0;
-  double best_n = 0;
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    const double nj = tv_rows_sum(row[j] * row[j]);
-    if (j == 0 || nj < best_n) { best_n = nj; best = j; }
-  }
-  double mine = 0;
-#pragma unroll
-  for (int j = 0; j < 9; ++j) if (j == best) mine = row[j];
+  const double mine = null_vector_wave<9, kJacobiSweeps>(row, 9);
   float h[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) h[k] = (float)__shfl(mine, kTvRows + k);
@@ -274,41 +247,30 @@ static bool tv_all_finite(const float* p, size_t n) {
   return true;
 }
 
-static int tv_validate(int n_problems, const osh_two_view_problem* ps, size_t* total_m, size_t* total_i, int* max_iter) {
+static int tv_validate(int n_problems, const osh_two_view_problem* ps, RansacBatch& batch) {
   if (n_problems > OSH_TWOVIEW_MAX_PROBLEMS) { set_error("osh_orb_two_view_reconstruct: more than %d problems", OSH_TWOVIEW_MAX_PROBLEMS); return OSH_ERR_UNSUPPORTED; }
-  size_t M = 0, I = 0;
-  int mx = 0;
+  batch.base.reserve((size_t)n_problems);
   for (int k = 0; k < n_problems; ++k) {
     const osh_two_view_problem& p = ps[k];
     if (p.n_matches < 0 || p.n_iterations < 0 || p.n_keys1 < 0 || p.n_keys2 < 0) { set_error("problem %d: negative count", k); return OSH_ERR_INVALID; }
     if (p.n_matches > OSH_TWOVIEW_MAX_MATCHES) { set_error("problem %d: more than %d matches", k, OSH_TWOVIEW_MAX_MATCHES); return OSH_ERR_UNSUPPORTED; }
     if (p.n_iterations > OSH_TWOVIEW_MAX_ITERATIONS) { set_error("problem %d: more than %d iterations", k, OSH_TWOVIEW_MAX_ITERATIONS); return OSH_ERR_UNSUPPORTED; }
-    M += (size_t)p.n_matches; I += (size_t)p.n_iterations; mx = std::max(mx, p.n_iterations);
-    if (M > (size_t)OSH_TWOVIEW_MAX_TOTAL_MATCHES) { set_error("osh_orb_two_view_reconstruct: more than %d matches in one call", OSH_TWOVIEW_MAX_TOTAL_MATCHES); return OSH_ERR_UNSUPPORTED; }
-    if (I > (size_t)OSH_TWOVIEW_MAX_TOTAL_ITERATIONS) { set_error("osh_orb_two_view_reconstruct: more than %d iterations in one call", OSH_TWOVIEW_MAX_TOTAL_ITERATIONS); return OSH_ERR_UNSUPPORTED; }
+    batch.add(p.n_matches, p.n_iterations, 0);
+    if (batch.N > (size_t)OSH_TWOVIEW_MAX_TOTAL_MATCHES) { set_error("osh_orb_two_view_reconstruct: more than %d matches in one call", OSH_TWOVIEW_MAX_TOTAL_MATCHES); return OSH_ERR_UNSUPPORTED; }
+    if (batch.I > (size_t)OSH_TWOVIEW_MAX_TOTAL_ITERATIONS) { set_error("osh_orb_two_view_reconstruct: more than %d iterations in one call", OSH_TWOVIEW_MAX_TOTAL_ITERATIONS); return OSH_ERR_UNSUPPORTED; }
     if (!tv_all_finite(p.K, 9) || !tv_all_finite(p.T1, 9) || !tv_all_finite(p.T2, 9) || !std::isfinite(p.sigma)) { set_error("problem %d: K, T1, T2 or sigma not finite", k); return OSH_ERR_INVALID; }
     if (p.K[0] == 0.f || p.K[4] == 0.f) { set_error("problem %d: fx or fy is 0", k); return OSH_ERR_INVALID; }
     if (p.sigma == 0.f) { set_error("problem %d: sigma is 0", k); return OSH_ERR_INVALID; }
     const size_t n = (size_t)p.n_matches;
     if (n && (!p.idx1 || !p.idx2 || !p.pt1 || !p.pt2 || !p.pn1 || !p.pn2)) { set_error("problem %d: NULL match array with n_matches = %d", k, p.n_matches); return OSH_ERR_INVALID; }
-    if (p.n_iterations && !p.sets) { set_error("problem %d: NULL sets with n_iterations = %d", k, p.n_iterations); return OSH_ERR_INVALID; }
-    if (p.n_iterations && p.n_matches < 8) { set_error("problem %d: %d matches cannot fill a minimal set of 8", k, p.n_matches); return OSH_ERR_INVALID; }
     if (!tv_all_finite(p.pt1, n * 2) || !tv_all_finite(p.pt2, n * 2)) { set_error("problem %d: keypoint coordinate not finite", k); return OSH_ERR_INVALID; }
     if (!tv_all_finite(p.pn1, n * 2) || !tv_all_finite(p.pn2, n * 2)) { set_error("problem %d: normalised coordinate not finite", k); return OSH_ERR_INVALID; }
     for (size_t i = 0; i < n; ++i) {
       if (p.idx1[i] < 0 || p.idx1[i] >= p.n_keys1) { set_error("problem %d: match %zu: index %d outside [0, %d) of frame 1", k, i, p.idx1[i], p.n_keys1); return OSH_ERR_INVALID; }
       if (p.idx2[i] < 0 || p.idx2[i] >= p.n_keys2) { set_error("problem %d: match %zu: index %d outside [0, %d) of frame 2", k, i, p.idx2[i], p.n_keys2); return OSH_ERR_INVALID; }
     }
-    for (int it = 0; it < p.n_iterations; ++it) {
-      const int32_t* s = p.sets + 8 * (size_t)it;
-      for (int a = 0; a < 8; ++a) {
-        if (s[a] < 0 || s[a] >= p.n_matches) { set_error("problem %d: set %d: index %d outside [0, %d)", k, it, s[a], p.n_matches); return OSH_ERR_INVALID; }
-        for (int b = 0; b < a; ++b)
-          if (s[a] == s[b]) { set_error("problem %d: set %d repeats index %d", k, it, s[a]); return OSH_ERR_INVALID; }
-      }
-    }
+    OSH_TRY(validate_minimal_sets<8>("osh_orb_two_view_reconstruct", k, p.sets, p.n_iterations, p.n_matches, "matches"));
   }
-  *total_m = M; *total_i = I; *max_iter = mx;
   return OSH_OK;
 }
 
@@ -319,9 +281,8 @@ using namespace osh;
 extern "C" int osh_orb_two_view_reconstruct(osh_orb_ctx* c, int32_t n_problems, const osh_two_view_problem* ps, const osh_two_view_result* results) {
   PhaseClock clock;
   if (n_problems < 0 || (n_problems && (!ps || !results))) { set_error("osh_orb_two_view_reconstruct: bad arguments"); return OSH_ERR_INVALID; }
-  size_t M = 0, I = 0;
-  int max_iter = 0;
-  OSH_TRY(tv_validate(n_problems, ps, &M, &I, &max_iter));   // the problems first: a refusal needs no context and no device
+  RansacBatch batch;
+  OSH_TRY(tv_validate(n_problems, ps, batch));   // the problems first: a refusal needs no context and no device
   if (!c) { set_error("osh_orb_two_view_reconstruct: no context"); return OSH_ERR_INVALID; }
   if (n_problems == 0) return OSH_OK;
   int device = 0;
@@ -332,7 +293,7 @@ extern "C" int osh_orb_two_view_reconstruct(osh_orb_ctx* c, int32_t n_problems, 
   bool debug = false;
   for (int k = 0; k < n_problems; ++k) debug = debug || results[k].debug_model_n || results[k].debug_model || results[k].debug_score;
 
-  const size_t nP = (size_t)n_problems;
+  const size_t nP = (size_t)n_problems, M = batch.N, I = batch.I;
   Layout in, out, work;
   const auto s_prob = in.take<TvProblem>(nP);
   const auto s_pt1 = in.take<float2>(M); const auto s_pt2 = in.take<float2>(M);
@@ -350,20 +311,16 @@ extern "C" int osh_orb_two_view_reconstruct(osh_orb_ctx* c, int32_t n_problems, 
   OSH_TRY(st->call.reserve(in, out, work.bytes));
 
   char* h = st->call.host_in();
-  std::vector<size_t> base_m(nP), base_h(nP);
-  size_t bm = 0, bh = 0;
   for (int k = 0; k < n_problems; ++k) {
     const osh_two_view_problem& p = ps[k];
-    const size_t n = (size_t)p.n_matches, ni = (size_t)p.n_iterations;
-    base_m[k] = bm; base_h[k] = bh;
-    tv_fill_problem(s_prob.in(h)[k], p, (int)bm, (int)bh);
+    const size_t n = (size_t)p.n_matches, bm = batch.base[k].p;
+    tv_fill_problem(s_prob.in(h)[k], p, (int)bm, (int)batch.base[k].h);
     if (n) {
       std::memcpy(s_pt1.in(h) + bm, p.pt1, n * 8); std::memcpy(s_pt2.in(h) + bm, p.pt2, n * 8);
       std::memcpy(s_pn1.in(h) + bm, p.pn1, n * 8); std::memcpy(s_pn2.in(h) + bm, p.pn2, n * 8);
     }
-    if (ni) std::memcpy(s_sets.in(h) + bh * 8, p.sets, ni * 32);
-    bm += n; bh += ni;
   }
+  batch.stage_sets<8>(s_sets.in(h), ps);
   clock.mark();
   OSH_TRY(st->call.upload(s));
   OSH_TRY(clock.mark_synced(s));
@@ -378,8 +335,8 @@ extern "C" int osh_orb_two_view_reconstruct(osh_orb_ctx* c, int32_t n_problems, 
   v.mn = h_mn.in(dh); v.m = h_m.in(dh); v.score = h_score.in(dh); v.minv = w_minv.in(dw);
   v.inl = w_inl.in(dw); v.hx3d = w_x3d.in(dw); v.hcode = w_code.in(dw); v.hkey = w_key.in(dw);
   v.head = o_head.in(dout); v.out_inlier = o_inl.in(dout); v.out_tri = o_tri.in(dout); v.out_x3d = o_x3d.in(dout);
-  if (max_iter > 0) {
-    hipLaunchKernelGGL(k_tv_hypothesis, dim3((unsigned)max_iter, 2, (unsigned)n_problems), dim3(kTvWave), 0, s, v);
+  if (batch.max_iter > 0) {
+    hipLaunchKernelGGL(k_tv_hypothesis, dim3((unsigned)batch.max_iter, 2, (unsigned)n_problems), dim3(kTvWave), 0, s, v);
     OSH_TRY(launch_check("two-view hypotheses"));
   }
   hipLaunchKernelGGL(k_tv_select, dim3((unsigned)n_problems), dim3(kTvWave), 0, s, v);
@@ -393,12 +350,12 @@ extern "C" int osh_orb_two_view_reconstruct(osh_orb_ctx* c, int32_t n_problems, 
   const char* ho = st->call.host_out();
   for (int k = 0; k < n_problems; ++k) {
     const osh_two_view_result& r = results[k];
-    const size_t n = (size_t)ps[k].n_matches, ni = (size_t)ps[k].n_iterations;
+    const size_t n = (size_t)ps[k].n_matches, ni = (size_t)ps[k].n_iterations, bm = batch.base[k].p, bh = batch.base[k].h;
     tv_write_head(r, o_head.in(ho)[k]);
-    scatter(r.inlier, o_inl, ho, base_m[k], n); scatter(r.triangulated, o_tri, ho, base_m[k], n); scatter(r.x3d, o_x3d, ho, base_m[k], n, 3);
+    scatter(r.inlier, o_inl, ho, bm, n); scatter(r.triangulated, o_tri, ho, bm, n); scatter(r.x3d, o_x3d, ho, bm, n, 3);
     if (debug) {
-      scatter(r.debug_model_n, h_mn, ho, 2 * base_h[k], 2 * ni, 9); scatter(r.debug_model, h_m, ho, 2 * base_h[k], 2 * ni, 9);
-      scatter(r.debug_score, h_score, ho, 2 * base_h[k], 2 * ni);
+      scatter(r.debug_model_n, h_mn, ho, 2 * bh, 2 * ni, 9); scatter(r.debug_model, h_m, ho, 2 * bh, 2 * ni, 9);
+      scatter(r.debug_score, h_score, ho, 2 * bh, 2 * ni);
     }
   }
   clock.mark();

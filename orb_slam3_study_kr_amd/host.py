@@ -1120,7 +1120,7 @@ class MlpnpSolver:
                best_pose=None, best_flags=None) -> dict:
         """Walks a given answer of the device for the prepared round as iterate would."""
         n = self.state()["N"]
-        words = capi.mlpnp_mask_words(n)
+        words = capi.ransac_mask_words(n)
 
         def mask(flags):
             bits = np.zeros(words * 32, np.uint8)
@@ -1300,7 +1300,7 @@ class Sim3Solver:
     def keep(self, record, record_count, record_T, record_flags):
         """Hands the prepared round a given answer: the record iterations, their counts, transforms [k, 13] and flags [k, N]."""
         n = self.state()["N"]
-        words = capi.sim3r_mask_words(n)
+        words = capi.ransac_mask_words(n)
         record, record_count = np.ascontiguousarray(record, np.int32), np.ascontiguousarray(record_count, np.int32)
         T = np.ascontiguousarray(record_T, np.float32).reshape(-1, 13)
         bits = np.zeros((len(record), words * 32), np.uint8)

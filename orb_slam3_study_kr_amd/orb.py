@@ -218,13 +218,9 @@ class OrbMatcher:
     def mlpnp_check_inliers(self, problem, poses):
         """CheckInliers (src/MLPnPsolver.cpp:262-293) of the poses [k, 12] against a synth_mlpnp.Problem's correspondences
         (osh_orb_mlpnp_check_inliers): count [k], mask [k, words]."""
-        cp, _cr, _keep, _outs = mlpnp_args([problem])
-        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
-        count = np.zeros(poses.shape[0], np.int32)
-        mask = np.zeros((poses.shape[0], capi.mlpnp_mask_words(problem.n)), np.uint32)
-        capi.check(self.lib.osh_orb_mlpnp_check_inliers(self.ctx, cp, poses.shape[0], capi.ptr(poses, capi.c_double_p),
-                                                        capi.ptr(count, capi.c_int32_p), capi.ptr(mask, capi.c_uint32_p)),
-                   "osh_orb_mlpnp_check_inliers", self.lib)
+        rc, count, mask = _ransac_check_inliers(lambda *a: self.lib.osh_orb_mlpnp_check_inliers(self.ctx, *a), mlpnp_args, problem, poses,
+                                                np.float64, 12)
+        capi.check(rc, "osh_orb_mlpnp_check_inliers", self.lib)
         return count, mask
 
     def mlpnp_times(self):
@@ -246,13 +242,9 @@ class OrbMatcher:
     def sim3_ransac_check_inliers(self, problem, T12s):
         """CheckInliers (src/Sim3Solver.cc:415-439) of the transforms [k, 13] (R, t, s) against a synth_sim3_ransac.Problem's
         correspondences (osh_orb_sim3_ransac_check_inliers): count [k], mask [k, words]."""
-        cp, _cr, _keep, _outs = sim3_ransac_args([problem])
-        T = np.ascontiguousarray(T12s, np.float32).reshape(-1, 13)
-        count = np.zeros(T.shape[0], np.int32)
-        mask = np.zeros((T.shape[0], capi.sim3r_mask_words(problem.n)), np.uint32)
-        capi.check(self.lib.osh_orb_sim3_ransac_check_inliers(self.ctx, cp, T.shape[0], capi.ptr(T, capi.c_float_p),
-                                                              capi.ptr(count, capi.c_int32_p), capi.ptr(mask, capi.c_uint32_p)),
-                   "osh_orb_sim3_ransac_check_inliers", self.lib)
+        rc, count, mask = _ransac_check_inliers(lambda *a: self.lib.osh_orb_sim3_ransac_check_inliers(self.ctx, *a), sim3_ransac_args, problem,
+                                                T12s, np.float32, 13)
+        capi.check(rc, "osh_orb_sim3_ransac_check_inliers", self.lib)
         return count, mask
 
     def sim3_ransac_times(self):
@@ -1017,6 +1009,58 @@ def newpoint_cpu(segments, host_lib=None):
     return outs, float(ms.value)
 
 
+def mask_bits(mask, n: int) -> np.ndarray:
+    """The flags [.., n] of inlier mask words [.., words] (bit i % 32 of word i / 32 is correspondence i)."""
+    m = np.ascontiguousarray(mask, np.uint32)
+    bits = np.unpackbits(m.view(np.uint8).reshape(m.shape[:-1] + (-1,)), axis=-1, bitorder="little")
+    return bits[..., :n].astype(bool)
+
+
+mlpnp_mask_bits = mask_bits   # the name callers written against the MLPnP entry use
+
+
+def _ransac_outputs(res, a, o, fill, keep, outs):
+    """The tail of two_view_args, mlpnp_args and sim3_ransac_args for one problem: the output arrays o pre-filled with the byte
+    `fill` (None: left as they are) and wired into the result struct, o and the input arrays a appended to outs and keep."""
+    if fill is not None:
+        for v in o.values():
+            v.view(np.uint8)[...] = fill
+    _wire_outputs(res, o)
+    keep.append(a)
+    outs.append(o)
+
+
+def _ransac_cpu(symbol, args, problems, debug, host_lib):
+    """The host build of a RANSAC entry in one thread (`symbol` of the test library) on what `args` builds: the per-problem output
+    dicts and the wall time in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    cp, cr, _keep, outs = args(problems, debug)
+    ms = C.c_double(0)
+    rc = getattr(host_lib, symbol)(len(problems), cp, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"{symbol} -> {rc}")
+    return outs, float(ms.value)
+
+
+def _ransac_check_inliers(call, args, problem, transforms, dtype, width):
+    """CheckInliers of the transforms [k, width] against one problem through call(problem, k, transforms, count, mask): its return
+    code, count [k], mask [k, words]."""
+    cp, _cr, _keep, _outs = args([problem])
+    T = np.ascontiguousarray(transforms, dtype).reshape(-1, width)
+    count = np.zeros(T.shape[0], np.int32)
+    mask = np.zeros((T.shape[0], capi.ransac_mask_words(problem.n)), np.uint32)
+    rc = call(cp, T.shape[0], capi.ptr(T, _POINTER[np.dtype(dtype)]), capi.ptr(count, capi.c_int32_p), capi.ptr(mask, capi.c_uint32_p))
+    return rc, count, mask
+
+
+def _ransac_check_inliers_cpu(symbol, args, problem, transforms, dtype, width, host_lib):
+    """The same on the host (`symbol` of the test library): count [k], mask [k, words]."""
+    rc, count, mask = _ransac_check_inliers(getattr(host_lib or capi.load_host_library(), symbol), args, problem, transforms, dtype, width)
+    if rc != 0:
+        raise RuntimeError(f"{symbol} -> {rc}")
+    return count, mask
+
+
 _TWOVIEW_ARRAYS = (("idx1", np.int32), ("idx2", np.int32), ("pt1", np.float32), ("pt2", np.float32), ("pn1", np.float32),
                    ("pn2", np.float32), ("sets", np.int32))
 
@@ -1047,25 +1091,14 @@ def two_view_args(problems, debug: bool = False, fill=None):
         if debug:
             o.update(debug_model_n=np.zeros((2, it, 3, 3), f32), debug_model=np.zeros((2, it, 3, 3), f32), debug_score=np.zeros((2, it), f32),
                      debug_R=np.zeros((8, 3, 3), f32), debug_t=np.zeros((8, 3), f32))
-        if fill is not None:
-            for v in o.values():
-                v.view(np.uint8)[...] = fill
-        _wire_outputs(cr[k], o)
-        keep.append(a)
-        outs.append(o)
+        _ransac_outputs(cr[k], a, o, fill, keep, outs)
     return cp, cr, keep, outs
 
 
 def two_view_cpu(problems, debug: bool = False, host_lib=None):
     """csrc/two_view.h on the host in one thread (osh_host_two_view_cpu of the test library): the per-problem output dicts of
     two_view_reconstruct and the wall time in ms."""
-    host_lib = host_lib or capi.load_host_library()
-    cp, cr, _keep, outs = two_view_args(problems, debug)
-    ms = C.c_double(0)
-    rc = host_lib.osh_host_two_view_cpu(len(problems), cp, cr, C.byref(ms))
-    if rc != 0:
-        raise RuntimeError(f"osh_host_two_view_cpu -> {rc}")
-    return outs, float(ms.value)
+    return _ransac_cpu("osh_host_two_view_cpu", two_view_args, problems, debug, host_lib)
 
 
 _MLPNP_ARRAYS = (("bearing", np.float64), ("p3d", np.float64), ("p2d", np.float32), ("max_error", np.float32), ("sets", np.int32))
@@ -1089,7 +1122,7 @@ def mlpnp_args(problems, debug: bool = False, fill=None):
         c.min_inliers, c.best_inliers_in, c.best_refine_ok_in = int(pb.min_inliers), int(pb.best_inliers_in), int(pb.best_refine_ok_in)
         for name, dt in _MLPNP_ARRAYS:
             setattr(c, name, capi.ptr(a[name], _POINTER[np.dtype(dt)]))
-        i32, f64, words = np.int32, np.float64, capi.mlpnp_mask_words(n)
+        i32, f64, words = np.int32, np.float64, capi.ransac_mask_words(n)
         o = dict(first_hit=np.zeros(1, i32), hit_record=np.zeros(1, i32), hit_pose=np.zeros(12, f64), hit_count=np.zeros(1, i32),
                  hit_mask=np.zeros(words, np.uint32), best_iteration=np.zeros(1, i32), best_count=np.zeros(1, i32),
                  best_mask=np.zeros(words, np.uint32), best_pose=np.zeros(12, f64), best_refine_ok=np.zeros(1, i32),
@@ -1097,46 +1130,19 @@ def mlpnp_args(problems, debug: bool = False, fill=None):
                  debug_record_count=np.zeros(it, i32))
         if debug:
             o.update(debug_pose=np.zeros((it, 12), f64), debug_record_pose=np.zeros((it, 12), f64))
-        if fill is not None:
-            for v in o.values():
-                v.view(np.uint8)[...] = fill
-        _wire_outputs(cr[k], o)
-        keep.append(a)
-        outs.append(o)
+        _ransac_outputs(cr[k], a, o, fill, keep, outs)
     return cp, cr, keep, outs
 
 
 def mlpnp_cpu(problems, debug: bool = False, host_lib=None):
     """csrc/mlpnp.h on the host in one thread (osh_host_mlpnp_cpu of the test library): the per-problem output dicts of mlpnp_solve
     and the wall time in ms."""
-    host_lib = host_lib or capi.load_host_library()
-    cp, cr, _keep, outs = mlpnp_args(problems, debug)
-    ms = C.c_double(0)
-    rc = host_lib.osh_host_mlpnp_cpu(len(problems), cp, cr, C.byref(ms))
-    if rc != 0:
-        raise RuntimeError(f"osh_host_mlpnp_cpu -> {rc}")
-    return outs, float(ms.value)
+    return _ransac_cpu("osh_host_mlpnp_cpu", mlpnp_args, problems, debug, host_lib)
 
 
 def mlpnp_check_inliers_cpu(problem, poses, host_lib=None):
     """CheckInliers of csrc/mlpnp.h on the host (osh_host_mlpnp_check_inliers): count [k], mask [k, words]."""
-    host_lib = host_lib or capi.load_host_library()
-    cp, _cr, _keep, _outs = mlpnp_args([problem])
-    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
-    count = np.zeros(poses.shape[0], np.int32)
-    mask = np.zeros((poses.shape[0], capi.mlpnp_mask_words(problem.n)), np.uint32)
-    rc = host_lib.osh_host_mlpnp_check_inliers(cp, poses.shape[0], capi.ptr(poses, capi.c_double_p), capi.ptr(count, capi.c_int32_p),
-                                               capi.ptr(mask, capi.c_uint32_p))
-    if rc != 0:
-        raise RuntimeError(f"osh_host_mlpnp_check_inliers -> {rc}")
-    return count, mask
-
-
-def mlpnp_mask_bits(mask, n: int) -> np.ndarray:
-    """The flags [.., n] of mask words [.., words]."""
-    m = np.ascontiguousarray(mask, np.uint32)
-    bits = np.unpackbits(m.view(np.uint8).reshape(m.shape[:-1] + (-1,)), axis=-1, bitorder="little")
-    return bits[..., :n].astype(bool)
+    return _ransac_check_inliers_cpu("osh_host_mlpnp_check_inliers", mlpnp_args, problem, poses, np.float64, 12, host_lib)
 
 
 def mlpnp_stage(name: str, *args, host_lib=None):
@@ -1207,45 +1213,25 @@ def sim3_ransac_args(problems, debug: bool = False, fill=None):
         c.min_inliers, c.best_inliers_in = int(pb.min_inliers), int(pb.best_inliers_in)
         for name, dt in _SIM3R_ARRAYS:
             setattr(c, name, capi.ptr(a[name], _POINTER[np.dtype(dt)]))
-        i32, f32, words = np.int32, np.float32, capi.sim3r_mask_words(n)
+        i32, f32, words = np.int32, np.float32, capi.ransac_mask_words(n)
         o = dict(first_hit=np.zeros(1, i32), n_records=np.zeros(1, i32), record=np.zeros(it, i32), record_count=np.zeros(it, i32),
                  record_T=np.zeros((it, 13), f32), record_mask=np.zeros((it, words), np.uint32), best_iteration=np.zeros(1, i32),
                  best_count=np.zeros(1, i32), debug_count=np.zeros(it, i32))
         if debug:
             o.update(debug_T=np.zeros((it, 13), f32))
-        if fill is not None:
-            for v in o.values():
-                v.view(np.uint8)[...] = fill
-        _wire_outputs(cr[k], o)
-        keep.append(a)
-        outs.append(o)
+        _ransac_outputs(cr[k], a, o, fill, keep, outs)
     return cp, cr, keep, outs
 
 
 def sim3_ransac_cpu(problems, debug: bool = False, host_lib=None):
     """csrc/sim3_ransac.h on the host in one thread (osh_host_sim3r_cpu of the test library): the per-problem output dicts of
     sim3_ransac and the wall time in ms."""
-    host_lib = host_lib or capi.load_host_library()
-    cp, cr, _keep, outs = sim3_ransac_args(problems, debug)
-    ms = C.c_double(0)
-    rc = host_lib.osh_host_sim3r_cpu(len(problems), cp, cr, C.byref(ms))
-    if rc != 0:
-        raise RuntimeError(f"osh_host_sim3r_cpu -> {rc}")
-    return outs, float(ms.value)
+    return _ransac_cpu("osh_host_sim3r_cpu", sim3_ransac_args, problems, debug, host_lib)
 
 
 def sim3_ransac_check_inliers_cpu(problem, T12s, host_lib=None):
     """CheckInliers of csrc/sim3_ransac.h on the host (osh_host_sim3r_check_inliers): count [k], mask [k, words]."""
-    host_lib = host_lib or capi.load_host_library()
-    cp, _cr, _keep, _outs = sim3_ransac_args([problem])
-    T = np.ascontiguousarray(T12s, np.float32).reshape(-1, 13)
-    count = np.zeros(T.shape[0], np.int32)
-    mask = np.zeros((T.shape[0], capi.sim3r_mask_words(problem.n)), np.uint32)
-    rc = host_lib.osh_host_sim3r_check_inliers(cp, T.shape[0], capi.ptr(T, capi.c_float_p), capi.ptr(count, capi.c_int32_p),
-                                               capi.ptr(mask, capi.c_uint32_p))
-    if rc != 0:
-        raise RuntimeError(f"osh_host_sim3r_check_inliers -> {rc}")
-    return count, mask
+    return _ransac_check_inliers_cpu("osh_host_sim3r_check_inliers", sim3_ransac_args, problem, T12s, np.float32, 13, host_lib)
 
 
 def sim3_ransac_stage(name: str, *args, host_lib=None):

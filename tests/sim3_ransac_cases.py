@@ -6,7 +6,7 @@ import functools
 import numpy as np
 
 import sim3_ransac_numpy as s3n
-from orb_slam3_study_kr_amd import synth_sim3_ransac as ss
+from orb_slam3_study_kr_amd import orb, synth_sim3_ransac as ss
 
 SIZES = (3, 4, 63, 64, 65, 300)          # below, at and above one wavefront of correspondences, and several blocks of 64
 ITERATIONS = (1, 3, 300)
@@ -101,9 +101,8 @@ def transforms(pb, seed):
 
 def mask_bits(mask, n):
     """The flags [.., n] of mask words [.., words], and whether every bit beyond n is 0."""
-    m = np.ascontiguousarray(mask, np.uint32)
-    bits = np.unpackbits(m.view(np.uint8).reshape(m.shape[:-1] + (4 * m.shape[-1],)), axis=-1, bitorder="little")
-    return bits[..., :n].astype(bool), not bits[..., n:].any()
+    bits = orb.mask_bits(mask, 32 * np.shape(mask)[-1])
+    return bits[..., :n], not bits[..., n:].any()
 
 
 def assert_self_consistent(pb, out):

@@ -63,7 +63,7 @@ def assert_self_consistent(pb, o, what):
     hit, best = int(o["hit_record"][0]), int(o["best_iteration"][0])
     if hit >= 0:
         assert np.array_equal(o["hit_pose"].view(np.uint64), o["debug_record_pose"][hit].view(np.uint64)), what
-        flags = orb.mlpnp_mask_bits(o["hit_mask"], n)
+        flags = orb.mask_bits(o["hit_mask"], n)
         assert int(flags.sum()) == int(o["hit_count"][0]), what
         if pb.camera_type == sm.PINHOLE:
             assert np.array_equal(flags, numpy_flags(pb, o["hit_pose"])), what
@@ -71,7 +71,7 @@ def assert_self_consistent(pb, o, what):
         assert not o["hit_pose"].any() and not o["hit_mask"].any() and int(o["hit_count"][0]) == 0, what
     if best >= 0:
         assert np.array_equal(o["best_pose"].view(np.uint64), o["debug_pose"][best].view(np.uint64)), what
-        flags = orb.mlpnp_mask_bits(o["best_mask"], n)
+        flags = orb.mask_bits(o["best_mask"], n)
         assert int(flags.sum()) == int(o["best_count"][0]) == int(o["debug_count"][best]), what
         if pb.camera_type == sm.PINHOLE:
             assert np.array_equal(flags, numpy_flags(pb, o["best_pose"])), what
@@ -79,7 +79,7 @@ def assert_self_consistent(pb, o, what):
         assert not o["best_pose"].any() and not o["best_mask"].any(), what
     # mask bits beyond n stay 0
     for name in ("hit_mask", "best_mask"):
-        assert not orb.mlpnp_mask_bits(o[name], 32 * o[name].shape[0])[n:].any(), what
+        assert not orb.mask_bits(o[name], 32 * o[name].shape[0])[n:].any(), what
 
 
 # ------------------------------------------------------------------------------------------------------------ scoring
@@ -89,12 +89,12 @@ def test_scoring_pinhole_equals_numpy_bit_for_bit(matcher, n):
     rng = np.random.RandomState(n)
     poses = np.stack([pb.pose] + [perturbed(pb.pose, rng, s) for s in (1e-6, 1e-4, 2e-3, 1e-2, 1e-1, 1.0)])
     count, mask = matcher.mlpnp_check_inliers(pb, poses)
-    flags = orb.mlpnp_mask_bits(mask, n)
+    flags = orb.mask_bits(mask, n)
     for k, pose in enumerate(poses):
         want = numpy_flags(pb, pose)
         assert np.array_equal(flags[k], want), f"pose {k}"
         assert count[k] == want.sum()
-    assert not orb.mlpnp_mask_bits(mask, 32 * mask.shape[1])[:, n:].any()
+    assert not orb.mask_bits(mask, 32 * mask.shape[1])[:, n:].any()
     assert 0 < count[3] and count[6] < count[0] == pb.inlier.sum()   # the poses span all-inliers-found to almost none
 
 
@@ -109,7 +109,7 @@ def test_scoring_kb8_equals_numpy_away_from_the_threshold(matcher, n):
         assert np.all(np.abs(e2.astype(np.float64) - pb.max_error) > 1e-3 * pb.max_error), "a point lies near its threshold"
         want.append(flags)
     count, mask = matcher.mlpnp_check_inliers(pb, poses)
-    assert np.array_equal(orb.mlpnp_mask_bits(mask, n), np.stack(want))
+    assert np.array_equal(orb.mask_bits(mask, n), np.stack(want))
     assert np.array_equal(count, np.stack(want).sum(1))
     assert np.array_equal(want[0], pb.inlier)
 
@@ -172,7 +172,7 @@ def test_refine_pose_meets_the_measured_bound(matcher, kind):
     pb = mc.scene(kind)
     o = matcher.mlpnp_solve([pb], debug=True)[0]
     assert int(o["first_hit"][0]) >= 0 and int(o["hit_record"][0]) >= 0
-    flags = orb.mlpnp_mask_bits(o["best_mask"], pb.n)
+    flags = orb.mask_bits(o["best_mask"], pb.n)
     assert np.array_equal(flags, pb.inlier)
     idx = np.flatnonzero(flags)
     rot, trans = mn.pose_difference(o["hit_pose"], mn.compute_pose(pb.bearing[idx], pb.p3d[idx]))
@@ -227,7 +227,7 @@ def test_end_to_end_against_the_truth(matcher, camera, noise):
     bound = mc.DEVICE_BOUND["general"] if noise == 0.0 else tuple(2 * v for v in NUMPY_VS_TRUTH[camera])
     for name, o in (("device", matcher.mlpnp_solve([pb])[0]), ("host build", orb.mlpnp_cpu([pb])[0][0])):
         assert int(o["first_hit"][0]) >= 0 and int(o["best_refine_ok"][0]) == 1, name
-        assert np.array_equal(orb.mlpnp_mask_bits(o["hit_mask"], pb.n), pb.inlier), name
+        assert np.array_equal(orb.mask_bits(o["hit_mask"], pb.n), pb.inlier), name
         assert int(o["hit_count"][0]) == pb.inlier.sum() > pb.min_inliers
         rot, trans = mn.pose_difference(o["hit_pose"], pb.pose)
         print(f"{name}, camera {camera}, noise {noise}: against truth: rotation {rot:.3e} rad, translation {trans:.3e}; bound {bound}")
@@ -272,4 +272,4 @@ def test_largest_problem_the_entry_accepts(matcher):
     o = matcher.mlpnp_solve([pb], debug=True, fill=0xCD)[0]
     assert_self_consistent(pb, o, "2048 correspondences")
     assert int(o["first_hit"][0]) >= 0
-    assert np.array_equal(orb.mlpnp_mask_bits(o["hit_mask"], pb.n), pb.inlier)
+    assert np.array_equal(orb.mask_bits(o["hit_mask"], pb.n), pb.inlier)

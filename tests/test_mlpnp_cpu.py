@@ -203,7 +203,7 @@ def test_check_inliers_pinhole_bit_for_bit(n):
     nan = pb.pose.copy(); nan[3] = np.nan
     poses.append(nan)
     count, mask = orb.mlpnp_check_inliers_cpu(pb, np.stack(poses))
-    flags = orb.mlpnp_mask_bits(mask, n)
+    flags = orb.mask_bits(mask, n)
     for k, pose in enumerate(poses):
         want = mn.check_inliers(pb.camera_type, pb.camera, pose, pb.p3d, pb.p2d, pb.max_error)
         assert np.array_equal(flags[k], want) and count[k] == want.sum(), f"pose {k}"
@@ -269,11 +269,42 @@ def test_host_build_end_to_end(camera):
     pb = mc.end_to_end(camera, 0.5)
     o = orb.mlpnp_cpu([pb], debug=True)[0][0]
     assert int(o["first_hit"][0]) >= 0
-    assert np.array_equal(orb.mlpnp_mask_bits(o["hit_mask"], pb.n), pb.inlier)
+    assert np.array_equal(orb.mask_bits(o["hit_mask"], pb.n), pb.inlier)
     for k in range(pb.sets.shape[0]):
         flags = mn.check_inliers(pb.camera_type, pb.camera, o["debug_pose"][k], pb.p3d, pb.p2d, pb.max_error)
         if camera == sm.PINHOLE:
             assert int(flags.sum()) == o["debug_count"][k]
-    idx = np.flatnonzero(orb.mlpnp_mask_bits(o["best_mask"], pb.n))
+    idx = np.flatnonzero(orb.mask_bits(o["best_mask"], pb.n))
     rot, trans = mn.pose_difference(o["hit_pose"], mn.compute_pose(pb.bearing[idx], pb.p3d[idx]))
     assert rot <= mc.HOST_VS_NUMPY["general"][0] and trans <= mc.HOST_VS_NUMPY["general"][1]
+
+
+# ------------------------------------------------------------------------------------------------------------ refusals
+def test_refusals_need_no_device():
+    """osh_orb_mlpnp_solve looks at the problems before it asks for a context: with a null context every refusal comes back with
+    its return code and its message, the second problem named."""
+    import dataclasses
+    from orb_slam3_study_kr_amd import capi
+    lib = capi.load_library()
+    pb = sm.make_problem(seed=4, n=65, iterations=3)
+    repeats = pb.sets.copy(); repeats[1, 5] = repeats[1, 0]
+    outside = pb.sets.copy(); outside[2, 0] = 65
+    five = dataclasses.replace(pb, bearing=pb.bearing[:5], p3d=pb.p3d[:5], p2d=pb.p2d[:5], max_error=pb.max_error[:5],
+                               sets=np.tile(np.arange(6, dtype=np.int32) % 5, (1, 1)))
+    bad = [(dataclasses.replace(pb, sets=repeats), "osh_orb_mlpnp_solve: problem 1: set 1 repeats index", capi.OSH_ERR_INVALID),
+           (dataclasses.replace(pb, sets=outside), "osh_orb_mlpnp_solve: problem 1: set 2: index 65 outside [0, 65)", capi.OSH_ERR_INVALID),
+           (five, "osh_orb_mlpnp_solve: problem 1: 5 correspondences cannot fill a minimal set of 6", capi.OSH_ERR_INVALID)]
+    for problem, message, code in bad:
+        cp, cr, _keep, _outs = orb.mlpnp_args([pb, problem])
+        assert lib.osh_orb_mlpnp_solve(None, 2, cp, cr) == code
+        assert message in capi.last_error(lib)
+    cp, cr, _keep, _outs = orb.mlpnp_args([pb, pb])
+    cp[1].sets = None
+    assert lib.osh_orb_mlpnp_solve(None, 2, cp, cr) == capi.OSH_ERR_INVALID
+    assert "osh_orb_mlpnp_solve: problem 1: NULL sets with n_iterations = 3" in capi.last_error(lib)
+    cp, cr, _keep, _outs = orb.mlpnp_args([pb] * (capi.OSH_MLPNP_MAX_PROBLEMS + 1))
+    assert lib.osh_orb_mlpnp_solve(None, capi.OSH_MLPNP_MAX_PROBLEMS + 1, cp, cr) == capi.OSH_ERR_UNSUPPORTED
+    assert "osh_orb_mlpnp_solve: more than 64 problems" in capi.last_error(lib)
+    # what is valid gets as far as the context
+    cp, cr, _keep, _outs = orb.mlpnp_args([pb])
+    assert lib.osh_orb_mlpnp_solve(None, 1, cp, cr) == capi.OSH_ERR_INVALID and "no context" in capi.last_error(lib)

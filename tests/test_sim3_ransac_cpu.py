@@ -211,7 +211,7 @@ def test_refusals_need_no_device():
     assert "more than 64 problems" in capi.last_error(lib)
     # the scoring entry refuses the same points, and too many transforms
     T = np.zeros((capi.OSH_SIM3R_MAX_ITERATIONS + 1, 13), np.float32)
-    count, mask = np.zeros(len(T), np.int32), np.zeros((len(T), capi.sim3r_mask_words(pb.n)), np.uint32)
+    count, mask = np.zeros(len(T), np.int32), np.zeros((len(T), capi.ransac_mask_words(pb.n)), np.uint32)
     cp, cr, _keep, _outs = orb.sim3_ransac_args([pb])
     args = (capi.ptr(T, capi.c_float_p), capi.ptr(count, capi.c_int32_p), capi.ptr(mask, capi.c_uint32_p))
     assert lib.osh_orb_sim3_ransac_check_inliers(None, cp, len(T), *args) == capi.OSH_ERR_UNSUPPORTED and "more than 1024 transforms" in capi.last_error(lib)

@@ -329,3 +329,33 @@ def test_reconstruct_answers_beyond_the_device_limits():
         assert np.array_equal(got["triangulated"][pb.idx1], cpu["triangulated"])
         unmatched = scene.matches12 < 0
         assert not got["p3d"][unmatched].any() and not got["triangulated"][unmatched].any()
+
+
+def test_refusals_need_no_device():
+    """osh_orb_two_view_reconstruct looks at the problems before it asks for a context: with a null context every refusal comes
+    back with its return code and its message, entry and problem named."""
+    import dataclasses
+    lib = capi.load_library()
+    scene = case("general")[0]
+    pb = st.problem(scene, 3, head=65)
+    repeats = pb.sets.copy(); repeats[1, 7] = repeats[1, 0]
+    outside = pb.sets.copy(); outside[2, 0] = 65
+    seven = st.problem(scene, 1, head=7, sets=np.tile(np.arange(8, dtype=np.int32) % 7, (1, 1)))
+    bad = [(dataclasses.replace(pb, sets=repeats), "osh_orb_two_view_reconstruct: problem 1: set 1 repeats index", capi.OSH_ERR_INVALID),
+           (dataclasses.replace(pb, sets=outside), "osh_orb_two_view_reconstruct: problem 1: set 2: index 65 outside [0, 65)", capi.OSH_ERR_INVALID),
+           (seven, "osh_orb_two_view_reconstruct: problem 1: 7 matches cannot fill a minimal set of 8", capi.OSH_ERR_INVALID)]
+    for problem, message, code in bad:
+        cp, cr, _keep, _outs = orb.two_view_args([pb, problem])
+        assert lib.osh_orb_two_view_reconstruct(None, 2, cp, cr) == code
+        assert message in capi.last_error(lib)
+    cp, cr, _keep, _outs = orb.two_view_args([pb, pb])
+    cp[1].sets = None
+    assert lib.osh_orb_two_view_reconstruct(None, 2, cp, cr) == capi.OSH_ERR_INVALID
+    assert "osh_orb_two_view_reconstruct: problem 1: NULL sets with n_iterations = 3" in capi.last_error(lib)
+    few = st.problem(scene, 0, head=8)
+    cp, cr, _keep, _outs = orb.two_view_args([few] * (capi.OSH_TWOVIEW_MAX_PROBLEMS + 1))
+    assert lib.osh_orb_two_view_reconstruct(None, capi.OSH_TWOVIEW_MAX_PROBLEMS + 1, cp, cr) == capi.OSH_ERR_UNSUPPORTED
+    assert "osh_orb_two_view_reconstruct: more than 4096 problems" in capi.last_error(lib)
+    # what is valid gets as far as the context
+    cp, cr, _keep, _outs = orb.two_view_args([pb])
+    assert lib.osh_orb_two_view_reconstruct(None, 1, cp, cr) == capi.OSH_ERR_INVALID and "no context" in capi.last_error(lib)
