@@ -306,9 +306,17 @@ int osh_lba_get_plan_stats(osh_lba_ctx* ctx, int64_t stats[8]);
  * stats = {items, symmetric items, records, contributions, rhs contributions, MFMA instructions
  * per pass, useful 6x6 products per pass, reduce entries}. */
 int osh_lba_schur_plan_stats(const osh_lba_problem* problem, int64_t stats[8]);
+/* The same check of the plan cut at item_max landmarks per item (8 .. 256), whatever the environment says: the plan of any size
+ * class of calls (osh_lba_pack_cuts) on one window.  item_max <= 0: as osh_lba_schur_plan_stats. */
+int osh_lba_schur_plan_stats_cut(const osh_lba_problem* problem, int item_max, int64_t stats[8]);
+
+/* Host-only: how finely a call of n_windows windows cuts its work: cuts = {landmarks per Schur item, edges per landmark chunk}.
+ * They follow the size class of the call (1-2 windows: 24 / 256, 3-8: 32 / 512, 9-128: 64 / 1024, more: 256 / 1024); use_env != 0
+ * applies the tuning aids OSH_LBA_ITEM_MAX / OSH_LBA_CHUNK_EDGES as osh_lba_upload does, which reads them once per call. */
+int osh_lba_pack_cuts(int32_t n_windows, int use_env, int32_t cuts[2]);
 
 /* Host-only (needs no GPU): the item shapes of the Schur plan of `problem` cut at item_max landmarks per item (<= 0: what a call
- * with one window uses): hist[((sym * 9 + nx) * 9 + ny) * 65 + landmarks] = number of such items (2 * 9 * 9 * 65 entries), and
+ * with one window uses; at most 256): hist[((sym * 9 + nx) * 9 + ny) * 257 + landmarks] = number of such items (2 * 9 * 9 * 257 entries), and
  * cycles = matrix-pipe cycles of one pass {with whole 16x16x4 tiles, with the symmetric items' four-block instructions} at 64 / 17
  * cycles per instruction. */
 int osh_lba_schur_plan_shapes(const osh_lba_problem* problem, int item_max, int64_t* hist, int64_t cycles[2]);
@@ -326,6 +334,10 @@ int osh_lba_schur_block_list(int sym, int nx, int ny, int use_blocks, int32_t* o
  * contributions, chunks, staging bytes, merged left/right edge pairs, reduce entries}; *pack_ms (may be NULL) = wall time
  * of the packing. */
 int osh_lba_pack_check(int32_t n_windows, const osh_lba_problem* problems, int32_t n_threads, int64_t stats[8], double* pack_ms);
+/* The same check of the batch cut at item_max landmarks per Schur item (8 .. 256) and chunk_edges edges per landmark chunk (256, 512,
+ * 1024), whatever the environment says; a value <= 0 is what an upload of n_windows windows uses. */
+int osh_lba_pack_check_cut(int32_t n_windows, const osh_lba_problem* problems, int32_t n_threads, int32_t item_max, int32_t chunk_edges,
+                           int64_t stats[8], double* pack_ms);
 
 /* Host-only self check of the packer osh_liba_solve and the inertial debug exports run before their one copy (needs no GPU):
  * window offsets, landmark-major edge order with a rig's left + right pairs, the pose-by-pose walk order, the (landmark, pose) ->

@@ -622,6 +622,9 @@ _SIGNATURES = {
     "osh_lba_set_pack_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "osh_lba_pack_compare": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(LbaProblem), c_int64_p]),
     "osh_lba_schur_plan_stats": (C.c_int, [C.POINTER(LbaProblem), c_int64_p]),
+    "osh_lba_schur_plan_stats_cut": (C.c_int, [C.POINTER(LbaProblem), C.c_int, c_int64_p]),
+    "osh_lba_pack_cuts": (C.c_int, [C.c_int32, C.c_int, c_int32_p]),
+    "osh_lba_pack_check_cut": (C.c_int, [C.c_int32, C.POINTER(LbaProblem), C.c_int32, C.c_int32, C.c_int32, c_int64_p, c_double_p]),
     "osh_lba_schur_plan_shapes": (C.c_int, [C.POINTER(LbaProblem), C.c_int, c_int64_p, c_int64_p]),
     "osh_lba_schur_block_list": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p]),
     "osh_lba_pack_check": (C.c_int, [C.c_int32, C.POINTER(LbaProblem), C.c_int32, c_int64_p, c_double_p]),

@@ -1821,11 +1821,12 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
   else if (const char* e = std::getenv("OSH_LBA_PACK")) on_device = on_device && std::strcmp(e, "host") != 0;
   else on_device = on_device && nw >= kDevicePackMinWindows;
   c->device_packed = on_device;
+  const PackCuts cuts = pack_cuts(nw);   // the environment is read here, once per upload
   if (on_device) {
-    const int rc = device_pack_batch(c->dpack, s, nw, pr, default_pack_threads(nw), pb, c->d_arena, c->d_ptwin);
+    const int rc = device_pack_batch(c->dpack, s, nw, pr, default_pack_threads(nw), cuts, pb, c->d_arena, c->d_ptwin);
     if (rc != OSH_OK) { set_error("%s", pb.msg); return rc; }
   } else {
-    const int rc = pack_batch(nw, pr, [&](int which, size_t bytes) { return c->h_arena[which].reserve(bytes); }, default_pack_threads(nw), pb);
+    const int rc = pack_batch(nw, pr, [&](int which, size_t bytes) { return c->h_arena[which].reserve(bytes); }, default_pack_threads(nw), cuts, pb);
     if (rc != OSH_OK) { set_error("%s", pb.msg); return rc; }
   }
   const auto t1 = std::chrono::steady_clock::now();

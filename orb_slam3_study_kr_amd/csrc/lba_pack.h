@@ -34,9 +34,21 @@ constexpr int kChunkMaxEdges = 1024;   // edges of one chunk at most (= one bloc
 // Edges per chunk for a batch of nw windows: a call with one or two windows spreads its landmark-major kernels over four times as
 // many blocks (a config-2 window: 74 blocks of 1024 edges take 11-12 us per launch, 300 of 256 edges ...), as item_max_lm() does for the
 // Schur items.  A multiple of kChunkEdges.
-inline int chunk_max_edges(int nw) {
+constexpr int chunk_edges_tier(int nw) { return nw <= 2 ? 256 : (nw <= 8 ? 512 : kChunkMaxEdges); }
+inline int chunk_max_edges(int nw) {   // (reads the environment: call it once per upload, not per window)
   if (const char* e = std::getenv("OSH_LBA_CHUNK_EDGES")) { const int v = std::atoi(e); if (v >= kChunkEdges && v <= kChunkMaxEdges && v % kChunkEdges == 0) return v; }   // (tuning aid)
-  return nw <= 2 ? 256 : (nw <= 8 ? 512 : kChunkMaxEdges);
+  return chunk_edges_tier(nw);
+}
+// How finely one call cuts its work: landmarks per Schur item, edges per landmark chunk.  Both follow the number of windows of the
+// call (the size classes: 1-2, 3-8, 9-kItemBatchWindows, more); the partial sums of a window follow them.
+struct PackCuts { int item_max, chunk_edges; };
+// The cuts of a call of nw windows, read ONCE per upload and handed down to the packing threads.  item_max / chunk_edges > 0 take the
+// place of the environment and the size class (the host checks); an invalid value counts as not given.
+inline PackCuts pack_cuts(int nw, int item_max = 0, int chunk_edges = 0) {
+  PackCuts c;
+  c.item_max = (item_max >= 8 && item_max <= kItemMaxLm) ? item_max : item_max_lm(nw);
+  c.chunk_edges = (chunk_edges >= kChunkEdges && chunk_edges <= kChunkMaxEdges && chunk_edges % kChunkEdges == 0) ? chunk_edges : chunk_max_edges(nw);
+  return c;
 }
 
 // internal edge kinds of the sorted edge list (the C-ABI kinds OSH_EDGE_* plus the merged rig edge)
@@ -192,8 +204,8 @@ inline void pack_pose(const double* in7, double* out7) {
   for (int k = 0; k < 3; ++k) out7[4 + k] = in7[4 + k];
 }
 
-inline int pack_batch(int nw, const osh_lba_problem* pr, const std::function<void*(int, size_t)>& alloc, int n_threads, PackedBatch& pb,
-                      bool allow_f32 = true) {
+inline int pack_batch(int nw, const osh_lba_problem* pr, const std::function<void*(int, size_t)>& alloc, int n_threads, const PackCuts cuts,
+                      PackedBatch& pb, bool allow_f32 = true) {
   using namespace pack_detail;
   if (pack_describe(nw, pr, pb) != OSH_OK) return pb.err;
   auto fail = [&](int code, const char* fmt, auto... a) {
@@ -311,7 +323,7 @@ inline int pack_batch(int nw, const osh_lba_problem* pr, const std::function<voi
     d.E = n_sorted;
     // Schur work plan on the old numbering (schur_plan.h)
     L.recs.reserve((size_t)p.n_points + p.n_points / 4);
-    if (!plan_window(w, p.n_free, p.n_points, old_lmo.data(), nfree.data(), tmp_epose.data(), L.builds, L.recs, L.plan, sc.plan, item_max_lm(nw)))
+    if (!plan_window(w, p.n_free, p.n_points, old_lmo.data(), nfree.data(), tmp_epose.data(), L.builds, L.recs, L.plan, sc.plan, cuts.item_max))
       return lfail(OSH_ERR_UNSUPPORTED, "window %d: a landmark has more than 254 optimisable observers", w);
     // renumber the landmarks in the order of the plan's owner records (symmetric builds, in build order)
     std::vector<int>& old2new = sc.old2new;
@@ -363,9 +375,9 @@ inline int pack_batch(int nw, const osh_lba_problem* pr, const std::function<voi
     for (const plan_detail::Build& bd : L.builds) {
       if (bd.sym) { L.n_sym++; L.recs_sym += bd.n_rec; } else { L.n_cross++; L.recs_cross += bd.n_rec; }
     }
-    // chunks of the landmark-major kernels: consecutive landmarks, <= chunk_max_edges(nw) edges and <= kBlock landmarks (a single
+    // chunks of the landmark-major kernels: consecutive landmarks, <= cuts.chunk_edges edges and <= kBlock landmarks (a single
     // landmark with more edges gets its own multi-pass chunk)
-    const int chunk_edges = chunk_max_edges(nw);
+    const int chunk_edges = cuts.chunk_edges;
     int j = 0;
     while (j < p.n_points) {
       int j1 = j + 1;
@@ -386,7 +398,7 @@ inline int pack_batch(int nw, const osh_lba_problem* pr, const std::function<voi
     for (std::thread& t : pool) t.join();
   }
   for (int w = 0; w < nw; ++w) if (locals[w].err != OSH_OK) return fail(locals[w].err, "%s", locals[w].msg);
-  if (pb.rec_f32 && inexact.load()) return pack_batch(nw, pr, alloc, n_threads, pb, false);
+  if (pb.rec_f32 && inexact.load()) return pack_batch(nw, pr, alloc, n_threads, cuts, pb, false);
 
   // ---- phase 2: offsets of the plan sections, then a parallel merge
   struct WOff { size_t chunk, sym_item, cross_item, sym_rec, cross_rec, rblk, crange; int contrib, ccontrib; };

@@ -11,17 +11,24 @@
 
 using namespace osh;
 
-extern "C" int osh_lba_pack_check(int32_t nw, const osh_lba_problem* pr, int32_t n_threads, int64_t stats[8], double* pack_ms) {
+// item_max / chunk_edges > 0: the batch cut at that many landmarks per Schur item / edges per landmark chunk (any size class,
+// checked without the environment); <= 0: what an upload of nw windows uses (lba_pack.h:pack_cuts).
+extern "C" int osh_lba_pack_check_cut(int32_t nw, const osh_lba_problem* pr, int32_t n_threads, int32_t item_max, int32_t chunk_edges, int64_t stats[8], double* pack_ms) {
   if (nw <= 0 || !pr || !stats) { set_error("osh_lba_pack_check: bad arguments"); return OSH_ERR_INVALID; }
+  if ((item_max > 0 && (item_max < 8 || item_max > kItemMaxLm)) || (chunk_edges > 0 && (chunk_edges < kChunkEdges || chunk_edges > kChunkMaxEdges || chunk_edges % kChunkEdges))) {
+    set_error("osh_lba_pack_check_cut: item_max %d outside 8..%d or chunk_edges %d not a multiple of %d up to %d", item_max, kItemMaxLm, chunk_edges, kChunkEdges, kChunkMaxEdges);
+    return OSH_ERR_INVALID;
+  }
+  const PackCuts cuts = pack_cuts(nw, item_max, chunk_edges);
   void* mem[2] = {nullptr, nullptr};
   size_t cap[2] = {0, 0};
   PackedBatch pb;
   // grow-only staging like the upload's pinned arenas; the timed pass is the second one (staging already touched)
   auto alloc = [&](int which, size_t bytes) { if (bytes > cap[which]) { std::free(mem[which]); mem[which] = std::malloc(bytes); cap[which] = bytes; } return mem[which]; };
   const int nt = n_threads > 0 ? n_threads : default_pack_threads(nw);
-  int rc = pack_batch(nw, pr, alloc, nt, pb);
+  int rc = pack_batch(nw, pr, alloc, nt, cuts, pb);
   const auto t0 = std::chrono::steady_clock::now();
-  if (rc == OSH_OK && pack_ms) rc = pack_batch(nw, pr, alloc, nt, pb);
+  if (rc == OSH_OK && pack_ms) rc = pack_batch(nw, pr, alloc, nt, cuts, pb);
   const auto t1 = std::chrono::steady_clock::now();
   if (pack_ms) *pack_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
   auto done = [&](int code) { std::free(mem[0]); std::free(mem[1]); return code; };
@@ -101,7 +108,7 @@ extern "C" int osh_lba_pack_check(int32_t nw, const osh_lba_problem* pr, int32_t
     for (int c = 0; c < d.n_chunks; ++c) {
       const Chunk& ch = chunks[d.chunk_off + c];
       CHECK(ch.win == w && ch.lm0 == next_lm && ch.lm1 > ch.lm0 && (ch.lm1 - ch.lm0) <= kBlock, "window %d: chunk %d", w, c);
-      CHECK(ch.lm1 - ch.lm0 == 1 || lmo[ch.lm1] - lmo[ch.lm0] <= kChunkMaxEdges, "window %d: chunk %d too long", w, c);
+      CHECK(ch.lm1 - ch.lm0 == 1 || lmo[ch.lm1] - lmo[ch.lm0] <= cuts.chunk_edges, "window %d: chunk %d too long", w, c);
       next_lm = ch.lm1;
     }
     CHECK(next_lm == p.n_points, "window %d: chunks do not cover the landmarks", w);
@@ -116,6 +123,7 @@ extern "C" int osh_lba_pack_check(int32_t nw, const osh_lba_problem* pr, int32_t
     CHECK(sym == (it < pb.n_sym) && I.win >= 0 && I.win < nw, "item %zu: symmetry / window", it);
     const WinDesc& d = pb.win[I.win];
     const int* lmo = lmoff + d.lmoff_off;
+    CHECK(I.n_lm >= 1 && I.n_lm <= cuts.item_max, "item %zu: %d landmarks, cut at %d", it, I.n_lm, cuts.item_max);
     if (sym && I.win != next_owner_w) { next_owner_w = I.win; next_owner_lm = 0; }
     for (int r = 0; r < I.n_lm; ++r) {
       const SRec& R = recs[(size_t)I.rec_off + r];
@@ -144,4 +152,8 @@ extern "C" int osh_lba_pack_check(int32_t nw, const osh_lba_problem* pr, int32_t
   stats[0] = (int64_t)pb.n_items; stats[1] = (int64_t)pb.n_sym; stats[2] = (int64_t)pb.n_recs; stats[3] = (int64_t)pb.n_contrib;
   stats[4] = (int64_t)pb.n_chunks; stats[5] = (int64_t)(pb.arena_bytes[0] + pb.arena_bytes[1]); stats[6] = merged; stats[7] = (int64_t)pb.n_rblk;
   return done(OSH_OK);
+}
+
+extern "C" int osh_lba_pack_check(int32_t nw, const osh_lba_problem* pr, int32_t n_threads, int64_t stats[8], double* pack_ms) {
+  return osh_lba_pack_check_cut(nw, pr, n_threads, 0, 0, stats, pack_ms);
 }

@@ -29,8 +29,8 @@ struct DevPackState {
 bool device_pack_supported(int nw, const osh_lba_problem* pr);
 
 // Packs `nw` problems into d_arena[0..1] (layout of PackedBatch, host pointers pb.arena[] stay null) and d_ptwin (window of every
-// landmark).  Returns pb.err; message in pb.msg.  Synchronises `s` (the staging may be reused on return).
-int device_pack_batch(DevPackState& st, hipStream_t s, int nw, const osh_lba_problem* pr, int n_threads, PackedBatch& pb, DevBuf* d_arena, DevBuf& d_ptwin);
+// landmark), cut as `cuts` says (lba_pack.h:pack_cuts).  Returns pb.err; message in pb.msg.  Synchronises `s` (the staging may be reused on return).
+int device_pack_batch(DevPackState& st, hipStream_t s, int nw, const osh_lba_problem* pr, int n_threads, PackCuts cuts, PackedBatch& pb, DevBuf* d_arena, DevBuf& d_ptwin);
 
 // Test hook: packs with both packers and compares every section; stats[0..3] = bytes compared, sections compared, items, records.
 int device_pack_compare(DevPackState& st, hipStream_t s, int nw, const osh_lba_problem* pr, int64_t stats[4]);

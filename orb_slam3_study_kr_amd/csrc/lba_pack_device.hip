@@ -466,7 +466,7 @@ __device__ __forceinline__ u64 pack_slots_dev(const unsigned short* S, int ns, c
 }
 
 // The greedy merge of schur_plan.h:plan_window (one thread): consecutive keys whose pose sets unite to <= 8 poses without
-// changing the tile count share an item; an item takes at most 64 units.  KF(q, g): word q of the g-th smallest key, CF(g): its units.
+// changing the tile count share an item; an item takes at most item_max units.  KF(q, g): word q of the g-th smallest key, CF(g): its units.
 template <class KeyF, class CntF>
 __device__ void greedy_items(int ng, KeyF KF, CntF CF, DBuild* builds, int* wk, int* out5, const int item_max) {
   int* curX = wk; int* curY = wk + 16; int* gX = wk + 32; int* gY = wk + 40; int* ux = wk + 48; int* uy = wk + 64;
@@ -729,7 +729,7 @@ __global__ __launch_bounds__(NT, 8) void k_pack_pre2(PackArgs a) {
       sh_n[9] = ns;
     }
     __syncthreads();
-    // spans -> items of at most 64 units, in order (symmetric spans come first: key word 0 sorts them so)
+    // spans -> items of at most item_max units, in order (symmetric spans come first: key word 0 sorts them so)
     const int ns = sh_n[9];
     int carry_b = 0;
     for (int base = 0; base < ns; base += NT) {
@@ -823,25 +823,25 @@ __global__ __launch_bounds__(NT, 8) void k_pack_pre2(PackArgs a) {
     const DBuild bd = z.builds[b];
     const int nx = bd.shape & 0xff, ny = (bd.shape >> 8) & 0xff;
     const bool sym = (bd.shape >> 16) & 1;
-    u64 xs = ~0ull, ys = ~0ull;
-    if (lane < bd.n) {
-      const int p = bd.base + lane;
+    unsigned lo = 0, hi = 0, cl = 0;
+    for (int q0 = lane; q0 < bd.n; q0 += 64) {   // (an item has up to kItemMaxLm units: several rounds of 64 lanes)
+      const int p = bd.base + q0;
       const int lm = z.plm[p], ab = z.pab[p];
       const int pa = ab & 0xff, pb = ab >> 8;
       const int k = s.nfree[lm];
       const int* obs = s.sepose + s.lmo[lm];
-      xs = pack_slots_dev(bd.X, nx, obs, pa * kItemPoses, min(k, pa * kItemPoses + kItemPoses));
-      ys = pack_slots_dev(bd.Y, ny, obs, pb * kItemPoses, min(k, pb * kItemPoses + kItemPoses));
+      const u64 xs = pack_slots_dev(bd.X, nx, obs, pa * kItemPoses, min(k, pa * kItemPoses + kItemPoses));
+      const u64 ys = pack_slots_dev(bd.Y, ny, obs, pb * kItemPoses, min(k, pb * kItemPoses + kItemPoses));
       z.uxs[p] = xs; z.uys[p] = ys;
+      unsigned xp = 0, yp = 0;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) { if (((xs >> (8 * q)) & 0xff) != kAbsent) xp |= 1u << q; if (((ys >> (8 * q)) & 0xff) != kAbsent) yp |= 1u << q; }
+      u64 live = 0;
+#pragma unroll
+      for (int sa = 0; sa < 8; ++sa)
+        if (xp & (1u << sa)) live |= (u64)(yp & (sym ? (0xffu << sa) & 0xffu : 0xffu)) << (8 * sa);
+      lo |= (unsigned)live; hi |= (unsigned)(live >> 32); cl |= sym ? xp : 0u;
     }
-    unsigned xp = 0, yp = 0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { if (((xs >> (8 * q)) & 0xff) != kAbsent) xp |= 1u << q; if (((ys >> (8 * q)) & 0xff) != kAbsent) yp |= 1u << q; }
-    u64 live = 0;
-#pragma unroll
-    for (int sa = 0; sa < 8; ++sa)
-      if (xp & (1u << sa)) live |= (u64)(yp & (sym ? (0xffu << sa) & 0xffu : 0xffu)) << (8 * sa);
-    unsigned lo = (unsigned)live, hi = (unsigned)(live >> 32), cl = sym ? xp : 0u;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { lo |= (unsigned)__shfl_xor((int)lo, o, 64); hi |= (unsigned)__shfl_xor((int)hi, o, 64); cl |= (unsigned)__shfl_xor((int)cl, o, 64); }
     if (lane == 0) {
@@ -985,8 +985,8 @@ __global__ __launch_bounds__(NT) void k_pack_post(PackArgs a) {
       a.a_posex[it * 8 + lane] = bd.X[lane] == 0xffff ? -1 : (int)bd.X[lane];
       a.a_posey[it * 8 + lane] = bd.Y[lane] == 0xffff ? -1 : (int)bd.Y[lane];
     }
-    if (lane < bd.n) {
-      const int p = bd.base + lane;
+    for (int q0 = lane; q0 < bd.n; q0 += 64) {   // (up to kItemMaxLm records)
+      const int p = bd.base + q0;
       const int lm = z.plm[p], ab = z.pab[p];
       const int pa = ab & 0xff, pb = ab >> 8;
       const int k = s.nfree[lm];
@@ -998,7 +998,7 @@ __global__ __launch_bounds__(NT) void k_pack_post(PackArgs a) {
       r.x_lo = (unsigned)xs; r.x_hi = (unsigned)(xs >> 32); r.y_lo = (unsigned)ys; r.y_hi = (unsigned)(ys >> 32);
       r.flags = ((pa == 0 && pb == 0) ? (1 | (min(k, kItemPoses) << 8)) : 0) | (a0 << 16) | ((a1 - a0) << 24);
       r.pad = z.lmo_new[jn + 1] - z.lmo_new[jn];
-      a.a_recs[(size_t)rec0 + lane] = r;
+      a.a_recs[(size_t)rec0 + q0] = r;
     }
     if ((bd.live >> lane) & 1) t.ent[t.bpre[b] + __popcll(bd.live & ((1ull << lane) - 1ull))] = (b << 6) | lane;
     if (lane < 8 && ((bd.clive >> lane) & 1)) t.cent[t.cpre[b] + __popc((unsigned)bd.clive & ((1u << lane) - 1u))] = (b << 3) | lane;
@@ -1062,7 +1062,7 @@ void parallel_windows(int nw, int n_threads, F f) {
 
 }  // namespace
 
-int device_pack_batch(DevPackState& st, hipStream_t s, int nw, const osh_lba_problem* pr, int n_threads, PackedBatch& pb, DevBuf* d_arena, DevBuf& d_ptwin) {
+int device_pack_batch(DevPackState& st, hipStream_t s, int nw, const osh_lba_problem* pr, int n_threads, const PackCuts cuts, PackedBatch& pb, DevBuf* d_arena, DevBuf& d_ptwin) {
   const auto t0 = std::chrono::steady_clock::now();
   if (pack_describe(nw, pr, pb) != OSH_OK) return pb.err;
   auto fail = [&](int code, const char* fmt, auto... a) {
@@ -1199,8 +1199,8 @@ int device_pack_batch(DevPackState& st, hipStream_t s, int nw, const osh_lba_pro
   a.r_pose = reinterpret_cast<const double*>(dr + o_pose); a.r_cam = reinterpret_cast<const double*>(dr + o_cam); a.r_pt = reinterpret_cast<const double*>(dr + o_pt);
   a.r_epose = reinterpret_cast<const int*>(dr + o_ep); a.r_epoint = reinterpret_cast<const int*>(dr + o_el); a.r_kind = dr + o_kind; a.r_rec = dr + o_rec;
   a.rec_f32 = f32 ? 1 : 0;
-  a.item_max = item_max_lm(nw);
-  a.chunk_edges = chunk_max_edges(nw);
+  a.item_max = cuts.item_max;
+  a.chunk_edges = cuts.chunk_edges;
   a.s1 = st.d_s1.as<int>();
   mark(2);
   hipLaunchKernelGGL(k_pack_pre1, dim3((unsigned)nw), dim3(NT), 0, s, a);
@@ -1309,9 +1309,10 @@ int device_pack_batch(DevPackState& st, hipStream_t s, int nw, const osh_lba_pro
 int device_pack_compare(DevPackState& st, hipStream_t s, int nw, const osh_lba_problem* pr, int64_t stats[4]) {
   PackedBatch pd, ph;
   DevBuf d_arena[2], d_ptwin;
-  if (device_pack_batch(st, s, nw, pr, default_pack_threads(nw), pd, d_arena, d_ptwin) != OSH_OK) { set_error("device packer: %s", pd.msg); return pd.err; }
+  const PackCuts cuts = pack_cuts(nw);
+  if (device_pack_batch(st, s, nw, pr, default_pack_threads(nw), cuts, pd, d_arena, d_ptwin) != OSH_OK) { set_error("device packer: %s", pd.msg); return pd.err; }
   std::vector<unsigned char> hmem[2];
-  if (pack_batch(nw, pr, [&](int which, size_t bytes) { hmem[which].resize(bytes); return (void*)hmem[which].data(); }, default_pack_threads(nw), ph) != OSH_OK) {
+  if (pack_batch(nw, pr, [&](int which, size_t bytes) { hmem[which].resize(bytes); return (void*)hmem[which].data(); }, default_pack_threads(nw), cuts, ph) != OSH_OK) {
     set_error("host packer: %s", ph.msg);
     return ph.err;
   }

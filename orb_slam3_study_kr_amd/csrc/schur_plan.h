@@ -27,15 +27,22 @@
 namespace osh {
 
 constexpr int kItemPoses = 8;     // row / column poses of one item
-constexpr int kItemMaxLm = 64;    // landmarks per item at most (load balance; partial sums are per item)
+constexpr int kItemMaxLm = 256;   // landmarks per item at most (a wavefront walks an item's chunks in turn; partial sums are per item)
+constexpr int kItemBatchWindows = 128;   // calls with more windows than this cut their items at kItemMaxLm
 // Landmarks per item for a batch of nw windows.  One wavefront walks an item's chunks one after the other, so in a call with one or two
 // windows -- the live-SLAM pattern, where every item has a CU to itself anyway -- an item of 64 landmarks is the latency of the Schur
 // launches (28 us per launch for the cross items of a config-2 window): such calls cut their items at 24 landmarks, up to eight
-// windows at 32.  More items mean more 6x6 contributions for k_schur_reduce and k_pose_reduce, which is why a large batch keeps 64
-// (one config-2 window, optimize(): 2.55 ms at 64, 2.40 at 32, 2.34 at 24, 2.37 at 16, 2.41 at 8).
-inline int item_max_lm(int nw) {
+// windows at 32, up to kItemBatchWindows at 64 (one config-2 window, optimize(): 2.55 ms at 64, 2.40 at 32, 2.34 at 24, 2.37 at 16,
+// 2.41 at 8).  Every item pays costs that do not depend on its length -- a chain of dependent loads before its first chunk, staging its
+// poses, the store epilogue, the rhs / Hpp reductions, and one 6x6 contribution per live pose pair that k_schur_reduce reads back -- and a
+// call of more than kItemBatchWindows windows has tens of items per wavefront slot whatever the cut (a config-2 window: 301 symmetric
+// items and 7836 contributions at 64, 141 and 4467 at 256, 135 and 4365 uncut; the longest item: 8, 32 and 81 chunks), so such calls
+// cut at 256 (DESIGN.md section 4 has the measured table).  The partial sums of S, b_s and Hpp follow the cut: a window's last bits
+// (about 1e-9 relative) depend on the size class of the call it is solved in, not on its place in the call.
+constexpr int item_max_tier(int nw) { return nw <= 2 ? 24 : (nw <= 8 ? 32 : (nw <= kItemBatchWindows ? 64 : kItemMaxLm)); }
+inline int item_max_lm(int nw) {   // (reads the environment: call it once per upload, not per window)
   if (const char* e = std::getenv("OSH_LBA_ITEM_MAX")) { const int v = std::atoi(e); if (v >= 8 && v <= kItemMaxLm) return v; }   // (tuning aid)
-  return nw <= 2 ? 24 : (nw <= 8 ? 32 : kItemMaxLm);
+  return item_max_tier(nw);
 }
 constexpr unsigned kAbsent = 0xffu;
 

@@ -4,6 +4,7 @@
 // contribution slot is written by exactly one (item, pose pair) and lies in the range of its block
 // of S, and that every landmark has exactly one dinv owner.  Needs no GPU.
 #include "common.h"
+#include "lba_pack.h"
 #include "schur_plan.h"
 #include <map>
 #include <set>
@@ -46,7 +47,7 @@ static int build_window_plan(const osh_lba_problem* p, int item_max, WindowPlan&
   return OSH_OK;
 }
 
-// Shapes of the plan of one window (needs no GPU): hist[sym][nx][ny][landmarks] = items of that shape ([2][9][9][65]), and the
+// Shapes of the plan of one window (needs no GPU): hist[sym][nx][ny][landmarks] = items of that shape ([2][9][9][kItemMaxLm + 1]), and the
 // matrix-pipe cycles of one pass with whole tiles and with the four-block instructions of the symmetric items, at the 64 and 17
 // cycles per instruction that profiles/ubench/mfma_f64_blocks.hip measured.  item_max <= 0: what a call with one window uses.
 extern "C" int osh_lba_schur_plan_shapes(const osh_lba_problem* p, int item_max, int64_t* hist, int64_t cycles[2]) {
@@ -54,12 +55,12 @@ extern "C" int osh_lba_schur_plan_shapes(const osh_lba_problem* p, int item_max,
   if (item_max > kItemMaxLm) { set_error("osh_lba_schur_plan_shapes: item_max %d > %d", item_max, kItemMaxLm); return OSH_ERR_INVALID; }
   WindowPlan wp;
   if (const int rc = build_window_plan(p, item_max > 0 ? item_max : item_max_lm(1), wp)) return rc;
-  std::fill(hist, hist + 2 * 9 * 9 * 65, (int64_t)0);
+  std::fill(hist, hist + 2 * 9 * 9 * (kItemMaxLm + 1), (int64_t)0);
   cycles[0] = cycles[1] = 0;
   for (const SItem& I : wp.plan.items) {
     const int nx = I.shape & 0xff, ny = (I.shape >> 8) & 0xff, sym = (I.shape >> 16) & 1;
-    if (nx > 8 || ny > 8 || I.n_lm > 64) { set_error("plan: item of shape (%d, %d), %d landmarks", nx, ny, I.n_lm); return OSH_ERR_DEVICE; }
-    hist[((sym * 9 + nx) * 9 + ny) * 65 + I.n_lm]++;
+    if (nx > 8 || ny > 8 || I.n_lm > kItemMaxLm) { set_error("plan: item of shape (%d, %d), %d landmarks", nx, ny, I.n_lm); return OSH_ERR_DEVICE; }
+    hist[((sym * 9 + nx) * 9 + ny) * (kItemMaxLm + 1) + I.n_lm]++;
     const long long ksteps = 6 * (long long)((I.n_lm + 7) / 8);
     const SchurStep t = schur_step(sym, nx, ny, false), b = schur_step(sym, nx, ny, true);
     cycles[0] += ksteps * (64 * t.tiles + 17 * t.blocks);
@@ -86,12 +87,14 @@ extern "C" int osh_lba_schur_block_list(int sym, int nx, int ny, int use_blocks,
   return OSH_OK;
 }
 
-extern "C" int osh_lba_schur_plan_stats(const osh_lba_problem* p, int64_t stats[8]) {
+// item_max > 0: the plan cut at that many landmarks per item (8 .. kItemMaxLm: the plan of any size class, checked without the
+// environment); <= 0: what a call with one window uses, item_max_lm(1), which OSH_LBA_ITEM_MAX overrides.
+extern "C" int osh_lba_schur_plan_stats_cut(const osh_lba_problem* p, int item_max, int64_t stats[8]) {
   if (!p || !stats) { set_error("osh_lba_schur_plan_stats: NULL argument"); return OSH_ERR_INVALID; }
+  if (item_max > 0 && (item_max < 8 || item_max > kItemMaxLm)) { set_error("osh_lba_schur_plan_stats_cut: item_max %d outside 8..%d", item_max, kItemMaxLm); return OSH_ERR_INVALID; }
   const int P = p->n_free, L = p->n_points;
-  // (a call with one window cuts its items at item_max_lm(1) landmarks; OSH_LBA_ITEM_MAX overrides it: the tests run the check at 8, 24 and 64)
   WindowPlan wp;
-  if (const int rc = build_window_plan(p, item_max_lm(1), wp)) return rc;
+  if (const int rc = build_window_plan(p, item_max > 0 ? item_max : item_max_lm(1), wp)) return rc;
   const std::vector<std::vector<int>>& obs = wp.obs;
   const std::vector<int>&lmo = wp.lmo, &nfree = wp.nfree;
   const SchurPlan& plan = wp.plan;
@@ -165,5 +168,16 @@ extern "C" int osh_lba_schur_plan_stats(const osh_lba_problem* p, int64_t stats[
   stats[0] = (int64_t)plan.items.size(); stats[1] = plan.n_sym; stats[2] = (int64_t)plan.recs.size();
   stats[3] = (int64_t)plan.n_contrib; stats[4] = (int64_t)plan.n_ccontrib; stats[5] = plan.tile_steps; stats[6] = plan.pair_blocks;
   stats[7] = (int64_t)plan.rblk.size();
+  return OSH_OK;
+}
+
+extern "C" int osh_lba_schur_plan_stats(const osh_lba_problem* p, int64_t stats[8]) { return osh_lba_schur_plan_stats_cut(p, 0, stats); }
+
+// Landmarks per Schur item / edges per landmark chunk of a call of n_windows windows (the size classes of schur_plan.h:item_max_tier
+// and lba_pack.h:chunk_edges_tier; use_env != 0: with the tuning aids OSH_LBA_ITEM_MAX / OSH_LBA_CHUNK_EDGES applied, as an upload does).
+extern "C" int osh_lba_pack_cuts(int32_t n_windows, int use_env, int32_t cuts[2]) {
+  if (n_windows <= 0 || !cuts) { set_error("osh_lba_pack_cuts: bad arguments"); return OSH_ERR_INVALID; }
+  cuts[0] = use_env ? item_max_lm(n_windows) : item_max_tier(n_windows);
+  cuts[1] = use_env ? chunk_max_edges(n_windows) : chunk_edges_tier(n_windows);
   return OSH_OK;
 }

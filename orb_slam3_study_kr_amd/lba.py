@@ -269,12 +269,46 @@ class LbaSolver:
         return {capi.KERNEL_NAMES[k]: (int(launches[k]), float(ms[k])) for k in range(capi.OSH_K_COUNT)}
 
 
+ITEM_MAX_LM = 256   # csrc/schur_plan.h:kItemMaxLm
+
+
+def pack_cuts(n_windows: int, use_env: bool = False) -> tuple[int, int]:
+    """(landmarks per Schur item, edges per landmark chunk) of a call of n_windows windows: its size class, or with use_env what an
+    upload would use under OSH_LBA_ITEM_MAX / OSH_LBA_CHUNK_EDGES."""
+    lib = capi.load_library()
+    out = np.zeros(2, dtype=np.int32)
+    capi.check(lib.osh_lba_pack_cuts(int(n_windows), int(use_env), capi.ptr(out, capi.c_int32_p)), "osh_lba_pack_cuts", lib)
+    return int(out[0]), int(out[1])
+
+
+def schur_plan_check(window: LbaWindow, item_max: int = 0) -> dict:
+    """Host-only check of the Schur plan of one window cut at item_max landmarks per item (0: a one-window call's): raises on a
+    plan that does not cover every observer pair exactly once, returns its statistics."""
+    lib = capi.load_library()
+    pr = window.as_struct()
+    st = np.zeros(8, dtype=np.int64)
+    capi.check(lib.osh_lba_schur_plan_stats_cut(C.byref(pr), int(item_max), capi.ptr(st, capi.c_int64_p)), "osh_lba_schur_plan_stats_cut", lib)
+    return dict(items=int(st[0]), sym_items=int(st[1]), records=int(st[2]), contributions=int(st[3]), rhs_contributions=int(st[4]),
+                mfma_per_pass=int(st[5]), useful_blocks=int(st[6]), reduce_entries=int(st[7]))
+
+
+def pack_check(windows, item_max: int = 0, chunk_edges: int = 0, threads: int = 0) -> dict:
+    """Host-only check of the batch packer on `windows`, cut as given (0: as an upload of that many windows)."""
+    lib = capi.load_library()
+    arr = (capi.LbaProblem * len(windows))(*[w.as_struct() for w in windows])
+    st = np.zeros(8, dtype=np.int64)
+    capi.check(lib.osh_lba_pack_check_cut(len(windows), arr, int(threads), int(item_max), int(chunk_edges), capi.ptr(st, capi.c_int64_p), None),
+               "osh_lba_pack_check_cut", lib)
+    return dict(items=int(st[0]), sym_items=int(st[1]), records=int(st[2]), contributions=int(st[3]), chunks=int(st[4]),
+                staging_bytes=int(st[5]), merged_pairs=int(st[6]), reduce_entries=int(st[7]))
+
+
 def schur_plan_shapes(window: LbaWindow, item_max: int = 0) -> tuple[dict, int, int]:
     """Item shapes of the Schur plan of one window, on the CPU: ({(sym, nx, ny, landmarks): items}, matrix-pipe cycles of one pass
     with whole tiles, the same with the symmetric items' four-block instructions).  item_max 0: what a call with one window uses."""
     lib = capi.load_library()
     pr = window.as_struct()
-    hist = np.zeros((2, 9, 9, 65), dtype=np.int64)
+    hist = np.zeros((2, 9, 9, ITEM_MAX_LM + 1), dtype=np.int64)
     cyc = np.zeros(2, dtype=np.int64)
     capi.check(lib.osh_lba_schur_plan_shapes(C.byref(pr), int(item_max), capi.ptr(hist, capi.c_int64_p), capi.ptr(cyc, capi.c_int64_p)),
                "osh_lba_schur_plan_shapes", lib)
