@@ -29,7 +29,7 @@ const char* get_error();
 
 // The solvers that run on an osh_lba_ctx besides the visual BA (pose_device.hip, posei_device.hip, sim3opt_device.hip,
 // liba_device.hip and the pose graphs of pgo_env.h) share its device and stream, and keep their staging and work buffers in its
-// attachment slots (a StagedCall each, PgoBuffers for the pose graphs; defined in lba_device.hip).
+// attachment slots (a StagedCall each, PgoBuffers for the pose graphs; defined in lba_device.hip, the driver of the kernels in lba_*.h).
 enum LbaAttachSlot { kAttachLiba = 0, kAttachPose = 1, kAttachPosei = 2, kAttachPgo = 3, kAttachSim3 = 4, kAttachCount };
 // The context's device (made current) and stream.
 int lba_stream(osh_lba_ctx* c, int* device, hipStream_t* stream);

@@ -1,6 +1,7 @@
 """Python driver over the local-BA C-ABI (include/orbslam3_hip.h, osh_lba_*).
 
-Thin plumbing only: every number is computed by the HIP kernels in csrc/lba_device.hip.
+Thin plumbing only: every number is computed by the HIP kernels that csrc/lba_device.hip launches
+(csrc/lba_lm_kernels.h, lba_schur_items.h, lba_reduce_solve.h).
 """
 from __future__ import annotations
 

@@ -1,4 +1,4 @@
-"""Symmetric Schur items from 4 x 4 blocks (csrc/lba_device.hip:k_schur_fused<true, false, true>): the diagonal tiles and the ragged
+"""Symmetric Schur items from 4 x 4 blocks (csrc/lba_schur_items.h:k_schur_fused<true, false, true>): the diagonal tiles and the ragged
 last tile column of a symmetric pinhole item are formed with v_mfma_f64_4x4x4_4b_f64 over the k sequence of the whole tiles, so every
 entry of S keeps its bits.  Nine small windows of 1 ... 8 and 12 optimisable keyframes, each uploaded alone, which together hold
 symmetric items of every number of row poses, of one to three chunks (8 x 8 lanes; one and two in the 12 x 5 and 16 x 4 mappings, whose

@@ -1,4 +1,4 @@
-"""Cross items of the Schur plan (parts a < b of tracks with 9-13 optimisable observers, csrc/lba_device.hip:k_schur_fused<false, false>):
+"""Cross items of the Schur plan (parts a < b of tracks with 9-13 optimisable observers, csrc/lba_schur_items.h:k_schur_fused<false, false>):
 the column side of an item with at most four column poses is formed for two chunks of 8 landmarks in one 16 x 4 pass.  Windows of 14
 optimisable + 2 fixed keyframes whose landmarks are all seen by 9-13 optimisable keyframes, so that the cross items carry every block
 of S they touch; each window is checked to contain the chunk shapes it is named after (a Python restatement of the cross-item part of

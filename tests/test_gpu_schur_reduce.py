@@ -1,4 +1,4 @@
-"""k_schur_reduce (csrc/lba_device.hip): in a call of more than 8 windows 18 lanes reduce one block of S (or one rhs segment) of the
+"""k_schur_reduce (csrc/lba_reduce_solve.h): in a call of more than 8 windows 18 lanes reduce one block of S (or one rhs segment) of the
 batch's block list, two entries per lane, 14 blocks per 256 threads; in a call of at most 8 windows 36 lanes, one entry per lane, 7 per
 256 threads (k_schur_reduce_deep).  Which blocks share a wavefront and a thread block, and with which other window's blocks, depends on
 where the window stands in the batch and on nothing else, so a window's S, b_s and its whole optimisation must not depend on the order

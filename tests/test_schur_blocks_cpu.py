@@ -1,4 +1,4 @@
-"""Symmetric Schur items from 4 x 4 blocks (csrc/lba_device.hip:k_schur_fused<true, false, true>, csrc/schur_plan.h:schur_step /
+"""Symmetric Schur items from 4 x 4 blocks (csrc/lba_schur_items.h:k_schur_fused<true, false, true>, csrc/schur_plan.h:schur_step /
 schur_instr_list), checked on the CPU through the host-only exports osh_lba_schur_block_list and osh_lba_schur_plan_shapes: the
 instructions of one k step store every entry of every live pose pair exactly once, at exactly the places the whole-tile path stores,
 for every item shape; the plan statistic counts them; and the headline window's matrix-pipe cycles are the ones DESIGN.md section 8(1)
