@@ -23,6 +23,22 @@ class ORBextractor {
   std::vector<cv::KeyPoint> DistributeOctTree(const std::vector<cv::KeyPoint>& vToDistributeKeys, const int& minX, const int& maxX,
                                               const int& minY, const int& maxY, const int& nFeatures, const int& level);
 
+  /* ADD THIS MEMBER to the reference's class: DistributeOctTree with the same arguments and the same result, as one
+   * osh_orb_octree_distribute call (csrc/orb_octree_device.hip).  Beyond the call's limits, without a context or on a device error
+   * the same statements run on the host (osh::octree_distribute_host of csrc/orb_octree.h) after a message on stderr */
+  std::vector<cv::KeyPoint> DistributeOctTreeDevice(const std::vector<cv::KeyPoint>& vToDistributeKeys, const int& minX, const int& maxX,
+                                                    const int& minY, const int& maxY, const int& nFeatures, const int& level);
+
+  /* ADD THIS MEMBER too: operator() of several extractors as ONE osh_orb_extract call (csrc/orb_extract_device.hip), for example
+   * the left and the right extractor of a stereo frame: image i goes through extractor i, vKeypoints[i] / vDescriptors[i] /
+   * vMonoIndex[i] are what operator() would leave in _keypoints / _descriptors and return (-1 for an empty image), with
+   * vLappingAreas[i] as its vLappingArea.  The candidates stay on the device between the detector and the descriptors, and the
+   * quadtree is the rule of include/orbslam3_hip.h, not DistributeOctTree.  Every extractor's mnPyramidToken names its levels on
+   * the device; mvImagePyramid is filled as ComputePyramid fills it when bKeepPyramid is set and left with empty levels when not */
+  static void ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
+                           std::vector<std::vector<cv::KeyPoint> >& vKeypoints, std::vector<cv::Mat>& vDescriptors,
+                           const std::vector<std::vector<int> >& vLappingAreas, std::vector<int>& vMonoIndex, bool bKeepPyramid = true);
+
   std::vector<cv::Point> pattern;   /* the 512 sampling points, filled by the constructor */
 
   int nfeatures = 0;

@@ -1356,6 +1356,77 @@ typedef struct osh_fast_resident_frame {
 } osh_fast_resident_frame;
 int osh_orb_fast_detect_resident(osh_orb_ctx* ctx, int32_t n_frames, const osh_fast_resident_frame* frames, osh_fast_result* results);
 
+/* ------------------------------------------------- the quadtree of the candidates (ORBextractor::DistributeOctTree) */
+/*
+ * ORBextractor::DistributeOctTree (src/ORBextractor.cc:480-779) for n_lists (frame, level) lists in one call: which of a level's
+ * FAST candidates ComputeKeyPointsOctTree keeps.  The rule is stated here once; csrc/orb_octree.h is its device and host build.
+ *
+ * Inputs per list: n candidates (x, y, response) in float32, in input order, relative to (minX, minY); W = maxX - minX and
+ * H = maxY - minY; N, the number of features wanted.
+ *
+ * Roots: nIni = round((float)W / (float)H) (C round, halves away from zero), hX = (float)W / nIni; root i has UL.x = (int)(hX * (float)i),
+ * UR.x = (int)(hX * (float)(i + 1)) and rows [0, H).  A candidate goes to root (int)(x / hX), a float32 division, truncated.  Empty
+ * roots are dropped; a root with one key is a leaf.
+ *
+ * Divide: halfX = ceil((UR.x - UL.x) / 2), halfY likewise, mx = UL.x + halfX, my = UL.y + halfY; the children in order are n1
+ * left-top, n2 right-top, n3 left-bottom, n4 right-bottom.  A key goes left when x < (float)mx and top when y < (float)my; nothing else
+ * is tested, so keys outside their box are legal and follow the comparisons.  Key order inside a child is the parent's order.  A
+ * child with exactly one key is a leaf.
+ *
+ * The list is ordered: non-empty children are pushed to the FRONT in the order n1, n2, n3, n4 and the divided node is erased.
+ *
+ * Round A: walk the list front to back and divide every non-leaf; E collects the children with more than one key, in push order.
+ * Finish when size >= N or size == prevSize (the size before the round); otherwise go to round B when size + 3 |E| > N, and run
+ * another round A when not.  The first round runs for any N.
+ *
+ * Round B: sort E ascending by (key count, UL.x) and walk it from the back: divide the node, push its children, collect those with
+ * more than one key into a new E, erase the node, and break as soon as size >= N.  Afterwards finish when size >= N or
+ * size == prevSize; otherwise run round B again with the new E.
+ *
+ * Result: per node, in list order front to back, the key with the largest response; among equal responses the first in key order,
+ * which is the smallest input index.  The count is at most max(N + 3, 4 nIni).
+ *
+ * Kept as the reference has it: when every key of a lone root falls into one quadrant the list does not grow, the
+ * size == prevSize rule ends the walk and one keypoint is kept; two candidates on one pixel end by the same rule.
+ * Intended deviations: nIni == 0 (W < H / 2, where the reference divides by zero) is taken as 1; a root index equal to nIni (the
+ * reference indexes past its vector) is taken as nIni - 1; entries of E equal in both sort keys keep their order in E, a stable
+ * sort (the reference's std::sort leaves their order to the library once there are more than 16 entries).
+ *
+ * results[k].index receives the kept input indices in result order and n_out their count; when n_out > capacity the count is
+ * written, the array is not, and the call still returns OSH_OK: size the array and call again.  status is OSH_OK, or the code the
+ * call returns when the list reached one of the kernel's loop bounds (csrc/orb_octree.h derives them; no valid input does).
+ *
+ * Refused before any device work and without a context, which stays usable: with OSH_ERR_INVALID a negative count or capacity, a
+ * NULL array whose count is not 0, width or height <= 0 or above OSH_FAST_MAX_SIDE, a candidate whose x, y or response is not
+ * finite, whose x is outside [0, width) or whose y is negative; with OSH_ERR_UNSUPPORTED n_features above OSH_OCTREE_MAX_FEATURES,
+ * more than OSH_OCTREE_MAX_CANDIDATES candidates in a list, or nIni above OSH_OCTREE_MAX_ROOTS.
+ * OSH_OCTREE_MAX_ROOTS is a limit of the kernel, not of the rule: the first round may leave 4 nIni nodes whatever N is, so nIni
+ * bounds the list the workgroup keeps in LDS beside N, and the kernel sorts the candidates into their roots with one wavefront per
+ * root passing over all candidates, work that grows with nIni times n.  64 roots is an area 64 times as wide as high (a level of
+ * an image is between 1 and 3); csrc/orb_octree.h's host build has no such limit and ORBextractor::DistributeOctTreeDevice uses
+ * it beyond.
+ */
+#define OSH_OCTREE_MAX_FEATURES   2048    /* N of a list                                                          */
+#define OSH_OCTREE_MAX_CANDIDATES 65536   /* candidates of a list                                                 */
+#define OSH_OCTREE_MAX_ROOTS      64      /* nIni: an area up to 64 times as wide as high                         */
+typedef struct osh_octree_list {
+  int32_t n;                 /* candidates (vToDistributeKeys.size())                                                       */
+  const float* xy;           /* [n*2] pt relative to (minX, minY)                                                           */
+  const float* response;     /* [n]                                                                                         */
+  int32_t width, height;     /* maxX - minX, maxY - minY                                                                    */
+  int32_t n_features;        /* N (mnFeaturesPerLevel[level])                                                               */
+} osh_octree_list;
+typedef struct osh_octree_result {
+  int32_t capacity;          /* in:  entries index can take                                                                 */
+  int32_t n_out;             /* out: keypoints kept                                                                         */
+  int32_t status;            /* out: OSH_OK, or why the list has no result                                                  */
+  int32_t* index;            /* [capacity] the kept candidates as input indices, in result order                            */
+} osh_octree_result;
+int osh_orb_octree_distribute(osh_orb_ctx* ctx, int32_t n_lists, const osh_octree_list* lists, osh_octree_result* results);
+/* Host-clock phases (ms) of the last osh_orb_octree_distribute under osh_orb_set_profiling: ms[0] validation + staging, ms[1]
+ * upload, ms[2] kernel, ms[3] download + write-back. */
+int osh_orb_octree_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 /* ------------------------------------------------- the image pyramid (ORBextractor::ComputePyramid) */
 /*
  * ORBextractor::ComputePyramid (src/ORBextractor.cc:1170-1195) for n_frames images in one call: every level is resampled on the
@@ -1466,6 +1537,62 @@ int osh_orb_describe(osh_orb_ctx* ctx, int32_t n_frames, const osh_describe_fram
 /* Host-clock phases (ms) of the last osh_orb_describe under osh_orb_set_profiling: ms[0] validation + staging, ms[1] upload,
  * ms[2] kernels, ms[3] download + write-back. */
 int osh_orb_describe_get_times(osh_orb_ctx* ctx, double ms[4]);
+
+/* ------------------------------------------------- a whole ORBextractor::operator() per frame */
+/*
+ * ORBextractor::operator() (src/ORBextractor.cc:1086-1168) up to its write-back, for n_frames images in ONE call: the pyramid as
+ * osh_orb_pyramid_build builds it (it becomes the context's resident pyramid, results[k].pyramid_token names frame k's levels for
+ * a later osh_orb_ic_angle or osh_orb_describe), the detector of osh_orb_fast_detect_resident on those levels, per level the
+ * quadtree of osh_orb_octree_distribute with n_features[level] on the candidates where the detector left them, minBorder = 16
+ * added to the kept ones (:880-890), IC_Angle of osh_orb_ic_angle and the blur and descriptors of osh_orb_describe on the kept
+ * keypoints.  Every stage is the statement of its own section above and runs the same kernels, so every output equals the chain of
+ * those calls bit for bit.  Only the image and the plans and tables of the stages go up; between the detector and the descriptors
+ * no keypoint array crosses to the host (the detector's cell offsets and the quadtree's kept counts do: they size what follows);
+ * one download brings the results.
+ *
+ * Per frame the keypoints come back level after level, inside a level in the quadtree's result order: level_count[l] of them on
+ * level l, xy in the pixels of their level, response, angle, size = (float)(int)(31 * scale[level]) and 32 descriptor bytes each.
+ * The scaling to level 0 and the vLappingArea placement of :1143-1164 stay with the caller.  When n_out > capacity the counts are
+ * written, the arrays of that frame are not, and the call still returns OSH_OK.  levels / border: as in osh_pyramid_result (NULL:
+ * the bordered levels are not downloaded).
+ *
+ * Refused before any device work and without a context, the resident pyramid staying as it was: with OSH_ERR_INVALID whatever
+ * osh_orb_pyramid_build refuses of the image, n_levels, inv_scale, levels and border; a threshold outside [1, 255] or
+ * min_th > ini_th; a NULL scale, n_features, pattern or level_count; a scale that is not finite and positive; a negative capacity
+ * or a NULL result array with capacity > 0; a table point outside [-15, 15] or a table that reaches more than 19 pixels (a kept
+ * corner is 19 pixels from the edges of its level); blur weights that do not sum to 256; with OSH_ERR_UNSUPPORTED n_features[l]
+ * above OSH_OCTREE_MAX_FEATURES.  A level with more than OSH_OCTREE_MAX_CANDIDATES candidates or a detect area of more than
+ * OSH_OCTREE_MAX_ROOTS roots is refused with OSH_ERR_UNSUPPORTED too, but is only known after the detector ran: the new pyramid
+ * is then resident.
+ */
+typedef struct osh_extract_frame {
+  osh_stereo_image image;            /* read in place                                                                       */
+  int32_t n_levels;
+  const float* inv_scale;            /* [n_levels] mvInvScaleFactor                                                         */
+  const float* scale;                /* [n_levels] mvScaleFactor, for the size field                                        */
+  int32_t ini_th, min_th;            /* iniThFAST, minThFAST                                                                */
+  const int32_t* n_features;         /* [n_levels] mnFeaturesPerLevel                                                       */
+  const int8_t* pattern;             /* [1024] the sampling table, x and y interleaved                                      */
+  const uint16_t* blur_q8;           /* [7] weights that sum to 256, or NULL: the default                                   */
+} osh_extract_frame;
+typedef struct osh_extract_result {
+  int32_t capacity;                  /* in:  keypoints the arrays can take                                                  */
+  int32_t n_out;                     /* out: keypoints of the frame, all levels                                             */
+  uint64_t pyramid_token;            /* out                                                                                 */
+  int32_t* level_count;              /* [n_levels] out                                                                      */
+  float* xy;                         /* [capacity*2] in the pixels of their level                                           */
+  int32_t* level;                    /* [capacity]                                                                          */
+  float* response;                   /* [capacity]                                                                          */
+  float* angle;                      /* [capacity] degrees in [0, 360)                                                      */
+  float* size;                       /* [capacity]                                                                          */
+  uint8_t* descriptors;              /* [capacity*32]                                                                       */
+  const osh_pyramid_image* levels;   /* [n_levels] where the bordered levels go, or NULL: no download                       */
+  int32_t border;
+} osh_extract_result;
+int osh_orb_extract(osh_orb_ctx* ctx, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results);
+/* Host-clock times (ms) of the last osh_orb_extract under osh_orb_set_profiling: ms[0] checks and the pyramid, ms[1] the detector,
+ * ms[2] the quadtree, ms[3] orientation, blur, descriptors, download and write-back. */
+int osh_orb_extract_get_times(osh_orb_ctx* ctx, double ms[4]);
 
 /* ------------------------------------------------- bag-of-words transform */
 /*

@@ -651,6 +651,30 @@ typedef struct osh_host_orbextractor_output {
  * first `capacity` keypoints and `cand_capacity` candidates).  -1: bad arguments, -2: the member left something inconsistent. */
 int osh_host_orbextractor_compute_keypoints(const osh_host_orbextractor_input* in, const osh_host_orbextractor_output* out);
 
+/* ---- ORBextractor::DistributeOctTree (csrc/orb_octree.h, csrc/host/ORBextractor.cc, csrc/hosttest/octree.cc) ---- */
+struct osh_octree_list;
+struct osh_octree_result;
+/* csrc/orb_octree.h compiled for the host, on one thread (osh::octree_distribute_host): arguments, checks, return codes and the
+ * overflow convention of osh_orb_octree_distribute without a context; the limits on n_features, candidates and roots are those of
+ * the device call although the host statements have none.  *ms (may be NULL) = wall time of the lists without the checks. */
+int osh_host_orb_octree_cpu(int32_t n_lists, const struct osh_octree_list* lists, struct osh_octree_result* results, double* ms);
+/* ORBextractor::DistributeOctTreeDevice of a stand-in extractor on the candidates of `list` with minX = minY = 16, maxX = 16 + width,
+ * maxY = 16 + height: index [capacity] receives the input index of each kept keypoint in result order (carried through
+ * cv::KeyPoint::class_id), xy [capacity*2] and response [capacity] (each may be NULL) the kept keypoints themselves,
+ * *distribute_calls the number of DistributeOctTree calls the member made (the test double records them).  Returns the number of kept keypoints.  -1: bad arguments. */
+int osh_host_orbextractor_distribute_device(const struct osh_octree_list* list, int32_t capacity, int32_t* index, float* xy, float* response,
+                                            int32_t* distribute_calls);
+
+/* ORBextractor::ExtractBatch of n stand-in extractors ORBextractor(nfeatures, scale_factor, nlevels, ini_th, min_th), one per
+ * input (an input with rows == 0 is an empty image; `lapping` is its vLappingArea), with bKeepPyramid = keep_pyramid.  Output i
+ * (capacity, pixel_capacity, xy, angle, size, response, octave, descriptors, ret, desc_rows, level_rows, level_cols, pyramid and
+ * pixels_needed as osh_host_orbextractor_extract fills them, the levels being mvImagePyramid after the call) and tokens[i] =
+ * mnPyramidToken.  Returns 0.  -1: bad arguments. */
+struct osh_host_extract_input;
+struct osh_host_extract_output;
+int osh_host_orbextractor_extract_batch(int32_t n, const struct osh_host_extract_input* in, const struct osh_host_extract_output* out,
+                                        int32_t keep_pyramid, uint64_t* tokens);
+
 /* ---- ORBextractor::operator() (csrc/orb_brief.h, csrc/host/ORBextractor.cc, csrc/hosttest/orbextractor.cc) ---- */
 struct osh_describe_frame;
 struct osh_describe_result;

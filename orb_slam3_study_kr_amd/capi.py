@@ -498,6 +498,22 @@ class FastResidentFrame(C.Structure):
     _fields_ = [("pyramid_token", C.c_uint64), ("ini_th", C.c_int32), ("min_th", C.c_int32)]
 
 
+class OctreeList(C.Structure):
+    """``osh_octree_list`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n", C.c_int32), ("xy", c_float_p), ("response", c_float_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("n_features", C.c_int32)]
+
+
+class OctreeResult(C.Structure):
+    """``osh_octree_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("capacity", C.c_int32), ("n_out", C.c_int32), ("status", C.c_int32), ("index", c_int32_p)]
+
+
+OSH_OCTREE_MAX_FEATURES, OSH_OCTREE_MAX_CANDIDATES, OSH_OCTREE_MAX_ROOTS = 2048, 1 << 16, 64
+
+
 class PyramidImage(C.Structure):
     """``osh_pyramid_image`` (include/orbslam3_hip.h)."""
 
@@ -528,6 +544,21 @@ class IcAngleResult(C.Structure):
     """``osh_ic_angle_result`` (include/orbslam3_hip.h)."""
 
     _fields_ = [("angle", c_float_p), ("m10", c_int32_p), ("m01", c_int32_p)]
+
+
+class ExtractFrame(C.Structure):
+    """``osh_extract_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("image", StereoImage), ("n_levels", C.c_int32), ("inv_scale", c_float_p), ("scale", c_float_p), ("ini_th", C.c_int32),
+                ("min_th", C.c_int32), ("n_features", c_int32_p), ("pattern", C.POINTER(C.c_int8)), ("blur_q8", C.POINTER(C.c_uint16))]
+
+
+class ExtractResult(C.Structure):
+    """``osh_extract_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("capacity", C.c_int32), ("n_out", C.c_int32), ("pyramid_token", C.c_uint64), ("level_count", c_int32_p), ("xy", c_float_p),
+                ("level", c_int32_p), ("response", c_float_p), ("angle", c_float_p), ("size", c_float_p), ("descriptors", c_uint8_p),
+                ("levels", C.POINTER(PyramidImage)), ("border", C.c_int32)]
 
 
 class DescribeFrame(C.Structure):
@@ -674,10 +705,14 @@ _SIGNATURES = {
     "osh_orb_fast_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_ic_angle_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_fast_detect_resident": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FastResidentFrame), C.POINTER(FastResult)]),
+    "osh_orb_octree_distribute": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(OctreeList), C.POINTER(OctreeResult)]),
+    "osh_orb_octree_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_pyramid_build": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(PyramidFrame), C.POINTER(PyramidResult)]),
     "osh_orb_pyramid_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_describe": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(DescribeFrame), C.POINTER(DescribeResult)]),
     "osh_orb_describe_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_extract": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(ExtractFrame), C.POINTER(ExtractResult)]),
+    "osh_orb_extract_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_bow_tree_check": (C.c_int, [C.POINTER(BowTree)]),
     "osh_bow_vocab_create": (C.c_int, [C.c_int, C.POINTER(BowTree), C.POINTER(C.c_void_p)]),
     "osh_bow_vocab_destroy": (None, [C.c_void_p]),
@@ -802,9 +837,13 @@ _HOST_SIGNATURES = {
     "osh_host_brief_reach": (C.c_int, [C.POINTER(C.c_int8)]),
     "osh_host_orbextractor_pattern": (C.c_int, [C.POINTER(C.c_int8)]),
     "osh_host_orbextractor_extract": (C.c_int, [C.POINTER(HostExtractInput), C.POINTER(HostExtractOutput)]),
+    "osh_host_orbextractor_extract_batch": (C.c_int, [C.c_int32, C.POINTER(HostExtractInput), C.POINTER(HostExtractOutput), C.c_int32,
+                                                      C.POINTER(C.c_uint64)]),
     "osh_host_orb_fast_cpu": (C.c_int, [C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult), c_double_p]),
     "osh_host_orb_ic_angle_cpu": (C.c_int, [C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult), c_double_p]),
     "osh_host_orb_fast_level_cells": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
+    "osh_host_orb_octree_cpu": (C.c_int, [C.c_int32, C.POINTER(OctreeList), C.POINTER(OctreeResult), c_double_p]),
+    "osh_host_orbextractor_distribute_device": (C.c_int, [C.POINTER(OctreeList), C.c_int32, c_int32_p, c_float_p, c_float_p, c_int32_p]),
     "osh_host_orbextractor_compute_keypoints": (C.c_int, [C.POINTER(HostOrbExtractorInput), C.POINTER(HostOrbExtractorOutput)]),
     "osh_host_create_new_map_points": (C.c_int, [C.POINTER(HostNewPointScene), C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_float_p,
                                                  c_int32_p, c_int32_p, c_float_p]),

@@ -29,6 +29,18 @@
 //   * operator(): cos and sin of the keypoint angle through the FP64 functions, the sample offsets in unfused float32, the blur as
 //     include/orbslam3_hip.h defines it (parity with cv::GaussianBlur is not pinned); on a device error or a refused call a message
 //     goes to stderr and the result is no keypoints (return value 0, descriptors released).
+//
+// ExtractBatch (a member to ADD): operator() of several extractors, for example the left and the right one of a stereo frame, as ONE
+// osh_orb_extract call (csrc/orb_extract_device.hip): pyramid, detector, quadtree, orientation, blur and descriptors on the device
+// with no keypoint array crossing to the host in between, then the write-back of :1143-1164 per extractor.  Its quadtree is the rule
+// of include/orbslam3_hip.h (DistributeOctTreeDevice's), not DistributeOctTree.  An empty image gives -1 for that extractor; a device
+// error or a refused call gives a message on stderr and no keypoints for any extractor.
+//
+// DistributeOctTreeDevice (a member to ADD; :480-779): the arguments and the result of DistributeOctTree, the selection as ONE
+// osh_orb_octree_distribute call (csrc/orb_octree_device.hip) under the rule include/orbslam3_hip.h states.  Nothing calls it here:
+// ComputeKeyPointsOctTree keeps the reference's DistributeOctTree, an integrator opts in.  Its deviations from the reference's list
+// code (the stable sort, nIni == 0, a root index equal to nIni) are those of the rule; candidates the call refuses as invalid (not
+// finite, x outside [0, maxX - minX), negative y, an empty area) give a message on stderr and no keypoints.
 #include "ORBextractor.h"
 
 #include <cmath>
@@ -37,6 +49,7 @@
 #include <vector>
 
 #include "orbslam3_hip.h"
+#include "../orb_octree.h"
 
 namespace ORB_SLAM3 {
 
@@ -198,6 +211,157 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
   for (std::vector<cv::KeyPoint>& kps : allKeypoints)
     for (cv::KeyPoint& kp : kps) kp.angle = angle[n++];
   mnPyramidToken = res.pyramid_token;
+}
+
+std::vector<cv::KeyPoint> ORBextractor::DistributeOctTreeDevice(const std::vector<cv::KeyPoint>& vToDistributeKeys, const int& minX, const int& maxX,
+                                                                const int& minY, const int& maxY, const int& N, const int& /*level*/) {
+  std::vector<cv::KeyPoint> vResultKeys;
+  const int n = (int)vToDistributeKeys.size(), W = maxX - minX, H = maxY - minY;
+  std::vector<float> xy((size_t)n * 2), response(n);
+  for (int k = 0; k < n; ++k) { xy[2 * k] = vToDistributeKeys[k].pt.x; xy[2 * k + 1] = vToDistributeKeys[k].pt.y; response[k] = vToDistributeKeys[k].response; }
+  const char* why = "";
+  const int valid = osh::oct_validate_list(n, xy.data(), response.data(), W, H, N, &why);
+  if (valid == osh::kOctInvalid) {
+    std::fprintf(stderr, "ORBextractor::DistributeOctTreeDevice: %s\n", why);
+    return vResultKeys;
+  }
+  std::vector<int32_t> index(n);   // a node keeps one of its keys: never more than n
+  int kept = -1;
+  if (valid != osh::kOctOk) {
+    std::fprintf(stderr, "ORBextractor::DistributeOctTreeDevice: %s: on the host\n", why);
+  } else {
+    const osh_octree_list list{n, xy.data(), response.data(), W, H, N};
+    osh_octree_result res{n, 0, 0, index.data()};
+    osh_orb_ctx* ctx = HostMatcherContext();
+    if (ctx && osh_orb_octree_distribute(ctx, 1, &list, &res) == OSH_OK) kept = res.n_out;
+    else std::fprintf(stderr, "ORBextractor::DistributeOctTreeDevice: %s: on the host\n", osh_last_error());
+  }
+  if (kept < 0) {
+    std::vector<int> host;
+    if (osh::octree_distribute_host(n, xy.data(), response.data(), W, H, N, host) != osh::kOctOk) return vResultKeys;
+    kept = (int)host.size();
+    std::copy(host.begin(), host.end(), index.begin());
+  }
+  vResultKeys.reserve(kept);
+  for (int i = 0; i < kept; ++i) vResultKeys.push_back(vToDistributeKeys[index[i]]);
+  return vResultKeys;
+}
+
+void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
+                                std::vector<std::vector<cv::KeyPoint> >& vKeypoints, std::vector<cv::Mat>& vDescriptors,
+                                const std::vector<std::vector<int> >& vLappingAreas, std::vector<int>& vMonoIndex, bool bKeepPyramid) {
+  constexpr int kEdge = 19;   // EDGE_THRESHOLD
+  const size_t nExtractors = vpExtractors.size();
+  vKeypoints.resize(nExtractors);
+  vDescriptors.resize(nExtractors);
+  vMonoIndex.assign(nExtractors, 0);
+  if (vImages.size() != nExtractors || vLappingAreas.size() != nExtractors) {
+    std::fprintf(stderr, "ORBextractor::ExtractBatch: %d extractors, %d images, %d lapping areas\n", (int)nExtractors, (int)vImages.size(), (int)vLappingAreas.size());
+    return;
+  }
+  // one frame of the call per extractor with an image; everything a frame points to lives in `job` until the call returns
+  struct Job {
+    size_t extractor;
+    std::vector<cv::Mat> levels;
+    std::vector<osh_pyramid_image> out;
+    std::vector<int8_t> table;
+    std::vector<int32_t> levelCount, level;
+    std::vector<float> xy, response, angle, size;
+    std::vector<uint8_t> desc;
+  };
+  std::vector<Job> jobs;
+  bool ok = true;
+  for (size_t i = 0; i < nExtractors; ++i) {
+    ORBextractor* ex = vpExtractors[i];
+    if (vImages[i].empty()) { vMonoIndex[i] = -1; continue; }   // operator() returns before it touches anything
+    vKeypoints[i].clear();
+    vDescriptors[i].release();
+    ex->mnPyramidToken = ex->mnBuiltPyramidToken = 0;
+    ex->mvImagePyramid.assign(ex->nlevels > 0 ? ex->nlevels : 0, cv::Mat());
+    const int nl = ex->nlevels;
+    if (nl <= 0 || (int)ex->mvInvScaleFactor.size() < nl || (int)ex->mvScaleFactor.size() < nl || (int)ex->mnFeaturesPerLevel.size() < nl ||
+        ex->pattern.size() != 512 || vLappingAreas[i].size() < 2) {
+      std::fprintf(stderr, "ORBextractor::ExtractBatch: extractor %d: its level tables, its pattern or its lapping area do not fit\n", (int)i);
+      ok = false;
+      continue;
+    }
+    jobs.emplace_back();
+    Job& j = jobs.back();
+    j.extractor = i;
+    j.table.resize(1024);
+    for (int k = 0; k < 512; ++k) {
+      ok = ok && ex->pattern[k].x >= -128 && ex->pattern[k].x <= 127 && ex->pattern[k].y >= -128 && ex->pattern[k].y <= 127;
+      j.table[2 * k] = (int8_t)ex->pattern[k].x; j.table[2 * k + 1] = (int8_t)ex->pattern[k].y;
+    }
+    size_t capacity = 0;   // the quadtree keeps at most max(N + 3, 4 nIni) keypoints of a level, nIni <= OSH_OCTREE_MAX_ROOTS
+    for (int l = 0; l < nl; ++l) capacity += (size_t)std::max(std::max(ex->mnFeaturesPerLevel[l], 0) + 3, 4 * OSH_OCTREE_MAX_ROOTS);
+    j.levelCount.resize(nl); j.level.resize(capacity); j.xy.resize(capacity * 2); j.response.resize(capacity); j.angle.resize(capacity);
+    j.size.resize(capacity); j.desc.resize(capacity * 32);
+    if (bKeepPyramid) {   // :1174-1178 per level, as ComputePyramid: the bordered `temp` and the level as the view into it
+      j.levels.resize(nl); j.out.resize(nl);
+      for (int l = 0; l < nl; ++l) {
+        const float fw = (float)vImages[i].cols * ex->mvInvScaleFactor[l], fh = (float)vImages[i].rows * ex->mvInvScaleFactor[l];
+        const int w = fw >= 0.f && fw < 1.0e6f ? (int)std::nearbyint(fw) : 0, h = fh >= 0.f && fh < 1.0e6f ? (int)std::nearbyint(fh) : 0;
+        if (w <= 0 || h <= 0) { std::fprintf(stderr, "ORBextractor::ExtractBatch: extractor %d: level %d has no pixels or too many\n", (int)i, l); ok = false; break; }
+        cv::Mat temp(h + 2 * kEdge, w + 2 * kEdge);
+        j.levels[l] = temp.view(kEdge, kEdge, h, w);
+        j.out[l].data = j.levels[l].ptr<uint8_t>(0);
+        j.out[l].rows = h; j.out[l].cols = w; j.out[l].stride = (int64_t)(size_t)j.levels[l].step;
+      }
+    }
+  }
+  if (!ok) std::fprintf(stderr, "ORBextractor::ExtractBatch: nothing extracted\n");
+  osh_orb_ctx* ctx = ok && !jobs.empty() ? HostMatcherContext() : nullptr;
+  if (ok && !jobs.empty() && !ctx) { std::fprintf(stderr, "ORBextractor::ExtractBatch: %s\n", osh_last_error()); ok = false; }
+  if (!ok || jobs.empty()) return;
+  std::vector<osh_extract_frame> frames(jobs.size());
+  std::vector<osh_extract_result> results(jobs.size());
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    Job& j = jobs[k];
+    const ORBextractor* ex = vpExtractors[j.extractor];
+    const cv::Mat& image = vImages[j.extractor];
+    osh_extract_frame& f = frames[k];
+    f.image.data = image.ptr<uint8_t>(0); f.image.rows = image.rows; f.image.cols = image.cols; f.image.stride = (int64_t)(size_t)image.step;
+    f.n_levels = ex->nlevels; f.inv_scale = ex->mvInvScaleFactor.data(); f.scale = ex->mvScaleFactor.data();
+    f.ini_th = ex->iniThFAST; f.min_th = ex->minThFAST; f.n_features = ex->mnFeaturesPerLevel.data();
+    f.pattern = j.table.data(); f.blur_q8 = nullptr;
+    osh_extract_result& r = results[k];
+    r = osh_extract_result{};
+    r.capacity = (int32_t)j.response.size(); r.level_count = j.levelCount.data(); r.xy = j.xy.data(); r.level = j.level.data();
+    r.response = j.response.data(); r.angle = j.angle.data(); r.size = j.size.data(); r.descriptors = j.desc.data();
+    r.levels = bKeepPyramid ? j.out.data() : nullptr; r.border = kEdge;
+  }
+  if (osh_orb_extract(ctx, (int32_t)jobs.size(), frames.data(), results.data()) != OSH_OK) {
+    std::fprintf(stderr, "ORBextractor::ExtractBatch: %s\n", osh_last_error());
+    return;
+  }
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    const Job& j = jobs[k];
+    ORBextractor* ex = vpExtractors[j.extractor];
+    const osh_extract_result& r = results[k];
+    if (r.n_out > r.capacity) { std::fprintf(stderr, "ORBextractor::ExtractBatch: extractor %d: %d keypoints for %d places\n", (int)j.extractor, r.n_out, r.capacity); continue; }
+    if (bKeepPyramid) ex->mvImagePyramid = j.levels;
+    ex->mnPyramidToken = r.pyramid_token;
+    const int nkeypoints = r.n_out;
+    std::vector<cv::KeyPoint>& keypoints = vKeypoints[j.extractor];
+    cv::Mat& descriptors = vDescriptors[j.extractor];
+    keypoints = std::vector<cv::KeyPoint>(nkeypoints);
+    if (nkeypoints) descriptors.create(nkeypoints, 32, CV_8U);
+    // :1120-1167: scale to level 0, keypoints of the lapping area from the back, the others from the front
+    const std::vector<int>& lapping = vLappingAreas[j.extractor];
+    int monoIndex = 0, stereoIndex = nkeypoints - 1;
+    for (int i = 0; i < nkeypoints; ++i) {
+      cv::KeyPoint keypoint;
+      const int level = j.level[i];
+      keypoint.pt.x = j.xy[2 * i]; keypoint.pt.y = j.xy[2 * i + 1]; keypoint.response = j.response[i]; keypoint.angle = j.angle[i];
+      keypoint.size = j.size[i]; keypoint.octave = level; keypoint.class_id = -1;
+      if (level != 0) keypoint.pt *= ex->mvScaleFactor[level];
+      const int at = keypoint.pt.x >= lapping[0] && keypoint.pt.x <= lapping[1] ? stereoIndex-- : monoIndex++;
+      keypoints.at(at) = keypoint;
+      std::memcpy(descriptors.ptr<uint8_t>(at), &j.desc[32 * (size_t)i], 32);
+    }
+    vMonoIndex[j.extractor] = monoIndex;
+  }
 }
 
 int ORBextractor::operator()(cv::InputArray _image, cv::InputArray /*_mask*/, std::vector<cv::KeyPoint>& _keypoints, cv::OutputArray _descriptors,

@@ -13,6 +13,7 @@
 // A frame reads the pyramid its token names (the context's resident pyramid) or brings its own: orb_pyramid_set.h.
 #include "common.h"
 #include "orb_brief.h"
+#include "orb_extract.h"
 #include "orb_pyramid_set.h"
 #include "orb_stage.h"
 #include <cmath>
@@ -31,14 +32,6 @@ constexpr int kBlurInH = kBlurTH + 2 * kBriefHalo;   // 22
 constexpr int kBlurImgPitch = 72;
 constexpr int kBlurHPitch = kBlurTW;
 constexpr int kBriefBlock = 256;                     // k_orb_brief: four keypoints
-
-struct BlurLevelDev {
-  const unsigned char* src;    // first pixel of the packed level
-  unsigned char* dst;          // of the blurred level
-  int rows, cols;
-  unsigned short w[8];         // w[0..6]
-};
-struct BlurTileDev { int level, tx, ty; };
 
 __global__ __launch_bounds__(kBlurBlock) void k_orb_blur(const BlurLevelDev* levels, const BlurTileDev* tiles) {
   __shared__ unsigned char sh_img[kBlurInH * kBlurImgPitch];
@@ -76,18 +69,6 @@ __global__ __launch_bounds__(kBlurBlock) void k_orb_blur(const BlurLevelDev* lev
     if (gx < cols && gy < rows) L.dst[(size_t)gy * cols + gx] = brief_blur_round(acc);
   }
 }
-
-struct BriefView {
-  int n;
-  const PyramidLevelDev* levels;   // the blurred levels of every frame of the call, frame after frame
-  const int* level_index;          // [n] the keypoint's entry of `levels`
-  const int* frame;                // [n] the keypoint's frame: its table
-  const float2* xy;                // [n]
-  const float* angle;              // [n]
-  const signed char* pattern;      // [n_frames * 1024]
-  unsigned long long* desc;        // [n * 4]
-  float2* cos_sin;                 // [n]
-};
 
 __global__ __launch_bounds__(kBriefBlock) void k_orb_brief(BriefView v) {
   // the tables of the block's four keypoints; neighbours of one frame read the same bytes again, from L2
@@ -147,6 +128,30 @@ static int brief_validate_frame(int k, const osh_describe_frame& f, const osh_de
   return OSH_OK;
 }
 
+BlurLevelDev blur_level(const unsigned char* src, unsigned char* dst, int rows, int cols, const uint16_t* w) {
+  uint16_t default_w[kBriefTaps];
+  if (!w) { brief_gaussian_q8(kBriefTaps, 2.0, default_w); w = default_w; }
+  BlurLevelDev B{src, dst, rows, cols, {0, 0, 0, 0, 0, 0, 0, 0}};
+  for (int u = 0; u < kBriefTaps; ++u) B.w[u] = w[u];
+  return B;
+}
+
+void blur_tiles(int l, int rows, int cols, std::vector<BlurTileDev>& tiles) {
+  const int nty = (rows + kBlurTH - 1) / kBlurTH, ntx = (cols + kBlurTW - 1) / kBlurTW;
+  for (int ty = 0; ty < nty; ++ty) for (int tx = 0; tx < ntx; ++tx) tiles.push_back({l, tx, ty});
+}
+
+unsigned char* brief_blurred(osh_orb_ctx* c, size_t bytes) {
+  BriefState* st = orb_state<BriefState>(c, kOrbAttachBrief);
+  return st->blurred.reserve(bytes) == OSH_OK ? st->blurred.as<unsigned char>() : nullptr;
+}
+
+int brief_launch(hipStream_t s, size_t n_tiles, const BlurLevelDev* blur, const BlurTileDev* tiles, const BriefView& v) {
+  if (n_tiles) hipLaunchKernelGGL(k_orb_blur, dim3((unsigned)n_tiles), dim3(kBlurBlock), 0, s, blur, tiles);
+  if (v.n) hipLaunchKernelGGL(k_orb_brief, dim3((unsigned)((v.n + kBriefBlock / 64 - 1) / (kBriefBlock / 64))), dim3(kBriefBlock), 0, s, v);
+  return launch_check("ORB blur and descriptors");
+}
+
 }  // namespace osh
 
 using namespace osh;
@@ -188,11 +193,8 @@ extern "C" int osh_orb_describe(osh_orb_ctx* c, int32_t n_frames, const osh_desc
     if (blur_bytes > (size_t)1 << 32) { set_error("osh_orb_describe: batch too large"); return OSH_ERR_UNSUPPORTED; }
   }
   std::vector<BlurTileDev> tiles;
-  for (size_t l = 0; l < lv.size(); ++l) {
-    if (!blur[l].wanted) continue;
-    const int nty = (lv[l].rows + kBlurTH - 1) / kBlurTH, ntx = (lv[l].cols + kBlurTW - 1) / kBlurTW;
-    for (int ty = 0; ty < nty; ++ty) for (int tx = 0; tx < ntx; ++tx) tiles.push_back({(int)l, tx, ty});
-  }
+  for (size_t l = 0; l < lv.size(); ++l)
+    if (blur[l].wanted) blur_tiles((int)l, lv[l].rows, lv[l].cols, tiles);
 
   Layout in, out;
   const auto s_blur = in.take<BlurLevelDev>(lv.size());
@@ -212,14 +214,9 @@ extern "C" int osh_orb_describe(osh_orb_ctx* c, int32_t n_frames, const osh_desc
   const unsigned char* resident = rp ? rp->images() : nullptr;
   const unsigned char* uploaded = s_img.in(static_cast<const char*>(st->call.dev_in()));
   unsigned char* blurred = st->blurred.as<unsigned char>();
-  uint16_t default_w[kBriefTaps];
-  brief_gaussian_q8(kBriefTaps, 2.0, default_w);
   for (size_t l = 0; l < lv.size(); ++l) {
-    BlurLevelDev& B = s_blur.in(h)[l];
-    B.src = pl.data(l, resident, uploaded); B.dst = blurred + blur[l].off; B.rows = lv[l].rows; B.cols = lv[l].cols;
-    const uint16_t* w = frames[blur[l].frame].blur_q8 ? frames[blur[l].frame].blur_q8 : default_w;
-    for (int u = 0; u < kBriefTaps; ++u) B.w[u] = w[u];
-    B.w[7] = 0;
+    const BlurLevelDev B = blur_level(pl.data(l, resident, uploaded), blurred + blur[l].off, lv[l].rows, lv[l].cols, frames[blur[l].frame].blur_q8);
+    s_blur.in(h)[l] = B;
     s_levels.in(h)[l] = {B.dst, lv[l].rows, lv[l].cols};
   }
   if (!tiles.empty()) std::memcpy(s_tiles.in(h), tiles.data(), sizeof(BlurTileDev) * tiles.size());
@@ -239,14 +236,10 @@ extern "C" int osh_orb_describe(osh_orb_ctx* c, int32_t n_frames, const osh_desc
   OSH_TRY(st->call.upload(s));
   OSH_TRY(clock.mark_synced(s));
   char* di = st->call.dev_in(); char* dout = st->call.dev_out();
-  if (!tiles.empty()) hipLaunchKernelGGL(k_orb_blur, dim3((unsigned)tiles.size()), dim3(kBlurBlock), 0, s, s_blur.in(di), s_tiles.in(di));
-  if (N) {
-    BriefView v{};
-    v.n = (int)N; v.levels = s_levels.in(di); v.level_index = s_index.in(di); v.frame = s_frame.in(di); v.xy = s_xy.in(di);
-    v.angle = s_angle.in(di); v.pattern = s_pattern.in(di); v.desc = o_desc.in(dout); v.cos_sin = o_cs.in(dout);
-    hipLaunchKernelGGL(k_orb_brief, dim3((unsigned)((N + kBriefBlock / 64 - 1) / (kBriefBlock / 64))), dim3(kBriefBlock), 0, s, v);
-  }
-  OSH_TRY(launch_check("ORB blur and descriptors"));
+  BriefView v{};
+  v.n = (int)N; v.levels = s_levels.in(di); v.level_index = s_index.in(di); v.frame = s_frame.in(di); v.xy = s_xy.in(di);
+  v.angle = s_angle.in(di); v.pattern = s_pattern.in(di); v.desc = o_desc.in(dout); v.cos_sin = o_cs.in(dout);
+  OSH_TRY(brief_launch(s, tiles.size(), s_blur.in(di), s_tiles.in(di), v));
   OSH_TRY(clock.mark_synced(s));
   OSH_TRY(st->call.download(s));   // synchronises
   const char* ho = st->call.host_out();

@@ -11,9 +11,12 @@
 //   k_fast_emit    one wavefront per cell: the set bits of the mask in ascending order at offset[cell] + rank, the score of each
 //                  read again from the packed level.
 // The host reads the offsets between scan and emit: they size the output.  Where a result lands is a function of the counts alone.
+// fast_emit is the detector up to there: the candidates stay in the context's emit buffer; fast_download brings them to the host for
+// the two detect entries, and osh_orb_extract (orb_extract_device.hip) leaves them where they are (fast_emit_resident, orb_extract.h).
 //
 // osh_orb_ic_angle: k_ic_angle, one keypoint per lane, reads its 31-pixel disc from the packed level.
 #include "common.h"
+#include "orb_extract.h"
 #include "orb_fast.h"
 #include "orb_pyramid_set.h"
 #include "orb_stage.h"
@@ -236,9 +239,17 @@ using namespace osh;
 // The kernels of a planned detector call over the resident pyramid and the results of every frame.  `frames` (osh_orb_fast_detect):
 // their levels are staged into st->pyramid.h_images and uploaded into its buffer first, img_bytes of them; nullptr: the pyramid is there.
 // The caller writes the tokens into the results.
-static int fast_run(const char* entry, FastState* st, hipStream_t s, PhaseClock& clock, const FastPlan& p, const osh_fast_frame* frames, size_t img_bytes,
-                    osh_fast_result* results) {
-  const int n_frames = (int)p.fh.size(), n_cells = (int)p.cells.size();
+// `frames` (osh_orb_fast_detect) as below.  What it leaves: the candidates on the device in st->emitted, where osh_orb_extract's
+// octree reads them, and the offsets and used_min_th on the host in st->call's output.
+struct FastEmitRun {
+  const int* offset = nullptr;            // host, [n_cells + 1]
+  const unsigned char* used = nullptr;    // host, [n_cells]
+  size_t total = 0, bytes = 0;            // candidates of the call; bytes of their four arrays
+  Section<float2> xy{0}; Section<float> response{0}; Section<int> level{0}, cell{0};   // in st->emitted / st->h_emitted
+};
+static int fast_emit(const char* entry, FastState* st, hipStream_t s, PhaseClock& clock, const FastPlan& p, const osh_fast_frame* frames, size_t img_bytes,
+                     FastEmitRun& run) {
+  const int n_cells = (int)p.cells.size(), n_frames = (int)p.fh.size();
   std::vector<int> order(n_cells);
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p.cells[a].w * p.cells[a].h > p.cells[b].w * p.cells[b].h; });
@@ -285,15 +296,25 @@ static int fast_run(const char* entry, FastState* st, hipStream_t s, PhaseClock&
   const auto e_level = em.take<int>(total); const auto e_cell = em.take<int>(total);
   if (total) {
     OSH_TRY(st->emitted.reserve(em.bytes));
-    if (!st->h_emitted.reserve(em.bytes)) { set_error("%s: pinned allocation of %zu bytes failed", entry, em.bytes); return OSH_ERR_DEVICE; }
     char* de = st->emitted.as<char>();
     v.xy = e_xy.in(de); v.response = e_resp.in(de); v.level = e_level.in(de); v.cell = e_cell.in(de);
     hipLaunchKernelGGL(k_fast_emit, dim3((unsigned)n_cells), dim3(64), 0, s, v);
     OSH_TRY(launch_check("FAST emit"));
   }
-  OSH_TRY(clock.mark_synced(s));
-  if (total) {
-    OSH_HIP(hipMemcpyAsync(st->h_emitted.p, st->emitted.p, em.bytes, hipMemcpyDeviceToHost, s));
+  run.offset = offset; run.used = used; run.total = total; run.bytes = em.bytes;
+  run.xy = e_xy; run.response = e_resp; run.level = e_level; run.cell = e_cell;
+  return OSH_OK;
+}
+
+// The candidates of a fast_emit down to the host and into the results of every frame
+static int fast_download(const char* entry, FastState* st, hipStream_t s, const FastPlan& p, const FastEmitRun& run, osh_fast_result* results) {
+  const int n_frames = (int)p.fh.size();
+  const int* offset = run.offset;
+  const unsigned char* used = run.used;
+  const auto e_xy = run.xy; const auto e_resp = run.response; const auto e_level = run.level; const auto e_cell = run.cell;
+  if (run.total) {
+    if (!st->h_emitted.reserve(run.bytes)) { set_error("%s: pinned allocation of %zu bytes failed", entry, run.bytes); return OSH_ERR_DEVICE; }
+    OSH_HIP(hipMemcpyAsync(st->h_emitted.p, st->emitted.p, run.bytes, hipMemcpyDeviceToHost, s));
     OSH_HIP(hipStreamSynchronize(s));
   }
   const char* he = static_cast<const char*>(st->h_emitted.p);
@@ -314,6 +335,58 @@ static int fast_run(const char* entry, FastState* st, hipStream_t s, PhaseClock&
     }
   }
   return OSH_OK;
+}
+
+static int fast_run(const char* entry, FastState* st, hipStream_t s, PhaseClock& clock, const FastPlan& p, const osh_fast_frame* frames, size_t img_bytes,
+                    osh_fast_result* results) {
+  FastEmitRun run;
+  OSH_TRY(fast_emit(entry, st, s, clock, p, frames, img_bytes, run));
+  OSH_TRY(clock.mark_synced(s));
+  return fast_download(entry, st, s, p, run, results);
+}
+
+// The plan of a detector call over frames of the resident pyramid; OSH_ERR_INVALID for a token that names none of them
+static int fast_plan_resident(const char* entry, const FastState* st, int n_frames, const osh_fast_resident_frame* frames, FastPlan& p) {
+  for (int k = 0; k < n_frames; ++k) {
+    const FastFrameHost* F = st->pyramid.frame(frames[k].pyramid_token);
+    if (!F) { set_error("%s: frame %d: the token names no frame of this context's resident pyramid", entry, k); return OSH_ERR_INVALID; }
+    p.fh.push_back({(int)p.lh.size(), F->n_levels, (int)p.cells.size(), 0});
+    for (int l = 0; l < F->n_levels; ++l) {
+      const FastLevelHost& L = st->pyramid.levels[F->level0 + l];
+      OSH_TRY(fast_plan_level(entry, p, l, L.rows, L.cols, L.img_off, frames[k].ini_th, frames[k].min_th));
+    }
+    p.fh[k].n_cells = (int)p.cells.size() - p.fh[k].cell0;
+  }
+  return OSH_OK;
+}
+
+int osh::fast_emit_resident(const char* entry, osh_orb_ctx* c, hipStream_t s, int n_frames, const osh_fast_resident_frame* frames, FastEmitted& e) {
+  FastState* st = orb_state<FastState>(c, kOrbAttachFast);
+  FastPlan p;
+  OSH_TRY(fast_plan_resident(entry, st, n_frames, frames, p));
+  PhaseClock clock;
+  FastEmitRun run;
+  OSH_TRY(fast_emit(entry, st, s, clock, p, nullptr, 0, run));
+  e.levels.clear(); e.level0.clear();
+  for (int k = 0; k < n_frames; ++k) {
+    e.level0.push_back((int)e.levels.size());
+    for (int l = 0; l < p.fh[k].n_levels; ++l) {
+      const FastLevelHost& L = p.lh[p.fh[k].level0 + l];
+      e.levels.push_back({L.rows, L.cols, L.img_off, run.offset[L.cell0], run.offset[L.cell0 + L.n_cells] - run.offset[L.cell0]});
+    }
+  }
+  e.level0.push_back((int)e.levels.size());
+  e.images = st->pyramid.images();
+  e.xy = run.total ? run.xy.in(st->emitted.as<const char>()) : nullptr;
+  e.response = run.total ? run.response.in(st->emitted.as<const char>()) : nullptr;
+  return OSH_OK;
+}
+
+int osh::ic_angle_launch(hipStream_t s, int n, const PyramidLevelDev* levels, const int* level_index, const float2* xy, float* angle, int* m10, int* m01) {
+  IcView v{};
+  v.n = n; v.levels = levels; v.level_index = level_index; v.xy = xy; v.angle = angle; v.m10 = m10; v.m01 = m01;
+  hipLaunchKernelGGL(k_ic_angle, dim3((unsigned)((n + kIcBlock - 1) / kIcBlock)), dim3(kIcBlock), 0, s, v);
+  return launch_check("IC_Angle");
 }
 
 extern "C" int osh_orb_fast_detect(osh_orb_ctx* c, int32_t n_frames, const osh_fast_frame* frames, osh_fast_result* results) {
@@ -359,16 +432,7 @@ extern "C" int osh_orb_fast_detect_resident(osh_orb_ctx* c, int32_t n_frames, co
   if (n_frames == 0) return OSH_OK;
   FastState* st = orb_state<FastState>(c, kOrbAttachFast);
   FastPlan p;
-  for (int k = 0; k < n_frames; ++k) {
-    const FastFrameHost* F = st->pyramid.frame(frames[k].pyramid_token);
-    if (!F) { set_error("osh_orb_fast_detect_resident: frame %d: the token names no frame of this context's resident pyramid", k); return OSH_ERR_INVALID; }
-    p.fh.push_back({(int)p.lh.size(), F->n_levels, (int)p.cells.size(), 0});
-    for (int l = 0; l < F->n_levels; ++l) {
-      const FastLevelHost& L = st->pyramid.levels[F->level0 + l];
-      OSH_TRY(fast_plan_level("osh_orb_fast_detect_resident", p, l, L.rows, L.cols, L.img_off, frames[k].ini_th, frames[k].min_th));
-    }
-    p.fh[k].n_cells = (int)p.cells.size() - p.fh[k].cell0;
-  }
+  OSH_TRY(fast_plan_resident("osh_orb_fast_detect_resident", st, n_frames, frames, p));
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(orb_stream(c, &device, &s));
@@ -422,12 +486,8 @@ extern "C" int osh_orb_ic_angle(osh_orb_ctx* c, int32_t n_frames, const osh_ic_a
   clock.mark();
   OSH_TRY(st->ic_call.upload(s));
   OSH_TRY(clock.mark_synced(s));
-  IcView v{};
   char* di = st->ic_call.dev_in(); char* dout = st->ic_call.dev_out();
-  v.n = (int)N; v.levels = s_levels.in(di); v.level_index = s_index.in(di); v.xy = s_xy.in(di);
-  v.angle = o_angle.in(dout); v.m10 = o_m10.in(dout); v.m01 = o_m01.in(dout);
-  hipLaunchKernelGGL(k_ic_angle, dim3((unsigned)((N + kIcBlock - 1) / kIcBlock)), dim3(kIcBlock), 0, s, v);
-  OSH_TRY(launch_check("IC_Angle"));
+  OSH_TRY(ic_angle_launch(s, (int)N, s_levels.in(di), s_index.in(di), s_xy.in(di), o_angle.in(dout), o_m10.in(dout), o_m01.in(dout)));
   OSH_TRY(clock.mark_synced(s));
   OSH_TRY(st->ic_call.download(s));
   const char* ho = st->ic_call.host_out();

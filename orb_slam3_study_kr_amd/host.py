@@ -1479,3 +1479,67 @@ def orbextractor_compute_keypoints(pyramid, nfeatures=1000, scale_factor=1.2, in
             break
         cap, cand_cap = n, int(o["cand_level_count"].sum())
     return {k: v[:nlevels] if k in ("level_count", "cand_level_count", "cand_args", "features_per_level", "scale_factors") else v for k, v in o.items()}
+
+
+def orbextractor_distribute_device(xy, response, width, height, n_features) -> dict:
+    """ORBextractor::DistributeOctTreeDevice of a stand-in extractor on one list of candidates (relative to minBorder) through
+    osh_host_orbextractor_distribute_device: a dict with index (the kept input indices in result order), xy, response of the kept
+    keypoints and distribute_calls, the number of DistributeOctTree calls the member made."""
+    lib = capi.load_host_library()
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    response = np.ascontiguousarray(response, np.float32).reshape(-1)
+    n = len(response)
+    lst = capi.OctreeList(n, capi.ptr(xy, capi.c_float_p), capi.ptr(response, capi.c_float_p), int(width), int(height), int(n_features))
+    index, kxy, kresp = np.full(max(n, 1), -1, np.int32), np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.float32)
+    calls = C.c_int32(-1)
+    kept = lib.osh_host_orbextractor_distribute_device(C.byref(lst), n, capi.ptr(index, capi.c_int32_p), capi.ptr(kxy, capi.c_float_p),
+                                                       capi.ptr(kresp, capi.c_float_p), C.byref(calls))
+    if kept < 0:
+        raise RuntimeError(f"osh_host_orbextractor_distribute_device returned {kept}")
+    return dict(index=index[:kept], xy=kxy[:kept], response=kresp[:kept], distribute_calls=int(calls.value))
+
+
+
+def orbextractor_extract_batch(images, lappings, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, keep_pyramid=True) -> list:
+    """ORBextractor::ExtractBatch of one stand-in extractor per image (None or an empty array: an empty image) with its lapping
+    area, through osh_host_orbextractor_extract_batch: per image a dict with ret (monoIndex), desc_rows, token (mnPyramidToken),
+    pyramid (mvImagePyramid after the call, a list of levels), xy, angle, size, response, octave, descriptors [n, 32] of
+    _keypoints, and call_ms, the wall time of the one ExtractBatch call."""
+    lib = capi.load_host_library()
+    n = len(images)
+    imgs = [np.zeros((0, 0), np.uint8) if im is None else np.ascontiguousarray(im, np.uint8) for im in images]
+    cin = (capi.HostExtractInput * max(n, 1))()
+    for i, img in enumerate(imgs):
+        c = cin[i]
+        c.nfeatures, c.scale_factor, c.nlevels, c.ini_th, c.min_th = int(nfeatures), float(scale_factor), int(nlevels), int(ini_th), int(min_th)
+        c.rows, c.cols = (img.shape if img.size else (0, 0))
+        c.pixels = capi.ptr(img if img.size else None, capi.c_uint8_p)
+        c.lapping[0], c.lapping[1] = int(lappings[i][0]), int(lappings[i][1])
+    cap = [2 * int(nfeatures) + 300 * int(nlevels)] * n
+    pix = [int(sum((img.shape[0] + 2) * (img.shape[1] + 2) for _ in range(nlevels))) if img.size else 1 for img in imgs]
+    outs, cout = [], (capi.HostExtractOutput * max(n, 1))()
+    for i in range(n):
+        o = dict(level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), pyramid=np.zeros(pix[i], np.uint8),
+                 xy=np.zeros((cap[i], 2), np.float32), angle=np.zeros(cap[i], np.float32), size=np.zeros(cap[i], np.float32),
+                 response=np.zeros(cap[i], np.float32), octave=np.zeros(cap[i], np.int32), descriptors=np.zeros((cap[i], 32), np.uint8),
+                 ret=np.zeros(1, np.int32), desc_rows=np.zeros(1, np.int32), pixels_needed=np.zeros(1, np.int32), call_ms=np.zeros(1, np.float64))
+        cout[i].capacity, cout[i].pixel_capacity = cap[i], pix[i]
+        for name, arr in o.items():
+            setattr(cout[i], name, capi.ptr(arr, dict(capi.HostExtractOutput._fields_)[name]))
+        outs.append(o)
+    tokens = (C.c_uint64 * max(n, 1))()
+    rc = lib.osh_host_orbextractor_extract_batch(n, cin, cout, int(bool(keep_pyramid)), tokens)
+    if rc != 0:
+        raise RuntimeError(f"osh_host_orbextractor_extract_batch returned {rc}")
+    res = []
+    for i, o in enumerate(outs):
+        k = int(o["desc_rows"][0])
+        d = dict(ret=int(o["ret"][0]), desc_rows=k, token=int(tokens[i]), call_ms=float(o["call_ms"][0]))
+        for name in ("xy", "angle", "size", "response", "octave", "descriptors"):
+            d[name] = o[name][:k]
+        d["pyramid"], off = [], 0
+        for r, c in zip(o["level_rows"].tolist(), o["level_cols"].tolist()):
+            d["pyramid"].append(o["pyramid"][off:off + r * c].reshape(r, c).copy())
+            off += r * c
+        res.append(d)
+    return res

@@ -283,6 +283,17 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_fast_detect_resident(self.ctx, len(items), cf, cr), "osh_orb_fast_detect_resident", self.lib)
         return _fast_outputs(cr, outs)
 
+    def octree_distribute(self, lists, capacities=None) -> list:
+        """ORBextractor::DistributeOctTree (src/ORBextractor.cc:480-779) for a batch of lists (xy [n, 2], response [n], width,
+        height, n_features) in one osh_orb_octree_distribute call: per list a dict with n_out, status and index (the kept input
+        indices in result order).  capacities: per list the room of index; a list that does not fit comes back with its count and
+        None for the array.  None: room for every candidate."""
+        cl, cr, _keep, outs = octree_args(lists, capacities)
+        capi.check(self.lib.osh_orb_octree_distribute(self.ctx, len(lists), cl, cr), "osh_orb_octree_distribute", self.lib)
+        return _octree_outputs(cr, outs)
+
+    octree_times = functools.partialmethod(_times, "osh_orb_octree_get_times")                   # of the last octree_distribute
+
     def pyramid_build(self, items, download: bool = True) -> list:
         """ORBextractor::ComputePyramid (src/ORBextractor.cc:1170-1195) for a batch of items dict(image uint8 [rows, cols] (rows may
         be strided), inv_scale [n_levels], optionally border (19)) in one osh_orb_pyramid_build call: per item a dict with token,
@@ -311,6 +322,20 @@ class OrbMatcher:
 
     describe_cpu = staticmethod(lambda items, borders=None, debug=False: describe_cpu(items, borders=borders, debug=debug))
     extract = staticmethod(lambda image, **kw: extract(image, **kw))
+
+    def extract(self, items, capacities=None, download: bool = False) -> list:
+        """ORBextractor::operator() up to its write-back for a batch of items dict(image, inv_scale, scale, n_features [n_levels],
+        pattern [512, 2] int8, optionally ini_th (20), min_th (7), blur_q8 [7], border (19)) in ONE osh_orb_extract call: per item a
+        dict with n_out, token, level_count and xy [n, 2] (level pixels), level, response, angle, size, descriptors [n, 32] (None
+        when the arrays were too small), and with `download` also levels / bordered as pyramid_build gives them.  capacities: per
+        item the room of the arrays; None: a first call with no room sizes them."""
+        if capacities is None:
+            capacities = [r["n_out"] for r in self.extract(items, [0] * len(items))]
+        cf, cr, _keep, outs = extract_args(items, capacities, download)
+        capi.check(self.lib.osh_orb_extract(self.ctx, len(items), cf, cr), "osh_orb_extract", self.lib)
+        return _extract_outputs(cr, outs)
+
+    extract_times = functools.partialmethod(_times, "osh_orb_extract_get_times")                 # of the last extract
 
     def kb8_triangulate(self, rig: "capi.Kb8Rig", xy1, xy2, sigma1, sigma2) -> dict:
         """KannalaBrandt8::TriangulateMatches for explicit keypoint pairs (osh_kb8_triangulate): ret [n], p3d [n, 3], cos_parallax [n]."""
@@ -519,6 +544,47 @@ def _fast_outputs(cr, outs):
     return res
 
 
+def octree_args(lists, capacities=None, counts=None):
+    """The osh_octree_list / osh_octree_result arrays of OrbMatcher.octree_distribute for lists (xy, response, width, height,
+    n_features) and per list the room of its index array (None: its candidate count): (lists, results, keep-alive, index arrays).
+    counts: per list the candidate count to hand over whatever the arrays hold (for the refusals); xy and response may be None."""
+    n_lists = len(lists)
+    cl = (capi.OctreeList * max(n_lists, 1))()
+    cr = (capi.OctreeResult * max(n_lists, 1))()
+    keep, outs = [], []
+    for k, (xy, response, width, height, n_features) in enumerate(lists):
+        xy = None if xy is None else np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        response = None if response is None else np.ascontiguousarray(response, np.float32).reshape(-1)
+        n = 0 if response is None else len(response)
+        cl[k].n = n if counts is None else int(counts[k])
+        cl[k].xy = None if xy is None else capi.ptr(xy, capi.c_float_p)
+        cl[k].response = None if response is None else capi.ptr(response, capi.c_float_p)
+        cl[k].width, cl[k].height, cl[k].n_features = int(width), int(height), int(n_features)
+        cap = n if capacities is None else int(capacities[k])
+        index = np.full(max(cap, 0), -1, np.int32)
+        cr[k].capacity = cap
+        cr[k].index = capi.ptr(index, capi.c_int32_p) if cap > 0 else None
+        keep.append((xy, response))
+        outs.append(index)
+    return cl, cr, keep, outs
+
+
+def _octree_outputs(cr, outs):
+    """Per list: the count, the status and, when the array was large enough, the kept indices (else None)."""
+    return [dict(n_out=int(cr[k].n_out), status=int(cr[k].status), index=o[:int(cr[k].n_out)] if 0 <= int(cr[k].n_out) <= int(cr[k].capacity) else None)
+            for k, o in enumerate(outs)]
+
+
+def octree_cpu(lists, capacities=None, host_lib=None, counts=None):
+    """csrc/orb_octree.h on the host in one thread (osh_host_orb_octree_cpu of the test library): the per-list dicts of
+    OrbMatcher.octree_distribute, the return code (the checks are those of the device call) and the wall time of the lists in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    ms = C.c_double(0)
+    cl, cr, _keep, outs = octree_args(lists, capacities, counts)
+    rc = host_lib.osh_host_orb_octree_cpu(len(lists), cl, cr, C.byref(ms))
+    return _octree_outputs(cr, outs), int(rc), float(ms.value)
+
+
 def fast_resident_args(items, capacities):
     """The osh_fast_resident_frame / osh_fast_result arrays of OrbMatcher.fast_detect_resident for items dict(token, n_levels,
     ini_th, min_th) and per item a (capacity, cell_capacity)."""
@@ -585,6 +651,47 @@ def _pyramid_outputs(cr, outs):
     res = []
     for k, o in enumerate(outs):
         d = dict(o, token=int(cr[k].pyramid_token), shapes=list(zip(o["level_rows"].tolist(), o["level_cols"].tolist())))
+        res.append(d)
+    return res
+
+
+def extract_args(items, capacities, download: bool = False):
+    """The osh_extract_frame / osh_extract_result arrays of OrbMatcher.extract: (frames, results, keep-alive, per-item outputs)."""
+    n = len(items)
+    pf, pr, pkeep, pouts = pyramid_args(items, download)
+    cf = (capi.ExtractFrame * max(n, 1))()
+    cr = (capi.ExtractResult * max(n, 1))()
+    keep, outs = [pkeep], []
+    for k, it in enumerate(items):
+        nl = int(pf[k].n_levels)
+        a = dict(scale=np.ascontiguousarray(it["scale"], np.float32), n_features=np.ascontiguousarray(it["n_features"], np.int32),
+                 pattern=np.ascontiguousarray(it["pattern"], np.int8), blur=None if it.get("blur_q8") is None else np.ascontiguousarray(it["blur_q8"], np.uint16))
+        f = cf[k]
+        f.image, f.n_levels, f.inv_scale = pf[k].image, nl, pf[k].inv_scale
+        f.scale, f.n_features = capi.ptr(a["scale"], capi.c_float_p), capi.ptr(a["n_features"], capi.c_int32_p)
+        f.ini_th, f.min_th = int(it.get("ini_th", 20)), int(it.get("min_th", 7))
+        f.pattern, f.blur_q8 = capi.ptr(a["pattern"], C.POINTER(C.c_int8)), capi.ptr(a["blur"], C.POINTER(C.c_uint16))
+        cap = int(capacities[k])
+        o = dict(level_count=np.zeros(nl, np.int32), xy=np.zeros((cap, 2), np.float32), level=np.zeros(cap, np.int32), response=np.zeros(cap, np.float32),
+                 angle=np.zeros(cap, np.float32), size=np.zeros(cap, np.float32), descriptors=np.zeros((cap, 32), np.uint8))
+        cr[k].capacity = cap
+        _wire_outputs(cr[k], o)
+        cr[k].levels, cr[k].border = pr[k].levels, pr[k].border
+        o.update({name: pouts[k][name] for name in ("levels", "bordered") if name in pouts[k]})
+        keep.append(a)
+        outs.append(o)
+    return cf, cr, keep, outs
+
+
+def _extract_outputs(cr, outs):
+    """Per item: the counts, the token and, when the arrays were large enough, the arrays cut to their lengths (else None)."""
+    res = []
+    for k, o in enumerate(outs):
+        n = int(cr[k].n_out)
+        d = dict(n_out=n, token=int(cr[k].pyramid_token), level_count=o["level_count"])
+        for name in ("xy", "level", "response", "angle", "size", "descriptors"):
+            d[name] = o[name][:n] if n <= int(cr[k].capacity) else None
+        d.update({name: o[name] for name in ("levels", "bordered") if name in o})
         res.append(d)
     return res
 
