@@ -41,13 +41,17 @@
 // ComputeKeyPointsOctTree keeps the reference's DistributeOctTree, an integrator opts in.  Its deviations from the reference's list
 // code (the stable sort, nIni == 0, a root index equal to nIni) are those of the rule; candidates the call refuses as invalid (not
 // finite, x outside [0, maxX - minX), negative y, an empty area) give a message on stderr and no keypoints.
+//
+// What more than one body needs is stated once: the size of a level, `pattern` as the table of the calls and the write-back of
+// :1143-1164 in csrc/host/orb_extract_steps.h (no device call; it goes into the integrator's tree with this file), the bordered
+// levels, a cv::Mat as an image of the calls and the messages that carry osh_last_error() in the helpers below.
 #include "ORBextractor.h"
 
-#include <cmath>
+#include <algorithm>
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
+#include "orb_extract_steps.h"
 #include "orbslam3_hip.h"
 #include "../orb_octree.h"
 
@@ -55,15 +59,48 @@ namespace ORB_SLAM3 {
 
 osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
 
-// The levels of mvImagePyramid as the calls read them: in place, views into the bordered images included
+// "ORBextractor::<who>: <what><then>" on stderr; `what` is the reason of the call that was just refused unless the caller has its own
+static void Report(const char* who, const char* what = osh_last_error(), const char* then = "") {
+  std::fprintf(stderr, "ORBextractor::%s: %s%s\n", who, what, then);
+}
+
+// This thread's context; null: reported under `who`
+static osh_orb_ctx* Context(const char* who) {
+  osh_orb_ctx* ctx = HostMatcherContext();
+  if (!ctx) Report(who);
+  return ctx;
+}
+
+// A cv::Mat as an osh_stereo_image or osh_pyramid_image: in place, a view into a bordered image with that image's stride
+template <class Image>
+static Image ImageOf(const cv::Mat& im) {
+  Image image{};
+  image.data = im.empty() ? nullptr : const_cast<uint8_t*>(im.ptr<uint8_t>(0));
+  image.rows = im.rows; image.cols = im.cols; image.stride = (int64_t)(size_t)im.step;
+  return image;
+}
+
+// The levels of mvImagePyramid as the calls read them
 static std::vector<osh_stereo_image> PyramidViews(const std::vector<cv::Mat>& levels, int nlevels) {
   std::vector<osh_stereo_image> pyramid(nlevels);
-  for (int level = 0; level < nlevels; ++level) {
-    const cv::Mat& im = levels[level];
-    pyramid[level].data = im.empty() ? nullptr : im.ptr<uint8_t>(0);
-    pyramid[level].rows = im.rows; pyramid[level].cols = im.cols; pyramid[level].stride = (int64_t)(size_t)im.step;
-  }
+  for (int level = 0; level < nlevels; ++level) pyramid[level] = ImageOf<osh_stereo_image>(levels[level]);
   return pyramid;
+}
+
+// :1174-1178 per level: the bordered `temp` is allocated and levels[level] is the view into it, as the reference leaves
+// mvImagePyramid[level]; out[level] is where a call writes that level.  Returns the first level that has no pixels or too many,
+// nlevels when there is none
+static int BorderedLevels(const cv::Mat& image, const std::vector<float>& invScale, int nlevels, std::vector<cv::Mat>& levels,
+                          std::vector<osh_pyramid_image>& out) {
+  levels.resize(nlevels); out.resize(nlevels);
+  for (int level = 0; level < nlevels; ++level) {
+    int h, w;
+    if (!LevelShape(image.rows, image.cols, invScale[level], h, w)) return level;
+    cv::Mat temp(h + 2 * kEdge, w + 2 * kEdge);
+    levels[level] = temp.view(kEdge, kEdge, h, w);
+    out[level] = ImageOf<osh_pyramid_image>(levels[level]);
+  }
+  return nlevels;
 }
 
 // The `total` keypoints of allKeypoints, level after level, as the arrays of one call; `angle` may be null
@@ -90,7 +127,6 @@ static bool ByTokenOrPyramid(bool& have_token, ByToken by_token, ByPyramid by_py
 }
 
 void ORBextractor::ComputePyramid(cv::Mat image) {
-  constexpr int kEdge = 19;   // EDGE_THRESHOLD
   mnBuiltPyramidToken = 0;
   mvImagePyramid.assign(nlevels > 0 ? nlevels : 0, cv::Mat());
   if (nlevels <= 0 || image.empty()) return;
@@ -98,37 +134,17 @@ void ORBextractor::ComputePyramid(cv::Mat image) {
     std::fprintf(stderr, "ORBextractor::ComputePyramid: mvInvScaleFactor has %d of %d entries\n", (int)mvInvScaleFactor.size(), nlevels);
     return;
   }
-  // :1174-1178 per level: the bordered `temp` and mvImagePyramid[level] as the view into it; the sizes are cvRound's
-  std::vector<cv::Mat> levels(nlevels);
-  std::vector<osh_pyramid_image> out(nlevels);
-  for (int level = 0; level < nlevels; ++level) {
-    const float scale = mvInvScaleFactor[level];
-    const float fw = (float)image.cols * scale, fh = (float)image.rows * scale;
-    const int w = fw >= 0.f && fw < 1.0e6f ? (int)std::nearbyint(fw) : 0, h = fh >= 0.f && fh < 1.0e6f ? (int)std::nearbyint(fh) : 0;
-    if (w <= 0 || h <= 0) {
-      std::fprintf(stderr, "ORBextractor::ComputePyramid: level %d has no pixels or too many\n", level);
-      return;
-    }
-    cv::Mat temp(h + 2 * kEdge, w + 2 * kEdge);
-    levels[level] = temp.view(kEdge, kEdge, h, w);
-    out[level].data = levels[level].ptr<uint8_t>(0);
-    out[level].rows = h; out[level].cols = w; out[level].stride = (int64_t)(size_t)levels[level].step;
-  }
-  osh_orb_ctx* ctx = HostMatcherContext();
-  if (!ctx) {
-    std::fprintf(stderr, "ORBextractor::ComputePyramid: %s\n", osh_last_error());
-    return;
-  }
+  std::vector<cv::Mat> levels;
+  std::vector<osh_pyramid_image> out;
+  const int bad = BorderedLevels(image, mvInvScaleFactor, nlevels, levels, out);
+  if (bad < nlevels) { std::fprintf(stderr, "ORBextractor::ComputePyramid: level %d has no pixels or too many\n", bad); return; }
+  osh_orb_ctx* ctx = Context("ComputePyramid");
+  if (!ctx) return;
   // the resize and copyMakeBorder of every level (:1181-1193) in one call; the levels stay on the device under the token
-  osh_pyramid_frame frame{};
-  frame.image.data = image.ptr<uint8_t>(0); frame.image.rows = image.rows; frame.image.cols = image.cols; frame.image.stride = (int64_t)(size_t)image.step;
-  frame.n_levels = nlevels; frame.inv_scale = mvInvScaleFactor.data();
+  const osh_pyramid_frame frame{ImageOf<osh_stereo_image>(image), nlevels, mvInvScaleFactor.data()};
   osh_pyramid_result res{};
   res.levels = out.data(); res.border = kEdge;
-  if (osh_orb_pyramid_build(ctx, 1, &frame, &res) != OSH_OK) {
-    std::fprintf(stderr, "ORBextractor::ComputePyramid: %s\n", osh_last_error());
-    return;
-  }
+  if (osh_orb_pyramid_build(ctx, 1, &frame, &res) != OSH_OK) return Report("ComputePyramid");
   mvImagePyramid = levels;
   mnBuiltPyramidToken = res.pyramid_token;
 }
@@ -144,11 +160,8 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
     std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: the pyramid has %d of %d levels\n", (int)mvImagePyramid.size(), nlevels);
     return;
   }
-  osh_orb_ctx* ctx = HostMatcherContext();
-  if (!ctx) {
-    std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: %s\n", osh_last_error());
-    return;
-  }
+  osh_orb_ctx* ctx = Context("ComputeKeyPointsOctTree");
+  if (!ctx) return;
 
   // every cell of every level (:787-872) in one call
   const std::vector<osh_stereo_image> pyramid = PyramidViews(mvImagePyramid, nlevels);
@@ -165,10 +178,8 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
   for (int attempt = 0; attempt < 2; ++attempt) {
     xy.resize(capacity * 2); response.resize(capacity);
     res.capacity = (int32_t)capacity; res.xy = xy.data(); res.response = response.data();
-    if (!ByTokenOrPyramid(use_resident, [&] { return osh_orb_fast_detect_resident(ctx, 1, &resident, &res); }, [&] { return osh_orb_fast_detect(ctx, 1, &frame, &res); })) {
-      std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: %s\n", osh_last_error());
-      return;
-    }
+    if (!ByTokenOrPyramid(use_resident, [&] { return osh_orb_fast_detect_resident(ctx, 1, &resident, &res); }, [&] { return osh_orb_fast_detect(ctx, 1, &frame, &res); }))
+      return Report("ComputeKeyPointsOctTree");
     if ((size_t)res.n_out <= capacity) break;
     capacity = (size_t)res.n_out;   // the counts came back without the arrays: once more with room for them
   }
@@ -203,7 +214,7 @@ void ORBextractor::ComputeKeyPointsOctTree(std::vector<std::vector<cv::KeyPoint>
   const osh_ic_angle_frame icf{0, nullptr, res.pyramid_token, (int32_t)total, pts.data(), lvl.data()};
   const osh_ic_angle_result icr{angle.data(), nullptr, nullptr};
   if (osh_orb_ic_angle(ctx, 1, &icf, &icr) != OSH_OK) {
-    std::fprintf(stderr, "ORBextractor::ComputeKeyPointsOctTree: %s\n", osh_last_error());
+    Report("ComputeKeyPointsOctTree");
     for (std::vector<cv::KeyPoint>& kps : allKeypoints) kps.clear();
     return;
   }
@@ -222,19 +233,19 @@ std::vector<cv::KeyPoint> ORBextractor::DistributeOctTreeDevice(const std::vecto
   const char* why = "";
   const int valid = osh::oct_validate_list(n, xy.data(), response.data(), W, H, N, &why);
   if (valid == osh::kOctInvalid) {
-    std::fprintf(stderr, "ORBextractor::DistributeOctTreeDevice: %s\n", why);
+    Report("DistributeOctTreeDevice", why);
     return vResultKeys;
   }
   std::vector<int32_t> index(n);   // a node keeps one of its keys: never more than n
   int kept = -1;
   if (valid != osh::kOctOk) {
-    std::fprintf(stderr, "ORBextractor::DistributeOctTreeDevice: %s: on the host\n", why);
+    Report("DistributeOctTreeDevice", why, ": on the host");
   } else {
     const osh_octree_list list{n, xy.data(), response.data(), W, H, N};
     osh_octree_result res{n, 0, 0, index.data()};
     osh_orb_ctx* ctx = HostMatcherContext();
     if (ctx && osh_orb_octree_distribute(ctx, 1, &list, &res) == OSH_OK) kept = res.n_out;
-    else std::fprintf(stderr, "ORBextractor::DistributeOctTreeDevice: %s: on the host\n", osh_last_error());
+    else Report("DistributeOctTreeDevice", osh_last_error(), ": on the host");
   }
   if (kept < 0) {
     std::vector<int> host;
@@ -250,7 +261,6 @@ std::vector<cv::KeyPoint> ORBextractor::DistributeOctTreeDevice(const std::vecto
 void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
                                 std::vector<std::vector<cv::KeyPoint> >& vKeypoints, std::vector<cv::Mat>& vDescriptors,
                                 const std::vector<std::vector<int> >& vLappingAreas, std::vector<int>& vMonoIndex, bool bKeepPyramid) {
-  constexpr int kEdge = 19;   // EDGE_THRESHOLD
   const size_t nExtractors = vpExtractors.size();
   vKeypoints.resize(nExtractors);
   vDescriptors.resize(nExtractors);
@@ -289,39 +299,27 @@ void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, 
     Job& j = jobs.back();
     j.extractor = i;
     j.table.resize(1024);
-    for (int k = 0; k < 512; ++k) {
-      ok = ok && ex->pattern[k].x >= -128 && ex->pattern[k].x <= 127 && ex->pattern[k].y >= -128 && ex->pattern[k].y <= 127;
-      j.table[2 * k] = (int8_t)ex->pattern[k].x; j.table[2 * k + 1] = (int8_t)ex->pattern[k].y;
-    }
+    if (!PatternTable(ex->pattern.data(), j.table.data())) ok = false;
     size_t capacity = 0;   // the quadtree keeps at most max(N + 3, 4 nIni) keypoints of a level, nIni <= OSH_OCTREE_MAX_ROOTS
     for (int l = 0; l < nl; ++l) capacity += (size_t)std::max(std::max(ex->mnFeaturesPerLevel[l], 0) + 3, 4 * OSH_OCTREE_MAX_ROOTS);
     j.levelCount.resize(nl); j.level.resize(capacity); j.xy.resize(capacity * 2); j.response.resize(capacity); j.angle.resize(capacity);
     j.size.resize(capacity); j.desc.resize(capacity * 32);
-    if (bKeepPyramid) {   // :1174-1178 per level, as ComputePyramid: the bordered `temp` and the level as the view into it
-      j.levels.resize(nl); j.out.resize(nl);
-      for (int l = 0; l < nl; ++l) {
-        const float fw = (float)vImages[i].cols * ex->mvInvScaleFactor[l], fh = (float)vImages[i].rows * ex->mvInvScaleFactor[l];
-        const int w = fw >= 0.f && fw < 1.0e6f ? (int)std::nearbyint(fw) : 0, h = fh >= 0.f && fh < 1.0e6f ? (int)std::nearbyint(fh) : 0;
-        if (w <= 0 || h <= 0) { std::fprintf(stderr, "ORBextractor::ExtractBatch: extractor %d: level %d has no pixels or too many\n", (int)i, l); ok = false; break; }
-        cv::Mat temp(h + 2 * kEdge, w + 2 * kEdge);
-        j.levels[l] = temp.view(kEdge, kEdge, h, w);
-        j.out[l].data = j.levels[l].ptr<uint8_t>(0);
-        j.out[l].rows = h; j.out[l].cols = w; j.out[l].stride = (int64_t)(size_t)j.levels[l].step;
-      }
+    if (bKeepPyramid) {   // the levels as ComputePyramid leaves them
+      const int bad = BorderedLevels(vImages[i], ex->mvInvScaleFactor, nl, j.levels, j.out);
+      if (bad < nl) { std::fprintf(stderr, "ORBextractor::ExtractBatch: extractor %d: level %d has no pixels or too many\n", (int)i, bad); ok = false; }
     }
   }
   if (!ok) std::fprintf(stderr, "ORBextractor::ExtractBatch: nothing extracted\n");
-  osh_orb_ctx* ctx = ok && !jobs.empty() ? HostMatcherContext() : nullptr;
-  if (ok && !jobs.empty() && !ctx) { std::fprintf(stderr, "ORBextractor::ExtractBatch: %s\n", osh_last_error()); ok = false; }
   if (!ok || jobs.empty()) return;
+  osh_orb_ctx* ctx = Context("ExtractBatch");
+  if (!ctx) return;
   std::vector<osh_extract_frame> frames(jobs.size());
   std::vector<osh_extract_result> results(jobs.size());
   for (size_t k = 0; k < jobs.size(); ++k) {
     Job& j = jobs[k];
     const ORBextractor* ex = vpExtractors[j.extractor];
-    const cv::Mat& image = vImages[j.extractor];
     osh_extract_frame& f = frames[k];
-    f.image.data = image.ptr<uint8_t>(0); f.image.rows = image.rows; f.image.cols = image.cols; f.image.stride = (int64_t)(size_t)image.step;
+    f.image = ImageOf<osh_stereo_image>(vImages[j.extractor]);
     f.n_levels = ex->nlevels; f.inv_scale = ex->mvInvScaleFactor.data(); f.scale = ex->mvScaleFactor.data();
     f.ini_th = ex->iniThFAST; f.min_th = ex->minThFAST; f.n_features = ex->mnFeaturesPerLevel.data();
     f.pattern = j.table.data(); f.blur_q8 = nullptr;
@@ -331,10 +329,7 @@ void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, 
     r.response = j.response.data(); r.angle = j.angle.data(); r.size = j.size.data(); r.descriptors = j.desc.data();
     r.levels = bKeepPyramid ? j.out.data() : nullptr; r.border = kEdge;
   }
-  if (osh_orb_extract(ctx, (int32_t)jobs.size(), frames.data(), results.data()) != OSH_OK) {
-    std::fprintf(stderr, "ORBextractor::ExtractBatch: %s\n", osh_last_error());
-    return;
-  }
+  if (osh_orb_extract(ctx, (int32_t)jobs.size(), frames.data(), results.data()) != OSH_OK) return Report("ExtractBatch");
   for (size_t k = 0; k < jobs.size(); ++k) {
     const Job& j = jobs[k];
     ORBextractor* ex = vpExtractors[j.extractor];
@@ -347,20 +342,15 @@ void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, 
     cv::Mat& descriptors = vDescriptors[j.extractor];
     keypoints = std::vector<cv::KeyPoint>(nkeypoints);
     if (nkeypoints) descriptors.create(nkeypoints, 32, CV_8U);
-    // :1120-1167: scale to level 0, keypoints of the lapping area from the back, the others from the front
-    const std::vector<int>& lapping = vLappingAreas[j.extractor];
-    int monoIndex = 0, stereoIndex = nkeypoints - 1;
+    WriteBack<cv::KeyPoint> place(nkeypoints, ex->mvScaleFactor.data(), vLappingAreas[j.extractor].data(), keypoints.data(),
+                                  nkeypoints ? descriptors.ptr<uint8_t>(0) : nullptr, (size_t)descriptors.step);
     for (int i = 0; i < nkeypoints; ++i) {
       cv::KeyPoint keypoint;
-      const int level = j.level[i];
       keypoint.pt.x = j.xy[2 * i]; keypoint.pt.y = j.xy[2 * i + 1]; keypoint.response = j.response[i]; keypoint.angle = j.angle[i];
-      keypoint.size = j.size[i]; keypoint.octave = level; keypoint.class_id = -1;
-      if (level != 0) keypoint.pt *= ex->mvScaleFactor[level];
-      const int at = keypoint.pt.x >= lapping[0] && keypoint.pt.x <= lapping[1] ? stereoIndex-- : monoIndex++;
-      keypoints.at(at) = keypoint;
-      std::memcpy(descriptors.ptr<uint8_t>(at), &j.desc[32 * (size_t)i], 32);
+      keypoint.size = j.size[i]; keypoint.octave = j.level[i]; keypoint.class_id = -1;
+      place(keypoint, &j.desc[32 * (size_t)i]);
     }
-    vMonoIndex[j.extractor] = monoIndex;
+    vMonoIndex[j.extractor] = place.monoIndex;
   }
 }
 
@@ -380,16 +370,12 @@ int ORBextractor::operator()(cv::InputArray _image, cv::InputArray /*_mask*/, st
   if (nkeypoints) {
     bool ok = pattern.size() == 512 && (int)vLappingArea.size() >= 2;
     if (!ok) std::fprintf(stderr, "ORBextractor::operator(): the pattern has %d of 512 points or vLappingArea fewer than 2 entries\n", (int)pattern.size());
-    osh_orb_ctx* ctx = ok ? HostMatcherContext() : nullptr;
-    if (ok && !ctx) { std::fprintf(stderr, "ORBextractor::operator(): %s\n", osh_last_error()); ok = false; }
-    if (ok) {
+    osh_orb_ctx* ctx = ok ? Context("operator()") : nullptr;
+    if (ctx) {
       std::vector<float> pts, angle;
       std::vector<int32_t> lvl;
       int8_t table[1024];
-      for (int i = 0; i < 512; ++i) {
-        ok = ok && pattern[i].x >= -128 && pattern[i].x <= 127 && pattern[i].y >= -128 && pattern[i].y <= 127;
-        table[2 * i] = (int8_t)pattern[i].x; table[2 * i + 1] = (int8_t)pattern[i].y;
-      }
+      ok = PatternTable(pattern.data(), table);
       if (!ok) std::fprintf(stderr, "ORBextractor::operator(): a pattern point does not fit 8 bits\n");
       FlattenKeypoints(allKeypoints, nlevels, (size_t)nkeypoints, pts, lvl, &angle);
       const std::vector<osh_stereo_image> pyramid = PyramidViews(mvImagePyramid, nlevels);
@@ -402,10 +388,10 @@ int ORBextractor::operator()(cv::InputArray _image, cv::InputArray /*_mask*/, st
       bool have_token = mnPyramidToken != 0;
       if (ok && !ByTokenOrPyramid(have_token, [&] { return osh_orb_describe(ctx, 1, &named, &r); }, [&] { return osh_orb_describe(ctx, 1, &brought, &r); })) {
         ok = false;
-        std::fprintf(stderr, "ORBextractor::operator(): %s\n", osh_last_error());
+        Report("operator()");
       }
     }
-    if (!ok) { nkeypoints = 0; for (std::vector<cv::KeyPoint>& kps : allKeypoints) kps.clear(); }
+    if (!ok || !ctx) { nkeypoints = 0; for (std::vector<cv::KeyPoint>& kps : allKeypoints) kps.clear(); }
   }
 
   cv::Mat descriptors;
@@ -413,20 +399,13 @@ int ORBextractor::operator()(cv::InputArray _image, cv::InputArray /*_mask*/, st
   else { _descriptors.create(nkeypoints, 32, CV_8U); descriptors = _descriptors.getMat(); }
   _keypoints = std::vector<cv::KeyPoint>(nkeypoints);
 
-  // :1120-1167: scale to level 0, keypoints of the lapping area from the back, the others from the front
-  int monoIndex = 0, stereoIndex = nkeypoints - 1;
+  // ComputeKeyPointsOctTree left the level of every keypoint in its `octave`
+  WriteBack<cv::KeyPoint> place(nkeypoints, mvScaleFactor.data(), vLappingArea.data(), _keypoints.data(), nkeypoints ? descriptors.ptr<uint8_t>(0) : nullptr,
+                                (size_t)descriptors.step);
   size_t i = 0;
-  for (int level = 0; level < nlevels; ++level) {
-    const float scale = mvScaleFactor[level];
-    for (cv::KeyPoint& keypoint : allKeypoints[level]) {
-      if (level != 0) keypoint.pt *= scale;
-      const int at = keypoint.pt.x >= vLappingArea[0] && keypoint.pt.x <= vLappingArea[1] ? stereoIndex-- : monoIndex++;
-      _keypoints.at(at) = keypoint;
-      std::memcpy(descriptors.ptr<uint8_t>(at), &desc[32 * i], 32);
-      ++i;
-    }
-  }
-  return monoIndex;
+  for (const std::vector<cv::KeyPoint>& kps : allKeypoints)
+    for (const cv::KeyPoint& keypoint : kps) place(keypoint, &desc[32 * i++]);
+  return place.monoIndex;
 }
 
 }  // namespace ORB_SLAM3

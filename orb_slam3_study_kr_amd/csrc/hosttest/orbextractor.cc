@@ -2,7 +2,7 @@
 // ORBextractor::ComputeKeyPointsOctTree and ORBextractor::operator() (csrc/host/ORBextractor.cc), and the C wrappers that drive them
 // (include/orbslam3_hip_host.h): the constructor (scale tables and mnFeaturesPerLevel as reference src/ORBextractor.cc:409-447, and
 // a generated sampling table), a DistributeOctTree test double, osh_host_orbextractor_compute_keypoints,
-// osh_host_orbextractor_extract, osh_host_orbextractor_compute_pyramid, and csrc/orb_fast.h / csrc/orb_brief.h / csrc/orb_pyramid.h
+// osh_host_orbextractor_extract, osh_host_orbextractor_extract_batch, osh_host_orbextractor_compute_pyramid, and csrc/orb_fast.h / csrc/orb_brief.h / csrc/orb_pyramid.h
 // on the host in one thread (osh_host_orb_fast_cpu, osh_host_orb_ic_angle_cpu, osh_host_orb_describe_cpu, osh_host_orb_pyramid_cpu:
 // the CPU baselines of profiles/fast_timing.py, profiles/brief_timing.py and profiles/pyramid_timing.py;
 // osh_host_orb_fast_level_cells).  Test library only.  ComputePyramid is the product body of csrc/host/ORBextractor.cc.
@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "ORBextractor.h"
+#include "orb_extract_steps.h"
 #include "../orb_brief.h"
 #include "../orb_fast.h"
 #include "../orb_pyramid.h"
@@ -124,6 +125,74 @@ std::vector<cv::KeyPoint> ORBextractor::DistributeOctTree(const std::vector<cv::
 
 using namespace ORB_SLAM3;
 
+namespace {
+// The stand-in extractor, the image (empty: no rows or no columns) and the lapping area of an osh_host_extract_input
+struct Standin {
+  ORBextractor ex;
+  cv::Mat image;
+  std::vector<int> lapping;
+  explicit Standin(const osh_host_extract_input& in)
+      : ex(in.nfeatures, in.scale_factor, in.nlevels, in.ini_th, in.min_th), lapping{in.lapping[0], in.lapping[1]} {
+    if (!in.rows || !in.cols) return;
+    image = cv::Mat(in.rows, in.cols);
+    std::memcpy(image.ptr<uint8_t>(0), in.pixels, (size_t)in.rows * in.cols);
+  }
+};
+
+// The keypoints of `all`, level after level: the count of every level, and while there is room (`capacity`) the fields whose array
+// is not null.  Returns how many keypoints there are, so a first pass without room counts
+int PutLevelKeypoints(const std::vector<std::vector<cv::KeyPoint> >& all, int nlevels, int32_t capacity, int32_t* level_count, float* xy, float* angle,
+                      float* response, float* size = nullptr, int32_t* octave = nullptr) {
+  size_t n = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    level_count[l] = (int32_t)all[l].size();
+    for (const cv::KeyPoint& kp : all[l]) {
+      if (n < (size_t)capacity) {
+        if (xy) { xy[2 * n] = kp.pt.x; xy[2 * n + 1] = kp.pt.y; }
+        if (angle) angle[n] = kp.angle;
+        if (response) response[n] = kp.response;
+        if (size) size[n] = kp.size;
+        if (octave) octave[n] = kp.octave;
+      }
+      ++n;
+    }
+  }
+  return (int)n;
+}
+
+// The shapes of the extractor's levels and, while they fit pixel_capacity, their pixels one after the other without the borders
+void PutPyramid(const ORBextractor& ex, int nlevels, const osh_host_extract_output& o) {
+  size_t pixels = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    const cv::Mat im = l < (int)ex.mvImagePyramid.size() ? ex.mvImagePyramid[l] : cv::Mat();
+    o.level_rows[l] = im.rows; o.level_cols[l] = im.cols;
+    if (o.pyramid && pixels + (size_t)im.rows * im.cols <= (size_t)o.pixel_capacity)
+      for (int r = 0; r < im.rows; ++r) std::memcpy(o.pyramid + pixels + (size_t)r * im.cols, im.ptr<uint8_t>(r), (size_t)im.cols);
+    pixels += (size_t)im.rows * im.cols;
+  }
+  *o.pixels_needed = (int32_t)pixels;
+}
+
+// _keypoints and _descriptors as a call left them, the first `capacity` of them.  False: the descriptors are not [keys.size(), 32]
+bool PutKeypoints(const std::vector<cv::KeyPoint>& keys, const cv::Mat& desc, const osh_host_extract_output& o) {
+  if (!keys.empty() && (desc.rows != (int)keys.size() || desc.cols != 32)) return false;
+  for (size_t i = 0; i < keys.size() && i < (size_t)o.capacity; ++i) {
+    if (o.xy) { o.xy[2 * i] = keys[i].pt.x; o.xy[2 * i + 1] = keys[i].pt.y; }
+    if (o.angle) o.angle[i] = keys[i].angle;
+    if (o.size) o.size[i] = keys[i].size;
+    if (o.response) o.response[i] = keys[i].response;
+    if (o.octave) o.octave[i] = keys[i].octave;
+    if (o.descriptors) std::memcpy(o.descriptors + 32 * i, desc.ptr<uint8_t>((int)i), 32);
+  }
+  return true;
+}
+
+// The whole bordered image of a level (the level is a view at (19, 19) of it) into `dst`, its rows im.step bytes apart there too
+void CopyBordered(const cv::Mat& im, uint8_t* dst) {
+  for (int r = -kEdge; r < im.rows + kEdge; ++r) std::memcpy(dst + (size_t)(r + kEdge) * im.step, im.ptr<uint8_t>(0) + (long long)r * (long long)im.step - kEdge, im.step);
+}
+}  // namespace
+
 extern "C" int osh_host_orb_fast_cpu(int32_t n_frames, const osh_fast_frame* frames, osh_fast_result* results, double* ms) {
   if (n_frames < 0 || (n_frames && (!frames || !results))) return -1;
   const auto t0 = std::chrono::steady_clock::now();
@@ -220,13 +289,11 @@ extern "C" int osh_host_orb_pyramid_cpu(int32_t n_frames, const osh_pyramid_fram
 }
 
 extern "C" int osh_host_orbextractor_compute_pyramid(const osh_host_extract_input* in, const osh_host_pyramid_output* out) {
-  constexpr int kEdge = 19;
   if (!in || !out || in->nlevels < 1 || in->rows <= 0 || in->cols <= 0 || !in->pixels || !out->level_rows || !out->level_cols || !out->pixels_needed ||
       !out->level_count || !out->hand_level_count || !out->built_token || out->capacity < 0 || out->pixel_capacity < 0) return -1;
-  ORBextractor ex(in->nfeatures, in->scale_factor, in->nlevels, in->ini_th, in->min_th);
-  cv::Mat image(in->rows, in->cols);
-  std::memcpy(image.ptr<uint8_t>(0), in->pixels, (size_t)in->rows * in->cols);
-  ex.ComputePyramid(image);
+  Standin s(*in);
+  ORBextractor& ex = s.ex;
+  ex.ComputePyramid(s.image);
   out->built_token[0] = ex.mnBuiltPyramidToken; out->built_token[1] = 0;
   if ((int)ex.mvImagePyramid.size() != in->nlevels) return -2;
   // the whole bordered images: the levels are views at (19, 19) of them
@@ -237,42 +304,26 @@ extern "C" int osh_host_orbextractor_compute_pyramid(const osh_host_extract_inpu
     if (im.empty()) continue;
     if (im.step != (size_t)im.cols + 2 * kEdge) return -2;
     const size_t bytes = (size_t)(im.rows + 2 * kEdge) * im.step;
-    if (out->bordered && pixels + bytes <= (size_t)out->pixel_capacity)
-      for (int r = -kEdge; r < im.rows + kEdge; ++r) std::memcpy(out->bordered + pixels + (size_t)(r + kEdge) * im.step, im.ptr<uint8_t>(0) + (long long)r * (long long)im.step - kEdge, im.step);
+    if (out->bordered && pixels + bytes <= (size_t)out->pixel_capacity) CopyBordered(im, out->bordered + pixels);
     pixels += bytes;
   }
   *out->pixels_needed = (int32_t)pixels;
-  auto report = [&](const std::vector<std::vector<cv::KeyPoint> >& all, int32_t* level_count, float* xy, float* angle, float* response) {
-    size_t n = 0;
-    for (int l = 0; l < in->nlevels; ++l) {
-      level_count[l] = (int32_t)all[l].size();
-      for (const cv::KeyPoint& kp : all[l]) {
-        if (n < (size_t)out->capacity) {
-          if (xy) { xy[2 * n] = kp.pt.x; xy[2 * n + 1] = kp.pt.y; }
-          if (angle) angle[n] = kp.angle;
-          if (response) response[n] = kp.response;
-        }
-        ++n;
-      }
-    }
-    return (int)n;
-  };
   // ComputeKeyPointsOctTree right after ComputePyramid (the resident levels), then on a hand-set copy of that pyramid
   std::vector<std::vector<cv::KeyPoint> > all;
   ex.ComputeKeyPointsOctTree(all);
   if ((int)all.size() != in->nlevels) return -2;
-  const int n = report(all, out->level_count, out->xy, out->angle, out->response);
+  const int n = PutLevelKeypoints(all, in->nlevels, out->capacity, out->level_count, out->xy, out->angle, out->response);
   for (int l = 0; l < in->nlevels; ++l) {
     const cv::Mat im = ex.mvImagePyramid[l];
     if (im.empty()) continue;
     cv::Mat whole(im.rows + 2 * kEdge, im.cols + 2 * kEdge);
-    for (int r = -kEdge; r < im.rows + kEdge; ++r) std::memcpy(whole.ptr<uint8_t>(r + kEdge), im.ptr<uint8_t>(0) + (long long)r * (long long)im.step - kEdge, im.step);
+    CopyBordered(im, whole.ptr<uint8_t>(0));
     ex.mvImagePyramid[l] = whole.view(kEdge, kEdge, im.rows, im.cols);
   }
   out->built_token[1] = ex.mnBuiltPyramidToken;   // 0: the first call consumed it
   ex.ComputeKeyPointsOctTree(all);
   if ((int)all.size() != in->nlevels) return -2;
-  const int n_hand = report(all, out->hand_level_count, out->hand_xy, out->hand_angle, out->hand_response);
+  const int n_hand = PutLevelKeypoints(all, in->nlevels, out->capacity, out->hand_level_count, out->hand_xy, out->hand_angle, out->hand_response);
   return std::max(n, n_hand);
 }
 
@@ -313,7 +364,7 @@ extern "C" int osh_host_orbextractor_compute_keypoints(const osh_host_orbextract
     if (out->features_per_level) out->features_per_level[l] = ex.mnFeaturesPerLevel[l];
     if (out->scale_factors) out->scale_factors[l] = ex.mvScaleFactor[l];
   }
-  size_t n = 0, nc = 0;
+  size_t nc = 0;
   for (const ORBextractor::DistributeCall& d : ex.mvDistributeCalls) {
     if (d.level < 0 || d.level >= in->nlevels) return -2;
     out->cand_level_count[d.level] += (int32_t)d.keys.size();
@@ -326,20 +377,7 @@ extern "C" int osh_host_orbextractor_compute_keypoints(const osh_host_orbextract
       ++nc;
     }
   }
-  for (int l = 0; l < in->nlevels; ++l) {
-    out->level_count[l] = (int32_t)all[l].size();
-    for (const cv::KeyPoint& kp : all[l]) {
-      if (n < (size_t)out->capacity) {
-        if (out->xy) { out->xy[2 * n] = kp.pt.x; out->xy[2 * n + 1] = kp.pt.y; }
-        if (out->response) out->response[n] = kp.response;
-        if (out->angle) out->angle[n] = kp.angle;
-        if (out->size) out->size[n] = kp.size;
-        if (out->octave) out->octave[n] = kp.octave;
-      }
-      ++n;
-    }
-  }
-  return (int)n;
+  return PutLevelKeypoints(all, in->nlevels, out->capacity, out->level_count, out->xy, out->angle, out->response, out->size, out->octave);
 }
 
 extern "C" int osh_host_orb_describe_cpu(int32_t n_frames, const osh_describe_frame* frames, const osh_describe_result* results, double* ms) {
@@ -388,63 +426,66 @@ extern "C" int osh_host_brief_reach(const int8_t* pattern) { return pattern ? os
 
 extern "C" int osh_host_orbextractor_pattern(int8_t* pattern) {
   if (!pattern) return -1;
-  const ORBextractor ex(1, 1.2f, 1, 20, 7);
-  for (int i = 0; i < 512; ++i) { pattern[2 * i] = (int8_t)ex.pattern[i].x; pattern[2 * i + 1] = (int8_t)ex.pattern[i].y; }
+  PatternTable(ORBextractor(1, 1.2f, 1, 20, 7).pattern.data(), pattern);
   return 0;
 }
 
 extern "C" int osh_host_orbextractor_extract(const osh_host_extract_input* in, const osh_host_extract_output* out) {
   if (!in || !out || in->nlevels < 1 || in->rows < 0 || in->cols < 0 || (in->rows && in->cols && !in->pixels) || !out->level_rows || !out->level_cols ||
       !out->level_count || !out->ret || !out->desc_rows || !out->pixels_needed || out->capacity < 0 || out->pixel_capacity < 0) return -1;
-  ORBextractor ex(in->nfeatures, in->scale_factor, in->nlevels, in->ini_th, in->min_th);
-  cv::Mat image;
-  if (in->rows && in->cols) {
-    image = cv::Mat(in->rows, in->cols);
-    std::memcpy(image.ptr<uint8_t>(0), in->pixels, (size_t)in->rows * in->cols);
-  }
-  std::vector<int> lapping{in->lapping[0], in->lapping[1]};
+  Standin s(*in);
+  ORBextractor& ex = s.ex;
   // the stages on their own first: what operator() computes inside is a function of the image alone
   std::vector<std::vector<cv::KeyPoint> > all(in->nlevels);
-  size_t pixels = 0;
-  if (!image.empty()) {
-    ex.ComputePyramid(image);
+  if (!s.image.empty()) {
+    ex.ComputePyramid(s.image);
     ex.ComputeKeyPointsOctTree(all);
     if ((int)all.size() != in->nlevels) return -1;
   }
-  for (int l = 0; l < in->nlevels; ++l) {
-    const cv::Mat& im = image.empty() ? image : ex.mvImagePyramid[l];
-    out->level_rows[l] = im.rows; out->level_cols[l] = im.cols;
-    if (out->pyramid && pixels + (size_t)im.rows * im.cols <= (size_t)out->pixel_capacity)
-      for (int r = 0; r < im.rows; ++r) std::memcpy(out->pyramid + pixels + (size_t)r * im.cols, im.ptr<uint8_t>(r), (size_t)im.cols);
-    pixels += (size_t)im.rows * im.cols;
-  }
-  *out->pixels_needed = (int32_t)pixels;
-  size_t n = 0;
-  for (int l = 0; l < in->nlevels; ++l) {
-    out->level_count[l] = (int32_t)all[l].size();
-    for (const cv::KeyPoint& kp : all[l]) {
-      if (n < (size_t)out->capacity) {
-        if (out->level_xy) { out->level_xy[2 * n] = kp.pt.x; out->level_xy[2 * n + 1] = kp.pt.y; }
-        if (out->level_angle) out->level_angle[n] = kp.angle;
-      }
-      ++n;
-    }
-  }
+  PutPyramid(ex, in->nlevels, *out);
+  PutLevelKeypoints(all, in->nlevels, out->capacity, out->level_count, out->level_xy, out->level_angle, nullptr);
   std::vector<cv::KeyPoint> keys(3);   // what the call must replace
   cv::Mat desc(2, 32);
   const auto t0 = std::chrono::steady_clock::now();
-  *out->ret = ex(image, cv::Mat(), keys, desc, lapping);
+  *out->ret = ex(s.image, cv::Mat(), keys, desc, s.lapping);
   if (out->call_ms) *out->call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out->desc_rows = desc.rows;
   if (*out->ret < 0) return 0;   // an empty image: nothing was touched
-  if (!keys.empty() && (desc.rows != (int)keys.size() || desc.cols != 32)) return -1;
-  for (size_t i = 0; i < keys.size() && i < (size_t)out->capacity; ++i) {
-    if (out->xy) { out->xy[2 * i] = keys[i].pt.x; out->xy[2 * i + 1] = keys[i].pt.y; }
-    if (out->angle) out->angle[i] = keys[i].angle;
-    if (out->size) out->size[i] = keys[i].size;
-    if (out->response) out->response[i] = keys[i].response;
-    if (out->octave) out->octave[i] = keys[i].octave;
-    if (out->descriptors) std::memcpy(out->descriptors + 32 * i, desc.ptr<uint8_t>((int)i), 32);
-  }
+  if (!PutKeypoints(keys, desc, *out)) return -1;
   return (int)keys.size();
+}
+
+extern "C" int osh_host_orbextractor_extract_batch(int32_t n, const osh_host_extract_input* in, const osh_host_extract_output* out, int32_t keep_pyramid,
+                                                   uint64_t* tokens) {
+  if (n < 0 || (n && (!in || !out || !tokens))) return -1;
+  std::vector<Standin> standins;
+  standins.reserve((size_t)(n > 0 ? n : 0));   // the extractors stay where they are
+  for (int i = 0; i < n; ++i) {
+    const osh_host_extract_input& a = in[i];
+    const osh_host_extract_output& o = out[i];
+    if (a.nlevels < 1 || a.rows < 0 || a.cols < 0 || (a.rows && a.cols && !a.pixels) || !o.level_rows || !o.level_cols || !o.ret || !o.desc_rows || !o.pixels_needed ||
+        o.capacity < 0 || o.pixel_capacity < 0) return -1;
+    standins.emplace_back(a);
+  }
+  std::vector<ORBextractor*> extractors;
+  std::vector<cv::Mat> images;
+  std::vector<std::vector<int> > lapping;
+  for (Standin& s : standins) { extractors.push_back(&s.ex); images.push_back(s.image); lapping.push_back(s.lapping); }
+  std::vector<std::vector<cv::KeyPoint> > keys((size_t)n, std::vector<cv::KeyPoint>(3));   // what the call must replace
+  std::vector<cv::Mat> desc((size_t)n, cv::Mat(2, 32));
+  std::vector<int> mono;
+  const auto t0 = std::chrono::steady_clock::now();
+  ORBextractor::ExtractBatch(extractors, images, keys, desc, lapping, mono, keep_pyramid != 0);
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if ((int)keys.size() != n || (int)desc.size() != n || (int)mono.size() != n) return -1;
+  for (int i = 0; i < n; ++i) {
+    const osh_host_extract_output& o = out[i];
+    if (o.call_ms) *o.call_ms = ms;
+    *o.ret = mono[i]; *o.desc_rows = desc[i].rows;
+    tokens[i] = extractors[i]->mnPyramidToken;
+    PutPyramid(*extractors[i], in[i].nlevels, o);
+    if (mono[i] < 0) continue;   // an empty image: the extractor's outputs were not touched
+    if (!PutKeypoints(keys[i], desc[i], o)) return -1;
+  }
+  return 0;
 }

@@ -1452,6 +1452,7 @@ def orbextractor_compute_keypoints(pyramid, nfeatures=1000, scale_factor=1.2, in
     refusal).  Returns level_count and the keypoints level after level (xy, response, angle, size, octave), the candidates every
     DistributeOctTree call received (cand_level_count, cand_xy, cand_response, cand_args [nlevels, 6]: minX maxX minY maxY nFeatures
     level), and the extractor's features_per_level and scale_factors."""
+    from . import orb
     lib = capi.load_host_library()
     nlevels = len(pyramid) if nlevels is None else int(nlevels)
     rows = np.asarray([p.shape[0] for p in pyramid], np.int32)
@@ -1461,23 +1462,14 @@ def orbextractor_compute_keypoints(pyramid, nfeatures=1000, scale_factor=1.2, in
     cin.nfeatures, cin.scale_factor, cin.nlevels, cin.ini_th, cin.min_th = int(nfeatures), float(scale_factor), nlevels, int(ini_th), int(min_th)
     cin.n_images, cin.border = len(pyramid), int(border)
     cin.rows, cin.cols, cin.pixels = capi.ptr(rows, capi.c_int32_p), capi.ptr(cols, capi.c_int32_p), capi.ptr(pixels, capi.c_uint8_p)
-    cap = cand_cap = 0
-    for _ in range(2):   # the first pass counts
-        o = dict(level_count=np.zeros(max(nlevels, 1), np.int32), xy=np.zeros((cap, 2), np.float32), response=np.zeros(cap, np.float32),
-                 angle=np.zeros(cap, np.float32), size=np.zeros(cap, np.float32), octave=np.zeros(cap, np.int32),
-                 cand_level_count=np.zeros(max(nlevels, 1), np.int32), cand_xy=np.zeros((cand_cap, 2), np.float32),
-                 cand_response=np.zeros(cand_cap, np.float32), cand_args=np.zeros((max(nlevels, 1), 6), np.int32),
-                 features_per_level=np.zeros(max(nlevels, 1), np.int32), scale_factors=np.zeros(max(nlevels, 1), np.float32))
-        cout = capi.HostOrbExtractorOutput()
-        cout.capacity, cout.cand_capacity = cap, cand_cap
-        for name, a in o.items():
-            setattr(cout, name, capi.ptr(a, {np.dtype(np.float32): capi.c_float_p, np.dtype(np.int32): capi.c_int32_p}[a.dtype]))
-        n = lib.osh_host_orbextractor_compute_keypoints(C.byref(cin), C.byref(cout))
-        if n < 0:
-            raise RuntimeError(f"osh_host_orbextractor_compute_keypoints returned {n}")
-        if n <= cap and int(o["cand_level_count"].sum()) <= cand_cap:
-            break
-        cap, cand_cap = n, int(o["cand_level_count"].sum())
+    arrays = lambda cap, cand_cap: dict(
+        level_count=np.zeros(max(nlevels, 1), np.int32), xy=np.zeros((cap, 2), np.float32), response=np.zeros(cap, np.float32),
+        angle=np.zeros(cap, np.float32), size=np.zeros(cap, np.float32), octave=np.zeros(cap, np.int32),
+        cand_level_count=np.zeros(max(nlevels, 1), np.int32), cand_xy=np.zeros((cand_cap, 2), np.float32),
+        cand_response=np.zeros(cand_cap, np.float32), cand_args=np.zeros((max(nlevels, 1), 6), np.int32),
+        features_per_level=np.zeros(max(nlevels, 1), np.int32), scale_factors=np.zeros(max(nlevels, 1), np.float32))
+    _n, o = orb.counted_call(lib.osh_host_orbextractor_compute_keypoints, "osh_host_orbextractor_compute_keypoints", cin, capi.HostOrbExtractorOutput,
+                             "cand_capacity", arrays, lambda n, o: (n, int(o["cand_level_count"].sum())))
     return {k: v[:nlevels] if k in ("level_count", "cand_level_count", "cand_args", "features_per_level", "scale_factors") else v for k, v in o.items()}
 
 
@@ -1499,22 +1491,16 @@ def orbextractor_distribute_device(xy, response, width, height, n_features) -> d
     return dict(index=index[:kept], xy=kxy[:kept], response=kresp[:kept], distribute_calls=int(calls.value))
 
 
-
 def orbextractor_extract_batch(images, lappings, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, keep_pyramid=True) -> list:
     """ORBextractor::ExtractBatch of one stand-in extractor per image (None or an empty array: an empty image) with its lapping
     area, through osh_host_orbextractor_extract_batch: per image a dict with ret (monoIndex), desc_rows, token (mnPyramidToken),
     pyramid (mvImagePyramid after the call, a list of levels), xy, angle, size, response, octave, descriptors [n, 32] of
     _keypoints, and call_ms, the wall time of the one ExtractBatch call."""
+    from . import orb
     lib = capi.load_host_library()
     n = len(images)
-    imgs = [np.zeros((0, 0), np.uint8) if im is None else np.ascontiguousarray(im, np.uint8) for im in images]
     cin = (capi.HostExtractInput * max(n, 1))()
-    for i, img in enumerate(imgs):
-        c = cin[i]
-        c.nfeatures, c.scale_factor, c.nlevels, c.ini_th, c.min_th = int(nfeatures), float(scale_factor), int(nlevels), int(ini_th), int(min_th)
-        c.rows, c.cols = (img.shape if img.size else (0, 0))
-        c.pixels = capi.ptr(img if img.size else None, capi.c_uint8_p)
-        c.lapping[0], c.lapping[1] = int(lappings[i][0]), int(lappings[i][1])
+    imgs = [orb.fill_host_extract_input(cin[i], im, nfeatures, scale_factor, nlevels, ini_th, min_th, lappings[i]) for i, im in enumerate(images)]
     cap = [2 * int(nfeatures) + 300 * int(nlevels)] * n
     pix = [int(sum((img.shape[0] + 2) * (img.shape[1] + 2) for _ in range(nlevels))) if img.size else 1 for img in imgs]
     outs, cout = [], (capi.HostExtractOutput * max(n, 1))()
@@ -1524,8 +1510,7 @@ def orbextractor_extract_batch(images, lappings, nfeatures=1000, scale_factor=1.
                  response=np.zeros(cap[i], np.float32), octave=np.zeros(cap[i], np.int32), descriptors=np.zeros((cap[i], 32), np.uint8),
                  ret=np.zeros(1, np.int32), desc_rows=np.zeros(1, np.int32), pixels_needed=np.zeros(1, np.int32), call_ms=np.zeros(1, np.float64))
         cout[i].capacity, cout[i].pixel_capacity = cap[i], pix[i]
-        for name, arr in o.items():
-            setattr(cout[i], name, capi.ptr(arr, dict(capi.HostExtractOutput._fields_)[name]))
+        orb._wire_outputs(cout[i], o)
         outs.append(o)
     tokens = (C.c_uint64 * max(n, 1))()
     rc = lib.osh_host_orbextractor_extract_batch(n, cin, cout, int(bool(keep_pyramid)), tokens)
@@ -1537,9 +1522,6 @@ def orbextractor_extract_batch(images, lappings, nfeatures=1000, scale_factor=1.
         d = dict(ret=int(o["ret"][0]), desc_rows=k, token=int(tokens[i]), call_ms=float(o["call_ms"][0]))
         for name in ("xy", "angle", "size", "response", "octave", "descriptors"):
             d[name] = o[name][:k]
-        d["pyramid"], off = [], 0
-        for r, c in zip(o["level_rows"].tolist(), o["level_cols"].tolist()):
-            d["pyramid"].append(o["pyramid"][off:off + r * c].reshape(r, c).copy())
-            off += r * c
+        d["pyramid"] = orb.cut_levels(o["pyramid"], zip(o["level_rows"].tolist(), o["level_cols"].tolist()))
         res.append(d)
     return res

@@ -321,7 +321,6 @@ class OrbMatcher:
         return _describe_outputs(outs)
 
     describe_cpu = staticmethod(lambda items, borders=None, debug=False: describe_cpu(items, borders=borders, debug=debug))
-    extract = staticmethod(lambda image, **kw: extract(image, **kw))
 
     def extract(self, items, capacities=None, download: bool = False) -> list:
         """ORBextractor::operator() up to its write-back for a batch of items dict(image, inv_scale, scale, n_features [n_levels],
@@ -450,6 +449,15 @@ def _wire_outputs(res, outs):
         setattr(res, name, capi.ptr(o, _POINTER[o.dtype]))
 
 
+def _bordered_image(im, rows, cols, border):
+    """A whole image of 167 with `border` pixels around a level of rows x cols, and `im` (a capi.StereoImage or capi.PyramidImage)
+    set to the level as a view into it.  Returns the whole image and the level."""
+    whole = np.full((max(rows, 0) + 2 * border, max(cols, 0) + 2 * border), 167, np.uint8)
+    im.data = C.cast(whole.ctypes.data + border * whole.shape[1] + border, capi.c_uint8_p)
+    im.rows, im.cols, im.stride = rows, cols, whole.shape[1]
+    return whole, whole[border:border + rows, border:border + cols]
+
+
 def pyramid_images(levels, border, keep: dict):
     """The osh_stereo_image array of a pyramid (a list of uint8 [rows, cols] arrays; None: the level's data stays NULL), every level
     handed over as a view into an image with `border` pixels of 167 around it.  The images are added to `keep`."""
@@ -457,12 +465,59 @@ def pyramid_images(levels, border, keep: dict):
     for l, m in enumerate(levels):
         if m is None:
             continue
-        whole = np.full((m.shape[0] + 2 * border, m.shape[1] + 2 * border), 167, dtype=np.uint8)
-        whole[border:border + m.shape[0], border:border + m.shape[1]] = m
-        keep[f"img{len(keep)}"] = whole
-        imgs[l].data = C.cast(whole.ctypes.data + border * whole.shape[1] + border, capi.c_uint8_p)
-        imgs[l].rows, imgs[l].cols, imgs[l].stride = m.shape[0], m.shape[1], whole.shape[1]
+        keep[f"img{len(keep)}"], level = _bordered_image(imgs[l], m.shape[0], m.shape[1], border)
+        level[:] = m
     return imgs
+
+
+def _fill_pyramid_or_token(f, it, border, keep: dict):
+    """The pyramid of an osh_ic_angle_frame or osh_describe_frame: brought along (it["pyramid"], a list of levels) or, without one,
+    resident under it["token"]."""
+    if it.get("pyramid") is not None:
+        f.n_levels = len(it["pyramid"])
+        f.pyramid = keep["pyr"] = pyramid_images(list(it["pyramid"]), border, keep)
+    else:
+        f.pyramid_token = int(it["token"])
+
+
+def cut_levels(flat, shapes, copy: bool = True) -> list:
+    """Flat pixels cut into levels of the given (rows, cols), one after the other; views into `flat` without `copy`."""
+    levels, off = [], 0
+    for r, c in shapes:
+        level = flat[off:off + r * c].reshape(r, c)
+        levels.append(level.copy() if copy else level)
+        off += r * c
+    return levels
+
+
+def counted_call(fn, name, cin, out_type, second, arrays, needed):
+    """A wrapper of the test library whose first pass counts: arrays(capacity, second capacity) makes the output arrays, which go
+    into an out_type with the two capacities (the fields `capacity` and `second`), and needed(n, o) says what the pass with the
+    return value n asked for.  At most two passes; returns n and the arrays of the pass that had the room."""
+    caps = (0, 0)
+    for _ in range(2):
+        o = arrays(*caps)
+        cout = out_type(capacity=caps[0], **{second: caps[1]})
+        _wire_outputs(cout, o)
+        n = fn(C.byref(cin), C.byref(cout))
+        if n < 0:
+            raise RuntimeError(f"{name} returned {n}")
+        need = needed(n, o)
+        if need[0] <= caps[0] and need[1] <= caps[1]:
+            break
+        caps = need
+    return n, o
+
+
+def fill_host_extract_input(cin, image, nfeatures, scale_factor, nlevels, ini_th, min_th, lapping=(0, 0)):
+    """A capi.HostExtractInput from the stand-in constructor's arguments and a uint8 image (None or an empty array: an empty image).
+    Returns the array `pixels` points to."""
+    img = np.zeros((0, 0), np.uint8) if image is None else np.ascontiguousarray(image, np.uint8)
+    cin.nfeatures, cin.scale_factor, cin.nlevels, cin.ini_th, cin.min_th = int(nfeatures), float(scale_factor), int(nlevels), int(ini_th), int(min_th)
+    cin.rows, cin.cols = (img.shape if img.size else (0, 0))
+    cin.pixels = capi.ptr(img if img.size else None, capi.c_uint8_p)
+    cin.lapping[0], cin.lapping[1] = int(lapping[0]), int(lapping[1])
+    return img
 
 
 def stereo_args(frames, stages: bool = False, borders=None):
@@ -507,6 +562,16 @@ def fast_level_cells(rows, cols, host_lib=None):
     return tuple(int(g) for g in geom), rects[:n].copy()
 
 
+def _fast_result(res, n_levels, capacity):
+    """The output arrays of an osh_fast_result for a (capacity, cell_capacity), wired into `res`."""
+    cap, cell_cap = (int(c) for c in capacity)
+    o = dict(level_count=np.zeros(n_levels, np.int32), xy=np.zeros((cap, 2), np.float32), response=np.zeros(cap, np.float32),
+             level=np.zeros(cap, np.int32), cell=np.zeros(cap, np.int32), used_min_th=np.zeros(cell_cap, np.uint8))
+    res.capacity, res.cell_capacity = cap, cell_cap
+    _wire_outputs(res, o)
+    return o
+
+
 def fast_args(frames, capacities, borders=None):
     """The osh_fast_frame / osh_fast_result arrays of OrbMatcher.fast_detect for frames with .pyramid / .ini_th / .min_th
     (synth_fast.FastFrame) and per frame a (capacity, cell_capacity): (frames, results, keep-alive, per-frame dicts of outputs)."""
@@ -520,13 +585,8 @@ def fast_args(frames, capacities, borders=None):
         cf[k].pyramid = pyramid_images(list(fr.pyramid), 0 if borders is None else int(borders[k]), a)
         a["pyr"] = cf[k].pyramid
         cf[k].ini_th, cf[k].min_th = int(fr.ini_th), int(fr.min_th)
-        cap, cell_cap = (int(c) for c in capacities[k])
-        o = dict(level_count=np.zeros(len(fr.pyramid), np.int32), xy=np.zeros((cap, 2), np.float32), response=np.zeros(cap, np.float32),
-                 level=np.zeros(cap, np.int32), cell=np.zeros(cap, np.int32), used_min_th=np.zeros(cell_cap, np.uint8))
-        cr[k].capacity, cr[k].cell_capacity = cap, cell_cap
-        _wire_outputs(cr[k], o)
         keep.append(a)
-        outs.append(o)
+        outs.append(_fast_result(cr[k], len(fr.pyramid), capacities[k]))
     return cf, cr, keep, outs
 
 
@@ -594,12 +654,7 @@ def fast_resident_args(items, capacities):
     outs = []
     for k, it in enumerate(items):
         cf[k].pyramid_token, cf[k].ini_th, cf[k].min_th = int(it["token"]), int(it["ini_th"]), int(it["min_th"])
-        cap, cell_cap = (int(c) for c in capacities[k])
-        o = dict(level_count=np.zeros(int(it["n_levels"]), np.int32), xy=np.zeros((cap, 2), np.float32), response=np.zeros(cap, np.float32),
-                 level=np.zeros(cap, np.int32), cell=np.zeros(cap, np.int32), used_min_th=np.zeros(cell_cap, np.uint8))
-        cr[k].capacity, cr[k].cell_capacity = cap, cell_cap
-        _wire_outputs(cr[k], o)
-        outs.append(o)
+        outs.append(_fast_result(cr[k], int(it["n_levels"]), capacities[k]))
     return cf, cr, outs, outs
 
 
@@ -635,11 +690,9 @@ def pyramid_args(items, download: bool = True):
             lv = (capi.PyramidImage * max(nl, 1))()
             o["bordered"], o["levels"] = [], []
             for l, (r, c) in enumerate(shapes):
-                whole = np.full((max(r, 0) + 2 * b, max(c, 0) + 2 * b), 167, np.uint8)
+                whole, level = _bordered_image(lv[l], r, c, b)
                 o["bordered"].append(whole)
-                o["levels"].append(whole[b:b + r, b:b + c])
-                lv[l].data = C.cast(whole.ctypes.data + b * whole.shape[1] + b, capi.c_uint8_p)
-                lv[l].rows, lv[l].cols, lv[l].stride = r, c, whole.shape[1]
+                o["levels"].append(level)
             a["lv"] = lv
             cr[k].levels, cr[k].border = lv, b
         keep.append(a)
@@ -714,39 +767,23 @@ def compute_pyramid(image, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=2
     ComputeKeyPointsOctTree), and the keypoints of ComputeKeyPointsOctTree right after it (level_count, xy, angle, response) and
     from a hand-set copy of the pyramid (hand_*)."""
     host_lib = host_lib or capi.load_host_library()
-    img = np.ascontiguousarray(image, np.uint8)
     cin = capi.HostExtractInput()
-    cin.nfeatures, cin.scale_factor, cin.nlevels, cin.ini_th, cin.min_th = int(nfeatures), float(scale_factor), int(nlevels), int(ini_th), int(min_th)
-    cin.rows, cin.cols = img.shape
-    cin.pixels = capi.ptr(img, capi.c_uint8_p)
-    cap = pix = 0
-    for _ in range(2):   # the first pass counts
-        o = dict(level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), bordered=np.zeros(max(pix, 1), np.uint8),
-                 pixels_needed=np.zeros(1, np.int32), built_token=np.zeros(2, np.uint64), level_count=np.zeros(nlevels, np.int32),
-                 xy=np.zeros((cap, 2), np.float32), angle=np.zeros(cap, np.float32), response=np.zeros(cap, np.float32),
-                 hand_level_count=np.zeros(nlevels, np.int32), hand_xy=np.zeros((cap, 2), np.float32), hand_angle=np.zeros(cap, np.float32),
-                 hand_response=np.zeros(cap, np.float32))
-        cout = capi.HostPyramidOutput()
-        cout.capacity, cout.pixel_capacity = cap, pix
-        _wire_outputs(cout, o)
-        n = host_lib.osh_host_orbextractor_compute_pyramid(C.byref(cin), C.byref(cout))
-        if n < 0:
-            raise RuntimeError(f"osh_host_orbextractor_compute_pyramid returned {n}")
-        if n <= cap and int(o["pixels_needed"][0]) <= pix:
-            break
-        cap, pix = n, int(o["pixels_needed"][0])
+    _img = fill_host_extract_input(cin, image, nfeatures, scale_factor, nlevels, ini_th, min_th)
+    arrays = lambda cap, pix: dict(
+        level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), bordered=np.zeros(max(pix, 1), np.uint8),
+        pixels_needed=np.zeros(1, np.int32), built_token=np.zeros(2, np.uint64), level_count=np.zeros(nlevels, np.int32),
+        xy=np.zeros((cap, 2), np.float32), angle=np.zeros(cap, np.float32), response=np.zeros(cap, np.float32),
+        hand_level_count=np.zeros(nlevels, np.int32), hand_xy=np.zeros((cap, 2), np.float32), hand_angle=np.zeros(cap, np.float32),
+        hand_response=np.zeros(cap, np.float32))
+    _n, o = counted_call(host_lib.osh_host_orbextractor_compute_pyramid, "osh_host_orbextractor_compute_pyramid", cin, capi.HostPyramidOutput,
+                         "pixel_capacity", arrays, lambda n, o: (n, int(o["pixels_needed"][0])))
     n1, n2 = int(o["level_count"].sum()), int(o["hand_level_count"].sum())
     out = dict(shapes=list(zip(o["level_rows"].tolist(), o["level_cols"].tolist())), built_token=[int(t) for t in o["built_token"]],
                level_count=o["level_count"], hand_level_count=o["hand_level_count"])
     for name in ("xy", "angle", "response"):
         out[name], out["hand_" + name] = o[name][:n1], o["hand_" + name][:n2]
-    out["bordered"], off = [], 0
-    for r, c in out["shapes"]:
-        if r == 0:
-            out["bordered"].append(None)
-            continue
-        out["bordered"].append(o["bordered"][off:off + (r + 38) * (c + 38)].reshape(r + 38, c + 38).copy())
-        off += (r + 38) * (c + 38)
+    whole = cut_levels(o["bordered"], [(r + 38, c + 38) if r else (0, 0) for r, c in out["shapes"]])
+    out["bordered"] = [w if r else None for w, (r, _) in zip(whole, out["shapes"])]
     return out
 
 
@@ -761,12 +798,7 @@ def ic_angle_args(items, borders=None):
         a = dict(xy=np.ascontiguousarray(it["xy"], np.float32).reshape(-1, 2), level=np.ascontiguousarray(it["level"], np.int32))
         n = cf[k].n = a["level"].shape[0]
         cf[k].xy, cf[k].level = capi.ptr(a["xy"], capi.c_float_p), capi.ptr(a["level"], capi.c_int32_p)
-        if it.get("pyramid") is not None:
-            cf[k].n_levels = len(it["pyramid"])
-            cf[k].pyramid = pyramid_images(list(it["pyramid"]), 0 if borders is None else int(borders[k]), a)
-            a["pyr"] = cf[k].pyramid
-        else:
-            cf[k].pyramid_token = int(it["token"])
+        _fill_pyramid_or_token(cf[k], it, 0 if borders is None else int(borders[k]), a)
         o = dict(angle=np.zeros(n, np.float32), m10=np.zeros(n, np.int32), m01=np.zeros(n, np.int32))
         _wire_outputs(cr[k], o)
         keep.append(a)
@@ -815,8 +847,7 @@ def describe_args(items, borders=None, debug: bool = False):
         a = dict(xy=np.ascontiguousarray(it["xy"], np.float32).reshape(-1, 2), level=np.ascontiguousarray(it["level"], np.int32),
                  angle=np.ascontiguousarray(it["angle"], np.float32))
         n = cf[k].n = a["level"].shape[0]
-        for name in ("xy", "level", "angle"):
-            setattr(cf[k], name, capi.ptr(a[name], _POINTER[a[name].dtype]))
+        _wire_outputs(cf[k], a)
         if it.get("pattern") is not None:
             a["pattern"] = np.ascontiguousarray(it["pattern"], np.int8).reshape(-1)
             assert a["pattern"].shape[0] == 1024
@@ -825,13 +856,10 @@ def describe_args(items, borders=None, debug: bool = False):
             a["blur_q8"] = np.ascontiguousarray(it["blur_q8"], np.uint16).reshape(-1)
             assert a["blur_q8"].shape[0] == 7
             cf[k].blur_q8 = capi.ptr(a["blur_q8"], _POINTER[a["blur_q8"].dtype])
+        _fill_pyramid_or_token(cf[k], it, 0 if borders is None else int(borders[k]), a)
         if it.get("pyramid") is not None:
-            cf[k].n_levels = len(it["pyramid"])
-            cf[k].pyramid = pyramid_images(list(it["pyramid"]), 0 if borders is None else int(borders[k]), a)
-            a["pyr"] = cf[k].pyramid
             shapes = [(0, 0) if p is None else tuple(p.shape) for p in it["pyramid"]]
         else:
-            cf[k].pyramid_token = int(it["token"])
             shapes = [tuple(s) for s in it.get("shapes", ())]
         o = dict(descriptors=np.zeros((n, 32), np.uint8))
         if debug:
@@ -849,10 +877,7 @@ def _describe_outputs(outs):
     for o in outs:
         d = {k: v for k, v in o.items() if k != "shapes"}
         if "blurred" in d:
-            flat, d["blurred"], off = d["blurred"], [], 0
-            for r, c in o["shapes"]:
-                d["blurred"].append(flat[off:off + r * c].reshape(r, c))
-                off += r * c
+            d["blurred"] = cut_levels(d["blurred"], o["shapes"], copy=False)
         res.append(d)
     return res
 
@@ -901,38 +926,22 @@ def extract(image, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_t
     ComputeKeyPointsOctTree (level_count, level_xy, level_angle) and _keypoints (xy, angle, size, response, octave) with
     descriptors [n, 32]; call_ms is the wall time of the operator() call alone."""
     host_lib = host_lib or capi.load_host_library()
-    img = np.zeros((0, 0), np.uint8) if image is None else np.ascontiguousarray(image, np.uint8)
     cin = capi.HostExtractInput()
-    cin.nfeatures, cin.scale_factor, cin.nlevels, cin.ini_th, cin.min_th = int(nfeatures), float(scale_factor), int(nlevels), int(ini_th), int(min_th)
-    cin.rows, cin.cols = (img.shape if img.size else (0, 0))
-    cin.pixels = capi.ptr(img if img.size else None, capi.c_uint8_p)
-    cin.lapping[0], cin.lapping[1] = int(lapping[0]), int(lapping[1])
-    cap = pix = 0
-    for _ in range(2):   # the first pass counts
-        o = dict(level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), pyramid=np.zeros(max(pix, 1), np.uint8),
-                 level_count=np.zeros(nlevels, np.int32), level_xy=np.zeros((cap, 2), np.float32), level_angle=np.zeros(cap, np.float32),
-                 xy=np.zeros((cap, 2), np.float32), angle=np.zeros(cap, np.float32), size=np.zeros(cap, np.float32),
-                 response=np.zeros(cap, np.float32), octave=np.zeros(cap, np.int32), descriptors=np.zeros((cap, 32), np.uint8),
-                 ret=np.zeros(1, np.int32), desc_rows=np.zeros(1, np.int32), pixels_needed=np.zeros(1, np.int32), call_ms=np.zeros(1, np.float64))
-        cout = capi.HostExtractOutput()
-        cout.capacity, cout.pixel_capacity = cap, pix
-        _wire_outputs(cout, o)
-        n = host_lib.osh_host_orbextractor_extract(C.byref(cin), C.byref(cout))
-        if n < 0:
-            raise RuntimeError(f"osh_host_orbextractor_extract returned {n}")
-        need = max(n, int(o["level_count"].sum()))
-        if need <= cap and int(o["pixels_needed"][0]) <= pix:
-            break
-        cap, pix = need, int(o["pixels_needed"][0])
+    _img = fill_host_extract_input(cin, image, nfeatures, scale_factor, nlevels, ini_th, min_th, lapping)
+    arrays = lambda cap, pix: dict(
+        level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), pyramid=np.zeros(max(pix, 1), np.uint8),
+        level_count=np.zeros(nlevels, np.int32), level_xy=np.zeros((cap, 2), np.float32), level_angle=np.zeros(cap, np.float32),
+        xy=np.zeros((cap, 2), np.float32), angle=np.zeros(cap, np.float32), size=np.zeros(cap, np.float32),
+        response=np.zeros(cap, np.float32), octave=np.zeros(cap, np.int32), descriptors=np.zeros((cap, 32), np.uint8),
+        ret=np.zeros(1, np.int32), desc_rows=np.zeros(1, np.int32), pixels_needed=np.zeros(1, np.int32), call_ms=np.zeros(1, np.float64))
+    n, o = counted_call(host_lib.osh_host_orbextractor_extract, "osh_host_orbextractor_extract", cin, capi.HostExtractOutput, "pixel_capacity", arrays,
+                        lambda n, o: (max(n, int(o["level_count"].sum())), int(o["pixels_needed"][0])))
     nl = int(o["level_count"].sum())
     out = dict(ret=int(o["ret"][0]), desc_rows=int(o["desc_rows"][0]), call_ms=float(o["call_ms"][0]), n=n, level_count=o["level_count"], level_xy=o["level_xy"][:nl],
                level_angle=o["level_angle"][:nl])
     for name in ("xy", "angle", "size", "response", "octave", "descriptors"):
         out[name] = o[name][:n]
-    out["pyramid"], off = [], 0
-    for r, c in zip(o["level_rows"].tolist(), o["level_cols"].tolist()):
-        out["pyramid"].append(o["pyramid"][off:off + r * c].reshape(r, c).copy())
-        off += r * c
+    out["pyramid"] = cut_levels(o["pyramid"], zip(o["level_rows"].tolist(), o["level_cols"].tolist()))
     return out
 
 

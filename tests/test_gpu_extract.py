@@ -183,6 +183,26 @@ def test_extract_batch_of_a_left_and_right_pair(matcher, keep):
             assert all(p.size == 0 for p in g["pyramid"])
 
 
+@pytest.mark.parametrize("keep", (True, False))
+def test_extract_batch_refuses_an_image_whose_level_rounds_to_no_pixels(matcher, capfd, keep):
+    # 40 rows by 1 column, 8 levels at 1.2: the width of level 4 is nearbyint(1 * 0.48225) = 0.  The valid frame beside it gets
+    # nothing either: one refused extractor refuses the call
+    tall, valid = np.full((40, 1), 90, np.uint8), sf.make_image(3, 120, 160)
+    capfd.readouterr()
+    got = host.orbextractor_extract_batch([tall, valid], [(0, 0), (0, 60)], nfeatures=300, nlevels=8, keep_pyramid=keep)
+    err = capfd.readouterr().err
+    if keep:   # ExtractBatch sizes the levels it keeps and refuses by itself
+        assert "ORBextractor::ExtractBatch: extractor 0: level 4 has no pixels or too many" in err
+        assert "ORBextractor::ExtractBatch: nothing extracted" in err
+    else:      # the pyramid stage of osh_orb_extract refuses
+        assert "ORBextractor::ExtractBatch: osh_orb_pyramid_build: frame 0: level 4 rounds to 0 pixels in a direction" in err
+        assert "nothing extracted" not in err
+    for g in got:
+        assert g["ret"] == 0 and g["desc_rows"] == 0 and g["token"] == 0
+        assert len(g["xy"]) == 0 and len(g["descriptors"]) == 0
+        assert len(g["pyramid"]) == 8 and all(p.size == 0 for p in g["pyramid"])
+
+
 def test_phase_times(matcher):
     matcher.set_profiling(True)
     try:

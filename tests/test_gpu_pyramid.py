@@ -213,6 +213,18 @@ def test_compute_pyramid_through_the_stand_in(hip_lib):
     assert np.array_equal(e["level_count"], r["level_count"]) and np.array_equal(e["level_xy"], r["xy"])
 
 
+def test_compute_pyramid_refuses_an_image_whose_level_rounds_to_no_pixels(hip_lib, capfd):
+    # 40 rows by 1 column, 8 levels at 1.2: the width of level 4 is nearbyint(1 * 0.48225) = 0, the first level with no pixels
+    capfd.readouterr()
+    r = orb.compute_pyramid(np.full((40, 1), 90, np.uint8), nfeatures=300, nlevels=8)
+    assert "ORBextractor::ComputePyramid: level 4 has no pixels or too many" in capfd.readouterr().err
+    assert r["shapes"] == [(0, 0)] * 8 and all(b is None for b in r["bordered"])
+    assert r["built_token"] == [0, 0]
+    # ComputeKeyPointsOctTree on the empty levels: no keypoint, neither right after it nor on the hand-set copy
+    assert int(r["level_count"].sum()) == 0 and int(r["hand_level_count"].sum()) == 0
+    assert len(r["xy"]) == 0 and len(r["hand_xy"]) == 0
+
+
 def test_time_slots(hip_lib):
     with orb.OrbMatcher(0) as m:
         assert (m.pyramid_times() == 0).all()
