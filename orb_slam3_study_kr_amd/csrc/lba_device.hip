@@ -101,12 +101,13 @@ struct osh_lba_ctx {
   int solve_nb = 24, solve_W = 0, solve_threads = kSolveThreadsLatency;
   bool solve_big = false;            // a window's reduced system exceeds the LDS-resident factorisation: big_solve.h
   DevBuf d_bigV, d_bigz, d_bigfail;
-  size_t solve_lds = 0, backsub_lds = 0, lin_lds = 0;
+  size_t solve_lds = 0, backsub_lds = 0, lin_lds = 0, fin_lds = 0;
   double upload_pack_ms = 0, upload_copy_ms = 0;
   // edge kernels of the batch's camera models: the KannalaBrandt8 instantiations only when a window asks for them
   void (*kp_lin_lm)(BatchView) = nullptr;
   void (*kp_schur_sym)(BatchView, int, int) = nullptr;
   void (*kp_schur_cross)(BatchView, int, int) = nullptr;
+  void (*kp_pose_only)(BatchView, int, int) = nullptr;   // the pose side alone (first round of optimize(), launched with mode 0)
   void (*kp_finalize)(BatchView) = nullptr;
   void (*kp_backsub)(BatchView) = nullptr;
   void (*kp_debug_hpl)(BatchView, double*) = nullptr;
@@ -214,6 +215,7 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
   // ---- LDS budgets
   {
     c->lin_lds = (size_t)LinLds::doubles(std::min(pb.np_max, kLdsPoses)) * sizeof(double);
+    c->fin_lds = (size_t)FinLds::doubles(std::min(pb.np_max, kLdsPoses)) * sizeof(double);
     int backsub_doubles = 0;   // the largest need of a window (backsub_lds_doubles: each window stages what fits)
     for (const WinDesc& d : pb.win) backsub_doubles = std::max(backsub_doubles, backsub_lds_doubles(d.P, d.F, backsub_stages(d.P, d.F)));
     c->backsub_lds = (size_t)backsub_doubles * sizeof(double);
@@ -260,6 +262,9 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
     c->h_stop_cap = nw;
   }
   OSH_HIP(hipMemsetAsync(c->d_xp.p, 0, std::max<size_t>(NFP * 6 * 8, 8), s));
+  // state buffer 1: the fixed keyframes' poses, which no kernel writes, once per upload (reset_state has the whole argument; the
+  // optimisable poses copied with them are overwritten before they are read)
+  if (NP) OSH_HIP(hipMemcpyAsync(c->d_pose[1].p, c->dsec<double>(PackedBatch::POSE), NP * 7 * 8, hipMemcpyDeviceToDevice, s));
   if (!on_device) {
     // window of every landmark (for k_gather_out): the host packer writes it into the tail of the pinned output staging (reused
     // by the download later); the device packer has filled d_ptwin itself
@@ -317,21 +322,26 @@ extern "C" int osh_lba_upload(osh_lba_ctx* c, int32_t nw, const osh_lba_problem*
   const bool f32 = bv.e_rec32 != nullptr;
   if (pb.has_kb8) {
     c->kp_lin_lm = f32 ? k_lin_lm<true, true> : k_lin_lm<true, false>; c->kp_schur_sym = k_schur_fused<true, true>; c->kp_schur_cross = k_schur_fused<false, true>;
-    c->kp_finalize = k_finalize<true>;
+    c->kp_finalize = f32 ? k_finalize<true, true> : k_finalize<true, false>; c->kp_pose_only = k_schur_fused<true, true, false, true>;
     c->kp_backsub = f32 ? k_backsub<true, true> : k_backsub<true, false>; c->kp_debug_hpl = k_debug_hpl<true>;
   } else {
     c->kp_lin_lm = f32 ? k_lin_lm<false, true> : k_lin_lm<false, false>; c->kp_schur_cross = k_schur_fused<false, false>;
     // symmetric items: the diagonal and ragged tiles from 4 x 4 blocks; OSH_LBA_SCHUR_TILES keeps whole tiles (the same bits: tests/test_gpu_schur_blocks.py)
     c->kp_schur_sym = std::getenv("OSH_LBA_SCHUR_TILES") ? k_schur_fused<true, false> : k_schur_fused<true, false, true>;
-    c->kp_finalize = k_finalize<false>;
+    c->kp_finalize = f32 ? k_finalize<false, true> : k_finalize<false, false>; c->kp_pose_only = k_schur_fused<true, false, false, true>;
     c->kp_backsub = f32 ? k_backsub<false, true> : k_backsub<false, false>; c->kp_debug_hpl = k_debug_hpl<false>;
   }
+  // The controls of tests/test_gpu_lba_pose_only.py, tests/test_gpu_lba_finalize.py and of the before/after traces: the full Schur
+  // kernel called with mode 0 for the pose side of the first round, and the edge-by-edge k_finalize (no dynamic LDS).  The same bits.
+  if (std::getenv("OSH_LBA_POSE_PASS_FULL")) c->kp_pose_only = c->kp_schur_sym;
+  if (std::getenv("OSH_LBA_FINALIZE_PLAIN")) { c->kp_finalize = pb.has_kb8 ? k_finalize_plain<true> : k_finalize_plain<false>; c->fin_lds = 0; }
 
   // opt in to large dynamic LDS
   constexpr int kTB = kSolveThreadsBatch, kTL = kSolveThreadsLatency;
   OSH_TRY(allow_dynamic_lds(c->device, kMaxDynamicLds, k_solve<24, kTB>, k_solve<12, kTB>, k_solve<6, kTB>, k_solve<24, kTL>,
                             k_solve<12, kTL>, k_solve<6, kTL>, k_backsub<false, false>, k_backsub<false, true>, k_backsub<true, false>,
-                            k_backsub<true, true>, k_lin_lm<false, false>, k_lin_lm<false, true>, k_lin_lm<true, false>, k_lin_lm<true, true>));
+                            k_backsub<true, true>, k_lin_lm<false, false>, k_lin_lm<false, true>, k_lin_lm<true, false>, k_lin_lm<true, true>,
+                            k_finalize<false, false>, k_finalize<false, true>, k_finalize<true, false>, k_finalize<true, true>));
   c->n_windows = nw;
   return OSH_OK;
 }
@@ -390,14 +400,25 @@ static int launch_solve(osh_lba_ctx* c, hipStream_t s) {
   return launch_check("k_solve");
 }
 
-static int reset_state(osh_lba_ctx* c) {
+// Back to the uploaded estimates, controller reset.  `*n_active`: the windows k_reset leaves active, counted here from the same
+// three conditions (the stream starts the first round without a round trip for a number the host already has).
+// State buffer 0 is rewritten whole.  Of buffer 1 every entry but the fixed keyframes' poses is written before it is read:
+//   poses of optimisable keyframes   k_solve's tail (solve_tail) writes all P of an active window into buffer sel ^ 1 before
+//                                    k_backsub reads them, in every round; sel only becomes 1 by accepting such a trial
+//   landmarks                        k_backsub writes every trial landmark of an active window's chunks before its own trial residual
+//                                    reads them, and again sel only becomes 1 afterwards
+//   a window that is not active      stays at sel == last_eval_sel == 0: k_finalize and k_gather_out read buffer 0 alone
+//   poses of fixed keyframes         read from both buffers (the trial residual stages all P + F), written by no kernel: they are in
+//                                    buffer 1 since the upload copied the pose array there, and still are
+// So nothing is copied into buffer 1 here.  `both` (the debug entries, which read buffer 1 of windows that may not be active)
+// restores it as well.
+static int reset_state(osh_lba_ctx* c, int* n_active, bool both = false) {
   hipStream_t s = c->stream;
   const PackedBatch& pb = c->pb;
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < (both ? 2 : 1); ++k) {
     if (pb.NP) OSH_HIP(hipMemcpyAsync(c->d_pose[k].p, c->dsec<double>(PackedBatch::POSE), pb.NP * 7 * 8, hipMemcpyDeviceToDevice, s));
     if (pb.NL) OSH_HIP(hipMemcpyAsync(c->d_pt[k].p, c->dsec<double>(PackedBatch::PT), pb.NL * 3 * 8, hipMemcpyDeviceToDevice, s));
   }
-  OSH_HIP(hipMemsetAsync(c->d_nactive.p, 0, sizeof(int), s));
   const unsigned char* dstop = nullptr;
   if (c->any_stop) {
     snapshot_stop(c);
@@ -406,6 +427,11 @@ static int reset_state(osh_lba_ctx* c) {
   }
   hipLaunchKernelGGL(k_reset, dim3((c->n_windows + 63) / 64), dim3(64), 0, s, c->bv, dstop);
   OSH_TRY(launch_check("k_reset"));
+  int n = 0;
+  for (int w = 0; w < c->n_windows; ++w) n += (pb.win[w].max_iter > 0 && !(c->any_stop && c->h_stop[w]) && pb.win[w].E > 0) ? 1 : 0;
+  if (n_active) *n_active = n;
+  // (a stop flag is polled into the same pinned snapshot after every round: the copy above has to have read it first)
+  if (c->any_stop) OSH_HIP(hipStreamSynchronize(s));
   return OSH_OK;
 }
 
@@ -422,7 +448,7 @@ static int first_linearisation(osh_lba_ctx* c) {
   hipStream_t s = c->stream;
   const PackedBatch& pb = c->pb;
   LAUNCH(OSH_K_LINEARIZE, c->kp_lin_lm, pb.n_chunks, kBlock, c->lin_lds, c->bv);
-  LAUNCH(OSH_K_LIN_POSE, c->kp_schur_sym, pb.n_sym, 64, 0, c->bv, 0, 0);
+  LAUNCH(OSH_K_LIN_POSE, c->kp_pose_only, pb.n_sym, 64, 0, c->bv, 0, 0);
   LAUNCH(OSH_K_POSE_HESS, k_pose_reduce, (pb.NFP + 1) / 2, 64, 0, c->bv, 0);
   LAUNCH(OSH_K_CONTROL, k_control, c->n_windows, 64, 0, c->bv, 0);
   LAUNCH(OSH_K_LIN_AUX, c->kp_lin_lm, pb.n_chunks, kBlock, c->lin_lds, c->bv);
@@ -461,9 +487,8 @@ extern "C" int osh_lba_optimize(osh_lba_ctx* c) {
   hipStream_t s = c->stream;
   const PackedBatch& pb = c->pb;
   if (c->timer.enabled) OSH_TRY(c->timer.init());
-  OSH_TRY(reset_state(c));
   int n_active = 0;
-  OSH_TRY(read_nactive(c, &n_active));
+  OSH_TRY(reset_state(c, &n_active));
   int max_iter = 0;
   for (const WinDesc& d : pb.win) max_iter = std::max(max_iter, d.max_iter);
   const long max_rounds = (long)max_iter * kLmMaxTrials + 1;
@@ -495,7 +520,7 @@ extern "C" int osh_lba_optimize(osh_lba_ctx* c) {
     }
   }
   if (pb.n_chunks) {
-    hipLaunchKernelGGL(c->kp_finalize, dim3((unsigned)pb.n_chunks), dim3(kBlock), 0, s, c->bv);
+    hipLaunchKernelGGL(c->kp_finalize, dim3((unsigned)pb.n_chunks), dim3(kBlock), c->fin_lds, s, c->bv);
     OSH_TRY(launch_check("k_finalize"));
   }
   {
@@ -581,7 +606,7 @@ extern "C" int osh_lba_linearize(osh_lba_ctx* c, int32_t window, double* Hpp, do
   OSH_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const PackedBatch& pb = c->pb;
-  OSH_TRY(reset_state(c));
+  OSH_TRY(reset_state(c, nullptr, true));
   OSH_TRY(first_linearisation(c));
   OSH_HIP(hipStreamSynchronize(s));
   const WinDesc& d = pb.win[window];
@@ -630,7 +655,7 @@ extern "C" int osh_lba_linearize(osh_lba_ctx* c, int32_t window, double* Hpp, do
     // mark every window evaluated so k_finalize emits chi2 of the current state
     for (auto& st : h_lm) { st.iterations = 1; st.last_eval_sel = st.sel; }
     OSH_HIP(hipMemcpy(c->d_lm.p, h_lm.data(), c->n_windows * sizeof(LmState), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(c->kp_finalize, dim3((unsigned)pb.n_chunks), dim3(kBlock), 0, s, c->bv);
+    hipLaunchKernelGGL(c->kp_finalize, dim3((unsigned)pb.n_chunks), dim3(kBlock), c->fin_lds, s, c->bv);
     OSH_TRY(launch_check("k_finalize"));
     OSH_HIP(hipStreamSynchronize(s));
     OSH_HIP(hipMemcpy(chi2, c->d_out_chi2.as<double>() + d.out_off, (size_t)d.in_edges * 8, hipMemcpyDeviceToHost));
@@ -646,9 +671,9 @@ extern "C" int osh_lba_debug_trial(osh_lba_ctx* c, int32_t window, double lambda
   OSH_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const PackedBatch& pb = c->pb;
-  OSH_TRY(reset_state(c));
+  OSH_TRY(reset_state(c, nullptr, true));
   LAUNCH(OSH_K_LINEARIZE, c->kp_lin_lm, pb.n_chunks, kBlock, c->lin_lds, c->bv);
-  LAUNCH(OSH_K_LIN_POSE, c->kp_schur_sym, pb.n_sym, 64, 0, c->bv, 0, 0);
+  LAUNCH(OSH_K_LIN_POSE, c->kp_pose_only, pb.n_sym, 64, 0, c->bv, 0, 0);
   LAUNCH(OSH_K_POSE_HESS, k_pose_reduce, (pb.NFP + 1) / 2, 64, 0, c->bv, 0);
   LAUNCH(OSH_K_CONTROL, k_control, c->n_windows, 64, 0, c->bv, 0);
   OSH_HIP(hipStreamSynchronize(s));
@@ -755,6 +780,6 @@ extern "C" const char* osh_lba_kernel_name(int k) {
   // slot OSH_K_RESIDUAL keeps its name and reports no launches: the trial residual has been the tail of k_backsub since round 3
   static const char* names[OSH_K_COUNT] = {"k_lin_lm<false, true>", "k_pose_reduce", "k_schur_fused<true, false> (mode 1)", "k_solve", "k_backsub<false, true>",
                                            "k_residual<false, true>", "k_control", "k_schur_reduce", "k_schur_fused<false, false>",
-                                           "k_lin_lm<false, true> (factors only)", "k_schur_fused<true, false> (mode 0)"};
+                                           "k_lin_lm<false, true> (factors only)", "k_schur_fused<true, false, false, true> (pose side alone)"};
   return (k >= 0 && k < OSH_K_COUNT) ? names[k] : "?";
 }

@@ -257,8 +257,106 @@ __global__ __launch_bounds__(kBlock) void k_backsub(BatchView bv) {
 // levenberg.cpp:123-147) and isDepthPositive from the FINAL estimates (Optimizer.cc:1425), in the caller's edge order.
 // A merged fisheye-rig edge reports to both of its caller edges.
 // --------------------------------------------------------------------------------------------
-template <bool KB8>
+// Landmark-major like its neighbours: the lane's edges of all passes are requested up front (load_lane_edges, the caller's edge
+// index with them), the window's poses and the chunk's landmarks are parked in LDS behind one barrier, and the rest only computes.
+// Two states can be needed: the one evaluated last (chi2) and the final one (depth sign).  They are the same buffer unless the
+// window's last trial was rejected, and then only what the depth sign reads of the final state is staged beside the first:
+// quaternion + translation and the landmarks.  chi2 through win_edge_rho and the sign through quat_rotate, as in k_finalize_plain
+// below: the same bits (tests/test_gpu_lba_finalize.py).  Windows of more than kLdsPoses keyframes read their poses from global memory.
+template <bool KB8, bool F32>
 __global__ __launch_bounds__(kBlock) void k_finalize(BatchView bv) {
+  extern __shared__ __attribute__((aligned(16))) double sh_fin[];   // FinLds (lba_view.h)
+  const Chunk ch = bv.chunks[blockIdx.x];
+  const WinDesc wd = bv.win[ch.win];   // by value: the fields stay in SGPRs across the kernel's stores
+  const LmView st = lm_view(bv.lm, ch.win);
+  const int tid = threadIdx.x;
+  const int nl = ch.lm1 - ch.lm0;
+  const int* lmo = bv.lm_off + wd.lmoff_off;
+  const int e0 = lmo[ch.lm0], e1 = lmo[ch.lm1];
+  const bool evaluated = st.iterations > 0;
+  const int f = st.sel, s = evaluated ? st.last_eval_sel : f;
+  const bool two = s != f;
+  const int np = wd.P + wd.F;
+  const bool staged = np <= kLdsPoses;
+  double* sh_X = sh_fin + FinLds::kX;
+  double* sh_Xf = two ? sh_fin + FinLds::kXf : sh_X;
+  double* sh_pose = sh_fin + FinLds::kPose;
+  double* sh_qf = sh_pose + np * kPoseRec;
+  const double* poses = bv.pose_state[s] + (size_t)wd.pose_off * 7;
+  const double* poses_f = bv.pose_state[f] + (size_t)wd.pose_off * 7;
+  const double* cams = bv.pose_cam + (size_t)wd.pose_off * 5;
+  const bool rig = KB8 && wd.kb8_on;
+  for (int base = e0; base < e1; base += kChunkMaxEdges) {
+    LaneEdges le;
+    load_lane_edges<F32>(bv, wd, base, e1, tid, le);
+    int eo[kPasses], ek[kPasses];
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) {
+      const size_t ge = (size_t)wd.edge_off + min(base + p * kChunkEdges + tid, max(e1 - 1, 0));
+      eo[p] = bv.e_orig[ge];
+      ek[p] = rig ? bv.e_kind[ge] : kKindMono;
+    }
+    if (base == e0) {
+      stage_points(sh_X, bv.pt_state[s] + (size_t)wd.pt_off * 3, ch.lm0, nl, tid);
+      if (two) stage_points(sh_Xf, bv.pt_state[f] + (size_t)wd.pt_off * 3, ch.lm0, nl, tid);
+      if (staged) {
+        stage_poses(sh_pose, poses, cams, np, tid, kBlock);
+        if (two) { for (int k = tid; k < 7 * np; k += kBlock) sh_qf[k] = poses_f[k]; }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) {
+      const int e = base + p * kChunkEdges + tid;
+      if (e >= e1) continue;
+      const size_t ge = (size_t)wd.edge_off + e;
+      const int ip = le.ip[p], li = le.il[p] - ch.lm0;
+      double qt[7], cam[5], R[9], X[3];
+      fetch_pose(staged, sh_pose, poses, cams, ip, qt, cam, R);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) X[k] = sh_X[li * 3 + k];
+      double chi_l = 0.0, chi_r = 0.0;
+      if (evaluated) {
+        const double rec[4] = {le.ra[p].x, le.ra[p].y, le.rb[p].x, le.rb[p].y};
+        (void)win_edge_rho<KB8>(wd, bv, ge, rec, qt, cam, R, X, chi_l, chi_r);
+      }
+      if (two) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) qt[k] = staged ? sh_qf[ip * 7 + k] : poses_f[(size_t)ip * 7 + k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[k] = sh_Xf[li * 3 + k];
+      }
+      double rot[3];
+      dev::quat_rotate(qt, X, rot);
+      const double Xl[3] = {rot[0] + qt[4], rot[1] + qt[5], rot[2] + qt[6]};
+      const size_t go = (size_t)wd.out_off + eo[p];
+      const int kind = ek[p];
+      double zr = 0.0;
+      if (KB8 && kind >= kKindBody) {   // isDepthPositive of the body edge: ((mTrl * T).map(X))(2) > 0
+        double Xr[3];
+        dev::quat_rotate(wd.trl, Xl, Xr);
+        zr = Xr[2] + wd.trl[6];
+      }
+      if (kind == kKindBody) {
+        bv.out_chi2[go] = chi_r;
+        bv.out_depth[go] = zr > 0.0 ? 1 : 0;
+      } else {
+        bv.out_chi2[go] = chi_l;
+        bv.out_depth[go] = (Xl[2] > 0.0) ? 1 : 0;
+        if (kind == kKindBoth) {
+          const size_t go2 = (size_t)wd.out_off + bv.e_orig2[ge];
+          bv.out_chi2[go2] = chi_r;
+          bv.out_depth[go2] = zr > 0.0 ? 1 : 0;
+        }
+      }
+    }
+  }
+}
+
+// The kernel above before it became landmark-major: each lane walks its edges one after the other and gathers the poses and landmarks
+// of both states from global memory.  Kept as the control (OSH_LBA_FINALIZE_PLAIN at upload).
+template <bool KB8>
+__global__ __launch_bounds__(kBlock) void k_finalize_plain(BatchView bv) {
   const Chunk ch = bv.chunks[blockIdx.x];
   const WinDesc wd = bv.win[ch.win];   // by value: the fields stay in SGPRs across the kernel's stores
   const LmView st = lm_view(bv.lm, ch.win);

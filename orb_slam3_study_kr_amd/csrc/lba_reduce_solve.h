@@ -381,7 +381,8 @@ __global__ __launch_bounds__(256) void k_schur_env(BatchView bv) {
   }
 }
 
-// reset the controller before optimize()
+// reset the controller before optimize()  (the host counts the windows this leaves active itself, from the same three conditions:
+// reset_state; *n_active is cleared by phase 0 and counted by phase 1 of every round)
 __global__ void k_reset(BatchView bv, const unsigned char* stop) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= bv.n_windows) return;
@@ -394,7 +395,6 @@ __global__ void k_reset(BatchView bv, const unsigned char* stop) {
   st.active = (wd.max_iter > 0 && !st.stop && wd.E > 0) ? 1 : 0;
   st.need_lin = st.active; st.lin_now = 0; st.need_dl = 0;
   st.sel = 0; st.last_eval_sel = 0; st.iterations = 0; st.trials = 0; st.solve_ok = 1; st.n_trace = 0;
-  if (st.active) atomicAdd(bv.n_active, 1);
 }
 
 __global__ void k_set_stop(BatchView bv, const unsigned char* stop) {

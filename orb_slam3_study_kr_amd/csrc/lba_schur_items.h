@@ -23,6 +23,11 @@ namespace osh {
 //   4 of them (pinhole) that image is filled for two chunks at a time by one 16 x 4 pass (cross_pairs).
 //   mode 0: pose side only (the first round of optimize(): computeLambdaInit needs Hpp before any Schur product)
 //   mode 1: Schur products, and the pose side when this round opened an iteration other than the first
+//   POSE_ONLY (symmetric items, launched with mode 0): the instantiation of the first round of optimize().  Nothing of the Schur
+//   side exists in it -- no accumulator tiles, no landmark factors, no image, no multiply, no contribution store -- so it runs in
+//   half the registers of the full kernel called with mode 0 (124 against 254).  The lane's edge description, core_pose_side, the
+//   chunk walk, the lane reduction and the hcontrib store are the statements of the full kernel: Hpp, b_p and lambda_0 are the same bits
+//   (tests/test_gpu_lba_pose_only.py; OSH_LBA_POSE_PASS_FULL at upload keeps the full kernel for this launch).
 // --------------------------------------------------------------------------------------------
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int kSiLm = 8;               // landmarks per chunk, items of 6 .. 8 row poses (and every cross item)
@@ -47,10 +52,17 @@ constexpr int kSiImage = 32 * 49;
 // Every instruction of k step ks reads image columns 4 ks .. 4 ks + 3: the k sequence of every entry is the one of the tiles.
 // (schur_plan.h: schur_live_blocks, and schur_step for the instruction counts.)
 
-template <bool SYM, bool KB8, bool BLK = false>
+constexpr int kSiPoseRed = 14 * 64;    // the lane reduction of the pose side: 14 of the 27 entries of every lane at a time
+
+template <bool SYM, bool KB8, bool BLK = false, bool POSE_ONLY = false>
 __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, int item_base, int mode) {
   static_assert(!BLK || (SYM && !KB8), "block path: symmetric pinhole items");
-  __shared__ double shA[(SYM && !KB8) ? kSiImage : kSiRows * (3 * kSiLm + 1)];   // (the wider mappings: symmetric pinhole items only)
+  static_assert(!POSE_ONLY || (SYM && !BLK), "pose side alone: symmetric items, no products");
+  constexpr bool kSchur = !POSE_ONLY;
+  // (the wider mappings: symmetric pinhole items only; POSE_ONLY: no image, the scratch of the lane reduction alone)
+  constexpr int kImage = POSE_ONLY ? kSiPoseRed : ((SYM && !KB8) ? kSiImage : kSiRows * (3 * kSiLm + 1));
+  static_assert(kImage >= kSiPoseRed, "the lane reduction of the pose side goes through the image buffer");
+  __shared__ double shA[kImage];
   __shared__ double shB[SYM ? 1 : kSiRows * (3 * kSiLm + 1)];
   __shared__ double shPose[(SYM ? 1 : 2) * 8 * kPoseRec];
   __shared__ int shP[64 + 8];
@@ -60,12 +72,12 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
   const LmView st = lm_view(bv.lm, it.win);
   if (!st.active) return;
   const bool do_hpp = SYM && (mode == 0 ? st.need_lin != 0 : (st.lin_now != 0 && st.iter > 0));
-  const bool do_schur = mode != 0;
+  const bool do_schur = kSchur && mode != 0;
   if (!do_hpp && !do_schur) return;
   const int lane = threadIdx.x;
   const int nx = it.shape & 0xff, ny = (it.shape >> 8) & 0xff;
   const int TX = (6 * nx + 15) >> 4, TY = (6 * ny + 15) >> 4;
-  shP[lane] = bv.spair[(size_t)item_idx * 64 + lane];
+  if (kSchur) shP[lane] = bv.spair[(size_t)item_idx * 64 + lane];
   if (lane < 8) shP[64 + lane] = bv.scslot[(size_t)item_idx * 8 + lane];
   {
     // poses of the item's slots -> LDS (lanes 0..7: row poses, lanes 8..15: column poses of a cross item)
@@ -99,7 +111,7 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
     constexpr int LM = decltype(lmc)::value, PS = decltype(psc)::value;   // landmarks per chunk, pose lanes
     constexpr int KS = 3 * LM + 1;                                        // LDS row stride (doubles): odd, conflict-free MFMA reads
     constexpr int KST = (3 * LM) / 4;                                     // k steps per chunk
-    static_assert(LM * PS <= 64 && (3 * LM) % 4 == 0 && ((6 * PS + 15) / 16) * 16 * KS <= ((SYM && !KB8) ? kSiImage : kSiRows * (3 * kSiLm + 1)), "chunk mapping");
+    static_assert(LM * PS <= 64 && (3 * LM) % 4 == 0 && (POSE_ONLY || ((6 * PS + 15) / 16) * 16 * KS <= kImage), "chunk mapping");
     const int l = lane / PS, s = lane - l * PS;
     const bool lane_on = LM * PS == 64 || l < LM;
     f64x4 acc[3][3];
@@ -120,7 +132,7 @@ __global__ __launch_bounds__(64, KB8 ? 1 : 2) void k_schur_fused(BatchView bv, i
     for (int k = 0; k < 21; ++k) H[k] = 0.0;
 #pragma unroll
     for (int k = 0; k < 6; ++k) hb[k] = 0.0;
-    if (PS < 8) {
+    if (kSchur && PS < 8) {
       // image rows past the pose lanes (up to the end of the last tile): nobody writes them
       for (int idx = lane; idx < (((6 * PS + 15) / 16) * 16 - 6 * PS) * KS; idx += 64) shA[6 * PS * KS + idx] = 0.0;
     }

@@ -136,6 +136,15 @@ struct LinLds {
   __host__ __device__ static constexpr int doubles(int n_staged) { return kPose + n_staged * kPoseRec; }
 };
 
+// k_finalize: the chunk's landmarks of the state evaluated last and of the final state ([256 * 3] each), the staged poses of the
+// state evaluated last, then quaternion + translation (7) of every pose of the final state.  The second landmark array and the final
+// poses are only filled when the two states differ (a window whose last trial was rejected).
+struct FinLds {
+  static constexpr int kX = 0, kXf = kX + 3 * kBlock, kPose = kXf + 3 * kBlock;
+  __host__ __device__ static constexpr int doubles(int n_staged) { return kPose + n_staged * (kPoseRec + 7); }
+};
+static_assert(FinLds::doubles(kLdsPoses) * (int)sizeof(double) <= kMaxDynamicLds, "kLdsPoses keyframes of both states fit the block");
+
 // k_backsub for a window of P optimisable and F fixed keyframes: partials, reduce scratch and the chunk's landmarks;
 // when `staged`, x_p and the optimisable poses at the current estimates; the trial poses of all keyframes when there are at most
 // kLdsPoses.  x_p and the current poses are staged when that fits the block (with two fixed keyframes: up to 393 optimisable ones; the
