@@ -32,6 +32,11 @@ class Preintegrated {
   void IntegrateNewMeasurement(const Eigen::Vector3f& acceleration, const Eigen::Vector3f& angVel, const float& dt);
   void SetNewBias(const Bias& bu_);
   Bias GetDeltaBias(const Bias& b_);
+  // src/ImuTypes.cc:239-263 re-integrates the previous keyframe's measurements in front of this one's; the stand-in records its
+  // argument (LocalMapping::KeyFrameCulling is its only caller here)
+  void MergePrevious(Preintegrated* pPrev) { mpMergedPrevious = pPrev; ++mnMerges; }
+  Preintegrated* mpMergedPrevious = nullptr;
+  int mnMerges = 0;
   float dT;
   Eigen::Matrix<float, 15, 15> C;
   float Nga[6], NgaWalk[6];

@@ -66,6 +66,11 @@ class KeyFrame {
   float ComputeSceneMedianDepth(const int q);
   // src/KeyFrame.cc:379-476: rebuilds the covisibility links from the map point matches; the stand-in counts the calls
   void UpdateConnections(bool upParent = true) { (void)upParent; ++mnConnectionUpdates; }
+  // what LocalMapping::KeyFrameCulling calls.  src/KeyFrame.cc:204-222 re-sorts the covisibility list: the stand-in counts the calls.
+  void UpdateBestCovisibles() { ++mnBestCovisibleUpdates; }
+  // src/KeyFrame.cc:573-680: the guards for the initial keyframe and mbNotErase, EraseObservation on every match and mbBad; the
+  // stand-in counts the connection and spanning-tree updates instead of performing them (stand-in body: csrc/hosttest/kfcull.cc)
+  void SetBadFlag();
 
   long unsigned int mnId;
   long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
@@ -87,6 +92,8 @@ class KeyFrame {
   float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
   float invfx = 0, invfy = 0, mb = 0;          // include/KeyFrame.h:374
   float mfScaleFactor = 0;                     // include/KeyFrame.h:396
+  double mTimeStamp = 0;                       // include/KeyFrame.h:315 (const there)
+  float mThDepth = 0;                          // include/KeyFrame.h:374 (const there)
   std::vector<float> mvDepth;                  // include/KeyFrame.h:384 (negative value for monocular points)
   int N = 0, NLeft = -1;
   std::vector<cv::KeyPoint> mvKeys, mvKeysUn, mvKeysRight;
@@ -124,9 +131,11 @@ class KeyFrame {
   std::set<KeyFrame*> mspChildrens, mspLoopEdges;
   std::vector<MapPoint*> mvpMapPoints;
   bool mbBad = false;
+  bool mbNotErase = false, mbToBeErased = false;   // include/KeyFrame.h:479-480
   Map* mpMap;
   int mnPoseSets = 0;
   int mnConnectionUpdates = 0;
+  int mnBestCovisibleUpdates = 0, mnConnectionErasures = 0, mnSpanningTreeUpdates = 0;
 };
 }  // namespace ORB_SLAM3
 #endif

@@ -21,6 +21,7 @@ class Map {
   int GetMapChangeIndex() { return mnMapChange; }
   bool IsBad() { return mbBad; }                                      // src/Map.cc:246-249
   bool GetIniertialBA2() { return mbIMU_BA2; }                        // src/Map.cc:315-319
+  bool isImuInitialized() { return mbImuInitialized; }                // src/Map.cc:92-96
   void AddMapPoint(MapPoint* pMP) { mvpMapPoints.push_back(pMP); }    // src/Map.cc:80-84 (a set there)
   void AddKeyFrame(KeyFrame* pKF) { mvpKeyFrames.push_back(pKF); }    // src/Map.cc:60-78 (a set there; ids and the lower keyframe are left out)
   std::mutex mMutexMapUpdate;
@@ -32,6 +33,7 @@ class Map {
   bool mbIsInertial = false;
   bool mbBad = false;
   bool mbIMU_BA2 = false;
+  bool mbImuInitialized = false;
   int mnMapChange = 0;
   long unsigned int mnKeyFrames = 0;
   std::vector<KeyFrame*> mvpKeyFrames;

@@ -44,6 +44,9 @@ class MapPoint {
   int PredictScale(const float& currentDist, KeyFrame* pKF);   // src/MapPoint.cc:514-529
   Eigen::Vector3f GetNormal() { return mNormalVector; }
   KeyFrame* GetReferenceKeyFrame() { return mpRefKF; }
+  // what LocalMapping::MapPointCulling calls (src/MapPoint.cc:323-327 and :216-240; stand-in body: csrc/hosttest/kfcull.cc)
+  float GetFoundRatio() { return static_cast<float>(mnFound) / mnVisible; }
+  void SetBadFlag();
 
   /* ADD THIS MEMBER to the reference's class: ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403) and UpdateNormalAndDepth
    * (:426-494) for every point of the list, in list order, in one device call (csrc/host/MapPoint.cc).  A bad point, a point
@@ -56,6 +59,7 @@ class MapPoint {
   static long unsigned int nNextId;           // include/MapPoint.h:165
   static std::mutex mGlobalMutex;             // include/MapPoint.h:151 (held while PoseOptimization reads the positions)
   long unsigned int mnId;
+  long int mnFirstKFid = 0;                   // include/MapPoint.h:166
   long unsigned int mnBALocalForKF = 0;
   long unsigned int mnBALocalForMerge = 0;    // include/MapPoint.h:139
   long unsigned int mnFuseCandidateForKF = 0; // include/MapPoint.h:185 (LocalMapping::SearchInNeighbors)

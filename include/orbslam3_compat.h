@@ -40,6 +40,9 @@ struct Matrix {
   T& operator()(int r, int c) { return v[r * C + c]; }
   const T& operator()(int r, int c) const { return v[r * C + c]; }
   void setIdentity() { for (int r = 0; r < R; ++r) for (int c = 0; c < C; ++c) v[r * C + c] = r == c ? T(1) : T(0); }
+  // what LocalMapping::KeyFrameCulling writes for the distance of two IMU positions (src/LocalMapping.cc:1068)
+  Matrix operator-(const Matrix& o) const { Matrix d; for (int i = 0; i < R * C; ++i) d.v[i] = v[i] - o.v[i]; return d; }
+  T norm() const { T s = T(0); for (int i = 0; i < R * C; ++i) s += v[i] * v[i]; return std::sqrt(s); }
   template <class U> Matrix<U, R, C> cast() const { Matrix<U, R, C> o; for (int i = 0; i < R * C; ++i) o.v[i] = (U)v[i]; return o; }
 };
 using Matrix3f = Matrix<float, 3, 3>;

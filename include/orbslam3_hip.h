@@ -1263,6 +1263,64 @@ int osh_orb_refresh_map_points(osh_orb_ctx* ctx, int32_t n_batches, const osh_ma
  * points sorted into the wavefront and the block class), ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
 int osh_orb_refresh_map_points_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- LocalMapping::KeyFrameCulling */
+/*
+ * The counts of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:932-1089): for every candidate keyframe, over its slots that
+ * hold a point which is not bad and pass the depth test, nMPs and nRedundantObservations (the point has nObs > 3 and more than 3
+ * other observers at level <= the slot's level + 1), and the decision (float)nRedundant > redundant_th * (float)nMPs as one float32
+ * product and one comparison.  The rule, its records and the proof that the order of culls does not matter: csrc/keyframe_cull.h.
+ *
+ * osh_orb_keyframe_cull_stage uploads one problem, which stays resident under the context until the next stage call: stage once
+ * per KeyFrameCulling call.  The keyframe table has n_keyframes entries, the candidates first (candidate c is table entry c), then
+ * every other observer.  osh_orb_keyframe_cull_count evaluates the candidates first_candidate .. n_candidates - 1 under a removed
+ * set (table indices, in any order, repeats allowed): a removed observer takes its weight from its points' n_obs, a point that lost
+ * an observer and is left with n_obs <= 2 is bad, removed observers are not counted.  One call is one launch of the counting kernel
+ * and one download; entry i of each result array is candidate first_candidate + i.  The call may be repeated any number of times
+ * on one staged problem, with any sets: nothing is carried from one count to the next.  first_candidate == n_candidates is valid
+ * and launches nothing.
+ *
+ * Refused before any device work and without a context, which stays usable.  OSH_ERR_UNSUPPORTED: more than
+ * OSH_KFCULL_MAX_CANDIDATES candidates, OSH_KFCULL_MAX_KEYFRAMES table entries, OSH_KFCULL_MAX_SLOTS slots,
+ * OSH_KFCULL_MAX_POINTS points or OSH_KFCULL_MAX_OBSERVATIONS observations (the totals are read from the last entry of the offset
+ * arrays before any other array is touched).  OSH_ERR_INVALID: a negative count, n_candidates > n_keyframes, a NULL array whose
+ * count is not 0, offsets that do not start at 0 or decrease, a slot's point outside [0, n_points), an observer outside
+ * [0, n_keyframes), a level outside [0, 255], a weight outside 1..3, point_bad other than 0 or 1; for a count: n_removed < 0,
+ * a removed index outside [0, OSH_KFCULL_MAX_KEYFRAMES) or, with a context, outside the staged table, first_candidate outside
+ * [0, OSH_KFCULL_MAX_CANDIDATES] or, with a context, above the staged n_candidates, and a count before any stage.
+ */
+#define OSH_KFCULL_MAX_CANDIDATES   128         /* the reference stops after 101                                       */
+#define OSH_KFCULL_MAX_KEYFRAMES    4096        /* the table and the removed mask                                      */
+#define OSH_KFCULL_MAX_SLOTS        4194304     /* 2^22 = OSH_MAPPOINT_MAX_POINTS, all candidates together             */
+#define OSH_KFCULL_MAX_POINTS       4194304     /* 2^22 = OSH_MAPPOINT_MAX_POINTS                                      */
+#define OSH_KFCULL_MAX_OBSERVATIONS 33554432    /* 2^25 = OSH_MAPPOINT_MAX_ENTRIES                                     */
+typedef struct osh_kfcull_problem {
+  int32_t n_keyframes;            /* size of the keyframe table                                                                  */
+  int32_t n_candidates;
+  float redundant_th;             /* 0.9f or 0.5f (:943-948)                                                                     */
+  const int32_t* cand_slot_off;   /* [n_candidates+1] the slots of candidate c are [cand_slot_off[c], cand_slot_off[c+1])        */
+  const int32_t* slot_point;      /* [n_slots]  index into the points                                                            */
+  const int32_t* slot_level;      /* [n_slots]  scaleLevel (:1001-1003)                                                          */
+  int32_t n_points;
+  const int32_t* point_n_obs;     /* [n_points] the point's own nObs when staged                                                 */
+  const uint8_t* point_bad;       /* [n_points] isBad()                                                                          */
+  const int32_t* point_obs_off;   /* [n_points+1] the observations of point p are [point_obs_off[p], point_obs_off[p+1])         */
+  const int32_t* obs_kf;          /* [n_obs]    table index of the observer                                                      */
+  const int32_t* obs_level;       /* [n_obs]    scaleLeveli (:1013-1026)                                                         */
+  const int32_t* obs_weight;      /* [n_obs]    what MapPoint::EraseObservation subtracts from nObs for this observer, 1..3      */
+} osh_kfcull_problem;
+/* Caller-allocated, n_candidates - first_candidate entries each; each may be NULL (not wanted). */
+typedef struct osh_kfcull_result {
+  int32_t* n_mps;
+  int32_t* n_redundant;
+  uint8_t* redundant;             /* the decision of :1044                                                                       */
+} osh_kfcull_result;
+int osh_orb_keyframe_cull_stage(osh_orb_ctx* ctx, const osh_kfcull_problem* problem);
+int osh_orb_keyframe_cull_count(osh_orb_ctx* ctx, int32_t n_removed, const int32_t* removed_kf, int32_t first_candidate,
+                                const osh_kfcull_result* result);
+/* Host-clock phases (ms) under osh_orb_set_profiling.  The last stage call: ms[0] validation + staging (the records packed),
+ * ms[1] upload.  The last count call: ms[2] the mask built and uploaded + the kernel, ms[3] download + write-back. */
+int osh_orb_keyframe_cull_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 /* ------------------------------------------------- FAST corners and orientation (ORBextractor) */
 /*
  * The integer part of ORBextractor::ComputeKeyPointsOctTree (src/ORBextractor.cc:781-896) for n_frames pyramids in one call: what

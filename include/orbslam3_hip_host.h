@@ -891,6 +891,76 @@ int osh_host_local_mapping_search_in_neighbors(osh_host_graph* g, int32_t kf, in
  * the keyframe than before. */
 int osh_host_local_mapping_process_new_keyframe(osh_host_graph* g, int32_t kf, int32_t capacity, int32_t* recent, int32_t* in_map);
 
+/* ---- LocalMapping::KeyFrameCulling and MapPointCulling (csrc/hosttest/kfcull.cc) ---- */
+/* A stand-in map for the two culling steps.  Keyframe i has kf_n_slots[i] slots (its keypoints and match table), the first
+ * kf_n_left[i] of them left keypoints of a rig (-1: no rig, all in mvKeysUn); kf_camera2: mpCamera2 is set.  The slots of all
+ * keyframes follow one another: the point held (-1: none; it gets the observation through MapPoint::AddObservation), the
+ * keypoint's octave, mvuRight and mvDepth.  mp_n_obs overrides the point's nObs where it is not -1. */
+typedef struct osh_host_cull_scene {
+  int32_t n_kf;
+  const int64_t* kf_id;
+  const int32_t* kf_n_slots;
+  const int32_t* kf_n_left;
+  const uint8_t* kf_camera2;
+  const float* kf_th_depth;
+  const double* kf_timestamp;
+  const uint8_t* kf_not_erase;
+  const uint8_t* kf_bad;
+  const float* kf_imu_pos;      /* [n_kf*3] GetImuPosition() */
+  const int32_t* kf_prev;       /* mPrevKF / mNextKF as keyframe indices, -1: none */
+  const int32_t* kf_next;
+  const uint8_t* kf_has_preint; /* the keyframe owns an IMU::Preintegrated */
+  const int32_t* slot_point;
+  const int32_t* slot_octave;
+  const float* slot_u_right;
+  const float* slot_depth;
+  int32_t n_mp;
+  const int32_t* mp_n_obs;
+  const uint8_t* mp_bad;
+  int64_t init_kf_id;           /* Map::GetInitKFid() */
+  int32_t keyframes_in_map;     /* Map::KeyFramesInMap() */
+  int32_t imu_initialized;      /* Map::isImuInitialized() */
+  int32_t inertial_ba2;         /* Map::GetIniertialBA2() */
+} osh_host_cull_scene;
+osh_host_graph* osh_host_cull_graph_create(const osh_host_cull_scene* scene);   /* NULL: bad arguments; freed by osh_host_graph_destroy */
+/* LocalMapping::KeyFrameCulling with mpCurrentKeyFrame = keyframe kf (its covisibility list: osh_host_graph_set_covisible) and
+ * the three flags.  Returns the number of keyframes the call made bad, the first `capacity` of them in list order in culled;
+ * *n_device_calls = the osh_orb_keyframe_cull_count calls it made (0 on the host path).  After the call the wrapper evaluates the
+ * state rule of csrc/keyframe_cull.h for every packed point under the set of culled keyframes and compares it with the objects
+ * (Observations(), isBad()): -2 when they differ.  -1: bad arguments. */
+int osh_host_local_mapping_keyframe_culling(osh_host_graph* g, int32_t kf, int32_t monocular, int32_t inertial, int32_t abort_ba,
+                                            int32_t capacity, int32_t* culled, int32_t* n_device_calls);
+/* LocalMapping::MapPointCulling with mpCurrentKeyFrame = keyframe kf and mlpRecentAddedMapPoints = the points mp[0..n).  Returns the
+ * length of the list afterwards, the first `capacity` as point indices in remaining. */
+int osh_host_local_mapping_map_point_culling(osh_host_graph* g, int32_t kf, int32_t monocular, int32_t n, const int32_t* mp,
+                                             int32_t capacity, int32_t* remaining);
+/* mnFirstKFid, mnVisible and mnFound of a point (what MapPointCulling reads). */
+int osh_host_mp_set_culling(osh_host_graph* g, int32_t mp, int64_t first_kf_id, int32_t n_visible, int32_t n_found);
+/* What KeyFrameCulling packs for the candidate list kf[0..n) (PackKeyFrameCull of csrc/host/host_pack.h), without a device:
+ * sizes = table entries, slots, points, observations; every array may be NULL (call once for the sizes).  table_kf: the keyframe
+ * of each table entry; slot_point and obs_kf index the packed points and the table; slot_index: the slot's place in its keyframe;
+ * point_mp: the map point of each packed point; the others as osh_kfcull_problem. */
+int osh_host_kfcull_pack(osh_host_graph* g, int32_t n, const int32_t* kf, int32_t monocular, int32_t sizes[4], int32_t* table_kf,
+                         int32_t* cand_slot_off, int32_t* slot_point, int32_t* slot_level, int32_t* slot_index, int32_t* point_mp,
+                         int32_t* point_n_obs, uint8_t* point_bad, int32_t* point_obs_off, int32_t* obs_kf, int32_t* obs_level,
+                         int32_t* obs_weight);
+/* csrc/keyframe_cull.h on the host in one thread: the results of osh_orb_keyframe_cull_count for a valid problem (it is not
+ * validated here); *ms = the wall time of the counting loop. */
+struct osh_kfcull_problem;
+struct osh_kfcull_result;
+int osh_host_keyframe_cull_cpu(const struct osh_kfcull_problem* problem, int32_t n_removed, const int32_t* removed_kf,
+                               int32_t first_candidate, const struct osh_kfcull_result* result, double* ms);
+/* For profiles/keyframe_cull_timing.py, on the candidate list kf[0..n): ms[0] = the wall time of PackKeyFrameCull; ms[1] = that of
+ * the counting loop in the reference's shape on the same objects in one thread (per candidate and slot a copy of GetObservations()
+ * and a walk over it); totals = the sums of nMPs and nRedundantObservations that loop finds. */
+int osh_host_kfcull_time(osh_host_graph* g, int32_t n, const int32_t* kf, int32_t monocular, double ms[2], int64_t totals[2]);
+/* out = isBad, mbToBeErased, mPrevKF, mNextKF (keyframe indices, -1: none), the calls of UpdateBestCovisibles, the connection and
+ * the spanning-tree updates SetBadFlag counted, the keyframe whose preintegration this one's MergePrevious received last (-1:
+ * none), the number of MergePrevious calls. */
+int osh_host_kf_cull_state(osh_host_graph* g, int32_t kf, int64_t out[9]);
+/* out = Observations(), isBad(), the size of GetObservations(). */
+int osh_host_mp_cull_state(osh_host_graph* g, int32_t mp, int64_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -478,6 +478,36 @@ class MapPointResult(C.Structure):
 OSH_MAPPOINT_MAX_DESCRIPTORS, OSH_MAPPOINT_MAX_POINTS, OSH_MAPPOINT_MAX_ENTRIES = 256, 1 << 22, 1 << 25
 
 
+class KfCullProblem(C.Structure):
+    """``osh_kfcull_problem`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n_keyframes", C.c_int32), ("n_candidates", C.c_int32), ("redundant_th", C.c_float), ("cand_slot_off", c_int32_p),
+                ("slot_point", c_int32_p), ("slot_level", c_int32_p), ("n_points", C.c_int32), ("point_n_obs", c_int32_p),
+                ("point_bad", c_uint8_p), ("point_obs_off", c_int32_p), ("obs_kf", c_int32_p), ("obs_level", c_int32_p),
+                ("obs_weight", c_int32_p)]
+
+
+class KfCullResult(C.Structure):
+    """``osh_kfcull_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n_mps", c_int32_p), ("n_redundant", c_int32_p), ("redundant", c_uint8_p)]
+
+
+class HostCullScene(C.Structure):
+    """``osh_host_cull_scene`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("n_kf", C.c_int32), ("kf_id", c_int64_p), ("kf_n_slots", c_int32_p), ("kf_n_left", c_int32_p), ("kf_camera2", c_uint8_p),
+                ("kf_th_depth", c_float_p), ("kf_timestamp", c_double_p), ("kf_not_erase", c_uint8_p), ("kf_bad", c_uint8_p),
+                ("kf_imu_pos", c_float_p), ("kf_prev", c_int32_p), ("kf_next", c_int32_p), ("kf_has_preint", c_uint8_p),
+                ("slot_point", c_int32_p), ("slot_octave", c_int32_p), ("slot_u_right", c_float_p), ("slot_depth", c_float_p),
+                ("n_mp", C.c_int32), ("mp_n_obs", c_int32_p), ("mp_bad", c_uint8_p), ("init_kf_id", C.c_int64),
+                ("keyframes_in_map", C.c_int32), ("imu_initialized", C.c_int32), ("inertial_ba2", C.c_int32)]
+
+
+OSH_KFCULL_MAX_CANDIDATES, OSH_KFCULL_MAX_KEYFRAMES = 128, 4096
+OSH_KFCULL_MAX_SLOTS, OSH_KFCULL_MAX_POINTS, OSH_KFCULL_MAX_OBSERVATIONS = 1 << 22, 1 << 22, 1 << 25
+
+
 class FastFrame(C.Structure):
     """``osh_fast_frame`` (include/orbslam3_hip.h)."""
 
@@ -700,6 +730,9 @@ _SIGNATURES = {
     "osh_orb_sim3_ransac_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_refresh_map_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MapPointBatch), C.POINTER(MapPointResult)]),
     "osh_orb_refresh_map_points_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_keyframe_cull_stage": (C.c_int, [C.c_void_p, C.POINTER(KfCullProblem)]),
+    "osh_orb_keyframe_cull_count": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.POINTER(KfCullResult)]),
+    "osh_orb_keyframe_cull_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_fast_detect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult)]),
     "osh_orb_ic_angle": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult)]),
     "osh_orb_fast_get_times": (C.c_int, [C.c_void_p, c_double_p]),
@@ -1111,6 +1144,20 @@ _HOST_SIGNATURES.update({
     "osh_host_graph_fuse": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p, C.c_float, C.c_int32]),
     "osh_host_local_mapping_search_in_neighbors": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "osh_host_local_mapping_process_new_keyframe": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
+})
+
+# LocalMapping::KeyFrameCulling / MapPointCulling and their stand-in map (csrc/hosttest/kfcull.cc)
+_HOST_SIGNATURES.update({
+    "osh_host_cull_graph_create": (C.c_void_p, [C.POINTER(HostCullScene)]),
+    "osh_host_local_mapping_keyframe_culling": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
+    "osh_host_local_mapping_map_point_culling": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_int32_p]),
+    "osh_host_mp_set_culling": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "osh_host_kfcull_pack": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                                       c_int32_p, c_int32_p, c_int32_p, c_uint8_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    "osh_host_keyframe_cull_cpu": (C.c_int, [C.POINTER(KfCullProblem), C.c_int32, c_int32_p, C.c_int32, C.POINTER(KfCullResult), c_double_p]),
+    "osh_host_kfcull_time": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, c_double_p, c_int64_p]),
+    "osh_host_kf_cull_state": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
+    "osh_host_mp_cull_state": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
 })
 
 

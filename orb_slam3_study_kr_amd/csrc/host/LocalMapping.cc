@@ -1,5 +1,5 @@
-// LocalMapping.cc -- LocalMapping::ProcessNewKeyFrame (reference src/LocalMapping.cc:306-346), CreateNewMapPoints (:398-741) and
-// SearchInNeighbors (:743-853) on MI355X (host side).
+// LocalMapping.cc -- LocalMapping::ProcessNewKeyFrame (reference src/LocalMapping.cc:306-346), MapPointCulling (:354-395),
+// CreateNewMapPoints (:398-741), SearchInNeighbors (:743-853) and KeyFrameCulling (:932-1089) on MI355X (host side).
 //
 // ProcessNewKeyFrame and SearchInNeighbors follow the reference statement for statement: the order of vpTargetKFs, the
 // mnFuseTargetForKF / mnFuseCandidateForKF marks, the mbAbortBA exits, one ORBmatcher::Fuse per target keyframe (and one more for
@@ -18,7 +18,23 @@
 // (:503-720) runs for all pairs of the neighbour in ONE osh_orb_triangulate_new_points call (csrc/newpoint_device.hip), and the
 // part that changes the map (:722-738) is replayed on the host for the accepted pairs in match order.
 //
+// KeyFrameCulling:
+// Everything but the counting loop (:976-1042) is the reference's statement for statement: the candidate list, redundant_th, the
+// last_ID walk, count++ and the skip of the initial and of bad keyframes, the decision, the inertial guards and both cull branches
+// with MergePrevious and the re-linking, the two exits.  The counting is osh_orb_keyframe_cull_count on a problem that
+// PackKeyFrameCull (host_pack.h) builds and osh_orb_keyframe_cull_stage uploads ONCE per call: the first count, with the empty
+// removed set, gives nMPs and nRedundantObservations of every candidate; whenever SetBadFlag has actually made a keyframe bad
+// (isBad() afterwards: one with mbNotErase only gets mbToBeErased) it joins the removed set and one more count gives the values
+// of the candidates after it.  So a call that culls n keyframes makes n + 1 device calls.  The host never recounts: that a culled
+// keyframe's points lose an observer and may go bad is the state rule of csrc/keyframe_cull.h, evaluated on the device.  Without a
+// device, on a device error or beyond the limits of the entry the same counts come from the host build of that header.
+// The loop leaves after the 101st keyframe of the list (:1084) unless that one is skipped by a `continue`, which passes the exit
+// test as well; the first OSH_KFCULL_MAX_CANDIDATES = 128 keyframes of the list are packed, and a keyframe the loop reaches beyond
+// them is counted alone on the host from the map as it is then.
+//
 // Deviations from the reference, all intended:
+//   * KeyFrameCulling reads the level of a right slot i of a rig from mvKeysRight[i - NLeft]; the reference reads mvKeysRight[i]
+//     (:1003), the wrong key or one past the end;
 //   * the null vector of GeometricTools::Triangulate comes from an FP64 Jacobi method on the device, and x3D is rounded to float32
 //     once (include/orbslam3_hip.h);
 //   * in the monocular median-depth test a neighbour without map points is skipped; the reference indexes an empty vector there
@@ -31,6 +47,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "../keyframe_cull.h"
 #include "ORBmatcher.h"
 #include "host_pack.h"
 #include "orbslam3_hip.h"
@@ -163,6 +180,186 @@ void LocalMapping::ProcessNewKeyFrame() {
 
   // Insert Keyframe in Map
   mpAtlas->AddKeyFrame(mpCurrentKeyFrame);
+}
+
+// src/LocalMapping.cc:354-395
+void LocalMapping::MapPointCulling() {
+  // Check Recent Added MapPoints
+  std::list<MapPoint*>::iterator lit = mlpRecentAddedMapPoints.begin();
+  const unsigned long int nCurrentKFid = mpCurrentKeyFrame->mnId;
+
+  int nThObs;
+  if (mbMonocular) nThObs = 2;
+  else nThObs = 3;
+  const int cnThObs = nThObs;
+
+  while (lit != mlpRecentAddedMapPoints.end()) {
+    MapPoint* pMP = *lit;
+    if (pMP->isBad()) {
+      lit = mlpRecentAddedMapPoints.erase(lit);
+    } else if (pMP->GetFoundRatio() < 0.25f) {
+      pMP->SetBadFlag();
+      lit = mlpRecentAddedMapPoints.erase(lit);
+    } else if (((int)nCurrentKFid - (int)pMP->mnFirstKFid) >= 2 && pMP->Observations() <= cnThObs) {
+      pMP->SetBadFlag();
+      lit = mlpRecentAddedMapPoints.erase(lit);
+    } else if (((int)nCurrentKFid - (int)pMP->mnFirstKFid) >= 3) {
+      lit = mlpRecentAddedMapPoints.erase(lit);
+    } else {
+      lit++;
+    }
+  }
+}
+
+namespace {
+
+// nMPs, nRedundantObservations and the decision of the candidates from `first` on under a removed set, on the device (a staged
+// problem) or by the host build of csrc/keyframe_cull.h
+struct KeyFrameCullCounter {
+  const KeyFrameCullPack& pk;
+  float redundant_th;
+  osh_orb_ctx* ctx = nullptr;   // null: the host path
+  int device_calls = 0;
+  int base = 0;                 // the candidate entry 0 of the arrays belongs to
+  std::vector<int32_t> n_mps, n_redundant;
+  std::vector<uint8_t> redundant;
+  std::vector<osh::KcPoint> h_point;   // the host path's records, built on first use
+  std::vector<uint32_t> h_obs;
+
+  KeyFrameCullCounter(const KeyFrameCullPack& pack, float th) : pk(pack), redundant_th(th), n_mps(pack.n_candidates), n_redundant(pack.n_candidates), redundant(pack.n_candidates) {}
+
+  void Stage() {
+    if (!pk.within_device_limits()) return;
+    ctx = HostMatcherContext();
+    if (!ctx) return;
+    osh_kfcull_problem b;
+    pk.fill(b, redundant_th);
+    if (osh_orb_keyframe_cull_stage(ctx, &b) != OSH_OK) {
+      std::fprintf(stderr, "LocalMapping::KeyFrameCulling: %s; counted on the host\n", osh_last_error());
+      ctx = nullptr;
+    }
+  }
+  void Count(const std::vector<int32_t>& removed, int first) {
+    base = first;
+    if (ctx) {
+      const osh_kfcull_result r{n_mps.data(), n_redundant.data(), redundant.data()};
+      ++device_calls;
+      if (osh_orb_keyframe_cull_count(ctx, (int32_t)removed.size(), removed.data(), first, &r) == OSH_OK) return;
+      std::fprintf(stderr, "LocalMapping::KeyFrameCulling: %s; counted on the host\n", osh_last_error());
+      ctx = nullptr;
+    }
+    if (h_point.size() != pk.points.size() || h_obs.size() != pk.obs_kf.size()) {
+      h_point.resize(pk.points.size()); h_obs.resize(pk.obs_kf.size());
+      for (size_t p = 0; p < pk.points.size(); ++p)
+        h_point[p] = osh::KcPoint{pk.point_obs_off[p], pk.point_obs_off[p + 1] - pk.point_obs_off[p], pk.point_n_obs[p], (int)pk.point_bad[p]};
+      for (size_t e = 0; e < pk.obs_kf.size(); ++e) h_obs[e] = osh::kc_obs_word(pk.obs_kf[e], pk.obs_level[e], pk.obs_weight[e]);
+    }
+    std::vector<uint32_t> mask((pk.table.size() + 31) / 32 + 1, 0u);
+    for (const int32_t k : removed) mask[k >> 5] |= 1u << (k & 31);
+    const osh::KcView v{pk.cand_slot_off.data(), pk.slot_point.data(), pk.slot_level.data(), h_point.data(), h_obs.data()};
+    for (int k = first; k < pk.n_candidates; ++k) {
+      int a, b;
+      osh::kc_count_candidate(v, mask.data(), k, a, b);
+      n_mps[k - first] = a; n_redundant[k - first] = b; redundant[k - first] = (uint8_t)osh::kc_decide(b, a, redundant_th);
+    }
+  }
+};
+
+}  // namespace
+
+// src/LocalMapping.cc:932-1089
+void LocalMapping::KeyFrameCulling() {
+  // Check redundant keyframes (only local keyframes): a keyframe is considered redundant if 90% of the MapPoints it sees are seen
+  // in at least other 3 keyframes (in the same or finer scale); only close stereo points are considered
+  const int Nd = 21;
+  mpCurrentKeyFrame->UpdateBestCovisibles();
+  std::vector<KeyFrame*> vpLocalKeyFrames = mpCurrentKeyFrame->GetVectorCovisibleKeyFrames();
+
+  float redundant_th;
+  if (!mbInertial) redundant_th = 0.9;
+  else if (mbMonocular) redundant_th = 0.9;
+  else redundant_th = 0.5;
+
+  const bool bInitImu = mpAtlas->isImuInitialized();
+  int count = 0;
+
+  // Compute last KF from optimizable window:
+  unsigned int last_ID = 0;
+  if (mbInertial) {
+    int count = 0;
+    KeyFrame* aux_KF = mpCurrentKeyFrame;
+    while (count < Nd && aux_KF->mPrevKF) {
+      aux_KF = aux_KF->mPrevKF;
+      count++;
+    }
+    last_ID = aux_KF->mnId;
+  }
+
+  // the counting of :976-1042 for all candidates at once
+  mnKeyFrameCullDeviceCalls = 0;
+  const std::vector<KeyFrame*> vpCandidates(vpLocalKeyFrames.begin(), vpLocalKeyFrames.begin() + std::min<size_t>(vpLocalKeyFrames.size(), OSH_KFCULL_MAX_CANDIDATES));
+  KeyFrameCullPack pk;
+  PackKeyFrameCull(vpCandidates, mbMonocular, pk);
+  KeyFrameCullCounter counter(pk, redundant_th);
+  std::vector<int32_t> removed;
+  counter.Stage();
+  counter.Count(removed, 0);
+
+  int at = -1;   // the candidate's place in the list
+  for (std::vector<KeyFrame*>::iterator vit = vpLocalKeyFrames.begin(), vend = vpLocalKeyFrames.end(); vit != vend; vit++) {
+    count++;
+    at++;
+    KeyFrame* pKF = *vit;
+
+    if ((pKF->mnId == pKF->GetMap()->GetInitKFid()) || pKF->isBad()) continue;
+
+    bool bRedundant;   // nRedundantObservations > redundant_th * nMPs
+    if (at < pk.n_candidates) {
+      bRedundant = counter.redundant[at - counter.base] != 0;
+    } else {           // past the packed candidates: this keyframe alone, from the map as it is now, on the host
+      KeyFrameCullPack one;
+      PackKeyFrameCull(std::vector<KeyFrame*>(1, pKF), mbMonocular, one);
+      KeyFrameCullCounter single(one, redundant_th);
+      single.Count(std::vector<int32_t>(), 0);
+      bRedundant = single.redundant[0] != 0;
+    }
+    if (bRedundant) {
+      if (mbInertial) {
+        if (mpAtlas->KeyFramesInMap() <= Nd) continue;
+
+        if (pKF->mnId > (mpCurrentKeyFrame->mnId - 2)) continue;
+
+        if (pKF->mPrevKF && pKF->mNextKF) {
+          const float t = pKF->mNextKF->mTimeStamp - pKF->mPrevKF->mTimeStamp;
+
+          if ((bInitImu && (pKF->mnId < last_ID) && t < 3.) || (t < 0.5)) {
+            pKF->mNextKF->mpImuPreintegrated->MergePrevious(pKF->mpImuPreintegrated);
+            pKF->mNextKF->mPrevKF = pKF->mPrevKF;
+            pKF->mPrevKF->mNextKF = pKF->mNextKF;
+            pKF->mNextKF = NULL;
+            pKF->mPrevKF = NULL;
+            pKF->SetBadFlag();
+          } else if (!mpCurrentKeyFrame->GetMap()->GetIniertialBA2() && ((pKF->GetImuPosition() - pKF->mPrevKF->GetImuPosition()).norm() < 0.02) && (t < 3)) {
+            pKF->mNextKF->mpImuPreintegrated->MergePrevious(pKF->mpImuPreintegrated);
+            pKF->mNextKF->mPrevKF = pKF->mPrevKF;
+            pKF->mPrevKF->mNextKF = pKF->mNextKF;
+            pKF->mNextKF = NULL;
+            pKF->mPrevKF = NULL;
+            pKF->SetBadFlag();
+          }
+        }
+      } else {
+        pKF->SetBadFlag();
+      }
+      // a keyframe that is gone takes an observer from its points: the candidates after it are counted again
+      if (pKF->isBad() && at < pk.n_candidates) {
+        removed.push_back(at);
+        counter.Count(removed, at + 1);
+      }
+    }
+    if ((count > 20 && mbAbortBA) || count > 100) break;
+  }
+  mnKeyFrameCullDeviceCalls = counter.device_calls;
 }
 
 // src/LocalMapping.cc:743-853

@@ -7,6 +7,7 @@
 #include <list>
 #include <map>
 #include <set>
+#include <unordered_map>
 #include <vector>
 #include "CameraModels/GeometricCamera.h"
 #include "Frame.h"
@@ -718,6 +719,93 @@ inline void PackMapPointRefresh(const std::vector<MapPoint*>& vpMPs, MapPointRef
     pk.ref_centre.push_back(pk.centre_index(pRefKF));
     pk.level_scale.push_back(pRefKF->mvScaleFactors[level]);
     pk.top_scale.push_back(pRefKF->mvScaleFactors[pRefKF->mnScaleLevels - 1]);
+  }
+}
+
+// ---- LocalMapping::KeyFrameCulling: the problem of osh_orb_keyframe_cull_stage
+// What the counting loop of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:976-1042) reads, as the records of
+// csrc/keyframe_cull.h.  The keyframe table starts with the candidates in list order (candidate c is entry c); every other observer
+// follows in the order it is first met.  A candidate that is the map's initial keyframe or bad (:974) or that occurs a second time
+// in the list keeps its entry and gets no slots.  A slot is packed when it holds a point and passes the depth test of :989-993; a
+// bad point is packed too, its state is evaluated with the removed set.  The observations of each DISTINCT point are walked once.
+// An observation with neither index (no keypoint to take a level from) is left out.
+struct KeyFrameCullPack {
+  std::vector<KeyFrame*> table;    // candidates first
+  std::vector<MapPoint*> points;
+  int32_t n_candidates = 0;
+  std::vector<int32_t> cand_slot_off{0}, slot_point, slot_level, slot_index, point_n_obs, point_obs_off{0}, obs_kf, obs_level, obs_weight;
+  std::vector<uint8_t> point_bad;
+  void fill(osh_kfcull_problem& b, float redundant_th) const {
+    b.n_keyframes = (int32_t)table.size(); b.n_candidates = n_candidates; b.redundant_th = redundant_th;
+    b.cand_slot_off = cand_slot_off.data(); b.slot_point = slot_point.data(); b.slot_level = slot_level.data();
+    b.n_points = (int32_t)points.size(); b.point_n_obs = point_n_obs.data(); b.point_bad = point_bad.data();
+    b.point_obs_off = point_obs_off.data(); b.obs_kf = obs_kf.data(); b.obs_level = obs_level.data(); b.obs_weight = obs_weight.data();
+  }
+  bool within_device_limits() const {
+    return n_candidates <= OSH_KFCULL_MAX_CANDIDATES && table.size() <= (size_t)OSH_KFCULL_MAX_KEYFRAMES &&
+           slot_point.size() <= (size_t)OSH_KFCULL_MAX_SLOTS && points.size() <= (size_t)OSH_KFCULL_MAX_POINTS &&
+           obs_kf.size() <= (size_t)OSH_KFCULL_MAX_OBSERVATIONS;
+  }
+};
+inline void PackKeyFrameCull(const std::vector<KeyFrame*>& vpCandidates, bool bMonocular, KeyFrameCullPack& pk) {
+  std::unordered_map<KeyFrame*, int> table_of;
+  std::unordered_map<MapPoint*, int> point_of;
+  pk.n_candidates = (int32_t)vpCandidates.size();
+  std::vector<uint8_t> first(vpCandidates.size(), 0);
+  for (size_t c = 0; c < vpCandidates.size(); ++c) {
+    pk.table.push_back(vpCandidates[c]);
+    first[c] = table_of.emplace(vpCandidates[c], (int)c).second ? 1 : 0;
+  }
+  for (size_t c = 0; c < vpCandidates.size(); ++c) {
+    KeyFrame* pKF = vpCandidates[c];
+    if (first[c] && !(pKF->mnId == pKF->GetMap()->GetInitKFid()) && !pKF->isBad()) {
+      const std::vector<MapPoint*> vpMapPoints = pKF->GetMapPointMatches();
+      for (size_t i = 0, iend = vpMapPoints.size(); i < iend; i++) {
+        MapPoint* pMP = vpMapPoints[i];
+        if (!pMP) continue;
+        if (!bMonocular) {
+          if (pKF->mvDepth[i] > pKF->mThDepth || pKF->mvDepth[i] < 0) continue;
+        }
+        // :1001-1003, with the right keypoint of a rig slot at i - NLeft (the reference reads mvKeysRight[i])
+        const int scaleLevel = (pKF->NLeft == -1) ? pKF->mvKeysUn[i].octave
+                               : ((int)i < pKF->NLeft) ? pKF->mvKeys[i].octave : pKF->mvKeysRight[i - pKF->NLeft].octave;
+        auto at = point_of.find(pMP);
+        if (at == point_of.end()) {
+          at = point_of.emplace(pMP, (int)pk.points.size()).first;
+          pk.points.push_back(pMP);
+          pk.point_n_obs.push_back(pMP->Observations());
+          pk.point_bad.push_back(pMP->isBad() ? 1 : 0);
+          const std::map<KeyFrame*, std::tuple<int, int>> observations = pMP->GetObservations();
+          for (const auto& ob : observations) {
+            KeyFrame* pKFi = ob.first;
+            const int leftIndex = std::get<0>(ob.second), rightIndex = std::get<1>(ob.second);
+            if (leftIndex == -1 && rightIndex == -1) continue;
+            int scaleLeveli = -1;   // :1013-1026
+            if (pKFi->NLeft == -1) {
+              scaleLeveli = pKFi->mvKeysUn[leftIndex == -1 ? rightIndex : leftIndex].octave;
+            } else {
+              if (leftIndex != -1) scaleLeveli = pKFi->mvKeys[leftIndex].octave;
+              if (rightIndex != -1) {
+                const int rightLevel = pKFi->mvKeysRight[rightIndex - pKFi->NLeft].octave;
+                scaleLeveli = (scaleLeveli == -1 || scaleLeveli > rightLevel) ? rightLevel : scaleLeveli;
+              }
+            }
+            int weight = 0;         // src/MapPoint.cc:178-186
+            if (leftIndex != -1) weight += (!pKFi->mpCamera2 && pKFi->mvuRight[leftIndex] >= 0) ? 2 : 1;
+            if (rightIndex != -1) weight += 1;
+            auto kf_at = table_of.find(pKFi);
+            if (kf_at == table_of.end()) {
+              kf_at = table_of.emplace(pKFi, (int)pk.table.size()).first;
+              pk.table.push_back(pKFi);
+            }
+            pk.obs_kf.push_back(kf_at->second); pk.obs_level.push_back(scaleLeveli); pk.obs_weight.push_back(weight);
+          }
+          pk.point_obs_off.push_back((int32_t)pk.obs_kf.size());
+        }
+        pk.slot_point.push_back(at->second); pk.slot_level.push_back(scaleLevel); pk.slot_index.push_back((int32_t)i);
+      }
+    }
+    pk.cand_slot_off.push_back((int32_t)pk.slot_point.size());
   }
 }
 }  // namespace ORB_SLAM3

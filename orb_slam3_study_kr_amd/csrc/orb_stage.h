@@ -13,6 +13,8 @@
 // osh_orb_two_view_reconstruct (two_view_device.hip), osh_orb_mlpnp_solve (mlpnp_device.hip) and osh_orb_sim3_ransac
 // (sim3_ransac_device.hip) have problems of correspondences and minimal sets: ransac_stage.h is their validator, batch bookkeeping and
 // ballot loops; they use scatter, PhaseClock, orb_state and copy_times (MLPnP with five times).
+// osh_orb_keyframe_cull_stage / _count (keyframe_cull_device.hip) keep one problem resident and count it under removed sets: they use
+// PhaseClock, orb_state and copy_times.
 #pragma once
 #include "common.h"
 #include <chrono>

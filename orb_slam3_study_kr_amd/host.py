@@ -330,6 +330,118 @@ class HostGraph:
         return dict(recent=recent[:n].copy(), in_map=int(in_map.value))
 
 
+class HostCullGraph:
+    """The stand-in map of a synth_keyframe_cull.CullScene (osh_host_cull_graph_create) for LocalMapping::KeyFrameCulling,
+    MapPointCulling and PackKeyFrameCull.  Keyframe and point indices are those of the scene."""
+
+    def __init__(self, sc):
+        self.lib = capi.load_host_library()
+        self.sc = sc
+        kfs = sc.kfs
+        u8 = lambda a: np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+        slots = [s for kf in kfs for s in kf["slots"]]
+        a = dict(
+            kf_id=np.ascontiguousarray([kf["id"] for kf in kfs], dtype=np.int64), kf_n_slots=_i32([len(kf["slots"]) for kf in kfs]),
+            kf_n_left=_i32([kf["n_left"] for kf in kfs]), kf_camera2=u8([kf["camera2"] for kf in kfs]),
+            kf_th_depth=_f32([kf["th_depth"] for kf in kfs]), kf_timestamp=np.ascontiguousarray([kf["timestamp"] for kf in kfs], dtype=np.float64),
+            kf_not_erase=u8([kf["not_erase"] for kf in kfs]), kf_bad=u8([kf["bad"] for kf in kfs]),
+            kf_imu_pos=_f32([kf["imu_pos"] for kf in kfs]).reshape(-1), kf_prev=_i32([kf["prev"] for kf in kfs]), kf_next=_i32([kf["next"] for kf in kfs]),
+            kf_has_preint=u8([kf["preint"] for kf in kfs]), slot_point=_i32([s[0] for s in slots]).reshape(-1), slot_octave=_i32([s[1] for s in slots]).reshape(-1),
+            slot_u_right=_f32([s[2] for s in slots]).reshape(-1), slot_depth=_f32([s[3] for s in slots]).reshape(-1),
+            mp_n_obs=_i32([sc.mp_n_obs.get(j, -1) for j in range(sc.n_mp)]).reshape(-1), mp_bad=u8([j in sc.mp_bad for j in range(sc.n_mp)]))
+        c = capi.HostCullScene()
+        c.n_kf, c.n_mp = len(kfs), sc.n_mp
+        c.init_kf_id, c.keyframes_in_map = int(sc.init_kf_id), int(sc.keyframes_in_map)
+        c.imu_initialized, c.inertial_ba2 = int(sc.imu_initialized), int(sc.inertial_ba2)
+        types = dict(capi.HostCullScene._fields_)
+        for name, arr in a.items():
+            setattr(c, name, capi.ptr(arr, types[name]))
+        self.g = C.c_void_p(self.lib.osh_host_cull_graph_create(C.byref(c)))
+        if not self.g:
+            raise RuntimeError("osh_host_cull_graph_create refused the scene")
+        if sc.current is not None:
+            cov = _i32(sc.covisible).reshape(-1)
+            self.lib.osh_host_graph_set_covisible(self.g, sc.current, len(cov), capi.ptr(cov, capi.c_int32_p))
+
+    def close(self):
+        if self.g:
+            self.lib.osh_host_graph_destroy(self.g)
+            self.g = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def keyframe_culling(self) -> dict:
+        """LocalMapping::KeyFrameCulling with the scene's current keyframe and flags: the culled keyframes in list order and the
+        number of osh_orb_keyframe_cull_count calls.  The wrapper's check of the state rule against the objects raises here."""
+        sc = self.sc
+        culled = np.full(max(1, len(sc.covisible)), -1, dtype=np.int32)
+        calls = C.c_int32(-1)
+        n = self.lib.osh_host_local_mapping_keyframe_culling(self.g, sc.current, int(sc.monocular), int(sc.inertial), int(sc.abort_ba), len(culled),
+                                                             capi.ptr(culled, capi.c_int32_p), C.byref(calls))
+        if n == -2:
+            raise AssertionError("the state rule of keyframe_cull.h disagrees with the map points after SetBadFlag")
+        if n < 0:
+            raise RuntimeError(f"osh_host_local_mapping_keyframe_culling -> {n}")
+        return {"culled": [int(k) for k in culled[:n]], "device_calls": int(calls.value)}
+
+    def pack(self, candidates=None, monocular=None, objects: bool = True) -> dict:
+        """PackKeyFrameCull for a candidate list (default: the scene's covisibility list), as tests/keyframe_cull_numpy.pack.
+        objects=False leaves out table_kf and point_mp (a linear search per entry)."""
+        cand = _i32(self.sc.covisible if candidates is None else candidates).reshape(-1)
+        mono = int(self.sc.monocular if monocular is None else monocular)
+        sizes = np.zeros(4, dtype=np.int32)
+        nul = [None] * 12
+
+        def call(arrs):
+            rc = self.lib.osh_host_kfcull_pack(self.g, len(cand), capi.ptr(cand, capi.c_int32_p), mono, capi.ptr(sizes, capi.c_int32_p),
+                                               *[capi.ptr(x, capi.c_uint8_p if i == 7 else capi.c_int32_p) for i, x in enumerate(arrs)])
+            assert rc == 0, rc
+        call(nul)
+        T, S, P, E = (int(x) for x in sizes)
+        names = ["table_kf", "cand_slot_off", "slot_point", "slot_level", "slot_index", "point_mp", "point_n_obs", "point_bad", "point_obs_off",
+                 "obs_kf", "obs_level", "obs_weight"]
+        shape = [T, len(cand) + 1, S, S, S, P, P, P, P + 1, E, E, E]
+        arrs = [np.zeros(n, dtype=np.uint8 if name == "point_bad" else np.int32) for name, n in zip(names, shape)]
+        call([None if (not objects and name in ("table_kf", "point_mp")) else x for name, x in zip(names, arrs)])
+        return dict(zip(names, arrs))
+
+    def pack_and_reference_times(self, candidates=None, monocular=None) -> dict:
+        """osh_host_kfcull_time: the wall time of PackKeyFrameCull and of the reference-shaped counting loop, with that loop's totals."""
+        cand = _i32(self.sc.covisible if candidates is None else candidates).reshape(-1)
+        mono = int(self.sc.monocular if monocular is None else monocular)
+        ms, totals = np.zeros(2, dtype=np.float64), np.zeros(2, dtype=np.int64)
+        rc = self.lib.osh_host_kfcull_time(self.g, len(cand), capi.ptr(cand, capi.c_int32_p), mono, capi.ptr(ms, capi.c_double_p), capi.ptr(totals, capi.c_int64_p))
+        assert rc == 0, rc
+        return {"pack_ms": float(ms[0]), "reference_loop_ms": float(ms[1]), "n_mps": int(totals[0]), "n_redundant": int(totals[1])}
+
+    def kf_state(self, k: int) -> dict:
+        out = np.zeros(9, dtype=np.int64)
+        assert self.lib.osh_host_kf_cull_state(self.g, int(k), capi.ptr(out, capi.c_int64_p)) == 0
+        names = ["bad", "to_be_erased", "prev", "next", "best_covisible_updates", "connection_erasures", "spanning_tree_updates", "merged_previous", "merges"]
+        return dict(zip(names, (int(x) for x in out)))
+
+    def mp_state(self, j: int) -> dict:
+        out = np.zeros(3, dtype=np.int64)
+        assert self.lib.osh_host_mp_cull_state(self.g, int(j), capi.ptr(out, capi.c_int64_p)) == 0
+        return {"n_obs": int(out[0]), "bad": int(out[1]), "observers": int(out[2])}
+
+    def set_point_culling(self, j: int, first_kf_id: int, n_visible: int, n_found: int):
+        assert self.lib.osh_host_mp_set_culling(self.g, int(j), int(first_kf_id), int(n_visible), int(n_found)) == 0
+
+    def map_point_culling(self, kf: int, points, monocular: bool) -> list:
+        """LocalMapping::MapPointCulling with mlpRecentAddedMapPoints = points: the list afterwards."""
+        pts = _i32(points).reshape(-1)
+        rem = np.full(max(1, len(pts)), -1, dtype=np.int32)
+        n = self.lib.osh_host_local_mapping_map_point_culling(self.g, int(kf), int(monocular), len(pts), capi.ptr(pts, capi.c_int32_p), len(rem),
+                                                              capi.ptr(rem, capi.c_int32_p))
+        assert n >= 0, n
+        return [int(x) for x in rem[:n]]
+
+
 class HostFrame:
     def __init__(self, xy, octave, desc, angle=None, uright=None, pose_qt=None, mbf=float(synth.BF), mb=0.110078, kb8=None):
         self.lib = capi.load_host_library()

@@ -261,6 +261,24 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_refresh_map_points(self.ctx, len(batches), cb, cr), "osh_orb_refresh_map_points", self.lib)
         return outs
 
+    def keyframe_cull_stage(self, problem):
+        """Uploads a synth_keyframe_cull.CullProblem (osh_orb_keyframe_cull_stage): it stays resident until the next stage call."""
+        cp, _keep = kfcull_problem(problem)
+        capi.check(self.lib.osh_orb_keyframe_cull_stage(self.ctx, C.byref(cp)), "osh_orb_keyframe_cull_stage", self.lib)
+        self._kfcull_candidates = int(problem.n_candidates)
+
+    def keyframe_cull_count(self, removed=(), first_candidate: int = 0, n_candidates: int | None = None) -> dict:
+        """nMPs, nRedundantObservations and the decision of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:976-1044) for the
+        candidates from first_candidate on of the staged problem under a removed set (osh_orb_keyframe_cull_count)."""
+        n = max(0, (self._kfcull_candidates if n_candidates is None else n_candidates) - first_candidate)
+        out, cr = kfcull_result(n)
+        rm = np.ascontiguousarray(removed, np.int32).reshape(-1)
+        capi.check(self.lib.osh_orb_keyframe_cull_count(self.ctx, len(rm), capi.ptr(rm, capi.c_int32_p), int(first_candidate), C.byref(cr)),
+                   "osh_orb_keyframe_cull_count", self.lib)
+        return out
+
+    keyframe_cull_times = functools.partialmethod(_times, "osh_orb_keyframe_cull_get_times")   # of the last stage and the last count
+
     def fast_detect(self, frames, capacities=None, borders=None) -> list:
         """The cell-wise FAST corners of ORBextractor::ComputeKeyPointsOctTree (src/ORBextractor.cc:787-872) for a batch of
         synth_fast.FastFrame in one osh_orb_fast_detect call: per frame a dict with n_out, n_cells, token, level_count and xy [n, 2],
@@ -1419,6 +1437,42 @@ def mappoint_cpu(batches, host_lib=None):
     if rc != 0:
         raise RuntimeError(f"osh_host_mappoint_refresh_cpu -> {rc}")
     return outs, float(ms.value)
+
+
+_KFCULL_ARRAYS = (("cand_slot_off", np.int32), ("slot_point", np.int32), ("slot_level", np.int32), ("point_n_obs", np.int32),
+                  ("point_bad", np.uint8), ("point_obs_off", np.int32), ("obs_kf", np.int32), ("obs_level", np.int32), ("obs_weight", np.int32))
+
+
+def kfcull_problem(problem):
+    """The osh_kfcull_problem of a synth_keyframe_cull.CullProblem and the arrays that keep its pointers alive."""
+    cp = capi.KfCullProblem()
+    cp.n_keyframes, cp.n_candidates, cp.redundant_th = int(problem.n_keyframes), int(problem.n_candidates), float(problem.redundant_th)
+    cp.n_points = int(problem.n_points)
+    keep = {}
+    for name, dt in _KFCULL_ARRAYS:
+        keep[name] = np.ascontiguousarray(getattr(problem, name), dt)
+        setattr(cp, name, capi.ptr(keep[name], capi.c_int32_p if dt is np.int32 else capi.c_uint8_p))
+    return cp, keep
+
+
+def kfcull_result(n: int, fill: int = 0):
+    out = {"n_mps": np.full(n, fill, np.int32), "n_redundant": np.full(n, fill, np.int32), "redundant": np.full(n, fill, np.uint8)}
+    cr = capi.KfCullResult(capi.ptr(out["n_mps"], capi.c_int32_p), capi.ptr(out["n_redundant"], capi.c_int32_p), capi.ptr(out["redundant"], capi.c_uint8_p))
+    return out, cr
+
+
+def kfcull_cpu(problem, removed=(), first_candidate: int = 0, host_lib=None):
+    """csrc/keyframe_cull.h on the host in one thread (osh_host_keyframe_cull_cpu of the test library): the dict of
+    keyframe_cull_count and the wall time of the counting loop in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    cp, _keep = kfcull_problem(problem)
+    out, cr = kfcull_result(max(0, int(problem.n_candidates) - first_candidate))
+    rm = np.ascontiguousarray(removed, np.int32).reshape(-1)
+    ms = C.c_double(0)
+    rc = host_lib.osh_host_keyframe_cull_cpu(C.byref(cp), len(rm), capi.ptr(rm, capi.c_int32_p), int(first_candidate), C.byref(cr), C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_keyframe_cull_cpu -> {rc}")
+    return out, float(ms.value)
 
 
 def kb8_rig(cam1, cam2, precision1, precision2, R12, t12) -> "capi.Kb8Rig":
