@@ -7,6 +7,7 @@
 #define ORBEXTRACTOR_H
 #include <vector>
 #include "orbslam3_compat.h"
+#include "RectifyMap.h"
 namespace ORB_SLAM3 {
 class ORBextractor {
  public:
@@ -38,6 +39,21 @@ class ORBextractor {
   static void ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
                            std::vector<std::vector<cv::KeyPoint> >& vKeypoints, std::vector<cv::Mat>& vDescriptors,
                            const std::vector<std::vector<int> >& vLappingAreas, std::vector<int>& vMonoIndex, bool bKeepPyramid = true);
+
+  /* ADD THIS MEMBER too: ExtractBatch on the camera images as they arrive, as ONE osh_orb_extract_raw call
+   * (csrc/orb_prepare_device.hip): vRawImages[i] (CV_8UC1, CV_8UC3 or CV_8UC4) is remapped with vPrep[i].pMap or resized to
+   * vPrep[i].newRows x newCols on the device, turned grey with vPrep[i].bRGB, and extracted as ExtractBatch extracts the result, so
+   * that the cv::remap / cv::resize of System::Track* and the cvtColor of Tracking::GrabImage* are not run.  Everything else is
+   * ExtractBatch's.  *pvGray (may be null) receives the prepared grey images, what Tracking keeps as mImGray */
+  static void ExtractBatchRaw(const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vRawImages,
+                              const std::vector<ImagePrep>& vPrep, std::vector<std::vector<cv::KeyPoint> >& vKeypoints,
+                              std::vector<cv::Mat>& vDescriptors, const std::vector<std::vector<int> >& vLappingAreas,
+                              std::vector<int>& vMonoIndex, bool bKeepPyramid = true, std::vector<cv::Mat>* pvGray = nullptr);
+  /* ADD THIS MEMBER too: the body of the two (pvPrep null: ExtractBatch) */
+  static void ExtractBatchFrom(const char* who, const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
+                               const std::vector<ImagePrep>* pvPrep, std::vector<std::vector<cv::KeyPoint> >& vKeypoints,
+                               std::vector<cv::Mat>& vDescriptors, const std::vector<std::vector<int> >& vLappingAreas,
+                               std::vector<int>& vMonoIndex, bool bKeepPyramid, std::vector<cv::Mat>* pvGray);
 
   std::vector<cv::Point> pattern;   /* the 512 sampling points, filled by the constructor */
 

@@ -232,26 +232,31 @@ struct KeyPoint { Point2f pt; float size = 0, angle = -1, response = 0; int octa
 // Row-major byte matrix (CV_8U only: descriptor matrices N x 32 and the pyramid levels of an ORBextractor cross this boundary).
 // `step` is the row stride in bytes as in cv::Mat; it equals cols unless the matrix is a view() into a larger one, which is how the
 // reference's pyramid levels are stored (views into a bordered image, src/ORBextractor.cc ComputePyramid).
+// A camera image before ORBextractor::ExtractBatchRaw may have 3 or 4 interleaved channels (CV_8UC3, CV_8UC4): channels() says how
+// many, 1 unless the matrix was made with a count; `cols` stays in pixels and `step` in bytes.
 class Mat {
  public:
   int rows = 0, cols = 0;
   size_t step = 0;
   Mat() {}
   Mat(int r, int c) : rows(r), cols(c), step((size_t)c), buf_(new std::vector<uint8_t>((size_t)r * c, 0)), off_(0) {}
+  Mat(int r, int c, int channels) : rows(r), cols(c), step((size_t)c * channels), buf_(new std::vector<uint8_t>((size_t)r * c * channels, 0)), off_(0), cn_(channels) {}
   bool empty() const { return rows == 0; }
+  int channels() const { return cn_; }
   template <class T> T* ptr(int r = 0) { return reinterpret_cast<T*>(buf_->data() + off_ + (size_t)r * step); }
   template <class T> const T* ptr(int r = 0) const { return reinterpret_cast<const T*>(buf_->data() + off_ + (size_t)r * step); }
-  Mat row(int r) const { Mat m; m.rows = 1; m.cols = cols; m.step = step; m.buf_ = buf_; m.off_ = off_ + (size_t)r * step; return m; }
+  Mat row(int r) const { Mat m; m.rows = 1; m.cols = cols; m.step = step; m.buf_ = buf_; m.off_ = off_ + (size_t)r * step; m.cn_ = cn_; return m; }
   // rows [r0, r0 + nr) x columns [c0, c0 + nc) of this matrix, sharing its storage (cv::Mat::operator()(Rect))
-  Mat view(int r0, int c0, int nr, int nc) const { Mat m; m.rows = nr; m.cols = nc; m.step = step; m.buf_ = buf_; m.off_ = off_ + (size_t)r0 * step + c0; return m; }
+  Mat view(int r0, int c0, int nr, int nc) const { Mat m; m.rows = nr; m.cols = nc; m.step = step; m.buf_ = buf_; m.off_ = off_ + (size_t)r0 * step + (size_t)c0 * cn_; m.cn_ = cn_; return m; }
   // what ORBextractor::operator() asks of its InputArray / OutputArray arguments, which are Mat references here
   void create(int r, int c, int /*type*/) { if (r != rows || c != cols || step != (size_t)c || !buf_) *this = Mat(r, c); }
   void release() { *this = Mat(); }
   Mat getMat() const { return *this; }   // shares the storage
-  Mat clone() const { Mat m(rows, cols); for (int r = 0; r < rows; ++r) std::memcpy(m.buf_->data() + (size_t)r * cols, buf_->data() + off_ + (size_t)r * step, (size_t)cols); return m; }
+  Mat clone() const { Mat m(rows, cols, cn_); for (int r = 0; r < rows; ++r) std::memcpy(m.buf_->data() + (size_t)r * cols * cn_, buf_->data() + off_ + (size_t)r * step, (size_t)cols * cn_); return m; }
  private:
   std::shared_ptr<std::vector<uint8_t>> buf_;
   size_t off_ = 0;
+  int cn_ = 1;
 };
 typedef const Mat& InputArray;
 typedef Mat& OutputArray;

@@ -1652,6 +1652,95 @@ int osh_orb_extract(osh_orb_ctx* ctx, int32_t n_frames, const osh_extract_frame*
  * ms[2] the quadtree, ms[3] orientation, blur, descriptors, download and write-back. */
 int osh_orb_extract_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- the image front end: rectify or resize, then grey */
+/*
+ * What the reference does to a camera image before ORBextractor::operator() reads it, for n_frames raw images in one call:
+ * cv::remap(im, out, M1, M2, cv::INTER_LINEAR) of System::TrackStereo (src/System.cc:252-269) with the CV_32F maps of
+ * Settings::precomputeRectificationMaps (src/Settings.cc:485-509), the cv::resize(im, out, newImSize) of TrackStereo, TrackRGBD and
+ * TrackMonocular (:263-264, :340, :417), and the cvtColor(.., RGB2GRAY / BGR2GRAY / RGBA2GRAY / BGRA2GRAY) of
+ * Tracking::GrabImageStereo / GrabImageRGBD / GrabImageMonocular (src/Tracking.cc:1462-1489, :1524-1538, :1568-1582).  The result is
+ * the grey level-0 image the extractor reads.  osh_orb_prepare is the stage alone; osh_orb_extract_raw runs it in front of an
+ * osh_orb_extract, so that only the raw image crosses to the device.
+ *
+ * The three steps are DEFINED HERE; OpenCV is not available to compare with, and what follows is its 8-bit path as recalled, not
+ * verified: PARITY WITH OPENCV IS NOT PINNED.  The order is the reference's: geometry first, on every channel, then grey.
+ *   Input: 8-bit, 1, 3 or 4 interleaved channels, read in place through a row stride; channel order OSH_PREP_RGB or OSH_PREP_BGR
+ *   (mbRGB); a fourth channel is ignored.
+ *   Remap (a frame that names a rectify map): the source size is the input's, the output size is the map's.  For destination pixel
+ *   (y, x): mx = map_x[y][x], my = map_y[y][x] in float32.  A coordinate is usable when it is finite and |m| <= 32768; if either is
+ *   unusable the pixel is 0 in every channel.  sx = cvRound(mx * 32.f) (the product is exact; halves go to even), ix = sx >> 5
+ *   (arithmetic shift: floor), fx = sx & 31; sy, iy, fy likewise.  Per channel, with p(r, c) = 0 outside the source, each tap on
+ *   its own:
+ *     out = ((32 - fy) * ((32 - fx) * p(iy, ix) + fx * p(iy, ix + 1)) + fy * ((32 - fx) * p(iy + 1, ix) + fx * p(iy + 1, ix + 1)) + 512) >> 10
+ *   (cv::remap's Q5 coordinate and Q15 weight table with one rounding: for 5-bit fractions the table entries are exactly
+ *   (32 - fx)(32 - fy) * 32 and so on and sum to 32768; BORDER_CONSTANT with value 0).
+ *   Resize (a frame without a map whose output size differs from the input's): per channel exactly the tables, the pixel and the
+ *   exact-halving path of osh_orb_pyramid_build above, from the input size to the output size.  The tables are computed on the host.
+ *   Neither (same size, no map): the channel values pass through.
+ *   Grey: 1 channel: the value itself; 3 or 4 channels: Y = (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14, R and B taken by the
+ *   order flag.
+ * The kernel is integer except the one mx * 32.f and its round-to-nearest-even conversion.
+ *
+ * A rectify map is an object of its own, immutable after creation and resident once on its device: every osh_orb_ctx of that
+ * device, on any thread, may use it at the same time.  It must outlive the calls that use it.  The maps are input data
+ * (stereoRectify and initUndistortRectifyMap stay the integrator's and run once at start-up); their values are not refused:
+ * unusable ones give black pixels.  osh_rectify_map_create refuses, before any device work, with OSH_ERR_INVALID a NULL pointer, a
+ * size that is not positive or a stride under 4 * cols, and with OSH_ERR_UNSUPPORTED either size above OSH_FAST_MAX_SIDE in a
+ * direction.
+ */
+#define OSH_PREP_RGB 0
+#define OSH_PREP_BGR 1
+typedef struct osh_rectify_map_desc {
+  int32_t rows, cols;                /* of the output: the size of both maps                                                */
+  const float* map_x;                /* M1l.ptr<float>(): the source x of every destination pixel                           */
+  int64_t map_x_stride;              /* bytes from one row to the next (M1l.step), >= 4 * cols                              */
+  const float* map_y;                /* M2l.ptr<float>()                                                                    */
+  int64_t map_y_stride;
+  int32_t src_rows, src_cols;        /* the size of the images the map was made for                                         */
+} osh_rectify_map_desc;
+typedef struct osh_rectify_map osh_rectify_map;
+int  osh_rectify_map_create(int device, const osh_rectify_map_desc* desc, osh_rectify_map** out);
+void osh_rectify_map_destroy(osh_rectify_map* map);
+
+typedef struct osh_prepare_image {
+  const uint8_t* data;               /* first byte of the first pixel; read in place                                        */
+  int32_t rows, cols;                /* in pixels                                                                           */
+  int64_t stride;                    /* bytes from one row to the next, >= cols * channels                                  */
+  int32_t channels;                  /* 1, 3 or 4, interleaved                                                              */
+} osh_prepare_image;
+typedef struct osh_prepare_frame {
+  osh_prepare_image image;
+  int32_t order;                     /* OSH_PREP_RGB or OSH_PREP_BGR (mbRGB); checked for every channel count               */
+  const osh_rectify_map* map;        /* or NULL: no remap                                                                   */
+  int32_t out_rows, out_cols;        /* 0, 0: the map's size, else the input's                                              */
+} osh_prepare_frame;
+typedef struct osh_prepare_result {
+  int32_t rows, cols;                /* out: the size of the prepared image                                                 */
+  uint8_t* gray;                     /* where the prepared image is written, or NULL: it stays on the device                */
+  int64_t gray_stride;               /* >= cols of the prepared image                                                       */
+} osh_prepare_result;
+/*
+ * Refused before any device work, without a context, the resident pyramid staying as it was: with OSH_ERR_INVALID a NULL or empty
+ * image; a stride under cols * channels; channels not in {1, 3, 4}; an unknown order; a map whose source size is not the image's;
+ * both a map and an output size that is not the map's; a non-positive output size (one of out_rows / out_cols 0, or negative); a
+ * gray stride under the output's cols; with OSH_ERR_UNSUPPORTED an input or output side above OSH_FAST_MAX_SIDE.  A map of another
+ * device than the context's is refused with OSH_ERR_INVALID as soon as there is a context, before any device work as well.  No
+ * thread reads or writes outside an image for input that passed.
+ */
+int osh_orb_prepare(osh_orb_ctx* ctx, int32_t n_frames, const osh_prepare_frame* frames, osh_prepare_result* results);
+/* An osh_orb_extract whose level 0 is made on the device from the raw image: prepare_frames[k] says how, extract_frames[k].image
+ * must have data == NULL and rows / cols either 0, 0 or the prepared size (anything else is refused with OSH_ERR_INVALID).  The
+ * prepared image is written straight into the level-0 slot of the context's resident pyramid.  Everything else about frames and
+ * results, the overflow convention, the limits, the refusals and the pyramid tokens is osh_orb_extract's, word for word, and every
+ * output equals an osh_orb_extract on the image osh_orb_prepare gives, bit for bit.  prepare_results may be NULL; otherwise
+ * prepare_results[k] is filled as by osh_orb_prepare. */
+int osh_orb_extract_raw(osh_orb_ctx* ctx, int32_t n_frames, const osh_prepare_frame* prepare_frames, const osh_extract_frame* extract_frames,
+                        osh_extract_result* extract_results, osh_prepare_result* prepare_results);
+/* Host-clock phases (ms) of the last osh_orb_prepare under osh_orb_set_profiling: ms[0] validation, tables and staging of the raw
+ * images, ms[1] upload, ms[2] kernels, ms[3] download + the scatter of the rows.  osh_orb_extract_raw fills the times of
+ * osh_orb_extract_get_times instead, the preparation counted into ms[0]. */
+int osh_orb_prepare_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 /* ------------------------------------------------- bag-of-words transform */
 /*
  * TemplatedVocabulary::transform (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1259) for ORB descriptors: what

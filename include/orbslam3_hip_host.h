@@ -751,6 +751,37 @@ typedef struct osh_host_pyramid_output {
 /* Returns the larger of the two keypoint counts.  -1: bad arguments, -2: the member left something inconsistent. */
 int osh_host_orbextractor_compute_pyramid(const osh_host_extract_input* in, const osh_host_pyramid_output* out);
 
+/* ---- the image front end (csrc/orb_prepare.h, csrc/hosttest/prepare.cc) ---- */
+struct osh_prepare_frame;
+struct osh_prepare_result;
+struct osh_rectify_map_desc;
+/* csrc/orb_prepare.h (the statements k_prepare runs) compiled for the host, on one thread: frames and results as osh_orb_prepare
+ * without a context, except that a frame's rectify map is the host descriptor maps[k] (NULL: no map; `maps` itself may be NULL) and
+ * frames[k].map must be NULL: a resident map needs a device.  What osh_orb_prepare and osh_rectify_map_create refuse is refused
+ * here with the same code (OSH_ERR_INVALID / OSH_ERR_UNSUPPORTED) and no message; every result must name a gray image.  *ms (may be
+ * NULL) = wall time of the loops.  -1: bad arguments. */
+int osh_host_orb_prepare_cpu(int32_t n_frames, const struct osh_prepare_frame* frames, const struct osh_rectify_map_desc* const* maps,
+                             struct osh_prepare_result* results, double* ms);
+
+/* ORBextractor::ExtractBatchRaw of n stand-in extractors (made from in[i] as osh_host_orbextractor_extract_batch makes them; the
+ * rows, cols and pixels of in[i] are not read) on the raw images raw[i], each with an ImagePrep of its own and, when it names maps,
+ * a RectifyMap of its own made for the image's size.  Outputs and tokens as osh_host_orbextractor_extract_batch.  gray (may be
+ * NULL): the call passes pvGray, and image i of it is written to gray[i] (rows packed, when gray[i] is not NULL and its
+ * gray_capacity[i] bytes suffice) with its size in gray_rows[i] / gray_cols[i] (0, 0: pvGray[i] came back empty).  Returns 0.
+ * -1: bad arguments. */
+typedef struct osh_host_raw_image {
+  int32_t rows, cols, channels;   /* rows == 0: an empty image */
+  const uint8_t* pixels;          /* rows packed, channels interleaved */
+  int32_t rgb;                    /* ImagePrep::bRGB */
+  int32_t map_rows, map_cols;     /* of map_x / map_y */
+  const float* map_x;             /* rows packed; NULL: ImagePrep::pMap is null */
+  const float* map_y;
+  int32_t new_rows, new_cols;     /* ImagePrep::newRows, newCols */
+} osh_host_raw_image;
+int osh_host_orbextractor_extract_batch_raw(int32_t n, const struct osh_host_extract_input* in, const osh_host_raw_image* raw,
+                                            const struct osh_host_extract_output* out, int32_t keep_pyramid, uint64_t* tokens,
+                                            uint8_t* const* gray, const int32_t* gray_capacity, int32_t* gray_rows, int32_t* gray_cols);
+
 /* ---- ORBVocabulary / ComputeBoW (include/ORBVocabulary.h, csrc/host/ORBVocabulary.cc, csrc/hosttest/bow.cc) ---- */
 struct osh_bow_tree;
 struct osh_bow_result;

@@ -605,6 +605,32 @@ class DescribeResult(C.Structure):
     _fields_ = [("descriptors", c_uint8_p), ("cos_sin", c_float_p), ("blurred", c_uint8_p)]
 
 
+class RectifyMapDesc(C.Structure):
+    """``osh_rectify_map_desc`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("map_x", c_float_p), ("map_x_stride", C.c_int64), ("map_y", c_float_p),
+                ("map_y_stride", C.c_int64), ("src_rows", C.c_int32), ("src_cols", C.c_int32)]
+
+
+class PrepareImage(C.Structure):
+    """``osh_prepare_image`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("data", c_uint8_p), ("rows", C.c_int32), ("cols", C.c_int32), ("stride", C.c_int64), ("channels", C.c_int32)]
+
+
+class PrepareFrame(C.Structure):
+    """``osh_prepare_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("image", PrepareImage), ("order", C.c_int32), ("map", C.c_void_p), ("out_rows", C.c_int32), ("out_cols", C.c_int32)]
+
+
+class PrepareResult(C.Structure):
+    """``osh_prepare_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("gray", c_uint8_p), ("gray_stride", C.c_int64)]
+
+
+OSH_PREP_RGB, OSH_PREP_BGR = 0, 1
 OSH_FAST_MAX_SIDE = 32768
 OSH_FAST_AT_INI, OSH_FAST_AT_MIN, OSH_FAST_EMPTY = 0, 1, 2
 
@@ -746,6 +772,12 @@ _SIGNATURES = {
     "osh_orb_describe_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_extract": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(ExtractFrame), C.POINTER(ExtractResult)]),
     "osh_orb_extract_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_rectify_map_create": (C.c_int, [C.c_int, C.POINTER(RectifyMapDesc), C.POINTER(C.c_void_p)]),
+    "osh_rectify_map_destroy": (None, [C.c_void_p]),
+    "osh_orb_prepare": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(PrepareFrame), C.POINTER(PrepareResult)]),
+    "osh_orb_extract_raw": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(PrepareFrame), C.POINTER(ExtractFrame), C.POINTER(ExtractResult),
+                                      C.POINTER(PrepareResult)]),
+    "osh_orb_prepare_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_bow_tree_check": (C.c_int, [C.POINTER(BowTree)]),
     "osh_bow_vocab_create": (C.c_int, [C.c_int, C.POINTER(BowTree), C.POINTER(C.c_void_p)]),
     "osh_bow_vocab_destroy": (None, [C.c_void_p]),
@@ -853,6 +885,14 @@ class HostExtractOutput(C.Structure):
                 ("call_ms", c_double_p)]
 
 
+class HostRawImage(C.Structure):
+    """``osh_host_raw_image`` (include/orbslam3_hip_host.h)."""
+
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("channels", C.c_int32), ("pixels", c_uint8_p), ("rgb", C.c_int32),
+                ("map_rows", C.c_int32), ("map_cols", C.c_int32), ("map_x", c_float_p), ("map_y", c_float_p), ("new_rows", C.c_int32),
+                ("new_cols", C.c_int32)]
+
+
 class HostPyramidOutput(C.Structure):
     """``osh_host_pyramid_output`` (include/orbslam3_hip_host.h)."""
 
@@ -864,6 +904,8 @@ class HostPyramidOutput(C.Structure):
 
 _HOST_SIGNATURES = {
     "osh_host_orb_pyramid_cpu": (C.c_int, [C.c_int32, C.POINTER(PyramidFrame), C.POINTER(PyramidResult), c_double_p]),
+    "osh_host_orb_prepare_cpu": (C.c_int, [C.c_int32, C.POINTER(PrepareFrame), C.POINTER(C.POINTER(RectifyMapDesc)), C.POINTER(PrepareResult),
+                                           c_double_p]),
     "osh_host_orbextractor_compute_pyramid": (C.c_int, [C.POINTER(HostExtractInput), C.POINTER(HostPyramidOutput)]),
     "osh_host_orb_describe_cpu": (C.c_int, [C.c_int32, C.POINTER(DescribeFrame), C.POINTER(DescribeResult), c_double_p]),
     "osh_host_brief_gaussian_q8": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_uint16)]),
@@ -872,6 +914,9 @@ _HOST_SIGNATURES = {
     "osh_host_orbextractor_extract": (C.c_int, [C.POINTER(HostExtractInput), C.POINTER(HostExtractOutput)]),
     "osh_host_orbextractor_extract_batch": (C.c_int, [C.c_int32, C.POINTER(HostExtractInput), C.POINTER(HostExtractOutput), C.c_int32,
                                                       C.POINTER(C.c_uint64)]),
+    "osh_host_orbextractor_extract_batch_raw": (C.c_int, [C.c_int32, C.POINTER(HostExtractInput), C.POINTER(HostRawImage),
+                                                          C.POINTER(HostExtractOutput), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(c_uint8_p),
+                                                          c_int32_p, c_int32_p, c_int32_p]),
     "osh_host_orb_fast_cpu": (C.c_int, [C.c_int32, C.POINTER(FastFrame), C.POINTER(FastResult), c_double_p]),
     "osh_host_orb_ic_angle_cpu": (C.c_int, [C.c_int32, C.POINTER(IcAngleFrame), C.POINTER(IcAngleResult), c_double_p]),
     "osh_host_orb_fast_level_cells": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),

@@ -36,6 +36,12 @@
 // of include/orbslam3_hip.h (DistributeOctTreeDevice's), not DistributeOctTree.  An empty image gives -1 for that extractor; a device
 // error or a refused call gives a message on stderr and no keypoints for any extractor.
 //
+// ExtractBatchRaw (a member to ADD): ExtractBatch on the camera images as they arrive, as ONE osh_orb_extract_raw call
+// (csrc/orb_prepare_device.hip): per image an ImagePrep (include/RectifyMap.h) says how the grey level-0 image is made on the device
+// (the cv::remap or cv::resize of System::Track* on every channel, then the cvtColor of Tracking::GrabImage*, as
+// include/orbslam3_hip.h defines them; parity with OpenCV is not pinned).  The two share one body, ExtractBatchFrom; the write-back,
+// mvImagePyramid, mnPyramidToken, the -1 of an empty image and the error behaviour are ExtractBatch's.
+//
 // DistributeOctTreeDevice (a member to ADD; :480-779): the arguments and the result of DistributeOctTree, the selection as ONE
 // osh_orb_octree_distribute call (csrc/orb_octree_device.hip) under the rule include/orbslam3_hip.h states.  Nothing calls it here:
 // ComputeKeyPointsOctTree keeps the reference's DistributeOctTree, an integrator opts in.  Its deviations from the reference's list
@@ -58,6 +64,7 @@
 namespace ORB_SLAM3 {
 
 osh_orb_ctx* HostMatcherContext();   // csrc/host/ORBmatcher.cc
+int HostMatcherDevice();
 
 // "ORBextractor::<who>: <what><then>" on stderr; `what` is the reason of the call that was just refused unless the caller has its own
 static void Report(const char* who, const char* what = osh_last_error(), const char* then = "") {
@@ -90,12 +97,12 @@ static std::vector<osh_stereo_image> PyramidViews(const std::vector<cv::Mat>& le
 // :1174-1178 per level: the bordered `temp` is allocated and levels[level] is the view into it, as the reference leaves
 // mvImagePyramid[level]; out[level] is where a call writes that level.  Returns the first level that has no pixels or too many,
 // nlevels when there is none
-static int BorderedLevels(const cv::Mat& image, const std::vector<float>& invScale, int nlevels, std::vector<cv::Mat>& levels,
+static int BorderedLevels(int rows, int cols, const std::vector<float>& invScale, int nlevels, std::vector<cv::Mat>& levels,
                           std::vector<osh_pyramid_image>& out) {
   levels.resize(nlevels); out.resize(nlevels);
   for (int level = 0; level < nlevels; ++level) {
     int h, w;
-    if (!LevelShape(image.rows, image.cols, invScale[level], h, w)) return level;
+    if (!LevelShape(rows, cols, invScale[level], h, w)) return level;
     cv::Mat temp(h + 2 * kEdge, w + 2 * kEdge);
     levels[level] = temp.view(kEdge, kEdge, h, w);
     out[level] = ImageOf<osh_pyramid_image>(levels[level]);
@@ -136,7 +143,7 @@ void ORBextractor::ComputePyramid(cv::Mat image) {
   }
   std::vector<cv::Mat> levels;
   std::vector<osh_pyramid_image> out;
-  const int bad = BorderedLevels(image, mvInvScaleFactor, nlevels, levels, out);
+  const int bad = BorderedLevels(image.rows, image.cols, mvInvScaleFactor, nlevels, levels, out);
   if (bad < nlevels) { std::fprintf(stderr, "ORBextractor::ComputePyramid: level %d has no pixels or too many\n", bad); return; }
   osh_orb_ctx* ctx = Context("ComputePyramid");
   if (!ctx) return;
@@ -261,12 +268,30 @@ std::vector<cv::KeyPoint> ORBextractor::DistributeOctTreeDevice(const std::vecto
 void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
                                 std::vector<std::vector<cv::KeyPoint> >& vKeypoints, std::vector<cv::Mat>& vDescriptors,
                                 const std::vector<std::vector<int> >& vLappingAreas, std::vector<int>& vMonoIndex, bool bKeepPyramid) {
+  ExtractBatchFrom("ExtractBatch", vpExtractors, vImages, nullptr, vKeypoints, vDescriptors, vLappingAreas, vMonoIndex, bKeepPyramid, nullptr);
+}
+
+void ORBextractor::ExtractBatchRaw(const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vRawImages,
+                                   const std::vector<ImagePrep>& vPrep, std::vector<std::vector<cv::KeyPoint> >& vKeypoints,
+                                   std::vector<cv::Mat>& vDescriptors, const std::vector<std::vector<int> >& vLappingAreas,
+                                   std::vector<int>& vMonoIndex, bool bKeepPyramid, std::vector<cv::Mat>* pvGray) {
+  ExtractBatchFrom("ExtractBatchRaw", vpExtractors, vRawImages, &vPrep, vKeypoints, vDescriptors, vLappingAreas, vMonoIndex, bKeepPyramid, pvGray);
+}
+
+// pvPrep null: vImages are grey and go up as they are (osh_orb_extract); else they are raw and level 0 is made on the device
+// (osh_orb_extract_raw)
+void ORBextractor::ExtractBatchFrom(const char* who, const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
+                                    const std::vector<ImagePrep>* pvPrep, std::vector<std::vector<cv::KeyPoint> >& vKeypoints,
+                                    std::vector<cv::Mat>& vDescriptors, const std::vector<std::vector<int> >& vLappingAreas,
+                                    std::vector<int>& vMonoIndex, bool bKeepPyramid, std::vector<cv::Mat>* pvGray) {
   const size_t nExtractors = vpExtractors.size();
   vKeypoints.resize(nExtractors);
   vDescriptors.resize(nExtractors);
   vMonoIndex.assign(nExtractors, 0);
-  if (vImages.size() != nExtractors || vLappingAreas.size() != nExtractors) {
-    std::fprintf(stderr, "ORBextractor::ExtractBatch: %d extractors, %d images, %d lapping areas\n", (int)nExtractors, (int)vImages.size(), (int)vLappingAreas.size());
+  if (pvGray) pvGray->assign(nExtractors, cv::Mat());
+  if (vImages.size() != nExtractors || vLappingAreas.size() != nExtractors || (pvPrep && pvPrep->size() != nExtractors)) {
+    std::fprintf(stderr, "ORBextractor::%s: %d extractors, %d images, %d lapping areas%s\n", who, (int)nExtractors, (int)vImages.size(), (int)vLappingAreas.size(),
+                 pvPrep && pvPrep->size() != nExtractors ? ", another number of ImagePrep" : "");
     return;
   }
   // one frame of the call per extractor with an image; everything a frame points to lives in `job` until the call returns
@@ -275,6 +300,8 @@ void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, 
     std::vector<cv::Mat> levels;
     std::vector<osh_pyramid_image> out;
     std::vector<int8_t> table;
+    int rows, cols;   // of the grey image that is extracted
+    cv::Mat gray;
     std::vector<int32_t> levelCount, level;
     std::vector<float> xy, response, angle, size;
     std::vector<uint8_t> desc;
@@ -291,7 +318,7 @@ void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, 
     const int nl = ex->nlevels;
     if (nl <= 0 || (int)ex->mvInvScaleFactor.size() < nl || (int)ex->mvScaleFactor.size() < nl || (int)ex->mnFeaturesPerLevel.size() < nl ||
         ex->pattern.size() != 512 || vLappingAreas[i].size() < 2) {
-      std::fprintf(stderr, "ORBextractor::ExtractBatch: extractor %d: its level tables, its pattern or its lapping area do not fit\n", (int)i);
+      std::fprintf(stderr, "ORBextractor::%s: extractor %d: its level tables, its pattern or its lapping area do not fit\n", who, (int)i);
       ok = false;
       continue;
     }
@@ -300,26 +327,49 @@ void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, 
     j.extractor = i;
     j.table.resize(1024);
     if (!PatternTable(ex->pattern.data(), j.table.data())) ok = false;
+    j.rows = vImages[i].rows; j.cols = vImages[i].cols;
+    if (pvPrep) {
+      const ImagePrep& prep = (*pvPrep)[i];
+      PreparedShape(vImages[i].rows, vImages[i].cols, prep.pMap ? prep.pMap->rows() : 0, prep.pMap ? prep.pMap->cols() : 0, prep.newRows, prep.newCols, j.rows, j.cols);
+      if (pvGray && j.rows > 0 && j.cols > 0 && j.rows <= OSH_FAST_MAX_SIDE && j.cols <= OSH_FAST_MAX_SIDE) j.gray = cv::Mat(j.rows, j.cols);
+    }
     size_t capacity = 0;   // the quadtree keeps at most max(N + 3, 4 nIni) keypoints of a level, nIni <= OSH_OCTREE_MAX_ROOTS
     for (int l = 0; l < nl; ++l) capacity += (size_t)std::max(std::max(ex->mnFeaturesPerLevel[l], 0) + 3, 4 * OSH_OCTREE_MAX_ROOTS);
     j.levelCount.resize(nl); j.level.resize(capacity); j.xy.resize(capacity * 2); j.response.resize(capacity); j.angle.resize(capacity);
     j.size.resize(capacity); j.desc.resize(capacity * 32);
     if (bKeepPyramid) {   // the levels as ComputePyramid leaves them
-      const int bad = BorderedLevels(vImages[i], ex->mvInvScaleFactor, nl, j.levels, j.out);
-      if (bad < nl) { std::fprintf(stderr, "ORBextractor::ExtractBatch: extractor %d: level %d has no pixels or too many\n", (int)i, bad); ok = false; }
+      const int bad = BorderedLevels(j.rows, j.cols, ex->mvInvScaleFactor, nl, j.levels, j.out);
+      if (bad < nl) { std::fprintf(stderr, "ORBextractor::%s: extractor %d: level %d has no pixels or too many\n", who, (int)i, bad); ok = false; }
     }
   }
-  if (!ok) std::fprintf(stderr, "ORBextractor::ExtractBatch: nothing extracted\n");
+  if (!ok) std::fprintf(stderr, "ORBextractor::%s: nothing extracted\n", who);
   if (!ok || jobs.empty()) return;
-  osh_orb_ctx* ctx = Context("ExtractBatch");
+  osh_orb_ctx* ctx = Context(who);
   if (!ctx) return;
   std::vector<osh_extract_frame> frames(jobs.size());
   std::vector<osh_extract_result> results(jobs.size());
+  std::vector<osh_prepare_frame> rawFrames(pvPrep ? jobs.size() : 0);
+  std::vector<osh_prepare_result> rawResults(pvPrep ? jobs.size() : 0);
   for (size_t k = 0; k < jobs.size(); ++k) {
     Job& j = jobs[k];
     const ORBextractor* ex = vpExtractors[j.extractor];
     osh_extract_frame& f = frames[k];
-    f.image = ImageOf<osh_stereo_image>(vImages[j.extractor]);
+    if (pvPrep) {   // the raw image goes up; the frame of the extraction names the prepared size and brings no pixels
+      const ImagePrep& prep = (*pvPrep)[j.extractor];
+      const cv::Mat& raw = vImages[j.extractor];
+      osh_prepare_frame& p = rawFrames[k];
+      p = osh_prepare_frame{};
+      p.image.data = raw.ptr<uint8_t>(0); p.image.rows = raw.rows; p.image.cols = raw.cols; p.image.stride = (int64_t)(size_t)raw.step;
+      p.image.channels = raw.channels();
+      p.order = prep.bRGB ? OSH_PREP_RGB : OSH_PREP_BGR;
+      p.out_rows = prep.newRows; p.out_cols = prep.newCols;
+      if (prep.pMap && !(p.map = prep.pMap->OnDevice(HostMatcherDevice()))) return Report(who);
+      rawResults[k] = osh_prepare_result{};
+      if (!j.gray.empty()) { rawResults[k].gray = j.gray.ptr<uint8_t>(0); rawResults[k].gray_stride = (int64_t)(size_t)j.gray.step; }
+      f.image = osh_stereo_image{nullptr, j.rows, j.cols, (int64_t)j.cols};
+    } else {
+      f.image = ImageOf<osh_stereo_image>(vImages[j.extractor]);
+    }
     f.n_levels = ex->nlevels; f.inv_scale = ex->mvInvScaleFactor.data(); f.scale = ex->mvScaleFactor.data();
     f.ini_th = ex->iniThFAST; f.min_th = ex->minThFAST; f.n_features = ex->mnFeaturesPerLevel.data();
     f.pattern = j.table.data(); f.blur_q8 = nullptr;
@@ -329,12 +379,15 @@ void ORBextractor::ExtractBatch(const std::vector<ORBextractor*>& vpExtractors, 
     r.response = j.response.data(); r.angle = j.angle.data(); r.size = j.size.data(); r.descriptors = j.desc.data();
     r.levels = bKeepPyramid ? j.out.data() : nullptr; r.border = kEdge;
   }
-  if (osh_orb_extract(ctx, (int32_t)jobs.size(), frames.data(), results.data()) != OSH_OK) return Report("ExtractBatch");
+  const int rc = pvPrep ? osh_orb_extract_raw(ctx, (int32_t)jobs.size(), rawFrames.data(), frames.data(), results.data(), rawResults.data())
+                        : osh_orb_extract(ctx, (int32_t)jobs.size(), frames.data(), results.data());
+  if (rc != OSH_OK) return Report(who);
   for (size_t k = 0; k < jobs.size(); ++k) {
     const Job& j = jobs[k];
     ORBextractor* ex = vpExtractors[j.extractor];
     const osh_extract_result& r = results[k];
-    if (r.n_out > r.capacity) { std::fprintf(stderr, "ORBextractor::ExtractBatch: extractor %d: %d keypoints for %d places\n", (int)j.extractor, r.n_out, r.capacity); continue; }
+    if (pvGray) (*pvGray)[j.extractor] = j.gray;
+    if (r.n_out > r.capacity) { std::fprintf(stderr, "ORBextractor::%s: extractor %d: %d keypoints for %d places\n", who, (int)j.extractor, r.n_out, r.capacity); continue; }
     if (bKeepPyramid) ex->mvImagePyramid = j.levels;
     ex->mnPyramidToken = r.pyramid_token;
     const int nkeypoints = r.n_out;

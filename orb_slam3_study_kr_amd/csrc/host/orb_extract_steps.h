@@ -21,6 +21,14 @@ inline bool LevelShape(int rows, int cols, float invScale, int& h, int& w) {
   return w > 0 && h > 0;
 }
 
+// rows x cols of the grey image ExtractBatchRaw extracts from, as osh_orb_prepare sizes it: the size asked for (newImSize) when there
+// is one, else the rectification map's when there is a map (mapRows > 0), else the raw image's
+inline void PreparedShape(int rawRows, int rawCols, int mapRows, int mapCols, int newRows, int newCols, int& h, int& w) {
+  if (newRows != 0 || newCols != 0) { h = newRows; w = newCols; }
+  else if (mapRows > 0) { h = mapRows; w = mapCols; }
+  else { h = rawRows; w = rawCols; }
+}
+
 // The 512 points of `pattern` as the int8 table [1024] of osh_orb_describe and osh_orb_extract, x and y interleaved.  False: a
 // coordinate does not fit 8 bits (the table is filled all the same)
 template <class Point>

@@ -7,6 +7,7 @@
 #pragma once
 #include "common.h"
 #include "orb_pyramid_set.h"
+#include <functional>
 #include <vector>
 
 namespace osh {
@@ -23,6 +24,22 @@ struct FastEmitted {
 // The detector over frames of the resident pyramid (tokens as osh_orb_fast_detect_resident), nothing downloaded but the cell offsets
 int fast_emit_resident(const char* entry, osh_orb_ctx* c, hipStream_t s, int n_frames, const osh_fast_resident_frame* frames, FastEmitted& e);
 int ic_angle_launch(hipStream_t s, int n, const PyramidLevelDev* levels, const int* level_index, const float2* xy, float* angle, int* m10, int* m01);
+
+// ---- orb_pyramid_device.hip
+// Where the level 0 of every frame of a build comes from when it is not a host image: a device producer (orb_prepare_device.hip)
+struct Level0Producer {
+  // the refusals that need the context's device; called before the resident pyramid is touched
+  std::function<int(int device)> check;
+  // on the stream, before k_pyr_level: level 0 of frame k (rows packed at `cols` bytes) to images + level0_off[k]
+  std::function<int(hipStream_t s, unsigned char* images, const std::vector<long long>& level0_off)> produce;
+};
+// osh_orb_pyramid_build with level 0 from the host images (producer == nullptr) or from a device producer (frames[k].image then
+// carries the size and no data).  Refusals, tokens and outputs are osh_orb_pyramid_build's.
+int pyramid_build_from(osh_orb_ctx* c, int32_t n_frames, const osh_pyramid_frame* frames, osh_pyramid_result* results, const Level0Producer* producer);
+
+// ---- orb_extract_device.hip
+// osh_orb_extract with the pyramid built by pyramid_build_from(.., producer)
+int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results, const Level0Producer* producer);
 
 // ---- orb_octree_device.hip
 struct OctListDev {

@@ -9,6 +9,7 @@
 //   k_extract_gather               one wavefront per list: the kept candidates in level-then-list order with minBorder added (:880-890);
 //   ic_angle_launch, brief_launch  k_ic_angle, k_orb_blur on the levels that hold a keypoint, k_orb_brief, all reading the gathered keypoints.
 // Uploads besides the image: the plans of the stages (cells, lists, levels, tiles, tables).  One download at the end.
+// extract_from (orb_extract.h) is the body; osh_orb_extract_raw (orb_prepare_device.hip) calls it with a device producer of level 0.
 #include "common.h"
 #include "orb_brief.h"
 #include "orb_extract.h"
@@ -66,13 +67,9 @@ static int extract_validate(int k, const osh_extract_frame& f, const osh_extract
   return OSH_OK;
 }
 
-}  // namespace osh
-
-using namespace osh;
-
-extern "C" int osh_orb_extract(osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results) {
+// The body of osh_orb_extract and osh_orb_extract_raw (orb_prepare_device.hip): they differ in where level 0 comes from
+int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results, const Level0Producer* producer) {
   PhaseClock clock;
-  const char* entry = "osh_orb_extract";
   if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("%s: bad arguments", entry); return OSH_ERR_INVALID; }
   for (int k = 0; k < n_frames; ++k) OSH_TRY(extract_validate(k, frames[k], results[k]));   // a refusal needs no context and no device
   // the pyramid: exactly an osh_orb_pyramid_build, which refuses what it refuses before it touches the resident pyramid
@@ -82,7 +79,7 @@ extern "C" int osh_orb_extract(osh_orb_ctx* c, int32_t n_frames, const osh_extra
     pf[k] = {frames[k].image, frames[k].n_levels, frames[k].inv_scale};
     pr[k] = {0, nullptr, nullptr, results[k].levels, results[k].border};
   }
-  OSH_TRY(osh_orb_pyramid_build(c, n_frames, pf.data(), pr.data()));
+  OSH_TRY(pyramid_build_from(c, n_frames, pf.data(), pr.data(), producer));
   if (n_frames == 0) return OSH_OK;
   int device = 0;
   hipStream_t s = nullptr;
@@ -196,6 +193,14 @@ extern "C" int osh_orb_extract(osh_orb_ctx* c, int32_t n_frames, const osh_extra
   clock.mark();
   clock.store(st->ms);
   return OSH_OK;
+}
+
+}  // namespace osh
+
+using namespace osh;
+
+extern "C" int osh_orb_extract(osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results) {
+  return extract_from("osh_orb_extract", c, n_frames, frames, results, nullptr);
 }
 
 extern "C" int osh_orb_extract_get_times(osh_orb_ctx* c, double ms[4]) {

@@ -14,7 +14,10 @@
 //   k_pyr_border   only when a frame asks for its levels: every level with `border` pixels around it by reflect-101 into an arena
 //                  of its own (rows padded to dwords), one D2H copy, and the rows scattered into the caller's images.
 // Level l waits for level l - 1 through the order of the stream: ordinary launches, no barrier across blocks.
+// pyramid_build_from (orb_extract.h) is the body: osh_orb_pyramid_build and osh_orb_extract call it with the upload above, and
+// osh_orb_extract_raw (orb_prepare_device.hip) with a device producer that writes level 0 on the stream before k_pyr_level.
 #include "common.h"
+#include "orb_extract.h"
 #include "orb_pyramid_set.h"
 #include "orb_pyramid.h"
 #include "orb_stage.h"
@@ -103,9 +106,12 @@ __global__ __launch_bounds__(kPyrBorderBlock) void k_pyr_border(PyrView v) {
 
 struct PyrFrameHost { int rows[OSH_STEREO_MAX_LEVELS], cols[OSH_STEREO_MAX_LEVELS]; };
 
-static int pyramid_validate(int k, const osh_pyramid_frame& f, const osh_pyramid_result& r, PyrFrameHost& sz) {
+// device_level0: the image brings no data (a device producer makes level 0), its size is checked all the same
+static int pyramid_validate(int k, const osh_pyramid_frame& f, const osh_pyramid_result& r, PyrFrameHost& sz, bool device_level0) {
   const char* entry = "osh_orb_pyramid_build";
-  OSH_TRY(fast_validate_pyramid(entry, k, 1, &f.image));
+  osh_stereo_image im = f.image;
+  if (device_level0) { im.data = reinterpret_cast<const uint8_t*>(&im); im.stride = im.cols; }   // not read: only NULL is refused
+  OSH_TRY(fast_validate_pyramid(entry, k, 1, &im));
   if (f.n_levels < 1 || f.n_levels > OSH_STEREO_MAX_LEVELS) { set_error("%s: frame %d: n_levels %d outside [1, %d]", entry, k, f.n_levels, OSH_STEREO_MAX_LEVELS); return OSH_ERR_INVALID; }
   if (!f.inv_scale) { set_error("%s: frame %d: NULL inv_scale", entry, k); return OSH_ERR_INVALID; }
   if (r.border < 0) { set_error("%s: frame %d: negative border", entry, k); return OSH_ERR_INVALID; }
@@ -126,16 +132,15 @@ static int pyramid_validate(int k, const osh_pyramid_frame& f, const osh_pyramid
   return OSH_OK;
 }
 
-}  // namespace osh
-
-using namespace osh;
-
-extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh_pyramid_frame* frames, osh_pyramid_result* results) {
+// The body of osh_orb_pyramid_build: the sizing, the tables, the jobs, the launch of the upper levels, the bordered download and the
+// commit.  Level 0 comes from the host images (producer == nullptr: packed and uploaded) or from a device producer that runs on the
+// stream before k_pyr_level (orb_extract.h).
+int pyramid_build_from(osh_orb_ctx* c, int32_t n_frames, const osh_pyramid_frame* frames, osh_pyramid_result* results, const Level0Producer* producer) {
   PhaseClock clock;
   const char* entry = "osh_orb_pyramid_build";
   if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("%s: bad arguments", entry); return OSH_ERR_INVALID; }
   std::vector<PyrFrameHost> sz((size_t)n_frames);
-  for (int k = 0; k < n_frames; ++k) OSH_TRY(pyramid_validate(k, frames[k], results[k], sz[k]));   // a refusal needs no context and no device
+  for (int k = 0; k < n_frames; ++k) OSH_TRY(pyramid_validate(k, frames[k], results[k], sz[k], producer != nullptr));   // a refusal needs no context and no device
   if (!c) { set_error("%s: no context", entry); return OSH_ERR_INVALID; }
   if (n_frames == 0) return OSH_OK;
   if (n_frames > 65535) { set_error("%s: more than 65535 frames in one call", entry); return OSH_ERR_UNSUPPORTED; }
@@ -213,6 +218,7 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
   int device = 0;
   hipStream_t s = nullptr;
   OSH_TRY(orb_stream(c, &device, &s));
+  if (producer) OSH_TRY(producer->check(device));   // its refusals that need the context's device: the resident pyramid stays
   FastState* st = orb_state<FastState>(c, kOrbAttachFast);
   clock.profiling = orb_profiling(c);
   st->pyramid.invalidate();   // the resident pyramid is about to be replaced
@@ -224,8 +230,8 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
   out.take<int>(1);   // nothing comes back through this staging; an empty region has no pinned buffer
   OSH_TRY(st->pyr_call.reserve(in, out));
   OSH_TRY(st->pyramid.buffer.reserve(bytes));
-  unsigned char* hi = static_cast<unsigned char*>(st->pyramid.h_images.reserve(img0_bytes));
-  if (!hi) { set_error("%s: pinned allocation of %zu bytes failed", entry, img0_bytes); return OSH_ERR_DEVICE; }
+  unsigned char* hi = producer ? nullptr : static_cast<unsigned char*>(st->pyramid.h_images.reserve(img0_bytes));
+  if (!producer && !hi) { set_error("%s: pinned allocation of %zu bytes failed", entry, img0_bytes); return OSH_ERR_DEVICE; }
   if (bordered_bytes) {
     OSH_TRY(st->bordered.reserve(bordered_bytes));
     if (!st->h_bordered.reserve(bordered_bytes)) { set_error("%s: pinned allocation of %zu bytes failed", entry, bordered_bytes); return OSH_ERR_DEVICE; }
@@ -234,10 +240,16 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
   if (!jobs.empty()) std::memcpy(s_jobs.in(h), jobs.data(), sizeof(PyrJobDev) * jobs.size());
   if (!bjobs.empty()) std::memcpy(s_bjobs.in(h), bjobs.data(), sizeof(PyrBorderJobDev) * bjobs.size());
   if (!taps.empty()) std::memcpy(s_taps.in(h), taps.data(), sizeof(PyrTap) * taps.size());
-  for (int k = 0; k < n_frames; ++k) pack_level(hi + lh[fh[k].level0].img_off, frames[k].image);
+  for (int k = 0; !producer && k < n_frames; ++k) pack_level(hi + lh[fh[k].level0].img_off, frames[k].image);
   clock.mark();
   OSH_TRY(st->pyr_call.upload(s));
-  OSH_HIP(hipMemcpyAsync(st->pyramid.buffer.p, hi, img0_bytes, hipMemcpyHostToDevice, s));
+  if (producer) {
+    std::vector<long long> level0_off((size_t)n_frames);
+    for (int k = 0; k < n_frames; ++k) level0_off[k] = lh[fh[k].level0].img_off;
+    OSH_TRY(producer->produce(s, st->pyramid.buffer.as<unsigned char>(), level0_off));
+  } else {
+    OSH_HIP(hipMemcpyAsync(st->pyramid.buffer.p, hi, img0_bytes, hipMemcpyHostToDevice, s));
+  }
   OSH_TRY(clock.mark_synced(s));
 
   PyrView v{};
@@ -274,6 +286,14 @@ extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh
   clock.mark();
   clock.store(st->ms_pyr);
   return OSH_OK;
+}
+
+}  // namespace osh
+
+using namespace osh;
+
+extern "C" int osh_orb_pyramid_build(osh_orb_ctx* c, int32_t n_frames, const osh_pyramid_frame* frames, osh_pyramid_result* results) {
+  return pyramid_build_from(c, n_frames, frames, results, nullptr);
 }
 
 extern "C" int osh_orb_pyramid_get_times(osh_orb_ctx* c, double ms[4]) {

@@ -9,6 +9,7 @@
 // osh_orb_fast_detect / osh_orb_ic_angle (orb_fast_device.hip) and osh_orb_describe (orb_brief_device.hip) have pyramids, brought
 // along or resident on the context: orb_pyramid_set.h, built on pack_level, is their level list; they use scatter, PhaseClock,
 // orb_state and copy_times.  osh_orb_pyramid_build (orb_pyramid_device.hip) fills the resident pyramid: pack_level, PhaseClock, orb_state.
+// osh_orb_prepare / osh_orb_extract_raw (orb_prepare_device.hip) have raw images and resident rectify maps: PhaseClock, orb_state, copy_times.
 // osh_orb_refresh_map_points (mappoint_device.hip) has batches of map points: it uses scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_two_view_reconstruct (two_view_device.hip), osh_orb_mlpnp_solve (mlpnp_device.hip) and osh_orb_sim3_ransac
 // (sim3_ransac_device.hip) have problems of correspondences and minimal sets: ransac_stage.h is their validator, batch bookkeeping and

@@ -1637,3 +1637,72 @@ def orbextractor_extract_batch(images, lappings, nfeatures=1000, scale_factor=1.
         d["pyramid"] = orb.cut_levels(o["pyramid"], zip(o["level_rows"].tolist(), o["level_cols"].tolist()))
         res.append(d)
     return res
+
+
+def orbextractor_extract_batch_raw(items, lappings, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, keep_pyramid=True,
+                                   want_gray=True) -> list:
+    """ORBextractor::ExtractBatchRaw of one stand-in extractor per item dict(image uint8 [rows, cols] or [rows, cols, 3 | 4] (None: an
+    empty image), optionally order ("rgb" / "bgr"), map_x / map_y (float32 [rows, cols]: a RectifyMap of its own), out_shape), through
+    osh_host_orbextractor_extract_batch_raw: per item the dict of orbextractor_extract_batch and, with want_gray, gray (the image of
+    *pvGray; None when it came back empty)."""
+    from . import orb
+    lib = capi.load_host_library()
+    n = len(items)
+    cin = (capi.HostExtractInput * max(n, 1))()
+    raw = (capi.HostRawImage * max(n, 1))()
+    keep, shapes = [], []
+    for i, it in enumerate(items):
+        orb.fill_host_extract_input(cin[i], None, nfeatures, scale_factor, nlevels, ini_th, min_th, lappings[i])
+        img = None if it.get("image") is None else np.ascontiguousarray(it["image"], np.uint8)
+        r = raw[i]
+        r.rgb = int(it.get("order", "rgb") == "rgb")
+        shape = (0, 0)
+        if img is not None and img.size:
+            r.rows, r.cols, r.channels = img.shape[0], img.shape[1], 1 if img.ndim == 2 else img.shape[2]
+            r.pixels = capi.ptr(img, capi.c_uint8_p)
+            shape = img.shape[:2]
+        else:
+            r.channels = 1
+        if it.get("map_x") is not None:
+            mx, my = np.ascontiguousarray(it["map_x"], np.float32), np.ascontiguousarray(it["map_y"], np.float32)
+            r.map_rows, r.map_cols = mx.shape
+            r.map_x, r.map_y = capi.ptr(mx, capi.c_float_p), capi.ptr(my, capi.c_float_p)
+            keep.append((mx, my))
+            shape = mx.shape
+        if it.get("out_shape") is not None:
+            r.new_rows, r.new_cols = int(it["out_shape"][0]), int(it["out_shape"][1])
+            shape = (max(r.new_rows, 0), max(r.new_cols, 0))
+        keep.append(img)
+        shapes.append(shape)
+    cap = [2 * int(nfeatures) + 300 * int(nlevels)] * n
+    pix = [int((s[0] + 2) * (s[1] + 2) * nlevels) if s[0] * s[1] else 1 for s in shapes]
+    outs, cout = [], (capi.HostExtractOutput * max(n, 1))()
+    for i in range(n):
+        o = dict(level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), pyramid=np.zeros(pix[i], np.uint8),
+                 xy=np.zeros((cap[i], 2), np.float32), angle=np.zeros(cap[i], np.float32), size=np.zeros(cap[i], np.float32),
+                 response=np.zeros(cap[i], np.float32), octave=np.zeros(cap[i], np.int32), descriptors=np.zeros((cap[i], 32), np.uint8),
+                 ret=np.zeros(1, np.int32), desc_rows=np.zeros(1, np.int32), pixels_needed=np.zeros(1, np.int32), call_ms=np.zeros(1, np.float64))
+        cout[i].capacity, cout[i].pixel_capacity = cap[i], pix[i]
+        orb._wire_outputs(cout[i], o)
+        outs.append(o)
+    tokens = (C.c_uint64 * max(n, 1))()
+    grays = [np.full(max(s[0] * s[1], 1), 167, np.uint8) for s in shapes]
+    gptr = (capi.c_uint8_p * max(n, 1))(*[capi.ptr(g, capi.c_uint8_p) for g in grays])
+    gcap = np.asarray([g.size for g in grays] or [0], np.int32)
+    grows, gcols = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), -1, np.int32)
+    rc = lib.osh_host_orbextractor_extract_batch_raw(n, cin, raw, cout, int(bool(keep_pyramid)), tokens, gptr if want_gray else None,
+                                                     capi.ptr(gcap, capi.c_int32_p), capi.ptr(grows, capi.c_int32_p), capi.ptr(gcols, capi.c_int32_p))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_orbextractor_extract_batch_raw returned {rc}")
+    res = []
+    for i, o in enumerate(outs):
+        k = int(o["desc_rows"][0])
+        d = dict(ret=int(o["ret"][0]), desc_rows=k, token=int(tokens[i]), call_ms=float(o["call_ms"][0]))
+        for name in ("xy", "angle", "size", "response", "octave", "descriptors"):
+            d[name] = o[name][:k]
+        d["pyramid"] = orb.cut_levels(o["pyramid"], zip(o["level_rows"].tolist(), o["level_cols"].tolist()))
+        if want_gray:
+            gr, gc = int(grows[i]), int(gcols[i])
+            d["gray"] = grays[i][:gr * gc].reshape(gr, gc) if gr > 0 and gr * gc <= grays[i].size else None
+        res.append(d)
+    return res

@@ -17,6 +17,7 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_create(device, C.byref(self.ctx)), "osh_orb_create", self.lib)
         self._shape = None
         self._keep = None
+        self.device = device
 
     def close(self):
         if self.ctx:
@@ -352,7 +353,36 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_extract(self.ctx, len(items), cf, cr), "osh_orb_extract", self.lib)
         return _extract_outputs(cr, outs)
 
-    extract_times = functools.partialmethod(_times, "osh_orb_extract_get_times")                 # of the last extract
+    extract_times = functools.partialmethod(_times, "osh_orb_extract_get_times")                 # of the last extract or extract_raw
+
+    def rectify_map(self, map_x, map_y, src_shape) -> "RectifyMap":
+        """A rectify map (osh_rectify_map) resident on this matcher's device from the float32 maps [rows, cols] (rows may be strided)
+        and the (rows, cols) of the images it was made for; the caller closes it."""
+        return RectifyMap(map_x, map_y, src_shape, self.device)
+
+    def prepare(self, items, download: bool = True) -> list:
+        """The image front end (remap or resize, then grey) for a batch of items dict(image uint8 [rows, cols] or [rows, cols, 3 | 4]
+        (rows may be strided), optionally order ("rgb" / "bgr"), map (a RectifyMap), out_shape (rows, cols)) in one osh_orb_prepare
+        call: per item a dict with shape and, with `download`, gray (a view into `gray_whole`, whose rows are longer)."""
+        cf, cr, _maps, _keep, outs = prepare_args(items, download)
+        capi.check(self.lib.osh_orb_prepare(self.ctx, len(items), cf, cr), "osh_orb_prepare", self.lib)
+        return _prepare_outputs(cr, outs)
+
+    prepare_times = functools.partialmethod(_times, "osh_orb_prepare_get_times")                 # of the last prepare
+
+    def extract_raw(self, items, capacities=None, download: bool = False, gray: bool = False) -> list:
+        """extract() on raw images in ONE osh_orb_extract_raw call: items carry the keys of prepare() and of extract() (image being
+        the raw one).  Per item the dict of extract(), and with `gray` also gray and shape as prepare() gives them."""
+        if capacities is None:
+            capacities = [r["n_out"] for r in self.extract_raw(items, [0] * len(items))]
+        pf, pr, _maps, _pkeep, pouts = prepare_args(items, gray)
+        cf, cr, _keep, outs = extract_raw_args(items, capacities, download)
+        capi.check(self.lib.osh_orb_extract_raw(self.ctx, len(items), pf, cf, cr, pr if gray else None), "osh_orb_extract_raw", self.lib)
+        res = _extract_outputs(cr, outs)
+        if gray:
+            for d, p in zip(res, _prepare_outputs(pr, pouts)):
+                d.update(p)
+        return res
 
     def kb8_triangulate(self, rig: "capi.Kb8Rig", xy1, xy2, sigma1, sigma2) -> dict:
         """KannalaBrandt8::TriangulateMatches for explicit keypoint pairs (osh_kb8_triangulate): ret [n], p3d [n, 3], cos_parallax [n]."""
@@ -391,6 +421,45 @@ class BowVocab:
     def close(self):
         if self.handle:
             self.lib.osh_bow_vocab_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class RectifyMap:
+    """The float32 maps of a camera and the source size they were made for; with a device, resident there as an osh_rectify_map and
+    shared by every OrbMatcher of the device.  device None: the description alone, for prepare_cpu."""
+
+    def __init__(self, map_x, map_y, src_shape, device: int | None = None):
+        self.map_x, self.map_y = np.asarray(map_x), np.asarray(map_y)
+        for m in (self.map_x, self.map_y):
+            assert m.dtype == np.float32 and m.ndim == 2 and m.shape == self.map_x.shape and (m.shape[1] == 1 or m.strides[1] == 4)
+        self.src_shape = (int(src_shape[0]), int(src_shape[1]))
+        self.shape = tuple(self.map_x.shape)
+        self.handle = C.c_void_p()
+        self.lib = None
+        if device is not None:
+            self.lib = capi.load_library()
+            d = self.desc()
+            capi.check(self.lib.osh_rectify_map_create(device, C.byref(d), C.byref(self.handle)), "osh_rectify_map_create", self.lib)
+
+    def desc(self) -> "capi.RectifyMapDesc":
+        """The osh_rectify_map_desc; it points into this object's arrays."""
+        d = capi.RectifyMapDesc()
+        d.rows, d.cols = self.shape
+        d.src_rows, d.src_cols = self.src_shape
+        d.map_x, d.map_y = C.cast(self.map_x.ctypes.data, capi.c_float_p), C.cast(self.map_y.ctypes.data, capi.c_float_p)
+        d.map_x_stride = self.map_x.strides[0] if self.shape[0] > 1 else max(self.map_x.strides[0], 4 * self.shape[1])
+        d.map_y_stride = self.map_y.strides[0] if self.shape[0] > 1 else max(self.map_y.strides[0], 4 * self.shape[1])
+        return d
+
+    def close(self):
+        if self.handle:
+            self.lib.osh_rectify_map_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __enter__(self):
@@ -765,6 +834,81 @@ def _extract_outputs(cr, outs):
         d.update({name: o[name] for name in ("levels", "bordered") if name in o})
         res.append(d)
     return res
+
+
+def prepared_shape(it) -> tuple:
+    """(rows, cols) of the image a prepare item gives: the map's size, else out_shape, else the input's."""
+    if it.get("map") is not None:
+        return tuple(it["map"].shape)
+    if it.get("out_shape") is not None:
+        return (int(it["out_shape"][0]), int(it["out_shape"][1]))
+    return tuple(it["image"].shape[:2])
+
+
+def prepare_args(items, download: bool = True):
+    """The osh_prepare_frame / osh_prepare_result arrays of OrbMatcher.prepare: (frames, results, the host descriptors of the maps
+    for prepare_cpu, keep-alive, per-item dicts of outputs).  The image is read in place: a view with strided rows stays one.  With
+    `download` every result names a view into an image of 167 whose rows are 5 bytes longer."""
+    n = len(items)
+    cf = (capi.PrepareFrame * max(n, 1))()
+    cr = (capi.PrepareResult * max(n, 1))()
+    maps = (C.POINTER(capi.RectifyMapDesc) * max(n, 1))()
+    keep, outs = [], []
+    for k, it in enumerate(items):
+        img = it["image"]
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        assert img.dtype == np.uint8 and img.ndim in (2, 3) and (img.ndim == 2 or img.strides[2] == 1) and (img.shape[1] == 1 or img.strides[1] == ch)
+        f = cf[k]
+        f.image.data = C.cast(img.ctypes.data, capi.c_uint8_p)
+        f.image.rows, f.image.cols, f.image.channels = img.shape[0], img.shape[1], ch
+        f.image.stride = img.strides[0] if img.shape[0] > 1 else max(img.strides[0], img.shape[1] * ch)
+        order = it.get("order", "rgb")
+        f.order = {"rgb": capi.OSH_PREP_RGB, "bgr": capi.OSH_PREP_BGR}.get(order, order)
+        a = dict(img=img)
+        m = it.get("map")
+        if m is not None:
+            f.map = m.handle.value
+            a["desc"] = m.desc()
+            maps[k] = C.pointer(a["desc"])
+        if it.get("out_shape") is not None:
+            f.out_rows, f.out_cols = int(it["out_shape"][0]), int(it["out_shape"][1])
+        o = {}
+        if download:
+            rows, cols = prepared_shape(it)
+            o["gray_whole"] = np.full((max(rows, 0), max(cols, 0) + 5), 167, np.uint8)
+            o["gray"] = o["gray_whole"][:, :max(cols, 0)]
+            cr[k].gray, cr[k].gray_stride = C.cast(o["gray_whole"].ctypes.data, capi.c_uint8_p), o["gray_whole"].shape[1]
+        keep.append(a)
+        outs.append(o)
+    return cf, cr, maps, keep, outs
+
+
+def _prepare_outputs(cr, outs):
+    return [dict(o, shape=(int(cr[k].rows), int(cr[k].cols))) for k, o in enumerate(outs)]
+
+
+def prepare_cpu(items, host_lib=None):
+    """csrc/orb_prepare.h on the host in one thread (osh_host_orb_prepare_cpu of the test library): the per-item dicts of
+    OrbMatcher.prepare and the wall time of the loops in ms.  A map may be a RectifyMap without a device."""
+    host_lib = host_lib or capi.load_host_library()
+    ms = C.c_double(0)
+    cf, cr, maps, _keep, outs = prepare_args(items, True)
+    for k in range(len(items)):
+        cf[k].map = None   # the host build reads the descriptor
+    rc = host_lib.osh_host_orb_prepare_cpu(len(items), cf, maps, cr, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_orb_prepare_cpu -> {rc}")
+    return _prepare_outputs(cr, outs), float(ms.value)
+
+
+def extract_raw_args(items, capacities, download: bool = False):
+    """The osh_extract_frame / osh_extract_result arrays of OrbMatcher.extract_raw: those of extract_args for an image of the
+    prepared size that brings no data."""
+    sized = [dict(it, image=np.empty(prepared_shape(it), np.uint8)) for it in items]
+    cf, cr, keep, outs = extract_args(sized, capacities, download)
+    for k in range(len(items)):
+        cf[k].image.data = C.cast(None, capi.c_uint8_p)
+    return cf, cr, keep, outs
 
 
 def pyramid_cpu(items, download: bool = True, host_lib=None):
