@@ -572,8 +572,14 @@ int osh_pgo4_linearize(osh_lba_ctx* ctx, const osh_pgo4_problem* problem, double
  * Levenberg-Marquardt with a dense 7x7 solve.  Round 1 is optimize(5); a pair is an outlier when either edge's chi2 (the
  * unrobustified e^T Omega e of the last trial, as double against the float th2) exceeds th2.  With at least 10 inliers left,
  * round 2 runs optimize(n_bad > 0 ? 10 : 5) over the inliers without robust kernels, and the final estimate re-classifies them.
+ * The three budgets are inputs (iterations[3], as osh_pose_problem.iterations): OptimizeSim3 passes {5, 10, 5}.  A budget of 0 runs
+ * no iteration of that round (iterations 0, chi2_end 0, the estimate and every chi2 of the round before unchanged; the
+ * classification that follows the round still runs), so budgets (0, 0, 0) classify the pairs by their chi2 at the input S12 in the
+ * final classification, and (k, 0, 0) show the state after k robust iterations.  A negative budget or one above
+ * OSH_SIM3_MAX_ITERATIONS is OSH_ERR_INVALID before any device work.
  * One problem per block on the device; `n` problems per call.  Sim3 layout: qx qy qz qw tx ty tz s.
  */
+#define OSH_SIM3_MAX_ITERATIONS 100
 typedef struct osh_sim3_problem {
   int32_t n_pairs;
   double S12[8];              /* initial g2oS12 */
@@ -588,6 +594,7 @@ typedef struct osh_sim3_problem {
   const double* obs2;         /* [n_pairs*2] measurement of e21 */
   const double* info1;        /* [n_pairs] information of e12 (times the 2x2 identity) */
   const double* info2;        /* [n_pairs] information of e21 */
+  int32_t iterations[3];      /* optimize(N) budgets: round 1, round 2 when n_bad > 0, round 2 otherwise; OptimizeSim3 is {5, 10, 5} */
 } osh_sim3_problem;
 
 typedef struct osh_sim3_result {

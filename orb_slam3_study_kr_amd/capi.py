@@ -136,7 +136,7 @@ class Sim3Problem(C.Structure):
         ("n_pairs", C.c_int32), ("S12", C.c_double * 8), ("fix_scale", C.c_int32), ("th2", C.c_float),
         ("cam1", C.c_double * 8), ("cam2", C.c_double * 8), ("kb8_1", C.c_int32), ("kb8_2", C.c_int32),
         ("X1c", c_double_p), ("X2c", c_double_p), ("obs1", c_double_p), ("obs2", c_double_p),
-        ("info1", c_double_p), ("info2", c_double_p),
+        ("info1", c_double_p), ("info2", c_double_p), ("iterations", C.c_int32 * 3),
     ]
 
 
@@ -150,6 +150,7 @@ class Sim3Result(C.Structure):
     ]
 
 
+OSH_SIM3_MAX_ITERATIONS = 100   # the limit of every osh_sim3_problem.iterations entry
 OSH_PGO_MAX_VERTICES = 4000
 OSH_PGO_SOLVE_ENVELOPE = 0
 OSH_PGO_SOLVE_DENSE = 1

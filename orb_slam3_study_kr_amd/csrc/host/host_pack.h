@@ -466,6 +466,7 @@ struct Sim3OptPack {
     const double S[8] = {q.x(), q.y(), q.z(), q.w(), t(0), t(1), t(2), S12.scale()};
     for (int k = 0; k < 8; ++k) { p.S12[k] = S[k]; p.cam1[k] = cam1[k]; p.cam2[k] = cam2[k]; }
     p.fix_scale = bFixScale ? 1 : 0; p.th2 = th2; p.kb8_1 = kb8_1; p.kb8_2 = kb8_2;
+    p.iterations[0] = 5; p.iterations[1] = 10; p.iterations[2] = 5;   // optimize(5), optimize(nBad > 0 ? 10 : 5) (src/Optimizer.cc:2287, :2325-2331)
     p.X1c = X1c.data(); p.X2c = X2c.data(); p.obs1 = obs1.data(); p.obs2 = obs2.data(); p.info1 = info1.data(); p.info2 = info2.data();
   }
 };

@@ -7,7 +7,9 @@
 // Levenberg-Marquardt loop of optimization_algorithm_levenberg.cpp:99-169 (three-bad-iterations stop) with the dense 7x7 solve of
 // LinearSolverDense.  The whole call -- optimize(5), the classification of the pairs by their last computed chi2, the early
 // return under 10 inliers, optimize(nBad > 0 ? 10 : 5) without kernels and the final classification -- runs in ONE block per
-// problem: thread per pair, fixed-order block reductions (bitwise reproducible, independent of the batch).
+// problem: thread per pair, fixed-order block reductions (bitwise reproducible, independent of the batch).  The budgets 5, 10 and 5
+// are inputs (osh_sim3_problem.iterations, 0..OSH_SIM3_MAX_ITERATIONS each): a budget of 0 runs no iteration of its round, which
+// lets tests/test_gpu_sim3_stages.py see one stage at a time in the ordinary outputs.
 //
 // Per linearisation the 14 perturbed states Sim3(+-delta e_d) * S12 (g2o's push / oplus / pop) and their inverses are formed once
 // in LDS; g2o recomputes the same values for every edge, so the Jacobian bits are unchanged.
@@ -33,6 +35,7 @@ struct Sim3Desc {
   int kb8_1, kb8_2;
   float th2;
   double delta;   // Huber delta (double)(float)sqrt(th2)
+  int iterations[3];   // optimize(N): round 1, round 2 when n_bad > 0, round 2 otherwise
 };
 struct Sim3Out {
   double S[8];
@@ -269,11 +272,12 @@ __global__ __launch_bounds__(kST) void k_sim3_opt(Sim3View v) {
   const double th2 = (double)d.th2;   // a float threshold compared with the double chi2
   int sel = 0, n_bad = 0;
   // round 0: optimize(5) with Huber kernels over every pair; round 1: optimize(nBad > 0 ? 10 : 5) over the inliers without
-  // kernels, from the round-0 estimate (one call site of the optimiser: the kernel is inlined once)
+  // kernels, from the round-0 estimate (one call site of the optimiser: the kernel is inlined once).  The budgets are
+  // d.iterations, {5, 10, 5} from OptimizeSim3
   for (int round = 0; round < 2; ++round) {
     int iters = 0;
     double chi = 0.0;
-    sel = sim3_optimize<KB8>(v, d, sm, sel, round == 0 ? 5 : (n_bad > 0 ? 10 : 5), round == 0, iters, chi);
+    sel = sim3_optimize<KB8>(v, d, sm, sel, round == 0 ? d.iterations[0] : (n_bad > 0 ? d.iterations[1] : d.iterations[2]), round == 0, iters, chi);
     if (tid == 0) { out.iterations[round] = iters; out.chi2_end[round] = chi; }
     if (round == 0) {
       // classification by the chi2 each edge last computed (the last trial's, accepted or not)
@@ -341,11 +345,16 @@ static int sim3_run(osh_lba_ctx* ctx, int n, const osh_sim3_problem* pr, int lin
     if (!(p.th2 > 0.0f) || !std::isfinite(p.th2)) { set_error("problem %d: th2 must be positive and finite", f); return OSH_ERR_INVALID; }
     if (!(p.S12[7] > 0.0) || !std::isfinite(p.S12[7])) { set_error("problem %d: the scale of S12 must be positive and finite", f); return OSH_ERR_INVALID; }
     if ((p.kb8_1 != 0 && p.kb8_1 != 1) || (p.kb8_2 != 0 && p.kb8_2 != 1)) { set_error("problem %d: camera model out of range", f); return OSH_ERR_INVALID; }
+    for (int k = 0; k < 3; ++k)
+      if (p.iterations[k] < 0 || p.iterations[k] > OSH_SIM3_MAX_ITERATIONS) {
+        set_error("problem %d: iterations[%d] = %d outside 0..%d", f, k, p.iterations[k], OSH_SIM3_MAX_ITERATIONS); return OSH_ERR_INVALID;
+      }
     Sim3Desc& d = h_desc[f];
     std::memset(&d, 0, sizeof(d));
     d.n = p.n_pairs; d.off = (int)NP; d.fix_scale = p.fix_scale ? 1 : 0;
     for (int k = 0; k < 8; ++k) { d.S[k] = p.S12[k]; d.cam1[k] = p.cam1[k]; d.cam2[k] = p.cam2[k]; }
     d.kb8_1 = p.kb8_1; d.kb8_2 = p.kb8_2;
+    for (int k = 0; k < 3; ++k) d.iterations[k] = p.iterations[k];
     any_kb8 = any_kb8 || p.kb8_1 || p.kb8_2;
     d.th2 = p.th2;
     d.delta = (double)std::sqrt(p.th2);   // const float deltaHuber = sqrt(th2) (src/Optimizer.cc:2165)

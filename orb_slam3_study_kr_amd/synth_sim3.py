@@ -5,7 +5,7 @@ with pixel noise, a fraction of swapped matches (outliers), and optionally pairs
 (i2 < 0), bad map points, NULL map points of pKF1, second points behind pKF2's camera, fixed or free scale, and Pinhole or
 KannalaBrandt8 cameras.  host_input() turns a case into the stand-in input of the test-only host library (osh_host_sim3_input),
 pack() restates the walk of src/Optimizer.cc:2162-2277 on the same float data, and problem() builds an osh_sim3_problem from a
-pack.  Sim3 arrays are qx qy qz qw tx ty tz s.
+pack (its budgets from the pack's "iterations" when present, else ITERATIONS).  Sim3 arrays are qx qy qz qw tx ty tz s.
 """
 from __future__ import annotations
 
@@ -18,6 +18,7 @@ from . import capi
 
 F32 = np.float32
 TH2 = 10.0   # LoopClosing's th2 for OptimizeSim3 (src/LoopClosing.cc:558, :768)
+ITERATIONS = (5, 10, 5)   # optimize(5), then optimize(nBad > 0 ? 10 : 5): osh_sim3_problem.iterations
 
 
 def _quat_from_axis_angle(w):
@@ -263,6 +264,7 @@ def problem(pk: dict, keep: list | None = None) -> capi.Sim3Problem:
     p.fix_scale = int(pk["fix_scale"]); p.th2 = pk["th2"]
     p.cam1[:] = [float(v) for v in pk["cam1"]]; p.cam2[:] = [float(v) for v in pk["cam2"]]
     p.kb8_1 = int(pk["kb8_1"]); p.kb8_2 = int(pk["kb8_2"])
+    p.iterations[:] = [int(v) for v in pk.get("iterations", ITERATIONS)]
     for k in ("X1c", "X2c", "obs1", "obs2", "info1", "info2"):
         a = np.ascontiguousarray(pk[k], np.float64)
         keep.append(a)

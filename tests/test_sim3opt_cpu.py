@@ -64,6 +64,7 @@ def test_host_pack_matches_the_walk(all_points, kb8):
         assert np.array_equal(arr[k][:n].reshape(pk[k].shape), pk[k]), k
     assert list(prob.S12) == list(pk["S12"]) and prob.fix_scale == int(pk["fix_scale"]) and prob.th2 == np.float32(pk["th2"])
     assert list(prob.cam1) == list(pk["cam1"]) and list(prob.cam2) == list(pk["cam2"]) and prob.kb8_1 == prob.kb8_2 == int(kb8)
+    assert list(prob.iterations) == [5, 10, 5] == list(ss.ITERATIONS) == list(ss.problem(pk).iterations)
     # the special slots: bad points, NULL pMP1 and points behind pKF2 never make a pair; i2 < 0 pairs only with bAllPoints
     N = 200
     specials = dict(no_i2=range(N, N + 7), bad=range(N + 7, N + 13), null=range(N + 13, N + 18), neg=range(N + 18, N + 22))
