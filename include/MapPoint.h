@@ -33,7 +33,10 @@ class MapPoint {
   MapPoint* GetReplaced() { return mpReplaced; }
   void IncreaseVisible(int n = 1) { mnVisible += n; }
   void IncreaseFound(int n = 1) { mnFound += n; }
-  void ComputeDistinctiveDescriptors() { ++mnDescriptorUpdates; }
+  // counts the call; with sbRecomputeDescriptors (test-double state, off by default) it also picks mDescriptor as src/MapPoint.cc:329-403
+  // does (stand-in body: csrc/hosttest/graph_stubs.cc), so that MapPoint::Replace changes the survivor's descriptor as in the reference
+  void ComputeDistinctiveDescriptors();
+  static bool sbRecomputeDescriptors;
   Map* GetMap() { return mpMap; }
   void UpdateNormalAndDepth() { ++mnNormalUpdates; }
   cv::Mat GetDescriptor() { return mDescriptor.clone(); }

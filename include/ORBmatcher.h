@@ -2,7 +2,9 @@
  * reference's signatures (include/ORBmatcher.h:36-102). */
 #ifndef ORBMATCHER_H
 #define ORBMATCHER_H
+#include <functional>
 #include <set>
+#include <utility>
 #include <vector>
 #include "Frame.h"
 #include "KeyFrame.h"
@@ -47,6 +49,27 @@ class ORBmatcher {
   int Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const float th = 3.0, const bool bRight = false);
   // Project MapPoints into KeyFrame using a given Sim3 and search for duplicated MapPoints (include/ORBmatcher.h:90, src/ORBmatcher.cc:1340-1455)
   int Fuse(KeyFrame* pKF, Sophus::Sim3f& Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint);
+  /* ADD THESE MEMBERS to the reference's class (csrc/host/ORBmatcher.cc, csrc/host/fuse_batch.h): one map point list fused into many
+   * keyframes with ONE device search (osh_orb_fuse_search) instead of one per keyframe.
+   * FuseBatch(targets, vpMapPoints): the returned counts and every change to the map equal calling Fuse(pKF, vpMapPoints, th, bRight)
+   * for the targets in order.
+   * FuseBatch(targets, vpPoints, th, vvpReplacePoints, after): equals Fuse(pKF, Scw, vpPoints, th, vvpReplacePoints[k]) for the
+   * targets in order; after(k) (may be empty) is called once target k has been replayed and before target k + 1 is: the place of
+   * LoopClosing::SearchAndFuse's Replace loop.  vvpReplacePoints is sized [targets][points] here.
+   * A list point whose descriptor an earlier target's replay (or `after`) changed gets its best candidate redone on the host with
+   * the current descriptor; mnFuseBatchResearched counts those pairs over the object's calls, mnFuseBatchResearchedChanged those of
+   * them whose best index, or whose acceptance (distance <= TH_LOW), came out differently than under the uploaded descriptor: the
+   * pairs where a replay that ignored staleness would have acted differently.  If the search fails on the device
+   * a message goes to stderr and the call falls back to the loop of Fuse calls.
+   * Stand-in only, not for the reference's class: mbFuseBatchSearchOnHost (runs the search by the same statements on the calling
+   * thread instead of the device) and mnFuseBatchResearchedChanged. */
+  struct FuseTarget { KeyFrame* pKF; float th; bool bRight; };
+  typedef std::function<void(int)> AfterTarget;
+  std::vector<int> FuseBatch(const std::vector<FuseTarget>& targets, const std::vector<MapPoint*>& vpMapPoints);
+  std::vector<int> FuseBatch(const std::vector<std::pair<KeyFrame*, Sophus::Sim3f>>& targets, const std::vector<MapPoint*>& vpPoints, float th,
+                             std::vector<std::vector<MapPoint*>>& vvpReplacePoints, AfterTarget after = AfterTarget());
+  int mnFuseBatchResearched = 0, mnFuseBatchResearchedChanged = 0;
+  bool mbFuseBatchSearchOnHost = false;
   static const int TH_LOW;
   static const int TH_HIGH;
   static const int HISTO_LENGTH;

@@ -1876,6 +1876,97 @@ int osh_orb_bow_db_query(osh_orb_ctx* ctx, osh_bow_db* db, int32_t n_queries, co
  * ms[2] kernels, ms[3] download + write-back. */
 int osh_orb_bow_db_get_times(osh_orb_ctx* ctx, double ms[4]);
 
+/* ------------------------------------------------- ORBmatcher::Fuse, one point list into many keyframes */
+/*
+ * The part of both ORBmatcher::Fuse overloads (src/ORBmatcher.cc:1148-1338 and :1340-1455) that does not depend on what their
+ * loops do to the map, for every (target keyframe, map point) pair of n_targets x points->n in one call.  Per pair, in float32
+ * with single rounded operations and no fused multiply-add (the statements: csrc/orb_fuse.h):
+ *   p3Dc = Rcw * p3Dw + tcw, three-term sums as a0 + (a1 + a2); z < 0: OSH_FUSE_BEHIND.  The projection of the target's camera
+ *   (atan2, cos, sin and log as the FP64 function rounded once); outside x >= min_x && x < max_x && y >= min_y && y < max_y:
+ *   OSH_FUSE_OUTSIDE (z == 0 ends here through inf / NaN).  ur = u - bf / z.  PO = p3Dw - Ow, dist = |PO|; dist < 0.8f * min_dist
+ *   or dist > 1.2f * max_dist: OSH_FUSE_DISTANCE.  PO . normal < 0.5 * dist (compared in double): OSH_FUSE_ANGLE.  level =
+ *   MapPoint::PredictScale = ceil(log(max_dist / dist) / log_scale_factor) clamped to [0, n_levels - 1] (a value no int holds
+ *   gives level 0, as the conversion of the reference's build does); radius = th * scale_factors[level].  The window of
+ *   KeyFrame::GetFeaturesInArea(u, v, radius) on the target's grid (src/KeyFrame.cc:704-745), its cells ix-major, then iy, then in
+ *   insertion order; no keypoint with |dx| < radius && |dy| < radius: OSH_FUSE_EMPTY.  Otherwise OSH_FUSE_SEARCHED: the candidates
+ *   are the keypoints of the window whose octave is level - 1 or level and, in mode OSH_FUSE_CHI2, whose reprojection error passes
+ *   (key_uright >= 0: (ex^2 + ey^2 + er^2) * inv_level_sigma2[octave] <= 7.8, else (ex^2 + ey^2) * inv_level_sigma2[octave] <= 5.99;
+ *   the float product compared in double); best_idx is the first candidate of the scan with the least Hamming distance below 256.
+ * The grid of a target is binned from key_xy by the rule of the grid upload (osh_orb_upload_grid: PosInGrid's rounding, keypoint
+ * order inside a cell).  Which camera of a rig a target is, is the caller's matter: it hands over that side's pose, camera and
+ * keypoints.  A point with skip != 0 (a null entry of the list) gets OSH_FUSE_SKIPPED and nothing else is computed.
+ *
+ * Result arrays are [n_targets * n], target-major; each may be NULL.  Every word of every array that is not NULL is written: u, v,
+ * ur are 0 up to OSH_FUSE_OUTSIDE, level is -1 and radius 0 up to OSH_FUSE_ANGLE, n_candidates is 0, best_idx -1 and best_dist
+ * 256 unless a candidate was found.
+ *
+ * Refused before any device work and without a context, which stays usable.  OSH_ERR_INVALID (the message names the target or the
+ * point and the field): a negative count, a NULL array whose count is not 0, a non-finite pose, camera, bf, image bound, grid
+ * value, level table entry, th or keypoint coordinate, n_levels outside [1, OSH_FUSE_MAX_LEVELS], an octave outside [0, n_levels),
+ * a non-positive grid size or cell inverse, an unknown mode or camera kind.  OSH_ERR_UNSUPPORTED: more than OSH_FUSE_MAX_TARGETS
+ * targets, OSH_FUSE_MAX_POINTS points, OSH_FUSE_MAX_KEYS keypoints in a target, OSH_FUSE_MAX_CELLS grid cells in a target (the
+ * bound on the cells of a window), OSH_FUSE_MAX_CELL_ENTRIES keypoints in a cell, or 2^27 pairs.  Non-finite point data is not
+ * refused: such a pair fails its gates as the reference's arithmetic would.  No targets or no points is a valid empty call.
+ */
+#define OSH_FUSE_MAX_TARGETS      1024
+#define OSH_FUSE_MAX_POINTS       1048576   /* 2^20 */
+#define OSH_FUSE_MAX_KEYS         65536     /* keypoints of one target */
+#define OSH_FUSE_MAX_CELLS        16384     /* cols * rows of one target: the cell number of a window fits the key's 14 bits */
+#define OSH_FUSE_MAX_CELL_ENTRIES 255       /* keypoints in one cell: the entry fits the key's 8 bits */
+#define OSH_FUSE_MAX_LEVELS       OSH_STEREO_MAX_LEVELS
+#define OSH_FUSE_PINHOLE 0
+#define OSH_FUSE_KB8     1
+#define OSH_FUSE_CHI2    0   /* Fuse(KeyFrame*, vector<MapPoint*>, th, bRight): with the reprojection-error gate */
+#define OSH_FUSE_SIM3    1   /* Fuse(KeyFrame*, Sim3f, ...): without it */
+#define OSH_FUSE_SKIPPED  0
+#define OSH_FUSE_BEHIND   1
+#define OSH_FUSE_OUTSIDE  2
+#define OSH_FUSE_DISTANCE 3
+#define OSH_FUSE_ANGLE    4
+#define OSH_FUSE_EMPTY    5
+#define OSH_FUSE_SEARCHED 6
+typedef struct osh_fuse_target {
+  float Rcw[9], tcw[3], Ow[3];     /* row-major rotation, translation, camera centre                                          */
+  int32_t camera;                  /* OSH_FUSE_PINHOLE / OSH_FUSE_KB8                                                         */
+  float fx, fy, cx, cy, kb8[4];    /* kb8 is read for OSH_FUSE_KB8 only                                                       */
+  float bf;
+  float min_x, max_x, min_y, max_y;                          /* mnMinX, mnMaxX, mnMinY, mnMaxY (KeyFrame::IsInImage)          */
+  float grid_min_x, grid_min_y, cell_w_inv, cell_h_inv;      /* mnMinX, mnMinY, mfGridElementWidthInv / HeightInv             */
+  int32_t cols, rows;                                        /* mnGridCols, mnGridRows                                        */
+  int32_t n_levels;
+  float log_scale_factor;
+  float scale_factors[OSH_FUSE_MAX_LEVELS], inv_level_sigma2[OSH_FUSE_MAX_LEVELS];   /* the first n_levels are read          */
+  float th;
+  int32_t n_keys;
+  const float* key_xy;             /* [n_keys*2]                                                                              */
+  const int32_t* key_octave;       /* [n_keys]                                                                                */
+  const float* key_uright;         /* [n_keys] mvuRight, or NULL: no stereo term                                              */
+  const uint8_t* descriptors;      /* [n_keys*32]                                                                             */
+} osh_fuse_target;
+typedef struct osh_fuse_points {
+  int32_t n;
+  const float* pos;                /* [n*3] GetWorldPos                                                                       */
+  const float* normal;             /* [n*3] GetNormal                                                                         */
+  const float* min_dist;           /* [n]   mfMinDistance                                                                     */
+  const float* max_dist;           /* [n]   mfMaxDistance                                                                     */
+  const uint8_t* desc;             /* [n*32] GetDescriptor                                                                    */
+  const uint8_t* skip;             /* [n] or NULL                                                                             */
+} osh_fuse_points;
+typedef struct osh_fuse_result {
+  int32_t* stage;
+  float* u; float* v; float* ur;
+  int32_t* level;
+  float* radius;
+  int32_t* n_candidates;           /* after the level and chi2 gates                                                          */
+  int32_t* best_idx;               /* index among the target's own keypoints, or -1                                           */
+  int32_t* best_dist;              /* or 256                                                                                  */
+} osh_fuse_result;
+int osh_orb_fuse_search(osh_orb_ctx* ctx, int32_t n_targets, const osh_fuse_target* targets, const osh_fuse_points* points,
+                        int32_t mode, const osh_fuse_result* result);
+/* Host-clock phases (ms) of the last osh_orb_fuse_search under osh_orb_set_profiling: ms[0] validation + staging (the grids are
+ * binned here), ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
+int osh_orb_fuse_get_times(osh_orb_ctx* ctx, double ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -992,6 +992,50 @@ int osh_host_kf_cull_state(osh_host_graph* g, int32_t kf, int64_t out[9]);
 /* out = Observations(), isBad(), the size of GetObservations(). */
 int osh_host_mp_cull_state(osh_host_graph* g, int32_t mp, int64_t out[3]);
 
+/* ---- ORBmatcher::Fuse for many targets (csrc/orb_fuse.h, csrc/hosttest/fuse_batch.cc) ---- */
+struct osh_fuse_target;
+struct osh_fuse_points;
+struct osh_fuse_result;
+/* csrc/orb_fuse.h (the statements k_fuse_project / k_fuse_search run) compiled for the host, on one thread, the grids binned by
+ * csrc/orb_grid_bin.h: arguments and results as osh_orb_fuse_search without a context and without its validation (the call must be
+ * valid).  *ms (may be NULL) = wall time of the whole call.  -1: bad arguments or a cell above OSH_FUSE_MAX_CELL_ENTRIES. */
+int osh_host_fuse_search_cpu(int32_t n_targets, const struct osh_fuse_target* targets, const struct osh_fuse_points* points, int32_t mode,
+                             const struct osh_fuse_result* result, double* ms);
+/* MapPoint::sbRecomputeDescriptors of the stand-in: when on, MapPoint::ComputeDistinctiveDescriptors (and with it MapPoint::Replace)
+ * really picks the descriptor, as the reference does; off by default, process wide. */
+void osh_host_set_recompute_descriptors(int32_t on);
+/* ORBmatcher::FuseBatch(targets, vpMapPoints) on the graph: target k = (keyframe kf[k], th[k], right[k]); mp: the list (-1: a null
+ * entry).  cpu_search: the search runs by csrc/orb_fuse.h on the calling thread instead of the device.  fused [n_targets]: the
+ * returned counts; researched [2] = mnFuseBatchResearched, mnFuseBatchResearchedChanged.  -1: bad arguments. */
+int osh_host_graph_fuse_batch(osh_host_graph* g, int32_t n_targets, const int32_t* kf, const float* th, const uint8_t* right, int32_t n,
+                              const int32_t* mp, int32_t cpu_search, int32_t* fused, int32_t* researched);
+/* The Sim3 overload of FuseBatch: sim3 [n_targets*8] = qw qx qy qz tx ty tz s of every Scw.  replace_after: `after(k)` runs
+ * LoopClosing::SearchAndFuse's loop, vpReplacePoints[i]->Replace(vpPoints[i]).  replace [n_targets*n] (may be NULL): every
+ * vpReplacePoint list as point indices (-1: none). */
+int osh_host_graph_fuse_batch_sim3(osh_host_graph* g, int32_t n_targets, const int32_t* kf, const float* sim3, int32_t n, const int32_t* mp,
+                                   float th, int32_t cpu_search, int32_t replace_after, int32_t* fused, int32_t* replace, int32_t* researched);
+/* One ORBmatcher::Fuse(KeyFrame*, Sim3f&, vpPoints, th, vpReplacePoint) on the graph; returns its result, replace [n] as above. */
+int osh_host_graph_fuse_sim3(osh_host_graph* g, int32_t kf, const float sim3[8], int32_t n, const int32_t* mp, float th, int32_t* replace);
+/* point mp ->Replace(point by). */
+int osh_host_graph_replace(osh_host_graph* g, int32_t mp, int32_t by);
+/* LoopClosing::SearchAndFuse: with_poses: the KeyFrameAndPose overload, sim3 [n_kf*8] doubles (qw qx qy qz tx ty tz s) of the g2o::Sim3
+ * of every keyframe; else the keyframe-list overload.  order [n_kf]: the keyframe indices in the order the call walked them (the
+ * map's order is by pointer value).  info = replacements made, mnFuseBatchResearched, mnFuseBatchResearchedChanged. */
+int osh_host_loop_search_and_fuse(osh_host_graph* g, int32_t with_poses, int32_t n_kf, const int32_t* kf, const double* sim3, int32_t n,
+                                  const int32_t* mp, int32_t cpu_search, int32_t* order, int32_t info[3]);
+/* What one ORBmatcher::Fuse call decides per point before its device search (FuseCandidateLists of csrc/host/ORBmatcher.cc: the
+ * stand-in camera's own project, the SE3f pose, KeyFrame::GetFeaturesInArea): sim3 NULL: the first overload with (th, right); else
+ * the Sim3 overload through that Scw (8 floats).  count [n]: the length of the point's candidate list, -1 when the point is no
+ * query; cand: the lists one after another as indices in the keyframe's own arrays, the first `capacity` of them.  Returns the
+ * total length of the lists; -1: bad arguments. */
+int osh_host_graph_fuse_candidates(osh_host_graph* g, int32_t kf, const float* sim3, float th, int32_t right, int32_t n, const int32_t* mp,
+                                   int32_t* count, int32_t capacity, int32_t* cand);
+/* The same call as FuseBatch sees it: the pack of that one target (csrc/host/fuse_batch.h) searched by csrc/orb_fuse.h on the calling
+ * thread (cpu_search) or by osh_orb_fuse_search.  stage, n_candidates, best_idx (in the keyframe's own arrays), best_dist [n].
+ * -1: bad arguments, -2: the search failed. */
+int osh_host_graph_fuse_pack_search(osh_host_graph* g, int32_t kf, const float* sim3, float th, int32_t right, int32_t n, const int32_t* mp,
+                                    int32_t cpu_search, int32_t* stage, int32_t* n_candidates, int32_t* best_idx, int32_t* best_dist);
+
 #ifdef __cplusplus
 }
 #endif

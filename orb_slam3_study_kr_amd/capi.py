@@ -479,6 +479,37 @@ class MapPointResult(C.Structure):
 OSH_MAPPOINT_MAX_DESCRIPTORS, OSH_MAPPOINT_MAX_POINTS, OSH_MAPPOINT_MAX_ENTRIES = 256, 1 << 22, 1 << 25
 
 
+class FuseTarget(C.Structure):
+    """``osh_fuse_target`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("camera", C.c_int32), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("kb8", C.c_float * 4), ("bf", C.c_float), ("min_x", C.c_float),
+                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("grid_min_x", C.c_float), ("grid_min_y", C.c_float),
+                ("cell_w_inv", C.c_float), ("cell_h_inv", C.c_float), ("cols", C.c_int32), ("rows", C.c_int32), ("n_levels", C.c_int32),
+                ("log_scale_factor", C.c_float), ("scale_factors", C.c_float * 16), ("inv_level_sigma2", C.c_float * 16), ("th", C.c_float),
+                ("n_keys", C.c_int32), ("key_xy", c_float_p), ("key_octave", c_int32_p), ("key_uright", c_float_p), ("descriptors", c_uint8_p)]
+
+
+class FusePoints(C.Structure):
+    """``osh_fuse_points`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("n", C.c_int32), ("pos", c_float_p), ("normal", c_float_p), ("min_dist", c_float_p), ("max_dist", c_float_p),
+                ("desc", c_uint8_p), ("skip", c_uint8_p)]
+
+
+class FuseResult(C.Structure):
+    """``osh_fuse_result`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("stage", c_int32_p), ("u", c_float_p), ("v", c_float_p), ("ur", c_float_p), ("level", c_int32_p), ("radius", c_float_p),
+                ("n_candidates", c_int32_p), ("best_idx", c_int32_p), ("best_dist", c_int32_p)]
+
+
+OSH_FUSE_MAX_TARGETS, OSH_FUSE_MAX_POINTS, OSH_FUSE_MAX_KEYS, OSH_FUSE_MAX_CELLS, OSH_FUSE_MAX_CELL_ENTRIES, OSH_FUSE_MAX_LEVELS = 1024, 1 << 20, 65536, 16384, 255, 16
+OSH_FUSE_PINHOLE, OSH_FUSE_KB8 = 0, 1
+OSH_FUSE_CHI2, OSH_FUSE_SIM3 = 0, 1
+OSH_FUSE_SKIPPED, OSH_FUSE_BEHIND, OSH_FUSE_OUTSIDE, OSH_FUSE_DISTANCE, OSH_FUSE_ANGLE, OSH_FUSE_EMPTY, OSH_FUSE_SEARCHED = range(7)
+
+
 class KfCullProblem(C.Structure):
     """``osh_kfcull_problem`` (include/orbslam3_hip.h)."""
 
@@ -757,6 +788,8 @@ _SIGNATURES = {
     "osh_orb_sim3_ransac_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_refresh_map_points": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MapPointBatch), C.POINTER(MapPointResult)]),
     "osh_orb_refresh_map_points_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_fuse_search": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FuseTarget), C.POINTER(FusePoints), C.c_int32, C.POINTER(FuseResult)]),
+    "osh_orb_fuse_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_orb_keyframe_cull_stage": (C.c_int, [C.c_void_p, C.POINTER(KfCullProblem)]),
     "osh_orb_keyframe_cull_count": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.POINTER(KfCullResult)]),
     "osh_orb_keyframe_cull_get_times": (C.c_int, [C.c_void_p, c_double_p]),
@@ -1204,6 +1237,20 @@ _HOST_SIGNATURES.update({
     "osh_host_kfcull_time": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, c_double_p, c_int64_p]),
     "osh_host_kf_cull_state": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
     "osh_host_mp_cull_state": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
+})
+
+# ORBmatcher::Fuse for many targets (csrc/hosttest/fuse_batch.cc)
+_HOST_SIGNATURES.update({
+    "osh_host_fuse_search_cpu": (C.c_int, [C.c_int32, C.POINTER(FuseTarget), C.POINTER(FusePoints), C.c_int32, C.POINTER(FuseResult), c_double_p]),
+    "osh_host_set_recompute_descriptors": (None, [C.c_int32]),
+    "osh_host_graph_fuse_batch": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, c_uint8_p, C.c_int32, c_int32_p, C.c_int32, c_int32_p, c_int32_p]),
+    "osh_host_graph_fuse_batch_sim3": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.c_int32, c_int32_p, C.c_float, C.c_int32, C.c_int32,
+                                                 c_int32_p, c_int32_p, c_int32_p]),
+    "osh_host_graph_fuse_sim3": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, C.c_int32, c_int32_p, C.c_float, c_int32_p]),
+    "osh_host_graph_replace": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "osh_host_graph_fuse_candidates": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, C.c_float, C.c_int32, C.c_int32, c_int32_p, c_int32_p, C.c_int32, c_int32_p]),
+    "osh_host_graph_fuse_pack_search": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, C.c_float, C.c_int32, C.c_int32, c_int32_p, C.c_int32] + [c_int32_p] * 4),
+    "osh_host_loop_search_and_fuse": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p, c_double_p, C.c_int32, c_int32_p, C.c_int32, c_int32_p, c_int32_p]),
 })
 
 

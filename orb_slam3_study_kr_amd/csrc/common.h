@@ -47,9 +47,9 @@ T* attachment(osh_lba_ctx* c, LbaAttachSlot slot) {
 // osh_orb_stereo_match (stereo_device.hip), osh_orb_fisheye_stereo_match (fisheye_stereo_device.hip) and osh_orb_bow_transform
 // (bow_device.hip), osh_orb_bow_db_query (bowdb_device.hip), osh_orb_triangulate_new_points (newpoint_device.hip) and
 // osh_orb_fast_detect / osh_orb_ic_angle (orb_fast_device.hip), osh_orb_describe (orb_brief_device.hip), osh_orb_refresh_map_points
-// (mappoint_device.hip), osh_orb_two_view_reconstruct (two_view_device.hip), osh_orb_mlpnp_solve (mlpnp_device.hip), osh_orb_sim3_ransac (sim3_ransac_device.hip), osh_orb_octree_distribute (orb_octree_device.hip), osh_orb_extract (orb_extract_device.hip), osh_orb_keyframe_cull_stage / _count (keyframe_cull_device.hip), osh_orb_prepare / osh_orb_extract_raw (orb_prepare_device.hip) run on an osh_orb_ctx the same way: the context's device (made current) and stream, one attachment pointer each (handed to free_fn by osh_orb_destroy;
+// (mappoint_device.hip), osh_orb_two_view_reconstruct (two_view_device.hip), osh_orb_mlpnp_solve (mlpnp_device.hip), osh_orb_sim3_ransac (sim3_ransac_device.hip), osh_orb_octree_distribute (orb_octree_device.hip), osh_orb_extract (orb_extract_device.hip), osh_orb_keyframe_cull_stage / _count (keyframe_cull_device.hip), osh_orb_prepare / osh_orb_extract_raw (orb_prepare_device.hip), osh_orb_fuse_search (orb_fuse_device.hip) run on an osh_orb_ctx the same way: the context's device (made current) and stream, one attachment pointer each (handed to free_fn by osh_orb_destroy;
 // orb_state of orb_stage.h is the typed fetch-or-create), and whether osh_orb_set_profiling switched timing on.
-enum OrbAttachSlot { kOrbAttachStereo = 0, kOrbAttachFisheye = 1, kOrbAttachBow = 2, kOrbAttachBowDb = 3, kOrbAttachNewPoint = 4, kOrbAttachFast = 5, kOrbAttachBrief = 6, kOrbAttachMapPoint = 7, kOrbAttachTwoView = 8, kOrbAttachMlpnp = 9, kOrbAttachSim3Ransac = 10, kOrbAttachOctree = 11, kOrbAttachExtract = 12, kOrbAttachKfCull = 13, kOrbAttachPrepare = 14, kOrbAttachCount };
+enum OrbAttachSlot { kOrbAttachStereo = 0, kOrbAttachFisheye = 1, kOrbAttachBow = 2, kOrbAttachBowDb = 3, kOrbAttachNewPoint = 4, kOrbAttachFast = 5, kOrbAttachBrief = 6, kOrbAttachMapPoint = 7, kOrbAttachTwoView = 8, kOrbAttachMlpnp = 9, kOrbAttachSim3Ransac = 10, kOrbAttachOctree = 11, kOrbAttachExtract = 12, kOrbAttachKfCull = 13, kOrbAttachPrepare = 14, kOrbAttachFuse = 15, kOrbAttachCount };
 int orb_stream(osh_orb_ctx* c, int* device, hipStream_t* stream);
 void** orb_attachment(osh_orb_ctx* c, void (*free_fn)(void*), OrbAttachSlot slot);
 bool orb_profiling(osh_orb_ctx* c);

@@ -405,11 +405,15 @@ void LocalMapping::SearchInNeighbors() {
   // Search matches by projection from current KF in target KFs
   ORBmatcher matcher;
   std::vector<MapPoint*> vpMapPointMatches = mpCurrentKeyFrame->GetMapPointMatches();
+  // one batch for all targets (ORBmatcher::FuseBatch): the map it leaves is the one of the reference's loop of Fuse calls.  On a rig
+  // the second call is Fuse(pKFi, vpMapPointMatches, true), whose `true` binds to th: th = 1, the left camera again
+  std::vector<ORBmatcher::FuseTarget> vFuseTargets;
   for (std::vector<KeyFrame*>::iterator vit = vpTargetKFs.begin(), vend = vpTargetKFs.end(); vit != vend; vit++) {
     KeyFrame* pKFi = *vit;
-    matcher.Fuse(pKFi, vpMapPointMatches);
-    if (pKFi->NLeft != -1) matcher.Fuse(pKFi, vpMapPointMatches, true);
+    vFuseTargets.push_back(ORBmatcher::FuseTarget{pKFi, 3.0f, false});
+    if (pKFi->NLeft != -1) vFuseTargets.push_back(ORBmatcher::FuseTarget{pKFi, 1.0f, false});
   }
+  matcher.FuseBatch(vFuseTargets, vpMapPointMatches);
 
   if (mbAbortBA) return;
 
@@ -428,8 +432,9 @@ void LocalMapping::SearchInNeighbors() {
     }
   }
 
-  matcher.Fuse(mpCurrentKeyFrame, vpFuseCandidates);
-  if (mpCurrentKeyFrame->NLeft != -1) matcher.Fuse(mpCurrentKeyFrame, vpFuseCandidates, true);
+  vFuseTargets.assign(1, ORBmatcher::FuseTarget{mpCurrentKeyFrame, 3.0f, false});
+  if (mpCurrentKeyFrame->NLeft != -1) vFuseTargets.push_back(ORBmatcher::FuseTarget{mpCurrentKeyFrame, 1.0f, false});
+  matcher.FuseBatch(vFuseTargets, vpFuseCandidates);
 
   // Update points (:837-849): the pairs of all non-bad matches as one batch
   vpMapPointMatches = mpCurrentKeyFrame->GetMapPointMatches();

@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <set>
 
+#include "fuse_batch.h"
 #include "orb_search.h"
 
 namespace ORB_SLAM3 {
@@ -613,24 +614,15 @@ int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, std::vect
   return nmatches;
 }
 
-// src/ORBmatcher.cc:1148-1338.  Every map point is projected into the keyframe and its candidate list (the features in the search
-// radius that pass the level and the reprojection-chi2 gates, in GetFeaturesInArea's order) is formed up front: none of that depends
-// on what the loop does to earlier points.  ONE batched device search gives the best candidate of every point; the part that is
-// order dependent -- "already in the keyframe", Replace in either direction, AddObservation / AddMapPoint -- is replayed in the
-// reference's order on the map itself.
-namespace {
-
-// The part of both Fuse overloads that does not depend on what their loops do to the map: per map point the projection gates
-// (src/ORBmatcher.cc:1196-1260 / 1372-1412) and the candidate list -- the features of GetFeaturesInArea, in its order, that pass the
-// level gate and (first overload, chi2_gate) the reprojection-error gate -- then ONE batched device search over the lists.
-// qOf[i] = query of point i or -1; best / bestD by query.
-bool fuse_search(KeyFrame* pKF, const Sophus::SE3f& Tcw, const Eigen::Vector3f& Ow, GeometricCamera* pCamera, const std::vector<MapPoint*>& vpMapPoints,
-                 const float th, const bool bRight, const bool chi2_gate, std::vector<int>& qOf, std::vector<int32_t>& best, std::vector<int32_t>& bestD) {
+// The host part of fuse_search, with external linkage (declared in fuse_batch.h) so that the test library can read what one Fuse call
+// decides per point before its device search: qOf[i] = query of point i or -1; query q's candidates are idx[off[q] .. off[q + 1]).
+void FuseCandidateLists(KeyFrame* pKF, const Sophus::SE3f& Tcw, const Eigen::Vector3f& Ow, GeometricCamera* pCamera, const std::vector<MapPoint*>& vpMapPoints,
+                        const float th, const bool bRight, const bool chi2_gate, std::vector<int>& qOf, std::vector<uint8_t>& qdesc,
+                        std::vector<int32_t>& off, std::vector<int32_t>& idx) {
   const float& bf = pKF->mbf;
   const int nMPs = (int)vpMapPoints.size();
   qOf.assign(nMPs, -1);
-  std::vector<uint8_t> qdesc;
-  std::vector<int32_t> off(1, 0), idx;
+  qdesc.clear(); idx.clear(); off.assign(1, 0);
   int nq = 0;
   for (int i = 0; i < nMPs; i++) {
     MapPoint* pMP = vpMapPoints[i];
@@ -669,9 +661,27 @@ bool fuse_search(KeyFrame* pKF, const Sophus::SE3f& Tcw, const Eigen::Vector3f& 
     push_desc(qdesc, pMP->GetDescriptor(), 0);
     qOf[i] = nq++;
   }
+}
+
+// src/ORBmatcher.cc:1148-1338.  Every map point is projected into the keyframe and its candidate list (the features in the search
+// radius that pass the level and the reprojection-chi2 gates, in GetFeaturesInArea's order) is formed up front: none of that depends
+// on what the loop does to earlier points.  ONE batched device search gives the best candidate of every point; the part that is
+// order dependent -- "already in the keyframe", Replace in either direction, AddObservation / AddMapPoint -- is replayed in the
+// reference's order on the map itself.
+namespace {
+
+// The part of both Fuse overloads that does not depend on what their loops do to the map: per map point the projection gates
+// (src/ORBmatcher.cc:1196-1260 / 1372-1412) and the candidate list -- the features of GetFeaturesInArea, in its order, that pass the
+// level gate and (first overload, chi2_gate) the reprojection-error gate -- then ONE batched device search over the lists.
+// qOf[i] = query of point i or -1; best / bestD by query.
+bool fuse_search(KeyFrame* pKF, const Sophus::SE3f& Tcw, const Eigen::Vector3f& Ow, GeometricCamera* pCamera, const std::vector<MapPoint*>& vpMapPoints,
+                 const float th, const bool bRight, const bool chi2_gate, std::vector<int>& qOf, std::vector<int32_t>& best, std::vector<int32_t>& bestD) {
+  std::vector<uint8_t> qdesc;
+  std::vector<int32_t> off, idx;
+  FuseCandidateLists(pKF, Tcw, Ow, pCamera, vpMapPoints, th, bRight, chi2_gate, qOf, qdesc, off, idx);
   Found found;
   best.clear(); bestD.clear();
-  if (nq != 0 && !device_search_lists(qdesc, pKF->mDescriptors, pKF->mDescriptors.rows, off, idx, found)) return false;
+  if (off.size() > 1 && !device_search_lists(qdesc, pKF->mDescriptors, pKF->mDescriptors.rows, off, idx, found)) return false;
   best.swap(found.best_idx); bestD.swap(found.best_dist);
   return true;
 }
@@ -744,6 +754,129 @@ int ORBmatcher::Fuse(KeyFrame* pKF, Sophus::Sim3f& Scw, const std::vector<MapPoi
     }
   }
   return nFused;
+}
+
+// ---- FuseBatch: pack, one search, replay (fuse_batch.h)
+namespace {
+
+// the Sim3 overload's pose and centre, as Fuse(KeyFrame*, Sim3f&, ...) forms them
+void sim3_pose(const Sophus::Sim3f& Scw, Sophus::SE3f& Tcw, Eigen::Vector3f& Ow) {
+  const Eigen::Vector3f ts = Scw.translation();
+  const float sc = Scw.scale();
+  Tcw = Sophus::SE3f(Scw.rotationMatrix(), Eigen::Vector3f(ts(0) / sc, ts(1) / sc, ts(2) / sc));
+  Ow = Tcw.inverse().translation();
+}
+
+bool fuse_batch_search(FuseBatchPack& pk, int mode, bool on_host, FuseBatchFound& found) {
+  pk.bind();
+  found.size(pk.targets.size() * (size_t)pk.P);
+  if (pk.targets.empty() || pk.P == 0) return true;
+  if (on_host) return FuseSearchOnHost(pk, mode, found);
+  osh_orb_ctx* ctx = HostMatcherContext();
+  if (!ctx) return false;
+  return osh_orb_fuse_search(ctx, (int32_t)pk.targets.size(), pk.targets.data(), &pk.points, mode, &found.result) == OSH_OK || device_failed("fuse batch search");
+}
+
+}  // namespace
+
+std::vector<int> ORBmatcher::FuseBatch(const std::vector<FuseTarget>& targets, const std::vector<MapPoint*>& vpMapPoints) {
+  const int K = (int)targets.size(), nMPs = (int)vpMapPoints.size();
+  std::vector<int> fused(K, 0);
+  FuseBatchPack pk;
+  pk.set_points(vpMapPoints);
+  for (const FuseTarget& t : targets) {
+    KeyFrame* pKF = t.pKF;
+    if (t.bRight) pk.add_target(pKF, pKF->GetRightPose(), pKF->GetRightCameraCenter(), pKF->mpCamera2, t.th, true, true);
+    else pk.add_target(pKF, pKF->GetPose(), pKF->GetCameraCenter(), pKF->mpCamera, t.th, false, true);
+  }
+  FuseBatchFound found;
+  if (!fuse_batch_search(pk, OSH_FUSE_CHI2, mbFuseBatchSearchOnHost, found)) {
+    for (int k = 0; k < K; ++k) fused[k] = Fuse(targets[k].pKF, vpMapPoints, targets[k].th, targets[k].bRight);
+    return fused;
+  }
+  FuseBatchReplay replay(pk, found, OSH_FUSE_CHI2, TH_LOW);
+  for (int k = 0; k < K; ++k) {
+    KeyFrame* pKF = targets[k].pKF;
+    int nFused = 0;
+    for (int i = 0; i < nMPs; i++) {                                  // Fuse, csrc/host/ORBmatcher.cc: the same loop
+      MapPoint* pMP = vpMapPoints[i];
+      if (!pMP) continue;
+      if (pMP->isBad()) continue;
+      else if (pMP->IsInKeyFrame(pKF)) continue;
+      int bestIdx, bestDist;
+      if (!replay.best_of(k, i, pMP, bestIdx, bestDist)) continue;
+      if (bestIdx >= 0 && bestDist <= TH_LOW) {
+        MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);
+        if (pMPinKF) {
+          if (!pMPinKF->isBad()) {
+            if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+            else pMPinKF->Replace(pMP);
+          }
+        } else {
+          pMP->AddObservation(pKF, bestIdx);
+          pKF->AddMapPoint(pMP, bestIdx);
+        }
+        nFused++;
+      }
+    }
+    fused[k] = nFused;
+    if (k + 1 < K) replay.mark_stale(vpMapPoints);
+  }
+  mnFuseBatchResearched += replay.researched; mnFuseBatchResearchedChanged += replay.changed;
+  return fused;
+}
+
+std::vector<int> ORBmatcher::FuseBatch(const std::vector<std::pair<KeyFrame*, Sophus::Sim3f>>& targets, const std::vector<MapPoint*>& vpPoints, float th,
+                                       std::vector<std::vector<MapPoint*>>& vvpReplacePoints, AfterTarget after) {
+  const int K = (int)targets.size(), nPoints = (int)vpPoints.size();
+  std::vector<int> fused(K, 0);
+  vvpReplacePoints.assign(K, std::vector<MapPoint*>(nPoints, static_cast<MapPoint*>(nullptr)));
+  FuseBatchPack pk;
+  pk.set_points(vpPoints);
+  for (const auto& t : targets) {
+    Sophus::SE3f Tcw;
+    Eigen::Vector3f Ow;
+    sim3_pose(t.second, Tcw, Ow);
+    pk.add_target(t.first, Tcw, Ow, t.first->mpCamera, th, false, false);
+  }
+  FuseBatchFound found;
+  if (!fuse_batch_search(pk, OSH_FUSE_SIM3, mbFuseBatchSearchOnHost, found)) {
+    for (int k = 0; k < K; ++k) {
+      Sophus::Sim3f Scw = targets[k].second;
+      fused[k] = Fuse(targets[k].first, Scw, vpPoints, th, vvpReplacePoints[k]);
+      if (after) after(k);
+    }
+    return fused;
+  }
+  FuseBatchReplay replay(pk, found, OSH_FUSE_SIM3, TH_LOW);
+  for (int k = 0; k < K; ++k) {
+    KeyFrame* pKF = targets[k].first;
+    const std::set<MapPoint*> spAlreadyFound = pKF->GetMapPoints();    // as found when this target's turn comes, as at Fuse's entry
+    std::vector<MapPoint*>& vpReplacePoint = vvpReplacePoints[k];
+    int nFused = 0;
+    for (int iMP = 0; iMP < nPoints; iMP++) {
+      MapPoint* pMP = vpPoints[iMP];
+      if (!pMP) continue;                                             // the reference dereferences a null entry here
+      if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;
+      int bestIdx, bestDist;
+      if (!replay.best_of(k, iMP, pMP, bestIdx, bestDist)) continue;
+      if (bestIdx >= 0 && bestDist <= TH_LOW) {
+        MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);
+        if (pMPinKF) {
+          if (!pMPinKF->isBad()) vpReplacePoint[iMP] = pMPinKF;
+        } else {
+          pMP->AddObservation(pKF, bestIdx);
+          pKF->AddMapPoint(pMP, bestIdx);
+        }
+        nFused++;
+      }
+    }
+    fused[k] = nFused;
+    if (after) after(k);
+    if (k + 1 < K) replay.mark_stale(vpPoints);
+  }
+  mnFuseBatchResearched += replay.researched; mnFuseBatchResearchedChanged += replay.changed;
+  return fused;
 }
 
 // src/ORBmatcher.cc:223-420.  The candidate loops of every keyframe feature run as batched device searches over the feature

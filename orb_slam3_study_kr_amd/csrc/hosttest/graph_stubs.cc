@@ -1,7 +1,11 @@
 // graph_stubs.cc -- bodies of the few KeyFrame / MapPoint / Frame methods of the minimal test doubles in include/
 // (a real ORB-SLAM3 tree supplies its own; only Optimizer.cc / ORBmatcher.cc are the drop-in).
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstdint>
+#include <utility>
+#include <vector>
 #include "Frame.h"
 #include "KeyFrame.h"
 #include "MapPoint.h"
@@ -9,6 +13,41 @@
 namespace ORB_SLAM3 {
 
 std::mutex MapPoint::mGlobalMutex;
+bool MapPoint::sbRecomputeDescriptors = false;
+
+// src/MapPoint.cc:329-403: the descriptor with the least median distance to the others, over the observations of keyframes that
+// are not bad, in map order; only when the test asked for it
+void MapPoint::ComputeDistinctiveDescriptors() {
+  ++mnDescriptorUpdates;
+  if (!sbRecomputeDescriptors || mbBad) return;
+  std::vector<std::pair<KeyFrame*, int>> rows;
+  for (const auto& ob : mObservations) {
+    KeyFrame* pKF = ob.first;
+    if (pKF->isBad()) continue;
+    const int leftIndex = std::get<0>(ob.second), rightIndex = std::get<1>(ob.second);
+    if (leftIndex != -1) rows.push_back(std::make_pair(pKF, leftIndex));
+    if (rightIndex != -1) rows.push_back(std::make_pair(pKF, rightIndex));
+  }
+  const size_t N = rows.size();
+  if (N == 0) return;
+  std::vector<int> dist(N * N, 0);
+  for (size_t i = 0; i < N; ++i)
+    for (size_t j = i + 1; j < N; ++j) {
+      const uint32_t* a = rows[i].first->mDescriptors.ptr<uint32_t>(rows[i].second);
+      const uint32_t* b = rows[j].first->mDescriptors.ptr<uint32_t>(rows[j].second);
+      int d = 0;
+      for (int k = 0; k < 8; ++k) d += __builtin_popcount(a[k] ^ b[k]);
+      dist[i * N + j] = dist[j * N + i] = d;
+    }
+  int BestMedian = INT_MAX, BestIdx = 0;
+  for (size_t i = 0; i < N; ++i) {
+    std::vector<int> vDists(dist.begin() + i * N, dist.begin() + (i + 1) * N);
+    std::sort(vDists.begin(), vDists.end());
+    const int median = vDists[(size_t)(0.5 * (N - 1))];
+    if (median < BestMedian) { BestMedian = median; BestIdx = (int)i; }
+  }
+  mDescriptor = rows[BestIdx].first->mDescriptors.row(rows[BestIdx].second).clone();
+}
 
 // src/KeyFrame.cc:109-122: cache Rcw, Twc and the IMU position Owb = Rwc * tcb + twc
 void KeyFrame::SetPose(const Sophus::SE3f& Tcw) {

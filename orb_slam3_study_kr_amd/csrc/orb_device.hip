@@ -11,6 +11,7 @@
 // Integer-VALU bound: per descriptor pair 8 v_xor_b32 + 8 v_bcnt_u32_b32 and
 // 4 select ops; the 32-byte train rows are staged in LDS and read as wave-wide broadcasts.
 #include "common.h"
+#include "orb_grid_bin.h"
 #include "orb_hamming.h"
 #include <algorithm>
 #include <cmath>
@@ -675,23 +676,11 @@ extern "C" int osh_orb_upload_grid(osh_orb_ctx* c, const osh_orb_batch* b, const
   const size_t nq = (size_t)b->n_pairs * b->n_query, nt = (size_t)b->n_pairs * b->n_train;
   const int ncell = g->cols * g->rows;
   // Frame::AssignFeaturesToGrid (src/Frame.cc:397-417): counting sort by cell, keypoint order inside a cell
-  std::vector<int> coff((size_t)b->n_pairs * (ncell + 1), 0), cidx(std::max<size_t>(nt, 1), 0), cell_of(std::max<size_t>(b->n_train, 1));
+  std::vector<int> coff((size_t)b->n_pairs * (ncell + 1), 0), cidx(std::max<size_t>(nt, 1), 0), cell_of, fill;
   for (int p = 0; p < b->n_pairs; ++p) {
-    int* off = &coff[(size_t)p * (ncell + 1)];
-    const float* xy = g->train_xy + (size_t)p * b->n_train * 2;
-    for (int i = 0; i < b->n_train; ++i) {
-      const int posX = (int)std::round((xy[2 * i] - g->min_x) * g->cell_w_inv);       // PosInGrid, src/Frame.cc:726-736
-      const int posY = (int)std::round((xy[2 * i + 1] - g->min_y) * g->cell_h_inv);
-      cell_of[i] = (posX < 0 || posX >= g->cols || posY < 0 || posY >= g->rows) ? -1 : posX * g->rows + posY;
-      if (cell_of[i] >= 0) off[cell_of[i] + 1]++;
-    }
-    for (int k = 0; k < ncell; ++k) {
-      if (off[k + 1] > 255) { set_error("pair %d: more than 255 keypoints in one grid cell", p); return OSH_ERR_UNSUPPORTED; }
-      off[k + 1] += off[k];
-    }
-    std::vector<int> fill(off, off + ncell);
-    int* ci = &cidx[(size_t)p * b->n_train];
-    for (int i = 0; i < b->n_train; ++i) if (cell_of[i] >= 0) ci[fill[cell_of[i]]++] = i;
+    const int most = bin_keypoints(g->train_xy + (size_t)p * b->n_train * 2, b->n_train, g->min_x, g->min_y, g->cell_w_inv, g->cell_h_inv, g->cols,
+                                   g->rows, 255, &coff[(size_t)p * (ncell + 1)], &cidx[(size_t)p * b->n_train], cell_of, fill);
+    if (most > 255) { set_error("pair %d: more than 255 keypoints in one grid cell", p); return OSH_ERR_UNSUPPORTED; }
   }
   auto up = [&](DevBuf& d, const void* src, size_t bytes) -> int {
     OSH_TRY(d.reserve(std::max<size_t>(bytes, 8)));

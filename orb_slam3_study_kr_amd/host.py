@@ -312,6 +312,81 @@ class HostGraph:
         mps = _i32(mps)
         return self.lib.osh_host_graph_fuse(self.g, int(kf), mps.shape[0], capi.ptr(mps, capi.c_int32_p), float(th), int(right))
 
+    def fuse_batch(self, targets, mps, cpu_search: bool = False):
+        """ORBmatcher::FuseBatch(targets, vpMapPoints): targets = [(keyframe, th, right)].  Returns the counts and (mnFuseBatchResearched, mnFuseBatchResearchedChanged)."""
+        mps, kf = _i32(mps), _i32([t[0] for t in targets])
+        th, right = _f32([t[1] for t in targets]), np.ascontiguousarray([t[2] for t in targets], dtype=np.uint8)
+        fused, researched = np.zeros(max(len(targets), 1), np.int32), np.zeros(2, np.int32)
+        rc = self.lib.osh_host_graph_fuse_batch(self.g, len(targets), capi.ptr(kf, capi.c_int32_p), capi.ptr(th, capi.c_float_p), capi.ptr(right, capi.c_uint8_p),
+                                                mps.shape[0], capi.ptr(mps, capi.c_int32_p), int(cpu_search), capi.ptr(fused, capi.c_int32_p), capi.ptr(researched, capi.c_int32_p))
+        assert rc == 0
+        return fused[:len(targets)].tolist(), (int(researched[0]), int(researched[1]))
+
+    def fuse_batch_sim3(self, targets, mps, th: float = 4.0, cpu_search: bool = False, replace_after: bool = False):
+        """The Sim3 overload: targets = [(keyframe, sim3 of 8 floats qw qx qy qz tx ty tz s)].  Returns the counts, the vpReplacePoint
+        lists [targets, points] as point indices and mnFuseBatchResearched."""
+        mps, kf = _i32(mps), _i32([t[0] for t in targets])
+        sim3 = _f32(np.array([t[1] for t in targets]).reshape(-1))
+        n_t, n = len(targets), mps.shape[0]
+        fused, replace, researched = np.zeros(max(n_t, 1), np.int32), np.full(max(n_t * n, 1), -1, np.int32), np.zeros(2, np.int32)
+        rc = self.lib.osh_host_graph_fuse_batch_sim3(self.g, n_t, capi.ptr(kf, capi.c_int32_p), capi.ptr(sim3, capi.c_float_p), n, capi.ptr(mps, capi.c_int32_p),
+                                                     float(th), int(cpu_search), int(replace_after), capi.ptr(fused, capi.c_int32_p),
+                                                     capi.ptr(replace, capi.c_int32_p), capi.ptr(researched, capi.c_int32_p))
+        assert rc == 0
+        return fused[:n_t].tolist(), replace[:n_t * n].reshape(n_t, n), (int(researched[0]), int(researched[1]))
+
+    def fuse_sim3(self, kf: int, sim3, mps, th: float = 4.0):
+        """One ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint): the count and the list as point indices."""
+        mps, s = _i32(mps), _f32(np.asarray(sim3))
+        replace = np.full(max(mps.shape[0], 1), -1, np.int32)
+        n = self.lib.osh_host_graph_fuse_sim3(self.g, int(kf), capi.ptr(s, capi.c_float_p), mps.shape[0], capi.ptr(mps, capi.c_int32_p), float(th),
+                                              capi.ptr(replace, capi.c_int32_p))
+        assert n >= 0
+        return n, replace[:mps.shape[0]]
+
+    def fuse_candidates(self, kf: int, mps, th: float = 3.0, right: bool = False, sim3=None):
+        """What one ORBmatcher::Fuse call decides per point before its device search: count [n] (-1: no query) and the candidate
+        lists, one per query in point order, as indices in the keyframe's own arrays."""
+        mps = _i32(mps)
+        s = None if sim3 is None else _f32(np.asarray(sim3))
+        count = np.zeros(max(mps.shape[0], 1), np.int32)
+        args = (self.g, int(kf), capi.ptr(s, capi.c_float_p), float(th), int(right), mps.shape[0], capi.ptr(mps, capi.c_int32_p), capi.ptr(count, capi.c_int32_p))
+        total = self.lib.osh_host_graph_fuse_candidates(*args, 0, C.cast(None, capi.c_int32_p))
+        assert total >= 0
+        cand = np.zeros(max(total, 1), np.int32)
+        assert self.lib.osh_host_graph_fuse_candidates(*args, total, capi.ptr(cand, capi.c_int32_p)) == total
+        count = count[:mps.shape[0]]
+        lists, at = [], 0
+        for c in count:
+            lists.append(None if c < 0 else cand[at:at + c].copy())
+            at += max(int(c), 0)
+        return count, lists
+
+    def fuse_pack_search(self, kf: int, mps, th: float = 3.0, right: bool = False, sim3=None, cpu_search: bool = False) -> dict:
+        """The same call as FuseBatch packs and searches it: stage, n_candidates, best_idx (keyframe's own arrays), best_dist [n]."""
+        mps = _i32(mps)
+        s = None if sim3 is None else _f32(np.asarray(sim3))
+        out = {k: np.zeros(max(mps.shape[0], 1), np.int32) for k in ("stage", "n_candidates", "best_idx", "best_dist")}
+        rc = self.lib.osh_host_graph_fuse_pack_search(self.g, int(kf), capi.ptr(s, capi.c_float_p), float(th), int(right), mps.shape[0],
+                                                      capi.ptr(mps, capi.c_int32_p), int(cpu_search), *[capi.ptr(v, capi.c_int32_p) for v in out.values()])
+        assert rc == 0, rc
+        return {k: v[:mps.shape[0]] for k, v in out.items()}
+
+    def replace(self, mp: int, by: int):
+        assert self.lib.osh_host_graph_replace(self.g, int(mp), int(by)) == 0
+
+    def loop_search_and_fuse(self, kfs, mps, sim3=None, cpu_search: bool = False):
+        """LoopClosing::SearchAndFuse: with sim3 [len(kfs), 8] the KeyFrameAndPose overload, else the keyframe-list one.  Returns the
+        order the keyframes were walked in, the replacements made and mnFuseBatchResearched."""
+        kfs, mps = _i32(kfs), _i32(mps)
+        s = None if sim3 is None else np.ascontiguousarray(np.asarray(sim3, np.float64).reshape(-1))
+        order, info = np.zeros(max(kfs.shape[0], 1), np.int32), np.zeros(3, np.int32)
+        rc = self.lib.osh_host_loop_search_and_fuse(self.g, int(s is not None), kfs.shape[0], capi.ptr(kfs, capi.c_int32_p), capi.ptr(s, capi.c_double_p),
+                                                    mps.shape[0], capi.ptr(mps, capi.c_int32_p), int(cpu_search), capi.ptr(order, capi.c_int32_p),
+                                                    capi.ptr(info, capi.c_int32_p))
+        assert rc == 0
+        return order[:kfs.shape[0]].tolist(), int(info[0]), (int(info[1]), int(info[2]))
+
     def set_covisible(self, kf: int, others):
         others = _i32(others)
         assert self.lib.osh_host_graph_set_covisible(self.g, int(kf), others.shape[0], capi.ptr(others, capi.c_int32_p)) == 0

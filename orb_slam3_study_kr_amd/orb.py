@@ -262,6 +262,15 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_refresh_map_points(self.ctx, len(batches), cb, cr), "osh_orb_refresh_map_points", self.lib)
         return outs
 
+    def fuse_search(self, targets, points, mode: int = capi.OSH_FUSE_CHI2, fill=None) -> dict:
+        """The search of ORBmatcher::Fuse (src/ORBmatcher.cc:1148-1455) for a list of synth_fuse.Target and one synth_fuse.Points in
+        one osh_orb_fuse_search call: stage, u, v, ur, level, radius, n_candidates, best_idx, best_dist, each [n_targets, n]."""
+        ct, cp, cr, _keep, out = fuse_args(targets, points, fill)
+        capi.check(self.lib.osh_orb_fuse_search(self.ctx, len(targets), ct, C.byref(cp), mode, C.byref(cr)), "osh_orb_fuse_search", self.lib)
+        return out
+
+    fuse_times = functools.partialmethod(_times, "osh_orb_fuse_get_times")                       # of the last fuse_search
+
     def keyframe_cull_stage(self, problem):
         """Uploads a synth_keyframe_cull.CullProblem (osh_orb_keyframe_cull_stage): it stays resident until the next stage call."""
         cp, _keep = kfcull_problem(problem)
@@ -1712,3 +1721,62 @@ def frustum_args(pos, normal, min_dist, max_dist):
         setattr(res, k, capi.ptr(outs[k], capi.c_float_p))
     res.level = capi.ptr(outs["level"], capi.c_int32_p)
     return (pts, pos, normal, min_dist, max_dist), res, outs
+
+
+_FUSE_OUTPUTS = (("stage", np.int32), ("u", np.float32), ("v", np.float32), ("ur", np.float32), ("level", np.int32), ("radius", np.float32),
+                 ("n_candidates", np.int32), ("best_idx", np.int32), ("best_dist", np.int32))
+
+
+def fuse_args(targets, points, fill=None):
+    """The osh_fuse_target array, osh_fuse_points and osh_fuse_result of OrbMatcher.fuse_search for repeated calls, the arrays that
+    keep their pointers alive and the dict of output arrays [n_targets, n]; fill = (int32 value, float32 value) presets them."""
+    ct = (capi.FuseTarget * max(len(targets), 1))()
+    keep = []
+    for c, t in zip(ct, targets):
+        sf, inv, log_sf = t.level_tables()
+        c.Rcw[:] = [float(x) for x in np.asarray(t.Rcw, np.float32).reshape(9)]
+        c.tcw[:] = [float(x) for x in np.asarray(t.tcw, np.float32)]
+        c.Ow[:] = [float(x) for x in np.asarray(t.Ow, np.float32)]
+        c.camera, c.fx, c.fy, c.cx, c.cy, c.bf = int(t.camera), t.fx, t.fy, t.cx, t.cy, t.bf
+        c.kb8[:] = [float(x) for x in t.kb8]
+        c.min_x, c.max_x, c.min_y, c.max_y = [float(x) for x in t.bounds]
+        c.grid_min_x, c.grid_min_y = [float(x) for x in t.grid_min]
+        c.cell_w_inv, c.cell_h_inv = [float(x) for x in t.cell_inv]
+        c.cols, c.rows, c.n_levels, c.log_scale_factor, c.th = int(t.cols), int(t.rows), int(t.n_levels), float(log_sf), float(t.th)
+        c.scale_factors[:len(sf)] = [float(x) for x in sf[:16]]
+        c.inv_level_sigma2[:len(inv)] = [float(x) for x in inv[:16]]
+        a = dict(key_xy=np.ascontiguousarray(t.key_xy, np.float32), key_octave=np.ascontiguousarray(t.key_octave, np.int32),
+                 descriptors=np.ascontiguousarray(t.desc, np.uint8))
+        if t.key_uright is not None:
+            a["key_uright"] = np.ascontiguousarray(t.key_uright, np.float32)
+        c.n_keys = int(a["key_octave"].shape[0])
+        for name, arr in a.items():
+            setattr(c, name, capi.ptr(arr, _POINTER[arr.dtype]))
+        keep.append(a)
+    cp = capi.FusePoints()
+    a = dict(pos=np.ascontiguousarray(points.pos, np.float32), normal=np.ascontiguousarray(points.normal, np.float32),
+             min_dist=np.ascontiguousarray(points.min_dist, np.float32), max_dist=np.ascontiguousarray(points.max_dist, np.float32),
+             desc=np.ascontiguousarray(points.desc, np.uint8))
+    if points.skip is not None:
+        a["skip"] = np.ascontiguousarray(points.skip, np.uint8)
+    cp.n = int(a["min_dist"].shape[0])
+    for name, arr in a.items():
+        setattr(cp, name, capi.ptr(arr, _POINTER[arr.dtype]))
+    keep.append(a)
+    ifill, ffill = (0, 0.0) if fill is None else fill
+    out = {name: np.full((len(targets), cp.n), ifill if dt is np.int32 else ffill, dt) for name, dt in _FUSE_OUTPUTS}
+    cr = capi.FuseResult()
+    _wire_outputs(cr, out)
+    return ct, cp, cr, keep, out
+
+
+def fuse_cpu(targets, points, mode: int = capi.OSH_FUSE_CHI2, host_lib=None):
+    """csrc/orb_fuse.h on the host in one thread (osh_host_fuse_search_cpu of the test library): the output dict of fuse_search and
+    the wall time of the call in ms."""
+    host_lib = host_lib or capi.load_host_library()
+    ct, cp, cr, _keep, out = fuse_args(targets, points)
+    ms = C.c_double(0)
+    rc = host_lib.osh_host_fuse_search_cpu(len(targets), ct, C.byref(cp), mode, C.byref(cr), C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_fuse_search_cpu -> {rc}")
+    return out, float(ms.value)
