@@ -32,6 +32,17 @@ class Frame {
   int isInFrustum(const std::vector<MapPoint*>& vpMPs, float viewingCosLimit, std::vector<bool>& vbInView);
   // src/Frame.cc:816-986 on the device: fills mvuRight / mvDepth (all -1 with a message on stderr on a device error)
   void ComputeStereoMatches();
+  // ADD THIS MEMBER: what the stereo constructor's two ExtractORB threads followed by ComputeStereoMatches do (src/Frame.cc:118-141)
+  // as ONE osh_orb_extract_stereo on the thread's context: the two images go up, mvKeys / mvKeysRight / mDescriptors /
+  // mDescriptorsRight (level-0 pixels, result order: the lapping area is the rectified constructor's {0, 0}), N, mvuRight and
+  // mvDepth come back, and no pyramid and no keypoint array crosses to the host in between.  With the preps null the images are
+  // grey (ExtractBatch's form), else raw (ExtractBatchRaw's form: remapped or resized and turned grey on the device; both preps or
+  // none).  Both extractors' mnPyramidToken name their levels on the device; mvImagePyramid is left with empty levels.  *pvGray
+  // (may be null) receives the prepared grey images of the raw form; they come down as level 0 of the bordered levels, so a caller
+  // that asks for them pays the pyramid download.  A device error, a refused call or a missing context: a message on stderr, no
+  // keypoints, N = 0, mvuRight and mvDepth empty
+  void ExtractAndMatchStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const ImagePrep* pPrepLeft = nullptr, const ImagePrep* pPrepRight = nullptr,
+                             std::vector<cv::Mat>* pvGray = nullptr);
   // src/Frame.cc:1131-1171 on the device: fills mvLeftToRightMatch / mvRightToLeftMatch / mvDepth / mvStereo3Dpoints of a
   // KannalaBrandt8 rig frame.  A device error, a camera pair that is not CAM_FISHEYE or members that do not fit together: a
   // message on stderr and every keypoint unmatched (all -1)

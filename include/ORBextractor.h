@@ -49,11 +49,20 @@ class ORBextractor {
                               const std::vector<ImagePrep>& vPrep, std::vector<std::vector<cv::KeyPoint> >& vKeypoints,
                               std::vector<cv::Mat>& vDescriptors, const std::vector<std::vector<int> >& vLappingAreas,
                               std::vector<int>& vMonoIndex, bool bKeepPyramid = true, std::vector<cv::Mat>* pvGray = nullptr);
-  /* ADD THIS MEMBER too: the body of the two (pvPrep null: ExtractBatch) */
+  /* ADD THIS TYPE too: the stereo match that Frame::ExtractAndMatchStereo asks ExtractBatchFrom to run behind the extraction of
+   * a left and a right image (osh_orb_extract_stereo, csrc/stereo_device.hip).  bOk: the call ran and both results fit; vuRight
+   * and vDepth then hold one entry per left keypoint, in the order of vKeypoints[0] */
+  struct StereoMatch {
+    float bf = 0, b = 0;
+    std::vector<float> vuRight, vDepth;
+    bool bOk = false;
+  };
+  /* ADD THIS MEMBER too: the body of the two (pvPrep null: ExtractBatch).  pStereo (may be null): the call has exactly two
+   * extractors with an image each, the left one first, and runs as ONE osh_orb_extract_stereo */
   static void ExtractBatchFrom(const char* who, const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
                                const std::vector<ImagePrep>* pvPrep, std::vector<std::vector<cv::KeyPoint> >& vKeypoints,
                                std::vector<cv::Mat>& vDescriptors, const std::vector<std::vector<int> >& vLappingAreas,
-                               std::vector<int>& vMonoIndex, bool bKeepPyramid, std::vector<cv::Mat>* pvGray);
+                               std::vector<int>& vMonoIndex, bool bKeepPyramid, std::vector<cv::Mat>* pvGray, StereoMatch* pStereo = nullptr);
 
   std::vector<cv::Point> pattern;   /* the 512 sampling points, filled by the constructor */
 

@@ -804,6 +804,37 @@ int osh_orb_stereo_match(osh_orb_ctx* ctx, int32_t n_frames, const osh_stereo_fr
 /* With osh_orb_set_profiling on, the last osh_orb_stereo_match is synchronised between its phases and their host-clock times (ms) are
  * kept: ms[0] validation + staging (pyramid rows into pinned memory), ms[1] upload, ms[2] kernels, ms[3] download + write-back. */
 int osh_orb_stereo_get_times(osh_orb_ctx* ctx, double ms[4]);
+/*
+ * osh_orb_stereo_match on pyramids that are already on the device: left_token / right_token name two frames of the context's
+ * resident pyramid (from osh_orb_pyramid_build, osh_orb_extract or osh_orb_extract_raw on the same context).  Keypoints and
+ * descriptors come from the host; the pixels are read where they lie, so nothing is staged or uploaded but the keypoints.  The SAD
+ * window and the median cut are the same kernels, the descriptor search walks per-row candidate lists built on the device
+ * (osh_orb_stereo_set_row_search below), and every output equals osh_orb_stereo_match on the downloaded levels bit for bit.  The
+ * resident pyramid is only read.
+ * Refused with OSH_ERR_INVALID before any device work, the resident pyramid staying as it was: everything osh_orb_stereo_match
+ * refuses of the keypoints, bf and b (without a context), a token that names no frame of this context's resident pyramid, two
+ * tokens whose frames differ in n_levels or whose n_levels is not the frame's.  osh_orb_stereo_get_times gives its phases.
+ */
+typedef struct osh_stereo_resident_frame {
+  int32_t n_left, n_right;
+  const float* left_xy;            /* as osh_stereo_frame                                                   */
+  const int32_t* left_octave;
+  const uint8_t* left_desc;
+  const float* right_xy;
+  const int32_t* right_octave;
+  const uint8_t* right_desc;
+  int32_t n_levels;
+  const float* scale_factors;
+  const float* inv_scale_factors;
+  uint64_t left_token, right_token;   /* the frames of the resident pyramid that hold the two pyramids      */
+  float bf, b;
+} osh_stereo_resident_frame;
+int osh_orb_stereo_match_resident(osh_orb_ctx* ctx, int32_t n_frames, const osh_stereo_resident_frame* frames, const osh_stereo_result* results);
+/* The descriptor search of osh_orb_stereo_match_resident and osh_orb_extract_stereo on this context: enable != 0 (the default) the
+ * row lists (the reference's vRowIndices built on the device, one wavefront per left keypoint on the list of its row), 0 the
+ * k_stereo_hamming of osh_orb_stereo_match.  Both give the same bits; the switch exists to measure one against the other.  A batch
+ * with more than 2^24 rows or room for more than 2^26 list entries runs k_stereo_hamming whatever the switch says. */
+int osh_orb_stereo_set_row_search(osh_orb_ctx* ctx, int32_t enable);
 
 /* ------------------------------------------------- fisheye stereo matching */
 /*
@@ -1747,6 +1778,34 @@ int osh_orb_extract_raw(osh_orb_ctx* ctx, int32_t n_frames, const osh_prepare_fr
  * images, ms[1] upload, ms[2] kernels, ms[3] download + the scatter of the rows.  osh_orb_extract_raw fills the times of
  * osh_orb_extract_get_times instead, the preparation counted into ms[0]. */
 int osh_orb_prepare_get_times(osh_orb_ctx* ctx, double ms[4]);
+
+/* ------------------------------------------------- a rectified stereo frame in one call */
+/*
+ * The stereo constructor's two ExtractORB threads and ComputeStereoMatches (src/Frame.cc:118-141) for n_pairs rectified pairs in
+ * ONE call: an osh_orb_extract (prepare_frames NULL) or osh_orb_extract_raw of the 2 * n_pairs images, pair p's left image as
+ * frame 2p and its right image as frame 2p + 1, followed on the same stream by the stereo match of every pair.  The kept keypoints
+ * are scaled to level 0 on the device (src/ORBextractor.cc:1143-1150: pt *= scale[level] for level != 0, one float32 multiply per
+ * coordinate) and matched where they lie, their descriptors where the descriptor kernel left them, against the pair's levels in
+ * the resident pyramid: no pyramid and no keypoint array crosses to the host in between, and one download brings everything.
+ * The scale factors of the match are extract_frames[2p].scale and .inv_scale.
+ *
+ * extract_results[k] is filled as by osh_orb_extract(_raw), bit for bit (keypoints in the pixels of their level).  stereo_results[p]
+ * is what osh_orb_stereo_match gives on those keypoints scaled as above and the downloaded levels, bit for bit; left keypoint i is
+ * keypoint i of extract_results[2p] and best_right indexes extract_results[2p + 1].  When either frame of a pair has
+ * n_out > capacity, that frame's arrays and the pair's stereo arrays are not written, and the call still returns OSH_OK.
+ *
+ * Refused before any device work, besides what osh_orb_extract(_raw) refuses: a NULL pairs or stereo_results, b <= 0 or a
+ * non-finite bf / b, the two frames of a pair with different n_levels, a NULL u_right or depth with a positive left capacity
+ * (OSH_ERR_INVALID); more than 32767 pairs (OSH_ERR_UNSUPPORTED).
+ */
+typedef struct osh_stereo_pair {
+  float bf, b;                       /* mbf, mb                                                                             */
+} osh_stereo_pair;
+int osh_orb_extract_stereo(osh_orb_ctx* ctx, int32_t n_pairs, const osh_prepare_frame* prepare_frames, const osh_extract_frame* extract_frames,
+                           const osh_stereo_pair* pairs, osh_extract_result* extract_results, const osh_stereo_result* stereo_results);
+/* Host-clock times (ms) of the last osh_orb_extract_stereo under osh_orb_set_profiling: ms[0..3] the phases of
+ * osh_orb_extract_get_times without the stereo tail, ms[4] the stereo tail (scaling, search, SAD window, median cut). */
+int osh_orb_extract_stereo_get_times(osh_orb_ctx* ctx, double ms[5]);
 
 /* ------------------------------------------------- bag-of-words transform */
 /*

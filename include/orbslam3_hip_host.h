@@ -782,6 +782,22 @@ int osh_host_orbextractor_extract_batch_raw(int32_t n, const struct osh_host_ext
                                             const struct osh_host_extract_output* out, int32_t keep_pyramid, uint64_t* tokens,
                                             uint8_t* const* gray, const int32_t* gray_capacity, int32_t* gray_rows, int32_t* gray_cols);
 
+/* Frame::ExtractAndMatchStereo of a stand-in Frame (mbf = bf, mb = b, the scale factors of the left extractor) whose left and right
+ * extractors are made from in[0] and in[1] as osh_host_orbextractor_extract_batch makes them.  raw NULL: the grey form on the images
+ * of in[0] / in[1]; else the raw form on raw[0] / raw[1], each with an ImagePrep (and RectifyMap) of its own as
+ * osh_host_orbextractor_extract_batch_raw makes them.  chain != 0: the same frame through the two calls the member replaces,
+ * ExtractBatch or ExtractBatchRaw with bKeepPyramid = true and the lapping areas {0, 0}, then ComputeStereoMatches.  out[0] / out[1]
+ * receive mvKeys / mDescriptors and mvKeysRight / mDescriptorsRight with the extractors' pyramids (ret = 0), tokens[0..1] the
+ * extractors' mnPyramidToken, n[0..3] = N, mvuRight.size(), mvDepth.size(), mvKeysRight.size(), u_right / depth [u_capacity]
+ * mvuRight / mvDepth when they fit, gray .. gray_cols (may be NULL; raw form only) the images of pvGray as
+ * osh_host_orbextractor_extract_batch_raw returns them, *call_ms (may be NULL) the wall time of the member calls alone.  Before the
+ * call the frame holds three keypoints, mvuRight and mvDepth of three sevens: what the member must replace.  Returns 0.
+ * -1: bad arguments or descriptors that do not fit the keypoints. */
+int osh_host_frame_extract_and_match_stereo(const struct osh_host_extract_input* in, const osh_host_raw_image* raw, float bf, float b, int32_t chain,
+                                            const struct osh_host_extract_output* out, uint64_t* tokens, int32_t u_capacity, float* u_right, float* depth,
+                                            int32_t* n, uint8_t* const* gray, const int32_t* gray_capacity, int32_t* gray_rows, int32_t* gray_cols,
+                                            double* call_ms);
+
 /* ---- ORBVocabulary / ComputeBoW (include/ORBVocabulary.h, csrc/host/ORBVocabulary.cc, csrc/hosttest/bow.cc) ---- */
 struct osh_bow_tree;
 struct osh_bow_result;

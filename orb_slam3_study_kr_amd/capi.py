@@ -293,6 +293,25 @@ class StereoResult(C.Structure):
                 ("sad", c_int32_p), ("best_inc", c_int32_p), ("stage", c_uint8_p)]
 
 
+class StereoResidentFrame(C.Structure):
+    """``osh_stereo_resident_frame`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [
+        ("n_left", C.c_int32), ("n_right", C.c_int32),
+        ("left_xy", c_float_p), ("left_octave", c_int32_p), ("left_desc", c_uint8_p),
+        ("right_xy", c_float_p), ("right_octave", c_int32_p), ("right_desc", c_uint8_p),
+        ("n_levels", C.c_int32), ("scale_factors", c_float_p), ("inv_scale_factors", c_float_p),
+        ("left_token", C.c_uint64), ("right_token", C.c_uint64),
+        ("bf", C.c_float), ("b", C.c_float),
+    ]
+
+
+class StereoPair(C.Structure):
+    """``osh_stereo_pair`` (include/orbslam3_hip.h)."""
+
+    _fields_ = [("bf", C.c_float), ("b", C.c_float)]
+
+
 OSH_STEREO_MAX_LEVELS = 16
 OSH_STEREO_NO_INC = -128
 (OSH_STEREO_NO_CANDIDATE, OSH_STEREO_HAMMING, OSH_STEREO_RIGHT_GUARD, OSH_STEREO_PATCH, OSH_STEREO_BORDER_INC, OSH_STEREO_DELTA,
@@ -773,6 +792,8 @@ _SIGNATURES = {
     "osh_orb_distance_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, c_int32_p]),
     "osh_orb_stereo_match": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(StereoFrame), C.POINTER(StereoResult)]),
     "osh_orb_stereo_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_stereo_set_row_search": (C.c_int, [C.c_void_p, C.c_int32]),
+    "osh_orb_stereo_match_resident": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(StereoResidentFrame), C.POINTER(StereoResult)]),
     "osh_orb_fisheye_stereo_match": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FisheyeStereoFrame), C.POINTER(FisheyeStereoResult)]),
     "osh_orb_fisheye_stereo_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_kb8_triangulate": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Kb8Rig)] + [c_float_p] * 7),
@@ -812,6 +833,9 @@ _SIGNATURES = {
     "osh_orb_extract_raw": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(PrepareFrame), C.POINTER(ExtractFrame), C.POINTER(ExtractResult),
                                       C.POINTER(PrepareResult)]),
     "osh_orb_prepare_get_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "osh_orb_extract_stereo": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(PrepareFrame), C.POINTER(ExtractFrame), C.POINTER(StereoPair),
+                                         C.POINTER(ExtractResult), C.POINTER(StereoResult)]),
+    "osh_orb_extract_stereo_get_times": (C.c_int, [C.c_void_p, c_double_p]),
     "osh_bow_tree_check": (C.c_int, [C.POINTER(BowTree)]),
     "osh_bow_vocab_create": (C.c_int, [C.c_int, C.POINTER(BowTree), C.POINTER(C.c_void_p)]),
     "osh_bow_vocab_destroy": (None, [C.c_void_p]),
@@ -948,6 +972,9 @@ _HOST_SIGNATURES = {
     "osh_host_orbextractor_extract": (C.c_int, [C.POINTER(HostExtractInput), C.POINTER(HostExtractOutput)]),
     "osh_host_orbextractor_extract_batch": (C.c_int, [C.c_int32, C.POINTER(HostExtractInput), C.POINTER(HostExtractOutput), C.c_int32,
                                                       C.POINTER(C.c_uint64)]),
+    "osh_host_frame_extract_and_match_stereo": (C.c_int, [C.POINTER(HostExtractInput), C.POINTER(HostRawImage), C.c_float, C.c_float, C.c_int32,
+                                                          C.POINTER(HostExtractOutput), C.POINTER(C.c_uint64), C.c_int32, c_float_p, c_float_p,
+                                                          c_int32_p, C.POINTER(c_uint8_p), c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_double)]),
     "osh_host_orbextractor_extract_batch_raw": (C.c_int, [C.c_int32, C.POINTER(HostExtractInput), C.POINTER(HostRawImage),
                                                           C.POINTER(HostExtractOutput), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(c_uint8_p),
                                                           c_int32_p, c_int32_p, c_int32_p]),

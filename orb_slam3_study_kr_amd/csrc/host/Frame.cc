@@ -126,6 +126,40 @@ void Frame::ComputeStereoMatches() {
   mvDepth.swap(depth);
 }
 
+void Frame::ExtractAndMatchStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const ImagePrep* pPrepLeft, const ImagePrep* pPrepRight,
+                                  std::vector<cv::Mat>* pvGray) {
+  mvKeys.clear(); mvKeysRight.clear();
+  mDescriptors.release(); mDescriptorsRight.release();
+  mvuRight.clear(); mvDepth.clear();
+  N = 0;
+  if (pvGray) pvGray->clear();
+  if (!mpORBextractorLeft || !mpORBextractorRight || (pPrepLeft == nullptr) != (pPrepRight == nullptr)) {
+    std::fprintf(stderr, "Frame::ExtractAndMatchStereo: two extractors and an ImagePrep for both images or for none\n");
+    return;
+  }
+  // the packing, the call and the write-back are ExtractBatchFrom's, with the match of the pair behind the two extractions
+  const std::vector<ORBextractor*> extractors{mpORBextractorLeft, mpORBextractorRight};
+  const std::vector<cv::Mat> images{imLeft, imRight};
+  std::vector<ImagePrep> prep;
+  if (pPrepLeft) prep = {*pPrepLeft, *pPrepRight};
+  std::vector<std::vector<cv::KeyPoint> > keys;
+  std::vector<cv::Mat> descriptors;
+  const std::vector<std::vector<int> > lapping(2, std::vector<int>{0, 0});   // :118-119
+  std::vector<int> mono;
+  ORBextractor::StereoMatch stereo;
+  stereo.bf = mbf; stereo.b = mb;
+  ORBextractor::ExtractBatchFrom("ExtractAndMatchStereo", extractors, images, pPrepLeft ? &prep : nullptr, keys, descriptors, lapping, mono, false, pvGray, &stereo);
+  if (!stereo.bOk || keys.size() != 2 || descriptors.size() != 2 || stereo.vuRight.size() != keys[0].size()) {
+    if (pvGray) pvGray->clear();
+    return;   // ExtractBatchFrom has said why
+  }
+  mvKeys.swap(keys[0]); mvKeysRight.swap(keys[1]);
+  mDescriptors = descriptors[0]; mDescriptorsRight = descriptors[1];
+  N = (int)mvKeys.size();                     // :132
+  mvuRight.swap(stereo.vuRight);
+  mvDepth.swap(stereo.vDepth);
+}
+
 void Frame::ComputeStereoFishEyeMatches() {
   const size_t nl = mvKeys.size(), nr = mvKeysRight.size();
   mvLeftToRightMatch = std::vector<int>(nl, -1);   // :1139-1144; the state in which every keypoint is unmatched

@@ -283,8 +283,9 @@ void ORBextractor::ExtractBatchRaw(const std::vector<ORBextractor*>& vpExtractor
 void ORBextractor::ExtractBatchFrom(const char* who, const std::vector<ORBextractor*>& vpExtractors, const std::vector<cv::Mat>& vImages,
                                     const std::vector<ImagePrep>* pvPrep, std::vector<std::vector<cv::KeyPoint> >& vKeypoints,
                                     std::vector<cv::Mat>& vDescriptors, const std::vector<std::vector<int> >& vLappingAreas,
-                                    std::vector<int>& vMonoIndex, bool bKeepPyramid, std::vector<cv::Mat>* pvGray) {
+                                    std::vector<int>& vMonoIndex, bool bKeepPyramid, std::vector<cv::Mat>* pvGray, StereoMatch* pStereo) {
   const size_t nExtractors = vpExtractors.size();
+  if (pStereo) { pStereo->bOk = false; pStereo->vuRight.clear(); pStereo->vDepth.clear(); }
   vKeypoints.resize(nExtractors);
   vDescriptors.resize(nExtractors);
   vMonoIndex.assign(nExtractors, 0);
@@ -308,6 +309,10 @@ void ORBextractor::ExtractBatchFrom(const char* who, const std::vector<ORBextrac
   };
   std::vector<Job> jobs;
   bool ok = true;
+  // osh_orb_extract_stereo hands no prepared image back: a caller that keeps the grey images gets them as the level 0 of the
+  // downloaded levels, and pays for that download
+  const bool bGrayFromLevels = pStereo && pvPrep && pvGray;
+  const bool bLevels = bKeepPyramid || bGrayFromLevels;
   for (size_t i = 0; i < nExtractors; ++i) {
     ORBextractor* ex = vpExtractors[i];
     if (vImages[i].empty()) { vMonoIndex[i] = -1; continue; }   // operator() returns before it touches anything
@@ -337,12 +342,16 @@ void ORBextractor::ExtractBatchFrom(const char* who, const std::vector<ORBextrac
     for (int l = 0; l < nl; ++l) capacity += (size_t)std::max(std::max(ex->mnFeaturesPerLevel[l], 0) + 3, 4 * OSH_OCTREE_MAX_ROOTS);
     j.levelCount.resize(nl); j.level.resize(capacity); j.xy.resize(capacity * 2); j.response.resize(capacity); j.angle.resize(capacity);
     j.size.resize(capacity); j.desc.resize(capacity * 32);
-    if (bKeepPyramid) {   // the levels as ComputePyramid leaves them
+    if (bLevels) {   // the levels as ComputePyramid leaves them
       const int bad = BorderedLevels(j.rows, j.cols, ex->mvInvScaleFactor, nl, j.levels, j.out);
       if (bad < nl) { std::fprintf(stderr, "ORBextractor::%s: extractor %d: level %d has no pixels or too many\n", who, (int)i, bad); ok = false; }
     }
   }
   if (!ok) std::fprintf(stderr, "ORBextractor::%s: nothing extracted\n", who);
+  if (ok && pStereo && (nExtractors != 2 || jobs.size() != 2)) {
+    std::fprintf(stderr, "ORBextractor::%s: a stereo frame is two extractors with an image each, not %d with %d\n", who, (int)nExtractors, (int)jobs.size());
+    return;
+  }
   if (!ok || jobs.empty()) return;
   osh_orb_ctx* ctx = Context(who);
   if (!ctx) return;
@@ -377,11 +386,30 @@ void ORBextractor::ExtractBatchFrom(const char* who, const std::vector<ORBextrac
     r = osh_extract_result{};
     r.capacity = (int32_t)j.response.size(); r.level_count = j.levelCount.data(); r.xy = j.xy.data(); r.level = j.level.data();
     r.response = j.response.data(); r.angle = j.angle.data(); r.size = j.size.data(); r.descriptors = j.desc.data();
-    r.levels = bKeepPyramid ? j.out.data() : nullptr; r.border = kEdge;
+    r.levels = bLevels ? j.out.data() : nullptr; r.border = kEdge;
   }
-  const int rc = pvPrep ? osh_orb_extract_raw(ctx, (int32_t)jobs.size(), rawFrames.data(), frames.data(), results.data(), rawResults.data())
-                        : osh_orb_extract(ctx, (int32_t)jobs.size(), frames.data(), results.data());
-  if (rc != OSH_OK) return Report(who);
+  int rc;
+  if (pStereo) {   // the two extractions and the match of the left keypoints against the right ones in one call
+    pStereo->vuRight.resize(jobs[0].response.size()); pStereo->vDepth.resize(jobs[0].response.size());
+    const osh_stereo_pair pair{pStereo->bf, pStereo->b};
+    const osh_stereo_result matched{pStereo->vuRight.data(), pStereo->vDepth.data(), nullptr, nullptr, nullptr, nullptr, nullptr};
+    rc = osh_orb_extract_stereo(ctx, 1, pvPrep ? rawFrames.data() : nullptr, frames.data(), &pair, results.data(), &matched);
+    for (size_t k = 0; rc == OSH_OK && bGrayFromLevels && k < jobs.size(); ++k) {
+      Job& j = jobs[k];
+      for (int r = 0; !j.gray.empty() && !j.levels.empty() && r < j.rows; ++r) std::memcpy(j.gray.ptr<uint8_t>(r), j.levels[0].ptr<uint8_t>(r), (size_t)j.cols);
+    }
+  } else {
+    rc = pvPrep ? osh_orb_extract_raw(ctx, (int32_t)jobs.size(), rawFrames.data(), frames.data(), results.data(), rawResults.data())
+                : osh_orb_extract(ctx, (int32_t)jobs.size(), frames.data(), results.data());
+  }
+  if (rc != OSH_OK) {
+    if (pStereo) { pStereo->vuRight.clear(); pStereo->vDepth.clear(); }
+    return Report(who);
+  }
+  if (pStereo) {
+    pStereo->bOk = results[0].n_out <= results[0].capacity && results[1].n_out <= results[1].capacity;
+    pStereo->vuRight.resize(pStereo->bOk ? (size_t)results[0].n_out : 0); pStereo->vDepth.resize(pStereo->vuRight.size());
+  }
   for (size_t k = 0; k < jobs.size(); ++k) {
     const Job& j = jobs[k];
     ORBextractor* ex = vpExtractors[j.extractor];

@@ -9,6 +9,7 @@
 #include <memory>
 #include <vector>
 
+#include "Frame.h"
 #include "ORBextractor.h"
 #include "RectifyMap.h"
 #include "orbextractor_io.h"
@@ -75,6 +76,87 @@ extern "C" int osh_host_orbextractor_extract_batch_raw(int32_t n, const osh_host
     }
     if (mono[i] < 0) continue;   // an empty image: the extractor's outputs were not touched
     if (!PutKeypoints(keys[i], desc[i], o)) return -1;
+  }
+  return 0;
+}
+
+extern "C" int osh_host_frame_extract_and_match_stereo(const osh_host_extract_input* in, const osh_host_raw_image* raw, float bf, float b, int32_t chain,
+                                                       const osh_host_extract_output* out, uint64_t* tokens, int32_t u_capacity, float* u_right, float* depth,
+                                                       int32_t* n, uint8_t* const* gray, const int32_t* gray_capacity, int32_t* gray_rows, int32_t* gray_cols,
+                                                       double* call_ms) {
+  if (!in || !out || !tokens || !n || u_capacity < 0 || (u_capacity && (!u_right || !depth)) || (gray && (!raw || !gray_capacity || !gray_rows || !gray_cols))) return -1;
+  std::vector<Standin> standins;
+  standins.reserve(2);   // the extractors stay where they are
+  std::vector<cv::Mat> images;
+  std::vector<std::unique_ptr<RectifyMap> > maps;
+  std::vector<ImagePrep> prep;
+  for (int i = 0; i < 2; ++i) {
+    const osh_host_extract_output& o = out[i];
+    if (in[i].nlevels < 1 || in[i].rows < 0 || in[i].cols < 0 || (!raw && in[i].rows && in[i].cols && !in[i].pixels) || !o.level_rows || !o.level_cols || !o.ret ||
+        !o.desc_rows || !o.pixels_needed || o.capacity < 0 || o.pixel_capacity < 0) return -1;
+    osh_host_extract_input extractor = in[i];
+    if (raw) extractor.rows = extractor.cols = 0;   // the stand-in's own image stays empty
+    standins.emplace_back(extractor);
+    if (!raw) { images.push_back(standins.back().image); continue; }
+    const osh_host_raw_image& a = raw[i];
+    if (a.rows < 0 || a.cols < 0 || a.channels < 1 || (a.rows && a.cols && !a.pixels) || (a.map_x && (!a.map_y || a.map_rows <= 0 || a.map_cols <= 0))) return -1;
+    cv::Mat image;
+    if (a.rows && a.cols) {
+      image = cv::Mat(a.rows, a.cols, a.channels);
+      std::memcpy(image.ptr<uint8_t>(0), a.pixels, (size_t)a.rows * a.cols * a.channels);
+    }
+    images.push_back(image);
+    ImagePrep p;
+    p.bRGB = a.rgb != 0; p.newRows = a.new_rows; p.newCols = a.new_cols;
+    if (a.map_x) {
+      const size_t step = sizeof(float) * (size_t)a.map_cols;
+      maps.emplace_back(new RectifyMap(a.map_x, step, a.map_y, step, a.map_rows, a.map_cols, a.rows, a.cols));
+      p.pMap = maps.back().get();
+    }
+    prep.push_back(p);
+  }
+  Frame F;
+  F.mpORBextractorLeft = &standins[0].ex; F.mpORBextractorRight = &standins[1].ex;
+  F.mbf = bf; F.mb = b;
+  F.mvScaleFactors = standins[0].ex.mvScaleFactor; F.mvInvScaleFactors = standins[0].ex.mvInvScaleFactor;
+  F.mvKeys.resize(3); F.mvKeysRight.resize(3); F.mvuRight.assign(3, 7.f); F.mvDepth.assign(3, 7.f); F.N = 3;   // what the call must replace
+  std::vector<cv::Mat> grays(1, cv::Mat(2, 2));
+  const auto t0 = std::chrono::steady_clock::now();
+  if (chain) {   // the two calls the member replaces
+    const std::vector<ORBextractor*> extractors{F.mpORBextractorLeft, F.mpORBextractorRight};
+    const std::vector<std::vector<int> > lapping(2, std::vector<int>{0, 0});
+    std::vector<std::vector<cv::KeyPoint> > keys;
+    std::vector<cv::Mat> desc;
+    std::vector<int> mono;
+    if (raw) ORBextractor::ExtractBatchRaw(extractors, images, prep, keys, desc, lapping, mono, true, gray ? &grays : nullptr);
+    else ORBextractor::ExtractBatch(extractors, images, keys, desc, lapping, mono, true);
+    if (keys.size() != 2 || desc.size() != 2) return -1;
+    F.mvKeys.swap(keys[0]); F.mvKeysRight.swap(keys[1]); F.mDescriptors = desc[0]; F.mDescriptorsRight = desc[1];   // as the member does
+    F.N = (int)F.mvKeys.size();
+    F.ComputeStereoMatches();
+  } else {
+    F.ExtractAndMatchStereo(images[0], images[1], raw ? &prep[0] : nullptr, raw ? &prep[1] : nullptr, gray ? &grays : nullptr);
+  }
+  if (call_ms) *call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  n[0] = F.N; n[1] = (int32_t)F.mvuRight.size(); n[2] = (int32_t)F.mvDepth.size(); n[3] = (int32_t)F.mvKeysRight.size();
+  if (F.mvuRight.size() <= (size_t)u_capacity && F.mvDepth.size() <= (size_t)u_capacity) {
+    if (!F.mvuRight.empty()) std::memcpy(u_right, F.mvuRight.data(), sizeof(float) * F.mvuRight.size());
+    if (!F.mvDepth.empty()) std::memcpy(depth, F.mvDepth.data(), sizeof(float) * F.mvDepth.size());
+  }
+  const std::vector<cv::KeyPoint>* keys[2] = {&F.mvKeys, &F.mvKeysRight};
+  const cv::Mat* desc[2] = {&F.mDescriptors, &F.mDescriptorsRight};
+  for (int i = 0; i < 2; ++i) {
+    const osh_host_extract_output& o = out[i];
+    *o.ret = 0; *o.desc_rows = desc[i]->rows;
+    tokens[i] = standins[i].ex.mnPyramidToken;
+    PutPyramid(standins[i].ex, in[i].nlevels, o);
+    if (gray) {
+      const cv::Mat g = (size_t)i < grays.size() ? grays[i] : cv::Mat();
+      gray_rows[i] = g.rows; gray_cols[i] = g.cols;
+      if (gray[i] && (size_t)g.rows * g.cols <= (size_t)gray_capacity[i])
+        for (int r = 0; r < g.rows; ++r) std::memcpy(gray[i] + (size_t)r * g.cols, g.ptr<uint8_t>(r), (size_t)g.cols);
+    }
+    if (!PutKeypoints(*keys[i], *desc[i], o)) return -1;
   }
   return 0;
 }

@@ -3,7 +3,8 @@
 // go through it: fast_emit (orb_fast_device.hip) leaves the candidates where k_fast_emit wrote them, octree_run
 // (orb_octree_device.hip) reads candidates and leaves the kept indices on the device, ic_angle_launch and brief_launch
 // (orb_fast_device.hip, orb_brief_device.hip) read keypoint arrays on the device.  The stage entries stage host arrays into those
-// forms and download what they leave; the fused call chains them.
+// forms and download what they leave; the fused call chains them.  A tail (ExtractTail below) may follow the descriptors on the same
+// stream and add its outputs to the one download: the stereo match of osh_orb_extract_stereo (stereo_device.hip).
 #pragma once
 #include "common.h"
 #include "orb_pyramid_set.h"
@@ -38,8 +39,34 @@ struct Level0Producer {
 int pyramid_build_from(osh_orb_ctx* c, int32_t n_frames, const osh_pyramid_frame* frames, osh_pyramid_result* results, const Level0Producer* producer);
 
 // ---- orb_extract_device.hip
-// osh_orb_extract with the pyramid built by pyramid_build_from(.., producer)
-int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results, const Level0Producer* producer);
+// What a tail of the fused call sees once the descriptors are launched: the kept keypoints of the call on the device, frame k's at
+// [frame_kp0[k], frame_kp0[k] + frame_n[k]) in level-then-list order, and the level tables of the call
+struct ExtractKept {
+  size_t K;                               // keypoints of the call
+  const float2* xy;                       // device [K] in the pixels of their level
+  const int* level_index;                 // device [K] the keypoint's entry of e->levels
+  const unsigned long long* desc;         // device [K * 4], 256-byte aligned: the 32 bytes of keypoint i at desc + 4 i
+  const unsigned char* images;            // device: first byte of the resident pyramid
+};
+// A stage that runs after brief_launch and before the one download of extract_from (the stereo match of osh_orb_extract_stereo).
+// With no tail the call launches and downloads what it did without the hook.
+struct ExtractTail {
+  // The frames in the order their keypoints are laid out on the device (a permutation of 0 .. n_frames - 1)
+  std::vector<int> order;
+  // On the host, the counts known: the tail's sections of the call's three layouts (`out` comes down with the results)
+  std::function<int(const FastEmitted& e, const std::vector<size_t>& frame_kp0, const std::vector<size_t>& frame_n, Layout& in, Layout& out, Layout& work)> plan;
+  std::function<void(char* host_in)> stage;   // its inputs into the staging buffer
+  std::function<int(hipStream_t s, char* dev_in, char* dev_out, char* dev_work, const ExtractKept& kept)> launch;
+  std::function<void(const char* host_out)> collect;   // after the download; not called when the call kept no keypoint
+};
+// osh_orb_extract with the pyramid built by pyramid_build_from(.., producer) and an optional tail
+int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results, const Level0Producer* producer,
+                 const ExtractTail* tail = nullptr);
+
+// ---- orb_prepare_device.hip
+// The body of osh_orb_extract_raw: extract_from with the device producer of level 0, then the prepared images (prepare_results may be NULL)
+int extract_raw_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_prepare_frame* prepare_frames, const osh_extract_frame* extract_frames,
+                     osh_extract_result* extract_results, osh_prepare_result* prepare_results, const ExtractTail* tail);
 
 // ---- orb_octree_device.hip
 struct OctListDev {

@@ -9,6 +9,9 @@
 //   k_extract_gather               one wavefront per list: the kept candidates in level-then-list order with minBorder added (:880-890);
 //   ic_angle_launch, brief_launch  k_ic_angle, k_orb_blur on the levels that hold a keypoint, k_orb_brief, all reading the gathered keypoints.
 // Uploads besides the image: the plans of the stages (cells, lists, levels, tiles, tables).  One download at the end.
+// A caller of extract_from may hang a tail behind brief_launch (ExtractTail of orb_extract.h): it chooses the order in which the frames'
+// keypoints are laid out, adds its sections to the call's three layouts, launches on the same stream and reads its outputs from the
+// same download.  osh_orb_extract_stereo (stereo_device.hip) does, with the stereo match; without a tail nothing changes.
 // extract_from (orb_extract.h) is the body; osh_orb_extract_raw (orb_prepare_device.hip) calls it with a device producer of level 0.
 #include "common.h"
 #include "orb_brief.h"
@@ -39,6 +42,7 @@ __global__ __launch_bounds__(64) void k_extract_gather(const GatherDev* lists, c
 struct ExtractState {
   StagedCall call;   // [lists | levels | blur plan | tiles | tables] in, [xy | response | angle | descriptors] out, the rest as work
   double ms[4] = {0, 0, 0, 0};
+  double ms_tail[5] = {0, 0, 0, 0, 0};   // of the last call with a tail: the four phases without the tail, then the tail
 };
 
 // What the call checks itself; the image, n_levels and inv_scale are osh_orb_pyramid_build's to refuse
@@ -68,10 +72,12 @@ static int extract_validate(int k, const osh_extract_frame& f, const osh_extract
 }
 
 // The body of osh_orb_extract and osh_orb_extract_raw (orb_prepare_device.hip): they differ in where level 0 comes from
-int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results, const Level0Producer* producer) {
+int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results, const Level0Producer* producer,
+                 const ExtractTail* tail) {
   PhaseClock clock;
   if (n_frames < 0 || (n_frames && (!frames || !results))) { set_error("%s: bad arguments", entry); return OSH_ERR_INVALID; }
   for (int k = 0; k < n_frames; ++k) OSH_TRY(extract_validate(k, frames[k], results[k]));   // a refusal needs no context and no device
+  if (tail && tail->order.size() != (size_t)n_frames) { set_error("%s: the tail orders %zu frames of %d", entry, tail->order.size(), n_frames); return OSH_ERR_INVALID; }
   // the pyramid: exactly an osh_orb_pyramid_build, which refuses what it refuses before it touches the resident pyramid
   std::vector<osh_pyramid_frame> pf((size_t)n_frames);
   std::vector<osh_pyramid_result> pr((size_t)n_frames);
@@ -111,18 +117,25 @@ int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_
   const int* d_kept = nullptr;
   if (!lists.empty()) OSH_TRY(octree_run(c, s, lists, e.xy, e.response, count, status, &d_kept));
   std::vector<int> level_count(e.levels.size(), 0);
-  std::vector<size_t> frame_kp0((size_t)n_frames + 1, 0);
-  size_t K = 0, at = 0;
-  for (int k = 0; k < n_frames; ++k) {
+  // frame k's keypoints are [frame_kp0[k], frame_kp0[k] + frame_n[k]): frame after frame, or in the order a tail asks for
+  std::vector<size_t> frame_kp0((size_t)n_frames, 0), frame_n((size_t)n_frames, 0), frame_list0((size_t)n_frames + 1, 0);
+  for (size_t at = 0, k = 0; k <= (size_t)n_frames; ++k) {
+    frame_list0[k] = at;
+    for (; k < (size_t)n_frames && at < gather.size() && gather[at].frame == (int)k; ++at) {
+      if (status[at] != OSH_OK) { set_error("%s: frame %d: an octree list reached a loop bound", entry, (int)k); return status[at]; }
+      frame_n[k] += (size_t)count[at];
+    }
+  }
+  size_t K = 0;
+  for (int j = 0; j < n_frames; ++j) {
+    const int k = tail ? tail->order[j] : j;
     frame_kp0[k] = K;
-    for (; at < gather.size() && gather[at].frame == k; ++at) {
-      if (status[at] != OSH_OK) { set_error("%s: frame %d: an octree list reached a loop bound", entry, k); return status[at]; }
+    for (size_t at = frame_list0[k]; at < frame_list0[k + 1]; ++at) {
       gather[at].out0 = lists[at].out0; gather[at].n = count[at]; gather[at].kp0 = (int)K;
       level_count[gather[at].level_index] = count[at];
       K += (size_t)count[at];
     }
   }
-  frame_kp0[n_frames] = K;
   clock.mark();
 
   // orientation, blur and descriptors of the kept keypoints
@@ -146,7 +159,9 @@ int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_
   const auto o_desc = out.take<unsigned long long>(K * 4);
   const auto w_index = work.take<int>(K); const auto w_frame = work.take<int>(K);
   const auto w_m10 = work.take<int>(K); const auto w_m01 = work.take<int>(K); const auto w_cs = work.take<float2>(K);
+  double tail_ms = 0;
   if (K) {
+    if (tail) OSH_TRY(tail->plan(e, frame_kp0, frame_n, in, out, work));   // after the call's own sections: those stay where they are
     OSH_TRY(st->call.reserve(in, out, work.bytes));
     unsigned char* blurred = brief_blurred(c, blur_bytes);
     if (!blurred) return OSH_ERR_DEVICE;
@@ -162,6 +177,7 @@ int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_
       std::memcpy(s_pattern.in(h) + (size_t)k * 2 * kBriefPoints, frames[k].pattern, 2 * kBriefPoints);
     }
     if (!tiles.empty()) std::memcpy(s_tiles.in(h), tiles.data(), sizeof(BlurTileDev) * tiles.size());
+    if (tail) tail->stage(h);
     OSH_TRY(st->call.upload(s));
     char* di = st->call.dev_in(); char* dout = st->call.dev_out(); char* dw = st->call.dev_work();
     hipLaunchKernelGGL(k_extract_gather, dim3((unsigned)gather.size()), dim3(64), 0, s, s_gather.in(di), e.xy, e.response, d_kept, o_xy.in(dout), o_resp.in(dout),
@@ -172,13 +188,20 @@ int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_
     v.n = (int)K; v.levels = s_blurred.in(di); v.level_index = w_index.in(dw); v.frame = w_frame.in(dw); v.xy = o_xy.in(dout);
     v.angle = o_angle.in(dout); v.pattern = s_pattern.in(di); v.desc = o_desc.in(dout); v.cos_sin = w_cs.in(dw);
     OSH_TRY(brief_launch(s, tiles.size(), s_blur.in(di), s_tiles.in(di), v));
+    if (tail) {
+      if (clock.profiling) OSH_HIP(hipStreamSynchronize(s));
+      const PhaseClock::clk::time_point t0 = PhaseClock::clk::now();
+      OSH_TRY(tail->launch(s, di, dout, dw, ExtractKept{K, o_xy.in(dout), w_index.in(dw), o_desc.in(dout), e.images}));
+      if (clock.profiling) OSH_HIP(hipStreamSynchronize(s));
+      tail_ms = std::chrono::duration<double, std::milli>(PhaseClock::clk::now() - t0).count();
+    }
     OSH_TRY(st->call.download(s));   // synchronises
   }
   const char* ho = st->call.host_out();
   for (int k = 0; k < n_frames; ++k) {
     osh_extract_result& r = results[k];
     const osh_extract_frame& f = frames[k];
-    const size_t base = frame_kp0[k], n = frame_kp0[k + 1] - base;
+    const size_t base = frame_kp0[k], n = frame_n[k];
     r.n_out = (int32_t)n; r.pyramid_token = pr[k].pyramid_token;
     for (int l = 0; l < f.n_levels; ++l) r.level_count[l] = level_count[e.level0[k] + l];
     if (n > (size_t)r.capacity) continue;   // counts only: the caller sizes its arrays and calls again
@@ -190,8 +213,13 @@ int extract_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_
       for (int j = 0; j < r.level_count[l]; ++j, ++i) { r.level[i] = l; r.size[i] = diameter; }
     }
   }
+  if (tail && K) tail->collect(ho);
   clock.mark();
   clock.store(st->ms);
+  if (tail && clock.profiling) {
+    for (int k = 0; k < 4; ++k) st->ms_tail[k] = st->ms[k];
+    st->ms_tail[3] -= tail_ms; st->ms_tail[4] = tail_ms;
+  }
   return OSH_OK;
 }
 
@@ -201,6 +229,12 @@ using namespace osh;
 
 extern "C" int osh_orb_extract(osh_orb_ctx* c, int32_t n_frames, const osh_extract_frame* frames, osh_extract_result* results) {
   return extract_from("osh_orb_extract", c, n_frames, frames, results, nullptr);
+}
+
+extern "C" int osh_orb_extract_stereo_get_times(osh_orb_ctx* c, double ms[5]) {
+  if (!c || !ms) { set_error("osh_orb_extract_stereo_get_times: bad arguments"); return OSH_ERR_INVALID; }
+  std::memcpy(ms, orb_state<ExtractState>(c, kOrbAttachExtract)->ms_tail, sizeof(double) * 5);
+  return OSH_OK;
 }
 
 extern "C" int osh_orb_extract_get_times(osh_orb_ctx* c, double ms[4]) {

@@ -306,9 +306,10 @@ extern "C" int osh_orb_prepare(osh_orb_ctx* c, int32_t n_frames, const osh_prepa
   return OSH_OK;
 }
 
-extern "C" int osh_orb_extract_raw(osh_orb_ctx* c, int32_t n_frames, const osh_prepare_frame* prepare_frames, const osh_extract_frame* extract_frames,
-                                   osh_extract_result* extract_results, osh_prepare_result* prepare_results) {
-  const char* entry = "osh_orb_extract_raw";
+namespace osh {
+
+int extract_raw_from(const char* entry, osh_orb_ctx* c, int32_t n_frames, const osh_prepare_frame* prepare_frames, const osh_extract_frame* extract_frames,
+                     osh_extract_result* extract_results, osh_prepare_result* prepare_results, const ExtractTail* tail) {
   if (n_frames < 0 || (n_frames && (!prepare_frames || !extract_frames || !extract_results))) { set_error("%s: bad arguments", entry); return OSH_ERR_INVALID; }
   PrepPlan P;
   OSH_TRY(prepare_plan(entry, n_frames, prepare_frames, prepare_results, P));   // a refusal needs no context and no device
@@ -330,7 +331,7 @@ extern "C" int osh_orb_extract_raw(osh_orb_ctx* c, int32_t n_frames, const osh_p
     st = orb_state<PrepState>(c, kOrbAttachPrepare);
     return prepare_produce(entry, st, s, n_frames, prepare_frames, P, images, level0_off.data(), nullptr);
   };
-  OSH_TRY(extract_from(entry, c, n_frames, ef.data(), extract_results, &producer));
+  OSH_TRY(extract_from(entry, c, n_frames, ef.data(), extract_results, &producer, tail));
   if (n_frames == 0 || !prepare_results) return OSH_OK;
   // the prepared images are the level 0 of the frames: they lie one after another at the start of the resident pyramid
   int device = 0;
@@ -340,6 +341,13 @@ extern "C" int osh_orb_extract_raw(osh_orb_ctx* c, int32_t n_frames, const osh_p
   std::vector<long long> off((size_t)n_frames);
   for (int k = 0; k < n_frames; ++k) off[k] = rp.levels[rp.frames[k].level0].img_off;
   return prepare_collect(entry, st, s, n_frames, P, rp.images(), P.out_bytes, off.data(), prepare_results);
+}
+
+}  // namespace osh
+
+extern "C" int osh_orb_extract_raw(osh_orb_ctx* c, int32_t n_frames, const osh_prepare_frame* prepare_frames, const osh_extract_frame* extract_frames,
+                                   osh_extract_result* extract_results, osh_prepare_result* prepare_results) {
+  return extract_raw_from("osh_orb_extract_raw", c, n_frames, prepare_frames, extract_frames, extract_results, prepare_results, nullptr);
 }
 
 extern "C" int osh_orb_prepare_get_times(osh_orb_ctx* c, double ms[4]) {

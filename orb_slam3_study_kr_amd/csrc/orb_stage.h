@@ -2,6 +2,8 @@
 // share: both take a batch of frames with left and right ORB keypoints (xy, octave, 32-byte descriptor per keypoint), lay the frames'
 // keypoints one after another in six arrays, run on an osh_orb_ctx attachment and time the same four host-clock phases.  Kernels,
 // views, device frame descriptors, outputs and whatever a validator checks beyond the checks below stay with their entry.
+// osh_orb_stereo_match_resident and the stereo tail of osh_orb_extract_stereo (stereo_device.hip) are the rectified matcher on
+// resident pyramids: stereo_frame.h holds what the three rectified entries share beyond this file.
 // osh_kb8_triangulate is not a client: it stages four flat arrays and no frames through a StagedCall of its own.
 // osh_orb_bow_transform (bow_device.hip) has frames of descriptors only: it uses scatter, PhaseClock, orb_state and copy_times.
 // osh_orb_bow_db_query (bowdb_device.hip) has queries against a database: it uses PhaseClock, orb_state and copy_times.

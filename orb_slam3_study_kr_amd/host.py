@@ -1714,6 +1714,31 @@ def orbextractor_extract_batch(images, lappings, nfeatures=1000, scale_factor=1.
     return res
 
 
+def _fill_host_raw_image(r, it, keep: list) -> tuple:
+    """A capi.HostRawImage from an item dict(image, optionally order, map_x / map_y, out_shape); the arrays its pointers refer to are
+    added to `keep`.  Returns the (rows, cols) of the prepared image."""
+    img = None if it.get("image") is None else np.ascontiguousarray(it["image"], np.uint8)
+    r.rgb = int(it.get("order", "rgb") == "rgb")
+    shape = (0, 0)
+    if img is not None and img.size:
+        r.rows, r.cols, r.channels = img.shape[0], img.shape[1], 1 if img.ndim == 2 else img.shape[2]
+        r.pixels = capi.ptr(img, capi.c_uint8_p)
+        shape = img.shape[:2]
+    else:
+        r.channels = 1
+    if it.get("map_x") is not None:
+        mx, my = np.ascontiguousarray(it["map_x"], np.float32), np.ascontiguousarray(it["map_y"], np.float32)
+        r.map_rows, r.map_cols = mx.shape
+        r.map_x, r.map_y = capi.ptr(mx, capi.c_float_p), capi.ptr(my, capi.c_float_p)
+        keep.append((mx, my))
+        shape = mx.shape
+    if it.get("out_shape") is not None:
+        r.new_rows, r.new_cols = int(it["out_shape"][0]), int(it["out_shape"][1])
+        shape = (max(r.new_rows, 0), max(r.new_cols, 0))
+    keep.append(img)
+    return tuple(shape)
+
+
 def orbextractor_extract_batch_raw(items, lappings, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, keep_pyramid=True,
                                    want_gray=True) -> list:
     """ORBextractor::ExtractBatchRaw of one stand-in extractor per item dict(image uint8 [rows, cols] or [rows, cols, 3 | 4] (None: an
@@ -1728,27 +1753,7 @@ def orbextractor_extract_batch_raw(items, lappings, nfeatures=1000, scale_factor
     keep, shapes = [], []
     for i, it in enumerate(items):
         orb.fill_host_extract_input(cin[i], None, nfeatures, scale_factor, nlevels, ini_th, min_th, lappings[i])
-        img = None if it.get("image") is None else np.ascontiguousarray(it["image"], np.uint8)
-        r = raw[i]
-        r.rgb = int(it.get("order", "rgb") == "rgb")
-        shape = (0, 0)
-        if img is not None and img.size:
-            r.rows, r.cols, r.channels = img.shape[0], img.shape[1], 1 if img.ndim == 2 else img.shape[2]
-            r.pixels = capi.ptr(img, capi.c_uint8_p)
-            shape = img.shape[:2]
-        else:
-            r.channels = 1
-        if it.get("map_x") is not None:
-            mx, my = np.ascontiguousarray(it["map_x"], np.float32), np.ascontiguousarray(it["map_y"], np.float32)
-            r.map_rows, r.map_cols = mx.shape
-            r.map_x, r.map_y = capi.ptr(mx, capi.c_float_p), capi.ptr(my, capi.c_float_p)
-            keep.append((mx, my))
-            shape = mx.shape
-        if it.get("out_shape") is not None:
-            r.new_rows, r.new_cols = int(it["out_shape"][0]), int(it["out_shape"][1])
-            shape = (max(r.new_rows, 0), max(r.new_cols, 0))
-        keep.append(img)
-        shapes.append(shape)
+        shapes.append(_fill_host_raw_image(raw[i], it, keep))
     cap = [2 * int(nfeatures) + 300 * int(nlevels)] * n
     pix = [int((s[0] + 2) * (s[1] + 2) * nlevels) if s[0] * s[1] else 1 for s in shapes]
     outs, cout = [], (capi.HostExtractOutput * max(n, 1))()
@@ -1781,3 +1786,63 @@ def orbextractor_extract_batch_raw(items, lappings, nfeatures=1000, scale_factor
             d["gray"] = grays[i][:gr * gc].reshape(gr, gc) if gr > 0 and gr * gc <= grays[i].size else None
         res.append(d)
     return res
+
+
+def frame_extract_and_match_stereo(left, right, bf, b, raw=False, chain=False, want_gray=False, nfeatures=1000, scale_factor=1.2, nlevels=8,
+                                   ini_th=20, min_th=7) -> dict:
+    """Frame::ExtractAndMatchStereo of a stand-in Frame with two stand-in extractors through osh_host_frame_extract_and_match_stereo.
+    left / right: uint8 images (None: an empty image), or with `raw` the items of orbextractor_extract_batch_raw.  chain: the two
+    calls the member replaces instead, ExtractBatch(Raw) with bKeepPyramid and ComputeStereoMatches.  A dict with left / right (the
+    dicts of orbextractor_extract_batch for mvKeys / mDescriptors and mvKeysRight / mDescriptorsRight), N, u_right, depth (mvuRight
+    and mvDepth), n_right and call_ms, the wall time of the member calls alone; with want_gray the sides also carry gray."""
+    from . import orb
+    lib = capi.load_host_library()
+    cin = (capi.HostExtractInput * 2)()
+    rawc = (capi.HostRawImage * 2)()
+    keep, shapes = [], []
+    for i, side in enumerate((left, right)):
+        if raw:
+            orb.fill_host_extract_input(cin[i], None, nfeatures, scale_factor, nlevels, ini_th, min_th)
+            shapes.append(_fill_host_raw_image(rawc[i], side, keep))
+        else:
+            img = orb.fill_host_extract_input(cin[i], side, nfeatures, scale_factor, nlevels, ini_th, min_th)
+            keep.append(img)
+            shapes.append(img.shape if img.size else (0, 0))
+    cap = 2 * int(nfeatures) + 300 * int(nlevels)
+    outs, cout = [], (capi.HostExtractOutput * 2)()
+    for i in range(2):
+        pix = int((shapes[i][0] + 2) * (shapes[i][1] + 2) * nlevels) if shapes[i][0] * shapes[i][1] else 1
+        o = dict(level_rows=np.zeros(nlevels, np.int32), level_cols=np.zeros(nlevels, np.int32), pyramid=np.zeros(pix, np.uint8),
+                 xy=np.zeros((cap, 2), np.float32), angle=np.zeros(cap, np.float32), size=np.zeros(cap, np.float32),
+                 response=np.zeros(cap, np.float32), octave=np.zeros(cap, np.int32), descriptors=np.zeros((cap, 32), np.uint8),
+                 ret=np.zeros(1, np.int32), desc_rows=np.zeros(1, np.int32), pixels_needed=np.zeros(1, np.int32))
+        cout[i].capacity, cout[i].pixel_capacity = cap, pix
+        orb._wire_outputs(cout[i], o)
+        outs.append(o)
+    tokens = (C.c_uint64 * 2)()
+    u_right, depth = np.full(cap, 5, np.float32), np.full(cap, 5, np.float32)
+    counts = np.full(4, -1, np.int32)
+    grays = [np.full(max(s[0] * s[1], 1), 167, np.uint8) for s in shapes]
+    gptr = (capi.c_uint8_p * 2)(*[capi.ptr(g, capi.c_uint8_p) for g in grays])
+    gcap = np.asarray([g.size for g in grays], np.int32)
+    grows, gcols = np.full(2, -1, np.int32), np.full(2, -1, np.int32)
+    ms = C.c_double(0)
+    rc = lib.osh_host_frame_extract_and_match_stereo(cin, rawc if raw else None, float(bf), float(b), int(bool(chain)), cout, tokens, cap,
+                                                     capi.ptr(u_right, capi.c_float_p), capi.ptr(depth, capi.c_float_p), capi.ptr(counts, capi.c_int32_p),
+                                                     gptr if want_gray else None, capi.ptr(gcap, capi.c_int32_p), capi.ptr(grows, capi.c_int32_p),
+                                                     capi.ptr(gcols, capi.c_int32_p), C.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"osh_host_frame_extract_and_match_stereo returned {rc}")
+    sides = []
+    for i, o in enumerate(outs):
+        k = int(o["desc_rows"][0])
+        d = dict(desc_rows=k, token=int(tokens[i]))
+        for name in ("xy", "angle", "size", "response", "octave", "descriptors"):
+            d[name] = o[name][:k]
+        d["pyramid"] = orb.cut_levels(o["pyramid"], zip(o["level_rows"].tolist(), o["level_cols"].tolist()))
+        if want_gray:
+            gr, gc = int(grows[i]), int(gcols[i])
+            d["gray"] = grays[i][:gr * gc].reshape(gr, gc) if gr > 0 and gr * gc <= grays[i].size else None
+        sides.append(d)
+    return dict(left=sides[0], right=sides[1], N=int(counts[0]), u_right=u_right[:max(int(counts[1]), 0)], depth=depth[:max(int(counts[2]), 0)],
+                n_right=int(counts[3]), call_ms=float(ms.value))

@@ -148,6 +148,37 @@ class OrbMatcher:
         capi.check(self.lib.osh_orb_stereo_match(self.ctx, len(frames), cf, cr), "osh_orb_stereo_match", self.lib)
         return outs
 
+    def stereo_match_resident(self, frames, tokens, stages: bool = False) -> list:
+        """stereo_match on pyramids that are resident on this matcher's context, in one osh_orb_stereo_match_resident call: frames
+        bring keypoints, scale factors, bf and b (their pyramids are not read), tokens[k] = (left_token, right_token) from
+        pyramid_build, extract or extract_raw.  The per-frame dicts are stereo_match's."""
+        cf, cr, _keep, outs = stereo_resident_args(frames, tokens, stages)
+        capi.check(self.lib.osh_orb_stereo_match_resident(self.ctx, len(frames), cf, cr), "osh_orb_stereo_match_resident", self.lib)
+        return outs
+
+    def set_stereo_row_search(self, enable: bool):
+        """The descriptor search of stereo_match_resident and extract_stereo: the row lists (default) or k_stereo_hamming."""
+        capi.check(self.lib.osh_orb_stereo_set_row_search(self.ctx, int(bool(enable))), "osh_orb_stereo_set_row_search", self.lib)
+
+    def extract_stereo(self, pairs, capacities=None, download: bool = False, stages: bool = False, raw: bool = False) -> list:
+        """A rectified stereo frame per pair in ONE osh_orb_extract_stereo call: pairs are dict(left, right, bf, b), left / right
+        items of extract() (of extract_raw() with `raw`).  Per pair a dict with left / right (the dicts of extract()) and stereo (the
+        dict of stereo_match for the left keypoints in extract order, level-0 scaled on the device; None when a frame's arrays
+        were too small).  capacities: the room of the 2 n frames, left then right; None: a first call with no room sizes them."""
+        if capacities is None:
+            sized = self.extract_stereo(pairs, [0] * (2 * len(pairs)), raw=raw)
+            capacities = [r[side]["n_out"] for r in sized for side in ("left", "right")]
+        pf, cf, cp, cr, cs, _keep, outs, souts = extract_stereo_args(pairs, capacities, download, stages, raw)
+        capi.check(self.lib.osh_orb_extract_stereo(self.ctx, len(pairs), pf, cf, cp, cr, cs), "osh_orb_extract_stereo", self.lib)
+        return _extract_stereo_outputs(cr, outs, souts)
+
+    def extract_stereo_times(self):
+        """Host-clock times (ms) of the last extract_stereo under set_profiling(True): the four phases of extract_times without
+        the stereo tail, then the stereo tail."""
+        ms = np.zeros(5, dtype=np.float64)
+        capi.check(self.lib.osh_orb_extract_stereo_get_times(self.ctx, capi.ptr(ms, capi.c_double_p)), "osh_orb_extract_stereo_get_times", self.lib)
+        return ms
+
     def _times(self, symbol):
         """Host-clock phases (ms) of an entry's last call under set_profiling(True): staging, upload, kernels, download."""
         ms = np.zeros(4, dtype=np.float64)
@@ -644,6 +675,68 @@ def stereo_args(frames, stages: bool = False, borders=None):
         keep.append((a, pyr))
         outs.append(o)
     return cf, cr, keep, outs
+
+
+def _stereo_result(res, n, stages: bool) -> dict:
+    """The output arrays of an osh_stereo_result for n left keypoints, wired into `res`."""
+    o = dict(u_right=np.zeros(n, np.float32), depth=np.zeros(n, np.float32))
+    if stages:
+        o.update(best_right=np.zeros(n, np.int32), hamming=np.zeros(n, np.int32), sad=np.zeros((n, 11), np.int32),
+                 best_inc=np.zeros(n, np.int32), stage=np.zeros(n, np.uint8))
+    _wire_outputs(res, o)
+    return o
+
+
+def stereo_resident_args(frames, tokens, stages: bool = False):
+    """The osh_stereo_resident_frame / osh_stereo_result arrays of OrbMatcher.stereo_match_resident: stereo_args without the
+    pyramids, tokens[k] = (left_token, right_token) in their place."""
+    n_frames = len(frames)
+    cf = (capi.StereoResidentFrame * max(n_frames, 1))()
+    cr = (capi.StereoResult * max(n_frames, 1))()
+    keep, outs = [], []
+    for k, fr in enumerate(frames):
+        f = cf[k]
+        a = _fill_keypoints(f, fr)
+        a.update(sf=np.ascontiguousarray(fr.scale_factors, np.float32), isf=np.ascontiguousarray(fr.inv_scale_factors, np.float32))
+        f.n_levels = fr.n_levels
+        f.scale_factors, f.inv_scale_factors = capi.ptr(a["sf"], capi.c_float_p), capi.ptr(a["isf"], capi.c_float_p)
+        f.left_token, f.right_token = int(tokens[k][0]), int(tokens[k][1])
+        f.bf, f.b = fr.bf, fr.b
+        keep.append(a)
+        outs.append(_stereo_result(cr[k], f.n_left, stages))
+    return cf, cr, keep, outs
+
+
+def extract_stereo_args(pairs, capacities, download: bool = False, stages: bool = False, raw: bool = False):
+    """The arrays of OrbMatcher.extract_stereo for pairs dict(left, right, bf, b) (left / right: items of extract, or of extract_raw
+    with `raw`) and the capacities of the 2 n frames: (prepare frames or None, extract frames, pairs, extract results, stereo
+    results, keep-alive, per-frame extract outputs, per-pair stereo outputs)."""
+    items = [it for p in pairs for it in (p["left"], p["right"])]
+    pf, pkeep = None, None
+    if raw:
+        pf, _pr, _maps, pkeep, _pouts = prepare_args(items, False)
+        cf, cr, keep, outs = extract_raw_args(items, capacities, download)
+    else:
+        cf, cr, keep, outs = extract_args(items, capacities, download)
+    cp = (capi.StereoPair * max(len(pairs), 1))()
+    cs = (capi.StereoResult * max(len(pairs), 1))()
+    souts = []
+    for p, pair in enumerate(pairs):
+        cp[p].bf, cp[p].b = float(pair["bf"]), float(pair["b"])
+        souts.append(_stereo_result(cs[p], int(capacities[2 * p]), stages))
+    return pf, cf, cp, cr, cs, (keep, pkeep, _maps if raw else None), outs, souts
+
+
+def _extract_stereo_outputs(cr, outs, souts):
+    """Per pair: left / right as _extract_outputs gives them, and stereo: the arrays cut to the left count, None when either frame
+    did not fit (stereo_arrays: the arrays as they were handed over)."""
+    ex = _extract_outputs(cr, outs)
+    res = []
+    for p, so in enumerate(souts):
+        left, right = ex[2 * p], ex[2 * p + 1]
+        fits = left["xy"] is not None and right["xy"] is not None
+        res.append(dict(left=left, right=right, stereo={name: v[:left["n_out"]] for name, v in so.items()} if fits else None, stereo_arrays=so))
+    return res
 
 
 def fast_level_cells(rows, cols, host_lib=None):
